@@ -8,10 +8,12 @@ the timed region.
 
 Inner solve (--pc): "lu" (default, the reference's own setting, .examples/eigenvalues.py:100) = exact nested-dissection
 multifrontal LU on the device, every solve verified against b - C x and wrapped in GMRES; "ilu" = ILU(k)-preconditioned
-GMRES with the blocked SpTRSV (the north-star variant).  The headline `value` is the --pc run; the other variant is timed once and
-reported under config.other_pc so both numbers are always on the line.
+GMRES with the blocked SpTRSV (the north-star variant).  The headline `value` is the --pc run; with --full the other variant is
+timed once and reported under config.other_pc.
 
-    python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1                  # the headline only
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full           # + every secondary figure below
+    python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 N > 1 (one rank per GPU): `value` is the SAME workload as at N = 1 -- every rank solves the S30k problem on its own GPU, no
@@ -23,7 +25,7 @@ process group of its own; the children cut the nested-dissection forest of C = A
 in-place all-gather of the subtree roots' update matrices, replicated top; Krylov bases replicated; an operator apply = the
 exact solve of the one-GPU path with two all-gathers), solve once with one Arnoldi step per read-back and once with the
 batched steps and compare the eigenvalues, time the steps, and time the same problem on ONE GPU beside it
-(`one_gpu_same_workload_eigenpairs_per_s`).  The children run under a time limit (`--sharded-timeout`): the multi-rank RCCL
+(`one_gpu_same_workload_eigenpairs_per_s`, with --full).  The children run under a time limit (`--sharded-timeout`): the multi-rank RCCL
 exchange has never run on hardware available to the build, and a fault or hang there must cost `config.sharded`, not the
 bench line.  `--layout sharded` makes the sharded run the headline instead (strong scaling, S500k).  Rehearsal on one GPU:
 tools/rehearse_two_ranks.sh (LSA_BENCH_DEVICE=0 LSA_BENCH_BACKEND=gloo: all ranks on device 0, host-staged all-gather).
@@ -32,6 +34,12 @@ Set-up (untimed): assembly, prepare() (ordering, upload, pattern analysis) and t
 of kernel loading and of the runtime); then W warm-up steps, then K timed steps between barriers.  What the
 set-up costs is on the line: `config.prepare_ms`, `config.analysis_ms`, `config.cold_first_solve_ms` (prepare + the process's
 first solve: what a caller with ONE eigenproblem pays), `config.setup_solves`.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the result line.  Everything else is measured
+with --full only: config.other_pc, the solves in flight, config.lu_apply (and config.analysis_ms), config.sptrsv_roofline,
+config.pattern_3d, `roofline`, `cpu_baseline`, and at N > 1 config.sharded_3d and config.replicas of the sharded layout.
+--dump-outputs DIR writes what the last timed step returned (rank 0): eigenvalues.npy (k, 2) and eigenvectors.npy (k, n, 2),
+float64 with a trailing (re, im) axis; the inputs are deterministic, so two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line.  `roofline` is measured on the SpMV kernel (the kernel the metric names) on SROOF, a
 ~1.5e8-nnz CSR with the cylinder-flow row pattern that does not fit the 256 MB Infinity Cache; `cpu_baseline` is the
@@ -411,6 +419,29 @@ def roofline_3d(args, device):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, pairs) -> None:
+    """--dump-outputs: what the last timed step returned to its caller, as float64 arrays with a trailing (re, im) axis --
+    eigenvalues.npy (k, 2) and eigenvectors.npy (k, n, 2), in the order solve() returned them.  Above 64 MB the
+    eigenvectors keep a fixed sample of rows (seed 0, sorted), listed in eigenvector_rows.npy."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    lam = np.array([p[0] for p in pairs], dtype=np.complex128)
+    vec = np.array([p[1].as_array() for p in pairs], dtype=np.complex128).reshape(len(pairs), -1) if pairs else np.zeros((0, 0), np.complex128)
+    split = lambda z: np.stack([z.real, z.imag], axis=-1).astype(np.float64)  # noqa: E731
+    np.save(out_dir / "eigenvalues.npy", split(lam))
+    k, n = vec.shape
+    # (1 MB held back for the eigenvalues and the .npy headers; + 8 bytes per row for the sampled row's index)
+    rows_max = (DUMP_BUDGET_BYTES - (1 << 20)) // (16 * k + 8)
+    if n > rows_max:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=rows_max, replace=False))
+        vec = vec[:, rows]
+        np.save(out_dir / "eigenvector_rows.npy", rows.astype(np.float64))
+    np.save(out_dir / "eigenvectors.npy", split(vec))
+    log(f"outputs of the last timed step written to {out_dir}: {k} eigenvalues, eigenvectors {vec.shape[1]} of {n} rows")
+
+
 def run_sharded_children(args, rank: int, world: int, local_rank: int, case: str | None = None, k: int | None = None, ncv: int | None = None,
                          timeout: float | None = None, port_offset: int = 37, steps: int | None = None):
     """config.sharded at N > 1: every rank starts ONE child process (this file with --sharded-child) that joins a process
@@ -428,7 +459,7 @@ def run_sharded_children(args, rank: int, world: int, local_rank: int, case: str
     limit = args.sharded_timeout if timeout is None else timeout
     cmd = [sys.executable, str(ROOT / "bench.py"), "--sharded-child", "--gpus", str(world), "--steps", str(args.steps if steps is None else steps),
            "--warmup", str(args.warmup), "--case", case, "--k", str(k or args.k), "--ncv", str(ncv or args.ncv), "--atol", str(args.atol), "--no-roofline",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline"] + (["--full"] if args.full else [])
     t0 = time.perf_counter()
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     try:
@@ -482,8 +513,16 @@ def main() -> None:
     ap.add_argument("--roof-iters", type=int, default=50)
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the other inner-solver variant, solves in flight, LU apply and "
+                         "SpTRSV rooflines, the 3D pattern, the SpMV roofline, the CPU baseline (N > 1: the 3D sharded leg and the replicas "
+                         "figure). Off: set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (eigenvalues, eigenvectors) to DIR/<name>.npy as float64")
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)  # child process of the cpu_baseline leg
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_worker:
         args.case = args.case or "S30k"
         _cpu_worker(args)
@@ -611,10 +650,12 @@ def main() -> None:
     t0 = time.perf_counter()
     step_marks = [t0]
     for _ in range(args.steps):
-        solver.solve()
+        last_pairs = solver.solve()
         step_marks.append(time.perf_counter())
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), last_pairs)
     log("seconds per step: " + " ".join(f"{b - a:.3f}" for a, b in zip(step_marks[:-1], step_marks[1:]))
         + f"; last solve: factor {solver.solver.stats.get('seconds_factor', 0.0):.3f} s, Arnoldi {solver.solver.stats.get('seconds_solve', 0.0):.3f} s")
     # count pairs that pass the true residual test (device evaluation, after the timed region)
@@ -637,13 +678,13 @@ def main() -> None:
         barrier()  # every parent has released its solver: the children find the GPUs free
         sharded_rec = run_sharded_children(args, rank, world, local_rank)
         barrier()
-        if args.sharded_3d_case and args.sharded_3d_timeout > 0:
+        if args.full and args.sharded_3d_case and args.sharded_3d_timeout > 0:
             # BASELINE config 4's discretisation over the ranks, top fronts of the forest distributed: informative only
             sharded_3d = run_sharded_children(args, rank, world, local_rank, case=args.sharded_3d_case, k=10, ncv=40, timeout=args.sharded_3d_timeout,
                                               port_offset=53, steps=min(args.steps, 3))
             barrier()
     replicas = None
-    if sharded and not args.no_other_pc:
+    if args.full and sharded and not args.no_other_pc:
         # secondary figure: the same N GPUs as N independent solves of the N = 1 workload (no data-path collective)
         try:
             so = build_solver(es, sigma, args, device, args.pc)
@@ -665,7 +706,7 @@ def main() -> None:
         except Exception as exc:  # noqa: BLE001  (every rank takes the same path: the collectives above stay matched)
             replicas = {"error": f"{type(exc).__name__}: {exc}"}
     other = None
-    if rank == 0 and not args.no_other_pc and world == 1 and not args.sharded_child:
+    if args.full and rank == 0 and not args.no_other_pc and world == 1 and not args.sharded_child:
         opc = "ilu" if args.pc == "lu" else "lu"
         try:  # the other inner-solver variant is informative only: it must never cost the bench line
             so = build_solver(es, sigma, args, device, opc)
@@ -741,7 +782,7 @@ def main() -> None:
                 "seconds_restart": stats.get("seconds_restart"),
             },
         }
-        if world == 1 and not args.no_other_pc:
+        if args.full and world == 1 and not args.no_other_pc:
             for name, fn in (("two_solves_in_flight", lambda: solves_in_flight(es, sigma, args, device)),
                              # (three is the most one GPU takes: with four the solves' streams outnumber the hardware queues and
                              #  the rate falls below that of two -- tools/micro/jobs_in_flight.py: 385 / 589 / 756 / 483 at J = 1..4)
@@ -755,7 +796,7 @@ def main() -> None:
                     out["config"][name] = {"error": f"{type(exc).__name__}: {exc}"}
         la = out["config"].get("lu_apply")
         out["config"]["analysis_ms"] = 1e3 * la["seconds_analyse"] if isinstance(la, dict) and "seconds_analyse" in la else None
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 roof = spmv_roofline(args, device)
                 out["roofline"] = {
@@ -775,7 +816,7 @@ def main() -> None:
             # the CPU baseline is a leg of the N = 1 run (same S30k workload as its GPU line); the sharded run's workload
             # takes the oracle many minutes and would hold the other ranks in the closing barrier
             out["cpu_baseline"] = None
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             try:
                 base, lam_cpu = cpu_baseline(es, sigma, args)
                 out["cpu_baseline"] = base

@@ -7,8 +7,8 @@ export TMPDIR=/tmp
 OUT=gpurun_out/$R
 mkdir -p $OUT
 set -x
-python3 bench.py > $OUT/bench_line.json 2> $OUT/bench.err || exit 1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 bench.py > $OUT/bench_line_under_rocprof.json 2> $OUT/bench_rocprof.err || exit 1
+python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 bench.py --full > $OUT/bench_line_under_rocprof.json 2> $OUT/bench_rocprof.err || exit 1
 cp $(find $OUT/prof_bench -name '*kernel_stats.csv' | head -1) $OUT/bench_kernel_stats.csv
 rm -rf $OUT/prof_bench
 for c in FETCH_SIZE WRITE_SIZE; do

@@ -2,8 +2,8 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 OUT=gpurun_out/r04b
 mkdir -p $OUT
-python3 bench.py > $OUT/bench_line.json 2> $OUT/bench.err || exit 1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 bench.py > $OUT/bench_line_under_rocprof.json 2> $OUT/bench_rocprof.err || exit 1
+python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 bench.py --full > $OUT/bench_line_under_rocprof.json 2> $OUT/bench_rocprof.err || exit 1
 cp $(find $OUT/prof_bench -name '*kernel_stats.csv' | head -1) $OUT/bench_kernel_stats.csv
 rm -rf $OUT/prof_bench
 python3 -c "
