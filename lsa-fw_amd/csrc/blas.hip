@@ -447,7 +447,16 @@ __global__ __launch_bounds__(kThreads) void cgs_scale_kernel(int64_t n, const T*
 // a sub-wave of LPR lanes per row exactly as spmv_subwave_kernel walks it: entries lane, lane + LPR, ... in order, butterfly over
 // the sub-wave -- the products are bit for bit those of k_spmv on v_next and y.  Up to three trips of a row are requested at once.
 // (Requesting the row's entries ahead of the norm's partial sums changed nothing: 12.4 / 13.2 us; the two gathers per entry bound it.)
-template <typename MT, int LPR>
+// the sum of per-workgroup partials of |w|^2 by one workgroup of kThreads, in a fixed order (valid in thread 0)
+__device__ __forceinline__ double parts_sum(const double* __restrict__ nrm_part, int nparts, double* smem /* >= 4 */) {
+    double a = 0.0;
+    for (int k = threadIdx.x; k < nparts; k += kThreads) a += nrm_part[k];
+    return block_sum<double>(a, smem);
+}
+
+// DELAYED (the DCGS2 step, see dcgs_update_kernel): w is the vector projected once, left unscaled; t <- M w, and workgroup 0
+// writes ||w|| from the update's partials into hout[0] (h1, h2, vnext unused)
+template <typename MT, int LPR, bool DELAYED = false>
 __global__ __launch_bounds__(kThreads) void cgs_tail_kernel(int32_t n, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
                                                             const MT* __restrict__ mval, const cplx* __restrict__ cval,
                                                             const cplx* __restrict__ w, const cplx* __restrict__ y,
@@ -457,17 +466,23 @@ __global__ __launch_bounds__(kThreads) void cgs_tail_kernel(int32_t n, const int
     __shared__ double smem[4];
     __shared__ double tot_s;
     __shared__ double csum[4][2];
-    double a = 0.0;
-    for (int k = threadIdx.x; k < nparts; k += kThreads) a += nrm_part[k];
-    const double tsum = block_sum<double>(a, smem);
-    if (threadIdx.x == 0) tot_s = tsum;
-    __syncthreads();
-    const double tot = tot_s;
-    if (blockIdx.x == 0) {
-        for (int c = threadIdx.x; c < j; c += kThreads) hout[c] = s_add(h1[c], h2[c]);
-        if (threadIdx.x == 0) s_from(hout[j], sqrt(tot), 0.0);
+    double s = 1.0;
+    if constexpr (DELAYED) {
+        if (blockIdx.x == 0) {
+            const double tsum = parts_sum(nrm_part, nparts, smem);
+            if (threadIdx.x == 0) s_from(hout[0], sqrt(tsum), 0.0);
+        }
+    } else {
+        const double tsum = parts_sum(nrm_part, nparts, smem);
+        if (threadIdx.x == 0) tot_s = tsum;
+        __syncthreads();
+        const double tot = tot_s;
+        if (blockIdx.x == 0) {
+            for (int c = threadIdx.x; c < j; c += kThreads) hout[c] = s_add(h1[c], h2[c]);
+            if (threadIdx.x == 0) s_from(hout[j], sqrt(tot), 0.0);
+        }
+        s = 1.0 / sqrt(tot);
     }
-    const double s = 1.0 / sqrt(tot);
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int32_t lane = (int32_t)(gid % LPR);
     const int64_t row_stride = ((int64_t)gridDim.x * blockDim.x) / LPR;
@@ -495,7 +510,8 @@ __global__ __launch_bounds__(kThreads) void cgs_tail_kernel(int32_t n, const int
 #pragma unroll
             for (int u = 0; u < 3; ++u)
                 if (p + u * LPR < p1) {
-                    fma_acc(am, vm[u], s_mul(s, xw[u]));
+                    if constexpr (DELAYED) fma_acc(am, vm[u], xw[u]);
+                    else fma_acc(am, vm[u], s_mul(s, xw[u]));
                     fma_acc(ac, vc[u], xy[u]);
                 }
         }
@@ -509,7 +525,7 @@ __global__ __launch_bounds__(kThreads) void cgs_tail_kernel(int32_t n, const int
             rw += s_abs2(s_sub(told, ac));
             rb += s_abs2(told);
             t[row] = am;
-            vnext[row] = s_mul(s, w[row]);
+            if constexpr (!DELAYED) vnext[row] = s_mul(s, w[row]);
         }
     }
     rw = wave_sum_dpp(rw);
@@ -538,6 +554,265 @@ __global__ __launch_bounds__(kThreads) void cgs_tail_checks_kernel(int nparts, c
         checks[2 * blockIdx.x] = sa;
         checks[2 * blockIdx.x + 1] = sb;
     }
+}
+
+// ---- DCGS2: an Arnoldi step with one reduction (delayed reorthogonalisation) ------------------------------------------------
+// Bielich, Langou, Thomas, Swirydowicz, Yamazaki, Boman, "Low-synch Gram-Schmidt with delayed reorthogonalization for Krylov
+// solvers" (Parallel Computing 2022).  On entry to step j, Q = V[:, 0:j] is orthonormal and p = V[:, j] has been projected once
+// but not normalised; y = OP p.  The second projection of p rides in step j's single reduction:
+//   dcgs_dot     partials of a = Q^H p, alpha = p^H p, b = Q^H y, beta = p^H y (V[:, 0:j+1] against p and y, chunk-major,
+//                p-dots at columns [0, kFuseCols), y-dots at [kFuseCols, 2 kFuseCols) of a chunk's row of partials)
+//   dcgs_update  every workgroup sums the partials in chunk order, nu = sqrt(alpha - |a|^2), c = (beta - a^H b) / nu, and per
+//                row q = (p - Q a) / nu into V[:, j] (in place: a row is read and written by one thread), w = (y - Q b - c q) / nu
+//                into V[:, j+1] (projected once, unscaled), per-workgroup |w|^2; workgroup 0 writes a, b, nu, c to the step's slot
+// and the norm of w is summed by the tail (cgs_tail_kernel<.., true>) or by dcgs_norm.  first != 0: V[:, j] is final already
+// (a = 0, nu = 1: y is projected once against V[:, 0:j+1]).  Without y (the flush at the end of a run of steps) the update only
+// makes V[:, j] final.  Slot of a step (complex entries, lds = ncv): a at [0, j), b at [lds, lds + j), nu at 2 lds, c at
+// 2 lds + 1, ||w|| at 2 lds + 2.
+template <bool Y>
+__global__ __launch_bounds__(kThreads) void dcgs_dot_kernel(int64_t n, int jc, int64_t rows_per_block, const cplx* __restrict__ V, int64_t ldv,
+                                                            const cplx* __restrict__ y, cplx* __restrict__ part, int ldp,
+                                                            const cplx* __restrict__ chk_b, const cplx* __restrict__ chk_z, double* __restrict__ chk_part) {
+    __shared__ cplx wsum[4][2 * kColTile];
+    __shared__ double dsm[4][2];
+    const cplx* __restrict__ p = V + (int64_t)(jc - 1) * ldv;
+    const int chunk = blockIdx.x;
+    const int c0 = blockIdx.y * kColTile;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t r0 = (int64_t)chunk * rows_per_block;
+    const int64_t r1 = (r0 + rows_per_block < n) ? r0 + rows_per_block : n;
+    cplx ap[kColTile], ay[kColTile];
+#pragma unroll
+    for (int c = 0; c < kColTile; ++c) ap[c] = ay[c] = cplx{0.0, 0.0};
+    const int nc = (jc - c0 < kColTile) ? (jc - c0) : kColTile;
+    if (nc == kColTile) {
+        int64_t i = r0 + threadIdx.x;
+        for (; i + kThreads < r1; i += 2 * kThreads) {  // two rows per thread and trip, as cgs_dot_kernel
+            const cplx pa = p[i], pb = p[i + kThreads];
+            cplx ya = cplx{0.0, 0.0}, yb = cplx{0.0, 0.0};
+            if constexpr (Y) {
+                ya = y[i];
+                yb = y[i + kThreads];
+            }
+            cplx va[kColTile], vb[kColTile];
+#pragma unroll
+            for (int c = 0; c < kColTile; ++c) {
+                va[c] = V[i + (int64_t)(c0 + c) * ldv];
+                vb[c] = V[i + kThreads + (int64_t)(c0 + c) * ldv];
+            }
+#pragma unroll
+            for (int c = 0; c < kColTile; ++c) {
+                fma_conj_acc(ap[c], va[c], pa);
+                fma_conj_acc(ap[c], vb[c], pb);
+                if constexpr (Y) {
+                    fma_conj_acc(ay[c], va[c], ya);
+                    fma_conj_acc(ay[c], vb[c], yb);
+                }
+            }
+        }
+        for (; i < r1; i += kThreads) {
+            const cplx pv = p[i];
+            const cplx yv = Y ? y[i] : cplx{0.0, 0.0};
+#pragma unroll
+            for (int c = 0; c < kColTile; ++c) {
+                const cplx v = V[i + (int64_t)(c0 + c) * ldv];
+                fma_conj_acc(ap[c], v, pv);
+                if constexpr (Y) fma_conj_acc(ay[c], v, yv);
+            }
+        }
+    } else {
+        for (int64_t i = r0 + threadIdx.x; i < r1; i += kThreads) {
+            const cplx pv = p[i];
+            const cplx yv = Y ? y[i] : cplx{0.0, 0.0};
+#pragma unroll
+            for (int c = 0; c < kColTile; ++c)
+                if (c < nc) {
+                    const cplx v = V[i + (int64_t)(c0 + c) * ldv];
+                    fma_conj_acc(ap[c], v, pv);
+                    if constexpr (Y) fma_conj_acc(ay[c], v, yv);
+                }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < kColTile; ++c) {
+        const cplx sp = wave_sum_dpp(ap[c]);
+        if (lane == 0) wsum[wave][c] = sp;
+        if constexpr (Y) {
+            const cplx sy = wave_sum_dpp(ay[c]);
+            if (lane == 0) wsum[wave][kColTile + c] = sy;
+        }
+    }
+    double rw = 0.0, rb = 0.0;
+    const bool chk = chk_part != nullptr && blockIdx.y == 0;
+    if (chk) {
+        for (int64_t i = r0 + threadIdx.x; i < r1; i += kThreads) {
+            const cplx bi = chk_b[i];
+            rw += s_abs2(s_sub(bi, chk_z[i]));
+            rb += s_abs2(bi);
+        }
+        rw = wave_sum_dpp(rw);
+        rb = wave_sum_dpp(rb);
+        if (lane == 0) {
+            dsm[wave][0] = rw;
+            dsm[wave][1] = rb;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < nc) {
+        const int c = threadIdx.x;
+        part[(int64_t)chunk * ldp + c0 + c] = s_add(s_add(wsum[0][c], wsum[1][c]), s_add(wsum[2][c], wsum[3][c]));
+    }
+    if (Y && threadIdx.x >= 32 && threadIdx.x < 32 + nc) {
+        const int c = threadIdx.x - 32;
+        part[(int64_t)chunk * ldp + kFuseCols + c0 + c] =
+            s_add(s_add(wsum[0][kColTile + c], wsum[1][kColTile + c]), s_add(wsum[2][kColTile + c], wsum[3][kColTile + c]));
+    }
+    if (chk && threadIdx.x >= 64 && threadIdx.x < 66) {
+        const int q = threadIdx.x - 64;
+        chk_part[2 * chunk + q] = (dsm[0][q] + dsm[1][q]) + (dsm[2][q] + dsm[3][q]);
+    }
+}
+
+// Workgroup = 64 rows, four lanes per row (lane class q takes the columns c = q mod 4), the first eight basis entries of a
+// thread requested before the coefficients exist: the layout and the load schedule of cgs_axpy_kernel, with two sums per row
+// (Q a and Q b) from one pass over Q.
+template <bool Y>
+__global__ __launch_bounds__(kThreads) void dcgs_update_kernel(int64_t n, int j, cplx* V, int64_t ldv, const cplx* __restrict__ part, int nchunks,
+                                                               int ldp, const cplx* __restrict__ y, int first, double* __restrict__ nrm_part,
+                                                               cplx* __restrict__ slot, int lds, const double* __restrict__ chk_part,
+                                                               double* __restrict__ chk_out) {
+    __shared__ double wn[4];
+    __shared__ cplx hs[2 * kFuseCols];  // a, alpha at [0, j]; b, beta at kFuseCols + [0, j]
+    __shared__ double nu_s;
+    __shared__ cplx c_s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = lane >> 4;
+    const int64_t i = (int64_t)blockIdx.x * 64 + wave * 16 + (lane & 15);
+    cplx v0[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v0[u] = (i < n && q + 4 * u < j) ? V[i + (int64_t)(q + 4 * u) * ldv] : cplx{0.0, 0.0};
+    cplx pi = cplx{0.0, 0.0}, yi = cplx{0.0, 0.0};
+    if (q == 0 && i < n) {
+        pi = V[i + (int64_t)j * ldv];
+        if constexpr (Y) yi = y[i];
+    }
+    {
+        // thread t sums entry t of a chunk's row of partials over the chunks, in chunk order, 32 requests at a time
+        const int t = threadIdx.x;
+        const int c = t < kFuseCols ? t : t - kFuseCols;
+        const bool need = c <= j && (Y || t < kFuseCols);
+        cplx acc = cplx{0.0, 0.0};
+        if (need) {
+            for (int k0 = 0; k0 < nchunks; k0 += 32) {
+                cplx pv[32];
+#pragma unroll
+                for (int u = 0; u < 32; ++u) pv[u] = (k0 + u < nchunks) ? part[(int64_t)(k0 + u) * ldp + t] : cplx{0.0, 0.0};
+#pragma unroll
+                for (int u = 0; u < 32; ++u)
+                    if (k0 + u < nchunks) acc = s_add(acc, pv[u]);
+            }
+            hs[t] = acc;
+        }
+        if (chk_out && blockIdx.x == 0 && threadIdx.x < 2) {
+            double a = 0.0;
+            for (int k = 0; k < nchunks; ++k) a += chk_part[2 * k + threadIdx.x];
+            chk_out[threadIdx.x] = a;
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        // |a|^2 and a^H b by wavefront 0, lanes over the columns, then one wave sum each (fixed order)
+        double s1 = 0.0;
+        cplx s2 = cplx{0.0, 0.0};
+        for (int c = lane; c < j; c += 64) {
+            s1 += s_abs2(hs[c]);
+            if constexpr (Y) fma_conj_acc(s2, hs[c], hs[kFuseCols + c]);
+        }
+        s1 = wave_sum_dpp(s1);
+        if constexpr (Y) s2 = wave_sum_dpp(s2);
+        if (lane == 0) {
+            const cplx beta = Y ? hs[kFuseCols + j] : cplx{0.0, 0.0};
+            if (first) {
+                nu_s = 1.0;
+                c_s = beta;
+            } else {
+                const double d = hs[j].re - s1;  // (< 0 only by rounding, at a breakdown; NaN stays NaN)
+                const double nu = sqrt(d < 0.0 ? 0.0 : d);
+                const double inv = 1.0 / nu;
+                nu_s = nu;
+                c_s = s_mul(inv, s_sub(beta, s2));
+            }
+        }
+    }
+    __syncthreads();
+    const double nu = nu_s, inv = 1.0 / nu;
+    const cplx cc = c_s;
+    if (blockIdx.x == 0) {
+        for (int c = threadIdx.x; c < j; c += kThreads) {
+            slot[c] = first ? cplx{0.0, 0.0} : hs[c];
+            if constexpr (Y) slot[lds + c] = hs[kFuseCols + c];
+        }
+        if (threadIdx.x == 0) {
+            slot[2 * lds] = cplx{nu, 0.0};
+            slot[2 * lds + 1] = cc;
+        }
+    }
+    cplx aa = cplx{0.0, 0.0}, ab = cplx{0.0, 0.0};
+    if (i < n) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (q + 4 * u < j) {
+                if (!first) fma_acc(aa, hs[q + 4 * u], v0[u]);
+                if constexpr (Y) fma_acc(ab, hs[kFuseCols + q + 4 * u], v0[u]);
+            }
+        for (int c = q + 32; c < j; c += 32) {
+            cplx v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = (c + 4 * u < j) ? V[i + (int64_t)(c + 4 * u) * ldv] : cplx{0.0, 0.0};
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (c + 4 * u < j) {
+                    if (!first) fma_acc(aa, hs[c + 4 * u], v[u]);
+                    if constexpr (Y) fma_acc(ab, hs[kFuseCols + c + 4 * u], v[u]);
+                }
+        }
+    }
+    // the four partial sums of a row sit 16 lanes apart: bring them together in class order (fixed order of additions)
+    const int l1 = (lane & 15) + 16, l2 = (lane & 15) + 32, l3 = (lane & 15) + 48;
+    const cplx a1 = cplx{__shfl(aa.re, l1), __shfl(aa.im, l1)}, a2 = cplx{__shfl(aa.re, l2), __shfl(aa.im, l2)},
+               a3 = cplx{__shfl(aa.re, l3), __shfl(aa.im, l3)};
+    cplx b1 = cplx{0.0, 0.0}, b2 = b1, b3 = b1;
+    if constexpr (Y) {
+        b1 = cplx{__shfl(ab.re, l1), __shfl(ab.im, l1)};
+        b2 = cplx{__shfl(ab.re, l2), __shfl(ab.im, l2)};
+        b3 = cplx{__shfl(ab.re, l3), __shfl(ab.im, l3)};
+    }
+    double nrm = 0.0;
+    if (q == 0 && i < n) {
+        cplx qv = pi;
+        if (!first) {
+            qv = s_mul(inv, s_sub(pi, s_add(s_add(aa, a1), s_add(a2, a3))));
+            V[i + (int64_t)j * ldv] = qv;
+        }
+        if constexpr (Y) {
+            const cplx r = s_mul(inv, s_sub(s_sub(yi, s_add(s_add(ab, b1), s_add(b2, b3))), s_mul(cc, qv)));
+            V[i + (int64_t)(j + 1) * ldv] = r;
+            nrm = s_abs2(r);
+        }
+    }
+    if constexpr (Y) {
+        nrm = wave_sum_dpp(nrm);
+        if (lane == 0) wn[wave] = nrm;
+        __syncthreads();
+        if (threadIdx.x == 0) nrm_part[blockIdx.x] = (wn[0] + wn[1]) + (wn[2] + wn[3]);
+    }
+}
+
+// the provisional ||w|| of a DCGS2 step where no tail launch sums it (one workgroup: the sum of cgs_tail_kernel's workgroup 0)
+__global__ __launch_bounds__(kThreads) void dcgs_norm_kernel(const double* __restrict__ nrm_part, int nparts, cplx* __restrict__ out) {
+    __shared__ double smem[4];
+    const double t = parts_sum(nrm_part, nparts, smem);
+    if (threadIdx.x == 0) s_from(out[0], sqrt(t), 0.0);
 }
 
 // ---- Ritz vectors: unit norm and a canonical phase for all columns in two launches --------------------------------------------
@@ -1089,4 +1364,67 @@ int k_cgs2_tail_checks(lsa_ctx* ctx, int nslots, int nparts, const double* tail_
     if (nslots <= 0) return LSA_OK;
     hipLaunchKernelGGL(cgs_tail_checks_kernel, dim3(nslots), dim3(kThreads), 0, ctx->stream, nparts, tail_parts, checks);
     return check_launch(ctx, "cgs2_tail_checks");
+}
+
+// DCGS2 (see dcgs_dot_kernel): the reduction and the update of step j (Q = V[:, 0:j], p = V[:, j]) in two launches, into the
+// fused workspace (its two blocks of partials side by side are one chunk-major array of 2 kFuseCols columns).  y == nullptr:
+// the flush, which only makes V[:, j] final.  The check of the inner solve (chk_b, chk_z -> chk_out) rides as in k_cgs2_fused.
+bool k_dcgs2_fits(int64_t n, int ncv) { return cgs2_fused_shape(n, ncv + 1, nullptr); }
+
+// the check's pairs and the |w|^2 partials in the fused workspace (behind part1, part2, h1, h2 of k_cgs2_fused)
+static double* fused_chk_part(void* work) { return (double*)((char*)work + (size_t)16 * (size_t)(2 * kFuseChunks * kFuseCols + 2 * kFuseCols)); }
+static double* fused_nrm_part(void* work) { return fused_chk_part(work) + 2 * kFuseChunks; }
+
+int k_dcgs2_step(lsa_ctx* ctx, int64_t n, int j, void* V, int64_t ldv, const void* y, int first, void* slot, int lds, void* work,
+                 const void* chk_b, const void* chk_z, double* chk_out) {
+    int64_t rpb = 0;
+    if (!cgs2_fused_shape(n, j + 1, &rpb) || j < 0 || j + 1 > lds + 1 || (first && !y))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "k_dcgs2_step: shape outside the fused form");
+    const int nchunks = (int)((n + rpb - 1) / rpb);
+    const int blocks = (int)((n + 63) / 64);
+    cplx* part = (cplx*)work;
+    double* chk_part = fused_chk_part(work);
+    double* nrm_part = fused_nrm_part(work);
+    const dim3 dgrid(nchunks, (j + 1 + kColTile - 1) / kColTile);
+    const int ldp = 2 * kFuseCols;
+    if (y) {
+        hipLaunchKernelGGL((dcgs_dot_kernel<true>), dgrid, dim3(kThreads), 0, ctx->stream, n, j + 1, rpb, (const cplx*)V, ldv, (const cplx*)y, part, ldp,
+                           (const cplx*)chk_b, (const cplx*)chk_z, chk_out ? chk_part : (double*)nullptr);
+        hipLaunchKernelGGL((dcgs_update_kernel<true>), dim3(blocks), dim3(kThreads), 0, ctx->stream, n, j, (cplx*)V, ldv, (const cplx*)part, nchunks, ldp,
+                           (const cplx*)y, first, nrm_part, (cplx*)slot, lds, (const double*)chk_part, chk_out);
+    } else {
+        hipLaunchKernelGGL((dcgs_dot_kernel<false>), dgrid, dim3(kThreads), 0, ctx->stream, n, j + 1, rpb, (const cplx*)V, ldv, (const cplx*)nullptr, part,
+                           ldp, (const cplx*)nullptr, (const cplx*)nullptr, (double*)nullptr);
+        hipLaunchKernelGGL((dcgs_update_kernel<false>), dim3(blocks), dim3(kThreads), 0, ctx->stream, n, j, (cplx*)V, ldv, (const cplx*)part, nchunks, ldp,
+                           (const cplx*)nullptr, 0, (double*)nullptr, (cplx*)slot, lds, (const double*)nullptr, (double*)nullptr);
+    }
+    return check_launch(ctx, "dcgs2_step");
+}
+
+// the provisional ||V[:, j+1]|| of the step k_dcgs2_step just queued, into its slot (the form without a tail launch)
+int k_dcgs2_norm(lsa_ctx* ctx, int64_t n, void* work, void* slot, int lds) {
+    double* nrm_part = fused_nrm_part(work);
+    hipLaunchKernelGGL(dcgs_norm_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)nrm_part, (int)((n + 63) / 64),
+                       (cplx*)slot + 2 * (size_t)lds + 2);
+    return check_launch(ctx, "dcgs2_norm");
+}
+
+// the tail of a DCGS2 step (k_cgs2_fused_tail's last launch, unscaled): t <- M V[:, j+1] for the next step, this step's check
+// pairs, the provisional ||V[:, j+1]|| into the slot
+int k_dcgs2_tail(lsa_ctx* ctx, int64_t n, int j, const void* V, int64_t ldv, const void* y, void* work, const lsa_mat* M, const lsa_mat* C, void* t,
+                 double* tail_part, void* slot, int lds) {
+    const int blocks = (int)((n + 63) / 64);
+    double* nrm_part = fused_nrm_part(work);
+    const cplx* w = (const cplx*)V + (size_t)(j + 1) * (size_t)ldv;
+    cplx* nout = (cplx*)slot + 2 * (size_t)lds + 2;
+    const int tparts = k_cgs2_tail_parts(n);
+    if (M->dtype == LSA_C128)
+        hipLaunchKernelGGL((cgs_tail_kernel<cplx, 16, true>), dim3(tparts), dim3(kThreads), 0, ctx->stream, (int32_t)n, C->rp, C->ci, (const cplx*)M->val,
+                           (const cplx*)C->val, w, (const cplx*)y, (const double*)nrm_part, blocks, (cplx*)nullptr, (cplx*)t, 0, (const cplx*)nullptr,
+                           (const cplx*)nullptr, nout, tail_part);
+    else
+        hipLaunchKernelGGL((cgs_tail_kernel<double, 16, true>), dim3(tparts), dim3(kThreads), 0, ctx->stream, (int32_t)n, C->rp, C->ci,
+                           (const double*)M->val, (const cplx*)C->val, w, (const cplx*)y, (const double*)nrm_part, blocks, (cplx*)nullptr, (cplx*)t, 0,
+                           (const cplx*)nullptr, (const cplx*)nullptr, nout, tail_part);
+    return check_launch(ctx, "dcgs2_tail");
 }

@@ -258,6 +258,17 @@ int k_cgs2_tail_parts(int64_t n);  // workgroups of the tail kernel = (|t - C y|
 int k_cgs2_fused_tail(lsa_ctx* ctx, int64_t n, int j, const void* V, int64_t ldv, const void* y, void* w, void* vnext, void* hcol_dev, void* work,
                       const lsa_mat* M, const lsa_mat* C, void* t, double* tail_part);
 int k_cgs2_tail_checks(lsa_ctx* ctx, int nslots, int nparts, const double* tail_parts, double* checks);
+// DCGS2 (delayed reorthogonalisation) of a pipelined Arnoldi step in the fused workspace, complex vectors: one reduction and one
+// update (k_dcgs2_step: V[:, j] projected twice and normalised in place, y projected once into V[:, j+1], the step's a, b, nu, c
+// into its slot of 2 lds + 4 entries; y == nullptr: the flush, V[:, j] only), then either the tail (k_dcgs2_tail: t <- M V[:, j+1]
+// and the check pairs, as k_cgs2_fused_tail) or k_dcgs2_norm; both leave the provisional ||V[:, j+1]|| at slot[2 lds + 2].
+// first != 0: V[:, j] is final already.  Fits for bases of up to ncv + 1 vectors with ncv + 1 <= 128 (n <= 262 k).
+bool k_dcgs2_fits(int64_t n, int ncv);
+int k_dcgs2_step(lsa_ctx* ctx, int64_t n, int j, void* V, int64_t ldv, const void* y, int first, void* slot, int lds, void* work,
+                 const void* chk_b, const void* chk_z, double* chk_out);
+int k_dcgs2_norm(lsa_ctx* ctx, int64_t n, void* work, void* slot, int lds);
+int k_dcgs2_tail(lsa_ctx* ctx, int64_t n, int j, const void* V, int64_t ldv, const void* y, void* work, const lsa_mat* M, const lsa_mat* C, void* t,
+                 double* tail_part, void* slot, int lds);
 int k_spmv_plain_subwave_lanes(const lsa_mat* A);  // spmv.hip
 // Out[:, 0:k] = V[:, 0:m] Q   (Q m x k column-major on the device, ldq)
 int k_basis_gemm(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V, int64_t ldv, const void* Q, int ldq,

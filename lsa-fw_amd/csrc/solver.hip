@@ -472,10 +472,10 @@ struct lsa_krylov {
     double* imag2 = nullptr;         // device: sum Im^2 of the columns of the last canonical Ritz vectors
     void* xtmp = nullptr;            // device: the Ritz vectors in the caller's row order (ncv + 1 columns), allocated on first use
     std::vector<double> imag_norms;  // ... their square roots on the host (lsa_krylov_imag_norms)
-    void* Hdev = nullptr;      // batch x (ncv + 2) complex
-    double* checks = nullptr;  // batch x 2: ||b - C x||^2, ||b||^2
+    void* Hdev = nullptr;      // max(batch, 1) slots of 2 ncv + 4 complex: a Hessenberg column (CGS2) or a, b, nu, c, ||w|| (DCGS2)
+    double* checks = nullptr;  // max(batch, 1) x 2: ||b - C x||^2, ||b||^2
     int32_t batch = 0;
-    bool pipeline = false;
+    bool pipeline = false;  // the pipelined path may run (false after a solve needed the one-step path's judgement)
     // tail form of a pipelined step (k_cgs2_fused_tail): the step's last launch also multiplies t = M v_{j+1} for the next step
     // and leaves the pairs of this step's check of the inner solve; w2 takes the orthogonalised vector (w keeps the solve's result)
     void* w2 = nullptr;
@@ -483,6 +483,9 @@ struct lsa_krylov {
     int32_t tail_nparts = 0;
     int32_t t_for = -1;            // op->t holds M v_j for this j (valid inside one lsa_krylov_extend call), -1: nothing
 };
+
+// bytes of one step's slot in Hdev: a CGS2 Hessenberg column (ncv + 2 entries) or DCGS2's a, b, nu, c, ||w|| (2 ncv + 3)
+static size_t krylov_slot_bytes(int32_t ncv) { return (size_t)(2 * ncv + 4) * 16; }
 
 static void krylov_free(lsa_krylov* k) {
     for (void* p : {k->V, k->V2, k->w, k->qdev, k->Hdev, (void*)k->checks, (void*)k->imag2, k->xtmp, (void*)k->row_perm, k->w2, (void*)k->tail_parts})
@@ -828,7 +831,7 @@ int lsa_krylov_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, lsa_krylov** out) {
         ctx->krylov_cache = nullptr;
         if (c->n == op->n && c->ncv == ncv && c->batch == batch) {
             c->op = op;
-            c->pipeline = batch > 1;
+            c->pipeline = true;
             c->imag_norms.clear();
             (void)hipMemsetAsync(c->w, 0, vb, ctx->stream);
             *out = c;
@@ -851,16 +854,15 @@ int lsa_krylov_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, lsa_krylov** out) {
     (void)hipMemsetAsync(k->w, 0, vb, ctx->stream);
     k->hcol.assign((size_t)ncv + 2, zc(0));
     // Arnoldi steps are queued in batches when the inner solve is one exact LU solve and the exchange (if any) is
-    // stream-ordered (RCCL): LSA_KRYLOV_BATCH steps per read-back (default 16; 0 or 1 = one step at a time)
+    // stream-ordered (RCCL): LSA_KRYLOV_BATCH steps per read-back (default 16; 0 or 1 = one step at a time, except in the
+    // delayed form, whose basis must not depend on the batch size: there it means one step per read-back)
     k->batch = batch;
-    if (k->batch > 1) {
-        if (hipMalloc(&k->Hdev, (size_t)k->batch * (size_t)(ncv + 2) * 16) != hipSuccess ||
-            hipMalloc((void**)&k->checks, (size_t)k->batch * 2 * sizeof(double)) != hipSuccess) {
-            lsa_krylov_destroy(k);
-            return lsa_set_error(ctx, LSA_ERR_HIP, "lsa_krylov_create: out of device memory (pipeline buffers)");
-        }
-        k->pipeline = true;
+    const size_t slots = (size_t)std::max(batch, 1);
+    if (hipMalloc(&k->Hdev, slots * krylov_slot_bytes(ncv)) != hipSuccess || hipMalloc((void**)&k->checks, slots * 2 * sizeof(double)) != hipSuccess) {
+        lsa_krylov_destroy(k);
+        return lsa_set_error(ctx, LSA_ERR_HIP, "lsa_krylov_create: out of device memory (pipeline buffers)");
     }
+    k->pipeline = true;
     *out = k;
     return LSA_OK;
 }
@@ -957,7 +959,7 @@ static int krylov_enqueue_step(lsa_ctx* ctx, lsa_krylov* k, int32_t j, int32_t s
     pcr.nd = op->nd;
     pcr.nd_dist = op->nd_dist;
     pcr.adjoint = op->adjoint;
-    void* hcol_dev = (char*)k->Hdev + (size_t)slot * (size_t)(k->ncv + 2) * 16;
+    void* hcol_dev = (char*)k->Hdev + (size_t)slot * krylov_slot_bytes(k->ncv);
     if (tail) {
         // 18 launches: [M v_j unless the previous step's tail left it] + the sweeps + dot, update, dot, update + tail
         if (k->t_for != j) LSA_CHECK(spmv_global(ctx, op->Kmul, dtype, vj, op->t, false));
@@ -999,11 +1001,64 @@ static int krylov_enqueue_step(lsa_ctx* ctx, lsa_krylov* k, int32_t j, int32_t s
     return orthonormalize_enqueue(ctx, dtype, k->n, k->V, k->n, j + 1, k->w, vn, k->ow, hcol_dev);
 }
 
-// true when an operator apply is one exact LU solve whose result only needs checking, with nothing on the way that
-// synchronises with the host by itself (the host-staged exchange does)
-static bool krylov_can_pipeline(const lsa_ctx* ctx, const lsa_krylov* k) {
+// The delayed form of the pipelined steps (DCGS2: one reduction and one update per step instead of CGS2's four launches; see
+// k_dcgs2_step) where the five-launch CGS2 runs otherwise: one rank, forward operator, a basis of at most 128 vectors of at most
+// 262 k rows.  On entry to step j, V[:, j] holds the previous step's vector projected once and column j-1 of H is provisional;
+// step j's reduction finishes both.  LSA_KRYLOV_DELAYED=0: CGS2.
+static bool krylov_delayed_ok(const lsa_ctx* ctx, const lsa_krylov* k) {
+    static const bool enabled = !(getenv("LSA_KRYLOV_DELAYED") && atoi(getenv("LSA_KRYLOV_DELAYED")) == 0);
+    static const bool fuse = !(getenv("LSA_KRYLOV_FUSED") && atoi(getenv("LSA_KRYLOV_FUSED")) == 0);
     const lsa_op* op = k->op;
-    if (!k->pipeline || !op->Kfac || !op->nd || op->pc) return false;
+    return enabled && fuse && ctx->nranks == 1 && !op->adjoint && op->n == k->n && k_dcgs2_fits(k->n, k->ncv);
+}
+
+// one step of the delayed form: [M p unless the previous tail left it] + the sweeps + reduce, update + tail (16 launches), or
+// without the tail form M p + the sweeps + C y + reduce, update, norm.  first: V[:, j] is final (the first step of a run)
+static int krylov_enqueue_dstep(lsa_ctx* ctx, lsa_krylov* k, int32_t j, int32_t slot, bool tail, bool first) {
+    lsa_op* op = k->op;
+    const int dtype = LSA_C128;
+    const void* vj = (char*)k->V + (size_t)j * (size_t)k->n * 16;
+    void* sl = (char*)k->Hdev + (size_t)slot * krylov_slot_bytes(k->ncv);
+    PcRef pcr;
+    pcr.nd = op->nd;
+    pcr.nd_dist = op->nd_dist;
+    pcr.adjoint = op->adjoint;
+    LSA_CHECK(k->ow.ensure_fused(ctx, k->n));
+    if (tail) {
+        if (k->t_for != j) LSA_CHECK(spmv_global(ctx, op->Kmul, dtype, vj, op->t, false));
+        k->t_for = -1;
+        LSA_CHECK(pc_global(ctx, pcr, op->Kfac->row0, op->n, dtype, op->t, k->w));
+        LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, k->w, first ? 1 : 0, sl, k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
+        LSA_CHECK(k_dcgs2_tail(ctx, k->n, j, k->V, k->n, k->w, k->ow.fused, op->Kmul, op->Kfac, op->t, k->tail_parts + (size_t)slot * 2 * (size_t)k->tail_nparts,
+                               sl, k->ncv));
+        k->t_for = j + 1;
+        return LSA_OK;
+    }
+    k->t_for = -1;
+    const void* rhs = vj;
+    if (op->Kmul) {
+        LSA_CHECK(spmv_global(ctx, op->Kmul, dtype, vj, op->t, false));
+        rhs = op->t;
+    }
+    LSA_CHECK(pc_global(ctx, pcr, op->Kfac->row0, op->n, dtype, rhs, k->w));
+    LSA_CHECK(spmv_global(ctx, op->Kfac, dtype, k->w, op->gw.z, false));
+    if (op->refine) {  // as krylov_enqueue_step
+        LSA_CHECK(k_residual_norms(ctx, dtype, op->n, rhs, op->gw.z, op->gw.w, k->checks + 2 * (size_t)slot));
+        LSA_CHECK(pc_global(ctx, pcr, op->Kfac->row0, op->n, dtype, op->gw.w, op->gw.z));
+        const double one[2] = {1.0, 0.0};
+        LSA_CHECK(k_axpy(ctx, dtype, op->n, one, op->gw.z, k->w));
+        LSA_CHECK(spmv_global(ctx, op->Kfac, dtype, k->w, op->gw.z, false));
+    }
+    if (op->keep) LSA_CHECK(k_mask(ctx, dtype, op->n, op->keep, k->w));
+    LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, k->w, first ? 1 : 0, sl, k->ncv, k->ow.fused, rhs, op->gw.z, k->checks + 2 * (size_t)slot));
+    return k_dcgs2_norm(ctx, k->n, k->ow.fused, sl, k->ncv);
+}
+
+// true when an operator apply is one exact LU solve whose result only needs checking, with nothing on the way that
+// synchronises with the host by itself (the host-staged exchange does); batches of one step only in the delayed form
+static bool krylov_can_pipeline(const lsa_ctx* ctx, const lsa_krylov* k, bool delayed) {
+    const lsa_op* op = k->op;
+    if (!k->pipeline || !(k->batch > 1 || delayed) || !op->Kfac || !op->nd || op->pc) return false;
     if (ctx->nranks > 1 && (!op->nd_dist || ctx->host_gather)) return false;
     return true;
 }
@@ -1026,27 +1081,66 @@ int lsa_krylov_extend(lsa_ctx* ctx, lsa_krylov* k, int32_t j0, int32_t j1, void*
         for (int32_t i = 0; i <= j; ++i) colmax = std::max(colmax, std::abs(hcol[i]));
         return beta <= 1e-14 * std::max(colmax, 1e-300) ? 1 : 0;
     };
+    // delayed form: column jc of H from a step's slot (h = ([b; c] - H[0:jc+1, 0:jc] a) / nu, the provisional ||w|| below it;
+    // first: a = 0, nu = 1), and the step's a, nu finishing column jc - 1; the columns before j0 are the caller's (Arnoldi
+    // relation, zero below row j0), those from j0 on are Hessenberg
+    auto finish_column = [&](int32_t jc, const cplx* sl) -> int {
+        const int32_t ncv = k->ncv;
+        const double nu = sl[2 * ncv].re;
+        for (int32_t i = 0; i < jc; ++i) Hh[(size_t)(jc - 1) * ldh + i] = cplx{Hh[(size_t)(jc - 1) * ldh + i].re + sl[i].re, Hh[(size_t)(jc - 1) * ldh + i].im + sl[i].im};
+        Hh[(size_t)(jc - 1) * ldh + jc] = cplx{nu, 0.0};
+        if (!std::isfinite(nu)) return -1;
+        double colmax = 0.0;
+        for (int32_t i = 0; i < jc; ++i) colmax = std::max(colmax, std::hypot(Hh[(size_t)(jc - 1) * ldh + i].re, Hh[(size_t)(jc - 1) * ldh + i].im));
+        return nu <= 1e-14 * std::max(colmax, 1e-300) ? 1 : 0;
+    };
+    std::vector<cplx> hwork((size_t)k->ncv + 2);
+    auto provisional_column = [&](int32_t jc, const cplx* sl, bool first) -> int {
+        const int32_t ncv = k->ncv;
+        const double inv = 1.0 / sl[2 * ncv].re;
+        cplx* h = hwork.data();
+        for (int32_t i = 0; i < jc; ++i) h[i] = sl[ncv + i];
+        h[jc] = sl[2 * ncv + 1];
+        if (!first) {
+            for (int32_t c = 0; c < jc; ++c) {
+                const cplx a = sl[c];
+                const cplx* Hc = Hh + (size_t)c * ldh;
+                const int32_t rows = std::min(jc, std::max(j0, c + 1));
+                for (int32_t i = 0; i <= rows; ++i) {
+                    h[i].re -= Hc[i].re * a.re - Hc[i].im * a.im;
+                    h[i].im -= Hc[i].re * a.im + Hc[i].im * a.re;
+                }
+            }
+            for (int32_t i = 0; i <= jc; ++i) h[i] = cplx{h[i].re * inv, h[i].im * inv};
+        }
+        for (int32_t i = 0; i <= jc; ++i) k->hcol[i] = zc(h[i].re, h[i].im);
+        k->hcol[jc + 1] = zc(sl[2 * ncv + 2].re, 0.0);
+        return take_column(jc, k->hcol.data());
+    };
     int32_t j = j0;
-    if (krylov_can_pipeline(ctx, k)) {
+    const bool delayed = krylov_delayed_ok(ctx, k);
+    if (krylov_can_pipeline(ctx, k, delayed)) {
         if (!op->gw_ready) {
             LSA_CHECK(op->gw.alloc(ctx, op->n, std::max(1, std::min({op->opts.ksp_restart, op->opts.ksp_maxit, 40})), LSA_C128));
             op->gw_ready = true;
         }
-        const size_t colb = (size_t)(k->ncv + 2) * 16;
-        LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)k->batch * (colb + 2 * sizeof(double))));
+        const int32_t slots = std::max(k->batch, 1);
+        const size_t colb = krylov_slot_bytes(k->ncv);
+        LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)slots * (colb + 2 * sizeof(double))));
         const double rtol = op->opts.ksp_rtol;
         k->t_for = -1;  // (op->t is anybody's between calls)
+        bool pending = false;  // delayed form: V[:, j] is projected once, column j - 1 of H provisional
         while (j < j1 && k->pipeline) {
-            const int32_t nb = std::min<int32_t>(k->batch, j1 - j);
+            const int32_t nb = std::min<int32_t>(slots, j1 - j);
             const double tq = now_s();
             const bool tail = krylov_tail_ok(ctx, k);
             if (tail && !k->tail_parts) {
                 k->tail_nparts = k_cgs2_tail_parts(k->n);
                 LSA_HIP_ALLOC(ctx, hipMalloc(&k->w2, (size_t)k->n * 16));
-                LSA_HIP_ALLOC(ctx, hipMalloc((void**)&k->tail_parts, (size_t)k->batch * 2 * (size_t)k->tail_nparts * sizeof(double)));
+                LSA_HIP_ALLOC(ctx, hipMalloc((void**)&k->tail_parts, (size_t)slots * 2 * (size_t)k->tail_nparts * sizeof(double)));
             }
             for (int32_t s = 0; s < nb; ++s) {
-                int rc = krylov_enqueue_step(ctx, k, j + s, s, tail);
+                int rc = delayed ? krylov_enqueue_dstep(ctx, k, j + s, s, tail, s == 0 && !pending) : krylov_enqueue_step(ctx, k, j + s, s, tail);
                 if (rc != LSA_OK) {
                     (void)hipStreamSynchronize(ctx->stream);
                     op->st.seconds_solve += now_s() - t0;
@@ -1056,14 +1150,28 @@ int lsa_krylov_extend(lsa_ctx* ctx, lsa_krylov* k, int32_t j0, int32_t j1, void*
             if (tail) LSA_CHECK(k_cgs2_tail_checks(ctx, nb, k->tail_nparts, k->tail_parts, k->checks));
             char* host = (char*)ctx->pinned;
             LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, k->Hdev, (size_t)nb * colb, hipMemcpyDeviceToHost, ctx->stream));
-            LSA_HIP_CHECK(ctx, hipMemcpyAsync(host + (size_t)k->batch * colb, k->checks, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            LSA_HIP_CHECK(ctx, hipMemcpyAsync(host + (size_t)slots * colb, k->checks, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             const double tw = now_s();
             LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
             static const bool timing = getenv("LSA_KRYLOV_TIMING") != nullptr;
             if (timing) fprintf(stderr, "[lsa_krylov] %d steps queued in %.3f ms, waited %.3f ms\n", nb, 1e3 * (tw - tq), 1e3 * (now_s() - tw));
-            const double* chk = (const double*)(host + (size_t)k->batch * colb);
+            const double* chk = (const double*)(host + (size_t)slots * colb);
             int32_t accepted = 0;
             for (int32_t s = 0; s < nb; ++s, ++accepted) {
+                const cplx* hc = (const cplx*)(host + (size_t)s * colb);
+                const bool first = s == 0 && !pending;
+                if (delayed && !first) {
+                    // the step's a and nu depend on V alone, not on its solve: they finish column j + s - 1 and V[:, j + s] even
+                    // when this step is cut below (it is queued again with V[:, j + s] final)
+                    pending = false;
+                    const int what = finish_column(j + s, hc);
+                    if (what != 0) {
+                        op->st.seconds_solve += now_s() - t0;
+                        if (what < 0) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "Arnoldi: non-finite norm at step %d", j + s - 1);
+                        if (breakdown) *breakdown = j + s - 1;
+                        return LSA_OK;
+                    }
+                }
                 const double beta0 = std::sqrt(chk[2 * s]), bnorm = std::sqrt(chk[2 * s + 1]);
                 if (!(beta0 <= rtol * bnorm)) {
                     if (!op->refine && std::isfinite(beta0)) {
@@ -1077,15 +1185,20 @@ int lsa_krylov_extend(lsa_ctx* ctx, lsa_krylov* k, int32_t j0, int32_t j1, void*
                     k->pipeline = false;
                     break;
                 }
-                const cplx* hc = (const cplx*)(host + (size_t)s * colb);
-                for (int32_t i = 0; i <= j + s + 1; ++i) k->hcol[i] = zc(hc[i].re, hc[i].im);
                 ++op->st.op_applies;
                 op->st.spmv_calls += (op->Kmul ? 2 : 1) + (op->refine ? 1 : 0);
                 op->st.sptrsv_calls += op->refine ? 4 : 2;
                 if (op->refine) ++op->st.refined_solves;
                 op->st.last_rel_res = bnorm > 0.0 ? beta0 / bnorm : 0.0;
                 op->st.max_rel_res = std::max(op->st.max_rel_res, op->st.last_rel_res);
-                const int what = take_column(j + s, k->hcol.data());
+                int what;
+                if (delayed) {
+                    what = provisional_column(j + s, hc, first);
+                    pending = true;
+                } else {
+                    for (int32_t i = 0; i <= j + s + 1; ++i) k->hcol[i] = zc(hc[i].re, hc[i].im);
+                    what = take_column(j + s, k->hcol.data());
+                }
                 if (what < 0) {
                     op->st.seconds_solve += now_s() - t0;
                     return lsa_set_error(ctx, LSA_ERR_NONFINITE, "Arnoldi: non-finite norm at step %d", j + s);
@@ -1098,6 +1211,19 @@ int lsa_krylov_extend(lsa_ctx* ctx, lsa_krylov* k, int32_t j0, int32_t j1, void*
             }
             j += accepted;
             if (accepted < nb) k->t_for = -1;  // the steps behind the one that stopped the batch ran on; t is theirs
+        }
+        if (pending) {
+            // the flush: the reduction and the update without a solve make V[:, j1] and column j1 - 1 final, so that the restart,
+            // the Ritz vectors and the next call see what CGS2 leaves
+            LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, nullptr, 0, k->Hdev, k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
+            char* host = (char*)ctx->pinned;
+            LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, k->Hdev, colb, hipMemcpyDeviceToHost, ctx->stream));
+            LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+            const int what = finish_column(j, (const cplx*)host);
+            op->st.seconds_solve += now_s() - t0;
+            if (what < 0) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "Arnoldi: non-finite norm at step %d", j - 1);
+            if (what > 0 && breakdown) *breakdown = j - 1;
+            return LSA_OK;
         }
     }
     k->t_for = -1;
