@@ -214,6 +214,11 @@ int lsa_ndlu_refactor(lsa_ctx *ctx, lsa_ndlu *f, const lsa_mat *C);
 void lsa_ndlu_destroy(lsa_ndlu *f);
 /* x = C^-1 b */
 int lsa_ndlu_solve(lsa_ctx *ctx, lsa_ndlu *f, const lsa_vec *b, lsa_vec *x);
+/* x[z] = C_z^-1 b[z], z < J <= 16, for J factorisations of one analysis (one pattern, made by lsa_ndlu_create or
+ * lsa_ndlu_create_tree in this context on one rank): one launch per tree level and direction for the whole batch, and each x[z]
+ * holds exactly the bits lsa_ndlu_solve(f[z], b[z]) gives.  Factorisations of different analyses, or two problems sharing a
+ * factorisation or an output: LSA_ERR_ARG. */
+int lsa_ndlu_solve_batch(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, const lsa_vec *const *b, lsa_vec *const *x);
 /* x = C^-T b (conj = 0) or C^-H b (conj != 0) on the same factors: the sweeps of the transposed forest.  The adjoint
  * eigenproblem (Sensitivity/__init__.py:47-57,247-287 forms A^H, M^H explicitly and factorises again) needs no second
  * factorisation and no transposed matrix. */

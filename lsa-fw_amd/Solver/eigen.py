@@ -131,3 +131,53 @@ class EigenSolver:
         pairs = list(self._solver.get_all_eigenpairs_up_to(cfg.num_eig))
         logger.info("Retrieved %d eigenpairs", len(pairs))
         return pairs
+
+
+def solve_batch(solvers, *, max_batch: int = 8) -> list[list[tuple[float | complex, iComplexPETScVector]]]:
+    """Solve several :class:`EigenSolver` s built as for ``.solve()`` (a parameter sweep on one mesh) and return what each
+    ``.solve()`` returns, in order.  Every solver is left as ``.solve()`` leaves it (``get_eigenvalue``,
+    ``get_eigenvector``, ``residuals()``, ``stats``).
+
+    Solvers with one sparsity pattern and one configuration apart from the target (shift-invert with the exact LU, one
+    GPU, forward problem, no projection, the same real or complex factor type: :func:`Solver.batch.plan_batches`) form
+    groups of at most ``max_batch``: a group shares one context, one fill-reducing ordering, one pattern-only analysis of
+    the LU and its index tables (pattern-keyed reuse); each problem then runs its own numeric factorisation and
+    Krylov-Schur iteration, one problem after another, and returns exactly the bits of a solo solve.
+    ``stats["shared_analysis"]`` says whether a solver took the group path (``stats["batch_size"]``: its group's size);
+    every other solver is solved alone (one log line says why)."""
+    from .batch import plan_batches
+    from .utils import SharedContext
+
+    solvers = list(solvers)
+    if not solvers:
+        raise ValueError("solve_batch needs at least one solver")
+    for s in solvers:
+        if not isinstance(s, EigenSolver):
+            raise TypeError(f"solve_batch takes EigenSolver objects, got {type(s).__name__}")
+    if len({id(s) for s in solvers}) != len(solvers):
+        raise ValueError("solve_batch: a solver appears more than once")
+    plan = plan_batches([s.solver for s in solvers], max_batch)
+    results: list = [None] * len(solvers)
+    for group in plan.groups:
+        lead = solvers[group[0]].solver
+        lead.prepare()
+        prep = lead._prepared
+        if prep.get("share") is None:
+            prep["share"] = SharedContext()
+        for i in group[1:]:
+            solvers[i].solver.prepare(_share=prep)
+        logger.info("Group of %d eigenproblems on one pattern: one context, ordering and LU analysis", len(group))
+        prev = None
+        for i in group:
+            eps = solvers[i].solver
+            if prev is not None and prev.stats.get("analysis_reused") != 1:
+                # the previous factorisation did not run on the group's analysis: the context holds another one now
+                eps.redo_pattern_phase()
+            results[i] = solvers[i].solve()
+            eps._stats.update({"shared_analysis": True, "batch_size": len(group)})
+            prev = eps
+    for i, reason in sorted(plan.alone.items()):
+        logger.info("Eigenproblem %d is solved alone: %s", i, reason)
+        results[i] = solvers[i].solve()
+        solvers[i].solver._stats.update({"shared_analysis": False, "batch_size": 1})
+    return results

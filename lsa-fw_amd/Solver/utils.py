@@ -412,11 +412,14 @@ class iEpsSolver:
         # real <-> complex factors are different scalar types on the device (lsa_ndlu_prepare)
         return (complex(old[3]).imag != 0.0) == (complex(self._target).imag != 0.0)
 
-    def prepare(self) -> None:
+    def prepare(self, _share: dict | None = None) -> None:
         """Host-side analysis + upload: shared pattern, fill-reducing / pivot-safe ordering, CSR -> HBM.
 
         ``solve()`` calls this on demand; calling it first keeps file I/O, ordering and the PCIe upload out of a timed
-        ``solve()`` (the metric of BASELINE.json counts factorisation + iteration, not upload)."""
+        ``solve()`` (the metric of BASELINE.json counts factorisation + iteration, not upload).
+
+        ``_share``: the prepared state of another solver of the same batch group (:func:`Solver.eigen.solve_batch`: same
+        pattern, same configuration): its context, ordering and pattern-only LU analysis are taken instead of made again."""
         import lsa_hip
 
         if self._A is None:
@@ -464,7 +467,7 @@ class iEpsSolver:
             if Kc.nnz > 60 * n:
                 zd = Kc.diagonal() == 0
                 zero_diag = zd if zd.any() else None
-            nd_tree = lsa_hip.nd_order(Kc, 0, constraint=zero_diag)
+            nd_tree = lsa_hip.nd_order(Kc, 0, constraint=zero_diag) if _share is None else _share["nd_tree"]
             perm = nd_tree["perm"]
         elif self._ordering == "rcm" and n > 8 and pc_code >= 1 and K is not None:
             perm = pivot_safe_rcm(sp.csr_matrix(K))
@@ -472,7 +475,11 @@ class iEpsSolver:
             perm = np.arange(n)
         Ap = _permute(A, perm)
         Mp = None if M is None else _permute(M, perm)
-        ctx = lsa_hip.Context(self._device)
+        ctx = lsa_hip.Context(self._device) if _share is None else _share["ctx"]
+        share = None
+        if _share is not None:
+            share = _share["share"]
+            share.users += 1
         part = dAd = dMd = forest = None
         world = _dist_rank_world()[1] if self._layout == "sharded" else 1
         if self._layout == "sharded" and world > 1 and pc_code == 2 and sinvert:
@@ -515,11 +522,12 @@ class iEpsSolver:
         else:
             dA = lsa_hip.CsrMatrix.from_scipy(ctx, Ap)
             dM = None if Mp is None else lsa_hip.CsrMatrix.from_scipy(ctx, Mp)
-        if pc_code == 2 and K is not None and forest is None:
-            # pattern-only phase of the nested-dissection LU (elimination forest, index tables, memory plan, buffers) for the
-            # scalar type the library will give C = A - sigma M (lsa_op_create): complex only for a complex shift or complex
-            # operators (K above is complex whenever the target was stored as a Python complex)
-            cplx_factors = A.dtype.kind == "c" or (M is not None and M.dtype.kind == "c") or (sinvert and complex(sigma).imag != 0.0)
+        # the scalar type the library will give C = A - sigma M (lsa_op_create): complex only for a complex shift or complex
+        # operators (K above is complex whenever the target was stored as a Python complex)
+        cplx_factors = A.dtype.kind == "c" or (M is not None and M.dtype.kind == "c") or (sinvert and complex(sigma).imag != 0.0)
+        if pc_code == 2 and K is not None and forest is None and _share is None:
+            # pattern-only phase of the nested-dissection LU (elimination forest, index tables, memory plan, buffers) for that
+            # scalar type
             fac = dAd if dAd is not None else dA
             try:
                 if nd_tree is not None and dAd is None:
@@ -540,7 +548,25 @@ class iEpsSolver:
         self._prepared = {"sig": self._signature(), "ctx": ctx, "dA": dA, "dM": dM, "dAd": dAd, "dMd": dMd, "part": part, "perm": perm,
                           "forest": forest,
                           "n": n, "sinvert": sinvert, "cayley": self._st_type is iSTType.CAYLEY, "sigma": sigma, "pc_code": pc_code,
-                          "levels": levels}
+                          "levels": levels, "nd_tree": nd_tree, "share": share, "cplx_factors": cplx_factors}
+
+    def redo_pattern_phase(self) -> None:
+        """The pattern-only LU phase of :meth:`prepare` again, from the shared forest, for a member of a batch group that took
+        its context from another: when the previous member's factorisation did not run on the group's analysis (a zero pivot
+        made the library analyse again with constraints), the analysis it left in the context is not the one this problem's
+        solo solve would use."""
+        import lsa_hip
+
+        prep = self._prepared
+        if prep is None or prep["nd_tree"] is None or prep["share"] is None:
+            return
+        nd_tree = prep["nd_tree"]
+        try:
+            prep["dA"].prepare_lu_tree(prep["cplx_factors"], nd_tree["first"], nd_tree["size"], nd_tree["parent"])
+        except lsa_hip.LsaError as exc:  # (as in prepare: the operator build falls back to ILU(k) + GMRES)
+            if exc.status != lsa_hip.LSA_ERR_OOM:
+                raise
+            logger.warning("The exact LU does not fit the device memory (%s); the solve will fall back to ILU(k) + GMRES.", exc)
 
     def release(self) -> None:
         """Free the device copies made by :meth:`prepare`."""
@@ -549,11 +575,13 @@ class iEpsSolver:
         self._comm_seen = {"allgather_calls": 0, "allgather_bytes_received": 0}  # counters live in the context
         if prep is not None:
             ctx = prep.pop("ctx")
+            share = prep.pop("share", None)
             prep.clear()
             import gc
 
             gc.collect()  # matrix handles hold device memory; they must go before the context
-            ctx.close()
+            if share is None or share.drop():  # (a context shared by a batch group goes with its last user)
+                ctx.close()
 
     def __del__(self):
         try:
@@ -949,6 +977,17 @@ class iEpsSolver:
     def stats(self) -> dict:
         """Counters of the last solve (outer applies, inner iterations, kernel launches, factor/solve seconds)."""
         return dict(self._stats)
+
+
+class SharedContext:
+    """Users of one context prepared for a batch group (:func:`Solver.eigen.solve_batch`); the last to release it closes it."""
+
+    def __init__(self) -> None:
+        self.users = 1
+
+    def drop(self) -> bool:
+        self.users -= 1
+        return self.users == 0
 
 
 def _restart_length(requested: int, n: int, budget_bytes: float = 48e9) -> int:

@@ -1294,6 +1294,45 @@ __global__ __launch_bounds__(256) void nd_bwd_kernel(const NdSweepNode* __restri
     nd_bwd_tile<MT, VT, LPR, ORDERED>(nd, r0, (int32_t)blockIdx.y, vs, ufac, idx, gell, x, xb);
 }
 
+// ---- batched sweeps: J factorisations of one analysis (lsa_ndlu_solve_batch).  The tables are shared, factors and vectors come
+// per problem, by value in the kernel arguments (blockIdx.z picks them: a uniform load from the argument segment); every problem
+// runs the solo kernels' grid and tiles, so it gets their bits.
+constexpr int kNdBatchMax = 16;
+struct NdBatchPtrs {
+    const void* lfac[kNdBatchMax];
+    const void* ufac[kNdBatchMax];
+    const void* rhs[kNdBatchMax];
+    void* x[kNdBatchMax];
+    void* ubuf[kNdBatchMax];
+    void* acc[kNdBatchMax];
+    void* xb[kNdBatchMax];
+};
+
+// upward sweep, one tree level: workgroup (x = node of the level, y = tile, z = problem)
+template <typename MT, typename VT, int LPR, bool ORDERED>
+__global__ __launch_bounds__(256) void nd_fwd_batch_kernel(const NdSweepNode* __restrict__ lnodes, const int32_t* __restrict__ idx,
+                                                           const int32_t* __restrict__ gell, const int32_t* __restrict__ cmap, NdBatchPtrs p) {
+    __shared__ VT vs[kCH];
+    const NdSweepNode nd = lnodes[blockIdx.x];
+    const int32_t r0 = (int32_t)blockIdx.y * (512 / LPR);
+    if (r0 >= nd.orows + nd.brow) return;
+    const int z = blockIdx.z;
+    nd_fwd_tile<MT, VT, LPR, ORDERED>(nd, r0, vs, (const MT*)p.lfac[z], idx, gell, cmap, (const VT*)p.rhs[z], (VT*)p.x[z], (VT*)p.ubuf[z], (VT*)p.acc[z],
+                                      (VT*)p.xb[z]);
+}
+
+// downward sweep, one tree level: (node, tile, problem)
+template <typename MT, typename VT, int LPR, bool ORDERED>
+__global__ __launch_bounds__(256) void nd_bwd_batch_kernel(const NdSweepNode* __restrict__ lnodes, const int32_t* __restrict__ idx,
+                                                           const int32_t* __restrict__ gell, NdBatchPtrs p) {
+    __shared__ VT vs[kCH];
+    const NdSweepNode nd = lnodes[blockIdx.x];
+    const int32_t r0 = (int32_t)blockIdx.y * (512 / LPR);
+    if (r0 >= nd.m || nd.f == nd.m) return;
+    const int z = blockIdx.z;
+    nd_bwd_tile<MT, VT, LPR, ORDERED>(nd, r0, (int32_t)blockIdx.y, vs, (const MT*)p.ufac[z], idx, gell, (VT*)p.x[z], (VT*)p.xb[z]);
+}
+
 // ---- downward sweep of DISTRIBUTED top nodes: a rank finishes its slice of the node's own rows (nd_bwd_kernel on a record
 // that describes the slice), the slices are exchanged through the own-row buffer (pack, one in-place all-gather per level), and
 // this kernel completes x and fills the boundary vectors of the node's children: entry k of child c's boundary is the parent's
@@ -2219,6 +2258,75 @@ int nd_apply(lsa_ctx* ctx, lsa_ndlu* f, const VT* b, VT* x) {
     return f->ordered ? nd_apply_ordered<MT, VT, true>(ctx, f, b, x) : nd_apply_ordered<MT, VT, false>(ctx, f, b, x);
 }
 
+// x_z = C_z^-1 b_z for J factorisations of one analysis (checked by nd_batch_compatible): the level loop of nd_apply_ordered,
+// one launch per level and direction for the whole batch, the tables of f[0]
+template <typename MT, typename VT, bool ORDERED>
+int nd_apply_batch_ordered(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const VT* const* b, VT* const* x) {
+    hipStream_t st = ctx->stream;
+    const lsa_ndlu* f0 = f[0];
+    NdBatchPtrs p;
+    memset(&p, 0, sizeof p);
+    for (int32_t z = 0; z < J; ++z) {
+        if (f[z]->acc_vbytes != (int)sizeof(VT)) {  // as nd_apply_ordered: entries no child writes must read zero
+            LSA_HIP_CHECK(ctx, hipMemsetAsync(f[z]->d_acc, 0, (size_t)std::max<int64_t>(f[z]->acc_entries, 1) * 16, st));
+            f[z]->acc_vbytes = (int)sizeof(VT);
+        }
+        p.lfac[z] = f[z]->d_lfac;
+        p.ufac[z] = f[z]->d_ufac;
+        p.rhs[z] = b[z];
+        p.x[z] = x[z];
+        p.ubuf[z] = f[z]->d_ubuf;
+        p.acc[z] = f[z]->d_acc;
+        p.xb[z] = f[z]->d_xb;
+    }
+    for (const NdLevel& L : f0->levels) {
+        if (L.fwd_tiles == 0) continue;
+        const dim3 grid(L.node_count, L.fwd_tiles, J);
+        const NdSweepNode* ln = f0->d_lnodes + L.node_begin;
+        if (L.sweep_rows == 8)
+            hipLaunchKernelGGL((nd_fwd_batch_kernel<MT, VT, 64, ORDERED>), grid, dim3(256), 0, st, ln, f0->d_idx, f0->d_gell, f0->d_cmap, p);
+        else if (L.sweep_rows == 128)
+            hipLaunchKernelGGL((nd_fwd_batch_kernel<MT, VT, 4, ORDERED>), grid, dim3(256), 0, st, ln, f0->d_idx, f0->d_gell, f0->d_cmap, p);
+        else
+            hipLaunchKernelGGL((nd_fwd_batch_kernel<MT, VT, 16, ORDERED>), grid, dim3(256), 0, st, ln, f0->d_idx, f0->d_gell, f0->d_cmap, p);
+    }
+    for (size_t l = f0->levels.size(); l-- > 0;) {
+        const NdLevel& L = f0->levels[l];
+        if (L.bwd_tiles == 0) continue;
+        const dim3 grid(L.node_count, L.bwd_tiles, J);
+        const NdSweepNode* ln = f0->d_lnodes_bwd + L.node_begin;
+        if (L.sweep_rows == 8) hipLaunchKernelGGL((nd_bwd_batch_kernel<MT, VT, 64, ORDERED>), grid, dim3(256), 0, st, ln, f0->d_idx, f0->d_gell, p);
+        else hipLaunchKernelGGL((nd_bwd_batch_kernel<MT, VT, 16, ORDERED>), grid, dim3(256), 0, st, ln, f0->d_idx, f0->d_gell, p);
+    }
+    LSA_HIP_CHECK(ctx, hipGetLastError());
+    return LSA_OK;
+}
+
+template <typename MT, typename VT>
+int nd_apply_batch(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const VT* const* b, VT* const* x) {
+    return f[0]->ordered ? nd_apply_batch_ordered<MT, VT, true>(ctx, J, f, b, x) : nd_apply_batch_ordered<MT, VT, false>(ctx, J, f, b, x);
+}
+
+// g can run in a batch with f: one rank, no distributed nodes, and the same analysis (pattern, constraints, forest or leaf size,
+// memory plan, sweep levels), so that f's tables address g's factors and buffers as g's own do
+bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g) {
+    const NdSymbolic &A = f->S, &B = g->S;
+    if (A.nranks != 1 || B.nranks != 1 || A.has_dist || B.has_dist) return false;
+    if (f->dtype != g->dtype || f->ordered != g->ordered || A.n != B.n || A.nnz != B.nnz || A.pattern_hash != B.pattern_hash ||
+        A.constraint_hash != B.constraint_hash || A.tree_hash != B.tree_hash || A.leaf_size != B.leaf_size)
+        return false;
+    if (f->lfac_entries != g->lfac_entries || f->ufac_entries != g->ufac_entries || f->acc_entries != g->acc_entries || f->h_lfac_off != g->h_lfac_off ||
+        f->h_upd_off != g->h_upd_off || A.lvl_nodes != B.lvl_nodes || f->levels.size() != g->levels.size())
+        return false;
+    for (size_t l = 0; l < f->levels.size(); ++l) {
+        const NdLevel &a = f->levels[l], &c = g->levels[l];
+        if (a.node_begin != c.node_begin || a.node_count != c.node_count || a.fwd_tiles != c.fwd_tiles || a.bwd_tiles != c.bwd_tiles ||
+            a.sweep_rows != c.sweep_rows || a.dist_count != 0 || c.dist_count != 0)
+            return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 namespace {
@@ -2597,6 +2705,42 @@ int lsa_ndlu_solve(lsa_ctx* ctx, lsa_ndlu* f, const lsa_vec* b, lsa_vec* x) {
     if (!ctx || !f || !b || !x) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve: null argument");
     if (b->n != f->S.n || x->n != f->S.n || b->dtype != x->dtype) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve: shape/dtype mismatch");
     LSA_CHECK(ndlu_solve_dev(ctx, f, b->dtype, b->d, x->d));
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return LSA_OK;
+}
+
+int lsa_ndlu_solve_batch(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const lsa_vec* const* b, lsa_vec* const* x) {
+    if (!ctx || !f || !b || !x) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: null argument");
+    if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: J = %d outside [1, %d]", J, kNdBatchMax);
+    for (int32_t z = 0; z < J; ++z) {
+        if (!f[z] || !b[z] || !x[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: null argument (problem %d)", z);
+        if (b[z]->n != f[z]->S.n || x[z]->n != f[z]->S.n || b[z]->dtype != x[z]->dtype || x[z]->dtype != x[0]->dtype)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: shape/dtype mismatch (problem %d)", z);
+        if (f[z]->dtype == LSA_C128 && x[z]->dtype != LSA_C128)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: complex factors need complex vectors");
+        if (!nd_batch_compatible(f[0], f[z]))
+            return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: factorisation %d is not of the same analysis as factorisation 0", z);
+        for (int32_t y = 0; y < z; ++y)
+            if (f[y] == f[z] || x[y]->d == x[z]->d || x[y]->d == b[z]->d || b[y]->d == x[z]->d)
+                return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: problems %d and %d share a factorisation or an output", y, z);
+    }
+    if (f[0]->S.n == 0) return LSA_OK;
+    const int vdtype = x[0]->dtype;
+    std::vector<const void*> bd((size_t)J);
+    std::vector<void*> xd((size_t)J);
+    for (int32_t z = 0; z < J; ++z) {
+        bd[(size_t)z] = b[z]->d;
+        xd[(size_t)z] = x[z]->d;
+        if (bd[(size_t)z] == xd[(size_t)z]) {  // an aliased right-hand side is copied first, into the problem's own buffer
+            LSA_HIP_CHECK(ctx, hipMemcpyAsync(f[z]->d_tmp, bd[(size_t)z], (size_t)f[z]->S.n * esize(vdtype), hipMemcpyDeviceToDevice, ctx->stream));
+            bd[(size_t)z] = f[z]->d_tmp;
+        }
+    }
+    int rc;
+    if (f[0]->dtype == LSA_C128) rc = nd_apply_batch<cplx, cplx>(ctx, J, f, (const cplx* const*)bd.data(), (cplx* const*)xd.data());
+    else if (vdtype == LSA_C128) rc = nd_apply_batch<double, cplx>(ctx, J, f, (const cplx* const*)bd.data(), (cplx* const*)xd.data());
+    else rc = nd_apply_batch<double, double>(ctx, J, f, (const double* const*)bd.data(), (double* const*)xd.data());
+    LSA_CHECK(rc);
     LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return LSA_OK;
 }

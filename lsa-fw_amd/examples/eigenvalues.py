@@ -21,7 +21,7 @@ ROOT = Path(__file__).resolve().parents[2]
 sys.path[:0] = [str(ROOT / "lsa-fw_amd")]
 
 from FEM.utils import iPETScMatrix  # noqa: E402
-from Solver.eigen import EigenSolver, EigensolverConfig  # noqa: E402
+from Solver.eigen import EigenSolver, EigensolverConfig, solve_batch  # noqa: E402
 from Solver.utils import PreconditionerType, iSTType  # noqa: E402
 
 _SAVE_DIR: Final[Path] = Path("cases") / "cylinder"
@@ -60,10 +60,8 @@ def synthesize(save_dir: Path, case: str) -> None:
         iPETScMatrix(es.M).export(mat_dir / "M.mtx")
 
 
-def solve_case(save_dir: Path, re: float, target: complex) -> Path | None:
-    """One Reynolds number of the sweep: read the MatrixMarket pair, shift-invert at the tabulated target with the exact LU
-    as inner solver, store the selected eigenvalue as ``"<real> <imag>"`` (the call sequence of the reference's loop body,
-    ``.examples/eigenvalues.py:61-107``; same file names and output format, so its post-processing reads these results)."""
+def build_case(save_dir: Path, re: float, target: complex) -> EigenSolver | None:
+    """The solver of one Reynolds number, configured as the reference's loop body does; None when its matrices are absent."""
     root = save_dir / f"reynolds_{re:.1f}"
     files = {name: root / "matrices" / f"{name}.mtx" for name in ("A", "M")}
     absent = [str(path) for path in files.values() if not path.exists()]
@@ -82,13 +80,46 @@ def solve_case(save_dir: Path, re: float, target: complex) -> Path | None:
     eps.set_st_type(iSTType.SINVERT)
     eps.set_target(target)
     eps.set_st_pc_type(PreconditionerType.LU)
-    eps.solve()
+    return eigensolver
+
+
+def write_result(save_dir: Path, re: float, target: complex, eps) -> Path:
+    """Store the selected eigenvalue of a solved case as ``"<real> <imag>"``."""
+    root = save_dir / f"reynolds_{re:.1f}"
     value = eps.get_eigenvalue(_EIG_INDEX)
     result_file = root / f"sigma_eig{_EIG_INDEX}.txt"
     result_file.write_text(f"{value.real} {value.imag}\n", encoding="utf-8")
     logger.info("Re %.1f: eigenvalue %d nearest %s is %s -> %s", re, _EIG_INDEX, target, value, result_file)
+    return result_file
+
+
+def solve_case(save_dir: Path, re: float, target: complex) -> Path | None:
+    """One Reynolds number of the sweep: read the MatrixMarket pair, shift-invert at the tabulated target with the exact LU
+    as inner solver, store the selected eigenvalue as ``"<real> <imag>"`` (the call sequence of the reference's loop body,
+    ``.examples/eigenvalues.py:61-107``; same file names and output format, so its post-processing reads these results)."""
+    eigensolver = build_case(save_dir, re, target)
+    if eigensolver is None:
+        return None
+    eps = eigensolver.solver
+    eps.solve()
+    result_file = write_result(save_dir, re, target, eps)
     eps.release()
     return result_file
+
+
+def solve_cases_batched(save_dir: Path, cases: list[tuple[float, complex]], batch: int) -> None:
+    """The sweep in groups of ``batch`` Reynolds numbers (Solver.eigen.solve_batch: one context, ordering and LU analysis per
+    group); the same result files as one case at a time."""
+    for g0 in range(0, len(cases), batch):
+        group = [(re, target, build_case(save_dir, re, target)) for re, target in cases[g0:g0 + batch]]
+        group = [c for c in group if c[2] is not None]
+        if not group:
+            continue
+        solve_batch([es for _, _, es in group], max_batch=batch)
+        for re, target, es in group:
+            write_result(save_dir, re, target, es.solver)
+        for _, _, es in group:
+            es.solver.release()
 
 
 def main(argv: list[str] | None = None) -> None:
@@ -101,6 +132,9 @@ def main(argv: list[str] | None = None) -> None:
                          "1.5x, three 2x the eigenpairs per second; four oversubscribe the hardware queues and fall back "
                          "below two (DESIGN.md section 6).  The host-side loading and ordering of one case hides behind the "
                          "GPU work of the others.")
+    ap.add_argument("--batch", type=int, default=0, metavar="J",
+                    help="solve the Reynolds numbers in groups of J (1 <= J <= 16) that share one context, ordering and LU "
+                         "analysis (Solver.eigen.solve_batch); the same files as one case at a time")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     if args.synthesize:
@@ -109,7 +143,11 @@ def main(argv: list[str] | None = None) -> None:
     import os
 
     os.environ.setdefault("LSA_HOST_BLAS_THREADS", "1")  # this script owns its process: keep spinning BLAS workers off the launch path
-    if args.jobs <= 1:
+    if args.batch:
+        if not 1 <= args.batch <= 16:
+            ap.error("--batch takes a group size from 1 to 16")
+        solve_cases_batched(args.save_dir, cases, args.batch)
+    elif args.jobs <= 1:
         for re, target in cases:
             solve_case(args.save_dir, re, target)
     else:

@@ -152,6 +152,7 @@ SIGNATURES = {
     "lsa_ndlu_refactor": (ctypes.c_int, [_P, _P, _P]),
     "lsa_ndlu_destroy": (None, [_P]),
     "lsa_ndlu_solve": (ctypes.c_int, [_P, _P, _P, _P]),
+    "lsa_ndlu_solve_batch": (ctypes.c_int, [_P, _I32, _PP, _PP, _PP]),
     "lsa_ndlu_solve_adjoint": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P]),
     "lsa_ndlu_solve_time": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.POINTER(_DBL)]),
     "lsa_ndlu_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64),
@@ -629,6 +630,9 @@ def nd_order(A, leaf_size: int = 0, constraint=None) -> dict:
             "parent": ex["parent"], "level": ex["level"]}
 
 
+NDLU_BATCH_MAX = 16  # factorisations of one lsa_ndlu_solve_batch call (kNdBatchMax in csrc/ndlu.hip)
+
+
 class NdLu:
     """Nested-dissection multifrontal LU of a CSR matrix, resident on the device (``lsa_ndlu_*``)."""
 
@@ -662,6 +666,21 @@ class NdLu:
 
     def solve(self, b: DeviceVector, x: DeviceVector) -> None:
         self.ctx.check(self.ctx._lib.lsa_ndlu_solve(self.ctx.handle, self.handle, b.handle, x.handle))
+
+    @staticmethod
+    def solve_batch(factors: "list[NdLu]", bs: "list[DeviceVector]", xs: "list[DeviceVector]") -> None:
+        """``xs[z] = C_z^-1 bs[z]`` for up to 16 factorisations of one analysis in one context (``lsa_ndlu_solve_batch``): one
+        launch per tree level and direction for the whole batch, each result bit-identical to :meth:`solve`."""
+        J = len(factors)
+        if J == 0 or len(bs) != J or len(xs) != J:
+            raise ValueError("solve_batch needs as many right-hand sides and outputs as factorisations (at least one)")
+        if J > NDLU_BATCH_MAX:
+            raise ValueError(f"solve_batch takes at most {NDLU_BATCH_MAX} factorisations, got {J}")
+        ctx = factors[0].ctx
+        if any(f.ctx is not ctx for f in factors) or any(v.ctx is not ctx for v in list(bs) + list(xs)):
+            raise ValueError("solve_batch: the factorisations and vectors must live in one context")
+        arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
+        ctx.check(ctx._lib.lsa_ndlu_solve_batch(ctx.handle, J, arr(factors), arr(bs), arr(xs)))
 
     def solve_adjoint(self, b: DeviceVector, x: DeviceVector, conj: bool = True) -> None:
         """x = C^-H b (``conj``) or C^-T b on the same factors."""
