@@ -378,6 +378,43 @@ int lsa_dense_sym_inertia(int32_t n, const double *A, int32_t lda, double tol_re
 int lsa_dense_schur_reorder(int32_t n, void *T, int32_t ldt, void *Q, int32_t ldq, const int32_t *select, int32_t *nselected);
 int lsa_dense_tri_eigenvectors(int32_t n, const void *T, int32_t ldt, void *S, int32_t lds);
 
+/* ---- symmetric-definite problems: SLEPc EPS Krylov-Schur, symmetric variant with B-inner product (EPS_GHEP / EPS_HEP,
+ * Solver/utils.py:244-270 with iEpsProblemType.GHEP; Elasticity/utils.py:141-155) -------------------------------------------------
+ * Thick-restart Lanczos for OP = (K - sigma M)^-1 M, sigma real, which is self-adjoint in the M-inner product.  Everything on the
+ * device is float64: a real basis V with V^T M V = I, a real symmetric projected matrix, real eigenvalues, M-orthonormal vectors.
+ * The operator handle is the one of the general path (lsa_op_create, mode 0); its factors must be real and exact (pc_type 2). */
+typedef struct lsa_lanczos lsa_lanczos;   /* SLEPc EPS Krylov-Schur, symmetric variant with B-inner product (GHEP) */
+/* Basis of ncv + 1 real vectors (SLEPc.BV with BVSetMatrix(M)).  LSA_ERR_ARG unless the operator is shift-invert with real
+ * exact factors, forward, unprojected, on one rank. */
+int lsa_lanczos_create(lsa_ctx *ctx, lsa_op *op, int32_t ncv, lsa_lanczos **out);
+void lsa_lanczos_destroy(lsa_lanczos *l);
+/* as lsa_krylov_set_row_permutation: the vectors of lsa_lanczos_solve leave in the caller's numbering */
+int lsa_lanczos_set_row_permutation(lsa_ctx *ctx, lsa_lanczos *l, const int32_t *perm);
+/* v_0 = v / sqrt(v^T M v) (host real vector of length n), M-normalised on the device (BVInsertVec + BVNormColumn);
+ * LSA_ERR_ARG when v^T M v is not positive */
+int lsa_lanczos_set_start(lsa_ctx *ctx, lsa_lanczos *l, const double *host_v);
+/* Lanczos steps j = j0 .. j1-1 (EPSFullLanczos / BVOrthogonalize with the B-inner product): w = OP v_j, two passes of classical
+ * Gram-Schmidt against v_0..v_j in the M-inner product, v_{j+1} = w / beta_j.  T is the caller's (ncv+1) x ncv column-major real
+ * matrix (ldt >= j1 + 1): T[j, j] = alpha_j, T[j+1, j] = beta_j and, for j + 1 < ncv, T[j, j+1] = beta_j are written; every other
+ * entry is the caller's.  *breakdown = step index if beta_j vanished (invariant subspace), else -1.  LSA_ERR_ARG when w^T M w is
+ * not positive (M is not positive definite on the Krylov space), LSA_ERR_DIVERGED when an inner solve misses the operator's
+ * ksp_rtol after one refinement step. */
+int lsa_lanczos_extend(lsa_ctx *ctx, lsa_lanczos *l, int32_t j0, int32_t j1, double *T, int32_t ldt, int32_t *breakdown);
+/* the first ncols columns of the basis, in the basis' own row numbering (n x ncols column-major on the host); for tests (BVGetColumn) */
+int lsa_lanczos_basis(lsa_ctx *ctx, const lsa_lanczos *l, int32_t ncols, double *host_V);
+/* The whole iteration (SLEPc.EPS.solve() with EPS_GHEP): expand to ncv vectors, eigen-decomposition of the projected matrix
+ * (lsa_dense_syev), Ritz values ranked by opts->which on lambda = sigma + 1/theta, residual estimates |beta y_mi| / |theta_i|
+ * against opts->tol, thick restart with nconv + (m - nconv) keep_fraction vectors.  opts->transform must be 0 and the imaginary
+ * parts of sigma and target 0.  v0: host start vector (n doubles) or NULL (random from opts->seed).  Outputs, wanted first:
+ * theta_out / lambda_out[max_out] (real), X_out (n x max_out real column-major, x^T M x = 1, the entry of largest magnitude
+ * positive; NULL: no vectors), est_out[max_out].  Returns LSA_OK also when fewer than nev pairs converged (see result). */
+int lsa_lanczos_solve(lsa_ctx *ctx, lsa_lanczos *l, const lsa_ks_options *opts, const double *v0, int32_t max_out,
+                      double *theta_out, double *lambda_out, double *X_out, double *est_out, lsa_ks_result *result);
+/* The dense kernel of that iteration (host only; LAPACK's dsyev, which SLEPc's DS of type HEP calls): real symmetric A (n x n
+ * column-major, lower triangle read), eigenvalues ascending in w, orthonormal eigenvectors over A.  Householder
+ * tridiagonalisation + implicit QL.  LSA_ERR_DIVERGED if the QL iteration stalls. */
+int lsa_dense_syev(int32_t n, double *A, int32_t lda, double *w);
+
 /* ---- MatrixMarket reader (host only): the A.mtx / M.mtx stage boundary --------------------------------------------
  * Stands in for scipy.io.mmread + the per-entry setValue loop of iPETScMatrix.from_path / from_matrix
  * (FEM/utils.py:143-147,208-215).  Coordinate format; general / symmetric / hermitian / skew-symmetric; real / integer /

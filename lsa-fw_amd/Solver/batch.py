@@ -78,7 +78,7 @@ def batch_key(eps) -> tuple[tuple | None, str]:
         return None, "operators on different patterns with a dense union"
     key = (_pattern_digest(A, M), n, cplx, constraint, eps._problem_type, eps._nev, eps._ncv, eps._tol, eps._max_it, eps._which,
            eps._ksp_type, eps._ksp_rtol, eps._restart_len, eps._ksp_max_it, eps._ilu_shift, eps._ordering, eps._seed, eps._device,
-           eps._lu, None if eps._antishift is None else complex(eps._antishift))
+           eps._lu, None if eps._antishift is None else complex(eps._antishift), bool(getattr(eps, "_symmetric", False)))
     return key, ""
 
 

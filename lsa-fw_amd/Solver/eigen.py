@@ -88,10 +88,15 @@ def _warn_about_symmetry(kind: iEpsProblemType, A: iPETScMatrix, M: iPETScMatrix
 class EigenSolver:
     """``A x = lambda M x`` (``M`` optional) on the GPU; thin shell around :class:`iEpsSolver`."""
 
-    def __init__(self, *args, check_hermitian: bool = True, **solver_kwargs) -> None:
+    def __init__(self, *args, check_hermitian: bool = True, symmetric: bool = False, **solver_kwargs) -> None:
         """``EigenSolver(A, M=None, cfg=None, *, check_hermitian=True)`` as in ``Solver/eigen.py:67-74``, or the legacy
         ``EigenSolver(cfg, A=..., M=...)``.  Keywords the reference does not know (``device``, ``ilu_levels``,
-        ``restart``, ``layout``, ...) are handed to :class:`iEpsSolver`."""
+        ``restart``, ``layout``, ...) are handed to :class:`iEpsSolver`.
+
+        ``symmetric=True`` (build-only, default off): ``HEP`` / ``GHEP`` problems with real symmetric operators, shift-invert at
+        a real target and the exact factorisation run the real thick-restart Lanczos iteration in the ``M``-inner product
+        (what SLEPc does for ``GHEP``): eigenvalues are ``float``, eigenvectors real with ``x^T M x = 1``.  Anything else runs
+        the general iteration as before and says why in ``solver.stats["symmetric_fallback"]``."""
         A, M, cfg = _sort_arguments(args, solver_kwargs)
         if A is None:
             raise ValueError("Operator A is required.")
@@ -102,7 +107,7 @@ class EigenSolver:
         if check_hermitian:
             _warn_about_symmetry(self._cfg.problem_type, A, M)
 
-        eps = iEpsSolver(A, M, **solver_kwargs)
+        eps = iEpsSolver(A, M, symmetric=symmetric, **solver_kwargs)
         eps.set_problem_type(self._cfg.problem_type)
         eps.set_tolerances(self._cfg.atol, self._cfg.max_it)
         eps.set_dimensions(self._cfg.num_eig, self._cfg.ncv)

@@ -225,6 +225,70 @@ def pivot_safe_rcm(C: sp.csr_matrix) -> np.ndarray:
     return perm[delay_zero_diagonal_rows(Cp)]
 
 
+def symmetry_defect(X) -> float:
+    """``||X - X^T||_F / ||X||_F`` of a sparse matrix as given (0 for an empty one); ``inf`` for a complex or non-square one."""
+    X = sp.csr_matrix(X)
+    if X.dtype.kind == "c" or X.shape[0] != X.shape[1]:
+        return float("inf")
+    norm = float(np.sqrt(np.sum(X.data.astype(np.float64) ** 2)))
+    if norm == 0.0:
+        return 0.0
+    D = (X - X.T).tocsr()
+    return float(np.sqrt(np.sum(D.data.astype(np.float64) ** 2))) / norm
+
+
+_SYMMETRY_TOL = 1e-12  # relative Frobenius defect below which a matrix counts as symmetric in value (assembly order leaves ~1e-16)
+_SYMMETRIC_WHICH = ("TARGET_MAGNITUDE", "TARGET_REAL", "LARGEST_MAGNITUDE", "LARGEST_REAL", "SMALLEST_REAL")
+
+
+def _symmetric_path(eps: "iEpsSolver") -> tuple[bool, str]:
+    """Whether a solve of ``eps`` can run the real thick-restart Lanczos iteration with the ``M``-inner product
+    (``lsa_lanczos_solve``; SLEPc's symmetric Krylov-Schur behind ``GHEP`` / ``HEP``), and if not, why.  Pure Python, no device:
+    the problem type, the matrices as given (real, symmetric in value to a relative Frobenius defect of 1e-12), shift-invert
+    with a real target, the exact LU, one rank, the forward unprojected problem, a ``which`` that means something on a real
+    spectrum."""
+    if eps._problem_type not in _HERMITIAN:
+        return False, f"problem type {eps._problem_type.name} is not HEP or GHEP"
+    if eps._A is None:
+        return False, "operators are not set"
+    if eps._st_type is not iSTType.SINVERT:
+        return False, f"spectral transformation {eps._st_type.name} is not SINVERT"
+    if complex(eps._target).imag != 0.0:
+        return False, f"the target {complex(eps._target)} is complex"
+    if eps._pc_type not in (PreconditionerType.LU, PreconditionerType.CHOLESKY):
+        return False, f"preconditioner {eps._pc_type.name} is not the exact factorisation (LU or CHOLESKY)"
+    if eps._ilu_levels is not None:
+        return False, f"an ILU level ({eps._ilu_levels}) replaces the exact factorisation"
+    if eps._layout != "single":
+        return False, "more than one rank (sharded layout)"
+    if eps._adjoint:
+        return False, "adjoint=True (for a symmetric pencil the adjoint problem is the forward one)"
+    if eps._project_out is not None:
+        return False, "a projection (project_out) is set"
+    which = eps._which or iEpsWhich.TARGET_MAGNITUDE
+    if which is not iEpsWhich.ALL and which.name not in _SYMMETRIC_WHICH:
+        return False, f"which = {which.name} has no meaning on a real spectrum"
+    cached = getattr(eps, "_symmetry_checked", None)
+    if cached is None or cached[0] != (id(eps._A), id(eps._M)):
+        defects = []
+        for name, X in (("A", eps._A), ("M", eps._M)):
+            if X is None:
+                continue
+            Xs = X.as_scipy_array()
+            if Xs.dtype.kind == "c":
+                defects.append((name, "complex", float("inf")))
+            else:
+                defects.append((name, "real", symmetry_defect(Xs)))
+        cached = ((id(eps._A), id(eps._M)), defects)
+        eps._symmetry_checked = cached
+    for name, kind, defect in cached[1]:
+        if kind == "complex":
+            return False, f"{name} is complex"
+        if not defect <= _SYMMETRY_TOL:
+            return False, f"{name} is not symmetric in value (relative Frobenius defect {defect:.2e} > {_SYMMETRY_TOL:.0e})"
+    return True, ""
+
+
 class _RawPC:
     def __init__(self, owner: "iEpsSolver"):
         self._o = owner
@@ -295,13 +359,17 @@ class iEpsSolver:
 
     Build-only knobs (the reference leaves them to the PETSc options database) are keyword arguments:
     ``ksp_type`` (inner Krylov method, GMRES), ``ksp_rtol``, ``restart``, ``ksp_max_it``, ``ilu_levels``,
-    ``ilu_shift``, ``device``.
+    ``ilu_shift``, ``device``, ``symmetric``.
+
+    ``symmetric=True`` asks for the real thick-restart Lanczos iteration with the ``M``-inner product on ``HEP`` / ``GHEP`` problems
+    (:func:`_symmetric_path` decides; ``stats["method"]`` says which iteration ran, ``stats["symmetric_fallback"]`` why the general
+    one ran instead): real eigenvalues, real eigenvectors with ``x^T M x = 1``.
     """
 
     def __init__(self, A=None, M=None, comm=None, *, device: int = 0, ksp_type: KSPType = KSPType.GMRES,
                  ksp_rtol: float | None = None, restart: int = 1000, ksp_max_it: int = 4000, ilu_levels: int | None = None,
                  ilu_shift: float = 0.0, ordering: str = "rcm", seed: int = 0, layout: str = "single",
-                 project_out: np.ndarray | None = None, lu: str = "nd", adjoint: bool = False) -> None:
+                 project_out: np.ndarray | None = None, lu: str = "nd", adjoint: bool = False, symmetric: bool = False) -> None:
         if M is not None and A is None:
             raise ValueError("Cannot set right-hand operator M without left-hand operator A.")
         self._A = self._M = None
@@ -325,6 +393,9 @@ class iEpsSolver:
         # (A - conj(target) M)^-H M^H applied on the factors of A - conj(target) M: no transposed matrix is formed
         # (reference: Sensitivity/__init__.py:47-57,247-248 builds A^H and M^H explicitly)
         self._adjoint = bool(adjoint)
+        self._symmetric = bool(symmetric)  # opt-in: real Lanczos with the M-inner product where _symmetric_path allows it
+        self._real_vectors = False  # the last solve ran it: real eigenvalues, real M-orthonormal vectors
+        self._fallback_logged: set = set()
         self._device, self._seed = device, seed
         if layout not in ("single", "sharded"):
             raise ValueError("layout must be 'single' or 'sharded'")
@@ -612,6 +683,11 @@ class iEpsSolver:
             raise NotImplementedError("adjoint=True needs shift-invert with the exact LU (PreconditionerType.LU, lu='nd'), on one GPU or in the "
                                       "subtree-parallel sharded layout")
         ksp_rtol = self._ksp_rtol if self._ksp_rtol is not None else float(np.clip(self._tol * 1e-2, 1e-13, 1e-8))
+        use_lanczos, fallback = False, None
+        if self._symmetric:
+            use_lanczos, fallback = _symmetric_path(self)
+            if use_lanczos and prep["pc_code"] != 2:
+                use_lanczos, fallback = False, "the exact LU is not in use"
         op = basis = None
         try:
             op = lsa_hip.ShiftInvertOperator(
@@ -636,9 +712,33 @@ class iEpsSolver:
             mask = keep if part is None else part.pad_vector(np.ones(n) if keep is None else keep)
             if keep is not None:
                 op.set_projection(mask)
-            basis = lsa_hip.KrylovBasis(ctx, op, ncv, mask)
-            if part is None:
-                basis.set_row_permutation(perm)  # Ritz vectors leave the device in the caller's numbering
+            res = None
+            basis_bytes = 0
+            if use_lanczos:
+                # real thick-restart Lanczos in the M-inner product (lsa_lanczos_solve).  What the library refuses (M not positive
+                # definite on the Krylov space, an inner solve short of ksp_rtol after its refinement step, factors that came
+                # out complex or inexact) is answered by the general iteration below, on the same operator.
+                try:
+                    basis = lsa_hip.LanczosBasis(ctx, op, ncv)
+                    basis.set_row_permutation(perm)
+                    cached = getattr(self, "_v0_real_cache", None)
+                    if cached is None or cached[0] != (n, self._seed):
+                        cached = ((n, self._seed), np.random.default_rng(self._seed).standard_normal(n))
+                        self._v0_real_cache = cached
+                    res = basis.solve(nev, self._tol, self._max_it, which.value, float(complex(sigma).real), target=float(complex(self._target).real),
+                                      v0=cached[1], seed=self._seed)
+                    basis_bytes = basis.basis_bytes
+                except (lsa_hip.LsaError, ValueError) as exc:
+                    use_lanczos, fallback, res, basis = False, f"the library refused the symmetric iteration: {exc}", None, None
+            if self._symmetric and not use_lanczos and fallback not in self._fallback_logged:
+                self._fallback_logged.add(fallback)
+                logger.warning("symmetric=True, but the solve runs the general (complex Arnoldi) iteration: %s.", fallback)
+            if res is None:
+                basis = lsa_hip.KrylovBasis(ctx, op, ncv, mask)
+                if part is None:
+                    basis.set_row_permutation(perm)  # Ritz vectors leave the device in the caller's numbering
+                # V, the restart's second basis and, with a row permutation, the Ritz vectors in the caller's numbering
+                basis_bytes = 16 * basis.n * (ncv + 1) * (3 if part is None else 2)
             tiny = np.finfo(float).tiny
             if cayley:  # theta = (lambda + nu) / (lambda - sigma)
                 back = lambda th: (sigma * th + nu) / np.where(th == 1.0, 1.0 + 1e-300, th - 1.0)  # noqa: E731
@@ -649,7 +749,9 @@ class iEpsSolver:
             theta_key = lambda th: lam_key(back(np.asarray(th, dtype=np.complex128)))  # noqa: E731
             import os
 
-            if os.environ.get("LSA_KS_DRIVER", "native") == "python":
+            if res is not None:
+                pass
+            elif os.environ.get("LSA_KS_DRIVER", "native") == "python":
                 # the same outer iteration in Python over LAPACK (lsa_hip/krylov_schur.py): test double of the library's loop
                 res = krylov_schur(basis, nev, self._tol, self._max_it, theta_key, rng_seed=self._seed)
             else:
@@ -665,7 +767,7 @@ class iEpsSolver:
                                   target=self._target, v0=v0, seed=self._seed)
             imag_norms = getattr(basis, "imag_norms", None)  # set when the device already put the vectors into canonical phase
             theta = res.theta
-            lam = back(np.asarray(theta, dtype=np.complex128))
+            lam = res.lam if use_lanczos else back(np.asarray(theta, dtype=np.complex128))
             if part is None:
                 X = res.vectors
             else:
@@ -674,6 +776,10 @@ class iEpsSolver:
                 X[perm, :] = vecs
             self._stats = op.stats()
             self._stats["krylov_restarts"] = res.restarts
+            self._stats["method"] = "lanczos" if use_lanczos else "arnoldi"
+            self._stats["basis_bytes"] = int(basis_bytes)
+            if self._symmetric and not use_lanczos:
+                self._stats["symmetric_fallback"] = fallback
             if res.history and "seconds_dense" in res.history[-1]:  # the library's loop times its phases
                 self._stats.update({k: res.history[-1][k] for k in ("seconds_expand", "seconds_dense", "seconds_restart")})
             if part is not None:
@@ -696,6 +802,7 @@ class iEpsSolver:
         finally:
             basis = None
             op = None
+        self._real_vectors = use_lanczos
         order = np.argsort(lam_key(lam), kind="stable")
         self._eigenvalues = lam[order]
         # column access (one eigenvector) must be contiguous; the Krylov-Schur driver already returns the wanted pairs first
@@ -783,7 +890,7 @@ class iEpsSolver:
                         self.solve()
                         restarts += self._restarts
                         for k, v in self._stats.items():
-                            if isinstance(v, (int, float)) and k not in ("last_rel_res", "max_rel_res"):
+                            if isinstance(v, (int, float)) and k not in ("last_rel_res", "max_rel_res", "basis_bytes"):
                                 stats_total[k] = stats_total.get(k, 0) + v
                         if rep == 0:
                             lam = np.real(self._eigenvalues)  # the cover is judged on the first solve's set
@@ -858,6 +965,7 @@ class iEpsSolver:
             logger.warning("iEpsWhich.ALL on [%g, %g]: %d eigenvalues found by a sweep of shift-invert solves; completeness is heuristic "
                            "(inertia counts need a real symmetric pair and the exact LU on one GPU) -- a multiple eigenvalue can be "
                            "under-counted.", a, b, len(found_lam))
+        stats_total.update({k: self._stats[k] for k in ("method", "basis_bytes", "symmetric_fallback") if k in self._stats})  # (not sums: the last solve's)
         stats_total["interval_expected"] = -1 if proof is None else proof["expected"]
         stats_total["interval_complete"] = int(proof is not None and proof["found"] == proof["expected"])
         order = np.argsort(found_lam)
@@ -933,6 +1041,8 @@ class iEpsSolver:
         """Eigenvector ``idx`` with unit 2-norm; the imaginary part is dropped when its norm is <= 1e-6, as the
         reference's real build does (``Solver/utils.py:280-291``)."""
         v = self._eigenvectors[:, idx]
+        if self._real_vectors and v.dtype.kind == "f":  # the symmetric path: real, x^T M x = 1 (unit 2-norm for a standard problem)
+            return iComplexPETScVector(iPETScVector._adopt(v.copy()))
         imag_norms = getattr(self, "_imag_norms", None)
         if imag_norms is not None:  # unit norm and canonical phase were applied on the device (lsa_krylov_ritz_vectors)
             if imag_norms[idx] <= 1e-6:
@@ -970,7 +1080,8 @@ class iEpsSolver:
         yield from pairs
 
     def get_eigenvector_array(self, idx: int) -> np.ndarray:
-        """Complex ndarray of eigenvector ``idx`` (convenience; not in the reference)."""
+        """ndarray of eigenvector ``idx`` (convenience; not in the reference): complex, or real ``float64`` when the symmetric
+        iteration ran."""
         return self._eigenvectors[:, idx].copy()
 
     @property

@@ -497,6 +497,178 @@ struct Rng {  // splitmix64 + Box-Muller: start vectors and the fresh directions
     }
 };
 
+// ---- real symmetric eigenproblem (the projected matrix of the Lanczos iteration) ---------------------------------------------
+// Householder reduction to tridiagonal form with the transformations accumulated, then the implicit QL algorithm with Wilkinson
+// shifts (EISPACK's tred2 / tql2, Wilkinson & Reinsch, Handbook for Automatic Computation II).  a: n x n column-major with leading
+// dimension lda, lower triangle read, eigenvectors written over it; d: eigenvalues ascending.  The matrix is scaled by a power of
+// two to max|a| ~ 1 first, so that the sums of squares neither overflow nor underflow.  false: the QL iteration stalled.
+bool sym_eig(int n, double* a, int lda, double* d) {
+    if (n == 0) return true;
+    auto A = [&](int i, int j) -> double& { return a[(size_t)j * lda + i]; };
+    double amax = 0.0;
+    for (int j = 0; j < n; ++j)
+        for (int i = j; i < n; ++i) {
+            if (!std::isfinite(A(i, j))) return false;
+            amax = std::max(amax, std::fabs(A(i, j)));
+        }
+    if (amax == 0.0) {
+        for (int j = 0; j < n; ++j) {
+            for (int i = 0; i < n; ++i) A(i, j) = i == j ? 1.0 : 0.0;
+            d[j] = 0.0;
+        }
+        return true;
+    }
+    int ex = 0;
+    (void)std::frexp(amax, &ex);
+    const double scale = std::ldexp(1.0, -ex), unscale = std::ldexp(1.0, ex);
+    for (int j = 0; j < n; ++j)
+        for (int i = j; i < n; ++i) {
+            const double v = A(i, j) * scale;
+            A(i, j) = v;
+            A(j, i) = v;
+        }
+    std::vector<double> e((size_t)n, 0.0);
+    // -- tred2
+    for (int j = 0; j < n; ++j) d[j] = A(n - 1, j);
+    for (int i = n - 1; i > 0; --i) {
+        double sc = 0.0, h = 0.0;
+        for (int k = 0; k < i; ++k) sc += std::fabs(d[k]);
+        if (sc == 0.0) {
+            e[i] = d[i - 1];
+            for (int j = 0; j < i; ++j) {
+                d[j] = A(i - 1, j);
+                A(i, j) = 0.0;
+                A(j, i) = 0.0;
+            }
+        } else {
+            for (int k = 0; k < i; ++k) {
+                d[k] /= sc;
+                h += d[k] * d[k];
+            }
+            double f = d[i - 1], g = std::sqrt(h);
+            if (f > 0.0) g = -g;
+            e[i] = sc * g;
+            h -= f * g;
+            d[i - 1] = f - g;
+            for (int j = 0; j < i; ++j) e[j] = 0.0;
+            for (int j = 0; j < i; ++j) {
+                f = d[j];
+                A(j, i) = f;
+                g = e[j] + A(j, j) * f;
+                for (int k = j + 1; k <= i - 1; ++k) {
+                    g += A(k, j) * d[k];
+                    e[k] += A(k, j) * f;
+                }
+                e[j] = g;
+            }
+            f = 0.0;
+            for (int j = 0; j < i; ++j) {
+                e[j] /= h;
+                f += e[j] * d[j];
+            }
+            const double hh = f / (h + h);
+            for (int j = 0; j < i; ++j) e[j] -= hh * d[j];
+            for (int j = 0; j < i; ++j) {
+                f = d[j];
+                g = e[j];
+                for (int k = j; k <= i - 1; ++k) A(k, j) -= f * e[k] + g * d[k];
+                d[j] = A(i - 1, j);
+                A(i, j) = 0.0;
+            }
+        }
+        d[i] = h;
+    }
+    for (int i = 0; i < n - 1; ++i) {
+        A(n - 1, i) = A(i, i);
+        A(i, i) = 1.0;
+        const double h = d[i + 1];
+        if (h != 0.0) {
+            for (int k = 0; k <= i; ++k) d[k] = A(k, i + 1) / h;
+            for (int j = 0; j <= i; ++j) {
+                double g = 0.0;
+                for (int k = 0; k <= i; ++k) g += A(k, i + 1) * A(k, j);
+                for (int k = 0; k <= i; ++k) A(k, j) -= g * d[k];
+            }
+        }
+        for (int k = 0; k <= i; ++k) A(k, i + 1) = 0.0;
+    }
+    for (int j = 0; j < n; ++j) {
+        d[j] = A(n - 1, j);
+        A(n - 1, j) = 0.0;
+    }
+    A(n - 1, n - 1) = 1.0;
+    e[0] = 0.0;
+    // -- tql2
+    for (int i = 1; i < n; ++i) e[i - 1] = e[i];
+    e[n - 1] = 0.0;
+    double f = 0.0, tst1 = 0.0;
+    const double eps = 2.220446049250313e-16;
+    for (int l = 0; l < n; ++l) {
+        tst1 = std::max(tst1, std::fabs(d[l]) + std::fabs(e[l]));
+        int m = l;
+        while (m < n - 1) {
+            if (std::fabs(e[m]) <= eps * tst1) break;
+            ++m;
+        }
+        if (m > l) {
+            int iter = 0;
+            do {
+                if (++iter > 60) return false;
+                double g = d[l];
+                double p = (d[l + 1] - g) / (2.0 * e[l]);
+                double r = std::hypot(p, 1.0);
+                if (p < 0.0) r = -r;
+                d[l] = e[l] / (p + r);
+                d[l + 1] = e[l] * (p + r);
+                const double dl1 = d[l + 1];
+                double h = g - d[l];
+                for (int i = l + 2; i < n; ++i) d[i] -= h;
+                f += h;
+                p = d[m];
+                double c = 1.0, c2 = c, c3 = c, s = 0.0, s2 = 0.0;
+                const double el1 = e[l + 1];
+                for (int i = m - 1; i >= l; --i) {
+                    c3 = c2;
+                    c2 = c;
+                    s2 = s;
+                    g = c * e[i];
+                    h = c * p;
+                    r = std::hypot(p, e[i]);
+                    e[i + 1] = s * r;
+                    s = e[i] / r;
+                    c = p / r;
+                    p = c * d[i] - s * g;
+                    d[i + 1] = h + s * (c * g + s * d[i]);
+                    for (int k = 0; k < n; ++k) {
+                        h = A(k, i + 1);
+                        A(k, i + 1) = s * A(k, i) + c * h;
+                        A(k, i) = c * A(k, i) - s * h;
+                    }
+                }
+                p = -s * s2 * c3 * el1 * e[l] / dl1;
+                e[l] = s * p;
+                d[l] = c * p;
+            } while (std::fabs(e[l]) > eps * tst1);
+        }
+        d[l] += f;
+        e[l] = 0.0;
+    }
+    // ascending order (selection sort: the columns move with their values)
+    for (int i = 0; i < n - 1; ++i) {
+        int k = i;
+        double p = d[i];
+        for (int j = i + 1; j < n; ++j)
+            if (d[j] < p) k = j, p = d[j];
+        if (k != i) {
+            d[k] = d[i];
+            d[i] = p;
+            for (int j = 0; j < n; ++j) std::swap(A(j, i), A(j, k));
+        }
+    }
+    for (int j = 0; j < n; ++j) d[j] *= unscale;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -787,6 +959,138 @@ int lsa_eigs_sinvert(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, const dou
     if (kr) lsa_krylov_destroy(kr);
     if (op) lsa_op_destroy(op);
     return rc;
+}
+
+int lsa_dense_syev(int32_t n, double* A, int32_t lda, double* w) {
+    if (n < 0 || (n > 0 && (!A || !w)) || lda < std::max(1, n)) return LSA_ERR_ARG;
+    for (int j = 0; j < n; ++j)
+        for (int i = j; i < n; ++i)
+            if (!std::isfinite(A[(size_t)j * lda + i])) return LSA_ERR_NONFINITE;
+    return sym_eig(n, A, lda, w) ? LSA_OK : LSA_ERR_DIVERGED;
+}
+
+// Thick-restart Lanczos = the symmetric variant of Krylov-Schur (SLEPc's EPSSolve_KrylovSchur_Symm behind EPS_GHEP / EPS_HEP): the
+// loop of lsa_krylov_solve with a real M-orthonormal basis (lanczos.hip), a real symmetric projected matrix T (after a restart:
+// diag(theta_1..theta_k) with the spike beta y_{m,i} in row and column k, tridiagonal behind it) and lsa_dense_syev in place of the
+// complex Schur form.
+int lsa_lanczos_solve(lsa_ctx* ctx, lsa_lanczos* l, const lsa_ks_options* o, const double* v0, int32_t max_out, double* theta_out,
+                      double* lambda_out, double* X_out, double* est_out, lsa_ks_result* result) {
+    if (!ctx || !l || !o || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_solve: null argument");
+    int32_t m = 0;
+    int64_t n = 0;
+    LSA_CHECK(lanczos_shape(l, &n, &m));
+    if (o->nev < 1 || o->max_restarts < 0 || !(o->tol > 0.0) || max_out < 0 || (max_out > 0 && (!theta_out || !lambda_out)))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_solve: nev, tol must be positive, output buffers are required");
+    if (o->transform != 0 || o->sigma[1] != 0.0 || o->target[1] != 0.0)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_solve: shift-invert (transform 0) with a real shift and a real target only");
+    switch (o->which) {
+        case LSA_WHICH_TARGET_MAGNITUDE: case LSA_WHICH_TARGET_REAL: case LSA_WHICH_LARGEST_MAGNITUDE: case LSA_WHICH_LARGEST_REAL:
+        case LSA_WHICH_SMALLEST_REAL: break;
+        default: return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_solve: which = %d has no meaning for a real spectrum", o->which);
+    }
+    max_out = std::min(max_out, m);
+    const int nev = std::min<int>(o->nev, m);
+    const double keep_fraction = o->keep_fraction > 0.0 && o->keep_fraction < 1.0 ? o->keep_fraction : 0.5;
+    const Selector sel{o->which, 0, {o->sigma[0], 0.0}, {0.0, 0.0}, {o->target[0], 0.0}};
+    Rng rng{o->seed * 0x2545F4914F6CDD1Dull + 0x1234567ull};
+    std::vector<double> vec((size_t)n);
+    auto random_vector = [&]() {
+        double other = 0.0;
+        for (int64_t i = 0; i < n; ++i) rng.normal_pair(vec[(size_t)i], other);
+    };
+    if (v0) memcpy(vec.data(), v0, (size_t)n * sizeof(double));
+    else random_vector();
+    LSA_CHECK(lanczos_inject(ctx, l, 0, vec.data()));
+    const int ldt = m + 1;
+    std::vector<double> T((size_t)ldt * m, 0.0), Y((size_t)m * m), theta((size_t)m), est((size_t)m), rel((size_t)m), keys((size_t)m);
+    std::vector<int> rank((size_t)m);
+    auto Tm = [&](int r, int c) -> double& { return T[(size_t)c * ldt + r]; };
+    int kept = 0, restarts = 0;
+    int64_t applies = 0;
+    memset(result, 0, sizeof *result);
+    double t_expand = 0.0, t_dense = 0.0, t_restart = 0.0;
+    while (true) {
+        // ---- expand to m vectors; continue past exact breakdowns (invariant subspace) with a fresh direction ----
+        double t0 = now_s();
+        int j = kept;
+        while (j < m) {
+            int32_t bd = -1;
+            LSA_CHECK(lsa_lanczos_extend(ctx, l, j, m, T.data(), ldt, &bd));
+            if (bd < 0) {
+                applies += m - j;
+                break;
+            }
+            applies += bd - j + 1;
+            if (bd + 1 >= m) break;  // broke down on the last step: the m vectors span an invariant subspace
+            random_vector();
+            LSA_CHECK(lanczos_inject(ctx, l, bd + 1, vec.data()));
+            j = bd + 1;
+        }
+        t_expand += now_s() - t0;
+        t0 = now_s();
+        const double beta = Tm(m, m - 1);
+        for (int c = 0; c < m; ++c)
+            for (int r = 0; r < m; ++r) Y[(size_t)c * m + r] = Tm(r, c);
+        // ---- Ritz pairs and residual estimates ----
+        if (!sym_eig(m, Y.data(), m, theta.data()))
+            return lsa_set_error(ctx, LSA_ERR_DIVERGED, "Lanczos: the QL algorithm on the projected matrix did not converge");
+        for (int c = 0; c < m; ++c) {
+            est[(size_t)c] = std::fabs(beta * Y[(size_t)c * m + (m - 1)]);
+            keys[(size_t)c] = sel.key(Z{theta[(size_t)c], 0.0});
+            rel[(size_t)c] = est[(size_t)c] / std::max(std::fabs(theta[(size_t)c]), 2.2250738585072014e-308);
+            rank[(size_t)c] = c;
+        }
+        std::stable_sort(rank.begin(), rank.end(), [&](int x, int y) { return keys[(size_t)x] < keys[(size_t)y]; });
+        int nconv = 0;
+        while (nconv < m && rel[(size_t)rank[(size_t)nconv]] <= o->tol) ++nconv;
+        if (nconv >= nev || nconv >= m || restarts >= o->max_restarts) {
+            const int nout = std::min<int>(nconv, max_out);
+            if (nout > 0) {
+                std::vector<double> Yo((size_t)m * nout);
+                for (int c = 0; c < nout; ++c) {
+                    const int src = rank[(size_t)c];
+                    memcpy(&Yo[(size_t)c * m], &Y[(size_t)src * m], (size_t)m * sizeof(double));
+                    theta_out[c] = theta[(size_t)src];
+                    lambda_out[c] = sel.back(Z{theta[(size_t)src], 0.0}).re;
+                    if (est_out) est_out[c] = rel[(size_t)src];
+                }
+                t_dense += now_s() - t0;
+                t0 = now_s();
+                if (X_out) LSA_CHECK(lanczos_ritz_vectors(ctx, l, m, nout, Yo.data(), m, X_out));
+                t_restart += now_s() - t0;
+                t0 = now_s();
+            }
+            t_dense += now_s() - t0;
+            result->seconds_expand = t_expand;
+            result->seconds_dense = t_dense;
+            result->seconds_restart = t_restart;
+            result->nconv = nconv;
+            result->nout = nout;
+            result->restarts = restarts;
+            result->op_applies = applies;
+            result->next_unconverged = nconv < m ? rel[(size_t)rank[(size_t)nconv]] : 0.0;
+            return LSA_OK;
+        }
+        // ---- keep the wanted Ritz vectors and restart: T <- diag(theta_kept) with the spike beta y_{m,i} in row and column knew ----
+        int knew = nconv + (int)((m - nconv) * keep_fraction);
+        knew = std::max(std::min(knew, m - 1), 1);
+        std::vector<double> Yk((size_t)m * knew);
+        for (int c = 0; c < knew; ++c) memcpy(&Yk[(size_t)c * m], &Y[(size_t)rank[(size_t)c] * m], (size_t)m * sizeof(double));
+        t_dense += now_s() - t0;
+        t0 = now_s();
+        LSA_CHECK(lanczos_restart(ctx, l, m, knew, Yk.data(), m));
+        t_restart += now_s() - t0;
+        std::fill(T.begin(), T.end(), 0.0);
+        for (int c = 0; c < knew; ++c) {
+            const int src = rank[(size_t)c];
+            Tm(c, c) = theta[(size_t)src];
+            const double spike = beta * Y[(size_t)src * m + (m - 1)];
+            Tm(knew, c) = spike;
+            Tm(c, knew) = spike;
+        }
+        kept = knew;
+        ++restarts;
+    }
 }
 
 }  // extern "C"

@@ -274,6 +274,28 @@ int k_spmv_plain_subwave_lanes(const lsa_mat* A);  // spmv.hip
 int k_basis_gemm(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V, int64_t ldv, const void* Q, int ldq,
                  void* Out, int64_t ldo);
 
+// ---- what the Lanczos iteration (lanczos.hip) needs of a shift-invert operator (solver.hip) -------------------------------
+struct lsa_ndlu;
+struct lsa_op_parts {
+    int64_t n;
+    const lsa_mat *Kmul, *Kfac;  // y = Kfac^-1 (Kmul x); Kmul null: standard problem
+    lsa_ndlu* nd;                // exact LU of Kfac, or null
+    bool plain;                  // forward, unprojected, whole on this rank
+    double ksp_rtol;
+    double normF;                // ||Kfac||_F (0: unknown): the scale of the backward-error judgement of a direct solve
+    bool* refine;                // the operator's flag: solves carry one step of iterative refinement
+    lsa_stats* st;
+};
+int lsa_op_get_parts(lsa_op* op, lsa_op_parts* out);
+// the pieces of the symmetric outer iteration that live with the basis (lanczos.hip); the loop itself is lsa_lanczos_solve (dense.hip)
+int lanczos_shape(const lsa_lanczos* l, int64_t* n, int32_t* ncv);
+// v_j = host vector M-orthonormalised against v_0..v_{j-1} (continues after a breakdown; j = 0: lsa_lanczos_set_start)
+int lanczos_inject(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, const double* host_v);
+// thick restart: V[:, 0:knew] = V[:, 0:m] Y (Y m x knew column-major on the host), V[:, knew] = V[:, m]
+int lanczos_restart(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t knew, const double* Y, int32_t ldy);
+// X = V[:, 0:m] Y to the host in the caller's row numbering, each column's entry of largest magnitude positive
+int lanczos_ritz_vectors(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t nvec, const double* Y, int32_t ldy, double* X);
+
 // ---- ILU (ilu.hip) -------------------------------------------------------------------------------------
 struct lsa_ilu {
     lsa_ctx* ctx;

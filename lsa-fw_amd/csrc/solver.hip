@@ -812,6 +812,27 @@ int lsa_op_apply(lsa_ctx* ctx, lsa_op* op, const lsa_vec* x, lsa_vec* y) {
     return rc;
 }
 
+}  // extern "C"
+
+int lsa_op_get_parts(lsa_op* op, lsa_op_parts* out) {
+    if (!op || !out) return LSA_ERR_ARG;
+    out->n = op->n;
+    out->Kmul = op->Kmul;
+    out->Kfac = op->Kfac;
+    out->nd = op->nd;
+    // shift-invert (mode 0: the factorised matrix is the C = A - sigma M built here, the multiplied one the caller's M), forward,
+    // unprojected, whole on one rank
+    out->plain = op->Kfac && op->Kfac == op->owned && op->Kmul == op->M_whole && !op->owned_mul && !op->adjoint && !op->keep && !op->nd_dist &&
+                 op->ctx->nranks == 1;
+    out->ksp_rtol = op->opts.ksp_rtol;
+    out->normF = op->normF;
+    out->refine = &op->refine;
+    out->st = &op->st;
+    return LSA_OK;
+}
+
+extern "C" {
+
 int lsa_op_stats(const lsa_op* op, lsa_stats* out) {
     if (!op || !out) return LSA_ERR_ARG;
     *out = op->st;

@@ -183,6 +183,14 @@ SIGNATURES = {
     "lsa_dense_schur_reorder": (ctypes.c_int, [_I32, _P, _I32, _P, _I32, _P, ctypes.POINTER(_I32)]),
     "lsa_dense_tri_eigenvectors": (ctypes.c_int, [_I32, _P, _I32, _P, _I32]),
     "lsa_eig_residuals": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P]),
+    "lsa_lanczos_create": (ctypes.c_int, [_P, _P, _I32, _PP]),
+    "lsa_lanczos_destroy": (None, [_P]),
+    "lsa_lanczos_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
+    "lsa_lanczos_set_start": (ctypes.c_int, [_P, _P, _P]),
+    "lsa_lanczos_extend": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_I32)]),
+    "lsa_lanczos_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
+    "lsa_lanczos_solve": (ctypes.c_int, [_P, _P, ctypes.POINTER(lsa_ks_options), _P, _I32, _P, _P, _P, _P, ctypes.POINTER(lsa_ks_result)]),
+    "lsa_dense_syev": (ctypes.c_int, [_I32, _P, _I32, _P]),
     "lsa_mm_open": (ctypes.c_int, [ctypes.c_char_p, _PP, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int)]),
     "lsa_mm_read_csr": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_mm_error": (ctypes.c_char_p, [_P]),
@@ -872,6 +880,102 @@ class KrylovBasis:
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
             self.ctx._lib.lsa_krylov_destroy(self.handle)
             self.handle = None
+
+
+class LanczosBasis:
+    """Real ``M``-orthonormal Lanczos basis in HBM for a symmetric-definite pencil (``lsa_lanczos_*``): the symmetric counterpart of
+    :class:`KrylovBasis`.  ``op`` must be a shift-invert operator with real exact factors (``pc_type=2``, real shift)."""
+
+    def __init__(self, ctx: Context, op: ShiftInvertOperator, ncv: int):
+        self.ctx, self._op = ctx, op
+        self.n, self.ncv = op.n, int(ncv)
+        h = ctypes.c_void_p()
+        ctx.check(ctx._lib.lsa_lanczos_create(ctx.handle, op.handle, self.ncv, ctypes.byref(h)))
+        self.handle = h
+        self._has_perm = False
+
+    @property
+    def basis_bytes(self) -> int:
+        """Device bytes of the ``n x (ncv + 1)`` arrays the handle owns: the basis, the restart's second basis and, with a row
+        permutation, the Ritz vectors in the caller's numbering."""
+        return 8 * self.n * (self.ncv + 1) * (3 if self._has_perm else 2)
+
+    def set_row_permutation(self, perm: np.ndarray | None) -> None:
+        """``perm[i]`` = the caller's index of basis row ``i``: the vectors of :meth:`solve` come back in the caller's numbering."""
+        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        self.ctx.check(self.ctx._lib.lsa_lanczos_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
+        self._has_perm = p is not None
+
+    def set_start(self, v: np.ndarray) -> None:
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (self.n,):
+            raise ValueError(f"start vector must have shape ({self.n},)")
+        self.ctx.check(self.ctx._lib.lsa_lanczos_set_start(self.ctx.handle, self.handle, _ptr(v)))
+
+    def extend(self, j0: int, j1: int, T: np.ndarray) -> int:
+        """Lanczos steps j0..j1-1 writing ``alpha_j``, ``beta_j`` into the Fortran-ordered (ncv+1, ncv) real T; returns the
+        breakdown step or -1."""
+        assert T.flags.f_contiguous and T.dtype == np.float64
+        bd = _I32(-1)
+        self.ctx.check(self.ctx._lib.lsa_lanczos_extend(self.ctx.handle, self.handle, int(j0), int(j1), _ptr(T), T.shape[0], ctypes.byref(bd)))
+        return bd.value
+
+    def basis(self, ncols: int) -> np.ndarray:
+        """The first ``ncols`` basis vectors on the host, in the basis' own row numbering."""
+        V = np.empty((self.n, int(ncols)), dtype=np.float64, order="F")
+        self.ctx.check(self.ctx._lib.lsa_lanczos_basis(self.ctx.handle, self.handle, int(ncols), _ptr(V)))
+        return V
+
+    def solve(self, nev: int, tol: float, max_restarts: int, which: int, sigma: float, *, target: float | None = None,
+              v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None, vectors: bool = True):
+        """The whole thick-restart Lanczos iteration inside the library (``lsa_lanczos_solve``).  Returns a
+        :class:`lsa_hip.krylov_schur.KrylovSchurResult` with real ``theta``, real ``M``-orthonormal ``vectors`` and ``lam``."""
+        from .krylov_schur import KrylovSchurResult
+
+        max_out = self.ncv if max_out is None else min(int(max_out), self.ncv)
+        target = sigma if target is None else target
+        o = lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=int(which), transform=0,
+                           sigma=(_DBL * 2)(float(sigma), 0.0), antishift=(_DBL * 2)(0.0, 0.0), target=(_DBL * 2)(float(target), 0.0),
+                           seed=int(seed), keep_fraction=0.5)
+        theta = np.zeros(max(max_out, 1), dtype=np.float64)
+        lam = np.zeros(max(max_out, 1), dtype=np.float64)
+        est = np.zeros(max(max_out, 1), dtype=np.float64)
+        X = np.empty((self.n, max_out), dtype=np.float64, order="F") if vectors else None
+        res = lsa_ks_result()
+        v = None
+        if v0 is not None:
+            v = np.ascontiguousarray(v0, dtype=np.float64)
+            if v.shape != (self.n,):
+                raise ValueError(f"start vector must have shape ({self.n},)")
+        self.ctx.check(self.ctx._lib.lsa_lanczos_solve(self.ctx.handle, self.handle, ctypes.byref(o), None if v is None else _ptr(v), max_out,
+                                                       _ptr(theta), _ptr(lam), None if X is None else _ptr(X), _ptr(est), ctypes.byref(res)))
+        k = res.nout
+        vec = np.zeros((self.n, 0), dtype=np.float64) if X is None else (X[:, :k] if k == max_out else np.asfortranarray(X[:, :k]))
+        r = KrylovSchurResult(theta[:k].copy(), vec, est[:k].copy(), int(res.nconv), int(res.restarts), int(res.op_applies),
+                              [{"nconv": int(res.nconv), "next_unconverged": float(res.next_unconverged), "seconds_expand": res.seconds_expand,
+                                "seconds_dense": res.seconds_dense, "seconds_restart": res.seconds_restart}])
+        r.lam = lam[:k].copy()
+        return r
+
+    def __del__(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx._lib.lsa_lanczos_destroy(self.handle)
+            self.handle = None
+
+
+def dense_syev(A: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Eigenvalues (ascending) and orthonormal eigenvectors of a real symmetric matrix by the library's own host routine
+    (``lsa_dense_syev``: Householder tridiagonalisation + implicit QL; the lower triangle is read).  No GPU needed."""
+    lib = load_library()
+    Q = np.array(A, dtype=np.float64, order="F", copy=True)
+    if Q.ndim != 2 or Q.shape[0] != Q.shape[1]:
+        raise ValueError("dense_syev needs a square matrix")
+    n = Q.shape[0]
+    w = np.zeros(max(n, 1), dtype=np.float64)
+    rc = lib.lsa_dense_syev(n, _ptr(Q), max(n, 1), _ptr(w))
+    if rc != 0:
+        raise LsaError(rc, "lsa_dense_syev failed")
+    return w[:n], Q
 
 
 def eigs_sinvert(ctx: Context, A: CsrMatrix, M: CsrMatrix | None, sigma: complex, nev: int, *, ncv: int = 0, tol: float = 1e-10, max_restarts: int = 500,
