@@ -55,7 +55,7 @@ typedef struct {
     double last_rel_res;     /* relative residual estimate of the last inner solve    */
     double max_rel_res;      /* worst one seen                                        */
     double seconds_factor;   /* wall seconds spent in symbolic + numeric factorisation */
-    double seconds_solve;    /* wall seconds spent inside lsa_op_apply / lsa_krylov_extend */
+    double seconds_solve;    /* wall seconds spent inside lsa_op_apply / lsa_krylov_extend / lsa_lanczos_extend, failed calls included */
     int32_t stagnated_solves; /* inner solves accepted at a stagnated true residual in (10 rtol, 1000 rtol]: the caller warns */
     int32_t pc_fallback;     /* 1 if the exact LU did not fit the device memory and ILU(k) + GMRES took its place */
     int32_t backward_accepted; /* direct solves whose ||b - C x|| / ||b|| missed rtol but whose backward error

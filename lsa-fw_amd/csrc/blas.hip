@@ -999,6 +999,14 @@ __global__ __launch_bounds__(kThreads) void basis_gemm_kernel(int64_t n, int m, 
     }
 }
 
+// out[perm[i], c] = in[i, c]  (column-major n x ncols; grid.y = column)
+template <typename T>
+__global__ void scatter_rows_kernel(int64_t n, const int32_t* __restrict__ perm, const T* __restrict__ in, T* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const size_t off = (size_t)blockIdx.y * (size_t)n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[off + (size_t)perm[i]] = in[off + (size_t)i];
+}
+
 inline int stream_blocks(lsa_ctx* ctx, int64_t n) {
     int64_t want = (n + kThreads - 1) / kThreads;
     int64_t cap = (int64_t)ctx->num_cu * 8;
@@ -1250,37 +1258,64 @@ int k_basis_gemm(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V
     return check_launch(ctx, "basis_gemm");
 }
 
+// Out[perm[i], c] = In[i, c]  (column-major n x ncols, both with leading dimension n)
+int k_scatter_rows(lsa_ctx* ctx, int dtype, int64_t n, int ncols, const int32_t* perm, const void* In, void* Out) {
+    if (ncols <= 0) return LSA_OK;
+    const int blocks = (int)std::max<int64_t>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->num_cu * 16), 1);
+    DISPATCH_T(dtype, { hipLaunchKernelGGL((scatter_rows_kernel<T>), dim3(blocks, ncols), dim3(256), 0, ctx->stream, n, perm, (const T*)In, (T*)Out); });
+    return check_launch(ctx, "scatter_rows");
+}
+
+// The fused workspace: part1 | part2 (kFuseChunks x kFuseCols partial sums each, chunk-major; DCGS2 reads the two side by side as
+// one array of 2 kFuseCols columns) | h1 | h2 (kFuseCols each) | chk_part (the check's pairs, 2 kFuseChunks doubles) | nrm_part
+// (the |w|^2 of the second update's workgroups).  esz: bytes of an entry of the first four -- 16 everywhere (and for the byte
+// count) except in k_cgs2_fused on a real basis, which packs them by 8.
+struct FusedWork {
+    void *part1, *part2, *h1, *h2;
+    double *chk_part, *nrm_part;
+    static size_t part_bytes(size_t esz) { return esz * (size_t)kFuseChunks * kFuseCols; }
+    static size_t head_bytes(size_t esz) { return 2 * part_bytes(esz) + 2 * esz * kFuseCols + sizeof(double) * 2 * kFuseChunks; }  // in front of nrm_part
+    FusedWork(void* work, size_t esz) {
+        char* p = (char*)work;
+        part1 = p;
+        part2 = p + part_bytes(esz);
+        h1 = p + 2 * part_bytes(esz);
+        h2 = p + 2 * part_bytes(esz) + esz * kFuseCols;
+        nrm_part = (double*)(p + head_bytes(esz));
+        chk_part = nrm_part - 2 * kFuseChunks;
+    }
+};
+
+size_t k_cgs2_fused_work_bytes(lsa_ctx* ctx, int64_t n, int jmax) {
+    (void)ctx;
+    (void)jmax;
+    return FusedWork::head_bytes(16) + sizeof(double) * (size_t)((n + 63) / 64 + 8);
+}
+
+// what the fused forms handle: at most kFuseCols basis vectors, chunks of 1024 to 4096 rows (rpb_out)
+static bool cgs2_fused_shape(int64_t n, int j, int64_t* rpb_out) {
+    if (j <= 0 || j > kFuseCols || n <= 0) return false;
+    int64_t rpb = (n + kFuseChunks - 1) / kFuseChunks;
+    rpb = ((rpb + kThreads - 1) / kThreads) * kThreads;
+    if (rpb < 1024) rpb = 1024;  // (every workgroup of the axpy sums the partials of all chunks: few, fat chunks)
+    if (rpb > 4096) return false;  // long vectors: the second stages are noise there, and wider grids stream better
+    if (rpb_out) *rpb_out = rpb;
+    return true;
+}
+
 // CGS2 of w against V[:, 0:j] and v_next = w / ||w|| in five launches (see cgs_dot_kernel), with the inner solve's residual
 // check (chk_b, chk_z -> chk_out[2] = |b - z|^2, |b|^2; all three null: none) folded in.  `work` holds at least
 // k_cgs2_fused_work_bytes(ctx, n, j) bytes.  Returns 1 when the shape is outside what the fused form handles (nothing was
 // launched: the caller takes the kernel-per-stage path), LSA_OK or a negative status otherwise.
-size_t k_cgs2_fused_work_bytes(lsa_ctx* ctx, int64_t n, int jmax) {
-    (void)ctx;
-    (void)jmax;
-    return (size_t)16 * (size_t)(2 * kFuseChunks * kFuseCols + 2 * kFuseCols) + sizeof(double) * (size_t)(2 * kFuseChunks + (n + 63) / 64 + 8);
-}
-
 int k_cgs2_fused(lsa_ctx* ctx, int dtype, int64_t n, int j, const void* V, int64_t ldv, void* w, void* vnext, void* hcol_dev, void* work,
                  const void* chk_b, const void* chk_z, double* chk_out) {
-    if (j <= 0 || j > kFuseCols || n <= 0) return 1;
-    int64_t rpb = (n + kFuseChunks - 1) / kFuseChunks;
-    rpb = ((rpb + kThreads - 1) / kThreads) * kThreads;
-    if (rpb < 1024) rpb = 1024;  // (every workgroup of the axpy sums the partials of all chunks: few, fat chunks)
-    if (rpb > 4096) return 1;    // long vectors: the second stages are noise there, and wider grids stream better
+    int64_t rpb = 0;
+    if (!cgs2_fused_shape(n, j, &rpb)) return 1;
     const int nchunks = (int)((n + rpb - 1) / rpb);
     const int blocks = (int)((n + 63) / 64);  // workgroups of the axpy: 64 rows each
-    const size_t esz = dtype == LSA_C128 ? 16 : 8;
-    char* p = (char*)work;
-    void* part1 = p;
-    p += esz * (size_t)kFuseChunks * kFuseCols;
-    void* part2 = p;
-    p += esz * (size_t)kFuseChunks * kFuseCols;
-    void* h1 = p;
-    p += esz * kFuseCols;
-    void* h2 = p;
-    p += esz * kFuseCols;
-    double* chk_part = (double*)p;
-    double* nrm_part = chk_part + 2 * kFuseChunks;
+    const FusedWork fw(work, dtype == LSA_C128 ? 16 : 8);
+    void *part1 = fw.part1, *part2 = fw.part2, *h1 = fw.h1, *h2 = fw.h2;
+    double *chk_part = fw.chk_part, *nrm_part = fw.nrm_part;
     const dim3 dgrid(nchunks, (j + kColTile - 1) / kColTile);
     DISPATCH_T(dtype, {
         hipLaunchKernelGGL((cgs_dot_kernel<T>), dgrid, dim3(kThreads), 0, ctx->stream, n, j, rpb, (const T*)V, ldv, (const T*)w, (T*)part1, kFuseCols,
@@ -1295,16 +1330,6 @@ int k_cgs2_fused(lsa_ctx* ctx, int dtype, int64_t n, int j, const void* V, int64
                            j, (const T*)h1, (const T*)h2, (T*)hcol_dev);
     });
     return check_launch(ctx, "cgs2_fused");
-}
-
-static bool cgs2_fused_shape(int64_t n, int j, int64_t* rpb_out) {
-    if (j <= 0 || j > kFuseCols || n <= 0) return false;
-    int64_t rpb = (n + kFuseChunks - 1) / kFuseChunks;
-    rpb = ((rpb + kThreads - 1) / kThreads) * kThreads;
-    if (rpb < 1024) rpb = 1024;
-    if (rpb > 4096) return false;
-    if (rpb_out) *rpb_out = rpb;
-    return true;
 }
 
 bool k_cgs2_tail_fits(lsa_ctx* ctx, int64_t n, int jmax, const lsa_mat* M, const lsa_mat* C) {
@@ -1327,18 +1352,9 @@ int k_cgs2_fused_tail(lsa_ctx* ctx, int64_t n, int j, const void* V, int64_t ldv
     if (!cgs2_fused_shape(n, j, &rpb)) return lsa_set_error(ctx, LSA_ERR_ARG, "k_cgs2_fused_tail: shape outside the fused form");
     const int nchunks = (int)((n + rpb - 1) / rpb);
     const int blocks = (int)((n + 63) / 64);
-    const size_t esz = 16;
-    char* p = (char*)work;
-    void* part1 = p;
-    p += esz * (size_t)kFuseChunks * kFuseCols;
-    void* part2 = p;
-    p += esz * (size_t)kFuseChunks * kFuseCols;
-    void* h1 = p;
-    p += esz * kFuseCols;
-    void* h2 = p;
-    p += esz * kFuseCols;
-    double* chk_part = (double*)p;
-    double* nrm_part = chk_part + 2 * kFuseChunks;
+    const FusedWork fw(work, 16);
+    void *part1 = fw.part1, *part2 = fw.part2, *h1 = fw.h1, *h2 = fw.h2;
+    double* nrm_part = fw.nrm_part;
     const dim3 dgrid(nchunks, (j + kColTile - 1) / kColTile);
     hipLaunchKernelGGL((cgs_dot_kernel<T>), dgrid, dim3(kThreads), 0, ctx->stream, n, j, rpb, (const T*)V, ldv, (const T*)y, (T*)part1, kFuseCols,
                        (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
@@ -1371,10 +1387,6 @@ int k_cgs2_tail_checks(lsa_ctx* ctx, int nslots, int nparts, const double* tail_
 // the flush, which only makes V[:, j] final.  The check of the inner solve (chk_b, chk_z -> chk_out) rides as in k_cgs2_fused.
 bool k_dcgs2_fits(int64_t n, int ncv) { return cgs2_fused_shape(n, ncv + 1, nullptr); }
 
-// the check's pairs and the |w|^2 partials in the fused workspace (behind part1, part2, h1, h2 of k_cgs2_fused)
-static double* fused_chk_part(void* work) { return (double*)((char*)work + (size_t)16 * (size_t)(2 * kFuseChunks * kFuseCols + 2 * kFuseCols)); }
-static double* fused_nrm_part(void* work) { return fused_chk_part(work) + 2 * kFuseChunks; }
-
 int k_dcgs2_step(lsa_ctx* ctx, int64_t n, int j, void* V, int64_t ldv, const void* y, int first, void* slot, int lds, void* work,
                  const void* chk_b, const void* chk_z, double* chk_out) {
     int64_t rpb = 0;
@@ -1382,9 +1394,9 @@ int k_dcgs2_step(lsa_ctx* ctx, int64_t n, int j, void* V, int64_t ldv, const voi
         return lsa_set_error(ctx, LSA_ERR_ARG, "k_dcgs2_step: shape outside the fused form");
     const int nchunks = (int)((n + rpb - 1) / rpb);
     const int blocks = (int)((n + 63) / 64);
-    cplx* part = (cplx*)work;
-    double* chk_part = fused_chk_part(work);
-    double* nrm_part = fused_nrm_part(work);
+    const FusedWork fw(work, 16);
+    cplx* part = (cplx*)fw.part1;  // part1 and part2 as one array of ldp columns
+    double *chk_part = fw.chk_part, *nrm_part = fw.nrm_part;
     const dim3 dgrid(nchunks, (j + 1 + kColTile - 1) / kColTile);
     const int ldp = 2 * kFuseCols;
     if (y) {
@@ -1403,7 +1415,7 @@ int k_dcgs2_step(lsa_ctx* ctx, int64_t n, int j, void* V, int64_t ldv, const voi
 
 // the provisional ||V[:, j+1]|| of the step k_dcgs2_step just queued, into its slot (the form without a tail launch)
 int k_dcgs2_norm(lsa_ctx* ctx, int64_t n, void* work, void* slot, int lds) {
-    double* nrm_part = fused_nrm_part(work);
+    double* nrm_part = FusedWork(work, 16).nrm_part;
     hipLaunchKernelGGL(dcgs_norm_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)nrm_part, (int)((n + 63) / 64),
                        (cplx*)slot + 2 * (size_t)lds + 2);
     return check_launch(ctx, "dcgs2_norm");
@@ -1414,7 +1426,7 @@ int k_dcgs2_norm(lsa_ctx* ctx, int64_t n, void* work, void* slot, int lds) {
 int k_dcgs2_tail(lsa_ctx* ctx, int64_t n, int j, const void* V, int64_t ldv, const void* y, void* work, const lsa_mat* M, const lsa_mat* C, void* t,
                  double* tail_part, void* slot, int lds) {
     const int blocks = (int)((n + 63) / 64);
-    double* nrm_part = fused_nrm_part(work);
+    double* nrm_part = FusedWork(work, 16).nrm_part;
     const cplx* w = (const cplx*)V + (size_t)(j + 1) * (size_t)ldv;
     cplx* nout = (cplx*)slot + 2 * (size_t)lds + 2;
     const int tparts = k_cgs2_tail_parts(n);

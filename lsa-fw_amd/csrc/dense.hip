@@ -669,6 +669,69 @@ bool sym_eig(int n, double* a, int lda, double* d) {
     return true;
 }
 
+// ---- what the two outer loops (lsa_krylov_solve, lsa_lanczos_solve) share ------------------------------------------------
+int ks_check_options(lsa_ctx* ctx, const char* who, const lsa_ks_options* o, int32_t max_out, const void* theta_out, const void* lambda_out) {
+    if (o->nev < 1 || o->max_restarts < 0 || !(o->tol > 0.0) || max_out < 0 || (max_out > 0 && (!theta_out || !lambda_out)))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "%s: nev, tol must be positive, output buffers are required", who);
+    return LSA_OK;
+}
+double ks_keep_fraction(const lsa_ks_options* o) { return o->keep_fraction > 0.0 && o->keep_fraction < 1.0 ? o->keep_fraction : 0.5; }
+Rng ks_rng(const lsa_ks_options* o) { return Rng{o->seed * 0x2545F4914F6CDD1Dull + 0x1234567ull}; }
+
+// Expand the basis from `kept` to m vectors; continue past exact breakdowns (invariant subspace) with a fresh direction.
+// extend(j, &bd): the steps [j, m), bd = the step that broke down or -1; inject_random(j): a random vector orthonormalised into
+// column j.  Adds the operator applies to *applies.
+template <class Extend, class InjectRandom>
+int ks_expand(int kept, int m, int64_t* applies, Extend extend, InjectRandom inject_random) {
+    int j = kept;
+    while (j < m) {
+        int32_t bd = -1;
+        LSA_CHECK(extend(j, &bd));
+        if (bd < 0) {
+            *applies += m - j;
+            break;
+        }
+        *applies += bd - j + 1;
+        if (bd + 1 >= m) break;  // broke down on the last step: the m vectors span an invariant subspace
+        LSA_CHECK(inject_random(bd + 1));
+        j = bd + 1;
+    }
+    return LSA_OK;
+}
+
+// rank <- 0..m-1 sorted by key (stable); returns how many of the leading ones have a relative residual estimate within tol
+int ks_rank_converged(int m, const std::vector<double>& keys, const std::vector<double>& rel, double tol, std::vector<int>& rank) {
+    for (int c = 0; c < m; ++c) rank[(size_t)c] = c;
+    std::stable_sort(rank.begin(), rank.end(), [&](int x, int y) { return keys[(size_t)x] < keys[(size_t)y]; });
+    int nconv = 0;
+    while (nconv < m && rel[(size_t)rank[(size_t)nconv]] <= tol) ++nconv;
+    return nconv;
+}
+
+// vectors kept by a restart: the converged ones and keep_fraction of the rest, at least one and at most m - 1
+int ks_keep_count(int m, int nconv, double keep_fraction) { return std::max(std::min(nconv + (int)((m - nconv) * keep_fraction), m - 1), 1); }
+
+struct KsClock {  // seconds per phase of the outer loop; lap() books the time since the last lap
+    double expand = 0.0, dense = 0.0, restart = 0.0, t0 = 0.0;
+    void start() { t0 = now_s(); }
+    void lap(double& phase) {
+        const double t = now_s();
+        phase += t - t0;
+        t0 = t;
+    }
+};
+
+void ks_fill_result(lsa_ks_result* r, const KsClock& clk, int nconv, int nout, int restarts, int64_t applies, double next_unconverged) {
+    r->seconds_expand = clk.expand;
+    r->seconds_dense = clk.dense;
+    r->seconds_restart = clk.restart;
+    r->nconv = nconv;
+    r->nout = nout;
+    r->restarts = restarts;
+    r->op_applies = applies;
+    r->next_unconverged = next_unconverged;
+}
+
 }  // namespace
 
 extern "C" {
@@ -794,12 +857,11 @@ int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const
     int64_t n = 0;
     LSA_CHECK(lsa_krylov_shape(k, &n, &m));
     if (m > n) return lsa_set_error(ctx, LSA_ERR_ARG, "ncv = %d exceeds the problem size %lld", m, (long long)n);
-    if (o->nev < 1 || o->max_restarts < 0 || !(o->tol > 0.0) || max_out < 0 || (max_out > 0 && (!theta_out || !lambda_out)))
-        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve: nev, tol must be positive, output buffers are required");
+    LSA_CHECK(ks_check_options(ctx, "lsa_krylov_solve", o, max_out, theta_out, lambda_out));
     const int nev = std::min<int>(o->nev, m);
-    const double keep_fraction = o->keep_fraction > 0.0 && o->keep_fraction < 1.0 ? o->keep_fraction : 0.5;
+    const double keep_fraction = ks_keep_fraction(o);
     const Selector sel{o->which, o->transform, {o->sigma[0], o->sigma[1]}, {o->antishift[0], o->antishift[1]}, {o->target[0], o->target[1]}};
-    Rng rng{o->seed * 0x2545F4914F6CDD1Dull + 0x1234567ull};
+    Rng rng = ks_rng(o);
     std::vector<Z> vec((size_t)n);
     auto random_vector = [&]() {
         for (int64_t i = 0; i < n; ++i) {
@@ -825,27 +887,20 @@ int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const
     int kept = 0, restarts = 0;
     int64_t applies = 0;
     memset(result, 0, sizeof *result);
-    double t_expand = 0.0, t_dense = 0.0, t_restart = 0.0;
+    KsClock clk;
+    auto extend = [&](int j, int32_t* bd) {
+        LSA_CHECK(lsa_krylov_extend(ctx, k, j, m, H.data(), ldh, bd));
+        if (*bd >= 0) Hm(*bd + 1, *bd) = {0.0, 0.0};
+        return (int)LSA_OK;
+    };
+    auto inject_random = [&](int j) {
+        random_vector();
+        return lsa_krylov_inject(ctx, k, j, vec.data());
+    };
     while (true) {
-        // ---- expand to m vectors; continue past exact breakdowns (invariant subspace) with a fresh direction ----
-        double t0 = now_s();
-        int j = kept;
-        while (j < m) {
-            int32_t bd = -1;
-            LSA_CHECK(lsa_krylov_extend(ctx, k, j, m, H.data(), ldh, &bd));
-            if (bd < 0) {
-                applies += m - j;
-                break;
-            }
-            applies += bd - j + 1;
-            Hm(bd + 1, bd) = {0.0, 0.0};
-            if (bd + 1 >= m) break;  // broke down on the last step: the m vectors span an invariant subspace
-            random_vector();
-            LSA_CHECK(lsa_krylov_inject(ctx, k, bd + 1, vec.data()));
-            j = bd + 1;
-        }
-        t_expand += now_s() - t0;
-        t0 = now_s();
+        clk.start();
+        LSA_CHECK(ks_expand(kept, m, &applies, extend, inject_random));
+        clk.lap(clk.expand);
         for (int c = 0; c < m; ++c) {
             b[(size_t)c] = Hm(m, c);  // b^H: the row under the square part
             for (int r = 0; r < m; ++r) Tm(r, c) = Hm(r, c);
@@ -865,11 +920,8 @@ int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const
             w[(size_t)c] = Tm(c, c);
             keys[(size_t)c] = sel.key(w[(size_t)c]);
             rel[(size_t)c] = est[(size_t)c] / std::max(zabs(w[(size_t)c]), 2.2250738585072014e-308);
-            rank[(size_t)c] = c;
         }
-        std::stable_sort(rank.begin(), rank.end(), [&](int x, int y) { return keys[(size_t)x] < keys[(size_t)y]; });
-        int nconv = 0;
-        while (nconv < m && rel[(size_t)rank[(size_t)nconv]] <= o->tol) ++nconv;
+        const int nconv = ks_rank_converged(m, keys, rel, o->tol, rank);
         if (nconv >= nev || nconv >= m || restarts >= o->max_restarts) {
             const int nout = std::min<int>(nconv, max_out);
             if (nout > 0) {
@@ -885,26 +937,16 @@ int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const
                     ((Z*)lambda_out)[c] = sel.back(w[(size_t)src]);
                     if (est_out) est_out[c] = rel[(size_t)src];
                 }
-                t_dense += now_s() - t0;
-                t0 = now_s();
+                clk.lap(clk.dense);
                 if (X_out) LSA_CHECK(lsa_krylov_ritz_vectors(ctx, k, m, nout, Y.data(), m, 3, X_out));
-                t_restart += now_s() - t0;
-                t0 = now_s();
+                clk.lap(clk.restart);
             }
-            t_dense += now_s() - t0;
-            result->seconds_expand = t_expand;
-            result->seconds_dense = t_dense;
-            result->seconds_restart = t_restart;
-            result->nconv = nconv;
-            result->nout = nout;
-            result->restarts = restarts;
-            result->op_applies = applies;
-            result->next_unconverged = nconv < m ? rel[(size_t)rank[(size_t)nconv]] : 0.0;
+            clk.lap(clk.dense);
+            ks_fill_result(result, clk, nconv, nout, restarts, applies, nconv < m ? rel[(size_t)rank[(size_t)nconv]] : 0.0);
             return k_agree_in_step(ctx, "lsa_krylov_solve");  // (a sharded solve ends with the ranks comparing their exchange counts)
         }
         // ---- truncate to the wanted part of the Schur form and restart ----
-        int knew = nconv + (int)((m - nconv) * keep_fraction);
-        knew = std::max(std::min(knew, m - 1), 1);
+        int knew = ks_keep_count(m, nconv, keep_fraction);
         {
             // ties at the selection threshold are all selected (what a sort callback of the Schur routine would do)
             std::vector<double> sorted(keys);
@@ -914,10 +956,9 @@ int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const
             const int sdim = schur_reorder(m, Tm, Qm, select);
             knew = std::max(std::min(sdim, m - 1), 1);
         }
-        t_dense += now_s() - t0;
-        t0 = now_s();
+        clk.lap(clk.dense);
         LSA_CHECK(lsa_krylov_restart(ctx, k, m, knew, Q.data(), m));
-        t_restart += now_s() - t0;
+        clk.lap(clk.restart);
         std::fill(H.begin(), H.end(), Z{0.0, 0.0});
         for (int c = 0; c < knew; ++c) {
             for (int r = 0; r <= c; ++r) Hm(r, c) = Tm(r, c);
@@ -979,8 +1020,7 @@ int lsa_lanczos_solve(lsa_ctx* ctx, lsa_lanczos* l, const lsa_ks_options* o, con
     int32_t m = 0;
     int64_t n = 0;
     LSA_CHECK(lanczos_shape(l, &n, &m));
-    if (o->nev < 1 || o->max_restarts < 0 || !(o->tol > 0.0) || max_out < 0 || (max_out > 0 && (!theta_out || !lambda_out)))
-        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_solve: nev, tol must be positive, output buffers are required");
+    LSA_CHECK(ks_check_options(ctx, "lsa_lanczos_solve", o, max_out, theta_out, lambda_out));
     if (o->transform != 0 || o->sigma[1] != 0.0 || o->target[1] != 0.0)
         return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_solve: shift-invert (transform 0) with a real shift and a real target only");
     switch (o->which) {
@@ -990,9 +1030,9 @@ int lsa_lanczos_solve(lsa_ctx* ctx, lsa_lanczos* l, const lsa_ks_options* o, con
     }
     max_out = std::min(max_out, m);
     const int nev = std::min<int>(o->nev, m);
-    const double keep_fraction = o->keep_fraction > 0.0 && o->keep_fraction < 1.0 ? o->keep_fraction : 0.5;
+    const double keep_fraction = ks_keep_fraction(o);
     const Selector sel{o->which, 0, {o->sigma[0], 0.0}, {0.0, 0.0}, {o->target[0], 0.0}};
-    Rng rng{o->seed * 0x2545F4914F6CDD1Dull + 0x1234567ull};
+    Rng rng = ks_rng(o);
     std::vector<double> vec((size_t)n);
     auto random_vector = [&]() {
         double other = 0.0;
@@ -1008,26 +1048,16 @@ int lsa_lanczos_solve(lsa_ctx* ctx, lsa_lanczos* l, const lsa_ks_options* o, con
     int kept = 0, restarts = 0;
     int64_t applies = 0;
     memset(result, 0, sizeof *result);
-    double t_expand = 0.0, t_dense = 0.0, t_restart = 0.0;
+    KsClock clk;
+    auto extend = [&](int j, int32_t* bd) { return lsa_lanczos_extend(ctx, l, j, m, T.data(), ldt, bd); };
+    auto inject_random = [&](int j) {
+        random_vector();
+        return lanczos_inject(ctx, l, j, vec.data());
+    };
     while (true) {
-        // ---- expand to m vectors; continue past exact breakdowns (invariant subspace) with a fresh direction ----
-        double t0 = now_s();
-        int j = kept;
-        while (j < m) {
-            int32_t bd = -1;
-            LSA_CHECK(lsa_lanczos_extend(ctx, l, j, m, T.data(), ldt, &bd));
-            if (bd < 0) {
-                applies += m - j;
-                break;
-            }
-            applies += bd - j + 1;
-            if (bd + 1 >= m) break;  // broke down on the last step: the m vectors span an invariant subspace
-            random_vector();
-            LSA_CHECK(lanczos_inject(ctx, l, bd + 1, vec.data()));
-            j = bd + 1;
-        }
-        t_expand += now_s() - t0;
-        t0 = now_s();
+        clk.start();
+        LSA_CHECK(ks_expand(kept, m, &applies, extend, inject_random));
+        clk.lap(clk.expand);
         const double beta = Tm(m, m - 1);
         for (int c = 0; c < m; ++c)
             for (int r = 0; r < m; ++r) Y[(size_t)c * m + r] = Tm(r, c);
@@ -1038,11 +1068,8 @@ int lsa_lanczos_solve(lsa_ctx* ctx, lsa_lanczos* l, const lsa_ks_options* o, con
             est[(size_t)c] = std::fabs(beta * Y[(size_t)c * m + (m - 1)]);
             keys[(size_t)c] = sel.key(Z{theta[(size_t)c], 0.0});
             rel[(size_t)c] = est[(size_t)c] / std::max(std::fabs(theta[(size_t)c]), 2.2250738585072014e-308);
-            rank[(size_t)c] = c;
         }
-        std::stable_sort(rank.begin(), rank.end(), [&](int x, int y) { return keys[(size_t)x] < keys[(size_t)y]; });
-        int nconv = 0;
-        while (nconv < m && rel[(size_t)rank[(size_t)nconv]] <= o->tol) ++nconv;
+        const int nconv = ks_rank_converged(m, keys, rel, o->tol, rank);
         if (nconv >= nev || nconv >= m || restarts >= o->max_restarts) {
             const int nout = std::min<int>(nconv, max_out);
             if (nout > 0) {
@@ -1054,32 +1081,21 @@ int lsa_lanczos_solve(lsa_ctx* ctx, lsa_lanczos* l, const lsa_ks_options* o, con
                     lambda_out[c] = sel.back(Z{theta[(size_t)src], 0.0}).re;
                     if (est_out) est_out[c] = rel[(size_t)src];
                 }
-                t_dense += now_s() - t0;
-                t0 = now_s();
+                clk.lap(clk.dense);
                 if (X_out) LSA_CHECK(lanczos_ritz_vectors(ctx, l, m, nout, Yo.data(), m, X_out));
-                t_restart += now_s() - t0;
-                t0 = now_s();
+                clk.lap(clk.restart);
             }
-            t_dense += now_s() - t0;
-            result->seconds_expand = t_expand;
-            result->seconds_dense = t_dense;
-            result->seconds_restart = t_restart;
-            result->nconv = nconv;
-            result->nout = nout;
-            result->restarts = restarts;
-            result->op_applies = applies;
-            result->next_unconverged = nconv < m ? rel[(size_t)rank[(size_t)nconv]] : 0.0;
+            clk.lap(clk.dense);
+            ks_fill_result(result, clk, nconv, nout, restarts, applies, nconv < m ? rel[(size_t)rank[(size_t)nconv]] : 0.0);
             return LSA_OK;
         }
         // ---- keep the wanted Ritz vectors and restart: T <- diag(theta_kept) with the spike beta y_{m,i} in row and column knew ----
-        int knew = nconv + (int)((m - nconv) * keep_fraction);
-        knew = std::max(std::min(knew, m - 1), 1);
+        const int knew = ks_keep_count(m, nconv, keep_fraction);
         std::vector<double> Yk((size_t)m * knew);
         for (int c = 0; c < knew; ++c) memcpy(&Yk[(size_t)c * m], &Y[(size_t)rank[(size_t)c] * m], (size_t)m * sizeof(double));
-        t_dense += now_s() - t0;
-        t0 = now_s();
+        clk.lap(clk.dense);
         LSA_CHECK(lanczos_restart(ctx, l, m, knew, Yk.data(), m));
-        t_restart += now_s() - t0;
+        clk.lap(clk.restart);
         std::fill(T.begin(), T.end(), 0.0);
         for (int c = 0; c < knew; ++c) {
             const int src = rank[(size_t)c];

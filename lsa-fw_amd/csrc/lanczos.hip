@@ -244,13 +244,6 @@ __global__ __launch_bounds__(kLzThreads) void lz_sign_kernel(int64_t n, double* 
         for (int64_t i = threadIdx.x; i < n; i += kLzThreads) x[i] = -x[i];
 }
 
-// out[perm[i], c] = in[i, c]  (column-major n x ncols; grid.y = column)
-__global__ void lz_scatter_rows_kernel(int64_t n, const int32_t* __restrict__ perm, const double* __restrict__ in, double* __restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const size_t off = (size_t)blockIdx.y * (size_t)n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[off + (size_t)perm[i]] = in[off + (size_t)i];
-}
-
 int lz_check_launch(lsa_ctx* ctx, const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return lsa_set_error(ctx, LSA_ERR_HIP, "%s: kernel launch failed: %s", what, hipGetErrorString(e));
@@ -259,7 +252,7 @@ int lz_check_launch(lsa_ctx* ctx, const char* what) {
 
 // the fused kernels unless LSA_LANCZOS_FUSED=0 (read once per process, like LSA_KRYLOV_FUSED): then k_multi_dot + k_multi_axpy
 bool lz_fused() {
-    static const bool fused = !(getenv("LSA_LANCZOS_FUSED") && atoi(getenv("LSA_LANCZOS_FUSED")) == 0);
+    static const bool fused = env_flag("LSA_LANCZOS_FUSED", true);
     return fused;
 }
 
@@ -396,12 +389,7 @@ int lanczos_inject(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, const double* host_v
 int lanczos_restart(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t knew, const double* Y, int32_t ldy) {
     if (!ctx || !l || !Y) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos restart: null argument");
     if (m < 1 || m > l->ncv || knew < 1 || knew > m || ldy < m) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos restart: bad sizes m=%d knew=%d", m, knew);
-    LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)m * knew * sizeof(double)));
-    double* p = (double*)ctx->pinned;
-    for (int32_t c = 0; c < knew; ++c)
-        for (int32_t r = 0; r < m; ++r) p[(size_t)c * m + r] = Y[(size_t)c * ldy + r];
-    LSA_HIP_CHECK(ctx, hipMemcpyAsync(l->qdev, p, (size_t)m * knew * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    LSA_CHECK(k_basis_gemm(ctx, LSA_F64, l->n, m, knew, l->V, l->n, l->qdev, m, l->V2, l->n));
+    LSA_CHECK(basis_times_host_matrix(ctx, LSA_F64, l->n, m, knew, l->V, Y, ldy, l->qdev, l->V2, 0));
     LSA_CHECK(k_copy(ctx, LSA_F64, l->n, lz_col(l, m), l->V2 + (size_t)knew * (size_t)l->n));
     LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     std::swap(l->V, l->V2);
@@ -415,18 +403,12 @@ int lanczos_ritz_vectors(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t nvec, 
     if (m < 1 || m > l->ncv || nvec < 0 || nvec > l->ncv || ldy < m) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos vectors: bad sizes");
     if (nvec == 0) return LSA_OK;
     const size_t vb = (size_t)l->n * sizeof(double);
-    LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)m * nvec * sizeof(double)));
-    double* p = (double*)ctx->pinned;
-    for (int32_t c = 0; c < nvec; ++c)
-        for (int32_t r = 0; r < m; ++r) p[(size_t)c * m + r] = Y[(size_t)c * ldy + r];
-    LSA_HIP_CHECK(ctx, hipMemcpyAsync(l->qdev, p, (size_t)m * nvec * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    LSA_CHECK(k_basis_gemm(ctx, LSA_F64, l->n, m, nvec, l->V, l->n, l->qdev, m, l->V2, l->n));
+    LSA_CHECK(basis_times_host_matrix(ctx, LSA_F64, l->n, m, nvec, l->V, Y, ldy, l->qdev, l->V2, 0));
     hipLaunchKernelGGL(lz_sign_kernel, dim3(nvec), dim3(kLzThreads), 0, ctx->stream, l->n, l->V2, l->n);
     const double* src = l->V2;
     if (l->row_perm) {
         if (!l->xtmp) LSA_HIP_ALLOC(ctx, hipMalloc((void**)&l->xtmp, std::max<size_t>(vb, 8) * (size_t)(l->ncv + 1)));
-        const int blocks = (int)std::max<int64_t>(std::min<int64_t>((l->n + 255) / 256, (int64_t)ctx->num_cu * 16), 1);
-        hipLaunchKernelGGL(lz_scatter_rows_kernel, dim3(blocks, nvec), dim3(256), 0, ctx->stream, l->n, l->row_perm, (const double*)l->V2, l->xtmp);
+        LSA_CHECK(k_scatter_rows(ctx, LSA_F64, l->n, nvec, l->row_perm, l->V2, l->xtmp));
         src = l->xtmp;
     }
     LSA_CHECK(lz_check_launch(ctx, "lanczos vectors"));
@@ -479,18 +461,7 @@ void lsa_lanczos_destroy(lsa_lanczos* l) {
 
 int lsa_lanczos_set_row_permutation(lsa_ctx* ctx, lsa_lanczos* l, const int32_t* perm) {
     if (!ctx || !l) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_set_row_permutation: null argument");
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (l->row_perm) (void)hipFree(l->row_perm);
-    l->row_perm = nullptr;
-    if (!perm) return LSA_OK;
-    std::vector<char> seen((size_t)l->n, 0);
-    for (int64_t i = 0; i < l->n; ++i) {
-        if (perm[i] < 0 || perm[i] >= l->n || seen[(size_t)perm[i]]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_set_row_permutation: not a permutation of 0..n-1");
-        seen[(size_t)perm[i]] = 1;
-    }
-    LSA_HIP_ALLOC(ctx, hipMalloc((void**)&l->row_perm, sizeof(int32_t) * (size_t)std::max<int64_t>(l->n, 1)));
-    LSA_HIP_CHECK(ctx, hipMemcpy(l->row_perm, perm, sizeof(int32_t) * (size_t)l->n, hipMemcpyHostToDevice));
-    return LSA_OK;
+    return basis_upload_row_permutation(ctx, "lsa_lanczos_set_row_permutation", l->n, perm, &l->row_perm);
 }
 
 int lsa_lanczos_set_start(lsa_ctx* ctx, lsa_lanczos* l, const double* host_v) { return lanczos_inject(ctx, l, 0, host_v); }
@@ -514,17 +485,9 @@ int lsa_lanczos_extend(lsa_ctx* ctx, lsa_lanczos* l, int32_t j0, int32_t j1, dou
         }
         while (true) {
             const bool refine = *l->P.refine;
-            rc = ndlu_solve_dev(ctx, l->P.nd, LSA_F64, l->rhs[l->cur], l->w);
-            if (rc == LSA_OK) rc = k_spmv(ctx, l->P.Kfac, LSA_F64, l->w, l->z);
-            if (rc == LSA_OK && refine) {
-                // w += C^-1 (rhs - C w): takes what large factors leave behind to rounding level
-                rc = k_residual_norms(ctx, LSA_F64, n, l->rhs[l->cur], l->z, l->r, l->chk_part);
-                if (rc == LSA_OK) rc = ndlu_solve_dev(ctx, l->P.nd, LSA_F64, l->r, l->z);
-                const double one[2] = {1.0, 0.0};
-                if (rc == LSA_OK) rc = k_axpy(ctx, LSA_F64, n, one, l->z, l->w);
-                if (rc == LSA_OK) rc = k_spmv(ctx, l->P.Kfac, LSA_F64, l->w, l->z);
-                if (rc == LSA_OK) rc = k_nrm2(ctx, LSA_F64, n, l->w, l->slot + b2_at + 4);  // for the backward-error judgement below
-            }
+            // (w += C^-1 (rhs - C w) with refine: takes what large factors leave behind to rounding level)
+            rc = direct_solve_enqueue(ctx, l->op, LSA_F64, l->rhs[l->cur], l->w, l->z, l->r, refine, l->chk_part);
+            if (rc == LSA_OK && refine) rc = k_nrm2(ctx, LSA_F64, n, l->w, l->slot + b2_at + 4);  // for the backward-error judgement below
             if (rc == LSA_OK) rc = lz_orth_tail(ctx, l, j + 1, j + 1, true);
             if (rc == LSA_OK) rc = lz_read_slot(ctx, l);
             if (rc != LSA_OK) break;
@@ -534,12 +497,7 @@ int lsa_lanczos_extend(lsa_ctx* ctx, lsa_lanczos* l, int32_t j0, int32_t j1, dou
             const bool backward = refine && res > rtol * bnorm && l->P.normF > 0.0 && res <= 1e-12 * l->P.normF * std::sqrt(l->hslot[b2_at + 4]);
             if (backward) ++st->backward_accepted;
             if (res <= rtol * bnorm || backward) {
-                ++st->op_applies;
-                st->spmv_calls += refine ? 2 : 1;
-                st->sptrsv_calls += refine ? 4 : 2;
-                if (refine) ++st->refined_solves;
-                st->last_rel_res = bnorm > 0.0 ? res / bnorm : 0.0;
-                st->max_rel_res = std::max(st->max_rel_res, st->last_rel_res);
+                stats_book_direct_solve(st, 1, refine, res, bnorm);
                 break;
             }
             if (!refine && std::isfinite(res)) {  // from here on every step carries the refinement step; this one is done again

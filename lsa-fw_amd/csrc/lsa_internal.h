@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -190,6 +191,11 @@ int k_agree_status(lsa_ctx* ctx, int rc);  // comm.hip: collective agreement on 
 int k_agree_min_i64(lsa_ctx* ctx, int64_t* value);  // comm.hip: the smallest of the ranks' values (collective)
 int k_agree_in_step(lsa_ctx* ctx, const char* where);  // comm.hip: error on every rank unless all ranks have made the same number of exchanges (collective)
 int lsa_ensure_scratch(lsa_ctx* ctx, size_t dbytes, size_t hbytes);
+// an on/off LSA_* switch of the environment: unset -> dflt, else whether its value reads as a non-zero integer
+inline bool env_flag(const char* name, bool dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) != 0 : dflt;
+}
 
 #define LSA_HIP_CHECK(ctx, expr)                                                                         \
     do {                                                                                                 \
@@ -273,6 +279,22 @@ int k_spmv_plain_subwave_lanes(const lsa_mat* A);  // spmv.hip
 // Out[:, 0:k] = V[:, 0:m] Q   (Q m x k column-major on the device, ldq)
 int k_basis_gemm(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V, int64_t ldv, const void* Q, int ldq,
                  void* Out, int64_t ldo);
+// Out[perm[i], c] = In[i, c] for the columns c < ncols (both n x ncols, leading dimension n)
+int k_scatter_rows(lsa_ctx* ctx, int dtype, int64_t n, int ncols, const int32_t* perm, const void* In, void* Out);
+
+// ---- what the basis handles lsa_krylov (solver.hip) and lsa_lanczos (lanczos.hip) share (solver.hip) ----------------------
+// *row_perm <- a device copy of perm after checking that it permutes 0..n-1 (null: dropped); who: the caller's name for the message
+int basis_upload_row_permutation(lsa_ctx* ctx, const char* who, int64_t n, const int32_t* perm, int32_t** row_perm);
+// Out[:, 0:k] = V[:, 0:m] Q for a host matrix Q (m x k, leading dimension ldq; V and Out: n): packed densely into the pinned
+// scratch (kept pinned_extra bytes longer for the caller), uploaded to qdev, k_basis_gemm
+int basis_times_host_matrix(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V, const void* Q, int ldq, void* qdev, void* Out,
+                            size_t pinned_extra);
+// The direct inner solve of a Krylov step, queued without a read-back: y = C^-1 rhs, z = C y and, with refine, one step of
+// iterative refinement (r = rhs - z, z = C^-1 r, y += z, z = C y; the two sums of that residual pass land in norms[0..2]).  C is
+// the operator's factorised matrix with its exact LU, rows and exchanges as the operator has them; the caller judges rhs - z.
+int direct_solve_enqueue(lsa_ctx* ctx, lsa_op* op, int dtype, const void* rhs, void* y, void* z, void* r, bool refine, double* norms);
+// books one accepted direct solve of relative residual res / bnorm: `products` sparse products besides the refinement's one
+void stats_book_direct_solve(lsa_stats* st, int products, bool refine, double res, double bnorm);
 
 // ---- what the Lanczos iteration (lanczos.hip) needs of a shift-invert operator (solver.hip) -------------------------------
 struct lsa_ndlu;

@@ -19,6 +19,23 @@ inline double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// The switches of the Krylov steps ("Environment knobs"), read once per process.
+struct KrylovSwitches {
+    bool fused;        // LSA_KRYLOV_FUSED (default on): CGS2 in five launches where the shape allows; off: a kernel per stage
+    bool four_passes;  // LSA_KRYLOV_PASSES=4: the per-stage CGS2 takes four passes over the basis instead of three
+    bool tail;         // LSA_KRYLOV_TAIL (default on): the tail form of a pipelined step
+    bool delayed;      // LSA_KRYLOV_DELAYED (default on): DCGS2 in the pipelined steps
+    bool timing;       // LSA_KRYLOV_TIMING set: print queueing and waiting time per batch
+};
+const KrylovSwitches& krylov_switches() {
+    static const KrylovSwitches sw = [] {
+        const char* passes = getenv("LSA_KRYLOV_PASSES");
+        return KrylovSwitches{env_flag("LSA_KRYLOV_FUSED", true), passes && atoi(passes) == 4, env_flag("LSA_KRYLOV_TAIL", true),
+                              env_flag("LSA_KRYLOV_DELAYED", true), getenv("LSA_KRYLOV_TIMING") != nullptr};
+    }();
+    return sw;
+}
+
 // small device arrays used by the orthogonalisation (sized for `cap` basis vectors)
 struct OrthWork {
     void *h1 = nullptr, *h2 = nullptr, *hcol = nullptr;
@@ -47,20 +64,30 @@ struct OrthWork {
     }
 };
 
+// the check of an inner solve that rides along with an orthogonalisation: out[0..2] = |b - z|^2, |b|^2 (r takes b - z where the
+// check is a kernel of its own)
+struct SolveCheck {
+    const void *b, *z;
+    void* r;
+    double* out;
+};
+
 // the device part of CGS2: orthogonalise w against V[:, 0:j] and normalise into vnext; the j+1 Hessenberg entries go to
-// `hcol_dev`, nothing is read back
+// `hcol_dev`, nothing is read back.  Five launches where the switches and the shape allow it, else a kernel per stage with
+// three passes over the basis where k_multi_axpy_dot takes the shape, else four: the two fallbacks are selected by size.
 int orthonormalize_enqueue(lsa_ctx* ctx, int dtype, int64_t n, const void* V, int64_t ldv, int j, void* w, void* vnext, OrthWork& ow,
-                           void* hcol_dev) {
-    static const bool fuse = !(getenv("LSA_KRYLOV_FUSED") && atoi(getenv("LSA_KRYLOV_FUSED")) == 0);
-    if (fuse) {  // five launches instead of nine where the shape allows it (same arithmetic as the batched Arnoldi steps)
+                           void* hcol_dev, const SolveCheck* chk = nullptr) {
+    const KrylovSwitches& sw = krylov_switches();
+    if (sw.fused) {  // (the check rides in the first reduction)
         LSA_CHECK(ow.ensure_fused(ctx, n));
-        const int frc = k_cgs2_fused(ctx, dtype, n, j, V, ldv, w, vnext, hcol_dev, ow.fused, nullptr, nullptr, nullptr);
+        const int frc = k_cgs2_fused(ctx, dtype, n, j, V, ldv, w, vnext, hcol_dev, ow.fused, chk ? chk->b : nullptr, chk ? chk->z : nullptr,
+                                     chk ? chk->out : nullptr);
         if (frc <= 0) return frc;
     }
+    if (chk) LSA_CHECK(k_residual_norms(ctx, dtype, n, chk->b, chk->z, chk->r, chk->out));
     LSA_CHECK(k_multi_dot(ctx, dtype, n, j, V, ldv, w, ow.h1));
     // long vectors: the first projection and the second dot product share one pass over the basis (three passes instead of four)
-    static const bool three = !(getenv("LSA_KRYLOV_PASSES") && atoi(getenv("LSA_KRYLOV_PASSES")) == 4);
-    const int arc = three ? k_multi_axpy_dot(ctx, dtype, n, j, V, ldv, ow.h1, w, ow.h2) : 1;
+    const int arc = sw.four_passes ? 1 : k_multi_axpy_dot(ctx, dtype, n, j, V, ldv, ow.h1, w, ow.h2);
     if (arc < 0) return arc;
     if (arc > 0) {
         LSA_CHECK(k_multi_axpy(ctx, dtype, n, j, V, ldv, ow.h1, w, nullptr));
@@ -394,13 +421,6 @@ int gmres_run(lsa_ctx* ctx, const lsa_mat* C, PcRef pc, int dtype, const void* b
     return LSA_OK;
 }
 
-// out[perm[i], c] = in[i, c]  (column-major n x ncols; grid.y = column)
-__global__ void scatter_rows_kernel(int64_t n, const int32_t* __restrict__ perm, const cplx* __restrict__ in, cplx* __restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const size_t off = (size_t)blockIdx.y * (size_t)n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[off + (size_t)perm[i]] = in[off + (size_t)i];
-}
-
 template <typename T>
 __global__ void shift_diag_kernel(int32_t n, int32_t row0, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
                                   T* __restrict__ val, cplx shift, int32_t* __restrict__ missing) {
@@ -457,6 +477,16 @@ struct lsa_op {
     bool refine = false;     // queued Arnoldi steps carry one step of iterative refinement (set the first time a direct solve misses rtol)
     lsa_stats st;
 };
+
+static PcRef pc_of(const lsa_op* op) {
+    PcRef pc;
+    pc.ilu = op->pc;
+    pc.nd = op->nd;
+    pc.nd_dist = op->nd_dist;
+    pc.adjoint = op->adjoint;
+    pc.normF = op->normF;
+    return pc;
+}
 
 struct lsa_krylov {
     lsa_ctx* ctx;
@@ -757,13 +787,7 @@ static int op_apply_dev(lsa_ctx* ctx, lsa_op* op, const void* x, void* y) {
         LSA_CHECK(op->gw.alloc(ctx, op->n, restart, dtype));
         op->gw_ready = true;
     }
-    PcRef pcr;
-    pcr.ilu = op->pc;
-    pcr.nd = op->nd;
-    pcr.nd_dist = op->nd_dist;
-    pcr.adjoint = op->adjoint;
-    pcr.normF = op->normF;
-    LSA_CHECK(gmres_run(ctx, op->Kfac, pcr, dtype, rhs, y, false, op->opts.ksp_rtol, op->opts.ksp_maxit, op->gw, nullptr, nullptr, &op->st));
+    LSA_CHECK(gmres_run(ctx, op->Kfac, pc_of(op), dtype, rhs, y, false, op->opts.ksp_rtol, op->opts.ksp_maxit, op->gw, nullptr, nullptr, &op->st));
     if (op->keep) LSA_CHECK(k_mask(ctx, dtype, op->n, op->keep, y));
     return LSA_OK;
 }
@@ -829,6 +853,56 @@ int lsa_op_get_parts(lsa_op* op, lsa_op_parts* out) {
     out->refine = &op->refine;
     out->st = &op->st;
     return LSA_OK;
+}
+
+int direct_solve_enqueue(lsa_ctx* ctx, lsa_op* op, int dtype, const void* rhs, void* y, void* z, void* r, bool refine, double* norms) {
+    const PcRef pc = pc_of(op);
+    const lsa_mat* C = op->Kfac;
+    LSA_CHECK(pc_global(ctx, pc, C->row0, op->n, dtype, rhs, y));
+    LSA_CHECK(spmv_global(ctx, C, dtype, y, z, op->adjoint));
+    if (refine) {
+        // y += C^-1 (rhs - C y): the factors of a large 3D problem leave 1e-11 of the right-hand side behind, this step takes it to
+        // rounding level
+        LSA_CHECK(k_residual_norms(ctx, dtype, op->n, rhs, z, r, norms));
+        LSA_CHECK(pc_global(ctx, pc, C->row0, op->n, dtype, r, z));
+        const double one[2] = {1.0, 0.0};
+        LSA_CHECK(k_axpy(ctx, dtype, op->n, one, z, y));
+        LSA_CHECK(spmv_global(ctx, C, dtype, y, z, op->adjoint));
+    }
+    return LSA_OK;
+}
+
+void stats_book_direct_solve(lsa_stats* st, int products, bool refine, double res, double bnorm) {
+    ++st->op_applies;
+    st->spmv_calls += products + (refine ? 1 : 0);
+    st->sptrsv_calls += refine ? 4 : 2;
+    if (refine) ++st->refined_solves;
+    st->last_rel_res = bnorm > 0.0 ? res / bnorm : 0.0;
+    st->max_rel_res = std::max(st->max_rel_res, st->last_rel_res);
+}
+
+int basis_upload_row_permutation(lsa_ctx* ctx, const char* who, int64_t n, const int32_t* perm, int32_t** row_perm) {
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (*row_perm) (void)hipFree(*row_perm);
+    *row_perm = nullptr;
+    if (!perm) return LSA_OK;
+    std::vector<char> seen((size_t)n, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        if (perm[i] < 0 || perm[i] >= n || seen[(size_t)perm[i]]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: not a permutation of 0..n-1", who);
+        seen[(size_t)perm[i]] = 1;
+    }
+    LSA_HIP_ALLOC(ctx, hipMalloc((void**)row_perm, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)));
+    LSA_HIP_CHECK(ctx, hipMemcpy(*row_perm, perm, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+    return LSA_OK;
+}
+
+int basis_times_host_matrix(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V, const void* Q, int ldq, void* qdev, void* Out,
+                            size_t pinned_extra) {
+    const size_t es = esize(dtype), qbytes = (size_t)m * k * es;
+    LSA_CHECK(lsa_ensure_scratch(ctx, 0, qbytes + pinned_extra));
+    for (int c = 0; c < k; ++c) memcpy((char*)ctx->pinned + (size_t)c * m * es, (const char*)Q + (size_t)c * ldq * es, (size_t)m * es);
+    LSA_HIP_CHECK(ctx, hipMemcpyAsync(qdev, ctx->pinned, qbytes, hipMemcpyHostToDevice, ctx->stream));
+    return k_basis_gemm(ctx, dtype, n, m, k, V, n, qdev, m, Out, n);
 }
 
 extern "C" {
@@ -919,18 +993,7 @@ int lsa_krylov_shape(const lsa_krylov* k, int64_t* n, int32_t* ncv) {
 
 int lsa_krylov_set_row_permutation(lsa_ctx* ctx, lsa_krylov* k, const int32_t* perm) {
     if (!ctx || !k) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_set_row_permutation: null argument");
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (k->row_perm) (void)hipFree(k->row_perm);
-    k->row_perm = nullptr;
-    if (!perm) return LSA_OK;
-    std::vector<char> seen((size_t)k->n, 0);
-    for (int64_t i = 0; i < k->n; ++i) {
-        if (perm[i] < 0 || perm[i] >= k->n || seen[(size_t)perm[i]]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_set_row_permutation: not a permutation of 0..n-1");
-        seen[(size_t)perm[i]] = 1;
-    }
-    LSA_HIP_ALLOC(ctx, hipMalloc((void**)&k->row_perm, sizeof(int32_t) * (size_t)std::max<int64_t>(k->n, 1)));
-    LSA_HIP_CHECK(ctx, hipMemcpy(k->row_perm, perm, sizeof(int32_t) * (size_t)k->n, hipMemcpyHostToDevice));
-    return LSA_OK;
+    return basis_upload_row_permutation(ctx, "lsa_krylov_set_row_permutation", k->n, perm, &k->row_perm);
 }
 
 int lsa_krylov_set_start(lsa_ctx* ctx, lsa_krylov* k, const void* host_v) {
@@ -956,332 +1019,282 @@ int lsa_krylov_inject(lsa_ctx* ctx, lsa_krylov* k, int32_t j, const void* host_v
     return LSA_OK;
 }
 
-// One batch of Arnoldi steps [j, j + nb) queued without a host round trip: operator apply by one exact LU solve, the
-// check b - C x of that solve, CGS2.  Everything the host decides on (the check, the Hessenberg column, breakdown) is read
-// back once per batch.
-// the steps of a batch can take the tail form: a generalised problem whose M and C share their index arrays, whole on this rank,
-// plain forward products, nothing between the solve and the orthogonalisation (no projection mask, no refinement step)
-static bool krylov_tail_ok(lsa_ctx* ctx, const lsa_krylov* k) {
-    static const bool enabled = !(getenv("LSA_KRYLOV_TAIL") && atoi(getenv("LSA_KRYLOV_TAIL")) == 0);
-    static const bool fuse = !(getenv("LSA_KRYLOV_FUSED") && atoi(getenv("LSA_KRYLOV_FUSED")) == 0);
+// ---- Arnoldi steps ------------------------------------------------------------------------------------------------
+// Which form a batch of Arnoldi steps takes.  One step at a time through op_apply_dev (GMRES, or a direct solve with the
+// judgement of gmres_run), or pipelined: the steps of a batch are queued without a host round trip -- operator apply by one exact
+// LU solve, the check b - C x of that solve, the orthogonalisation -- and everything the host decides on (the check, the
+// Hessenberg column, breakdown) is read back once per batch.
+enum class Orth {
+    cgs2_fused,   // CGS2 in five launches; a step whose shape k_cgs2_fused does not take runs the per-stage kernels
+    cgs2_staged,  // CGS2 with a kernel per stage (LSA_KRYLOV_FUSED=0)
+    dcgs2,        // delayed reorthogonalisation: one reduction and one update per step (k_dcgs2_step).  On entry to step j, V[:, j]
+                  // holds the previous step's vector projected once and column j-1 of H is provisional; step j's reduction finishes both
+};
+struct StepPlan {
+    bool pipelined = false;
+    Orth orth = Orth::cgs2_fused;
+    bool tail = false;  // the step's last launch also multiplies t = M v_{j+1} for the next step and leaves the pairs of this step's check
+};
+
+// Decided anew for every batch.  Inside one lsa_krylov_extend call only two inputs move: k->pipeline (false from the first solve
+// that needed the one-step path's judgement until the cache hands the workspace out again) and op->refine (off to on: the tail form
+// is lost, never gained); the orthogonalisation is therefore the same for every batch of a call.
+static StepPlan step_plan(lsa_ctx* ctx, const lsa_krylov* k) {
+    const KrylovSwitches& sw = krylov_switches();
     const lsa_op* op = k->op;
-    if (!enabled || !fuse || !op->Kmul || !op->Kfac || op->adjoint || op->keep || op->refine || op->n != k->n) return false;
-    return k_cgs2_tail_fits(ctx, k->n, k->ncv, op->Kmul, op->Kfac);
+    StepPlan p;
+    // DCGS2 where the five-launch CGS2 runs otherwise: one rank, forward operator, a basis of at most 128 vectors of at most 262 k rows
+    if (!sw.fused) p.orth = Orth::cgs2_staged;
+    else if (sw.delayed && ctx->nranks == 1 && !op->adjoint && op->n == k->n && k_dcgs2_fits(k->n, k->ncv)) p.orth = Orth::dcgs2;
+    // an operator apply is one exact LU solve whose result only needs checking, with nothing on the way that synchronises with the
+    // host by itself (the host-staged exchange does); batches of one step only in the delayed form, whose basis must not depend on
+    // the batch size
+    p.pipelined = k->pipeline && (k->batch > 1 || p.orth == Orth::dcgs2) && op->Kfac && op->nd && !op->pc &&
+                  !(ctx->nranks > 1 && (!op->nd_dist || ctx->host_gather));
+    // tail form: a generalised problem whose M and C share their index arrays, whole on this rank, plain forward products, nothing
+    // between the solve and the orthogonalisation (no projection mask, no refinement step)
+    p.tail = p.pipelined && sw.tail && sw.fused && op->Kmul && !op->adjoint && !op->keep && !op->refine && op->n == k->n &&
+             k_cgs2_tail_fits(ctx, k->n, k->ncv, op->Kmul, op->Kfac);
+    return p;
 }
 
-static int krylov_enqueue_step(lsa_ctx* ctx, lsa_krylov* k, int32_t j, int32_t slot, bool tail) {
+// Queues step j of a pipelined batch into `slot`.  Tail form: [M v_j unless the previous step's tail left it] + the sweeps + the
+// orthogonalisation + the tail (CGS2: 18 launches, DCGS2: 16).  Otherwise M v_j + the direct solve with its C y (and refinement
+// step) + the mask + the orthogonalisation with the check riding in its first reduction.  first: V[:, j] is final (DCGS2: the
+// first step of a run).
+static int krylov_enqueue_step(lsa_ctx* ctx, lsa_krylov* k, const StepPlan& plan, int32_t j, int32_t slot, bool first) {
     lsa_op* op = k->op;
     const int dtype = LSA_C128;
     const size_t vb = (size_t)k->n * 16;
     const void* vj = (char*)k->V + (size_t)j * vb;
     void* vn = (char*)k->V + (size_t)(j + 1) * vb;
-    const void* rhs = vj;
-    PcRef pcr;
-    pcr.nd = op->nd;
-    pcr.nd_dist = op->nd_dist;
-    pcr.adjoint = op->adjoint;
-    void* hcol_dev = (char*)k->Hdev + (size_t)slot * krylov_slot_bytes(k->ncv);
-    if (tail) {
-        // 18 launches: [M v_j unless the previous step's tail left it] + the sweeps + dot, update, dot, update + tail
+    void* sl = (char*)k->Hdev + (size_t)slot * krylov_slot_bytes(k->ncv);
+    double* chk = k->checks + 2 * (size_t)slot;
+    const bool dcgs2 = plan.orth == Orth::dcgs2;
+    if (plan.orth != Orth::cgs2_staged) LSA_CHECK(k->ow.ensure_fused(ctx, k->n));
+    if (plan.tail) {
         if (k->t_for != j) LSA_CHECK(spmv_global(ctx, op->Kmul, dtype, vj, op->t, false));
         k->t_for = -1;
-        LSA_CHECK(pc_global(ctx, pcr, op->Kfac->row0, op->n, dtype, op->t, k->w));
-        LSA_CHECK(k->ow.ensure_fused(ctx, k->n));
-        LSA_CHECK(k_cgs2_fused_tail(ctx, k->n, j + 1, k->V, k->n, k->w, k->w2, vn, hcol_dev, k->ow.fused, op->Kmul, op->Kfac, op->t,
-                                    k->tail_parts + (size_t)slot * 2 * (size_t)k->tail_nparts));
+        LSA_CHECK(pc_global(ctx, pc_of(op), op->Kfac->row0, op->n, dtype, op->t, k->w));
+        double* parts = k->tail_parts + (size_t)slot * 2 * (size_t)k->tail_nparts;
+        if (dcgs2) {
+            LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, k->w, first ? 1 : 0, sl, k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
+            LSA_CHECK(k_dcgs2_tail(ctx, k->n, j, k->V, k->n, k->w, k->ow.fused, op->Kmul, op->Kfac, op->t, parts, sl, k->ncv));
+        } else {
+            LSA_CHECK(k_cgs2_fused_tail(ctx, k->n, j + 1, k->V, k->n, k->w, k->w2, vn, sl, k->ow.fused, op->Kmul, op->Kfac, op->t, parts));
+        }
         k->t_for = j + 1;
         return LSA_OK;
     }
     k->t_for = -1;
+    const void* rhs = vj;
     if (op->Kmul) {
         LSA_CHECK(spmv_global(ctx, op->Kmul, dtype, vj, op->t, op->adjoint));
         rhs = op->t;
     }
-    LSA_CHECK(pc_global(ctx, pcr, op->Kfac->row0, op->n, dtype, rhs, k->w));
-    LSA_CHECK(spmv_global(ctx, op->Kfac, dtype, k->w, op->gw.z, op->adjoint));
-    if (op->refine) {
-        // y += C^-1 (t - C y): the factors of a large 3D problem leave 1e-11 of the right-hand side behind, this step takes it to
-        // rounding level (the norms this residual pass leaves in the check slot are overwritten by the final check below)
-        LSA_CHECK(k_residual_norms(ctx, dtype, op->n, rhs, op->gw.z, op->gw.w, k->checks + 2 * (size_t)slot));
-        LSA_CHECK(pc_global(ctx, pcr, op->Kfac->row0, op->n, dtype, op->gw.w, op->gw.z));
-        const double one[2] = {1.0, 0.0};
-        LSA_CHECK(k_axpy(ctx, dtype, op->n, one, op->gw.z, k->w));
-        LSA_CHECK(spmv_global(ctx, op->Kfac, dtype, k->w, op->gw.z, op->adjoint));
-    }
-    static const bool fuse = !(getenv("LSA_KRYLOV_FUSED") && atoi(getenv("LSA_KRYLOV_FUSED")) == 0);
-    if (fuse) {
-        // the check ||b - C y||, ||b|| rides in the first reduction of the orthogonalisation (its vector b - C y is needed only
-        // by the one-step path, which recomputes it)
-        LSA_CHECK(k->ow.ensure_fused(ctx, k->n));
-        if (op->keep) LSA_CHECK(k_mask(ctx, dtype, op->n, op->keep, k->w));
-        const int frc = k_cgs2_fused(ctx, dtype, k->n, j + 1, k->V, k->n, k->w, vn, hcol_dev, k->ow.fused, rhs, op->gw.z, k->checks + 2 * (size_t)slot);
-        if (frc <= 0) return frc;
-    }
-    LSA_CHECK(k_residual_norms(ctx, dtype, op->n, rhs, op->gw.z, op->gw.w, k->checks + 2 * (size_t)slot));
-    if (op->keep && !fuse) LSA_CHECK(k_mask(ctx, dtype, op->n, op->keep, k->w));
-    return orthonormalize_enqueue(ctx, dtype, k->n, k->V, k->n, j + 1, k->w, vn, k->ow, hcol_dev);
-}
-
-// The delayed form of the pipelined steps (DCGS2: one reduction and one update per step instead of CGS2's four launches; see
-// k_dcgs2_step) where the five-launch CGS2 runs otherwise: one rank, forward operator, a basis of at most 128 vectors of at most
-// 262 k rows.  On entry to step j, V[:, j] holds the previous step's vector projected once and column j-1 of H is provisional;
-// step j's reduction finishes both.  LSA_KRYLOV_DELAYED=0: CGS2.
-static bool krylov_delayed_ok(const lsa_ctx* ctx, const lsa_krylov* k) {
-    static const bool enabled = !(getenv("LSA_KRYLOV_DELAYED") && atoi(getenv("LSA_KRYLOV_DELAYED")) == 0);
-    static const bool fuse = !(getenv("LSA_KRYLOV_FUSED") && atoi(getenv("LSA_KRYLOV_FUSED")) == 0);
-    const lsa_op* op = k->op;
-    return enabled && fuse && ctx->nranks == 1 && !op->adjoint && op->n == k->n && k_dcgs2_fits(k->n, k->ncv);
-}
-
-// one step of the delayed form: [M p unless the previous tail left it] + the sweeps + reduce, update + tail (16 launches), or
-// without the tail form M p + the sweeps + C y + reduce, update, norm.  first: V[:, j] is final (the first step of a run)
-static int krylov_enqueue_dstep(lsa_ctx* ctx, lsa_krylov* k, int32_t j, int32_t slot, bool tail, bool first) {
-    lsa_op* op = k->op;
-    const int dtype = LSA_C128;
-    const void* vj = (char*)k->V + (size_t)j * (size_t)k->n * 16;
-    void* sl = (char*)k->Hdev + (size_t)slot * krylov_slot_bytes(k->ncv);
-    PcRef pcr;
-    pcr.nd = op->nd;
-    pcr.nd_dist = op->nd_dist;
-    pcr.adjoint = op->adjoint;
-    LSA_CHECK(k->ow.ensure_fused(ctx, k->n));
-    if (tail) {
-        if (k->t_for != j) LSA_CHECK(spmv_global(ctx, op->Kmul, dtype, vj, op->t, false));
-        k->t_for = -1;
-        LSA_CHECK(pc_global(ctx, pcr, op->Kfac->row0, op->n, dtype, op->t, k->w));
-        LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, k->w, first ? 1 : 0, sl, k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
-        LSA_CHECK(k_dcgs2_tail(ctx, k->n, j, k->V, k->n, k->w, k->ow.fused, op->Kmul, op->Kfac, op->t, k->tail_parts + (size_t)slot * 2 * (size_t)k->tail_nparts,
-                               sl, k->ncv));
-        k->t_for = j + 1;
-        return LSA_OK;
-    }
-    k->t_for = -1;
-    const void* rhs = vj;
-    if (op->Kmul) {
-        LSA_CHECK(spmv_global(ctx, op->Kmul, dtype, vj, op->t, false));
-        rhs = op->t;
-    }
-    LSA_CHECK(pc_global(ctx, pcr, op->Kfac->row0, op->n, dtype, rhs, k->w));
-    LSA_CHECK(spmv_global(ctx, op->Kfac, dtype, k->w, op->gw.z, false));
-    if (op->refine) {  // as krylov_enqueue_step
-        LSA_CHECK(k_residual_norms(ctx, dtype, op->n, rhs, op->gw.z, op->gw.w, k->checks + 2 * (size_t)slot));
-        LSA_CHECK(pc_global(ctx, pcr, op->Kfac->row0, op->n, dtype, op->gw.w, op->gw.z));
-        const double one[2] = {1.0, 0.0};
-        LSA_CHECK(k_axpy(ctx, dtype, op->n, one, op->gw.z, k->w));
-        LSA_CHECK(spmv_global(ctx, op->Kfac, dtype, k->w, op->gw.z, false));
-    }
+    // (the norms a refinement step leaves in the check slot are overwritten by the final check below)
+    LSA_CHECK(direct_solve_enqueue(ctx, op, dtype, rhs, k->w, op->gw.z, op->gw.w, op->refine, chk));
+    // the check ||b - C y||, ||b|| rides in the first reduction of the orthogonalisation (its vector b - C y is needed only by the
+    // one-step path, which recomputes it); the per-stage form has it as a kernel of its own, in front of the mask
+    const SolveCheck check{rhs, op->gw.z, op->gw.w, chk};
+    const bool rides = plan.orth != Orth::cgs2_staged;
+    if (!rides) LSA_CHECK(k_residual_norms(ctx, dtype, op->n, check.b, check.z, check.r, check.out));
     if (op->keep) LSA_CHECK(k_mask(ctx, dtype, op->n, op->keep, k->w));
-    LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, k->w, first ? 1 : 0, sl, k->ncv, k->ow.fused, rhs, op->gw.z, k->checks + 2 * (size_t)slot));
-    return k_dcgs2_norm(ctx, k->n, k->ow.fused, sl, k->ncv);
+    if (dcgs2) {
+        LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, k->w, first ? 1 : 0, sl, k->ncv, k->ow.fused, check.b, check.z, check.out));
+        return k_dcgs2_norm(ctx, k->n, k->ow.fused, sl, k->ncv);
+    }
+    return orthonormalize_enqueue(ctx, dtype, k->n, k->V, k->n, j + 1, k->w, vn, k->ow, sl, rides ? &check : nullptr);
 }
 
-// true when an operator apply is one exact LU solve whose result only needs checking, with nothing on the way that
-// synchronises with the host by itself (the host-staged exchange does); batches of one step only in the delayed form
-static bool krylov_can_pipeline(const lsa_ctx* ctx, const lsa_krylov* k, bool delayed) {
-    const lsa_op* op = k->op;
-    if (!k->pipeline || !(k->batch > 1 || delayed) || !op->Kfac || !op->nd || op->pc) return false;
-    if (ctx->nranks > 1 && (!op->nd_dist || ctx->host_gather)) return false;
-    return true;
+// the caller's H of one lsa_krylov_extend call: the columns before j0 are the caller's (Arnoldi relation, zero below row j0), those
+// from j0 on are Hessenberg
+struct HessView {
+    cplx* Hh;
+    int32_t ldh, j0, ncv;
+    cplx* col(int32_t j) const { return Hh + (size_t)j * ldh; }
+};
+
+// what a column's new norm says: 1 = breakdown (nothing left of the vector against the size of what was taken out of it), -1 = not
+// finite, 0 = go on
+static int judge_norm(double beta, const cplx* col, int32_t rows) {
+    if (!std::isfinite(beta)) return -1;
+    double colmax = 0.0;
+    for (int32_t i = 0; i < rows; ++i) colmax = std::max(colmax, std::hypot(col[i].re, col[i].im));
+    return beta <= 1e-14 * std::max(colmax, 1e-300) ? 1 : 0;
+}
+
+// fills column j of H from h (j + 2 entries, the norm last)
+static int take_column(const HessView& H, int32_t j, const cplx* h) {
+    cplx* Hj = H.col(j);
+    for (int32_t i = 0; i < H.ldh; ++i) Hj[i] = i <= j + 1 ? h[i] : cplx{0.0, 0.0};
+    return judge_norm(h[j + 1].re, h, j + 1);
+}
+
+// delayed form: a step's a and nu (its slot's first entries and entry 2 ncv) finish column jc - 1 of H
+static int finish_column(const HessView& H, int32_t jc, const cplx* sl) {
+    cplx* Hp = H.col(jc - 1);
+    const double nu = sl[2 * H.ncv].re;
+    for (int32_t i = 0; i < jc; ++i) Hp[i] = cplx{Hp[i].re + sl[i].re, Hp[i].im + sl[i].im};
+    Hp[jc] = cplx{nu, 0.0};
+    return judge_norm(nu, Hp, jc);
+}
+
+// delayed form: column jc of H from a step's slot, h = ([b; c] - H[0:jc+1, 0:jc] a) / nu with the provisional ||w|| below it
+// (first: a = 0, nu = 1); h: jc + 2 entries of work space
+static int provisional_column(const HessView& H, int32_t jc, const cplx* sl, bool first, cplx* h) {
+    const int32_t ncv = H.ncv;
+    const double inv = 1.0 / sl[2 * ncv].re;
+    for (int32_t i = 0; i < jc; ++i) h[i] = sl[ncv + i];
+    h[jc] = sl[2 * ncv + 1];
+    if (!first) {
+        for (int32_t c = 0; c < jc; ++c) {
+            const cplx a = sl[c];
+            const cplx* Hc = H.col(c);
+            const int32_t rows = std::min(jc, std::max(H.j0, c + 1));
+            for (int32_t i = 0; i <= rows; ++i) {
+                h[i].re -= Hc[i].re * a.re - Hc[i].im * a.im;
+                h[i].im -= Hc[i].re * a.im + Hc[i].im * a.re;
+            }
+        }
+        for (int32_t i = 0; i <= jc; ++i) h[i] = cplx{h[i].re * inv, h[i].im * inv};
+    }
+    h[jc + 1] = cplx{sl[2 * ncv + 2].re, 0.0};
+    return take_column(H, jc, h);
+}
+
+static int arnoldi_nonfinite(lsa_ctx* ctx, int32_t j) { return lsa_set_error(ctx, LSA_ERR_NONFINITE, "Arnoldi: non-finite norm at step %d", j); }
+
+// Steps [*j, j1) in batches while the plan pipelines; *j: the first step not done.  Ends early on a breakdown (*breakdown) or
+// when a solve needs the one-step path (k->pipeline goes false; the caller runs the rest there).
+static int extend_pipelined(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, int32_t* jp, int32_t j1, int32_t* breakdown) {
+    lsa_op* op = k->op;
+    StepPlan plan = step_plan(ctx, k);
+    if (!op->gw_ready) {
+        LSA_CHECK(op->gw.alloc(ctx, op->n, std::max(1, std::min({op->opts.ksp_restart, op->opts.ksp_maxit, 40})), LSA_C128));
+        op->gw_ready = true;
+    }
+    const int32_t slots = std::max(k->batch, 1);
+    const size_t colb = krylov_slot_bytes(k->ncv);
+    LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)slots * (colb + 2 * sizeof(double))));
+    if (plan.tail && !k->tail_parts) {
+        k->tail_nparts = k_cgs2_tail_parts(k->n);
+        LSA_HIP_ALLOC(ctx, hipMalloc(&k->w2, (size_t)k->n * 16));
+        LSA_HIP_ALLOC(ctx, hipMalloc((void**)&k->tail_parts, (size_t)slots * 2 * (size_t)k->tail_nparts * sizeof(double)));
+    }
+    const bool delayed = plan.orth == Orth::dcgs2;
+    const double rtol = op->opts.ksp_rtol;
+    char* host = (char*)ctx->pinned;
+    cplx* hwork = (cplx*)k->hcol.data();  // (ncv + 2 complex numbers)
+    k->t_for = -1;  // (op->t is anybody's between calls)
+    bool pending = false;  // delayed form: V[:, j] is projected once, column j - 1 of H provisional
+    int32_t j = *jp;
+    for (; j < j1 && plan.pipelined; plan = step_plan(ctx, k)) {
+        const int32_t nb = std::min<int32_t>(slots, j1 - j);
+        const double tq = now_s();
+        for (int32_t s = 0; s < nb; ++s) {
+            const int rc = krylov_enqueue_step(ctx, k, plan, j + s, s, s == 0 && !pending);
+            if (rc != LSA_OK) {
+                (void)hipStreamSynchronize(ctx->stream);
+                return rc;
+            }
+        }
+        if (plan.tail) LSA_CHECK(k_cgs2_tail_checks(ctx, nb, k->tail_nparts, k->tail_parts, k->checks));
+        LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, k->Hdev, (size_t)nb * colb, hipMemcpyDeviceToHost, ctx->stream));
+        LSA_HIP_CHECK(ctx, hipMemcpyAsync(host + (size_t)slots * colb, k->checks, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        const double tw = now_s();
+        LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (krylov_switches().timing) fprintf(stderr, "[lsa_krylov] %d steps queued in %.3f ms, waited %.3f ms\n", nb, 1e3 * (tw - tq), 1e3 * (now_s() - tw));
+        const double* chk = (const double*)(host + (size_t)slots * colb);
+        int32_t accepted = 0;
+        for (int32_t s = 0; s < nb; ++s, ++accepted) {
+            const cplx* hc = (const cplx*)(host + (size_t)s * colb);
+            const bool first = s == 0 && !pending;
+            if (delayed && !first) {
+                // the step's a and nu depend on V alone, not on its solve: they finish column j + s - 1 and V[:, j + s] even
+                // when this step is cut below (it is queued again with V[:, j + s] final)
+                pending = false;
+                const int what = finish_column(H, j + s, hc);
+                if (what < 0) return arnoldi_nonfinite(ctx, j + s - 1);
+                if (what > 0) {
+                    *breakdown = j + s - 1;
+                    return LSA_OK;
+                }
+            }
+            const double beta0 = std::sqrt(chk[2 * s]), bnorm = std::sqrt(chk[2 * s + 1]);
+            if (!(beta0 <= rtol * bnorm)) {
+                // a direct solve missed rtol: from here on every queued step carries one refinement step (large 3D factors; the
+                // steps of this batch from s on are queued again).  Refined and still short of rtol: this solve needs the judgement
+                // of the one-step path (backward error next to an eigenvalue, GMRES), and so will its neighbours: the rest of this
+                // basis runs one step at a time
+                if (!op->refine && std::isfinite(beta0)) op->refine = true;
+                else k->pipeline = false;
+                break;
+            }
+            stats_book_direct_solve(&op->st, op->Kmul ? 2 : 1, op->refine, beta0, bnorm);
+            const int what = delayed ? provisional_column(H, j + s, hc, first, hwork) : take_column(H, j + s, hc);
+            pending = delayed;
+            if (what < 0) return arnoldi_nonfinite(ctx, j + s);
+            if (what > 0) {  // the steps queued behind a breakdown worked on noise: the caller restarts from here
+                *breakdown = j + s;
+                return LSA_OK;
+            }
+        }
+        j += accepted;
+        if (accepted < nb) k->t_for = -1;  // the steps behind the one that stopped the batch ran on; t is theirs
+    }
+    *jp = j;
+    if (pending) {
+        // the flush: the reduction and the update without a solve make V[:, j1] and column j1 - 1 final, so that the restart,
+        // the Ritz vectors and the next call see what CGS2 leaves
+        LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, nullptr, 0, k->Hdev, k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
+        LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, k->Hdev, colb, hipMemcpyDeviceToHost, ctx->stream));
+        LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        const int what = finish_column(H, j, (const cplx*)host);
+        if (what < 0) return arnoldi_nonfinite(ctx, j - 1);
+        if (what > 0) *breakdown = j - 1;
+    }
+    return LSA_OK;
+}
+
+// steps [j, j1) one at a time: the operator apply with its own judgement of the inner solve, CGS2, one read-back per step
+static int extend_one_step(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, int32_t j, int32_t j1, int32_t* breakdown) {
+    const size_t vb = (size_t)k->n * 16;
+    k->t_for = -1;
+    for (; j < j1; ++j) {
+        const void* vj = (char*)k->V + (size_t)j * vb;
+        void* vn = (char*)k->V + (size_t)(j + 1) * vb;
+        LSA_CHECK(op_apply_dev(ctx, k->op, vj, k->w));
+        LSA_CHECK(orthonormalize(ctx, LSA_C128, k->n, k->V, k->n, j + 1, k->w, vn, k->ow, k->hcol.data()));
+        const int what = take_column(H, j, (const cplx*)k->hcol.data());  // (std::complex<double> has cplx's layout)
+        if (what < 0) return arnoldi_nonfinite(ctx, j);
+        if (what > 0) {
+            *breakdown = j;
+            break;
+        }
+    }
+    return LSA_OK;
 }
 
 int lsa_krylov_extend(lsa_ctx* ctx, lsa_krylov* k, int32_t j0, int32_t j1, void* H, int32_t ldh, int32_t* breakdown) {
     if (!ctx || !k || !H) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_extend: null argument");
     if (j0 < 0 || j1 < j0 || j1 > k->ncv || ldh < j1 + 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_extend: bad step range [%d, %d) for ncv %d", j0, j1, k->ncv);
     const double t0 = now_s();
-    const size_t vb = (size_t)k->n * 16;
-    if (breakdown) *breakdown = -1;
-    cplx* Hh = (cplx*)H;
-    lsa_op* op = k->op;
-    // fills column j of H from hcol (j + 2 entries) and tells whether the step broke down; < 0: non-finite
-    auto take_column = [&](int32_t j, const zc* hcol) -> int {
-        for (int32_t i = 0; i < ldh; ++i) Hh[(size_t)j * ldh + i] = cplx{0.0, 0.0};
-        for (int32_t i = 0; i <= j + 1; ++i) Hh[(size_t)j * ldh + i] = cplx{hcol[i].real(), hcol[i].imag()};
-        const double beta = hcol[j + 1].real();
-        if (!std::isfinite(beta)) return -1;
-        double colmax = 0.0;
-        for (int32_t i = 0; i <= j; ++i) colmax = std::max(colmax, std::abs(hcol[i]));
-        return beta <= 1e-14 * std::max(colmax, 1e-300) ? 1 : 0;
-    };
-    // delayed form: column jc of H from a step's slot (h = ([b; c] - H[0:jc+1, 0:jc] a) / nu, the provisional ||w|| below it;
-    // first: a = 0, nu = 1), and the step's a, nu finishing column jc - 1; the columns before j0 are the caller's (Arnoldi
-    // relation, zero below row j0), those from j0 on are Hessenberg
-    auto finish_column = [&](int32_t jc, const cplx* sl) -> int {
-        const int32_t ncv = k->ncv;
-        const double nu = sl[2 * ncv].re;
-        for (int32_t i = 0; i < jc; ++i) Hh[(size_t)(jc - 1) * ldh + i] = cplx{Hh[(size_t)(jc - 1) * ldh + i].re + sl[i].re, Hh[(size_t)(jc - 1) * ldh + i].im + sl[i].im};
-        Hh[(size_t)(jc - 1) * ldh + jc] = cplx{nu, 0.0};
-        if (!std::isfinite(nu)) return -1;
-        double colmax = 0.0;
-        for (int32_t i = 0; i < jc; ++i) colmax = std::max(colmax, std::hypot(Hh[(size_t)(jc - 1) * ldh + i].re, Hh[(size_t)(jc - 1) * ldh + i].im));
-        return nu <= 1e-14 * std::max(colmax, 1e-300) ? 1 : 0;
-    };
-    std::vector<cplx> hwork((size_t)k->ncv + 2);
-    auto provisional_column = [&](int32_t jc, const cplx* sl, bool first) -> int {
-        const int32_t ncv = k->ncv;
-        const double inv = 1.0 / sl[2 * ncv].re;
-        cplx* h = hwork.data();
-        for (int32_t i = 0; i < jc; ++i) h[i] = sl[ncv + i];
-        h[jc] = sl[2 * ncv + 1];
-        if (!first) {
-            for (int32_t c = 0; c < jc; ++c) {
-                const cplx a = sl[c];
-                const cplx* Hc = Hh + (size_t)c * ldh;
-                const int32_t rows = std::min(jc, std::max(j0, c + 1));
-                for (int32_t i = 0; i <= rows; ++i) {
-                    h[i].re -= Hc[i].re * a.re - Hc[i].im * a.im;
-                    h[i].im -= Hc[i].re * a.im + Hc[i].im * a.re;
-                }
-            }
-            for (int32_t i = 0; i <= jc; ++i) h[i] = cplx{h[i].re * inv, h[i].im * inv};
-        }
-        for (int32_t i = 0; i <= jc; ++i) k->hcol[i] = zc(h[i].re, h[i].im);
-        k->hcol[jc + 1] = zc(sl[2 * ncv + 2].re, 0.0);
-        return take_column(jc, k->hcol.data());
-    };
-    int32_t j = j0;
-    const bool delayed = krylov_delayed_ok(ctx, k);
-    if (krylov_can_pipeline(ctx, k, delayed)) {
-        if (!op->gw_ready) {
-            LSA_CHECK(op->gw.alloc(ctx, op->n, std::max(1, std::min({op->opts.ksp_restart, op->opts.ksp_maxit, 40})), LSA_C128));
-            op->gw_ready = true;
-        }
-        const int32_t slots = std::max(k->batch, 1);
-        const size_t colb = krylov_slot_bytes(k->ncv);
-        LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)slots * (colb + 2 * sizeof(double))));
-        const double rtol = op->opts.ksp_rtol;
-        k->t_for = -1;  // (op->t is anybody's between calls)
-        bool pending = false;  // delayed form: V[:, j] is projected once, column j - 1 of H provisional
-        while (j < j1 && k->pipeline) {
-            const int32_t nb = std::min<int32_t>(slots, j1 - j);
-            const double tq = now_s();
-            const bool tail = krylov_tail_ok(ctx, k);
-            if (tail && !k->tail_parts) {
-                k->tail_nparts = k_cgs2_tail_parts(k->n);
-                LSA_HIP_ALLOC(ctx, hipMalloc(&k->w2, (size_t)k->n * 16));
-                LSA_HIP_ALLOC(ctx, hipMalloc((void**)&k->tail_parts, (size_t)slots * 2 * (size_t)k->tail_nparts * sizeof(double)));
-            }
-            for (int32_t s = 0; s < nb; ++s) {
-                int rc = delayed ? krylov_enqueue_dstep(ctx, k, j + s, s, tail, s == 0 && !pending) : krylov_enqueue_step(ctx, k, j + s, s, tail);
-                if (rc != LSA_OK) {
-                    (void)hipStreamSynchronize(ctx->stream);
-                    op->st.seconds_solve += now_s() - t0;
-                    return rc;
-                }
-            }
-            if (tail) LSA_CHECK(k_cgs2_tail_checks(ctx, nb, k->tail_nparts, k->tail_parts, k->checks));
-            char* host = (char*)ctx->pinned;
-            LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, k->Hdev, (size_t)nb * colb, hipMemcpyDeviceToHost, ctx->stream));
-            LSA_HIP_CHECK(ctx, hipMemcpyAsync(host + (size_t)slots * colb, k->checks, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            const double tw = now_s();
-            LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            static const bool timing = getenv("LSA_KRYLOV_TIMING") != nullptr;
-            if (timing) fprintf(stderr, "[lsa_krylov] %d steps queued in %.3f ms, waited %.3f ms\n", nb, 1e3 * (tw - tq), 1e3 * (now_s() - tw));
-            const double* chk = (const double*)(host + (size_t)slots * colb);
-            int32_t accepted = 0;
-            for (int32_t s = 0; s < nb; ++s, ++accepted) {
-                const cplx* hc = (const cplx*)(host + (size_t)s * colb);
-                const bool first = s == 0 && !pending;
-                if (delayed && !first) {
-                    // the step's a and nu depend on V alone, not on its solve: they finish column j + s - 1 and V[:, j + s] even
-                    // when this step is cut below (it is queued again with V[:, j + s] final)
-                    pending = false;
-                    const int what = finish_column(j + s, hc);
-                    if (what != 0) {
-                        op->st.seconds_solve += now_s() - t0;
-                        if (what < 0) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "Arnoldi: non-finite norm at step %d", j + s - 1);
-                        if (breakdown) *breakdown = j + s - 1;
-                        return LSA_OK;
-                    }
-                }
-                const double beta0 = std::sqrt(chk[2 * s]), bnorm = std::sqrt(chk[2 * s + 1]);
-                if (!(beta0 <= rtol * bnorm)) {
-                    if (!op->refine && std::isfinite(beta0)) {
-                        // a direct solve missed rtol: from here on every queued step carries one refinement step (large 3D
-                        // factors; the steps of this batch from s on are queued again)
-                        op->refine = true;
-                        break;
-                    }
-                    // refined and still short of rtol: this solve needs the judgement of the one-step path (backward error
-                    // next to an eigenvalue, GMRES), and so will its neighbours: the rest of this basis runs one step at a time
-                    k->pipeline = false;
-                    break;
-                }
-                ++op->st.op_applies;
-                op->st.spmv_calls += (op->Kmul ? 2 : 1) + (op->refine ? 1 : 0);
-                op->st.sptrsv_calls += op->refine ? 4 : 2;
-                if (op->refine) ++op->st.refined_solves;
-                op->st.last_rel_res = bnorm > 0.0 ? beta0 / bnorm : 0.0;
-                op->st.max_rel_res = std::max(op->st.max_rel_res, op->st.last_rel_res);
-                int what;
-                if (delayed) {
-                    what = provisional_column(j + s, hc, first);
-                    pending = true;
-                } else {
-                    for (int32_t i = 0; i <= j + s + 1; ++i) k->hcol[i] = zc(hc[i].re, hc[i].im);
-                    what = take_column(j + s, k->hcol.data());
-                }
-                if (what < 0) {
-                    op->st.seconds_solve += now_s() - t0;
-                    return lsa_set_error(ctx, LSA_ERR_NONFINITE, "Arnoldi: non-finite norm at step %d", j + s);
-                }
-                if (what > 0) {  // the steps queued behind a breakdown worked on noise: the caller restarts from here
-                    if (breakdown) *breakdown = j + s;
-                    op->st.seconds_solve += now_s() - t0;
-                    return LSA_OK;
-                }
-            }
-            j += accepted;
-            if (accepted < nb) k->t_for = -1;  // the steps behind the one that stopped the batch ran on; t is theirs
-        }
-        if (pending) {
-            // the flush: the reduction and the update without a solve make V[:, j1] and column j1 - 1 final, so that the restart,
-            // the Ritz vectors and the next call see what CGS2 leaves
-            LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, nullptr, 0, k->Hdev, k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
-            char* host = (char*)ctx->pinned;
-            LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, k->Hdev, colb, hipMemcpyDeviceToHost, ctx->stream));
-            LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            const int what = finish_column(j, (const cplx*)host);
-            op->st.seconds_solve += now_s() - t0;
-            if (what < 0) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "Arnoldi: non-finite norm at step %d", j - 1);
-            if (what > 0 && breakdown) *breakdown = j - 1;
-            return LSA_OK;
-        }
-    }
-    k->t_for = -1;
-    for (; j < j1; ++j) {
-        const void* vj = (char*)k->V + (size_t)j * vb;
-        void* vn = (char*)k->V + (size_t)(j + 1) * vb;
-        int rc = op_apply_dev(ctx, op, vj, k->w);
-        if (rc != LSA_OK) {
-            op->st.seconds_solve += now_s() - t0;
-            return rc;
-        }
-        LSA_CHECK(orthonormalize(ctx, LSA_C128, k->n, k->V, k->n, j + 1, k->w, vn, k->ow, k->hcol.data()));
-        const int what = take_column(j, k->hcol.data());
-        if (what < 0) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "Arnoldi: non-finite norm at step %d", j);
-        if (what > 0) {
-            if (breakdown) *breakdown = j;
-            break;
-        }
-    }
-    op->st.seconds_solve += now_s() - t0;
-    return LSA_OK;
+    const HessView Hv{(cplx*)H, ldh, j0, k->ncv};
+    int32_t j = j0, bd = -1;
+    int rc = LSA_OK;
+    if (step_plan(ctx, k).pipelined) rc = extend_pipelined(ctx, k, Hv, &j, j1, &bd);
+    if (rc == LSA_OK && bd < 0) rc = extend_one_step(ctx, k, Hv, j, j1, &bd);
+    if (breakdown) *breakdown = bd;
+    k->op->st.seconds_solve += now_s() - t0;
+    return rc;
 }
 
 int lsa_krylov_restart(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t knew, const void* Q, int32_t ldq) {
     if (!ctx || !k || !Q) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_restart: null argument");
     if (m < 1 || m > k->ncv || knew < 0 || knew > m || ldq < m) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_restart: bad sizes m=%d knew=%d", m, knew);
     const size_t vb = (size_t)k->n * 16;
-    if (knew > 0) {
-        // pack Q densely (m x knew) and upload
-        LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)m * knew * 16));
-        const cplx* Qh = (const cplx*)Q;
-        cplx* p = (cplx*)ctx->pinned;
-        for (int32_t c = 0; c < knew; ++c)
-            for (int32_t r = 0; r < m; ++r) p[(size_t)c * m + r] = Qh[(size_t)c * ldq + r];
-        LSA_HIP_CHECK(ctx, hipMemcpyAsync(k->qdev, p, (size_t)m * knew * 16, hipMemcpyHostToDevice, ctx->stream));
-        LSA_CHECK(k_basis_gemm(ctx, LSA_C128, k->n, m, knew, k->V, k->n, k->qdev, m, k->V2, k->n));
-    }
+    if (knew > 0) LSA_CHECK(basis_times_host_matrix(ctx, LSA_C128, k->n, m, knew, k->V, Q, ldq, k->qdev, k->V2, 0));
     LSA_CHECK(k_copy(ctx, LSA_C128, k->n, (char*)k->V + (size_t)m * vb, (char*)k->V2 + (size_t)knew * vb));
     LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     std::swap(k->V, k->V2);
@@ -1294,13 +1307,8 @@ int lsa_krylov_ritz_vectors(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t nvec
     if (m < 1 || m > k->ncv + 1 || nvec < 0 || nvec > k->ncv + 1 || ldy < m) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_ritz_vectors: bad sizes");
     if (nvec == 0) return LSA_OK;
     const size_t vb = (size_t)k->n * 16;
-    LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)m * nvec * 16 + (size_t)nvec * sizeof(double)));
-    const cplx* Yh = (const cplx*)Y;
-    cplx* p = (cplx*)ctx->pinned;
-    for (int32_t c = 0; c < nvec; ++c)
-        for (int32_t r = 0; r < m; ++r) p[(size_t)c * m + r] = Yh[(size_t)c * ldy + r];
-    LSA_HIP_CHECK(ctx, hipMemcpyAsync(k->qdev, p, (size_t)m * nvec * 16, hipMemcpyHostToDevice, ctx->stream));
-    LSA_CHECK(k_basis_gemm(ctx, LSA_C128, k->n, m, nvec, k->V, k->n, k->qdev, m, k->V2, k->n));
+    // (the pinned scratch keeps room behind the packed Y for the norms of the imaginary parts)
+    LSA_CHECK(basis_times_host_matrix(ctx, LSA_C128, k->n, m, nvec, k->V, Y, ldy, k->qdev, k->V2, (size_t)nvec * sizeof(double)));
     k->imag_norms.clear();
     if (normalise & 2) {
         // unit norm and canonical phase of all columns in three launches; the norms of the imaginary parts come back with them
@@ -1322,8 +1330,7 @@ int lsa_krylov_ritz_vectors(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t nvec
     if (k->row_perm) {  // rows back into the caller's numbering on the device (a fancy-indexed scatter of n x nvec on the host costs more than the solve's Schur forms)
         if (!k->xtmp) LSA_HIP_ALLOC(ctx, hipMalloc(&k->xtmp, vb * (size_t)(k->ncv + 1)));
         tmp = k->xtmp;
-        const int blocks = (int)std::min<int64_t>((k->n + 255) / 256, (int64_t)ctx->num_cu * 16);
-        hipLaunchKernelGGL(scatter_rows_kernel, dim3(blocks, nvec), dim3(256), 0, ctx->stream, k->n, k->row_perm, (const cplx*)k->V2, (cplx*)tmp);
+        LSA_CHECK(k_scatter_rows(ctx, LSA_C128, k->n, nvec, k->row_perm, k->V2, tmp));
         src = tmp;
     }
     hipError_t e = hipMemcpyAsync(X, src, vb * (size_t)nvec, hipMemcpyDeviceToHost, ctx->stream);
