@@ -12,7 +12,8 @@
 // in a second arena from the node's chunk to its parent's (offsets from a first-fit allocator run over the chunk order at
 // analysis time).  Device memory is therefore sum(m^2 + 2 m b) + one chunk's fronts + the live update matrices, not
 // sum(f^2): what lets the 3D cases beyond a million unknowns fit (round 2 kept every front whole: 40-60 % dead storage).
-// All nodes of a tree level run in one launch per sweep: 2 * (levels) - 1 dependent launches per solve.
+// All nodes of a tree level run in one launch per sweep: 2 * (levels) - 1 dependent launches per solve -- two fewer where the
+// root and its children are swept as one assembled inverse (NdTop below).
 //
 // Sweeps without index chasing: the iteration's vectors are kept in the elimination order (a node's own unknowns are
 // contiguous: the caller orders the matrix by lsa_nd_order and hands the tree back), children PUSH their update entries
@@ -1306,6 +1307,7 @@ struct NdBatchPtrs {
     void* ubuf[kNdBatchMax];
     void* acc[kNdBatchMax];
     void* xb[kNdBatchMax];
+    const void* top[kNdBatchMax];  // the assembled inverse of the top (nd_top_batch_kernel), or null
 };
 
 // upward sweep, one tree level: workgroup (x = node of the level, y = tile, z = problem)
@@ -1331,6 +1333,174 @@ __global__ __launch_bounds__(256) void nd_bwd_batch_kernel(const NdSweepNode* __
     if (r0 >= nd.m || nd.f == nd.m) return;
     const int z = blockIdx.z;
     nd_bwd_tile<MT, VT, LPR, ORDERED>(nd, r0, (int32_t)blockIdx.y, vs, (const MT*)p.ufac[z], idx, gell, (VT*)p.x[z], (VT*)p.xb[z]);
+}
+
+// ---- the top of the forest as ONE assembled inverse.  The root R (no boundary) and its children c, when they are the two
+// highest levels, are three dependent launches that each do almost nothing: children upward, root, children downward.  With
+//     v_c = rhs[own_c] + (what c's children pushed onto c's own positions)
+//     z_R = rhs[own_R] + sum over c of (what c's children pushed onto c's boundary positions, scattered by cmap_c)
+// those three steps are [x_c...; x_R] = T [v_c...; z_R] with the dense s x s matrix (s = m_R + sum m_c)
+//     T[R, R] = inv_R                    T[R, c] =  inv_R[:, cmap_c] s1_c            (s1_c = -F21 inv_c: boundary rows of L_c)
+//     T[c, R] = -U_c inv_R[cmap_c, :]    T[c, d] = [c == d] inv_c + T[c, R][:, cmap_d] s1_d
+// i.e. the exact inverse of the top Schur complement, ASSEMBLED from blocks the factorisation of the unmerged forest leaves
+// (nd_top_gemm_kernel, two launches per factorisation) instead of being eliminated as one wide pivot block.  One launch
+// (nd_top_kernel) then replaces the three; the transposed sweeps keep reading the unmerged blocks.
+constexpr int kTopChildren = 8;  // most children of the root the merged top takes
+struct NdTopNode {
+    int64_t acc_off, ge_off;  // the node's slot rows (what ITS children pushed) and gather rows
+    int32_t own0, m, f, nchild;
+    int32_t off, pad0;        // its first unknown in the order of the top: children in rank order, then the root
+};
+struct NdTop {
+    int32_t s, nchild;
+    NdTopNode node[kTopChildren + 1];  // the root's children, then the root
+};
+
+// one product of the assembly: C = D + sign * A B over tiles of 32 x 32, with A's columns or B's rows picked through a
+// boundary map (cmap of a child: positions in the root's front)
+struct NdTopJob {
+    int64_t a_off, b_off, c_off, d_off;  // A in lfac / ufac / T (a_src 0 / 1 / 2), B and D in lfac (d_off < 0: none), C in T
+    int32_t M, N, K, lda, ldb, ldd;
+    int32_t a_src, gather;               // gather 1: A's column k is acol[k]; 2: B's row k is brow[k]; the map at cmap + map_off
+    int32_t map_off, negate;
+};
+static_assert(sizeof(NdTopJob) == 72, "assembly job layout");
+
+// Plain FMA tiles: 256 threads, 2 x 2 results each, K in steps of 16 through LDS.  Every entry of C is one thread's sum in
+// the order of k: two factorisations of one matrix give the same T bit for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void nd_top_gemm_kernel(const int32_t* __restrict__ tiles, const NdTopJob* __restrict__ jobs,
+                                                          const int32_t* __restrict__ cmap, const T* __restrict__ lfac,
+                                                          const T* __restrict__ ufac, T* top, int32_t ldc) {
+    __shared__ T As[16][33], Bs[16][33];
+    const NdTopJob jb = jobs[tiles[2 * blockIdx.x]];
+    const int32_t tile = tiles[2 * blockIdx.x + 1], i0 = (tile >> 16) * 32, j0 = (tile & 0xFFFF) * 32;
+    const T* A = (jb.a_src == 0 ? lfac : jb.a_src == 1 ? ufac : (const T*)top) + jb.a_off;
+    const T* B = lfac + jb.b_off;
+    const int32_t* map = cmap + jb.map_off;
+    const int tid = threadIdx.x, ti = tid / 16, tj = tid % 16;
+    T acc[2][2] = {{scalar_traits<T>::zero(), scalar_traits<T>::zero()}, {scalar_traits<T>::zero(), scalar_traits<T>::zero()}};
+    for (int32_t k0 = 0; k0 < jb.K; k0 += 16) {
+        // A tile 32 x 16 (thread: row tid / 16 and + 16, column tid % 16), B tile 16 x 32 (row tid / 32 and + 8, column tid % 32)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int32_t i = i0 + ti + 16 * h, k = k0 + tj;
+            As[tj][ti + 16 * h] = i < jb.M && k < jb.K ? A[(size_t)i * jb.lda + (jb.gather == 1 ? map[k] : k)] : scalar_traits<T>::zero();
+            const int32_t kb = k0 + tid / 32 + 8 * h, j = j0 + tid % 32;
+            Bs[tid / 32 + 8 * h][tid % 32] = kb < jb.K && j < jb.N ? B[(size_t)(jb.gather == 2 ? map[kb] : kb) * jb.ldb + j] : scalar_traits<T>::zero();
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const T a0 = As[k][ti], a1 = As[k][ti + 16], b0 = Bs[k][tj], b1 = Bs[k][tj + 16];
+            fma_acc(acc[0][0], a0, b0);
+            fma_acc(acc[0][1], a0, b1);
+            fma_acc(acc[1][0], a1, b0);
+            fma_acc(acc[1][1], a1, b1);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int32_t i = i0 + ti + 16 * h, j = j0 + tj + 16 * g;
+            if (i >= jb.M || j >= jb.N) continue;
+            const T d = jb.d_off >= 0 ? lfac[jb.d_off + (size_t)i * jb.ldd + j] : scalar_traits<T>::zero();
+            top[jb.c_off + (size_t)i * ldc + j] = jb.negate ? s_sub(d, acc[h][g]) : s_add(d, acc[h][g]);
+        }
+}
+
+// the output of top row i (final: no downward step follows): into x, and to the boundary vectors of the grandchildren -- a row
+// of child c through c's gather rows at its own position; a row of the root, for every child c that has it at boundary
+// position p, through c's gather rows at m_c + p (what nd_bwd_tile hands on for a child of the root)
+template <typename VT>
+__device__ __forceinline__ void nd_top_store(const NdTop& tp, int32_t i, VT val, const int32_t* __restrict__ icmap, const int32_t* __restrict__ gell,
+                                             VT* __restrict__ x, VT* __restrict__ xb) {
+    const int32_t K = tp.nchild;
+    const NdTopNode& R = tp.node[K];
+    if (i >= R.off) {
+        const int32_t k = i - R.off;
+        x[R.own0 + k] = val;
+        for (int32_t c = 0; c < K; ++c) {
+            const NdTopNode& nd = tp.node[c];
+            const int32_t p = icmap[(size_t)c * R.m + k];
+            if (p >= 0) push_down(gell + nd.ge_off, nd.nchild, nd.f, nd.m + p, xb, val);
+        }
+        return;
+    }
+    for (int32_t c = 0; c < K; ++c) {
+        const NdTopNode& nd = tp.node[c];
+        if (i < nd.off || i >= nd.off + nd.m) continue;
+        x[nd.own0 + i - nd.off] = val;
+        push_down(gell + nd.ge_off, nd.nchild, nd.f, i - nd.off, xb, val);
+    }
+}
+
+// One tile of the merged top: 8 rows of T from r0, a wave per row pair (the shape of nd_fwd_tile<..., 64, ...>).  Every
+// workgroup stages [v_c...; z_R] from the right-hand side and the slot rows of the root's children; the sums have one order
+// (a child's slot rows in rank order, the children in rank order).  Vectors in elimination order only.
+template <typename MT, typename VT>
+__device__ __forceinline__ void nd_top_tile(const NdTop& tp, int32_t r0, VT* vs, const MT* __restrict__ top, const int32_t* __restrict__ icmap,
+                                            const int32_t* __restrict__ gell, const VT* __restrict__ rhs, VT* __restrict__ x,
+                                            const VT* __restrict__ acc, VT* __restrict__ xb) {
+    constexpr int LPR = 64;
+    const int32_t s = tp.s, K = tp.nchild;
+    const NdTopNode& R = tp.node[K];
+    const int tid = threadIdx.x, sw = tid / LPR, sl = tid % LPR;
+    const int32_t ra = r0 + sw, rb = ra + 256 / LPR;
+    const MT* Ta = top + (size_t)min(ra, s - 1) * s;
+    const MT* Tb = top + (size_t)min(rb, s - 1) * s;
+    VT acc0 = scalar_traits<VT>::zero(), acc1 = scalar_traits<VT>::zero();
+    MT pa[4], pb[4];
+    row_pair_prefetch<LPR>(Ta, Tb, min(kCH, s), sl, pa, pb);
+    for (int32_t c0 = 0; c0 < s; c0 += kCH) {
+        const int32_t c1 = min(c0 + kCH, s);
+        for (int32_t c = 0; c < K; ++c) {
+            const NdTopNode& nd = tp.node[c];
+            const VT* slots = acc + nd.acc_off;
+            for (int32_t j = max(c0, nd.off) + tid; j < min(c1, nd.off + nd.m); j += 256) {
+                const int32_t r = j - nd.off;
+                vs[j - c0] = slot_sum(slots, nd.nchild, nd.f, r, rhs[nd.own0 + r]);
+            }
+        }
+        for (int32_t j = max(c0, R.off) + tid; j < c1; j += 256) {
+            const int32_t k = j - R.off;
+            VT z = rhs[R.own0 + k];
+            for (int32_t c = 0; c < K; ++c) {
+                const NdTopNode& nd = tp.node[c];
+                const int32_t p = icmap[(size_t)c * R.m + k];
+                if (p >= 0) z = s_add(z, slot_sum(acc + nd.acc_off, nd.nchild, nd.f, nd.m + p, scalar_traits<VT>::zero()));
+            }
+            vs[j - c0] = z;
+        }
+        __syncthreads();
+        if (c0 == 0) two_row_dot_prefetched<LPR>(Ta, Tb, vs, c1 - c0, sl, acc0, acc1, pa, pb);
+        else two_row_dot<LPR>(Ta + c0, Tb + c0, vs, c1 - c0, sl, acc0, acc1);
+        __syncthreads();
+    }
+    const VT s0 = lanes_sum<LPR>(acc0), s1 = lanes_sum<LPR>(acc1);
+    if (sl == 0) {
+        if (ra < s) nd_top_store(tp, ra, s0, icmap, gell, x, xb);
+        if (rb < s) nd_top_store(tp, rb, s1, icmap, gell, x, xb);
+    }
+}
+
+template <typename MT, typename VT>
+__global__ __launch_bounds__(256) void nd_top_kernel(NdTop tp, const MT* __restrict__ top, const int32_t* __restrict__ icmap,
+                                                     const int32_t* __restrict__ gell, const VT* __restrict__ rhs, VT* __restrict__ x,
+                                                     const VT* __restrict__ acc, VT* __restrict__ xb) {
+    __shared__ VT vs[kCH];
+    nd_top_tile<MT, VT>(tp, (int32_t)blockIdx.x * 8, vs, top, icmap, gell, rhs, x, acc, xb);
+}
+
+// (tile, problem)
+template <typename MT, typename VT>
+__global__ __launch_bounds__(256) void nd_top_batch_kernel(NdTop tp, const int32_t* __restrict__ icmap, const int32_t* __restrict__ gell, NdBatchPtrs p) {
+    __shared__ VT vs[kCH];
+    const int z = blockIdx.y;
+    nd_top_tile<MT, VT>(tp, (int32_t)blockIdx.x * 8, vs, (const MT*)p.top[z], icmap, gell, (const VT*)p.rhs[z], (VT*)p.x[z], (const VT*)p.acc[z],
+                        (VT*)p.xb[z]);
 }
 
 // ---- downward sweep of DISTRIBUTED top nodes: a rank finishes its slice of the node's own rows (nd_bwd_kernel on a record
@@ -1517,6 +1687,15 @@ struct lsa_ndlu {
     hipEvent_t ev_panel = nullptr, ev_pivots = nullptr;
     double seconds_analyse = 0.0, seconds_numeric = 0.0;
     int32_t solve_launches = 0;
+    // the root and its children as one assembled inverse (nd_top_kernel): top.s = 0 where the forest is not eligible
+    NdTop top = {};
+    int32_t top_level = -1;                    // the root's level; the level below it has no launch of its own
+    void* d_top = nullptr;                     // T, top.s^2 scalars of the factor type, assembled by every numeric factorisation
+    int32_t* d_top_icmap = nullptr;            // per child of the root, per own row of the root: its position in the child's boundary, or -1
+    NdTopJob* d_top_jobs = nullptr;
+    int32_t* d_top_tiles = nullptr;            // (job, tile) pairs of the two assembly launches
+    int32_t top_tiles[2] = {0, 0};
+    int64_t top_replaced_entries = 0;          // factor scalars the sweeps no longer read
     int acc_vbytes = 0;  // scalar size of the vectors the slot rows were last used with (their never-written entries must read zero)
 };
 
@@ -1524,6 +1703,8 @@ namespace {
 
 void nd_free(lsa_ndlu* f) {
     if (!f) return;
+    for (void* p : {f->d_top, (void*)f->d_top_icmap, (void*)f->d_top_jobs, (void*)f->d_top_tiles})
+        if (p) (void)hipFree(p);
     for (void* p : {(void*)f->d_lnodes_bwd, (void*)f->d_dist_nodes, (void*)f->d_child_ptr, (void*)f->d_child_idx, f->d_xstage, f->d_xg, (void*)f->d_tgoff, f->d_tg})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)f->d_nodes, (void*)f->d_lnodes, (void*)f->d_gell, (void*)f->d_idx, (void*)f->d_cmap, (void*)f->d_tiles,
@@ -1541,6 +1722,91 @@ int upload(lsa_ctx* ctx, const std::vector<U>& h, U** d) {
     const size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(U);
     LSA_HIP_ALLOC(ctx, hipMalloc((void**)d, bytes));
     if (!h.empty()) LSA_HIP_CHECK(ctx, hipMemcpy(*d, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice));
+    return LSA_OK;
+}
+
+// The merged top (NdTop): decided once per analysis.  Eligible: one rank, vectors in elimination order, one root that is alone
+// on the last level, and the level below it holds exactly the root's children, none of them a leaf, all with slot rows; at
+// most LSA_ND_TOPINV unknowns in all (0 = off).  Anything else keeps the launch per level and direction.
+int nd_setup_top(lsa_ctx* ctx, lsa_ndlu* f, const std::vector<NdNodeDev>& nodes) {
+    const NdSymbolic& S = f->S;
+    f->top = NdTop{};
+    f->top_level = -1;
+    // (default: the widest top measured -- 739 / 608 / 1203 unknowns at 5 k / 30 k / 121 k unknowns, each faster per apply and per
+    //  factorisation + 184 applies)
+    static const int32_t limit = getenv("LSA_ND_TOPINV") && *getenv("LSA_ND_TOPINV") ? std::max(0, atoi(getenv("LSA_ND_TOPINV"))) : 1280;
+    if (limit <= 0 || S.nranks != 1 || S.has_dist || !f->ordered || S.nlevels < 3) return LSA_OK;
+    const int32_t lr = S.nlevels - 1;
+    if (S.lvl_ptr[(size_t)lr + 1] - S.lvl_ptr[(size_t)lr] != 1) return LSA_OK;
+    const int32_t R = S.lvl_nodes[(size_t)S.lvl_ptr[(size_t)lr]];
+    int32_t roots = 0;
+    for (int32_t t = 0; t < S.nt; ++t) roots += S.parent[(size_t)t] < 0;
+    const int32_t c0 = S.child_ptr[(size_t)R], K = S.child_ptr[(size_t)R + 1] - c0, mR = S.m[(size_t)R];
+    if (roots != 1 || S.parent[(size_t)R] >= 0 || S.f[(size_t)R] != mR || K < 1 || K > kTopChildren) return LSA_OK;
+    if (S.lvl_ptr[(size_t)lr] - S.lvl_ptr[(size_t)lr - 1] != K) return LSA_OK;
+    NdTop tp = {};
+    tp.nchild = K;
+    int64_t s = 0, replaced = (int64_t)mR * mR;
+    for (int32_t ci = 0; ci < K; ++ci) {
+        const int32_t c = S.child_idx[(size_t)c0 + ci];
+        const NdNodeDev& nd = nodes[(size_t)c];
+        bool on_level = false;
+        for (int32_t q = S.lvl_ptr[(size_t)lr - 1]; q < S.lvl_ptr[(size_t)lr]; ++q) on_level |= S.lvl_nodes[(size_t)q] == c;
+        if (!on_level || nd.nchild < 1 || nd.acc_off < 0 || nd.f <= nd.m || nd.m < 1 || S.kind[(size_t)c] == 3 || S.kind[(size_t)c] == 4) return LSA_OK;
+        tp.node[ci] = NdTopNode{nd.acc_off, nd.ge_off, nd.own0, nd.m, nd.f, nd.nchild, (int32_t)s, 0};
+        s += nd.m;
+        replaced += (int64_t)nd.m * nd.m + 2 * (int64_t)nd.m * (nd.f - nd.m);
+    }
+    const NdNodeDev& nr = nodes[(size_t)R];
+    tp.node[K] = NdTopNode{nr.acc_off, nr.ge_off, nr.own0, mR, mR, K, (int32_t)s, 0};
+    s += mR;
+    if (s > limit) return LSA_OK;
+    tp.s = (int32_t)s;
+    std::vector<int32_t> icmap((size_t)K * mR, -1);
+    for (int32_t ci = 0; ci < K; ++ci) {
+        const int32_t c = S.child_idx[(size_t)c0 + ci];
+        for (int32_t p = 0; p < S.f[(size_t)c] - S.m[(size_t)c]; ++p) {
+            const int32_t k = S.cmap[(size_t)S.cmap_off[(size_t)c] + p];
+            if (k < 0 || k >= mR) return LSA_OK;  // (cannot happen under a root without boundary)
+            icmap[(size_t)ci * mR + k] = p;
+        }
+    }
+    // the assembly: launch 1 = inv_R, -Q_c = -U_c inv_R[cmap_c, :], P_c = inv_R[:, cmap_c] s1_c; launch 2 = the children's blocks
+    std::vector<NdTopJob> jobs;
+    std::vector<int32_t> tiles;
+    auto add = [&](const NdTopJob& jb) {
+        for (int32_t ti = 0; ti < (jb.M + 31) / 32; ++ti)
+            for (int32_t tj = 0; tj < (jb.N + 31) / 32; ++tj) {
+                tiles.push_back((int32_t)jobs.size());
+                tiles.push_back((ti << 16) | tj);
+            }
+        jobs.push_back(jb);
+    };
+    const int64_t oR = tp.node[K].off;
+    add(NdTopJob{0, 0, oR * s + oR, nr.lfac_off, mR, mR, 0, 1, 1, mR, 0, 0, 0, 0});
+    for (int32_t ci = 0; ci < K; ++ci) {
+        const NdNodeDev& nd = nodes[(size_t)S.child_idx[(size_t)c0 + ci]];
+        const int32_t m = nd.m, b = nd.f - nd.m;
+        const int64_t o = tp.node[ci].off;
+        add(NdTopJob{nd.ufac_off, nr.lfac_off, o * s + oR, -1, m, mR, b, b, mR, 0, 1, 2, nd.cmap_off, 1});
+        add(NdTopJob{nr.lfac_off, nd.lfac_off + (int64_t)m * m, oR * s + o, -1, mR, m, b, mR, m, 0, 0, 1, nd.cmap_off, 0});
+    }
+    f->top_tiles[0] = (int32_t)tiles.size() / 2;
+    for (int32_t ci = 0; ci < K; ++ci)
+        for (int32_t di = 0; di < K; ++di) {
+            const NdNodeDev &nc = nodes[(size_t)S.child_idx[(size_t)c0 + ci]], &nd = nodes[(size_t)S.child_idx[(size_t)c0 + di]];
+            add(NdTopJob{tp.node[ci].off * s + oR, nd.lfac_off + (int64_t)nd.m * nd.m, tp.node[ci].off * s + tp.node[di].off, ci == di ? nc.lfac_off : -1, nc.m,
+                         nd.m, nd.f - nd.m, (int32_t)s, nd.m, nc.m, 2, 1, nd.cmap_off, 0});
+        }
+    f->top_tiles[1] = (int32_t)tiles.size() / 2 - f->top_tiles[0];
+    LSA_CHECK(upload(ctx, icmap, &f->d_top_icmap));
+    LSA_CHECK(upload(ctx, jobs, &f->d_top_jobs));
+    LSA_CHECK(upload(ctx, tiles, &f->d_top_tiles));
+    LSA_HIP_ALLOC(ctx, hipMalloc(&f->d_top, (size_t)(s * s) * esize(f->dtype)));
+    f->top = tp;
+    f->top_level = lr;
+    f->top_replaced_entries = replaced;
+    f->solve_launches -= 2;
     return LSA_OK;
 }
 
@@ -1918,6 +2184,7 @@ int nd_setup(lsa_ctx* ctx, lsa_ndlu* f, int64_t free_agreed = 0) {
     }
     f->solve_launches = 0;
     for (const NdLevel& L : f->levels) f->solve_launches += (L.fwd_tiles > 0) + (L.bwd_tiles > 0);
+    LSA_CHECK(nd_setup_top(ctx, f, nodes));
     return LSA_OK;
 }
 
@@ -2150,6 +2417,11 @@ int nd_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C) {
         if (L.save.count > 0)
             hipLaunchKernelGGL((nd_save_update_kernel<T>), dim3(L.save.count), dim3(256), 0, st, tl + 2 * L.save.off, f->d_nodes, (const T*)front, upd);
     }
+    if (f->top.s > 0)  // the merged top of the sweeps, assembled from the blocks just made (the second launch reads the first one's -Q_c)
+        for (int q = 0, t0 = 0; q < 2; t0 += f->top_tiles[q++])
+            if (f->top_tiles[q] > 0)
+                hipLaunchKernelGGL((nd_top_gemm_kernel<T>), dim3(f->top_tiles[q]), dim3(256), 0, st, f->d_top_tiles + 2 * t0, f->d_top_jobs, f->d_cmap,
+                                   (const T*)lfac, (const T*)ufac, (T*)f->d_top, f->top.s);
     if (!exchanged && S.nranks > 1 && f->xupd_slot > 0)  // (no replicated level: still a collective)
         LSA_CHECK(k_allgather_inplace(ctx, f->d_upd, (size_t)f->xupd_slot * sizeof(T)));
     int32_t hflag[4] = {0, 0, 0, 0};
@@ -2204,6 +2476,7 @@ int nd_apply_ordered(lsa_ctx* ctx, lsa_ndlu* f, const VT* b, VT* x) {
     const MT* ufac = (const MT*)f->d_ufac;
     const NdSymbolic& S = f->S;
     VT *ubuf = (VT*)f->d_ubuf, *acc = (VT*)f->d_acc, *xb = (VT*)f->d_xb;
+    const bool top = f->top.s > 0;  // root and children in one launch (nd_top_kernel); their downward launch falls away
     if (f->acc_vbytes != (int)sizeof(VT)) {
         // the slot rows are indexed in units of the vector scalar: after a solve with the other scalar type the entries no
         // child writes no longer read zero
@@ -2215,7 +2488,11 @@ int nd_apply_ordered(lsa_ctx* ctx, lsa_ndlu* f, const VT* b, VT* x) {
         if ((int32_t)li == S.phase_b_level && S.nranks > 1 && S.xu_slot > 0) LSA_CHECK(k_allgather_inplace(ctx, f->d_ubuf, (size_t)S.xu_slot * sizeof(VT)));
         if (li == f->levels.size()) break;
         const NdLevel& L = f->levels[li];
-        if (L.fwd_tiles > 0) {
+        if (ORDERED && top && (int32_t)li + 1 == f->top_level) continue;  // the root's children: inside the root's launch
+        if (ORDERED && top && (int32_t)li == f->top_level) {
+            hipLaunchKernelGGL((nd_top_kernel<MT, VT>), dim3((f->top.s + 7) / 8), dim3(256), 0, st, f->top, (const MT*)f->d_top, f->d_top_icmap, f->d_gell, b, x,
+                               (const VT*)acc, xb);
+        } else if (L.fwd_tiles > 0) {
             const dim3 grid(L.node_count, L.fwd_tiles);
             const NdSweepNode* ln = f->d_lnodes + L.node_begin;
             if (L.sweep_rows == 8)
@@ -2230,7 +2507,7 @@ int nd_apply_ordered(lsa_ctx* ctx, lsa_ndlu* f, const VT* b, VT* x) {
     }
     for (size_t l = f->levels.size(); l-- > 0;) {
         const NdLevel& L = f->levels[l];
-        if (L.bwd_tiles > 0) {
+        if (L.bwd_tiles > 0 && !(ORDERED && top && (int32_t)l + 1 == f->top_level)) {
             const dim3 grid(L.node_count, L.bwd_tiles);
             const NdSweepNode* ln = f->d_lnodes_bwd + L.node_begin;
             if (L.sweep_rows == 8) hipLaunchKernelGGL((nd_bwd_kernel<MT, VT, 64, ORDERED>), grid, dim3(256), 0, st, ln, ufac, f->d_idx, f->d_gell, x, xb);
@@ -2278,8 +2555,16 @@ int nd_apply_batch_ordered(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const VT
         p.ubuf[z] = f[z]->d_ubuf;
         p.acc[z] = f[z]->d_acc;
         p.xb[z] = f[z]->d_xb;
+        p.top[z] = f[z]->d_top;
     }
-    for (const NdLevel& L : f0->levels) {
+    const bool top = ORDERED && f0->top.s > 0;  // as nd_apply_ordered
+    for (size_t li = 0; li < f0->levels.size(); ++li) {
+        const NdLevel& L = f0->levels[li];
+        if (top && (int32_t)li + 1 == f0->top_level) continue;
+        if (top && (int32_t)li == f0->top_level) {
+            hipLaunchKernelGGL((nd_top_batch_kernel<MT, VT>), dim3((f0->top.s + 7) / 8, J), dim3(256), 0, st, f0->top, f0->d_top_icmap, f0->d_gell, p);
+            continue;
+        }
         if (L.fwd_tiles == 0) continue;
         const dim3 grid(L.node_count, L.fwd_tiles, J);
         const NdSweepNode* ln = f0->d_lnodes + L.node_begin;
@@ -2292,7 +2577,7 @@ int nd_apply_batch_ordered(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const VT
     }
     for (size_t l = f0->levels.size(); l-- > 0;) {
         const NdLevel& L = f0->levels[l];
-        if (L.bwd_tiles == 0) continue;
+        if (L.bwd_tiles == 0 || (top && (int32_t)l + 1 == f0->top_level)) continue;
         const dim3 grid(L.node_count, L.bwd_tiles, J);
         const NdSweepNode* ln = f0->d_lnodes_bwd + L.node_begin;
         if (L.sweep_rows == 8) hipLaunchKernelGGL((nd_bwd_batch_kernel<MT, VT, 64, ORDERED>), grid, dim3(256), 0, st, ln, f0->d_idx, f0->d_gell, p);
@@ -2324,6 +2609,7 @@ bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g) {
             a.sweep_rows != c.sweep_rows || a.dist_count != 0 || c.dist_count != 0)
             return false;
     }
+    if (f->top.s != g->top.s || f->top_level != g->top_level) return false;
     return true;
 }
 
@@ -2809,7 +3095,9 @@ int lsa_ndlu_info(const lsa_ndlu* f, int32_t* ntree, int32_t* nlevels, int32_t* 
     if (factor_entries) *factor_entries = S.factor_entries;
     if (front_entries) *front_entries = f->lfac_entries + f->ufac_entries + f->work_entries + f->upd_entries;  // scalars of the device buffers
     // one solve reads every factor scalar once, the right-hand side once, and reads + writes the solution and the update vectors
-    if (apply_bytes) *apply_bytes = S.factor_entries * (int64_t)esize(f->dtype) + 16 * (3 * (int64_t)S.n + 2 * S.u_off[(size_t)S.nt]);
+    // (with the merged top: its s^2 scalars instead of the packed blocks of the root and its children)
+    const int64_t swept = S.factor_entries - f->top_replaced_entries * (f->top.s > 0) + (int64_t)f->top.s * f->top.s;
+    if (apply_bytes) *apply_bytes = swept * (int64_t)esize(f->dtype) + 16 * (3 * (int64_t)S.n + 2 * S.u_off[(size_t)S.nt]);
     if (apply_launches) *apply_launches = f->solve_launches;
     if (seconds_analyse) *seconds_analyse = f->seconds_analyse;
     if (seconds_numeric) *seconds_numeric = f->seconds_numeric;
