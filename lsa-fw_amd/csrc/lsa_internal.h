@@ -350,7 +350,7 @@ int blk_setup(lsa_ctx* ctx, lsa_ilu* pc, int32_t B);
 int blk_solve(lsa_ctx* ctx, lsa_ilu* pc, int which, int vdtype, const void* b, void* x);
 void blk_release(lsa_ilu* pc);
 
-// ---- nested-dissection multifrontal LU (ndlu.hip) -------------------------------------------------------
+// ---- nested-dissection multifrontal LU (ndlu_sweeps.hip) -------------------------------------------------------
 struct lsa_ndlu;
 int ndlu_solve_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, const void* b, void* x);
 int ndlu_solve_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, const void* b, void* x);

@@ -1,4 +1,5 @@
-// Nested-dissection multifrontal LU: the analysis result shared by nd_symbolic.hip (host) and ndlu.hip (device).
+// Nested-dissection multifrontal LU: the analysis result shared by nd_symbolic.hip (host) and the device side (ndlu.hip: set-up,
+// cache and C-ABI; ndlu_factor.hip; ndlu_sweeps.hip; their shared records are in ndlu_internal.h).
 //
 // Elimination tree of supernodes ("tree nodes") from recursive graph bisection.  Node t owns m_t unknowns (a leaf
 // subdomain or a separator) and has a boundary of b_t unknowns that belong to its ancestors; its front is the dense
@@ -91,6 +92,31 @@ int nd_analyse_tree(int32_t n, const int32_t* rp, const int32_t* ci, int32_t nt,
 int nd_analyse(int32_t n, const int32_t* rp, const int32_t* ci, int32_t leaf_size, const int8_t* constraint, NdSymbolic* out, char* err,
                int errlen, bool order_only = false);
 uint64_t nd_pattern_hash(int32_t n, const int32_t* rp, const int32_t* ci);
+// What a parked analysis is matched by, besides its pattern (FNV-1a over 32-bit words; never 0, which stands for "none"): the set
+// of constraint unknowns, and the caller's tree with the rank it was analysed for.  The analysis stores them
+// (NdSymbolic::constraint_hash, tree_hash) and the cache of ndlu.hip computes them for what it is asked for.
+inline void nd_hash_mix(uint64_t& h, int32_t v) {
+    h ^= (uint64_t)(uint32_t)v;
+    h *= 1099511628211ull;
+}
+inline uint64_t nd_constraint_hash(int32_t n, const int8_t* constraint) {
+    uint64_t h = 1469598103934665603ull;
+    for (int32_t v = 0; v < n; ++v)
+        if (constraint[v]) nd_hash_mix(h, v);
+    return h | 1ull;
+}
+inline uint64_t nd_tree_hash(int32_t nt, const int32_t* first, const int32_t* size, const int32_t* parent, const int32_t* owner, int rank, int nranks) {
+    uint64_t h = 1469598103934665603ull;
+    for (int32_t t = 0; t < nt; ++t) {
+        nd_hash_mix(h, first[t]);
+        nd_hash_mix(h, size[t]);
+        nd_hash_mix(h, parent[t]);
+        nd_hash_mix(h, owner ? owner[t] : 0);
+    }
+    nd_hash_mix(h, rank);
+    nd_hash_mix(h, nranks);
+    return h | 1ull;
+}
 
 // Where everything of a factorisation lives on the device, from the analysis alone (host arithmetic; nd_symbolic.hip):
 // packed factors, the chunks of working fronts that share one arena, the update arena laid out by a first-fit allocator run

@@ -1,5 +1,6 @@
 // Host-side analysis of the nested-dissection multifrontal LU (no GPU needed): ordering by recursive graph bisection,
-// supernodal elimination forest, front index lists and every index table the device kernels of ndlu.hip walk.
+// supernodal elimination forest, front index lists and every index table the device kernels of ndlu_factor.hip and
+// ndlu_sweeps.hip walk.
 //
 // Stands in for the symbolic phase of the sparse direct solver behind PETSc's PC LU, which is what the reference's
 // cylinder runs select for the ST's KSP (.examples/eigenvalues.py:100; Sensitivity/__init__.py:182,260).  Only the
@@ -726,11 +727,8 @@ int nd_analyse(int32_t n, const int32_t* rp, const int32_t* ci, int32_t leaf_siz
             for (int32_t v : own[(size_t)t]) node_of_v[(size_t)v] = t;
         std::vector<int32_t> target((size_t)n, -1), left((size_t)nt, 0);
         for (int32_t t = 0; t < nt; ++t) left[(size_t)t] = (int32_t)own[(size_t)t].size();
-        uint64_t h = 1469598103934665603ull;
         for (int32_t v = 0; v < n; ++v) {
             if (!constraint[v]) continue;
-            h ^= (uint64_t)(uint32_t)v;
-            h *= 1099511628211ull;
             const int32_t t0 = node_of_v[(size_t)v];
             int32_t best = t0;
             for (int64_t p = g.ptr[v]; p < g.ptr[(size_t)v + 1]; ++p) {
@@ -744,7 +742,7 @@ int nd_analyse(int32_t n, const int32_t* rp, const int32_t* ci, int32_t leaf_siz
             target[(size_t)v] = best;
             --left[(size_t)t0];
         }
-        S.constraint_hash = h | 1ull;
+        S.constraint_hash = nd_constraint_hash(n, constraint);
         std::vector<std::vector<int32_t>> moved((size_t)nt);
         for (int32_t t = 0; t < nt; ++t) {
             std::vector<int32_t>& L = own[(size_t)t];
@@ -861,11 +859,6 @@ int nd_analyse_tree(int32_t n, const int32_t* rp, const int32_t* ci, int32_t nt,
     S.nnz = n > 0 ? rp[n] : 0;
     S.leaf_size = 0;
     S.pattern_hash = nd_pattern_hash(n, rp, ci);
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](int32_t v) {
-        h ^= (uint64_t)(uint32_t)v;
-        h *= 1099511628211ull;
-    };
     std::vector<std::vector<int32_t>> own((size_t)nt);
     std::vector<int32_t> par(parent, parent + nt);
     for (int32_t t = 0; t < nt; ++t) {
@@ -873,14 +866,8 @@ int nd_analyse_tree(int32_t n, const int32_t* rp, const int32_t* ci, int32_t nt,
             return fail(LSA_ERR_ARG, "nd_analyse_tree: node range or parent out of bounds");
         own[(size_t)t].resize((size_t)size[t]);
         std::iota(own[(size_t)t].begin(), own[(size_t)t].end(), first[t]);
-        mix(first[t]);
-        mix(size[t]);
-        mix(parent[t]);
-        mix(owner ? owner[t] : 0);
     }
-    mix(rank);
-    mix(nranks);
-    S.tree_hash = h | 1ull;
+    S.tree_hash = nd_tree_hash(nt, first, size, parent, owner, rank, nranks);
     Graph g;
     build_graph(n, rp, ci, g);
     return nd_finish(S, n, rp, ci, g, own, par, owner, rank, nranks, fail);

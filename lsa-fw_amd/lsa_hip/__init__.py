@@ -638,7 +638,7 @@ def nd_order(A, leaf_size: int = 0, constraint=None) -> dict:
             "parent": ex["parent"], "level": ex["level"]}
 
 
-NDLU_BATCH_MAX = 16  # factorisations of one lsa_ndlu_solve_batch call (kNdBatchMax in csrc/ndlu.hip)
+NDLU_BATCH_MAX = 16  # factorisations of one lsa_ndlu_solve_batch call (kNdBatchMax in csrc/ndlu_internal.h)
 
 
 class NdLu:

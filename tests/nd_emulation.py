@@ -1,5 +1,5 @@
 """numpy walk of the nested-dissection analysis tables, in the order and with the data flow of the device kernels of
-``csrc/ndlu.hip`` (test infrastructure: checks ``lsa_nd_analyse`` without a GPU; never imported by the product).
+``csrc/ndlu_factor.hip`` and ``csrc/ndlu_sweeps.hip`` (test infrastructure: checks ``lsa_nd_analyse`` without a GPU; never imported by the product).
 
 Every step reads only what the matching kernel reads: ``asm_dst`` (assembly), ``cmap`` (extend-add), ``gptr``/``gidx``
 (upward sweep), ``idx`` (both sweeps); the pivot blocks are inverted with LAPACK instead of the panel Gauss-Jordan."""
@@ -80,7 +80,8 @@ class Emulated:
 class EmulatedRanks:
     """The subtree-parallel factorisation walked rank by rank in numpy: per-rank tables of ``lsa_nd_analyse_tree``, own
     subtrees first, the in-place all-gathers of the exchange regions (subtree-root fronts, then update vectors), then the
-    replicated top -- the data flow of ``nd_numeric`` / ``nd_apply`` in ``csrc/ndlu.hip`` with more than one rank."""
+    replicated top -- the data flow of ``nd_numeric`` (``csrc/ndlu_factor.hip``) and ``nd_sweep`` (``csrc/ndlu_sweeps.hip``) with more
+    than one rank."""
 
     def __init__(self, tables_per_rank: list[dict], values: np.ndarray):
         self.P = len(tables_per_rank)
@@ -181,7 +182,7 @@ class EmulatedRanks:
 
 class EmulatedDistributedTop:
     """The forest cut over ranks WITH DISTRIBUTED TOP NODES (kind 4), walked in numpy with the data flow of ``nd_numeric`` /
-    ``nd_apply_ordered``: a distributed node keeps on every rank the whole pivot block and F12, and the rank's slice of the
+    ``nd_sweep``: a distributed node keeps on every rank the whole pivot block and F12, and the rank's slice of the
     boundary rows (front (m + brow) x f); its children's update matrices reach it row by row from the ranks that hold them;
     the inverse is formed redundantly, ``L = -F21[rows] inv`` and the update rows locally, ``U`` by slices of the own rows.
     Sweeps: a rank produces its slice of a distributed node's update entries into its slot of the level's exchange region

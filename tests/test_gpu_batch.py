@@ -96,14 +96,20 @@ def _factors(hip_ctx, name, res, targets):
 
 
 @pytest.mark.parametrize("J,shifts,vdtype", [(1, "complex", np.complex128), (3, "complex", np.complex128), (3, "real", np.complex128),
-                                             (3, "real", np.float64)])
+                                             (3, "real", np.float64), (16, "complex_S2k", np.complex128)])
 def test_ndlu_solve_batch_equals_solo_solves(hip_ctx, J, shifts, vdtype):
     """Complex factors (complex shifts), real factors with complex and with real vectors: each instance of the batched sweeps
-    against lsa_ndlu_solve per factor set."""
+    (the kernels at the batch's pointer capacity) against lsa_ndlu_solve per factor set (the same kernels at capacity one).
+    J = 16 fills the pointer struct to its last slot: sixteen distinct complex shifts of one Reynolds number of S2k."""
     import lsa_hip
 
-    targets = TARGETS[:J] if shifts == "complex" else tuple(0.05 + 0.01 * j for j in range(J))
-    fs = _factors(hip_ctx, "S5k", REYNOLDS[:J], targets)
+    name, res = ("S2k", REYNOLDS[:1] * J) if shifts == "complex_S2k" else ("S5k", REYNOLDS[:J])
+    if shifts == "complex_S2k":
+        targets = tuple(TARGETS[0] + 0.01 * j * (1 + 1j) for j in range(J))
+    else:
+        targets = TARGETS[:J] if shifts == "complex" else tuple(0.05 + 0.01 * j for j in range(J))
+    assert len(set(targets)) == J == len(res)
+    fs = _factors(hip_ctx, name, res, targets)
     n = fs[0][1].shape[0]
     rng = np.random.default_rng(11)
     bs = [rng.standard_normal(n) + 1j * rng.standard_normal(n) for _ in range(J)]
@@ -141,6 +147,8 @@ def test_ndlu_solve_batch_rejects_other_analyses(hip_ctx):
         lsa_hip.NdLu.solve_batch([f5, fr], v5[:2], v5[2:])
     with pytest.raises(ValueError, match="share a factorisation"):
         lsa_hip.NdLu.solve_batch([f5, f5], v5[:2], v5[2:])
+    with pytest.raises(ValueError, match="at most 16"):
+        lsa_hip.NdLu.solve_batch([f5] * 17, v5[:1] * 17, v5[1:2] * 17)
 
 
 # ---- solve_batch ------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-"""GPU suite: the root of the elimination forest and its children swept as one assembled inverse (``nd_top_kernel``,
-``nd_top_gemm_kernel`` in ``csrc/ndlu.hip``) against the launch per level and direction it replaces (``LSA_ND_TOPINV=0``).
+"""GPU suite: the root of the elimination forest and its children swept as one assembled inverse (``nd_top_kernel`` in
+``csrc/ndlu_sweeps.hip``, ``nd_top_gemm_kernel`` in ``csrc/ndlu_factor.hip``) against the launch per level and direction it replaces (``LSA_ND_TOPINV=0``).
 The knob is read once per process: every setting runs in a child (tests/topinv_child.py)."""
 
 import json

@@ -1,5 +1,5 @@
-"""CPU suite: the top of the elimination forest as one assembled inverse (``nd_top_kernel`` / ``nd_top_gemm_kernel`` in
-``csrc/ndlu.hip``), checked in numpy on the analysis tables.
+"""CPU suite: the top of the elimination forest as one assembled inverse (``nd_top_kernel`` in ``csrc/ndlu_sweeps.hip``,
+``nd_top_gemm_kernel`` in ``csrc/ndlu_factor.hip``), checked in numpy on the analysis tables.
 
 The root R and its children c are three dependent steps of the emulated walk (children upward, root, children downward).
 With the blocks a factorisation leaves -- ``inv_t``, ``s1_t = -F21 inv_t``, ``U_t = inv_t F12`` -- they are one product

@@ -1,4 +1,4 @@
-// Development aid: FP64 matrix-core product C += A B (row-major), tile-shape variants of the kernel in csrc/ndlu.hip, and the
+// Development aid: FP64 matrix-core product C += A B (row-major), tile-shape variants of the kernel in csrc/ndlu_factor.hip, and the
 // bare instruction rate.   hipcc -O3 --offload-arch=gfx950 tools/micro/mfma_gemm_bench.hip -o /tmp/mfma_bench && /tmp/mfma_bench
 #include <hip/hip_runtime.h>
 #include <cstdio>
