@@ -224,6 +224,25 @@ int lsa_ndlu_solve_batch(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, const lsa_
  * factorisation and no transposed matrix. */
 int lsa_ndlu_solve_adjoint(lsa_ctx *ctx, lsa_ndlu *f, int conj, const lsa_vec *b, lsa_vec *x);
 int lsa_ndlu_solve_time(lsa_ctx *ctx, lsa_ndlu *f, const lsa_vec *b, lsa_vec *x, int iters, double *avg_ms);
+/* X[:, q] = op(C)^-1 B[:, q], q < nrhs, on ONE factorisation: PETSc MatMatSolve / KSPMatSolve (the reference reaches them through
+ * the kept KSP of iKSP, Solver/utils.py:331-419, one right-hand side at a time).  trans: 0 = C^-1, 1 = C^-T, 2 = C^-H.  B and X are
+ * column-major blocks: column q starts at q * ld scalars, ld >= n, each vector at least ld (nrhs - 1) + n long.  B == X with
+ * ldb == ldx solves in place; any other overlap, nrhs < 1, ld < n, a short block, mixed vector dtypes, complex factors with real
+ * vectors: LSA_ERR_ARG.  For trans = 0 on one rank the columns go through the sweeps in passes of up to 8 (real vectors) or 4
+ * (complex vectors) that read every factor scalar once per pass (lsa_ndlu_multi_info); a forest cut over ranks and the
+ * transposed systems run column by column.  Either
+ * way column q holds exactly the bits lsa_ndlu_solve / lsa_ndlu_solve_adjoint gives for it.  nrhs = 1 is lsa_ndlu_solve.  The
+ * sweep buffers of the further columns of a pass are made by the first call and released with the factorisation; where they
+ * do not fit, the passes get narrower, down to column by column. */
+int lsa_ndlu_solve_multi(lsa_ctx *ctx, lsa_ndlu *f, int trans, int32_t nrhs, const lsa_vec *B, int64_t ldb, lsa_vec *X, int64_t ldx);
+/* `iters` such block solves back to back (B and X apart), bracketed by HIP events on the context's stream; *avg_ms = mean per
+ * block solve (KSPMatSolve timed as lsa_ndlu_solve_time times KSPSolve) */
+int lsa_ndlu_solve_multi_time(lsa_ctx *ctx, lsa_ndlu *f, int trans, int32_t nrhs, const lsa_vec *B, int64_t ldb, lsa_vec *X, int64_t ldx,
+                              int iters, double *avg_ms);
+/* what the last lsa_ndlu_solve_multi on f used (the work MatMatSolve hides): width = columns of its widest pass (1: column by
+ * column, 0: none yet), extra_bytes = device memory of the per-column sweep buffers, launches_per_pass = dependent launches of
+ * one pass (those of one lsa_ndlu_solve) */
+int lsa_ndlu_multi_info(const lsa_ndlu *f, int32_t *width, int64_t *extra_bytes, int32_t *launches_per_pass);
 /* Inertia (numbers of negative, zero, positive eigenvalues) of a REAL SYMMETRIC C from its factorisation: what SLEPc's spectrum
  * slicing takes from the symmetric-indefinite factorisation behind EPS.setInterval / EPS_ALL (Solver/utils.py:248-254: the
  * number of eigenvalues of a definite pencil below sigma is the number of negative eigenvalues of A - sigma M).  Sum over the

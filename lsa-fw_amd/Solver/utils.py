@@ -1207,3 +1207,392 @@ def _permute(A: sp.csr_matrix, perm: np.ndarray) -> sp.csr_matrix:
         out = A[perm][:, perm].tocsr()
     out.sort_indices()
     return out
+
+
+# ---- iKSP: the kept linear solver of the reference (Solver/utils.py:331-419) ----------------------------------------------
+
+class _RawKspPC:
+    def __init__(self, owner: "iKSP"):
+        self._o = owner
+
+    def getType(self) -> str:
+        return self._o._pc_type.name.lower()
+
+
+class _RawLinearKSP:
+    """The ``PETSc.KSP`` getters callers poke through ``iKSP.raw`` (in the style of :class:`_RawKSP`)."""
+
+    def __init__(self, owner: "iKSP"):
+        self._o = owner
+
+    def getPC(self) -> _RawKspPC:
+        return _RawKspPC(self._o)
+
+    def getType(self) -> str:
+        return self._o.get_type()
+
+    def getIterationNumber(self) -> int:
+        return self._o.get_iteration_number()
+
+    def getResidualNorm(self) -> float:
+        return self._o.get_residual_norm()
+
+
+_DIRECT_PCS = (PreconditionerType.LU, PreconditionerType.CHOLESKY)
+_GMRES_PCS = (PreconditionerType.NONE, PreconditionerType.ILU, PreconditionerType.ICC)
+
+
+class iKSP:
+    """Linear solver that KEEPS its factorisation between solves (reference: ``Solver/utils.py:331-419``, the wrapper over
+    ``PETSc.KSP`` that ``Solver/nonlinear.py:48`` builds once per Newton loop and ``Solver/linear.py`` caches per type).
+
+    Same method and parameter names; the arithmetic runs in ``liblsa_hip.so``:
+
+    * ``PREONLY`` (or ``GMRES``) with ``LU`` / ``CHOLESKY``: the exact nested-dissection LU as the eigen path prepares it
+      (``lsa_hip.nd_order`` on the host, the matrix uploaded in elimination order, ``NdLu(tree=...)``).  Ordering, analysis and
+      factorisation happen at the first solve and are kept; ``set_operators`` with a matrix of the same pattern and value
+      type only refactors.  Every solve is verified with the device SpMV, ``||b - A x|| <= rtol ||b||``, takes one step of
+      iterative refinement if it misses, and raises ``RuntimeError`` if it still does.
+    * ``GMRES`` with ``NONE`` / ``ILU`` / ``ICC``: ``lsa_hip.gmres`` as ``LinearSolver.solve`` runs it, the ILU(k) factors kept.
+
+    Construction and the setters do no device work (the context opens at the first solve), so the class can be configured on
+    a machine without a GPU; there is no CPU fallback for ``solve``.  Extensions beyond the reference's class, marked in
+    their docstrings: :meth:`solve_many`, :attr:`stats`, the keyword ``device``, the attributes ``ilu_levels`` / ``restart``."""
+
+    ilu_levels = 2    # level of fill of the ILU(k) preconditioner (extension; LinearSolver.solve's default)
+    restart = 1000    # GMRES restart length (extension; LinearSolver.solve's default)
+
+    def __init__(self, A=None, comm=None, *, device: int = 0) -> None:
+        self._comm, self._device = comm, int(device)
+        self._ksp_type, self._pc_type = KSPType.GMRES, PreconditionerType.ILU  # PETSc's defaults
+        self._tol, self._max_it, self._rtol = 1e-12, 1000, 1e-8
+        self._guess_nonzero = False
+        self._mat: sp.csr_matrix | None = None
+        self._dirty = None         # None: the device state matches the operator; "values": same pattern; "pattern": rebuild
+        self._dev: dict | None = None
+        self._solution: np.ndarray | None = None
+        self._res_norm, self._its = 0.0, 0
+        self._stats = {"analyses": 0, "factorisations": 0, "refactorisations": 0, "solves": 0, "columns": 0, "multi_width": 0}
+        if A is not None:
+            self.set_operators(A)
+
+    @property
+    def raw(self) -> _RawLinearKSP:
+        return _RawLinearKSP(self)
+
+    @property
+    def stats(self) -> dict:
+        """Extension: counters since construction (``analyses``, ``factorisations``, ``refactorisations``, ``solves``,
+        ``columns``) and ``multi_width``, the widest pass of the last :meth:`solve_many`; ``factorisations`` starts again
+        from the state a :meth:`reset` or a new pattern rebuilds."""
+        return dict(self._stats)
+
+    def set_operators(self, A, P=None) -> None:
+        if P is not None and P is not A:
+            raise NotImplementedError("iKSP: a preconditioning matrix P other than A is not supported")
+        mat = sp.csr_matrix((A if isinstance(A, iPETScMatrix) else iPETScMatrix.from_matrix(A)).as_scipy_array())
+        if mat.shape[0] != mat.shape[1]:
+            raise ValueError(f"Operator A must be square, got shape {mat.shape}")
+        if not mat.has_sorted_indices:
+            mat = mat.copy()
+            mat.sort_indices()
+        old = self._mat
+        same = (old is not None and old.shape == mat.shape and np.iscomplexobj(old.data) == np.iscomplexobj(mat.data)
+                and np.array_equal(old.indptr, mat.indptr) and np.array_equal(old.indices, mat.indices))
+        self._mat = mat
+        if self._dev is not None:
+            self._dirty = "values" if (same and self._dirty != "pattern") else "pattern"
+
+    def set_type(self, ksp_type: KSPType) -> None:
+        if ksp_type not in (KSPType.PREONLY, KSPType.GMRES):
+            raise ValueError("KSP type not supported.")
+        if ksp_type is not self._ksp_type:
+            self._ksp_type = ksp_type
+            self._invalidate()
+
+    def get_type(self) -> str:
+        return self._ksp_type.to_petsc()
+
+    def set_tolerances(self, tol: float = 1e-12, max_it: int = 1000, rtol: float = 1e-8) -> None:
+        """``tol`` (absolute) is kept for signature compatibility; convergence is judged on ``rtol`` (as ``LinearSolver.solve``)."""
+        self._tol, self._max_it, self._rtol = float(tol), int(max_it), float(rtol)
+
+    def set_preconditioner(self, pc_type: PreconditionerType) -> None:
+        pc_type = PreconditionerType(pc_type)
+        if pc_type not in _DIRECT_PCS + _GMRES_PCS:
+            raise ValueError(f"Preconditioner {pc_type.name} not supported: use LU, CHOLESKY, ILU, ICC or NONE")
+        if pc_type is not self._pc_type:
+            self._pc_type = pc_type
+            self._invalidate()
+
+    def set_initial_guess_nonzero(self, flag: bool) -> None:
+        """``True``: the ``x`` handed to :meth:`solve` is GMRES's starting vector (``use_x0``).  The direct path ignores it."""
+        self._guess_nonzero = bool(flag)
+
+    def set_from_options(self, prefix: str | None = None) -> None:
+        """No-op: there is no options database."""
+
+    def _invalidate(self) -> None:
+        if self._dev is not None:
+            self._dirty = "pattern"
+
+    def _direct(self) -> bool:
+        if self._ksp_type is KSPType.PREONLY and self._pc_type not in _DIRECT_PCS:
+            raise ValueError("KSPType.PREONLY needs PreconditionerType.LU or CHOLESKY")
+        return self._pc_type in _DIRECT_PCS
+
+    def _rhs(self, b, ncols=None) -> np.ndarray:
+        if self._mat is None:
+            raise ValueError("iKSP: set_operators has not been called")
+        rhs = b.as_array() if hasattr(b, "as_array") else np.asarray(b)
+        n = self._mat.shape[0]
+        if ncols is None:
+            if rhs.shape != (n,):
+                raise ValueError(f"Right-hand side has shape {rhs.shape}, expected ({n},)")
+        elif rhs.ndim != 2 or rhs.shape[0] != n or rhs.shape[1] < 1:
+            raise ValueError(f"Right-hand sides have shape {rhs.shape}, expected ({n}, k) with k >= 1")
+        return rhs
+
+    # -- device state ----------------------------------------------------------------------------------------------------
+    def _release(self) -> None:
+        if self._dev is not None:
+            ctx = self._dev["ctx"]
+            self._dev.clear()
+            self._dev = None
+            import gc
+
+            gc.collect()
+            ctx.close()
+        self._dirty = None
+
+    def reset(self) -> None:
+        """Free the device state (context, factors, vectors); the next solve rebuilds it."""
+        self._release()
+        self._stats["factorisations"] = 0
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _build_direct(self, lsa_hip, dev: dict) -> None:
+        mat, n, ctx = self._mat, self._mat.shape[0], dev["ctx"]
+        tree = None
+        if n > 8:  # (the eigen path's rule: zero-diagonal unknowns as constraints on 3D-like patterns)
+            zero_diag = None
+            if mat.nnz > 60 * n:
+                zd = mat.diagonal() == 0
+                zero_diag = zd if zd.any() else None
+            o = lsa_hip.nd_order(mat, 0, constraint=zero_diag)
+            dev["perm"], tree = o["perm"], {"first": o["first"], "size": o["size"], "parent": o["parent"]}
+        else:
+            dev["perm"] = np.arange(n)
+        dev["dA"] = lsa_hip.CsrMatrix.from_scipy(ctx, _permute(mat, dev["perm"]))
+        self._stats["analyses"] += 1
+        dev["lu"] = lsa_hip.NdLu(ctx, dev["dA"], 0, tree=tree)
+        self._stats["factorisations"] += 1
+        dev["kind"] = "lu"
+
+    def _build_gmres(self, lsa_hip, dev: dict, pc: bool) -> None:
+        mat, n, ctx = self._mat, self._mat.shape[0], dev["ctx"]
+        dev["perm"] = pivot_safe_rcm(mat) if (pc and n > 8) else np.arange(n)
+        dev["dA"] = lsa_hip.CsrMatrix.from_scipy(ctx, _permute(mat, dev["perm"]))
+        dev["ilu"] = lsa_hip.Ilu(ctx, dev["dA"], levels=self.ilu_levels) if pc else None
+        if pc:
+            self._stats["factorisations"] += 1
+        dev["kind"] = "gmres"
+
+    def _ensure(self) -> dict:
+        import lsa_hip
+
+        direct = self._direct()
+        if self._dev is not None and self._dirty == "values" and self._dev["kind"] == "lu" and direct:
+            dev = self._dev
+            dA = lsa_hip.CsrMatrix.from_scipy(dev["ctx"], _permute(self._mat, dev["perm"]))
+            dev["lu"].refactor(dA)
+            dev["dA"] = dA
+            self._stats["refactorisations"] += 1
+            self._dirty = None
+        elif self._dev is not None and self._dirty == "values" and self._dev["kind"] == "gmres" and not direct and not self._dev.get("oom"):
+            # new values on the kept pattern: the ordering stays, the matrix is uploaded again and ILU(k) factored again on it
+            dev = self._dev
+            dev["dA"] = lsa_hip.CsrMatrix.from_scipy(dev["ctx"], _permute(self._mat, dev["perm"]))
+            if dev["ilu"] is not None:
+                dev["ilu"] = None
+                dev["ilu"] = lsa_hip.Ilu(dev["ctx"], dev["dA"], levels=self.ilu_levels)
+                self._stats["refactorisations"] += 1
+            self._dirty = None
+        elif self._dev is None or self._dirty is not None:
+            self._release()
+            self._stats["factorisations"] = 0
+            dev = {"ctx": lsa_hip.Context(self._device), "vec": {}}
+            self._dev = dev
+            try:
+                if direct:
+                    try:
+                        self._build_direct(lsa_hip, dev)
+                    except lsa_hip.LsaError as exc:
+                        if exc.status != lsa_hip.LSA_ERR_OOM:  # only running out of device memory is answered by a leaner method
+                            raise
+                        logger.warning("exact LU does not fit the device memory (%s); using ILU(%d)-GMRES", exc, self.ilu_levels)
+                        for k in ("lu", "dA"):
+                            dev.pop(k, None)
+                        self._build_gmres(lsa_hip, dev, True)
+                        dev["oom"] = True
+                else:
+                    self._build_gmres(lsa_hip, dev, self._pc_type is not PreconditionerType.NONE)
+            except Exception:
+                self._release()
+                raise
+        return self._dev
+
+    def _vector(self, dev: dict, name: str, length: int, dtype):
+        import lsa_hip
+
+        key = (name, int(length), np.dtype(dtype).str)
+        if key not in dev["vec"]:
+            for old in [k for k in dev["vec"] if k[0] == name]:
+                del dev["vec"][old]
+            dev["vec"][key] = lsa_hip.DeviceVector(dev["ctx"], length, dtype)
+        return dev["vec"][key]
+
+    def _vdt(self, rhs: np.ndarray):
+        return np.complex128 if (np.iscomplexobj(self._mat.data) or np.iscomplexobj(rhs)) else np.float64
+
+    def _residual(self, dev: dict, bp: np.ndarray, xp: np.ndarray, adjoint: bool = False) -> np.ndarray:
+        """b - A x (or b - A^H x) in the device order, the product by the device SpMV."""
+        dx = self._vector(dev, "rx", bp.shape[0], bp.dtype)
+        dy = self._vector(dev, "ry", bp.shape[0], bp.dtype)
+        dx.upload(xp)
+        if adjoint:
+            dev["dA"].rmatvec(dx, dy, conj=True)
+        else:
+            dev["dA"].matvec(dx, dy)
+        return bp - dy.numpy()
+
+    def _direct_columns(self, dev: dict, Bp: np.ndarray, adjoint: bool) -> np.ndarray:
+        """Columns of Bp (n x k, device order, Fortran layout) through the kept LU in one block solve, each verified and, if
+        needed, refined once."""
+        n, k = Bp.shape
+        lu = dev["lu"]
+        dB = self._vector(dev, "B", n * k, Bp.dtype)
+        dX = self._vector(dev, "X", n * k, Bp.dtype)
+
+        def block_solve(R: np.ndarray) -> np.ndarray:
+            kk = R.shape[1]
+            dB.upload(np.concatenate([R.reshape(-1, order="F"), np.zeros(n * (k - kk), dtype=R.dtype)]))
+            if k == 1 and not adjoint:
+                lu.solve(dB, dX)
+            else:  # (the block vectors are n k long: one column of them is still a block solve, with the bits of lu.solve)
+                lu.solve_multi(dB, dX, kk, trans="H" if adjoint else "N")
+            return dX.numpy()[: n * kk].reshape((n, kk), order="F")
+
+        def residuals(cols) -> np.ndarray:
+            return np.stack([self._residual(dev, Bp[:, q], Xp[:, q], adjoint) for q in cols], axis=1)
+
+        Xp = block_solve(Bp)
+        if k > 1 or adjoint:
+            self._stats["multi_width"] = lu.multi_info()["width"]
+        self._its = 1
+        bn = np.linalg.norm(Bp, axis=0)
+        res = residuals(range(k))
+        rn = np.linalg.norm(res, axis=0)
+        bad = np.flatnonzero(~(rn <= self._rtol * bn))
+        if bad.size:  # the columns that missed, and only they (a column's bits do not depend on its neighbours)
+            Xp[:, bad] += block_solve(np.asfortranarray(res[:, bad]))
+            self._its = 2
+            rn[bad] = np.linalg.norm(residuals(bad), axis=0)
+            bad = np.flatnonzero(~(rn <= self._rtol * bn))
+            if bad.size:
+                q = int(bad[0])
+                raise RuntimeError(f"iKSP: the direct solve of column {q} missed rtol after one refinement step: "
+                                   f"||b - A x|| / ||b|| = {rn[q] / max(bn[q], 1e-300):.3e} > {self._rtol:.1e}")
+        self._res_norm = float(rn.max())
+        return Xp
+
+    def _gmres_column(self, dev: dict, bp: np.ndarray, x0p: np.ndarray | None) -> np.ndarray:
+        import lsa_hip
+
+        n = bp.shape[0]
+        db = self._vector(dev, "b", n, bp.dtype)
+        dx = self._vector(dev, "x", n, bp.dtype)
+        db.upload(bp)
+        if x0p is not None:
+            dx.upload(x0p.astype(bp.dtype))
+        if dev.get("oom"):
+            rtol, restart, maxit = min(self._rtol, 1e-12), self.restart, max(self._max_it, 4000)
+        else:
+            rtol, restart, maxit = self._rtol, min(self.restart, self._max_it), self._max_it
+        its, rel = lsa_hip.gmres(dev["ctx"], dev["dA"], dev["ilu"], db, dx, rtol=rtol, restart=restart, maxit=maxit, use_x0=x0p is not None)
+        self._its = int(its)
+        self._res_norm = float(rel) * float(np.linalg.norm(bp))
+        return dx.numpy()
+
+    # -- solves ----------------------------------------------------------------------------------------------------------
+    def solve(self, b, x=None):
+        rhs = self._rhs(b)
+        dev = self._ensure()
+        perm, vdt = dev["perm"], self._vdt(rhs)
+        bp = np.ascontiguousarray(rhs[perm], dtype=vdt)
+        if dev["kind"] == "lu":
+            xp = self._direct_columns(dev, np.asfortranarray(bp.reshape(-1, 1)), False)[:, 0]
+        else:
+            guess = None
+            if self._guess_nonzero and x is not None:
+                guess = np.asarray(x.raw if hasattr(x, "raw") else x)[perm]
+            xp = self._gmres_column(dev, bp, guess)
+        out = np.empty(rhs.shape[0], dtype=vdt)
+        out[perm] = xp
+        self._solution = out
+        self._stats["solves"] += 1
+        self._stats["columns"] += 1
+        if x is None:
+            return iPETScVector(out)
+        if isinstance(x, iPETScVector):
+            x._a = out.copy()
+        else:
+            np.copyto(np.asarray(x), out, casting="same_kind")  # (TypeError for a complex solution into a real array)
+        return x
+
+    def solve_many(self, B, adjoint: bool = False) -> np.ndarray:
+        """Extension: ``A X = B`` (``adjoint``: ``A^H X = B``, on the same factors) for an ``(n, k)`` array of right-hand
+        sides; returns the ``(n, k)`` solutions.  On the LU path all columns go through ONE ``NdLu.solve_multi`` call (the
+        sweeps read every factor scalar once per pass of up to 8 real or 4 complex columns) with the verification of :meth:`solve` per column,
+        each column bit-identical to :meth:`solve`; on the GMRES path the columns are solved one after another and
+        ``adjoint`` is not available."""
+        rhs = self._rhs(B, ncols=True)
+        dev = self._ensure()
+        perm, vdt = dev["perm"], self._vdt(rhs)
+        k = rhs.shape[1]
+        Bp = np.asfortranarray(rhs[perm, :], dtype=vdt)
+        if dev["kind"] == "lu":
+            Xp = self._direct_columns(dev, Bp, bool(adjoint))
+        else:
+            if adjoint:
+                raise NotImplementedError("iKSP.solve_many(adjoint=True) needs the LU path (PreconditionerType.LU / CHOLESKY)")
+            cols, its, worst = [], 0, 0.0
+            for q in range(k):
+                cols.append(self._gmres_column(dev, np.ascontiguousarray(Bp[:, q]), None))
+                its, worst = its + self._its, max(worst, self._res_norm)
+            self._its, self._res_norm = its, worst
+            Xp = np.stack(cols, axis=1)
+        out = np.empty((rhs.shape[0], k), dtype=vdt)
+        out[perm, :] = Xp
+        self._solution = out[:, -1].copy()
+        self._stats["solves"] += 1
+        self._stats["columns"] += k
+        return out
+
+    def get_solution(self):
+        if self._solution is None:
+            raise RuntimeError("iKSP: no solve has been made")
+        return iPETScVector(self._solution)
+
+    def get_residual_norm(self) -> float:
+        """``||b - A x||`` of the last solve: recomputed with the device SpMV on the LU path, GMRES's estimate otherwise."""
+        return float(self._res_norm)
+
+    def get_iteration_number(self) -> int:
+        """LU path: 1, or 2 after a refinement step; GMRES path: the iterations of the last solve."""
+        return int(self._its)

@@ -34,6 +34,7 @@ namespace {
 
 void nd_free(lsa_ndlu* f) {
     if (!f) return;
+    ndlu_multi_free(f);
     for (void* p : {f->d_top, (void*)f->d_top_icmap, (void*)f->d_top_jobs, (void*)f->d_top_tiles})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)f->d_lnodes_bwd, (void*)f->d_dist_nodes, (void*)f->d_child_ptr, (void*)f->d_child_idx, f->d_xstage, f->d_xg, (void*)f->d_tgoff, f->d_tg})
@@ -865,6 +866,74 @@ int lsa_ndlu_solve_time(lsa_ctx* ctx, lsa_ndlu* f, const lsa_vec* b, lsa_vec* x,
     float ms = 0.f;
     LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     *avg_ms = (double)ms / iters;
+    return LSA_OK;
+}
+
+// shape, dtype and overlap rules of a block solve; `who` names the entry in the message
+static int nd_multi_check(lsa_ctx* ctx, const char* who, const lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, const lsa_vec* X,
+                          int64_t ldx) {
+    if (!ctx || !f || !B || !X) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument", who);
+    const int64_t n = f->S.n;
+    if (trans < 0 || trans > 2) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: trans = %d is none of 0 (N), 1 (T), 2 (H)", who, trans);
+    if (nrhs < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: nrhs = %d, need at least one column", who, nrhs);
+    if (ldb < n || ldx < n) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: leading dimensions %lld / %lld below n = %lld", who, (long long)ldb, (long long)ldx, (long long)n);
+    if (B->dtype != X->dtype) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: B and X differ in dtype", who);
+    if (f->dtype == LSA_C128 && B->dtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: complex factors need complex vectors", who);
+    const int64_t need_b = ldb * (int64_t)(nrhs - 1) + n, need_x = ldx * (int64_t)(nrhs - 1) + n;
+    if (B->n < need_b || X->n < need_x)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "%s: a block of %d columns needs %lld / %lld entries, B and X hold %lld / %lld", who, nrhs, (long long)need_b,
+                             (long long)need_x, (long long)B->n, (long long)X->n);
+    if (!(B->d == X->d && ldb == ldx)) {  // in place is the one overlap a solve can honour
+        const char *b0 = (const char*)B->d, *x0 = (const char*)X->d;
+        const size_t es = esize(B->dtype);
+        if (b0 < x0 + (size_t)need_x * es && x0 < b0 + (size_t)need_b * es) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: B and X overlap (in place needs B == X and ldb == ldx)", who);
+    }
+    return LSA_OK;
+}
+
+// the columns of a checked block solve, queued on the stream
+static int nd_multi_run(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx) {
+    const size_t es = esize(B->dtype);
+    if (trans == 0 && nrhs > 1 && f->S.nranks == 1 && !f->S.has_dist) return ndlu_solve_multi_dev(ctx, f, B->dtype, nrhs, B->d, ldb, X->d, ldx);
+    // one column, a forest cut over ranks, the transposed systems: the existing sweeps, column by column
+    if (nrhs > 1) f->multi_width = 1;
+    for (int32_t q = 0; q < nrhs; ++q) {
+        const void* b = (const char*)B->d + (size_t)q * (size_t)ldb * es;
+        void* x = (char*)X->d + (size_t)q * (size_t)ldx * es;
+        if (trans == 0) LSA_CHECK(ndlu_solve_dev(ctx, f, B->dtype, b, x));
+        else LSA_CHECK(ndlu_solve_adjoint_dev(ctx, f, trans == 2, B->dtype, b, x));
+    }
+    return LSA_OK;
+}
+
+int lsa_ndlu_solve_multi(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx) {
+    LSA_CHECK(nd_multi_check(ctx, "lsa_ndlu_solve_multi", f, trans, nrhs, B, ldb, X, ldx));
+    LSA_CHECK(nd_multi_run(ctx, f, trans, nrhs, B, ldb, X, ldx));
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return LSA_OK;
+}
+
+int lsa_ndlu_solve_multi_time(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx, int iters,
+                              double* avg_ms) {
+    if (!avg_ms || iters < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_time: bad argument");
+    LSA_CHECK(nd_multi_check(ctx, "lsa_ndlu_solve_multi_time", f, trans, nrhs, B, ldb, X, ldx));
+    if (B->d == X->d) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_time: repeated solves need B and X apart");
+    LSA_CHECK(nd_multi_run(ctx, f, trans, nrhs, B, ldb, X, ldx));  // (the first call makes the per-column buffers)
+    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    for (int i = 0; i < iters; ++i) LSA_CHECK(nd_multi_run(ctx, f, trans, nrhs, B, ldb, X, ldx));
+    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0.f;
+    LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    *avg_ms = (double)ms / iters;
+    return LSA_OK;
+}
+
+int lsa_ndlu_multi_info(const lsa_ndlu* f, int32_t* width, int64_t* extra_bytes, int32_t* launches_per_pass) {
+    if (!f) return LSA_ERR_ARG;
+    if (width) *width = f->multi_width;
+    if (extra_bytes) *extra_bytes = f->multi_bytes;
+    if (launches_per_pass) *launches_per_pass = f->solve_launches;
     return LSA_OK;
 }
 

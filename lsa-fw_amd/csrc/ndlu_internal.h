@@ -21,6 +21,8 @@ constexpr int kNB = 32;      // pivot columns per block of the Gauss-Jordan inve
 constexpr int kSB = 128;     // ... per super-block of the tournament path (nd_gj_update_kernel)
 constexpr int kTRmin = 256;  // tournament pivoting, smallest first-round chunk: sizes the candidate buffers
 constexpr int kNdBatchMax = 16;  // most problems of one batched solve (lsa_ndlu_solve_batch): the capacity of NdSweepPtrs there
+constexpr int kMCH = 256;        // vector entries per column staged in LDS per pass of a multi-column solve tile (ndlu_multi.hip)
+constexpr int kNdMultiMax = 8;   // most columns of one pass of lsa_ndlu_solve_multi (real vectors; complex ones: 4 -- nd_multi_cap): 16 KB of LDS
 
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 inline size_t esize(int dtype) { return dtype == LSA_C128 ? 16 : 8; }
@@ -181,6 +183,16 @@ struct lsa_ndlu {
     int32_t top_tiles[2] = {0, 0};
     int64_t top_replaced_entries = 0;          // factor scalars the sweeps no longer read
     int acc_vbytes = 0;  // scalar size of the vectors the slot rows were last used with (their never-written entries must read zero)
+    // lsa_ndlu_solve_multi: the sweep buffers of the columns of a pass beyond the first (which uses the buffers above), made by the
+    // first multi-column solve, as many as fitted; what the last such solve used (lsa_ndlu_multi_info)
+    struct MultiColumn {
+        void *ubuf = nullptr, *xb = nullptr, *acc = nullptr, *tmp = nullptr;
+        int acc_vbytes = 0;
+    };
+    std::vector<MultiColumn> multi;
+    bool multi_full = false;     // an allocation failed: no further columns are tried
+    int64_t multi_bytes = 0;
+    int32_t multi_width = 0;     // widest pass of the last multi-column solve (1: column by column; 0: none yet)
 };
 
 template <typename U>
@@ -198,3 +210,7 @@ int ndlu_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C);
 // such a b_z is replaced in the caller's array by the problem's own copy of it)
 bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g);
 int ndlu_solve_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, const void** b, void* const* x);
+// ndlu_multi.hip: X[:, q] = C^-1 B[:, q], q < nrhs, on device pointers (column q at q * ld scalars; B == X with ldb == ldx allowed),
+// in passes of up to kNdMultiMax (complex vectors: 4) columns that share every factor load; not synchronised.  One rank, no distributed node.
+int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx);
+void ndlu_multi_free(lsa_ndlu* f);

@@ -1,0 +1,458 @@
+// Nested-dissection multifrontal LU, solves with a block of right-hand sides on ONE factorisation (lsa_ndlu_solve_multi): the
+// sweeps of ndlu_sweeps.hip with R columns carried through every launch.  A workgroup owns the tile of rows of the packed L_t /
+// U_t / T it owns there, stages the R vectors' chunks side by side in LDS, loads every factor scalar ONCE and accumulates R
+// pairs of row sums from it.  Per column nothing else changes: the lane partition (LPR per level), each lane's ascending
+// sequence of multiply-adds, the sub-wave sum and the order of the children's contributions are those of the solo kernels, so
+// column q holds exactly the bits lsa_ndlu_solve gives for it.  (A lane's sequence sl, sl + LPR, ... runs on across chunks, so
+// the chunk -- kMCH entries per column, a multiple of 256 -- is free: four complex or eight real columns of kMCH = 256 are 16 KB of LDS.)
+// Columns beyond the first have sweep buffers of their own (lsa_ndlu::multi), made by the first such solve.
+#include "ndlu_sweep_parts.h"
+
+namespace {
+
+// what a multi-column launch gets: one factor set, R sets of vectors and sweep buffers (by value in the kernel arguments; the
+// column index is a compile-time constant wherever it is used)
+template <int R>
+struct NdMultiPtrs {
+    const void *lfac, *ufac, *top;
+    const void* rhs[R];
+    void* x[R];
+    void* ubuf[R];
+    void* acc[R];
+    void* xb[R];
+};
+
+// acc0[q] += Fa[0:cn] . vs_q, acc1[q] += Fb[0:cn] . vs_q for the R staged columns (vs_q = vs + q * kMCH): the loads and the order
+// of two_row_dot, each factor scalar used R times
+template <int LPR, int R, typename MT, typename VT>
+__device__ __forceinline__ void two_row_dot_multi(const MT* __restrict__ Fa, const MT* __restrict__ Fb, const VT* vs, int32_t cn, int sl, VT (&acc0)[R],
+                                                  VT (&acc1)[R]) {
+    int32_t k = sl;
+    for (; k + 3 * LPR < cn; k += 4 * LPR) {
+        const MT a0 = Fa[k], a1 = Fa[k + LPR], a2 = Fa[k + 2 * LPR], a3 = Fa[k + 3 * LPR];
+        const MT b0 = Fb[k], b1 = Fb[k + LPR], b2 = Fb[k + 2 * LPR], b3 = Fb[k + 3 * LPR];
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const VT* v = vs + q * kMCH;
+            const VT v0 = v[k], v1 = v[k + LPR], v2 = v[k + 2 * LPR], v3 = v[k + 3 * LPR];
+            fma_acc(acc0[q], a0, v0);
+            fma_acc(acc1[q], b0, v0);
+            fma_acc(acc0[q], a1, v1);
+            fma_acc(acc1[q], b1, v1);
+            fma_acc(acc0[q], a2, v2);
+            fma_acc(acc1[q], b2, v2);
+            fma_acc(acc0[q], a3, v3);
+            fma_acc(acc1[q], b3, v3);
+        }
+    }
+    for (; k < cn; k += LPR) {
+        const MT a0 = Fa[k], b0 = Fb[k];
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const VT v0 = vs[q * kMCH + k];
+            fma_acc(acc0[q], a0, v0);
+            fma_acc(acc1[q], b0, v0);
+        }
+    }
+}
+
+template <int LPR, int R, typename MT, typename VT>
+__device__ __forceinline__ void two_row_dot_prefetched_multi(const MT* __restrict__ Fa, const MT* __restrict__ Fb, const VT* vs, int32_t cn, int sl,
+                                                             VT (&acc0)[R], VT (&acc1)[R], const MT (&pa)[4], const MT (&pb)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int32_t k = sl + j * LPR;
+        if (k < cn) {
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const VT v0 = vs[q * kMCH + k];
+                fma_acc(acc0[q], pa[j], v0);
+                fma_acc(acc1[q], pb[j], v0);
+            }
+        }
+    }
+    if (cn > 4 * LPR) two_row_dot_multi<LPR, R>(Fa + 4 * LPR, Fb + 4 * LPR, vs + 4 * LPR, cn - 4 * LPR, sl, acc0, acc1);
+}
+
+// upward sweep, one tree level, R columns: workgroup (x = node of the level, y = tile of 512 / LPR rows of its packed L block);
+// nd_fwd_tile of ndlu_sweeps.hip per column (no distributed node reaches this form)
+template <typename MT, typename VT, int LPR, bool ORDERED, int R>
+__global__ __launch_bounds__(256) void nd_fwd_multi_kernel(const NdSweepNode* __restrict__ lnodes, const int32_t* __restrict__ idx,
+                                                           const int32_t* __restrict__ gell, const int32_t* __restrict__ cmap, NdMultiPtrs<R> p) {
+    __shared__ VT vs[R * kMCH];
+    const NdSweepNode nd = lnodes[blockIdx.x];
+    const int32_t r0 = (int32_t)blockIdx.y * (512 / LPR);
+    if (r0 >= nd.orows + nd.brow) return;
+    const int32_t m = nd.m, f = nd.f;
+    const int32_t mr = nd.orows, floc = mr + nd.brow;
+    const int32_t* ix = idx + nd.idx_off;
+    const int32_t* ge = gell + nd.ge_off;
+    const MT* L = (const MT*)p.lfac + nd.lfac_off;
+    const int tid = threadIdx.x, sw = tid / LPR, sl = tid % LPR;
+    const int32_t ra = r0 + sw, rb = ra + 256 / LPR;
+    const MT* La = L + (size_t)min(ra, floc - 1) * m;
+    const MT* Lb = L + (size_t)min(rb, floc - 1) * m;
+    VT acc0[R], acc1[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q) acc0[q] = acc1[q] = scalar_traits<VT>::zero();
+    // everything that depends only on the node record is requested first: the head of the rows, where the update entries go
+    MT pa[4], pb[4];
+    row_pair_prefetch<LPR>(La, Lb, min(kMCH, m), sl, pa, pb);
+    const bool push = nd.acc_off >= 0;
+    const int64_t slot0 = push ? nd.acc_off : 0;
+    int32_t ca = 0, cb = 0;
+    if (sl == 0 && nd.pacc_off >= 0) {
+        if (ra >= mr && ra < floc) ca = cmap[nd.cmap_off + ra - mr];
+        if (rb >= mr && rb < floc) cb = cmap[nd.cmap_off + rb - mr];
+    }
+    // ... then what the children added to the update entries these rows produce
+    VT ua[R], ub[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        ua[q] = ub[q] = scalar_traits<VT>::zero();
+        if (sl == 0) {
+            const VT* slots = (const VT*)p.acc[q] + slot0;
+            const VT* ubuf = (const VT*)p.ubuf[q];
+            if (ra >= mr && ra < floc) {
+                const int32_t jg = m + nd.brow0 + ra - mr;
+                ua[q] = push ? slot_sum(slots, nd.nchild, f, jg, ua[q]) : gather_updates(ge, nd.nchild, f, jg, ubuf, ua[q]);
+            }
+            if (rb >= mr && rb < floc) {
+                const int32_t jg = m + nd.brow0 + rb - mr;
+                ub[q] = push ? slot_sum(slots, nd.nchild, f, jg, ub[q]) : gather_updates(ge, nd.nchild, f, jg, ubuf, ub[q]);
+            }
+        }
+    }
+    for (int32_t c0 = 0; c0 < m; c0 += kMCH) {
+        const int32_t cn = min(kMCH, m - c0);
+        if (tid < cn) {  // (kMCH = 256: one entry per thread and column)
+            const int32_t src = ORDERED ? nd.own0 + c0 + tid : ix[c0 + tid];
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const VT v = ((const VT*)p.rhs[q])[src];
+                vs[q * kMCH + tid] = push ? slot_sum((const VT*)p.acc[q] + slot0, nd.nchild, f, c0 + tid, v)
+                                          : gather_updates(ge, nd.nchild, f, c0 + tid, (const VT*)p.ubuf[q], v);
+            }
+        }
+        __syncthreads();
+        if (c0 == 0) two_row_dot_prefetched_multi<LPR, R>(La, Lb, vs, cn, sl, acc0, acc1, pa, pb);
+        else two_row_dot_multi<LPR, R>(La + c0, Lb + c0, vs, cn, sl, acc0, acc1);
+        __syncthreads();
+    }
+    const bool root_push = f == m && !(nd.flags & 1);
+    const int32_t xa = ra < mr ? (ORDERED ? nd.own0 + nd.orow0 + ra : ix[nd.orow0 + ra]) : 0;
+    const int32_t xc = rb < mr ? (ORDERED ? nd.own0 + nd.orow0 + rb : ix[nd.orow0 + rb]) : 0;
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        const VT s0 = lanes_sum<LPR>(acc0[q]), s1 = lanes_sum<LPR>(acc1[q]);
+        if (sl == 0) {
+            VT* x = (VT*)p.x[q];
+            VT* xb = (VT*)p.xb[q];
+            VT* acc = (VT*)p.acc[q];
+            VT* ubuf = (VT*)p.ubuf[q];
+            if (ra < mr) {
+                x[xa] = s0;
+                if (root_push) push_down(ge, nd.nchild, f, ra, xb, s0);
+            } else if (ra < floc) {
+                const VT u = s_add(ua[q], s0);
+                if (nd.pacc_off >= 0) acc[nd.pacc_off + ca] = u;
+                else ubuf[nd.u_off + (ra - mr)] = u;
+            }
+            if (rb < mr) {
+                x[xc] = s1;
+                if (root_push) push_down(ge, nd.nchild, f, rb, xb, s1);
+            } else if (rb < floc) {
+                const VT u = s_add(ub[q], s1);
+                if (nd.pacc_off >= 0) acc[nd.pacc_off + cb] = u;
+                else ubuf[nd.u_off + (rb - mr)] = u;
+            }
+        }
+    }
+}
+
+// downward sweep, one tree level, R columns: nd_bwd_tile per column
+template <typename MT, typename VT, int LPR, bool ORDERED, int R>
+__global__ __launch_bounds__(256) void nd_bwd_multi_kernel(const NdSweepNode* __restrict__ lnodes, const int32_t* __restrict__ idx,
+                                                           const int32_t* __restrict__ gell, NdMultiPtrs<R> p) {
+    constexpr int ROWS = 512 / LPR;
+    __shared__ VT vs[R * kMCH];
+    const NdSweepNode nd = lnodes[blockIdx.x];
+    const int32_t r0 = (int32_t)blockIdx.y * ROWS, ty = (int32_t)blockIdx.y;
+    if (r0 >= nd.m || nd.f == nd.m) return;
+    const int32_t m = nd.m, f = nd.f, b = f - m;
+    const int32_t* ix = idx + nd.idx_off;
+    const int32_t* ge = gell + nd.ge_off;
+    const MT* U = (const MT*)p.ufac + nd.ufac_off;
+    const int tid = threadIdx.x, sw = tid / LPR, sl = tid % LPR;
+    const int32_t ra = r0 + sw, rb = r0 + sw + 256 / LPR;
+    const MT* Ua = U + (size_t)min(ra, m - 1) * b;
+    const MT* Ub = U + (size_t)min(rb, m - 1) * b;
+    const int32_t ia = ORDERED ? nd.own0 + min(ra, m - 1) : ix[min(ra, m - 1)], ib = ORDERED ? nd.own0 + min(rb, m - 1) : ix[min(rb, m - 1)];
+    MT pa[4], pb[4];
+    row_pair_prefetch<LPR>(Ua, Ub, min(kMCH, b), sl, pa, pb);
+    // the rows' own entries are needed only at the end: issue their loads before the sweep over the boundary
+    VT xa[R], xc[R], acc0[R], acc1[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        const VT* x = (const VT*)p.x[q];
+        xa[q] = x[ia];
+        xc[q] = x[ib];
+        acc0[q] = acc1[q] = scalar_traits<VT>::zero();
+    }
+    for (int32_t c0 = 0; c0 < b; c0 += kMCH) {
+        const int32_t cn = min(kMCH, b - c0);
+        if (tid < cn) {
+#pragma unroll
+            for (int q = 0; q < R; ++q) vs[q * kMCH + tid] = ((const VT*)p.xb[q])[nd.u_off + c0 + tid];
+        }
+        __syncthreads();
+        if (c0 == 0) two_row_dot_prefetched_multi<LPR, R>(Ua, Ub, vs, cn, sl, acc0, acc1, pa, pb);
+        else two_row_dot_multi<LPR, R>(Ua + c0, Ub + c0, vs, cn, sl, acc0, acc1);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        const VT s0 = lanes_sum<LPR>(acc0[q]), s1 = lanes_sum<LPR>(acc1[q]);
+        if (sl == 0) {
+            VT* x = (VT*)p.x[q];
+            VT* xb = (VT*)p.xb[q];
+            if (ra < m) {
+                const VT v = s_sub(xa[q], s0);
+                x[ia] = v;
+                push_down(ge, nd.nchild, f, ra, xb, v);
+            }
+            if (rb < m) {
+                const VT v = s_sub(xc[q], s1);
+                x[ib] = v;
+                push_down(ge, nd.nchild, f, rb, xb, v);
+            }
+        }
+    }
+    if (nd.nchild > 0) {  // the boundary entries this node received, handed on to the children whose boundaries hold them
+        const int32_t ntile = (m + ROWS - 1) / ROWS;
+        const int64_t total = (int64_t)nd.nchild * b;
+        for (int64_t e = (int64_t)ty * 256 + tid; e < total; e += (int64_t)ntile * 256) {
+            const int32_t c = (int32_t)(e / b), j = (int32_t)(e - (int64_t)c * b);
+            const int32_t g = ge[(size_t)c * f + m + j];
+            if (g >= 0) {
+#pragma unroll
+                for (int q = 0; q < R; ++q) {
+                    VT* xb = (VT*)p.xb[q];
+                    xb[g] = xb[nd.u_off + j];
+                }
+            }
+        }
+    }
+}
+
+// the merged top, R columns: nd_top_tile per column (8 rows of T per workgroup, a wave per row pair)
+template <typename MT, typename VT, int R>
+__global__ __launch_bounds__(256) void nd_top_multi_kernel(NdTop tp, const int32_t* __restrict__ icmap, const int32_t* __restrict__ gell, NdMultiPtrs<R> p) {
+    constexpr int LPR = 64;
+    __shared__ VT vs[R * kMCH];
+    const int32_t r0 = (int32_t)blockIdx.x * 8;
+    const int32_t s = tp.s, K = tp.nchild;
+    const NdTopNode& Rt = tp.node[K];
+    const MT* top = (const MT*)p.top;
+    const int tid = threadIdx.x, sw = tid / LPR, sl = tid % LPR;
+    const int32_t ra = r0 + sw, rb = ra + 256 / LPR;
+    const MT* Ta = top + (size_t)min(ra, s - 1) * s;
+    const MT* Tb = top + (size_t)min(rb, s - 1) * s;
+    VT acc0[R], acc1[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q) acc0[q] = acc1[q] = scalar_traits<VT>::zero();
+    MT pa[4], pb[4];
+    row_pair_prefetch<LPR>(Ta, Tb, min(kMCH, s), sl, pa, pb);
+    for (int32_t c0 = 0; c0 < s; c0 += kMCH) {
+        const int32_t c1 = min(c0 + kMCH, s);
+        const int32_t j = c0 + tid;  // (kMCH = 256: one entry per thread and column)
+        if (j < c1) {
+            if (j >= Rt.off) {
+                const int32_t k = j - Rt.off;
+#pragma unroll
+                for (int q = 0; q < R; ++q) {
+                    const VT* acc = (const VT*)p.acc[q];
+                    VT z = ((const VT*)p.rhs[q])[Rt.own0 + k];
+                    for (int32_t c = 0; c < K; ++c) {
+                        const NdTopNode& nd = tp.node[c];
+                        const int32_t pp = icmap[(size_t)c * Rt.m + k];
+                        if (pp >= 0) z = s_add(z, slot_sum(acc + nd.acc_off, nd.nchild, nd.f, nd.m + pp, scalar_traits<VT>::zero()));
+                    }
+                    vs[q * kMCH + tid] = z;
+                }
+            } else {
+                for (int32_t c = 0; c < K; ++c) {
+                    const NdTopNode& nd = tp.node[c];
+                    if (j < nd.off || j >= nd.off + nd.m) continue;
+                    const int32_t r = j - nd.off;
+#pragma unroll
+                    for (int q = 0; q < R; ++q)
+                        vs[q * kMCH + tid] = slot_sum((const VT*)p.acc[q] + nd.acc_off, nd.nchild, nd.f, r, ((const VT*)p.rhs[q])[nd.own0 + r]);
+                }
+            }
+        }
+        __syncthreads();
+        if (c0 == 0) two_row_dot_prefetched_multi<LPR, R>(Ta, Tb, vs, c1 - c0, sl, acc0, acc1, pa, pb);
+        else two_row_dot_multi<LPR, R>(Ta + c0, Tb + c0, vs, c1 - c0, sl, acc0, acc1);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        const VT s0 = lanes_sum<LPR>(acc0[q]), s1 = lanes_sum<LPR>(acc1[q]);
+        if (sl == 0) {
+            if (ra < s) nd_top_store(tp, ra, s0, icmap, gell, (VT*)p.x[q], (VT*)p.xb[q]);
+            if (rb < s) nd_top_store(tp, rb, s1, icmap, gell, (VT*)p.x[q], (VT*)p.xb[q]);
+        }
+    }
+}
+
+// x_q = C^-1 b_q for the R columns of one pass: nd_sweep of ndlu_sweeps.hip for one rank and no distributed node, the same
+// grids, one launch per level and direction for all columns.  Column 0 runs on the factorisation's own sweep buffers, column
+// q > 0 on f->multi[q - 1].
+template <typename MT, typename VT, bool ORDERED, int R>
+int nd_sweep_multi(lsa_ctx* ctx, lsa_ndlu* f, const VT* const* b, VT* const* x) {
+    hipStream_t st = ctx->stream;
+    NdMultiPtrs<R> p;
+    p.lfac = f->d_lfac;
+    p.ufac = f->d_ufac;
+    p.top = f->d_top;
+    const size_t acc_bytes = (size_t)std::max<int64_t>(f->acc_entries, 1) * 16;
+    for (int q = 0; q < R; ++q) {
+        void* acc = q == 0 ? f->d_acc : f->multi[(size_t)q - 1].acc;
+        int& vbytes = q == 0 ? f->acc_vbytes : f->multi[(size_t)q - 1].acc_vbytes;
+        if (vbytes != (int)sizeof(VT)) {  // (the rule of nd_sweep, per copy of the slot rows)
+            LSA_HIP_CHECK(ctx, hipMemsetAsync(acc, 0, acc_bytes, st));
+            vbytes = (int)sizeof(VT);
+        }
+        p.rhs[q] = b[q];
+        p.x[q] = x[q];
+        p.acc[q] = acc;
+        p.ubuf[q] = q == 0 ? f->d_ubuf : f->multi[(size_t)q - 1].ubuf;
+        p.xb[q] = q == 0 ? f->d_xb : f->multi[(size_t)q - 1].xb;
+    }
+    const bool top = ORDERED && f->top.s > 0;
+    for (size_t li = 0; li < f->levels.size(); ++li) {
+        const NdLevel& L = f->levels[li];
+        if (top && (int32_t)li + 1 == f->top_level) continue;  // the root's children: inside the root's launch
+        if (top && (int32_t)li == f->top_level) {
+            hipLaunchKernelGGL((nd_top_multi_kernel<MT, VT, R>), dim3((f->top.s + 7) / 8), dim3(256), 0, st, f->top, f->d_top_icmap, f->d_gell, p);
+        } else if (L.fwd_tiles > 0) {
+            nd_with_lpr<true>(L.sweep_rows, [&](auto lpr) {
+                hipLaunchKernelGGL((nd_fwd_multi_kernel<MT, VT, decltype(lpr)::value, ORDERED, R>), dim3(L.node_count, L.fwd_tiles), dim3(256), 0, st,
+                                   f->d_lnodes + L.node_begin, f->d_idx, f->d_gell, f->d_cmap, p);
+            });
+        }
+    }
+    for (size_t l = f->levels.size(); l-- > 0;) {
+        const NdLevel& L = f->levels[l];
+        if (L.bwd_tiles > 0 && !(top && (int32_t)l + 1 == f->top_level)) {
+            nd_with_lpr<false>(L.sweep_rows, [&](auto lpr) {
+                hipLaunchKernelGGL((nd_bwd_multi_kernel<MT, VT, decltype(lpr)::value, ORDERED, R>), dim3(L.node_count, L.bwd_tiles), dim3(256), 0, st,
+                                   f->d_lnodes_bwd + L.node_begin, f->d_idx, f->d_gell, p);
+            });
+        }
+    }
+    LSA_HIP_CHECK(ctx, hipGetLastError());
+    return LSA_OK;
+}
+
+// sweep buffers for passes of `want` columns; returns how many columns a pass can have (1 + the extra sets that fitted).  An
+// allocation that fails narrows the passes of this and every later call; it is not an error.
+int32_t nd_multi_ensure(lsa_ctx* ctx, lsa_ndlu* f, int32_t want) {
+    const size_t ub = (size_t)std::max<int64_t>(f->S.u_off[(size_t)f->S.nt], 1) * 16;
+    const size_t ab = (size_t)std::max<int64_t>(f->acc_entries, 1) * 16;
+    const size_t tb = (size_t)std::max<int32_t>(f->S.n, 1) * 16;
+    while ((int32_t)f->multi.size() + 1 < want && !f->multi_full) {
+        lsa_ndlu::MultiColumn c;
+        const bool ok = hipMalloc(&c.ubuf, ub) == hipSuccess && hipMalloc(&c.xb, ub) == hipSuccess && hipMalloc(&c.acc, ab) == hipSuccess &&
+                        hipMalloc(&c.tmp, tb) == hipSuccess;
+        // as nd_setup_buffers leaves them; the slot rows are zeroed by their first use (acc_vbytes = 0 matches no vector scalar)
+        if (!ok || hipMemsetAsync(c.ubuf, 0, ub, ctx->stream) != hipSuccess || hipMemsetAsync(c.xb, 0, ub, ctx->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            for (void* q : {c.ubuf, c.xb, c.acc, c.tmp})
+                if (q) (void)hipFree(q);
+            f->multi_full = true;
+            break;
+        }
+        f->multi.push_back(c);
+        f->multi_bytes += (int64_t)(2 * ub + ab + tb);
+    }
+    return std::min<int32_t>(want, (int32_t)f->multi.size() + 1);
+}
+
+// The widest pass for vectors of vbytes-byte scalars, from the measurement (profiles/multi_rhs.json): every
+// width measured beat the solo loop per column, but eight complex columns (255 VGPRs, one wave per SIMD) took 560 us per column
+// at 500 k unknowns where four take 453 (the same within 3 % at 30 k), so complex vectors stop at four and the kernels of eight
+// complex columns are not built; eight real columns (as many bytes as four complex ones) are as fast as four or faster.
+// LSA_ND_MULTI_WIDTH lowers it (1, 2, 4, 8; for measurements).
+int32_t nd_multi_cap(size_t vbytes) {
+    static const int32_t env = [] {
+        const char* e = getenv("LSA_ND_MULTI_WIDTH");
+        return e && *e ? std::max(1, std::min(kNdMultiMax, atoi(e))) : kNdMultiMax;
+    }();
+    return std::min<int32_t>(env, vbytes == 16 ? 4 : kNdMultiMax);
+}
+
+// columns of the next pass when `left` are left and a pass may have `most`: 8, 4, 2, or 1 (a solo solve)
+int32_t nd_pass_width(int32_t left, int32_t most) {
+    const int32_t w = std::min(left, most);
+    return w >= 8 ? 8 : w >= 4 ? 4 : w >= 2 ? 2 : 1;
+}
+
+template <typename MT, typename VT>
+int nd_solve_multi(lsa_ctx* ctx, lsa_ndlu* f, int32_t nrhs, const VT* B, int64_t ldb, VT* X, int64_t ldx) {
+    // (buffers for the widest pass that will run: the first)
+    const int32_t avail = nd_multi_ensure(ctx, f, nd_pass_width(nrhs, nd_multi_cap(sizeof(VT))));
+    const size_t nbytes = (size_t)f->S.n * sizeof(VT);
+    f->multi_width = 1;
+    for (int32_t q0 = 0; q0 < nrhs;) {
+        const int32_t R = nd_pass_width(nrhs - q0, avail);  // a remainder runs in narrower passes
+        if (R == 1) {
+            LSA_CHECK(ndlu_solve_dev(ctx, f, scalar_traits<VT>::dtype, B + (int64_t)q0 * ldb, X + (int64_t)q0 * ldx));
+            q0 += 1;
+            continue;
+        }
+        const VT* b[kNdMultiMax];
+        VT* x[kNdMultiMax];
+        for (int32_t q = 0; q < R; ++q) {
+            b[q] = B + (int64_t)(q0 + q) * ldb;
+            x[q] = X + (int64_t)(q0 + q) * ldx;
+            if (b[q] == x[q]) {  // in place: the sweeps read a right-hand side after they began to write the solution
+                void* tmp = q == 0 ? f->d_tmp : f->multi[(size_t)q - 1].tmp;
+                LSA_HIP_CHECK(ctx, hipMemcpyAsync(tmp, b[q], nbytes, hipMemcpyDeviceToDevice, ctx->stream));
+                b[q] = (const VT*)tmp;
+            }
+        }
+        auto run = [&](auto width) {
+            constexpr int W = decltype(width)::value;
+            return f->ordered ? nd_sweep_multi<MT, VT, true, W>(ctx, f, b, x) : nd_sweep_multi<MT, VT, false, W>(ctx, f, b, x);
+        };
+        if constexpr (sizeof(VT) == 8) {
+            if (R == 8) LSA_CHECK(run(std::integral_constant<int, 8>{}));
+        }
+        if (R == 4) LSA_CHECK(run(std::integral_constant<int, 4>{}));
+        if (R == 2) LSA_CHECK(run(std::integral_constant<int, 2>{}));
+        f->multi_width = std::max(f->multi_width, R);
+        q0 += R;
+    }
+    return LSA_OK;
+}
+
+}  // namespace
+
+void ndlu_multi_free(lsa_ndlu* f) {
+    for (lsa_ndlu::MultiColumn& c : f->multi)
+        for (void* q : {c.ubuf, c.xb, c.acc, c.tmp})
+            if (q) (void)hipFree(q);
+    f->multi.clear();
+    f->multi_bytes = 0;
+}
+
+int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx) {
+    if (f->S.nranks > 1 || f->S.has_dist) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi: the multi-column sweeps need one rank and no distributed node");
+    if (f->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi: complex factors need complex vectors");
+    if (f->S.n == 0) return LSA_OK;
+    if (f->dtype == LSA_C128) return nd_solve_multi<cplx, cplx>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
+    if (vdtype == LSA_C128) return nd_solve_multi<double, cplx>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
+    return nd_solve_multi<double, double>(ctx, f, nrhs, (const double*)B, ldb, (double*)X, ldx);
+}

@@ -1,0 +1,183 @@
+// Nested-dissection multifrontal LU, the solves: the device pieces every sweep kernel is built from -- the sub-wave sum, the row-pair
+// dot product and its prefetch, the gathers and pushes between a node and its children, the stores of the merged top -- and the
+// choice of a level's tile form.  Shared by ndlu_sweeps.hip (one vector per factor set) and ndlu_multi.hip (R vectors on one).
+#pragma once
+#include "ndlu_internal.h"
+
+namespace {
+
+// sum over LPR consecutive lanes (4, 16 or 64), returned to every one of them.  DPP moves inside a row of 16 lanes (two 32-bit
+// halves per double), the four row sums of a wavefront through SGPRs: a ds_bpermute butterfly is a chain of ~100-cycle steps,
+// and the sweeps are chains of short kernels that end in exactly this reduction.  Fixed order: bitwise repeatable.
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov_f64(double v) {
+    const long long bits = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)bits & 0xFFFFFFFFull), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)bits >> 32), CTRL, 0xF, 0xF, false);
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+template <int LPR>
+__device__ __forceinline__ double lanes_sum(double v) {
+    static_assert(LPR == 4 || LPR == 16 || LPR == 64, "sub-wave width");
+    v += dpp_mov_f64<0xB1>(v);  // quad_perm [1,0,3,2]
+    v += dpp_mov_f64<0x4E>(v);  // quad_perm [2,3,0,1]: every lane of a quad holds the quad's sum
+    if constexpr (LPR >= 16) {
+        v += dpp_mov_f64<0x141>(v);  // row_half_mirror
+        v += dpp_mov_f64<0x140>(v);  // row_mirror: every lane of a row of 16 holds the row's sum
+    }
+    if constexpr (LPR == 64) {
+        const long long bits = __double_as_longlong(v);
+        const int lo = (int)(unsigned)((unsigned long long)bits & 0xFFFFFFFFull), hi = (int)(unsigned)((unsigned long long)bits >> 32);
+        double tot = 0.0;
+#pragma unroll
+        for (int row = 0; row < 4; ++row) {
+            const unsigned l = (unsigned)__builtin_amdgcn_readlane(lo, 16 * row), h = (unsigned)__builtin_amdgcn_readlane(hi, 16 * row);
+            tot += __longlong_as_double((long long)(((unsigned long long)h << 32) | l));
+        }
+        v = tot;
+    }
+    return v;
+}
+template <int LPR>
+__device__ __forceinline__ cplx lanes_sum(cplx v) {
+    return cplx{lanes_sum<LPR>(v.re), lanes_sum<LPR>(v.im)};
+}
+
+// acc0 += Fa[0:cn] . vs, acc1 += Fb[0:cn] . vs over the LPR lanes of a sub-wave; eight row loads in flight per lane (the
+// sweeps are chains of short kernels: what they wait for is memory latency, not bandwidth)
+template <int LPR = 16, typename MT, typename VT>
+__device__ __forceinline__ void two_row_dot(const MT* __restrict__ Fa, const MT* __restrict__ Fb, const VT* vs, int32_t cn, int sl, VT& acc0,
+                                            VT& acc1) {
+    int32_t k = sl;
+    for (; k + 3 * LPR < cn; k += 4 * LPR) {
+        const MT a0 = Fa[k], a1 = Fa[k + LPR], a2 = Fa[k + 2 * LPR], a3 = Fa[k + 3 * LPR];
+        const MT b0 = Fb[k], b1 = Fb[k + LPR], b2 = Fb[k + 2 * LPR], b3 = Fb[k + 3 * LPR];
+        fma_acc(acc0, a0, vs[k]);
+        fma_acc(acc1, b0, vs[k]);
+        fma_acc(acc0, a1, vs[k + LPR]);
+        fma_acc(acc1, b1, vs[k + LPR]);
+        fma_acc(acc0, a2, vs[k + 2 * LPR]);
+        fma_acc(acc1, b2, vs[k + 2 * LPR]);
+        fma_acc(acc0, a3, vs[k + 3 * LPR]);
+        fma_acc(acc1, b3, vs[k + 3 * LPR]);
+    }
+    for (; k < cn; k += LPR) {
+        const MT a0 = Fa[k], b0 = Fb[k];
+        fma_acc(acc0, a0, vs[k]);
+        fma_acc(acc1, b0, vs[k]);
+    }
+}
+
+// the first 4 * LPR columns of a row pair, loaded before the vector they multiply is ready (they depend on the node record only)
+template <int LPR, typename MT>
+__device__ __forceinline__ void row_pair_prefetch(const MT* __restrict__ Fa, const MT* __restrict__ Fb, int32_t cn, int sl, MT (&pa)[4], MT (&pb)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int32_t k = sl + q * LPR;
+        pa[q] = k < cn ? Fa[k] : scalar_traits<MT>::zero();
+        pb[q] = k < cn ? Fb[k] : scalar_traits<MT>::zero();
+    }
+}
+
+template <int LPR, typename MT, typename VT>
+__device__ __forceinline__ void two_row_dot_prefetched(const MT* __restrict__ Fa, const MT* __restrict__ Fb, const VT* vs, int32_t cn, int sl, VT& acc0,
+                                                       VT& acc1, const MT (&pa)[4], const MT (&pb)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int32_t k = sl + q * LPR;
+        if (k < cn) {
+            fma_acc(acc0, pa[q], vs[k]);
+            fma_acc(acc1, pb[q], vs[k]);
+        }
+    }
+    if (cn > 4 * LPR) two_row_dot<LPR>(Fa + 4 * LPR, Fb + 4 * LPR, vs + 4 * LPR, cn - 4 * LPR, sl, acc0, acc1);
+}
+
+// PULL form: sum of the children's update-vector entries that land on front position j, through the per-child gather rows
+// (fixed order: child rank).  Used where a child's vector arrives by all-gather (the replicated top of a forest cut over ranks)
+// and by the transposed sweeps.
+template <typename VT>
+__device__ __forceinline__ VT gather_updates(const int32_t* __restrict__ ge, int32_t nchild, int32_t f, int32_t j, const VT* __restrict__ ubuf,
+                                             VT v) {
+    int32_t c = 0;
+    for (; c + 3 < nchild; c += 4) {
+        const int32_t g0 = ge[(size_t)c * f + j], g1 = ge[(size_t)(c + 1) * f + j], g2 = ge[(size_t)(c + 2) * f + j], g3 = ge[(size_t)(c + 3) * f + j];
+        const VT u0 = g0 >= 0 ? ubuf[g0] : scalar_traits<VT>::zero(), u1 = g1 >= 0 ? ubuf[g1] : scalar_traits<VT>::zero();
+        const VT u2 = g2 >= 0 ? ubuf[g2] : scalar_traits<VT>::zero(), u3 = g3 >= 0 ? ubuf[g3] : scalar_traits<VT>::zero();
+        v = s_add(s_add(s_add(s_add(v, u0), u1), u2), u3);
+    }
+    int32_t g[3] = {-1, -1, -1};
+    for (int q = 0; q < 3; ++q)
+        if (c + q < nchild) g[q] = ge[(size_t)(c + q) * f + j];
+    VT u[3];
+    for (int q = 0; q < 3; ++q) u[q] = g[q] >= 0 ? ubuf[g[q]] : scalar_traits<VT>::zero();
+    for (int q = 0; q < 3; ++q)
+        if (c + q < nchild) v = s_add(v, u[q]);
+    return v;
+}
+
+// PUSH form: the same sum from the node's slot rows (row c = what child c added to every front position; slots no child maps
+// to were zeroed once and are never written): contiguous loads, no index in between.  Same order of additions as the pull form.
+template <typename VT>
+__device__ __forceinline__ VT slot_sum(const VT* __restrict__ slots, int32_t nchild, int32_t f, int32_t j, VT v) {
+    int32_t c = 0;
+    for (; c + 3 < nchild; c += 4) {
+        const VT u0 = slots[(size_t)c * f + j], u1 = slots[(size_t)(c + 1) * f + j], u2 = slots[(size_t)(c + 2) * f + j],
+                 u3 = slots[(size_t)(c + 3) * f + j];
+        v = s_add(s_add(s_add(s_add(v, u0), u1), u2), u3);
+    }
+    VT u[3];
+    for (int q = 0; q < 3; ++q) u[q] = c + q < nchild ? slots[(size_t)(c + q) * f + j] : scalar_traits<VT>::zero();
+    for (int q = 0; q < 3; ++q)
+        if (c + q < nchild) v = s_add(v, u[q]);
+    return v;
+}
+
+// downward sweep: the value of front position j goes into the boundary vector of every child that has j in its boundary
+template <typename VT>
+__device__ __forceinline__ void push_down(const int32_t* __restrict__ ge, int32_t nchild, int32_t f, int32_t j, VT* __restrict__ xb, VT val) {
+    for (int32_t c = 0; c < nchild; ++c) {
+        const int32_t g = ge[(size_t)c * f + j];
+        if (g >= 0) xb[g] = val;
+    }
+}
+
+// ---- the merged top (NdTop, ndlu_internal.h): the root and its children in one launch
+// the output of top row i (final: no downward step follows): into x, and to the boundary vectors of the grandchildren -- a row
+// of child c through c's gather rows at its own position; a row of the root, for every child c that has it at boundary
+// position p, through c's gather rows at m_c + p (what nd_bwd_tile hands on for a child of the root)
+template <typename VT>
+__device__ __forceinline__ void nd_top_store(const NdTop& tp, int32_t i, VT val, const int32_t* __restrict__ icmap, const int32_t* __restrict__ gell,
+                                             VT* __restrict__ x, VT* __restrict__ xb) {
+    const int32_t K = tp.nchild;
+    const NdTopNode& R = tp.node[K];
+    if (i >= R.off) {
+        const int32_t k = i - R.off;
+        x[R.own0 + k] = val;
+        for (int32_t c = 0; c < K; ++c) {
+            const NdTopNode& nd = tp.node[c];
+            const int32_t p = icmap[(size_t)c * R.m + k];
+            if (p >= 0) push_down(gell + nd.ge_off, nd.nchild, nd.f, nd.m + p, xb, val);
+        }
+        return;
+    }
+    for (int32_t c = 0; c < K; ++c) {
+        const NdTopNode& nd = tp.node[c];
+        if (i < nd.off || i >= nd.off + nd.m) continue;
+        x[nd.own0 + i - nd.off] = val;
+        push_down(gell + nd.ge_off, nd.nchild, nd.f, i - nd.off, xb, val);
+    }
+}
+
+// The tile form of a level's launch from NdLevel::sweep_rows: LPR lanes per row pair, 512 / LPR rows per tile.  8 rows -> 64 lanes;
+// 128 -> 4, upwards only (THIN: the downward sweep of a thin level has few, long rows and stays with 32-row tiles, as
+// nd_setup_levels counted them); else 32 rows -> 16.
+template <bool THIN, typename F>
+void nd_with_lpr(int32_t sweep_rows, F&& launch) {
+    if (sweep_rows == 8) return launch(std::integral_constant<int, 64>{});
+    if constexpr (THIN)
+        if (sweep_rows == 128) return launch(std::integral_constant<int, 4>{});
+    launch(std::integral_constant<int, 16>{});
+}
+
+}  // namespace

@@ -155,6 +155,9 @@ SIGNATURES = {
     "lsa_ndlu_solve_batch": (ctypes.c_int, [_P, _I32, _PP, _PP, _PP]),
     "lsa_ndlu_solve_adjoint": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P]),
     "lsa_ndlu_solve_time": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.POINTER(_DBL)]),
+    "lsa_ndlu_solve_multi": (ctypes.c_int, [_P, _P, ctypes.c_int, _I32, _P, _I64, _P, _I64]),
+    "lsa_ndlu_solve_multi_time": (ctypes.c_int, [_P, _P, ctypes.c_int, _I32, _P, _I64, _P, _I64, ctypes.c_int, ctypes.POINTER(_DBL)]),
+    "lsa_ndlu_multi_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "lsa_ndlu_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64),
                                      ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_DBL), ctypes.POINTER(_DBL)]),
     "lsa_gmres": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, _DBL, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_I32), ctypes.POINTER(_DBL)]),
@@ -639,6 +642,9 @@ def nd_order(A, leaf_size: int = 0, constraint=None) -> dict:
 
 
 NDLU_BATCH_MAX = 16  # factorisations of one lsa_ndlu_solve_batch call (kNdBatchMax in csrc/ndlu_internal.h)
+NDLU_MULTI_MAX = 8  # most columns of one pass of lsa_ndlu_solve_multi (kNdMultiMax: real vectors; complex vectors run passes of at most 4)
+NDLU_MULTI_CHUNK = 256  # vector entries per column a multi-column sweep tile stages in LDS at a time (kMCH)
+_TRANS = {"N": 0, "T": 1, "H": 2}
 
 
 class NdLu:
@@ -698,6 +704,32 @@ class NdLu:
         ms = _DBL(0.0)
         self.ctx.check(self.ctx._lib.lsa_ndlu_solve_time(self.ctx.handle, self.handle, b.handle, x.handle, int(iters), ctypes.byref(ms)))
         return ms.value
+
+    def _multi_args(self, B: DeviceVector, X: DeviceVector, nrhs: int, ldb, ldx, trans: str):
+        if trans not in _TRANS:
+            raise ValueError(f"trans must be 'N', 'T' or 'H', got {trans!r}")
+        return (self.ctx.handle, self.handle, _TRANS[trans], int(nrhs), B.handle, int(self.n if ldb is None else ldb), X.handle,
+                int(self.n if ldx is None else ldx))
+
+    def solve_multi(self, B: DeviceVector, X: DeviceVector, nrhs: int, ldb: int | None = None, ldx: int | None = None, trans: str = "N") -> None:
+        """``X[:, q] = op(C)^-1 B[:, q]`` for ``nrhs`` columns on this factorisation (``lsa_ndlu_solve_multi``).  ``B`` and ``X``
+        are column-major blocks in one vector each (column ``q`` at ``q * ld``, ``ld`` defaulting to ``n``); ``B is X`` solves in
+        place.  ``trans``: ``"N"``, ``"T"`` or ``"H"``.  Every column is bit-identical to :meth:`solve` / :meth:`solve_adjoint`."""
+        self.ctx.check(self.ctx._lib.lsa_ndlu_solve_multi(*self._multi_args(B, X, nrhs, ldb, ldx, trans)))
+
+    def time_solve_multi(self, B: DeviceVector, X: DeviceVector, nrhs: int, iters: int, ldb: int | None = None, ldx: int | None = None,
+                         trans: str = "N") -> float:
+        """Mean milliseconds of one block solve over ``iters`` back-to-back repetitions (``lsa_ndlu_solve_multi_time``)."""
+        ms = _DBL(0.0)
+        self.ctx.check(self.ctx._lib.lsa_ndlu_solve_multi_time(*self._multi_args(B, X, nrhs, ldb, ldx, trans), int(iters), ctypes.byref(ms)))
+        return ms.value
+
+    def multi_info(self) -> dict:
+        """What the last :meth:`solve_multi` used: ``width`` (columns of its widest pass; 1 = column by column, 0 = none yet),
+        ``extra_bytes`` (per-column sweep buffers), ``launches_per_pass``."""
+        w, la, eb = _I32(0), _I32(0), _I64(0)
+        self.ctx.check(self.ctx._lib.lsa_ndlu_multi_info(self.handle, ctypes.byref(w), ctypes.byref(eb), ctypes.byref(la)))
+        return {"width": w.value, "extra_bytes": eb.value, "launches_per_pass": la.value}
 
     def inertia(self) -> tuple[int, int, int]:
         """(negative, zero, positive) eigenvalue counts of a REAL SYMMETRIC matrix from its factors (``lsa_ndlu_inertia``): for

@@ -1,0 +1,110 @@
+"""Block solves on one factorisation of the exact LU: milliseconds per column of ``NdLu.solve_multi`` against the solo solve.
+
+    python tools/multi_rhs_throughput.py [--cases S30k S500k C160k] [--nrhs 1 2 4 8 16 32] [--parent-solo-us US ...]
+                                         [--out profiles/multi_rhs.json]
+
+Per case (2D cylinder cases at the complex shift of the bench, 3D cube cases at their real shift; the matrix in the
+elimination order with the forest handed back, as ``Solver/utils.py`` prepares it): the time of one ``lsa_ndlu_solve``
+(``time_solve``, 100 back-to-back solves between HIP events), then for every ``nrhs`` the time of one block solve
+(``time_solve_multi``) divided by ``nrhs``, with what ``multi_info`` reports and the bytes one sweep reads.  With
+``LSA_ND_MULTI_WIDTH=W`` in the environment (read once per process) the library takes passes of at most ``W`` columns: the
+recorded ``width_cap``.  Every block solve is checked bit for bit against solo solves of its columns.  ``--parent-solo-us``
+(one figure per case) records beside the solo time what ``tools/bench_ndlu.py --case CASE`` of the PARENT commit, built
+apart, printed as "solve ... us per apply" on the same box: ``parent_commit_solo_ms`` and the ratio ``solo_vs_parent`` (the
+solo path is meant to be that code unchanged; DESIGN section 4b states a box-to-box spread of 4 %).  Appends to ``--out`` when
+the file exists (one case per call keeps a call short).
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path[:0] = [str(ROOT), str(ROOT / "lsa-fw_amd")]
+
+
+def measure(case: str, counts: list[int], iters: int, parent_solo_us: float | None = None) -> dict:
+    import numpy as np
+    import scipy.sparse as sp
+
+    import lsa_hip
+    from synthetic import fem
+
+    cube = case.startswith("C")
+    es = fem.cube_case(case) if cube else fem.cylinder_case(case)
+    sigma = fem.SIGMA_CUBE if cube else fem.SIGMA_RE50
+    C = sp.csr_matrix((es.A.data - sigma * es.M.data, es.A.indices, es.A.indptr), shape=es.A.shape)
+    zd = C.diagonal() == 0
+    o = lsa_hip.nd_order(C, 0, constraint=zd if (zd.any() and C.nnz > 60 * es.n) else None)
+    C = C[o["perm"]][:, o["perm"]].tocsr()
+    C.sort_indices()
+    ctx = lsa_hip.Context(0)
+    dC = lsa_hip.CsrMatrix.from_scipy(ctx, C)
+    t0 = time.time()
+    f = lsa_hip.NdLu(ctx, dC, 0, tree={"first": o["first"], "size": o["size"], "parent": o["parent"]})
+    info = f.info()
+    n, kmax = es.n, max(counts)
+    vdt = np.complex128 if np.iscomplexobj(C.data) else np.float64
+    rng = np.random.default_rng(0)
+    B = rng.standard_normal((n, kmax)) + (1j * rng.standard_normal((n, kmax)) if vdt is np.complex128 else 0.0)
+    B = np.asfortranarray(B.astype(vdt))
+    db, dx = lsa_hip.DeviceVector.from_numpy(ctx, np.ascontiguousarray(B[:, 0])), lsa_hip.DeviceVector(ctx, n, vdt)
+    f.time_solve(db, dx, 10)
+    solo_ms = f.time_solve(db, dx, iters)
+    out = {"case": case, "n": int(n), "sigma": [complex(sigma).real, complex(sigma).imag], "factor_dtype": np.dtype(vdt).name,
+           "create_seconds": round(time.time() - t0, 3), "factor_bytes_per_sweep": int(info["apply_bytes"]), "apply_launches": int(info["apply_launches"]),
+           "solo_ms": solo_ms, "solo_GBps": info["apply_bytes"] / solo_ms / 1e6, "width_cap": int(os.environ.get("LSA_ND_MULTI_WIDTH", lsa_hip.NDLU_MULTI_MAX)),
+           "multi": []}
+    ref = np.empty((n, min(kmax, 8)), dtype=vdt)  # solo answers of the first columns: the bit-for-bit check
+    for q in range(ref.shape[1]):
+        f.solve(lsa_hip.DeviceVector.from_numpy(ctx, np.ascontiguousarray(B[:, q])), dx)
+        ref[:, q] = dx.numpy()
+    for k in counts:
+        dB = lsa_hip.DeviceVector.from_numpy(ctx, B[:, :k].reshape(-1, order="F"))
+        dX = lsa_hip.DeviceVector(ctx, n * k, vdt)
+        f.time_solve_multi(dB, dX, k, iters=3)
+        ms = f.time_solve_multi(dB, dX, k, iters=max(3, iters // k))
+        X = dX.numpy().reshape((n, k), order="F")
+        same = bool(np.array_equal(X[:, :ref.shape[1]], ref[:, :k]))
+        res = float(np.linalg.norm(B[:, :k] - C @ X) / np.linalg.norm(B[:, :k]))
+        mi = f.multi_info()
+        out["multi"].append({"nrhs": k, "ms_per_block": ms, "ms_per_column": ms / k, "solo_over_multi_per_column": solo_ms / (ms / k),
+                             "bit_identical_to_solo": same, "residual": res, **mi})
+        print(f"{case} nrhs={k:2d}: {ms / k * 1e3:9.1f} us per column ({solo_ms / (ms / k):.2f}x the solo {solo_ms * 1e3:.1f} us), width {mi['width']}, "
+              f"extra {mi['extra_bytes'] / 1e6:.1f} MB, bits {'same' if same else 'DIFFER'}, residual {res:.1e}", flush=True)
+        del dB, dX
+    solo_after = f.time_solve(db, dx, iters)
+    out["solo_ms_after"] = solo_after
+    if parent_solo_us is not None:
+        out["parent_commit_solo_ms"] = parent_solo_us / 1e3
+        out["solo_vs_parent"] = solo_ms / (parent_solo_us / 1e3)
+        print(f"{case}: solo {solo_ms * 1e3:.1f} us, after the block solves {solo_after * 1e3:.1f} us, parent commit {parent_solo_us:.1f} us "
+              f"({out['solo_vs_parent']:.3f})", flush=True)
+    return out
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", nargs="+", default=["S30k", "S500k", "C160k"])
+    ap.add_argument("--nrhs", nargs="+", type=int, default=[1, 2, 4, 8, 16, 32])
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--parent-solo-us", nargs="+", type=float, default=None, help="per case: the parent commit's bench_ndlu.py figure on this box")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "multi_rhs.json"))
+    args = ap.parse_args()
+    path = Path(args.out)
+    doc = json.loads(path.read_text()) if path.exists() else {"tool": "tools/multi_rhs_throughput.py", "runs": []}
+    if args.parent_solo_us is not None and len(args.parent_solo_us) != len(args.cases):
+        ap.error("--parent-solo-us needs one figure per case")
+    for i, case in enumerate(args.cases):
+        doc["runs"].append(measure(case, args.nrhs, args.iters, None if args.parent_solo_us is None else args.parent_solo_us[i]))
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(doc, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
