@@ -71,6 +71,8 @@ int lsa_ctx_create(int device, lsa_ctx **out);
 void lsa_ctx_destroy(lsa_ctx *ctx);
 const char *lsa_last_error(const lsa_ctx *ctx);
 int lsa_ctx_synchronize(lsa_ctx *ctx);
+/* free and total bytes of the context's device memory right now (hipMemGetInfo) */
+int lsa_ctx_mem_info(lsa_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
 /* name of the GPU architecture the context runs on, e.g. "gfx950" */
 const char *lsa_ctx_arch(const lsa_ctx *ctx);
 
@@ -249,6 +251,10 @@ int lsa_ndlu_multi_info(const lsa_ndlu *f, int32_t *width, int64_t *extra_bytes,
  * tree nodes of the inertia of their pivot blocks, each evaluated on the host (O(m^3)): for the Hermitian problems of the
  * interval sweep.  Real factors on one rank only; the symmetry of C is the caller's statement. */
 int lsa_ndlu_inertia(lsa_ctx *ctx, lsa_ndlu *f, int64_t *negative, int64_t *zero, int64_t *positive);
+/* out[8] as lsa_nd_sym_memory fills it, for the analysis the context holds prepared (after lsa_ndlu_prepare / _prepare_tree, or
+ * parked by the last lsa_ndlu_destroy) with its own scalar type: what the next factorisation on it allocates.  LSA_ERR_ARG when
+ * the context holds none. */
+int lsa_ndlu_prepared_memory(lsa_ctx *ctx, int64_t *out);
 /* front_entries: scalars of the device buffers (packed factors + the working fronts of one chunk + the update arena);
  * apply_bytes: algorithmic bytes of one solve (every factor scalar once + the vectors); apply_launches: dependent
  * launches of one solve (two per tree level, less one: the roots have no downward step) */
@@ -379,6 +385,27 @@ int64_t lsa_mat_rows(const lsa_mat *m);
  * relative residual estimates.  Returns LSA_OK also when fewer than nev pairs converged in max_restarts (see result). */
 int lsa_krylov_solve(lsa_ctx *ctx, lsa_krylov *k, const lsa_ks_options *opts, const void *v0, const double *mask, int32_t max_out,
                      void *theta_out, void *lambda_out, void *X_out, double *est_out, lsa_ks_result *result);
+/* The same iteration for J problems of one group at once (1 <= J <= 16): workspaces of one context with one n and one ncv, no
+ * two of them sharing a workspace or an operator.  Problems whose Arnoldi steps run the pipelined DCGS2 tail form on factors of
+ * one LU analysis advance in lockstep: a round queues one step of each such problem as ONE batched sweep pair and ONE batched
+ * reduction, update and tail launch, and one read-back covers up to 16 rounds of all of them; Schur forms, convergence tests and
+ * restarts run per problem on the host.  A problem whose steps take another form (or change form on the way: a missed
+ * ksp_rtol, a breakdown) runs them through the code of lsa_krylov_solve, and every problem returns exactly the bits of its own
+ * lsa_krylov_solve.  (The tail form needs a complex C = A - sigma M: the problems of a group with a REAL shift on real
+ * matrices never advance in lockstep; all their steps run through the solo code inside this call.)  Every array argument has J entries (v0, X_out, est_out and their entries may be NULL as in the solo call);
+ * status[z] is the problem's own return code -- a failing problem does not stop the others, its error text names it -- and the
+ * call returns the first non-zero status (LSA_ERR_ARG at once for a bad group, with status untouched). */
+typedef struct {
+    int64_t rounds;               /* lockstep rounds queued                                                                 */
+    int64_t launches;             /* kernel launches of those rounds: products, sweeps, reduction, update, tail             */
+    int64_t periods;              /* read-backs of lockstep rounds (one synchronisation each)                               */
+    double launches_per_round;    /* launches / rounds                                                                      */
+    int64_t lockstep_steps[16];   /* per problem: Arnoldi steps accepted from lockstep rounds                               */
+    int64_t solo_steps[16];       /* per problem: Arnoldi steps that ran alone (lsa_krylov_solve's code)                    */
+} lsa_ks_batch_info;
+int lsa_krylov_solve_batch(lsa_ctx *ctx, int32_t J, lsa_krylov *const *k, const lsa_ks_options *const *opts, const void *const *v0,
+                           int32_t max_out, void *const *theta_out, void *const *lambda_out, void *const *X_out, double *const *est_out,
+                           lsa_ks_result *results, int32_t *status, lsa_ks_batch_info *info);
 /* Eigenpairs of A x = lambda M x nearest sigma in ONE call: builds and factors A - sigma M (lsa_op_create, mode 0), allocates
  * the basis, iterates, writes the pairs and releases everything.  ncv <= 0: max(2 nev, nev + 15) (SLEPc's default).  row_perm:
  * NULL, or perm[i] = the caller's index of row i (the matrices were uploaded in a permuted order, e.g. that of lsa_nd_order):

@@ -133,12 +133,105 @@ class EigenSolver:
         inner = self._solver.stats.get("gmres_iters")
         logger.info("Solve completed in %.2f s; converged %d eigenpairs%s", seconds, self._solver.get_num_converged(),
                     "" if inner is None else f"; iterations={inner}")
-        pairs = list(self._solver.get_all_eigenpairs_up_to(cfg.num_eig))
+        return self._pairs()
+
+    def _pairs(self) -> list[tuple[float | complex, iComplexPETScVector]]:
+        """What :meth:`solve` hands back, from the solver's collected results."""
+        pairs = list(self._solver.get_all_eigenpairs_up_to(self._cfg.num_eig))
         logger.info("Retrieved %d eigenpairs", len(pairs))
         return pairs
 
 
-def solve_batch(solvers, *, max_batch: int = 8) -> list[list[tuple[float | complex, iComplexPETScVector]]]:
+def _solve_group_in_turn(solvers, group, results) -> None:
+    """The members of a prepared group one after another on the group's context (each its own factorisation and iteration)."""
+    prev = None
+    for i in group:
+        eps = solvers[i].solver
+        if prev is not None and prev.stats.get("analysis_reused") != 1:
+            # the previous factorisation did not run on the group's analysis: the context holds another one now
+            eps.redo_pattern_phase()
+        results[i] = solvers[i].solve()
+        eps._stats.update({"shared_analysis": True, "batch_size": len(group)})
+        prev = eps
+
+
+def _solve_group_lockstep(solvers, group, results, max_batch: int) -> None:
+    """The members of a prepared group with all their operators and Krylov workspaces alive at once and ONE
+    ``lsa_krylov_solve_batch`` over them; as many at a time (a chunk) as 0.8 of the free device memory holds.  The library decides
+    per problem and expansion whether its steps can run in lockstep and runs them through the solo code otherwise; only a member
+    that cannot enter the call at all (the symmetric iteration, the Python test double of the outer loop) or whose factorisation
+    analysed again runs its own iteration after the chunk's call.  A member that fails does not stop the others of its chunk:
+    its error is raised once they are collected."""
+    import lsa_hip
+
+    from .batch import plan_batches
+    from .utils import _native_driver
+
+    lead = solvers[group[0]].solver
+    try:
+        per_problem = lead.lockstep_bytes_per_problem()
+    except ValueError:  # (no prepared analysis: the exact LU did not fit; the in-turn path answers that as .solve() does)
+        per_problem = 0
+    free, _total = lead._prepared["ctx"].mem_info()
+    sub = plan_batches([solvers[i].solver for i in group], max_batch, bytes_per_problem=per_problem, memory_budget=int(0.8 * free))
+    chunks = [[group[q] for q in c] for c in sub.groups]
+    if per_problem == 0 or (len(group) > 1 and all(len(c) == 1 for c in chunks)):  # the budget cuts the group to one problem at a time
+        logger.info("Lockstep: device memory holds one problem of this group at a time; solving one after another")
+        _solve_group_in_turn(solvers, group, results)
+        return
+    failed: list[BaseException] = []
+    for chunk in chunks:
+        runs: list[dict] = []
+        try:
+            for i in chunk:
+                eps = solvers[i].solver
+                if i != group[0]:
+                    # The prepared analysis went into an earlier member's factorisation (alive, or parked with another analysis
+                    # if it analysed again): the pattern-only phase runs again from the shared forest, so that this member
+                    # factorises on the analysis of its solo solve -- the group's.
+                    eps.redo_pattern_phase()
+                run = eps._open()
+                runs.append(run)
+                reused = run["op"].stats().get("analysis_reused") == 1
+                run["eligible"] = bool(_native_driver() and reused and not run["use_lanczos"] and run["basis"] is not None and run["mask"] is None)
+            members = [q for q, run in enumerate(runs) if run["eligible"]]
+            errors: dict[int, BaseException] = {}
+            if members:
+                args = [solvers[chunk[q]].solver._native_krylov_arguments(runs[q]) for q in members]
+                first = args[0]
+                res, info = lsa_hip.KrylovBasis.solve_batch(
+                    [runs[q]["basis"] for q in members], first["nev"], first["tol"], first["max_restarts"], first["which"], first["transform"],
+                    [a["sigma"] for a in args], antishift=[a["antishift"] for a in args], targets=[a["target"] for a in args], v0s=first["v0"],
+                    seed=first["seed"], raise_on_error=False)
+                logger.info("Lockstep group of %d: %d rounds, %.1f launches per round, %d read-backs", len(members), info["rounds"],
+                            info["launches_per_round"], info["periods"])
+                for z, q in enumerate(members):
+                    if isinstance(res[z], BaseException):
+                        errors[q] = res[z]
+                        continue
+                    runs[q]["res"] = res[z]
+                    runs[q]["lockstep"] = {"lockstep": info["lockstep_steps"][z] > 0, "lockstep_steps": info["lockstep_steps"][z],
+                                           "solo_steps": info["solo_steps"][z], "lockstep_rounds": info["rounds"],
+                                           "lockstep_launches_per_round": info["launches_per_round"]}
+            for q, i in enumerate(chunk):
+                if q in errors:
+                    continue
+                eps = solvers[i].solver
+                if runs[q]["res"] is None:
+                    eps._run(runs[q])
+                    runs[q]["lockstep"] = {"lockstep": False, "lockstep_steps": 0, "solo_steps": int(runs[q]["res"].op_applies)}
+                eps._collect(runs[q])
+                eps._stats.update({"shared_analysis": True, "batch_size": len(group)})
+                results[i] = solvers[i]._pairs()
+            failed.extend(errors[q] for q in sorted(errors))
+        finally:
+            for run in runs:
+                run.clear()
+    if failed:
+        raise failed[0]
+
+
+def solve_batch(solvers, *, max_batch: int = 8, lockstep: bool = False) -> list[list[tuple[float | complex, iComplexPETScVector]]]:
     """Solve several :class:`EigenSolver` s built as for ``.solve()`` (a parameter sweep on one mesh) and return what each
     ``.solve()`` returns, in order.  Every solver is left as ``.solve()`` leaves it (``get_eigenvalue``,
     ``get_eigenvector``, ``residuals()``, ``stats``).
@@ -149,10 +242,19 @@ def solve_batch(solvers, *, max_batch: int = 8) -> list[list[tuple[float | compl
     the LU and its index tables (pattern-keyed reuse); each problem then runs its own numeric factorisation and
     Krylov-Schur iteration, one problem after another, and returns exactly the bits of a solo solve.
     ``stats["shared_analysis"]`` says whether a solver took the group path (``stats["batch_size"]``: its group's size);
-    every other solver is solved alone (one log line says why)."""
+    every other solver is solved alone (one log line says why).
+
+    ``lockstep=True`` (build-only, default off): a group factorises all its problems first -- as many factor sets and Krylov
+    workspaces alive at once as 0.8 of the free device memory holds -- and runs ONE ``lsa_krylov_solve_batch`` over them:
+    every Arnoldi round queues one step of each problem as one batched sweep pair and one batched reduction, update and tail
+    launch, one read-back covers up to 16 rounds of all problems; Schur forms and restarts stay per problem.  Still the bits of
+    a solo solve.  ``stats["lockstep"]`` says whether a solver's steps ran that way, ``stats["lockstep_steps"]`` and
+    ``stats["solo_steps"]`` how many did and did not."""
     from .batch import plan_batches
     from .utils import SharedContext
 
+    if not isinstance(lockstep, bool):
+        raise TypeError(f"lockstep must be a bool, got {type(lockstep).__name__}")
     solvers = list(solvers)
     if not solvers:
         raise ValueError("solve_batch needs at least one solver")
@@ -172,15 +274,10 @@ def solve_batch(solvers, *, max_batch: int = 8) -> list[list[tuple[float | compl
         for i in group[1:]:
             solvers[i].solver.prepare(_share=prep)
         logger.info("Group of %d eigenproblems on one pattern: one context, ordering and LU analysis", len(group))
-        prev = None
-        for i in group:
-            eps = solvers[i].solver
-            if prev is not None and prev.stats.get("analysis_reused") != 1:
-                # the previous factorisation did not run on the group's analysis: the context holds another one now
-                eps.redo_pattern_phase()
-            results[i] = solvers[i].solve()
-            eps._stats.update({"shared_analysis": True, "batch_size": len(group)})
-            prev = eps
+        if lockstep:
+            _solve_group_lockstep(solvers, group, results, max_batch)
+        else:
+            _solve_group_in_turn(solvers, group, results)
     for i, reason in sorted(plan.alone.items()):
         logger.info("Eigenproblem %d is solved alone: %s", i, reason)
         results[i] = solvers[i].solve()

@@ -639,6 +639,18 @@ class iEpsSolver:
                 raise
             logger.warning("The exact LU does not fit the device memory (%s); the solve will fall back to ILU(k) + GMRES.", exc)
 
+    def lockstep_bytes_per_problem(self) -> int:
+        """Device bytes one member of a lockstep group keeps alive (after :meth:`prepare`): the factorisation by the memory plan of
+        the analysis the context holds prepared (``lsa_ndlu_prepared_memory``, the figures of ``lsa_nd_sym_memory``), the Krylov
+        workspace (3 x 16 n (ncv + 1)) and the matrices A, M and A - sigma M.  ``ValueError`` when no analysis is prepared."""
+        prep = self._prepared
+        n = prep["n"]
+        ncv = min(self._ncv if self._ncv is not None else max(2 * self._nev, self._nev + 15), n)
+        scalar = 16 if prep["cplx_factors"] else 8
+        nnz = prep["dA"].nnz
+        matrices = nnz * ((8 + 4) * (1 if prep["dM"] is None else 2) + scalar + 4)
+        return int(prep["ctx"].prepared_lu_bytes() + 3 * 16 * n * (ncv + 1) + matrices)
+
     def release(self) -> None:
         """Free the device copies made by :meth:`prepare`."""
         prep = getattr(self, "_prepared", None)
@@ -662,13 +674,37 @@ class iEpsSolver:
 
     def solve(self) -> None:
         """Run the eigensolver on the GPU (reference: ``self._eps.solve()``, ``Solver/utils.py:268-270``):
-        build and factorise ``A - sigma M`` on the device, then Krylov-Schur with device-resident Arnoldi."""
-        import lsa_hip
-        from lsa_hip.krylov_schur import krylov_schur
+        build and factorise ``A - sigma M`` on the device, then Krylov-Schur with device-resident Arnoldi.  Three parts -- open
+        the operator and the basis, run the iteration, collect results and statistics -- that
+        :func:`Solver.eigen.solve_batch` also calls one by one for the members of a lockstep group.
 
+        Leaves the eigenpairs and ``self.stats``: the operator's counters plus ``stats["krylov_restarts"]``, ``stats["method"]``
+        (``"arnoldi"`` or ``"lanczos"``), ``stats["basis_bytes"]``, the phase times of the library's loop and, where
+        ``symmetric=True`` ran the general iteration, ``stats["symmetric_fallback"]`` with the reason."""
         if self._which is iEpsWhich.ALL:
             self._solve_interval()
             return
+        run = self._open()
+        try:
+            self._run(run)
+            self._collect(run)
+        finally:
+            run.clear()  # (basis and operator go before the next solve builds its own)
+
+    def _start_vector(self, n: int) -> np.ndarray:
+        """The complex start vector of the library's Krylov-Schur loop, drawn here so that every driver begins from the same one."""
+        cached = getattr(self, "_v0_cache", None)
+        if cached is None or cached[0] != (n, self._seed):  # (0.7 ms at 30 k unknowns: a shift sweep draws it once)
+            rng = np.random.default_rng(self._seed)
+            cached = ((n, self._seed), rng.standard_normal(n) + 1j * rng.standard_normal(n))
+            self._v0_cache = cached
+        return cached[1]
+
+    def _open(self) -> dict:
+        """First part of :meth:`solve`: the operator (built and factorised) and, unless the symmetric iteration is tried first,
+        the Krylov basis.  Returns the run's state for :meth:`_run` and :meth:`_collect`; the caller clears it."""
+        import lsa_hip
+
         self.prepare()
         prep = self._prepared
         ctx, n, sinvert, sigma, perm = prep["ctx"], prep["n"], prep["sinvert"], prep["sigma"], prep["perm"]
@@ -678,7 +714,6 @@ class iEpsSolver:
         nu = complex(sigma if self._antishift is None else self._antishift)  # STCayleySetAntishift defaults to the shift
         which = self._which or (iEpsWhich.TARGET_MAGNITUDE if sinvert else iEpsWhich.LARGEST_MAGNITUDE)
         # (like SLEPc, an interval set without iEpsWhich.ALL has no effect; ALL is handled by _solve_interval)
-        lam_key = _lambda_rank_key(which, self._target)
         if self._adjoint and (not sinvert or cayley or prep["pc_code"] != 2 or (prep["part"] is not None and prep["forest"] is None)):
             raise NotImplementedError("adjoint=True needs shift-invert with the exact LU (PreconditionerType.LU, lu='nd'), on one GPU or in the "
                                       "subtree-parallel sharded layout")
@@ -688,9 +723,10 @@ class iEpsSolver:
             use_lanczos, fallback = _symmetric_path(self)
             if use_lanczos and prep["pc_code"] != 2:
                 use_lanczos, fallback = False, "the exact LU is not in use"
-        op = basis = None
+        run = {"op": None, "basis": None, "res": None, "basis_bytes": 0, "ncv": ncv, "nev": nev, "nu": nu, "which": which, "ksp_rtol": ksp_rtol,
+               "use_lanczos": use_lanczos, "fallback": fallback, "mask": None, "lockstep": None}
         try:
-            op = lsa_hip.ShiftInvertOperator(
+            op = run["op"] = lsa_hip.ShiftInvertOperator(
                 ctx, prep["dA"], prep["dM"], np.conj(sigma) if self._adjoint else sigma, mode=2 if cayley else 0 if sinvert else 1, antishift=nu,
                 ilu_levels=prep["levels"],
                 ilu_shift=self._ilu_shift,
@@ -709,37 +745,72 @@ class iEpsSolver:
                 keep = np.ones(n)
                 keep[self._project_out] = 0.0
                 keep = keep[perm]  # the iteration runs in permuted numbering
-            mask = keep if part is None else part.pad_vector(np.ones(n) if keep is None else keep)
+            run["mask"] = keep if part is None else part.pad_vector(np.ones(n) if keep is None else keep)
             if keep is not None:
-                op.set_projection(mask)
-            res = None
-            basis_bytes = 0
-            if use_lanczos:
-                # real thick-restart Lanczos in the M-inner product (lsa_lanczos_solve).  What the library refuses (M not positive
-                # definite on the Krylov space, an inner solve short of ksp_rtol after its refinement step, factors that came
-                # out complex or inexact) is answered by the general iteration below, on the same operator.
-                try:
-                    basis = lsa_hip.LanczosBasis(ctx, op, ncv)
-                    basis.set_row_permutation(perm)
-                    cached = getattr(self, "_v0_real_cache", None)
-                    if cached is None or cached[0] != (n, self._seed):
-                        cached = ((n, self._seed), np.random.default_rng(self._seed).standard_normal(n))
-                        self._v0_real_cache = cached
-                    res = basis.solve(nev, self._tol, self._max_it, which.value, float(complex(sigma).real), target=float(complex(self._target).real),
-                                      v0=cached[1], seed=self._seed)
-                    basis_bytes = basis.basis_bytes
-                except (lsa_hip.LsaError, ValueError) as exc:
-                    use_lanczos, fallback, res, basis = False, f"the library refused the symmetric iteration: {exc}", None, None
-            if self._symmetric and not use_lanczos and fallback not in self._fallback_logged:
-                self._fallback_logged.add(fallback)
-                logger.warning("symmetric=True, but the solve runs the general (complex Arnoldi) iteration: %s.", fallback)
-            if res is None:
-                basis = lsa_hip.KrylovBasis(ctx, op, ncv, mask)
-                if part is None:
-                    basis.set_row_permutation(perm)  # Ritz vectors leave the device in the caller's numbering
-                # V, the restart's second basis and, with a row permutation, the Ritz vectors in the caller's numbering
-                basis_bytes = 16 * basis.n * (ncv + 1) * (3 if part is None else 2)
+                op.set_projection(run["mask"])
+            if not use_lanczos:
+                self._open_krylov_basis(run)
+        except BaseException:
+            run.clear()
+            raise
+        return run
+
+    def _open_krylov_basis(self, run: dict) -> None:
+        import lsa_hip
+
+        prep = self._prepared
+        part, ncv = prep["part"], run["ncv"]
+        basis = run["basis"] = lsa_hip.KrylovBasis(prep["ctx"], run["op"], ncv, run["mask"])
+        if part is None:
+            basis.set_row_permutation(prep["perm"])  # Ritz vectors leave the device in the caller's numbering
+        # V, the restart's second basis and, with a row permutation, the Ritz vectors in the caller's numbering
+        run["basis_bytes"] = 16 * basis.n * (ncv + 1) * (3 if part is None else 2)
+
+    def _native_krylov_arguments(self, run: dict) -> dict:
+        """The arguments of ``KrylovBasis.solve`` for this run (``solve_batch`` hands the same ones to the group call)."""
+        prep = self._prepared
+        return {"nev": run["nev"], "tol": self._tol, "max_restarts": self._max_it, "which": run["which"].value,
+                "transform": 2 if prep["cayley"] else 0 if prep["sinvert"] else 1, "sigma": prep["sigma"], "antishift": run["nu"],
+                "target": self._target, "v0": self._start_vector(run["basis"].n), "seed": self._seed}
+
+    def _run(self, run: dict) -> None:
+        """Second part of :meth:`solve`: the iteration on the opened operator; leaves its result in ``run["res"]``."""
+        import lsa_hip
+        from lsa_hip.krylov_schur import krylov_schur
+
+        prep = self._prepared
+        ctx, n, sinvert, sigma, perm = prep["ctx"], prep["n"], prep["sinvert"], prep["sigma"], prep["perm"]
+        cayley, nu, ncv, nev, which = prep["cayley"], run["nu"], run["ncv"], run["nev"], run["which"]
+        op = run["op"]
+        if run["use_lanczos"]:
+            # real thick-restart Lanczos in the M-inner product (lsa_lanczos_solve).  What the library refuses (M not positive
+            # definite on the Krylov space, an inner solve short of ksp_rtol after its refinement step, factors that came
+            # out complex or inexact) is answered by the general iteration below, on the same operator.
+            try:
+                basis = run["basis"] = lsa_hip.LanczosBasis(ctx, op, ncv)
+                basis.set_row_permutation(perm)
+                cached = getattr(self, "_v0_real_cache", None)
+                if cached is None or cached[0] != (n, self._seed):
+                    cached = ((n, self._seed), np.random.default_rng(self._seed).standard_normal(n))
+                    self._v0_real_cache = cached
+                run["res"] = basis.solve(nev, self._tol, self._max_it, which.value, float(complex(sigma).real), target=float(complex(self._target).real),
+                                         v0=cached[1], seed=self._seed)
+                run["basis_bytes"] = basis.basis_bytes
+            except (lsa_hip.LsaError, ValueError) as exc:
+                run.update({"use_lanczos": False, "fallback": f"the library refused the symmetric iteration: {exc}", "res": None, "basis": None})
+        fallback = run["fallback"]
+        if self._symmetric and not run["use_lanczos"] and fallback not in self._fallback_logged:
+            self._fallback_logged.add(fallback)
+            logger.warning("symmetric=True, but the solve runs the general (complex Arnoldi) iteration: %s.", fallback)
+        if run["res"] is not None:
+            return
+        if run["basis"] is None:
+            self._open_krylov_basis(run)
+        basis = run["basis"]
+        if not _native_driver():
+            # the same outer iteration in Python over LAPACK (lsa_hip/krylov_schur.py): test double of the library's loop
             tiny = np.finfo(float).tiny
+            lam_key = _lambda_rank_key(which, self._target)
             if cayley:  # theta = (lambda + nu) / (lambda - sigma)
                 back = lambda th: (sigma * th + nu) / np.where(th == 1.0, 1.0 + 1e-300, th - 1.0)  # noqa: E731
             elif sinvert:  # theta = 1 / (lambda - sigma)
@@ -747,61 +818,62 @@ class iEpsSolver:
             else:
                 back = lambda th: th + sigma  # noqa: E731
             theta_key = lambda th: lam_key(back(np.asarray(th, dtype=np.complex128)))  # noqa: E731
-            import os
+            run["res"] = krylov_schur(basis, nev, self._tol, self._max_it, theta_key, rng_seed=self._seed)
+        else:
+            # one library call: Krylov-Schur with the library's own dense algebra (lsa_krylov_solve)
+            run["res"] = basis.solve(**self._native_krylov_arguments(run))
 
-            if res is not None:
-                pass
-            elif os.environ.get("LSA_KS_DRIVER", "native") == "python":
-                # the same outer iteration in Python over LAPACK (lsa_hip/krylov_schur.py): test double of the library's loop
-                res = krylov_schur(basis, nev, self._tol, self._max_it, theta_key, rng_seed=self._seed)
-            else:
-                # one library call: Krylov-Schur with the library's own dense algebra (lsa_krylov_solve).  The start vector is
-                # drawn here so that both drivers begin from the same one.
-                cached = getattr(self, "_v0_cache", None)
-                if cached is None or cached[0] != (basis.n, self._seed):  # (0.7 ms at 30 k unknowns: a shift sweep draws it once)
-                    rng = np.random.default_rng(self._seed)
-                    cached = ((basis.n, self._seed), rng.standard_normal(basis.n) + 1j * rng.standard_normal(basis.n))
-                    self._v0_cache = cached
-                v0 = cached[1]
-                res = basis.solve(nev, self._tol, self._max_it, which.value, 2 if cayley else 0 if sinvert else 1, sigma, antishift=nu,
-                                  target=self._target, v0=v0, seed=self._seed)
-            imag_norms = getattr(basis, "imag_norms", None)  # set when the device already put the vectors into canonical phase
-            theta = res.theta
-            lam = res.lam if use_lanczos else back(np.asarray(theta, dtype=np.complex128))
-            if part is None:
-                X = res.vectors
-            else:
-                vecs = part.unpad_vector(res.vectors)
-                X = np.empty_like(vecs)
-                X[perm, :] = vecs
-            self._stats = op.stats()
-            self._stats["krylov_restarts"] = res.restarts
-            self._stats["method"] = "lanczos" if use_lanczos else "arnoldi"
-            self._stats["basis_bytes"] = int(basis_bytes)
-            if self._symmetric and not use_lanczos:
-                self._stats["symmetric_fallback"] = fallback
-            if res.history and "seconds_dense" in res.history[-1]:  # the library's loop times its phases
-                self._stats.update({k: res.history[-1][k] for k in ("seconds_expand", "seconds_dense", "seconds_restart")})
-            if part is not None:
-                now = ctx.comm_stats()
-                last = getattr(self, "_comm_seen", {"allgather_calls": 0, "allgather_bytes_received": 0})
-                self._stats.update({k: now[k] - last[k] for k in now})  # of this solve
-                self._comm_seen = now
-                self._stats["ranks"] = part.nranks
-            if self._stats.get("pc_fallback"):
-                logger.warning("The exact LU did not fit the device memory: the inner solves ran ILU(%d)-preconditioned GMRES instead.",
-                               prep["levels"])
-            if self._stats.get("backward_accepted"):
-                logger.info("%d inner solves were accepted on their backward error (the shift lies next to eigenvalues: A - sigma M is "
-                            "ill-conditioned); worst true relative residual %.2e. A direct solver does no better; check residuals().",
-                            self._stats["backward_accepted"], self._stats.get("max_rel_res", 0.0))
-            if self._stats.get("stagnated_solves") or (self._stats.get("max_rel_res", 0.0) > 10.0 * ksp_rtol and not self._stats.get("backward_accepted")):
-                logger.warning("Inner solves stagnated above the requested tolerance: worst true relative residual %.2e (ksp_rtol %.1e, %d "
-                               "solves accepted at the rounding floor). Eigenpairs are those of an inexactly applied operator; check "
-                               "residuals().", self._stats.get("max_rel_res", 0.0), ksp_rtol, self._stats.get("stagnated_solves", 0))
-        finally:
-            basis = None
-            op = None
+    def _collect(self, run: dict) -> None:
+        """Third part of :meth:`solve`: eigenpairs in the caller's numbering and order, statistics, warnings."""
+        prep = self._prepared
+        ctx, n, sinvert, sigma, perm = prep["ctx"], prep["n"], prep["sinvert"], prep["sigma"], prep["perm"]
+        cayley, nu, which, ksp_rtol = prep["cayley"], run["nu"], run["which"], run["ksp_rtol"]
+        op, basis, res, part = run["op"], run["basis"], run["res"], prep["part"]
+        use_lanczos, fallback = run["use_lanczos"], run["fallback"]
+        lam_key = _lambda_rank_key(which, self._target)
+        tiny = np.finfo(float).tiny
+        if cayley:  # theta = (lambda + nu) / (lambda - sigma)
+            back = lambda th: (sigma * th + nu) / np.where(th == 1.0, 1.0 + 1e-300, th - 1.0)  # noqa: E731
+        elif sinvert:  # theta = 1 / (lambda - sigma)
+            back = lambda th: sigma + 1.0 / np.where(th == 0, tiny, th)  # noqa: E731
+        else:
+            back = lambda th: th + sigma  # noqa: E731
+        imag_norms = getattr(basis, "imag_norms", None)  # set when the device already put the vectors into canonical phase
+        theta = res.theta
+        lam = res.lam if use_lanczos else back(np.asarray(theta, dtype=np.complex128))
+        if part is None:
+            X = res.vectors
+        else:
+            vecs = part.unpad_vector(res.vectors)
+            X = np.empty_like(vecs)
+            X[perm, :] = vecs
+        self._stats = op.stats()
+        self._stats["krylov_restarts"] = res.restarts
+        self._stats["method"] = "lanczos" if use_lanczos else "arnoldi"
+        self._stats["basis_bytes"] = int(run["basis_bytes"])
+        if self._symmetric and not use_lanczos:
+            self._stats["symmetric_fallback"] = fallback
+        if res.history and "seconds_dense" in res.history[-1]:  # the library's loop times its phases
+            self._stats.update({k: res.history[-1][k] for k in ("seconds_expand", "seconds_dense", "seconds_restart")})
+        if run.get("lockstep") is not None:  # (a member of a lockstep group: Solver.eigen.solve_batch)
+            self._stats.update(run["lockstep"])
+        if part is not None:
+            now = ctx.comm_stats()
+            last = getattr(self, "_comm_seen", {"allgather_calls": 0, "allgather_bytes_received": 0})
+            self._stats.update({k: now[k] - last[k] for k in now})  # of this solve
+            self._comm_seen = now
+            self._stats["ranks"] = part.nranks
+        if self._stats.get("pc_fallback"):
+            logger.warning("The exact LU did not fit the device memory: the inner solves ran ILU(%d)-preconditioned GMRES instead.",
+                           prep["levels"])
+        if self._stats.get("backward_accepted"):
+            logger.info("%d inner solves were accepted on their backward error (the shift lies next to eigenvalues: A - sigma M is "
+                        "ill-conditioned); worst true relative residual %.2e. A direct solver does no better; check residuals().",
+                        self._stats["backward_accepted"], self._stats.get("max_rel_res", 0.0))
+        if self._stats.get("stagnated_solves") or (self._stats.get("max_rel_res", 0.0) > 10.0 * ksp_rtol and not self._stats.get("backward_accepted")):
+            logger.warning("Inner solves stagnated above the requested tolerance: worst true relative residual %.2e (ksp_rtol %.1e, %d "
+                           "solves accepted at the rounding floor). Eigenpairs are those of an inexactly applied operator; check "
+                           "residuals().", self._stats.get("max_rel_res", 0.0), ksp_rtol, self._stats.get("stagnated_solves", 0))
         self._real_vectors = use_lanczos
         order = np.argsort(lam_key(lam), kind="stable")
         self._eigenvalues = lam[order]
@@ -1088,6 +1160,13 @@ class iEpsSolver:
     def stats(self) -> dict:
         """Counters of the last solve (outer applies, inner iterations, kernel launches, factor/solve seconds)."""
         return dict(self._stats)
+
+
+def _native_driver() -> bool:
+    """Whether the outer iteration is the library's (``lsa_krylov_solve``) and not its Python test double (``LSA_KS_DRIVER=python``)."""
+    import os
+
+    return os.environ.get("LSA_KS_DRIVER", "native") != "python"
 
 
 class SharedContext:

@@ -456,6 +456,8 @@ __device__ __forceinline__ double parts_sum(const double* __restrict__ nrm_part,
 
 // DELAYED (the DCGS2 step, see dcgs_update_kernel): w is the vector projected once, left unscaled; t <- M w, and workgroup 0
 // writes ||w|| from the update's partials into hout[0] (h1, h2, vnext unused)
+// (cgs_tail_batch_kernel below carries a copy of this kernel's DELAYED body for the rounds of a lockstep group, whose problems must
+//  return the bits of this kernel: a change to the DELAYED path here is a change there, statement for statement)
 template <typename MT, int LPR, bool DELAYED = false>
 __global__ __launch_bounds__(kThreads) void cgs_tail_kernel(int32_t n, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
                                                             const MT* __restrict__ mval, const cplx* __restrict__ cval,
@@ -539,6 +541,103 @@ __global__ __launch_bounds__(kThreads) void cgs_tail_kernel(int32_t n, const int
     if (threadIdx.x < 2) chk_part[2 * blockIdx.x + threadIdx.x] = (csum[0][threadIdx.x] + csum[1][threadIdx.x]) + (csum[2][threadIdx.x] + csum[3][threadIdx.x]);
 }
 
+// The per-problem operands of the batched DCGS2 launches (a lockstep round of up to kKrylovGroupMax problems, lsa_krylov_solve_batch),
+// passed by value as NdSweepPtrs is for the sweeps; the problem is the grid's z.
+struct DcgsBatchArgs {  // reduction and update
+    cplx* V[kKrylovGroupMax];
+    const cplx* y[kKrylovGroupMax];
+    cplx* part[kKrylovGroupMax];
+    cplx* slot[kKrylovGroupMax];
+    double* nrm_part[kKrylovGroupMax];
+    int32_t j[kKrylovGroupMax];      // the problem's own step: problems of a round stand at different j
+    int32_t first[kKrylovGroupMax];
+};
+struct TailBatchArgs {  // (16 x 10 pointers: 1280 bytes of kernel arguments)
+    const int32_t* rp[kKrylovGroupMax];
+    const int32_t* ci[kKrylovGroupMax];
+    const void* mval[kKrylovGroupMax];
+    const cplx* cval[kKrylovGroupMax];
+    const cplx* w[kKrylovGroupMax];  // V[:, j + 1] of the problem
+    const cplx* y[kKrylovGroupMax];
+    const double* nrm_part[kKrylovGroupMax];
+    cplx* t[kKrylovGroupMax];
+    cplx* hout[kKrylovGroupMax];     // slot + 2 lds + 2
+    double* chk_part[kKrylovGroupMax];
+};
+
+// The DELAYED tail of up to kKrylovGroupMax problems in one launch: grid (tail parts, 1, problems).  Its body is a copy of
+// cgs_tail_kernel<MT, LPR, true>'s, statement for statement (the same lane partition, order of sums and fma sequence), not a
+// shared device function: with the body shared the compiler gave the solo instances other registers.
+template <typename MT, int LPR>
+__global__ __launch_bounds__(kThreads) void cgs_tail_batch_kernel(int32_t n, int nparts, TailBatchArgs a) {
+    __shared__ double smem[4];
+    __shared__ double csum[4][2];
+    const int z = blockIdx.z;
+    const int32_t* __restrict__ rp = a.rp[z];
+    const int32_t* __restrict__ ci = a.ci[z];
+    const MT* __restrict__ mval = (const MT*)a.mval[z];
+    const cplx* __restrict__ cval = a.cval[z];
+    const cplx* __restrict__ w = a.w[z];
+    const cplx* __restrict__ y = a.y[z];
+    cplx* t = a.t[z];
+    if (blockIdx.x == 0) {
+        const double tsum = parts_sum(a.nrm_part[z], nparts, smem);
+        if (threadIdx.x == 0) s_from(a.hout[z][0], sqrt(tsum), 0.0);
+    }
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t lane = (int32_t)(gid % LPR);
+    const int64_t row_stride = ((int64_t)gridDim.x * blockDim.x) / LPR;
+    double rw = 0.0, rb = 0.0;
+    for (int64_t row = gid / LPR; row < n; row += row_stride) {
+        const int32_t p0 = rp[row], p1 = rp[row + 1];
+        cplx am = cplx{0.0, 0.0}, ac = cplx{0.0, 0.0};
+        for (int32_t p = p0 + lane; p < p1; p += 3 * LPR) {
+            int32_t c[3];
+            MT vm[3];
+            cplx vc[3], xw[3], xy[3];
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                const bool in = p + u * LPR < p1;
+                c[u] = in ? ci[p + u * LPR] : 0;
+                vm[u] = in ? mval[p + u * LPR] : scalar_traits<MT>::zero();
+                vc[u] = in ? cval[p + u * LPR] : cplx{0.0, 0.0};
+            }
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                const bool in = p + u * LPR < p1;
+                xw[u] = in ? w[c[u]] : cplx{0.0, 0.0};
+                xy[u] = in ? y[c[u]] : cplx{0.0, 0.0};
+            }
+#pragma unroll
+            for (int u = 0; u < 3; ++u)
+                if (p + u * LPR < p1) {
+                    fma_acc(am, vm[u], xw[u]);
+                    fma_acc(ac, vc[u], xy[u]);
+                }
+        }
+#pragma unroll
+        for (int m = LPR / 2; m > 0; m >>= 1) {
+            am = s_add(am, cplx{__shfl_xor(am.re, m, 64), __shfl_xor(am.im, m, 64)});
+            ac = s_add(ac, cplx{__shfl_xor(ac.re, m, 64), __shfl_xor(ac.im, m, 64)});
+        }
+        if (lane == 0) {
+            const cplx told = t[row];
+            rw += s_abs2(s_sub(told, ac));
+            rb += s_abs2(told);
+            t[row] = am;
+        }
+    }
+    rw = wave_sum_dpp(rw);
+    rb = wave_sum_dpp(rb);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        csum[wave][0] = rw;
+        csum[wave][1] = rb;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) a.chk_part[z][2 * blockIdx.x + threadIdx.x] = (csum[0][threadIdx.x] + csum[1][threadIdx.x]) + (csum[2][threadIdx.x] + csum[3][threadIdx.x]);
+}
+
 // checks[2 s], checks[2 s + 1] = the sums of slot s's pairs (one workgroup per slot, fixed order)
 __global__ __launch_bounds__(kThreads) void cgs_tail_checks_kernel(int nparts, const double* __restrict__ parts, double* __restrict__ checks) {
     __shared__ double smem[4];
@@ -570,14 +669,14 @@ __global__ __launch_bounds__(kThreads) void cgs_tail_checks_kernel(int nparts, c
 // makes V[:, j] final.  Slot of a step (complex entries, lds = ncv): a at [0, j), b at [lds, lds + j), nu at 2 lds, c at
 // 2 lds + 1, ||w|| at 2 lds + 2.
 template <bool Y>
-__global__ __launch_bounds__(kThreads) void dcgs_dot_kernel(int64_t n, int jc, int64_t rows_per_block, const cplx* __restrict__ V, int64_t ldv,
-                                                            const cplx* __restrict__ y, cplx* __restrict__ part, int ldp,
-                                                            const cplx* __restrict__ chk_b, const cplx* __restrict__ chk_z, double* __restrict__ chk_part) {
+__device__ __forceinline__ void dcgs_dot_body(const int bx, const int by, int64_t n, int jc, int64_t rows_per_block, const cplx* __restrict__ V,
+                                              int64_t ldv, const cplx* __restrict__ y, cplx* __restrict__ part, int ldp,
+                                              const cplx* __restrict__ chk_b, const cplx* __restrict__ chk_z, double* __restrict__ chk_part) {
     __shared__ cplx wsum[4][2 * kColTile];
     __shared__ double dsm[4][2];
     const cplx* __restrict__ p = V + (int64_t)(jc - 1) * ldv;
-    const int chunk = blockIdx.x;
-    const int c0 = blockIdx.y * kColTile;
+    const int chunk = bx;
+    const int c0 = by * kColTile;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t r0 = (int64_t)chunk * rows_per_block;
     const int64_t r1 = (r0 + rows_per_block < n) ? r0 + rows_per_block : n;
@@ -643,7 +742,7 @@ __global__ __launch_bounds__(kThreads) void dcgs_dot_kernel(int64_t n, int jc, i
         }
     }
     double rw = 0.0, rb = 0.0;
-    const bool chk = chk_part != nullptr && blockIdx.y == 0;
+    const bool chk = chk_part != nullptr && by == 0;
     if (chk) {
         for (int64_t i = r0 + threadIdx.x; i < r1; i += kThreads) {
             const cplx bi = chk_b[i];
@@ -673,21 +772,38 @@ __global__ __launch_bounds__(kThreads) void dcgs_dot_kernel(int64_t n, int jc, i
     }
 }
 
+template <bool Y>
+__global__ __launch_bounds__(kThreads) void dcgs_dot_kernel(int64_t n, int jc, int64_t rows_per_block, const cplx* __restrict__ V, int64_t ldv,
+                                                            const cplx* __restrict__ y, cplx* __restrict__ part, int ldp,
+                                                            const cplx* __restrict__ chk_b, const cplx* __restrict__ chk_z, double* __restrict__ chk_part) {
+    dcgs_dot_body<Y>((int)blockIdx.x, (int)blockIdx.y, n, jc, rows_per_block, V, ldv, y, part, ldp, chk_b, chk_z, chk_part);
+}
+
+// the reductions of a round in one launch: grid (chunks, column tiles of the round's largest j, problems); a workgroup whose
+// column tile lies beyond its own problem's j returns as a whole, before any barrier
+__global__ __launch_bounds__(kThreads) void dcgs_dot_batch_kernel(int64_t n, int64_t rows_per_block, int64_t ldv, int ldp, DcgsBatchArgs a) {
+    const int z = blockIdx.z;
+    const int jc = a.j[z] + 1;
+    if ((int)blockIdx.y * kColTile >= jc) return;
+    dcgs_dot_body<true>((int)blockIdx.x, (int)blockIdx.y, n, jc, rows_per_block, a.V[z], ldv, a.y[z], a.part[z], ldp, (const cplx*)nullptr,
+                        (const cplx*)nullptr, (double*)nullptr);
+}
+
 // Workgroup = 64 rows, four lanes per row (lane class q takes the columns c = q mod 4), the first eight basis entries of a
 // thread requested before the coefficients exist: the layout and the load schedule of cgs_axpy_kernel, with two sums per row
 // (Q a and Q b) from one pass over Q.
 template <bool Y>
-__global__ __launch_bounds__(kThreads) void dcgs_update_kernel(int64_t n, int j, cplx* V, int64_t ldv, const cplx* __restrict__ part, int nchunks,
-                                                               int ldp, const cplx* __restrict__ y, int first, double* __restrict__ nrm_part,
-                                                               cplx* __restrict__ slot, int lds, const double* __restrict__ chk_part,
-                                                               double* __restrict__ chk_out) {
+__device__ __forceinline__ void dcgs_update_body(const int bx, int64_t n, int j, cplx* V, int64_t ldv, const cplx* __restrict__ part, int nchunks,
+                                                 int ldp, const cplx* __restrict__ y, int first, double* __restrict__ nrm_part,
+                                                 cplx* __restrict__ slot, int lds, const double* __restrict__ chk_part,
+                                                 double* __restrict__ chk_out) {
     __shared__ double wn[4];
     __shared__ cplx hs[2 * kFuseCols];  // a, alpha at [0, j]; b, beta at kFuseCols + [0, j]
     __shared__ double nu_s;
     __shared__ cplx c_s;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = lane >> 4;
-    const int64_t i = (int64_t)blockIdx.x * 64 + wave * 16 + (lane & 15);
+    const int64_t i = (int64_t)bx * 64 + wave * 16 + (lane & 15);
     cplx v0[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) v0[u] = (i < n && q + 4 * u < j) ? V[i + (int64_t)(q + 4 * u) * ldv] : cplx{0.0, 0.0};
@@ -713,7 +829,7 @@ __global__ __launch_bounds__(kThreads) void dcgs_update_kernel(int64_t n, int j,
             }
             hs[t] = acc;
         }
-        if (chk_out && blockIdx.x == 0 && threadIdx.x < 2) {
+        if (chk_out && bx == 0 && threadIdx.x < 2) {
             double a = 0.0;
             for (int k = 0; k < nchunks; ++k) a += chk_part[2 * k + threadIdx.x];
             chk_out[threadIdx.x] = a;
@@ -747,7 +863,7 @@ __global__ __launch_bounds__(kThreads) void dcgs_update_kernel(int64_t n, int j,
     __syncthreads();
     const double nu = nu_s, inv = 1.0 / nu;
     const cplx cc = c_s;
-    if (blockIdx.x == 0) {
+    if (bx == 0) {
         for (int c = threadIdx.x; c < j; c += kThreads) {
             slot[c] = first ? cplx{0.0, 0.0} : hs[c];
             if constexpr (Y) slot[lds + c] = hs[kFuseCols + c];
@@ -804,8 +920,23 @@ __global__ __launch_bounds__(kThreads) void dcgs_update_kernel(int64_t n, int j,
         nrm = wave_sum_dpp(nrm);
         if (lane == 0) wn[wave] = nrm;
         __syncthreads();
-        if (threadIdx.x == 0) nrm_part[blockIdx.x] = (wn[0] + wn[1]) + (wn[2] + wn[3]);
+        if (threadIdx.x == 0) nrm_part[bx] = (wn[0] + wn[1]) + (wn[2] + wn[3]);
     }
+}
+
+template <bool Y>
+__global__ __launch_bounds__(kThreads) void dcgs_update_kernel(int64_t n, int j, cplx* V, int64_t ldv, const cplx* __restrict__ part, int nchunks,
+                                                               int ldp, const cplx* __restrict__ y, int first, double* __restrict__ nrm_part,
+                                                               cplx* __restrict__ slot, int lds, const double* __restrict__ chk_part,
+                                                               double* __restrict__ chk_out) {
+    dcgs_update_body<Y>((int)blockIdx.x, n, j, V, ldv, part, nchunks, ldp, y, first, nrm_part, slot, lds, chk_part, chk_out);
+}
+
+// the updates of a round in one launch: grid (row blocks, 1, problems)
+__global__ __launch_bounds__(kThreads) void dcgs_update_batch_kernel(int64_t n, int64_t ldv, int nchunks, int ldp, int lds, DcgsBatchArgs a) {
+    const int z = blockIdx.z;
+    dcgs_update_body<true>((int)blockIdx.x, n, a.j[z], a.V[z], ldv, a.part[z], nchunks, ldp, a.y[z], a.first[z], a.nrm_part[z], a.slot[z], lds,
+                           (const double*)nullptr, (double*)nullptr);
 }
 
 // the provisional ||w|| of a DCGS2 step where no tail launch sums it (one workgroup: the sum of cgs_tail_kernel's workgroup 0)
@@ -1439,4 +1570,61 @@ int k_dcgs2_tail(lsa_ctx* ctx, int64_t n, int j, const void* V, int64_t ldv, con
                            (const double*)M->val, (const cplx*)C->val, w, (const cplx*)y, (const double*)nrm_part, blocks, (cplx*)nullptr, (cplx*)t, 0,
                            (const cplx*)nullptr, (const cplx*)nullptr, nout, tail_part);
     return check_launch(ctx, "dcgs2_tail");
+}
+
+// ---- the batched forms: one round of a lockstep group (lsa_krylov_solve_batch) ---------------------------------------------------
+// The reduction and the update of step j[z] of problem z (tail form: no check rides) for J <= 16 problems of one n in two
+// launches.  Every problem takes the lane partition and the order of sums of k_dcgs2_step: the kernels share its bodies.
+int k_dcgs2_step_batch(lsa_ctx* ctx, int J, int64_t n, const int32_t* j, void* const* V, int64_t ldv, const void* const* y, const int32_t* first,
+                       void* const* slot, int lds, void* const* work) {
+    if (J < 1 || J > kKrylovGroupMax) return lsa_set_error(ctx, LSA_ERR_ARG, "k_dcgs2_step_batch: J = %d outside [1, %d]", J, kKrylovGroupMax);
+    int64_t rpb = 0;
+    int jmax = 0;
+    DcgsBatchArgs a;
+    memset(&a, 0, sizeof a);
+    for (int z = 0; z < J; ++z) {
+        if (j[z] < 0 || j[z] + 1 > lds + 1 || !cgs2_fused_shape(n, j[z] + 1, &rpb) || !y[z])
+            return lsa_set_error(ctx, LSA_ERR_ARG, "k_dcgs2_step_batch: shape outside the fused form (problem %d)", z);
+        jmax = std::max(jmax, (int)j[z]);
+        const FusedWork fw(work[z], 16);
+        a.V[z] = (cplx*)V[z];
+        a.y[z] = (const cplx*)y[z];
+        a.part[z] = (cplx*)fw.part1;
+        a.slot[z] = (cplx*)slot[z];
+        a.nrm_part[z] = fw.nrm_part;
+        a.j[z] = j[z];
+        a.first[z] = first[z];
+    }
+    const int nchunks = (int)((n + rpb - 1) / rpb);
+    const int blocks = (int)((n + 63) / 64);
+    const int ldp = 2 * kFuseCols;
+    hipLaunchKernelGGL(dcgs_dot_batch_kernel, dim3(nchunks, (jmax + 1 + kColTile - 1) / kColTile, J), dim3(kThreads), 0, ctx->stream, n, rpb, ldv, ldp, a);
+    hipLaunchKernelGGL(dcgs_update_batch_kernel, dim3(blocks, 1, J), dim3(kThreads), 0, ctx->stream, n, ldv, nchunks, ldp, lds, a);
+    return check_launch(ctx, "dcgs2_step_batch");
+}
+
+// the tails of those steps in one launch (k_dcgs2_tail per problem); the matrices of a group are all real or all complex
+int k_dcgs2_tail_batch(lsa_ctx* ctx, int J, int64_t n, const int32_t* j, void* const* V, int64_t ldv, const void* const* y, void* const* work,
+                       const lsa_mat* const* M, const lsa_mat* const* C, void* const* t, double* const* tail_part, void* const* slot, int lds) {
+    if (J < 1 || J > kKrylovGroupMax) return lsa_set_error(ctx, LSA_ERR_ARG, "k_dcgs2_tail_batch: J = %d outside [1, %d]", J, kKrylovGroupMax);
+    TailBatchArgs a;
+    memset(&a, 0, sizeof a);
+    for (int z = 0; z < J; ++z) {
+        if (M[z]->dtype != M[0]->dtype) return lsa_set_error(ctx, LSA_ERR_ARG, "k_dcgs2_tail_batch: real and complex M in one round (problem %d)", z);
+        a.rp[z] = C[z]->rp;
+        a.ci[z] = C[z]->ci;
+        a.mval[z] = M[z]->val;
+        a.cval[z] = (const cplx*)C[z]->val;
+        a.w[z] = (const cplx*)V[z] + (size_t)(j[z] + 1) * (size_t)ldv;
+        a.y[z] = (const cplx*)y[z];
+        a.nrm_part[z] = FusedWork(work[z], 16).nrm_part;
+        a.t[z] = (cplx*)t[z];
+        a.hout[z] = (cplx*)slot[z] + 2 * (size_t)lds + 2;
+        a.chk_part[z] = tail_part[z];
+    }
+    const int blocks = (int)((n + 63) / 64);
+    const dim3 grid(k_cgs2_tail_parts(n), 1, J);
+    if (M[0]->dtype == LSA_C128) hipLaunchKernelGGL((cgs_tail_batch_kernel<cplx, 16>), grid, dim3(kThreads), 0, ctx->stream, (int32_t)n, blocks, a);
+    else hipLaunchKernelGGL((cgs_tail_batch_kernel<double, 16>), grid, dim3(kThreads), 0, ctx->stream, (int32_t)n, blocks, a);
+    return check_launch(ctx, "dcgs2_tail_batch");
 }

@@ -11,6 +11,10 @@ int lsa_set_error(lsa_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
+void lsa_name_problem(lsa_ctx* ctx, int32_t z) {
+    if (ctx) ctx->err = "problem " + std::to_string(z) + ": " + ctx->err;
+}
+
 int lsa_ensure_scratch(lsa_ctx* ctx, size_t dbytes, size_t hbytes) {
     if (dbytes > ctx->dscratch_bytes) {
         LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -98,6 +102,15 @@ void lsa_ctx_destroy(lsa_ctx* ctx) {
 
 const char* lsa_last_error(const lsa_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 const char* lsa_ctx_arch(const lsa_ctx* ctx) { return ctx ? ctx->arch.c_str() : ""; }
+
+int lsa_ctx_mem_info(lsa_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes) {
+    if (!ctx || !free_bytes || !total_bytes) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ctx_mem_info: null argument");
+    size_t f = 0, t = 0;
+    LSA_HIP_CHECK(ctx, hipMemGetInfo(&f, &t));
+    *free_bytes = (int64_t)f;
+    *total_bytes = (int64_t)t;
+    return LSA_OK;
+}
 
 int lsa_ctx_synchronize(lsa_ctx* ctx) {
     if (!ctx) return LSA_ERR_ARG;

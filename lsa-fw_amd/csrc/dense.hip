@@ -850,57 +850,114 @@ int lsa_dense_sym_inertia(int32_t n, const double* A, int32_t lda, double tol_re
 
 static_assert(sizeof(lsa_ks_result) == 56 && sizeof(lsa_ks_options) == 88, "lsa_ks_options layout is part of the C-ABI (tests/test_abi.py)");
 
-int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const void* v0, const double* mask, int32_t max_out, void* theta_out,
-                     void* lambda_out, void* X_out, double* est_out, lsa_ks_result* result) {
-    if (!ctx || !k || !o || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve: null argument");
+}  // extern "C"
+
+namespace {
+
+// What the Krylov-Schur iteration keeps per problem: the projected matrix and its Schur form, the vectors kept, the counters, the
+// clock, the generator and the result.  lsa_krylov_solve is the loop over one state, lsa_krylov_solve_batch the loop over J.
+struct KsState {
+    lsa_ctx* ctx;
+    lsa_krylov* k;
+    const lsa_ks_options* o;
+    const double* mask;
+    int32_t max_out;
+    void *theta_out, *lambda_out, *X_out;
+    double* est_out;
+    lsa_ks_result* result;
     int32_t m = 0;
     int64_t n = 0;
-    LSA_CHECK(lsa_krylov_shape(k, &n, &m));
-    if (m > n) return lsa_set_error(ctx, LSA_ERR_ARG, "ncv = %d exceeds the problem size %lld", m, (long long)n);
-    LSA_CHECK(ks_check_options(ctx, "lsa_krylov_solve", o, max_out, theta_out, lambda_out));
-    const int nev = std::min<int>(o->nev, m);
-    const double keep_fraction = ks_keep_fraction(o);
-    const Selector sel{o->which, o->transform, {o->sigma[0], o->sigma[1]}, {o->antishift[0], o->antishift[1]}, {o->target[0], o->target[1]}};
-    Rng rng = ks_rng(o);
-    std::vector<Z> vec((size_t)n);
-    auto random_vector = [&]() {
+    int nev = 0, ldh = 0;
+    double keep_fraction = 0.5;
+    Selector sel;
+    Rng rng;
+    std::vector<Z> vec, H, T, Q, S, b, bq, w;
+    std::vector<double> est, rel, keys;
+    std::vector<int> rank;
+    std::vector<char> select;
+    int kept = 0, restarts = 0;
+    int64_t applies = 0;
+    KsClock clk;
+
+    void random_vector() {
         for (int64_t i = 0; i < n; ++i) {
             rng.normal_pair(vec[(size_t)i].re, vec[(size_t)i].im);
             if (mask && mask[i] == 0.0) vec[(size_t)i] = {0.0, 0.0};
         }
-    };
-    if (v0) {
-        memcpy(vec.data(), v0, (size_t)n * sizeof(Z));
-        if (mask)
-            for (int64_t i = 0; i < n; ++i)
-                if (mask[i] == 0.0) vec[(size_t)i] = {0.0, 0.0};
-    } else {
-        random_vector();
     }
-    LSA_CHECK(lsa_krylov_inject(ctx, k, 0, vec.data()));
-    const int ldh = m + 1;
-    std::vector<Z> H((size_t)ldh * m, Z{0.0, 0.0}), T((size_t)m * m), Q((size_t)m * m), S((size_t)m * m), b((size_t)m), bq((size_t)m), w((size_t)m);
-    std::vector<double> est((size_t)m), rel((size_t)m), keys((size_t)m);
-    std::vector<int> rank((size_t)m);
-    std::vector<char> select((size_t)m);
-    const Mat Hm{H.data(), ldh}, Tm{T.data(), m}, Qm{Q.data(), m}, Sm{S.data(), m};
-    int kept = 0, restarts = 0;
-    int64_t applies = 0;
-    memset(result, 0, sizeof *result);
-    KsClock clk;
-    auto extend = [&](int j, int32_t* bd) {
+    // checks the arguments, injects the start vector, sizes the host arrays
+    int init(const char* who, const void* v0) {
+        LSA_CHECK(lsa_krylov_shape(k, &n, &m));
+        if (m > n) return lsa_set_error(ctx, LSA_ERR_ARG, "ncv = %d exceeds the problem size %lld", m, (long long)n);
+        LSA_CHECK(ks_check_options(ctx, who, o, max_out, theta_out, lambda_out));
+        nev = std::min<int>(o->nev, m);
+        keep_fraction = ks_keep_fraction(o);
+        sel = Selector{o->which, o->transform, {o->sigma[0], o->sigma[1]}, {o->antishift[0], o->antishift[1]}, {o->target[0], o->target[1]}};
+        rng = ks_rng(o);
+        vec.resize((size_t)n);
+        if (v0) {
+            memcpy(vec.data(), v0, (size_t)n * sizeof(Z));
+            if (mask)
+                for (int64_t i = 0; i < n; ++i)
+                    if (mask[i] == 0.0) vec[(size_t)i] = {0.0, 0.0};
+        } else {
+            random_vector();
+        }
+        LSA_CHECK(lsa_krylov_inject(ctx, k, 0, vec.data()));
+        ldh = m + 1;
+        H.assign((size_t)ldh * m, Z{0.0, 0.0});
+        for (auto* a : {&T, &Q, &S}) a->resize((size_t)m * m);
+        for (auto* a : {&b, &bq, &w}) a->resize((size_t)m);
+        for (auto* a : {&est, &rel, &keys}) a->resize((size_t)m);
+        rank.resize((size_t)m);
+        select.resize((size_t)m);
+        memset(result, 0, sizeof *result);
+        return LSA_OK;
+    }
+    int extend(int j, int32_t* bd) {
         LSA_CHECK(lsa_krylov_extend(ctx, k, j, m, H.data(), ldh, bd));
-        if (*bd >= 0) Hm(*bd + 1, *bd) = {0.0, 0.0};
+        if (*bd >= 0) H[(size_t)*bd * ldh + (size_t)*bd + 1] = {0.0, 0.0};
         return (int)LSA_OK;
-    };
-    auto inject_random = [&](int j) {
+    }
+    int inject_random(int j) {
         random_vector();
         return lsa_krylov_inject(ctx, k, j, vec.data());
-    };
-    while (true) {
+    }
+    // the expansion from `kept` to m vectors through the solo code
+    int expand() {
         clk.start();
-        LSA_CHECK(ks_expand(kept, m, &applies, extend, inject_random));
+        LSA_CHECK(ks_expand(kept, m, &applies, [&](int j, int32_t* bd) { return extend(j, bd); }, [&](int j) { return inject_random(j); }));
         clk.lap(clk.expand);
+        return LSA_OK;
+    }
+    // The expansion whose first run of steps the lockstep driver has made (its status and breakdown step, `seconds` of wall time
+    // booked to this problem): what follows a breakdown -- the fresh direction, the rest of the steps -- is the solo code's.
+    // *later_steps: the steps the solo code ran here after that first run (none unless it broke down).
+    int expand_after(int rc0, int32_t bd0, double seconds, int64_t* later_steps) {
+        bool first = true;
+        const int64_t before = applies + (bd0 < 0 ? m - kept : bd0 - kept + 1);
+        *later_steps = 0;
+        clk.start();
+        LSA_CHECK(ks_expand(kept, m, &applies,
+                            [&](int j, int32_t* bd) {
+                                if (!first) return extend(j, bd);
+                                first = false;
+                                LSA_CHECK(rc0);
+                                *bd = bd0;
+                                if (*bd >= 0) H[(size_t)*bd * ldh + (size_t)*bd + 1] = {0.0, 0.0};
+                                return (int)LSA_OK;
+                            },
+                            [&](int j) { return inject_random(j); }));
+        clk.lap(clk.expand);
+        clk.expand += seconds;
+        *later_steps = applies - before;
+        return LSA_OK;
+    }
+    // The body of the loop after an expansion: Ritz pairs, convergence test, then either the result (*done) or the restart.
+    int after_expand(const char* who, bool* done) {
+        const Mat Hm{H.data(), ldh}, Tm{T.data(), m}, Qm{Q.data(), m}, Sm{S.data(), m};
+        *done = false;
+        clk.start();
         for (int c = 0; c < m; ++c) {
             b[(size_t)c] = Hm(m, c);  // b^H: the row under the square part
             for (int r = 0; r < m; ++r) Tm(r, c) = Hm(r, c);
@@ -943,7 +1000,8 @@ int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const
             }
             clk.lap(clk.dense);
             ks_fill_result(result, clk, nconv, nout, restarts, applies, nconv < m ? rel[(size_t)rank[(size_t)nconv]] : 0.0);
-            return k_agree_in_step(ctx, "lsa_krylov_solve");  // (a sharded solve ends with the ranks comparing their exchange counts)
+            *done = true;
+            return k_agree_in_step(ctx, who);  // (a sharded solve ends with the ranks comparing their exchange counts)
         }
         // ---- truncate to the wanted part of the Schur form and restart ----
         int knew = ks_keep_count(m, nconv, keep_fraction);
@@ -968,7 +1026,107 @@ int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const
         }
         kept = knew;
         ++restarts;
+        return LSA_OK;
     }
+};
+
+}  // namespace
+
+extern "C" {
+
+int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const void* v0, const double* mask, int32_t max_out, void* theta_out,
+                     void* lambda_out, void* X_out, double* est_out, lsa_ks_result* result) {
+    if (!ctx || !k || !o || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve: null argument");
+    KsState st{ctx, k, o, mask, max_out, theta_out, lambda_out, X_out, est_out, result};
+    LSA_CHECK(st.init("lsa_krylov_solve", v0));
+    for (bool done = false; !done;) {
+        LSA_CHECK(st.expand());
+        LSA_CHECK(st.after_expand("lsa_krylov_solve", &done));
+    }
+    return LSA_OK;
+}
+
+static_assert(sizeof(lsa_ks_batch_info) == 288, "lsa_ks_batch_info layout is part of the C-ABI (tests/test_lockstep_cpu.py)");
+static_assert(sizeof(((lsa_ks_batch_info*)nullptr)->lockstep_steps) == 8 * kKrylovGroupMax && sizeof(((lsa_ks_batch_info*)nullptr)->solo_steps) == 8 * kKrylovGroupMax,
+              "the per-problem counters of lsa_ks_batch_info hold one entry per problem of a group");
+
+int lsa_krylov_solve_batch(lsa_ctx* ctx, int32_t J, lsa_krylov* const* k, const lsa_ks_options* const* opts, const void* const* v0, int32_t max_out,
+                           void* const* theta_out, void* const* lambda_out, void* const* X_out, double* const* est_out, lsa_ks_result* results,
+                           int32_t* status, lsa_ks_batch_info* info) {
+    if (!ctx || !k || !opts || !results || !status) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve_batch: null argument");
+    if (J < 1 || J > kKrylovGroupMax) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve_batch: J = %d outside [1, %d]", J, kKrylovGroupMax);
+    if (max_out > 0 && (!theta_out || !lambda_out)) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve_batch: output buffers are required");
+    for (int32_t z = 0; z < J; ++z)
+        if (!opts[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve_batch: null options (problem %d)", z);
+    LSA_CHECK(krylov_group_check(ctx, J, k));
+    if (info) memset(info, 0, sizeof *info);
+    std::vector<KsState> st;
+    st.reserve((size_t)J);
+    uint8_t active[kKrylovGroupMax] = {};
+    int32_t kept[kKrylovGroupMax] = {}, bd[kKrylovGroupMax], erc[kKrylovGroupMax];
+    void* Hs[kKrylovGroupMax] = {};
+    int32_t nactive = 0;
+    std::string errs[kKrylovGroupMax];     // the error text of every problem that failed
+    auto leave = [&](int32_t z, int rc) {  // problem z is done: with its result, or with its own error
+        if (rc != LSA_OK && status[z] == LSA_OK) {
+            status[z] = rc;
+            if (errs[z].empty()) errs[z] = ctx->err;  // (krylov_extend_batch has left the text of its own errors)
+        }
+        nactive -= active[z];
+        active[z] = 0;
+    };
+    for (int32_t z = 0; z < J; ++z) {
+        status[z] = LSA_OK;
+        st.push_back(KsState{ctx, k[z], opts[z], nullptr, max_out, theta_out ? theta_out[z] : nullptr, lambda_out ? lambda_out[z] : nullptr,
+                             X_out ? X_out[z] : nullptr, est_out ? est_out[z] : nullptr, &results[z]});
+        active[z] = 1;
+        ++nactive;
+        const int rc = st[(size_t)z].init("lsa_krylov_solve_batch", v0 ? v0[z] : nullptr);
+        if (rc != LSA_OK) {
+            lsa_name_problem(ctx, z);
+            leave(z, rc);
+        }
+        Hs[z] = st[(size_t)z].H.data();
+    }
+    KrylovGroupBuf gb;
+    int grc = nactive > 0 ? krylov_group_alloc(ctx, J, k, &gb) : (memset(&gb, 0, sizeof gb), (int)LSA_OK);
+    while (grc == LSA_OK && nactive > 0) {
+        const int32_t m = st[0].m, na = nactive;
+        for (int32_t z = 0; z < J; ++z) kept[z] = st[(size_t)z].kept;
+        const double t0 = now_s();
+        grc = krylov_extend_batch(ctx, &gb, k, active, kept, m, Hs, m + 1, bd, erc, errs, info);
+        if (grc != LSA_OK) break;
+        const double share = (now_s() - t0) / na;
+        for (int32_t z = 0; z < J; ++z) {
+            if (!active[z]) continue;
+            KsState& s = st[(size_t)z];
+            bool done = false;
+            int64_t later = 0;
+            int rc = s.expand_after(erc[z], bd[z], share, &later);
+            if (info) info->solo_steps[z] += later;  // (what followed a breakdown: the solo code's steps too)
+            if (rc == LSA_OK) rc = s.after_expand("lsa_krylov_solve_batch", &done);
+            if (rc != LSA_OK && erc[z] == LSA_OK) lsa_name_problem(ctx, z);  // (krylov_extend_batch has named its own)
+            if (rc != LSA_OK || done) leave(z, rc);
+        }
+    }
+    krylov_group_free(&gb);
+    if (info && info->rounds > 0) info->launches_per_round = (double)info->launches / (double)info->rounds;
+    if (grc != LSA_OK) {  // the group's own buffers could not be had: an error of every problem that was still going
+        for (int32_t z = 0; z < J; ++z)
+            if (active[z]) status[z] = grc;
+        return grc;
+    }
+    // the context's error text: those of all failed problems in problem order, each naming its problem (the first one's leads)
+    int first_rc = LSA_OK;
+    std::string all;
+    for (int32_t z = 0; z < J; ++z)
+        if (status[z] != LSA_OK) {
+            if (first_rc == LSA_OK) first_rc = status[z];
+            else all += "; ";
+            all += errs[z];
+        }
+    if (first_rc != LSA_OK) ctx->err = all;
+    return first_rc;
 }
 
 int lsa_eigs_sinvert(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, const double sigma[2], int32_t nev, int32_t ncv, double tol, int32_t max_restarts,

@@ -222,6 +222,10 @@ inline bool env_flag(const char* name, bool dflt) {
         if (_rc != LSA_OK) return _rc; \
     } while (0)
 
+// problems of one lockstep group (lsa_krylov_solve_batch): the capacity of the batched DCGS2 argument records (blas.hip), of the
+// batched sweeps (kNdBatchMax, ndlu_internal.h: asserted equal there) and of the per-problem arrays of lsa_ks_batch_info
+constexpr int kKrylovGroupMax = 16;
+
 // ---- kernels launched across translation units --------------------------------------------------------
 // (all launch on ctx->stream and return LSA_OK or a status)
 
@@ -275,6 +279,13 @@ int k_dcgs2_step(lsa_ctx* ctx, int64_t n, int j, void* V, int64_t ldv, const voi
 int k_dcgs2_norm(lsa_ctx* ctx, int64_t n, void* work, void* slot, int lds);
 int k_dcgs2_tail(lsa_ctx* ctx, int64_t n, int j, const void* V, int64_t ldv, const void* y, void* work, const lsa_mat* M, const lsa_mat* C, void* t,
                  double* tail_part, void* slot, int lds);
+// The batched forms of a tail-form DCGS2 step, for the rounds of a lockstep group (lsa_krylov_solve_batch): J <= 16 problems of
+// one n, each at its own step j[z], in two launches (reduction, update) and one (tail); per problem the bits of k_dcgs2_step and
+// k_dcgs2_tail.  work[z]: the problem's fused workspace.
+int k_dcgs2_step_batch(lsa_ctx* ctx, int J, int64_t n, const int32_t* j, void* const* V, int64_t ldv, const void* const* y, const int32_t* first,
+                       void* const* slot, int lds, void* const* work);
+int k_dcgs2_tail_batch(lsa_ctx* ctx, int J, int64_t n, const int32_t* j, void* const* V, int64_t ldv, const void* const* y, void* const* work,
+                       const lsa_mat* const* M, const lsa_mat* const* C, void* const* t, double* const* tail_part, void* const* slot, int lds);
 int k_spmv_plain_subwave_lanes(const lsa_mat* A);  // spmv.hip
 // Out[:, 0:k] = V[:, 0:m] Q   (Q m x k column-major on the device, ldq)
 int k_basis_gemm(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V, int64_t ldv, const void* Q, int ldq,
@@ -295,6 +306,23 @@ int basis_times_host_matrix(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, co
 int direct_solve_enqueue(lsa_ctx* ctx, lsa_op* op, int dtype, const void* rhs, void* y, void* z, void* r, bool refine, double* norms);
 // books one accepted direct solve of relative residual res / bnorm: `products` sparse products besides the refinement's one
 void stats_book_direct_solve(lsa_stats* st, int products, bool refine, double res, double bnorm);
+
+// ---- the lockstep expansion of a group of problems (solver.hip), driven by lsa_krylov_solve_batch (dense.hip) ---------------
+struct KrylovGroupBuf {  // the group's slots, checks and check pairs: cell (round s, problem z) at s J + z
+    int32_t J, slots, nparts;
+    void* Hdev;
+    double *checks, *tail_parts;
+};
+// argument errors of a group: null or foreign workspaces, other shapes, shared workspaces or operators
+int krylov_group_check(lsa_ctx* ctx, int32_t J, lsa_krylov* const* ks);
+int krylov_group_alloc(lsa_ctx* ctx, int32_t J, lsa_krylov* const* ks, KrylovGroupBuf* gb);
+void krylov_group_free(KrylovGroupBuf* gb);
+// lsa_krylov_extend(ks[z], j0[z], j1, Hs[z], ldh) for every active problem z, in lockstep where the plans allow; status[z] and
+// breakdown[z] per problem (an error stops that problem alone; its text, naming the problem, goes to errs[z]); info: counters, or null
+int krylov_extend_batch(lsa_ctx* ctx, KrylovGroupBuf* gb, lsa_krylov* const* ks, const uint8_t* active, const int32_t* j0, int32_t j1, void* const* Hs,
+                        int32_t ldh, int32_t* breakdown, int32_t* status, std::string* errs, lsa_ks_batch_info* info);
+// puts "problem z: " in front of the context's error text
+void lsa_name_problem(lsa_ctx* ctx, int32_t z);
 
 // ---- what the Lanczos iteration (lanczos.hip) needs of a shift-invert operator (solver.hip) -------------------------------
 struct lsa_ndlu;

@@ -134,6 +134,8 @@ struct NdMemoryPlan {
 };
 // budget_entries: scalars the working arena may take (a single front always fits); <= 0: every level in one chunk
 void nd_memory_plan(const NdSymbolic& S, int64_t budget_entries, NdMemoryPlan& P);
+// out[8] as lsa_nd_sym_memory documents it (include/lsa_hip.h), for any analysis
+int nd_memory_report(const NdSymbolic& S, int32_t scalar_bytes, int64_t work_budget_bytes, int64_t* out, int64_t* upd_off, int64_t* work_off, int32_t* chunk_of);
 // equal cut of `count` items over `nranks`: rank's [first, first + size)
 inline void nd_slice(int32_t count, int nranks, int rank, int32_t* first, int32_t* size) {
     const int32_t s = (count + nranks - 1) / std::max(nranks, 1);

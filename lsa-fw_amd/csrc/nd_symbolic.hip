@@ -1120,8 +1120,15 @@ int lsa_nd_sym_info(const lsa_nd_sym* h, int32_t* ntree, int32_t* nlevels, int32
 }
 
 int lsa_nd_sym_memory(const lsa_nd_sym* h, int32_t scalar_bytes, int64_t work_budget_bytes, int64_t* out, int64_t* upd_off, int64_t* work_off, int32_t* chunk_of) {
-    if (!h || !out || (scalar_bytes != 8 && scalar_bytes != 16)) return LSA_ERR_ARG;
-    const NdSymbolic& S = h->S;
+    if (!h) return LSA_ERR_ARG;
+    return nd_memory_report(h->S, scalar_bytes, work_budget_bytes, out, upd_off, work_off, chunk_of);
+}
+
+}  // extern "C"
+
+// the figures of lsa_nd_sym_memory for any analysis (also the one a context holds prepared: lsa_ndlu_prepared_memory)
+int nd_memory_report(const NdSymbolic& S, int32_t scalar_bytes, int64_t work_budget_bytes, int64_t* out, int64_t* upd_off, int64_t* work_off, int32_t* chunk_of) {
+    if (!out || (scalar_bytes != 8 && scalar_bytes != 16)) return LSA_ERR_ARG;
     if (S.order_only) return LSA_ERR_ARG;
     NdMemoryPlan P;
     nd_memory_plan(S, work_budget_bytes > 0 ? work_budget_bytes / scalar_bytes : 0, P);
@@ -1148,6 +1155,8 @@ int lsa_nd_sym_memory(const lsa_nd_sym* h, int32_t scalar_bytes, int64_t work_bu
             for (int32_t q = P.chunk_begin[c]; q < P.chunk_begin[c + 1]; ++q) chunk_of[(size_t)S.lvl_nodes[(size_t)q]] = (int32_t)c;
     return LSA_OK;
 }
+
+extern "C" {
 
 int lsa_nd_sym_export(const lsa_nd_sym* h, int32_t* perm, int32_t* node_start, int32_t* parent, int32_t* level, int32_t* front_size,
                       int32_t* idx) {

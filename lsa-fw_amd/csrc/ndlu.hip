@@ -966,6 +966,13 @@ int lsa_ndlu_inertia(lsa_ctx* ctx, lsa_ndlu* f, int64_t* negative, int64_t* zero
     return LSA_OK;
 }
 
+int lsa_ndlu_prepared_memory(lsa_ctx* ctx, int64_t* out) {
+    if (!ctx || !out) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_prepared_memory: null argument");
+    const lsa_ndlu* c = ctx->nd_cache;
+    if (!c) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_prepared_memory: the context holds no prepared analysis");
+    return nd_memory_report(c->S, (int32_t)esize(c->dtype), 0, out, nullptr, nullptr, nullptr);
+}
+
 int lsa_ndlu_info(const lsa_ndlu* f, int32_t* ntree, int32_t* nlevels, int32_t* max_front, int64_t* factor_entries, int64_t* front_entries,
                   int64_t* apply_bytes, int32_t* apply_launches, double* seconds_analyse, double* seconds_numeric) {
     if (!f) return LSA_ERR_ARG;

@@ -21,6 +21,7 @@ constexpr int kNB = 32;      // pivot columns per block of the Gauss-Jordan inve
 constexpr int kSB = 128;     // ... per super-block of the tournament path (nd_gj_update_kernel)
 constexpr int kTRmin = 256;  // tournament pivoting, smallest first-round chunk: sizes the candidate buffers
 constexpr int kNdBatchMax = 16;  // most problems of one batched solve (lsa_ndlu_solve_batch): the capacity of NdSweepPtrs there
+static_assert(kNdBatchMax == kKrylovGroupMax, "a lockstep round hands all its problems to one batched sweep");
 constexpr int kMCH = 256;        // vector entries per column staged in LDS per pass of a multi-column solve tile (ndlu_multi.hip)
 constexpr int kNdMultiMax = 8;   // most columns of one pass of lsa_ndlu_solve_multi (real vectors; complex ones: 4 -- nd_multi_cap): 16 KB of LDS
 

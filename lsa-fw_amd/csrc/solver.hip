@@ -9,6 +9,8 @@
 #include "lsa_internal.h"
 
 int ilu_check_abort(lsa_ctx* ctx, lsa_ilu* pc);
+bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g);                                                      // ndlu_sweeps.hip
+int ndlu_solve_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, const void** b, void* const* x);  // ndlu_sweeps.hip
 int k_allgather_inplace(lsa_ctx* ctx, void* vec, size_t bytes_per_rank);  // comm.hip
 
 namespace {
@@ -1165,35 +1167,95 @@ static int provisional_column(const HessView& H, int32_t jc, const cplx* sl, boo
 
 static int arnoldi_nonfinite(lsa_ctx* ctx, int32_t j) { return lsa_set_error(ctx, LSA_ERR_NONFINITE, "Arnoldi: non-finite norm at step %d", j); }
 
-// Steps [*j, j1) in batches while the plan pipelines; *j: the first step not done.  Ends early on a breakdown (*breakdown) or
-// when a solve needs the one-step path (k->pipeline goes false; the caller runs the rest there).
-static int extend_pipelined(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, int32_t* jp, int32_t j1, int32_t* breakdown) {
+// where an expansion stands: the first step not done, and (delayed form) whether V[:, j] is projected once only, column j - 1 of H
+// provisional.  extend_pipelined can be entered with any such state: the lockstep driver hands a problem over this way.
+struct ExtendCursor {
+    int32_t j;
+    bool pending;
+};
+
+// what a pipelined batch needs before its first step is queued: the operator's solve vectors and, in the tail form, its pairs
+static int pipelined_prepare(lsa_ctx* ctx, lsa_krylov* k, const StepPlan& plan) {
     lsa_op* op = k->op;
-    StepPlan plan = step_plan(ctx, k);
     if (!op->gw_ready) {
         LSA_CHECK(op->gw.alloc(ctx, op->n, std::max(1, std::min({op->opts.ksp_restart, op->opts.ksp_maxit, 40})), LSA_C128));
         op->gw_ready = true;
     }
-    const int32_t slots = std::max(k->batch, 1);
-    const size_t colb = krylov_slot_bytes(k->ncv);
-    LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)slots * (colb + 2 * sizeof(double))));
     if (plan.tail && !k->tail_parts) {
+        const int32_t slots = std::max(k->batch, 1);
         k->tail_nparts = k_cgs2_tail_parts(k->n);
         LSA_HIP_ALLOC(ctx, hipMalloc(&k->w2, (size_t)k->n * 16));
         LSA_HIP_ALLOC(ctx, hipMalloc((void**)&k->tail_parts, (size_t)slots * 2 * (size_t)k->tail_nparts * sizeof(double)));
     }
-    const bool delayed = plan.orth == Orth::dcgs2;
+    return LSA_OK;
+}
+
+// The accept loop over the nb steps of one read-back, from step c->j on: slot s at slots + s * slot_stride, its check pair at
+// chk + s * chk_stride.  Advances the cursor by the steps accepted (*accepted); fewer than nb: a solve missed rtol and op->refine
+// or k->pipeline has changed.  A breakdown sets *breakdown and leaves the cursor alone (the caller restarts from there).
+static int accept_steps(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, bool delayed, const char* slots, size_t slot_stride, const double* chk,
+                        size_t chk_stride, int32_t nb, ExtendCursor* c, int32_t* breakdown, int32_t* accepted_out) {
+    lsa_op* op = k->op;
     const double rtol = op->opts.ksp_rtol;
-    char* host = (char*)ctx->pinned;
     cplx* hwork = (cplx*)k->hcol.data();  // (ncv + 2 complex numbers)
+    const int32_t j = c->j;
+    int32_t accepted = 0;
+    *accepted_out = 0;
+    for (int32_t s = 0; s < nb; ++s, ++accepted) {
+        const cplx* hc = (const cplx*)(slots + (size_t)s * slot_stride);
+        const bool first = s == 0 && !c->pending;
+        if (delayed && !first) {
+            // the step's a and nu depend on V alone, not on its solve: they finish column j + s - 1 and V[:, j + s] even
+            // when this step is cut below (it is queued again with V[:, j + s] final)
+            c->pending = false;
+            const int what = finish_column(H, j + s, hc);
+            if (what < 0) return arnoldi_nonfinite(ctx, j + s - 1);
+            if (what > 0) {
+                *breakdown = j + s - 1;
+                return LSA_OK;
+            }
+        }
+        const double beta0 = std::sqrt(chk[(size_t)s * chk_stride]), bnorm = std::sqrt(chk[(size_t)s * chk_stride + 1]);
+        if (!(beta0 <= rtol * bnorm)) {
+            // a direct solve missed rtol: from here on every queued step carries one refinement step (large 3D factors; the
+            // steps of this batch from s on are queued again).  Refined and still short of rtol: this solve needs the judgement
+            // of the one-step path (backward error next to an eigenvalue, GMRES), and so will its neighbours: the rest of this
+            // basis runs one step at a time
+            if (!op->refine && std::isfinite(beta0)) op->refine = true;
+            else k->pipeline = false;
+            break;
+        }
+        stats_book_direct_solve(&op->st, op->Kmul ? 2 : 1, op->refine, beta0, bnorm);
+        const int what = delayed ? provisional_column(H, j + s, hc, first, hwork) : take_column(H, j + s, hc);
+        c->pending = delayed;
+        if (what < 0) return arnoldi_nonfinite(ctx, j + s);
+        if (what > 0) {  // the steps queued behind a breakdown worked on noise: the caller restarts from here
+            *breakdown = j + s;
+            return LSA_OK;
+        }
+    }
+    c->j = j + accepted;
+    *accepted_out = accepted;
+    if (accepted < nb) k->t_for = -1;  // the steps behind the one that stopped the batch ran on; t is theirs
+    return LSA_OK;
+}
+
+// Steps [c->j, j1) in batches while the plan pipelines; c: where the expansion stands on entry and on return.  Ends early on a
+// breakdown (*breakdown) or when a solve needs the one-step path (k->pipeline goes false; the caller runs the rest there).
+static int extend_pipelined(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, ExtendCursor* c, int32_t j1, int32_t* breakdown) {
+    StepPlan plan = step_plan(ctx, k);
+    LSA_CHECK(pipelined_prepare(ctx, k, plan));
+    const int32_t slots = std::max(k->batch, 1);
+    const size_t colb = krylov_slot_bytes(k->ncv);
+    LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)slots * (colb + 2 * sizeof(double))));
+    const bool delayed = plan.orth == Orth::dcgs2;
+    char* host = (char*)ctx->pinned;
     k->t_for = -1;  // (op->t is anybody's between calls)
-    bool pending = false;  // delayed form: V[:, j] is projected once, column j - 1 of H provisional
-    int32_t j = *jp;
-    for (; j < j1 && plan.pipelined; plan = step_plan(ctx, k)) {
-        const int32_t nb = std::min<int32_t>(slots, j1 - j);
+    for (; c->j < j1 && plan.pipelined; plan = step_plan(ctx, k)) {
+        const int32_t nb = std::min<int32_t>(slots, j1 - c->j);
         const double tq = now_s();
         for (int32_t s = 0; s < nb; ++s) {
-            const int rc = krylov_enqueue_step(ctx, k, plan, j + s, s, s == 0 && !pending);
+            const int rc = krylov_enqueue_step(ctx, k, plan, c->j + s, s, s == 0 && !c->pending);
             if (rc != LSA_OK) {
                 (void)hipStreamSynchronize(ctx->stream);
                 return rc;
@@ -1205,51 +1267,18 @@ static int extend_pipelined(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, int3
         const double tw = now_s();
         LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         if (krylov_switches().timing) fprintf(stderr, "[lsa_krylov] %d steps queued in %.3f ms, waited %.3f ms\n", nb, 1e3 * (tw - tq), 1e3 * (now_s() - tw));
-        const double* chk = (const double*)(host + (size_t)slots * colb);
         int32_t accepted = 0;
-        for (int32_t s = 0; s < nb; ++s, ++accepted) {
-            const cplx* hc = (const cplx*)(host + (size_t)s * colb);
-            const bool first = s == 0 && !pending;
-            if (delayed && !first) {
-                // the step's a and nu depend on V alone, not on its solve: they finish column j + s - 1 and V[:, j + s] even
-                // when this step is cut below (it is queued again with V[:, j + s] final)
-                pending = false;
-                const int what = finish_column(H, j + s, hc);
-                if (what < 0) return arnoldi_nonfinite(ctx, j + s - 1);
-                if (what > 0) {
-                    *breakdown = j + s - 1;
-                    return LSA_OK;
-                }
-            }
-            const double beta0 = std::sqrt(chk[2 * s]), bnorm = std::sqrt(chk[2 * s + 1]);
-            if (!(beta0 <= rtol * bnorm)) {
-                // a direct solve missed rtol: from here on every queued step carries one refinement step (large 3D factors; the
-                // steps of this batch from s on are queued again).  Refined and still short of rtol: this solve needs the judgement
-                // of the one-step path (backward error next to an eigenvalue, GMRES), and so will its neighbours: the rest of this
-                // basis runs one step at a time
-                if (!op->refine && std::isfinite(beta0)) op->refine = true;
-                else k->pipeline = false;
-                break;
-            }
-            stats_book_direct_solve(&op->st, op->Kmul ? 2 : 1, op->refine, beta0, bnorm);
-            const int what = delayed ? provisional_column(H, j + s, hc, first, hwork) : take_column(H, j + s, hc);
-            pending = delayed;
-            if (what < 0) return arnoldi_nonfinite(ctx, j + s);
-            if (what > 0) {  // the steps queued behind a breakdown worked on noise: the caller restarts from here
-                *breakdown = j + s;
-                return LSA_OK;
-            }
-        }
-        j += accepted;
-        if (accepted < nb) k->t_for = -1;  // the steps behind the one that stopped the batch ran on; t is theirs
+        LSA_CHECK(accept_steps(ctx, k, H, delayed, host, colb, (const double*)(host + (size_t)slots * colb), 2, nb, c, breakdown, &accepted));
+        if (*breakdown >= 0) return LSA_OK;
     }
-    *jp = j;
-    if (pending) {
+    if (c->pending) {
         // the flush: the reduction and the update without a solve make V[:, j1] and column j1 - 1 final, so that the restart,
         // the Ritz vectors and the next call see what CGS2 leaves
+        const int32_t j = c->j;
         LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, nullptr, 0, k->Hdev, k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
         LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, k->Hdev, colb, hipMemcpyDeviceToHost, ctx->stream));
         LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        c->pending = false;
         const int what = finish_column(H, j, (const cplx*)host);
         if (what < 0) return arnoldi_nonfinite(ctx, j - 1);
         if (what > 0) *breakdown = j - 1;
@@ -1276,19 +1305,219 @@ static int extend_one_step(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, int32
     return LSA_OK;
 }
 
+// the steps from the cursor to j1 through the solo code: pipelined batches while the plan allows, then one step at a time
+static int extend_rest(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, ExtendCursor* c, int32_t j1, int32_t* bd) {
+    int rc = LSA_OK;
+    if (step_plan(ctx, k).pipelined) rc = extend_pipelined(ctx, k, H, c, j1, bd);
+    if (rc == LSA_OK && *bd < 0) rc = extend_one_step(ctx, k, H, c->j, j1, bd);
+    return rc;
+}
+
 int lsa_krylov_extend(lsa_ctx* ctx, lsa_krylov* k, int32_t j0, int32_t j1, void* H, int32_t ldh, int32_t* breakdown) {
     if (!ctx || !k || !H) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_extend: null argument");
     if (j0 < 0 || j1 < j0 || j1 > k->ncv || ldh < j1 + 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_extend: bad step range [%d, %d) for ncv %d", j0, j1, k->ncv);
     const double t0 = now_s();
     const HessView Hv{(cplx*)H, ldh, j0, k->ncv};
-    int32_t j = j0, bd = -1;
-    int rc = LSA_OK;
-    if (step_plan(ctx, k).pipelined) rc = extend_pipelined(ctx, k, Hv, &j, j1, &bd);
-    if (rc == LSA_OK && bd < 0) rc = extend_one_step(ctx, k, Hv, j, j1, &bd);
+    ExtendCursor c{j0, false};
+    int32_t bd = -1;
+    const int rc = extend_rest(ctx, k, Hv, &c, j1, &bd);
     if (breakdown) *breakdown = bd;
     k->op->st.seconds_solve += now_s() - t0;
     return rc;
 }
+
+}  // extern "C"
+
+// ---- lockstep expansion of a group (lsa_krylov_solve_batch, dense.hip) ---------------------------------------------------------
+// Problems whose plan is the pipelined DCGS2 tail form on factors of one analysis advance together: a round queues one step of
+// every such problem that still has one in this read-back period -- M v_j where the previous tail did not leave it, ONE batched
+// sweep pair (ndlu_solve_batch_dev), ONE batched reduction, update and tail -- and one read-back covers up to k->batch rounds of
+// all of them (their slots, pairs and checks lie round-major in the group's buffers: two copies, one synchronisation).  The
+// accept loop is accept_steps per problem over its own slots.  A problem whose plan changes (a miss of ksp_rtol, k->pipeline
+// going false), that breaks down or is not eligible finishes its expansion through extend_rest from its cursor, exactly as its
+// solo solve continues from there; it is asked again at the next expansion.
+int krylov_group_alloc(lsa_ctx* ctx, int32_t J, lsa_krylov* const* ks, KrylovGroupBuf* gb) {
+    memset(gb, 0, sizeof *gb);
+    gb->J = J;
+    gb->slots = std::max(ks[0]->batch, 1);
+    gb->nparts = k_cgs2_tail_parts(ks[0]->n);
+    const size_t cells = (size_t)J * (size_t)gb->slots;
+    LSA_HIP_ALLOC(ctx, hipMalloc(&gb->Hdev, cells * krylov_slot_bytes(ks[0]->ncv)));
+    LSA_HIP_ALLOC(ctx, hipMalloc((void**)&gb->checks, cells * 2 * sizeof(double)));
+    LSA_HIP_ALLOC(ctx, hipMalloc((void**)&gb->tail_parts, cells * 2 * (size_t)gb->nparts * sizeof(double)));
+    // (cells of a round without a step of their problem are summed and copied with the others and never looked at: finite or not)
+    LSA_HIP_CHECK(ctx, hipMemsetAsync(gb->tail_parts, 0, cells * 2 * (size_t)gb->nparts * sizeof(double), ctx->stream));
+    return LSA_OK;
+}
+
+void krylov_group_free(KrylovGroupBuf* gb) {
+    for (void* p : {gb->Hdev, (void*)gb->checks, (void*)gb->tail_parts})
+        if (p) (void)hipFree(p);
+    memset(gb, 0, sizeof *gb);
+}
+
+int krylov_group_check(lsa_ctx* ctx, int32_t J, lsa_krylov* const* ks) {
+    for (int32_t z = 0; z < J; ++z) {
+        if (!ks[z] || !ks[z]->op) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve_batch: null workspace (problem %d)", z);
+        if (ks[z]->ctx != ctx) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve_batch: the workspace of problem %d lives in another context", z);
+        if (ks[z]->n != ks[0]->n || ks[z]->ncv != ks[0]->ncv || ks[z]->batch != ks[0]->batch)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve_batch: problem %d has another shape (n = %lld, ncv = %d) than problem 0 (n = %lld, ncv = %d)", z,
+                                 (long long)ks[z]->n, ks[z]->ncv, (long long)ks[0]->n, ks[0]->ncv);
+        for (int32_t y = 0; y < z; ++y)
+            if (ks[y] == ks[z] || ks[y]->op == ks[z]->op)
+                return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve_batch: problems %d and %d share a workspace or an operator", y, z);
+    }
+    return LSA_OK;
+}
+
+int krylov_extend_batch(lsa_ctx* ctx, KrylovGroupBuf* gb, lsa_krylov* const* ks, const uint8_t* active, const int32_t* j0, int32_t j1, void* const* Hs,
+                        int32_t ldh, int32_t* breakdown, int32_t* status, std::string* errs, lsa_ks_batch_info* info) {
+    const int32_t J = gb->J, slots = gb->slots;
+    const double t0 = now_s();
+    auto fail = [&](int32_t z, int rc) {  // problem z stops with its own status and its own text, which names it
+        status[z] = rc;
+        lsa_name_problem(ctx, z);
+        errs[z] = ctx->err;
+    };
+    struct Member {
+        ExtendCursor c;
+        HessView H;
+        bool lock;   // still asked for the lockstep set
+        int32_t nb;  // its steps in the current period (0: not a member)
+    } mem[kKrylovGroupMax];
+    int32_t nactive = 0;
+    int32_t ncv = 0;
+    for (int32_t z = 0; z < J; ++z) {
+        mem[z] = Member{ExtendCursor{0, false}, HessView{nullptr, 0, 0, 0}, false, 0};
+        if (!active[z]) continue;
+        ++nactive;
+        ncv = ks[z]->ncv;
+        breakdown[z] = -1;
+        status[z] = LSA_OK;
+        mem[z] = Member{ExtendCursor{j0[z], false}, HessView{(cplx*)Hs[z], ldh, j0[z], ks[z]->ncv}, true, 0};
+        ks[z]->t_for = -1;  // (op->t is anybody's between calls)
+    }
+    const size_t colb = krylov_slot_bytes(ncv);
+    const size_t cells = (size_t)J * (size_t)slots;
+    while (true) {
+        // ---- who is in lockstep in this read-back period
+        int32_t lead = -1, rounds = 0;
+        for (int32_t z = 0; z < J; ++z) {
+            Member& m = mem[z];
+            m.nb = 0;
+            if (!active[z] || !m.lock || status[z] != LSA_OK || breakdown[z] >= 0 || m.c.j >= j1) continue;
+            lsa_krylov* k = ks[z];
+            const StepPlan plan = step_plan(ctx, k);
+            bool in = plan.pipelined && plan.orth == Orth::dcgs2 && plan.tail;
+            if (in && lead >= 0)
+                in = nd_batch_compatible(ks[lead]->op->nd, k->op->nd) && ks[lead]->op->Kmul->dtype == k->op->Kmul->dtype;
+            if (!in) {
+                m.lock = false;
+                continue;
+            }
+            int rc = pipelined_prepare(ctx, k, plan);
+            if (rc == LSA_OK) rc = k->ow.ensure_fused(ctx, k->n);
+            if (rc != LSA_OK) {
+                fail(z, rc);
+                continue;
+            }
+            if (lead < 0) lead = z;
+            m.nb = std::min<int32_t>(slots, j1 - m.c.j);
+            rounds = std::max(rounds, m.nb);
+        }
+        if (lead < 0) break;
+        int rc = lsa_ensure_scratch(ctx, 0, cells * (colb + 2 * sizeof(double)));
+        int32_t sweep_launches = 0;
+        (void)lsa_ndlu_info(ks[lead]->op->nd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sweep_launches, nullptr, nullptr);
+        // ---- the rounds
+        for (int32_t s = 0; s < rounds && rc == LSA_OK; ++s) {
+            int32_t R = 0, jr[kKrylovGroupMax], fr[kKrylovGroupMax];
+            lsa_ndlu* nd[kKrylovGroupMax];
+            const lsa_mat *Mr[kKrylovGroupMax], *Cr[kKrylovGroupMax];
+            const void *rhs[kKrylovGroupMax], *yr[kKrylovGroupMax];
+            void *xr[kKrylovGroupMax], *Vr[kKrylovGroupMax], *slot[kKrylovGroupMax], *work[kKrylovGroupMax], *tr[kKrylovGroupMax];
+            double* parts[kKrylovGroupMax];
+            int32_t products = 0;
+            for (int32_t z = 0; z < J && rc == LSA_OK; ++z) {
+                if (s >= mem[z].nb) continue;
+                lsa_krylov* k = ks[z];
+                lsa_op* op = k->op;
+                const int32_t j = mem[z].c.j + s;
+                const size_t cell = (size_t)s * (size_t)J + (size_t)z;
+                if (k->t_for != j) {
+                    rc = spmv_global(ctx, op->Kmul, LSA_C128, (char*)k->V + (size_t)j * (size_t)k->n * 16, op->t, false);
+                    ++products;
+                }
+                k->t_for = -1;
+                jr[R] = j;
+                fr[R] = (s == 0 && !mem[z].c.pending) ? 1 : 0;
+                nd[R] = op->nd;
+                Mr[R] = op->Kmul;
+                Cr[R] = op->Kfac;
+                rhs[R] = op->t;
+                xr[R] = k->w;
+                yr[R] = k->w;
+                Vr[R] = k->V;
+                slot[R] = (char*)gb->Hdev + cell * colb;
+                work[R] = k->ow.fused;
+                tr[R] = op->t;
+                parts[R] = gb->tail_parts + cell * 2 * (size_t)gb->nparts;
+                ++R;
+            }
+            if (rc == LSA_OK) rc = ndlu_solve_batch_dev(ctx, R, nd, LSA_C128, rhs, xr);
+            if (rc == LSA_OK) rc = k_dcgs2_step_batch(ctx, R, ks[lead]->n, jr, Vr, ks[lead]->n, yr, fr, slot, ncv, work);
+            if (rc == LSA_OK) rc = k_dcgs2_tail_batch(ctx, R, ks[lead]->n, jr, Vr, ks[lead]->n, yr, work, Mr, Cr, tr, parts, slot, ncv);
+            for (int32_t z = 0; z < J; ++z)
+                if (s < mem[z].nb) ks[z]->t_for = mem[z].c.j + s + 1;
+            if (info) {
+                ++info->rounds;
+                info->launches += sweep_launches + 3 + products;
+            }
+        }
+        // ---- one read-back for the period: the checks of all cells in one launch, two copies, one synchronisation
+        if (rc == LSA_OK) rc = k_cgs2_tail_checks(ctx, rounds * J, gb->nparts, gb->tail_parts, gb->checks);
+        char* host = (char*)ctx->pinned;
+        if (rc == LSA_OK && (hipMemcpyAsync(host, gb->Hdev, (size_t)rounds * J * colb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                             hipMemcpyAsync(host + cells * colb, gb->checks, (size_t)rounds * J * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+            rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_krylov_solve_batch: read-back of a period failed");
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == LSA_OK) rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_krylov_solve_batch: a lockstep period failed on the device");
+        if (info) ++info->periods;
+        if (rc != LSA_OK) {  // the device work of the whole set is lost: an error of every member of this period
+            const std::string text = ctx->err;
+            for (int32_t z = 0; z < J; ++z)
+                if (mem[z].nb > 0) {
+                    ctx->err = text;
+                    fail(z, rc);
+                }
+            break;
+        }
+        const double* chk = (const double*)(host + cells * colb);
+        for (int32_t z = 0; z < J; ++z) {
+            Member& m = mem[z];
+            if (m.nb == 0) continue;
+            int32_t accepted = 0;
+            const int arc = accept_steps(ctx, ks[z], m.H, true, host + (size_t)z * colb, (size_t)J * colb, chk + 2 * (size_t)z, 2 * (size_t)J, m.nb, &m.c,
+                                         &breakdown[z], &accepted);
+            if (breakdown[z] >= 0) accepted = breakdown[z] + 1 - m.c.j;
+            if (arc != LSA_OK) fail(z, arc);
+            else if (info) info->lockstep_steps[z] += accepted;
+        }
+    }
+    // ---- whatever is left of each expansion, through the solo code (at least the flush of a problem that stayed to the end)
+    for (int32_t z = 0; z < J; ++z) {
+        if (!active[z] || status[z] != LSA_OK || breakdown[z] >= 0) continue;
+        const int32_t jb = mem[z].c.j;
+        const int xrc = extend_rest(ctx, ks[z], mem[z].H, &mem[z].c, j1, &breakdown[z]);
+        if (xrc != LSA_OK) fail(z, xrc);
+        else if (info) info->solo_steps[z] += (breakdown[z] >= 0 ? breakdown[z] + 1 : j1) - jb;
+    }
+    const double share = (now_s() - t0) / std::max(nactive, 1);
+    for (int32_t z = 0; z < J; ++z)
+        if (active[z]) ks[z]->op->st.seconds_solve += share;
+    return LSA_OK;
+}
+
+extern "C" {
 
 int lsa_krylov_restart(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t knew, const void* Q, int32_t ldq) {
     if (!ctx || !k || !Q) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_restart: null argument");

@@ -107,15 +107,16 @@ def solve_case(save_dir: Path, re: float, target: complex) -> Path | None:
     return result_file
 
 
-def solve_cases_batched(save_dir: Path, cases: list[tuple[float, complex]], batch: int) -> None:
+def solve_cases_batched(save_dir: Path, cases: list[tuple[float, complex]], batch: int, lockstep: bool = False) -> None:
     """The sweep in groups of ``batch`` Reynolds numbers (Solver.eigen.solve_batch: one context, ordering and LU analysis per
-    group); the same result files as one case at a time."""
+    group; with ``lockstep`` the group's problems also advance their Arnoldi steps together); the same result files as one
+    case at a time."""
     for g0 in range(0, len(cases), batch):
         group = [(re, target, build_case(save_dir, re, target)) for re, target in cases[g0:g0 + batch]]
         group = [c for c in group if c[2] is not None]
         if not group:
             continue
-        solve_batch([es for _, _, es in group], max_batch=batch)
+        solve_batch([es for _, _, es in group], max_batch=batch, lockstep=lockstep)
         for re, target, es in group:
             write_result(save_dir, re, target, es.solver)
         for _, _, es in group:
@@ -157,6 +158,9 @@ def main(argv: list[str] | None = None) -> None:
     ap.add_argument("--batch", type=int, default=0, metavar="J",
                     help="solve the Reynolds numbers in groups of J (1 <= J <= 16) that share one context, ordering and LU "
                          "analysis (Solver.eigen.solve_batch); the same files as one case at a time")
+    ap.add_argument("--lockstep", action="store_true",
+                    help="with --batch J: factorise the J problems of a group first and advance their Arnoldi steps together, one "
+                         "batched launch per kernel and round (solve_batch(..., lockstep=True)); the same files again")
     ap.add_argument("--symmetric", action="store_true",
                     help="instead of the Reynolds sweep: the symmetric-definite membrane pair (GHEP) on the real Lanczos path "
                          "(EigenSolver(..., symmetric=True))")
@@ -171,10 +175,12 @@ def main(argv: list[str] | None = None) -> None:
     import os
 
     os.environ.setdefault("LSA_HOST_BLAS_THREADS", "1")  # this script owns its process: keep spinning BLAS workers off the launch path
+    if args.lockstep and not args.batch:
+        ap.error("--lockstep needs --batch J")
     if args.batch:
         if not 1 <= args.batch <= 16:
             ap.error("--batch takes a group size from 1 to 16")
-        solve_cases_batched(args.save_dir, cases, args.batch)
+        solve_cases_batched(args.save_dir, cases, args.batch, args.lockstep)
     elif args.jobs <= 1:
         for re, target in cases:
             solve_case(args.save_dir, re, target)

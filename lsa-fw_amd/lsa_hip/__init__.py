@@ -101,6 +101,17 @@ class lsa_ks_result(ctypes.Structure):
     ]
 
 
+class lsa_ks_batch_info(ctypes.Structure):
+    _fields_ = [
+        ("rounds", ctypes.c_int64),
+        ("launches", ctypes.c_int64),
+        ("periods", ctypes.c_int64),
+        ("launches_per_round", ctypes.c_double),
+        ("lockstep_steps", ctypes.c_int64 * 16),
+        ("solo_steps", ctypes.c_int64 * 16),
+    ]
+
+
 _P = ctypes.c_void_p
 _I32, _I64, _DBL = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -111,6 +122,7 @@ SIGNATURES = {
     "lsa_ctx_destroy": (None, [_P]),
     "lsa_last_error": (ctypes.c_char_p, [_P]),
     "lsa_ctx_synchronize": (ctypes.c_int, [_P]),
+    "lsa_ctx_mem_info": (ctypes.c_int, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "lsa_ctx_arch": (ctypes.c_char_p, [_P]),
     "lsa_vec_create": (ctypes.c_int, [_P, _I64, ctypes.c_int, _PP]),
     "lsa_vec_destroy": (None, [_P]),
@@ -153,6 +165,7 @@ SIGNATURES = {
     "lsa_ndlu_destroy": (None, [_P]),
     "lsa_ndlu_solve": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_ndlu_solve_batch": (ctypes.c_int, [_P, _I32, _PP, _PP, _PP]),
+    "lsa_ndlu_prepared_memory": (ctypes.c_int, [_P, _P]),
     "lsa_ndlu_solve_adjoint": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P]),
     "lsa_ndlu_solve_time": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.POINTER(_DBL)]),
     "lsa_ndlu_solve_multi": (ctypes.c_int, [_P, _P, ctypes.c_int, _I32, _P, _I64, _P, _I64]),
@@ -181,6 +194,7 @@ SIGNATURES = {
     "lsa_krylov_shape": (ctypes.c_int, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "lsa_mat_rows": (_I64, [_P]),
     "lsa_krylov_solve": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "lsa_krylov_solve_batch": (ctypes.c_int, [_P, _I32, _PP, _PP, _PP, _I32, _PP, _PP, _PP, _PP, _P, _P, _P]),
     "lsa_eigs_sinvert": (ctypes.c_int, [_P, _P, _P, _DBL * 2, _I32, _I32, _DBL, _I32, ctypes.POINTER(lsa_op_options), _P, _P, _I32, _P, _P, _P, _P, _P]),
     "lsa_dense_schur": (ctypes.c_int, [_I32, _P, _I32, _P, _I32]),
     "lsa_dense_schur_reorder": (ctypes.c_int, [_I32, _P, _I32, _P, _I32, _P, ctypes.POINTER(_I32)]),
@@ -299,6 +313,19 @@ class Context:
 
     def synchronize(self) -> None:
         self.check(self._lib.lsa_ctx_synchronize(self.handle))
+
+    def prepared_lu_bytes(self) -> int:
+        """Device bytes the next factorisation on the analysis this context holds prepared allocates (``lsa_ndlu_prepared_memory``:
+        the memory plan of ``lsa_nd_sym_memory`` -- factors, working and update arenas, sweep buffers, index tables)."""
+        out = np.zeros(8, np.int64)
+        self.check(self._lib.lsa_ndlu_prepared_memory(self.handle, _ptr(out)))
+        return int(out[0] + out[1] + out[2] + out[4] + out[7])
+
+    def mem_info(self) -> tuple[int, int]:
+        """``(free, total)`` bytes of the device memory right now."""
+        free, total = _I64(0), _I64(0)
+        self.check(self._lib.lsa_ctx_mem_info(self.handle, ctypes.byref(free), ctypes.byref(total)))
+        return int(free.value), int(total.value)
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -869,32 +896,25 @@ class KrylovBasis:
                 self.imag_norms = out
         return X
 
-    def solve(self, nev: int, tol: float, max_restarts: int, which: int, transform: int, sigma: complex, *, antishift: complex = 0.0,
-              target: complex | None = None, v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None, vectors: bool = True):
-        """The whole Krylov-Schur iteration inside the library (``lsa_krylov_solve``: the dense algebra on the projected
-        matrix is the library's own).  ``which``: EPSWhich code (``iEpsWhich.value``); ``transform``: 0 shift-invert,
-        1 shift, 2 Cayley.  Returns a :class:`lsa_hip.krylov_schur.KrylovSchurResult` plus the eigenvalues ``lam``."""
+    @staticmethod
+    def _ks_options(nev, tol, max_restarts, which, transform, sigma, antishift, target, seed) -> lsa_ks_options:
+        target = sigma if target is None else target
+        return lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=int(which), transform=int(transform),
+                              sigma=(_DBL * 2)(complex(sigma).real, complex(sigma).imag), antishift=(_DBL * 2)(complex(antishift).real, complex(antishift).imag),
+                              target=(_DBL * 2)(complex(target).real, complex(target).imag), seed=int(seed), keep_fraction=0.5)
+
+    def _ks_start(self, v0):
+        if v0 is None:
+            return None
+        v = np.ascontiguousarray(v0, dtype=np.complex128)
+        if v.shape != (self.n,):
+            raise ValueError(f"start vector must have shape ({self.n},)")
+        return v
+
+    def _ks_collect(self, res: lsa_ks_result, theta, lam, est, X, max_out):
+        """What a library solve left in its output arrays, as a :class:`lsa_hip.krylov_schur.KrylovSchurResult` plus ``lam``."""
         from .krylov_schur import KrylovSchurResult
 
-        max_out = self.ncv if max_out is None else int(max_out)
-        target = sigma if target is None else target
-        o = lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=int(which), transform=int(transform),
-                           sigma=(_DBL * 2)(complex(sigma).real, complex(sigma).imag), antishift=(_DBL * 2)(complex(antishift).real, complex(antishift).imag),
-                           target=(_DBL * 2)(complex(target).real, complex(target).imag), seed=int(seed), keep_fraction=0.5)
-        theta = np.zeros(max(max_out, 1), dtype=np.complex128)
-        lam = np.zeros(max(max_out, 1), dtype=np.complex128)
-        est = np.zeros(max(max_out, 1), dtype=np.float64)
-        X = np.empty((self.n, max_out), dtype=np.complex128, order="F") if vectors else None
-        res = lsa_ks_result()
-        v = None
-        if v0 is not None:
-            v = np.ascontiguousarray(v0, dtype=np.complex128)
-            if v.shape != (self.n,):
-                raise ValueError(f"start vector must have shape ({self.n},)")
-        mask = None if self._mask is None else np.ascontiguousarray(self._mask, dtype=np.float64)
-        self.ctx.check(self.ctx._lib.lsa_krylov_solve(self.ctx.handle, self.handle, ctypes.byref(o), None if v is None else _ptr(v),
-                                                      None if mask is None else _ptr(mask), max_out, _ptr(theta), _ptr(lam),
-                                                      None if X is None else _ptr(X), _ptr(est), ctypes.byref(res)))
         k = res.nout
         self.imag_norms = None
         if X is not None and k > 0:
@@ -907,6 +927,78 @@ class KrylovBasis:
                                 "seconds_dense": res.seconds_dense, "seconds_restart": res.seconds_restart}])
         r.lam = lam[:k].copy()
         return r
+
+    def solve(self, nev: int, tol: float, max_restarts: int, which: int, transform: int, sigma: complex, *, antishift: complex = 0.0,
+              target: complex | None = None, v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None, vectors: bool = True):
+        """The whole Krylov-Schur iteration inside the library (``lsa_krylov_solve``: the dense algebra on the projected
+        matrix is the library's own).  ``which``: EPSWhich code (``iEpsWhich.value``); ``transform``: 0 shift-invert,
+        1 shift, 2 Cayley.  Returns a :class:`lsa_hip.krylov_schur.KrylovSchurResult` plus the eigenvalues ``lam``."""
+        max_out = self.ncv if max_out is None else int(max_out)
+        o = self._ks_options(nev, tol, max_restarts, which, transform, sigma, antishift, target, seed)
+        theta = np.zeros(max(max_out, 1), dtype=np.complex128)
+        lam = np.zeros(max(max_out, 1), dtype=np.complex128)
+        est = np.zeros(max(max_out, 1), dtype=np.float64)
+        X = np.empty((self.n, max_out), dtype=np.complex128, order="F") if vectors else None
+        res = lsa_ks_result()
+        v = self._ks_start(v0)
+        mask = None if self._mask is None else np.ascontiguousarray(self._mask, dtype=np.float64)
+        self.ctx.check(self.ctx._lib.lsa_krylov_solve(self.ctx.handle, self.handle, ctypes.byref(o), None if v is None else _ptr(v),
+                                                      None if mask is None else _ptr(mask), max_out, _ptr(theta), _ptr(lam),
+                                                      None if X is None else _ptr(X), _ptr(est), ctypes.byref(res)))
+        return self._ks_collect(res, theta, lam, est, X, max_out)
+
+    @staticmethod
+    def solve_batch(bases: "list[KrylovBasis]", nev: int, tol: float, max_restarts: int, which: int, transform: int, sigmas, *, antishift=0.0,
+                    targets=None, v0s=None, seed: int = 0, max_out: int | None = None, vectors: bool = True, raise_on_error: bool = True, ctx: Context | None = None):
+        """:meth:`solve` for up to 16 bases of one context and one shape in one library call (``lsa_krylov_solve_batch``): problems
+        whose Arnoldi steps take the pipelined DCGS2 tail form on factors of one LU analysis advance in lockstep (one batched
+        sweep pair and one batched reduction, update and tail launch per round for all of them), every problem returns the bits
+        of its own :meth:`solve`.  ``sigmas`` (and ``targets``, ``v0s``, ``antishift`` when sequences): one per basis.
+
+        Returns ``(results, info)``: the results in order, and the counters of ``lsa_ks_batch_info`` (``rounds``, ``launches``,
+        ``periods``, ``launches_per_round``, ``lockstep_steps`` and ``solo_steps`` per problem).  A problem that failed raises
+        (the first failing problem's status, with the texts of all failed problems, each naming its problem) unless
+        ``raise_on_error`` is off: then its entry is its own exception and the others are results."""
+        bases = list(bases)
+        J = len(bases)
+        per = lambda x, z: x[z] if isinstance(x, (list, tuple, np.ndarray)) and not np.isscalar(x) else x  # noqa: E731
+        if any(b._mask is not None for b in bases):
+            raise ValueError("solve_batch: bases with a mask (projected operators, sharded layout) are solved one by one")
+        ctx = bases[0].ctx if J else ctx  # (``ctx``: only needed for an empty list, whose refusal is the library's too)
+        max_out = (bases[0].ncv if J else 0) if max_out is None else int(max_out)
+        opts = [KrylovBasis._ks_options(nev, tol, max_restarts, which, transform, per(sigmas, z), per(antishift, z),
+                                        None if targets is None else per(targets, z), seed) for z in range(J)]
+        vs = [None if v0s is None else bases[z]._ks_start(v0s if isinstance(v0s, np.ndarray) and v0s.ndim == 1 else v0s[z]) for z in range(J)]
+        theta = [np.zeros(max(max_out, 1), dtype=np.complex128) for _ in range(J)]
+        lam = [np.zeros(max(max_out, 1), dtype=np.complex128) for _ in range(J)]
+        est = [np.zeros(max(max_out, 1), dtype=np.float64) for _ in range(J)]
+        X = [np.empty((b.n, max_out), dtype=np.complex128, order="F") if vectors else None for b in bases]
+        res = (lsa_ks_result * max(J, 1))()
+        status = (ctypes.c_int32 * max(J, 1))()
+        info = lsa_ks_batch_info()
+        arr = lambda ptrs: (ctypes.c_void_p * max(J, 1))(*ptrs)  # noqa: E731
+        addr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        if ctx is None:
+            raise ValueError("solve_batch needs at least one basis")
+        rc = ctx._lib.lsa_krylov_solve_batch(ctx.handle, J, arr([b.handle.value for b in bases]), arr([ctypes.addressof(o) for o in opts]),
+                                             arr([addr(v) for v in vs]), max_out, arr([addr(a) for a in theta]), arr([addr(a) for a in lam]),
+                                             arr([addr(a) for a in X]), arr([addr(a) for a in est]), ctypes.byref(res), ctypes.byref(status),
+                                             ctypes.byref(info))
+        # (the context's error text after a failure: the texts of all failed problems in order, each naming its problem)
+        text = ctx._lib.lsa_last_error(ctx.handle).decode(errors="replace") if rc != 0 else ""
+        if rc != 0 and (raise_on_error or all(st == 0 for st in status)):
+            ctx.check(rc)
+        out = []
+        for z, b in enumerate(bases):
+            if status[z] != 0:
+                mine = next((t for t in text.split("; ") if t.startswith(f"problem {z}:")), f"problem {z} failed: {text}")
+                out.append(ValueError(mine) if status[z] == -1 else LsaError(status[z], mine))
+            else:
+                out.append(b._ks_collect(res[z], theta[z], lam[z], est[z], X[z], max_out))
+        counters = {"rounds": int(info.rounds), "launches": int(info.launches), "periods": int(info.periods),
+                    "launches_per_round": float(info.launches_per_round), "lockstep_steps": [int(info.lockstep_steps[z]) for z in range(J)],
+                    "solo_steps": [int(info.solo_steps[z]) for z in range(J)]}
+        return out, counters
 
     def __del__(self):
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):

@@ -1,4 +1,5 @@
-"""Throughput of a Reynolds sweep on the bench case: Solver.eigen.solve_batch against a solo loop and three solves in flight.
+"""Throughput of a Reynolds sweep on the bench case: Solver.eigen.solve_batch, in turn and in lockstep, against a solo loop and three
+solves in flight.
 
     python tools/batch_throughput.py [--case S30k] [--sizes 1 2 4 8] [--reps 2] [--out profiles/batch_throughput.json]
 
@@ -9,11 +10,17 @@ as it does in the harness.  Modes alternate inside one process, ``reps`` times p
 
 - ``solo``: one problem after another, each with its own context, ordering and analysis;
 - ``batch``: ``solve_batch(max_batch=J)``: one context, ordering and analysis per group, the problems one after another;
+- ``lockstep``: ``solve_batch(max_batch=J, lockstep=True)``: all J factorisations first, then one ``lsa_krylov_solve_batch`` whose
+  Arnoldi rounds hold one step of every problem (batched sweeps, batched DCGS2 launches); also reports the rounds, the launches
+  per round and the read-backs of the group's call;
 - ``threads3``: three solo solves in flight (threads, one context each: ``examples/eigenvalues.py --jobs 3``).
 
 Per mode: aggregate eigenpairs/s (median over reps) and the time split from the solvers' statistics -- numeric
 factorisations, Arnoldi expansion (device steps), host dense work (Schur forms), restarts and Ritz vectors, and the rest
-(ordering, analysis, uploads, Python).  Every batched problem is checked bit for bit against its solo solve.
+(ordering, analysis, uploads, Python), in total and per problem.  Under lockstep the expansion time of a problem is its share
+(1 / active problems) of the wall time of the group's expansions, and the dense phase of the J problems runs back to back on
+the host with the device idle: its share of the wall time is reported.  Every batched problem is checked bit for bit against
+its solo solve.
 """
 
 from __future__ import annotations
@@ -52,7 +59,8 @@ def build(es, target):
 
 def outcome(s, pairs):
     st = s.solver.stats
-    return {"pairs": len(pairs), "lam": s.solver._eigenvalues.copy(), "X": np.array(s.solver._eigenvectors), **{k: st.get(k, 0.0) for k in SPLIT}}
+    return {"pairs": len(pairs), "lam": s.solver._eigenvalues.copy(), "X": np.array(s.solver._eigenvectors), **{k: st.get(k, 0.0) for k in SPLIT},
+            **{k: st[k] for k in ("lockstep_steps", "solo_steps", "lockstep_rounds", "lockstep_launches_per_round") if k in st}}
 
 
 def run_solo(problems):
@@ -64,11 +72,11 @@ def run_solo(problems):
     return out
 
 
-def run_batch(problems):
+def run_batch(problems, lockstep=False):
     from Solver.eigen import solve_batch
 
     solvers = [build(es, target) for es, target in problems]
-    pairs = solve_batch(solvers, max_batch=len(solvers))
+    pairs = solve_batch(solvers, max_batch=len(solvers), lockstep=lockstep)
     out = [outcome(s, p) for s, p in zip(solvers, pairs)]
     for s in solvers:
         s.solver.release()
@@ -108,21 +116,27 @@ def main() -> None:
         for J in args.sizes:
             problems = cases[:J]
             rec = {"J": J}
-            samples = {m: [] for m in ("solo", "batch", "threads3")}
+            samples = {m: [] for m in ("solo", "batch", "lockstep", "threads3")}
             splits = {m: None for m in samples}
             for _ in range(args.reps):
                 for mode in samples:
                     t = time.perf_counter()
-                    res = run_solo(problems) if mode == "solo" else run_batch(problems) if mode == "batch" else run_threads(problems, pool)
+                    res = (run_solo(problems) if mode == "solo" else run_batch(problems) if mode == "batch"
+                           else run_batch(problems, lockstep=True) if mode == "lockstep" else run_threads(problems, pool))
                     wall = time.perf_counter() - t
                     samples[mode].append(sum(r["pairs"] for r in res) / wall)
                     split = {k: sum(r[k] for r in res) for k in SPLIT}
                     split["seconds_other"] = wall - sum(split.values()) if mode != "threads3" else None
                     split["seconds_wall"] = wall
+                    split["per_problem_ms"] = {k[len("seconds_"):]: 1e3 * split[k] / J for k in SPLIT}
+                    split["dense_share_of_wall"] = split["seconds_dense"] / wall
+                    if mode == "lockstep":
+                        split.update({"rounds": res[0].get("lockstep_rounds", 0), "launches_per_round": res[0].get("lockstep_launches_per_round", 0.0),
+                                      "lockstep_steps": [r.get("lockstep_steps", 0) for r in res], "solo_steps": [r.get("solo_steps", 0) for r in res]})
                     splits[mode] = split
                     if mode == "solo":
                         solo = res
-                    if mode == "batch":
+                    if mode in ("batch", "lockstep"):
                         same = all(np.array_equal(b["lam"], s["lam"]) and np.array_equal(b["X"], s["X"]) for b, s in zip(res, solo))
                         bitwise &= same
             for mode, v in samples.items():
@@ -131,6 +145,9 @@ def main() -> None:
                 rec[f"{mode}_split_last"] = splits[mode]
             rec["batch_over_solo"] = rec["batch_eigenpairs_per_s"] / rec["solo_eigenpairs_per_s"]
             rec["batch_over_threads3"] = rec["batch_eigenpairs_per_s"] / rec["threads3_eigenpairs_per_s"]
+            rec["lockstep_over_batch"] = rec["lockstep_eigenpairs_per_s"] / rec["batch_eigenpairs_per_s"]
+            rec["lockstep_over_threads3"] = rec["lockstep_eigenpairs_per_s"] / rec["threads3_eigenpairs_per_s"]
+            rec["expand_ms_per_problem"] = {m: splits[m]["per_problem_ms"]["expand"] for m in ("solo", "batch", "lockstep")}
             rows.append(rec)
             print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in rec.items() if not k.endswith(("_samples", "_split_last"))}), flush=True)
     out = {"case": args.case, "config": "k=20, ncv=80, tol=1e-10, SINVERT, exact LU", "reps": args.reps,
