@@ -295,6 +295,8 @@ int lsa_op_stats(const lsa_op *op, lsa_stats *out);
  * transposes and factorises again).  Transposed sweeps of the nested-dissection LU, transposed SpMV; one rank, or the
  * subtree-parallel layout of lsa_op_create_dist (same exchanges as the forward solve; the transposed products use the whole
  * matrices every rank holds). */
+/* (A change of direction also clears the operator's "solves carry a refinement step" state: the other direction's solves decide
+ * that for themselves, as those of a new operator do.) */
 int lsa_op_set_adjoint(lsa_ctx *ctx, lsa_op *op, int on);
 /* Projected operator  y = P Kfac^-1 Kmul x  with P = diag(keep): keep[i] in {0, 1}, host array of n doubles (NULL
  * removes the projection).  Stands in for the velocity-subspace projection of ArpackEigenSolver's matvec
@@ -310,6 +312,8 @@ void lsa_krylov_destroy(lsa_krylov *k);
  * returns its vectors in the caller's numbering, rows scattered on the device.  NULL removes it. */
 int lsa_krylov_set_row_permutation(lsa_ctx *ctx, lsa_krylov *k, const int32_t *perm);
 /* v_0 = v / ||v||  (host complex vector of length n) */
+/* (A start vector begins a new run on the workspace: the pipelined step path is armed again, whatever an earlier run on the
+ * same workspace found out about its inner solves.  lsa_krylov_inject with j = 0 is this call.) */
 int lsa_krylov_set_start(lsa_ctx *ctx, lsa_krylov *k, const void *host_v);
 /* v_j = host vector orthonormalised (CGS2) against v_0..v_{j-1}: used to continue after an exact breakdown
  * (invariant subspace found, e.g. repeated eigenvalues) with a fresh direction; j = 0 equals set_start. */
@@ -333,6 +337,13 @@ int lsa_krylov_imag_norms(const lsa_krylov *k, int32_t nvec, double *out);
  * res[i] = ||A x_i - lam_i M x_i|| / (||A x_i|| + |lam_i| ||M x_i|| + 1e-16), X on the host (n x nvec). */
 int lsa_eig_residuals(lsa_ctx *ctx, const lsa_mat *A, const lsa_mat *M, int32_t nvec, const void *lam, const void *X,
                       double *res);
+/* pairing of left and right eigenvectors, SLEPc's EPSGetLeftEigenvector convention a^H A = lam a^H M and the products the
+ * reference forms to scale its adjoint mode (Sensitivity/__init__.py:281-287), on the device: X, Z on the host (n x nvec complex,
+ * column-major), G[i + j*nvec] = z_i^H M x_j, norm_z[j] = ||z_j||, norm_mx[j] = ||M x_j||.  M == NULL: the identity (n says how
+ * long the vectors are; with M it must be M's size).  The products M x_j are those of lsa_spmv, every sum is a fixed-order
+ * two-stage reduction: two calls return the same bits. */
+int lsa_eig_biorth(lsa_ctx *ctx, const lsa_mat *M, int64_t n, int32_t nvec, const void *X, const void *Z, void *G,
+                   double *norm_z, double *norm_mx);
 
 /* ---- the whole eigen-solve behind one call: SLEPc.EPS.solve() (Solver/utils.py:268-270) ------------------------------------------
  * Krylov-Schur outer iteration (SLEPc's default EPS: expand to ncv vectors, Schur form of the projected matrix with the wanted

@@ -55,6 +55,7 @@ class EigenSensitivitySolver:
         self._sigma: complex | None = None
         self._v: np.ndarray | None = None
         self._a: np.ndarray | None = None
+        self.pair_stats: dict | None = None  # the solver's statistics of the last solve_pair
 
     def solve_direct_mode(self, target: complex | None = None) -> tuple[complex, np.ndarray]:
         target = self._target if target is None else target
@@ -99,6 +100,31 @@ class EigenSensitivitySolver:
         # the reference scales by 1/prod; with the conjugating dot the scale that makes a^H M v = 1 is 1/conj(prod)
         self._a = a / np.conj(prod)
         return self._a
+
+    def solve_pair(self, target: complex | None = None) -> tuple[complex, np.ndarray, np.ndarray]:
+        """Direct and adjoint mode from ONE two-sided solve at the target (``EigenSolver(..., two_sided=True)``): one factorisation of
+        ``A - target M``, the direct iteration, then the adjoint iteration on the same factors, both to ``tol_direct``.  Returns
+        ``(sigma, v, a)``: the pair nearest the target and its left eigenvector scaled so that ``a^H M v = 1``, and leaves them for
+        :meth:`compute_wavemaker`.  (:meth:`solve_direct_mode` + :meth:`solve_adjoint_mode` shift the adjoint problem at the converged
+        ``conj(sigma)`` as the reference does; this route shifts both at the target.)  ``self.pair_stats``: the solver's statistics."""
+        target = self._target if target is None else target
+        if target is None:
+            raise ValueError("solve_pair needs a target: the two-sided solve is a shift-invert solve")
+        cfg = EigensolverConfig(num_eig=self._max_modes, problem_type=iEpsProblemType.GNHEP, atol=self._tol_direct, max_it=self._max_it)
+        es = EigenSolver(self._A, self._M, cfg, check_hermitian=False, two_sided=True, **self._kw)
+        es.solver.set_st_type(iSTType.SINVERT)
+        es.solver.set_target(target)
+        es.solver.set_st_pc_type(PreconditionerType.LU)
+        if not (pairs := es.solve()):
+            raise RuntimeError("No eigenpairs returned by the eigensolver.")
+        i = min(range(len(pairs)), key=lambda q: abs(pairs[q][0] - target))
+        a = es.solver.get_left_eigenvector_array(i, "biorth")
+        if a is None or not np.isfinite(es.solver.get_condition_numbers()[i]):
+            raise RuntimeError("Bi-orthonormal normalization failed: no left eigenvector with a^H B v != 0 for the pair nearest the target.")
+        self.pair_stats = es.solver.stats
+        self._sigma, self._v, self._a = complex(pairs[i][0]), es.solver.get_eigenvector_array(i), a
+        logger.info("Direct and adjoint eigenpair from one two-sided solve: sigma = %.4e %+.4e j", self._sigma.real, self._sigma.imag)
+        return self._sigma, self._v, self._a
 
     def compute_wavemaker(self, dofs_ux: np.ndarray, dofs_uy: np.ndarray) -> np.ndarray:
         """Nodal structural sensitivity |a_u| |v_u| / |a_u^H M v_u| on the velocity nodes."""

@@ -57,6 +57,8 @@ def batch_key(eps) -> tuple[tuple | None, str]:
         return None, "sharded layout"
     if eps._adjoint:
         return None, "adjoint problem"
+    if getattr(eps, "_two_sided", False):
+        return None, "two-sided solve"
     if eps._project_out is not None:
         return None, "projection (project_out)"
     if eps._ordering == "natural":

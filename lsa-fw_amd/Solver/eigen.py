@@ -88,7 +88,7 @@ def _warn_about_symmetry(kind: iEpsProblemType, A: iPETScMatrix, M: iPETScMatrix
 class EigenSolver:
     """``A x = lambda M x`` (``M`` optional) on the GPU; thin shell around :class:`iEpsSolver`."""
 
-    def __init__(self, *args, check_hermitian: bool = True, symmetric: bool = False, **solver_kwargs) -> None:
+    def __init__(self, *args, check_hermitian: bool = True, symmetric: bool = False, two_sided: bool = False, **solver_kwargs) -> None:
         """``EigenSolver(A, M=None, cfg=None, *, check_hermitian=True)`` as in ``Solver/eigen.py:67-74``, or the legacy
         ``EigenSolver(cfg, A=..., M=...)``.  Keywords the reference does not know (``device``, ``ilu_levels``,
         ``restart``, ``layout``, ...) are handed to :class:`iEpsSolver`.
@@ -96,7 +96,11 @@ class EigenSolver:
         ``symmetric=True`` (build-only, default off): ``HEP`` / ``GHEP`` problems with real symmetric operators, shift-invert at
         a real target and the exact factorisation run the real thick-restart Lanczos iteration in the ``M``-inner product
         (what SLEPc does for ``GHEP``): eigenvalues are ``float``, eigenvectors real with ``x^T M x = 1``.  Anything else runs
-        the general iteration as before and says why in ``solver.stats["symmetric_fallback"]``."""
+        the general iteration as before and says why in ``solver.stats["symmetric_fallback"]``.
+
+        ``two_sided=True`` (build-only, default off): the solve also computes the left eigenvectors ``a^H A = lambda a^H M`` on the
+        factorisation it has (:meth:`iEpsSolver.set_two_sided`); :meth:`solve` returns what it returns without it,
+        :meth:`left_eigenvectors` the left vectors, ``solver.get_condition_numbers()`` the condition numbers of the eigenvalues."""
         A, M, cfg = _sort_arguments(args, solver_kwargs)
         if A is None:
             raise ValueError("Operator A is required.")
@@ -107,7 +111,7 @@ class EigenSolver:
         if check_hermitian:
             _warn_about_symmetry(self._cfg.problem_type, A, M)
 
-        eps = iEpsSolver(A, M, symmetric=symmetric, **solver_kwargs)
+        eps = iEpsSolver(A, M, symmetric=symmetric, two_sided=two_sided, **solver_kwargs)
         eps.set_problem_type(self._cfg.problem_type)
         eps.set_tolerances(self._cfg.atol, self._cfg.max_it)
         eps.set_dimensions(self._cfg.num_eig, self._cfg.ncv)
@@ -140,6 +144,17 @@ class EigenSolver:
         pairs = list(self._solver.get_all_eigenpairs_up_to(self._cfg.num_eig))
         logger.info("Retrieved %d eigenpairs", len(pairs))
         return pairs
+
+
+    def left_eigenvectors(self, normalise: str = "biorth") -> list[iComplexPETScVector | None]:
+        """The left eigenvectors of the last two-sided solve, aligned with the pairs :meth:`solve` returned (``None`` where a pair
+        found no left partner); ``normalise="biorth"``: ``a_i^H M v_i = 1``, ``"unit"``: 2-norm 1.
+
+        ``v_i`` there is the stored eigenvector, ``solver.get_eigenvector_array(i)``.  :meth:`solve` hands out the same vector except
+        where its imaginary part has a norm <= 1e-6: then it returns the renormalised real part (as the reference's real build
+        does), and ``a_i^H M v_i = 1`` holds with THAT vector only to about 1e-6."""
+        count = min(self._solver.get_num_converged(), self._cfg.num_eig)
+        return [self._solver.get_left_eigenvector(i, normalise) for i in range(count)]
 
 
 def _solve_group_in_turn(solvers, group, results) -> None:

@@ -170,6 +170,59 @@ def _lambda_rank_key(which: iEpsWhich, target: complex):
     return keys[which]
 
 
+_CONJUGATE_WHICH = {"LARGEST_IMAGINARY": "SMALLEST_IMAGINARY", "SMALLEST_IMAGINARY": "LARGEST_IMAGINARY"}
+
+
+def conjugate_which(which: iEpsWhich) -> iEpsWhich:
+    """The key that orders ``conj(Lambda)`` (with the conjugated target) as ``which`` orders ``Lambda``: the two imaginary-part keys
+    swap, every other key of :func:`_lambda_rank_key` is its own image."""
+    return iEpsWhich[_CONJUGATE_WHICH.get(which.name, which.name)]
+
+
+def _conj_target(z) -> complex:
+    """``conj(z)`` as the ``complex`` a solver stores for the conjugated target: a real ``z`` stays ``z + 0j`` (not ``z - 0j``), so that
+    the back-transformed eigenvalues carry the zero signs a solver set up at ``conj(z)`` gives them."""
+    z = complex(z)
+    return complex(z.real, -z.imag) if z.imag != 0.0 else z
+
+
+def pair_left_right(lam: np.ndarray, mu: np.ndarray) -> np.ndarray:
+    """``match[i]`` = the index ``j`` of the adjoint eigenvalue ``mu[j]`` that belongs to ``lam[i]``, or -1: ``lam[i]`` and
+    ``conj(mu[j])`` are paired when each is the other's nearest neighbour.  No tolerance: the two phases see the same spectrum
+    through differently conditioned problems, and ill-conditioned eigenvalues agree to no fixed number of digits."""
+    lam = np.asarray(lam, dtype=np.complex128).ravel()
+    mu = np.asarray(mu, dtype=np.complex128).ravel()
+    match = np.full(lam.shape[0], -1, dtype=np.int64)
+    if lam.size == 0 or mu.size == 0:
+        return match
+    dist = np.abs(lam[:, None] - np.conj(mu)[None, :])
+    nearest_left = np.argmin(dist, axis=1)   # per direct value
+    nearest_right = np.argmin(dist, axis=0)  # per adjoint value
+    mutual = nearest_right[nearest_left] == np.arange(lam.shape[0])
+    match[mutual] = nearest_left[mutual]
+    return match
+
+
+def biorth_figures(G: np.ndarray, norm_z: np.ndarray, norm_mx: np.ndarray) -> tuple[np.ndarray, np.ndarray, float]:
+    """From ``G = Z^H M X`` of paired left and right vectors and the norms ``||z_i||``, ``||M x_i||``: the condition numbers
+    ``kappa_i = ||z_i|| ||M x_i|| / |G_ii|``, which pairs are degenerate (``|G_ii|`` zero or so small that its reciprocal overflows:
+    a defective pair, ``kappa = inf``) and the bi-orthogonality defect ``max_{i != j} |G_ij| / sqrt(|G_ii| |G_jj|)`` over the others."""
+    G = np.asarray(G, dtype=np.complex128)
+    d = np.abs(np.diagonal(G))
+    with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+        kappa = np.asarray(norm_z, dtype=np.float64) * np.asarray(norm_mx, dtype=np.float64) / d
+        degenerate = ~np.isfinite(1.0 / d) | ~np.isfinite(kappa)
+    # (Cauchy-Schwarz: kappa >= 1; where a^H M v is parallel to its factors, three separately rounded sums can say 1 - ulp)
+    kappa = np.where(degenerate, np.inf, np.maximum(kappa, 1.0))
+    ok = np.flatnonzero(~degenerate)
+    defect = 0.0
+    if ok.size > 1:
+        S = np.abs(G[np.ix_(ok, ok)]) / np.sqrt(np.outer(d[ok], d[ok]))
+        np.fill_diagonal(S, 0.0)
+        defect = float(S.max())
+    return kappa, degenerate, defect
+
+
 def delay_zero_diagonal_rows(C: sp.csr_matrix, block_starts: np.ndarray | None = None, fraction: float = 0.5) -> np.ndarray:
     """Permutation (new -> old) that moves every zero-diagonal row (the pressure rows of the saddle-point operator)
     behind ``fraction`` of the rows it couples to, so that its ILU pivot receives fill from enough velocity rows: one
@@ -361,6 +414,11 @@ class iEpsSolver:
     ``ksp_type`` (inner Krylov method, GMRES), ``ksp_rtol``, ``restart``, ``ksp_max_it``, ``ilu_levels``,
     ``ilu_shift``, ``device``, ``symmetric``.
 
+    ``two_sided=True`` (or :meth:`set_two_sided`; SLEPc's ``EPSSetTwoSided``) adds the left eigenvectors ``a^H A = lambda a^H M`` to a
+    shift-invert solve with the exact LU on one GPU: after the direct iteration the same operator is switched to
+    ``(A - sigma M)^-H M^H`` on the same factors and the same iteration runs again on the same basis (:meth:`_left_phase`); no second
+    factorisation.  :meth:`get_left_eigenvector`, :meth:`get_condition_numbers`, ``stats["left"]``.
+
     ``symmetric=True`` asks for the real thick-restart Lanczos iteration with the ``M``-inner product on ``HEP`` / ``GHEP`` problems
     (:func:`_symmetric_path` decides; ``stats["method"]`` says which iteration ran, ``stats["symmetric_fallback"]`` why the general
     one ran instead): real eigenvalues, real eigenvectors with ``x^T M x = 1``.
@@ -369,7 +427,8 @@ class iEpsSolver:
     def __init__(self, A=None, M=None, comm=None, *, device: int = 0, ksp_type: KSPType = KSPType.GMRES,
                  ksp_rtol: float | None = None, restart: int = 1000, ksp_max_it: int = 4000, ilu_levels: int | None = None,
                  ilu_shift: float = 0.0, ordering: str = "rcm", seed: int = 0, layout: str = "single",
-                 project_out: np.ndarray | None = None, lu: str = "nd", adjoint: bool = False, symmetric: bool = False) -> None:
+                 project_out: np.ndarray | None = None, lu: str = "nd", adjoint: bool = False, symmetric: bool = False,
+                 two_sided: bool = False) -> None:
         if M is not None and A is None:
             raise ValueError("Cannot set right-hand operator M without left-hand operator A.")
         self._A = self._M = None
@@ -395,6 +454,9 @@ class iEpsSolver:
         self._adjoint = bool(adjoint)
         self._symmetric = bool(symmetric)  # opt-in: real Lanczos with the M-inner product where _symmetric_path allows it
         self._real_vectors = False  # the last solve ran it: real eigenvalues, real M-orthonormal vectors
+        self._two_sided = False
+        self._left: dict | None = None  # what the left phase of the last two-sided solve found (:meth:`_left_phase`)
+        self.set_two_sided(two_sided)
         self._fallback_logged: set = set()
         self._device, self._seed = device, seed
         if layout not in ("single", "sharded"):
@@ -454,6 +516,36 @@ class iEpsSolver:
 
     def set_st_pc_type(self, pc_type: PreconditionerType) -> None:
         self._pc_type = PreconditionerType(pc_type)
+
+    def set_two_sided(self, flag: bool) -> None:
+        """Left eigenvectors too (``EPSSetTwoSided``).  ``ValueError`` together with ``adjoint=True``, whose right vectors they are."""
+        if flag and self._adjoint:
+            raise ValueError("two_sided=True with adjoint=True: the adjoint problem's eigenvectors ARE the left eigenvectors of (A, M)")
+        self._two_sided = bool(flag)
+
+    def get_two_sided(self) -> bool:
+        return self._two_sided
+
+    def _check_two_sided(self) -> None:
+        """What a two-sided solve cannot be, said before any device work."""
+        needs = ("two_sided=True needs shift-invert (iSTType.SINVERT) with the exact LU (PreconditionerType.LU, lu='nd'), on one GPU and "
+                 "without a projection")
+        if self._adjoint:
+            raise ValueError("two_sided=True with adjoint=True: the adjoint problem's eigenvectors ARE the left eigenvectors of (A, M)")
+        if self._which is iEpsWhich.ALL:
+            raise NotImplementedError(f"{needs}; spectrum slicing (iEpsWhich.ALL) is not two-sided")
+        if self._st_type is not iSTType.SINVERT:
+            raise NotImplementedError(f"{needs}; the spectral transformation is {self._st_type.name}")
+        if self._pc_type not in (PreconditionerType.LU, PreconditionerType.CHOLESKY) or self._ilu_levels is not None:
+            raise NotImplementedError(f"{needs}; the preconditioner is {self._pc_type.name}" +
+                                      ("" if self._ilu_levels is None else f" with ILU level {self._ilu_levels}"))
+        if self._layout != "single":
+            raise NotImplementedError(f"{needs}; the layout is '{self._layout}'")
+        if self._project_out is not None:
+            # (P C^-1 M P flipped is P C^-H M^H P: its eigenvectors are left eigenvectors of the PROJECTED operator, which are
+            #  bi-orthogonal to the right ones in the plain inner product, not through M: a^H M v and kappa would mean nothing)
+            raise NotImplementedError(f"{needs}; project_out is set (the flipped projected operator has the left eigenvectors of "
+                                      "P (A - sigma M)^-1 M P, not of (A, M))")
 
     # ---- solve ---------------------------------------------------------------------------------------------------------
     def _fill_level(self) -> tuple[int, int]:
@@ -681,6 +773,9 @@ class iEpsSolver:
         Leaves the eigenpairs and ``self.stats``: the operator's counters plus ``stats["krylov_restarts"]``, ``stats["method"]``
         (``"arnoldi"`` or ``"lanczos"``), ``stats["basis_bytes"]``, the phase times of the library's loop and, where
         ``symmetric=True`` ran the general iteration, ``stats["symmetric_fallback"]`` with the reason."""
+        self._left = None
+        if self._two_sided:
+            self._check_two_sided()
         if self._which is iEpsWhich.ALL:
             self._solve_interval()
             return
@@ -688,8 +783,11 @@ class iEpsSolver:
         try:
             self._run(run)
             self._collect(run)
+            left = self._left_phase(run) if self._two_sided else None
         finally:
             run.clear()  # (basis and operator go before the next solve builds its own)
+        if left is not None:
+            self._pair_left(*left)  # (after the factors are gone: the pairing's device blocks need none of the run)
 
     def _start_vector(self, n: int) -> np.ndarray:
         """The complex start vector of the library's Krylov-Schur loop, drawn here so that every driver begins from the same one."""
@@ -882,6 +980,90 @@ class iEpsSolver:
         self._imag_norms = imag_norms[order] if (imag_norms is not None and len(imag_norms) == len(order)) else None
         self._residual_estimates = res.residuals[order]
         self._restarts = res.restarts
+
+    def _left_phase(self, run: dict) -> tuple:
+        """Fourth part of a two-sided :meth:`solve`, after :meth:`_collect` and before the run is cleared: the adjoint iteration.
+
+        The run's operator is switched to ``(A - sigma M)^-H M^H`` (``lsa_op_set_adjoint``: the same factors, transposed sweeps and
+        products), the outer iteration of :meth:`_run` runs again on the run's basis -- same ``nev``, ``ncv``, ``tol``, restarts, seed
+        and start vector; ``sigma`` and the target conjugated, ``which`` mapped by :func:`conjugate_which` -- and the operator is
+        switched back.  That is the iteration a fresh ``adjoint=True`` solver at ``conj(target)`` runs, and it returns that solver's
+        bits.  ``stats`` keeps the direct phase's figures, ``stats["left"]`` gets this phase's own; :meth:`_pair_left` finishes it
+        once the run is cleared.
+
+        Where the symmetric iteration ran, left and right eigenvectors coincide and there is no second iteration."""
+        import time
+
+        from lsa_hip.krylov_schur import krylov_schur
+
+        prep, op, basis = self._prepared, run["op"], run["basis"]
+        started = time.perf_counter()
+        before = op.stats()  # (what _collect has just read: the operator's counters are cumulative)
+        restarts = 0
+        if run["use_lanczos"]:
+            mu, Z = self._eigenvalues.copy(), self._eigenvectors
+        else:
+            which = conjugate_which(run["which"])
+            sigma, target = _conj_target(prep["sigma"]), _conj_target(self._target)
+            lam_key = _lambda_rank_key(which, target)
+            tiny = np.finfo(float).tiny
+            back = lambda th: sigma + 1.0 / np.where(th == 0, tiny, th)  # noqa: E731  (theta = 1 / (mu - conj(sigma)))
+            op.set_adjoint(True)
+            try:
+                if not _native_driver():
+                    theta_key = lambda th: lam_key(back(np.asarray(th, dtype=np.complex128)))  # noqa: E731
+                    res = krylov_schur(basis, run["nev"], self._tol, self._max_it, theta_key, rng_seed=self._seed)
+                else:
+                    args = self._native_krylov_arguments(run)
+                    args.update({"which": which.value, "sigma": sigma, "antishift": _conj_target(run["nu"]), "target": target})
+                    res = basis.solve(**args)
+            finally:
+                op.set_adjoint(False)
+            mu = back(np.asarray(res.theta, dtype=np.complex128))
+            order = np.argsort(lam_key(mu), kind="stable")
+            mu, Z = mu[order], res.vectors
+            if not (np.array_equal(order, np.arange(len(order))) and Z.flags.f_contiguous):
+                Z = np.asfortranarray(Z[:, order])
+            restarts = int(res.restarts)
+        after = op.stats()
+        self._stats["left"] = {
+            "applies": int(after["op_applies"] - before["op_applies"]), "restarts": restarts, "converged": int(len(mu)),
+            "seconds": time.perf_counter() - started, "seconds_solve": after["seconds_solve"] - before["seconds_solve"],
+            "seconds_factor": after["seconds_factor"] - before["seconds_factor"],
+            # the library keeps no count of factorisations: its one factor clock (analysis + factorisation) did or did not move
+            "refactored": int(after["seconds_factor"] != before["seconds_factor"]),
+            "sptrsv_calls": int(after["sptrsv_calls"] - before["sptrsv_calls"]), "spmv_calls": int(after["spmv_calls"] - before["spmv_calls"]),
+            "backward_accepted": int(after["backward_accepted"] - before["backward_accepted"])}
+        return mu, Z, bool(run["use_lanczos"])
+
+    def _pair_left(self, mu: np.ndarray, Z: np.ndarray, own_partners: bool) -> None:
+        """Last part of a two-sided :meth:`solve`: the adjoint pairs ``(mu_j, z_j)`` are matched to the direct ones by
+        :func:`pair_left_right` (``own_partners``: the symmetric iteration's vectors are their own partners, multiple eigenvalues
+        included); ``z^H M x`` and the norms come from the device (``lsa_eig_biorth``), the figures from :func:`biorth_figures`."""
+        import time
+
+        import lsa_hip
+
+        started = time.perf_counter()
+        prep = self._prepared
+        match = np.arange(len(mu), dtype=np.int64) if own_partners else pair_left_right(self._eigenvalues, mu)
+        paired = np.flatnonzero(match >= 0)
+        k = len(self._eigenvalues)
+        gram, kappa, degenerate = np.full(k, np.nan, dtype=np.complex128), np.full(k, np.nan), np.zeros(k, dtype=bool)
+        defect = 0.0
+        if paired.size:
+            perm = prep["perm"]  # (the device matrices are in the permuted numbering)
+            G, norm_z, norm_mx = lsa_hip.eig_biorth(prep["ctx"], prep["dM"], self._eigenvectors[:, paired][perm, :], Z[:, match[paired]][perm, :])
+            kappa[paired], degenerate[paired], defect = biorth_figures(G, norm_z, norm_mx)
+            gram[paired] = np.diagonal(G)
+        if degenerate.any():
+            logger.warning("Two-sided solve: a^H M v underflows for %d pair(s) (defective eigenvalues): their condition number is inf and "
+                           "their left vectors are returned with unit norm.", int(degenerate.sum()))
+        if paired.size < k:
+            logger.warning("Two-sided solve: %d of %d eigenpairs found no left partner among the %d adjoint pairs.", k - paired.size, k, len(mu))
+        self._left = {"values": mu, "vectors": Z, "match": match, "gram": gram, "kappa": kappa, "degenerate": degenerate}
+        left = self._stats["left"]
+        left.update({"seconds": left["seconds"] + time.perf_counter() - started, "unmatched": int(k - paired.size), "biorth_defect": defect})
 
     def _solve_interval(self) -> None:
         """``iEpsWhich.ALL`` + ``set_interval(a, b)`` (reference: ``Solver/utils.py:248-254``, SLEPc's spectrum slicing):
@@ -1155,6 +1337,47 @@ class iEpsSolver:
         """ndarray of eigenvector ``idx`` (convenience; not in the reference): complex, or real ``float64`` when the symmetric
         iteration ran."""
         return self._eigenvectors[:, idx].copy()
+
+    # ---- left eigenvectors of a two-sided solve (EPSGetLeftEigenvector; convention a^H A = lambda a^H M) -----------------------------
+    def _left_results(self) -> dict:
+        if self._left is None:
+            raise RuntimeError("No left eigenvectors: set two_sided (set_two_sided(True) or two_sided=True) before solve().")
+        return self._left
+
+    def get_left_eigenvector_array(self, idx: int, normalise: str = "biorth") -> np.ndarray | None:
+        """ndarray of the left eigenvector paired with eigenpair ``idx``, ``None`` where the pairing found none.  ``normalise``:
+        ``"unit"``, as the adjoint iteration returns it (2-norm 1, canonical phase), or ``"biorth"``, scaled so that ``a^H M v = 1``
+        with :meth:`get_eigenvector_array` ``(idx)`` (a degenerate pair, ``kappa = inf``, keeps its unit vector)."""
+        if normalise not in ("unit", "biorth"):
+            raise ValueError(f"normalise must be 'unit' or 'biorth', got {normalise!r}")
+        left = self._left_results()
+        j = int(left["match"][idx])
+        if j < 0:
+            return None
+        a = left["vectors"][:, j].copy()  # (real where the symmetric iteration ran)
+        if normalise == "biorth" and not left["degenerate"][idx]:
+            a /= np.conj(left["gram"][idx]) if a.dtype.kind == "c" else left["gram"][idx].real
+        return a
+
+    def get_left_eigenvector(self, idx: int, normalise: str = "biorth") -> iComplexPETScVector | None:
+        """:meth:`get_left_eigenvector_array` in the vector wrapper :meth:`get_eigenvector` returns."""
+        a = self.get_left_eigenvector_array(idx, normalise)
+        if a is None:
+            return None
+        if a.dtype.kind != "c":
+            return iComplexPETScVector(iPETScVector._adopt(a))
+        return iComplexPETScVector(iPETScVector._adopt(a.real), iPETScVector._adopt(a.imag))
+
+    def get_condition_numbers(self) -> np.ndarray:
+        """``kappa_i = ||a_i|| ||M v_i|| / |a_i^H M v_i|`` per eigenpair of the last two-sided solve: ``nan`` where no left vector
+        was paired, ``inf`` for a degenerate pair."""
+        return self._left_results()["kappa"].copy()
+
+    def get_adjoint_eigenpairs(self) -> tuple[np.ndarray, np.ndarray]:
+        """The left phase's own result, unpaired: eigenvalues ``mu`` of ``(A^H, M^H)`` and unit eigenvectors (columns), in the order a
+        solver with ``adjoint=True`` at ``conj(target)`` returns them."""
+        left = self._left_results()
+        return left["values"].copy(), left["vectors"].copy()
 
     @property
     def stats(self) -> dict:

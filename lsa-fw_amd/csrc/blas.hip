@@ -181,6 +181,26 @@ __global__ __launch_bounds__(kThreads) void residual_norms_partial_kernel(int64_
     }
 }
 
+// the partial sums of |x|^2 and |y|^2 of two vectors in one pass (slots 2 blk, 2 blk + 1; nrm2_finish2_kernel sums them)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void pair_nrm2_partial_kernel(int64_t n, const T* __restrict__ x, const T* __restrict__ y,
+                                                                     double* __restrict__ partial) {
+    __shared__ double smem[4];
+    double rx = 0.0, ry = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        rx += s_abs2(x[i]);
+        ry += s_abs2(y[i]);
+    }
+    const double sx = block_sum<double>(rx, smem);
+    __syncthreads();
+    const double sy = block_sum<double>(ry, smem);
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = sx;
+        partial[2 * blockIdx.x + 1] = sy;
+    }
+}
+
 __global__ __launch_bounds__(64) void nrm2_finish2_kernel(int nblocks, const double* __restrict__ partial, double* __restrict__ out) {
     double a0 = 0.0, a1 = 0.0;
     for (int k = threadIdx.x; k < nblocks; k += 64) {
@@ -1358,6 +1378,17 @@ int k_residual_norms(lsa_ctx* ctx, int dtype, int64_t n, const void* b, const vo
     });
     hipLaunchKernelGGL(nrm2_finish2_kernel, dim3(1), dim3(64), 0, ctx->stream, blocks, partial, nrm2_dev);
     return check_launch(ctx, "residual_norms");
+}
+
+int k_pair_nrm2(lsa_ctx* ctx, int dtype, int64_t n, const void* x, const void* y, double* nrm2_dev) {
+    const int blocks = stream_blocks(ctx, n);
+    LSA_CHECK(lsa_ensure_scratch(ctx, sizeof(double) * 2 * (size_t)blocks, 0));
+    double* partial = (double*)ctx->dscratch;
+    DISPATCH_T(dtype, {
+        hipLaunchKernelGGL((pair_nrm2_partial_kernel<T>), dim3(blocks), dim3(kThreads), 0, ctx->stream, n, (const T*)x, (const T*)y, partial);
+    });
+    hipLaunchKernelGGL(nrm2_finish2_kernel, dim3(1), dim3(64), 0, ctx->stream, blocks, partial, nrm2_dev);
+    return check_launch(ctx, "pair_nrm2");
 }
 
 int k_scale_by_inv_norm(lsa_ctx* ctx, int dtype, int64_t n, const void* x, const double* nrm2_dev, void* y) {

@@ -248,6 +248,8 @@ int k_multi_axpy(lsa_ctx* ctx, int dtype, int64_t n, int j, const void* V, int64
 int k_columns_canonical(lsa_ctx* ctx, int64_t n, int ncols, void* X, int64_t ldx, int unit, double* imag2_dev);
 // nrm2_dev[0] = ||x||^2
 int k_nrm2(lsa_ctx* ctx, int dtype, int64_t n, const void* x, double* nrm2_dev);
+// nrm2_dev[0] = ||x||^2, nrm2_dev[1] = ||y||^2 in one pass over both (fixed-order two-stage sums)
+int k_pair_nrm2(lsa_ctx* ctx, int dtype, int64_t n, const void* x, const void* y, double* nrm2_dev);
 int k_mask(lsa_ctx* ctx, int dtype, int64_t n, const double* keep_dev, void* y);
 int k_residual_norms(lsa_ctx* ctx, int dtype, int64_t n, const void* b, const void* z, void* w, double* nrm2_dev);
 // y = x / sqrt(nrm2_dev[0])   (no host round trip)

@@ -807,6 +807,8 @@ int lsa_op_set_adjoint(lsa_ctx* ctx, lsa_op* op, int on) {
         op->Kfac = (on || !op->view_fac) ? op->owned : op->view_fac;
         op->Kmul = (on || !op->view_mul) ? (op->owned_mul ? op->owned_mul : op->M_whole) : op->view_mul;
     }
+    // (the other direction's solves decide about their refinement step for themselves, as those of a new operator do)
+    if (op->adjoint != (on != 0)) op->refine = false;
     op->adjoint = on != 0;
     return LSA_OK;
 }
@@ -1006,6 +1008,7 @@ int lsa_krylov_set_start(lsa_ctx* ctx, lsa_krylov* k, const void* host_v) {
     if (!(nrm > 0.0) || !std::isfinite(nrm)) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_set_start: start vector is zero or not finite");
     LSA_CHECK(k_scale_by_inv_norm(ctx, LSA_C128, k->n, k->w, k->ow.nrm2, k->V));
     LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    k->pipeline = true;  // a start vector begins a new run: what the last run on this workspace found out about its solves is not this one's
     return LSA_OK;
 }
 
@@ -1604,6 +1607,47 @@ int lsa_eig_residuals(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t 
     }
     (void)hipStreamSynchronize(ctx->stream);
     for (void* p : {x, ax, mx, (void*)nr})
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
+int lsa_eig_biorth(lsa_ctx* ctx, const lsa_mat* M, int64_t n, int32_t nvec, const void* X, const void* Z, void* G, double* norm_z, double* norm_mx) {
+    if (!ctx || !X || !Z || !G || !norm_z || !norm_mx || n < 1 || nvec < 0) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_eig_biorth: bad argument");
+    if (M && (M->n != n || M->ncols != n || M->row0 != 0))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_eig_biorth: M is %d x %d (first row %d), the vectors have %lld entries", M->n, M->ncols, M->row0, (long long)n);
+    if (nvec == 0) return LSA_OK;
+    const size_t vb = (size_t)n * 16, gb = (size_t)nvec * nvec * 16;
+    void *z = nullptr, *x = nullptr, *mx = nullptr, *g = nullptr;
+    double* nr = nullptr;  // (||z_j||^2, ||M x_j||^2) per column
+    int rc = LSA_OK;
+    if (hipMalloc(&z, vb * (size_t)nvec) != hipSuccess || hipMalloc(&x, vb) != hipSuccess || hipMalloc(&mx, vb) != hipSuccess ||
+        hipMalloc(&g, gb) != hipSuccess || hipMalloc((void**)&nr, (size_t)nvec * 2 * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = lsa_set_error(ctx, LSA_ERR_OOM, "lsa_eig_biorth: out of device memory (n=%lld, nvec=%d)", (long long)n, nvec);
+    }
+    if (rc == LSA_OK && hipMemcpyAsync(z, Z, vb * (size_t)nvec, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_eig_biorth: upload failed");
+    for (int32_t c = 0; c < nvec && rc == LSA_OK; ++c) {
+        if (hipMemcpyAsync(x, (const char*)X + (size_t)c * vb, vb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+            rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_eig_biorth: upload failed");
+            break;
+        }
+        rc = M ? k_spmv(ctx, M, LSA_C128, x, mx) : k_copy(ctx, LSA_C128, n, x, mx);
+        // column c of G is the V^H w of the CGS kernels with V = Z, w = M x_c
+        if (rc == LSA_OK) rc = k_multi_dot(ctx, LSA_C128, n, nvec, z, n, mx, (char*)g + (size_t)c * nvec * 16);
+        if (rc == LSA_OK) rc = k_pair_nrm2(ctx, LSA_C128, n, (const char*)z + (size_t)c * vb, mx, nr + 2 * (size_t)c);
+    }
+    std::vector<double> nrh((size_t)nvec * 2);
+    if (rc == LSA_OK && (hipMemcpyAsync(G, g, gb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                         hipMemcpyAsync(nrh.data(), nr, nrh.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+        rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_eig_biorth: download failed");
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (rc == LSA_OK && e != hipSuccess) rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_eig_biorth: %s", hipGetErrorString(e));
+    for (int32_t c = 0; c < nvec && rc == LSA_OK; ++c) {
+        norm_z[c] = std::sqrt(nrh[2 * (size_t)c]);
+        norm_mx[c] = std::sqrt(nrh[2 * (size_t)c + 1]);
+    }
+    for (void* p : {z, x, mx, g, (void*)nr})
         if (p) (void)hipFree(p);
     return rc;
 }

@@ -60,7 +60,7 @@ def synthesize(save_dir: Path, case: str) -> None:
         iPETScMatrix(es.M).export(mat_dir / "M.mtx")
 
 
-def build_case(save_dir: Path, re: float, target: complex) -> EigenSolver | None:
+def build_case(save_dir: Path, re: float, target: complex, two_sided: bool = False) -> EigenSolver | None:
     """The solver of one Reynolds number, configured as the reference's loop body does; None when its matrices are absent."""
     root = save_dir / f"reynolds_{re:.1f}"
     files = {name: root / "matrices" / f"{name}.mtx" for name in ("A", "M")}
@@ -75,7 +75,8 @@ def build_case(save_dir: Path, re: float, target: complex) -> EigenSolver | None
         logger.info("Re %.1f: %s read from %s: %d x %d, %d stored entries, Frobenius norm %.3e", re, name, path, *mat.shape, mat.nonzero_entries, mat.norm)
         pair[name] = mat
 
-    eigensolver = EigenSolver(pair["A"], pair["M"], cfg=EigensolverConfig(num_eig=_NUM_EIG, atol=_ATOL), check_hermitian=False)
+    eigensolver = EigenSolver(pair["A"], pair["M"], cfg=EigensolverConfig(num_eig=_NUM_EIG, atol=_ATOL), check_hermitian=False,
+                              two_sided=two_sided)
     eps = eigensolver.solver
     eps.set_st_type(iSTType.SINVERT)
     eps.set_target(target)
@@ -90,14 +91,17 @@ def write_result(save_dir: Path, re: float, target: complex, eps) -> Path:
     result_file = root / f"sigma_eig{_EIG_INDEX}.txt"
     result_file.write_text(f"{value.real} {value.imag}\n", encoding="utf-8")
     logger.info("Re %.1f: eigenvalue %d nearest %s is %s -> %s", re, _EIG_INDEX, target, value, result_file)
+    if eps.get_two_sided():  # condition number of every mode, from the left eigenvectors of the same solve
+        for i, kappa in enumerate(eps.get_condition_numbers()):
+            logger.info("Re %.1f: mode %d  lambda = %s  kappa = %.3e", re, i, eps.get_eigenvalue(i), kappa)
     return result_file
 
 
-def solve_case(save_dir: Path, re: float, target: complex) -> Path | None:
+def solve_case(save_dir: Path, re: float, target: complex, two_sided: bool = False) -> Path | None:
     """One Reynolds number of the sweep: read the MatrixMarket pair, shift-invert at the tabulated target with the exact LU
     as inner solver, store the selected eigenvalue as ``"<real> <imag>"`` (the call sequence of the reference's loop body,
     ``.examples/eigenvalues.py:61-107``; same file names and output format, so its post-processing reads these results)."""
-    eigensolver = build_case(save_dir, re, target)
+    eigensolver = build_case(save_dir, re, target, two_sided)
     if eigensolver is None:
         return None
     eps = eigensolver.solver
@@ -107,12 +111,12 @@ def solve_case(save_dir: Path, re: float, target: complex) -> Path | None:
     return result_file
 
 
-def solve_cases_batched(save_dir: Path, cases: list[tuple[float, complex]], batch: int, lockstep: bool = False) -> None:
+def solve_cases_batched(save_dir: Path, cases: list[tuple[float, complex]], batch: int, lockstep: bool = False, two_sided: bool = False) -> None:
     """The sweep in groups of ``batch`` Reynolds numbers (Solver.eigen.solve_batch: one context, ordering and LU analysis per
     group; with ``lockstep`` the group's problems also advance their Arnoldi steps together); the same result files as one
     case at a time."""
     for g0 in range(0, len(cases), batch):
-        group = [(re, target, build_case(save_dir, re, target)) for re, target in cases[g0:g0 + batch]]
+        group = [(re, target, build_case(save_dir, re, target, two_sided)) for re, target in cases[g0:g0 + batch]]
         group = [c for c in group if c[2] is not None]
         if not group:
             continue
@@ -164,6 +168,9 @@ def main(argv: list[str] | None = None) -> None:
     ap.add_argument("--symmetric", action="store_true",
                     help="instead of the Reynolds sweep: the symmetric-definite membrane pair (GHEP) on the real Lanczos path "
                          "(EigenSolver(..., symmetric=True))")
+    ap.add_argument("--two-sided", action="store_true",
+                    help="also compute the left eigenvectors on the same factorisation (EigenSolver(..., two_sided=True)) and print the "
+                         "condition number kappa of every mode; the same result files (with --batch such solves run one by one)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     if args.symmetric:
@@ -180,10 +187,10 @@ def main(argv: list[str] | None = None) -> None:
     if args.batch:
         if not 1 <= args.batch <= 16:
             ap.error("--batch takes a group size from 1 to 16")
-        solve_cases_batched(args.save_dir, cases, args.batch, args.lockstep)
+        solve_cases_batched(args.save_dir, cases, args.batch, args.lockstep, args.two_sided)
     elif args.jobs <= 1:
         for re, target in cases:
-            solve_case(args.save_dir, re, target)
+            solve_case(args.save_dir, re, target, args.two_sided)
     else:
         from concurrent.futures import ThreadPoolExecutor
 
@@ -191,7 +198,7 @@ def main(argv: list[str] | None = None) -> None:
         # serialise two solves on the same queues (read when the first HIP context is created)
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # (more than eight queues per GPU slow everything down: DESIGN.md section 6)
         with ThreadPoolExecutor(max_workers=args.jobs) as pool:
-            for fut in [pool.submit(solve_case, args.save_dir, re, target) for re, target in cases]:
+            for fut in [pool.submit(solve_case, args.save_dir, re, target, args.two_sided) for re, target in cases]:
                 fut.result()
     logger.info("All cases processed.")
 

@@ -200,6 +200,7 @@ SIGNATURES = {
     "lsa_dense_schur_reorder": (ctypes.c_int, [_I32, _P, _I32, _P, _I32, _P, ctypes.POINTER(_I32)]),
     "lsa_dense_tri_eigenvectors": (ctypes.c_int, [_I32, _P, _I32, _P, _I32]),
     "lsa_eig_residuals": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P]),
+    "lsa_eig_biorth": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
     "lsa_lanczos_create": (ctypes.c_int, [_P, _P, _I32, _PP]),
     "lsa_lanczos_destroy": (None, [_P]),
     "lsa_lanczos_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
@@ -1155,3 +1156,17 @@ def eig_residuals(ctx: Context, A: CsrMatrix, M: CsrMatrix | None, lam: np.ndarr
     res = np.empty(lam.shape[0], dtype=np.float64)
     ctx.check(ctx._lib.lsa_eig_residuals(ctx.handle, A.handle, M.handle if M is not None else None, lam.shape[0], _ptr(lam), _ptr(X), _ptr(res)))
     return res
+
+
+def eig_biorth(ctx: Context, M: CsrMatrix | None, X: np.ndarray, Z: np.ndarray) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``lsa_eig_biorth``: ``G = Z^H M X`` (k x k), ``||z_j||`` and ``||M x_j||`` for host blocks ``X``, ``Z`` (n x k), evaluated on the
+    device; ``M=None`` is the identity.  The products ``M x_j`` stay on the device (they are those of :meth:`CsrMatrix.matvec`)."""
+    X = np.asfortranarray(X, dtype=np.complex128)
+    Z = np.asfortranarray(Z, dtype=np.complex128)
+    if X.ndim != 2 or X.shape != Z.shape:
+        raise ValueError(f"eig_biorth: X {X.shape} and Z {Z.shape} must be two blocks of one shape (n, k)")
+    n, k = X.shape
+    G = np.zeros((k, k), dtype=np.complex128, order="F")
+    norm_z, norm_mx = np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.float64)
+    ctx.check(ctx._lib.lsa_eig_biorth(ctx.handle, M.handle if M is not None else None, n, k, _ptr(X), _ptr(Z), _ptr(G), _ptr(norm_z), _ptr(norm_mx)))
+    return G, norm_z, norm_mx
