@@ -472,6 +472,40 @@ int lsa_lanczos_solve(lsa_ctx *ctx, lsa_lanczos *l, const lsa_ks_options *opts, 
  * tridiagonalisation + implicit QL.  LSA_ERR_DIVERGED if the QL iteration stalls. */
 int lsa_dense_syev(int32_t n, double *A, int32_t lda, double *w);
 
+/* ---- resolvent (input-output) analysis: optimal gains, responses and forcings of M q' = A q + M f at a real frequency omega -------
+ * With R = (i omega M - A)^-1 the gains sigma_1 >= sigma_2 >= ... are the maxima of ||q||_M / ||f||_M over q = R M f; sigma_j^2
+ * are the largest eigenvalues of W = R M R^H M = C^-1 M C^-H M, C = A - i omega M, which is self-adjoint and non-negative in the
+ * M-(semi-)inner product.  The iteration is the thick-restart Lanczos of lsa_lanczos_* with a complex basis, V^H M V = I, and the
+ * same real symmetric projected matrix; both inner solves of a step run on ONE factorisation of C.  The operator handle is the
+ * one of the general path: lsa_op_create, mode 0, sigma = (0, omega), pc_type 2, M real symmetric positive semidefinite. */
+typedef struct lsa_resolvent lsa_resolvent;
+/* Basis of ncv + 1 complex vectors.  LSA_ERR_ARG, with a message that names the condition, unless the operator is shift-invert
+ * (mode 0) with M, M real, exact factors (real for omega = 0, else complex), forward, unprojected, on one rank. */
+int lsa_resolvent_create(lsa_ctx *ctx, lsa_op *op, int32_t ncv, lsa_resolvent **out);
+void lsa_resolvent_destroy(lsa_resolvent *r);
+/* as lsa_krylov_set_row_permutation: the vectors of lsa_resolvent_solve leave in the caller's numbering */
+int lsa_resolvent_set_row_permutation(lsa_ctx *ctx, lsa_resolvent *r, const int32_t *perm);
+/* v_0 = v / sqrt(v^H M v) (host complex vector of length n), M-normalised on the device; LSA_ERR_ARG when v^H M v is not positive */
+int lsa_resolvent_set_start(lsa_ctx *ctx, lsa_resolvent *r, const void *host_v);
+/* Lanczos steps j = j0 .. j1-1 on W: z = C^-H M v_j, w = C^-1 M z, two passes of classical Gram-Schmidt against v_0..v_j in the
+ * M-inner product, v_{j+1} = w / beta_j.  T is the caller's (ncv+1) x ncv column-major REAL matrix (ldt >= j1 + 1), written as by
+ * lsa_lanczos_extend: alpha_j = Re v_j^H M W v_j (the imaginary part is rounding and is dropped), beta_j > 0.  Both solves are
+ * checked against the operator's ksp_rtol, each direction with its own refinement step once one of its solves missed it;
+ * LSA_ERR_DIVERGED when a solve misses it after that step, LSA_ERR_ARG when w^H M w is negative.  For tests. */
+int lsa_resolvent_extend(lsa_ctx *ctx, lsa_resolvent *r, int32_t j0, int32_t j1, double *T, int32_t ldt, int32_t *breakdown);
+/* the first ncols columns of the basis, in the basis' own row numbering (n x ncols complex column-major on the host); for tests */
+int lsa_resolvent_basis(lsa_ctx *ctx, const lsa_resolvent *r, int32_t ncols, void *host_V);
+/* The whole iteration, through the loop of lsa_lanczos_solve: Ritz values ranked largest first, accepted on |beta y_mi| / theta_i <=
+ * opts->tol; of opts only nev, max_restarts, tol, seed and keep_fraction are read.  v0: host start vector (n complex) or NULL
+ * (random from opts->seed).  Outputs, largest gain first: theta_out[max_out] = sigma_j^2, gain_out[max_out] = sigma_j, Q_out the
+ * responses (n x max_out complex column-major, q_j^H M q_k = delta_jk, the entry of largest magnitude real positive; NULL: none),
+ * F_out the forcings f_j = R^H M q_j / sigma_j (same shape, f_j^H M f_k = delta_jk, R M f_j = sigma_j q_j; one checked adjoint
+ * solve each after convergence; needs Q_out; NULL: none), est_out[max_out].  counts (NULL or 4 entries): accepted adjoint and
+ * forward solves of this handle so far, and how many of each carried the refinement step.  Returns LSA_OK also when fewer than nev
+ * gains converged (see result). */
+int lsa_resolvent_solve(lsa_ctx *ctx, lsa_resolvent *r, const lsa_ks_options *opts, const void *v0, int32_t max_out, double *theta_out,
+                        double *gain_out, void *Q_out, void *F_out, double *est_out, lsa_ks_result *result, int64_t *counts);
+
 /* ---- MatrixMarket reader (host only): the A.mtx / M.mtx stage boundary --------------------------------------------
  * Stands in for scipy.io.mmread + the per-entry setValue loop of iPETScMatrix.from_path / from_matrix
  * (FEM/utils.py:143-147,208-215).  Coordinate format; general / symmetric / hermitian / skew-symmetric; real / integer /

@@ -798,9 +798,11 @@ class iEpsSolver:
             self._v0_cache = cached
         return cached[1]
 
-    def _open(self) -> dict:
+    def _open(self, basis: bool = True) -> dict:
         """First part of :meth:`solve`: the operator (built and factorised) and, unless the symmetric iteration is tried first,
-        the Krylov basis.  Returns the run's state for :meth:`_run` and :meth:`_collect`; the caller clears it."""
+        the Krylov basis (``basis=False``: the operator alone, for a caller that brings its own basis --
+        :class:`Solver.resolvent.ResolventSolver`).  Returns the run's state for :meth:`_run` and :meth:`_collect`; the caller
+        clears it."""
         import lsa_hip
 
         self.prepare()
@@ -846,7 +848,7 @@ class iEpsSolver:
             run["mask"] = keep if part is None else part.pad_vector(np.ones(n) if keep is None else keep)
             if keep is not None:
                 op.set_projection(run["mask"])
-            if not use_lanczos:
+            if basis and not use_lanczos:
                 self._open_krylov_basis(run)
         except BaseException:
             run.clear()

@@ -732,6 +732,132 @@ void ks_fill_result(lsa_ks_result* r, const KsClock& clk, int nconv, int nout, i
     r->next_unconverged = next_unconverged;
 }
 
+// ---- the thick-restart Lanczos loop, once, for the two bases it serves ------------------------------------------------------------
+// The real M-orthonormal basis of a symmetric-definite pencil (lanczos.hip) and the complex one of the resolvent's W (resolvent.hip)
+// have one and the same real symmetric projected matrix; the loop reaches a basis through extend, inject, restart and vectors, and
+// ranks and maps the Ritz values through key and back.
+struct TrlRealBasis {
+    using scalar = double;
+    lsa_ctx* ctx;
+    lsa_lanczos* l;
+    Selector sel;
+    int64_t n = 0;
+    int32_t m = 0;
+    void random(Rng& rng, std::vector<double>& vec) const {
+        double other = 0.0;
+        for (int64_t i = 0; i < n; ++i) rng.normal_pair(vec[(size_t)i], other);
+    }
+    int inject(int j, const double* v) { return lanczos_inject(ctx, l, j, v); }
+    int extend(int j, double* T, int ldt, int32_t* bd) { return lsa_lanczos_extend(ctx, l, j, m, T, ldt, bd); }
+    int restart(int knew, const double* Yk) { return lanczos_restart(ctx, l, m, knew, Yk, m); }
+    int vectors(int nout, const double* Yo, const double*, double* X) { return lanczos_ritz_vectors(ctx, l, m, nout, Yo, m, X); }
+    double key(double theta) const { return sel.key(Z{theta, 0.0}); }
+    double back(double theta) const { return sel.back(Z{theta, 0.0}).re; }
+};
+
+struct TrlResolventBasis {
+    using scalar = cplx;
+    lsa_ctx* ctx;
+    lsa_resolvent* r;
+    cplx* F;  // the forcings' destination, or null
+    int64_t n = 0;
+    int32_t m = 0;
+    void random(Rng& rng, std::vector<cplx>& vec) const {
+        for (int64_t i = 0; i < n; ++i) rng.normal_pair(vec[(size_t)i].re, vec[(size_t)i].im);
+    }
+    int inject(int j, const cplx* v) { return resolvent_inject(ctx, r, j, v); }
+    int extend(int j, double* T, int ldt, int32_t* bd) { return lsa_resolvent_extend(ctx, r, j, m, T, ldt, bd); }
+    int restart(int knew, const double* Yk) { return resolvent_restart(ctx, r, m, knew, Yk, m); }
+    int vectors(int nout, const double* Yo, const double* gains, cplx* Q) {
+        LSA_CHECK(resolvent_ritz_vectors(ctx, r, m, nout, Yo, m, Q));
+        return F ? resolvent_forcings(ctx, r, nout, gains, F) : LSA_OK;
+    }
+    double key(double theta) const { return -theta; }  // the largest gains first
+    double back(double theta) const { return theta > 0.0 ? std::sqrt(theta) : 0.0; }  // theta = sigma^2
+};
+
+template <class Basis>
+int trl_solve(lsa_ctx* ctx, Basis& b, const lsa_ks_options* o, const typename Basis::scalar* v0, int32_t max_out, double* theta_out,
+              double* lambda_out, typename Basis::scalar* X_out, double* est_out, lsa_ks_result* result) {
+    using S = typename Basis::scalar;
+    const int32_t m = b.m;
+    const int64_t n = b.n;
+    max_out = std::min(max_out, m);
+    const int nev = std::min<int>(o->nev, m);
+    const double keep_fraction = ks_keep_fraction(o);
+    Rng rng = ks_rng(o);
+    std::vector<S> vec((size_t)n);
+    if (v0) memcpy(vec.data(), v0, (size_t)n * sizeof(S));
+    else b.random(rng, vec);
+    LSA_CHECK(b.inject(0, vec.data()));
+    const int ldt = m + 1;
+    std::vector<double> T((size_t)ldt * m, 0.0), Y((size_t)m * m), theta((size_t)m), est((size_t)m), rel((size_t)m), keys((size_t)m);
+    std::vector<int> rank((size_t)m);
+    auto Tm = [&](int r, int c) -> double& { return T[(size_t)c * ldt + r]; };
+    int kept = 0, restarts = 0;
+    int64_t applies = 0;
+    memset(result, 0, sizeof *result);
+    KsClock clk;
+    auto extend = [&](int j, int32_t* bd) { return b.extend(j, T.data(), ldt, bd); };
+    auto inject_random = [&](int j) {
+        b.random(rng, vec);
+        return b.inject(j, vec.data());
+    };
+    while (true) {
+        clk.start();
+        LSA_CHECK(ks_expand(kept, m, &applies, extend, inject_random));
+        clk.lap(clk.expand);
+        const double beta = Tm(m, m - 1);
+        for (int c = 0; c < m; ++c)
+            for (int r = 0; r < m; ++r) Y[(size_t)c * m + r] = Tm(r, c);
+        // ---- Ritz pairs and residual estimates ----
+        if (!sym_eig(m, Y.data(), m, theta.data()))
+            return lsa_set_error(ctx, LSA_ERR_DIVERGED, "Lanczos: the QL algorithm on the projected matrix did not converge");
+        for (int c = 0; c < m; ++c) {
+            est[(size_t)c] = std::fabs(beta * Y[(size_t)c * m + (m - 1)]);
+            keys[(size_t)c] = b.key(theta[(size_t)c]);
+            rel[(size_t)c] = est[(size_t)c] / std::max(std::fabs(theta[(size_t)c]), 2.2250738585072014e-308);
+        }
+        const int nconv = ks_rank_converged(m, keys, rel, o->tol, rank);
+        if (nconv >= nev || nconv >= m || restarts >= o->max_restarts) {
+            const int nout = std::min<int>(nconv, max_out);
+            if (nout > 0) {
+                std::vector<double> Yo((size_t)m * nout);
+                for (int c = 0; c < nout; ++c) {
+                    const int src = rank[(size_t)c];
+                    memcpy(&Yo[(size_t)c * m], &Y[(size_t)src * m], (size_t)m * sizeof(double));
+                    theta_out[c] = theta[(size_t)src];
+                    lambda_out[c] = b.back(theta[(size_t)src]);
+                    if (est_out) est_out[c] = rel[(size_t)src];
+                }
+                clk.lap(clk.dense);
+                if (X_out) LSA_CHECK(b.vectors(nout, Yo.data(), lambda_out, X_out));
+                clk.lap(clk.restart);
+            }
+            clk.lap(clk.dense);
+            ks_fill_result(result, clk, nconv, nout, restarts, applies, nconv < m ? rel[(size_t)rank[(size_t)nconv]] : 0.0);
+            return LSA_OK;
+        }
+        // ---- keep the wanted Ritz vectors and restart: T <- diag(theta_kept) with the spike beta y_{m,i} in row and column knew ----
+        const int knew = ks_keep_count(m, nconv, keep_fraction);
+        std::vector<double> Yk((size_t)m * knew);
+        for (int c = 0; c < knew; ++c) memcpy(&Yk[(size_t)c * m], &Y[(size_t)rank[(size_t)c] * m], (size_t)m * sizeof(double));
+        clk.lap(clk.dense);
+        LSA_CHECK(b.restart(knew, Yk.data()));
+        clk.lap(clk.restart);
+        std::fill(T.begin(), T.end(), 0.0);
+        for (int c = 0; c < knew; ++c) {
+            const int src = rank[(size_t)c];
+            Tm(c, c) = theta[(size_t)src];
+            const double spike = beta * Y[(size_t)src * m + (m - 1)];
+            Tm(knew, c) = spike;
+            Tm(c, knew) = spike;
+        }
+        kept = knew;
+        ++restarts;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1171,13 +1297,12 @@ int lsa_dense_syev(int32_t n, double* A, int32_t lda, double* w) {
 // Thick-restart Lanczos = the symmetric variant of Krylov-Schur (SLEPc's EPSSolve_KrylovSchur_Symm behind EPS_GHEP / EPS_HEP): the
 // loop of lsa_krylov_solve with a real M-orthonormal basis (lanczos.hip), a real symmetric projected matrix T (after a restart:
 // diag(theta_1..theta_k) with the spike beta y_{m,i} in row and column k, tridiagonal behind it) and lsa_dense_syev in place of the
-// complex Schur form.
+// complex Schur form.  The loop itself is trl_solve (above), which the resolvent iteration shares.
 int lsa_lanczos_solve(lsa_ctx* ctx, lsa_lanczos* l, const lsa_ks_options* o, const double* v0, int32_t max_out, double* theta_out,
                       double* lambda_out, double* X_out, double* est_out, lsa_ks_result* result) {
     if (!ctx || !l || !o || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_solve: null argument");
-    int32_t m = 0;
-    int64_t n = 0;
-    LSA_CHECK(lanczos_shape(l, &n, &m));
+    TrlRealBasis b{ctx, l, Selector{}};
+    LSA_CHECK(lanczos_shape(l, &b.n, &b.m));
     LSA_CHECK(ks_check_options(ctx, "lsa_lanczos_solve", o, max_out, theta_out, lambda_out));
     if (o->transform != 0 || o->sigma[1] != 0.0 || o->target[1] != 0.0)
         return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_solve: shift-invert (transform 0) with a real shift and a real target only");
@@ -1186,85 +1311,21 @@ int lsa_lanczos_solve(lsa_ctx* ctx, lsa_lanczos* l, const lsa_ks_options* o, con
         case LSA_WHICH_SMALLEST_REAL: break;
         default: return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_solve: which = %d has no meaning for a real spectrum", o->which);
     }
-    max_out = std::min(max_out, m);
-    const int nev = std::min<int>(o->nev, m);
-    const double keep_fraction = ks_keep_fraction(o);
-    const Selector sel{o->which, 0, {o->sigma[0], 0.0}, {0.0, 0.0}, {o->target[0], 0.0}};
-    Rng rng = ks_rng(o);
-    std::vector<double> vec((size_t)n);
-    auto random_vector = [&]() {
-        double other = 0.0;
-        for (int64_t i = 0; i < n; ++i) rng.normal_pair(vec[(size_t)i], other);
-    };
-    if (v0) memcpy(vec.data(), v0, (size_t)n * sizeof(double));
-    else random_vector();
-    LSA_CHECK(lanczos_inject(ctx, l, 0, vec.data()));
-    const int ldt = m + 1;
-    std::vector<double> T((size_t)ldt * m, 0.0), Y((size_t)m * m), theta((size_t)m), est((size_t)m), rel((size_t)m), keys((size_t)m);
-    std::vector<int> rank((size_t)m);
-    auto Tm = [&](int r, int c) -> double& { return T[(size_t)c * ldt + r]; };
-    int kept = 0, restarts = 0;
-    int64_t applies = 0;
-    memset(result, 0, sizeof *result);
-    KsClock clk;
-    auto extend = [&](int j, int32_t* bd) { return lsa_lanczos_extend(ctx, l, j, m, T.data(), ldt, bd); };
-    auto inject_random = [&](int j) {
-        random_vector();
-        return lanczos_inject(ctx, l, j, vec.data());
-    };
-    while (true) {
-        clk.start();
-        LSA_CHECK(ks_expand(kept, m, &applies, extend, inject_random));
-        clk.lap(clk.expand);
-        const double beta = Tm(m, m - 1);
-        for (int c = 0; c < m; ++c)
-            for (int r = 0; r < m; ++r) Y[(size_t)c * m + r] = Tm(r, c);
-        // ---- Ritz pairs and residual estimates ----
-        if (!sym_eig(m, Y.data(), m, theta.data()))
-            return lsa_set_error(ctx, LSA_ERR_DIVERGED, "Lanczos: the QL algorithm on the projected matrix did not converge");
-        for (int c = 0; c < m; ++c) {
-            est[(size_t)c] = std::fabs(beta * Y[(size_t)c * m + (m - 1)]);
-            keys[(size_t)c] = sel.key(Z{theta[(size_t)c], 0.0});
-            rel[(size_t)c] = est[(size_t)c] / std::max(std::fabs(theta[(size_t)c]), 2.2250738585072014e-308);
-        }
-        const int nconv = ks_rank_converged(m, keys, rel, o->tol, rank);
-        if (nconv >= nev || nconv >= m || restarts >= o->max_restarts) {
-            const int nout = std::min<int>(nconv, max_out);
-            if (nout > 0) {
-                std::vector<double> Yo((size_t)m * nout);
-                for (int c = 0; c < nout; ++c) {
-                    const int src = rank[(size_t)c];
-                    memcpy(&Yo[(size_t)c * m], &Y[(size_t)src * m], (size_t)m * sizeof(double));
-                    theta_out[c] = theta[(size_t)src];
-                    lambda_out[c] = sel.back(Z{theta[(size_t)src], 0.0}).re;
-                    if (est_out) est_out[c] = rel[(size_t)src];
-                }
-                clk.lap(clk.dense);
-                if (X_out) LSA_CHECK(lanczos_ritz_vectors(ctx, l, m, nout, Yo.data(), m, X_out));
-                clk.lap(clk.restart);
-            }
-            clk.lap(clk.dense);
-            ks_fill_result(result, clk, nconv, nout, restarts, applies, nconv < m ? rel[(size_t)rank[(size_t)nconv]] : 0.0);
-            return LSA_OK;
-        }
-        // ---- keep the wanted Ritz vectors and restart: T <- diag(theta_kept) with the spike beta y_{m,i} in row and column knew ----
-        const int knew = ks_keep_count(m, nconv, keep_fraction);
-        std::vector<double> Yk((size_t)m * knew);
-        for (int c = 0; c < knew; ++c) memcpy(&Yk[(size_t)c * m], &Y[(size_t)rank[(size_t)c] * m], (size_t)m * sizeof(double));
-        clk.lap(clk.dense);
-        LSA_CHECK(lanczos_restart(ctx, l, m, knew, Yk.data(), m));
-        clk.lap(clk.restart);
-        std::fill(T.begin(), T.end(), 0.0);
-        for (int c = 0; c < knew; ++c) {
-            const int src = rank[(size_t)c];
-            Tm(c, c) = theta[(size_t)src];
-            const double spike = beta * Y[(size_t)src * m + (m - 1)];
-            Tm(knew, c) = spike;
-            Tm(c, knew) = spike;
-        }
-        kept = knew;
-        ++restarts;
-    }
+    b.sel = Selector{o->which, 0, {o->sigma[0], 0.0}, {0.0, 0.0}, {o->target[0], 0.0}};
+    return trl_solve(ctx, b, o, v0, max_out, theta_out, lambda_out, X_out, est_out, result);
+}
+
+// The resolvent iteration (resolvent.hip): the same loop on the complex basis of W = C^-1 M C^-H M; theta_j = sigma_j^2, largest first.
+int lsa_resolvent_solve(lsa_ctx* ctx, lsa_resolvent* r, const lsa_ks_options* o, const void* v0, int32_t max_out, double* theta_out,
+                        double* gain_out, void* Q_out, void* F_out, double* est_out, lsa_ks_result* result, int64_t* counts) {
+    if (!ctx || !r || !o || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_solve: null argument");
+    if (F_out && !Q_out) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_solve: the forcings are computed from the responses: F_out needs Q_out");
+    TrlResolventBasis b{ctx, r, (cplx*)F_out};
+    LSA_CHECK(resolvent_shape(r, &b.n, &b.m));
+    LSA_CHECK(ks_check_options(ctx, "lsa_resolvent_solve", o, max_out, theta_out, gain_out));
+    const int rc = trl_solve(ctx, b, o, (const cplx*)v0, max_out, theta_out, gain_out, (cplx*)Q_out, est_out, result);
+    if (counts) resolvent_counts(r, counts);
+    return rc;
 }
 
 }  // extern "C"

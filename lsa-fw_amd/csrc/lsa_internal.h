@@ -305,7 +305,9 @@ int basis_times_host_matrix(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, co
 // The direct inner solve of a Krylov step, queued without a read-back: y = C^-1 rhs, z = C y and, with refine, one step of
 // iterative refinement (r = rhs - z, z = C^-1 r, y += z, z = C y; the two sums of that residual pass land in norms[0..2]).  C is
 // the operator's factorised matrix with its exact LU, rows and exchanges as the operator has them; the caller judges rhs - z.
-int direct_solve_enqueue(lsa_ctx* ctx, lsa_op* op, int dtype, const void* rhs, void* y, void* z, void* r, bool refine, double* norms);
+// direction: -1 the operator's own (lsa_op_set_adjoint), 0 C^-1, 1 C^-H on the same factors (one rank), whatever the operator's is.
+int direct_solve_enqueue(lsa_ctx* ctx, lsa_op* op, int dtype, const void* rhs, void* y, void* z, void* r, bool refine, double* norms,
+                         int direction = -1);
 // books one accepted direct solve of relative residual res / bnorm: `products` sparse products besides the refinement's one
 void stats_book_direct_solve(lsa_stats* st, int products, bool refine, double res, double bnorm);
 
@@ -333,6 +335,7 @@ struct lsa_op_parts {
     const lsa_mat *Kmul, *Kfac;  // y = Kfac^-1 (Kmul x); Kmul null: standard problem
     lsa_ndlu* nd;                // exact LU of Kfac, or null
     bool plain;                  // forward, unprojected, whole on this rank
+    bool shift_invert, adjoint, projected, one_rank;  // what `plain` is made of, for callers that say which one is missing
     double ksp_rtol;
     double normF;                // ||Kfac||_F (0: unknown): the scale of the backward-error judgement of a direct solve
     bool* refine;                // the operator's flag: solves carry one step of iterative refinement
@@ -347,6 +350,20 @@ int lanczos_inject(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, const double* host_v
 int lanczos_restart(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t knew, const double* Y, int32_t ldy);
 // X = V[:, 0:m] Y to the host in the caller's row numbering, each column's entry of largest magnitude positive
 int lanczos_ritz_vectors(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t nvec, const double* Y, int32_t ldy, double* X);
+
+// ---- the resolvent iteration (resolvent.hip): a complex basis, M-orthonormal, for W = C^-1 M C^-H M; the loop is the one of
+// lsa_lanczos_solve (dense.hip), which reaches either basis through these pieces ------------------------------------------------
+int resolvent_shape(const lsa_resolvent* r, int64_t* n, int32_t* ncv);
+int resolvent_inject(lsa_ctx* ctx, lsa_resolvent* r, int32_t j, const cplx* host_v);
+// Y: real, m x knew column-major on the host (the eigenvectors of the real projected matrix)
+int resolvent_restart(lsa_ctx* ctx, lsa_resolvent* r, int32_t m, int32_t knew, const double* Y, int32_t ldy);
+// Q = V[:, 0:m] Y to the host in the caller's row numbering, each column's entry of largest magnitude real positive; the columns stay
+// on the device for resolvent_forcings
+int resolvent_ritz_vectors(lsa_ctx* ctx, lsa_resolvent* r, int32_t m, int32_t nvec, const double* Y, int32_t ldy, cplx* Q);
+// F[:, c] = -C^-H M q_c / gain[c] for the columns resolvent_ritz_vectors left: one checked adjoint solve each
+int resolvent_forcings(lsa_ctx* ctx, lsa_resolvent* r, int32_t nvec, const double* gain, cplx* F);
+// accepted adjoint solves, accepted forward solves, and how many of each carried the refinement step
+void resolvent_counts(const lsa_resolvent* r, int64_t counts[4]);
 
 // ---- ILU (ilu.hip) -------------------------------------------------------------------------------------
 struct lsa_ilu {

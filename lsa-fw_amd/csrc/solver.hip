@@ -852,6 +852,10 @@ int lsa_op_get_parts(lsa_op* op, lsa_op_parts* out) {
     // unprojected, whole on one rank
     out->plain = op->Kfac && op->Kfac == op->owned && op->Kmul == op->M_whole && !op->owned_mul && !op->adjoint && !op->keep && !op->nd_dist &&
                  op->ctx->nranks == 1;
+    out->shift_invert = op->Kfac && op->Kfac == op->owned && op->Kmul == op->M_whole && !op->owned_mul;
+    out->adjoint = op->adjoint;
+    out->projected = op->keep != nullptr;
+    out->one_rank = !op->nd_dist && op->ctx->nranks == 1;
     out->ksp_rtol = op->opts.ksp_rtol;
     out->normF = op->normF;
     out->refine = &op->refine;
@@ -859,11 +863,14 @@ int lsa_op_get_parts(lsa_op* op, lsa_op_parts* out) {
     return LSA_OK;
 }
 
-int direct_solve_enqueue(lsa_ctx* ctx, lsa_op* op, int dtype, const void* rhs, void* y, void* z, void* r, bool refine, double* norms) {
-    const PcRef pc = pc_of(op);
+int direct_solve_enqueue(lsa_ctx* ctx, lsa_op* op, int dtype, const void* rhs, void* y, void* z, void* r, bool refine, double* norms, int direction) {
+    PcRef pc = pc_of(op);
+    // (an explicit direction leaves the operator's own, and with it the refinement state lsa_op_set_adjoint would clear, alone)
+    const bool adjoint = direction < 0 ? op->adjoint : direction != 0;
+    pc.adjoint = adjoint;
     const lsa_mat* C = op->Kfac;
     LSA_CHECK(pc_global(ctx, pc, C->row0, op->n, dtype, rhs, y));
-    LSA_CHECK(spmv_global(ctx, C, dtype, y, z, op->adjoint));
+    LSA_CHECK(spmv_global(ctx, C, dtype, y, z, adjoint));
     if (refine) {
         // y += C^-1 (rhs - C y): the factors of a large 3D problem leave 1e-11 of the right-hand side behind, this step takes it to
         // rounding level
@@ -871,7 +878,7 @@ int direct_solve_enqueue(lsa_ctx* ctx, lsa_op* op, int dtype, const void* rhs, v
         LSA_CHECK(pc_global(ctx, pc, C->row0, op->n, dtype, r, z));
         const double one[2] = {1.0, 0.0};
         LSA_CHECK(k_axpy(ctx, dtype, op->n, one, z, y));
-        LSA_CHECK(spmv_global(ctx, C, dtype, y, z, op->adjoint));
+        LSA_CHECK(spmv_global(ctx, C, dtype, y, z, adjoint));
     }
     return LSA_OK;
 }

@@ -1,0 +1,143 @@
+"""Optimal gains: the library's resolvent iteration against what a user can drive from the host on kept factors.
+
+    python tools/resolvent_ab.py [--cases S30k C160k] [--reps 3] [--out profiles/resolvent_ab.json]
+
+``library`` (a): ``Solver.resolvent.ResolventSolver.solve`` -- set-up, one factorisation of ``A - i omega M``, the thick-restart Lanczos
+iteration on ``W = C^-1 M C^-H M`` with both inner solves, their checks and the orthogonalisation on the device, one read-back per step.
+``host`` (b): ARPACK on a ``LinearOperator`` whose product is ``iKSP.solve_many(adjoint=True)`` then ``iKSP.solve`` on ONE kept
+factorisation of the same matrix, the two products with ``M`` in scipy: two host round trips and two host-side verifications per
+product.  ``W`` is self-adjoint in the ``M``-inner product, not in the Euclidean one ARPACK's symmetric driver assumes, and ``M`` is
+singular (no ``M^(1/2)``, no ``M^-1``), so (b) runs the general driver ``eigs`` on ``W`` and takes the real parts.
+
+num_modes 6, ncv 32, tolerance 1e-8; omega = the imaginary part of the case's bench target (S30k: 0.738, C160k: 0, real factors).
+Every timed sample builds its solver anew (construction, preparation, factorisation, iteration, release inside the clock); the two
+settings alternate in one process after one warm-up of each; medians and spread over ``reps`` samples.  The gains of (b) are
+compared with those of (a).  Launches and read-backs per step are counted from the step's code (``csrc/resolvent.hip``), not timed;
+the per-kernel times of the three step kernels come from a separate ``rocprofv3 --kernel-trace --stats`` run of ``--only library``.
+No test asserts these times.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path[:0] = [str(ROOT), str(ROOT / "lsa-fw_amd")]
+
+MODES, NCV, TOL = 6, 32, 1e-8
+
+
+def problem(case: str):
+    from synthetic import fem
+
+    if case.startswith("C"):
+        return fem.cube_case(case), float(complex(fem.SIGMA_CUBE).imag)
+    return fem.cylinder_case(case), float(complex(fem.SIGMA_RE50).imag)
+
+
+def library(es, omega: float) -> dict:
+    from Solver.resolvent import ResolventConfig, ResolventSolver
+
+    t0 = time.perf_counter()
+    rs = ResolventSolver(es.A, es.M, ResolventConfig(num_modes=MODES, ncv=NCV, atol=TOL))
+    rs.solver.set_target(complex(0.0, omega))
+    rs.solver.prepare()
+    t1 = time.perf_counter()
+    res = rs.solve(omega, forcings=False)
+    t2 = time.perf_counter()
+    rs.release()
+    st = res.stats
+    steps = max(st["applies"], 1)
+    return {"gains": res.gains, "seconds": time.perf_counter() - t0, "seconds_setup": t1 - t0, "seconds_solve_call": t2 - t1,
+            "seconds_factor": st["seconds_factor"], "seconds_steps": st["seconds_expand"], "seconds_host_dense": st["seconds_dense"],
+            "seconds_restart": st["seconds_restart"], "applies": st["applies"], "restarts": st["restarts"],
+            "refinements": st["refinements"], "seconds_per_step": st["seconds_expand"] / steps, "read_backs_per_step": 1}
+
+
+def host(es, omega: float) -> dict:
+    from Solver.utils import KSPType, PreconditionerType, iKSP
+
+    t0 = time.perf_counter()
+    A, M = sp.csr_matrix(es.A), sp.csr_matrix(es.M)
+    C = (A - 1j * omega * M).tocsr() if omega != 0.0 else A
+    ksp = iKSP(C)
+    ksp.set_type(KSPType.PREONLY)
+    ksp.set_preconditioner(PreconditionerType.LU)
+    ksp.set_tolerances(rtol=1e-10)
+    n = A.shape[0]
+    products = [0]
+
+    def W(v):
+        products[0] += 1
+        z = ksp.solve_many(np.asarray(M @ v, dtype=np.complex128).reshape(n, 1), adjoint=True)[:, 0]
+        return ksp.solve(np.asarray(M @ z, dtype=np.complex128)).as_array()
+
+    t1 = time.perf_counter()
+    W(np.ones(n, dtype=np.complex128))  # orders, analyses, factorises
+    t2 = time.perf_counter()
+    rng = np.random.default_rng(0)
+    v0 = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+    theta = spla.eigs(spla.LinearOperator((n, n), matvec=W, dtype=np.complex128), k=MODES, ncv=NCV, which="LM", tol=TOL, v0=v0,
+                      return_eigenvectors=False)
+    t3 = time.perf_counter()
+    ksp.reset()
+    gains = np.sqrt(np.sort(theta.real)[::-1])
+    return {"gains": gains, "seconds": time.perf_counter() - t0, "seconds_setup": t1 - t0, "seconds_first_product": t2 - t1,
+            "seconds_iteration": t3 - t2, "products": products[0] - 1, "seconds_per_product": (t3 - t2) / max(products[0] - 1, 1),
+            "read_backs_per_product": 2}
+
+
+def plain(run: dict) -> dict:
+    return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in run.items()}
+
+
+def spread(values) -> dict:
+    return {"median": statistics.median(values), "min": min(values), "max": max(values)}
+
+
+def main(argv=None) -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", nargs="+", default=["S30k", "C160k"])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--only", choices=("library", "host"), default=None, help="one setting alone, once per case (for a kernel trace)")
+    ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "resolvent_ab.json")
+    args = ap.parse_args(argv)
+    settings = {"library": library, "host": host}
+    if args.only:
+        for case in args.cases:
+            es, omega = problem(case)
+            print(json.dumps({"case": case, args.only: plain(settings[args.only](es, omega))}), flush=True)
+        return
+    result = {"config": {"num_modes": MODES, "ncv": NCV, "tol": TOL, "reps": args.reps}, "cases": []}
+    for case in args.cases:
+        es, omega = problem(case)
+        warm = {name: fn(es, omega) for name, fn in settings.items()}  # warm-up: code objects, buffers
+        runs = {name: [] for name in settings}
+        for _ in range(args.reps):
+            for name, fn in settings.items():
+                runs[name].append(fn(es, omega))
+        a, b = warm["library"]["gains"], warm["host"]["gains"]
+        entry = {"case": case, "n": int(es.A.shape[0]), "omega": omega,
+                 "gain_difference": float(np.abs(a - b).max() / a[0]) if a.shape == b.shape else None,
+                 "library": {"seconds": spread([r["seconds"] for r in runs["library"]]),
+                             "seconds_per_step": spread([r["seconds_per_step"] for r in runs["library"]]), "last": plain(runs["library"][-1])},
+                 "host": {"seconds": spread([r["seconds"] for r in runs["host"]]),
+                          "seconds_per_product": spread([r["seconds_per_product"] for r in runs["host"]]), "last": plain(runs["host"][-1])}}
+        entry["speedup_median"] = entry["host"]["seconds"]["median"] / entry["library"]["seconds"]["median"]
+        result["cases"].append(entry)
+        print(json.dumps(entry), flush=True)
+    args.out.parent.mkdir(parents=True, exist_ok=True)
+    args.out.write_text(json.dumps(result, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
