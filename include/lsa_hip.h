@@ -506,6 +506,47 @@ int lsa_resolvent_basis(lsa_ctx *ctx, const lsa_resolvent *r, int32_t ncols, voi
 int lsa_resolvent_solve(lsa_ctx *ctx, lsa_resolvent *r, const lsa_ks_options *opts, const void *v0, int32_t max_out, double *theta_out,
                         double *gain_out, void *Q_out, void *F_out, double *est_out, lsa_ks_result *result, int64_t *counts);
 
+/* ---- transient growth: optimal energy gains and initial conditions of M q' = A q over a finite horizon ---------------------------
+ * One implicit-Euler step (M - dt A) q+ = M q is q+ = -sigma C^-1 M q with C = A - sigma M, sigma = 1 / dt; over N steps the propagator
+ * is Phi = (-sigma C^-1 M)^N and its adjoint in the M-inner product Phi+ = (-sigma C^-T M)^N, on the same factors.  The gains
+ * G_1 >= G_2 >= ... = max ||q(N dt)||_M^2 / ||q(0)||_M^2 are the largest eigenvalues of W = Phi+ Phi: the thick-restart Lanczos iteration
+ * of lsa_lanczos_* with a real M-orthonormal basis and a march of 2N solves on ONE factorisation of C behind every step.  The
+ * operator handle is the one of the general path: lsa_op_create, mode 0, sigma = (1 / dt, 0), pc_type 2, A and M real, M symmetric
+ * positive semidefinite. */
+typedef struct lsa_growth lsa_growth;
+/* Basis of ncv + 1 real vectors for horizons of nsteps >= 1 steps.  keep: host array of n doubles in {0, 1}, or NULL for all ones:
+ * rows with 0 (constrained dofs, each decoupled in row and column of A and M) are left out of the flow -- every right-hand side of
+ * the march and every start vector is multiplied by it.  LSA_ERR_ARG, with a message that names the condition, unless the operator
+ * is shift-invert (mode 0) with M, M real, real exact factors, forward, unprojected, on one rank, at a real positive shift. */
+int lsa_growth_create(lsa_ctx *ctx, lsa_op *op, int32_t ncv, int32_t nsteps, const double *keep, lsa_growth **out);
+void lsa_growth_destroy(lsa_growth *g);
+/* as lsa_krylov_set_row_permutation: the vectors of lsa_growth_solve leave in the caller's numbering (keep and the start vectors
+ * are in the basis' own) */
+int lsa_growth_set_row_permutation(lsa_ctx *ctx, lsa_growth *g, const int32_t *perm);
+/* another horizon on the same handle and factors; what follows gives the bytes a new handle with this nsteps gives */
+int lsa_growth_set_steps(lsa_ctx *ctx, lsa_growth *g, int32_t nsteps);
+/* v_0 = keep (.) v, M-normalised on the device (host vector of length n); LSA_ERR_ARG when its M-norm is not positive */
+int lsa_growth_set_start(lsa_ctx *ctx, lsa_growth *g, const double *host_v);
+/* Lanczos steps j = j0 .. j1-1 on W: N forward and N transposed solves, each followed by a product with M, the mask and the factor
+ * -sigma; then the reorthogonalisation and tail of lsa_lanczos_extend.  T as there ((ncv+1) x ncv column-major, ldt >= j1 + 1).
+ * Every solve of the march is checked against the operator's ksp_rtol -- the last one in the step's first reduction, the others
+ * through a device log read back with the step's slot: one host synchronisation per step -- each direction with its own refinement
+ * step once one of its solves missed; LSA_ERR_DIVERGED (naming direction, march index and step) when a solve misses after it. */
+int lsa_growth_extend(lsa_ctx *ctx, lsa_growth *g, int32_t j0, int32_t j1, double *T, int32_t ldt, int32_t *breakdown);
+/* the first ncols columns of the basis, in the basis' own row numbering (n x ncols column-major on the host); for tests */
+int lsa_growth_basis(lsa_ctx *ctx, const lsa_growth *g, int32_t ncols, double *host_V);
+/* The whole iteration, through the loop of lsa_lanczos_solve: Ritz values ranked largest first, accepted on |beta y_mi| / theta_i <=
+ * opts->tol; of opts only nev, max_restarts, tol, seed and keep_fraction are read.  v0: host start vector (n doubles) or NULL (random
+ * from opts->seed).  Outputs, largest gain first: theta_out[max_out] = gain_out[max_out] = G_j; Q0_out the optimal initial conditions
+ * (n x max_out column-major, M-orthonormal, zero on masked rows, the entry of largest magnitude positive; NULL: none); QT_out the
+ * responses Phi q0_j, not normalised (same shape; needs Q0_out; NULL: none); energy_out[j (N + 1) + s] = ||Phi_s q0_j||_M^2 for
+ * s = 0..N (needs Q0_out; NULL: none) -- responses and energies from one more forward march of N checked solves per vector;
+ * est_out[max_out].  counts (NULL or 4 entries): accepted forward and transposed solves of this handle so far, and how many of
+ * each carried the refinement step.  Returns LSA_OK also when fewer than nev gains converged (see result). */
+int lsa_growth_solve(lsa_ctx *ctx, lsa_growth *g, const lsa_ks_options *opts, const double *v0, int32_t max_out, double *theta_out,
+                     double *gain_out, double *Q0_out, double *QT_out, double *energy_out, double *est_out, lsa_ks_result *result,
+                     int64_t *counts);
+
 /* ---- MatrixMarket reader (host only): the A.mtx / M.mtx stage boundary --------------------------------------------
  * Stands in for scipy.io.mmread + the per-entry setValue loop of iPETScMatrix.from_path / from_matrix
  * (FEM/utils.py:143-147,208-215).  Coordinate format; general / symmetric / hermitian / skew-symmetric; real / integer /

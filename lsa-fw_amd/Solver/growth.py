@@ -1,0 +1,234 @@
+"""Transient growth on the MI355X path: optimal energy gains and initial conditions of ``M q' = A q`` over finite horizons.
+
+The third question of a linear stability analysis, beside the eigenvalues of :class:`Solver.eigen.EigenSolver` and the gains of
+:class:`Solver.resolvent.ResolventSolver` (same conventions: ``A x = lambda M x``): how much a perturbation of a *stable* flow can
+grow in finite time, ``G(T) = max ||q(T)||_M^2 / ||q(0)||_M^2``, and from which initial condition.  Time is marched by implicit
+Euler: one step ``(M - dt A) q+ = M q`` is ``q+ = -sigma C^-1 M q`` with ``C = A - sigma M`` and ``sigma = 1 / dt``, the shift-invert
+operator the library factorises.  Over ``N = T / dt`` steps the propagator is ``Phi = (-sigma C^-1 M)^N``, its adjoint in the
+``M``-inner product is ``Phi+ = (-sigma C^-T M)^N`` on the same factors, and the gains are the largest eigenvalues of
+``W = Phi+ Phi``; the library runs its thick-restart Lanczos iteration on it with a march of ``2 N`` solves on ONE nested-dissection
+LU behind every step (``lsa_growth_*``, ``csrc/growth.hip``)::
+
+    cfg = TransientGrowthConfig(dt=0.25, num_modes=2, ncv=12)
+    tg = TransientGrowthSolver(A, M, cfg)
+    res = tg.solve(4.0)                  # res.gains, res.initial, res.responses, res.energy, res.times
+    curve = tg.sweep([2.0, 4.0, 10.0])   # one factorisation for every horizon of this dt
+
+Constrained dofs (Dirichlet rows kept as identity rows in ``A`` and ``M``) are uncoupled scalar ODEs ``q' = q`` and no part of the
+flow; unmasked, each is a spurious "gain" ``(1 - dt)^(-2 N)``.  ``constrained="auto"`` finds and leaves them out.  Crank-Nicolson,
+other energy weights, regional masks and lockstep over horizons are not built.
+"""
+
+from __future__ import annotations
+
+import logging
+import time
+from dataclasses import dataclass, field
+
+import numpy as np
+import scipy.sparse as sp
+
+from .eigen import _require_matching_squares, _wrap
+from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType, symmetry_defect, _SYMMETRY_TOL
+
+logger = logging.getLogger(__name__)
+
+
+@dataclass(frozen=True)
+class TransientGrowthConfig:
+    dt: float  # the implicit-Euler time step
+    num_modes: int = 1  # gains (with their initial conditions and responses) to compute
+    ncv: int = 12  # Krylov subspace dimension
+    atol: float = 1e-8  # relative tolerance on G: |beta y_mi| / theta_i
+    max_it: int = 500  # restarts allowed
+
+
+@dataclass
+class TransientGrowthResult:
+    horizon: float
+    steps: int
+    dt: float
+    gains: np.ndarray  # G_j, descending
+    initial: np.ndarray  # n x k, q0_j^T M q0_k = delta_jk, zero on constrained rows, the entry of largest magnitude positive
+    responses: np.ndarray  # n x k, Phi q0_j (not normalised: its M-norm squared is G_j)
+    energy: np.ndarray  # k x (steps + 1): ||Phi_s q0_j||_M^2 at s = 0..steps
+    times: np.ndarray  # steps + 1: s dt
+    estimates: np.ndarray  # relative residual estimates of G_j
+    stats: dict = field(default_factory=dict)
+
+
+def decoupled_dofs(A, M) -> np.ndarray:
+    """Every index whose row *and* column hold no off-diagonal non-zero in both ``A`` and ``M``: an uncoupled scalar ODE, no part of
+    the flow (sorted)."""
+    n = A.shape[0]
+    coupled = np.zeros(n, dtype=bool)
+    for X in (A, M):
+        C = sp.coo_matrix(X)
+        off = (C.row != C.col) & (C.data != 0)
+        coupled[C.row[off]] = True
+        coupled[C.col[off]] = True
+    return np.flatnonzero(~coupled)
+
+
+def horizon_steps(T, dt: float) -> int:
+    """``T / dt`` as a whole number of steps; ``ValueError`` unless ``T`` is a positive whole multiple of ``dt``
+    (``|T / dt - round(T / dt)| <= 1e-9 T / dt``, at least one step)."""
+    try:
+        ratio = float(T) / dt
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"the horizon must be a real number, got {T!r}") from exc
+    steps = round(ratio) if np.isfinite(ratio) else 0
+    if not np.isfinite(ratio) or steps < 1 or abs(ratio - steps) > 1e-9 * ratio:
+        raise ValueError(f"the horizon T = {T!r} is not a positive whole multiple of dt = {dt!r}")
+    return int(steps)
+
+
+class TransientGrowthSolver:
+    """Optimal energy gains of ``(A, M)`` over horizons ``T = N dt``; thin shell around :class:`iEpsSolver` 's preparation (union
+    pattern, nested-dissection ordering, permuted numbering, upload, LU) and ``lsa_hip.GrowthBasis``.  The operator and its
+    factorisation of ``A - M / dt`` are built by the first :meth:`solve` and kept until :meth:`release`."""
+
+    def __init__(self, A, M, cfg: TransientGrowthConfig, *, constrained="auto", device: int = 0, layout: str = "single",
+                 pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
+                 ksp_rtol: float | None = None) -> None:
+        if A is None:
+            raise ValueError("Operator A is required.")
+        if M is None:
+            raise ValueError("Transient growth needs M: the energy is measured in the M-inner product")
+        if cfg is None:
+            raise ValueError("Transient growth needs a TransientGrowthConfig: the time step dt has no default")
+        A, M = _wrap(A), _wrap(M)
+        _require_matching_squares(A, M)
+        As, Ms = A.as_scipy_array(), M.as_scipy_array()
+        if As.dtype.kind == "c" or Ms.dtype.kind == "c":
+            raise ValueError(f"Transient growth needs real A and M (a real march on real factors); {'A' if As.dtype.kind == 'c' else 'M'} is complex")
+        defect = symmetry_defect(Ms)
+        if not defect <= _SYMMETRY_TOL:
+            raise ValueError(f"Transient growth needs a symmetric M; its relative symmetry defect is {defect:.3e}")
+        self._cfg = cfg
+        if not (np.isfinite(cfg.dt) and cfg.dt > 0.0):
+            raise ValueError(f"dt = {cfg.dt!r} must be a positive time step")
+        if cfg.num_modes < 1:
+            raise ValueError("num_modes must be at least 1")
+        if cfg.ncv <= cfg.num_modes:
+            raise ValueError(f"ncv = {cfg.ncv} must exceed num_modes = {cfg.num_modes}")
+        n = As.shape[0]
+        if constrained is None:
+            self._constrained = np.zeros(0, dtype=np.int64)
+        else:
+            free = decoupled_dofs(As, Ms)
+            if isinstance(constrained, str):
+                if constrained != "auto":
+                    raise ValueError(f"constrained must be 'auto', an index array or None, got {constrained!r}")
+                self._constrained = free
+            else:
+                idx = np.unique(np.asarray(constrained, dtype=np.int64).ravel())
+                if idx.size and (idx[0] < 0 or idx[-1] >= n):
+                    raise ValueError("constrained holds dof indices outside [0, n)")
+                coupled = np.setdiff1d(idx, free)
+                if coupled.size:
+                    raise ValueError(f"constrained index {int(coupled[0])} is coupled to other dofs in A or M ({coupled.size} such indices): only a "
+                                     "dof whose row and column hold no off-diagonal non-zero can be left out of the flow")
+                self._constrained = idx
+        if layout != "single":
+            raise NotImplementedError(f"Transient growth runs on one GPU; the layout is '{layout}'")
+        pc_type = PreconditionerType(pc_type)
+        if pc_type not in (PreconditionerType.LU, PreconditionerType.CHOLESKY) or ilu_levels is not None:
+            raise NotImplementedError("Transient growth needs the exact LU (PreconditionerType.LU): every solve of the march runs on its "
+                                      f"factors; the preconditioner is {pc_type.name}" + ("" if ilu_levels is None else f" with ILU level {ilu_levels}"))
+        eps = iEpsSolver(A, M, device=device, seed=seed, ksp_rtol=ksp_rtol)
+        eps.set_problem_type(iEpsProblemType.GNHEP)
+        eps.set_st_type(iSTType.SINVERT)
+        eps.set_st_pc_type(pc_type)
+        eps.set_tolerances(cfg.atol, cfg.max_it)
+        eps.set_dimensions(cfg.num_modes, cfg.ncv)
+        eps.set_target(1.0 / cfg.dt)
+        self._eps = eps
+        self._seed = seed
+        self._n = n
+        self._run = None  # the operator (with its factors) and the basis, from the first solve to release()
+        self._basis = None
+
+    @property
+    def config(self) -> TransientGrowthConfig:
+        return self._cfg
+
+    @property
+    def constrained(self) -> np.ndarray:
+        """The dof indices left out of the flow (sorted)."""
+        return self._constrained
+
+    @property
+    def solver(self) -> iEpsSolver:
+        """The eigen path's solver object whose preparation this one shares."""
+        return self._eps
+
+    def _open(self, steps: int):
+        import lsa_hip
+
+        eps = self._eps
+        run = eps._open(basis=False)
+        try:
+            prep, op = eps._prepared, run["op"]
+            if prep["pc_code"] != 2 or op.stats().get("pc_fallback"):
+                raise NotImplementedError("Transient growth needs the exact LU; it does not fit the device memory")
+            keep = np.ones(self._n)
+            keep[self._constrained] = 0.0
+            basis = lsa_hip.GrowthBasis(prep["ctx"], op, run["ncv"], steps, keep[prep["perm"]])  # (the iteration runs in permuted numbering)
+            basis.set_row_permutation(prep["perm"])
+        except BaseException:
+            run.clear()
+            raise
+        self._run, self._basis = run, basis
+
+    def solve(self, T: float) -> TransientGrowthResult:
+        """Gains, initial conditions, responses and energy curves at the horizon ``T``, a positive whole multiple of ``dt``.  The first
+        call orders, analyses and factorises ``A - M / dt``; every later one changes the number of steps only and returns the bytes a
+        fresh solver gives for its horizon."""
+        cfg = self._cfg
+        steps = horizon_steps(T, cfg.dt)
+        started = time.time()
+        reused = self._basis is not None
+        if reused:
+            self._basis.set_steps(steps)
+        else:
+            self._open(steps)
+        run, basis = self._run, self._basis
+        nev, op = run["nev"], run["op"]
+        before = op.stats()
+        rng = np.random.default_rng(self._seed)
+        out = basis.solve(nev, cfg.atol, cfg.max_it, v0=rng.standard_normal(basis.n), seed=self._seed, max_out=nev)
+        st = op.stats()
+        k = len(out["gains"])
+        if out["nconv"] < nev:
+            logger.warning("Transient growth: %d of %d gains converged in %d restarts (next estimate %.3e)", out["nconv"], nev, out["restarts"],
+                           out["next_unconverged"])
+        stats = {"applies": out["applies"], "restarts": out["restarts"], "nconv": out["nconv"], "forward_solves": out["forward_solves"],
+                 "transposed_solves": out["transposed_solves"], "refinements": out["refined_forward"] + out["refined_transposed"],
+                 "refined_forward": out["refined_forward"], "refined_transposed": out["refined_transposed"], "factorisation_reused": reused,
+                 "constrained": int(self._constrained.size), "max_rel_res": st.get("max_rel_res"), "basis_bytes": basis.basis_bytes,
+                 "seconds_factor": st.get("seconds_factor"), "seconds_solve": st.get("seconds_solve") - (before.get("seconds_solve") if reused else 0.0),
+                 "seconds_expand": out["seconds_expand"], "seconds_dense": out["seconds_dense"], "seconds_restart": out["seconds_restart"],
+                 "seconds_total": time.time() - started}
+        return TransientGrowthResult(float(T), steps, cfg.dt, out["gains"], out["initial"][:, :k], out["responses"][:, :k], out["energy"][:k],
+                                     cfg.dt * np.arange(steps + 1), out["estimates"], stats)
+
+    def sweep(self, horizons) -> list[TransientGrowthResult]:
+        """One result per horizon on ONE factorisation: every horizon after the first changes the number of steps only
+        (``stats["factorisation_reused"]``) and returns the bytes a fresh solver gives for it."""
+        for T in horizons:
+            horizon_steps(T, self._cfg.dt)  # (a bad horizon is refused before the first one runs)
+        return [self.solve(T) for T in horizons]
+
+    def release(self) -> None:
+        self._basis = None  # (the basis goes before its operator)
+        if self._run is not None:
+            self._run.clear()
+            self._run = None
+        self._eps.release()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass

@@ -732,9 +732,9 @@ void ks_fill_result(lsa_ks_result* r, const KsClock& clk, int nconv, int nout, i
     r->next_unconverged = next_unconverged;
 }
 
-// ---- the thick-restart Lanczos loop, once, for the two bases it serves ------------------------------------------------------------
-// The real M-orthonormal basis of a symmetric-definite pencil (lanczos.hip) and the complex one of the resolvent's W (resolvent.hip)
-// have one and the same real symmetric projected matrix; the loop reaches a basis through extend, inject, restart and vectors, and
+// ---- the thick-restart Lanczos loop, once, for the three bases it serves ----------------------------------------------------------
+// The real M-orthonormal basis of a symmetric-definite pencil (lanczos.hip), the complex one of the resolvent's W (resolvent.hip) and
+// the real one of the transient-growth W (growth.hip) have one and the same real symmetric projected matrix; the loop reaches a basis through extend, inject, restart and vectors, and
 // ranks and maps the Ritz values through key and back.
 struct TrlRealBasis {
     using scalar = double;
@@ -774,6 +774,28 @@ struct TrlResolventBasis {
     }
     double key(double theta) const { return -theta; }  // the largest gains first
     double back(double theta) const { return theta > 0.0 ? std::sqrt(theta) : 0.0; }  // theta = sigma^2
+};
+
+struct TrlGrowthBasis {
+    using scalar = double;
+    lsa_ctx* ctx;
+    lsa_growth* g;
+    double *QT, *energy;  // the responses' and the energy curves' destinations, or null
+    int64_t n = 0;
+    int32_t m = 0;
+    void random(Rng& rng, std::vector<double>& vec) const {
+        double other = 0.0;
+        for (int64_t i = 0; i < n; ++i) rng.normal_pair(vec[(size_t)i], other);
+    }
+    int inject(int j, const double* v) { return growth_inject(ctx, g, j, v); }
+    int extend(int j, double* T, int ldt, int32_t* bd) { return lsa_growth_extend(ctx, g, j, m, T, ldt, bd); }
+    int restart(int knew, const double* Yk) { return growth_restart(ctx, g, m, knew, Yk, m); }
+    int vectors(int nout, const double* Yo, const double*, double* Q0) {
+        LSA_CHECK(growth_ritz_vectors(ctx, g, m, nout, Yo, m, Q0));
+        return (QT || energy) ? growth_responses(ctx, g, nout, QT, energy) : LSA_OK;
+    }
+    double key(double theta) const { return -theta; }  // the largest gains first
+    double back(double theta) const { return theta; }   // theta = G itself
 };
 
 template <class Basis>
@@ -1325,6 +1347,21 @@ int lsa_resolvent_solve(lsa_ctx* ctx, lsa_resolvent* r, const lsa_ks_options* o,
     LSA_CHECK(ks_check_options(ctx, "lsa_resolvent_solve", o, max_out, theta_out, gain_out));
     const int rc = trl_solve(ctx, b, o, (const cplx*)v0, max_out, theta_out, gain_out, (cplx*)Q_out, est_out, result);
     if (counts) resolvent_counts(r, counts);
+    return rc;
+}
+
+// Transient growth (growth.hip): the same loop on the real basis of W = Phi+ Phi, a march of 2N solves behind every step; theta_j = G_j,
+// largest first.
+int lsa_growth_solve(lsa_ctx* ctx, lsa_growth* g, const lsa_ks_options* o, const double* v0, int32_t max_out, double* theta_out, double* gain_out,
+                     double* Q0_out, double* QT_out, double* energy_out, double* est_out, lsa_ks_result* result, int64_t* counts) {
+    if (!ctx || !g || !o || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_solve: null argument");
+    if ((QT_out || energy_out) && !Q0_out)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_solve: the responses and energies are marched from the initial conditions: they need Q0_out");
+    TrlGrowthBasis b{ctx, g, QT_out, energy_out};
+    LSA_CHECK(growth_shape(g, &b.n, &b.m, nullptr));
+    LSA_CHECK(ks_check_options(ctx, "lsa_growth_solve", o, max_out, theta_out, gain_out));
+    const int rc = trl_solve(ctx, b, o, v0, max_out, theta_out, gain_out, Q0_out, est_out, result);
+    if (counts) growth_counts(g, counts);
     return rc;
 }
 

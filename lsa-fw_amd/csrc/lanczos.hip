@@ -13,6 +13,8 @@
 //     t = M w;  beta^2 = w^T t              lz_dot_kernel on the one extra column
 //     v_{j+1} = w / beta;  rhs' = t / beta  lz_tail_kernel, which also leaves beta^2 and the check's two sums in the step's slot
 // Three products with M per step, one host synchronisation (the read-back of the slot).  For a standard problem (M = NULL) t is w.
+// The first line is the default; lanczos_set_operator puts another operator behind a step (growth.hip: a march of solves), which
+// leaves w, z and the right-hand side of its last solve where the single solve does and judges its solves itself.
 //
 // Every reduction runs in a fixed order (per-thread strided sums, a shuffle tree inside the wavefront, the four wave sums in wave
 // order, the chunks' partial sums strided over 64 lanes and the same tree) and there are no floating-point atomics: two runs give
@@ -279,6 +281,10 @@ struct lsa_lanczos {
     double* qdev = nullptr;      // (ncv + 1)^2: the restart's and the Ritz vectors' coefficients
     int ldp = 0;
     std::vector<double> hslot;
+    // another operator behind a step than the single solve (lanczos_set_operator), and the right-hand side of its last solve: the
+    // check pair of the step's first reduction is (chk_b, z) then
+    const lanczos_operator* hook = nullptr;
+    const double* chk_b = nullptr;
 };
 
 namespace {
@@ -311,6 +317,7 @@ int lz_orth_tail(lsa_ctx* ctx, lsa_lanczos* l, int32_t ncols, int32_t target, bo
     double* vnext = lz_col(l, target);
     double* rhs_next = l->rhs[l->cur ^ 1];
     double* out = l->slot + 2 * (size_t)(l->ncv + 1);
+    const double* chk_b = l->chk_b ? l->chk_b : l->rhs[l->cur];
     if (lz_fused()) {
         // k_multi_dot's chunks: at most 2048 of them, whole multiples of 256 rows, at least 512 rows
         int64_t rows_per_block = ((n + kLzMaxChunks - 1) / kLzMaxChunks + kLzThreads - 1) / kLzThreads * kLzThreads;
@@ -323,21 +330,21 @@ int lz_orth_tail(lsa_ctx* ctx, lsa_lanczos* l, int32_t ncols, int32_t target, bo
             const int tiles = (ncols + 1 + kLzColTile - 1) / kLzColTile;
             const bool c = chk && pass == 0;
             hipLaunchKernelGGL(lz_dot_kernel, dim3(nchunks, tiles), dim3(kLzThreads), 0, ctx->stream, n, ncols, rows_per_block, l->V, n, t, l->w, l->part,
-                               nchunks, c ? l->rhs[l->cur] : nullptr, c ? l->z : nullptr, c ? l->chk_part : nullptr);
+                               nchunks, c ? chk_b : nullptr, c ? l->z : nullptr, c ? l->chk_part : nullptr);
             hipLaunchKernelGGL(lz_update_kernel, dim3(ublocks), dim3(kLzThreads), (size_t)ncols * sizeof(double), ctx->stream, n, ncols, l->V,
                                n, l->part, nchunks, nchunks, l->w, l->slot + (size_t)pass * (l->ncv + 1));
         }
         LSA_CHECK(lz_mass(ctx, l, l->w, l->t));
         const bool c = chk && ncols == 0;
         hipLaunchKernelGGL(lz_dot_kernel, dim3(nchunks, 1), dim3(kLzThreads), 0, ctx->stream, n, 0, rows_per_block, l->V, n, t, l->w, l->part, nchunks,
-                           c ? l->rhs[l->cur] : nullptr, c ? l->z : nullptr, c ? l->chk_part : nullptr);
+                           c ? chk_b : nullptr, c ? l->z : nullptr, c ? l->chk_part : nullptr);
         const int tblocks = (int)std::max<int64_t>(std::min<int64_t>((n + kLzThreads - 1) / kLzThreads, (int64_t)ctx->num_cu * 8), 1);
         hipLaunchKernelGGL(lz_tail_kernel, dim3(tblocks), dim3(kLzThreads), 0, ctx->stream, n, l->w, t, l->part, nchunks, vnext, rhs_next,
                            chk ? l->chk_part : nullptr, nchunks, out);
         return lz_check_launch(ctx, "lanczos step");
     }
     // the unfused form: the library's multi-dot and multi-axpy, the same tail with single partial sums
-    if (chk) LSA_CHECK(k_residual_norms(ctx, LSA_F64, n, l->rhs[l->cur], l->z, l->r, l->chk_part));
+    if (chk) LSA_CHECK(k_residual_norms(ctx, LSA_F64, n, chk_b, l->z, l->r, l->chk_part));
     for (int pass = 0; pass < 2 && ncols > 0; ++pass) {
         LSA_CHECK(lz_mass(ctx, l, l->w, l->t));
         double* h = l->slot + (size_t)pass * (l->ncv + 1);
@@ -357,6 +364,7 @@ int lz_read_slot(lsa_ctx* ctx, lsa_lanczos* l) {
     const size_t bytes = lz_slot_doubles(l->ncv) * sizeof(double);
     LSA_CHECK(lsa_ensure_scratch(ctx, 0, bytes));
     LSA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->pinned, l->slot, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (l->hook) LSA_CHECK(l->hook->read_back(ctx, l->hook->self));  // (its log travels behind the same synchronisation)
     LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(l->hslot.data(), ctx->pinned, bytes);
     return LSA_OK;
@@ -370,6 +378,10 @@ int lanczos_shape(const lsa_lanczos* l, int64_t* n, int32_t* ncv) {
     if (ncv) *ncv = l->ncv;
     return LSA_OK;
 }
+
+void lanczos_set_operator(lsa_lanczos* l, const lanczos_operator* hook) { l->hook = hook; }
+
+const double* lanczos_ritz_device(const lsa_lanczos* l) { return l->V2; }
 
 int lanczos_inject(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, const double* host_v) {
     if (!ctx || !l || !host_v) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos: null argument");
@@ -483,7 +495,23 @@ int lsa_lanczos_extend(lsa_ctx* ctx, lsa_lanczos* l, int32_t j0, int32_t j1, dou
             if (rc != LSA_OK) break;
             l->rhs_for = j;
         }
-        while (true) {
+        while (l->hook) {
+            // the hook's operator: it queues w = OP v_j from rhs = M v_j and names the right-hand side of its last solve (z = C w of
+            // that solve is in l->z); the step's reductions, tail and single read-back are those of the default; the hook judges
+            bool refined = false;
+            rc = l->hook->enqueue(ctx, l->hook->self, j, l->rhs[l->cur], l->w, l->z, l->r, l->slot + b2_at + 4, &l->chk_b, &refined);
+            if (rc == LSA_OK) rc = lz_orth_tail(ctx, l, j + 1, j + 1, true);
+            if (rc == LSA_OK) rc = lz_read_slot(ctx, l);
+            if (rc != LSA_OK) break;
+            const int verdict = l->hook->judge(ctx, l->hook->self, j, std::sqrt(l->hslot[b2_at + 1]), std::sqrt(l->hslot[b2_at + 2]),
+                                               refined ? std::sqrt(l->hslot[b2_at + 4]) : 0.0);
+            if (verdict == 0) break;
+            if (verdict < 0) {  // (the hook has set the error)
+                rc = LSA_ERR_DIVERGED;
+                break;
+            }
+        }
+        while (!l->hook) {
             const bool refine = *l->P.refine;
             // (w += C^-1 (rhs - C w) with refine: takes what large factors leave behind to rounding level)
             rc = direct_solve_enqueue(ctx, l->op, LSA_F64, l->rhs[l->cur], l->w, l->z, l->r, refine, l->chk_part);

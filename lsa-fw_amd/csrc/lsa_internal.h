@@ -338,6 +338,7 @@ struct lsa_op_parts {
     bool shift_invert, adjoint, projected, one_rank;  // what `plain` is made of, for callers that say which one is missing
     double ksp_rtol;
     double normF;                // ||Kfac||_F (0: unknown): the scale of the backward-error judgement of a direct solve
+    double sigma[2];             // the shift the operator was built at
     bool* refine;                // the operator's flag: solves carry one step of iterative refinement
     lsa_stats* st;
 };
@@ -350,6 +351,23 @@ int lanczos_inject(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, const double* host_v
 int lanczos_restart(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t knew, const double* Y, int32_t ldy);
 // X = V[:, 0:m] Y to the host in the caller's row numbering, each column's entry of largest magnitude positive
 int lanczos_ritz_vectors(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t nvec, const double* Y, int32_t ldy, double* X);
+// the columns lanczos_ritz_vectors left on the device (n x nvec, the basis' own row numbering)
+const double* lanczos_ritz_device(const lsa_lanczos* l);
+// Another operator behind a Lanczos step than the single solve w = C^-1 rhs (the default, hook == null): growth.hip's march.
+struct lanczos_operator {
+    void* self;
+    // queue w = OP v_j from rhs = M v_j (rhs stays intact: a step may be done again).  The last solve of the operator leaves C times
+    // its solution in z and the address of its right-hand side in *chk_b: that pair is checked in the step's first reduction.
+    // *refined: the last solve carried the refinement step and left |its solution|^2 at xnorm2_dev.  r: a work vector.
+    int (*enqueue)(lsa_ctx* ctx, void* self, int32_t j, const double* rhs, double* w, double* z, double* r, double* xnorm2_dev, const double** chk_b,
+                   bool* refined);
+    // queue the read-back of what the operator logged on the device; the step's one synchronisation follows
+    int (*read_back)(lsa_ctx* ctx, void* self);
+    // after the synchronisation: res, bnorm (and xnorm when refined) of the last solve.  0: accepted, 1: do the step again, -1: failed
+    // (the error is set)
+    int (*judge)(lsa_ctx* ctx, void* self, int32_t j, double res, double bnorm, double xnorm);
+};
+void lanczos_set_operator(lsa_lanczos* l, const lanczos_operator* hook);  // (hook outlives the basis' steps; null: the default)
 
 // ---- the resolvent iteration (resolvent.hip): a complex basis, M-orthonormal, for W = C^-1 M C^-H M; the loop is the one of
 // lsa_lanczos_solve (dense.hip), which reaches either basis through these pieces ------------------------------------------------
@@ -364,6 +382,21 @@ int resolvent_ritz_vectors(lsa_ctx* ctx, lsa_resolvent* r, int32_t m, int32_t nv
 int resolvent_forcings(lsa_ctx* ctx, lsa_resolvent* r, int32_t nvec, const double* gain, cplx* F);
 // accepted adjoint solves, accepted forward solves, and how many of each carried the refinement step
 void resolvent_counts(const lsa_resolvent* r, int64_t counts[4]);
+
+// ---- transient growth (growth.hip): the real basis of an lsa_lanczos with a march of 2N solves behind every step; the loop is the
+// one of lsa_lanczos_solve (dense.hip), which reaches the handle through these pieces ------------------------------------------------
+int growth_shape(const lsa_growth* g, int64_t* n, int32_t* ncv, int32_t* nsteps);
+// v_j = keep (.) host vector, M-orthonormalised against v_0..v_{j-1}
+int growth_inject(lsa_ctx* ctx, lsa_growth* g, int32_t j, const double* host_v);
+int growth_restart(lsa_ctx* ctx, lsa_growth* g, int32_t m, int32_t knew, const double* Y, int32_t ldy);
+// Q0 = V[:, 0:m] Y to the host in the caller's row numbering, each column's entry of largest magnitude positive; the columns stay on
+// the device for growth_responses
+int growth_ritz_vectors(lsa_ctx* ctx, lsa_growth* g, int32_t m, int32_t nvec, const double* Y, int32_t ldy, double* Q0);
+// QT[:, c] = Phi q0_c and energy[c (N + 1) + s] = ||Phi_s q0_c||_M^2, s = 0..N, for the columns growth_ritz_vectors left: one forward
+// march of N checked solves each (either destination may be null)
+int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, double* energy);
+// accepted forward solves, accepted transposed solves, and how many of each carried the refinement step
+void growth_counts(const lsa_growth* g, int64_t counts[4]);
 
 // ---- ILU (ilu.hip) -------------------------------------------------------------------------------------
 struct lsa_ilu {

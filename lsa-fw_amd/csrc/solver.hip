@@ -469,6 +469,7 @@ struct lsa_op {
     bool nd_dist = false;    // ... subtree-parallel over the ranks: works on whole replicated vectors
     bool adjoint = false;    // y = Kfac^-H Kmul^H x on the same factors (lsa_op_set_adjoint)
     double normF = 0.0;      // ||Kfac||_F
+    double sigma[2] = {0.0, 0.0};  // the shift the operator was built at
     lsa_mat *view_fac = nullptr, *view_mul = nullptr;  // this rank's rows of the whole matrices (subtree-parallel layout)
     const lsa_mat* M_whole = nullptr;                  // the caller's M (modes 0 and 2)
     lsa_op_options opts;
@@ -605,6 +606,8 @@ static int op_build(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, const lsa_
     op->owned = op->owned_diag = nullptr;
     op->pc = nullptr;
     op->opts = *opts;
+    op->sigma[0] = sigma[0];
+    op->sigma[1] = sigma[1];
     op->gw_ready = false;
     op->t = nullptr;
     memset(&op->st, 0, sizeof op->st);
@@ -858,6 +861,8 @@ int lsa_op_get_parts(lsa_op* op, lsa_op_parts* out) {
     out->one_rank = !op->nd_dist && op->ctx->nranks == 1;
     out->ksp_rtol = op->opts.ksp_rtol;
     out->normF = op->normF;
+    out->sigma[0] = op->sigma[0];
+    out->sigma[1] = op->sigma[1];
     out->refine = &op->refine;
     out->st = &op->st;
     return LSA_OK;

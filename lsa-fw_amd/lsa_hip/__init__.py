@@ -216,6 +216,14 @@ SIGNATURES = {
     "lsa_resolvent_extend": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_I32)]),
     "lsa_resolvent_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
     "lsa_resolvent_solve": (ctypes.c_int, [_P, _P, ctypes.POINTER(lsa_ks_options), _P, _I32, _P, _P, _P, _P, _P, ctypes.POINTER(lsa_ks_result), _P]),
+    "lsa_growth_create": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _PP]),
+    "lsa_growth_destroy": (None, [_P]),
+    "lsa_growth_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
+    "lsa_growth_set_steps": (ctypes.c_int, [_P, _P, _I32]),
+    "lsa_growth_set_start": (ctypes.c_int, [_P, _P, _P]),
+    "lsa_growth_extend": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_I32)]),
+    "lsa_growth_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
+    "lsa_growth_solve": (ctypes.c_int, [_P, _P, ctypes.POINTER(lsa_ks_options), _P, _I32, _P, _P, _P, _P, _P, _P, ctypes.POINTER(lsa_ks_result), _P]),
     "lsa_mm_open": (ctypes.c_int, [ctypes.c_char_p, _PP, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int)]),
     "lsa_mm_read_csr": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_mm_error": (ctypes.c_char_p, [_P]),
@@ -1174,6 +1182,98 @@ class ResolventBasis:
     def __del__(self):
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
             self.ctx._lib.lsa_resolvent_destroy(self.handle)
+            self.handle = None
+
+
+class GrowthBasis:
+    """Real ``M``-orthonormal Lanczos basis in HBM for the transient-growth operator ``W = Phi+ Phi``, ``Phi = (-sigma C^-1 M)^N``,
+    ``C = A - sigma M``, ``sigma = 1 / dt`` (``lsa_growth_*``): a march of ``2 N`` solves on one factorisation behind every step.
+    ``op`` must be a shift-invert operator (mode 0) at the real positive ``sigma`` with real exact factors (``pc_type=2``) and a real
+    ``M``; ``keep`` is the 0/1 mask of the free dofs in the operator's row numbering (``None``: all ones)."""
+
+    def __init__(self, ctx: Context, op: ShiftInvertOperator, ncv: int, nsteps: int, keep: np.ndarray | None = None):
+        self.ctx, self._op = ctx, op
+        self.n, self.ncv, self.nsteps = op.n, int(ncv), int(nsteps)
+        k = None
+        if keep is not None:
+            k = np.ascontiguousarray(keep, dtype=np.float64)
+            if k.shape != (self.n,):
+                raise ValueError(f"keep must have shape ({self.n},)")
+        h = ctypes.c_void_p()
+        ctx.check(ctx._lib.lsa_growth_create(ctx.handle, op.handle, self.ncv, self.nsteps, None if k is None else _ptr(k), ctypes.byref(h)))
+        self.handle = h
+        self._has_perm = False
+
+    @property
+    def basis_bytes(self) -> int:
+        """Device bytes of the ``n x (ncv + 1)`` arrays the handle owns: the basis, the restart's second basis and, with a row
+        permutation, the output vectors in the caller's numbering."""
+        return 8 * self.n * (self.ncv + 1) * (3 if self._has_perm else 2)
+
+    def set_row_permutation(self, perm: np.ndarray | None) -> None:
+        """``perm[i]`` = the caller's index of basis row ``i``: the vectors of :meth:`solve` come back in the caller's numbering."""
+        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        self.ctx.check(self.ctx._lib.lsa_growth_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
+        self._has_perm = p is not None
+
+    def set_steps(self, nsteps: int) -> None:
+        """Another horizon of ``nsteps`` steps on the same handle and factors."""
+        self.ctx.check(self.ctx._lib.lsa_growth_set_steps(self.ctx.handle, self.handle, int(nsteps)))
+        self.nsteps = int(nsteps)
+
+    def _start(self, v) -> np.ndarray:
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (self.n,):
+            raise ValueError(f"start vector must have shape ({self.n},)")
+        return v
+
+    def set_start(self, v: np.ndarray) -> None:
+        v = self._start(v)
+        self.ctx.check(self.ctx._lib.lsa_growth_set_start(self.ctx.handle, self.handle, _ptr(v)))
+
+    def extend(self, j0: int, j1: int, T: np.ndarray) -> int:
+        """Steps j0..j1-1 on ``W`` writing ``alpha_j``, ``beta_j`` into the Fortran-ordered (ncv+1, ncv) real T; returns the
+        breakdown step or -1."""
+        assert T.flags.f_contiguous and T.dtype == np.float64
+        bd = _I32(-1)
+        self.ctx.check(self.ctx._lib.lsa_growth_extend(self.ctx.handle, self.handle, int(j0), int(j1), _ptr(T), T.shape[0], ctypes.byref(bd)))
+        return bd.value
+
+    def basis(self, ncols: int) -> np.ndarray:
+        """The first ``ncols`` basis vectors on the host, in the basis' own row numbering."""
+        V = np.empty((self.n, int(ncols)), dtype=np.float64, order="F")
+        self.ctx.check(self.ctx._lib.lsa_growth_basis(self.ctx.handle, self.handle, int(ncols), _ptr(V)))
+        return V
+
+    def solve(self, nev: int, tol: float, max_restarts: int, *, v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None) -> dict:
+        """The whole iteration inside the library (``lsa_growth_solve``).  Returns a dict: ``gains`` (descending), ``initial``
+        (n x k, ``M``-orthonormal), ``responses`` (n x k, ``Phi q0``), ``energy`` (k x (nsteps + 1)), ``estimates``, ``nconv``,
+        ``restarts``, ``applies``, the loop's phase times and the handle's solve counts so far."""
+        max_out = self.ncv if max_out is None else min(int(max_out), self.ncv)
+        o = lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=0, transform=0, sigma=(_DBL * 2)(0.0, 0.0),
+                           antishift=(_DBL * 2)(0.0, 0.0), target=(_DBL * 2)(0.0, 0.0), seed=int(seed), keep_fraction=0.5)
+        theta = np.zeros(max(max_out, 1), dtype=np.float64)
+        gains = np.zeros(max(max_out, 1), dtype=np.float64)
+        est = np.zeros(max(max_out, 1), dtype=np.float64)
+        Q0 = np.zeros((self.n, max_out), dtype=np.float64, order="F")
+        QT = np.zeros((self.n, max_out), dtype=np.float64, order="F")
+        energy = np.zeros((max(max_out, 1), self.nsteps + 1), dtype=np.float64)
+        counts = np.zeros(4, dtype=np.int64)
+        res = lsa_ks_result()
+        v = None if v0 is None else self._start(v0)
+        self.ctx.check(self.ctx._lib.lsa_growth_solve(self.ctx.handle, self.handle, ctypes.byref(o), None if v is None else _ptr(v), max_out,
+                                                      _ptr(theta), _ptr(gains), _ptr(Q0), _ptr(QT), _ptr(energy), _ptr(est), ctypes.byref(res),
+                                                      _ptr(counts)))
+        k = res.nout
+        return {"gains": gains[:k].copy(), "initial": np.asfortranarray(Q0[:, :k]), "responses": np.asfortranarray(QT[:, :k]),
+                "energy": energy[:k].copy(), "estimates": est[:k].copy(), "nconv": int(res.nconv), "restarts": int(res.restarts),
+                "applies": int(res.op_applies), "next_unconverged": float(res.next_unconverged), "seconds_expand": res.seconds_expand,
+                "seconds_dense": res.seconds_dense, "seconds_restart": res.seconds_restart, "forward_solves": int(counts[0]),
+                "transposed_solves": int(counts[1]), "refined_forward": int(counts[2]), "refined_transposed": int(counts[3])}
+
+    def __del__(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx._lib.lsa_growth_destroy(self.handle)
             self.handle = None
 
 

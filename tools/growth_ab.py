@@ -1,0 +1,147 @@
+"""Optimal transient growth: the library's iteration against what a user can drive from the host on kept factors.
+
+    python tools/growth_ab.py [--cases S30k C160k] [--reps 3] [--out profiles/growth_ab.json]
+
+``library`` (a): ``Solver.growth.TransientGrowthSolver.solve`` -- set-up, one factorisation of ``A - M / dt``, the thick-restart Lanczos
+iteration on ``W = Phi+ Phi`` with the march of ``2 N`` solves, its checks, the mask and the orthogonalisation on the device, one
+read-back per step.
+``host`` (b): ``scipy.sparse.linalg.eigsh`` on a ``LinearOperator`` whose product marches through ``iKSP`` on ONE kept factorisation of
+the same matrix (``N`` calls of ``solve``, ``N`` of ``solve_many(adjoint=True)``), the products with ``M`` and the mask in scipy: ``2 N``
+host round trips per product.  ``W`` is self-adjoint in the ``M``-inner product, not in the Euclidean one, and ``M`` is singular (zero
+pressure block), so (b) solves the equivalent symmetric-definite problem ``S y = theta M_uu y`` on the dofs ``u`` that carry mass and are
+free, ``S = (Phi^T M Phi)_uu`` (``Phi = Xi M`` never sees the other dofs of its argument), with SuperLU for ``M_uu``.
+
+dt 0.25, T = 4 (N = 16), num_modes 2, ncv 12, tolerance 1e-8.  Every timed sample builds its solver anew (construction, preparation,
+factorisation, iteration, release inside the clock); the two settings alternate in one process after one warm-up of each; medians
+and spread over ``reps`` samples.  The gains of (b) are compared with those of (a).  No test asserts these times.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path[:0] = [str(ROOT), str(ROOT / "lsa-fw_amd")]
+
+DT, HORIZON, MODES, NCV, TOL = 0.25, 4.0, 2, 12, 1e-8
+
+
+def problem(case: str):
+    from synthetic import fem
+
+    return fem.cube_case(case) if case.startswith("C") else fem.cylinder_case(case)
+
+
+def library(es) -> dict:
+    from Solver.growth import TransientGrowthConfig, TransientGrowthSolver
+
+    t0 = time.perf_counter()
+    tg = TransientGrowthSolver(es.A, es.M, TransientGrowthConfig(dt=DT, num_modes=MODES, ncv=NCV, atol=TOL))
+    tg.solver.prepare()
+    t1 = time.perf_counter()
+    res = tg.solve(HORIZON)
+    t2 = time.perf_counter()
+    tg.release()
+    st = res.stats
+    steps = max(st["applies"], 1)
+    return {"gains": res.gains, "seconds": time.perf_counter() - t0, "seconds_setup": t1 - t0, "seconds_solve_call": t2 - t1,
+            "seconds_factor": st["seconds_factor"], "seconds_steps": st["seconds_expand"], "seconds_host_dense": st["seconds_dense"],
+            "seconds_restart": st["seconds_restart"], "applies": st["applies"], "restarts": st["restarts"], "refinements": st["refinements"],
+            "forward_solves": st["forward_solves"], "transposed_solves": st["transposed_solves"], "constrained": st["constrained"],
+            "seconds_per_step": st["seconds_expand"] / steps, "read_backs_per_step": 1}
+
+
+def host(es) -> dict:
+    from Solver.growth import decoupled_dofs
+    from Solver.utils import KSPType, PreconditionerType, iKSP
+
+    t0 = time.perf_counter()
+    A, M = sp.csr_matrix(es.A), sp.csr_matrix(es.M)
+    n, sigma, steps = A.shape[0], 1.0 / DT, round(HORIZON / DT)
+    keep = np.ones(n)
+    keep[decoupled_dofs(A, M)] = 0.0
+    u = np.flatnonzero((keep == 1.0) & (M.diagonal() > 0.0))  # free dofs that carry mass
+    Muu = M[u][:, u].tocsc()
+    ksp = iKSP((A - sigma * M).tocsr())
+    ksp.set_type(KSPType.PREONLY)
+    ksp.set_preconditioner(PreconditionerType.LU)
+    ksp.set_tolerances(rtol=1e-10)
+    products = [0]
+
+    def S(y):
+        products[0] += 1
+        q = np.zeros(n)
+        q[u] = y
+        for _ in range(steps):  # Phi q
+            q = -sigma * keep * ksp.solve(np.asarray(M @ q, dtype=np.float64)).as_array().real
+        q = M @ q
+        for _ in range(steps):  # Phi^T (M Phi q), Phi^T = (-sigma M C^-T)^N
+            q = -sigma * (M @ (keep * ksp.solve_many(np.asarray(q, dtype=np.float64).reshape(n, 1), adjoint=True)[:, 0].real))
+        return q[u]
+
+    t1 = time.perf_counter()
+    S(np.ones(u.size))  # orders, analyses, factorises
+    t2 = time.perf_counter()
+    v0 = np.random.default_rng(0).standard_normal(u.size)
+    theta = spla.eigsh(spla.LinearOperator((u.size, u.size), matvec=S, dtype=np.float64), k=MODES, M=Muu, ncv=NCV, which="LA", tol=TOL, v0=v0,
+                       return_eigenvectors=False)
+    t3 = time.perf_counter()
+    ksp.reset()
+    return {"gains": np.sort(theta)[::-1], "seconds": time.perf_counter() - t0, "seconds_setup": t1 - t0, "seconds_first_product": t2 - t1,
+            "seconds_iteration": t3 - t2, "products": products[0] - 1, "seconds_per_product": (t3 - t2) / max(products[0] - 1, 1),
+            "read_backs_per_product": 2 * steps}
+
+
+def plain(run: dict) -> dict:
+    return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in run.items()}
+
+
+def spread(values) -> dict:
+    return {"median": statistics.median(values), "min": min(values), "max": max(values)}
+
+
+def main(argv=None) -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", nargs="+", default=["S30k", "C160k"])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--only", choices=("library", "host"), default=None, help="one setting alone, once per case (for a kernel trace)")
+    ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "growth_ab.json")
+    args = ap.parse_args(argv)
+    settings = {"library": library, "host": host}
+    if args.only:
+        for case in args.cases:
+            print(json.dumps({"case": case, args.only: plain(settings[args.only](problem(case)))}), flush=True)
+        return
+    result = {"config": {"dt": DT, "horizon": HORIZON, "num_modes": MODES, "ncv": NCV, "tol": TOL, "reps": args.reps}, "cases": []}
+    for case in args.cases:
+        es = problem(case)
+        warm = {name: fn(es) for name, fn in settings.items()}  # warm-up: code objects, buffers
+        runs = {name: [] for name in settings}
+        for _ in range(args.reps):
+            for name, fn in settings.items():
+                runs[name].append(fn(es))
+        a, b = warm["library"]["gains"], warm["host"]["gains"]
+        entry = {"case": case, "n": int(es.A.shape[0]),
+                 "gain_difference": float(np.abs(a - b).max() / a[0]) if a.shape == b.shape else None,
+                 "library": {"seconds": spread([r["seconds"] for r in runs["library"]]),
+                             "seconds_per_step": spread([r["seconds_per_step"] for r in runs["library"]]), "last": plain(runs["library"][-1])},
+                 "host": {"seconds": spread([r["seconds"] for r in runs["host"]]),
+                          "seconds_per_product": spread([r["seconds_per_product"] for r in runs["host"]]), "last": plain(runs["host"][-1])}}
+        entry["speedup_median"] = entry["host"]["seconds"]["median"] / entry["library"]["seconds"]["median"]
+        result["cases"].append(entry)
+        print(json.dumps(entry), flush=True)
+    args.out.parent.mkdir(parents=True, exist_ok=True)
+    args.out.write_text(json.dumps(result, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
