@@ -101,7 +101,9 @@ int lsa_spmv(lsa_ctx *ctx, const lsa_mat *A, const lsa_vec *x, lsa_vec *y);
 int lsa_spmv_transpose(lsa_ctx *ctx, const lsa_mat *A, int conj, const lsa_vec *x, lsa_vec *y);
 /* Which kernel lsa_spmv launches for this matrix and vector type (template arguments included) and the bytes that
  * kernel moves per launch: values + column indices (2-byte offsets from the row's first column when the compressed form
- * is in use) + row pointers + one read of x and one write of y.  The numerator of an HBM-roofline fraction. */
+ * is in use) + row pointers + one read of x and one write of y.  The numerator of an HBM-roofline fraction.  The name is that
+ * of the launch: the XCD forms are named only where they run (8 x 64 row groups, 8 x 256 / lanes rows), the non-temporal
+ * instances carry their fourth argument. */
 int lsa_spmv_info(lsa_ctx *ctx, const lsa_mat *A, int xdtype, char *kernel, int32_t kernel_len, int64_t *bytes_moved);
 /* Launch y = A x `iters` times back to back on the context's stream, bracketed by HIP events on that
  * stream; *avg_ms = mean duration of one launch.  This is the measurement bench.py's roofline uses. */
@@ -264,7 +266,8 @@ int lsa_ndlu_info(const lsa_ndlu *f, int32_t *ntree, int32_t *nlevels, int32_t *
 
 /* ---- GMRES: KSPSolve of the ST (reference default PREONLY+LU; north star: GMRES+ILU) ----------------- */
 /* right-preconditioned restarted GMRES with CGS2; pc may be NULL.  x holds the initial guess on entry
- * when use_x0 != 0.  Returns LSA_ERR_DIVERGED if rtol is not reached within maxit iterations. */
+ * when use_x0 != 0.  Returns LSA_ERR_DIVERGED if rtol is not reached within maxit iterations.  min(restart, maxit) is
+ * at most 1024 for complex and 2048 for real vectors (what the basis product handles): LSA_ERR_ARG beyond. */
 int lsa_gmres(lsa_ctx *ctx, const lsa_mat *C, lsa_ilu *pc, const lsa_vec *b, lsa_vec *x, int use_x0, double rtol,
               int restart, int maxit, int32_t *iters, double *rel_res);
 
@@ -305,7 +308,8 @@ int lsa_op_set_adjoint(lsa_ctx *ctx, lsa_op *op, int on);
 int lsa_op_set_projection(lsa_ctx *ctx, lsa_op *op, const double *keep);
 
 /* ---- Krylov basis: BV + Arnoldi recurrences of EPS Krylov-Schur (SLEPc.EPS.solve, Solver/utils.py:270) -- */
-/* Basis of up to ncv+1 complex vectors of length n, resident in HBM, column-major. */
+/* Basis of up to ncv+1 complex vectors of length n, resident in HBM, column-major.  ncv <= 1024 (the basis product of
+ * lsa_krylov_restart / lsa_krylov_ritz_vectors keeps a tile of the small matrix in 64 KB of LDS): LSA_ERR_ARG beyond. */
 int lsa_krylov_create(lsa_ctx *ctx, lsa_op *op, int32_t ncv, lsa_krylov **out);
 void lsa_krylov_destroy(lsa_krylov *k);
 /* perm[i] = the caller's index of row i of the basis (the solve runs in a permuted numbering): lsa_krylov_ritz_vectors then

@@ -1109,8 +1109,11 @@ __global__ __launch_bounds__(64) void col_phase_finish_kernel(cplx* __restrict__
 }
 
 // Out[i, k0+t] = sum_c V[i, c] Q[c, k0+t], t < kOutTile
-constexpr int kOutTile = 8;  // (round 4: 4 -> 8 halves the passes over a basis that does not fit the caches)
-template <typename T>
+// kOutTile = 8 (round 4: 4 -> 8 halves the passes over a basis that does not fit the caches) while the m x 8 tile of Q fits the
+// 64 KB of LDS a launch gets without asking for more; wider bases (m > 512 complex, > 1024 real) run with tiles of 4 columns
+constexpr int kOutTileMax = 8, kOutTileWide = 4;
+constexpr size_t kBasisGemmLds = 64 * 1024;
+template <typename T, int kOutTile>
 __global__ __launch_bounds__(kThreads) void basis_gemm_kernel(int64_t n, int m, int k, const T* __restrict__ V, int64_t ldv,
                                                               const T* __restrict__ Q, int ldq, T* __restrict__ Out,
                                                               int64_t ldo) {
@@ -1407,16 +1410,29 @@ int k_hess_column(lsa_ctx* ctx, int dtype, int cnt, const void* h1, const void* 
     return check_launch(ctx, "hess_column");
 }
 
+// the widest basis k_basis_gemm multiplies: the m x 4 tile of Q must fit 64 KB of LDS (1024 complex columns, 2048 real ones)
+int k_basis_gemm_max_cols(int dtype) { return (int)(kBasisGemmLds / ((size_t)kOutTileWide * (dtype == LSA_C128 ? 16 : 8))); }
+
 int k_basis_gemm(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V, int64_t ldv, const void* Q, int ldq,
                  void* Out, int64_t ldo) {
     if (k <= 0 || m <= 0) return LSA_OK;
     const size_t esz = dtype == LSA_C128 ? 16 : 8;
+    if (m > k_basis_gemm_max_cols(dtype))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "basis product: %d basis columns, at most %d are supported for this scalar type", m, k_basis_gemm_max_cols(dtype));
     int bx = stream_blocks(ctx, n);
-    dim3 grid(bx, (k + kOutTile - 1) / kOutTile);
-    DISPATCH_T(dtype, {
-        hipLaunchKernelGGL((basis_gemm_kernel<T>), grid, dim3(kThreads), (size_t)m * kOutTile * esz, ctx->stream, n, m, k,
-                           (const T*)V, ldv, (const T*)Q, ldq, (T*)Out, ldo);
-    });
+    if ((size_t)m * kOutTileMax * esz <= kBasisGemmLds) {
+        dim3 grid(bx, (k + kOutTileMax - 1) / kOutTileMax);
+        DISPATCH_T(dtype, {
+            hipLaunchKernelGGL((basis_gemm_kernel<T, kOutTileMax>), grid, dim3(kThreads), (size_t)m * kOutTileMax * esz, ctx->stream, n, m, k,
+                               (const T*)V, ldv, (const T*)Q, ldq, (T*)Out, ldo);
+        });
+    } else {
+        dim3 grid(bx, (k + kOutTileWide - 1) / kOutTileWide);
+        DISPATCH_T(dtype, {
+            hipLaunchKernelGGL((basis_gemm_kernel<T, kOutTileWide>), grid, dim3(kThreads), (size_t)m * kOutTileWide * esz, ctx->stream, n, m, k,
+                               (const T*)V, ldv, (const T*)Q, ldq, (T*)Out, ldo);
+        });
+    }
     return check_launch(ctx, "basis_gemm");
 }
 

@@ -59,8 +59,9 @@ inline Z zsqrt(Z a) {
 inline void givens(Z f, Z g, double& c, Z& s, Z& r) {
     // both entries of ordinary size (LAPACK 3.10's zlartg, unscaled branch): one square root and one division on the chain
     // from one rotation of a QR sweep to the next
+    // (squares within (1e-150, 1e150): f2 * h2 <= 2e300 and >= 1e-300 stays a normal number; anything else takes the scaled branch)
     const double f2 = abs2(f), g2 = abs2(g);
-    if (f2 > 1e-200 && f2 < 1e200 && g2 > 1e-200 && g2 < 1e200) {
+    if (f2 > 1e-150 && f2 < 1e150 && g2 > 1e-150 && g2 < 1e150) {
         const double h2 = f2 + g2, d = std::sqrt(f2 * h2), id = 1.0 / d;
         c = f2 * id;
         const Z fd = id * f;

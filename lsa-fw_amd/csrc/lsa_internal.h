@@ -289,7 +289,8 @@ int k_dcgs2_step_batch(lsa_ctx* ctx, int J, int64_t n, const int32_t* j, void* c
 int k_dcgs2_tail_batch(lsa_ctx* ctx, int J, int64_t n, const int32_t* j, void* const* V, int64_t ldv, const void* const* y, void* const* work,
                        const lsa_mat* const* M, const lsa_mat* const* C, void* const* t, double* const* tail_part, void* const* slot, int lds);
 int k_spmv_plain_subwave_lanes(const lsa_mat* A);  // spmv.hip
-// Out[:, 0:k] = V[:, 0:m] Q   (Q m x k column-major on the device, ldq)
+// Out[:, 0:k] = V[:, 0:m] Q   (Q m x k column-major on the device, ldq); m <= k_basis_gemm_max_cols(dtype), LSA_ERR_ARG beyond
+int k_basis_gemm_max_cols(int dtype);
 int k_basis_gemm(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V, int64_t ldv, const void* Q, int ldq,
                  void* Out, int64_t ldo);
 // Out[perm[i], c] = In[i, c] for the columns c < ncols (both n x ncols, leading dimension n)

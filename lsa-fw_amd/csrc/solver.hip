@@ -537,6 +537,8 @@ int lsa_gmres(lsa_ctx* ctx, const lsa_mat* C, lsa_ilu* pc, const lsa_vec* b, lsa
     if (C->dtype == LSA_C128 && b->dtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_gmres: complex matrix needs complex vectors");
     if (restart < 1 || maxit < 1 || !(rtol > 0.0)) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_gmres: restart, maxit, rtol must be positive");
     restart = std::min(restart, maxit);
+    if (restart > k_basis_gemm_max_cols(b->dtype))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_gmres: restart=%d, the basis product handles at most %d basis vectors", restart, k_basis_gemm_max_cols(b->dtype));
     GmresWork W;
     int rc = W.alloc(ctx, C->n, restart, b->dtype);
     PcRef pcr;
@@ -932,6 +934,8 @@ int lsa_op_stats(const lsa_op* op, lsa_stats* out) {
 // ---- Krylov basis ------------------------------------------------------------------------------------------------
 int lsa_krylov_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, lsa_krylov** out) {
     if (!ctx || !op || !out || ncv < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_create: bad argument");
+    if (ncv > k_basis_gemm_max_cols(LSA_C128))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_create: ncv=%d, the basis product handles at most %d basis vectors", ncv, k_basis_gemm_max_cols(LSA_C128));
     const size_t vb = (size_t)std::max<int64_t>(op->n, 1) * 16;
     const char* be = getenv("LSA_KRYLOV_BATCH");
     const int32_t batch = be && *be ? std::max(0, std::min(atoi(be), 256)) : 16;

@@ -537,9 +537,13 @@ int lsa_spmv_info(lsa_ctx* ctx, const lsa_mat* A, int xdtype, char* kernel, int3
     const bool c16 = grouped ? ((variant & 0x800) && ensure_ci16(A)) : (spmv_wants_ci16(A, variant) && ensure_ci16(A));
     const char* mt = A->dtype == LSA_C128 ? "cplx" : "double";
     const char* vt = xdtype == LSA_C128 ? "cplx" : "double";
-    const char* base = grouped ? "spmv_group_kernel" : c16 ? "spmv_subwave16_kernel" : (variant & 0x200) ? "spmv_xcd_kernel" : (variant & 0x400) ? "spmv_subwave2_kernel" : "spmv_subwave_kernel";
+    // what launch_spmv decides: the XCD forms need eight workgroups' worth of work (8 x 64 groups, 8 x 256 / LPR rows), else the plain form runs
+    const bool xcd_groups = grouped && (variant & 0x8000) && !c16 && A->ngroups >= 8 * 64;
+    const bool xcd_rows = !grouped && (variant & 0x200) && A->n >= 8 * (256 / lpr);
+    const char* base = grouped ? "spmv_group_kernel" : xcd_rows ? "spmv_xcd_kernel" : c16 ? "spmv_subwave16_kernel" : (variant & 0x400) ? "spmv_subwave2_kernel" : "spmv_subwave_kernel";
     if (kernel && kernel_len > 0) {
-        if (grouped) snprintf(kernel, (size_t)kernel_len, "%s<%s,%s,%d,%s,%s>", base, mt, vt, lpr, c16 ? "true" : "false", (variant & 0x8000) && !c16 ? "true" : "false");
+        if (grouped) snprintf(kernel, (size_t)kernel_len, "%s<%s,%s,%d,%s,%s>", base, mt, vt, lpr, c16 ? "true" : "false", xcd_groups ? "true" : "false");
+        else if (variant & 0x100) snprintf(kernel, (size_t)kernel_len, "%s<%s,%s,%d,true>", base, mt, vt, lpr);  // the non-temporal instances name their fourth argument
         else snprintf(kernel, (size_t)kernel_len, "%s<%s,%s,%d>", base, mt, vt, lpr);
     }
     if (bytes_moved) {

@@ -56,6 +56,53 @@ def test_schur_form(kind, n):
     assert max(np.min(np.abs(w - z)) for z in w0) <= 1e-9 * max(np.abs(w0).max(), 1e-300)  # (random matrices: well-conditioned spectra)
 
 
+SCALES = [1e-140, 1e-120, 1e-90, 1e-77, 1e-60, 1.0, 1e60, 1e77, 1e90, 1e120, 1e140]
+
+
+@pytest.mark.parametrize("scale", SCALES)
+@pytest.mark.parametrize("kind", ["hessenberg", "after_restart", "general", "real"])
+@pytest.mark.parametrize("n", [12, 40])
+def test_schur_form_of_scaled_matrices(kind, n, scale):
+    """``s A`` for s from 1e-140 to 1e140: the rotations' fast path must hand entries whose squares would leave the normal range
+    after one more product (|.| around 1e+-77 to 1e+-100) to the scaled branch.  The Schur form of s A is s times that of A: T / s
+    is held to the tolerances of ``test_schur_form`` against the unscaled matrix."""
+    rng = np.random.default_rng(n + len(kind))
+    A = _shapes(rng, n, kind)
+    T, Q = _schur(A * scale)  # (asserts return code 0)
+    assert np.all(np.isfinite(T)) and np.all(np.isfinite(Q))
+    Ts = T / scale
+    assert np.linalg.norm(Q @ Ts @ Q.conj().T - A) <= 1e-13 * n * np.linalg.norm(A)
+    assert np.linalg.norm(Q.conj().T @ Q - np.eye(n)) <= 1e-13 * n
+    assert np.count_nonzero(np.tril(T, -1)) == 0
+    w, w0 = np.diag(Ts), sla.eigvals(A)
+    assert max(np.min(np.abs(w - z)) for z in w0) <= 1e-9 * np.abs(w0).max()
+
+
+@pytest.mark.parametrize("n", [12, 40])
+def test_schur_form_of_a_graded_matrix(n):
+    """``D A D^-1`` with D = diag(10^-45 .. 10^45): entries from 1e-90 to 1e90 meet in one rotation.  Backward error against the
+    norm of the graded matrix, at the tolerance of ``test_schur_form``; every output finite."""
+    rng = np.random.default_rng(n)
+    d = 10.0 ** np.linspace(-45.0, 45.0, n)
+    A = _shapes(rng, n, "general") * d[:, None] / d[None, :]
+    T, Q = _schur(A)
+    assert np.all(np.isfinite(T)) and np.all(np.isfinite(Q))
+    assert np.linalg.norm(Q @ T @ Q.conj().T - A) <= 1e-13 * n * np.linalg.norm(A)
+    assert np.linalg.norm(Q.conj().T @ Q - np.eye(n)) <= 1e-13 * n
+    assert np.count_nonzero(np.tril(T, -1)) == 0
+
+
+def test_schur_form_of_ordinary_entries_is_unchanged_bit_for_bit():
+    """The fast path of the rotations still takes every entry of ordinary size: one saved case (24 x 24, the shape after a
+    restart, O(1) entries with couplings down to 1e-11), T and Q as the library computed them before the fast path's bounds
+    were narrowed from squares in (1e-200, 1e200) to (1e-150, 1e150)."""
+    from pathlib import Path
+
+    saved = np.load(Path(__file__).parent / "golden" / "dense_schur_o1_n24.npz")
+    T, Q = _schur(saved["A"])
+    assert np.array_equal(T, saved["T"]) and np.array_equal(Q, saved["Q"])
+
+
 def test_schur_of_defective_and_repeated_spectra():
     J = np.array([[1, 1, 0, 0], [0, 1, 1, 0], [0, 0, 1, 0], [0, 0, 0, 2]], dtype=np.complex128)  # Jordan block + a simple eigenvalue
     T, Q = _schur(J)
