@@ -263,6 +263,11 @@ int lsa_ndlu_prepared_memory(lsa_ctx *ctx, int64_t *out);
 int lsa_ndlu_info(const lsa_ndlu *f, int32_t *ntree, int32_t *nlevels, int32_t *max_front, int64_t *factor_entries,
                   int64_t *front_entries, int64_t *apply_bytes, int32_t *apply_launches, double *seconds_analyse,
                   double *seconds_numeric);
+/* level `level` (0 = leaves) of f's sweeps, one launch upwards and one downwards: its nodes, its widest pivot block, the rows
+ * of a tile of the upward and of the downward launch (8: 64 lanes along a row pair, 32: 16 lanes, 128: 4 lanes) and the tiles
+ * of its tallest node in each (the launches' grid.y; 0: no launch).  LSA_ERR_ARG beyond the last level. */
+int lsa_ndlu_sweep_level(const lsa_ndlu *f, int32_t level, int32_t *nodes, int32_t *max_pivot, int32_t *fwd_rows, int32_t *bwd_rows,
+                         int32_t *fwd_tiles, int32_t *bwd_tiles);
 
 /* ---- GMRES: KSPSolve of the ST (reference default PREONLY+LU; north star: GMRES+ILU) ----------------- */
 /* right-preconditioned restarted GMRES with CGS2; pc may be NULL.  x holds the initial guess on entry

@@ -401,7 +401,11 @@ int nd_setup_levels(lsa_ctx* ctx, lsa_ndlu* f) {
         NdLevel& L = f->levels[(size_t)l];
         L.node_begin = S.lvl_ptr[(size_t)l];
         L.node_count = S.lvl_ptr[(size_t)l + 1] - L.node_begin;
-        // the sweeps wait for memory: a level whose fronts make fewer 32-row tiles than a few per CU gets 8-row tiles
+        // the sweeps wait for memory: a level whose fronts make fewer 32-row tiles than a few per CU gets 8-row tiles (64 lanes
+        // along a row pair).  Upwards only where the level's pivot blocks fill those lanes: a row of the packed L has m entries, and
+        // under pivot blocks narrower than `wide` the 8-row tiles are four times the workgroups (several rounds of them, half of
+        // them without a row where the fronts differ in height) for one factor scalar per lane or none.  A row of the packed U
+        // has f - m entries: downwards the 8-row tiles stay.
         int64_t tiles32 = 0;
         for (int32_t q = 0; q < L.node_count; ++q) {
             const int32_t t = S.lvl_nodes[(size_t)L.node_begin + q];
@@ -415,12 +419,14 @@ int nd_setup_levels(lsa_ctx* ctx, lsa_ndlu* f) {
         static const int32_t thin = getenv("LSA_ND_SWEEP_THIN") ? atoi(getenv("LSA_ND_SWEEP_THIN")) : 64;
         // (64-row tiles -- NP = 2 of nd_fwd_kernel -- on the leaf level of the 500 k-unknown forest, 42 000 tiles: 900 us per solve
         //  against 886 with 32-row tiles: no gain from sharing the gather, measured round 3)
-        L.sweep_rows = tiles32 <= few ? 8 : (L.max_m <= thin && l > 0) ? 128 : kRT;
+        static const int32_t wide = getenv("LSA_ND_SWEEP_WIDE") ? atoi(getenv("LSA_ND_SWEEP_WIDE")) : kSweepWide;
+        L.bwd_rows = tiles32 <= few ? 8 : kRT;
+        L.sweep_rows = tiles32 <= few ? (L.max_m >= wide ? 8 : kRT) : (L.max_m <= thin && l > 0) ? 128 : kRT;
         for (int32_t q = 0; q < L.node_count; ++q) {
             const int32_t t = S.lvl_nodes[(size_t)L.node_begin + q];
             L.fwd_tiles = std::max(L.fwd_tiles, (S.orows[(size_t)t] + S.brow[(size_t)t] + L.sweep_rows - 1) / L.sweep_rows);
-            const int32_t bwd_rows = L.sweep_rows == 8 ? 8 : kRT;  // (the downward sweep of a thin level has few, long rows: 32-row tiles; 32 as well where the upward sweep takes 64)
-            if (S.f[(size_t)t] > S.m[(size_t)t]) L.bwd_tiles = std::max(L.bwd_tiles, (S.orows[(size_t)t] + bwd_rows - 1) / bwd_rows);
+            // (the downward sweep of a thin level has few, long rows: 32-row tiles)
+            if (S.f[(size_t)t] > S.m[(size_t)t]) L.bwd_tiles = std::max(L.bwd_tiles, (S.orows[(size_t)t] + L.bwd_rows - 1) / L.bwd_rows);
         }
         if (L.fwd_tiles > 65535) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu: a front of more than %d rows is not supported", 65535 * 8);
     }
@@ -971,6 +977,19 @@ int lsa_ndlu_prepared_memory(lsa_ctx* ctx, int64_t* out) {
     const lsa_ndlu* c = ctx->nd_cache;
     if (!c) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_prepared_memory: the context holds no prepared analysis");
     return nd_memory_report(c->S, (int32_t)esize(c->dtype), 0, out, nullptr, nullptr, nullptr);
+}
+
+int lsa_ndlu_sweep_level(const lsa_ndlu* f, int32_t level, int32_t* nodes, int32_t* max_pivot, int32_t* fwd_rows, int32_t* bwd_rows, int32_t* fwd_tiles,
+                         int32_t* bwd_tiles) {
+    if (!f || level < 0 || (size_t)level >= f->levels.size()) return LSA_ERR_ARG;
+    const NdLevel& L = f->levels[(size_t)level];
+    if (nodes) *nodes = L.node_count;
+    if (max_pivot) *max_pivot = L.max_m;
+    if (fwd_rows) *fwd_rows = L.sweep_rows;
+    if (bwd_rows) *bwd_rows = L.bwd_rows;
+    if (fwd_tiles) *fwd_tiles = L.fwd_tiles;
+    if (bwd_tiles) *bwd_tiles = L.bwd_tiles;
+    return LSA_OK;
 }
 
 int lsa_ndlu_info(const lsa_ndlu* f, int32_t* ntree, int32_t* nlevels, int32_t* max_front, int64_t* factor_entries, int64_t* front_entries,

@@ -15,6 +15,7 @@
 int k_allgather_inplace(lsa_ctx* ctx, void* vec, size_t bytes_per_rank);  // comm.hip
 
 constexpr int kRT = 32;      // front rows per solve tile
+constexpr int kSweepWide = 512;  // upward 8-row tiles (64 lanes per row pair) only on levels with a pivot block at least this wide (nd_setup_levels)
 constexpr int kCH = 1024;    // vector entries staged in LDS per pass of a solve tile
 constexpr int kGT = 64;      // GEMM tile edge
 constexpr int kNB = 32;      // pivot columns per block of the Gauss-Jordan inversion (ndlu_factor.hip)
@@ -94,7 +95,8 @@ struct NdChunk {
 struct NdLevel {
     int32_t node_begin = 0, node_count = 0, max_m = 0, max_f = 0;
     int32_t fwd_tiles = 0, bwd_tiles = 0;  // grid.y of the sweep kernels: tiles of the tallest node (0 = nothing to do)
-    int32_t sweep_rows = 32;               // rows per upward-sweep tile: 32; 8 on levels with few tiles (both sweeps); 128 on thin levels
+    int32_t sweep_rows = 32;               // rows per upward-sweep tile: 32; 8 on levels with few tiles and wide pivot blocks; 128 on thin levels
+    int32_t bwd_rows = 32;                 // rows per downward-sweep tile: 32; 8 on levels with few tiles
     // distributed top nodes of the level: their range of the list d_dist_nodes, the level's exchange regions (entries per rank)
     int32_t dist_begin = 0, dist_count = 0, dist_children = 0, dist_rows = 0;  // ... most children / most entries (own rows, a child's boundary) of one of them
     int64_t ux_base = 0, ux_slot = 0, xg_base = 0, xg_slot = 0;

@@ -346,7 +346,7 @@ int nd_sweep_multi(lsa_ctx* ctx, lsa_ndlu* f, const VT* const* b, VT* const* x) 
     for (size_t l = f->levels.size(); l-- > 0;) {
         const NdLevel& L = f->levels[l];
         if (L.bwd_tiles > 0 && !(top && (int32_t)l + 1 == f->top_level)) {
-            nd_with_lpr<false>(L.sweep_rows, [&](auto lpr) {
+            nd_with_lpr<false>(L.bwd_rows, [&](auto lpr) {
                 hipLaunchKernelGGL((nd_bwd_multi_kernel<MT, VT, decltype(lpr)::value, ORDERED, R>), dim3(L.node_count, L.bwd_tiles), dim3(256), 0, st,
                                    f->d_lnodes_bwd + L.node_begin, f->d_idx, f->d_gell, p);
             });

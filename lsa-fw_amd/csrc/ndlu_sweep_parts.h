@@ -142,6 +142,19 @@ __device__ __forceinline__ void push_down(const int32_t* __restrict__ ge, int32_
     }
 }
 
+// push_down with the gather rows' entries of up to four children asked for beforehand (HAVE: g[c] = child c's entry, -1 = none)
+template <bool HAVE, typename VT>
+__device__ __forceinline__ void push_down_at(const int32_t* __restrict__ ge, int32_t nchild, int32_t f, int32_t j, const int32_t (&g)[4],
+                                             VT* __restrict__ xb, VT val) {
+    if (HAVE && nchild <= 4) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (g[c] >= 0) xb[g[c]] = val;
+    } else {
+        push_down(ge, nchild, f, j, xb, val);
+    }
+}
+
 // ---- the merged top (NdTop, ndlu_internal.h): the root and its children in one launch
 // the output of top row i (final: no downward step follows): into x, and to the boundary vectors of the grandchildren -- a row
 // of child c through c's gather rows at its own position; a row of the root, for every child c that has it at boundary
@@ -169,9 +182,64 @@ __device__ __forceinline__ void nd_top_store(const NdTop& tp, int32_t i, VT val,
     }
 }
 
-// The tile form of a level's launch from NdLevel::sweep_rows: LPR lanes per row pair, 512 / LPR rows per tile.  8 rows -> 64 lanes;
-// 128 -> 4, upwards only (THIN: the downward sweep of a thin level has few, long rows and stays with 32-row tiles, as
-// nd_setup_levels counted them); else 32 rows -> 16.
+// Where nd_top_store sends the output of top row i, asked for before the row is swept (it depends on the tables alone): the
+// row's place in x and its entries of the grandchildren's boundary vectors -- g[q] = -1: none.  They fit for a row of a child
+// with at most eight children, and for a row of the root under at most two children of at most four children each; fits = false
+// otherwise (nd_top_store then finds them after the reduction).
+struct NdTopTargets {
+    int32_t own;
+    bool fits;
+    int32_t g[8];
+};
+
+__device__ __forceinline__ void nd_top_targets(const NdTop& tp, int32_t i, const int32_t* __restrict__ icmap, const int32_t* __restrict__ gell,
+                                               NdTopTargets& t) {
+    const int32_t K = tp.nchild;
+    const NdTopNode& R = tp.node[K];
+    t.own = 0, t.fits = false;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) t.g[q] = -1;
+    if (i >= R.off) {
+        const int32_t k = i - R.off;
+        t.own = R.own0 + k;
+        t.fits = K <= 2;
+        if (!t.fits) return;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            if (c >= K) break;
+            const NdTopNode& nd = tp.node[c];
+            if (nd.nchild > 4) t.fits = false;
+            const int32_t p = icmap[(size_t)c * R.m + k];
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc)
+                if (p >= 0 && cc < nd.nchild) t.g[4 * c + cc] = gell[nd.ge_off + (size_t)cc * nd.f + nd.m + p];
+        }
+        return;
+    }
+    for (int32_t c = 0; c < K; ++c) {
+        const NdTopNode& nd = tp.node[c];
+        if (i < nd.off || i >= nd.off + nd.m) continue;
+        t.own = nd.own0 + i - nd.off;
+        t.fits = nd.nchild <= 8;
+#pragma unroll
+        for (int cc = 0; cc < 8; ++cc)
+            if (t.fits && cc < nd.nchild) t.g[cc] = gell[nd.ge_off + (size_t)cc * nd.f + i - nd.off];
+    }
+}
+
+template <typename VT>
+__device__ __forceinline__ void nd_top_store(const NdTop& tp, int32_t i, VT val, const NdTopTargets& t, const int32_t* __restrict__ icmap,
+                                             const int32_t* __restrict__ gell, VT* __restrict__ x, VT* __restrict__ xb) {
+    if (!t.fits) return nd_top_store(tp, i, val, icmap, gell, x, xb);
+    x[t.own] = val;
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+        if (t.g[q] >= 0) xb[t.g[q]] = val;
+}
+
+// The tile form of a level's launch from NdLevel::sweep_rows (upwards) or bwd_rows (downwards): LPR lanes per row pair, 512 / LPR
+// rows per tile.  8 rows -> 64 lanes; 128 -> 4, upwards only (THIN: the downward sweep of a thin level has few, long rows and
+// stays with 32-row tiles, as nd_setup_levels counted them); else 32 rows -> 16.
 template <bool THIN, typename F>
 void nd_with_lpr(int32_t sweep_rows, F&& launch) {
     if (sweep_rows == 8) return launch(std::integral_constant<int, 64>{});

@@ -133,6 +133,20 @@ __device__ __forceinline__ void nd_bwd_tile(const NdSweepNode& nd, int32_t r0, i
     row_pair_prefetch<LPR>(Ua, Ub, min(kCH, b), sl, pa, pb);
     // the rows' own entries are needed only at the end: issue their loads before the sweep over the boundary
     const VT xa = x[ia], xc = x[ib];
+    // ... and, in the 64-lane form, where the finished rows go in the boundary vectors of up to four children: push_down would
+    // load these indices after the reduction, a dependent load at the very end of the launch.  (The 16-lane form stays at the
+    // 128 registers that let four of its workgroups share a CU: it leaves them to push_down.)
+    constexpr bool GE = LPR == 64;
+    int32_t ga[4] = {-1, -1, -1, -1}, gb[4] = {-1, -1, -1, -1};
+    if constexpr (GE) {
+        if (sl == 0 && nd.nchild <= 4) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (c < nd.nchild && ra < m) ga[c] = ge[(size_t)c * f + ra];
+                if (c < nd.nchild && rb < m) gb[c] = ge[(size_t)c * f + rb];
+            }
+        }
+    }
     VT acc0 = scalar_traits<VT>::zero(), acc1 = scalar_traits<VT>::zero();
     for (int32_t c0 = 0; c0 < b; c0 += kCH) {
         const int32_t cn = min(kCH, b - c0);
@@ -148,12 +162,12 @@ __device__ __forceinline__ void nd_bwd_tile(const NdSweepNode& nd, int32_t r0, i
         if (ra < m) {
             const VT v = s_sub(xa, acc0);
             x[ia] = v;
-            push_down(ge, nd.nchild, f, ra, xb, v);
+            push_down_at<GE>(ge, nd.nchild, f, ra, ga, xb, v);
         }
         if (rb < m) {
             const VT v = s_sub(xc, acc1);
             x[ib] = v;
-            push_down(ge, nd.nchild, f, rb, xb, v);
+            push_down_at<GE>(ge, nd.nchild, f, rb, gb, xb, v);
         }
     }
     if (nd.nchild > 0) {  // the boundary entries this node received, handed on to the children whose boundaries hold them
@@ -196,6 +210,12 @@ __device__ __forceinline__ void nd_top_tile(const NdTop& tp, int32_t r0, VT* vs,
     VT acc0 = scalar_traits<VT>::zero(), acc1 = scalar_traits<VT>::zero();
     MT pa[4], pb[4];
     row_pair_prefetch<LPR>(Ta, Tb, min(kCH, s), sl, pa, pb);
+    // where the rows' outputs go: asked for now, needed after the reduction
+    NdTopTargets ta, tb;
+    if (sl == 0) {
+        nd_top_targets(tp, min(ra, s - 1), icmap, gell, ta);
+        nd_top_targets(tp, min(rb, s - 1), icmap, gell, tb);
+    }
     for (int32_t c0 = 0; c0 < s; c0 += kCH) {
         const int32_t c1 = min(c0 + kCH, s);
         for (int32_t c = 0; c < K; ++c) {
@@ -223,8 +243,8 @@ __device__ __forceinline__ void nd_top_tile(const NdTop& tp, int32_t r0, VT* vs,
     }
     const VT s0 = lanes_sum<LPR>(acc0), s1 = lanes_sum<LPR>(acc1);
     if (sl == 0) {
-        if (ra < s) nd_top_store(tp, ra, s0, icmap, gell, x, xb);
-        if (rb < s) nd_top_store(tp, rb, s1, icmap, gell, x, xb);
+        if (ra < s) nd_top_store(tp, ra, s0, ta, icmap, gell, x, xb);
+        if (rb < s) nd_top_store(tp, rb, s1, tb, icmap, gell, x, xb);
     }
 }
 
@@ -426,7 +446,7 @@ int nd_sweep(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const VT* const* b, VT
     for (size_t l = f0->levels.size(); l-- > 0;) {
         const NdLevel& L = f0->levels[l];
         if (L.bwd_tiles > 0 && !(top && (int32_t)l + 1 == f0->top_level)) {
-            nd_with_lpr<false>(L.sweep_rows, [&](auto lpr) {
+            nd_with_lpr<false>(L.bwd_rows, [&](auto lpr) {
                 hipLaunchKernelGGL((nd_bwd_kernel<MT, VT, decltype(lpr)::value, ORDERED, NB>), dim3(L.node_count, L.bwd_tiles, J), dim3(256), 0, st,
                                    f0->d_lnodes_bwd + L.node_begin, f0->d_idx, f0->d_gell, p);
             });
@@ -555,7 +575,7 @@ bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g) {
     for (size_t l = 0; l < f->levels.size(); ++l) {
         const NdLevel &a = f->levels[l], &c = g->levels[l];
         if (a.node_begin != c.node_begin || a.node_count != c.node_count || a.fwd_tiles != c.fwd_tiles || a.bwd_tiles != c.bwd_tiles ||
-            a.sweep_rows != c.sweep_rows || a.dist_count != 0 || c.dist_count != 0)
+            a.sweep_rows != c.sweep_rows || a.bwd_rows != c.bwd_rows || a.dist_count != 0 || c.dist_count != 0)
             return false;
     }
     if (f->top.s != g->top.s || f->top_level != g->top_level) return false;

@@ -173,6 +173,7 @@ SIGNATURES = {
     "lsa_ndlu_multi_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "lsa_ndlu_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64),
                                      ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_DBL), ctypes.POINTER(_DBL)]),
+    "lsa_ndlu_sweep_level": (ctypes.c_int, [_P, _I32] + [ctypes.POINTER(_I32)] * 6),
     "lsa_gmres": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, _DBL, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_I32), ctypes.POINTER(_DBL)]),
     "lsa_op_create": (ctypes.c_int, [_P, _P, _P, _DBL * 2, ctypes.c_int, ctypes.POINTER(lsa_op_options), _PP]),
     "lsa_op_create_sharded": (ctypes.c_int, [_P, _P, _P, _P, _P, _DBL * 2, ctypes.c_int, ctypes.POINTER(lsa_op_options), _PP]),
@@ -720,6 +721,18 @@ class NdLu:
                                     ctypes.byref(ab), ctypes.byref(nla), ctypes.byref(sa), ctypes.byref(sn))
         return {"tree_nodes": nt.value, "levels": nl.value, "max_front": mf.value, "factor_entries": fe.value, "front_entries": fre.value,
                 "apply_bytes": ab.value, "apply_launches": nla.value, "seconds_analyse": sa.value, "seconds_numeric": sn.value}
+
+    def sweep_levels(self) -> list[dict]:
+        """Per tree level (leaves first) what the sweeps launch: nodes, the widest pivot block, the rows of an upward and of a
+        downward tile, and the tiles of the tallest node upwards and downwards (``lsa_ndlu_sweep_level``)."""
+        keys = ("nodes", "max_pivot", "fwd_rows", "bwd_rows", "fwd_tiles", "bwd_tiles")
+        out = []
+        for level in range(self.info()["levels"]):
+            v = [_I32(0) for _ in keys]
+            if self.ctx._lib.lsa_ndlu_sweep_level(self.handle, level, *[ctypes.byref(a) for a in v]) != 0:
+                break
+            out.append({k: a.value for k, a in zip(keys, v)})
+        return out
 
     def solve(self, b: DeviceVector, x: DeviceVector) -> None:
         self.ctx.check(self.ctx._lib.lsa_ndlu_solve(self.ctx.handle, self.handle, b.handle, x.handle))

@@ -53,4 +53,6 @@ if es.n < 40000:
 f.time_solve(db, dx, 10)
 ms = f.time_solve(db, dx, 100)
 info = f.info()
+print("sweep levels (nodes, widest pivot block, tile rows up / down, tiles of the tallest node up / down):",
+      [tuple(lv.values()) for lv in f.sweep_levels()], flush=True)
 print(f"solve {ms * 1e3:.1f} us per apply; {info['apply_bytes'] / 1e6:.1f} MB -> {info['apply_bytes'] / ms / 1e6:.0f} GB/s; {info['apply_launches']} launches", flush=True)
