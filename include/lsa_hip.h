@@ -233,8 +233,9 @@ int lsa_ndlu_solve_time(lsa_ctx *ctx, lsa_ndlu *f, const lsa_vec *b, lsa_vec *x,
  * column-major blocks: column q starts at q * ld scalars, ld >= n, each vector at least ld (nrhs - 1) + n long.  B == X with
  * ldb == ldx solves in place; any other overlap, nrhs < 1, ld < n, a short block, mixed vector dtypes, complex factors with real
  * vectors: LSA_ERR_ARG.  For trans = 0 on one rank the columns go through the sweeps in passes of up to 8 (real vectors) or 4
- * (complex vectors) that read every factor scalar once per pass (lsa_ndlu_multi_info); a forest cut over ranks and the
- * transposed systems run column by column.  Either
+ * (complex vectors) that read every factor scalar once per pass (lsa_ndlu_multi_info); so do the transposed systems once
+ * lsa_ndlu_set_multi_transposed switched that on for the factorisation (off by default: they run column by column, as a
+ * forest cut over ranks always does).  Either
  * way column q holds exactly the bits lsa_ndlu_solve / lsa_ndlu_solve_adjoint gives for it.  nrhs = 1 is lsa_ndlu_solve.  The
  * sweep buffers of the further columns of a pass are made by the first call and released with the factorisation; where they
  * do not fit, the passes get narrower, down to column by column. */
@@ -243,8 +244,12 @@ int lsa_ndlu_solve_multi(lsa_ctx *ctx, lsa_ndlu *f, int trans, int32_t nrhs, con
  * block solve (KSPMatSolve timed as lsa_ndlu_solve_time times KSPSolve) */
 int lsa_ndlu_solve_multi_time(lsa_ctx *ctx, lsa_ndlu *f, int trans, int32_t nrhs, const lsa_vec *B, int64_t ldb, lsa_vec *X, int64_t ldx,
                               int iters, double *avg_ms);
-/* what the last lsa_ndlu_solve_multi on f used (the work MatMatSolve hides): width = columns of its widest pass (1: column by
- * column, 0: none yet), extra_bytes = device memory of the per-column sweep buffers, launches_per_pass = dependent launches of
+/* on != 0: lsa_ndlu_solve_multi and lsa_ndlu_solve_multi_time with trans != 0 carry the columns of a pass through one launch per
+ * tree level and direction of the transposed sweeps, as trans = 0 does (one rank, no distributed node; same passes, same bits per
+ * column).  The default is off. */
+int lsa_ndlu_set_multi_transposed(lsa_ctx *ctx, lsa_ndlu *f, int on);
+/* what the last lsa_ndlu_solve_multi on f used, in either direction (the work MatMatSolve hides): width = columns of its widest
+ * pass (1: column by column, 0: none yet), extra_bytes = device memory of the per-column sweep buffers, launches_per_pass = dependent launches of
  * one pass (those of one lsa_ndlu_solve) */
 int lsa_ndlu_multi_info(const lsa_ndlu *f, int32_t *width, int64_t *extra_bytes, int32_t *launches_per_pass);
 /* Inertia (numbers of negative, zero, positive eigenvalues) of a REAL SYMMETRIC C from its factorisation: what SLEPc's spectrum
@@ -494,6 +499,11 @@ int lsa_resolvent_create(lsa_ctx *ctx, lsa_op *op, int32_t ncv, lsa_resolvent **
 void lsa_resolvent_destroy(lsa_resolvent *r);
 /* as lsa_krylov_set_row_permutation: the vectors of lsa_resolvent_solve leave in the caller's numbering */
 int lsa_resolvent_set_row_permutation(lsa_ctx *ctx, lsa_resolvent *r, const int32_t *perm);
+/* on != 0: the forcings of lsa_resolvent_solve send their adjoint solves through ONE block solve on the factors (the wide passes of
+ * lsa_ndlu_solve_multi with trans = 2), each checked as before from one read-back; from the first column that misses ksp_rtol on
+ * the columns finish one by one with the refinement step.  Gains, forcings and the solve counts are those of the default (off),
+ * bit for bit.  The block's 2 nvec work vectors are made by the first such call; where they do not fit, the columns run one by one. */
+int lsa_resolvent_set_block_forcings(lsa_ctx *ctx, lsa_resolvent *r, int on);
 /* v_0 = v / sqrt(v^H M v) (host complex vector of length n), M-normalised on the device; LSA_ERR_ARG when v^H M v is not positive */
 int lsa_resolvent_set_start(lsa_ctx *ctx, lsa_resolvent *r, const void *host_v);
 /* Lanczos steps j = j0 .. j1-1 on W: z = C^-H M v_j, w = C^-1 M z, two passes of classical Gram-Schmidt against v_0..v_j in the

@@ -65,7 +65,7 @@ class ResolventSolver:
 
     def __init__(self, A, M, cfg: ResolventConfig | None = None, *, device: int = 0, layout: str = "single",
                  pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
-                 ksp_rtol: float | None = None) -> None:
+                 ksp_rtol: float | None = None, block_forcings: bool = False) -> None:
         if A is None:
             raise ValueError("Operator A is required.")
         if M is None:
@@ -97,6 +97,8 @@ class ResolventSolver:
         eps.set_dimensions(self._cfg.num_modes, self._cfg.ncv)
         self._eps = eps
         self._seed = seed
+        # the forcings' adjoint solves as one block solve on the factors (same bits; off by default)
+        self._block_forcings = bool(block_forcings)
 
     @property
     def config(self) -> ResolventConfig:
@@ -124,6 +126,8 @@ class ResolventSolver:
                 raise NotImplementedError("Resolvent analysis needs the exact LU; it does not fit the device memory")
             basis = lsa_hip.ResolventBasis(prep["ctx"], op, run["ncv"])
             basis.set_row_permutation(prep["perm"])
+            if self._block_forcings:
+                basis.set_block_forcings(True)
             out = basis.solve(nev, cfg.atol, cfg.max_it, v0=eps._start_vector(basis.n), seed=self._seed, max_out=nev, forcings=forcings)
             st = op.stats()
             basis_bytes = basis.basis_bytes

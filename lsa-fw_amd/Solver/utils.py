@@ -1561,7 +1561,7 @@ class iKSP:
 
     Construction and the setters do no device work (the context opens at the first solve), so the class can be configured on
     a machine without a GPU; there is no CPU fallback for ``solve``.  Extensions beyond the reference's class, marked in
-    their docstrings: :meth:`solve_many`, :attr:`stats`, the keyword ``device``, the attributes ``ilu_levels`` / ``restart``."""
+    their docstrings: :meth:`solve_many`, :attr:`stats`, :attr:`block_adjoint`, the keyword ``device``, the attributes ``ilu_levels`` / ``restart``."""
 
     ilu_levels = 2    # level of fill of the ILU(k) preconditioner (extension; LinearSolver.solve's default)
     restart = 1000    # GMRES restart length (extension; LinearSolver.solve's default)
@@ -1577,6 +1577,7 @@ class iKSP:
         self._solution: np.ndarray | None = None
         self._res_norm, self._its = 0.0, 0
         self._stats = {"analyses": 0, "factorisations": 0, "refactorisations": 0, "solves": 0, "columns": 0, "multi_width": 0}
+        self._block_adjoint = False
         if A is not None:
             self.set_operators(A)
 
@@ -1590,6 +1591,17 @@ class iKSP:
         ``columns``) and ``multi_width``, the widest pass of the last :meth:`solve_many`; ``factorisations`` starts again
         from the state a :meth:`reset` or a new pattern rebuilds."""
         return dict(self._stats)
+
+    @property
+    def block_adjoint(self) -> bool:
+        """Extension: ``True`` sends the columns of ``solve_many(B, adjoint=True)``, and of its refinement pass, through the
+        transposed sweeps in the wide passes of the forward block solve (``NdLu.set_multi_transposed``) instead of one after
+        another; ``stats["multi_width"]`` then reports that pass width.  Each column keeps its bits.  Default ``False``."""
+        return self._block_adjoint
+
+    @block_adjoint.setter
+    def block_adjoint(self, flag: bool) -> None:
+        self._block_adjoint = bool(flag)
 
     def set_operators(self, A, P=None) -> None:
         if P is not None and P is not A:
@@ -1789,6 +1801,8 @@ class iKSP:
             if k == 1 and not adjoint:
                 lu.solve(dB, dX)
             else:  # (the block vectors are n k long: one column of them is still a block solve, with the bits of lu.solve)
+                if adjoint:
+                    lu.set_multi_transposed(self._block_adjoint)
                 lu.solve_multi(dB, dX, kk, trans="H" if adjoint else "N")
             return dX.numpy()[: n * kk].reshape((n, kk), order="F")
 
@@ -1863,7 +1877,7 @@ class iKSP:
         """Extension: ``A X = B`` (``adjoint``: ``A^H X = B``, on the same factors) for an ``(n, k)`` array of right-hand
         sides; returns the ``(n, k)`` solutions.  On the LU path all columns go through ONE ``NdLu.solve_multi`` call (the
         sweeps read every factor scalar once per pass of up to 8 real or 4 complex columns) with the verification of :meth:`solve` per column,
-        each column bit-identical to :meth:`solve`; on the GMRES path the columns are solved one after another and
+        each column bit-identical to :meth:`solve` (``adjoint``: column by column unless :attr:`block_adjoint` is set); on the GMRES path the columns are solved one after another and
         ``adjoint`` is not available."""
         rhs = self._rhs(B, ncols=True)
         dev = self._ensure()

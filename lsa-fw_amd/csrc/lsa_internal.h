@@ -379,7 +379,8 @@ int resolvent_restart(lsa_ctx* ctx, lsa_resolvent* r, int32_t m, int32_t knew, c
 // Q = V[:, 0:m] Y to the host in the caller's row numbering, each column's entry of largest magnitude real positive; the columns stay
 // on the device for resolvent_forcings
 int resolvent_ritz_vectors(lsa_ctx* ctx, lsa_resolvent* r, int32_t m, int32_t nvec, const double* Y, int32_t ldy, cplx* Q);
-// F[:, c] = -C^-H M q_c / gain[c] for the columns resolvent_ritz_vectors left: one checked adjoint solve each
+// F[:, c] = -C^-H M q_c / gain[c] for the columns resolvent_ritz_vectors left: one checked adjoint solve each (with
+// lsa_resolvent_set_block_forcings: one block solve for all of them, each column checked, the same results)
 int resolvent_forcings(lsa_ctx* ctx, lsa_resolvent* r, int32_t nvec, const double* gain, cplx* F);
 // accepted adjoint solves, accepted forward solves, and how many of each carried the refinement step
 void resolvent_counts(const lsa_resolvent* r, int64_t counts[4]);
@@ -435,3 +436,7 @@ void blk_release(lsa_ilu* pc);
 struct lsa_ndlu;
 int ndlu_solve_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, const void* b, void* x);
 int ndlu_solve_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, const void* b, void* x);
+// ndlu_multi.hip: X[:, q] = C^-T B[:, q] (conj == 0) or C^-H B[:, q], q < nrhs, on device pointers (column q at q * ld scalars; B == X
+// with ldb == ldx allowed), in passes that carry their columns through one launch per tree level and direction of the transposed
+// sweeps; each column holds the bits of ndlu_solve_adjoint_dev.  One rank, no distributed node; not synchronised.
+int ndlu_solve_multi_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx);

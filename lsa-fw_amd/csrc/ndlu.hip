@@ -901,7 +901,9 @@ static int nd_multi_check(lsa_ctx* ctx, const char* who, const lsa_ndlu* f, int 
 static int nd_multi_run(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx) {
     const size_t es = esize(B->dtype);
     if (trans == 0 && nrhs > 1 && f->S.nranks == 1 && !f->S.has_dist) return ndlu_solve_multi_dev(ctx, f, B->dtype, nrhs, B->d, ldb, X->d, ldx);
-    // one column, a forest cut over ranks, the transposed systems: the existing sweeps, column by column
+    if (trans != 0 && f->multi_transposed && nrhs > 1 && f->S.nranks == 1 && !f->S.has_dist)
+        return ndlu_solve_multi_adjoint_dev(ctx, f, trans == 2, B->dtype, nrhs, B->d, ldb, X->d, ldx);
+    // one column, a forest cut over ranks, the transposed systems unless lsa_ndlu_set_multi_transposed: the existing sweeps, column by column
     if (nrhs > 1) f->multi_width = 1;
     for (int32_t q = 0; q < nrhs; ++q) {
         const void* b = (const char*)B->d + (size_t)q * (size_t)ldb * es;
@@ -932,6 +934,12 @@ int lsa_ndlu_solve_multi_time(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs
     float ms = 0.f;
     LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     *avg_ms = (double)ms / iters;
+    return LSA_OK;
+}
+
+int lsa_ndlu_set_multi_transposed(lsa_ctx* ctx, lsa_ndlu* f, int on) {
+    if (!ctx || !f) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_set_multi_transposed: null argument");
+    f->multi_transposed = on != 0;
     return LSA_OK;
 }
 

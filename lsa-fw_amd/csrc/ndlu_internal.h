@@ -24,7 +24,7 @@ constexpr int kTRmin = 256;  // tournament pivoting, smallest first-round chunk:
 constexpr int kNdBatchMax = 16;  // most problems of one batched solve (lsa_ndlu_solve_batch): the capacity of NdSweepPtrs there
 static_assert(kNdBatchMax == kKrylovGroupMax, "a lockstep round hands all its problems to one batched sweep");
 constexpr int kMCH = 256;        // vector entries per column staged in LDS per pass of a multi-column solve tile (ndlu_multi.hip)
-constexpr int kNdMultiMax = 8;   // most columns of one pass of lsa_ndlu_solve_multi (real vectors; complex ones: 4 -- nd_multi_cap): 16 KB of LDS
+constexpr int kNdMultiMax = 8;   // most columns of one pass of lsa_ndlu_solve_multi (real vectors; complex ones: 4 -- nd_multi_cap): 16 KB of LDS (transposed: 32 KB)
 
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 inline size_t esize(int dtype) { return dtype == LSA_C128 ? 16 : 8; }
@@ -196,6 +196,7 @@ struct lsa_ndlu {
     bool multi_full = false;     // an allocation failed: no further columns are tried
     int64_t multi_bytes = 0;
     int32_t multi_width = 0;     // widest pass of the last multi-column solve (1: column by column; 0: none yet)
+    bool multi_transposed = false;  // lsa_ndlu_set_multi_transposed: block solves with trans != 0 run in wide passes too
 };
 
 template <typename U>
@@ -216,4 +217,5 @@ int ndlu_solve_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype
 // ndlu_multi.hip: X[:, q] = C^-1 B[:, q], q < nrhs, on device pointers (column q at q * ld scalars; B == X with ldb == ldx allowed),
 // in passes of up to kNdMultiMax (complex vectors: 4) columns that share every factor load; not synchronised.  One rank, no distributed node.
 int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx);
+// (the transposed block solve, ndlu_solve_multi_adjoint_dev: lsa_internal.h)
 void ndlu_multi_free(lsa_ndlu* f);

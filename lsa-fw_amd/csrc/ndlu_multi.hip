@@ -6,6 +6,8 @@
 // column q holds exactly the bits lsa_ndlu_solve gives for it.  (A lane's sequence sl, sl + LPR, ... runs on across chunks, so
 // the chunk -- kMCH entries per column, a multiple of 256 -- is free: four complex or eight real columns of kMCH = 256 are 16 KB of LDS.)
 // Columns beyond the first have sweep buffers of their own (lsa_ndlu::multi), made by the first such solve.
+// The transposed systems C^-T / C^-H have the same form (nd_sweepT_multi_kernel, ndlu_solve_multi_adjoint_dev): nd_sweepT_kernel with R
+// columns carried through every launch, on the update vectors of the same per-column buffers.
 #include "ndlu_sweep_parts.h"
 
 namespace {
@@ -356,6 +358,171 @@ int nd_sweep_multi(lsa_ctx* ctx, lsa_ndlu* f, const VT* const* b, VT* const* x) 
     return LSA_OK;
 }
 
+// ---- the transposed / conjugate-transposed system, R columns: nd_sweepT_kernel of ndlu_sweeps.hip with every factor scalar
+// Fk[k * ld] loaded once for all of them.  Workgroup (node of the level, tile of 64 outputs), the lane = the output column of the
+// packed block, the four slices sl = tid >> 6 split the rows summed over.  Per column the arithmetic is the solo kernel's: slice sl
+// of a lane adds the rows sl, sl + 4, ... in ascending order into one accumulator -- a sequence that runs on across chunks, so the
+// chunk of kMCH = 256 entries gives the bits of the solo kernel's kCH --, the slices are added as (p0 + p1) + (p2 + p3), and the
+// epilogue is the solo one.  No distributed node reaches this form.
+template <int R>
+struct NdMultiTPtrs {
+    const void* rhs[R];
+    void* x[R];
+    void* ubuf[R];
+};
+
+// gather_updates for R update vectors: v[q] += the children's entries of ubuf[q] that land on front position j, the gather rows'
+// entries loaded once; per column the additions of gather_updates in their order
+template <int R, typename VT>
+__device__ __forceinline__ void gather_updates_multi(const int32_t* __restrict__ ge, int32_t nchild, int32_t f, int32_t j, void* const (&ubuf)[R],
+                                                     VT (&v)[R]) {
+    int32_t c = 0;
+    for (; c + 3 < nchild; c += 4) {
+        const int32_t g0 = ge[(size_t)c * f + j], g1 = ge[(size_t)(c + 1) * f + j], g2 = ge[(size_t)(c + 2) * f + j], g3 = ge[(size_t)(c + 3) * f + j];
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const VT* ub = (const VT*)ubuf[q];
+            const VT u0 = g0 >= 0 ? ub[g0] : scalar_traits<VT>::zero(), u1 = g1 >= 0 ? ub[g1] : scalar_traits<VT>::zero();
+            const VT u2 = g2 >= 0 ? ub[g2] : scalar_traits<VT>::zero(), u3 = g3 >= 0 ? ub[g3] : scalar_traits<VT>::zero();
+            v[q] = s_add(s_add(s_add(s_add(v[q], u0), u1), u2), u3);
+        }
+    }
+    int32_t g[3] = {-1, -1, -1};
+    for (int i = 0; i < 3; ++i)
+        if (c + i < nchild) g[i] = ge[(size_t)(c + i) * f + j];
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        const VT* ub = (const VT*)ubuf[q];
+        VT u[3];
+        for (int i = 0; i < 3; ++i) u[i] = g[i] >= 0 ? ub[g[i]] : scalar_traits<VT>::zero();
+        for (int i = 0; i < 3; ++i)
+            if (c + i < nchild) v[q] = s_add(v[q], u[i]);
+    }
+}
+
+template <typename MT, typename VT, bool CONJ, bool DOWN, int R>
+__global__ __launch_bounds__(256) void nd_sweepT_multi_kernel(const NdSweepNode* __restrict__ lnodes, const MT* __restrict__ lfac,
+                                                              const MT* __restrict__ ufac, const int32_t* __restrict__ idx,
+                                                              const int32_t* __restrict__ gell, NdMultiTPtrs<R> p) {
+    __shared__ VT vs[R * kMCH];
+    __shared__ VT part[R][4][64];
+    static_assert(kMCH == 256, "one staged entry per thread and column");
+    static_assert(sizeof(VT) * R * (kMCH + 4 * 64) <= 64 * 1024, "LDS of a transposed multi-column tile");
+    const NdSweepNode nd = lnodes[blockIdx.x];
+    const int32_t m = nd.m, f = nd.f, b = f - m;
+    const int32_t ncols = DOWN ? m : f;              // outputs of this sweep
+    const int32_t klo = DOWN ? nd.brow0 : nd.orow0;  // rows summed over (all of them: the node is not distributed)
+    const int32_t K = DOWN ? nd.brow : nd.orows;
+    const int32_t c0 = (int32_t)blockIdx.y * 64;
+    if (c0 >= ncols || (DOWN && b == 0)) return;
+    const int32_t* ix = idx + nd.idx_off;
+    const int32_t* ge = gell + nd.ge_off;
+    const int tid = threadIdx.x, lane = tid & 63, sl = tid >> 6;
+    const int32_t col = min(c0 + lane, ncols - 1);
+    const MT* Fc;
+    int32_t ld;
+    if (DOWN) Fc = lfac + nd.lfac_off + (size_t)nd.orows * m + col, ld = m;
+    else if (col < m) Fc = lfac + nd.lfac_off + col, ld = m;
+    else Fc = ufac + nd.ufac_off + (col - m), ld = b;
+    VT acc[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q) acc[q] = scalar_traits<VT>::zero();
+    for (int32_t k0 = 0; k0 < K; k0 += kMCH) {
+        const int32_t kn = min(kMCH, K - k0);
+        if (tid < kn) {  // one entry per thread and column, its index loaded once
+            if (DOWN) {
+                const int32_t src = ix[m + klo + k0 + tid];
+#pragma unroll
+                for (int q = 0; q < R; ++q) vs[q * kMCH + tid] = ((const VT*)p.x[q])[src];
+            } else {
+                const int32_t j = klo + k0 + tid, src = ix[j];
+                VT v[R];
+#pragma unroll
+                for (int q = 0; q < R; ++q) v[q] = ((const VT*)p.rhs[q])[src];
+                gather_updates_multi<R>(ge, nd.nchild, f, j, p.ubuf, v);
+#pragma unroll
+                for (int q = 0; q < R; ++q) vs[q * kMCH + tid] = v[q];
+            }
+        }
+        __syncthreads();
+        const MT* Fk = Fc + (size_t)k0 * ld;
+        int32_t k = sl;
+        for (; k + 12 < kn; k += 16) {
+            const MT a0 = maybe_conj<CONJ>(Fk[(size_t)k * ld]), a1 = maybe_conj<CONJ>(Fk[(size_t)(k + 4) * ld]);
+            const MT a2 = maybe_conj<CONJ>(Fk[(size_t)(k + 8) * ld]), a3 = maybe_conj<CONJ>(Fk[(size_t)(k + 12) * ld]);
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const VT* v = vs + q * kMCH;
+                fma_acc(acc[q], a0, v[k]);
+                fma_acc(acc[q], a1, v[k + 4]);
+                fma_acc(acc[q], a2, v[k + 8]);
+                fma_acc(acc[q], a3, v[k + 12]);
+            }
+        }
+        for (; k < kn; k += 4) {
+            const MT a0 = maybe_conj<CONJ>(Fk[(size_t)k * ld]);
+#pragma unroll
+            for (int q = 0; q < R; ++q) fma_acc(acc[q], a0, vs[q * kMCH + k]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q) part[q][sl][lane] = acc[q];
+    __syncthreads();
+    if (sl == 0 && c0 + lane < ncols) {
+        const int32_t r = c0 + lane;
+        VT z[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) z[q] = s_add(s_add(part[q][0][lane], part[q][1][lane]), s_add(part[q][2][lane], part[q][3][lane]));
+        if (DOWN || r < m) {
+            const int32_t dst = ix[r];
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                VT* x = (VT*)p.x[q];
+                x[dst] = DOWN ? s_add(x[dst], z[q]) : z[q];
+            }
+        } else {
+            VT u[R];
+#pragma unroll
+            for (int q = 0; q < R; ++q) u[q] = scalar_traits<VT>::zero();
+            gather_updates_multi<R>(ge, nd.nchild, f, r, p.ubuf, u);
+#pragma unroll
+            for (int q = 0; q < R; ++q) ((VT*)p.ubuf[q])[nd.u_off + (r - m)] = s_sub(u[q], z[q]);
+        }
+    }
+}
+
+// x_q = C^-T b_q (C^-H b_q with CONJ) for the R columns of one pass: the launches of nd_apply_T for one rank and no distributed
+// node -- all levels upward, then all levels downward, the unmerged blocks throughout (the transposed sweeps do not use the
+// assembled top).  Column 0 runs on the factorisation's own update vectors, column q > 0 on f->multi[q - 1].ubuf; the slot rows
+// and boundary vectors of the forward sweeps are not touched.
+template <typename MT, typename VT, bool CONJ, int R>
+int nd_sweepT_multi(lsa_ctx* ctx, lsa_ndlu* f, const VT* const* b, VT* const* x) {
+    hipStream_t st = ctx->stream;
+    const MT* lfac = (const MT*)f->d_lfac;
+    const MT* ufac = (const MT*)f->d_ufac;
+    NdMultiTPtrs<R> p;
+    for (int q = 0; q < R; ++q) {
+        p.rhs[q] = b[q];
+        p.x[q] = x[q];
+        p.ubuf[q] = q == 0 ? f->d_ubuf : f->multi[(size_t)q - 1].ubuf;
+    }
+    for (size_t li = 0; li < f->levels.size(); ++li) {
+        const NdLevel& L = f->levels[li];
+        if (L.fwd_tiles > 0)
+            hipLaunchKernelGGL((nd_sweepT_multi_kernel<MT, VT, CONJ, false, R>), dim3(L.node_count, (L.max_f + 63) / 64), dim3(256), 0, st,
+                               f->d_lnodes + L.node_begin, lfac, ufac, f->d_idx, f->d_gell, p);
+    }
+    for (size_t l = f->levels.size(); l-- > 0;) {
+        const NdLevel& L = f->levels[l];
+        if (L.bwd_tiles > 0)
+            hipLaunchKernelGGL((nd_sweepT_multi_kernel<MT, VT, CONJ, true, R>), dim3(L.node_count, (L.max_m + 63) / 64), dim3(256), 0, st,
+                               f->d_lnodes + L.node_begin, lfac, ufac, f->d_idx, f->d_gell, p);
+    }
+    LSA_HIP_CHECK(ctx, hipGetLastError());
+    return LSA_OK;
+}
+
 // sweep buffers for passes of `want` columns; returns how many columns a pass can have (1 + the extra sets that fitted).  An
 // allocation that fails narrows the passes of this and every later call; it is not an error.
 int32_t nd_multi_ensure(lsa_ctx* ctx, lsa_ndlu* f, int32_t want) {
@@ -438,6 +605,41 @@ int nd_solve_multi(lsa_ctx* ctx, lsa_ndlu* f, int32_t nrhs, const VT* B, int64_t
     return LSA_OK;
 }
 
+// the transposed block solve: the passes of nd_solve_multi; a last single column goes through the solo adjoint solve
+template <typename MT, typename VT, bool CONJ>
+int nd_solve_multi_adjoint(lsa_ctx* ctx, lsa_ndlu* f, int32_t nrhs, const VT* B, int64_t ldb, VT* X, int64_t ldx) {
+    const int32_t avail = nd_multi_ensure(ctx, f, nd_pass_width(nrhs, nd_multi_cap(sizeof(VT))));
+    const size_t nbytes = (size_t)f->S.n * sizeof(VT);
+    f->multi_width = 1;
+    for (int32_t q0 = 0; q0 < nrhs;) {
+        const int32_t R = nd_pass_width(nrhs - q0, avail);
+        if (R == 1) {
+            LSA_CHECK(ndlu_solve_adjoint_dev(ctx, f, CONJ, scalar_traits<VT>::dtype, B + (int64_t)q0 * ldb, X + (int64_t)q0 * ldx));
+            q0 += 1;
+            continue;
+        }
+        const VT* b[kNdMultiMax];
+        VT* x[kNdMultiMax];
+        for (int32_t q = 0; q < R; ++q) {
+            b[q] = B + (int64_t)(q0 + q) * ldb;
+            x[q] = X + (int64_t)(q0 + q) * ldx;
+            if (b[q] == x[q]) {  // in place: a tile reads the node's right-hand side while the others write its solution
+                void* tmp = q == 0 ? f->d_tmp : f->multi[(size_t)q - 1].tmp;
+                LSA_HIP_CHECK(ctx, hipMemcpyAsync(tmp, b[q], nbytes, hipMemcpyDeviceToDevice, ctx->stream));
+                b[q] = (const VT*)tmp;
+            }
+        }
+        if constexpr (sizeof(VT) == 8) {
+            if (R == 8) LSA_CHECK((nd_sweepT_multi<MT, VT, CONJ, 8>(ctx, f, b, x)));
+        }
+        if (R == 4) LSA_CHECK((nd_sweepT_multi<MT, VT, CONJ, 4>(ctx, f, b, x)));
+        if (R == 2) LSA_CHECK((nd_sweepT_multi<MT, VT, CONJ, 2>(ctx, f, b, x)));
+        f->multi_width = std::max(f->multi_width, R);
+        q0 += R;
+    }
+    return LSA_OK;
+}
+
 }  // namespace
 
 void ndlu_multi_free(lsa_ndlu* f) {
@@ -455,4 +657,19 @@ int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, co
     if (f->dtype == LSA_C128) return nd_solve_multi<cplx, cplx>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
     if (vdtype == LSA_C128) return nd_solve_multi<double, cplx>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
     return nd_solve_multi<double, double>(ctx, f, nrhs, (const double*)B, ldb, (double*)X, ldx);
+}
+
+// X[:, q] = C^-T B[:, q] (conj == 0) or C^-H B[:, q] on the factors of C, in passes that share every factor load
+int ndlu_solve_multi_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx) {
+    if (f->S.nranks > 1 || f->S.has_dist)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi: the transposed multi-column sweeps need one rank and no distributed node");
+    if (f->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi: complex factors need complex vectors");
+    if (f->S.n == 0) return LSA_OK;
+    if (f->dtype == LSA_C128) {
+        if (conj) return nd_solve_multi_adjoint<cplx, cplx, true>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
+        return nd_solve_multi_adjoint<cplx, cplx, false>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
+    }
+    // (real factors: C^H = C^T, one instance)
+    if (vdtype == LSA_C128) return nd_solve_multi_adjoint<double, cplx, false>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
+    return nd_solve_multi_adjoint<double, double, false>(ctx, f, nrhs, (const double*)B, ldb, (double*)X, ldx);
 }

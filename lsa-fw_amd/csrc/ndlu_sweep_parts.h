@@ -133,6 +133,13 @@ __device__ __forceinline__ VT slot_sum(const VT* __restrict__ slots, int32_t nch
     return v;
 }
 
+// a factor scalar as the transposed sweeps use it: conjugated for C^-H on complex factors
+template <bool CONJ, typename MT>
+__device__ __forceinline__ MT maybe_conj(MT a) {
+    if constexpr (CONJ) return s_conj(a);
+    else return a;
+}
+
 // downward sweep: the value of front position j goes into the boundary vector of every child that has j in its boundary
 template <typename VT>
 __device__ __forceinline__ void push_down(const int32_t* __restrict__ ge, int32_t nchild, int32_t f, int32_t j, VT* __restrict__ xb, VT val) {

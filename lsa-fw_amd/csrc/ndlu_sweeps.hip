@@ -304,12 +304,7 @@ __global__ __launch_bounds__(256) void nd_dist_unpack_kernel(const int32_t* __re
 //     down:  x[own] = y[own] + S1^T x[boundary]
 // Column access of row-major blocks: 64 lanes run along a row (coalesced), four slices of the rows per workgroup.  These
 // sweeps keep the pull form (gather rows + update vectors) and address the vectors through idx.
-template <bool CONJ, typename MT>
-__device__ __forceinline__ MT maybe_conj(MT a) {
-    if constexpr (CONJ) return s_conj(a);
-    else return a;
-}
-
+// (maybe_conj: ndlu_sweep_parts.h, shared with the multi-column form of this kernel in ndlu_multi.hip.)
 template <typename MT, typename VT, bool CONJ, bool DOWN>
 __global__ __launch_bounds__(256) void nd_sweepT_kernel(const NdSweepNode* __restrict__ lnodes, const MT* __restrict__ lfac, const MT* __restrict__ ufac,
                                                         const int32_t* __restrict__ idx, const int32_t* __restrict__ gell,

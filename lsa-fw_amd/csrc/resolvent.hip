@@ -280,6 +280,12 @@ struct lsa_resolvent {
     bool refine_adj = false, refine_fwd = false;
     int64_t solves_adj = 0, solves_fwd = 0, refined_adj = 0, refined_fwd = 0;
     std::vector<double> hslot;
+    // lsa_resolvent_set_block_forcings: the forcings' adjoint solves as one block solve.  Its work vectors (M q_c and C^-H M q_c,
+    // blk_cols columns each) and the three sums per column of the check are made by the first block call.
+    bool block_forcings = false;
+    cplx *blk_tm = nullptr, *blk_za = nullptr;
+    double* blk_norms = nullptr;
+    int32_t blk_cols = 0;
 };
 
 namespace {
@@ -292,7 +298,7 @@ size_t rz_slot_doubles(int32_t ncv) { return rz_out_at(ncv) + 10; }
 void rz_free(lsa_resolvent* l) {
     for (void* p : {(void*)l->V, (void*)l->V2, (void*)l->xtmp, (void*)l->row_perm, (void*)l->za, (void*)l->ca, (void*)l->tm, (void*)l->r, (void*)l->w,
                     (void*)l->t, (void*)l->cf, (void*)l->rhs[0], (void*)l->rhs[1], (void*)l->part, (void*)l->chk_part, (void*)l->slot, (void*)l->rnorms,
-                    (void*)l->qdev, (void*)l->imag2})
+                    (void*)l->qdev, (void*)l->imag2, (void*)l->blk_tm, (void*)l->blk_za, (void*)l->blk_norms})
         if (p) (void)hipFree(p);
     delete l;
 }
@@ -461,12 +467,86 @@ int resolvent_ritz_vectors(lsa_ctx* ctx, lsa_resolvent* l, int32_t m, int32_t nv
     return rz_scatter_out(ctx, l, nvec, Q);
 }
 
+namespace {
+
+// The forcings' first attempts as ONE adjoint block solve (lsa_resolvent_set_block_forcings, no refinement step switched on yet):
+// tm_c = M q_c for all columns, z_c = C^-H tm_c in the wide passes of the transposed sweeps, then per column what
+// direct_solve_enqueue and the loop of resolvent_forcings queue behind the sweeps -- the check product C^H z_c, its residual sums
+// and |z_c|^2 -- and one read-back for all of them.  The columns are judged in order: an accepted one is booked and scaled as the
+// loop does it; the first that misses ksp_rtol switches the refinement step on and ends the block.  *done: the columns finished;
+// the loop takes the rest (every column is the loop's, bit for bit and count for count).  An allocation that fails leaves all
+// columns to the loop.
+int rz_forcings_block(lsa_ctx* ctx, lsa_resolvent* l, int32_t nvec, const double* gain, int32_t* done) {
+    *done = 0;
+    const int64_t n = l->n;
+    if (l->blk_cols < nvec) {
+        for (void* p : {(void*)l->blk_tm, (void*)l->blk_za, (void*)l->blk_norms})
+            if (p) (void)hipFree(p);
+        l->blk_tm = l->blk_za = nullptr;
+        l->blk_norms = nullptr;
+        l->blk_cols = 0;
+        const size_t bytes = (size_t)std::max<int64_t>(n, 1) * sizeof(cplx) * (size_t)nvec;
+        if (hipMalloc((void**)&l->blk_tm, bytes) != hipSuccess || hipMalloc((void**)&l->blk_za, bytes) != hipSuccess ||
+            hipMalloc((void**)&l->blk_norms, (size_t)3 * (size_t)nvec * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            for (void* p : {(void*)l->blk_tm, (void*)l->blk_za, (void*)l->blk_norms})
+                if (p) (void)hipFree(p);
+            l->blk_tm = l->blk_za = nullptr;
+            l->blk_norms = nullptr;
+            return LSA_OK;
+        }
+        l->blk_cols = nvec;
+    }
+    for (int32_t c = 0; c < nvec; ++c)
+        if (!(gain[c] > 0.0) || !std::isfinite(gain[c]))
+            return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent forcings: gain %d is %.3e: no forcing belongs to it", c, gain[c]);
+    // (a product is counted where its column is accepted: a column the loop takes over forms, and counts, its own)
+    for (int32_t c = 0; c < nvec; ++c) LSA_CHECK(k_spmv(ctx, l->P.Kmul, LSA_C128, l->V2 + (size_t)c * (size_t)n, l->blk_tm + (size_t)c * (size_t)n));
+    LSA_CHECK(ndlu_solve_multi_adjoint_dev(ctx, l->P.nd, 1, LSA_C128, nvec, l->blk_tm, n, l->blk_za, n));
+    for (int32_t c = 0; c < nvec; ++c) {
+        const cplx* tm = l->blk_tm + (size_t)c * (size_t)n;
+        const cplx* za = l->blk_za + (size_t)c * (size_t)n;
+        LSA_CHECK(k_spmv_transpose(ctx, l->P.Kfac, 1, LSA_C128, za, l->ca));
+        LSA_CHECK(k_residual_norms(ctx, LSA_C128, n, tm, l->ca, l->r, l->blk_norms + 3 * (size_t)c));
+        LSA_CHECK(k_nrm2(ctx, LSA_C128, n, za, l->blk_norms + 3 * (size_t)c + 2));
+    }
+    const size_t bytes = (size_t)3 * (size_t)nvec * sizeof(double);
+    LSA_CHECK(lsa_ensure_scratch(ctx, 0, bytes));
+    LSA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->pinned, l->blk_norms, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<double> sums((const double*)ctx->pinned, (const double*)ctx->pinned + 3 * (size_t)nvec);
+    for (int32_t c = 0; c < nvec; ++c) {
+        const double res = std::sqrt(sums[3 * (size_t)c]), bnorm = std::sqrt(sums[3 * (size_t)c + 1]), xnorm = std::sqrt(sums[3 * (size_t)c + 2]);
+        bool backward = false;
+        const int verdict = rz_judge(l->P, false, res, bnorm, xnorm, &backward);
+        if (verdict > 0) {
+            l->refine_adj = true;
+            break;
+        }
+        if (verdict < 0)
+            return lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_resolvent forcings: the adjoint solve of forcing %d left a relative residual of %.3e after its "
+                                                        "refinement step (ksp_rtol %.1e) and a backward error above 1e-12 ||C||_F", c,
+                                 bnorm > 0.0 ? res / bnorm : res, l->P.ksp_rtol);
+        ++l->P.st->spmv_calls;
+        rz_book(l, true, false, backward, res, bnorm);
+        hipLaunchKernelGGL(rz_scale_kernel, dim3(rz_grid(ctx, n, 8)), dim3(kRzThreads), 0, ctx->stream, n, -1.0 / gain[c], l->blk_za + (size_t)c * (size_t)n,
+                           l->V2 + (size_t)c * (size_t)n);
+        LSA_CHECK(rz_check_launch(ctx, "resolvent forcings"));
+        *done = c + 1;
+    }
+    return LSA_OK;
+}
+
+}  // namespace
+
 int resolvent_forcings(lsa_ctx* ctx, lsa_resolvent* l, int32_t nvec, const double* gain, cplx* F) {
     if (!ctx || !l || !gain || !F) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent forcings: null argument");
     if (nvec < 0 || nvec > l->ncv) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent forcings: bad sizes");
     const int64_t n = l->n;
     double* norms = l->slot + rz_out_at(l->ncv);  // (the step's slot is free between steps: |rhs - C^H z|^2, |rhs|^2, and |z|^2 behind them)
-    for (int32_t c = 0; c < nvec; ++c) {
+    int32_t first = 0;
+    if (l->block_forcings && !l->refine_adj && nvec > 1) LSA_CHECK(rz_forcings_block(ctx, l, nvec, gain, &first));
+    for (int32_t c = first; c < nvec; ++c) {
         if (!(gain[c] > 0.0) || !std::isfinite(gain[c]))
             return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent forcings: gain %d is %.3e: no forcing belongs to it", c, gain[c]);
         cplx* q = l->V2 + (size_t)c * (size_t)n;
@@ -549,6 +629,12 @@ void lsa_resolvent_destroy(lsa_resolvent* l) {
 int lsa_resolvent_set_row_permutation(lsa_ctx* ctx, lsa_resolvent* l, const int32_t* perm) {
     if (!ctx || !l) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_set_row_permutation: null argument");
     return basis_upload_row_permutation(ctx, "lsa_resolvent_set_row_permutation", l->n, perm, &l->row_perm);
+}
+
+int lsa_resolvent_set_block_forcings(lsa_ctx* ctx, lsa_resolvent* l, int on) {
+    if (!ctx || !l) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_set_block_forcings: null argument");
+    l->block_forcings = on != 0;
+    return LSA_OK;
 }
 
 int lsa_resolvent_set_start(lsa_ctx* ctx, lsa_resolvent* l, const void* host_v) { return resolvent_inject(ctx, l, 0, (const cplx*)host_v); }

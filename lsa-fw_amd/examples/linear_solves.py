@@ -58,6 +58,16 @@ def main() -> None:
     print(f"block solve of {args.rhs} columns {time.time() - t0:.3f} s: |B - J X|/|B| = {np.linalg.norm(B - J @ X) / np.linalg.norm(B):.1e}, "
           f"pass width {ksp.stats['multi_width']}")
 
+    # the adjoint systems J^H Y = B on the same factors (sensitivities): column by column by default, in the wide passes of the
+    # block solve above with block_adjoint -- the same bits either way
+    t0 = time.time()
+    Y = ksp.solve_many(B, adjoint=True)
+    t1 = time.time()
+    ksp.block_adjoint = True
+    Yb = ksp.solve_many(B, adjoint=True)
+    print(f"adjoint block solve {t1 - t0:.3f} s column by column, {time.time() - t1:.3f} s with block_adjoint (pass width {ksp.stats['multi_width']}): "
+          f"|B - J^H Y|/|B| = {np.linalg.norm(B - J.conj().T @ Yb) / np.linalg.norm(B):.1e}, same bits: {np.array_equal(Y, Yb)}")
+
     J2 = jacobian(es, 0.7)  # the next Newton step's Jacobian: the same pattern, new values
     ksp.set_operators(J2)
     t0 = time.time()

@@ -170,6 +170,7 @@ SIGNATURES = {
     "lsa_ndlu_solve_time": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.POINTER(_DBL)]),
     "lsa_ndlu_solve_multi": (ctypes.c_int, [_P, _P, ctypes.c_int, _I32, _P, _I64, _P, _I64]),
     "lsa_ndlu_solve_multi_time": (ctypes.c_int, [_P, _P, ctypes.c_int, _I32, _P, _I64, _P, _I64, ctypes.c_int, ctypes.POINTER(_DBL)]),
+    "lsa_ndlu_set_multi_transposed": (ctypes.c_int, [_P, _P, ctypes.c_int]),
     "lsa_ndlu_multi_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "lsa_ndlu_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64),
                                      ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_DBL), ctypes.POINTER(_DBL)]),
@@ -213,6 +214,7 @@ SIGNATURES = {
     "lsa_resolvent_create": (ctypes.c_int, [_P, _P, _I32, _PP]),
     "lsa_resolvent_destroy": (None, [_P]),
     "lsa_resolvent_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
+    "lsa_resolvent_set_block_forcings": (ctypes.c_int, [_P, _P, ctypes.c_int]),
     "lsa_resolvent_set_start": (ctypes.c_int, [_P, _P, _P]),
     "lsa_resolvent_extend": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_I32)]),
     "lsa_resolvent_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
@@ -780,8 +782,13 @@ class NdLu:
         self.ctx.check(self.ctx._lib.lsa_ndlu_solve_multi_time(*self._multi_args(B, X, nrhs, ldb, ldx, trans), int(iters), ctypes.byref(ms)))
         return ms.value
 
+    def set_multi_transposed(self, on: bool) -> None:
+        """``True``: :meth:`solve_multi` and :meth:`time_solve_multi` with ``trans`` ``"T"`` / ``"H"`` run in the wide passes of
+        ``trans="N"`` (``lsa_ndlu_set_multi_transposed``; same bits per column).  Off by default: column by column."""
+        self.ctx.check(self.ctx._lib.lsa_ndlu_set_multi_transposed(self.ctx.handle, self.handle, int(bool(on))))
+
     def multi_info(self) -> dict:
-        """What the last :meth:`solve_multi` used: ``width`` (columns of its widest pass; 1 = column by column, 0 = none yet),
+        """What the last :meth:`solve_multi` used, in either direction: ``width`` (columns of its widest pass; 1 = column by column, 0 = none yet),
         ``extra_bytes`` (per-column sweep buffers), ``launches_per_pass``."""
         w, la, eb = _I32(0), _I32(0), _I64(0)
         self.ctx.check(self.ctx._lib.lsa_ndlu_multi_info(self.handle, ctypes.byref(w), ctypes.byref(eb), ctypes.byref(la)))
@@ -1140,6 +1147,11 @@ class ResolventBasis:
         p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
         self.ctx.check(self.ctx._lib.lsa_resolvent_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
         self._has_perm = p is not None
+
+    def set_block_forcings(self, on: bool) -> None:
+        """``True``: the forcings of :meth:`solve` take their adjoint solves as one block solve on the factors
+        (``lsa_resolvent_set_block_forcings``); the results are those of the default, bit for bit."""
+        self.ctx.check(self.ctx._lib.lsa_resolvent_set_block_forcings(self.ctx.handle, self.handle, int(bool(on))))
 
     def _start(self, v) -> np.ndarray:
         v = np.ascontiguousarray(v, dtype=np.complex128)

@@ -1,6 +1,6 @@
 """Optimal gains: the library's resolvent iteration against what a user can drive from the host on kept factors.
 
-    python tools/resolvent_ab.py [--cases S30k C160k] [--reps 3] [--out profiles/resolvent_ab.json]
+    python tools/resolvent_ab.py [--cases S30k C160k] [--reps 3] [--forcings] [--out profiles/resolvent_ab.json]
 
 ``library`` (a): ``Solver.resolvent.ResolventSolver.solve`` -- set-up, one factorisation of ``A - i omega M``, the thick-restart Lanczos
 iteration on ``W = C^-1 M C^-H M`` with both inner solves, their checks and the orthogonalisation on the device, one read-back per step.
@@ -15,6 +15,12 @@ settings alternate in one process after one warm-up of each; medians and spread 
 compared with those of (a).  Launches and read-backs per step are counted from the step's code (``csrc/resolvent.hip``), not timed;
 the per-kernel times of the three step kernels come from a separate ``rocprofv3 --kernel-trace --stats`` run of ``--only library``.
 No test asserts these times.
+
+``--forcings`` measures the forcings phase instead and records it under the key ``forcings_phase`` of the same file (the other keys
+stay): ``ResolventSolver.solve`` without forcings, with them one adjoint solve at a time, and with ``block_forcings=True`` (one block
+solve), alternately after a warm-up of each.  The figure is ``stats["seconds_restart"]``, the loop's phase that holds the thick restarts, the
+Ritz vectors and, where asked for, the forcings: a setting's figure minus that of the run without forcings is its forcings phase.  The
+forcings of the two settings are compared bit for bit.
 """
 
 from __future__ import annotations
@@ -96,6 +102,39 @@ def host(es, omega: float) -> dict:
             "read_backs_per_product": 2}
 
 
+def forcings_run(es, omega: float, forcings: bool, block: bool) -> dict:
+    from Solver.resolvent import ResolventConfig, ResolventSolver
+
+    rs = ResolventSolver(es.A, es.M, ResolventConfig(num_modes=MODES, ncv=NCV, atol=TOL), block_forcings=block)
+    res = rs.solve(omega, forcings=forcings)
+    rs.release()
+    st = res.stats
+    return {"forcings": res.forcings, "gains": res.gains, "seconds_restart": st["seconds_restart"], "seconds_steps": st["seconds_expand"],
+            "adjoint_solves": st["adjoint_solves"], "refined_adjoint": st["refined_adjoint"]}
+
+
+def forcings_phase(cases, reps: int) -> dict:
+    settings = {"none": (False, False), "one_by_one": (True, False), "block": (True, True)}
+    out = {"config": {"num_modes": MODES, "ncv": NCV, "tol": TOL, "reps": reps}, "cases": []}
+    for case in cases:
+        es, omega = problem(case)
+        warm = {name: forcings_run(es, omega, *flags) for name, flags in settings.items()}
+        runs = {name: [] for name in settings}
+        for _ in range(reps):
+            for name, flags in settings.items():
+                runs[name].append(forcings_run(es, omega, *flags)["seconds_restart"])
+        med = {name: statistics.median(v) for name, v in runs.items()}
+        entry = {"case": case, "n": int(es.A.shape[0]), "omega": omega, "columns": int(len(warm["block"]["gains"])),
+                 "bit_identical": bool(np.array_equal(warm["one_by_one"]["forcings"], warm["block"]["forcings"])),
+                 "adjoint_solves": [warm["one_by_one"]["adjoint_solves"], warm["block"]["adjoint_solves"]],
+                 "refined_adjoint": [warm["one_by_one"]["refined_adjoint"], warm["block"]["refined_adjoint"]],
+                 "seconds_restart": {name: spread(v) for name, v in runs.items()},
+                 "forcings_seconds_one_by_one": med["one_by_one"] - med["none"], "forcings_seconds_block": med["block"] - med["none"]}
+        out["cases"].append(entry)
+        print(json.dumps(entry), flush=True)
+    return out
+
+
 def plain(run: dict) -> dict:
     return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in run.items()}
 
@@ -110,7 +149,14 @@ def main(argv=None) -> None:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--only", choices=("library", "host"), default=None, help="one setting alone, once per case (for a kernel trace)")
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "resolvent_ab.json")
+    ap.add_argument("--forcings", action="store_true", help="the forcings phase with block_forcings off and on -> key forcings_phase of --out")
     args = ap.parse_args(argv)
+    if args.forcings:
+        doc = json.loads(args.out.read_text()) if args.out.exists() else {}
+        doc["forcings_phase"] = forcings_phase(args.cases, args.reps)
+        args.out.parent.mkdir(parents=True, exist_ok=True)
+        args.out.write_text(json.dumps(doc, indent=1) + "\n")
+        return
     settings = {"library": library, "host": host}
     if args.only:
         for case in args.cases:
