@@ -566,6 +566,75 @@ int lsa_growth_solve(lsa_ctx *ctx, lsa_growth *g, const lsa_ks_options *opts, co
                      double *gain_out, double *Q0_out, double *QT_out, double *energy_out, double *est_out, lsa_ks_result *result,
                      int64_t *counts);
 
+/* ---- region eigensolver: all eigenvalues inside a contour, with a count (what SLEPc answers with EPSCISS and an RG region; the
+ * reference's door to it is iEpsSolver.set_interval_complex, Solver/utils.py:252-254) ------------------------------------------------
+ * Contour-integral (FEAST-type) subspace iteration for A x = lambda M x on an ellipse with centre c and semi-axes rx, ry: nodes
+ * z_k = c + rx cos t_k + i ry sin t_k, t_k = 2 pi (k + 1/2) / N (none on the real axis), weights w_k = (ry cos t_k + i rx sin t_k) / N.
+ * One iteration on the n x L complex block Y: B = M Y; Q = -sum_k w_k C_k^-1 B with C_k = A - z_k M factorised by the
+ * nested-dissection LU on ONE ordering and ONE pattern-only analysis (block solves in lsa_ndlu_solve_multi's passes); U = Q
+ * orthonormalised twice through its Gram matrix (directions below 1e-14 of the largest Gram eigenvalue are dropped: the rank may
+ * shrink); Ritz pairs of (U^H A U, U^H M U); residuals ||A x - lam M x|| / (||A x|| + |lam| ||M x||).  It stops when every Ritz
+ * value inside the ellipse has a residual <= tol (with none inside: from the second iteration on), or at max_it.  Every sum runs in a fixed order without atomics: two runs return
+ * the same bits, and so do kept and refactorised factor sets.
+ * The spectrum must not crowd the subspace: the iteration contracts like the quadrature's filter at the (L+1)-th nearest eigenvalue,
+ * so L has to exceed the count inside generously (dense spectra: by half as much again or more); `complete` says whether it did. */
+/* The two building blocks on lsa_vec blocks.  Blocks are column-major in ONE complex128 vector each: column c starts at c * ld
+ * scalars, ld >= n, the vector at least ld (cols - 1) + n long; anything else is LSA_ERR_ARG. */
+/* Y[:, 0:ncols] = A X[:, 0:ncols]: MatMatMult on a dense block.  A whole square matrix (no row shard), float64 or complex128; X and Y
+ * apart.  Every pass of up to 8 columns reads A's indices and values once.  The sums are not in lsa_spmv's order: column c need not
+ * hold lsa_spmv's bits. */
+int lsa_spmm(lsa_ctx *ctx, const lsa_mat *A, int32_t ncols, const lsa_vec *X, int64_t ldx, lsa_vec *Y, int64_t ldy);
+/* G = U^H W over the first n rows: U has p columns, W has q, 1 <= p, q <= 128; G is the caller's p x q column-major complex host
+ * array.  Per-workgroup partial sums, then one finishing pass in chunk order; synchronises.  U and W one and the same block
+ * (same vector, ld and column count): the diagonal is returned exactly real. */
+int lsa_block_gram(lsa_ctx *ctx, int64_t n, int32_t p, const lsa_vec *U, int64_t ldu, int32_t q, const lsa_vec *W, int64_t ldw, void *G);
+typedef struct lsa_contour lsa_contour;
+typedef struct {
+    int32_t iterations;        /* iterations run                                                                          */
+    int32_t rank;              /* columns of the last orthonormal basis (<= subspace)                                     */
+    int32_t inside;            /* Ritz values inside the ellipse in the last iteration                                    */
+    int32_t converged_inside;  /* ... of them with residual <= tol                                                        */
+    int32_t complete;          /* 1: stopped because all inside had converged AND inside < rank (spare directions left)   */
+    int32_t nout;              /* pairs written: min(inside, max_out)                                                     */
+    double estimate;           /* Re sum_j y_j^H q_j / L at iteration 0: stochastic estimate of the count inside (sizing) */
+    int64_t block_solves;      /* accepted column solves (nodes x columns x iterations)                                   */
+    int64_t refined_solves;    /* ... that carried the refinement step                                                    */
+    int64_t backward_accepted; /* ... accepted on the backward error                                                      */
+    double worst_rel_res;      /* worst ||b - C_k x|| / ||b|| of an accepted column solve                                 */
+} lsa_contour_result;
+typedef struct {
+    int32_t kept;              /* 1: N factor sets alive; 0: one set refactorised node by node in every iteration          */
+    int32_t nodes;
+    int64_t bytes;             /* device bytes of the six n x L blocks, the N value arrays of C_k and the small buffers
+                                  (the factor sets: lsa_ndlu_info / lsa_ndlu_prepared_memory)                              */
+    double seconds_factor;     /* building C_k, factorising (creation) and refactorising (solves)                          */
+    double seconds_solve;      /* block solves with their checks and refinement steps                                      */
+    double seconds_product;    /* M Y, A U, M U, the Ritz blocks and their residual sums                                   */
+    double seconds_gram;       /* Gram matrices and basis updates                                                          */
+    double seconds_dense;      /* host: Hermitian eigen-decompositions, the reduced problem                                */
+    lsa_stats solver;          /* counters of the column solves (op_applies, refined_solves, backward_accepted, max_rel_res, ...) */
+} lsa_contour_stats;
+/* A, M: the pencil on one shared pattern (M real), both outliving the handle.  Builds C_k = A - z_k M for the N nodes and
+ * factorises: keep_factors != 0 keeps N factor sets (every set after the first redoes the pattern-only phase from the first one's
+ * forest), 0 keeps one and refactorises it node by node in every iteration; both return the same bits.  The first set takes the
+ * analysis the context holds prepared (lsa_ndlu_prepare / lsa_ndlu_prepare_tree with LSA_C128).  ksp_rtol: what every column of
+ * every block solve must reach (||b - C_k x|| <= ksp_rtol ||b||; one refinement step on a miss, kept for that node from then on;
+ * then a backward error <= 1e-12 ||C_k||_F ||x||; else LSA_ERR_DIVERGED naming node and column).  LSA_ERR_ARG, naming the condition:
+ * several ranks, a missing or complex M, nodes < 4 or odd, subspace < 2, > 128 or > n, radii not positive.  A node on an eigenvalue:
+ * LSA_ERR_ZERO_PIVOT with the node's index in the message. */
+int lsa_contour_create(lsa_ctx *ctx, const lsa_mat *A, const lsa_mat *M, int32_t nodes, const double centre[2], const double radii[2],
+                       int32_t subspace, int keep_factors, double ksp_rtol, lsa_contour **out);
+void lsa_contour_destroy(lsa_contour *h);
+/* as lsa_krylov_set_row_permutation: the vectors of lsa_contour_solve leave in the caller's numbering (Y0 is in the matrices' own) */
+int lsa_contour_set_row_permutation(lsa_ctx *ctx, lsa_contour *h, const int32_t *perm);
+/* The iteration from the start block Y0 (host, n x subspace complex column-major).  Outputs: the Ritz pairs INSIDE the ellipse of the
+ * last iteration, nearest the centre (in the ellipse's metric) first: lam_out[max_out] complex, X_out (n x max_out complex
+ * column-major, unit 2-norm, canonical phase, the caller's row numbering; NULL: none), res_out[max_out].  LSA_OK also when the
+ * iteration ended at max_it or with a full subspace (see result->complete). */
+int lsa_contour_solve(lsa_ctx *ctx, lsa_contour *h, double tol, int32_t max_it, const void *Y0_host, int32_t max_out, void *lam_out,
+                      void *X_out, double *res_out, lsa_contour_result *result);
+int lsa_contour_info(const lsa_contour *h, lsa_contour_stats *out);
+
 /* ---- MatrixMarket reader (host only): the A.mtx / M.mtx stage boundary --------------------------------------------
  * Stands in for scipy.io.mmread + the per-entry setValue loop of iPETScMatrix.from_path / from_matrix
  * (FEM/utils.py:143-147,208-215).  Coordinate format; general / symmetric / hermitian / skew-symmetric; real / integer /

@@ -1,0 +1,250 @@
+"""Region eigensolver on the MI355X path: ALL eigenvalues of ``A x = lambda M x`` inside a contour, with a statement of completeness.
+
+:class:`Solver.eigen.EigenSolver` answers "which eigenvalues lie nearest this target"; a Krylov-Schur run proves nothing about what
+it did not find.  Stability analysis asks "is anything in this part of the right half plane?" of a non-symmetric pencil.  The library
+answers with a contour-integral (FEAST-type) subspace iteration (``lsa_contour_*``, ``csrc/contour.hip``): the spectral projector of
+the region is applied to a block of ``subspace`` vectors by a quadrature over ``nodes`` points of an ellipse, each a block solve on
+a nested-dissection LU of ``A - z_k M``; the Ritz pairs of the projected pencil converge to the eigenpairs inside::
+
+    cfg = RegionConfig(nodes=16, subspace=48, atol=1e-10, max_it=20)
+    rs = RegionEigenSolver(A, M, cfg)
+    res = rs.solve(Ellipse(0.018 + 0.738j, 0.12, 0.12))   # res.eigenvalues, res.count, res.complete
+    res = rs.solve(Rectangle(-0.05, 0.1, 0.65, 0.8))      # the circumscribing ellipse, filtered to the rectangle
+
+``complete`` is true when the iteration stopped because every Ritz value inside the ellipse had converged (an iteration that shows
+none inside is confirmed by a second one first) AND directions of the subspace were left over: then the ``count`` eigenvalues returned are all there are.  ``subspace`` must exceed the count inside
+generously (a dense spectrum next to the contour slows the iteration down to the quadrature's filter at the ``(subspace + 1)``-th
+nearest eigenvalue); ``estimate`` (a stochastic estimate of the count, from the first quadrature) helps sizing it.  The conjugate-node
+saving for real pencils, two-sided projection, automatic growth of the subspace and more than one GPU are not built (DESIGN.md,
+section 9).
+"""
+
+from __future__ import annotations
+
+import logging
+import math
+import time
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from .eigen import _require_matching_squares, _wrap
+from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType
+
+logger = logging.getLogger(__name__)
+
+
+def _finite(*values) -> bool:
+    return all(isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v) for v in values)
+
+
+@dataclass(frozen=True)
+class Ellipse:
+    """``((Re z - Re centre) / rx)^2 + ((Im z - Im centre) / ry)^2 < 1``."""
+
+    centre: complex
+    rx: float
+    ry: float
+
+    def __post_init__(self):
+        c = complex(self.centre)
+        if not (_finite(c.real, c.imag, self.rx, self.ry) and self.rx > 0 and self.ry > 0):
+            raise ValueError(f"Ellipse needs a finite centre and positive finite semi-axes, got centre={self.centre!r}, rx={self.rx!r}, ry={self.ry!r}")
+
+    def ellipse(self) -> "Ellipse":
+        return self
+
+    def contains(self, z) -> np.ndarray:
+        z, c = np.asarray(z, dtype=np.complex128), complex(self.centre)
+        return ((z.real - c.real) / self.rx) ** 2 + ((z.imag - c.imag) / self.ry) ** 2 < 1.0
+
+
+@dataclass(frozen=True)
+class Rectangle:
+    """``a < Re z < b`` and ``c < Im z < d`` (the arguments of ``set_interval_complex``).  The contour is the circumscribing ellipse,
+    with semi-axes ``sqrt(2)`` times the half-widths; eigenpairs and ``count`` are filtered to the rectangle, ``complete`` refers to
+    the ellipse and therefore covers the rectangle."""
+
+    a: float
+    b: float
+    c: float
+    d: float
+
+    def __post_init__(self):
+        if not (_finite(self.a, self.b, self.c, self.d) and self.a < self.b and self.c < self.d):
+            raise ValueError(f"Rectangle needs finite a < b and c < d, got ({self.a!r}, {self.b!r}, {self.c!r}, {self.d!r})")
+
+    def ellipse(self) -> Ellipse:
+        return Ellipse(complex(0.5 * (self.a + self.b), 0.5 * (self.c + self.d)), math.sqrt(2.0) * 0.5 * (self.b - self.a),
+                       math.sqrt(2.0) * 0.5 * (self.d - self.c))
+
+    def contains(self, z) -> np.ndarray:
+        z = np.asarray(z, dtype=np.complex128)
+        return (z.real > self.a) & (z.real < self.b) & (z.imag > self.c) & (z.imag < self.d)
+
+
+def contour_nodes(ellipse: Ellipse, nodes: int) -> tuple[np.ndarray, np.ndarray]:
+    """Nodes ``z_k = c + rx cos t_k + i ry sin t_k`` and weights ``w_k = (ry cos t_k + i rx sin t_k) / N`` at ``t_k = 2 pi (k + 1/2) / N``
+    (the half step keeps every node off the real axis): ``sum_k w_k / (z_k - lambda)`` is the midpoint rule for
+    ``(1 / 2 pi i) oint dz / (z - lambda)``.  The library computes the same numbers in ``lsa_contour_create``."""
+    t = 2.0 * np.pi * (np.arange(nodes) + 0.5) / nodes
+    c = complex(ellipse.centre)
+    return c + ellipse.rx * np.cos(t) + 1j * ellipse.ry * np.sin(t), (ellipse.ry * np.cos(t) + 1j * ellipse.rx * np.sin(t)) / nodes
+
+
+@dataclass(frozen=True)
+class RegionConfig:
+    nodes: int = 16  # quadrature nodes on the ellipse (even, at least 4): one factorisation each
+    subspace: int = 48  # columns of the block (2..128): must exceed the count inside generously
+    atol: float = 1e-10  # residual ||A x - lam M x|| / (||A x|| + |lam| ||M x||) of every Ritz pair inside
+    max_it: int = 20  # iterations allowed
+    keep_factors: bool | None = None  # all factor sets alive / one refactorised per node and iteration / None: by the free memory
+
+
+@dataclass
+class RegionResult:
+    eigenvalues: np.ndarray  # inside the region, nearest the centre first
+    eigenvectors: np.ndarray  # n x count complex, unit 2-norm, canonical phase, the caller's row order
+    residuals: np.ndarray
+    count: int
+    complete: bool  # every Ritz value inside the ellipse converged and the subspace had directions to spare
+    estimate: float  # stochastic estimate of the count inside the ellipse (first quadrature): for sizing `subspace`
+    iterations: int
+    stats: dict = field(default_factory=dict)
+
+
+def _check_config(cfg: RegionConfig) -> None:
+    if not isinstance(cfg.nodes, (int, np.integer)) or cfg.nodes < 4 or cfg.nodes % 2:
+        raise ValueError(f"nodes = {cfg.nodes!r} must be an even number of at least 4")
+    if not isinstance(cfg.subspace, (int, np.integer)) or not 2 <= cfg.subspace <= 128:
+        raise ValueError(f"subspace = {cfg.subspace!r} must lie between 2 and 128")
+    if not (_finite(cfg.atol) and cfg.atol > 0):
+        raise ValueError(f"atol = {cfg.atol!r} must be positive")
+    if not isinstance(cfg.max_it, (int, np.integer)) or cfg.max_it < 1:
+        raise ValueError(f"max_it = {cfg.max_it!r} must be at least 1")
+    if cfg.keep_factors not in (None, True, False):
+        raise ValueError(f"keep_factors = {cfg.keep_factors!r} must be True, False or None")
+
+
+class RegionEigenSolver:
+    """All eigenvalues of ``(A, M)`` inside a region; thin shell around :class:`iEpsSolver` 's preparation (union pattern,
+    nested-dissection ordering, permuted numbering, upload, pattern-only LU analysis) and ``lsa_hip.ContourSolver``."""
+
+    def __init__(self, A, M, cfg: RegionConfig | None = None, *, device: int = 0, layout: str = "single",
+                 pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
+                 ksp_rtol: float | None = None) -> None:
+        if A is None:
+            raise ValueError("Operator A is required.")
+        if M is None:
+            raise ValueError("The region eigensolver needs M: the contour integral is that of the pencil (A, M)")
+        A, M = _wrap(A), _wrap(M)
+        _require_matching_squares(A, M)
+        if M.as_scipy_array().dtype.kind == "c":
+            raise ValueError("The region eigensolver needs a real M; M is complex")
+        self._cfg = cfg if cfg is not None else RegionConfig()
+        _check_config(self._cfg)
+        if self._cfg.subspace > A.shape[0]:
+            raise ValueError(f"subspace = {self._cfg.subspace} exceeds the problem size {A.shape[0]}")
+        if layout != "single":
+            raise NotImplementedError(f"The region eigensolver runs on one GPU; the layout is '{layout}'")
+        pc_type = PreconditionerType(pc_type)
+        if pc_type not in (PreconditionerType.LU, PreconditionerType.CHOLESKY) or ilu_levels is not None:
+            raise NotImplementedError("The region eigensolver needs the exact LU (PreconditionerType.LU): every node of the contour is a block "
+                                      f"solve on its factors; the preconditioner is {pc_type.name}" + ("" if ilu_levels is None else f" with ILU level {ilu_levels}"))
+        eps = iEpsSolver(A, M, device=device, seed=seed, ksp_rtol=ksp_rtol)
+        eps.set_problem_type(iEpsProblemType.GNHEP)
+        eps.set_st_type(iSTType.SINVERT)
+        eps.set_st_pc_type(pc_type)
+        eps.set_tolerances(self._cfg.atol, self._cfg.max_it)
+        self._eps = eps
+        self._n = A.shape[0]
+        self._seed = seed
+        self._ksp_rtol = ksp_rtol if ksp_rtol is not None else float(np.clip(self._cfg.atol * 1e-2, 1e-13, 1e-8))
+
+    @property
+    def config(self) -> RegionConfig:
+        return self._cfg
+
+    @property
+    def solver(self) -> iEpsSolver:
+        """The eigen path's solver object whose preparation this one shares (``prepare()``, ``release()``)."""
+        return self._eps
+
+    def start_block(self) -> np.ndarray:
+        """The default start block: ``n x subspace`` complex normal from ``default_rng(seed)``, in the caller's row order."""
+        rng = np.random.default_rng(self._seed)
+        shape = (self._n, self._cfg.subspace)
+        return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
+
+    def _keep_factors(self, ctx) -> bool:
+        """``cfg.keep_factors``, or whether ``nodes`` factor sets and the blocks fit 0.8 of the free device memory."""
+        if self._cfg.keep_factors is not None:
+            return bool(self._cfg.keep_factors)
+        try:
+            need = self._cfg.nodes * ctx.prepared_lu_bytes() + 6 * 16 * self._n * self._cfg.subspace
+        except ValueError:  # (no analysis parked in the context: nothing to size by)
+            return False
+        return need <= 0.8 * ctx.mem_info()[0]
+
+    def solve(self, region, Y0: np.ndarray | None = None) -> RegionResult:
+        """The eigenpairs inside ``region`` (:class:`Ellipse` or :class:`Rectangle`) from the start block ``Y0`` (``n x subspace``,
+        the caller's row order; default :meth:`start_block`).  A second call keeps the context, the ordering and the LU analysis."""
+        import lsa_hip
+
+        if not isinstance(region, (Ellipse, Rectangle)):
+            raise ValueError(f"region must be an Ellipse or a Rectangle, got {region!r}")
+        ell, cfg, eps = region.ellipse(), self._cfg, self._eps
+        if Y0 is None:
+            Y0 = self.start_block()
+        Y0 = np.asarray(Y0, dtype=np.complex128)
+        if Y0.shape != (self._n, cfg.subspace):
+            raise ValueError(f"Y0 must have shape ({self._n}, {cfg.subspace}), got {Y0.shape}")
+        started = time.time()
+        z, _ = contour_nodes(ell, cfg.nodes)
+        eps.set_target(complex(z[0]))  # (a node is never real: the analysis is prepared for complex factors)
+        eps.prepare()
+        prep = eps._prepared
+        if prep["pc_code"] != 2:
+            raise NotImplementedError("The region eigensolver needs the exact LU")
+        ctx, perm = prep["ctx"], prep["perm"]
+        keep = self._keep_factors(ctx)
+        cs = None
+        try:
+            cs = lsa_hip.ContourSolver(ctx, prep["dA"], prep["dM"], cfg.nodes, ell.centre, ell.rx, ell.ry, cfg.subspace, keep_factors=keep,
+                                       ksp_rtol=self._ksp_rtol)
+            cs.set_row_permutation(perm)
+            out = cs.solve(cfg.atol, cfg.max_it, np.asfortranarray(Y0[perm]))
+            info = cs.info()
+        finally:
+            del cs  # (the handle goes before the matrices it borrows)
+        lam, X, res = out["eigenvalues"], out["eigenvectors"], out["residuals"]
+        if not out["complete"]:
+            if out["inside"] >= out["rank"]:
+                logger.warning("Region: the subspace is full: all %d Ritz values lie inside the contour after %d iterations, so eigenvalues may be "
+                               "missing; raise `subspace` (now %d; the estimate of the count inside is %.1f)", out["rank"], out["iterations"],
+                               cfg.subspace, out["estimate"])
+            else:
+                logger.warning("Region: max_it = %d reached with %d of %d Ritz values inside the contour converged (subspace %d, estimate of the "
+                               "count inside %.1f)", cfg.max_it, out["converged_inside"], out["inside"], cfg.subspace, out["estimate"])
+        sel = region.contains(lam)
+        st = info["solver"]
+        stats = {"iterations": out["iterations"], "rank": out["rank"], "inside_ellipse": out["inside"], "converged_inside": out["converged_inside"],
+                 "block_solves": out["block_solves"], "refined_solves": out["refined_solves"], "backward_accepted": out["backward_accepted"],
+                 "max_rel_res": out["worst_rel_res"], "factors_kept": info["kept"], "nodes": info["nodes"],
+                 "contour_bytes": info["bytes"], "analysis_reused": bool(st["analysis_reused"]), "seconds_factor": info["seconds_factor"],
+                 "seconds_solve": info["seconds_solve"], "seconds_product": info["seconds_product"], "seconds_gram": info["seconds_gram"],
+                 "seconds_dense": info["seconds_dense"], "seconds_total": time.time() - started}
+        return RegionResult(lam[sel], np.asfortranarray(X[:, sel]), res[sel], int(np.count_nonzero(sel)), bool(out["complete"]),
+                            float(out["estimate"]), int(out["iterations"]), stats)
+
+    def sweep(self, regions, Y0: np.ndarray | None = None) -> list[RegionResult]:
+        """One result per region on ONE context, ordering and LU analysis (``stats["analysis_reused"]``); every region returns the
+        bytes a fresh solver gives for it."""
+        regions = list(regions)
+        for r in regions:
+            if not isinstance(r, (Ellipse, Rectangle)):
+                raise ValueError(f"region must be an Ellipse or a Rectangle, got {r!r}")
+        return [self.solve(r, Y0) for r in regions]
+
+    def release(self) -> None:
+        self._eps.release()

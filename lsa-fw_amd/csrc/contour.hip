@@ -1,0 +1,796 @@
+// Region eigensolver: all eigenvalues of A x = lambda M x inside an ellipse, with a statement of completeness, by a contour-integral
+// (FEAST-type) subspace iteration on an n x L complex128 block Y (column-major):
+//     B = M Y                                                  ci_spmm_kernel
+//     for every node z_k of the contour: X = C_k^-1 B on the nested-dissection LU of C_k = A - z_k M (ndlu_solve_multi_dev), each
+//         column checked (R = C_k X by ci_spmm_kernel, the three sums by ci_residual_kernel), then Q (+)= -w_k X
+//                                                              ci_accumulate_kernel
+//     U = orth(Q) through the Gram matrix, twice               ci_gram_kernel + host Hermitian eigen-decomposition + k_basis_gemm
+//     A_h = U^H (A U), M_h = U^H (M U), Ritz pairs of M_h^-1 A_h on the host (complex LU, lsa_dense_schur)
+//     residuals of all Ritz pairs from A U, M U and S          k_basis_gemm + ci_residual_kernel
+// Q = -sum_k w_k C_k^-1 M Y is the quadrature of the spectral projector (1 / 2 pi i) oint (z M - A)^-1 M dz applied to Y.  The two
+// building blocks are also entry points of their own (lsa_spmm, lsa_block_gram); blocks have leading dimensions >= n there and n
+// inside the iteration.
+//
+// Every sum runs in a fixed order and there are no floating-point atomics: two calls give the same bits.
+//   ci_spmm_kernel   the entries of a row strided over the 8 lanes of its row group, each lane adding its entries in order; then the
+//                    xor tree over the 8 lanes.  A pass of up to 8 columns reads the matrix's indices and values once.
+//   ci_gram_kernel   the rows of a chunk strided over the 256 threads, each adding its rows in order; the xor tree of the wavefront;
+//                    the four waves in wave order; ci_gram_finish_kernel then adds the chunks in chunk order.
+#include <algorithm>
+#include <cmath>
+#include <complex>
+#include <numeric>
+
+#include "lsa_internal.h"
+#include "nd_internal.h"
+#include "ndlu_internal.h"
+
+namespace {
+
+constexpr int kCiThreads = 256;       // four wavefronts of 64
+constexpr int kCiRowLanes = 8;        // lanes that share a row of ci_spmm_kernel
+constexpr int kCiColTile = 8;         // columns of a pass of ci_spmm_kernel: 8 accumulators of 16 bytes per lane
+constexpr int kCiGramTile = 4;        // ci_gram_kernel: a workgroup sums a 4 x 4 tile of G (16 accumulators per thread)
+constexpr int kCiGramMaxChunks = 64;  // row chunks of ci_gram_kernel = partial sums per entry of G
+constexpr int kCiMaxCols = 128;       // p, q of lsa_block_gram
+
+// a complex entry is moved as one 16-byte access (cplx itself is only 8-byte aligned); every array of this file is 16-byte
+// aligned: hipMalloc, offsets in whole complex numbers
+typedef double ci_d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ cplx ci_ld(const cplx* p) {
+    const ci_d2 v = *reinterpret_cast<const ci_d2*>(p);
+    return cplx{v.x, v.y};
+}
+__device__ __forceinline__ double ci_ld(const double* p) { return *p; }
+__device__ __forceinline__ void ci_st(cplx* p, cplx v) {
+    ci_d2 o;
+    o.x = v.re;
+    o.y = v.im;
+    *reinterpret_cast<ci_d2*>(p) = o;
+}
+
+// Y[:, 0:nc] = A X[:, 0:nc], nc <= kCiColTile.  Row r belongs to the 8 lanes 8 (r % 32) .. of workgroup r / 32; lane s takes the
+// entries rp[r] + s, rp[r] + s + 8, ...: one load of the column index and of the value per entry, then the nc entries of that row
+// of X (all requested before the first multiply-add of a full pass).  Rows beyond n take an empty range, so that every lane of a
+// wavefront reaches the shuffles.
+template <typename MT>
+__global__ __launch_bounds__(kCiThreads) void ci_spmm_kernel(int32_t n, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                             const MT* __restrict__ val, int nc, const cplx* __restrict__ X, int64_t ldx,
+                                                             cplx* __restrict__ Y, int64_t ldy) {
+    const int sub = threadIdx.x & (kCiRowLanes - 1);
+    const int64_t row = (int64_t)blockIdx.x * (kCiThreads / kCiRowLanes) + (threadIdx.x / kCiRowLanes);
+    int32_t p0 = 0, p1 = 0;
+    if (row < n) {
+        p0 = rp[row];
+        p1 = rp[row + 1];
+    }
+    cplx acc[kCiColTile];
+#pragma unroll
+    for (int u = 0; u < kCiColTile; ++u) acc[u] = cplx{0.0, 0.0};
+    if (nc == kCiColTile) {
+        for (int32_t p = p0 + sub; p < p1; p += kCiRowLanes) {
+            const cplx* x = X + ci[p];
+            const MT a = ci_ld(val + p);
+            cplx xv[kCiColTile];
+#pragma unroll
+            for (int u = 0; u < kCiColTile; ++u) xv[u] = ci_ld(x + (int64_t)u * ldx);
+#pragma unroll
+            for (int u = 0; u < kCiColTile; ++u) fma_acc(acc[u], a, xv[u]);
+        }
+    } else {
+        for (int32_t p = p0 + sub; p < p1; p += kCiRowLanes) {
+            const cplx* x = X + ci[p];
+            const MT a = ci_ld(val + p);
+#pragma unroll
+            for (int u = 0; u < kCiColTile; ++u)
+                if (u < nc) fma_acc(acc[u], a, ci_ld(x + (int64_t)u * ldx));
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < kCiColTile; ++u) {
+#pragma unroll
+        for (int off = kCiRowLanes / 2; off >= 1; off >>= 1) {
+            acc[u].re += __shfl_xor(acc[u].re, off, 64);
+            acc[u].im += __shfl_xor(acc[u].im, off, 64);
+        }
+    }
+    if (sub == 0 && row < n) {
+#pragma unroll
+        for (int u = 0; u < kCiColTile; ++u)
+            if (u < nc) ci_st(Y + row + (int64_t)u * ldy, acc[u]);
+    }
+}
+
+__device__ __forceinline__ cplx ci_wave_sum(cplx v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        v.re += __shfl_xor(v.re, off, 64);
+        v.im += __shfl_xor(v.im, off, 64);
+    }
+    return v;
+}
+
+// Partial sums of the tile G[i0 .. i0 + 4, j0 .. j0 + 4) of G = U^H W over the rows of one chunk: workgroup (chunk, i0 / 4, j0 / 4)
+// writes part[(chunk q + j) p + i].  A full tile has its eight 16-byte loads of a row in flight before the first addition.
+__global__ __launch_bounds__(kCiThreads) void ci_gram_kernel(int64_t n, int64_t rows_per_block, int p, int q, const cplx* __restrict__ U, int64_t ldu,
+                                                             const cplx* __restrict__ W, int64_t ldw, cplx* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) cplx wsum[4][kCiGramTile * kCiGramTile];
+    const int chunk = blockIdx.x;
+    const int i0 = blockIdx.y * kCiGramTile, j0 = blockIdx.z * kCiGramTile;
+    const int np = (p - i0 < kCiGramTile) ? p - i0 : kCiGramTile;
+    const int nq = (q - j0 < kCiGramTile) ? q - j0 : kCiGramTile;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t r0 = (int64_t)chunk * rows_per_block;
+    const int64_t r1 = (r0 + rows_per_block < n) ? r0 + rows_per_block : n;
+    const cplx* ucol = U + (int64_t)i0 * ldu;
+    const cplx* wcol = W + (int64_t)j0 * ldw;
+    cplx acc[kCiGramTile][kCiGramTile];
+#pragma unroll
+    for (int a = 0; a < kCiGramTile; ++a)
+#pragma unroll
+        for (int b = 0; b < kCiGramTile; ++b) acc[a][b] = cplx{0.0, 0.0};
+    if (np == kCiGramTile && nq == kCiGramTile) {
+        for (int64_t i = r0 + threadIdx.x; i < r1; i += kCiThreads) {
+            cplx u[kCiGramTile], w[kCiGramTile];
+#pragma unroll
+            for (int a = 0; a < kCiGramTile; ++a) u[a] = ci_ld(ucol + i + (int64_t)a * ldu);
+#pragma unroll
+            for (int b = 0; b < kCiGramTile; ++b) w[b] = ci_ld(wcol + i + (int64_t)b * ldw);
+#pragma unroll
+            for (int a = 0; a < kCiGramTile; ++a)
+#pragma unroll
+                for (int b = 0; b < kCiGramTile; ++b) fma_conj_acc(acc[a][b], u[a], w[b]);
+        }
+    } else {
+        for (int64_t i = r0 + threadIdx.x; i < r1; i += kCiThreads) {
+            cplx u[kCiGramTile], w[kCiGramTile];
+#pragma unroll
+            for (int a = 0; a < kCiGramTile; ++a) u[a] = (a < np) ? ci_ld(ucol + i + (int64_t)a * ldu) : cplx{0.0, 0.0};
+#pragma unroll
+            for (int b = 0; b < kCiGramTile; ++b) w[b] = (b < nq) ? ci_ld(wcol + i + (int64_t)b * ldw) : cplx{0.0, 0.0};
+#pragma unroll
+            for (int a = 0; a < kCiGramTile; ++a)
+#pragma unroll
+                for (int b = 0; b < kCiGramTile; ++b)
+                    if (a < np && b < nq) fma_conj_acc(acc[a][b], u[a], w[b]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < kCiGramTile; ++a)
+#pragma unroll
+        for (int b = 0; b < kCiGramTile; ++b) {
+            const cplx s = ci_wave_sum(acc[a][b]);
+            if (lane == 0) ci_st(&wsum[wave][a * kCiGramTile + b], s);
+        }
+    __syncthreads();
+    if (threadIdx.x < kCiGramTile * kCiGramTile) {
+        const int a = threadIdx.x / kCiGramTile, b = threadIdx.x % kCiGramTile;
+        if (a < np && b < nq) {
+            const int e = threadIdx.x;
+            const cplx s = s_add(s_add(s_add(wsum[0][e], wsum[1][e]), wsum[2][e]), wsum[3][e]);
+            ci_st(part + ((int64_t)chunk * q + (j0 + b)) * p + (i0 + a), s);
+        }
+    }
+}
+
+// G[e] = the chunks' partial sums of entry e, added in chunk order (a thread per entry: neighbouring threads read neighbouring
+// entries of a chunk).  self: G = U^H U, whose diagonal is real -- the imaginary part the two roundings of conj(u) u leave is dropped.
+__global__ __launch_bounds__(kCiThreads) void ci_gram_finish_kernel(int p, int q, int nchunks, const cplx* __restrict__ part, int self, cplx* __restrict__ G) {
+    const int e = blockIdx.x * kCiThreads + threadIdx.x;
+    if (e >= p * q) return;
+    cplx s = ci_ld(part + e);
+    for (int c = 1; c < nchunks; ++c) s = s_add(s, ci_ld(part + (int64_t)c * p * q + e));
+    if (self && e % p == e / p) s.im = 0.0;
+    ci_st(G + e, s);
+}
+
+// Q = alpha X + beta Q on a block (beta = 0: Q is not read), one pass: the quadrature accumulation Q (+)= -w_k X_k, and the two
+// updates of a refinement step (R = B - R, X += D).  Column blockIdx.y, rows strided over the grid.
+__global__ __launch_bounds__(kCiThreads) void ci_accumulate_kernel(int64_t n, cplx alpha, const cplx* __restrict__ X, int64_t ldx, double beta, cplx* Q,
+                                                                   int64_t ldq) {
+    const cplx* x = X + (int64_t)blockIdx.y * ldx;
+    cplx* q = Q + (int64_t)blockIdx.y * ldq;
+    const int64_t stride = (int64_t)gridDim.x * kCiThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kCiThreads + threadIdx.x; i < n; i += stride) {
+        cplx v = s_mul(alpha, ci_ld(x + i));
+        if (beta != 0.0) {
+            const cplx o = ci_ld(q + i);
+            v.re = fma(beta, o.re, v.re);
+            v.im = fma(beta, o.im, v.im);
+        }
+        ci_st(q + i, v);
+    }
+}
+
+__device__ __forceinline__ double ci_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// Three sums per column j over the rows of one chunk: |P_j - lam_j Q_j|^2, |P_j|^2, |T_j|^2 (lam == null: 1) into
+// part[(chunk cols + j) 3 + 0..2].  The residuals of all Ritz pairs (P = A U S, Q = T = M U S, lam the Ritz values) and the check of
+// a block solve (P = B, Q = C_k X, T = X) are this kernel.
+__global__ __launch_bounds__(kCiThreads) void ci_residual_kernel(int64_t n, int64_t rows_per_block, const cplx* __restrict__ P, int64_t ldp,
+                                                                 const cplx* __restrict__ Qb, int64_t ldq, const cplx* __restrict__ T, int64_t ldt,
+                                                                 const cplx* __restrict__ lam, double* __restrict__ part) {
+    __shared__ double ws[4][3];
+    const int chunk = blockIdx.x, j = blockIdx.y;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t r0 = (int64_t)chunk * rows_per_block;
+    const int64_t r1 = (r0 + rows_per_block < n) ? r0 + rows_per_block : n;
+    const cplx l = lam ? ci_ld(lam + j) : cplx{1.0, 0.0};
+    const cplx ml = cplx{-l.re, -l.im};
+    const cplx *p = P + (int64_t)j * ldp, *q = Qb + (int64_t)j * ldq, *t = T + (int64_t)j * ldt;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = r0 + threadIdx.x; i < r1; i += kCiThreads) {
+        const cplx pv = ci_ld(p + i), qv = ci_ld(q + i), tv = ci_ld(t + i);
+        cplx d = pv;
+        fma_acc(d, ml, qv);
+        s[0] = fma(d.im, d.im, fma(d.re, d.re, s[0]));
+        s[1] = fma(pv.im, pv.im, fma(pv.re, pv.re, s[1]));
+        s[2] = fma(tv.im, tv.im, fma(tv.re, tv.re, s[2]));
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double v = ci_wave_sum(s[k]);
+        if (lane == 0) ws[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) part[((int64_t)chunk * gridDim.y + j) * 3 + threadIdx.x] = ((ws[0][threadIdx.x] + ws[1][threadIdx.x]) + ws[2][threadIdx.x]) + ws[3][threadIdx.x];
+}
+
+// out[e] = the chunks' partial sums of entry e < entries, added in chunk order
+__global__ __launch_bounds__(kCiThreads) void ci_residual_finish_kernel(int entries, int nchunks, const double* __restrict__ part, double* __restrict__ out) {
+    const int e = blockIdx.x * kCiThreads + threadIdx.x;
+    if (e >= entries) return;
+    double s = part[e];
+    for (int c = 1; c < nchunks; ++c) s += part[(int64_t)c * entries + e];
+    out[e] = s;
+}
+
+// row chunks of the two-stage sums: whole multiples of 256 rows, at least 1024 rows, at most kCiGramMaxChunks of them
+int64_t ci_chunk_rows(int64_t n) {
+    const int64_t rows = ((n + kCiGramMaxChunks - 1) / kCiGramMaxChunks + kCiThreads - 1) / kCiThreads * kCiThreads;
+    return std::max<int64_t>(rows, 4 * kCiThreads);
+}
+
+int ci_check_launch(lsa_ctx* ctx, const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lsa_set_error(ctx, LSA_ERR_HIP, "%s: kernel launch failed: %s", what, hipGetErrorString(e));
+    return LSA_OK;
+}
+
+// what a column-major block of `cols` columns of `rows` rows needs of its vector
+bool ci_block_fits(const lsa_vec* v, int64_t rows, int32_t cols, int64_t ld) { return ld >= rows && v->n >= ld * (int64_t)(cols - 1) + rows; }
+
+}  // namespace
+
+int k_spmm(lsa_ctx* ctx, const lsa_mat* A, int32_t ncols, const void* X, int64_t ldx, void* Y, int64_t ldy) {
+    if (A->n < 1 || ncols < 1) return LSA_OK;
+    const int per_block = kCiThreads / kCiRowLanes;
+    const int blocks = (A->n + per_block - 1) / per_block;
+    for (int32_t c0 = 0; c0 < ncols; c0 += kCiColTile) {
+        const int nc = std::min<int32_t>(kCiColTile, ncols - c0);
+        const cplx* x = (const cplx*)X + (int64_t)c0 * ldx;
+        cplx* y = (cplx*)Y + (int64_t)c0 * ldy;
+        if (A->dtype == LSA_C128)
+            hipLaunchKernelGGL(ci_spmm_kernel<cplx>, dim3(blocks), dim3(kCiThreads), 0, ctx->stream, A->n, A->rp, A->ci, (const cplx*)A->val, nc, x, ldx, y, ldy);
+        else
+            hipLaunchKernelGGL(ci_spmm_kernel<double>, dim3(blocks), dim3(kCiThreads), 0, ctx->stream, A->n, A->rp, A->ci, (const double*)A->val, nc, x, ldx, y, ldy);
+    }
+    return ci_check_launch(ctx, "k_spmm");
+}
+
+int k_block_gram(lsa_ctx* ctx, int64_t n, int32_t p, const void* U, int64_t ldu, int32_t q, const void* W, int64_t ldw, void* G_host) {
+    const int64_t rows_per_block = ci_chunk_rows(n);
+    const int nchunks = (int)((n + rows_per_block - 1) / rows_per_block);
+    const size_t entries = (size_t)p * (size_t)q;
+    LSA_CHECK(lsa_ensure_scratch(ctx, ((size_t)nchunks + 1) * entries * sizeof(cplx), entries * sizeof(cplx)));
+    cplx* part = (cplx*)ctx->dscratch;
+    cplx* G = part + (size_t)nchunks * entries;
+    const int self = U == W && ldu == ldw && p == q;
+    hipLaunchKernelGGL(ci_gram_kernel, dim3(nchunks, (p + kCiGramTile - 1) / kCiGramTile, (q + kCiGramTile - 1) / kCiGramTile), dim3(kCiThreads), 0,
+                       ctx->stream, n, rows_per_block, p, q, (const cplx*)U, ldu, (const cplx*)W, ldw, part);
+    hipLaunchKernelGGL(ci_gram_finish_kernel, dim3((int)((entries + kCiThreads - 1) / kCiThreads)), dim3(kCiThreads), 0, ctx->stream, p, q, nchunks, part,
+                       self, G);
+    LSA_CHECK(ci_check_launch(ctx, "k_block_gram"));
+    LSA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->pinned, G, entries * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(G_host, ctx->pinned, entries * sizeof(cplx));
+    return LSA_OK;
+}
+
+extern "C" {
+
+int lsa_spmm(lsa_ctx* ctx, const lsa_mat* A, int32_t ncols, const lsa_vec* X, int64_t ldx, lsa_vec* Y, int64_t ldy) {
+    if (!ctx || !A || !X || !Y) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm: null argument");
+    if (A->n != A->ncols || A->row0 != 0) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm: the matrix is a row shard (%d x %d): whole square matrices only", A->n, A->ncols);
+    if (ncols < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm: %d columns", ncols);
+    if (X->dtype != LSA_C128 || Y->dtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm: the blocks must be complex128");
+    if (X->d == Y->d) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm: X and Y must not alias");
+    if (!ci_block_fits(X, A->ncols, ncols, ldx) || !ci_block_fits(Y, A->n, ncols, ldy))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm: a block of %d columns of %d rows with ldx = %lld, ldy = %lld does not fit vectors of %lld and %lld entries "
+                                               "(ld >= n, length >= ld (ncols - 1) + n)", ncols, A->n, (long long)ldx, (long long)ldy, (long long)X->n, (long long)Y->n);
+    return k_spmm(ctx, A, ncols, X->d, ldx, Y->d, ldy);
+}
+
+int lsa_block_gram(lsa_ctx* ctx, int64_t n, int32_t p, const lsa_vec* U, int64_t ldu, int32_t q, const lsa_vec* W, int64_t ldw, void* G) {
+    if (!ctx || !U || !W || !G) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_block_gram: null argument");
+    if (n < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_block_gram: %lld rows", (long long)n);
+    if (p < 1 || p > kCiMaxCols || q < 1 || q > kCiMaxCols) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_block_gram: %d x %d: between 1 and %d columns each", p, q, kCiMaxCols);
+    if (U->dtype != LSA_C128 || W->dtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_block_gram: the blocks must be complex128");
+    if (!ci_block_fits(U, n, p, ldu) || !ci_block_fits(W, n, q, ldw))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_block_gram: blocks of %d and %d columns of %lld rows with ldu = %lld, ldw = %lld do not fit vectors of %lld and %lld "
+                                               "entries (ld >= n, length >= ld (cols - 1) + n)", p, q, (long long)n, (long long)ldu, (long long)ldw, (long long)U->n,
+                             (long long)W->n);
+    return k_block_gram(ctx, n, p, U->d, ldu, q, W->d, ldw, G);
+}
+
+}  // extern "C"
+
+// ---- the contour iteration ------------------------------------------------------------------------------------------------------
+
+typedef std::complex<double> ci_z;
+
+struct lsa_contour {
+    lsa_ctx* ctx = nullptr;
+    const lsa_mat *A = nullptr, *M = nullptr;
+    int64_t n = 0;
+    int32_t N = 0, L = 0;  // nodes, columns of the subspace
+    bool keep = false;     // N factor sets alive, or one that is refactorised node by node
+    double ksp_rtol = 0.0;
+    double centre[2] = {0.0, 0.0}, radii[2] = {0.0, 0.0};
+    std::vector<ci_z> z, w;         // nodes and weights
+    std::vector<lsa_mat*> C;        // C_k = A - z_k M (values only: A's index arrays)
+    std::vector<double> normF;      // ||C_k||_F
+    std::vector<lsa_ndlu*> F;       // keep: N factor sets, else one
+    int32_t cur = -1;               // the node whose values F[0] holds (refactorised sets)
+    std::vector<char> refine;       // per node: its block solves carry the refinement step
+    // n x L blocks: the basis, M Y, a node's solutions, the quadrature sum, and two work blocks (C_k X; A U and M U)
+    cplx *Y = nullptr, *B = nullptr, *X = nullptr, *Q = nullptr, *W1 = nullptr, *W2 = nullptr;
+    cplx *qdev = nullptr, *lamdev = nullptr;  // L x L coefficients of k_basis_gemm, L Ritz values
+    double *sums = nullptr, *imag2 = nullptr;  // 3 L column sums; what k_columns_canonical reports (not read)
+    int32_t* row_perm = nullptr;
+    lsa_stats st{};
+    int64_t bytes = 0;
+    double sec_factor = 0.0, sec_solve = 0.0, sec_product = 0.0, sec_gram = 0.0, sec_dense = 0.0;
+};
+
+namespace {
+
+void ct_free(lsa_contour* h) {
+    for (lsa_ndlu* f : h->F)
+        if (f) lsa_ndlu_destroy(f);
+    for (lsa_mat* c : h->C)
+        if (c) lsa_mat_destroy(c);
+    for (void* p : {(void*)h->Y, (void*)h->B, (void*)h->X, (void*)h->Q, (void*)h->W1, (void*)h->W2, (void*)h->qdev, (void*)h->lamdev, (void*)h->sums,
+                    (void*)h->imag2, (void*)h->row_perm})
+        if (p) (void)hipFree(p);
+    delete h;
+}
+
+int ct_sync(lsa_ctx* ctx) {
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return LSA_OK;
+}
+
+int ct_accumulate(lsa_ctx* ctx, int64_t n, int32_t cols, ci_z alpha, const cplx* X, double beta, cplx* Q) {
+    const int blocks = (int)std::max<int64_t>(std::min<int64_t>((n + kCiThreads - 1) / kCiThreads, (int64_t)ctx->num_cu * 2), 1);
+    hipLaunchKernelGGL(ci_accumulate_kernel, dim3(blocks, cols), dim3(kCiThreads), 0, ctx->stream, n, cplx{alpha.real(), alpha.imag()}, X, n, beta, Q, n);
+    return ci_check_launch(ctx, "ci_accumulate_kernel");
+}
+
+// out[3 j + 0..2] = |P_j - lam_j Q_j|^2, |P_j|^2, |T_j|^2 for j < cols, on the host (one synchronisation)
+int ct_column_sums(lsa_ctx* ctx, lsa_contour* h, int32_t cols, const cplx* P, const cplx* Qb, const cplx* T, const cplx* lam, double* out) {
+    const int64_t n = h->n, rows_per_block = ci_chunk_rows(n);
+    const int nchunks = (int)((n + rows_per_block - 1) / rows_per_block);
+    const int entries = 3 * cols;
+    LSA_CHECK(lsa_ensure_scratch(ctx, (size_t)nchunks * entries * sizeof(double), (size_t)entries * sizeof(double)));
+    double* part = (double*)ctx->dscratch;
+    hipLaunchKernelGGL(ci_residual_kernel, dim3(nchunks, cols), dim3(kCiThreads), 0, ctx->stream, n, rows_per_block, P, n, Qb, n, T, n, lam, part);
+    hipLaunchKernelGGL(ci_residual_finish_kernel, dim3((entries + kCiThreads - 1) / kCiThreads), dim3(kCiThreads), 0, ctx->stream, entries, nchunks, part,
+                       h->sums);
+    LSA_CHECK(ci_check_launch(ctx, "ci_residual_kernel"));
+    LSA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->pinned, h->sums, (size_t)entries * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    LSA_CHECK(ct_sync(ctx));
+    memcpy(out, ctx->pinned, (size_t)entries * sizeof(double));
+    return LSA_OK;
+}
+
+// Out[:, 0:k] = V[:, 0:m] T for a host matrix T (m x k, dense); the stream is drained first: the pinned staging area is the context's
+int ct_times_host(lsa_ctx* ctx, lsa_contour* h, int m, int k, const cplx* V, const ci_z* T, cplx* Out) {
+    LSA_CHECK(ct_sync(ctx));
+    return basis_times_host_matrix(ctx, LSA_C128, h->n, m, k, V, T, m, h->qdev, Out, 0);
+}
+
+// the factors of node k: its own set, or the one set refactorised for it
+int ct_factors(lsa_ctx* ctx, lsa_contour* h, int32_t k, lsa_ndlu** f) {
+    if (h->keep) {
+        *f = h->F[(size_t)k];
+        return LSA_OK;
+    }
+    if (h->cur != k) {
+        const double t0 = now_s();
+        h->cur = -1;
+        int rc = lsa_ndlu_refactor(ctx, h->F[0], h->C[(size_t)k]);
+        if (rc == LSA_OK) rc = ct_sync(ctx);
+        h->sec_factor += now_s() - t0;
+        if (rc != LSA_OK) return lsa_set_error(ctx, rc, "lsa_contour: node %d (z = %.6g%+.6gi): %s", k, h->z[(size_t)k].real(), h->z[(size_t)k].imag(), std::string(ctx->err).c_str());
+        h->cur = k;
+    }
+    *f = h->F[0];
+    return LSA_OK;
+}
+
+// X = C_k^-1 B for cols columns, every column judged by the rule of lsa_lanczos_extend: within ksp_rtol, else one refinement step (and
+// every later block solve of this node carries it), else a backward error within 1e-12 ||C_k||_F ||x||, else LSA_ERR_DIVERGED
+int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, double* worst) {
+    const int64_t n = h->n;
+    lsa_ndlu* f = nullptr;
+    LSA_CHECK(ct_factors(ctx, h, k, &f));
+    const double t0 = now_s();
+    std::vector<double> s((size_t)3 * cols);
+    bool refined = false;
+    int rc = ndlu_solve_multi_dev(ctx, f, LSA_C128, cols, h->B, n, h->X, n);
+    while (rc == LSA_OK) {
+        if (h->refine[(size_t)k] && !refined) {
+            // R = B - C X;  D = C^-1 R;  X += D
+            rc = k_spmm(ctx, h->C[(size_t)k], cols, h->X, n, h->W1, n);
+            if (rc == LSA_OK) rc = ct_accumulate(ctx, n, cols, ci_z(1.0, 0.0), h->B, -1.0, h->W1);
+            if (rc == LSA_OK) rc = ndlu_solve_multi_dev(ctx, f, LSA_C128, cols, h->W1, n, h->W1, n);
+            if (rc == LSA_OK) rc = ct_accumulate(ctx, n, cols, ci_z(1.0, 0.0), h->W1, 1.0, h->X);
+            if (rc != LSA_OK) break;
+            refined = true;
+        }
+        rc = k_spmm(ctx, h->C[(size_t)k], cols, h->X, n, h->W1, n);
+        if (rc == LSA_OK) rc = ct_column_sums(ctx, h, cols, h->B, h->W1, h->X, nullptr, s.data());
+        if (rc != LSA_OK) break;
+        bool again = false;
+        for (int32_t j = 0; j < cols && rc == LSA_OK; ++j) {
+            const double res = std::sqrt(s[3 * (size_t)j]), bnorm = std::sqrt(s[3 * (size_t)j + 1]), xnorm = std::sqrt(s[3 * (size_t)j + 2]);
+            if (res <= h->ksp_rtol * bnorm) continue;
+            if (!refined && std::isfinite(res)) {
+                again = true;
+                break;
+            }
+            if (!(refined && h->normF[(size_t)k] > 0.0 && res <= 1e-12 * h->normF[(size_t)k] * xnorm))
+                rc = refined ? lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_contour_solve: the solve of column %d at node %d left a relative residual of %.3e "
+                                                                    "after its refinement step (ksp_rtol %.1e) and a backward error above 1e-12 ||C||_F", j, k,
+                                             bnorm > 0.0 ? res / bnorm : res, h->ksp_rtol)
+                             : lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_contour_solve: the solve of column %d at node %d left a residual that is not finite "
+                                                                    "(%.3e, ||b|| = %.3e); no refinement step was taken", j, k, res, bnorm);
+        }
+        if (rc != LSA_OK) break;
+        if (again) {
+            h->refine[(size_t)k] = 1;
+            continue;
+        }
+        for (int32_t j = 0; j < cols; ++j) {
+            const double res = std::sqrt(s[3 * (size_t)j]), bnorm = std::sqrt(s[3 * (size_t)j + 1]);
+            if (res > h->ksp_rtol * bnorm) ++h->st.backward_accepted;
+            stats_book_direct_solve(&h->st, 1, refined, res, bnorm);
+            if (bnorm > 0.0) *worst = std::max(*worst, res / bnorm);
+        }
+        break;
+    }
+    h->sec_solve += now_s() - t0;
+    return rc;
+}
+
+// Hermitian eigen-decomposition of the m x m host matrix G through the complex Schur form (diagonal for a Hermitian matrix):
+// eigenvalues descending in val, their eigenvectors in the columns of vec
+int ct_herm_eig(lsa_ctx* ctx, int32_t m, std::vector<ci_z>& G, std::vector<double>& val, std::vector<ci_z>& vec) {
+    for (const ci_z& g : G)
+        if (!std::isfinite(g.real()) || !std::isfinite(g.imag())) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "lsa_contour_solve: a Gram matrix is not finite");
+    for (int32_t j = 0; j < m; ++j)  // exactly Hermitian: the mean of the two triangles
+        for (int32_t i = 0; i <= j; ++i) {
+            const ci_z a = 0.5 * (G[(size_t)j * m + i] + std::conj(G[(size_t)i * m + j]));
+            G[(size_t)j * m + i] = i == j ? ci_z(a.real(), 0.0) : a;
+            G[(size_t)i * m + j] = i == j ? ci_z(a.real(), 0.0) : std::conj(a);
+        }
+    std::vector<ci_z> Qs((size_t)m * m);
+    if (lsa_dense_schur(m, G.data(), m, Qs.data(), m) != LSA_OK) return lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_contour_solve: the QR algorithm stalled on a Gram matrix");
+    std::vector<int32_t> order((size_t)m);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return G[(size_t)a * m + a].real() > G[(size_t)b * m + b].real(); });
+    val.resize((size_t)m);
+    vec.resize((size_t)m * m);
+    for (int32_t c = 0; c < m; ++c) {
+        val[(size_t)c] = G[(size_t)order[(size_t)c] * m + order[(size_t)c]].real();
+        std::copy(Qs.begin() + (size_t)order[(size_t)c] * m, Qs.begin() + (size_t)(order[(size_t)c] + 1) * m, vec.begin() + (size_t)c * m);
+    }
+    return LSA_OK;
+}
+
+// out = in W Lambda^-1/2 over the eigenpairs of in^H in with eigenvalue >= 1e-14 max (the Gram matrix squares the singular values:
+// nothing below a relative 1e-7 is trusted); *rank: the columns kept
+int ct_orth_pass(lsa_ctx* ctx, lsa_contour* h, const cplx* in, int32_t cols, cplx* out, int32_t* rank) {
+    std::vector<ci_z> G((size_t)cols * cols), vec;
+    std::vector<double> val;
+    double t0 = now_s();
+    LSA_CHECK(k_block_gram(ctx, h->n, cols, in, h->n, cols, in, h->n, G.data()));
+    h->sec_gram += now_s() - t0;
+    t0 = now_s();
+    LSA_CHECK(ct_herm_eig(ctx, cols, G, val, vec));
+    if (!(val[0] > 0.0)) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "lsa_contour_solve: the block has no direction left (largest Gram eigenvalue %.3e)", val[0]);
+    int32_t r = 0;
+    while (r < cols && val[(size_t)r] >= 1e-14 * val[0]) ++r;
+    std::vector<ci_z> T((size_t)cols * r);
+    for (int32_t c = 0; c < r; ++c) {
+        const double sc = 1.0 / std::sqrt(val[(size_t)c]);
+        for (int32_t i = 0; i < cols; ++i) T[(size_t)c * cols + i] = sc * vec[(size_t)c * cols + i];
+    }
+    h->sec_dense += now_s() - t0;
+    t0 = now_s();
+    LSA_CHECK(ct_times_host(ctx, h, cols, r, in, T.data(), out));
+    h->sec_gram += now_s() - t0;
+    *rank = r;
+    return LSA_OK;
+}
+
+// the normalised radius of lambda: < 1 inside the ellipse
+double ct_radius2(const lsa_contour* h, ci_z lam) {
+    const double a = (lam.real() - h->centre[0]) / h->radii[0], b = (lam.imag() - h->centre[1]) / h->radii[1];
+    return a * a + b * b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsa_contour_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double centre[2], const double radii[2], int32_t subspace,
+                       int keep_factors, double ksp_rtol, lsa_contour** out) {
+    if (!ctx || !A || !out || !centre || !radii) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: null argument");
+    *out = nullptr;
+    if (ctx->nranks != 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: the context is one of %d ranks: one rank only", ctx->nranks);
+    if (A->n != A->ncols || A->row0 != 0) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: A is a row shard: whole square matrices only");
+    if (!M) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: M is missing: the contour integral is that of the pencil (A, M)");
+    if (M->dtype != LSA_F64) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: M is complex: a real M only");
+    if (M->n != A->n || M->ncols != A->ncols || M->nnz != A->nnz) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: A and M do not share one pattern");
+    if (nodes < 4 || nodes % 2 != 0) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: nodes = %d: an even number of at least 4", nodes);
+    if (subspace < 2 || subspace > kCiMaxCols || (int64_t)subspace > A->n)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: subspace = %d: between 2 and min(%d, n = %d)", subspace, kCiMaxCols, A->n);
+    if (!(radii[0] > 0.0) || !(radii[1] > 0.0) || !std::isfinite(radii[0]) || !std::isfinite(radii[1]) || !std::isfinite(centre[0]) || !std::isfinite(centre[1]))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: radii (%.3e, %.3e): finite and positive, with a finite centre", radii[0], radii[1]);
+    if (!(ksp_rtol > 0.0)) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: ksp_rtol = %.3e must be positive", ksp_rtol);
+    lsa_contour* h = new lsa_contour();
+    h->ctx = ctx;
+    h->A = A;
+    h->M = M;
+    h->n = A->n;
+    h->N = nodes;
+    h->L = subspace;
+    h->keep = keep_factors != 0;
+    h->ksp_rtol = ksp_rtol;
+    for (int q = 0; q < 2; ++q) {
+        h->centre[q] = centre[q];
+        h->radii[q] = radii[q];
+    }
+    h->refine.assign((size_t)nodes, 0);
+    h->C.assign((size_t)nodes, nullptr);
+    h->normF.assign((size_t)nodes, 0.0);
+    h->F.assign(h->keep ? (size_t)nodes : 1, nullptr);
+    const double pi = 3.14159265358979323846;
+    for (int32_t k = 0; k < nodes; ++k) {
+        const double th = 2.0 * pi * (k + 0.5) / nodes;
+        h->z.push_back(ci_z(centre[0] + radii[0] * std::cos(th), centre[1] + radii[1] * std::sin(th)));
+        h->w.push_back(ci_z(radii[1] * std::cos(th) / nodes, radii[0] * std::sin(th) / nodes));
+    }
+    const size_t blk = (size_t)h->n * sizeof(cplx) * (size_t)subspace, LL = (size_t)subspace * subspace * sizeof(cplx);
+    bool ok = true;
+    for (cplx** p : {&h->Y, &h->B, &h->X, &h->Q, &h->W1, &h->W2}) ok = ok && hipMalloc((void**)p, blk) == hipSuccess;
+    ok = ok && hipMalloc((void**)&h->qdev, LL) == hipSuccess && hipMalloc((void**)&h->lamdev, (size_t)subspace * sizeof(cplx)) == hipSuccess &&
+         hipMalloc((void**)&h->sums, (size_t)3 * subspace * sizeof(double)) == hipSuccess && hipMalloc((void**)&h->imag2, (size_t)subspace * sizeof(double)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        ct_free(h);
+        return lsa_set_error(ctx, LSA_ERR_OOM, "lsa_contour_create: out of device memory (n=%d, subspace=%d)", A->n, subspace);
+    }
+    h->bytes = (int64_t)(6 * blk + LL);
+    // C_k = A - z_k M on A's index arrays, and ||C_k||_F for the backward-error judgement
+    const double t0 = now_s();
+    int rc = LSA_OK;
+    for (int32_t k = 0; k < nodes && rc == LSA_OK; ++k) {
+        const double one[2] = {1.0, 0.0}, mz[2] = {-h->z[(size_t)k].real(), -h->z[(size_t)k].imag()};
+        rc = lsa_csr_axpby(ctx, A, M, one, mz, LSA_C128, &h->C[(size_t)k]);
+        if (rc == LSA_OK) rc = k_nrm2(ctx, LSA_C128, A->nnz, h->C[(size_t)k]->val, h->sums);
+        double v2 = 0.0;
+        if (rc == LSA_OK && (hipMemcpyAsync(&v2, h->sums, sizeof v2, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess))
+            rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_contour_create: reading ||C||_F failed");
+        if (rc == LSA_OK && std::isfinite(v2)) h->normF[(size_t)k] = std::sqrt(v2);
+        h->bytes += (int64_t)A->nnz * (int64_t)sizeof(cplx);
+    }
+    // The factor sets.  The first takes the analysis the context holds prepared (lsa_ndlu_prepare / _prepare_tree), or analyses; every
+    // further one redoes the pattern-only phase from the first one's forest: one ordering, one analysis, the bits of a refactorisation.
+    for (size_t k = 0; k < h->F.size() && rc == LSA_OK; ++k) {
+        if (k == 0) {
+            rc = lsa_ndlu_create(ctx, h->C[0], 0, &h->F[0]);
+        } else {
+            const NdSymbolic& S = h->F[0]->S;
+            if (S.tree_hash != 0) {
+                std::vector<int32_t> first((size_t)S.nt), size((size_t)S.nt);
+                for (int32_t t = 0; t < S.nt; ++t) {
+                    first[(size_t)t] = S.perm[(size_t)S.node_start[(size_t)t]];
+                    size[(size_t)t] = S.node_start[(size_t)t + 1] - S.node_start[(size_t)t];
+                }
+                lsa_ndlu_drop_cache(ctx);
+                rc = lsa_ndlu_create_tree(ctx, h->C[k], S.nt, first.data(), size.data(), S.parent.data(), nullptr, &h->F[k]);
+            } else {
+                lsa_ndlu_drop_cache(ctx);
+                rc = lsa_ndlu_create(ctx, h->C[k], S.leaf_size, &h->F[k]);
+            }
+        }
+        if (rc != LSA_OK) rc = lsa_set_error(ctx, rc, "lsa_contour_create: node %d (z = %.6g%+.6gi): %s", (int)k, h->z[k].real(), h->z[k].imag(), std::string(ctx->err).c_str());
+    }
+    if (rc == LSA_OK) rc = ct_sync(ctx);
+    if (rc != LSA_OK) {
+        const std::string msg = ctx->err;
+        ct_free(h);
+        return lsa_set_error(ctx, rc, "%s", msg.c_str());
+    }
+    h->cur = 0;
+    h->st.analysis_reused = h->F[0]->seconds_analyse == 0.0 ? 1 : 0;
+    h->sec_factor = now_s() - t0;
+    h->st.seconds_factor = h->sec_factor;
+    *out = h;
+    return LSA_OK;
+}
+
+void lsa_contour_destroy(lsa_contour* h) {
+    if (!h) return;
+    if (h->ctx && h->ctx->stream) (void)hipStreamSynchronize(h->ctx->stream);
+    ct_free(h);
+}
+
+int lsa_contour_set_row_permutation(lsa_ctx* ctx, lsa_contour* h, const int32_t* perm) {
+    if (!ctx || !h) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_set_row_permutation: null argument");
+    return basis_upload_row_permutation(ctx, "lsa_contour_set_row_permutation", h->n, perm, &h->row_perm);
+}
+
+int lsa_contour_info(const lsa_contour* h, lsa_contour_stats* out) {
+    if (!h || !out) return LSA_ERR_ARG;
+    out->kept = h->keep ? 1 : 0;
+    out->nodes = h->N;
+    out->bytes = h->bytes;
+    out->seconds_factor = h->sec_factor;
+    out->seconds_solve = h->sec_solve;
+    out->seconds_product = h->sec_product;
+    out->seconds_gram = h->sec_gram;
+    out->seconds_dense = h->sec_dense;
+    out->solver = h->st;
+    return LSA_OK;
+}
+
+int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, const void* Y0_host, int32_t max_out, void* lam_out, void* X_out,
+                      double* res_out, lsa_contour_result* result) {
+    if (!ctx || !h || !Y0_host || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_solve: null argument");
+    if (!(tol > 0.0) || max_it < 1 || max_out < 0 || (max_out > 0 && (!lam_out || !res_out)))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_solve: bad argument (tol %.3e, max_it %d, max_out %d)", tol, max_it, max_out);
+    const int64_t n = h->n;
+    const int32_t L = h->L;
+    *result = lsa_contour_result{};
+    const int64_t solves0 = h->st.op_applies, refined0 = h->st.refined_solves, backward0 = h->st.backward_accepted;
+    LSA_HIP_CHECK(ctx, hipMemcpyAsync(h->Y, Y0_host, (size_t)n * L * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
+    LSA_CHECK(ct_sync(ctx));
+    int32_t cols = L, r = 0, inside = 0, conv = 0;
+    bool stopped = false;
+    double worst = 0.0;
+    std::vector<ci_z> lam, S;
+    std::vector<double> res;
+    std::vector<int32_t> in_idx;
+    int32_t it = 0;
+    for (; it < max_it; ++it) {
+        // B = M Y, then the quadrature over the nodes: Q = -sum_k w_k C_k^-1 B
+        double t0 = now_s();
+        LSA_CHECK(k_spmm(ctx, h->M, cols, h->Y, n, h->B, n));
+        h->st.spmv_calls += cols;
+        h->sec_product += now_s() - t0;
+        for (int32_t k = 0; k < h->N; ++k) {
+            LSA_CHECK(ct_block_solve(ctx, h, k, cols, &worst));
+            LSA_CHECK(ct_accumulate(ctx, n, cols, -h->w[(size_t)k], h->X, k == 0 ? 0.0 : 1.0, h->Q));
+        }
+        if (it == 0) {  // the stochastic estimate of the count inside: Re sum_j y_j^H q_j / L
+            std::vector<ci_z> G((size_t)cols * cols);
+            t0 = now_s();
+            LSA_CHECK(k_block_gram(ctx, n, cols, h->Y, n, cols, h->Q, n, G.data()));
+            h->sec_gram += now_s() - t0;
+            double tr = 0.0;
+            for (int32_t j = 0; j < cols; ++j) tr += G[(size_t)j * cols + j].real();
+            result->estimate = tr / cols;
+        }
+        // U = orth(Q), twice through the Gram matrix: Q -> X -> Y
+        int32_t r1 = 0;
+        LSA_CHECK(ct_orth_pass(ctx, h, h->Q, cols, h->X, &r1));
+        LSA_CHECK(ct_orth_pass(ctx, h, h->X, r1, h->Y, &r));
+        // A U, M U and the projected pencil
+        t0 = now_s();
+        LSA_CHECK(k_spmm(ctx, h->A, r, h->Y, n, h->W1, n));
+        LSA_CHECK(k_spmm(ctx, h->M, r, h->Y, n, h->W2, n));
+        h->st.spmv_calls += 2 * r;
+        LSA_CHECK(ct_sync(ctx));
+        h->sec_product += now_s() - t0;
+        std::vector<ci_z> Ah((size_t)r * r), Mh((size_t)r * r);
+        t0 = now_s();
+        LSA_CHECK(k_block_gram(ctx, n, r, h->Y, n, r, h->W1, n, Ah.data()));
+        LSA_CHECK(k_block_gram(ctx, n, r, h->Y, n, r, h->W2, n, Mh.data()));
+        h->sec_gram += now_s() - t0;
+        t0 = now_s();
+        if (!dense_lu_solve(r, Mh.data(), Ah.data())) return lsa_set_error(ctx, LSA_ERR_ZERO_PIVOT, "lsa_contour_solve: U^H M U is singular at iteration %d (rank %d)", it, r);
+        std::vector<ci_z> Qs((size_t)r * r), St((size_t)r * r);
+        if (lsa_dense_schur(r, Ah.data(), r, Qs.data(), r) != LSA_OK) return lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_contour_solve: the QR algorithm stalled on the projected problem");
+        LSA_CHECK(lsa_dense_tri_eigenvectors(r, Ah.data(), r, St.data(), r));
+        lam.assign((size_t)r, ci_z());
+        S.assign((size_t)r * r, ci_z());
+        for (int32_t j = 0; j < r; ++j) {
+            lam[(size_t)j] = Ah[(size_t)j * r + j];
+            for (int32_t k = 0; k <= j; ++k)  // (the eigenvectors of a triangular matrix are triangular)
+                for (int32_t i = 0; i < r; ++i) S[(size_t)j * r + i] += Qs[(size_t)k * r + i] * St[(size_t)j * r + k];
+        }
+        for (const ci_z& l : lam)
+            if (!std::isfinite(l.real()) || !std::isfinite(l.imag())) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "lsa_contour_solve: a Ritz value is not finite at iteration %d", it);
+        h->sec_dense += now_s() - t0;
+        // residuals ||A x - lam M x|| / (||A x|| + |lam| ||M x||) of all Ritz pairs from A U S and M U S
+        t0 = now_s();
+        LSA_CHECK(ct_times_host(ctx, h, r, r, h->W1, S.data(), h->X));
+        LSA_CHECK(ct_times_host(ctx, h, r, r, h->W2, S.data(), h->B));
+        LSA_HIP_CHECK(ctx, hipMemcpyAsync(h->lamdev, lam.data(), (size_t)r * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
+        LSA_CHECK(ct_sync(ctx));
+        std::vector<double> s((size_t)3 * r);
+        LSA_CHECK(ct_column_sums(ctx, h, r, h->X, h->B, h->B, h->lamdev, s.data()));
+        h->sec_product += now_s() - t0;
+        res.assign((size_t)r, 0.0);
+        in_idx.clear();
+        conv = 0;
+        for (int32_t j = 0; j < r; ++j) {
+            res[(size_t)j] = std::sqrt(s[3 * (size_t)j]) / (std::sqrt(s[3 * (size_t)j + 1]) + std::abs(lam[(size_t)j]) * std::sqrt(s[3 * (size_t)j + 2]) + 1e-16);
+            if (ct_radius2(h, lam[(size_t)j]) < 1.0) {
+                in_idx.push_back(j);
+                if (res[(size_t)j] <= tol) ++conv;
+            }
+        }
+        inside = (int32_t)in_idx.size();
+        cols = r;
+        // (an iteration that shows NO Ritz value inside proves little on its own: a large cluster just outside the contour can fill
+        //  the block in the first quadrature; an empty region is declared only when a second iteration shows none either)
+        if (conv == inside && (inside > 0 || it > 0)) {
+            stopped = true;
+            ++it;
+            break;
+        }
+    }
+    result->iterations = it;
+    result->rank = r;
+    result->inside = inside;
+    result->converged_inside = conv;
+    result->complete = stopped && inside < r ? 1 : 0;
+    result->block_solves = h->st.op_applies - solves0;
+    result->refined_solves = h->st.refined_solves - refined0;
+    result->backward_accepted = h->st.backward_accepted - backward0;
+    result->worst_rel_res = worst;
+    // the inside pairs, nearest the centre (in the ellipse's own metric) first
+    std::stable_sort(in_idx.begin(), in_idx.end(), [&](int32_t a, int32_t b) { return ct_radius2(h, lam[(size_t)a]) < ct_radius2(h, lam[(size_t)b]); });
+    const int32_t nout = std::min<int32_t>(inside, max_out);
+    result->nout = nout;
+    for (int32_t c = 0; c < nout; ++c) {
+        ((ci_z*)lam_out)[c] = lam[(size_t)in_idx[(size_t)c]];
+        res_out[c] = res[(size_t)in_idx[(size_t)c]];
+    }
+    if (nout > 0 && X_out) {
+        std::vector<ci_z> Sel((size_t)r * nout);
+        for (int32_t c = 0; c < nout; ++c) std::copy(S.begin() + (size_t)in_idx[(size_t)c] * r, S.begin() + (size_t)(in_idx[(size_t)c] + 1) * r, Sel.begin() + (size_t)c * r);
+        LSA_CHECK(ct_times_host(ctx, h, r, nout, h->Y, Sel.data(), h->Q));
+        LSA_CHECK(k_columns_canonical(ctx, n, nout, h->Q, n, 1, h->imag2));
+        const cplx* src = h->Q;
+        if (h->row_perm) {
+            LSA_CHECK(k_scatter_rows(ctx, LSA_C128, n, nout, h->row_perm, h->Q, h->W1));
+            src = h->W1;
+        }
+        LSA_HIP_CHECK(ctx, hipMemcpyAsync(X_out, src, (size_t)n * nout * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
+        LSA_CHECK(ct_sync(ctx));
+    }
+    h->st.seconds_solve = h->sec_solve;
+    return LSA_OK;
+}
+
+}  // extern "C"

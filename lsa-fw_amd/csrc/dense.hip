@@ -883,6 +883,38 @@ int trl_solve(lsa_ctx* ctx, Basis& b, const lsa_ks_options* o, const typename Ba
 
 }  // namespace
 
+// Z = Mh^-1 Ah (r x r complex, column-major, leading dimension r) by LU with partial pivoting; Mh and Ah are overwritten (Ah by Z).
+// false: Mh is singular.  The reduced problem of the region eigensolver (contour.hip).
+bool dense_lu_solve(int32_t r, void* Mh_, void* Ah_) {
+    typedef std::complex<double> ci_z;
+    ci_z *Mh = (ci_z*)Mh_, *Ah = (ci_z*)Ah_;
+    for (int32_t c = 0; c < r; ++c) {
+        int32_t piv = c;
+        for (int32_t i = c + 1; i < r; ++i)
+            if (std::abs(Mh[(size_t)c * r + i]) > std::abs(Mh[(size_t)c * r + piv])) piv = i;
+        if (!(std::abs(Mh[(size_t)c * r + piv]) > 0.0)) return false;
+        if (piv != c)
+            for (int32_t j = 0; j < r; ++j) {
+                std::swap(Mh[(size_t)j * r + c], Mh[(size_t)j * r + piv]);
+                std::swap(Ah[(size_t)j * r + c], Ah[(size_t)j * r + piv]);
+            }
+        const ci_z d = Mh[(size_t)c * r + c];
+        for (int32_t i = c + 1; i < r; ++i) {
+            const ci_z l = Mh[(size_t)c * r + i] / d;
+            if (l == ci_z(0.0, 0.0)) continue;
+            for (int32_t j = c + 1; j < r; ++j) Mh[(size_t)j * r + i] -= l * Mh[(size_t)j * r + c];
+            for (int32_t j = 0; j < r; ++j) Ah[(size_t)j * r + i] -= l * Ah[(size_t)j * r + c];
+        }
+    }
+    for (int32_t j = 0; j < r; ++j)
+        for (int32_t i = r - 1; i >= 0; --i) {
+            ci_z v = Ah[(size_t)j * r + i];
+            for (int32_t k = i + 1; k < r; ++k) v -= Mh[(size_t)k * r + i] * Ah[(size_t)j * r + k];
+            Ah[(size_t)j * r + i] = v / Mh[(size_t)i * r + i];
+        }
+    return true;
+}
+
 extern "C" {
 
 int lsa_dense_schur(int32_t n, void* A, int32_t lda, void* Q, int32_t ldq) {

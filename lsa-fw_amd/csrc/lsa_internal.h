@@ -233,6 +233,15 @@ constexpr int kKrylovGroupMax = 16;
 int k_spmv(lsa_ctx* ctx, const lsa_mat* A, int xdtype, const void* x, void* y);
 int k_spmv_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, int xdtype, const void* x, void* y);
 
+// Block kernels of the region eigensolver (contour.hip): complex128 column-major blocks, column c at c * ld, ld >= n
+// Y[:, 0:ncols] = A X[:, 0:ncols] for a whole square A (f64 or c128), in passes of 8 columns that read A once each; not k_spmv's bits
+int k_spmm(lsa_ctx* ctx, const lsa_mat* A, int32_t ncols, const void* X, int64_t ldx, void* Y, int64_t ldy);
+// G_host (p x q column-major) = U^H W over n rows, p, q <= 128: fixed-order two-stage sums; synchronises.  U == W (one block): real diagonal
+int k_block_gram(lsa_ctx* ctx, int64_t n, int32_t p, const void* U, int64_t ldu, int32_t q, const void* W, int64_t ldw, void* G_host);
+
+// Z = Mh^-1 Ah for r x r complex host matrices (column-major, ld r) by LU with partial pivoting, both overwritten (dense.hip); false: singular
+bool dense_lu_solve(int32_t r, void* Mh, void* Ah);
+
 // BLAS-1 / tall-skinny kernels (blas.hip); T selected by dtype
 int k_copy(lsa_ctx* ctx, int dtype, int64_t n, const void* x, void* y);
 int k_set_zero(lsa_ctx* ctx, int dtype, int64_t n, void* x);

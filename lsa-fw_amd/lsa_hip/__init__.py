@@ -112,6 +112,36 @@ class lsa_ks_batch_info(ctypes.Structure):
     ]
 
 
+class lsa_contour_result(ctypes.Structure):
+    _fields_ = [
+        ("iterations", ctypes.c_int32),
+        ("rank", ctypes.c_int32),
+        ("inside", ctypes.c_int32),
+        ("converged_inside", ctypes.c_int32),
+        ("complete", ctypes.c_int32),
+        ("nout", ctypes.c_int32),
+        ("estimate", ctypes.c_double),
+        ("block_solves", ctypes.c_int64),
+        ("refined_solves", ctypes.c_int64),
+        ("backward_accepted", ctypes.c_int64),
+        ("worst_rel_res", ctypes.c_double),
+    ]
+
+
+class lsa_contour_stats(ctypes.Structure):
+    _fields_ = [
+        ("kept", ctypes.c_int32),
+        ("nodes", ctypes.c_int32),
+        ("bytes", ctypes.c_int64),
+        ("seconds_factor", ctypes.c_double),
+        ("seconds_solve", ctypes.c_double),
+        ("seconds_product", ctypes.c_double),
+        ("seconds_gram", ctypes.c_double),
+        ("seconds_dense", ctypes.c_double),
+        ("solver", lsa_stats),
+    ]
+
+
 _P = ctypes.c_void_p
 _I32, _I64, _DBL = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -227,6 +257,13 @@ SIGNATURES = {
     "lsa_growth_extend": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_I32)]),
     "lsa_growth_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
     "lsa_growth_solve": (ctypes.c_int, [_P, _P, ctypes.POINTER(lsa_ks_options), _P, _I32, _P, _P, _P, _P, _P, _P, ctypes.POINTER(lsa_ks_result), _P]),
+    "lsa_spmm": (ctypes.c_int, [_P, _P, _I32, _P, _I64, _P, _I64]),
+    "lsa_block_gram": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _P, _I64, _P]),
+    "lsa_contour_create": (ctypes.c_int, [_P, _P, _P, _I32, _DBL * 2, _DBL * 2, _I32, ctypes.c_int, _DBL, _PP]),
+    "lsa_contour_destroy": (None, [_P]),
+    "lsa_contour_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
+    "lsa_contour_solve": (ctypes.c_int, [_P, _P, _DBL, _I32, _P, _I32, _P, _P, _P, ctypes.POINTER(lsa_contour_result)]),
+    "lsa_contour_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_contour_stats)]),
     "lsa_mm_open": (ctypes.c_int, [ctypes.c_char_p, _PP, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int)]),
     "lsa_mm_read_csr": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_mm_error": (ctypes.c_char_p, [_P]),
@@ -510,6 +547,14 @@ class CsrMatrix:
 
     def rmatvec(self, x: DeviceVector, y: DeviceVector, conj: bool = True) -> None:
         self.ctx.check(self.ctx._lib.lsa_spmv_transpose(self.ctx.handle, self.handle, int(conj), x.handle, y.handle))
+
+    def matmat(self, X: DeviceVector, Y: DeviceVector, ncols: int, ldx: int | None = None, ldy: int | None = None) -> None:
+        """``Y[:, c] = self @ X[:, c]`` for ``ncols`` columns (``lsa_spmm``).  ``X`` and ``Y`` are column-major complex128 blocks in
+        one vector each (column ``c`` at ``c * ld``, ``ld`` defaulting to ``n``).  Two calls give the same bytes; a column need not
+        hold the bytes of :meth:`matvec`."""
+        n = self.shape[0]
+        self.ctx.check(self.ctx._lib.lsa_spmm(self.ctx.handle, self.handle, int(ncols), X.handle, int(n if ldx is None else ldx), Y.handle,
+                                              int(n if ldy is None else ldy)))
 
     def matvec_info(self, vector_dtype=np.complex128) -> dict:
         """Kernel ``lsa_spmv`` launches for this matrix / vector type and the bytes it moves per launch."""
@@ -1210,6 +1255,61 @@ class ResolventBasis:
             self.handle = None
 
 
+class ContourSolver:
+    """Contour-integral subspace iteration for the eigenvalues of ``(A, M)`` inside an ellipse (``lsa_contour_*``): ``nodes``
+    factorisations of ``A - z_k M`` on one LU analysis, kept alive (``keep_factors=True``) or refactorised node by node in every
+    iteration; both return the same bytes.  ``A`` and ``M`` share one pattern, ``M`` is real."""
+
+    def __init__(self, ctx: Context, A: CsrMatrix, M: CsrMatrix, nodes: int, centre: complex, rx: float, ry: float, subspace: int, *,
+                 keep_factors: bool = True, ksp_rtol: float = 1e-12):
+        self.ctx, self._keep = ctx, (A, M)  # (the handle borrows both matrices)
+        self.n, self.subspace, self.nodes = A.shape[0], int(subspace), int(nodes)
+        centre = complex(centre)
+        h = ctypes.c_void_p()
+        ctx.check(ctx._lib.lsa_contour_create(ctx.handle, A.handle, None if M is None else M.handle, self.nodes, (_DBL * 2)(centre.real, centre.imag),
+                                              (_DBL * 2)(float(rx), float(ry)), self.subspace, int(bool(keep_factors)), float(ksp_rtol), ctypes.byref(h)))
+        self.handle = h
+
+    def set_row_permutation(self, perm: np.ndarray | None) -> None:
+        """``perm[i]`` = the caller's index of row ``i``: the vectors of :meth:`solve` come back in the caller's numbering."""
+        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        self.ctx.check(self.ctx._lib.lsa_contour_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
+
+    def solve(self, tol: float, max_it: int, Y0: np.ndarray, max_out: int | None = None) -> dict:
+        """The iteration from the start block ``Y0`` (``n x subspace``, the matrices' own row numbering).  Returns the Ritz pairs
+        inside the ellipse (``eigenvalues``, ``eigenvectors``, ``residuals``) and the fields of ``lsa_contour_result``."""
+        Y0 = np.asfortranarray(Y0, dtype=np.complex128)
+        if Y0.shape != (self.n, self.subspace):
+            raise ValueError(f"the start block must have shape ({self.n}, {self.subspace}), got {Y0.shape}")
+        max_out = self.subspace if max_out is None else min(int(max_out), self.subspace)
+        lam = np.zeros(max(max_out, 1), dtype=np.complex128)
+        res = np.zeros(max(max_out, 1), dtype=np.float64)
+        X = np.empty((self.n, max_out), dtype=np.complex128, order="F")
+        out = lsa_contour_result()
+        self.ctx.check(self.ctx._lib.lsa_contour_solve(self.ctx.handle, self.handle, float(tol), int(max_it), _ptr(Y0), max_out, _ptr(lam), _ptr(X),
+                                                       _ptr(res), ctypes.byref(out)))
+        k = out.nout
+        d = {name: getattr(out, name) for name, _ in lsa_contour_result._fields_}
+        d["complete"] = bool(out.complete)
+        d.update(eigenvalues=lam[:k].copy(), eigenvectors=np.asfortranarray(X[:, :k]), residuals=res[:k].copy())
+        return d
+
+    def info(self) -> dict:
+        """``lsa_contour_info``: kept or refactorised factor sets, device bytes of the handle's own buffers, the phase times, and the
+        column solves' counters under ``"solver"``."""
+        st = lsa_contour_stats()
+        self.ctx.check(self.ctx._lib.lsa_contour_info(self.handle, ctypes.byref(st)))
+        d = {name: getattr(st, name) for name, _ in lsa_contour_stats._fields_ if name != "solver"}
+        d["kept"] = bool(st.kept)
+        d["solver"] = {name: getattr(st.solver, name) for name, _ in lsa_stats._fields_}
+        return d
+
+    def __del__(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx._lib.lsa_contour_destroy(self.handle)
+            self.handle = None
+
+
 class GrowthBasis:
     """Real ``M``-orthonormal Lanczos basis in HBM for the transient-growth operator ``W = Phi+ Phi``, ``Phi = (-sigma C^-1 M)^N``,
     ``C = A - sigma M``, ``sigma = 1 / dt`` (``lsa_growth_*``): a march of ``2 N`` solves on one factorisation behind every step.
@@ -1384,3 +1484,13 @@ def eig_biorth(ctx: Context, M: CsrMatrix | None, X: np.ndarray, Z: np.ndarray) 
     norm_z, norm_mx = np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.float64)
     ctx.check(ctx._lib.lsa_eig_biorth(ctx.handle, M.handle if M is not None else None, n, k, _ptr(X), _ptr(Z), _ptr(G), _ptr(norm_z), _ptr(norm_mx)))
     return G, norm_z, norm_mx
+
+
+def block_gram(ctx: Context, n: int, U: DeviceVector, p: int, W: DeviceVector, q: int, ldu: int | None = None, ldw: int | None = None) -> np.ndarray:
+    """``lsa_block_gram``: ``G = U^H W`` (``p x q``, both at most 128) over ``n`` rows of two column-major complex128 blocks (column
+    ``c`` at ``c * ld``, ``ld`` defaulting to ``n``), summed on the device in a fixed order.  ``U is W`` with one ``ld`` and one
+    column count returns an exactly real diagonal."""
+    G = np.zeros((int(p), int(q)), dtype=np.complex128, order="F")
+    ctx.check(ctx._lib.lsa_block_gram(ctx.handle, int(n), int(p), U.handle, int(n if ldu is None else ldu), int(q), W.handle,
+                                      int(n if ldw is None else ldw), _ptr(G)))
+    return G
