@@ -544,6 +544,16 @@ void lsa_growth_destroy(lsa_growth *g);
 int lsa_growth_set_row_permutation(lsa_ctx *ctx, lsa_growth *g, const int32_t *perm);
 /* another horizon on the same handle and factors; what follows gives the bytes a new handle with this nsteps gives */
 int lsa_growth_set_steps(lsa_ctx *ctx, lsa_growth *g, int32_t nsteps);
+/* The time-stepping scheme behind the march.  LSA_GROWTH_EULER (what a new handle has): implicit Euler as above, first order in dt.
+ * LSA_GROWTH_SDIRK2: the L-stable, stiffly accurate two-stage singly diagonally implicit Runge-Kutta method with gamma = 1 - 1/sqrt(2),
+ * second order in dt.  Both of its stages solve with M - gamma dt A, so the library takes sigma from the operator as before and the
+ * time step it stands for is dt = 1 / (gamma sigma): the caller builds the operator at sigma = 1 / (gamma dt).  With S = -sigma C^-1 M one
+ * time step is Phi_1 = S (a S + b I), a = 1 + sqrt(2), b = -sqrt(2), and its M-adjoint the same with C^-T: every time step is two
+ * solves (lsa_growth_extend: 2N forward and 2N transposed per step; lsa_growth_solve's final march: 2N per vector, energy_out at the
+ * second stage of each time step), each of them checked as under Euler.  Like lsa_growth_set_steps it begins anew: what follows
+ * gives the bytes a new handle set to this scheme gives.  LSA_ERR_ARG, naming the scheme, for any other code. */
+enum { LSA_GROWTH_EULER = 0, LSA_GROWTH_SDIRK2 = 1 };
+int lsa_growth_set_scheme(lsa_ctx *ctx, lsa_growth *g, int32_t scheme);
 /* v_0 = keep (.) v, M-normalised on the device (host vector of length n); LSA_ERR_ARG when its M-norm is not positive */
 int lsa_growth_set_start(lsa_ctx *ctx, lsa_growth *g, const double *host_v);
 /* Lanczos steps j = j0 .. j1-1 on W: N forward and N transposed solves, each followed by a product with M, the mask and the factor

@@ -2,8 +2,8 @@
 
 The third question of a linear stability analysis, beside the eigenvalues of :class:`Solver.eigen.EigenSolver` and the gains of
 :class:`Solver.resolvent.ResolventSolver` (same conventions: ``A x = lambda M x``): how much a perturbation of a *stable* flow can
-grow in finite time, ``G(T) = max ||q(T)||_M^2 / ||q(0)||_M^2``, and from which initial condition.  Time is marched by implicit
-Euler: one step ``(M - dt A) q+ = M q`` is ``q+ = -sigma C^-1 M q`` with ``C = A - sigma M`` and ``sigma = 1 / dt``, the shift-invert
+grow in finite time, ``G(T) = max ||q(T)||_M^2 / ||q(0)||_M^2``, and from which initial condition.  By default time is marched by
+implicit Euler: one step ``(M - dt A) q+ = M q`` is ``q+ = -sigma C^-1 M q`` with ``C = A - sigma M`` and ``sigma = 1 / dt``, the shift-invert
 operator the library factorises.  Over ``N = T / dt`` steps the propagator is ``Phi = (-sigma C^-1 M)^N``, its adjoint in the
 ``M``-inner product is ``Phi+ = (-sigma C^-T M)^N`` on the same factors, and the gains are the largest eigenvalues of
 ``W = Phi+ Phi``; the library runs its thick-restart Lanczos iteration on it with a march of ``2 N`` solves on ONE nested-dissection
@@ -15,8 +15,13 @@ LU behind every step (``lsa_growth_*``, ``csrc/growth.hip``)::
     curve = tg.sweep([2.0, 4.0, 10.0])   # one factorisation for every horizon of this dt
 
 Constrained dofs (Dirichlet rows kept as identity rows in ``A`` and ``M``) are uncoupled scalar ODEs ``q' = q`` and no part of the
-flow; unmasked, each is a spurious "gain" ``(1 - dt)^(-2 N)``.  ``constrained="auto"`` finds and leaves them out.  Crank-Nicolson,
-other energy weights, regional masks and lockstep over horizons are not built.
+flow; unmasked, each is a spurious "gain" ``(1 - dt)^(-2 N)``.  ``constrained="auto"`` finds and leaves them out.
+
+Implicit Euler is first order in ``dt``: at a ``dt`` of a quarter time unit its gains are a quarter low.  ``scheme="sdirk2"`` marches
+by the L-stable, stiffly accurate two-stage SDIRK method with ``gamma = 1 - 1/sqrt(2)`` instead, second order in ``dt``: both stages
+solve with ``M - gamma dt A``, so ``sigma = 1 / (gamma dt)`` and there is still ONE factorisation; with ``S = -sigma C^-1 M`` one time step
+is ``S (a S + b I)``, ``a = 1 + sqrt(2)``, ``b = -sqrt(2)``, and every step of the iteration marches ``4 N`` solves.  Other energy
+weights, regional masks, higher-order schemes and lockstep over horizons are not built.
 """
 
 from __future__ import annotations
@@ -33,14 +38,22 @@ from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType, sym
 
 logger = logging.getLogger(__name__)
 
+SDIRK2_GAMMA = 1.0 - 1.0 / np.sqrt(2.0)
+SCHEMES = {"euler": 1.0, "sdirk2": SDIRK2_GAMMA}  # the scheme's gamma: the factorised matrix is M - gamma dt A, sigma = 1 / (gamma dt)
+
 
 @dataclass(frozen=True)
 class TransientGrowthConfig:
-    dt: float  # the implicit-Euler time step
+    dt: float  # the time step
     num_modes: int = 1  # gains (with their initial conditions and responses) to compute
     ncv: int = 12  # Krylov subspace dimension
     atol: float = 1e-8  # relative tolerance on G: |beta y_mi| / theta_i
     max_it: int = 500  # restarts allowed
+    scheme: str = "euler"  # the time stepping: "euler" (implicit Euler, first order) or "sdirk2" (two-stage L-stable SDIRK, second order)
+
+    def __post_init__(self):
+        if self.scheme not in SCHEMES:
+            raise ValueError(f"scheme must be one of {sorted(SCHEMES)}, got {self.scheme!r}")
 
 
 @dataclass
@@ -55,6 +68,7 @@ class TransientGrowthResult:
     times: np.ndarray  # steps + 1: s dt
     estimates: np.ndarray  # relative residual estimates of G_j
     stats: dict = field(default_factory=dict)
+    scheme: str = "euler"  # the time stepping the gains belong to (steps, dt and times count time steps, not stages)
 
 
 def decoupled_dofs(A, M) -> np.ndarray:
@@ -86,7 +100,7 @@ def horizon_steps(T, dt: float) -> int:
 class TransientGrowthSolver:
     """Optimal energy gains of ``(A, M)`` over horizons ``T = N dt``; thin shell around :class:`iEpsSolver` 's preparation (union
     pattern, nested-dissection ordering, permuted numbering, upload, LU) and ``lsa_hip.GrowthBasis``.  The operator and its
-    factorisation of ``A - M / dt`` are built by the first :meth:`solve` and kept until :meth:`release`."""
+    factorisation of ``A - M / dt`` (``scheme="sdirk2"``: ``A - M / (gamma dt)``) are built by the first :meth:`solve` and kept until :meth:`release`."""
 
     def __init__(self, A, M, cfg: TransientGrowthConfig, *, constrained="auto", device: int = 0, layout: str = "single",
                  pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
@@ -142,7 +156,7 @@ class TransientGrowthSolver:
         eps.set_st_pc_type(pc_type)
         eps.set_tolerances(cfg.atol, cfg.max_it)
         eps.set_dimensions(cfg.num_modes, cfg.ncv)
-        eps.set_target(1.0 / cfg.dt)
+        eps.set_target(1.0 / (SCHEMES[cfg.scheme] * cfg.dt))
         self._eps = eps
         self._seed = seed
         self._n = n
@@ -174,7 +188,7 @@ class TransientGrowthSolver:
                 raise NotImplementedError("Transient growth needs the exact LU; it does not fit the device memory")
             keep = np.ones(self._n)
             keep[self._constrained] = 0.0
-            basis = lsa_hip.GrowthBasis(prep["ctx"], op, run["ncv"], steps, keep[prep["perm"]])  # (the iteration runs in permuted numbering)
+            basis = lsa_hip.GrowthBasis(prep["ctx"], op, run["ncv"], steps, keep[prep["perm"]], self._cfg.scheme)  # (the iteration runs in permuted numbering)
             basis.set_row_permutation(prep["perm"])
         except BaseException:
             run.clear()
@@ -183,7 +197,7 @@ class TransientGrowthSolver:
 
     def solve(self, T: float) -> TransientGrowthResult:
         """Gains, initial conditions, responses and energy curves at the horizon ``T``, a positive whole multiple of ``dt``.  The first
-        call orders, analyses and factorises ``A - M / dt``; every later one changes the number of steps only and returns the bytes a
+        call orders, analyses and factorises ``A - sigma M``; every later one changes the number of steps only and returns the bytes a
         fresh solver gives for its horizon."""
         cfg = self._cfg
         steps = horizon_steps(T, cfg.dt)
@@ -211,7 +225,7 @@ class TransientGrowthSolver:
                  "seconds_expand": out["seconds_expand"], "seconds_dense": out["seconds_dense"], "seconds_restart": out["seconds_restart"],
                  "seconds_total": time.time() - started}
         return TransientGrowthResult(float(T), steps, cfg.dt, out["gains"], out["initial"][:, :k], out["responses"][:, :k], out["energy"][:k],
-                                     cfg.dt * np.arange(steps + 1), out["estimates"], stats)
+                                     cfg.dt * np.arange(steps + 1), out["estimates"], stats, cfg.scheme)
 
     def sweep(self, horizons) -> list[TransientGrowthResult]:
         """One result per horizon on ONE factorisation: every horizon after the first changes the number of steps only

@@ -14,6 +14,15 @@
 // The march log travels to the host behind the step's one synchronisation; every solve is judged by the rule of lsa_lanczos_extend.
 // Each direction carries its own refinement step once one of its solves missed ksp_rtol.
 //
+// lsa_growth_set_scheme(LSA_GROWTH_SDIRK2) marches by the L-stable, stiffly accurate two-stage SDIRK method with gamma = 1 - 1/sqrt 2
+// instead: second order in dt.  Both stages solve with M - gamma dt A, so sigma = 1 / (gamma dt) and C is the same one matrix; with
+// S = -sigma C^-1 M one time step is Phi_1 = S (a S + b I), a = 1 + sqrt 2, b = -sqrt 2 (the stability function
+// (1 + (1 - 2 gamma) z) / (1 - gamma z)^2 written in s = 1 / (1 - gamma z)), its M-adjoint S+ (a S+ + b I) with S+ = -sigma C^-T M.  The
+// march of a step is 4N solves (k < 2N forward, k >= 2N transposed) and only the transition after an even solve differs:
+//         k odd:    b_{k+1} = -sigma keep (.) mx                        the next solve is a first stage: the statement above
+//         k even:   b_{k+1} = (-a sigma) keep (.) mx + b b_k            the next solve is the second stage: b_k already is -sigma keep (.) M q
+// b_k is the vector the kernel reads for the residual sum anyway: the combining form costs no load, no buffer and no launch more.
+//
 // The sums of tg_march_kernel are taken in the order of k_multi_dot (rows strided over the 256 threads of a chunk of at least 512
 // rows, xor tree over the wavefront, the four waves in wave order; tg_log_kernel: the chunks strided over 64 lanes and the same tree)
 // and there are no floating-point atomics: two runs give the same bits, and LSA_GROWTH_FUSED=0 -- the same step through
@@ -42,10 +51,12 @@ __device__ __forceinline__ double tg_wave_sum(double v) {
 // After an inner solve x of right-hand side b with z = C x and mx = M x, one pass over the rows: next = alpha keep (.) mx (alpha =
 // -sigma; next == null: the last solve of a final march, nothing follows) and the chunk sums part[q nchunks + chunk], q = 0..3, of
 // |b - z|^2, |b|^2, x^T mx and |x|^2.  The chunks are strided over the grid (sized from the CU count); next may not alias b.
+// kCombine (a second-stage right-hand side of SDIRK2; next is not null): next = cb b + alpha keep (.) mx, alpha then being -a sigma.
+template <bool kCombine>
 __global__ __launch_bounds__(kTgThreads) void tg_march_kernel(int64_t n, int64_t rows_per_chunk, int nchunks, double alpha, const double* __restrict__ b,
                                                               const double* __restrict__ z, const double* __restrict__ x,
                                                               const double* __restrict__ mx, const double* __restrict__ keep, double* __restrict__ next,
-                                                              double* __restrict__ part) {
+                                                              double* __restrict__ part, double cb) {
     __shared__ double wsum[4][4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
@@ -65,7 +76,10 @@ __global__ __launch_bounds__(kTgThreads) void tg_march_kernel(int64_t n, int64_t
             s2 = fma(xb, mb, s2);
             s3 = fma(xa, xa, s3);
             s3 = fma(xb, xb, s3);
-            if (next) {
+            if constexpr (kCombine) {
+                next[i] = fma(cb, ba, alpha * (ka * ma));
+                next[i2] = fma(cb, bb, alpha * (kb * mb));
+            } else if (next) {
                 next[i] = alpha * (ka * ma);
                 next[i2] = alpha * (kb * mb);
             }
@@ -77,7 +91,10 @@ __global__ __launch_bounds__(kTgThreads) void tg_march_kernel(int64_t n, int64_t
             s1 = fma(bi, bi, s1);
             s2 = fma(xi, mi, s2);
             s3 = fma(xi, xi, s3);
-            if (next) next[i] = alpha * (keep[i] * mi);
+            if constexpr (kCombine)
+                next[i] = fma(cb, bi, alpha * (keep[i] * mi));
+            else if (next)
+                next[i] = alpha * (keep[i] * mi);
         }
         s0 = tg_wave_sum(s0);
         s1 = tg_wave_sum(s1);
@@ -114,6 +131,13 @@ __global__ __launch_bounds__(kTgThreads) void tg_scale_kernel(int64_t n, double 
     for (int64_t i = (int64_t)blockIdx.x * kTgThreads + threadIdx.x; i < n; i += stride) y[i] = alpha * (keep[i] * x[i]);
 }
 
+// y = cb b + ca keep (.) x: the combining transition of the unfused form, tg_march_kernel<true>'s expression (y may alias neither)
+__global__ __launch_bounds__(kTgThreads) void tg_combine_kernel(int64_t n, double ca, double cb, const double* __restrict__ keep, const double* __restrict__ x,
+                                                                const double* __restrict__ b, double* __restrict__ y) {
+    const int64_t stride = (int64_t)gridDim.x * kTgThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kTgThreads + threadIdx.x; i < n; i += stride) y[i] = fma(cb, b[i], ca * (keep[i] * x[i]));
+}
+
 int tg_check_launch(lsa_ctx* ctx, const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return lsa_set_error(ctx, LSA_ERR_HIP, "%s: kernel launch failed: %s", what, hipGetErrorString(e));
@@ -121,6 +145,7 @@ int tg_check_launch(lsa_ctx* ctx, const char* what) {
 }
 
 // tg_march_kernel + tg_log_kernel unless LSA_GROWTH_FUSED=0 (read once per process): then k_residual_norms, k_multi_dot and the scale
+// (a combined right-hand side: tg_combine_kernel)
 bool tg_fused() {
     static const bool fused = env_flag("LSA_GROWTH_FUSED", true);
     return fused;
@@ -136,6 +161,7 @@ struct lsa_growth {
     lanczos_operator hook{};
     int64_t n = 0;
     int32_t ncv = 0, nsteps = 0, log_cap = 0;
+    int32_t scheme = LSA_GROWTH_EULER;  // LSA_GROWTH_SDIRK2: two solves per time step, the second on a combined right-hand side
     double sigma = 0.0;
     double* keep = nullptr;  // device 0/1 mask, the basis' row numbering
     std::vector<double> hkeep;
@@ -163,6 +189,14 @@ void tg_free(lsa_growth* g) {
     if (g->hlog) (void)hipHostFree(g->hlog);
     delete g;
 }
+
+// SDIRK2's coefficients: Phi_1 = S (a S + b I)
+const double kTgA = 1.0 + std::sqrt(2.0), kTgB = -std::sqrt(2.0);
+
+int32_t tg_stages(int32_t scheme) { return scheme == LSA_GROWTH_SDIRK2 ? 2 : 1; }
+
+// whether the right-hand side after solve k of a march is the combined one: under SDIRK2 the solves alternate first stage, second stage
+bool tg_combines(const lsa_growth* g, int32_t k) { return g->scheme == LSA_GROWTH_SDIRK2 && (k & 1) == 0; }
 
 int tg_grid(lsa_ctx* ctx, int64_t work, int per_cu) { return (int)std::max<int64_t>(std::min<int64_t>(work, (int64_t)ctx->num_cu * per_cu), 1); }
 
@@ -192,10 +226,18 @@ int tg_scale(lsa_ctx* ctx, lsa_growth* g, double alpha, const double* x, double*
     return tg_check_launch(ctx, "growth scale");
 }
 
-// What follows the inner solve x of b (z = C x): mx = M x, the next right-hand side -sigma keep (.) mx (next == null: none) and the
-// four sums of log entry k.
-int tg_after_solve(lsa_ctx* ctx, lsa_growth* g, int32_t k, const double* b, const double* z, const double* x, double* next) {
+int tg_combine(lsa_ctx* ctx, lsa_growth* g, double ca, double cb, const double* x, const double* b, double* y) {
+    hipLaunchKernelGGL(tg_combine_kernel, dim3(tg_grid(ctx, (g->n + kTgThreads - 1) / kTgThreads, 8)), dim3(kTgThreads), 0, ctx->stream, g->n, ca, cb, g->keep, x, b,
+                       y);
+    return tg_check_launch(ctx, "growth combine");
+}
+
+// What follows the inner solve x of b (z = C x): mx = M x, the next right-hand side -sigma keep (.) mx (next == null: none; combine,
+// with a next: (-a sigma) keep (.) mx + b b, SDIRK2's second stage) and the four sums of log entry k.
+int tg_after_solve(lsa_ctx* ctx, lsa_growth* g, int32_t k, const double* b, const double* z, const double* x, double* next, bool combine) {
     const int64_t n = g->n;
+    combine = combine && next;
+    const double ca = kTgA * -g->sigma, cb = kTgB;
     double* out = g->log + (size_t)4 * (size_t)k;
     LSA_CHECK(tg_mass(ctx, g, x, g->mx));
     if (tg_fused()) {
@@ -203,8 +245,12 @@ int tg_after_solve(lsa_ctx* ctx, lsa_growth* g, int32_t k, const double* b, cons
         int64_t rows_per_chunk = ((n + kTgMaxChunks - 1) / kTgMaxChunks + kTgThreads - 1) / kTgThreads * kTgThreads;
         rows_per_chunk = std::max<int64_t>(rows_per_chunk, 2 * kTgThreads);
         const int nchunks = (int)std::max<int64_t>((n + rows_per_chunk - 1) / rows_per_chunk, 1);
-        hipLaunchKernelGGL(tg_march_kernel, dim3(tg_grid(ctx, nchunks, 4)), dim3(kTgThreads), 0, ctx->stream, n, rows_per_chunk, nchunks, -g->sigma, b, z, x,
-                           g->mx, g->keep, next, g->part);
+        if (combine)
+            hipLaunchKernelGGL(tg_march_kernel<true>, dim3(tg_grid(ctx, nchunks, 4)), dim3(kTgThreads), 0, ctx->stream, n, rows_per_chunk, nchunks, ca, b, z, x,
+                               g->mx, g->keep, next, g->part, cb);
+        else
+            hipLaunchKernelGGL(tg_march_kernel<false>, dim3(tg_grid(ctx, nchunks, 4)), dim3(kTgThreads), 0, ctx->stream, n, rows_per_chunk, nchunks, -g->sigma, b, z,
+                               x, g->mx, g->keep, next, g->part, 0.0);
         hipLaunchKernelGGL(tg_log_kernel, dim3(1), dim3(kTgThreads), 0, ctx->stream, nchunks, g->part, out);
         return tg_check_launch(ctx, "growth march");
     }
@@ -214,6 +260,7 @@ int tg_after_solve(lsa_ctx* ctx, lsa_growth* g, int32_t k, const double* b, cons
     LSA_CHECK(k_multi_dot(ctx, LSA_F64, n, 1, b, n, b, out + 1));
     LSA_CHECK(k_multi_dot(ctx, LSA_F64, n, 1, x, n, g->mx, out + 2));
     LSA_CHECK(k_multi_dot(ctx, LSA_F64, n, 1, x, n, x, out + 3));
+    if (combine) return tg_combine(ctx, g, ca, cb, g->mx, b, next);
     return next ? tg_scale(ctx, g, -g->sigma, g->mx, next) : LSA_OK;
 }
 
@@ -262,7 +309,7 @@ int tg_judge_march(lsa_ctx* ctx, lsa_growth* g, std::vector<TgSolve>& sv, const 
 int tg_hook_enqueue(lsa_ctx* ctx, void* self, int32_t, const double* rhs, double* w, double* z, double* r, double* xnorm2_dev, const double** chk_b,
                     bool* refined) {
     lsa_growth* g = (lsa_growth*)self;
-    const int32_t N = g->nsteps, last = 2 * N - 1;
+    const int32_t N = tg_stages(g->scheme) * g->nsteps, last = 2 * N - 1;  // N solves each way
     g->used_fwd = g->refine_fwd;
     g->used_adj = g->refine_adj;
     const double* b = rhs;
@@ -270,7 +317,7 @@ int tg_hook_enqueue(lsa_ctx* ctx, void* self, int32_t, const double* rhs, double
         const bool adj = k >= N;
         LSA_CHECK(direct_solve_enqueue(ctx, g->op, LSA_F64, b, g->x, g->cz, g->r, adj ? g->used_adj : g->used_fwd, g->rnorms, adj ? 1 : 0));
         double* next = g->pp[k & 1];
-        LSA_CHECK(tg_after_solve(ctx, g, k, b, g->cz, g->x, next));
+        LSA_CHECK(tg_after_solve(ctx, g, k, b, g->cz, g->x, next, tg_combines(g, k)));
         b = next;
     }
     // the last solve lands where the default's single solve does; the step's first reduction checks it
@@ -292,7 +339,7 @@ int tg_hook_read_back(lsa_ctx* ctx, void* self) {
 
 int tg_hook_judge(lsa_ctx* ctx, void* self, int32_t j, double res, double bnorm, double xnorm) {
     lsa_growth* g = (lsa_growth*)self;
-    const int32_t N = g->nsteps, last = 2 * N - 1;
+    const int32_t N = tg_stages(g->scheme) * g->nsteps, last = 2 * N - 1;
     std::vector<TgSolve> sv((size_t)last + 1);
     for (int32_t k = 0; k < last; ++k) {
         const double* e = g->hlog + (size_t)4 * (size_t)k;
@@ -357,7 +404,7 @@ int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, doub
     if (nvec < 0 || nvec > g->ncv) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth responses: bad sizes");
     if (nvec == 0) return LSA_OK;
     const int64_t n = g->n;
-    const int32_t N = g->nsteps;
+    const int32_t stages = tg_stages(g->scheme), steps = g->nsteps, N = stages * steps;  // N solves; a time step's energy: its last stage's
     const size_t vb = (size_t)std::max<int64_t>(n, 1) * sizeof(double);
     if (!g->resp) LSA_HIP_ALLOC(ctx, hipMalloc((void**)&g->resp, vb * (size_t)g->ncv));
     const double* Q0 = lanczos_ritz_device(g->lz);
@@ -375,7 +422,7 @@ int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, doub
             for (int32_t s = 0; s < N; ++s) {
                 LSA_CHECK(direct_solve_enqueue(ctx, g->op, LSA_F64, b, g->x, g->cz, g->r, refine, g->rnorms, 0));
                 double* next = s + 1 < N ? g->pp[s & 1] : nullptr;
-                LSA_CHECK(tg_after_solve(ctx, g, s, b, g->cz, g->x, next));
+                LSA_CHECK(tg_after_solve(ctx, g, s, b, g->cz, g->x, next, tg_combines(g, s)));
                 b = next;
             }
             LSA_CHECK(k_copy(ctx, LSA_F64, n, g->x, g->resp + (size_t)c * (size_t)n));
@@ -390,8 +437,9 @@ int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, doub
             if (verdict < 0) return LSA_ERR_DIVERGED;
         }
         if (energy) {
-            energy[(size_t)c * (size_t)(N + 1)] = g->hlog[(size_t)4 * (size_t)N];
-            for (int32_t s = 0; s < N; ++s) energy[(size_t)c * (size_t)(N + 1) + (size_t)s + 1] = g->hlog[(size_t)4 * (size_t)s + 2];
+            energy[(size_t)c * (size_t)(steps + 1)] = g->hlog[(size_t)4 * (size_t)N];
+            for (int32_t s = 0; s < steps; ++s)
+                energy[(size_t)c * (size_t)(steps + 1) + (size_t)s + 1] = g->hlog[(size_t)4 * (size_t)(stages * (s + 1) - 1) + 2];
         }
     }
     g->P.st->seconds_solve += now_s() - t0;
@@ -473,9 +521,21 @@ int lsa_growth_set_row_permutation(lsa_ctx* ctx, lsa_growth* g, const int32_t* p
 int lsa_growth_set_steps(lsa_ctx* ctx, lsa_growth* g, int32_t nsteps) {
     if (!ctx || !g) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_set_steps: null argument");
     if (nsteps < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_set_steps: nsteps = %d: a horizon has at least one step", nsteps);
-    LSA_CHECK(tg_reserve_log(ctx, g, 2 * nsteps));
+    LSA_CHECK(tg_reserve_log(ctx, g, 2 * tg_stages(g->scheme) * nsteps));
     g->nsteps = nsteps;
     // a new horizon begins as a new handle does: the bytes of a horizon do not depend on what ran before it on these factors
+    g->refine_fwd = g->refine_adj = false;
+    g->logged = 0;
+    return LSA_OK;
+}
+
+int lsa_growth_set_scheme(lsa_ctx* ctx, lsa_growth* g, int32_t scheme) {
+    if (!ctx || !g) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_set_scheme: null argument");
+    if (scheme != LSA_GROWTH_EULER && scheme != LSA_GROWTH_SDIRK2)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_set_scheme: scheme = %d is neither LSA_GROWTH_EULER (0) nor LSA_GROWTH_SDIRK2 (1)", scheme);
+    LSA_CHECK(tg_reserve_log(ctx, g, 2 * tg_stages(scheme) * g->nsteps));
+    g->scheme = scheme;
+    // as a new horizon: the bytes of a scheme do not depend on what ran before it on these factors
     g->refine_fwd = g->refine_adj = false;
     g->logged = 0;
     return LSA_OK;

@@ -404,7 +404,8 @@ int growth_restart(lsa_ctx* ctx, lsa_growth* g, int32_t m, int32_t knew, const d
 // the device for growth_responses
 int growth_ritz_vectors(lsa_ctx* ctx, lsa_growth* g, int32_t m, int32_t nvec, const double* Y, int32_t ldy, double* Q0);
 // QT[:, c] = Phi q0_c and energy[c (N + 1) + s] = ||Phi_s q0_c||_M^2, s = 0..N, for the columns growth_ritz_vectors left: one forward
-// march of N checked solves each (either destination may be null)
+// march of N checked solves each, 2N under LSA_GROWTH_SDIRK2 with the energies at each time step's second stage (either destination may
+// be null)
 int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, double* energy);
 // accepted forward solves, accepted transposed solves, and how many of each carried the refinement step
 void growth_counts(const lsa_growth* g, int64_t counts[4]);

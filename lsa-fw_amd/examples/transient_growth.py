@@ -1,10 +1,13 @@
 """Growth curve of a synthetic cylinder case: the optimal energy gains G_1(T) >= G_2(T) >= ... of the linearised flow at Re = 50 over
-a list of horizons, on ONE factorisation of A - M / dt (``TransientGrowthSolver.sweep``).
+a list of horizons, on ONE factorisation of A - sigma M (``TransientGrowthSolver.sweep``).
 
-    python lsa-fw_amd/examples/transient_growth.py [--case S5k] [--modes 2] [--dt 0.25] [--horizons 1 2 4 10 20]
+    python lsa-fw_amd/examples/transient_growth.py [--case S5k] [--modes 2] [--dt 0.25] [--scheme euler] [--horizons 1 2 4 10 20]
+
+``--scheme euler`` (the default) marches by implicit Euler, first order in dt; ``--scheme sdirk2`` by the L-stable two-stage SDIRK
+method, second order: within 0.3 % of the flow's gains at dt = 0.5, where Euler at dt = 0.25 is 24 % low at T = 10.
 
 The flow is stable -- the leading eigenvalue has real part -0.018 -- and strongly non-normal: a well chosen perturbation still grows
-(G(4) = 2.2, G(20) = 3.5 on S2k) before it decays, which the eigenvalues alone do not say.  The Dirichlet rows of the pair are left
+(G(4) = 2.2, G(20) = 3.5 on S2k under implicit Euler at dt = 0.25; 2.55 at T = 4 under SDIRK2) before it decays, which the eigenvalues alone do not say.  The Dirichlet rows of the pair are left
 out of the flow (``constrained="auto"``).  Needs an AMD GPU (there is no CPU fallback).
 """
 
@@ -27,11 +30,12 @@ def main() -> None:
     ap.add_argument("--modes", type=int, default=2)
     ap.add_argument("--ncv", type=int, default=12)
     ap.add_argument("--dt", type=float, default=0.25)
+    ap.add_argument("--scheme", choices=("euler", "sdirk2"), default="euler")
     ap.add_argument("--horizons", type=float, nargs="+", default=[1.0, 2.0, 4.0, 10.0, 20.0])
     args = ap.parse_args()
     es = fem.cylinder_case(args.case)
-    tg = TransientGrowthSolver(es.A, es.M, TransientGrowthConfig(dt=args.dt, num_modes=args.modes, ncv=args.ncv, atol=1e-8))
-    print(f"{args.case}: n = {es.n}, {tg.constrained.size} constrained dofs left out, dt = {args.dt}")
+    tg = TransientGrowthSolver(es.A, es.M, TransientGrowthConfig(dt=args.dt, num_modes=args.modes, ncv=args.ncv, atol=1e-8, scheme=args.scheme))
+    print(f"{args.case}: n = {es.n}, {tg.constrained.size} constrained dofs left out, dt = {args.dt}, scheme {args.scheme}")
     print("       T  steps   " + "".join(f"G_{j + 1:<12d}" for j in range(args.modes)) + "applies restarts  factor s   steps s  factorisation reused")
     for res in tg.sweep(args.horizons):
         st = res.stats

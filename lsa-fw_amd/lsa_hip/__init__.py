@@ -253,6 +253,7 @@ SIGNATURES = {
     "lsa_growth_destroy": (None, [_P]),
     "lsa_growth_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
     "lsa_growth_set_steps": (ctypes.c_int, [_P, _P, _I32]),
+    "lsa_growth_set_scheme": (ctypes.c_int, [_P, _P, _I32]),
     "lsa_growth_set_start": (ctypes.c_int, [_P, _P, _P]),
     "lsa_growth_extend": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_I32)]),
     "lsa_growth_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
@@ -1314,11 +1315,18 @@ class GrowthBasis:
     """Real ``M``-orthonormal Lanczos basis in HBM for the transient-growth operator ``W = Phi+ Phi``, ``Phi = (-sigma C^-1 M)^N``,
     ``C = A - sigma M``, ``sigma = 1 / dt`` (``lsa_growth_*``): a march of ``2 N`` solves on one factorisation behind every step.
     ``op`` must be a shift-invert operator (mode 0) at the real positive ``sigma`` with real exact factors (``pc_type=2``) and a real
-    ``M``; ``keep`` is the 0/1 mask of the free dofs in the operator's row numbering (``None``: all ones)."""
+    ``M``; ``keep`` is the 0/1 mask of the free dofs in the operator's row numbering (``None``: all ones).  ``scheme="sdirk2"``
+    (``lsa_growth_set_scheme``) marches by the L-stable two-stage SDIRK method with ``gamma = 1 - 1/sqrt(2)`` instead of implicit Euler:
+    second order in ``dt``, ``sigma = 1 / (gamma dt)``, ``Phi = (S (a S + b I))^N`` with ``S = -sigma C^-1 M``, ``4 N`` solves a step."""
 
-    def __init__(self, ctx: Context, op: ShiftInvertOperator, ncv: int, nsteps: int, keep: np.ndarray | None = None):
+    SCHEMES = {"euler": 0, "sdirk2": 1}
+
+    def __init__(self, ctx: Context, op: ShiftInvertOperator, ncv: int, nsteps: int, keep: np.ndarray | None = None, scheme: str = "euler"):
+        if scheme not in self.SCHEMES:
+            raise ValueError(f"scheme must be one of {sorted(self.SCHEMES)}, got {scheme!r}")
         self.ctx, self._op = ctx, op
         self.n, self.ncv, self.nsteps = op.n, int(ncv), int(nsteps)
+        self.scheme = "euler"
         k = None
         if keep is not None:
             k = np.ascontiguousarray(keep, dtype=np.float64)
@@ -1328,6 +1336,13 @@ class GrowthBasis:
         ctx.check(ctx._lib.lsa_growth_create(ctx.handle, op.handle, self.ncv, self.nsteps, None if k is None else _ptr(k), ctypes.byref(h)))
         self.handle = h
         self._has_perm = False
+        if scheme != "euler":
+            self.set_scheme_code(self.SCHEMES[scheme])
+
+    def set_scheme_code(self, code: int) -> None:
+        """``lsa_growth_set_scheme`` with the bare code (0: implicit Euler, 1: SDIRK2); any other is the library's ``ValueError``."""
+        self.ctx.check(self.ctx._lib.lsa_growth_set_scheme(self.ctx.handle, self.handle, int(code)))
+        self.scheme = {v: k for k, v in self.SCHEMES.items()}[int(code)]
 
     @property
     def basis_bytes(self) -> int:

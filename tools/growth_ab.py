@@ -1,6 +1,6 @@
 """Optimal transient growth: the library's iteration against what a user can drive from the host on kept factors.
 
-    python tools/growth_ab.py [--cases S30k C160k] [--reps 3] [--out profiles/growth_ab.json]
+    python tools/growth_ab.py [--cases S30k C160k] [--reps 3] [--scheme euler] [--out profiles/growth_ab.json]
 
 ``library`` (a): ``Solver.growth.TransientGrowthSolver.solve`` -- set-up, one factorisation of ``A - M / dt``, the thick-restart Lanczos
 iteration on ``W = Phi+ Phi`` with the march of ``2 N`` solves, its checks, the mask and the orthogonalisation on the device, one
@@ -14,6 +14,9 @@ free, ``S = (Phi^T M Phi)_uu`` (``Phi = Xi M`` never sees the other dofs of its 
 dt 0.25, T = 4 (N = 16), num_modes 2, ncv 12, tolerance 1e-8.  Every timed sample builds its solver anew (construction, preparation,
 factorisation, iteration, release inside the clock); the two settings alternate in one process after one warm-up of each; medians
 and spread over ``reps`` samples.  The gains of (b) are compared with those of (a).  No test asserts these times.
+
+``--scheme sdirk2``: both settings take the two-stage step ``S (a S + b I)`` on the factorisation of ``A - M / (gamma dt)`` (``4 N`` solves
+per product; (b): ``4 N`` round trips).  Its results go under the key ``"sdirk2"`` of the output file, beside the Euler rows.
 """
 
 from __future__ import annotations
@@ -33,6 +36,8 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path[:0] = [str(ROOT), str(ROOT / "lsa-fw_amd")]
 
 DT, HORIZON, MODES, NCV, TOL = 0.25, 4.0, 2, 12, 1e-8
+SCHEME = "euler"  # (main sets it from --scheme)
+SDIRK_A, SDIRK_B = 1.0 + np.sqrt(2.0), -np.sqrt(2.0)
 
 
 def problem(case: str):
@@ -45,7 +50,7 @@ def library(es) -> dict:
     from Solver.growth import TransientGrowthConfig, TransientGrowthSolver
 
     t0 = time.perf_counter()
-    tg = TransientGrowthSolver(es.A, es.M, TransientGrowthConfig(dt=DT, num_modes=MODES, ncv=NCV, atol=TOL))
+    tg = TransientGrowthSolver(es.A, es.M, TransientGrowthConfig(dt=DT, num_modes=MODES, ncv=NCV, atol=TOL, scheme=SCHEME))
     tg.solver.prepare()
     t1 = time.perf_counter()
     res = tg.solve(HORIZON)
@@ -61,12 +66,13 @@ def library(es) -> dict:
 
 
 def host(es) -> dict:
-    from Solver.growth import decoupled_dofs
+    from Solver.growth import SCHEMES, decoupled_dofs
     from Solver.utils import KSPType, PreconditionerType, iKSP
 
     t0 = time.perf_counter()
     A, M = sp.csr_matrix(es.A), sp.csr_matrix(es.M)
-    n, sigma, steps = A.shape[0], 1.0 / DT, round(HORIZON / DT)
+    n, sigma, steps = A.shape[0], 1.0 / (SCHEMES[SCHEME] * DT), round(HORIZON / DT)
+    two = SCHEME == "sdirk2"
     keep = np.ones(n)
     keep[decoupled_dofs(A, M)] = 0.0
     u = np.flatnonzero((keep == 1.0) & (M.diagonal() > 0.0))  # free dofs that carry mass
@@ -77,15 +83,25 @@ def host(es) -> dict:
     ksp.set_tolerances(rtol=1e-10)
     products = [0]
 
+    def fwd(q):  # -sigma keep C^-1 M q
+        return -sigma * keep * ksp.solve(np.asarray(M @ q, dtype=np.float64)).as_array().real
+
+    def adj(q):  # -sigma M keep C^-T q
+        return -sigma * (M @ (keep * ksp.solve_many(np.asarray(q, dtype=np.float64).reshape(n, 1), adjoint=True)[:, 0].real))
+
     def S(y):
         products[0] += 1
         q = np.zeros(n)
         q[u] = y
-        for _ in range(steps):  # Phi q
-            q = -sigma * keep * ksp.solve(np.asarray(M @ q, dtype=np.float64)).as_array().real
+        for _ in range(steps):  # Phi q; sdirk2: one time step is s (a s + b) of the Euler-type step s
+            q = fwd(SDIRK_A * fwd(q) + SDIRK_B * q) if two else fwd(q)
         q = M @ q
-        for _ in range(steps):  # Phi^T (M Phi q), Phi^T = (-sigma M C^-T)^N
-            q = -sigma * (M @ (keep * ksp.solve_many(np.asarray(q, dtype=np.float64).reshape(n, 1), adjoint=True)[:, 0].real))
+        for _ in range(steps):  # Phi^T (M Phi q), Phi^T = (-sigma M C^-T)^N; sdirk2: (a s^T + b) s^T
+            if two:
+                q = adj(q)
+                q = SDIRK_A * adj(q) + SDIRK_B * q
+            else:
+                q = adj(q)
         return q[u]
 
     t1 = time.perf_counter()
@@ -98,7 +114,7 @@ def host(es) -> dict:
     ksp.reset()
     return {"gains": np.sort(theta)[::-1], "seconds": time.perf_counter() - t0, "seconds_setup": t1 - t0, "seconds_first_product": t2 - t1,
             "seconds_iteration": t3 - t2, "products": products[0] - 1, "seconds_per_product": (t3 - t2) / max(products[0] - 1, 1),
-            "read_backs_per_product": 2 * steps}
+            "read_backs_per_product": (4 if two else 2) * steps}
 
 
 def plain(run: dict) -> dict:
@@ -114,14 +130,17 @@ def main(argv=None) -> None:
     ap.add_argument("--cases", nargs="+", default=["S30k", "C160k"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--only", choices=("library", "host"), default=None, help="one setting alone, once per case (for a kernel trace)")
+    ap.add_argument("--scheme", choices=("euler", "sdirk2"), default="euler")
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "growth_ab.json")
     args = ap.parse_args(argv)
+    global SCHEME
+    SCHEME = args.scheme
     settings = {"library": library, "host": host}
     if args.only:
         for case in args.cases:
             print(json.dumps({"case": case, args.only: plain(settings[args.only](problem(case)))}), flush=True)
         return
-    result = {"config": {"dt": DT, "horizon": HORIZON, "num_modes": MODES, "ncv": NCV, "tol": TOL, "reps": args.reps}, "cases": []}
+    result = {"config": {"dt": DT, "horizon": HORIZON, "num_modes": MODES, "ncv": NCV, "tol": TOL, "reps": args.reps, "scheme": SCHEME}, "cases": []}
     for case in args.cases:
         es = problem(case)
         warm = {name: fn(es) for name, fn in settings.items()}  # warm-up: code objects, buffers
@@ -140,6 +159,10 @@ def main(argv=None) -> None:
         result["cases"].append(entry)
         print(json.dumps(entry), flush=True)
     args.out.parent.mkdir(parents=True, exist_ok=True)
+    if SCHEME != "euler":  # beside the Euler rows of the same file
+        kept = json.loads(args.out.read_text()) if args.out.exists() else {}
+        kept[SCHEME] = result
+        result = kept
     args.out.write_text(json.dumps(result, indent=1) + "\n")
 
 
