@@ -1059,6 +1059,7 @@ struct KsState {
     int kept = 0, restarts = 0;
     int64_t applies = 0;
     KsClock clk;
+    bool ahead = false;  // solo loop: the next cycle's first operator apply is queued before the dense phase (krylov_preapply)
 
     void random_vector() {
         for (int64_t i = 0; i < n; ++i) {
@@ -1107,6 +1108,7 @@ struct KsState {
     // the expansion from `kept` to m vectors through the solo code
     int expand() {
         clk.start();
+        krylov_arm_preapply(k, ahead && restarts < o->max_restarts);  // (the last cycle allowed ends in the result: nothing follows it)
         LSA_CHECK(ks_expand(kept, m, &applies, [&](int j, int32_t* bd) { return extend(j, bd); }, [&](int j) { return inject_random(j); }));
         clk.lap(clk.expand);
         return LSA_OK;
@@ -1143,6 +1145,8 @@ struct KsState {
             b[(size_t)c] = Hm(m, c);  // b^H: the row under the square part
             for (int r = 0; r < m; ++r) Tm(r, c) = Hm(r, c);
         }
+        // the final vector's operator apply runs on the device under the Schur form (if this cycle ends the solve, for nothing)
+        if (ahead && restarts < o->max_restarts) LSA_CHECK(krylov_preapply(ctx, k, m));
         // ---- Ritz pairs and residual estimates ----
         if (!schur(m, Tm, Qm)) return lsa_set_error(ctx, LSA_ERR_DIVERGED, "Krylov-Schur: the QR algorithm on the projected matrix did not converge");
         tri_eigenvectors(m, Tm, Sm);
@@ -1196,7 +1200,7 @@ struct KsState {
             knew = std::max(std::min(sdim, m - 1), 1);
         }
         clk.lap(clk.dense);
-        LSA_CHECK(lsa_krylov_restart(ctx, k, m, knew, Q.data(), m));
+        LSA_CHECK(ahead ? krylov_restart_queued(ctx, k, m, knew, Q.data(), m) : lsa_krylov_restart(ctx, k, m, knew, Q.data(), m));
         clk.lap(clk.restart);
         std::fill(H.begin(), H.end(), Z{0.0, 0.0});
         for (int c = 0; c < knew; ++c) {
@@ -1220,11 +1224,14 @@ int lsa_krylov_solve(lsa_ctx* ctx, lsa_krylov* k, const lsa_ks_options* o, const
     if (!ctx || !k || !o || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_solve: null argument");
     KsState st{ctx, k, o, mask, max_out, theta_out, lambda_out, X_out, est_out, result};
     LSA_CHECK(st.init("lsa_krylov_solve", v0));
-    for (bool done = false; !done;) {
-        LSA_CHECK(st.expand());
-        LSA_CHECK(st.after_expand("lsa_krylov_solve", &done));
+    st.ahead = true;
+    int rc = LSA_OK;
+    for (bool done = false; !done && rc == LSA_OK;) {
+        rc = st.expand();
+        if (rc == LSA_OK) rc = st.after_expand("lsa_krylov_solve", &done);
     }
-    return LSA_OK;
+    krylov_arm_preapply(k, false);
+    return rc;
 }
 
 static_assert(sizeof(lsa_ks_batch_info) == 288, "lsa_ks_batch_info layout is part of the C-ABI (tests/test_lockstep_cpu.py)");

@@ -321,6 +321,15 @@ int direct_solve_enqueue(lsa_ctx* ctx, lsa_op* op, int dtype, const void* rhs, v
 // books one accepted direct solve of relative residual res / bnorm: `products` sparse products besides the refinement's one
 void stats_book_direct_solve(lsa_stats* st, int products, bool refine, double res, double bnorm);
 
+// ---- the solo solve loop's queueing ahead (solver.hip; LSA_KRYLOV_PREAPPLY), driven by lsa_krylov_solve (dense.hip) -----------
+// armed: a full expansion queues the operator apply of its final vector V[:, ncv] behind its flush; krylov_preapply(m) queues it
+// where that has not happened (both only where the plan is the pipelined DCGS2 tail form).  The restart hands it to the first step
+// of the next expansion, which then starts at its orthogonalisation; whatever else comes first drops it.
+void krylov_arm_preapply(lsa_krylov* k, bool on);
+int krylov_preapply(lsa_ctx* ctx, lsa_krylov* k, int32_t m);
+// lsa_krylov_restart without its wait for the stream where the next expansion is pipelined (its read-back reports a failure)
+int krylov_restart_queued(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t knew, const void* Q, int32_t ldq);
+
 // ---- the lockstep expansion of a group of problems (solver.hip), driven by lsa_krylov_solve_batch (dense.hip) ---------------
 struct KrylovGroupBuf {  // the group's slots, checks and check pairs: cell (round s, problem z) at s J + z
     int32_t J, slots, nparts;

@@ -28,12 +28,14 @@ struct KrylovSwitches {
     bool tail;         // LSA_KRYLOV_TAIL (default on): the tail form of a pipelined step
     bool delayed;      // LSA_KRYLOV_DELAYED (default on): DCGS2 in the pipelined steps
     bool timing;       // LSA_KRYLOV_TIMING set: print queueing and waiting time per batch
+    bool preapply;     // LSA_KRYLOV_PREAPPLY (default on): queueing ahead -- the next batch (or the flush) before a batch is read back, the next
+                       // cycle's first inner solve under the host's Schur form, and a restart between them that does not wait for the stream
 };
 const KrylovSwitches& krylov_switches() {
     static const KrylovSwitches sw = [] {
         const char* passes = getenv("LSA_KRYLOV_PASSES");
         return KrylovSwitches{env_flag("LSA_KRYLOV_FUSED", true), passes && atoi(passes) == 4, env_flag("LSA_KRYLOV_TAIL", true),
-                              env_flag("LSA_KRYLOV_DELAYED", true), getenv("LSA_KRYLOV_TIMING") != nullptr};
+                              env_flag("LSA_KRYLOV_DELAYED", true), getenv("LSA_KRYLOV_TIMING") != nullptr, env_flag("LSA_KRYLOV_PREAPPLY", true)};
     }();
     return sw;
 }
@@ -505,16 +507,29 @@ struct lsa_krylov {
     double* imag2 = nullptr;         // device: sum Im^2 of the columns of the last canonical Ritz vectors
     void* xtmp = nullptr;            // device: the Ritz vectors in the caller's row order (ncv + 1 columns), allocated on first use
     std::vector<double> imag_norms;  // ... their square roots on the host (lsa_krylov_imag_norms)
-    void* Hdev = nullptr;      // max(batch, 1) slots of 2 ncv + 4 complex: a Hessenberg column (CGS2) or a, b, nu, c, ||w|| (DCGS2)
-    double* checks = nullptr;  // max(batch, 1) x 2: ||b - C x||^2, ||b||^2
+    void* Hdev = nullptr;      // two sets of max(batch, 1) slots of 2 ncv + 4 complex: a Hessenberg column (CGS2) or a, b, nu, c, ||w|| (DCGS2)
+    double* checks = nullptr;  // two sets of max(batch, 1) x 2: ||b - C x||^2, ||b||^2
     int32_t batch = 0;
     bool pipeline = false;  // the pipelined path may run (false after a solve needed the one-step path's judgement)
     // tail form of a pipelined step (k_cgs2_fused_tail): the step's last launch also multiplies t = M v_{j+1} for the next step
     // and leaves the pairs of this step's check of the inner solve; w2 takes the orthogonalised vector (w keeps the solve's result)
     void* w2 = nullptr;
-    double* tail_parts = nullptr;  // batch x tail_nparts pairs
+    double* tail_parts = nullptr;  // two sets of batch x tail_nparts pairs
     int32_t tail_nparts = 0;
     int32_t t_for = -1;            // op->t holds M v_j for this j (valid inside one lsa_krylov_extend call), -1: nothing
+    // The apply queued ahead of a restart (krylov_preapply): op->t = M v and w = C^-1 op->t of v = V[:, pre_col], which the restart
+    // copies to column pre_for, the first step of the next lsa_krylov_extend.  Written by pre_op; dropped by whatever else writes
+    // w or op->t, and at the latest by the next expansion, which takes it or not.
+    bool pre_armed = false;  // the solve loop wants the apply queued behind the flush of a full expansion
+    int32_t pre_col = -1, pre_for = -1;
+    const lsa_op* pre_op = nullptr;
+    void drop_preapply() { pre_col = pre_for = -1; }
+    hipEvent_t ev_read[2] = {nullptr, nullptr};  // the end of the read-back of either set of slots (queueing ahead)
+    int ensure_events(lsa_ctx* ctx_) {
+        for (hipEvent_t& e : ev_read)
+            if (!e) LSA_HIP_CHECK(ctx_, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return LSA_OK;
+    }
 };
 
 // bytes of one step's slot in Hdev: a CGS2 Hessenberg column (ncv + 2 entries) or DCGS2's a, b, nu, c, ||w|| (2 ncv + 3)
@@ -523,6 +538,8 @@ static size_t krylov_slot_bytes(int32_t ncv) { return (size_t)(2 * ncv + 4) * 16
 static void krylov_free(lsa_krylov* k) {
     for (void* p : {k->V, k->V2, k->w, k->qdev, k->Hdev, (void*)k->checks, (void*)k->imag2, k->xtmp, (void*)k->row_perm, k->w2, (void*)k->tail_parts})
         if (p) (void)hipFree(p);
+    for (hipEvent_t e : k->ev_read)
+        if (e) (void)hipEventDestroy(e);
     k->ow.release();
     delete k;
 }
@@ -947,6 +964,8 @@ int lsa_krylov_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, lsa_krylov** out) {
         if (c->n == op->n && c->ncv == ncv && c->batch == batch) {
             c->op = op;
             c->pipeline = true;
+            c->pre_armed = false;
+            c->drop_preapply();
             c->imag_norms.clear();
             (void)hipMemsetAsync(c->w, 0, vb, ctx->stream);
             *out = c;
@@ -972,7 +991,7 @@ int lsa_krylov_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, lsa_krylov** out) {
     // stream-ordered (RCCL): LSA_KRYLOV_BATCH steps per read-back (default 16; 0 or 1 = one step at a time, except in the
     // delayed form, whose basis must not depend on the batch size: there it means one step per read-back)
     k->batch = batch;
-    const size_t slots = (size_t)std::max(batch, 1);
+    const size_t slots = 2 * (size_t)std::max(batch, 1);  // (two sets: one is read back while the other is filled)
     if (hipMalloc(&k->Hdev, slots * krylov_slot_bytes(ncv)) != hipSuccess || hipMalloc((void**)&k->checks, slots * 2 * sizeof(double)) != hipSuccess) {
         lsa_krylov_destroy(k);
         return lsa_set_error(ctx, LSA_ERR_HIP, "lsa_krylov_create: out of device memory (pipeline buffers)");
@@ -1018,6 +1037,8 @@ int lsa_krylov_set_row_permutation(lsa_ctx* ctx, lsa_krylov* k, const int32_t* p
 
 int lsa_krylov_set_start(lsa_ctx* ctx, lsa_krylov* k, const void* host_v) {
     if (!ctx || !k || !host_v) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_set_start: null argument");
+    k->pre_armed = false;
+    k->drop_preapply();
     LSA_HIP_CHECK(ctx, hipMemcpyAsync(k->w, host_v, (size_t)k->n * 16, hipMemcpyHostToDevice, ctx->stream));
     double nrm = 0.0;
     LSA_CHECK(device_norm(ctx, LSA_C128, k->n, k->w, k->ow.nrm2, &nrm));
@@ -1032,6 +1053,7 @@ int lsa_krylov_inject(lsa_ctx* ctx, lsa_krylov* k, int32_t j, const void* host_v
     if (!ctx || !k || !host_v) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_inject: null argument");
     if (j < 0 || j > k->ncv) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_inject: index %d out of range", j);
     if (j == 0) return lsa_krylov_set_start(ctx, k, host_v);
+    k->drop_preapply();
     const size_t vb = (size_t)k->n * 16;
     LSA_HIP_CHECK(ctx, hipMemcpyAsync(k->w, host_v, vb, hipMemcpyHostToDevice, ctx->stream));
     LSA_CHECK(orthonormalize(ctx, LSA_C128, k->n, k->V, k->n, j, k->w, (char*)k->V + (size_t)j * vb, k->ow, k->hcol.data()));
@@ -1093,10 +1115,13 @@ static int krylov_enqueue_step(lsa_ctx* ctx, lsa_krylov* k, const StepPlan& plan
     double* chk = k->checks + 2 * (size_t)slot;
     const bool dcgs2 = plan.orth == Orth::dcgs2;
     if (plan.orth != Orth::cgs2_staged) LSA_CHECK(k->ow.ensure_fused(ctx, k->n));
+    // (the apply queued ahead of the restart is this step's: op->t and w hold it)
+    const bool ahead = plan.tail && dcgs2 && first && k->pre_for == j && k->pre_op == op;
+    k->drop_preapply();
     if (plan.tail) {
-        if (k->t_for != j) LSA_CHECK(spmv_global(ctx, op->Kmul, dtype, vj, op->t, false));
+        if (!ahead && k->t_for != j) LSA_CHECK(spmv_global(ctx, op->Kmul, dtype, vj, op->t, false));
         k->t_for = -1;
-        LSA_CHECK(pc_global(ctx, pc_of(op), op->Kfac->row0, op->n, dtype, op->t, k->w));
+        if (!ahead) LSA_CHECK(pc_global(ctx, pc_of(op), op->Kfac->row0, op->n, dtype, op->t, k->w));
         double* parts = k->tail_parts + (size_t)slot * 2 * (size_t)k->tail_nparts;
         if (dcgs2) {
             LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, k->w, first ? 1 : 0, sl, k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
@@ -1201,11 +1226,30 @@ static int pipelined_prepare(lsa_ctx* ctx, lsa_krylov* k, const StepPlan& plan) 
         op->gw_ready = true;
     }
     if (plan.tail && !k->tail_parts) {
-        const int32_t slots = std::max(k->batch, 1);
+        const int32_t slots = 2 * std::max(k->batch, 1);
         k->tail_nparts = k_cgs2_tail_parts(k->n);
         LSA_HIP_ALLOC(ctx, hipMalloc(&k->w2, (size_t)k->n * 16));
         LSA_HIP_ALLOC(ctx, hipMalloc((void**)&k->tail_parts, (size_t)slots * 2 * (size_t)k->tail_nparts * sizeof(double)));
     }
+    return LSA_OK;
+}
+
+// Queues the operator apply of the final vector V[:, m] ahead of the restart that will make it column `knew` (LSA_KRYLOV_PREAPPLY):
+// t = M v, the sweeps, w = C^-1 t, which is how the first step of the next expansion begins where the plan is the pipelined DCGS2
+// tail form.  Nothing is booked here: the step that takes the apply books it when its check is accepted.
+static int preapply_enqueue(lsa_ctx* ctx, lsa_krylov* k, int32_t m) {
+    if (k->pre_col == m && k->pre_op == k->op) return LSA_OK;  // (queued behind the flush already)
+    k->drop_preapply();
+    if (!krylov_switches().preapply || m < 1 || m > k->ncv) return LSA_OK;
+    const StepPlan plan = step_plan(ctx, k);
+    if (!(plan.pipelined && plan.tail && plan.orth == Orth::dcgs2)) return LSA_OK;
+    LSA_CHECK(pipelined_prepare(ctx, k, plan));
+    lsa_op* op = k->op;
+    k->t_for = -1;
+    LSA_CHECK(spmv_global(ctx, op->Kmul, LSA_C128, (char*)k->V + (size_t)m * (size_t)k->n * 16, op->t, false));
+    LSA_CHECK(pc_global(ctx, pc_of(op), op->Kfac->row0, op->n, LSA_C128, op->t, k->w));
+    k->pre_col = m;
+    k->pre_op = op;
     return LSA_OK;
 }
 
@@ -1261,44 +1305,116 @@ static int accept_steps(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, bool del
 
 // Steps [c->j, j1) in batches while the plan pipelines; c: where the expansion stands on entry and on return.  Ends early on a
 // breakdown (*breakdown) or when a solve needs the one-step path (k->pipeline goes false; the caller runs the rest there).
+// Queueing ahead (LSA_KRYLOV_PREAPPLY): what follows a batch if all of it is accepted -- the next batch, or the flush of the delayed
+// form and behind it the apply the solve loop has asked for -- is queued into the other set of slots BEFORE the batch is waited for,
+// so that the device works while the host reads the batch back and accepts it.  The kernels and their order are those of queueing
+// after the read-back.  A batch that is cut short or breaks down leaves what was queued behind it as it leaves its own later steps:
+// work on noise, waited for and queued again from the cursor.
 static int extend_pipelined(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, ExtendCursor* c, int32_t j1, int32_t* breakdown) {
     StepPlan plan = step_plan(ctx, k);
     LSA_CHECK(pipelined_prepare(ctx, k, plan));
     const int32_t slots = std::max(k->batch, 1);
     const size_t colb = krylov_slot_bytes(k->ncv);
-    LSA_CHECK(lsa_ensure_scratch(ctx, 0, (size_t)slots * (colb + 2 * sizeof(double))));
+    const size_t region = (size_t)slots * (colb + 2 * sizeof(double));  // of the pinned buffer, per set of slots
+    LSA_CHECK(lsa_ensure_scratch(ctx, 0, 2 * region));
     const bool delayed = plan.orth == Orth::dcgs2;
-    char* host = (char*)ctx->pinned;
+    const bool ahead = krylov_switches().preapply;
+    if (ahead) LSA_CHECK(k->ensure_events(ctx));
     k->t_for = -1;  // (op->t is anybody's between calls)
-    for (; c->j < j1 && plan.pipelined; plan = step_plan(ctx, k)) {
-        const int32_t nb = std::min<int32_t>(slots, j1 - c->j);
+    struct Queued {
+        int32_t j, nb, set;  // nb = 0: the flush in front of step j
+    };
+    auto host_of = [&](int32_t set) { return (char*)ctx->pinned + (size_t)set * region; };
+    auto slot_of = [&](int32_t set) { return (char*)k->Hdev + (size_t)set * (size_t)slots * colb; };
+    auto queued = [&](int32_t set) -> int {  // marks the end of a read-back
+        if (ahead) LSA_HIP_CHECK(ctx, hipEventRecord(k->ev_read[set], ctx->stream));
+        return LSA_OK;
+    };
+    auto wait_for = [&](const Queued& q) -> int {
+        const double tw = now_s();
+        if (ahead) LSA_HIP_CHECK(ctx, hipEventSynchronize(k->ev_read[q.set]));
+        else LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (krylov_switches().timing) fprintf(stderr, "[lsa_krylov] %d steps from %d: waited %.3f ms\n", q.nb, q.j, 1e3 * (now_s() - tw));
+        return LSA_OK;
+    };
+    auto queue_batch = [&](const StepPlan& p, int32_t j, bool first, int32_t set, Queued* q) -> int {
+        const int32_t nb = std::min<int32_t>(slots, j1 - j);
         const double tq = now_s();
         for (int32_t s = 0; s < nb; ++s) {
-            const int rc = krylov_enqueue_step(ctx, k, plan, c->j + s, s, s == 0 && !c->pending);
+            const int rc = krylov_enqueue_step(ctx, k, p, j + s, set * slots + s, s == 0 && first);
             if (rc != LSA_OK) {
                 (void)hipStreamSynchronize(ctx->stream);
                 return rc;
             }
         }
-        if (plan.tail) LSA_CHECK(k_cgs2_tail_checks(ctx, nb, k->tail_nparts, k->tail_parts, k->checks));
-        LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, k->Hdev, (size_t)nb * colb, hipMemcpyDeviceToHost, ctx->stream));
-        LSA_HIP_CHECK(ctx, hipMemcpyAsync(host + (size_t)slots * colb, k->checks, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        const double tw = now_s();
+        double* chk = k->checks + 2 * (size_t)set * (size_t)slots;
+        if (p.tail) LSA_CHECK(k_cgs2_tail_checks(ctx, nb, k->tail_nparts, k->tail_parts + (size_t)set * (size_t)slots * 2 * (size_t)k->tail_nparts, chk));
+        LSA_HIP_CHECK(ctx, hipMemcpyAsync(host_of(set), slot_of(set), (size_t)nb * colb, hipMemcpyDeviceToHost, ctx->stream));
+        LSA_HIP_CHECK(ctx, hipMemcpyAsync(host_of(set) + (size_t)slots * colb, chk, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        LSA_CHECK(queued(set));
+        if (krylov_switches().timing) fprintf(stderr, "[lsa_krylov] %d steps from %d queued in %.3f ms\n", nb, j, 1e3 * (now_s() - tq));
+        *q = Queued{j, nb, set};
+        return LSA_OK;
+    };
+    // the flush: the reduction and the update without a solve make V[:, j] and column j - 1 final, so that the restart, the Ritz
+    // vectors and the next call see what CGS2 leaves
+    auto queue_flush = [&](int32_t j, int32_t set, Queued* q) -> int {
+        LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, nullptr, 0, slot_of(set), k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
+        LSA_HIP_CHECK(ctx, hipMemcpyAsync(host_of(set), slot_of(set), colb, hipMemcpyDeviceToHost, ctx->stream));
+        LSA_CHECK(queued(set));
+        // (the solve loop's next act on a full basis is that vector's apply: behind the flush, the stream does not run empty)
+        if (k->pre_armed && j == k->ncv) LSA_CHECK(preapply_enqueue(ctx, k, j));
+        *q = Queued{j, 0, set};
+        return LSA_OK;
+    };
+    auto drain = [&]() -> int {  // what was queued ahead ran on noise: op->t, w and the slots are nobody's
+        k->t_for = -1;
+        k->drop_preapply();
         LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (krylov_switches().timing) fprintf(stderr, "[lsa_krylov] %d steps queued in %.3f ms, waited %.3f ms\n", nb, 1e3 * (tw - tq), 1e3 * (now_s() - tw));
+        return LSA_OK;
+    };
+    Queued cur{0, 0, 0}, next{0, 0, 0};
+    bool have = false, flushed = false;
+    if (c->j < j1 && plan.pipelined) {
+        LSA_CHECK(queue_batch(plan, c->j, !c->pending, 0, &cur));
+        have = true;
+    }
+    while (have) {
+        bool have_next = false;
+        if (ahead) {  // all of `cur` accepted: its last step leaves the delayed form pending
+            const int32_t jn = cur.j + cur.nb;
+            if (jn < j1) LSA_CHECK(queue_batch(plan, jn, !delayed, cur.set ^ 1, &next));
+            else if (delayed) LSA_CHECK(queue_flush(jn, cur.set ^ 1, &next));
+            have_next = jn < j1 || delayed;
+        }
+        LSA_CHECK(wait_for(cur));
         int32_t accepted = 0;
-        LSA_CHECK(accept_steps(ctx, k, H, delayed, host, colb, (const double*)(host + (size_t)slots * colb), 2, nb, c, breakdown, &accepted));
-        if (*breakdown >= 0) return LSA_OK;
+        const char* host = host_of(cur.set);
+        const int arc = accept_steps(ctx, k, H, delayed, host, colb, (const double*)(host + (size_t)slots * colb), 2, cur.nb, c, breakdown, &accepted);
+        if (arc != LSA_OK || *breakdown >= 0) {
+            if (have_next) (void)drain();
+            return arc;
+        }
+        if (accepted == cur.nb && have_next) {
+            cur = next;
+            if (cur.nb == 0) {
+                flushed = true;
+                break;
+            }
+            continue;
+        }
+        if (have_next) LSA_CHECK(drain());
+        plan = step_plan(ctx, k);
+        have = c->j < j1 && plan.pipelined;
+        if (have) LSA_CHECK(queue_batch(plan, c->j, !c->pending, 0, &cur));
     }
     if (c->pending) {
-        // the flush: the reduction and the update without a solve make V[:, j1] and column j1 - 1 final, so that the restart,
-        // the Ritz vectors and the next call see what CGS2 leaves
         const int32_t j = c->j;
-        LSA_CHECK(k_dcgs2_step(ctx, k->n, j, k->V, k->n, nullptr, 0, k->Hdev, k->ncv, k->ow.fused, nullptr, nullptr, nullptr));
-        LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, k->Hdev, colb, hipMemcpyDeviceToHost, ctx->stream));
-        LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (!flushed) LSA_CHECK(queue_flush(j, 0, &cur));
+        LSA_CHECK(wait_for(cur));
         c->pending = false;
-        const int what = finish_column(H, j, (const cplx*)host);
+        const int what = finish_column(H, j, (const cplx*)host_of(cur.set));
+        if (what != 0) k->drop_preapply();  // (the apply of a vector that is noise)
         if (what < 0) return arnoldi_nonfinite(ctx, j - 1);
         if (what > 0) *breakdown = j - 1;
     }
@@ -1309,6 +1425,7 @@ static int extend_pipelined(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, Exte
 static int extend_one_step(lsa_ctx* ctx, lsa_krylov* k, const HessView& H, int32_t j, int32_t j1, int32_t* breakdown) {
     const size_t vb = (size_t)k->n * 16;
     k->t_for = -1;
+    if (j < j1) k->drop_preapply();
     for (; j < j1; ++j) {
         const void* vj = (char*)k->V + (size_t)j * vb;
         void* vn = (char*)k->V + (size_t)(j + 1) * vb;
@@ -1339,13 +1456,39 @@ int lsa_krylov_extend(lsa_ctx* ctx, lsa_krylov* k, int32_t j0, int32_t j1, void*
     const HessView Hv{(cplx*)H, ldh, j0, k->ncv};
     ExtendCursor c{j0, false};
     int32_t bd = -1;
+    if (k->pre_for != j0 || j0 >= j1) k->drop_preapply();  // (an apply queued ahead is this call's first step's, or nobody's)
     const int rc = extend_rest(ctx, k, Hv, &c, j1, &bd);
+    k->pre_for = -1;
     if (breakdown) *breakdown = bd;
     k->op->st.seconds_solve += now_s() - t0;
     return rc;
 }
 
 }  // extern "C"
+
+// ---- what the solve loop (KsState, dense.hip) asks for besides the public calls ------------------------------------------------------
+void krylov_arm_preapply(lsa_krylov* k, bool on) { k->pre_armed = on && krylov_switches().preapply; }
+
+int krylov_preapply(lsa_ctx* ctx, lsa_krylov* k, int32_t m) { return k->pre_armed ? preapply_enqueue(ctx, k, m) : (int)LSA_OK; }
+
+// The restart of lsa_krylov_restart; queued: everything behind it is stream-ordered, so nothing waits here (the next read-back
+// reports a failure).  Not where the next expansion may go one step at a time: GMRES fills the pinned buffer from the host while
+// the copy of Q out of it would still be in flight.
+static int krylov_restart_impl(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t knew, const void* Q, int32_t ldq, bool queued) {
+    const size_t vb = (size_t)k->n * 16;
+    const int32_t ahead = k->pre_col == m && k->pre_op == k->op ? knew : -1;
+    k->drop_preapply();
+    if (knew > 0) LSA_CHECK(basis_times_host_matrix(ctx, LSA_C128, k->n, m, knew, k->V, Q, ldq, k->qdev, k->V2, 0));
+    LSA_CHECK(k_copy(ctx, LSA_C128, k->n, (char*)k->V + (size_t)m * vb, (char*)k->V2 + (size_t)knew * vb));
+    if (!queued) LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    std::swap(k->V, k->V2);
+    k->pre_for = ahead;
+    return LSA_OK;
+}
+
+int krylov_restart_queued(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t knew, const void* Q, int32_t ldq) {
+    return krylov_restart_impl(ctx, k, m, knew, Q, ldq, krylov_switches().preapply && step_plan(ctx, k).pipelined);
+}
 
 // ---- lockstep expansion of a group (lsa_krylov_solve_batch, dense.hip) ---------------------------------------------------------
 // Problems whose plan is the pipelined DCGS2 tail form on factors of one analysis advance together: a round queues one step of
@@ -1415,6 +1558,7 @@ int krylov_extend_batch(lsa_ctx* ctx, KrylovGroupBuf* gb, lsa_krylov* const* ks,
         status[z] = LSA_OK;
         mem[z] = Member{ExtendCursor{j0[z], false}, HessView{(cplx*)Hs[z], ldh, j0[z], ks[z]->ncv}, true, 0};
         ks[z]->t_for = -1;  // (op->t is anybody's between calls)
+        ks[z]->drop_preapply();
     }
     const size_t colb = krylov_slot_bytes(ncv);
     const size_t cells = (size_t)J * (size_t)slots;
@@ -1541,12 +1685,7 @@ extern "C" {
 int lsa_krylov_restart(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t knew, const void* Q, int32_t ldq) {
     if (!ctx || !k || !Q) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_restart: null argument");
     if (m < 1 || m > k->ncv || knew < 0 || knew > m || ldq < m) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_restart: bad sizes m=%d knew=%d", m, knew);
-    const size_t vb = (size_t)k->n * 16;
-    if (knew > 0) LSA_CHECK(basis_times_host_matrix(ctx, LSA_C128, k->n, m, knew, k->V, Q, ldq, k->qdev, k->V2, 0));
-    LSA_CHECK(k_copy(ctx, LSA_C128, k->n, (char*)k->V + (size_t)m * vb, (char*)k->V2 + (size_t)knew * vb));
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    std::swap(k->V, k->V2);
-    return LSA_OK;
+    return krylov_restart_impl(ctx, k, m, knew, Q, ldq, false);
 }
 
 int lsa_krylov_ritz_vectors(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t nvec, const void* Y, int32_t ldy, int normalise,
@@ -1555,6 +1694,7 @@ int lsa_krylov_ritz_vectors(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t nvec
     if (m < 1 || m > k->ncv + 1 || nvec < 0 || nvec > k->ncv + 1 || ldy < m) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_krylov_ritz_vectors: bad sizes");
     if (nvec == 0) return LSA_OK;
     const size_t vb = (size_t)k->n * 16;
+    k->drop_preapply();  // (an apply queued ahead of a restart that did not come: the stream still runs it, nothing here reads w)
     // (the pinned scratch keeps room behind the packed Y for the norms of the imaginary parts)
     LSA_CHECK(basis_times_host_matrix(ctx, LSA_C128, k->n, m, nvec, k->V, Y, ldy, k->qdev, k->V2, (size_t)nvec * sizeof(double)));
     k->imag_norms.clear();
@@ -1581,9 +1721,13 @@ int lsa_krylov_ritz_vectors(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t nvec
         LSA_CHECK(k_scatter_rows(ctx, LSA_C128, k->n, nvec, k->row_perm, k->V2, tmp));
         src = tmp;
     }
+    const bool timing = krylov_switches().timing;
+    if (timing) LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (the download alone)
+    const double td = now_s();
     hipError_t e = hipMemcpyAsync(X, src, vb * (size_t)nvec, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return lsa_set_error(ctx, LSA_ERR_HIP, "lsa_krylov_ritz_vectors: download failed: %s", hipGetErrorString(e));
+    if (timing) fprintf(stderr, "[lsa_krylov] %d Ritz vectors of %lld rows downloaded in %.3f ms\n", nvec, (long long)k->n, 1e3 * (now_s() - td));
     for (size_t c = 0; c < k->imag_norms.size(); ++c) k->imag_norms[c] = std::sqrt(((const double*)((const char*)ctx->pinned + (size_t)m * nvec * 16))[c]);
     return LSA_OK;
 }
