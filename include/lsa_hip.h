@@ -93,6 +93,14 @@ int lsa_mat_download_values(lsa_ctx *ctx, const lsa_mat *m, void *host_val);
  * its values: A must outlive it (destroy the result first).  The Python binding keeps A alive for that reason. */
 int lsa_csr_axpby(lsa_ctx *ctx, const lsa_mat *A, const lsa_mat *B, const double alpha[2], const double beta[2],
                   int out_dtype, lsa_mat **out);
+/* W = diag(left) M diag(right) on M's pattern: the windowed mass matrices behind the forcing and response windows of the resolvent
+ * and transient-growth analyses (Q = D M D).  M is real (LSA_F64), square and whole (no shard, no row view); left and right are
+ * host vectors of n doubles in M's row numbering, right == NULL means right = left.  The values are (left[i] * M_ij) * right[j], two
+ * roundings in that order -- the order scipy.sparse.diags(l) @ M @ diags(r) rounds in -- so a window of ones gives M's values bit
+ * for bit.  LIFETIME: like the result of lsa_csr_axpby, out BORROWS M's index arrays, host pattern and the row groups / compressed
+ * indices of its SpMV (8 bytes per entry of its own; lsa_spmv takes the same kernel form for it as for M): M must outlive it.
+ * LSA_ERR_ARG, naming the function, for a complex M, a shard or row view, or a non-finite entry of left or right. */
+int lsa_csr_window(lsa_ctx *ctx, const lsa_mat *M, const double *left, const double *right, lsa_mat **out);
 /* y = A x: MatMult (Solver/eigen2.py:174).  Real matrix with complex vectors is supported. */
 int lsa_spmv(lsa_ctx *ctx, const lsa_mat *A, const lsa_vec *x, lsa_vec *y);
 /* y = A^T x or A^H x (conj != 0) without a second copy of the values: a transposed INDEX (row pointers, rows, positions of the
@@ -486,7 +494,7 @@ int lsa_lanczos_solve(lsa_ctx *ctx, lsa_lanczos *l, const lsa_ks_options *opts, 
  * tridiagonalisation + implicit QL.  LSA_ERR_DIVERGED if the QL iteration stalls. */
 int lsa_dense_syev(int32_t n, double *A, int32_t lda, double *w);
 
-/* ---- resolvent (input-output) analysis: optimal gains, responses and forcings of M q' = A q + M f at a real frequency omega -------
+/* ---- resolvent (input-output) analysis: optimal gains, responses and forcings of M q' = A q + M f at a frequency omega -------------
  * With R = (i omega M - A)^-1 the gains sigma_1 >= sigma_2 >= ... are the maxima of ||q||_M / ||f||_M over q = R M f; sigma_j^2
  * are the largest eigenvalues of W = R M R^H M = C^-1 M C^-H M, C = A - i omega M, which is self-adjoint and non-negative in the
  * M-(semi-)inner product.  The iteration is the thick-restart Lanczos of lsa_lanczos_* with a complex basis, V^H M V = I, and the
@@ -504,7 +512,18 @@ int lsa_resolvent_set_row_permutation(lsa_ctx *ctx, lsa_resolvent *r, const int3
  * the columns finish one by one with the refinement step.  Gains, forcings and the solve counts are those of the default (off),
  * bit for bit.  The block's 2 nvec work vectors are made by the first such call; where they do not fit, the columns run one by one. */
 int lsa_resolvent_set_block_forcings(lsa_ctx *ctx, lsa_resolvent *r, int on);
-/* v_0 = v / sqrt(v^H M v) (host complex vector of length n), M-normalised on the device; LSA_ERR_ARG when v^H M v is not positive */
+/* Forcing weight Qf and response weight Qq in place of M (NULL: M): real symmetric positive semidefinite n x n matrices of any
+ * pattern, e.g. the windowed D M D of lsa_csr_window.  The response is q = R Qf f (the weak form: the forcing enters through its own
+ * mass matrix), the gains are the maxima of ||q||_Qq / ||f||_Qf, and sigma_j^2 are the non-zero eigenvalues of
+ * W = C^-1 Qf C^-H Qq, self-adjoint in the Qq-semi-inner product: no inverse of a weight appears and a step has the launches it had
+ * (rhs = Qq v, tm = Qf z, t = Qq w).  The basis and the responses are Qq-orthonormal, the forcings f_j = -C^-H Qq q_j / sigma_j are
+ * Qf-orthonormal (only Qf f_j is determined).  The matrices are BORROWED: they must outlive the handle.  The call begins anew as
+ * lsa_growth_set_steps does: no right-hand side is left over, and lsa_resolvent_set_start (or lsa_resolvent_solve) must follow.
+ * With no weights set every call returns the bits it returned before weights existed.  LSA_ERR_ARG, naming the function, for a
+ * complex matrix or one of another size. */
+int lsa_resolvent_set_weights(lsa_ctx *ctx, lsa_resolvent *r, const lsa_mat *Qf, const lsa_mat *Qq);
+/* v_0 = v / sqrt(v^H Qq v) (host complex vector of length n; Qq = M unless lsa_resolvent_set_weights gave another), normalised on
+ * the device; LSA_ERR_ARG when v^H Qq v is not positive */
 int lsa_resolvent_set_start(lsa_ctx *ctx, lsa_resolvent *r, const void *host_v);
 /* Lanczos steps j = j0 .. j1-1 on W: z = C^-H M v_j, w = C^-1 M z, two passes of classical Gram-Schmidt against v_0..v_j in the
  * M-inner product, v_{j+1} = w / beta_j.  T is the caller's (ncv+1) x ncv column-major REAL matrix (ldt >= j1 + 1), written as by
@@ -521,7 +540,9 @@ int lsa_resolvent_basis(lsa_ctx *ctx, const lsa_resolvent *r, int32_t ncols, voi
  * F_out the forcings f_j = R^H M q_j / sigma_j (same shape, f_j^H M f_k = delta_jk, R M f_j = sigma_j q_j; one checked adjoint
  * solve each after convergence; needs Q_out; NULL: none), est_out[max_out].  counts (NULL or 4 entries): accepted adjoint and
  * forward solves of this handle so far, and how many of each carried the refinement step.  Returns LSA_OK also when fewer than nev
- * gains converged (see result). */
+ * gains converged (see result).  Under lsa_resolvent_set_weights read Qq for M in Q_out's norms and Qf in F_out's, and R Qf f_j =
+ * sigma_j q_j.  The shift of the operator may be any complex number: sigma = (beta, omega) gives the discounted resolvent
+ * ((beta + i omega) M - A)^-1, and 1 / sigma_1 at a point z is the epsilon-level of the energy-norm pseudospectrum there. */
 int lsa_resolvent_solve(lsa_ctx *ctx, lsa_resolvent *r, const lsa_ks_options *opts, const void *v0, int32_t max_out, double *theta_out,
                         double *gain_out, void *Q_out, void *F_out, double *est_out, lsa_ks_result *result, int64_t *counts);
 
@@ -554,6 +575,17 @@ int lsa_growth_set_steps(lsa_ctx *ctx, lsa_growth *g, int32_t nsteps);
  * gives the bytes a new handle set to this scheme gives.  LSA_ERR_ARG, naming the scheme, for any other code. */
 enum { LSA_GROWTH_EULER = 0, LSA_GROWTH_SDIRK2 = 1 };
 int lsa_growth_set_scheme(lsa_ctx *ctx, lsa_growth *g, int32_t scheme);
+/* Response weight Q (NULL: M; real symmetric positive semidefinite, n x n, any pattern; BORROWED: it outlives the handle): the gains
+ * become the maxima of ||q(T)||_Q^2 / ||q(0)||_M^2, the largest eigenvalues of W = M^-1 Phi^T Q Phi.  No inverse appears: the march of a
+ * step turns around on -sigma keep (.) (Q x) instead of -sigma keep (.) (M x) after its last forward solve (index N - 1, N = stages *
+ * nsteps; log entry N - 1 then holds the windowed energy at T); nothing else in the march changes, under either scheme.  The basis
+ * and the initial conditions stay M-orthonormal.  Begins anew like lsa_growth_set_scheme.  LSA_ERR_ARG, naming the function, for a
+ * complex matrix or one of another size.  (An initial-condition weight would need Q^-1 and is not built.) */
+int lsa_growth_set_response_weight(lsa_ctx *ctx, lsa_growth *g, const lsa_mat *Q);
+/* out[j] = (Phi q0_j)^T Q (Phi q0_j), j < nvec, of the responses the last lsa_growth_solve marched (one more product and dot per mode
+ * in its final marches); with no response weight the M-energy at T, energy_out[j (N + 1) + N].  LSA_ERR_ARG when nvec exceeds what
+ * that call marched. */
+int lsa_growth_response_energy(lsa_ctx *ctx, const lsa_growth *g, int32_t nvec, double *out);
 /* v_0 = keep (.) v, M-normalised on the device (host vector of length n); LSA_ERR_ARG when its M-norm is not positive */
 int lsa_growth_set_start(lsa_ctx *ctx, lsa_growth *g, const double *host_v);
 /* Lanczos steps j = j0 .. j1-1 on W: N forward and N transposed solves, each followed by a product with M, the mask and the factor
@@ -571,7 +603,9 @@ int lsa_growth_basis(lsa_ctx *ctx, const lsa_growth *g, int32_t ncols, double *h
  * responses Phi q0_j, not normalised (same shape; needs Q0_out; NULL: none); energy_out[j (N + 1) + s] = ||Phi_s q0_j||_M^2 for
  * s = 0..N (needs Q0_out; NULL: none) -- responses and energies from one more forward march of N checked solves per vector;
  * est_out[max_out].  counts (NULL or 4 entries): accepted forward and transposed solves of this handle so far, and how many of
- * each carried the refinement step.  Returns LSA_OK also when fewer than nev gains converged (see result). */
+ * each carried the refinement step.  Returns LSA_OK also when fewer than nev gains converged (see result).  Under a response weight
+ * (lsa_growth_set_response_weight) gain_out holds the weighted gains, energy_out stays the whole-domain M-energy curve, and
+ * lsa_growth_response_energy gives the weighted energy at T. */
 int lsa_growth_solve(lsa_ctx *ctx, lsa_growth *g, const lsa_ks_options *opts, const double *v0, int32_t max_out, double *theta_out,
                      double *gain_out, double *Q0_out, double *QT_out, double *energy_out, double *est_out, lsa_ks_result *result,
                      int64_t *counts);

@@ -20,8 +20,12 @@ flow; unmasked, each is a spurious "gain" ``(1 - dt)^(-2 N)``.  ``constrained="a
 Implicit Euler is first order in ``dt``: at a ``dt`` of a quarter time unit its gains are a quarter low.  ``scheme="sdirk2"`` marches
 by the L-stable, stiffly accurate two-stage SDIRK method with ``gamma = 1 - 1/sqrt(2)`` instead, second order in ``dt``: both stages
 solve with ``M - gamma dt A``, so ``sigma = 1 / (gamma dt)`` and there is still ONE factorisation; with ``S = -sigma C^-1 M`` one time step
-is ``S (a S + b I)``, ``a = 1 + sqrt(2)``, ``b = -sqrt(2)``, and every step of the iteration marches ``4 N`` solves.  Other energy
-weights, regional masks, higher-order schemes and lockstep over horizons are not built.
+is ``S (a S + b I)``, ``a = 1 + sqrt(2)``, ``b = -sqrt(2)``, and every step of the iteration marches ``4 N`` solves.
+
+The response can be measured in another weight, ``G = max ||q(T)||_Q^2 / ||q(0)||_M^2``: ``response_window=d`` (``n`` non-negative dof
+weights, ``Q = D M D``: the energy inside a region, of one velocity component, ...) or ``response_weight=Q`` (a real symmetric positive
+semidefinite matrix).  Only the turn of a step's march changes.  Weights on the initial condition need ``Q^-1`` and are not built, nor
+are higher-order schemes and lockstep over horizons.
 """
 
 from __future__ import annotations
@@ -34,6 +38,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from .eigen import _require_matching_squares, _wrap
+from .resolvent import checked_side, device_weight, shared_pattern
 from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType, symmetry_defect, _SYMMETRY_TOL
 
 logger = logging.getLogger(__name__)
@@ -69,6 +74,8 @@ class TransientGrowthResult:
     estimates: np.ndarray  # relative residual estimates of G_j
     stats: dict = field(default_factory=dict)
     scheme: str = "euler"  # the time stepping the gains belong to (steps, dt and times count time steps, not stages)
+    # k values ||Phi q0_j||_Q^2, the energy at T in the response weight (equal to gains, as ||q0_j||_M = 1); energy stays the M-energy
+    response_energy: np.ndarray | None = None
 
 
 def decoupled_dofs(A, M) -> np.ndarray:
@@ -104,7 +111,7 @@ class TransientGrowthSolver:
 
     def __init__(self, A, M, cfg: TransientGrowthConfig, *, constrained="auto", device: int = 0, layout: str = "single",
                  pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
-                 ksp_rtol: float | None = None) -> None:
+                 ksp_rtol: float | None = None, response_window=None, response_weight=None) -> None:
         if A is None:
             raise ValueError("Operator A is required.")
         if M is None:
@@ -119,6 +126,8 @@ class TransientGrowthSolver:
         defect = symmetry_defect(Ms)
         if not defect <= _SYMMETRY_TOL:
             raise ValueError(f"Transient growth needs a symmetric M; its relative symmetry defect is {defect:.3e}")
+        # the response weight: a window (Q = D M D) or a matrix, checked here and built on the device with the basis
+        self._response = checked_side("response", response_window, response_weight, Ms)
         self._cfg = cfg
         if not (np.isfinite(cfg.dt) and cfg.dt > 0.0):
             raise ValueError(f"dt = {cfg.dt!r} must be a positive time step")
@@ -190,6 +199,9 @@ class TransientGrowthSolver:
             keep[self._constrained] = 0.0
             basis = lsa_hip.GrowthBasis(prep["ctx"], op, run["ncv"], steps, keep[prep["perm"]], self._cfg.scheme)  # (the iteration runs in permuted numbering)
             basis.set_row_permutation(prep["perm"])
+            if self._response is not None:
+                pattern = shared_pattern(eps._A.as_scipy_array(), eps._M.as_scipy_array()) if self._response[0] == "weight" else None
+                basis.set_response_weight(device_weight(prep, self._response, pattern))
         except BaseException:
             run.clear()
             raise
@@ -220,12 +232,12 @@ class TransientGrowthSolver:
         stats = {"applies": out["applies"], "restarts": out["restarts"], "nconv": out["nconv"], "forward_solves": out["forward_solves"],
                  "transposed_solves": out["transposed_solves"], "refinements": out["refined_forward"] + out["refined_transposed"],
                  "refined_forward": out["refined_forward"], "refined_transposed": out["refined_transposed"], "factorisation_reused": reused,
-                 "constrained": int(self._constrained.size), "max_rel_res": st.get("max_rel_res"), "basis_bytes": basis.basis_bytes,
+                 "constrained": int(self._constrained.size), "spmv_calls": st.get("spmv_calls"), "max_rel_res": st.get("max_rel_res"), "basis_bytes": basis.basis_bytes,
                  "seconds_factor": st.get("seconds_factor"), "seconds_solve": st.get("seconds_solve") - (before.get("seconds_solve") if reused else 0.0),
                  "seconds_expand": out["seconds_expand"], "seconds_dense": out["seconds_dense"], "seconds_restart": out["seconds_restart"],
                  "seconds_total": time.time() - started}
         return TransientGrowthResult(float(T), steps, cfg.dt, out["gains"], out["initial"][:, :k], out["responses"][:, :k], out["energy"][:k],
-                                     cfg.dt * np.arange(steps + 1), out["estimates"], stats, cfg.scheme)
+                                     cfg.dt * np.arange(steps + 1), out["estimates"], stats, cfg.scheme, out["response_energy"])
 
     def sweep(self, horizons) -> list[TransientGrowthResult]:
         """One result per horizon on ONE factorisation: every horizon after the first changes the number of steps only

@@ -11,8 +11,17 @@ solves of a step on ONE nested-dissection LU of ``A - i omega M`` (``lsa_resolve
     res = rs.solve(0.74)                 # res.gains, res.responses, res.forcings
     curve = rs.sweep([0.2, 0.4, 0.74])   # one context, ordering and LU analysis; a refactorisation per frequency
 
-The inner products are those of ``M`` (real symmetric positive semidefinite: a zero pressure block and identity Dirichlet rows are
-fine).  Other forcing / response weights, restriction masks and lockstep over frequencies are not built.
+By default the inner products are those of ``M`` (real symmetric positive semidefinite: a zero pressure block and identity
+Dirichlet rows are fine).  Forcing and response can be weighted separately, ``sigma = max ||q||_Qq / ||f||_Qf`` over ``q = R Qf f``::
+
+    inside = (x >= -3) & (x <= 3)                                  # a window: n non-negative dof weights, 0/1 or smooth
+    rs = ResolventSolver(A, M, cfg, forcing_window=inside, response_window=(x >= 2).astype(float))   # Q = D M D
+    rs = ResolventSolver(A, M, cfg, response_weight=Q)             # or any real symmetric positive semidefinite matrix
+
+``discount=beta`` shifts to ``((beta + i omega) M - A)^-1``, the discounted resolvent for an unstable base flow (``beta`` above the
+largest growth rate), and :meth:`ResolventSolver.norm_map` returns ``sigma_1(z)`` over complex points ``z``: ``1 / sigma_1`` is the
+epsilon-level of the energy-norm pseudospectrum.  Windows that project the operator, complex Hermitian weights, lockstep over
+frequencies or map points and several ranks are not built.
 """
 
 from __future__ import annotations
@@ -23,9 +32,10 @@ import time
 from dataclasses import dataclass, field
 
 import numpy as np
+import scipy.sparse as sp
 
 from .eigen import _require_matching_squares, _wrap
-from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType, symmetry_defect, _SYMMETRY_TOL
+from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType, symmetry_defect, _onto_pattern, _permute, _SYMMETRY_TOL
 
 logger = logging.getLogger(__name__)
 
@@ -40,12 +50,16 @@ class ResolventConfig:
 
 @dataclass
 class ResolventResult:
+    """``Qq`` and ``Qf`` below are the response and forcing weights of the solver (``D M D`` for a window ``D``); both are ``M``
+    where none was given."""
+
     omega: float
-    gains: np.ndarray  # sigma_j, descending
-    responses: np.ndarray  # n x k complex, q_j^H M q_k = delta_jk, the entry of largest magnitude real positive
-    forcings: np.ndarray | None  # n x k complex, f_j^H M f_k = delta_jk, R M f_j = sigma_j q_j (only M f_j is determined)
+    gains: np.ndarray  # sigma_j = ||q_j||_Qq / ||f_j||_Qf, descending
+    responses: np.ndarray  # n x k complex, q_j^H Qq q_k = delta_jk, the entry of largest magnitude real positive
+    forcings: np.ndarray | None  # n x k complex, f_j^H Qf f_k = delta_jk, R Qf f_j = sigma_j q_j (only Qf f_j is determined)
     estimates: np.ndarray  # relative residual estimates of sigma_j^2
     stats: dict = field(default_factory=dict)
+    discount: float = 0.0  # beta of the shift beta + i omega: R = ((beta + i omega) M - A)^-1
 
 
 def _real_frequency(omega) -> float:
@@ -59,13 +73,105 @@ def _real_frequency(omega) -> float:
     return float(z.real)
 
 
+def _real_discount(beta) -> float:
+    """``beta`` as a float; ``ValueError`` unless it is a finite real number."""
+    try:
+        z = complex(beta)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"discount must be a real number, got {beta!r}") from exc
+    if z.imag != 0.0 or not math.isfinite(z.real):
+        raise ValueError(f"discount must be a finite real number, got {beta!r}")
+    return float(z.real)
+
+
+def checked_window(name: str, window, Ms) -> np.ndarray:
+    """The window ``name`` as ``n`` float64 dof weights; ``ValueError`` unless it is a real array of ``n`` non-negative finite entries
+    under which ``D M D`` keeps a positive diagonal entry (some mass inside).  Pure host work."""
+    n = Ms.shape[0]
+    d = np.asarray(window)
+    if d.dtype.kind == "c":
+        raise ValueError(f"{name} has complex entries: a window is a real array of non-negative dof weights")
+    if d.dtype.kind not in "fiub":
+        raise ValueError(f"{name} must be a real array of dof weights, got dtype {d.dtype}")
+    if d.shape != (n,):
+        raise ValueError(f"{name} must have shape ({n},), got {d.shape}")
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    if not np.isfinite(d).all():
+        raise ValueError(f"{name} has NaN or infinite entries")
+    if (d < 0.0).any():
+        raise ValueError(f"{name} has negative entries: a window is non-negative")
+    if not ((d * Ms.diagonal()) * d > 0.0).any():
+        raise ValueError(f"{name} leaves no mass inside: D M D has no positive diagonal entry")
+    return d
+
+
+def checked_weight(name: str, weight, n: int):
+    """The weight ``name`` as a float64 CSR matrix; ``ValueError`` unless it is real, ``n x n``, finite and symmetric (the rule ``M``
+    is held to).  Pure host work."""
+    Q = _wrap(weight).as_scipy_array()
+    if Q.shape != (n, n):
+        raise ValueError(f"{name} must have shape ({n}, {n}), got {Q.shape}")
+    if Q.dtype.kind == "c":
+        raise ValueError(f"{name} is complex: a weight is a real symmetric positive semidefinite matrix")
+    Q = sp.csr_matrix(Q, dtype=np.float64)
+    Q.sum_duplicates()  # (also sorts the indices: one entry per position, as the upload wants them)
+    if not np.isfinite(Q.data).all():
+        raise ValueError(f"{name} has NaN or infinite entries")
+    defect = symmetry_defect(Q)
+    if not defect <= _SYMMETRY_TOL:
+        raise ValueError(f"{name} must be symmetric; its relative symmetry defect is {defect:.3e}")
+    return Q
+
+
+def checked_side(side: str, window, weight, Ms):
+    """One side's weighting as given to a front end: ``None`` (``M``), ``("window", d)`` or ``("weight", Q)``; a window and a weight
+    for the same side is a ``ValueError``."""
+    if window is not None and weight is not None:
+        raise ValueError(f"{side}_window and {side}_weight are both given: one side takes a window or a weight, not both")
+    if window is not None:
+        return "window", checked_window(f"{side}_window", window, Ms)
+    if weight is not None:
+        return "weight", checked_weight(f"{side}_weight", weight, Ms.shape[0])
+    return None
+
+
+def shared_pattern(A, M):
+    """The pattern the prepared device pair ``(A, M)`` stands on, as a CSR matrix of ones: the union of both (``iEpsSolver.prepare``)."""
+    ones = lambda X: sp.csr_matrix((np.ones(X.nnz), X.indices, X.indptr), shape=X.shape)  # noqa: E731
+    union = (ones(sp.csr_matrix(A)) + ones(sp.csr_matrix(M))).tocsr()
+    union.sort_indices()
+    return union
+
+
+def device_weight(prep: dict, spec, pattern=None):
+    """The device matrix of a checked side on the prepared, permuted numbering: ``D M D`` by ``CsrMatrix.windowed`` on the prepared
+    ``M`` for a window, an upload of the permuted matrix for a weight, ``None`` for ``M`` itself.  A weight whose entries all lie on
+    ``pattern`` (:func:`shared_pattern`) is uploaded on that pattern, explicit zeros included: its products then run in the kernel form
+    and summation order of ``M``'s, and ``weight = M`` gives the bits of no weight."""
+    import lsa_hip
+
+    if spec is None:
+        return None
+    kind, what = spec
+    perm = prep["perm"]
+    if kind == "window":
+        return prep["dM"].windowed(what[perm])
+    if pattern is not None:
+        mine = sp.csr_matrix((np.ones(what.nnz), what.indices, what.indptr), shape=what.shape)
+        if (pattern + mine).nnz == pattern.nnz:
+            what = _onto_pattern(what, pattern)
+    return lsa_hip.CsrMatrix.from_scipy(prep["ctx"], _permute(what, perm))
+
+
 class ResolventSolver:
-    """Optimal gains of ``(A, M)`` at real frequencies; thin shell around :class:`iEpsSolver` 's preparation (union pattern,
+    """Optimal gains of ``(A, M)`` at real frequencies (``discount``: at ``beta + i omega``), with optional forcing and response
+    windows or weights; thin shell around :class:`iEpsSolver` 's preparation (union pattern,
     nested-dissection ordering, permuted numbering, upload, pattern-only LU analysis) and ``lsa_hip.ResolventBasis``."""
 
     def __init__(self, A, M, cfg: ResolventConfig | None = None, *, device: int = 0, layout: str = "single",
                  pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
-                 ksp_rtol: float | None = None, block_forcings: bool = False) -> None:
+                 ksp_rtol: float | None = None, block_forcings: bool = False, forcing_window=None, response_window=None,
+                 forcing_weight=None, response_weight=None, discount: float = 0.0) -> None:
         if A is None:
             raise ValueError("Operator A is required.")
         if M is None:
@@ -78,6 +184,11 @@ class ResolventSolver:
         defect = symmetry_defect(Ms)
         if not defect <= _SYMMETRY_TOL:
             raise ValueError(f"Resolvent analysis needs a symmetric M; its relative symmetry defect is {defect:.3e}")
+        # forcing and response weights: a window D (n non-negative dof weights in the caller's numbering: Q = D M D) or a real
+        # symmetric positive semidefinite matrix per side; checked here, built on the device once per preparation
+        self._sides = (checked_side("forcing", forcing_window, forcing_weight, Ms), checked_side("response", response_window, response_weight, Ms))
+        self._discount = _real_discount(discount)
+        self.last_map_stats: list[dict] = []
         self._cfg = cfg if cfg is not None else ResolventConfig()
         if self._cfg.num_modes < 1:
             raise ValueError("num_modes must be at least 1")
@@ -109,32 +220,46 @@ class ResolventSolver:
         """The eigen path's solver object whose preparation this one shares (``prepare()``, ``release()``)."""
         return self._eps
 
-    def solve(self, omega: float, forcings: bool = True) -> ResolventResult:
-        """Gains, responses and (``forcings=True``) forcings at ``omega``: factorises ``A - i omega M`` (``omega = 0``: real factors)
-        and iterates.  A second call on the same solver keeps the context, the ordering and the LU analysis."""
+    def _weights_on_device(self, prep: dict):
+        """(Qf, Qq) as device matrices (``None``: ``M``), built once per preparation and kept with it."""
+        built = prep.get("resolvent_weights")
+        if built is None:
+            eps = self._eps
+            needs = any(spec is not None and spec[0] == "weight" for spec in self._sides)
+            pattern = shared_pattern(eps._A.as_scipy_array(), eps._M.as_scipy_array()) if needs else None
+            built = prep["resolvent_weights"] = tuple(device_weight(prep, spec, pattern) for spec in self._sides)
+        return built
+
+    def _iterate(self, shift: complex, nev: int, forcings: bool, warm=None):
+        """The iteration at one complex shift: factorises ``A - shift M`` (a real shift: real factors) and runs ``nev`` modes.
+        ``warm``: a start vector in the caller's numbering instead of the default one.  Returns the library's output and the
+        statistics of the solve."""
         import lsa_hip
 
-        omega = _real_frequency(omega)
         eps, cfg = self._eps, self._cfg
         started = time.time()
-        eps.set_target(complex(0.0, omega))
+        before = getattr(eps, "_prepared", None)
+        eps.set_target(shift)
         run = eps._open(basis=False)
-        nev, basis = run["nev"], None
+        basis = None
         try:
             prep, op = eps._prepared, run["op"]
+            prepared_anew = prep is not before  # (the first solve, or a change between real and complex factors)
             if prep["pc_code"] != 2 or op.stats().get("pc_fallback"):
                 raise NotImplementedError("Resolvent analysis needs the exact LU; it does not fit the device memory")
             basis = lsa_hip.ResolventBasis(prep["ctx"], op, run["ncv"])
             basis.set_row_permutation(prep["perm"])
             if self._block_forcings:
                 basis.set_block_forcings(True)
-            out = basis.solve(nev, cfg.atol, cfg.max_it, v0=eps._start_vector(basis.n), seed=self._seed, max_out=nev, forcings=forcings)
+            if any(spec is not None for spec in self._sides):
+                basis.set_weights(*self._weights_on_device(prep))
+            v0 = eps._start_vector(basis.n) if warm is None else np.asarray(warm, dtype=np.complex128)[prep["perm"]]
+            out = basis.solve(nev, cfg.atol, cfg.max_it, v0=v0, seed=self._seed, max_out=nev, forcings=forcings)
             st = op.stats()
             basis_bytes = basis.basis_bytes
         finally:
             del basis  # (the basis goes before its operator)
             run.clear()
-        k = len(out["gains"])
         if out["nconv"] < nev:
             logger.warning("Resolvent: %d of %d gains converged in %d restarts (next estimate %.3e)", out["nconv"], nev, out["restarts"],
                            out["next_unconverged"])
@@ -142,16 +267,64 @@ class ResolventSolver:
                  "forward_solves": out["forward_solves"], "refinements": out["refined_adjoint"] + out["refined_forward"],
                  "refined_adjoint": out["refined_adjoint"], "refined_forward": out["refined_forward"],
                  "analysis_reused": bool(st.get("analysis_reused")), "max_rel_res": st.get("max_rel_res"), "basis_bytes": basis_bytes,
+                 "spmv_calls": st.get("spmv_calls"), "prepared_anew": prepared_anew,
                  "seconds_factor": st.get("seconds_factor"), "seconds_solve": st.get("seconds_solve"), "seconds_expand": out["seconds_expand"],
                  "seconds_dense": out["seconds_dense"], "seconds_restart": out["seconds_restart"], "seconds_total": time.time() - started}
-        return ResolventResult(omega, out["gains"], out["responses"][:, :k], out["forcings"], out["estimates"], stats)
+        return out, stats
+
+    def solve(self, omega: float, forcings: bool = True, discount: float | None = None) -> ResolventResult:
+        """Gains, responses and (``forcings=True``) forcings at the real frequency ``omega``: factorises ``A - (beta + i omega) M``
+        with ``beta = discount`` (``None``: the solver's; a real shift, ``omega = 0`` at any ``beta``, runs on real factors) and
+        iterates.  The responses are orthonormal in the response weight, ``q_j^H Qq q_k = delta_jk``, the forcings in the forcing
+        weight, ``f_j^H Qf f_k = delta_jk``, with ``R Qf f_j = sigma_j q_j`` and ``R = ((beta + i omega) M - A)^-1``; both weights are
+        ``M`` where the solver was given none.  A second call on the same solver keeps the context, the ordering, the LU analysis
+        and the weights on the device."""
+        omega = _real_frequency(omega)
+        beta = self._discount if discount is None else _real_discount(discount)
+        nev = self._cfg.num_modes
+        out, stats = self._iterate(complex(beta, omega), nev, forcings)
+        k = len(out["gains"])
+        return ResolventResult(omega, out["gains"], out["responses"][:, :k], out["forcings"], out["estimates"], stats, beta)
 
     def sweep(self, omegas, forcings: bool = True) -> list[ResolventResult]:
         """One result per frequency on ONE context, ordering and LU analysis: every frequency after the first refactorises only
-        (``stats["analysis_reused"]``), and returns the bytes a fresh solver gives for it.  (Going between ``omega = 0`` and a
-        non-zero one changes the factors' scalar type and prepares anew.)"""
+        (``stats["analysis_reused"]``), and returns the bytes a fresh solver gives for it.  (Going between a real shift -- ``omega = 0``
+        -- and a complex one changes the factors' scalar type and prepares anew.)"""
         omegas = [_real_frequency(w) for w in omegas]
         return [self.solve(w, forcings=forcings) for w in omegas]
+
+    @staticmethod
+    def map_order(points) -> list[int]:
+        """The order in which :meth:`norm_map` visits its points: those off the real axis in the order given, then the real ones
+        (real factors: one group, so the analysis is prepared at most twice)."""
+        z = np.asarray(points, dtype=np.complex128).ravel()
+        return [i for i in range(z.size) if z[i].imag != 0.0] + [i for i in range(z.size) if z[i].imag == 0.0]
+
+    def _gain_at(self, z: complex, warm):
+        """(sigma_1, response, stats) at one point of :meth:`norm_map`."""
+        out, stats = self._iterate(complex(z), 1, False, warm)
+        if len(out["gains"]) < 1:
+            raise RuntimeError(f"norm_map: sigma_1 at z = {z!r} did not converge in {out['restarts']} restarts")
+        return float(out["gains"][0]), out["responses"][:, 0], stats
+
+    def norm_map(self, points, warm_start: bool = True) -> np.ndarray:
+        """``sigma_1(z_k)`` of the (possibly weighted) resolvent ``(z_k M - A)^-1`` at complex points ``z_k``, in the shape of
+        ``points``: ``1 / sigma_1`` is the epsilon-level of the energy-norm pseudospectrum.  One mode, no forcings, one context,
+        ordering and analysis; the real points are visited as one group (:meth:`map_order`).  ``warm_start``: the start vector of a
+        point is the previous point's response.  The statistics of every point, in the order given, are left in
+        ``self.last_map_stats``."""
+        z = np.asarray(points, dtype=np.complex128)
+        flat = z.ravel()
+        if not np.isfinite(flat).all():
+            raise ValueError("norm_map: the points must be finite complex numbers")
+        gains = np.zeros(flat.size)
+        stats: list = [None] * flat.size
+        warm = None
+        for i in self.map_order(flat):
+            gains[i], response, stats[i] = self._gain_at(complex(flat[i]), warm if warm_start else None)
+            warm = response
+        self.last_map_stats = stats
+        return gains.reshape(z.shape)
 
     def release(self) -> None:
         self._eps.release()

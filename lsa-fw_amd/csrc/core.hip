@@ -1,4 +1,7 @@
 // Context, device vectors and CSR matrices of liblsa_hip.so.
+#include <algorithm>
+#include <cmath>
+
 #include "lsa_internal.h"
 
 int lsa_set_error(lsa_ctx* ctx, int code, const char* fmt, ...) {
@@ -328,5 +331,81 @@ extern "C" int lsa_csr_axpby(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* B, c
         return lsa_set_error(ctx, LSA_ERR_HIP, "axpby launch failed: %s", hipGetErrorString(le));
     }
     *out = C;
+    return LSA_OK;
+}
+
+// ---- W = diag(left) M diag(right) on M's pattern (the forcing and response windows of resolvent.hip and growth.hip) ---------------------
+// out[p] = (left[i] M[p]) right[j] for the entries p of row i, j = ci[p]: two roundings in that order (no addition, so nothing
+// contracts into an fma), the order scipy's diags(l) @ M @ diags(r) rounds in.  A group of kWindowLanes lanes walks a row, the rows
+// strided over the grid: the row of an entry is the group's, found from the row pointers, not searched for.  Runs once per window.
+constexpr int kWindowLanes = 16;
+__global__ __launch_bounds__(256) void window_values_kernel(int32_t n, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                            const double* __restrict__ val, const double* __restrict__ left,
+                                                            const double* __restrict__ right, double* __restrict__ out) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t lane = (int32_t)(gid % kWindowLanes);
+    const int64_t stride = ((int64_t)gridDim.x * blockDim.x) / kWindowLanes;
+    for (int64_t r = gid / kWindowLanes; r < n; r += stride) {
+        const double l = left[r];
+        const int32_t p1 = rp[r + 1];
+        for (int32_t p = rp[r] + lane; p < p1; p += kWindowLanes) {
+            const double lm = l * val[p];
+            out[p] = lm * right[ci[p]];
+        }
+    }
+}
+
+extern "C" int lsa_csr_window(lsa_ctx* ctx, const lsa_mat* M, const double* left, const double* right, lsa_mat** out) {
+    if (!ctx || !M || !left || !out) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_csr_window: null argument");
+    if (M->dtype != LSA_F64) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_csr_window: the matrix is complex: a window weighs a real symmetric matrix");
+    if (M->row0 != 0 || M->n != M->ncols || !M->owns_values)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_csr_window: the matrix is a shard or a row view (%d rows of %d from row %d): whole square matrices only",
+                             M->n, M->ncols, M->row0);
+    const int32_t n = M->n;
+    for (const double* v : {left, right})
+        for (int32_t i = 0; v && i < n; ++i)
+            if (!std::isfinite(v[i]))
+                return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_csr_window: %s[%d] = %.3e is not finite", v == left ? "left" : "right", i, v[i]);
+    lsa_mat* W = new lsa_mat();
+    W->ctx = ctx;
+    W->n = n;
+    W->ncols = M->ncols;
+    W->row0 = 0;
+    W->nnz = M->nnz;
+    W->dtype = LSA_F64;
+    W->rp = M->rp;
+    W->ci = M->ci;
+    W->owns_index = false;
+    W->h_rp = M->h_rp;
+    W->h_ci = M->h_ci;
+    if (!M->h_hash) M->h_hash = std::make_shared<uint64_t>(0);
+    W->h_hash = M->h_hash;
+    if (!M->h_shared) M->h_shared = std::make_shared<PatternShared>();
+    W->h_shared = M->h_shared;
+    W->val = nullptr;
+    spmv_share_extras(M, W);
+    // the two windows side by side in one device buffer, gone with the call
+    double* dwin = nullptr;
+    const size_t wb = (size_t)std::max(n, 1) * sizeof(double);
+    hipError_t e = hipMalloc(&W->val, (size_t)(W->nnz > 0 ? W->nnz : 1) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&dwin, 2 * wb);
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(dwin, left, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(dwin + n, right ? right : left, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && n > 0 && W->nnz > 0) {
+        const int threads = 256;
+        const int64_t want = ((int64_t)n * kWindowLanes + threads - 1) / threads;
+        const int blocks = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+        hipLaunchKernelGGL(window_values_kernel, dim3(blocks), dim3(threads), 0, ctx->stream, n, M->rp, M->ci, (const double*)M->val, (const double*)dwin,
+                           (const double*)(dwin + n), (double*)W->val);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (the host windows and the device copy are free again)
+    if (dwin) (void)hipFree(dwin);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        lsa_mat_destroy(W);
+        return lsa_set_error(ctx, e == hipErrorOutOfMemory ? LSA_ERR_OOM : LSA_ERR_HIP, "lsa_csr_window: %s", hipGetErrorString(e));
+    }
+    *out = W;
     return LSA_OK;
 }

@@ -23,6 +23,13 @@
 //         k even:   b_{k+1} = (-a sigma) keep (.) mx + b b_k            the next solve is the second stage: b_k already is -sigma keep (.) M q
 // b_k is the vector the kernel reads for the residual sum anyway: the combining form costs no load, no buffer and no launch more.
 //
+// lsa_growth_set_response_weight measures the response in a weight Q instead of M: G = max ||q(T)||_Q^2 / ||q(0)||_M^2, the eigenvalues of
+// W = M^-1 Phi^T Q Phi = (C^-T M)^(N-1) C^-T Q Phi up to the -sigma factors, still M-self-adjoint.  The one change is the turn of the
+// march: after the last forward solve (k = N - 1, N = stages * nsteps) mx = Q x instead of M x, for the next right-hand side and for
+// the x^T mx sum (log entry N - 1: the windowed energy at T).  Under SDIRK2 that index is odd, so the transition is the plain one, and
+// the combining transition after the first transposed solve reads that same right-hand side as its b_k.  An initial-condition weight
+// would need Q^-1 and is not built.
+//
 // The sums of tg_march_kernel are taken in the order of k_multi_dot (rows strided over the 256 threads of a chunk of at least 512
 // rows, xor tree over the wavefront, the four waves in wave order; tg_log_kernel: the chunks strided over 64 lanes and the same tree)
 // and there are no floating-point atomics: two runs give the same bits, and LSA_GROWTH_FUSED=0 -- the same step through
@@ -163,6 +170,8 @@ struct lsa_growth {
     int32_t ncv = 0, nsteps = 0, log_cap = 0;
     int32_t scheme = LSA_GROWTH_EULER;  // LSA_GROWTH_SDIRK2: two solves per time step, the second on a combined right-hand side
     double sigma = 0.0;
+    const lsa_mat* Q = nullptr;  // the response weight at the turn of a step's march (lsa_growth_set_response_weight; borrowed), null: M
+    std::vector<double> renergy;  // x(T)^T Q x(T) of the modes the last final marches ran (lsa_growth_response_energy)
     double* keep = nullptr;  // device 0/1 mask, the basis' row numbering
     std::vector<double> hkeep;
     // the march's own vectors: the two right-hand sides it alternates between (the step's rhs stays intact), a solution, C x, M x and
@@ -216,9 +225,10 @@ int tg_reserve_log(lsa_ctx* ctx, lsa_growth* g, int32_t entries) {
     return LSA_OK;
 }
 
-int tg_mass(lsa_ctx* ctx, lsa_growth* g, const double* x, double* y) {
+// y = W x for the weight W: M, or the response weight at the turn
+int tg_mass(lsa_ctx* ctx, lsa_growth* g, const lsa_mat* W, const double* x, double* y) {
     ++g->P.st->spmv_calls;
-    return k_spmv(ctx, g->P.Kmul, LSA_F64, x, y);
+    return k_spmv(ctx, W, LSA_F64, x, y);
 }
 
 int tg_scale(lsa_ctx* ctx, lsa_growth* g, double alpha, const double* x, double* y) {
@@ -232,14 +242,15 @@ int tg_combine(lsa_ctx* ctx, lsa_growth* g, double ca, double cb, const double* 
     return tg_check_launch(ctx, "growth combine");
 }
 
-// What follows the inner solve x of b (z = C x): mx = M x, the next right-hand side -sigma keep (.) mx (next == null: none; combine,
-// with a next: (-a sigma) keep (.) mx + b b, SDIRK2's second stage) and the four sums of log entry k.
-int tg_after_solve(lsa_ctx* ctx, lsa_growth* g, int32_t k, const double* b, const double* z, const double* x, double* next, bool combine) {
+// What follows the inner solve x of b (z = C x): mx = W x (W: M, or the response weight after the last forward solve of a step's
+// march), the next right-hand side -sigma keep (.) mx (next == null: none; combine, with a next: (-a sigma) keep (.) mx + b b, SDIRK2's
+// second stage) and the four sums of log entry k.
+int tg_after_solve(lsa_ctx* ctx, lsa_growth* g, const lsa_mat* W, int32_t k, const double* b, const double* z, const double* x, double* next, bool combine) {
     const int64_t n = g->n;
     combine = combine && next;
     const double ca = kTgA * -g->sigma, cb = kTgB;
     double* out = g->log + (size_t)4 * (size_t)k;
-    LSA_CHECK(tg_mass(ctx, g, x, g->mx));
+    LSA_CHECK(tg_mass(ctx, g, W, x, g->mx));
     if (tg_fused()) {
         // k_multi_dot's chunks: at most 2048 of them, whole multiples of 256 rows, at least 512 rows
         int64_t rows_per_chunk = ((n + kTgMaxChunks - 1) / kTgMaxChunks + kTgThreads - 1) / kTgThreads * kTgThreads;
@@ -317,7 +328,9 @@ int tg_hook_enqueue(lsa_ctx* ctx, void* self, int32_t, const double* rhs, double
         const bool adj = k >= N;
         LSA_CHECK(direct_solve_enqueue(ctx, g->op, LSA_F64, b, g->x, g->cz, g->r, adj ? g->used_adj : g->used_fwd, g->rnorms, adj ? 1 : 0));
         double* next = g->pp[k & 1];
-        LSA_CHECK(tg_after_solve(ctx, g, k, b, g->cz, g->x, next, tg_combines(g, k)));
+        // the turn: the response is measured in Q, so Phi+ begins from -sigma keep (.) Q x(T) (log entry N - 1: the windowed energy at T)
+        const lsa_mat* W = (k == N - 1 && g->Q) ? g->Q : g->P.Kmul;
+        LSA_CHECK(tg_after_solve(ctx, g, W, k, b, g->cz, g->x, next, tg_combines(g, k)));
         b = next;
     }
     // the last solve lands where the default's single solve does; the step's first reduction checks it
@@ -410,23 +423,28 @@ int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, doub
     const double* Q0 = lanczos_ritz_device(g->lz);
     const double t0 = now_s();
     std::vector<TgSolve> sv((size_t)N);
+    g->renergy.assign((size_t)nvec, 0.0);
     for (int32_t c = 0; c < nvec; ++c) {
         const double* q0 = Q0 + (size_t)c * (size_t)n;
         double* e0 = g->log + (size_t)4 * (size_t)N;  // (entry N: q0^T M q0 alone)
         while (true) {
             const bool refine = g->refine_fwd;
-            LSA_CHECK(tg_mass(ctx, g, q0, g->mx));
+            LSA_CHECK(tg_mass(ctx, g, g->P.Kmul, q0, g->mx));
             LSA_CHECK(k_multi_dot(ctx, LSA_F64, n, 1, q0, n, g->mx, e0));
             LSA_CHECK(tg_scale(ctx, g, -g->sigma, g->mx, g->pp[1]));
             const double* b = g->pp[1];
             for (int32_t s = 0; s < N; ++s) {
                 LSA_CHECK(direct_solve_enqueue(ctx, g->op, LSA_F64, b, g->x, g->cz, g->r, refine, g->rnorms, 0));
                 double* next = s + 1 < N ? g->pp[s & 1] : nullptr;
-                LSA_CHECK(tg_after_solve(ctx, g, s, b, g->cz, g->x, next, tg_combines(g, s)));
+                LSA_CHECK(tg_after_solve(ctx, g, g->P.Kmul, s, b, g->cz, g->x, next, tg_combines(g, s)));
                 b = next;
             }
+            if (g->Q) {  // the windowed energy at T behind q0^T M q0: one more product and dot
+                LSA_CHECK(tg_mass(ctx, g, g->Q, g->x, g->mx));
+                LSA_CHECK(k_multi_dot(ctx, LSA_F64, n, 1, g->x, n, g->mx, e0 + 1));
+            }
             LSA_CHECK(k_copy(ctx, LSA_F64, n, g->x, g->resp + (size_t)c * (size_t)n));
-            LSA_HIP_CHECK(ctx, hipMemcpyAsync(g->hlog, g->log, ((size_t)4 * (size_t)N + 1) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            LSA_HIP_CHECK(ctx, hipMemcpyAsync(g->hlog, g->log, ((size_t)4 * (size_t)N + 2) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
             for (int32_t s = 0; s < N; ++s) {
                 const double* e = g->hlog + (size_t)4 * (size_t)s;
@@ -436,6 +454,7 @@ int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, doub
             if (verdict == 0) break;
             if (verdict < 0) return LSA_ERR_DIVERGED;
         }
+        g->renergy[(size_t)c] = g->Q ? g->hlog[(size_t)4 * (size_t)N + 1] : g->hlog[(size_t)4 * (size_t)(N - 1) + 2];
         if (energy) {
             energy[(size_t)c * (size_t)(steps + 1)] = g->hlog[(size_t)4 * (size_t)N];
             for (int32_t s = 0; s < steps; ++s)
@@ -538,6 +557,30 @@ int lsa_growth_set_scheme(lsa_ctx* ctx, lsa_growth* g, int32_t scheme) {
     // as a new horizon: the bytes of a scheme do not depend on what ran before it on these factors
     g->refine_fwd = g->refine_adj = false;
     g->logged = 0;
+    return LSA_OK;
+}
+
+int lsa_growth_set_response_weight(lsa_ctx* ctx, lsa_growth* g, const lsa_mat* Q) {
+    if (!ctx || !g) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_set_response_weight: null argument");
+    if (Q && Q->dtype != LSA_F64)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_set_response_weight: the weight is complex: a weight is real symmetric positive semidefinite");
+    if (Q && (Q->row0 != 0 || (int64_t)Q->n != g->n || (int64_t)Q->ncols != g->n))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_set_response_weight: the weight is %d x %d (from row %d), the problem has size %lld", Q->n, Q->ncols,
+                             Q->row0, (long long)g->n);
+    g->Q = Q;
+    // as a new scheme: the bytes of a weight do not depend on what ran before it on these factors
+    g->refine_fwd = g->refine_adj = false;
+    g->logged = 0;
+    g->renergy.clear();
+    return LSA_OK;
+}
+
+int lsa_growth_response_energy(lsa_ctx* ctx, const lsa_growth* g, int32_t nvec, double* out) {
+    if (!ctx || !g || !out) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_response_energy: null argument");
+    if (nvec < 0 || (size_t)nvec > g->renergy.size())
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_growth_response_energy: %d values asked for, the last lsa_growth_solve marched %d responses", nvec,
+                             (int)g->renergy.size());
+    std::copy(g->renergy.begin(), g->renergy.begin() + nvec, out);
     return LSA_OK;
 }
 

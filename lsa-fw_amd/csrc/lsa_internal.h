@@ -232,6 +232,9 @@ constexpr int kKrylovGroupMax = 16;
 // y = A x                       (spmv.hip)
 int k_spmv(lsa_ctx* ctx, const lsa_mat* A, int xdtype, const void* x, void* y);
 int k_spmv_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, int xdtype, const void* x, void* y);
+// `to` has `from`'s pattern and scalar type (lsa_csr_window): it borrows the row groups and compressed indices k_spmv uses for `from`
+// (built here where `from` has not met a product yet), so that both take one kernel form; owns_extras = false, `from` outlives `to`
+void spmv_share_extras(const lsa_mat* from, lsa_mat* to);
 
 // Block kernels of the region eigensolver (contour.hip): complex128 column-major blocks, column c at c * ld, ld >= n
 // Y[:, 0:ncols] = A X[:, 0:ncols] for a whole square A (f64 or c128), in passes of 8 columns that read A once each; not k_spmv's bits

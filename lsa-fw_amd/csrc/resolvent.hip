@@ -15,6 +15,11 @@
 //     twice:  t = M w;  h = V^H t;  w -= V h    rz_dot_kernel + rz_update_kernel
 //     t = M w;  beta^2 = Re w^H t           rz_dot_kernel on the one extra column
 //     v_{j+1} = w / beta;  rhs' = t / beta  rz_tail_kernel, which leaves beta^2 and both checks' sums in the step's slot
+// lsa_resolvent_set_weights puts a forcing weight Q_f and a response weight Q_q (real symmetric positive semidefinite, e.g. the windowed
+// D M D of lsa_csr_window) where M stands: q = R Q_f f, sigma = max ||q||_Qq / ||f||_Qf, W = C^-1 Q_f C^-H Q_q, self-adjoint in the
+// Q_q-semi-inner product.  No inverse of a weight appears and the step keeps its launches: rhs = Q_q v_j, tm = Q_f z and t = Q_q w
+// (rz_response, rz_forcing) replace the three uses of M; both are M on a new handle, whose bits are those of a handle without weights.
+// Nothing in the step needs Re sigma = 0: a shift beta + i omega gives the discounted resolvent.
 // One host synchronisation per step (the read-back of the slot).  Each direction decides about its own refinement step
 // (direct_solve_enqueue with an explicit direction: the operator's own direction, and the state lsa_op_set_adjoint clears, stay).
 //
@@ -261,6 +266,8 @@ struct lsa_resolvent {
     lsa_op_parts P{};
     int64_t n = 0;
     int32_t ncv = 0;
+    // the forcing and the response weight (lsa_resolvent_set_weights; borrowed): both are the operator's M on a new handle
+    const lsa_mat *Qf = nullptr, *Qq = nullptr;
     // the n x (ncv + 1) arrays: the basis, the restart's second basis (and the Ritz vectors, then the forcings) and, with a row
     // permutation, the output in the caller's numbering (on first use)
     cplx *V = nullptr, *V2 = nullptr, *xtmp = nullptr;
@@ -305,10 +312,16 @@ void rz_free(lsa_resolvent* l) {
 
 cplx* rz_col(const lsa_resolvent* l, int32_t j) { return l->V + (size_t)j * (size_t)l->n; }
 
-// y = M x (M real, complex vectors)
-int rz_mass(lsa_ctx* ctx, lsa_resolvent* l, const cplx* x, cplx* y) {
+// y = Q_q x, the response product (Q_q real, complex vectors; M unless lsa_resolvent_set_weights gave another)
+int rz_response(lsa_ctx* ctx, lsa_resolvent* l, const cplx* x, cplx* y) {
     ++l->P.st->spmv_calls;
-    return k_spmv(ctx, l->P.Kmul, LSA_C128, x, y);
+    return k_spmv(ctx, l->Qq, LSA_C128, x, y);
+}
+
+// y = Q_f x, the forcing product
+int rz_forcing(lsa_ctx* ctx, lsa_resolvent* l, const cplx* x, cplx* y) {
+    ++l->P.st->spmv_calls;
+    return k_spmv(ctx, l->Qf, LSA_C128, x, y);
 }
 
 int rz_grid(lsa_ctx* ctx, int64_t n, int per_cu) {
@@ -333,7 +346,7 @@ int rz_orth_tail(lsa_ctx* ctx, lsa_resolvent* l, int32_t ncols, int32_t target, 
         // every workgroup of the update finishes h for itself: a few hundred of them, their rows strided over the grid
         const int ublocks = rz_grid(ctx, n, 2);
         for (int pass = 0; pass < 2 && ncols > 0; ++pass) {
-            LSA_CHECK(rz_mass(ctx, l, l->w, l->t));
+            LSA_CHECK(rz_response(ctx, l, l->w, l->t));
             const int tiles = (ncols + 1 + kRzColTile - 1) / kRzColTile;
             const bool c = chk && pass == 0;
             hipLaunchKernelGGL(rz_dot_kernel, dim3(nchunks, tiles), dim3(kRzThreads), 0, ctx->stream, n, ncols, rows_per_block, l->V, n, l->t, l->w,
@@ -342,7 +355,7 @@ int rz_orth_tail(lsa_ctx* ctx, lsa_resolvent* l, int32_t ncols, int32_t target, 
             hipLaunchKernelGGL(rz_update_kernel, dim3(ublocks), dim3(kRzThreads), (size_t)ncols * sizeof(cplx), ctx->stream, n, ncols, l->V, n,
                                l->part, nchunks, nchunks, l->w, (cplx*)(l->slot + (size_t)pass * h_doubles));
         }
-        LSA_CHECK(rz_mass(ctx, l, l->w, l->t));
+        LSA_CHECK(rz_response(ctx, l, l->w, l->t));
         const bool c = chk && ncols == 0;
         hipLaunchKernelGGL(rz_dot_kernel, dim3(nchunks, 1), dim3(kRzThreads), 0, ctx->stream, n, 0, rows_per_block, l->V, n, l->t, l->w, l->part, nchunks,
                            c ? l->rhs[l->cur] : nullptr, c ? l->ca : nullptr, c ? l->tm : nullptr, c ? l->cf : nullptr, c ? l->chk_part : nullptr);
@@ -356,12 +369,12 @@ int rz_orth_tail(lsa_ctx* ctx, lsa_resolvent* l, int32_t ncols, int32_t target, 
         LSA_CHECK(k_residual_norms(ctx, LSA_C128, n, l->tm, l->cf, l->r, l->chk_part + 2));
     }
     for (int pass = 0; pass < 2 && ncols > 0; ++pass) {
-        LSA_CHECK(rz_mass(ctx, l, l->w, l->t));
+        LSA_CHECK(rz_response(ctx, l, l->w, l->t));
         double* h = l->slot + (size_t)pass * h_doubles;
         LSA_CHECK(k_multi_dot(ctx, LSA_C128, n, ncols, l->V, n, l->t, h));
         LSA_CHECK(k_multi_axpy(ctx, LSA_C128, n, ncols, l->V, n, h, l->w, nullptr));
     }
-    LSA_CHECK(rz_mass(ctx, l, l->w, l->t));
+    LSA_CHECK(rz_response(ctx, l, l->w, l->t));
     LSA_CHECK(k_multi_dot(ctx, LSA_C128, n, 1, l->w, n, l->t, out + 6));
     hipLaunchKernelGGL(rz_tail_kernel, dim3(tblocks), dim3(kRzThreads), 0, ctx->stream, n, l->w, l->t, (const cplx*)(out + 6), 1, vnext, rhs_next,
                        chk ? l->chk_part : nullptr, 1, out);
@@ -501,7 +514,7 @@ int rz_forcings_block(lsa_ctx* ctx, lsa_resolvent* l, int32_t nvec, const double
         if (!(gain[c] > 0.0) || !std::isfinite(gain[c]))
             return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent forcings: gain %d is %.3e: no forcing belongs to it", c, gain[c]);
     // (a product is counted where its column is accepted: a column the loop takes over forms, and counts, its own)
-    for (int32_t c = 0; c < nvec; ++c) LSA_CHECK(k_spmv(ctx, l->P.Kmul, LSA_C128, l->V2 + (size_t)c * (size_t)n, l->blk_tm + (size_t)c * (size_t)n));
+    for (int32_t c = 0; c < nvec; ++c) LSA_CHECK(k_spmv(ctx, l->Qq, LSA_C128, l->V2 + (size_t)c * (size_t)n, l->blk_tm + (size_t)c * (size_t)n));
     LSA_CHECK(ndlu_solve_multi_adjoint_dev(ctx, l->P.nd, 1, LSA_C128, nvec, l->blk_tm, n, l->blk_za, n));
     for (int32_t c = 0; c < nvec; ++c) {
         const cplx* tm = l->blk_tm + (size_t)c * (size_t)n;
@@ -550,7 +563,7 @@ int resolvent_forcings(lsa_ctx* ctx, lsa_resolvent* l, int32_t nvec, const doubl
         if (!(gain[c] > 0.0) || !std::isfinite(gain[c]))
             return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent forcings: gain %d is %.3e: no forcing belongs to it", c, gain[c]);
         cplx* q = l->V2 + (size_t)c * (size_t)n;
-        LSA_CHECK(rz_mass(ctx, l, q, l->tm));
+        LSA_CHECK(rz_response(ctx, l, q, l->tm));
         while (true) {
             const bool refine = l->refine_adj;
             LSA_CHECK(direct_solve_enqueue(ctx, l->op, LSA_C128, l->tm, l->za, l->ca, l->r, refine, l->rnorms, 1));
@@ -589,7 +602,8 @@ int lsa_resolvent_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, lsa_resolvent** 
     LSA_CHECK(lsa_op_get_parts(op, &P));
     if (!P.shift_invert) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_create: the operator is not shift-invert (mode 0): C = A - i omega M is what gets factorised");
     if (P.adjoint) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_create: the operator is in adjoint mode (lsa_op_set_adjoint): the iteration picks each solve's direction itself");
-    if (P.projected) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_create: the operator is projected (lsa_op_set_projection): restriction masks are not built");
+    if (P.projected) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_create: the operator is projected (lsa_op_set_projection): a projected operator is not built; "
+                                                            "restrict forcing and response with windows instead (lsa_csr_window, lsa_resolvent_set_weights)");
     if (!P.one_rank || ctx->nranks != 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_create: the operator is spread over several ranks: one rank only");
     if (!P.Kmul) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_create: the operator has no M: the gains are measured in the M-inner product");
     if (P.Kmul->dtype != LSA_F64) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_create: M is complex: the M-inner product needs a real symmetric M");
@@ -601,6 +615,7 @@ int lsa_resolvent_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, lsa_resolvent** 
     l->P = P;
     l->n = P.n;
     l->ncv = ncv;
+    l->Qf = l->Qq = P.Kmul;
     l->hslot.assign(rz_slot_doubles(ncv), 0.0);
     const size_t vb = (size_t)std::max<int64_t>(l->n, 1) * sizeof(cplx);
     bool ok = hipMalloc((void**)&l->V, vb * (size_t)(ncv + 1)) == hipSuccess && hipMalloc((void**)&l->V2, vb * (size_t)(ncv + 1)) == hipSuccess;
@@ -637,6 +652,28 @@ int lsa_resolvent_set_block_forcings(lsa_ctx* ctx, lsa_resolvent* l, int on) {
     return LSA_OK;
 }
 
+int lsa_resolvent_set_weights(lsa_ctx* ctx, lsa_resolvent* l, const lsa_mat* Qf, const lsa_mat* Qq) {
+    if (!ctx || !l) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_set_weights: null argument");
+    const lsa_mat* both[2] = {Qf, Qq};
+    for (int k = 0; k < 2; ++k) {
+        const lsa_mat* Q = both[k];
+        const char* which = k == 0 ? "forcing" : "response";
+        if (!Q) continue;
+        if (Q->dtype != LSA_F64)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_set_weights: the %s weight is complex: a weight is real symmetric positive semidefinite", which);
+        if (Q->row0 != 0 || (int64_t)Q->n != l->n || (int64_t)Q->ncols != l->n)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_set_weights: the %s weight is %d x %d (from row %d), the problem has size %lld", which, Q->n,
+                                 Q->ncols, Q->row0, (long long)l->n);
+    }
+    l->Qf = Qf ? Qf : l->P.Kmul;
+    l->Qq = Qq ? Qq : l->P.Kmul;
+    // other inner products begin as a new handle does: no right-hand side is left over, the refinement steps are off again, and a
+    // start vector must follow (the basis in hand is orthonormal in the old response weight)
+    l->rhs_for = -1;
+    l->refine_adj = l->refine_fwd = false;
+    return LSA_OK;
+}
+
 int lsa_resolvent_set_start(lsa_ctx* ctx, lsa_resolvent* l, const void* host_v) { return resolvent_inject(ctx, l, 0, (const cplx*)host_v); }
 
 int lsa_resolvent_extend(lsa_ctx* ctx, lsa_resolvent* l, int32_t j0, int32_t j1, double* T, int32_t ldt, int32_t* breakdown) {
@@ -650,7 +687,7 @@ int lsa_resolvent_extend(lsa_ctx* ctx, lsa_resolvent* l, int32_t j0, int32_t j1,
     int rc = LSA_OK;
     for (int32_t j = j0; j < j1 && rc == LSA_OK; ++j) {
         if (l->rhs_for != j) {  // (after a restart that moved another column here)
-            rc = rz_mass(ctx, l, rz_col(l, j), l->rhs[l->cur]);
+            rc = rz_response(ctx, l, rz_col(l, j), l->rhs[l->cur]);
             if (rc != LSA_OK) break;
             l->rhs_for = j;
         }
@@ -659,7 +696,7 @@ int lsa_resolvent_extend(lsa_ctx* ctx, lsa_resolvent* l, int32_t j0, int32_t j1,
             // z = C^-H rhs, ca = C^H z;  tm = M z;  w = C^-1 tm, cf = C w  (each with its direction's refinement step once switched on)
             rc = direct_solve_enqueue(ctx, l->op, LSA_C128, l->rhs[l->cur], l->za, l->ca, l->r, ra, l->rnorms, 1);
             if (rc == LSA_OK && ra) rc = k_nrm2(ctx, LSA_C128, n, l->za, l->slot + at + 8);  // for the backward-error judgement below
-            if (rc == LSA_OK) rc = rz_mass(ctx, l, l->za, l->tm);
+            if (rc == LSA_OK) rc = rz_forcing(ctx, l, l->za, l->tm);
             if (rc == LSA_OK) rc = direct_solve_enqueue(ctx, l->op, LSA_C128, l->tm, l->w, l->cf, l->r, rf, l->rnorms, 0);
             if (rc == LSA_OK && rf) rc = k_nrm2(ctx, LSA_C128, n, l->w, l->slot + at + 9);
             if (rc == LSA_OK) rc = rz_orth_tail(ctx, l, j + 1, j + 1, true);

@@ -397,6 +397,25 @@ static int spmv_variant() {
     return e ? (int)strtol(e, nullptr, 0) : 0;
 }
 
+void spmv_share_extras(const lsa_mat* from, lsa_mat* to) {
+    const int variant = spmv_variant();
+    // what launch_spmv and lsa_spmv_info would build for `from` on its first product, in their order
+    if (!(variant & 0x100)) {
+        if (spmv_wants_groups(from, variant) && ensure_groups(from)) {
+            if (variant & 0x800) (void)ensure_ci16(from);
+        } else if (spmv_wants_ci16(from, variant))
+            (void)ensure_ci16(from);
+    }
+    // a form `from` does not have is one `to` does not build for itself: it would own what it cannot free
+    to->grp_start = from->grp_state > 0 ? from->grp_start : nullptr;
+    to->ngroups = from->grp_state > 0 ? from->ngroups : 0;
+    to->grp_state = from->grp_state > 0 ? 1 : -1;
+    to->ci16 = from->ci16_state > 0 ? from->ci16 : nullptr;
+    to->cbase = from->ci16_state > 0 ? from->cbase : nullptr;
+    to->ci16_state = from->ci16_state > 0 ? 1 : -1;
+    to->owns_extras = false;
+}
+
 // LPR when k_spmv runs the plain row-per-sub-wave kernel on A with complex vectors (no variant word, no row groups, no compressed
 // indices), 0 otherwise: the fused tail of an Arnoldi step (blas.hip::cgs_tail_kernel) walks the rows the same way, so that
 // its two products are bit for bit those of k_spmv

@@ -162,6 +162,7 @@ SIGNATURES = {
     "lsa_mat_destroy": (None, [_P]),
     "lsa_mat_download_values": (ctypes.c_int, [_P, _P, _P]),
     "lsa_csr_axpby": (ctypes.c_int, [_P, _P, _P, _DBL * 2, _DBL * 2, ctypes.c_int, _PP]),
+    "lsa_csr_window": (ctypes.c_int, [_P, _P, _P, _P, _PP]),
     "lsa_spmv": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_spmv_transpose": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P]),
     "lsa_spmv_info": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_char_p, _I32, ctypes.POINTER(_I64)]),
@@ -245,6 +246,7 @@ SIGNATURES = {
     "lsa_resolvent_destroy": (None, [_P]),
     "lsa_resolvent_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
     "lsa_resolvent_set_block_forcings": (ctypes.c_int, [_P, _P, ctypes.c_int]),
+    "lsa_resolvent_set_weights": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_resolvent_set_start": (ctypes.c_int, [_P, _P, _P]),
     "lsa_resolvent_extend": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_I32)]),
     "lsa_resolvent_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
@@ -254,6 +256,8 @@ SIGNATURES = {
     "lsa_growth_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
     "lsa_growth_set_steps": (ctypes.c_int, [_P, _P, _I32]),
     "lsa_growth_set_scheme": (ctypes.c_int, [_P, _P, _I32]),
+    "lsa_growth_set_response_weight": (ctypes.c_int, [_P, _P, _P]),
+    "lsa_growth_response_energy": (ctypes.c_int, [_P, _P, _I32, _P]),
     "lsa_growth_set_start": (ctypes.c_int, [_P, _P, _P]),
     "lsa_growth_extend": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_I32)]),
     "lsa_growth_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
@@ -537,6 +541,28 @@ class CsrMatrix:
             )
         )
         return CsrMatrix(self.ctx, h, self.shape, self.nnz, dtype, keep=(self, other))
+
+    def windowed(self, left, right=None) -> "CsrMatrix":
+        """``diag(left) @ self @ diag(right)`` on this matrix' pattern (``lsa_csr_window``; ``right=None``: ``left``): the values
+        ``(left[i] * a_ij) * right[j]``, the bits of ``scipy.sparse.diags(left) @ A @ scipy.sparse.diags(right)``.  Real square
+        matrices only; the result shares this matrix' index arrays and SpMV kernel form and keeps it alive."""
+        n = self.shape[0]
+        vecs = []
+        for name, v in (("left", left), ("right", right)):
+            if v is None and name == "right":
+                vecs.append(None)
+                continue
+            a = np.asarray(v)
+            if a.dtype.kind == "c":
+                raise ValueError(f"lsa_csr_window: {name} is complex")
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (n,):
+                raise ValueError(f"lsa_csr_window: {name} must have shape ({n},), got {a.shape}")
+            vecs.append(a)
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx._lib.lsa_csr_window(self.ctx.handle, self.handle, _ptr(vecs[0]), None if vecs[1] is None else _ptr(vecs[1]),
+                                                    ctypes.byref(h)))
+        return CsrMatrix(self.ctx, h, self.shape, self.nnz, np.float64, keep=(self,))
 
     def values(self) -> np.ndarray:
         out = np.empty(self.nnz, dtype=self.dtype)
@@ -1172,10 +1198,12 @@ class LanczosBasis:
 class ResolventBasis:
     """Complex ``M``-orthonormal Lanczos basis in HBM for the resolvent's ``W = C^-1 M C^-H M``, ``C = A - i omega M``
     (``lsa_resolvent_*``): the counterpart of :class:`LanczosBasis` for optimal gains.  ``op`` must be a shift-invert operator
-    (mode 0) at ``sigma = 1j * omega`` with exact factors (``pc_type=2``) and a real ``M``."""
+    (mode 0) at ``sigma = 1j * omega`` (or ``beta + 1j * omega``: the discounted resolvent) with exact factors (``pc_type=2``) and a
+    real ``M``.  :meth:`set_weights` puts a forcing and a response weight where ``M`` stands: ``W = C^-1 Qf C^-H Qq``."""
 
     def __init__(self, ctx: Context, op: ShiftInvertOperator, ncv: int):
         self.ctx, self._op = ctx, op
+        self._weights = (None, None)
         self.n, self.ncv = op.n, int(ncv)
         h = ctypes.c_void_p()
         ctx.check(ctx._lib.lsa_resolvent_create(ctx.handle, op.handle, self.ncv, ctypes.byref(h)))
@@ -1198,6 +1226,14 @@ class ResolventBasis:
         """``True``: the forcings of :meth:`solve` take their adjoint solves as one block solve on the factors
         (``lsa_resolvent_set_block_forcings``); the results are those of the default, bit for bit."""
         self.ctx.check(self.ctx._lib.lsa_resolvent_set_block_forcings(self.ctx.handle, self.handle, int(bool(on))))
+
+    def set_weights(self, forcing: "CsrMatrix | None" = None, response: "CsrMatrix | None" = None) -> None:
+        """Forcing weight ``Q_f`` and response weight ``Q_q`` in place of ``M`` (``None``: ``M``; ``lsa_resolvent_set_weights``): real
+        symmetric positive semidefinite ``n x n`` device matrices, which this object keeps alive.  A start vector (or :meth:`solve`)
+        must follow."""
+        self.ctx.check(self.ctx._lib.lsa_resolvent_set_weights(self.ctx.handle, self.handle, None if forcing is None else forcing.handle,
+                                                               None if response is None else response.handle))
+        self._weights = (forcing, response)
 
     def _start(self, v) -> np.ndarray:
         v = np.ascontiguousarray(v, dtype=np.complex128)
@@ -1325,6 +1361,7 @@ class GrowthBasis:
         if scheme not in self.SCHEMES:
             raise ValueError(f"scheme must be one of {sorted(self.SCHEMES)}, got {scheme!r}")
         self.ctx, self._op = ctx, op
+        self._weight = None
         self.n, self.ncv, self.nsteps = op.n, int(ncv), int(nsteps)
         self.scheme = "euler"
         k = None
@@ -1355,6 +1392,12 @@ class GrowthBasis:
         p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
         self.ctx.check(self.ctx._lib.lsa_growth_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
         self._has_perm = p is not None
+
+    def set_response_weight(self, Q: "CsrMatrix | None") -> None:
+        """The response weight ``Q`` in place of ``M`` at the horizon (``None``: ``M``; ``lsa_growth_set_response_weight``): the gains
+        become ``max ||q(T)||_Q^2 / ||q(0)||_M^2``.  A real symmetric positive semidefinite ``n x n`` device matrix, kept alive here."""
+        self.ctx.check(self.ctx._lib.lsa_growth_set_response_weight(self.ctx.handle, self.handle, None if Q is None else Q.handle))
+        self._weight = Q
 
     def set_steps(self, nsteps: int) -> None:
         """Another horizon of ``nsteps`` steps on the same handle and factors."""
@@ -1387,7 +1430,8 @@ class GrowthBasis:
 
     def solve(self, nev: int, tol: float, max_restarts: int, *, v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None) -> dict:
         """The whole iteration inside the library (``lsa_growth_solve``).  Returns a dict: ``gains`` (descending), ``initial``
-        (n x k, ``M``-orthonormal), ``responses`` (n x k, ``Phi q0``), ``energy`` (k x (nsteps + 1)), ``estimates``, ``nconv``,
+        (n x k, ``M``-orthonormal), ``responses`` (n x k, ``Phi q0``), ``energy`` (k x (nsteps + 1), the ``M``-energy),
+        ``response_energy`` (k, the energy at ``T`` in the response weight), ``estimates``, ``nconv``,
         ``restarts``, ``applies``, the loop's phase times and the handle's solve counts so far."""
         max_out = self.ncv if max_out is None else min(int(max_out), self.ncv)
         o = lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=0, transform=0, sigma=(_DBL * 2)(0.0, 0.0),
@@ -1405,8 +1449,10 @@ class GrowthBasis:
                                                       _ptr(theta), _ptr(gains), _ptr(Q0), _ptr(QT), _ptr(energy), _ptr(est), ctypes.byref(res),
                                                       _ptr(counts)))
         k = res.nout
+        renergy = np.zeros(max(k, 1), dtype=np.float64)
+        self.ctx.check(self.ctx._lib.lsa_growth_response_energy(self.ctx.handle, self.handle, k, _ptr(renergy)))
         return {"gains": gains[:k].copy(), "initial": np.asfortranarray(Q0[:, :k]), "responses": np.asfortranarray(QT[:, :k]),
-                "energy": energy[:k].copy(), "estimates": est[:k].copy(), "nconv": int(res.nconv), "restarts": int(res.restarts),
+                "energy": energy[:k].copy(), "response_energy": renergy[:k].copy(), "estimates": est[:k].copy(), "nconv": int(res.nconv), "restarts": int(res.restarts),
                 "applies": int(res.op_applies), "next_unconverged": float(res.next_unconverged), "seconds_expand": res.seconds_expand,
                 "seconds_dense": res.seconds_dense, "seconds_restart": res.seconds_restart, "forward_solves": int(counts[0]),
                 "transposed_solves": int(counts[1]), "refined_forward": int(counts[2]), "refined_transposed": int(counts[3])}

@@ -184,6 +184,16 @@ class EigenSystem:
     def n(self) -> int:
         return self.A.shape[0]
 
+    def dof_xy(self) -> tuple[np.ndarray, np.ndarray]:
+        """(x, y) of every dof of a 2D case: a node's two velocity dofs and, on a vertex, its pressure dof sit at the node."""
+        X, Y = self.mesh.node_xy()
+        isv, off = self.mesh.is_vertex(), np.asarray(self.node_offset)
+        x, y = np.zeros(self.n), np.zeros(self.n)
+        for c in (0, 1):
+            x[off + c], y[off + c] = X, Y
+        x[off[isv] + 2], y[off[isv] + 2] = X[isv], Y[isv]
+        return x, y
+
 
 def wake_baseflow(X: np.ndarray, Y: np.ndarray, *, deficit: float = 1.25, width: float = 0.9, decay: float = 12.0):
     """Analytic cylinder-wake-like base flow U = (1 - a(x) exp(-y^2 / 2 s^2), 0), a = 0 upstream."""

@@ -1,6 +1,6 @@
 """Optimal transient growth: the library's iteration against what a user can drive from the host on kept factors.
 
-    python tools/growth_ab.py [--cases S30k C160k] [--reps 3] [--scheme euler] [--out profiles/growth_ab.json]
+    python tools/growth_ab.py [--cases S30k C160k] [--reps 3] [--scheme euler] [--windows] [--out profiles/growth_ab.json]
 
 ``library`` (a): ``Solver.growth.TransientGrowthSolver.solve`` -- set-up, one factorisation of ``A - M / dt``, the thick-restart Lanczos
 iteration on ``W = Phi+ Phi`` with the march of ``2 N`` solves, its checks, the mask and the orthogonalisation on the device, one
@@ -17,6 +17,11 @@ and spread over ``reps`` samples.  The gains of (b) are compared with those of (
 
 ``--scheme sdirk2``: both settings take the two-stage step ``S (a S + b I)`` on the factorisation of ``A - M / (gamma dt)`` (``4 N`` solves
 per product; (b): ``4 N`` round trips).  Its results go under the key ``"sdirk2"`` of the output file, beside the Euler rows.
+
+``--windows`` compares the library's solve with a response window (x in [2, 30]; cylinder cases) against its plain solve and against
+the plain problem solved through a window of ones (the same iteration with a windowed copy of ``M`` at the turn), alternately
+after a warm-up of each; the result goes under the key ``growth`` of ``profiles/windows_ab.json``.  Only the turn of a step's march
+differs, so the figure to compare is ``seconds_per_step``.
 """
 
 from __future__ import annotations
@@ -46,11 +51,21 @@ def problem(case: str):
     return fem.cube_case(case) if case.startswith("C") else fem.cylinder_case(case)
 
 
-def library(es) -> dict:
+RESPONSE_STRIP = (2.0, 30.0)
+
+
+def response_window(es) -> np.ndarray:
+    """The 0/1 response window of a cylinder case."""
+    x, _ = es.dof_xy()
+    return ((x >= RESPONSE_STRIP[0]) & (x <= RESPONSE_STRIP[1])).astype(float)
+
+
+def library(es, windows=False) -> dict:
     from Solver.growth import TransientGrowthConfig, TransientGrowthSolver
 
     t0 = time.perf_counter()
-    tg = TransientGrowthSolver(es.A, es.M, TransientGrowthConfig(dt=DT, num_modes=MODES, ncv=NCV, atol=TOL, scheme=SCHEME))
+    tg = TransientGrowthSolver(es.A, es.M, TransientGrowthConfig(dt=DT, num_modes=MODES, ncv=NCV, atol=TOL, scheme=SCHEME),
+                               response_window=np.ones(es.n) if windows == "ones" else response_window(es) if windows else None)
     tg.solver.prepare()
     t1 = time.perf_counter()
     res = tg.solve(HORIZON)
@@ -117,6 +132,31 @@ def host(es) -> dict:
             "read_backs_per_product": (4 if two else 2) * steps}
 
 
+def windows_ab(cases, reps: int) -> dict:
+    out = {"config": {"dt": DT, "horizon": HORIZON, "num_modes": MODES, "ncv": NCV, "tol": TOL, "reps": reps, "scheme": SCHEME,
+                      "response_strip": RESPONSE_STRIP}, "cases": []}
+    for case in cases:
+        if case.startswith("C"):
+            continue  # (the strip is the cylinder's)
+        es = problem(case)
+        settings = {"plain": False, "ones": "ones", "windowed": True}
+        warm = {name: library(es, w) for name, w in settings.items()}
+        runs = {name: [] for name in settings}
+        for _ in range(reps):
+            for name, w in settings.items():
+                runs[name].append(library(es, w))
+        entry = {"case": case, "n": int(es.A.shape[0]),
+                 **{name: {"gains": warm[name]["gains"].tolist(), "seconds": spread([r["seconds"] for r in runs[name]]),
+                           "seconds_per_step": spread([r["seconds_per_step"] for r in runs[name]]), "applies": warm[name]["applies"],
+                           "restarts": warm[name]["restarts"], "refinements": warm[name]["refinements"]} for name in settings}}
+        entry["per_step_ratio_median"] = entry["windowed"]["seconds_per_step"]["median"] / entry["plain"]["seconds_per_step"]["median"]
+        entry["per_step_ratio_ones_median"] = entry["ones"]["seconds_per_step"]["median"] / entry["plain"]["seconds_per_step"]["median"]
+        entry["ones_same_gains"] = bool(np.array_equal(warm["ones"]["gains"], warm["plain"]["gains"]))
+        out["cases"].append(entry)
+        print(json.dumps(entry), flush=True)
+    return out
+
+
 def plain(run: dict) -> dict:
     return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in run.items()}
 
@@ -132,9 +172,17 @@ def main(argv=None) -> None:
     ap.add_argument("--only", choices=("library", "host"), default=None, help="one setting alone, once per case (for a kernel trace)")
     ap.add_argument("--scheme", choices=("euler", "sdirk2"), default="euler")
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "growth_ab.json")
+    ap.add_argument("--windows", action="store_true", help="the windowed solve against the plain one -> key growth of profiles/windows_ab.json")
     args = ap.parse_args(argv)
     global SCHEME
     SCHEME = args.scheme
+    if args.windows:
+        path = ROOT / "profiles" / "windows_ab.json"
+        doc = json.loads(path.read_text()) if path.exists() else {}
+        doc["growth"] = windows_ab(args.cases, args.reps)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(doc, indent=1) + "\n")
+        return
     settings = {"library": library, "host": host}
     if args.only:
         for case in args.cases:

@@ -1,6 +1,6 @@
 """Optimal gains: the library's resolvent iteration against what a user can drive from the host on kept factors.
 
-    python tools/resolvent_ab.py [--cases S30k C160k] [--reps 3] [--forcings] [--out profiles/resolvent_ab.json]
+    python tools/resolvent_ab.py [--cases S30k C160k] [--reps 3] [--forcings] [--windows] [--out profiles/resolvent_ab.json]
 
 ``library`` (a): ``Solver.resolvent.ResolventSolver.solve`` -- set-up, one factorisation of ``A - i omega M``, the thick-restart Lanczos
 iteration on ``W = C^-1 M C^-H M`` with both inner solves, their checks and the orthogonalisation on the device, one read-back per step.
@@ -21,6 +21,13 @@ stay): ``ResolventSolver.solve`` without forcings, with them one adjoint solve a
 solve), alternately after a warm-up of each.  The figure is ``stats["seconds_restart"]``, the loop's phase that holds the thick restarts, the
 Ritz vectors and, where asked for, the forcings: a setting's figure minus that of the run without forcings is its forcings phase.  The
 forcings of the two settings are compared bit for bit.
+
+``--windows`` compares the library's solve with a forcing window (x in [-3, 3], |y| <= 3) and a response window (x in [2, 30]) against
+its plain solve and against the plain problem solved through windows of ones (the same iteration, step for step, with two
+windowed copies of ``M`` in flight: the like-for-like figure), alternately after a warm-up of each (cylinder cases), and times the call that builds one windowed matrix
+(``CsrMatrix.windowed``: the upload of the window, ``window_values_kernel`` and the synchronisation) on every case given; the result goes
+under the key ``resolvent`` of ``profiles/windows_ab.json``.  The weighted step has the launches of the plain one, so the figure to
+compare is ``seconds_per_step``; the iteration counts differ, since the windowed problem is another problem.
 """
 
 from __future__ import annotations
@@ -50,11 +57,26 @@ def problem(case: str):
     return fem.cylinder_case(case), float(complex(fem.SIGMA_RE50).imag)
 
 
-def library(es, omega: float) -> dict:
+FORCING_BOX, RESPONSE_STRIP = (-3.0, 3.0, -3.0, 3.0), (2.0, 30.0)
+
+
+def cylinder_windows(es):
+    """The 0/1 forcing and response windows of a cylinder case."""
+    x, y = es.dof_xy()
+    fx0, fx1, fy0, fy1 = FORCING_BOX
+    return (((x >= fx0) & (x <= fx1) & (y >= fy0) & (y <= fy1)).astype(float), ((x >= RESPONSE_STRIP[0]) & (x <= RESPONSE_STRIP[1])).astype(float))
+
+
+def library(es, omega: float, windows=False) -> dict:
     from Solver.resolvent import ResolventConfig, ResolventSolver
 
     t0 = time.perf_counter()
-    rs = ResolventSolver(es.A, es.M, ResolventConfig(num_modes=MODES, ncv=NCV, atol=TOL))
+    kw = {}
+    if windows == "ones":  # the plain problem through two windowed copies of M: the same iteration, two more matrices in flight
+        kw = dict(forcing_window=np.ones(es.n), response_window=np.ones(es.n))
+    elif windows:
+        kw = dict(zip(("forcing_window", "response_window"), cylinder_windows(es)))
+    rs = ResolventSolver(es.A, es.M, ResolventConfig(num_modes=MODES, ncv=NCV, atol=TOL), **kw)
     rs.solver.set_target(complex(0.0, omega))
     rs.solver.prepare()
     t1 = time.perf_counter()
@@ -135,6 +157,54 @@ def forcings_phase(cases, reps: int) -> dict:
     return out
 
 
+def window_call_seconds(es, reps: int) -> dict:
+    """Wall-clock seconds of ``CsrMatrix.windowed`` on the case's M (a smooth window: the time does not depend on the values)."""
+    import lsa_hip
+
+    ctx = lsa_hip.Context(0)
+    M = sp.csr_matrix(es.M)
+    dM = lsa_hip.CsrMatrix.from_scipy(ctx, M)
+    d = 0.5 * (1.0 + np.tanh(np.linspace(-3.0, 3.0, M.shape[0])))
+    dM.windowed(d)  # warm-up: the code object
+    times = []
+    for _ in range(max(reps, 3)):
+        t0 = time.perf_counter()
+        W = dM.windowed(d)
+        times.append(time.perf_counter() - t0)
+        del W
+    del dM
+    ctx.close()
+    return {"n": int(M.shape[0]), "nnz": int(M.nnz), "seconds": spread(times)}
+
+
+def windows_ab(cases, reps: int) -> dict:
+    out = {"config": {"num_modes": MODES, "ncv": NCV, "tol": TOL, "reps": reps, "forcing_box": FORCING_BOX, "response_strip": RESPONSE_STRIP},
+           "cases": [], "window_call": []}
+    for case in cases:
+        es, omega = problem(case)
+        out["window_call"].append({"case": case, **window_call_seconds(es, reps)})
+        print(json.dumps(out["window_call"][-1]), flush=True)
+        if case.startswith("C"):
+            continue  # (the boxes are the cylinder's)
+        settings = {"plain": False, "ones": "ones", "windowed": True}
+        warm = {name: library(es, omega, w) for name, w in settings.items()}
+        runs = {name: [] for name in settings}
+        for _ in range(reps):
+            for name, w in settings.items():
+                runs[name].append(library(es, omega, w))
+        entry = {"case": case, "n": int(es.A.shape[0]), "omega": omega,
+                 **{name: {"gains": warm[name]["gains"].tolist(), "seconds": spread([r["seconds"] for r in runs[name]]),
+                           "seconds_per_step": spread([r["seconds_per_step"] for r in runs[name]]),
+                           "seconds_setup": spread([r["seconds_setup"] for r in runs[name]]), "applies": warm[name]["applies"],
+                           "restarts": warm[name]["restarts"], "refinements": warm[name]["refinements"]} for name in settings}}
+        entry["per_step_ratio_median"] = entry["windowed"]["seconds_per_step"]["median"] / entry["plain"]["seconds_per_step"]["median"]
+        entry["per_step_ratio_ones_median"] = entry["ones"]["seconds_per_step"]["median"] / entry["plain"]["seconds_per_step"]["median"]
+        entry["ones_same_gains"] = bool(np.array_equal(warm["ones"]["gains"], warm["plain"]["gains"]))
+        out["cases"].append(entry)
+        print(json.dumps(entry), flush=True)
+    return out
+
+
 def plain(run: dict) -> dict:
     return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in run.items()}
 
@@ -150,7 +220,15 @@ def main(argv=None) -> None:
     ap.add_argument("--only", choices=("library", "host"), default=None, help="one setting alone, once per case (for a kernel trace)")
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "resolvent_ab.json")
     ap.add_argument("--forcings", action="store_true", help="the forcings phase with block_forcings off and on -> key forcings_phase of --out")
+    ap.add_argument("--windows", action="store_true", help="the windowed solve against the plain one -> key resolvent of profiles/windows_ab.json")
     args = ap.parse_args(argv)
+    if args.windows:
+        path = ROOT / "profiles" / "windows_ab.json"
+        doc = json.loads(path.read_text()) if path.exists() else {}
+        doc["resolvent"] = windows_ab(args.cases, args.reps)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(doc, indent=1) + "\n")
+        return
     if args.forcings:
         doc = json.loads(args.out.read_text()) if args.out.exists() else {}
         doc["forcings_phase"] = forcings_phase(args.cases, args.reps)
