@@ -1377,7 +1377,7 @@ int lsa_lanczos_solve(lsa_ctx* ctx, lsa_lanczos* l, const lsa_ks_options* o, con
     return trl_solve(ctx, b, o, v0, max_out, theta_out, lambda_out, X_out, est_out, result);
 }
 
-// The resolvent iteration (resolvent.hip): the same loop on the complex basis of W = C^-1 M C^-H M; theta_j = sigma_j^2, largest first.
+// The resolvent iteration (resolvent.hip): the same loop on the basis with complex scalars, for W = C^-1 M C^-H M; theta_j = sigma_j^2, largest first.
 int lsa_resolvent_solve(lsa_ctx* ctx, lsa_resolvent* r, const lsa_ks_options* o, const void* v0, int32_t max_out, double* theta_out,
                         double* gain_out, void* Q_out, void* F_out, double* est_out, lsa_ks_result* result, int64_t* counts) {
     if (!ctx || !r || !o || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_solve: null argument");

@@ -11,7 +11,7 @@
 //         k < 2N-1:   mx = M x;  b_{k+1} = -sigma keep (.) mx;  log[k] = |b_k - z|^2, |b_k|^2, x^T mx, |x|^2     tg_march_kernel + tg_log_kernel
 //     w = -sigma keep (.) x_{2N-1}          tg_scale_kernel: the one factor -sigma the march does not cover (b_0 carries none)
 //     the pair (b_{2N-1}, z) of the last solve rides in the step's first lz_dot_kernel reduction, where the default's single solve does
-// The march log travels to the host behind the step's one synchronisation; every solve is judged by the rule of lsa_lanczos_extend.
+// The march log travels to the host behind the step's one synchronisation; every solve is judged by direct_solve_verdict.
 // Each direction carries its own refinement step once one of its solves missed ksp_rtol.
 //
 // lsa_growth_set_scheme(LSA_GROWTH_SDIRK2) marches by the L-stable, stiffly accurate two-stage SDIRK method with gamma = 1 - 1/sqrt 2
@@ -44,8 +44,7 @@
 
 namespace {
 
-constexpr int kTgThreads = 256;     // four wavefronts of 64
-constexpr int kTgMaxChunks = 2048;  // row chunks = partial sums per log entry (k_multi_dot's rule)
+constexpr int kTgThreads = 256;  // four wavefronts of 64
 
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -145,12 +144,6 @@ __global__ __launch_bounds__(kTgThreads) void tg_combine_kernel(int64_t n, doubl
     for (int64_t i = (int64_t)blockIdx.x * kTgThreads + threadIdx.x; i < n; i += stride) y[i] = fma(cb, b[i], ca * (keep[i] * x[i]));
 }
 
-int tg_check_launch(lsa_ctx* ctx, const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lsa_set_error(ctx, LSA_ERR_HIP, "%s: kernel launch failed: %s", what, hipGetErrorString(e));
-    return LSA_OK;
-}
-
 // tg_march_kernel + tg_log_kernel unless LSA_GROWTH_FUSED=0 (read once per process): then k_residual_norms, k_multi_dot and the scale
 // (a combined right-hand side: tg_combine_kernel)
 bool tg_fused() {
@@ -177,12 +170,13 @@ struct lsa_growth {
     // the march's own vectors: the two right-hand sides it alternates between (the step's rhs stays intact), a solution, C x, M x and
     // the residual of a refinement step (of the unfused form too)
     double *pp[2] = {nullptr, nullptr}, *x = nullptr, *cz = nullptr, *mx = nullptr, *r = nullptr;
-    double* part = nullptr;    // 4 x kTgMaxChunks partial sums
+    double* part = nullptr;    // 4 x kDotMaxChunks partial sums
     double* log = nullptr;     // 4 sums per marched solve, and one more quadruple (a final march's q0^T M q0; scratch of the unfused form)
     double* rnorms = nullptr;  // the two sums a refinement step's residual pass leaves (not read)
     double* hlog = nullptr;    // pinned host copy of the log
     int32_t logged = 0;        // quadruples the last read-back carries
-    double *resp = nullptr, *xtmp = nullptr;  // the responses of lsa_growth_solve (n x ncv) and, with a row permutation, their scattered form
+    double* resp = nullptr;
+    void* xtmp = nullptr;  // the responses of lsa_growth_solve (n x ncv) and, with a row permutation, their scattered form
     int32_t* row_perm = nullptr;
     bool refine_fwd = false, refine_adj = false, used_fwd = false, used_adj = false;  // used_*: what the march being judged was queued with
     int64_t solves_fwd = 0, solves_adj = 0, refined_fwd = 0, refined_adj = 0;
@@ -193,7 +187,7 @@ namespace {
 void tg_free(lsa_growth* g) {
     if (g->lz) lsa_lanczos_destroy(g->lz);
     for (void* p : {(void*)g->keep, (void*)g->pp[0], (void*)g->pp[1], (void*)g->x, (void*)g->cz, (void*)g->mx, (void*)g->r, (void*)g->part, (void*)g->log,
-                    (void*)g->rnorms, (void*)g->resp, (void*)g->xtmp, (void*)g->row_perm})
+                    (void*)g->rnorms, (void*)g->resp, g->xtmp, (void*)g->row_perm})
         if (p) (void)hipFree(p);
     if (g->hlog) (void)hipHostFree(g->hlog);
     delete g;
@@ -233,13 +227,13 @@ int tg_mass(lsa_ctx* ctx, lsa_growth* g, const lsa_mat* W, const double* x, doub
 
 int tg_scale(lsa_ctx* ctx, lsa_growth* g, double alpha, const double* x, double* y) {
     hipLaunchKernelGGL(tg_scale_kernel, dim3(tg_grid(ctx, (g->n + kTgThreads - 1) / kTgThreads, 8)), dim3(kTgThreads), 0, ctx->stream, g->n, alpha, g->keep, x, y);
-    return tg_check_launch(ctx, "growth scale");
+    return lsa_check_launch(ctx, "growth scale");
 }
 
 int tg_combine(lsa_ctx* ctx, lsa_growth* g, double ca, double cb, const double* x, const double* b, double* y) {
     hipLaunchKernelGGL(tg_combine_kernel, dim3(tg_grid(ctx, (g->n + kTgThreads - 1) / kTgThreads, 8)), dim3(kTgThreads), 0, ctx->stream, g->n, ca, cb, g->keep, x, b,
                        y);
-    return tg_check_launch(ctx, "growth combine");
+    return lsa_check_launch(ctx, "growth combine");
 }
 
 // What follows the inner solve x of b (z = C x): mx = W x (W: M, or the response weight after the last forward solve of a step's
@@ -252,10 +246,8 @@ int tg_after_solve(lsa_ctx* ctx, lsa_growth* g, const lsa_mat* W, int32_t k, con
     double* out = g->log + (size_t)4 * (size_t)k;
     LSA_CHECK(tg_mass(ctx, g, W, x, g->mx));
     if (tg_fused()) {
-        // k_multi_dot's chunks: at most 2048 of them, whole multiples of 256 rows, at least 512 rows
-        int64_t rows_per_chunk = ((n + kTgMaxChunks - 1) / kTgMaxChunks + kTgThreads - 1) / kTgThreads * kTgThreads;
-        rows_per_chunk = std::max<int64_t>(rows_per_chunk, 2 * kTgThreads);
-        const int nchunks = (int)std::max<int64_t>((n + rows_per_chunk - 1) / rows_per_chunk, 1);
+        int64_t rows_per_chunk;
+        const int nchunks = dot_chunks(n, &rows_per_chunk);
         if (combine)
             hipLaunchKernelGGL(tg_march_kernel<true>, dim3(tg_grid(ctx, nchunks, 4)), dim3(kTgThreads), 0, ctx->stream, n, rows_per_chunk, nchunks, ca, b, z, x,
                                g->mx, g->keep, next, g->part, cb);
@@ -263,7 +255,7 @@ int tg_after_solve(lsa_ctx* ctx, lsa_growth* g, const lsa_mat* W, int32_t k, con
             hipLaunchKernelGGL(tg_march_kernel<false>, dim3(tg_grid(ctx, nchunks, 4)), dim3(kTgThreads), 0, ctx->stream, n, rows_per_chunk, nchunks, -g->sigma, b, z,
                                x, g->mx, g->keep, next, g->part, 0.0);
         hipLaunchKernelGGL(tg_log_kernel, dim3(1), dim3(kTgThreads), 0, ctx->stream, nchunks, g->part, out);
-        return tg_check_launch(ctx, "growth march");
+        return lsa_check_launch(ctx, "growth march");
     }
     // the unfused form: r = b - z (its own two sums go to the spare quadruple and are not read), then the four sums as single dots
     LSA_CHECK(k_residual_norms(ctx, LSA_F64, n, b, z, g->r, g->log + (size_t)4 * (size_t)g->log_cap));
@@ -273,14 +265,6 @@ int tg_after_solve(lsa_ctx* ctx, lsa_growth* g, const lsa_mat* W, int32_t k, con
     LSA_CHECK(k_multi_dot(ctx, LSA_F64, n, 1, x, n, x, out + 3));
     if (combine) return tg_combine(ctx, g, ca, cb, g->mx, b, next);
     return next ? tg_scale(ctx, g, -g->sigma, g->mx, next) : LSA_OK;
-}
-
-// The library's judgement of a direct solve (gmres_run, lsa_lanczos_extend): within ksp_rtol, or, after the refinement step, a
-// backward error within 1e-12 ||C||_F.  0: accepted (*backward says by which rule), 1: again with the refinement step, -1: diverged.
-int tg_judge(const lsa_op_parts& P, bool refine, double res, double bnorm, double xnorm, bool* backward) {
-    *backward = refine && res > P.ksp_rtol * bnorm && P.normF > 0.0 && res <= 1e-12 * P.normF * xnorm;
-    if (res <= P.ksp_rtol * bnorm || *backward) return 0;
-    return (!refine && std::isfinite(res)) ? 1 : -1;
 }
 
 struct TgSolve {  // one solve of a march as the host sees it
@@ -294,7 +278,7 @@ int tg_judge_march(lsa_ctx* ctx, lsa_growth* g, std::vector<TgSolve>& sv, const 
     int worst = 0;
     for (size_t k = 0; k < sv.size(); ++k) {
         TgSolve& s = sv[k];
-        const int v = tg_judge(g->P, s.refine, s.res, s.bnorm, s.xnorm, &s.backward);
+        const int v = direct_solve_verdict(g->P, s.refine, s.res, s.bnorm, s.xnorm, &s.backward);
         if (v < 0) {
             lsa_set_error(ctx, LSA_ERR_DIVERGED, "%s: the %s solve %d of the march of %s %d left a relative residual of %.3e after its refinement step "
                                                  "(ksp_rtol %.1e) and a backward error above 1e-12 ||C||_F", who, s.adjoint ? "transposed" : "forward", (int)k, what,
@@ -317,13 +301,12 @@ int tg_judge_march(lsa_ctx* ctx, lsa_growth* g, std::vector<TgSolve>& sv, const 
 }
 
 // ---- the operator behind a Lanczos step -------------------------------------------------------------------------------------------
-int tg_hook_enqueue(lsa_ctx* ctx, void* self, int32_t, const double* rhs, double* w, double* z, double* r, double* xnorm2_dev, const double** chk_b,
-                    bool* refined) {
+int tg_hook_enqueue(lsa_ctx* ctx, void* self, int32_t, const void* rhs, void* w, void* z, void* r, lanczos_check* chk) {
     lsa_growth* g = (lsa_growth*)self;
     const int32_t N = tg_stages(g->scheme) * g->nsteps, last = 2 * N - 1;  // N solves each way
     g->used_fwd = g->refine_fwd;
     g->used_adj = g->refine_adj;
-    const double* b = rhs;
+    const double* b = (const double*)rhs;
     for (int32_t k = 0; k < last; ++k) {
         const bool adj = k >= N;
         LSA_CHECK(direct_solve_enqueue(ctx, g->op, LSA_F64, b, g->x, g->cz, g->r, adj ? g->used_adj : g->used_fwd, g->rnorms, adj ? 1 : 0));
@@ -335,10 +318,11 @@ int tg_hook_enqueue(lsa_ctx* ctx, void* self, int32_t, const double* rhs, double
     }
     // the last solve lands where the default's single solve does; the step's first reduction checks it
     LSA_CHECK(direct_solve_enqueue(ctx, g->op, LSA_F64, b, w, z, r, g->used_adj, g->rnorms, 1));
-    if (g->used_adj) LSA_CHECK(k_nrm2(ctx, LSA_F64, g->n, w, xnorm2_dev));
-    LSA_CHECK(tg_scale(ctx, g, -g->sigma, w, w));
-    *chk_b = b;
-    *refined = g->used_adj;
+    if (g->used_adj) LSA_CHECK(k_nrm2(ctx, LSA_F64, g->n, w, chk[0].xnorm2_dev));
+    LSA_CHECK(tg_scale(ctx, g, -g->sigma, (const double*)w, (double*)w));
+    chk[0].b = b;
+    chk[0].z = z;
+    chk[0].refined = g->used_adj;
     g->logged = last;
     return LSA_OK;
 }
@@ -350,7 +334,7 @@ int tg_hook_read_back(lsa_ctx* ctx, void* self) {
     return LSA_OK;
 }
 
-int tg_hook_judge(lsa_ctx* ctx, void* self, int32_t j, double res, double bnorm, double xnorm) {
+int tg_hook_judge(lsa_ctx* ctx, void* self, int32_t j, const lanczos_sums* s) {
     lsa_growth* g = (lsa_growth*)self;
     const int32_t N = tg_stages(g->scheme) * g->nsteps, last = 2 * N - 1;
     std::vector<TgSolve> sv((size_t)last + 1);
@@ -359,22 +343,9 @@ int tg_hook_judge(lsa_ctx* ctx, void* self, int32_t j, double res, double bnorm,
         const bool adj = k >= N;
         sv[(size_t)k] = TgSolve{adj, adj ? g->used_adj : g->used_fwd, false, std::sqrt(e[0]), std::sqrt(e[1]), std::sqrt(e[3])};
     }
-    sv[(size_t)last] = TgSolve{true, g->used_adj, false, res, bnorm, xnorm};
+    sv[(size_t)last] = TgSolve{true, g->used_adj, false, s[0].res, s[0].bnorm, s[0].xnorm};
     g->logged = 0;
     return tg_judge_march(ctx, g, sv, "lsa_growth_extend", "step", j);
-}
-
-int tg_scatter_out(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, const double* dev, double* host) {
-    const size_t vb = (size_t)g->n * sizeof(double);
-    const double* src = dev;
-    if (g->row_perm) {
-        if (!g->xtmp) LSA_HIP_ALLOC(ctx, hipMalloc((void**)&g->xtmp, std::max<size_t>(vb, 8) * (size_t)g->ncv));
-        LSA_CHECK(k_scatter_rows(ctx, LSA_F64, g->n, nvec, g->row_perm, dev, g->xtmp));
-        src = g->xtmp;
-    }
-    LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, src, vb * (size_t)nvec, hipMemcpyDeviceToHost, ctx->stream));
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return LSA_OK;
 }
 
 }  // namespace
@@ -420,7 +391,7 @@ int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, doub
     const int32_t stages = tg_stages(g->scheme), steps = g->nsteps, N = stages * steps;  // N solves; a time step's energy: its last stage's
     const size_t vb = (size_t)std::max<int64_t>(n, 1) * sizeof(double);
     if (!g->resp) LSA_HIP_ALLOC(ctx, hipMalloc((void**)&g->resp, vb * (size_t)g->ncv));
-    const double* Q0 = lanczos_ritz_device(g->lz);
+    const double* Q0 = (const double*)lanczos_ritz_device(g->lz);
     const double t0 = now_s();
     std::vector<TgSolve> sv((size_t)N);
     g->renergy.assign((size_t)nvec, 0.0);
@@ -462,7 +433,7 @@ int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, doub
         }
     }
     g->P.st->seconds_solve += now_s() - t0;
-    return QT ? tg_scatter_out(ctx, g, nvec, g->resp, QT) : LSA_OK;
+    return QT ? basis_columns_to_host(ctx, LSA_F64, n, nvec, g->row_perm, g->resp, &g->xtmp, g->ncv, QT) : LSA_OK;
 }
 
 extern "C" {
@@ -497,7 +468,7 @@ int lsa_growth_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, int32_t nsteps, con
     g->sigma = P.sigma[0];
     g->hkeep.assign((size_t)P.n, 1.0);
     if (keep) std::copy(keep, keep + P.n, g->hkeep.begin());
-    int rc = lsa_lanczos_create(ctx, op, ncv, &g->lz);
+    int rc = lanczos_create_basis(ctx, op, ncv, LSA_F64, "lsa_growth", &g->lz);
     if (rc != LSA_OK) {
         g->lz = nullptr;
         tg_free(g);
@@ -506,7 +477,7 @@ int lsa_growth_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, int32_t nsteps, con
     const size_t vb = (size_t)std::max<int64_t>(g->n, 1) * sizeof(double);
     bool ok = true;
     for (double** p : {&g->keep, &g->pp[0], &g->pp[1], &g->x, &g->cz, &g->mx, &g->r}) ok = ok && hipMalloc((void**)p, vb) == hipSuccess;
-    ok = ok && hipMalloc((void**)&g->part, (size_t)kTgMaxChunks * 4 * sizeof(double)) == hipSuccess && hipMalloc((void**)&g->rnorms, 2 * sizeof(double)) == hipSuccess;
+    ok = ok && hipMalloc((void**)&g->part, (size_t)kDotMaxChunks * 4 * sizeof(double)) == hipSuccess && hipMalloc((void**)&g->rnorms, 2 * sizeof(double)) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         tg_free(g);
@@ -519,8 +490,12 @@ int lsa_growth_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, int32_t nsteps, con
         tg_free(g);
         return rc;
     }
-    g->hook = lanczos_operator{g, tg_hook_enqueue, tg_hook_read_back, tg_hook_judge};
-    lanczos_set_operator(g->lz, &g->hook);
+    g->hook = lanczos_operator{g, 1, tg_hook_enqueue, tg_hook_read_back, tg_hook_judge};
+    rc = lanczos_set_operator(ctx, g->lz, &g->hook);
+    if (rc != LSA_OK) {
+        tg_free(g);
+        return rc;
+    }
     *out = g;
     return LSA_OK;
 }

@@ -1,24 +1,35 @@
-// Thick-restart Lanczos (the symmetric variant of Krylov-Schur) for symmetric-definite pencils K x = lambda M x: what SLEPc runs
-// behind EPS_GHEP / EPS_HEP (reference: Solver/utils.py:244-270 with iEpsProblemType.GHEP; Elasticity/utils.py:141-155).
+// Thick-restart Lanczos (the symmetric variant of Krylov-Schur): the basis of the library's self-adjoint outer iterations.
 //
-// OP = (K - sigma M)^-1 M with a real sigma is self-adjoint in the M-inner product, so the basis V (n x (ncv + 1) doubles) is kept
-// M-orthonormal, V^T M V = I, the projected matrix is real symmetric, and no complex number is stored or moved: half of the bytes of
-// the general path's basis, sweeps and products.  This file holds the basis handle, the step and its kernels; the outer loop and
-// the dense symmetric eigen-solve are lsa_lanczos_solve and lsa_dense_syev (dense.hip).
+// The symmetric-definite pencil K x = lambda M x is what SLEPc runs behind EPS_GHEP / EPS_HEP (reference: Solver/utils.py:244-270 with
+// iEpsProblemType.GHEP; Elasticity/utils.py:141-155): OP = (K - sigma M)^-1 M with a real sigma is self-adjoint in the M-inner product,
+// so the basis V (n x (ncv + 1) doubles) is kept M-orthonormal, V^T M V = I, the projected matrix is real symmetric, and no complex
+// number is stored or moved: half of the bytes of the general path's basis, sweeps and products.  Transient growth (growth.hip) puts a
+// march of solves behind the step of the same real basis; the resolvent (resolvent.hip) has complex vectors and the same real
+// symmetric projected matrix (alpha_j = Re h_j, beta_j > 0, the eigenvectors Y of T real, the restart's spike real), so it owns this
+// basis with complex scalars (LSA_C128: V^H Q V = I) and its two solves are the operator behind the step.  This file holds the one
+// basis handle for both scalar types, the step and its kernels; the outer loop and the dense symmetric eigen-solve are
+// lsa_lanczos_solve and lsa_dense_syev (dense.hip).
 //
-// One step j (rhs = M v_j is left by the previous step's tail):
+// One step j (rhs = Q v_j is left by the previous step's tail; Q: the inner product's matrix, M unless lanczos_set_inner_product gave
+// another):
+//     w = OP v_j from rhs                   the operator (lanczos_operator), which names the inner solves to check: pairs (b, z = C x)
+//     twice:  t = Q w;  h = V^H t;  w -= V h    the dot and the update kernel: full reorthogonalisation against v_0..v_j; the first
+//                                           reduction also sums |b - z|^2 and |b|^2 of the operator's checks
+//     t = Q w;  beta^2 = Re w^H t           the dot kernel on the one extra column
+//     v_{j+1} = w / beta;  rhs' = t / beta  the tail kernel, which also leaves beta^2 and the checks' sums in the step's slot
+// Three products with Q per step, one host synchronisation (the read-back of the slot), after which the operator judges its solves:
+// accepted, or the step is done again (a refinement step switched on), or the iteration fails.  For a standard problem (no M, real
+// scalars only) t is w.  The default operator of a real basis is the single solve
 //     w = C^-1 rhs                          the real sweeps of the exact LU (ndlu_solve_dev, float64 vectors)
-//     z = C w                               for the inner-solve check |rhs - z| <= ksp_rtol |rhs| (one refinement step if it fails)
-//     twice:  t = M w;  h = V^T t;  w -= V h    lz_dot_kernel + lz_update_kernel: full reorthogonalisation against v_0..v_j
-//     t = M w;  beta^2 = w^T t              lz_dot_kernel on the one extra column
-//     v_{j+1} = w / beta;  rhs' = t / beta  lz_tail_kernel, which also leaves beta^2 and the check's two sums in the step's slot
-// Three products with M per step, one host synchronisation (the read-back of the slot).  For a standard problem (M = NULL) t is w.
-// The first line is the default; lanczos_set_operator puts another operator behind a step (growth.hip: a march of solves), which
-// leaves w, z and the right-hand side of its last solve where the single solve does and judges its solves itself.
+//     z = C w                               for the check |rhs - z| <= ksp_rtol |rhs| (one refinement step if it fails)
+// on the op's shared refinement flag.
 //
-// Every reduction runs in a fixed order (per-thread strided sums, a shuffle tree inside the wavefront, the four wave sums in wave
-// order, the chunks' partial sums strided over 64 lanes and the same tree) and there are no floating-point atomics: two runs give
-// the same bits, and the order is that of k_multi_dot / k_multi_axpy, so the unfused form of a step gives them too.
+// The step kernels exist per scalar type and are not one template: lz_* move 8-byte words, two rows in flight per lane, rz_* move
+// 16-byte entries one row at a time (the comment of growth.hip says why a lane's rows cannot be paired into 16-byte loads of doubles).
+// Every reduction runs in a fixed order (per-thread strided sums, a shuffle tree inside the wavefront -- real and imaginary part each
+// -- the four wave sums in wave order, the chunks' partial sums strided over 64 lanes and the same tree) and there are no
+// floating-point atomics: two runs give the same bits, and the order is that of k_multi_dot / k_multi_axpy, so the unfused form of a
+// step (LSA_LANCZOS_FUSED=0) gives them too.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -28,10 +39,10 @@
 
 namespace {
 
-constexpr int kLzThreads = 256;     // four wavefronts of 64
-constexpr int kLzColTile = 8;       // basis columns per workgroup of lz_dot_kernel
-constexpr int kLzMaxChunks = 2048;  // row chunks of lz_dot_kernel = partial sums per coefficient (k_multi_dot's rule)
-constexpr int kLzUnroll = 16;       // basis entries of a row requested at a time by lz_update_kernel
+constexpr int kLzThreads = 256;  // four wavefronts of 64
+constexpr int kLzColTile = 8;    // basis columns per workgroup of the dot kernels (k_multi_dot's tile)
+constexpr int kLzUnroll = 16;    // basis entries of a row requested at a time by lz_update_kernel
+constexpr int kRzUnroll = 8;     // ... by rz_update_kernel (8 x 16 bytes per lane)
 
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -45,6 +56,14 @@ inline double now_s() { return std::chrono::duration<double>(std::chrono::steady
 __device__ __forceinline__ double lz_wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ cplx lz_wave_sum(cplx v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        v.re += __shfl_xor(v.re, off, 64);
+        v.im += __shfl_xor(v.im, off, 64);
+    }
     return v;
 }
 
@@ -62,7 +81,20 @@ __device__ __forceinline__ double lz_finish_sum(const double* __restrict__ part,
     }
     return lz_wave_sum(a);
 }
+__device__ __forceinline__ cplx lz_finish_sum(const cplx* __restrict__ part, int nchunks, int lane) {
+    cplx a = cplx{0.0, 0.0};
+    for (int k0 = lane; k0 < nchunks; k0 += 8 * 64) {
+        cplx pv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) pv[u] = (k0 + 64 * u < nchunks) ? rz_ld(part + k0 + 64 * u) : cplx{0.0, 0.0};
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (k0 + 64 * u < nchunks) a = s_add(a, pv[u]);
+    }
+    return lz_wave_sum(a);
+}
 
+// ---- the step kernels for real scalars ---------------------------------------------------------------------------------------------
 // Partial sums of V^T t for the columns 0..ncols-1 and of w^T t (stored as column `ncols`), one pass over V: workgroup
 // (chunk, tile) sums kLzColTile columns over the rows of its chunk into part[c * ldp + chunk].  The workgroups of tile 0 also sum
 // the inner-solve check over their rows when chk_part is given: chk_part[2 chunk] = |chk_b - chk_z|^2, [2 chunk + 1] = |chk_b|^2.
@@ -246,10 +278,158 @@ __global__ __launch_bounds__(kLzThreads) void lz_sign_kernel(int64_t n, double* 
         for (int64_t i = threadIdx.x; i < n; i += kLzThreads) x[i] = -x[i];
 }
 
-int lz_check_launch(lsa_ctx* ctx, const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lsa_set_error(ctx, LSA_ERR_HIP, "%s: kernel launch failed: %s", what, hipGetErrorString(e));
-    return LSA_OK;
+// ---- the step kernels for complex scalars ------------------------------------------------------------------------------------------
+// Partial sums of V^H t for the columns 0..ncols-1 and of w^H t (stored as column `ncols`), one pass over V: workgroup (chunk, tile)
+// sums kLzColTile columns over the rows of its chunk into part[c * ldp + chunk].  The workgroups of tile 0 also sum the two inner-solve
+// checks over their rows when chk_part is given: chk_part[4 chunk + 0..3] = |b1 - z1|^2, |b1|^2, |b2 - z2|^2, |b2|^2.  A full tile
+// has its eight 16-byte loads of a row in flight before the first addition.
+__global__ __launch_bounds__(kLzThreads) void rz_dot_kernel(int64_t n, int ncols, int64_t rows_per_block, const cplx* __restrict__ V, int64_t ldv,
+                                                            const cplx* t, const cplx* w, cplx* __restrict__ part, int ldp,
+                                                            const cplx* __restrict__ b1, const cplx* __restrict__ z1, const cplx* __restrict__ b2,
+                                                            const cplx* __restrict__ z2, double* __restrict__ chk_part) {
+    __shared__ cplx wsum[4][kLzColTile];
+    __shared__ double csum[4][4];
+    const int chunk = blockIdx.x;
+    const int c0 = blockIdx.y * kLzColTile;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t r0 = (int64_t)chunk * rows_per_block;
+    const int64_t r1 = (r0 + rows_per_block < n) ? r0 + rows_per_block : n;
+    // column c of the tile: a basis column, or w for the one behind the basis
+    const cplx* col[kLzColTile];
+#pragma unroll
+    for (int c = 0; c < kLzColTile; ++c) col[c] = (c0 + c < ncols) ? V + (int64_t)(c0 + c) * ldv : w;
+    const int nc = (ncols + 1 - c0 < kLzColTile) ? (ncols + 1 - c0) : kLzColTile;
+    cplx acc[kLzColTile];
+#pragma unroll
+    for (int c = 0; c < kLzColTile; ++c) acc[c] = cplx{0.0, 0.0};
+    if (nc == kLzColTile) {
+        for (int64_t i = r0 + threadIdx.x; i < r1; i += kLzThreads) {
+            const cplx tv = rz_ld(t + i);
+            cplx v[kLzColTile];
+#pragma unroll
+            for (int c = 0; c < kLzColTile; ++c) v[c] = rz_ld(col[c] + i);
+#pragma unroll
+            for (int c = 0; c < kLzColTile; ++c) fma_conj_acc(acc[c], v[c], tv);
+        }
+    } else {
+        for (int64_t i = r0 + threadIdx.x; i < r1; i += kLzThreads) {
+            const cplx tv = rz_ld(t + i);
+#pragma unroll
+            for (int c = 0; c < kLzColTile; ++c)
+                if (c < nc) fma_conj_acc(acc[c], rz_ld(col[c] + i), tv);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < kLzColTile; ++c) {
+        const cplx s = lz_wave_sum(acc[c]);
+        if (lane == 0) wsum[wave][c] = s;
+    }
+    const bool chk = chk_part != nullptr && blockIdx.y == 0;
+    if (chk) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int64_t r = r0 + threadIdx.x; r < r1; r += kLzThreads) {
+            const cplx ba = rz_ld(b1 + r), bb = rz_ld(b2 + r);
+            const cplx da = s_sub(ba, rz_ld(z1 + r)), db = s_sub(bb, rz_ld(z2 + r));
+            s[0] = fma(da.im, da.im, fma(da.re, da.re, s[0]));
+            s[1] = fma(ba.im, ba.im, fma(ba.re, ba.re, s[1]));
+            s[2] = fma(db.im, db.im, fma(db.re, db.re, s[2]));
+            s[3] = fma(bb.im, bb.im, fma(bb.re, bb.re, s[3]));
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const double v = lz_wave_sum(s[q]);
+            if (lane == 0) csum[wave][q] = v;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < nc) {
+        const int c = threadIdx.x;
+        rz_st(part + (int64_t)(c0 + c) * ldp + chunk, s_add(s_add(s_add(wsum[0][c], wsum[1][c]), wsum[2][c]), wsum[3][c]));
+    }
+    if (chk && threadIdx.x >= 64 && threadIdx.x < 68) {
+        const int q = threadIdx.x - 64;
+        chk_part[4 * chunk + q] = ((csum[0][q] + csum[1][q]) + csum[2][q]) + csum[3][q];
+    }
+}
+
+// w -= V h for the columns 0..ncols-1.  The prologue finishes h from the partial sums (lz_finish_sum: every workgroup gets the same
+// bits; wave q takes the columns q, q + 4, ...); workgroup 0 writes h to h_out for the host.  Then a thread per row, the rows of a
+// workgroup strided over the grid: eight entries of the row are requested at a time -- the first eight ahead of the prologue, which
+// does not depend on them -- and added column after column.  The dynamic LDS holds h alone (no static LDS in front of it: 16-byte
+// aligned entries).
+__global__ __launch_bounds__(kLzThreads) void rz_update_kernel(int64_t n, int ncols, const cplx* __restrict__ V, int64_t ldv,
+                                                               const cplx* __restrict__ part, int nchunks, int ldp, cplx* w,
+                                                               cplx* __restrict__ h_out) {
+    extern __shared__ __attribute__((aligned(16))) char rz_dyn[];
+    cplx* hs = reinterpret_cast<cplx*>(rz_dyn);  // ncols coefficients
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int64_t stride = (int64_t)gridDim.x * kLzThreads;
+    int64_t i = (int64_t)blockIdx.x * kLzThreads + threadIdx.x;
+    cplx v[kRzUnroll];
+#pragma unroll
+    for (int u = 0; u < kRzUnroll; ++u) v[u] = (i < n && u < ncols) ? rz_ld(V + i + (int64_t)u * ldv) : cplx{0.0, 0.0};
+    for (int c = q; c < ncols; c += 4) {
+        const cplx a = lz_finish_sum(part + (int64_t)c * ldp, nchunks, lane);
+        if (lane == 0) {
+            rz_st(hs + c, a);
+            if (blockIdx.x == 0) rz_st(h_out + c, a);
+        }
+    }
+    __syncthreads();
+    bool first = true;
+    for (; i < n; i += stride) {
+        cplx acc = cplx{0.0, 0.0};
+        for (int c0 = 0; c0 < ncols; c0 += kRzUnroll) {
+            if (!(first && c0 == 0)) {
+#pragma unroll
+                for (int u = 0; u < kRzUnroll; ++u) v[u] = (c0 + u < ncols) ? rz_ld(V + i + (int64_t)(c0 + u) * ldv) : cplx{0.0, 0.0};
+            }
+#pragma unroll
+            for (int u = 0; u < kRzUnroll; ++u)
+                if (c0 + u < ncols) fma_acc(acc, rz_ld(hs + c0 + u), v[u]);
+        }
+        first = false;
+        rz_st(w + i, s_sub(rz_ld(w + i), acc));
+    }
+}
+
+// From the partial sums of w^H t (part[0..nchunks), lz_finish_sum): beta^2 = its real part, then v_next = w / beta and
+// rhs_next = t / beta.  Workgroup 0 leaves beta^2, the imaginary part (rounding) and the four sums of the two inner-solve checks
+// (chk_part, nchk quadruples) in out[0..6).  A beta^2 that is not positive and finite scales by zero: the host reads it from the slot
+// and stops.
+__global__ __launch_bounds__(kLzThreads) void rz_tail_kernel(int64_t n, const cplx* w, const cplx* t, const cplx* __restrict__ part, int nchunks,
+                                                             cplx* vnext, cplx* rhs_next, const double* __restrict__ chk_part, int nchk,
+                                                             double* __restrict__ out) {
+    __shared__ double b2s;
+    if (threadIdx.x < 64) {
+        const cplx a = lz_finish_sum(part, nchunks, threadIdx.x);
+        if (threadIdx.x == 0) b2s = a.re;
+        if (blockIdx.x == 0) {
+            double c[4] = {0.0, 0.0, 0.0, 0.0};
+            if (chk_part)
+                for (int k = threadIdx.x; k < nchk; k += 64) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) c[q] += chk_part[4 * k + q];
+                }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) c[q] = lz_wave_sum(c[q]);
+            if (threadIdx.x == 0) {
+                out[0] = a.re;
+                out[1] = a.im;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) out[2 + q] = c[q];
+            }
+        }
+    }
+    __syncthreads();
+    const double b2 = b2s;
+    const double inv = (b2 > 0.0 && b2 < 1.7e308) ? 1.0 / sqrt(b2) : 0.0;
+    const int64_t stride = (int64_t)gridDim.x * kLzThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kLzThreads + threadIdx.x; i < n; i += stride) {
+        const cplx wi = rz_ld(w + i), ti = rz_ld(t + i);
+        rz_st(vnext + i, s_mul(inv, wi));
+        rz_st(rhs_next + i, s_mul(inv, ti));
+    }
 }
 
 // the fused kernels unless LSA_LANCZOS_FUSED=0 (read once per process, like LSA_KRYLOV_FUSED): then k_multi_dot + k_multi_axpy
@@ -266,111 +446,236 @@ struct lsa_lanczos {
     lsa_op_parts P{};
     int64_t n = 0;
     int32_t ncv = 0;
-    // the n x (ncv + 1) arrays: the basis, the restart's second basis and (with a row permutation, on first use) the Ritz vectors in
-    // the caller's numbering
-    double *V = nullptr, *V2 = nullptr, *xtmp = nullptr;
+    int dtype = LSA_F64;  // the scalar type of every vector below
+    size_t es = 8;        // ... and its bytes
+    const char* who = "lsa_lanczos";  // the owner's name, for the messages
+    const lsa_mat* Q = nullptr;       // the inner product (lanczos_set_inner_product); null: the standard problem, t aliases w
+    // the n x (ncv + 1) arrays: the basis, the restart's second basis (and the Ritz vectors) and, with a row permutation, the output in
+    // the caller's numbering (on first use)
+    char *V = nullptr, *V2 = nullptr;
+    void* xtmp = nullptr;
     int32_t* row_perm = nullptr;
-    double *w = nullptr, *t = nullptr, *z = nullptr, *r = nullptr;  // work vectors: OP v_j, M w, C w, the refinement's residual
-    double* rhs[2] = {nullptr, nullptr};  // M v_j of the current step / of the next one (a step that is redone finds its own intact)
+    void *w = nullptr, *t = nullptr, *z = nullptr, *r = nullptr;  // work vectors: OP v_j, Q w, and two for the operator (C w, a residual)
+    void* rhs[2] = {nullptr, nullptr};  // Q v_j of the current step / of the next one (a step that is redone finds its own intact)
     int cur = 0;
-    int32_t rhs_for = -1;   // rhs[cur] holds M v_j for this j, -1: nothing
-    double* part = nullptr;      // (ncv + 2) x kLzMaxChunks partial sums, a coefficient's chunks side by side
-    double* chk_part = nullptr;  // kLzMaxChunks pairs
-    double* slot = nullptr;      // h of pass 1 (ncv + 1), h of pass 2 (ncv + 1), beta^2, |rhs - C w|^2, |rhs|^2, the unfused form's w^T t,
-                                 // |w|^2 of a refined solve
-    double* qdev = nullptr;      // (ncv + 1)^2: the restart's and the Ritz vectors' coefficients
-    int ldp = 0;
+    int32_t rhs_for = -1;        // rhs[cur] holds Q v_j for this j, -1: nothing
+    void* part = nullptr;        // (ncv + 2) x kDotMaxChunks partial sums, a coefficient's chunks side by side
+    double* chk_part = nullptr;  // kDotMaxChunks times the sums of the step's checks
+    double* slot = nullptr;      // see lz_slot
+    void* qdev = nullptr;        // (ncv + 1)^2: the restart's and the Ritz vectors' coefficients
+    double* imag2 = nullptr;     // complex scalars: ncv + 1, what k_columns_canonical reports (not read)
     std::vector<double> hslot;
-    // another operator behind a step than the single solve (lanczos_set_operator), and the right-hand side of its last solve: the
-    // check pair of the step's first reduction is (chk_b, z) then
+    // the operator behind a step and the checks its last enqueue named; builtin: the single solve of a real basis
+    lanczos_operator builtin{};
     const lanczos_operator* hook = nullptr;
-    const double* chk_b = nullptr;
+    lanczos_check chk[2] = {};
+    bool refine_used = false;  // what the default operator's solve being judged was queued with
 };
 
 namespace {
 
-size_t lz_slot_doubles(int32_t ncv) { return (size_t)2 * (ncv + 1) + 5; }
+// The slot, in doubles: h of pass 1 and h of pass 2 (ncv + 1 scalars each), then what the tail kernel writes at `out` -- beta^2 (complex:
+// and Im w^H t, rounding), |b - z|^2 and |b|^2 per check from `chk` -- then the unfused form's w^H t (a scalar, at `wt`) and |solution|^2 of
+// the checks' refined solves from `xnorm`.
+struct LzSlot {
+    size_t h, out, chk, wt, xnorm, doubles;
+};
+LzSlot lz_slot(const lsa_lanczos* l) {
+    const size_t sc = l->es / sizeof(double), nchk = sc;  // doubles per scalar; one check on the real basis, two on the complex one
+    LzSlot s;
+    s.h = sc * (size_t)(l->ncv + 1);
+    s.out = 2 * s.h;
+    s.chk = s.out + sc;
+    s.wt = s.chk + 2 * nchk;
+    s.xnorm = s.wt + sc;
+    s.doubles = s.xnorm + nchk;
+    return s;
+}
+
+int lz_nchecks(const lsa_lanczos* l) { return l->dtype == LSA_C128 ? 2 : 1; }
 
 void lz_free(lsa_lanczos* l) {
-    for (void* p : {(void*)l->V, (void*)l->V2, (void*)l->xtmp, (void*)l->row_perm, (void*)l->w, (void*)l->t, (void*)l->z, (void*)l->r, (void*)l->rhs[0],
-                    (void*)l->rhs[1], (void*)l->part, (void*)l->chk_part, (void*)l->slot, (void*)l->qdev})
+    for (void* p : {(void*)l->V, (void*)l->V2, l->xtmp, (void*)l->row_perm, l->w, l->t, l->z, l->r, l->rhs[0], l->rhs[1], l->part, (void*)l->chk_part,
+                    (void*)l->slot, l->qdev, (void*)l->imag2})
         if (p) (void)hipFree(p);
     delete l;
 }
 
-double* lz_col(const lsa_lanczos* l, int32_t j) { return l->V + (size_t)j * (size_t)l->n; }
+void* lz_col(const lsa_lanczos* l, int32_t j) { return l->V + (size_t)j * (size_t)l->n * l->es; }
 
-// t = M w (or t aliases w for a standard problem)
-int lz_mass(lsa_ctx* ctx, lsa_lanczos* l, const double* x, double* y) {
-    if (!l->P.Kmul) return LSA_OK;
+// t = Q w (or t aliases w for a standard problem)
+int lz_mass(lsa_ctx* ctx, lsa_lanczos* l, const void* x, void* y) {
+    if (!l->Q) return LSA_OK;
     ++l->P.st->spmv_calls;
-    return k_spmv(ctx, l->P.Kmul, LSA_F64, x, y);
+    return k_spmv(ctx, l->Q, l->dtype, x, y);
 }
 
-// M-orthogonalise l->w against the columns 0..ncols-1 (two passes), then v = w / beta into column `target` and M v into the
-// other right-hand side buffer; the slot's beta^2 and check sums are read back by the caller.  chk: this step's check pairs ride
-// in the first reduction.
+int lz_grid(lsa_ctx* ctx, int64_t n, int per_cu) {
+    return (int)std::max<int64_t>(std::min<int64_t>((n + kLzThreads - 1) / kLzThreads, (int64_t)ctx->num_cu * per_cu), 1);
+}
+
+// the three launches of the fused form by scalar type.  dot: ncols basis columns and w against t, the step's checks with chk
+void lz_launch_dot(lsa_ctx* ctx, lsa_lanczos* l, int nchunks, int64_t rows_per_block, int ncols, const void* t, bool chk) {
+    const dim3 grid(nchunks, (ncols + 1 + kLzColTile - 1) / kLzColTile);
+    const lanczos_check none{}, &c0 = chk ? l->chk[0] : none, &c1 = chk ? l->chk[1] : none;
+    double* chk_part = chk ? l->chk_part : nullptr;
+    if (l->dtype == LSA_F64)
+        hipLaunchKernelGGL(lz_dot_kernel, grid, dim3(kLzThreads), 0, ctx->stream, l->n, ncols, rows_per_block, (const double*)l->V, l->n, (const double*)t,
+                           (const double*)l->w, (double*)l->part, nchunks, (const double*)c0.b, (const double*)c0.z, chk_part);
+    else
+        hipLaunchKernelGGL(rz_dot_kernel, grid, dim3(kLzThreads), 0, ctx->stream, l->n, ncols, rows_per_block, (const cplx*)l->V, l->n, (const cplx*)t,
+                           (const cplx*)l->w, (cplx*)l->part, nchunks, (const cplx*)c0.b, (const cplx*)c0.z, (const cplx*)c1.b, (const cplx*)c1.z, chk_part);
+}
+
+// update: w -= V h from the partial sums, h to h_out.  Every workgroup finishes h for itself: a few hundred of them, their rows
+// strided over the grid
+void lz_launch_update(lsa_ctx* ctx, lsa_lanczos* l, int nchunks, int ncols, double* h_out) {
+    const dim3 grid(lz_grid(ctx, l->n, 2));
+    if (l->dtype == LSA_F64)
+        hipLaunchKernelGGL(lz_update_kernel, grid, dim3(kLzThreads), (size_t)ncols * l->es, ctx->stream, l->n, ncols, (const double*)l->V, l->n,
+                           (const double*)l->part, nchunks, nchunks, (double*)l->w, h_out);
+    else
+        hipLaunchKernelGGL(rz_update_kernel, grid, dim3(kLzThreads), (size_t)ncols * l->es, ctx->stream, l->n, ncols, (const cplx*)l->V, l->n,
+                           (const cplx*)l->part, nchunks, nchunks, (cplx*)l->w, (cplx*)h_out);
+}
+
+// tail: beta^2 from nparts partial sums at part, v_next and rhs_next, the slot's tail (the checks' sums from nparts partial sums with chk)
+void lz_launch_tail(lsa_ctx* ctx, lsa_lanczos* l, const void* t, const void* part, int nparts, void* vnext, void* rhs_next, bool chk, double* out) {
+    const dim3 grid(lz_grid(ctx, l->n, 8));
+    const double* chk_part = chk ? l->chk_part : nullptr;
+    if (l->dtype == LSA_F64)
+        hipLaunchKernelGGL(lz_tail_kernel, grid, dim3(kLzThreads), 0, ctx->stream, l->n, (const double*)l->w, (const double*)t, (const double*)part, nparts,
+                           (double*)vnext, (double*)rhs_next, chk_part, nparts, out);
+    else
+        hipLaunchKernelGGL(rz_tail_kernel, grid, dim3(kLzThreads), 0, ctx->stream, l->n, (const cplx*)l->w, (const cplx*)t, (const cplx*)part, nparts,
+                           (cplx*)vnext, (cplx*)rhs_next, chk_part, nparts, out);
+}
+
+// Q-orthogonalise l->w against the columns 0..ncols-1 (two passes), then v = w / beta into column `target` and Q v into the
+// other right-hand side buffer; the slot's beta^2 and check sums are read back by the caller.  chk: the checks the operator named
+// ride in the first reduction.
 int lz_orth_tail(lsa_ctx* ctx, lsa_lanczos* l, int32_t ncols, int32_t target, bool chk) {
     const int64_t n = l->n;
-    const bool has_m = l->P.Kmul != nullptr;
-    const double* t = has_m ? l->t : l->w;
-    double* vnext = lz_col(l, target);
-    double* rhs_next = l->rhs[l->cur ^ 1];
-    double* out = l->slot + 2 * (size_t)(l->ncv + 1);
-    const double* chk_b = l->chk_b ? l->chk_b : l->rhs[l->cur];
+    const void* t = l->Q ? l->t : l->w;
+    void* vnext = lz_col(l, target);
+    void* rhs_next = l->rhs[l->cur ^ 1];
+    const LzSlot S = lz_slot(l);
+    double* out = l->slot + S.out;
+    const char* what = l->dtype == LSA_C128 ? "resolvent step" : "lanczos step";
     if (lz_fused()) {
-        // k_multi_dot's chunks: at most 2048 of them, whole multiples of 256 rows, at least 512 rows
-        int64_t rows_per_block = ((n + kLzMaxChunks - 1) / kLzMaxChunks + kLzThreads - 1) / kLzThreads * kLzThreads;
-        rows_per_block = std::max<int64_t>(rows_per_block, 2 * kLzThreads);
-        const int nchunks = (int)std::max<int64_t>((n + rows_per_block - 1) / rows_per_block, 1);
-        // every workgroup of the update finishes h for itself: a few hundred of them, their rows strided over the grid
-        const int ublocks = (int)std::max<int64_t>(std::min<int64_t>((n + kLzThreads - 1) / kLzThreads, (int64_t)ctx->num_cu * 2), 1);
+        int64_t rows_per_block;
+        const int nchunks = dot_chunks(n, &rows_per_block);
         for (int pass = 0; pass < 2 && ncols > 0; ++pass) {
             LSA_CHECK(lz_mass(ctx, l, l->w, l->t));
-            const int tiles = (ncols + 1 + kLzColTile - 1) / kLzColTile;
-            const bool c = chk && pass == 0;
-            hipLaunchKernelGGL(lz_dot_kernel, dim3(nchunks, tiles), dim3(kLzThreads), 0, ctx->stream, n, ncols, rows_per_block, l->V, n, t, l->w, l->part,
-                               nchunks, c ? chk_b : nullptr, c ? l->z : nullptr, c ? l->chk_part : nullptr);
-            hipLaunchKernelGGL(lz_update_kernel, dim3(ublocks), dim3(kLzThreads), (size_t)ncols * sizeof(double), ctx->stream, n, ncols, l->V,
-                               n, l->part, nchunks, nchunks, l->w, l->slot + (size_t)pass * (l->ncv + 1));
+            lz_launch_dot(ctx, l, nchunks, rows_per_block, ncols, t, chk && pass == 0);
+            lz_launch_update(ctx, l, nchunks, ncols, l->slot + (size_t)pass * S.h);
         }
         LSA_CHECK(lz_mass(ctx, l, l->w, l->t));
-        const bool c = chk && ncols == 0;
-        hipLaunchKernelGGL(lz_dot_kernel, dim3(nchunks, 1), dim3(kLzThreads), 0, ctx->stream, n, 0, rows_per_block, l->V, n, t, l->w, l->part, nchunks,
-                           c ? chk_b : nullptr, c ? l->z : nullptr, c ? l->chk_part : nullptr);
-        const int tblocks = (int)std::max<int64_t>(std::min<int64_t>((n + kLzThreads - 1) / kLzThreads, (int64_t)ctx->num_cu * 8), 1);
-        hipLaunchKernelGGL(lz_tail_kernel, dim3(tblocks), dim3(kLzThreads), 0, ctx->stream, n, l->w, t, l->part, nchunks, vnext, rhs_next,
-                           chk ? l->chk_part : nullptr, nchunks, out);
-        return lz_check_launch(ctx, "lanczos step");
+        lz_launch_dot(ctx, l, nchunks, rows_per_block, 0, t, chk && ncols == 0);
+        lz_launch_tail(ctx, l, t, l->part, nchunks, vnext, rhs_next, chk, out);
+        return lsa_check_launch(ctx, what);
     }
     // the unfused form: the library's multi-dot and multi-axpy, the same tail with single partial sums
-    if (chk) LSA_CHECK(k_residual_norms(ctx, LSA_F64, n, chk_b, l->z, l->r, l->chk_part));
+    for (int k = 0; chk && k < lz_nchecks(l); ++k) LSA_CHECK(k_residual_norms(ctx, l->dtype, n, l->chk[k].b, l->chk[k].z, l->r, l->chk_part + 2 * k));
     for (int pass = 0; pass < 2 && ncols > 0; ++pass) {
         LSA_CHECK(lz_mass(ctx, l, l->w, l->t));
-        double* h = l->slot + (size_t)pass * (l->ncv + 1);
-        LSA_CHECK(k_multi_dot(ctx, LSA_F64, n, ncols, l->V, n, t, h));
-        LSA_CHECK(k_multi_axpy(ctx, LSA_F64, n, ncols, l->V, n, h, l->w, nullptr));
+        double* h = l->slot + (size_t)pass * S.h;
+        LSA_CHECK(k_multi_dot(ctx, l->dtype, n, ncols, l->V, n, t, h));
+        LSA_CHECK(k_multi_axpy(ctx, l->dtype, n, ncols, l->V, n, h, l->w, nullptr));
     }
     LSA_CHECK(lz_mass(ctx, l, l->w, l->t));
-    LSA_CHECK(k_multi_dot(ctx, LSA_F64, n, 1, l->w, n, t, out + 3));
-    const int tblocks = (int)std::max<int64_t>(std::min<int64_t>((n + kLzThreads - 1) / kLzThreads, (int64_t)ctx->num_cu * 8), 1);
-    hipLaunchKernelGGL(lz_tail_kernel, dim3(tblocks), dim3(kLzThreads), 0, ctx->stream, n, l->w, t, out + 3, 1, vnext, rhs_next,
-                       chk ? l->chk_part : nullptr, 1, out);
-    return lz_check_launch(ctx, "lanczos step (unfused)");
+    LSA_CHECK(k_multi_dot(ctx, l->dtype, n, 1, l->w, n, t, l->slot + S.wt));
+    lz_launch_tail(ctx, l, t, l->slot + S.wt, 1, vnext, rhs_next, chk, out);
+    return lsa_check_launch(ctx, l->dtype == LSA_C128 ? "resolvent step (unfused)" : "lanczos step (unfused)");
 }
 
 // the slot to the host: one synchronisation
 int lz_read_slot(lsa_ctx* ctx, lsa_lanczos* l) {
-    const size_t bytes = lz_slot_doubles(l->ncv) * sizeof(double);
+    const size_t bytes = l->hslot.size() * sizeof(double);
     LSA_CHECK(lsa_ensure_scratch(ctx, 0, bytes));
     LSA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->pinned, l->slot, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (l->hook) LSA_CHECK(l->hook->read_back(ctx, l->hook->self));  // (its log travels behind the same synchronisation)
+    if (l->hook && l->hook->read_back) LSA_CHECK(l->hook->read_back(ctx, l->hook->self));  // (its log travels behind the same synchronisation)
     LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(l->hslot.data(), ctx->pinned, bytes);
     return LSA_OK;
 }
 
+// V2[:, 0:k] = V[:, 0:m] Y for the real host matrix Y (complex scalars: widened for k_basis_gemm)
+int lz_basis_times_real(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t k, const double* Y, int32_t ldy) {
+    if (l->dtype == LSA_F64) return basis_times_host_matrix(ctx, LSA_F64, l->n, m, k, l->V, Y, ldy, l->qdev, l->V2, 0);
+    std::vector<cplx> Yc((size_t)m * k);
+    for (int32_t c = 0; c < k; ++c)
+        for (int32_t i = 0; i < m; ++i) Yc[(size_t)c * m + i] = cplx{Y[(size_t)c * ldy + i], 0.0};
+    return basis_times_host_matrix(ctx, LSA_C128, l->n, m, k, l->V, Yc.data(), m, l->qdev, l->V2, 0);
+}
+
+// ---- the default operator of a real basis: the single solve, on the op's shared refinement flag -------------------------------------
+int lz_solve_enqueue(lsa_ctx* ctx, void* self, int32_t, const void* rhs, void* w, void* z, void* r, lanczos_check* chk) {
+    lsa_lanczos* l = (lsa_lanczos*)self;
+    const bool refine = l->refine_used = *l->P.refine;
+    // (w += C^-1 (rhs - C w) with refine: takes what large factors leave behind to rounding level)
+    LSA_CHECK(direct_solve_enqueue(ctx, l->op, LSA_F64, rhs, w, z, r, refine, l->chk_part));
+    if (refine) LSA_CHECK(k_nrm2(ctx, LSA_F64, l->n, w, chk[0].xnorm2_dev));  // for the backward-error judgement
+    chk[0].b = rhs;
+    chk[0].z = z;
+    chk[0].refined = refine;
+    return LSA_OK;
+}
+
+int lz_solve_judge(lsa_ctx* ctx, void* self, int32_t j, const lanczos_sums* s) {
+    lsa_lanczos* l = (lsa_lanczos*)self;
+    const bool refine = l->refine_used;
+    bool backward = false;
+    const int verdict = direct_solve_verdict(l->P, refine, s[0].res, s[0].bnorm, s[0].xnorm, &backward);
+    if (verdict == 0) {
+        if (backward) ++l->P.st->backward_accepted;
+        stats_book_direct_solve(l->P.st, 1, refine, s[0].res, s[0].bnorm);
+    } else if (verdict > 0) {  // from here on every step carries the refinement step; this one is done again
+        *l->P.refine = true;
+    } else {
+        lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_lanczos_extend: the inner solve of step %d left a relative residual of %.3e after its refinement "
+                                             "step (ksp_rtol %.1e) and a backward error above 1e-12 ||C||_F", j, s[0].bnorm > 0.0 ? s[0].res / s[0].bnorm : s[0].res,
+                      l->P.ksp_rtol);
+    }
+    return verdict;
+}
+
 }  // namespace
+
+int lanczos_create_basis(lsa_ctx* ctx, lsa_op* op, int32_t ncv, int dtype, const char* who, lsa_lanczos** out) {
+    lsa_op_parts P{};
+    LSA_CHECK(lsa_op_get_parts(op, &P));
+    lsa_lanczos* l = new lsa_lanczos();
+    l->ctx = ctx;
+    l->op = op;
+    l->P = P;
+    l->n = P.n;
+    l->ncv = ncv;
+    l->dtype = dtype;
+    l->es = dtype == LSA_C128 ? sizeof(cplx) : sizeof(double);
+    l->who = who;
+    l->Q = P.Kmul;
+    l->builtin = lanczos_operator{l, 1, lz_solve_enqueue, nullptr, lz_solve_judge};
+    l->hook = dtype == LSA_F64 ? &l->builtin : nullptr;
+    const LzSlot S = lz_slot(l);
+    l->hslot.assign(S.doubles, 0.0);
+    const size_t vb = (size_t)std::max<int64_t>(l->n, 1) * l->es, nchk = (size_t)lz_nchecks(l);
+    bool ok = hipMalloc((void**)&l->V, vb * (size_t)(ncv + 1)) == hipSuccess && hipMalloc((void**)&l->V2, vb * (size_t)(ncv + 1)) == hipSuccess;
+    for (void** p : {&l->w, &l->t, &l->z, &l->r, &l->rhs[0], &l->rhs[1]}) ok = ok && hipMalloc(p, vb) == hipSuccess;
+    ok = ok && hipMalloc(&l->part, (size_t)kDotMaxChunks * (size_t)(ncv + 2) * l->es) == hipSuccess &&
+         hipMalloc((void**)&l->chk_part, (size_t)kDotMaxChunks * 2 * nchk * sizeof(double)) == hipSuccess &&
+         hipMalloc((void**)&l->slot, S.doubles * sizeof(double)) == hipSuccess &&
+         hipMalloc(&l->qdev, (size_t)(ncv + 1) * (size_t)(ncv + 1) * l->es) == hipSuccess &&
+         (dtype == LSA_F64 || hipMalloc((void**)&l->imag2, (size_t)(ncv + 1) * sizeof(double)) == hipSuccess);
+    if (!ok) {
+        (void)hipGetLastError();
+        lz_free(l);
+        return lsa_set_error(ctx, LSA_ERR_OOM, "%s_create: out of device memory (n=%lld, ncv=%d)", who, (long long)P.n, ncv);
+    }
+    (void)hipMemsetAsync(l->slot, 0, S.doubles * sizeof(double), ctx->stream);
+    *out = l;
+    return LSA_OK;
+}
 
 int lanczos_shape(const lsa_lanczos* l, int64_t* n, int32_t* ncv) {
     if (!l) return LSA_ERR_ARG;
@@ -379,30 +684,46 @@ int lanczos_shape(const lsa_lanczos* l, int64_t* n, int32_t* ncv) {
     return LSA_OK;
 }
 
-void lanczos_set_operator(lsa_lanczos* l, const lanczos_operator* hook) { l->hook = hook; }
+int lanczos_set_operator(lsa_ctx* ctx, lsa_lanczos* l, const lanczos_operator* hook) {
+    if (!hook && l->dtype == LSA_F64) hook = &l->builtin;
+    if (hook && hook->nchecks != lz_nchecks(l))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the operator names %d checked solves a step, the step kernels of this basis take %d", l->who, hook->nchecks,
+                             lz_nchecks(l));
+    l->hook = hook;
+    return LSA_OK;
+}
 
-const double* lanczos_ritz_device(const lsa_lanczos* l) { return l->V2; }
+void lanczos_set_inner_product(lsa_lanczos* l, const lsa_mat* Q) {
+    l->Q = Q ? Q : l->P.Kmul;
+    l->rhs_for = -1;
+}
 
-int lanczos_inject(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, const double* host_v) {
-    if (!ctx || !l || !host_v) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos: null argument");
-    if (j < 0 || j > l->ncv) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos: column %d out of range", j);
-    LSA_HIP_CHECK(ctx, hipMemcpyAsync(l->w, host_v, (size_t)l->n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+void* lanczos_ritz_device(const lsa_lanczos* l) { return l->V2; }
+
+int lanczos_ritz_to_host(lsa_ctx* ctx, lsa_lanczos* l, int32_t nvec, void* X) {
+    return basis_columns_to_host(ctx, l->dtype, l->n, nvec, l->row_perm, l->V2, &l->xtmp, l->ncv + 1, X);
+}
+
+int lanczos_inject(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, const void* host_v) {
+    if (!ctx || !l || !host_v) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument", l ? l->who : "lsa_lanczos");
+    if (j < 0 || j > l->ncv) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: column %d out of range", l->who, j);
+    LSA_HIP_CHECK(ctx, hipMemcpyAsync(l->w, host_v, (size_t)l->n * l->es, hipMemcpyHostToDevice, ctx->stream));
     LSA_CHECK(lz_orth_tail(ctx, l, j, j, false));
     LSA_CHECK(lz_read_slot(ctx, l));
-    const double b2 = l->hslot[2 * (size_t)(l->ncv + 1)];
+    const double b2 = l->hslot[lz_slot(l).out];
     if (!(b2 > 0.0) || !std::isfinite(b2))
-        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos: v^T M v = %.3e for the injected vector: M is not positive definite on the Krylov space (or the "
-                                               "vector is zero or not finite)", b2);
+        return lsa_set_error(ctx, LSA_ERR_ARG, "%s: v^%s M v = %.3e for the injected vector: M is not positive definite on the Krylov space (or the "
+                                               "vector is zero or not finite)", l->who, l->dtype == LSA_C128 ? "H" : "T", b2);
     l->cur ^= 1;
     l->rhs_for = j;
     return LSA_OK;
 }
 
 int lanczos_restart(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t knew, const double* Y, int32_t ldy) {
-    if (!ctx || !l || !Y) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos restart: null argument");
-    if (m < 1 || m > l->ncv || knew < 1 || knew > m || ldy < m) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos restart: bad sizes m=%d knew=%d", m, knew);
-    LSA_CHECK(basis_times_host_matrix(ctx, LSA_F64, l->n, m, knew, l->V, Y, ldy, l->qdev, l->V2, 0));
-    LSA_CHECK(k_copy(ctx, LSA_F64, l->n, lz_col(l, m), l->V2 + (size_t)knew * (size_t)l->n));
+    if (!ctx || !l || !Y) return lsa_set_error(ctx, LSA_ERR_ARG, "%s restart: null argument", l ? l->who : "lsa_lanczos");
+    if (m < 1 || m > l->ncv || knew < 1 || knew > m || ldy < m) return lsa_set_error(ctx, LSA_ERR_ARG, "%s restart: bad sizes m=%d knew=%d", l->who, m, knew);
+    LSA_CHECK(lz_basis_times_real(ctx, l, m, knew, Y, ldy));
+    LSA_CHECK(k_copy(ctx, l->dtype, l->n, lz_col(l, m), l->V2 + (size_t)knew * (size_t)l->n * l->es));
     LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     std::swap(l->V, l->V2);
     if (l->rhs_for == m) l->rhs_for = knew;  // (the same vector under its new index)
@@ -410,23 +731,18 @@ int lanczos_restart(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t knew, const
     return LSA_OK;
 }
 
-int lanczos_ritz_vectors(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t nvec, const double* Y, int32_t ldy, double* X) {
-    if (!ctx || !l || !Y || !X) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos vectors: null argument");
-    if (m < 1 || m > l->ncv || nvec < 0 || nvec > l->ncv || ldy < m) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos vectors: bad sizes");
+int lanczos_ritz_vectors(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t nvec, const double* Y, int32_t ldy, void* X) {
+    if (!ctx || !l || !Y || !X) return lsa_set_error(ctx, LSA_ERR_ARG, "%s vectors: null argument", l ? l->who : "lsa_lanczos");
+    if (m < 1 || m > l->ncv || nvec < 0 || nvec > l->ncv || ldy < m) return lsa_set_error(ctx, LSA_ERR_ARG, "%s vectors: bad sizes", l->who);
     if (nvec == 0) return LSA_OK;
-    const size_t vb = (size_t)l->n * sizeof(double);
-    LSA_CHECK(basis_times_host_matrix(ctx, LSA_F64, l->n, m, nvec, l->V, Y, ldy, l->qdev, l->V2, 0));
-    hipLaunchKernelGGL(lz_sign_kernel, dim3(nvec), dim3(kLzThreads), 0, ctx->stream, l->n, l->V2, l->n);
-    const double* src = l->V2;
-    if (l->row_perm) {
-        if (!l->xtmp) LSA_HIP_ALLOC(ctx, hipMalloc((void**)&l->xtmp, std::max<size_t>(vb, 8) * (size_t)(l->ncv + 1)));
-        LSA_CHECK(k_scatter_rows(ctx, LSA_F64, l->n, nvec, l->row_perm, l->V2, l->xtmp));
-        src = l->xtmp;
+    LSA_CHECK(lz_basis_times_real(ctx, l, m, nvec, Y, ldy));
+    if (l->dtype == LSA_F64) {
+        hipLaunchKernelGGL(lz_sign_kernel, dim3(nvec), dim3(kLzThreads), 0, ctx->stream, l->n, (double*)l->V2, l->n);
+        LSA_CHECK(lsa_check_launch(ctx, "lanczos vectors"));
+    } else {
+        LSA_CHECK(k_columns_canonical(ctx, l->n, nvec, l->V2, l->n, 0, l->imag2));
     }
-    LSA_CHECK(lz_check_launch(ctx, "lanczos vectors"));
-    LSA_HIP_CHECK(ctx, hipMemcpyAsync(X, src, vb * (size_t)nvec, hipMemcpyDeviceToHost, ctx->stream));
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return LSA_OK;
+    return lanczos_ritz_to_host(ctx, l, nvec, X);
 }
 
 extern "C" {
@@ -440,29 +756,7 @@ int lsa_lanczos_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, lsa_lanczos** out)
     if (!P.nd || !P.Kfac || P.Kfac->dtype != LSA_F64 || (P.Kmul && P.Kmul->dtype != LSA_F64))
         return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_create: needs real matrices, a real shift and the exact LU (pc_type 2) of K - sigma M");
     if ((int64_t)ncv > P.n) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_create: ncv = %d exceeds the problem size %lld", ncv, (long long)P.n);
-    lsa_lanczos* l = new lsa_lanczos();
-    l->ctx = ctx;
-    l->op = op;
-    l->P = P;
-    l->n = P.n;
-    l->ncv = ncv;
-    l->ldp = ncv + 2;
-    l->hslot.assign(lz_slot_doubles(ncv), 0.0);
-    const size_t vb = (size_t)std::max<int64_t>(l->n, 1) * sizeof(double);
-    bool ok = hipMalloc((void**)&l->V, vb * (size_t)(ncv + 1)) == hipSuccess && hipMalloc((void**)&l->V2, vb * (size_t)(ncv + 1)) == hipSuccess;
-    for (double** p : {&l->w, &l->t, &l->z, &l->r, &l->rhs[0], &l->rhs[1]}) ok = ok && hipMalloc((void**)p, vb) == hipSuccess;
-    ok = ok && hipMalloc((void**)&l->part, (size_t)kLzMaxChunks * l->ldp * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&l->chk_part, (size_t)kLzMaxChunks * 2 * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&l->slot, lz_slot_doubles(ncv) * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&l->qdev, (size_t)(ncv + 1) * (size_t)(ncv + 1) * sizeof(double)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        lz_free(l);
-        return lsa_set_error(ctx, LSA_ERR_OOM, "lsa_lanczos_create: out of device memory (n=%lld, ncv=%d)", (long long)P.n, ncv);
-    }
-    (void)hipMemsetAsync(l->slot, 0, lz_slot_doubles(ncv) * sizeof(double), ctx->stream);
-    *out = l;
-    return LSA_OK;
+    return lanczos_create_basis(ctx, op, ncv, LSA_F64, "lsa_lanczos", out);
 }
 
 void lsa_lanczos_destroy(lsa_lanczos* l) {
@@ -473,82 +767,66 @@ void lsa_lanczos_destroy(lsa_lanczos* l) {
 
 int lsa_lanczos_set_row_permutation(lsa_ctx* ctx, lsa_lanczos* l, const int32_t* perm) {
     if (!ctx || !l) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_set_row_permutation: null argument");
-    return basis_upload_row_permutation(ctx, "lsa_lanczos_set_row_permutation", l->n, perm, &l->row_perm);
+    const std::string who = std::string(l->who) + "_set_row_permutation";
+    return basis_upload_row_permutation(ctx, who.c_str(), l->n, perm, &l->row_perm);
 }
 
 int lsa_lanczos_set_start(lsa_ctx* ctx, lsa_lanczos* l, const double* host_v) { return lanczos_inject(ctx, l, 0, host_v); }
 
 int lsa_lanczos_extend(lsa_ctx* ctx, lsa_lanczos* l, int32_t j0, int32_t j1, double* T, int32_t ldt, int32_t* breakdown) {
-    if (!ctx || !l || !T) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_extend: null argument");
-    if (j0 < 0 || j1 < j0 || j1 > l->ncv || ldt < j1 + 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_extend: bad step range [%d, %d) for ncv %d", j0, j1, l->ncv);
+    if (!ctx || !l || !T) return lsa_set_error(ctx, LSA_ERR_ARG, "%s_extend: null argument", l ? l->who : "lsa_lanczos");
+    if (j0 < 0 || j1 < j0 || j1 > l->ncv || ldt < j1 + 1) return lsa_set_error(ctx, LSA_ERR_ARG, "%s_extend: bad step range [%d, %d) for ncv %d", l->who, j0, j1, l->ncv);
+    if (!l->hook) return lsa_set_error(ctx, LSA_ERR_ARG, "%s_extend: the basis has no operator behind its step", l->who);
     if (breakdown) *breakdown = -1;
     const double t0 = now_s();
-    const int64_t n = l->n;
-    lsa_stats* st = l->P.st;
-    const double rtol = l->P.ksp_rtol;
-    const size_t b2_at = 2 * (size_t)(l->ncv + 1);
+    const bool cx = l->dtype == LSA_C128;
+    const size_t sc = cx ? 2 : 1;  // doubles per scalar
+    const int nchk = lz_nchecks(l);
+    const LzSlot S = lz_slot(l);
+    const double* h = l->hslot.data();
     int rc = LSA_OK;
     for (int32_t j = j0; j < j1 && rc == LSA_OK; ++j) {
         if (l->rhs_for != j) {  // (after lsa_lanczos_basis users, a restart that moved another column here, or the standard problem's first step)
-            if (l->P.Kmul) rc = lz_mass(ctx, l, lz_col(l, j), l->rhs[l->cur]);
-            else rc = k_copy(ctx, LSA_F64, n, lz_col(l, j), l->rhs[l->cur]);
+            if (l->Q) rc = lz_mass(ctx, l, lz_col(l, j), l->rhs[l->cur]);
+            else rc = k_copy(ctx, l->dtype, l->n, lz_col(l, j), l->rhs[l->cur]);
             if (rc != LSA_OK) break;
             l->rhs_for = j;
         }
-        while (l->hook) {
-            // the hook's operator: it queues w = OP v_j from rhs = M v_j and names the right-hand side of its last solve (z = C w of
-            // that solve is in l->z); the step's reductions, tail and single read-back are those of the default; the hook judges
-            bool refined = false;
-            rc = l->hook->enqueue(ctx, l->hook->self, j, l->rhs[l->cur], l->w, l->z, l->r, l->slot + b2_at + 4, &l->chk_b, &refined);
+        while (true) {
+            // the operator queues w = OP v_j from rhs = Q v_j and names its checks; their sums ride in the step's first reduction and come
+            // back with the slot, the step's one read-back; the operator judges
+            for (int k = 0; k < nchk; ++k) l->chk[k] = lanczos_check{nullptr, nullptr, false, l->slot + S.xnorm + k};
+            rc = l->hook->enqueue(ctx, l->hook->self, j, l->rhs[l->cur], l->w, l->z, l->r, l->chk);
             if (rc == LSA_OK) rc = lz_orth_tail(ctx, l, j + 1, j + 1, true);
             if (rc == LSA_OK) rc = lz_read_slot(ctx, l);
             if (rc != LSA_OK) break;
-            const int verdict = l->hook->judge(ctx, l->hook->self, j, std::sqrt(l->hslot[b2_at + 1]), std::sqrt(l->hslot[b2_at + 2]),
-                                               refined ? std::sqrt(l->hslot[b2_at + 4]) : 0.0);
+            lanczos_sums sums[2];
+            for (int k = 0; k < nchk; ++k)
+                sums[k] = lanczos_sums{std::sqrt(h[S.chk + 2 * k]), std::sqrt(h[S.chk + 2 * k + 1]), l->chk[k].refined ? std::sqrt(h[S.xnorm + k]) : 0.0};
+            const int verdict = l->hook->judge(ctx, l->hook->self, j, sums);
             if (verdict == 0) break;
-            if (verdict < 0) {  // (the hook has set the error)
+            if (verdict < 0) {  // (the operator has set the error)
                 rc = LSA_ERR_DIVERGED;
                 break;
             }
         }
-        while (!l->hook) {
-            const bool refine = *l->P.refine;
-            // (w += C^-1 (rhs - C w) with refine: takes what large factors leave behind to rounding level)
-            rc = direct_solve_enqueue(ctx, l->op, LSA_F64, l->rhs[l->cur], l->w, l->z, l->r, refine, l->chk_part);
-            if (rc == LSA_OK && refine) rc = k_nrm2(ctx, LSA_F64, n, l->w, l->slot + b2_at + 4);  // for the backward-error judgement below
-            if (rc == LSA_OK) rc = lz_orth_tail(ctx, l, j + 1, j + 1, true);
-            if (rc == LSA_OK) rc = lz_read_slot(ctx, l);
-            if (rc != LSA_OK) break;
-            const double res = std::sqrt(l->hslot[b2_at + 1]), bnorm = std::sqrt(l->hslot[b2_at + 2]);
-            // The library's judgement of a direct solve (gmres_run): within ksp_rtol, or, after the refinement step, a backward
-            // error within 1e-12 ||C||_F -- ||rhs - C w|| cannot go below eps ||C|| ||w||, whatever the solver.
-            const bool backward = refine && res > rtol * bnorm && l->P.normF > 0.0 && res <= 1e-12 * l->P.normF * std::sqrt(l->hslot[b2_at + 4]);
-            if (backward) ++st->backward_accepted;
-            if (res <= rtol * bnorm || backward) {
-                stats_book_direct_solve(st, 1, refine, res, bnorm);
-                break;
-            }
-            if (!refine && std::isfinite(res)) {  // from here on every step carries the refinement step; this one is done again
-                *l->P.refine = true;
-                continue;
-            }
-            rc = lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_lanczos_extend: the inner solve of step %d left a relative residual of %.3e after its refinement "
-                                                      "step (ksp_rtol %.1e) and a backward error above 1e-12 ||C||_F", j, bnorm > 0.0 ? res / bnorm : res, rtol);
-            break;
-        }
         if (rc != LSA_OK) break;
-        const double alpha = l->hslot[j] + l->hslot[(size_t)(l->ncv + 1) + j];
-        const double b2 = l->hslot[b2_at];
+        // Re h_i of both passes.  alpha_j = Re h_j: OP is self-adjoint in the inner product, the imaginary part is rounding and is dropped
+        auto re = [&](int32_t i) { return h[sc * (size_t)i] + h[S.h + sc * (size_t)i]; };
+        const double alpha = re(j);
+        const double b2 = h[S.out];
         if (!std::isfinite(alpha) || !std::isfinite(b2)) {
-            rc = lsa_set_error(ctx, LSA_ERR_NONFINITE, "Lanczos: non-finite recurrence coefficient at step %d", j);
+            rc = lsa_set_error(ctx, LSA_ERR_NONFINITE, "%s: non-finite recurrence coefficient at step %d", cx ? "resolvent" : "Lanczos", j);
             break;
         }
         // what is left of w after both passes, against the size of what was taken out of it (the rule of the general loop's columns)
         double colmax = std::fabs(alpha);
-        for (int32_t i = 0; i < j; ++i) colmax = std::max(colmax, std::fabs(l->hslot[i] + l->hslot[(size_t)(l->ncv + 1) + i]));
+        for (int32_t i = 0; i < j; ++i)
+            colmax = std::max(colmax, cx ? std::hypot(re(i), h[2 * (size_t)i + 1] + h[S.h + 2 * (size_t)i + 1]) : std::fabs(re(i)));
         const double thr = 1e-14 * std::max(colmax, 1e-300);
         if (b2 < -thr * thr) {
-            rc = lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_extend: w^T M w = %.3e at step %d: M is not positive definite on the Krylov space", b2, j);
+            rc = lsa_set_error(ctx, LSA_ERR_ARG, "%s_extend: w^%s M w = %.3e at step %d: M is not positive %s on the Krylov space", l->who, cx ? "H" : "T", b2, j,
+                               cx ? "semidefinite" : "definite");
             break;
         }
         const double beta = b2 > 0.0 ? std::sqrt(b2) : 0.0;
@@ -564,14 +842,14 @@ int lsa_lanczos_extend(lsa_ctx* ctx, lsa_lanczos* l, int32_t j0, int32_t j1, dou
             break;
         }
     }
-    st->seconds_solve += now_s() - t0;
+    l->P.st->seconds_solve += now_s() - t0;
     return rc;
 }
 
 int lsa_lanczos_basis(lsa_ctx* ctx, const lsa_lanczos* l, int32_t ncols, double* host_V) {
-    if (!ctx || !l || !host_V) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_basis: null argument");
-    if (ncols < 0 || ncols > l->ncv + 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_lanczos_basis: %d columns of %d", ncols, l->ncv + 1);
-    LSA_HIP_CHECK(ctx, hipMemcpyAsync(host_V, l->V, (size_t)l->n * (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (!ctx || !l || !host_V) return lsa_set_error(ctx, LSA_ERR_ARG, "%s_basis: null argument", l ? l->who : "lsa_lanczos");
+    if (ncols < 0 || ncols > l->ncv + 1) return lsa_set_error(ctx, LSA_ERR_ARG, "%s_basis: %d columns of %d", l->who, ncols, l->ncv + 1);
+    LSA_HIP_CHECK(ctx, hipMemcpyAsync(host_V, l->V, (size_t)l->n * (size_t)ncols * l->es, hipMemcpyDeviceToHost, ctx->stream));
     LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return LSA_OK;
 }

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -80,6 +82,19 @@ __host__ __device__ inline cplx to_cplx(double a) { return cplx{a, 0.0}; }
 __host__ __device__ inline cplx to_cplx(cplx a) { return a; }
 __host__ __device__ inline void s_from(double& out, double re, double) { out = re; }
 __host__ __device__ inline void s_from(cplx& out, double re, double im) { out = cplx{re, im}; }
+// a complex entry moved as one 16-byte access (cplx itself is only 8-byte aligned: two 8-byte accesses otherwise), for arrays that are
+// 16-byte aligned: hipMalloc, columns of 16 n bytes, offsets in whole complex numbers (the complex step kernels of lanczos.hip, resolvent.hip)
+typedef double rz_d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ cplx rz_ld(const cplx* p) {
+    const rz_d2 v = *reinterpret_cast<const rz_d2*>(p);
+    return cplx{v.x, v.y};
+}
+__device__ __forceinline__ void rz_st(cplx* p, cplx v) {
+    rz_d2 o;
+    o.x = v.re;
+    o.y = v.im;
+    *reinterpret_cast<rz_d2*>(p) = o;
+}
 
 // ---- objects behind the opaque handles ----------------------------------------------------------------
 struct lsa_ctx {
@@ -196,6 +211,21 @@ inline bool env_flag(const char* name, bool dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) != 0 : dflt;
 }
+// after a kernel launch: the launch's own error, if any, as the library's status
+inline int lsa_check_launch(lsa_ctx* ctx, const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lsa_set_error(ctx, LSA_ERR_HIP, "%s: kernel launch failed: %s", what, hipGetErrorString(e));
+    return LSA_OK;
+}
+// k_multi_dot's row chunks, which the fused reductions of lanczos.hip and growth.hip keep for the sake of its bits: at most 2048 of
+// them, whole multiples of 256 rows, at least 512 rows.  Returns the number of chunks (= partial sums per coefficient).
+constexpr int kDotMaxChunks = 2048;
+inline int dot_chunks(int64_t n, int64_t* rows_per_chunk) {
+    int64_t rows = ((n + kDotMaxChunks - 1) / kDotMaxChunks + 255) / 256 * 256;
+    rows = std::max<int64_t>(rows, 512);
+    *rows_per_chunk = rows;
+    return (int)std::max<int64_t>((n + rows - 1) / rows, 1);
+}
 
 #define LSA_HIP_CHECK(ctx, expr)                                                                         \
     do {                                                                                                 \
@@ -308,13 +338,16 @@ int k_basis_gemm(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V
 // Out[perm[i], c] = In[i, c] for the columns c < ncols (both n x ncols, leading dimension n)
 int k_scatter_rows(lsa_ctx* ctx, int dtype, int64_t n, int ncols, const int32_t* perm, const void* In, void* Out);
 
-// ---- what the basis handles lsa_krylov (solver.hip) and lsa_lanczos (lanczos.hip) share (solver.hip) ----------------------
+// ---- what the basis handles lsa_krylov (solver.hip) and lsa_lanczos (lanczos.hip) and their owners share (solver.hip) ------
 // *row_perm <- a device copy of perm after checking that it permutes 0..n-1 (null: dropped); who: the caller's name for the message
 int basis_upload_row_permutation(lsa_ctx* ctx, const char* who, int64_t n, const int32_t* perm, int32_t** row_perm);
 // Out[:, 0:k] = V[:, 0:m] Q for a host matrix Q (m x k, leading dimension ldq; V and Out: n): packed densely into the pinned
 // scratch (kept pinned_extra bytes longer for the caller), uploaded to qdev, k_basis_gemm
 int basis_times_host_matrix(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, const void* V, const void* Q, int ldq, void* qdev, void* Out,
                             size_t pinned_extra);
+// device columns (n x ncols, leading dimension n) to the host in the caller's numbering: scattered through row_perm (null: as they
+// are) into *xtmp, which is made on first use with room for xtmp_cols columns; synchronises
+int basis_columns_to_host(lsa_ctx* ctx, int dtype, int64_t n, int ncols, const int32_t* row_perm, const void* dev, void** xtmp, int xtmp_cols, void* host);
 // The direct inner solve of a Krylov step, queued without a read-back: y = C^-1 rhs, z = C y and, with refine, one step of
 // iterative refinement (r = rhs - z, z = C^-1 r, y += z, z = C y; the two sums of that residual pass land in norms[0..2]).  C is
 // the operator's factorised matrix with its exact LU, rows and exchanges as the operator has them; the caller judges rhs - z.
@@ -365,37 +398,63 @@ struct lsa_op_parts {
     lsa_stats* st;
 };
 int lsa_op_get_parts(lsa_op* op, lsa_op_parts* out);
-// the pieces of the symmetric outer iteration that live with the basis (lanczos.hip); the loop itself is lsa_lanczos_solve (dense.hip)
+// The library's judgement of a direct solve x of right-hand side b (res = |b - C x|): within ksp_rtol, or, after the refinement step,
+// a backward error within 1e-12 ||C||_F -- |b - C x| cannot go below eps ||C|| |x|, whatever the solver.  0: accepted (*backward says
+// by which rule), 1: again with the refinement step switched on, -1: diverged.
+inline int direct_solve_verdict(const lsa_op_parts& P, bool refine, double res, double bnorm, double xnorm, bool* backward) {
+    *backward = refine && res > P.ksp_rtol * bnorm && P.normF > 0.0 && res <= 1e-12 * P.normF * xnorm;
+    if (res <= P.ksp_rtol * bnorm || *backward) return 0;
+    return (!refine && std::isfinite(res)) ? 1 : -1;
+}
+
+// ---- the basis of the self-adjoint outer iterations (lanczos.hip): real or complex scalars, orthonormal in a real symmetric inner
+// product, with an operator behind its step; the loop is lsa_lanczos_solve (dense.hip) -------------------------------------------
+// A basis of scalar type dtype (LSA_F64, LSA_C128) for an owner that has checked the operator itself; who: the owner's name in the
+// messages ("lsa_growth", "lsa_resolvent").  A basis with complex scalars has no operator until lanczos_set_operator gives it one.
+int lanczos_create_basis(lsa_ctx* ctx, lsa_op* op, int32_t ncv, int dtype, const char* who, lsa_lanczos** out);
 int lanczos_shape(const lsa_lanczos* l, int64_t* n, int32_t* ncv);
-// v_j = host vector M-orthonormalised against v_0..v_{j-1} (continues after a breakdown; j = 0: lsa_lanczos_set_start)
-int lanczos_inject(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, const double* host_v);
-// thick restart: V[:, 0:knew] = V[:, 0:m] Y (Y m x knew column-major on the host), V[:, knew] = V[:, m]
+// the inner product x^H Q y (Q real symmetric positive semidefinite; the operator's M on a new basis).  No right-hand side is left
+// over: a start vector must follow, the basis in hand being orthonormal in the old inner product.
+void lanczos_set_inner_product(lsa_lanczos* l, const lsa_mat* Q);
+// v_j = host vector orthonormalised against v_0..v_{j-1} (continues after a breakdown; j = 0: lsa_lanczos_set_start)
+int lanczos_inject(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, const void* host_v);
+// thick restart: V[:, 0:knew] = V[:, 0:m] Y (Y real, m x knew column-major on the host: the eigenvectors of the real projected
+// matrix), V[:, knew] = V[:, m]
 int lanczos_restart(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t knew, const double* Y, int32_t ldy);
-// X = V[:, 0:m] Y to the host in the caller's row numbering, each column's entry of largest magnitude positive
-int lanczos_ritz_vectors(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t nvec, const double* Y, int32_t ldy, double* X);
-// the columns lanczos_ritz_vectors left on the device (n x nvec, the basis' own row numbering)
-const double* lanczos_ritz_device(const lsa_lanczos* l);
-// Another operator behind a Lanczos step than the single solve w = C^-1 rhs (the default, hook == null): growth.hip's march.
+// X = V[:, 0:m] Y to the host in the caller's row numbering, each column's entry of largest magnitude (real) positive
+int lanczos_ritz_vectors(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t nvec, const double* Y, int32_t ldy, void* X);
+// the columns lanczos_ritz_vectors left on the device (n x nvec, the basis' own row numbering; an owner may overwrite them), and
+// nvec of them to the host in the caller's row numbering
+void* lanczos_ritz_device(const lsa_lanczos* l);
+int lanczos_ritz_to_host(lsa_ctx* ctx, lsa_lanczos* l, int32_t nvec, void* X);
+// The operator behind a step: it queues w = OP v_j and names the inner solves the step's first reduction checks.  The default of a
+// real basis is the single solve w = C^-1 rhs on the op's shared refinement flag; growth.hip puts a march of solves there,
+// resolvent.hip an adjoint solve, a weight and a forward solve.
+struct lanczos_check {  // one checked solve: right-hand side b, z = C (or C^H) times its solution, both of the basis' scalar type
+    const void *b, *z;
+    bool refined;        // the solve carried the refinement step and left |its solution|^2 at xnorm2_dev
+    double* xnorm2_dev;  // (given by the basis: it travels with the step's slot)
+};
+struct lanczos_sums {  // what the step's read-back holds of one check: |b - z|, |b|, and |solution| of a refined solve (else 0)
+    double res, bnorm, xnorm;
+};
 struct lanczos_operator {
     void* self;
-    // queue w = OP v_j from rhs = M v_j (rhs stays intact: a step may be done again).  The last solve of the operator leaves C times
-    // its solution in z and the address of its right-hand side in *chk_b: that pair is checked in the step's first reduction.
-    // *refined: the last solve carried the refinement step and left |its solution|^2 at xnorm2_dev.  r: a work vector.
-    int (*enqueue)(lsa_ctx* ctx, void* self, int32_t j, const double* rhs, double* w, double* z, double* r, double* xnorm2_dev, const double** chk_b,
-                   bool* refined);
-    // queue the read-back of what the operator logged on the device; the step's one synchronisation follows
+    int nchecks;  // the checks of a step: the real step kernels take one, the complex ones two
+    // queue w = OP v_j from rhs = Q v_j (rhs stays intact: a step may be done again) and fill chk[0..nchecks).  z, r: work vectors.
+    int (*enqueue)(lsa_ctx* ctx, void* self, int32_t j, const void* rhs, void* w, void* z, void* r, lanczos_check* chk);
+    // queue the read-back of what the operator logged on the device (null: nothing); the step's one synchronisation follows
     int (*read_back)(lsa_ctx* ctx, void* self);
-    // after the synchronisation: res, bnorm (and xnorm when refined) of the last solve.  0: accepted, 1: do the step again, -1: failed
-    // (the error is set)
-    int (*judge)(lsa_ctx* ctx, void* self, int32_t j, double res, double bnorm, double xnorm);
+    // after the synchronisation: the sums of the step's checks.  0: accepted (and booked), 1: do the step again, -1: failed (the error is set)
+    int (*judge)(lsa_ctx* ctx, void* self, int32_t j, const lanczos_sums* sums);
 };
-void lanczos_set_operator(lsa_lanczos* l, const lanczos_operator* hook);  // (hook outlives the basis' steps; null: the default)
+// hook outlives the basis' steps; null: the default.  LSA_ERR_ARG where nchecks is not what the basis' kernels take.
+int lanczos_set_operator(lsa_ctx* ctx, lsa_lanczos* l, const lanczos_operator* hook);
 
-// ---- the resolvent iteration (resolvent.hip): a complex basis, M-orthonormal, for W = C^-1 M C^-H M; the loop is the one of
-// lsa_lanczos_solve (dense.hip), which reaches either basis through these pieces ------------------------------------------------
+// ---- the resolvent iteration (resolvent.hip): the basis with complex scalars and the step W = C^-1 Q_f C^-H Q_q behind it; the loop
+// is the one of lsa_lanczos_solve (dense.hip), which reaches the handle through these pieces --------------------------------------
 int resolvent_shape(const lsa_resolvent* r, int64_t* n, int32_t* ncv);
 int resolvent_inject(lsa_ctx* ctx, lsa_resolvent* r, int32_t j, const cplx* host_v);
-// Y: real, m x knew column-major on the host (the eigenvectors of the real projected matrix)
 int resolvent_restart(lsa_ctx* ctx, lsa_resolvent* r, int32_t m, int32_t knew, const double* Y, int32_t ldy);
 // Q = V[:, 0:m] Y to the host in the caller's row numbering, each column's entry of largest magnitude real positive; the columns stay
 // on the device for resolvent_forcings

@@ -940,6 +940,19 @@ int basis_times_host_matrix(lsa_ctx* ctx, int dtype, int64_t n, int m, int k, co
     return k_basis_gemm(ctx, dtype, n, m, k, V, n, qdev, m, Out, n);
 }
 
+int basis_columns_to_host(lsa_ctx* ctx, int dtype, int64_t n, int ncols, const int32_t* row_perm, const void* dev, void** xtmp, int xtmp_cols, void* host) {
+    const size_t vb = (size_t)n * esize(dtype);
+    const void* src = dev;
+    if (row_perm) {
+        if (!*xtmp) LSA_HIP_ALLOC(ctx, hipMalloc(xtmp, std::max<size_t>(vb, esize(dtype)) * (size_t)xtmp_cols));
+        LSA_CHECK(k_scatter_rows(ctx, dtype, n, ncols, row_perm, dev, *xtmp));
+        src = *xtmp;
+    }
+    LSA_HIP_CHECK(ctx, hipMemcpyAsync(host, src, vb * (size_t)ncols, hipMemcpyDeviceToHost, ctx->stream));
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return LSA_OK;
+}
+
 extern "C" {
 
 int lsa_op_stats(const lsa_op* op, lsa_stats* out) {

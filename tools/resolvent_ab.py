@@ -12,7 +12,7 @@ singular (no ``M^(1/2)``, no ``M^-1``), so (b) runs the general driver ``eigs`` 
 num_modes 6, ncv 32, tolerance 1e-8; omega = the imaginary part of the case's bench target (S30k: 0.738, C160k: 0, real factors).
 Every timed sample builds its solver anew (construction, preparation, factorisation, iteration, release inside the clock); the two
 settings alternate in one process after one warm-up of each; medians and spread over ``reps`` samples.  The gains of (b) are
-compared with those of (a).  Launches and read-backs per step are counted from the step's code (``csrc/resolvent.hip``), not timed;
+compared with those of (a).  Launches and read-backs per step are counted from the step's code (``csrc/resolvent.hip``, ``csrc/lanczos.hip``), not timed;
 the per-kernel times of the three step kernels come from a separate ``rocprofv3 --kernel-trace --stats`` run of ``--only library``.
 No test asserts these times.
 
