@@ -679,6 +679,80 @@ int lsa_contour_solve(lsa_ctx *ctx, lsa_contour *h, double tol, int32_t max_it, 
                       void *X_out, double *res_out, lsa_contour_result *result);
 int lsa_contour_info(const lsa_contour *h, lsa_contour_stats *out);
 
+/* ---- stochastic forcing: EOFs and stochastic optimals of M q' = A q + f on a frequency quadrature ----------------------------------
+ * Under forcing that is white in time with spatial covariance weight Q_f, the response covariance of a stable (A, M) is
+ * P = (1 / 2 pi) int R Q_f R^H d omega with R(z) = (z M - A)^-1.  The variance carried by a structure, measured in Q_q, is an
+ * eigenvalue of P Q_q = (1 / 2 pi) int W(i omega) d omega with W(z) = C^-1 Q_f C^-H Q_q, C = A - z M: the step of lsa_resolvent_*.  For
+ * real A, M, W(conj z) = conj W(z), so the integral over the whole axis is the real operator
+ *     S = (1 / pi) sum_k w_k Re W(z_k)     over nodes z_k = beta + i omega_k, omega_k >= 0, weights w_k > 0,
+ * self-adjoint in the Q_q-semi-inner product: a real thick-restart Lanczos iteration (lsa_lanczos_*' basis and loop) with N kept
+ * factorisations of A - z_k M behind every step.  The results are those of the QUADRATURE operator S the caller gives: whether N
+ * nodes resolve the integral is the caller's to check (sharp resonances need many nodes, or a discount beta > 0, which smooths the
+ * integrand as it does for the resolvent). */
+/* Y[:, k] = (A - z_k M) X[:, k] for k < nodes in ONE launch: A, M real on one shared pattern (whole square matrices), shifts[2 k],
+ * shifts[2 k + 1] = Re, Im z_k on the host, X and Y complex128 vectors of at least n * nodes entries holding n x nodes column-major
+ * blocks (leading dimension n), apart.  Every non-zero's column index and two real values are read once for up to 16 columns.  The
+ * entries of a row are strided over 8 lanes, each adding its own in order, then a fixed tree: the same bits on every call.
+ * The check product of the forward solves of a stochastic-forcing step; exported for tests. */
+int lsa_shifted_spmm(lsa_ctx *ctx, const lsa_mat *A, const lsa_mat *M, int32_t nodes, const double *shifts, const lsa_vec *X, lsa_vec *Y);
+typedef struct lsa_stochastic lsa_stochastic;
+typedef struct {
+    int32_t nodes;
+    int32_t kind;              /* 0: EOFs, 1: stochastic optimals                                                          */
+    int64_t bytes;             /* device bytes: the N value arrays of C_k, the N factor sets, the n x N blocks, the basis   */
+    double seconds_factor;     /* building C_k and factorising (creation)                                                  */
+    double seconds_solve;      /* device seconds of the sweeps of all steps and applies (HIP events around the phases)      */
+    double seconds_product;    /* device seconds of their check products, weight products, sums and the accumulation       */
+    double seconds_dense;      /* host seconds of the loop's dense eigen-solves (lsa_stochastic_solve)                      */
+    lsa_stats solver;          /* counters of the inner solves (op_applies, refined_solves, backward_accepted, max_rel_res) */
+} lsa_stochastic_stats;
+/* A, M: real (LSA_F64) whole square matrices on one shared pattern, both outliving the handle.  shifts[2 nodes]: the nodes z_k (re,
+ * im pairs); weights[nodes]: w_k > 0.  Builds C_k = A - z_k M and keeps nodes factor sets alive on one ordering and one pattern-only
+ * analysis, as lsa_contour_create does with keep_factors (the first takes the analysis the context holds prepared, LSA_C128), and a
+ * real basis of ncv + 1 vectors.  ksp_rtol: what each of the 2 nodes solves of a step must reach.  LSA_ERR_ARG, naming the
+ * condition: a complex A or M, patterns that differ, a context of several ranks, nodes < 1, a weight that is not positive and finite,
+ * ncv < 1 or > n.  LSA_ERR_OOM before factorising (before the second set where the context holds no prepared analysis), with the
+ * bytes needed and the bytes available in the message, when nodes factor sets (the figures of lsa_ndlu_prepared_memory) exceed 0.8
+ * of the free device memory.  A node on an eigenvalue: LSA_ERR_ZERO_PIVOT with the node's index in the message. */
+int lsa_stochastic_create(lsa_ctx *ctx, const lsa_mat *A, const lsa_mat *M, int32_t nodes, const double *shifts, const double *weights, int32_t ncv,
+                          double ksp_rtol, lsa_stochastic **out);
+void lsa_stochastic_destroy(lsa_stochastic *h);
+/* as lsa_krylov_set_row_permutation: the vectors of lsa_stochastic_solve leave in the caller's numbering (start vectors and
+ * lsa_stochastic_apply are in the matrices' own) */
+int lsa_stochastic_set_row_permutation(lsa_ctx *ctx, lsa_stochastic *h, const int32_t *perm);
+/* Forcing weight Qf and response weight Qq in place of M (NULL: M; real symmetric positive semidefinite, n x n, any pattern; BORROWED:
+ * they outlive the handle), as lsa_resolvent_set_weights: W(z) = C^-1 Qf C^-H Qq.  No inverse of a weight appears.  Begins anew: the
+ * refinement steps are off again and a start vector must follow.  LSA_ERR_ARG, naming the weight, for a complex matrix or one of
+ * another size. */
+int lsa_stochastic_set_weights(lsa_ctx *ctx, lsa_stochastic *h, const lsa_mat *Qf, const lsa_mat *Qq);
+/* kind 0 (what a new handle has), EOFs: S above, Qq the inner product -- per node z = C^-H (Qq v), tm = Qf z, w = C^-1 tm.  kind 1,
+ * stochastic optimals: S' = (1 / pi) sum_k w_k Re(C_k^-H Qq C_k^-1 Qf), Qf the inner product: the same step with the two solves and the
+ * two weights swapped.  Begins anew like lsa_stochastic_set_weights.  LSA_ERR_ARG for any other code. */
+int lsa_stochastic_set_kind(lsa_ctx *ctx, lsa_stochastic *h, int32_t kind);
+/* on != 0: the forward solves of a step (the second ones of kind 0, the first ones of kind 1) go through the batched sweeps of
+ * lsa_ndlu_solve_batch, in groups of at most 16 factor sets of one analysis; a node that carries the refinement step runs alone.  The
+ * results are those of the default, bit for bit.  Off by default.  (Batched adjoint sweeps are not built: those solves run node by
+ * node.) */
+int lsa_stochastic_set_batch_forward(lsa_ctx *ctx, lsa_stochastic *h, int on);
+/* on != 0: every solve of every node carries the refinement step from the start (for tests: at small sizes no solve misses ksp_rtol) */
+int lsa_stochastic_set_refinement(lsa_ctx *ctx, lsa_stochastic *h, int on);
+/* One operator apply on a host vector in the matrices' own numbering: host_y = S host_v (kind 1: S'), each of its 2 nodes solves
+ * checked as in a step, and node_terms[k] = (w_k / pi) Re((Q v)^T w_k), node k's share of v^T Q S v (Q the kind's inner product; NULL:
+ * none).  For tests and for the frequency spectrum of a mode. */
+int lsa_stochastic_apply(lsa_ctx *ctx, lsa_stochastic *h, const double *host_v, double *host_y, double *node_terms);
+/* The whole iteration, through the loop of lsa_lanczos_solve: Ritz values ranked largest first, accepted on |beta y_mi| / theta_i <=
+ * opts->tol; of opts only nev, max_restarts, tol, seed and keep_fraction are read.  v0: host start vector (n doubles) or NULL (random
+ * from opts->seed).  Outputs, largest first: theta_out[max_out] the variances, X_out the modes (n x max_out column-major, real,
+ * orthonormal in the kind's weight, the entry of largest magnitude positive, the caller's row numbering; NULL: none),
+ * est_out[max_out].  counts (NULL or 4 entries): accepted adjoint and forward solves of this handle so far, and how many of each
+ * carried the refinement step.  Every one of the 2 nodes solves of a step is checked against ksp_rtol from a device log that travels
+ * with the step's one read-back, by the rule of lsa_lanczos_extend: within tolerance, else a refinement step for that node and
+ * direction from then on with the step done again, else a backward error within 1e-12 ||C_k||_F ||x||, else LSA_ERR_DIVERGED naming
+ * node and direction.  Returns LSA_OK also when fewer than nev values converged (see result). */
+int lsa_stochastic_solve(lsa_ctx *ctx, lsa_stochastic *h, const lsa_ks_options *opts, const double *v0, int32_t max_out, double *theta_out,
+                         double *X_out, double *est_out, lsa_ks_result *result, int64_t *counts);
+int lsa_stochastic_info(const lsa_stochastic *h, lsa_stochastic_stats *out);
+
 /* ---- MatrixMarket reader (host only): the A.mtx / M.mtx stage boundary --------------------------------------------
  * Stands in for scipy.io.mmread + the per-entry setValue loop of iPETScMatrix.from_path / from_matrix
  * (FEM/utils.py:143-147,208-215).  Coordinate format; general / symmetric / hermitian / skew-symmetric; real / integer /

@@ -1,0 +1,262 @@
+"""Response to stochastic forcing on the MI355X path: the variance ``M q' = A q + f`` sustains under forcing that is white in time,
+the structures that carry it (empirical orthogonal functions, EOFs) and the forcing structures that feed it (stochastic optimals).
+
+With ``R(z) = (z M - A)^-1`` the response covariance of a stable pair is ``P = (1 / 2 pi) int R Qf R^H d omega``; the EOFs are the
+eigenvectors of ``P Qq = (1 / 2 pi) int W(i omega) d omega``, ``W(z) = C^-1 Qf C^-H Qq`` with ``C = A - z M``: the operator a resolvent
+step applies.  For real ``A``, ``M`` the integral over the whole axis is ``S = (1 / pi) sum_k w_k Re W(i omega_k)`` over quadrature
+nodes ``omega_k >= 0``: a real operator, self-adjoint in the ``Qq``-semi-inner product.  The library runs a real thick-restart Lanczos
+iteration on it with ``nodes`` factorisations of ``A - i omega_k M`` kept alive on one ordering and one LU analysis
+(``lsa_stochastic_*``, ``csrc/stochastic.hip``)::
+
+    cfg = StochasticConfig(num_modes=4, ncv=24, atol=1e-8, nodes=16)
+    sf = StochasticForcingSolver(A, M, cfg)
+    res = sf.solve(band=(0.0, 1.5))                    # Gauss-Legendre on [0, 1.5]: res.variances, res.modes, res.spectrum
+    res = sf.solve(band=(0.0, np.inf), scale=0.5)      # the whole axis through omega = scale * tan(theta)
+    res = sf.solve(omegas=w, weights=dw, kind="optimals")
+
+**The results are those of the quadrature operator** ``S`` **the call defines, not of the integral**: whether ``nodes`` nodes resolve
+the integrand is the caller's to check, by solving again with more.  Near sharp resonances the leading variances converge slowly in
+``nodes`` (their sum converges much sooner); ``discount=beta`` evaluates ``W`` at ``beta + i omega`` and smooths the integrand, as it
+does for the resolvent.  Forcing and response windows and weights mean what they mean in :class:`Solver.resolvent.ResolventSolver`
+and are built on the device the same way (``CsrMatrix.windowed``).  Batched adjoint sweeps, a trace or captured-fraction estimate,
+several ranks, complex pencils and refactorising factor sets when ``nodes`` of them do not fit are not built.
+"""
+
+from __future__ import annotations
+
+import logging
+import math
+import time
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from .eigen import _require_matching_squares, _wrap
+from .resolvent import _real_discount, checked_side, device_weight, shared_pattern
+from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType, symmetry_defect, _SYMMETRY_TOL
+
+logger = logging.getLogger(__name__)
+
+KINDS = {"eofs": 0, "optimals": 1}
+MEMORY_FRACTION = 0.8  # of the free device memory: what the kept factor sets may take (``solve_batch``'s rule)
+
+
+@dataclass(frozen=True)
+class StochasticConfig:
+    num_modes: int = 4  # variances (with their modes) to compute
+    ncv: int = 24  # Krylov subspace dimension
+    atol: float = 1e-8  # relative tolerance on a variance: |beta y_mi| / theta_i
+    max_it: int = 500  # restarts allowed
+    nodes: int = 16  # quadrature nodes = factorisations kept alive (``band=`` rules; explicit ``omegas`` bring their own count)
+
+
+@dataclass
+class StochasticResult:
+    """``Q`` below is the weight of the kind: the response weight ``Qq`` for EOFs, the forcing weight ``Qf`` for stochastic optimals
+    (``M`` where the solver was given none)."""
+
+    variances: np.ndarray  # eigenvalues of the quadrature operator, descending
+    modes: np.ndarray  # n x k real, e_j^T Q e_k = delta_jk, the entry of largest magnitude positive
+    kind: str  # "eofs" or "optimals"
+    omegas: np.ndarray  # the quadrature nodes
+    weights: np.ndarray  # ... and weights
+    spectrum: np.ndarray  # k x N: [j, k] = node k's contribution to variances[j]; rows sum to variances
+    estimates: np.ndarray  # relative residual estimates of the variances
+    stats: dict = field(default_factory=dict)
+    discount: float = 0.0
+
+
+def gauss_legendre_band(a: float, b: float, nodes: int) -> tuple[np.ndarray, np.ndarray]:
+    """Gauss-Legendre nodes and weights on ``[a, b]``, ``0 <= a < b < inf``."""
+    if not (math.isfinite(a) and math.isfinite(b) and 0.0 <= a < b):
+        raise ValueError(f"band = ({a!r}, {b!r}) must satisfy 0 <= a < b < inf (the whole axis: band=(0, inf) with scale=)")
+    x, w = np.polynomial.legendre.leggauss(int(nodes))
+    return 0.5 * (b - a) * x + 0.5 * (b + a), 0.5 * (b - a) * w
+
+
+def tan_rule(scale: float, nodes: int) -> tuple[np.ndarray, np.ndarray]:
+    """``[0, inf)`` through ``omega = scale * tan(theta)``: Gauss-Legendre in ``theta`` on ``[0, pi / 2]``, ``d omega = scale / cos^2(theta)
+    d theta``."""
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"scale = {scale!r} must be a positive frequency")
+    theta, w = gauss_legendre_band(0.0, 0.5 * math.pi, nodes)
+    return scale * np.tan(theta), scale * w / np.cos(theta) ** 2
+
+
+def quadrature(nodes: int, band=None, scale=None, omegas=None, weights=None) -> tuple[np.ndarray, np.ndarray]:
+    """The nodes and weights a ``solve`` call names: ``band=(a, b)``, ``band=(0, inf)`` with ``scale``, or explicit arrays.
+    ``ValueError`` for anything else, a negative frequency or a weight that is not positive."""
+    if (band is None) == (omegas is None):
+        raise ValueError("give either band=(a, b) or omegas= and weights=")
+    if omegas is not None:
+        if weights is None or band is not None or scale is not None:
+            raise ValueError("explicit nodes come as omegas= and weights=, without band= or scale=")
+        om, w = np.atleast_1d(np.asarray(omegas, dtype=np.float64)), np.atleast_1d(np.asarray(weights, dtype=np.float64))
+        if om.ndim != 1 or om.shape != w.shape or om.size < 1:
+            raise ValueError(f"omegas and weights must be one-dimensional and of one length, got {om.shape} and {w.shape}")
+    else:
+        if weights is not None:
+            raise ValueError("weights= belongs to omegas=")
+        a, b = (float(t) for t in band)
+        if not isinstance(nodes, (int, np.integer)) or nodes < 1:
+            raise ValueError(f"nodes = {nodes!r} must be at least 1")
+        if math.isinf(b):
+            if a != 0.0 or scale is None:
+                raise ValueError("an unbounded band is band=(0, inf) with scale=")
+            om, w = tan_rule(float(scale), nodes)
+        else:
+            if scale is not None:
+                raise ValueError("scale= belongs to band=(0, inf)")
+            om, w = gauss_legendre_band(a, b, nodes)
+    if not np.isfinite(om).all() or (om < 0.0).any():
+        raise ValueError("the frequencies must be finite and non-negative: the quadrature over omega >= 0 stands for the whole axis")
+    if not np.isfinite(w).all() or (w <= 0.0).any():
+        raise ValueError("the quadrature weights must be positive and finite")
+    return om, w
+
+
+def plan_factor_sets(nodes: int, bytes_per_set: int, free_bytes: int, fraction: float = MEMORY_FRACTION) -> int:
+    """The bytes ``nodes`` kept factor sets need; ``MemoryError``, naming the bytes needed and the bytes available, when they exceed
+    ``fraction`` of the free device memory.  Pure host arithmetic (the library applies the same rule before it factorises)."""
+    need = int(nodes) * int(bytes_per_set)
+    have = int(fraction * int(free_bytes))
+    if need > have:
+        fit = have // max(int(bytes_per_set), 1)
+        raise MemoryError(f"stochastic forcing: {nodes} factor sets need {need} bytes, {fraction:g} of the {int(free_bytes)} bytes of free device "
+                          f"memory hold {have}: at most {fit} nodes fit (refactorising sets node by node is not built)")
+    return need
+
+
+class StochasticForcingSolver:
+    """EOFs and stochastic optimals of a real pair ``(A, M)`` on a frequency quadrature, with optional forcing and response windows
+    or weights; thin shell around :class:`iEpsSolver` 's preparation (union pattern, nested-dissection ordering, permuted numbering,
+    upload, pattern-only LU analysis) and ``lsa_hip.StochasticBasis``.  The results are those of the quadrature operator;
+    convergence in ``nodes`` is the caller's to check, and ``discount`` smooths the integrand."""
+
+    def __init__(self, A, M, cfg: StochasticConfig | None = None, *, device: int = 0, layout: str = "single",
+                 pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
+                 ksp_rtol: float | None = None, forcing_window=None, response_window=None, forcing_weight=None, response_weight=None,
+                 discount: float = 0.0, batch_forward: bool = True) -> None:
+        if A is None:
+            raise ValueError("Operator A is required.")
+        if M is None:
+            raise ValueError("Stochastic forcing needs M: the variance is measured in the M-inner product")
+        A, M = _wrap(A), _wrap(M)
+        _require_matching_squares(A, M)
+        if A.as_scipy_array().dtype.kind == "c":
+            raise ValueError("Stochastic forcing needs a real A: the quadrature over omega >= 0 stands for the whole axis only for a real pencil")
+        Ms = M.as_scipy_array()
+        if Ms.dtype.kind == "c":
+            raise ValueError("Stochastic forcing needs a real M (the M-inner product); M is complex")
+        defect = symmetry_defect(Ms)
+        if not defect <= _SYMMETRY_TOL:
+            raise ValueError(f"Stochastic forcing needs a symmetric M; its relative symmetry defect is {defect:.3e}")
+        self._sides = (checked_side("forcing", forcing_window, forcing_weight, Ms), checked_side("response", response_window, response_weight, Ms))
+        self._discount = _real_discount(discount)
+        self._cfg = cfg if cfg is not None else StochasticConfig()
+        if self._cfg.num_modes < 1:
+            raise ValueError("num_modes must be at least 1")
+        if self._cfg.ncv <= self._cfg.num_modes:
+            raise ValueError(f"ncv = {self._cfg.ncv} must exceed num_modes = {self._cfg.num_modes}")
+        if not isinstance(self._cfg.nodes, (int, np.integer)) or self._cfg.nodes < 1:
+            raise ValueError(f"nodes = {self._cfg.nodes!r} must be at least 1")
+        if layout != "single":
+            raise NotImplementedError(f"Stochastic forcing runs on one GPU; the layout is '{layout}'")
+        pc_type = PreconditionerType(pc_type)
+        if pc_type not in (PreconditionerType.LU, PreconditionerType.CHOLESKY) or ilu_levels is not None:
+            raise NotImplementedError("Stochastic forcing needs the exact LU (PreconditionerType.LU): every node of the quadrature is a pair of "
+                                      f"solves on its factors; the preconditioner is {pc_type.name}" + ("" if ilu_levels is None else f" with ILU level {ilu_levels}"))
+        eps = iEpsSolver(A, M, device=device, seed=seed, ksp_rtol=ksp_rtol)
+        eps.set_problem_type(iEpsProblemType.GNHEP)
+        eps.set_st_type(iSTType.SINVERT)
+        eps.set_st_pc_type(pc_type)
+        eps.set_tolerances(self._cfg.atol, self._cfg.max_it)
+        eps.set_dimensions(self._cfg.num_modes, self._cfg.ncv)
+        self._eps = eps
+        self._n = A.shape[0]
+        self._seed = seed
+        self._ksp_rtol = ksp_rtol if ksp_rtol is not None else float(np.clip(self._cfg.atol * 1e-2, 1e-13, 1e-8))
+        # the forward solves of a step through the batched sweeps: same bits, and 0.79-0.92 of the default's time per step on every
+        # case measured, so the front end switches it on; a new library handle has it off
+        self._batch_forward = bool(batch_forward)
+        self._force_refinement = False  # (tests: every solve with the refinement step)
+
+    @property
+    def config(self) -> StochasticConfig:
+        return self._cfg
+
+    @property
+    def solver(self) -> iEpsSolver:
+        """The eigen path's solver object whose preparation this one shares (``prepare()``, ``release()``)."""
+        return self._eps
+
+    def _weights_on_device(self, prep: dict):
+        """(Qf, Qq) as device matrices (``None``: ``M``), built once per preparation and kept with it."""
+        built = prep.get("stochastic_weights")
+        if built is None:
+            eps = self._eps
+            needs = any(spec is not None and spec[0] == "weight" for spec in self._sides)
+            pattern = shared_pattern(eps._A.as_scipy_array(), eps._M.as_scipy_array()) if needs else None
+            built = prep["stochastic_weights"] = tuple(device_weight(prep, spec, pattern) for spec in self._sides)
+        return built
+
+    def solve(self, band=None, *, scale: float | None = None, omegas=None, weights=None, kind: str = "eofs", discount: float | None = None) -> StochasticResult:
+        """The leading variances and modes of the quadrature operator over ``band=(a, b)`` (Gauss-Legendre, ``cfg.nodes`` nodes),
+        ``band=(0, inf)`` with ``scale=s`` (``omega = s tan(theta)``) or explicit ``omegas`` and ``weights``.  ``kind="eofs"``: the
+        response structures, orthonormal in ``Qq``; ``kind="optimals"``: the forcing structures, orthonormal in ``Qf``.  A second call
+        on the same solver keeps the context, the ordering, the LU analysis and the weights on the device."""
+        import lsa_hip
+
+        if kind not in KINDS:
+            raise ValueError(f"kind = {kind!r} must be 'eofs' or 'optimals'")
+        om, w = quadrature(self._cfg.nodes, band, scale, omegas, weights)
+        beta = self._discount if discount is None else _real_discount(discount)
+        cfg, eps, nev = self._cfg, self._eps, self._cfg.num_modes
+        shifts = beta + 1j * om
+        started = time.time()
+        eps.set_target(complex(beta, max(float(om.max()), 1.0)))  # (never real: the analysis is prepared for complex factors)
+        eps.prepare()
+        prep = eps._prepared
+        if prep["pc_code"] != 2:
+            raise NotImplementedError("Stochastic forcing needs the exact LU")
+        ctx, perm = prep["ctx"], prep["perm"]
+        try:
+            plan_factor_sets(om.size, ctx.prepared_lu_bytes(), ctx.mem_info()[0])
+        except ValueError:  # (no analysis parked in the context: the library judges on the first set's)
+            pass
+        basis = None
+        try:
+            basis = lsa_hip.StochasticBasis(ctx, prep["dA"], prep["dM"], shifts, w, min(cfg.ncv, self._n), ksp_rtol=self._ksp_rtol)
+            basis.set_row_permutation(perm)
+            if any(spec is not None for spec in self._sides):
+                basis.set_weights(*self._weights_on_device(prep))
+            basis.set_kind(KINDS[kind])
+            if self._batch_forward:
+                basis.set_batch_forward(True)
+            if self._force_refinement:
+                basis.set_refinement(True)
+            rng = np.random.default_rng(self._seed)
+            out = basis.solve(nev, cfg.atol, cfg.max_it, v0=rng.standard_normal(self._n)[perm], seed=self._seed, max_out=nev)
+            k = len(out["variances"])
+            spectrum = np.zeros((k, om.size))
+            for j in range(k):  # one apply per mode: node k's share of e_j^T Q S e_j
+                spectrum[j] = basis.apply(np.ascontiguousarray(out["modes"][perm, j]))[1]
+            info = basis.info()
+        finally:
+            del basis  # (the handle goes before the matrices it borrows)
+        if out["nconv"] < nev:
+            logger.warning("Stochastic forcing: %d of %d variances converged in %d restarts (next estimate %.3e)", out["nconv"], nev, out["restarts"],
+                           out["next_unconverged"])
+        st = info["solver"]
+        stats = {"applies": out["applies"], "restarts": out["restarts"], "nconv": out["nconv"], "nodes": int(om.size),
+                 "adjoint_solves": out["adjoint_solves"], "forward_solves": out["forward_solves"],
+                 "refined_adjoint": out["refined_adjoint"], "refined_forward": out["refined_forward"],
+                 "refinements": out["refined_adjoint"] + out["refined_forward"], "backward_accepted": st["backward_accepted"],
+                 "max_rel_res": st["max_rel_res"], "analysis_reused": bool(st["analysis_reused"]), "batch_forward": self._batch_forward,
+                 "stochastic_bytes": info["bytes"], "seconds_factor": info["seconds_factor"], "seconds_solve": info["seconds_solve"],
+                 "seconds_product": info["seconds_product"], "seconds_dense": info["seconds_dense"], "seconds_expand": out["seconds_expand"],
+                 "seconds_restart": out["seconds_restart"], "seconds_total": time.time() - started}
+        return StochasticResult(out["variances"], out["modes"], kind, om, w, spectrum, out["estimates"], stats, beta)
+
+    def release(self) -> None:
+        self._eps.release()

@@ -537,6 +537,66 @@ double ct_radius2(const lsa_contour* h, ci_z lam) {
 
 }  // namespace
 
+// The factor sets of a quadrature over shifts, for lsa_contour_create and lsa_stochastic_create: C[k] = A - z_k M on A's index arrays
+// and normF[k] = ||C_k||_F (the backward-error judgement's scale; sum_dev: a device double) for all nodes, then nsets <= nodes factor
+// sets F[0..nsets).  The first set takes the analysis the context holds prepared (lsa_ndlu_prepare / _prepare_tree), or analyses;
+// every further one redoes the pattern-only phase from the first one's forest: one ordering, one analysis, the bits of a
+// refactorisation.  budget > 0: LSA_ERR_OOM, with the bytes needed and the bytes available, where nsets sets (the figures of
+// lsa_ndlu_prepared_memory) exceed that fraction of the free device memory -- judged on the prepared analysis before anything is
+// factorised, else on the first set's before the second.  What was made before a failure stays in C and F for the caller to release.
+int shifted_factor_sets(lsa_ctx* ctx, const char* who, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* z, size_t nsets, double* sum_dev,
+                        double budget, lsa_mat** C, double* normF, lsa_ndlu** F) {
+    auto fits = [&](const NdSymbolic& S) {
+        int64_t out[8] = {};
+        size_t free_b = 0, total_b = 0;
+        if (nd_memory_report(S, (int32_t)sizeof(cplx), 0, out, nullptr, nullptr, nullptr) != LSA_OK || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return (int)LSA_OK;
+        const double need = (double)nsets * (double)(out[0] + out[1] + out[2] + out[4] + out[7]);
+        if (need <= budget * (double)free_b) return (int)LSA_OK;
+        return lsa_set_error(ctx, LSA_ERR_OOM, "%s: %d factor sets need %.0f bytes, %.1f of the %.0f bytes of free device memory hold %.0f; fewer nodes fit "
+                                               "(refactorising sets node by node is not built)", who, (int)nsets, need, budget, (double)free_b, budget * (double)free_b);
+    };
+    bool judged = false;
+    if (budget > 0.0 && ctx->nd_cache && ctx->nd_cache->dtype == LSA_C128 && ctx->nd_cache->S.n == A->n && ctx->nd_cache->S.nnz == A->nnz) {
+        LSA_CHECK(fits(ctx->nd_cache->S));
+        judged = true;
+    }
+    int rc = LSA_OK;
+    for (int32_t k = 0; k < nodes && rc == LSA_OK; ++k) {
+        const double one[2] = {1.0, 0.0}, mz[2] = {-z[2 * k], -z[2 * k + 1]};
+        rc = lsa_csr_axpby(ctx, A, M, one, mz, LSA_C128, &C[k]);
+        if (rc == LSA_OK) rc = k_nrm2(ctx, LSA_C128, A->nnz, C[k]->val, sum_dev);
+        double v2 = 0.0;
+        if (rc == LSA_OK && (hipMemcpyAsync(&v2, sum_dev, sizeof v2, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess))
+            rc = lsa_set_error(ctx, LSA_ERR_HIP, "%s: reading ||C||_F failed", who);
+        if (rc == LSA_OK && std::isfinite(v2)) normF[k] = std::sqrt(v2);
+    }
+    for (size_t k = 0; k < nsets && rc == LSA_OK; ++k) {
+        if (k == 0) {
+            rc = lsa_ndlu_create(ctx, C[0], 0, &F[0]);
+        } else {
+            const NdSymbolic& S = F[0]->S;
+            if (budget > 0.0 && !judged) {
+                LSA_CHECK(fits(S));
+                judged = true;
+            }
+            if (S.tree_hash != 0) {
+                std::vector<int32_t> first((size_t)S.nt), size((size_t)S.nt);
+                for (int32_t t = 0; t < S.nt; ++t) {
+                    first[(size_t)t] = S.perm[(size_t)S.node_start[(size_t)t]];
+                    size[(size_t)t] = S.node_start[(size_t)t + 1] - S.node_start[(size_t)t];
+                }
+                lsa_ndlu_drop_cache(ctx);
+                rc = lsa_ndlu_create_tree(ctx, C[k], S.nt, first.data(), size.data(), S.parent.data(), nullptr, &F[k]);
+            } else {
+                lsa_ndlu_drop_cache(ctx);
+                rc = lsa_ndlu_create(ctx, C[k], S.leaf_size, &F[k]);
+            }
+        }
+        if (rc != LSA_OK) rc = lsa_set_error(ctx, rc, "%s: node %d (z = %.6g%+.6gi): %s", who, (int)k, z[2 * k], z[2 * k + 1], std::string(ctx->err).c_str());
+    }
+    return rc;
+}
+
 extern "C" {
 
 int lsa_contour_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double centre[2], const double radii[2], int32_t subspace,
@@ -588,41 +648,10 @@ int lsa_contour_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t
         return lsa_set_error(ctx, LSA_ERR_OOM, "lsa_contour_create: out of device memory (n=%d, subspace=%d)", A->n, subspace);
     }
     h->bytes = (int64_t)(6 * blk + LL);
-    // C_k = A - z_k M on A's index arrays, and ||C_k||_F for the backward-error judgement
     const double t0 = now_s();
-    int rc = LSA_OK;
-    for (int32_t k = 0; k < nodes && rc == LSA_OK; ++k) {
-        const double one[2] = {1.0, 0.0}, mz[2] = {-h->z[(size_t)k].real(), -h->z[(size_t)k].imag()};
-        rc = lsa_csr_axpby(ctx, A, M, one, mz, LSA_C128, &h->C[(size_t)k]);
-        if (rc == LSA_OK) rc = k_nrm2(ctx, LSA_C128, A->nnz, h->C[(size_t)k]->val, h->sums);
-        double v2 = 0.0;
-        if (rc == LSA_OK && (hipMemcpyAsync(&v2, h->sums, sizeof v2, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess))
-            rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_contour_create: reading ||C||_F failed");
-        if (rc == LSA_OK && std::isfinite(v2)) h->normF[(size_t)k] = std::sqrt(v2);
-        h->bytes += (int64_t)A->nnz * (int64_t)sizeof(cplx);
-    }
-    // The factor sets.  The first takes the analysis the context holds prepared (lsa_ndlu_prepare / _prepare_tree), or analyses; every
-    // further one redoes the pattern-only phase from the first one's forest: one ordering, one analysis, the bits of a refactorisation.
-    for (size_t k = 0; k < h->F.size() && rc == LSA_OK; ++k) {
-        if (k == 0) {
-            rc = lsa_ndlu_create(ctx, h->C[0], 0, &h->F[0]);
-        } else {
-            const NdSymbolic& S = h->F[0]->S;
-            if (S.tree_hash != 0) {
-                std::vector<int32_t> first((size_t)S.nt), size((size_t)S.nt);
-                for (int32_t t = 0; t < S.nt; ++t) {
-                    first[(size_t)t] = S.perm[(size_t)S.node_start[(size_t)t]];
-                    size[(size_t)t] = S.node_start[(size_t)t + 1] - S.node_start[(size_t)t];
-                }
-                lsa_ndlu_drop_cache(ctx);
-                rc = lsa_ndlu_create_tree(ctx, h->C[k], S.nt, first.data(), size.data(), S.parent.data(), nullptr, &h->F[k]);
-            } else {
-                lsa_ndlu_drop_cache(ctx);
-                rc = lsa_ndlu_create(ctx, h->C[k], S.leaf_size, &h->F[k]);
-            }
-        }
-        if (rc != LSA_OK) rc = lsa_set_error(ctx, rc, "lsa_contour_create: node %d (z = %.6g%+.6gi): %s", (int)k, h->z[k].real(), h->z[k].imag(), std::string(ctx->err).c_str());
-    }
+    int rc = shifted_factor_sets(ctx, "lsa_contour_create", A, M, nodes, reinterpret_cast<const double*>(h->z.data()), h->F.size(), h->sums, 0.0, h->C.data(),
+                                 h->normF.data(), h->F.data());
+    h->bytes += (int64_t)nodes * A->nnz * (int64_t)sizeof(cplx);
     if (rc == LSA_OK) rc = ct_sync(ctx);
     if (rc != LSA_OK) {
         const std::string msg = ctx->err;

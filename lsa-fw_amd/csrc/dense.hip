@@ -799,6 +799,24 @@ struct TrlGrowthBasis {
     double back(double theta) const { return theta; }   // theta = G itself
 };
 
+struct TrlStochasticBasis {
+    using scalar = double;
+    lsa_ctx* ctx;
+    lsa_stochastic* h;
+    int64_t n = 0;
+    int32_t m = 0;
+    void random(Rng& rng, std::vector<double>& vec) const {
+        double other = 0.0;
+        for (int64_t i = 0; i < n; ++i) rng.normal_pair(vec[(size_t)i], other);
+    }
+    int inject(int j, const double* v) { return stochastic_inject(ctx, h, j, v); }
+    int extend(int j, double* T, int ldt, int32_t* bd) { return stochastic_extend(ctx, h, j, m, T, ldt, bd); }
+    int restart(int knew, const double* Yk) { return stochastic_restart(ctx, h, m, knew, Yk, m); }
+    int vectors(int nout, const double* Yo, const double*, double* X) { return stochastic_ritz_vectors(ctx, h, m, nout, Yo, m, X); }
+    double key(double theta) const { return -theta; }  // the largest variances first
+    double back(double theta) const { return theta; }
+};
+
 template <class Basis>
 int trl_solve(lsa_ctx* ctx, Basis& b, const lsa_ks_options* o, const typename Basis::scalar* v0, int32_t max_out, double* theta_out,
               double* lambda_out, typename Basis::scalar* X_out, double* est_out, lsa_ks_result* result) {
@@ -1402,6 +1420,21 @@ int lsa_growth_solve(lsa_ctx* ctx, lsa_growth* g, const lsa_ks_options* o, const
     LSA_CHECK(ks_check_options(ctx, "lsa_growth_solve", o, max_out, theta_out, gain_out));
     const int rc = trl_solve(ctx, b, o, v0, max_out, theta_out, gain_out, Q0_out, est_out, result);
     if (counts) growth_counts(g, counts);
+    return rc;
+}
+
+// Stochastic forcing (stochastic.hip): the same loop on the real basis of S = (1 / pi) sum_k w_k Re W(z_k), 2N solves on N kept factor
+// sets behind every step; theta_j = the variances, largest first.
+int lsa_stochastic_solve(lsa_ctx* ctx, lsa_stochastic* h, const lsa_ks_options* o, const double* v0, int32_t max_out, double* theta_out, double* X_out,
+                         double* est_out, lsa_ks_result* result, int64_t* counts) {
+    if (!ctx || !h || !o || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_stochastic_solve: null argument");
+    TrlStochasticBasis b{ctx, h};
+    LSA_CHECK(stochastic_shape(h, &b.n, &b.m));
+    std::vector<double> same((size_t)std::max(max_out, 1));  // (the loop's second copy of the values: no transform maps them)
+    LSA_CHECK(ks_check_options(ctx, "lsa_stochastic_solve", o, max_out, theta_out, same.data()));
+    const int rc = trl_solve(ctx, b, o, v0, max_out, theta_out, same.data(), X_out, est_out, result);
+    if (rc == LSA_OK) stochastic_book_dense(h, result->seconds_dense);
+    if (counts) stochastic_counts(h, counts);
     return rc;
 }
 

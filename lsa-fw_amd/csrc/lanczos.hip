@@ -645,6 +645,10 @@ int lz_solve_judge(lsa_ctx* ctx, void* self, int32_t j, const lanczos_sums* s) {
 int lanczos_create_basis(lsa_ctx* ctx, lsa_op* op, int32_t ncv, int dtype, const char* who, lsa_lanczos** out) {
     lsa_op_parts P{};
     LSA_CHECK(lsa_op_get_parts(op, &P));
+    return lanczos_create_basis_on(ctx, op, P, ncv, dtype, who, out);
+}
+
+int lanczos_create_basis_on(lsa_ctx* ctx, lsa_op* op, const lsa_op_parts& P, int32_t ncv, int dtype, const char* who, lsa_lanczos** out) {
     lsa_lanczos* l = new lsa_lanczos();
     l->ctx = ctx;
     l->op = op;
@@ -656,7 +660,7 @@ int lanczos_create_basis(lsa_ctx* ctx, lsa_op* op, int32_t ncv, int dtype, const
     l->who = who;
     l->Q = P.Kmul;
     l->builtin = lanczos_operator{l, 1, lz_solve_enqueue, nullptr, lz_solve_judge};
-    l->hook = dtype == LSA_F64 ? &l->builtin : nullptr;
+    l->hook = dtype == LSA_F64 && op ? &l->builtin : nullptr;  // (the default's single solve runs on an operator's factors)
     const LzSlot S = lz_slot(l);
     l->hslot.assign(S.doubles, 0.0);
     const size_t vb = (size_t)std::max<int64_t>(l->n, 1) * l->es, nchk = (size_t)lz_nchecks(l);
@@ -685,7 +689,7 @@ int lanczos_shape(const lsa_lanczos* l, int64_t* n, int32_t* ncv) {
 }
 
 int lanczos_set_operator(lsa_ctx* ctx, lsa_lanczos* l, const lanczos_operator* hook) {
-    if (!hook && l->dtype == LSA_F64) hook = &l->builtin;
+    if (!hook && l->dtype == LSA_F64 && l->op) hook = &l->builtin;
     if (hook && hook->nchecks != lz_nchecks(l))
         return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the operator names %d checked solves a step, the step kernels of this basis take %d", l->who, hook->nchecks,
                              lz_nchecks(l));

@@ -272,6 +272,16 @@ int k_spmm(lsa_ctx* ctx, const lsa_mat* A, int32_t ncols, const void* X, int64_t
 // G_host (p x q column-major) = U^H W over n rows, p, q <= 128: fixed-order two-stage sums; synchronises.  U == W (one block): real diagonal
 int k_block_gram(lsa_ctx* ctx, int64_t n, int32_t p, const void* U, int64_t ldu, int32_t q, const void* W, int64_t ldw, void* G_host);
 
+// The kept factor sets of a quadrature over shifts (contour.hip; lsa_contour_create and lsa_stochastic_create): C[k] = A - z_k M on A's
+// index arrays and normF[k] = ||C_k||_F for k < nodes (z: re, im pairs; sum_dev: a device double), then nsets <= nodes exact LUs
+// F[0..nsets) on one ordering and one analysis.  budget > 0: LSA_ERR_OOM before factorising where nsets sets exceed that fraction of
+// the free device memory.  What a failed call made stays in C and F for the caller to release.
+struct lsa_ndlu;
+int shifted_factor_sets(lsa_ctx* ctx, const char* who, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* z, size_t nsets, double* sum_dev,
+                        double budget, lsa_mat** C, double* normF, lsa_ndlu** F);
+// Y[:, k] = (A - z_k M) X[:, k], k < N: A, M real on one pattern, X, Y n x N complex (ld n), z_dev N complex on the device (stochastic.hip)
+int k_shifted_spmm(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t N, const void* z_dev, const void* X, void* Y);
+
 // Z = Mh^-1 Ah for r x r complex host matrices (column-major, ld r) by LU with partial pivoting, both overwritten (dense.hip); false: singular
 bool dense_lu_solve(int32_t r, void* Mh, void* Ah);
 
@@ -412,6 +422,9 @@ inline int direct_solve_verdict(const lsa_op_parts& P, bool refine, double res, 
 // A basis of scalar type dtype (LSA_F64, LSA_C128) for an owner that has checked the operator itself; who: the owner's name in the
 // messages ("lsa_growth", "lsa_resolvent").  A basis with complex scalars has no operator until lanczos_set_operator gives it one.
 int lanczos_create_basis(lsa_ctx* ctx, lsa_op* op, int32_t ncv, int dtype, const char* who, lsa_lanczos** out);
+// The same for an owner without a shift-invert operator (stochastic.hip keeps factor sets of its own): P names what the basis reads of
+// one -- n, Kmul (the inner product) and st, which outlives the basis -- and op is null: such a basis has no default operator.
+int lanczos_create_basis_on(lsa_ctx* ctx, lsa_op* op, const lsa_op_parts& P, int32_t ncv, int dtype, const char* who, lsa_lanczos** out);
 int lanczos_shape(const lsa_lanczos* l, int64_t* n, int32_t* ncv);
 // the inner product x^H Q y (Q real symmetric positive semidefinite; the operator's M on a new basis).  No right-hand side is left
 // over: a start vector must follow, the basis in hand being orthonormal in the old inner product.
@@ -480,6 +493,18 @@ int growth_ritz_vectors(lsa_ctx* ctx, lsa_growth* g, int32_t m, int32_t nvec, co
 int growth_responses(lsa_ctx* ctx, lsa_growth* g, int32_t nvec, double* QT, double* energy);
 // accepted forward solves, accepted transposed solves, and how many of each carried the refinement step
 void growth_counts(const lsa_growth* g, int64_t counts[4]);
+
+// ---- stochastic forcing (stochastic.hip): the real basis of an lsa_lanczos with 2N solves on N kept factor sets behind every step;
+// the loop is the one of lsa_lanczos_solve (dense.hip), which reaches the handle through these pieces ------------------------------
+int stochastic_shape(const lsa_stochastic* h, int64_t* n, int32_t* ncv);
+int stochastic_inject(lsa_ctx* ctx, lsa_stochastic* h, int32_t j, const double* host_v);
+int stochastic_extend(lsa_ctx* ctx, lsa_stochastic* h, int32_t j0, int32_t j1, double* T, int32_t ldt, int32_t* breakdown);
+int stochastic_restart(lsa_ctx* ctx, lsa_stochastic* h, int32_t m, int32_t knew, const double* Y, int32_t ldy);
+// X = V[:, 0:m] Y to the host in the caller's row numbering, orthonormal in the kind's weight, each column's entry of largest magnitude positive
+int stochastic_ritz_vectors(lsa_ctx* ctx, lsa_stochastic* h, int32_t m, int32_t nvec, const double* Y, int32_t ldy, double* X);
+// accepted adjoint solves, accepted forward solves, and how many of each carried the refinement step
+void stochastic_counts(const lsa_stochastic* h, int64_t counts[4]);
+void stochastic_book_dense(lsa_stochastic* h, double seconds);
 
 // ---- ILU (ilu.hip) -------------------------------------------------------------------------------------
 struct lsa_ilu {

@@ -142,6 +142,19 @@ class lsa_contour_stats(ctypes.Structure):
     ]
 
 
+class lsa_stochastic_stats(ctypes.Structure):
+    _fields_ = [
+        ("nodes", ctypes.c_int32),
+        ("kind", ctypes.c_int32),
+        ("bytes", ctypes.c_int64),
+        ("seconds_factor", ctypes.c_double),
+        ("seconds_solve", ctypes.c_double),
+        ("seconds_product", ctypes.c_double),
+        ("seconds_dense", ctypes.c_double),
+        ("solver", lsa_stats),
+    ]
+
+
 _P = ctypes.c_void_p
 _I32, _I64, _DBL = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -269,6 +282,17 @@ SIGNATURES = {
     "lsa_contour_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
     "lsa_contour_solve": (ctypes.c_int, [_P, _P, _DBL, _I32, _P, _I32, _P, _P, _P, ctypes.POINTER(lsa_contour_result)]),
     "lsa_contour_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_contour_stats)]),
+    "lsa_shifted_spmm": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P]),
+    "lsa_stochastic_create": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _I32, _DBL, _PP]),
+    "lsa_stochastic_destroy": (None, [_P]),
+    "lsa_stochastic_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
+    "lsa_stochastic_set_weights": (ctypes.c_int, [_P, _P, _P, _P]),
+    "lsa_stochastic_set_kind": (ctypes.c_int, [_P, _P, _I32]),
+    "lsa_stochastic_set_batch_forward": (ctypes.c_int, [_P, _P, ctypes.c_int]),
+    "lsa_stochastic_set_refinement": (ctypes.c_int, [_P, _P, ctypes.c_int]),
+    "lsa_stochastic_apply": (ctypes.c_int, [_P, _P, _P, _P, _P]),
+    "lsa_stochastic_solve": (ctypes.c_int, [_P, _P, ctypes.POINTER(lsa_ks_options), _P, _I32, _P, _P, _P, ctypes.POINTER(lsa_ks_result), _P]),
+    "lsa_stochastic_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_stochastic_stats)]),
     "lsa_mm_open": (ctypes.c_int, [ctypes.c_char_p, _PP, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int)]),
     "lsa_mm_read_csr": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_mm_error": (ctypes.c_char_p, [_P]),
@@ -1344,6 +1368,112 @@ class ContourSolver:
     def __del__(self):
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
             self.ctx._lib.lsa_contour_destroy(self.handle)
+            self.handle = None
+
+
+def shifted_spmm(ctx: Context, A: CsrMatrix, M: CsrMatrix, shifts, X: np.ndarray) -> np.ndarray:
+    """``Y[:, k] = (A - shifts[k] M) X[:, k]`` for all columns in one launch (``lsa_shifted_spmm``): ``A``, ``M`` real on one
+    pattern, ``X`` an ``n x N`` complex block on the host; returns ``Y`` on the host."""
+    z = np.ascontiguousarray(shifts, dtype=np.complex128).ravel()
+    X = np.asfortranarray(X, dtype=np.complex128)
+    n = A.shape[0]
+    if X.shape != (n, z.size):
+        raise ValueError(f"the block must have shape ({n}, {z.size}), got {X.shape}")
+    dX = DeviceVector.from_numpy(ctx, X.ravel(order="F"))
+    dY = DeviceVector(ctx, n * z.size, np.complex128)
+    ctx.check(ctx._lib.lsa_shifted_spmm(ctx.handle, A.handle, M.handle, z.size, _ptr(z), dX.handle, dY.handle))
+    return dY.numpy().reshape((n, z.size), order="F")
+
+
+class StochasticBasis:
+    """Real Lanczos basis in HBM for the stochastic-forcing operator ``S = (1 / pi) sum_k w_k Re(C_k^-1 Qf C_k^-H Qq)``,
+    ``C_k = A - z_k M`` (``lsa_stochastic_*``): ``len(shifts)`` factorisations kept alive on one LU analysis behind every step.
+    ``A`` and ``M`` are real and share one pattern.  ``kind`` 0: EOFs (``Qq`` the inner product), 1: stochastic optimals (the two
+    solves and the two weights swapped, ``Qf`` the inner product).  The results are those of the quadrature given."""
+
+    def __init__(self, ctx: Context, A: CsrMatrix, M: CsrMatrix, shifts, weights, ncv: int, *, ksp_rtol: float = 1e-12):
+        self.ctx, self._keep = ctx, (A, M)  # (the handle borrows both matrices)
+        self._weights = (None, None)
+        self.shifts = np.ascontiguousarray(shifts, dtype=np.complex128).ravel()
+        self.weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        if self.shifts.size != self.weights.size:
+            raise ValueError(f"{self.shifts.size} nodes and {self.weights.size} weights")
+        self.n, self.ncv, self.nodes = A.shape[0], int(ncv), int(self.shifts.size)
+        h = ctypes.c_void_p()
+        ctx.check(ctx._lib.lsa_stochastic_create(ctx.handle, A.handle, None if M is None else M.handle, self.nodes, _ptr(self.shifts), _ptr(self.weights),
+                                                 self.ncv, float(ksp_rtol), ctypes.byref(h)))
+        self.handle = h
+
+    def set_row_permutation(self, perm: np.ndarray | None) -> None:
+        """``perm[i]`` = the caller's index of basis row ``i``: the modes of :meth:`solve` come back in the caller's numbering."""
+        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        self.ctx.check(self.ctx._lib.lsa_stochastic_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
+
+    def set_weights(self, forcing: "CsrMatrix | None" = None, response: "CsrMatrix | None" = None) -> None:
+        """Forcing weight ``Q_f`` and response weight ``Q_q`` in place of ``M`` (``None``: ``M``; ``lsa_stochastic_set_weights``): real
+        symmetric positive semidefinite ``n x n`` device matrices, which this object keeps alive."""
+        self.ctx.check(self.ctx._lib.lsa_stochastic_set_weights(self.ctx.handle, self.handle, None if forcing is None else forcing.handle,
+                                                                None if response is None else response.handle))
+        self._weights = (forcing, response)
+
+    def set_kind(self, kind: int) -> None:
+        self.ctx.check(self.ctx._lib.lsa_stochastic_set_kind(self.ctx.handle, self.handle, int(kind)))
+
+    def set_batch_forward(self, on: bool) -> None:
+        """``True``: the forward solves of a step run through the batched sweeps of ``lsa_ndlu_solve_batch``; same bits."""
+        self.ctx.check(self.ctx._lib.lsa_stochastic_set_batch_forward(self.ctx.handle, self.handle, int(bool(on))))
+
+    def set_refinement(self, on: bool) -> None:
+        """``True``: every solve carries the refinement step from the start (for tests)."""
+        self.ctx.check(self.ctx._lib.lsa_stochastic_set_refinement(self.ctx.handle, self.handle, int(bool(on))))
+
+    def apply(self, v: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """``(S v, node terms)`` for a host vector in the matrices' own row numbering (``lsa_stochastic_apply``); the node terms sum
+        to ``v^T Q S v``."""
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (self.n,):
+            raise ValueError(f"the vector must have shape ({self.n},)")
+        y, terms = np.empty(self.n), np.zeros(self.nodes)
+        self.ctx.check(self.ctx._lib.lsa_stochastic_apply(self.ctx.handle, self.handle, _ptr(v), _ptr(y), _ptr(terms)))
+        return y, terms
+
+    def solve(self, nev: int, tol: float, max_restarts: int, *, v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None) -> dict:
+        """The whole iteration inside the library (``lsa_stochastic_solve``).  Returns a dict: ``variances`` (descending), ``modes``
+        (n x k real, orthonormal in the kind's weight), ``estimates``, ``nconv``, ``restarts``, ``applies``, the loop's phase times
+        and the handle's solve counts so far."""
+        max_out = self.ncv if max_out is None else min(int(max_out), self.ncv)
+        o = lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=0, transform=0, sigma=(_DBL * 2)(0.0, 0.0),
+                           antishift=(_DBL * 2)(0.0, 0.0), target=(_DBL * 2)(0.0, 0.0), seed=int(seed), keep_fraction=0.5)
+        theta = np.zeros(max(max_out, 1), dtype=np.float64)
+        est = np.zeros(max(max_out, 1), dtype=np.float64)
+        X = np.empty((self.n, max_out), dtype=np.float64, order="F")
+        counts = np.zeros(4, dtype=np.int64)
+        res = lsa_ks_result()
+        v = None
+        if v0 is not None:
+            v = np.ascontiguousarray(v0, dtype=np.float64)
+            if v.shape != (self.n,):
+                raise ValueError(f"start vector must have shape ({self.n},)")
+        self.ctx.check(self.ctx._lib.lsa_stochastic_solve(self.ctx.handle, self.handle, ctypes.byref(o), None if v is None else _ptr(v), max_out,
+                                                          _ptr(theta), _ptr(X), _ptr(est), ctypes.byref(res), _ptr(counts)))
+        k = res.nout
+        return {"variances": theta[:k].copy(), "modes": np.asfortranarray(X[:, :k]), "estimates": est[:k].copy(), "nconv": int(res.nconv),
+                "restarts": int(res.restarts), "applies": int(res.op_applies), "next_unconverged": float(res.next_unconverged),
+                "seconds_expand": res.seconds_expand, "seconds_dense": res.seconds_dense, "seconds_restart": res.seconds_restart,
+                "adjoint_solves": int(counts[0]), "forward_solves": int(counts[1]), "refined_adjoint": int(counts[2]),
+                "refined_forward": int(counts[3])}
+
+    def info(self) -> dict:
+        """``lsa_stochastic_info``: nodes, kind, device bytes, the phase times, and the inner solves' counters under ``"solver"``."""
+        st = lsa_stochastic_stats()
+        self.ctx.check(self.ctx._lib.lsa_stochastic_info(self.handle, ctypes.byref(st)))
+        d = {name: getattr(st, name) for name, _ in lsa_stochastic_stats._fields_ if name != "solver"}
+        d["solver"] = {name: getattr(st.solver, name) for name, _ in lsa_stats._fields_}
+        return d
+
+    def __del__(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx._lib.lsa_stochastic_destroy(self.handle)
             self.handle = None
 
 
