@@ -272,10 +272,11 @@ int lsa_ndlu_inertia(lsa_ctx *ctx, lsa_ndlu *f, int64_t *negative, int64_t *zero
 int lsa_ndlu_prepared_memory(lsa_ctx *ctx, int64_t *out);
 /* front_entries: scalars of the device buffers (packed factors + the working fronts of one chunk + the update arena);
  * apply_bytes: algorithmic bytes of one solve (every factor scalar once + the vectors); apply_launches: dependent
- * launches of one solve (two per tree level, less one: the roots have no downward step) */
+ * launches of one solve (two per tree level, less one: the roots have no downward step); factor_launches: kernel
+ * launches of the last numeric factorisation, counted on the host */
 int lsa_ndlu_info(const lsa_ndlu *f, int32_t *ntree, int32_t *nlevels, int32_t *max_front, int64_t *factor_entries,
                   int64_t *front_entries, int64_t *apply_bytes, int32_t *apply_launches, double *seconds_analyse,
-                  double *seconds_numeric);
+                  double *seconds_numeric, int32_t *factor_launches);
 /* level `level` (0 = leaves) of f's sweeps, one launch upwards and one downwards: its nodes, its widest pivot block, the rows
  * of a tile of the upward and of the downward launch (8: 64 lanes along a row pair, 32: 16 lanes, 128: 4 lanes) and the tiles
  * of its tallest node in each (the launches' grid.y; 0: no launch).  LSA_ERR_ARG beyond the last level. */

@@ -159,6 +159,12 @@ void nd_setup_knobs(lsa_ndlu* f) {
     f->ycap = kNB;
     const char* sbc = getenv("LSA_ND_SB_COLS");
     f->sb_cols = sbc && *sbc ? std::min(1024, std::max(kGT, atoi(sbc) / kGT * kGT)) : kSB;
+    // unset: staging in the finishing launch, S1 and S2 in one launch, 16-column panels in the instances where they measured
+    // faster;  16: the same with 16-column panels in every instance that has them (up to 512 rows);  8: the launch sequence
+    // before all of that (A/B runs in one library, tests/test_gpu_gj_panels.py)
+    const char* gp = getenv("LSA_ND_GJ_PANEL");
+    const int gpv = gp && *gp ? atoi(gp) : 0;
+    f->gj_panel = gpv == 8 || gpv == 16 ? gpv : 0;
 }
 
 // whether the matrix came in elimination order (a node's own unknowns are own0, own0 + 1, ...)
@@ -1001,7 +1007,7 @@ int lsa_ndlu_sweep_level(const lsa_ndlu* f, int32_t level, int32_t* nodes, int32
 }
 
 int lsa_ndlu_info(const lsa_ndlu* f, int32_t* ntree, int32_t* nlevels, int32_t* max_front, int64_t* factor_entries, int64_t* front_entries,
-                  int64_t* apply_bytes, int32_t* apply_launches, double* seconds_analyse, double* seconds_numeric) {
+                  int64_t* apply_bytes, int32_t* apply_launches, double* seconds_analyse, double* seconds_numeric, int32_t* factor_launches) {
     if (!f) return LSA_ERR_ARG;
     const NdSymbolic& S = f->S;
     if (ntree) *ntree = S.nt;
@@ -1020,6 +1026,7 @@ int lsa_ndlu_info(const lsa_ndlu* f, int32_t* ntree, int32_t* nlevels, int32_t* 
     if (apply_launches) *apply_launches = f->solve_launches;
     if (seconds_analyse) *seconds_analyse = f->seconds_analyse;
     if (seconds_numeric) *seconds_numeric = f->seconds_numeric;
+    if (factor_launches) *factor_launches = f->factor_launches;
     return LSA_OK;
 }
 

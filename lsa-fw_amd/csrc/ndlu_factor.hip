@@ -3,6 +3,15 @@
 // and the assembly of the merged top of the sweeps.  Layout and pivoting: ndlu.hip; records and tables: ndlu_internal.h.
 #include "ndlu_internal.h"
 
+#include <utility>
+
+// every kernel launch of the numeric factorisation, counted on the host (lsa_ndlu_info: factor_launches)
+#define ND_LAUNCH(f, ...)                   \
+    do {                                    \
+        ++(f)->factor_launches;             \
+        hipLaunchKernelGGL(__VA_ARGS__);    \
+    } while (0)
+
 namespace {
 
 template <typename T>
@@ -128,6 +137,17 @@ __device__ __forceinline__ unsigned long long pivot_key(double mag2, int32_t row
     return ((unsigned long long)__double_as_longlong(mag2) & ~0xFFFFull) | (unsigned long long)(65535 - row);
 }
 
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop that cannot stay rolled.  The pivots of a panel index a
+// thread's registers, and `#pragma unroll` gave up on that loop at 16 pivots (the row went to scratch memory).
+template <typename F, int... J>
+__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, J...>) {
+    (f(std::integral_constant<int, J>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
+
 // ---- blocked Gauss-Jordan inversion of the pivot blocks of a level ---------------------------------------------------------
 // Columns are eliminated in blocks of kNB; inside a block in panels of W columns (W = 8 for pivot blocks of up to 2048 rows,
 // narrower for taller ones so that a thread's rows of the panel stay in registers).  Rows are never interchanged: a row
@@ -146,11 +166,42 @@ __device__ __forceinline__ unsigned long long pivot_key(double mag2, int32_t row
 // the columns outside a block are touched once per kNB pivots instead of once per 8 (the update of a 6 000-row pivot block
 // streamed 1.1 GB per 8 pivots, and its panel did not fit the registers of one workgroup at W = 8).
 
-// k0 < 0: no panel in this launch (the tiles finish the block);  kprev < 0: no previous panel to apply
+// The finishing launch carries the staging in further workgroups (y >= ystage) unless LSA_ND_GJ_PANEL=8 asks for the separate
+// launch: staging reads the columns outside the block, the tiles write columns inside it, and ipiv is complete when the
+// last panel has ended.  Blocks of one panel have no finishing launch and keep the separate staging launch.
+// Panels of 16 columns (LSA_ND_GJ_PANEL=16, where a thread holds one row): a block is two panels, the second panel's launch
+// has no tiles (no block column lies outside both panels), and the finishing launch is the second panel's rank-16 update of
+// the first panel's columns.  Measured slower than panels of 8 (nd_numeric), hence not the default.
+
+// Yb[j][c] = A[pivot row of column kb + j][c], j < kw, for column c < c_hi of one node (nd_gj_stage_kernel; the
+// staging workgroups of a finishing launch);  ycap = rows of staging space per unknown
+template <typename T>
+__device__ __forceinline__ void gj_stage_column(const NdNodeDev& nd, const T* front, const int32_t* ipiv, int32_t kb, int32_t kw, int32_t ycap,
+                                                int32_t c, int32_t c_hi, T* ybuf) {
+    const int32_t m = nd.m, ld = nd.f;
+    const int32_t nb = min(kw, m - kb);
+    if (nb <= 0 || m <= kNB || c >= min(m, c_hi)) return;
+    const T* a = front + nd.front_off;
+    T* yb = ybuf + (size_t)ycap * nd.piv_off;
+    const int32_t* pv = ipiv + nd.piv_off + kb;
+    int32_t j = 0;
+    for (; j + 4 <= nb; j += 4) {  // (independent loads, issued together)
+        const T v0 = a[(size_t)pv[j] * ld + c], v1 = a[(size_t)pv[j + 1] * ld + c], v2 = a[(size_t)pv[j + 2] * ld + c], v3 = a[(size_t)pv[j + 3] * ld + c];
+        yb[(size_t)j * m + c] = v0;
+        yb[(size_t)(j + 1) * m + c] = v1;
+        yb[(size_t)(j + 2) * m + c] = v2;
+        yb[(size_t)(j + 3) * m + c] = v3;
+    }
+    for (; j < nb; ++j) yb[(size_t)j * m + c] = a[(size_t)pv[j] * ld + c];
+}
+
+// k0 < 0: no panel in this launch (the tiles finish the block);  kprev < 0: no previous panel to apply;
+// ystage > 0: workgroups y >= ystage stage the block's pivot rows in the columns [0, c_hi) into ybuf, NT columns each
 template <typename T, int NT, int RPT, int W>
 __global__ __launch_bounds__(NT) void nd_gj_fused_kernel(const int32_t* __restrict__ lvl_nodes, const NdNodeDev* __restrict__ nodes,
                                                          T* __restrict__ front, int32_t* __restrict__ ipiv, int32_t* __restrict__ rowq,
-                                                         int32_t kb, int32_t k0, int32_t kprev, int32_t* __restrict__ flag, double tiny2) {
+                                                         int32_t kb, int32_t k0, int32_t kprev, int32_t* __restrict__ flag, double tiny2,
+                                                         int32_t ystage, T* __restrict__ ybuf, int32_t c_hi) {
     __shared__ unsigned long long skey[W];
     __shared__ T prow_s[2][W];
     __shared__ int32_t prows[W];
@@ -161,6 +212,10 @@ __global__ __launch_bounds__(NT) void nd_gj_fused_kernel(const int32_t* __restri
     const int32_t m = nd.m, ld = nd.f;
     T* a = front + nd.front_off;
     const int tid = threadIdx.x, lane = tid & 63;
+    if (ystage > 0 && (int32_t)blockIdx.y >= ystage) {
+        gj_stage_column<T>(nd, front, ipiv, kb, kNB, kNB, ((int32_t)blockIdx.y - ystage) * NT + tid, c_hi, ybuf);
+        return;
+    }
     const int32_t wp = kprev >= 0 ? min(W, m - kprev) : 0;  // columns of the previous panel in this node
     if (blockIdx.y > 0) {
         // ---- tile of 16 block columns: the previous panel's rank-W update, all rows ----
@@ -181,11 +236,12 @@ __global__ __launch_bounds__(NT) void nd_gj_fused_kernel(const int32_t* __restri
         for (int j = 0; j < W; ++j) y[j] = yprev[j][tid & 15];
         // four rows per trip, their loads issued together (a trip is a chain of dependent loads; with 64 threads a tile of a
         // 64-row pivot block would otherwise walk 16 of them one after the other)
-        constexpr int RL = NT / 16;
-        for (int32_t i0 = tid >> 4; i0 < m; i0 += 4 * RL) {
-            T cur[4], mult[4][W];
+        // (two rows at W = 16: the same number of multipliers in registers)
+        constexpr int RL = NT / 16, U = W > 8 ? 2 : 4;
+        for (int32_t i0 = tid >> 4; i0 < m; i0 += U * RL) {
+            T cur[U], mult[U][W];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
+            for (int u = 0; u < U; ++u) {
                 const int32_t i = i0 + u * RL;
                 const T* ai = a + (size_t)min(i, m - 1) * ld;
                 cur[u] = ai[c];
@@ -193,7 +249,7 @@ __global__ __launch_bounds__(NT) void nd_gj_fused_kernel(const int32_t* __restri
                 for (int j = 0; j < W; ++j) mult[u][j] = j < wp ? ai[kprev + j] : scalar_traits<T>::zero();
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
+            for (int u = 0; u < U; ++u) {
                 const int32_t i = i0 + u * RL;
                 if (i >= m) break;
                 bool is_piv = false;
@@ -218,9 +274,11 @@ __global__ __launch_bounds__(NT) void nd_gj_fused_kernel(const int32_t* __restri
         pprev[tid] = tid < wp ? piv[kprev + tid] : -1;
     }
     __syncthreads();
-    if (wp > 0 && tid < W * W) {  // the previous panel's pivot rows in this panel's columns, before anything is overwritten
-        const int j = tid / W, cc = tid % W;
-        yprev[j][cc] = (j < wp && cc < w) ? a[(size_t)pprev[j] * ld + k0 + cc] : scalar_traits<T>::zero();
+    if (wp > 0) {  // the previous panel's pivot rows in this panel's columns, before anything is overwritten
+        for (int e = tid; e < W * W; e += NT) {
+            const int j = e / W, cc = e % W;
+            yprev[j][cc] = (j < wp && cc < w) ? a[(size_t)pprev[j] * ld + k0 + cc] : scalar_traits<T>::zero();
+        }
     }
     T r[RPT][W];
     bool used[RPT];
@@ -252,9 +310,9 @@ __global__ __launch_bounds__(NT) void nd_gj_fused_kernel(const int32_t* __restri
             }
         }
     }
-#pragma unroll
-    for (int jj = 0; jj < W; ++jj) {
-        if (jj >= w) break;
+    static_for<W>([&](auto jc) {
+        constexpr int jj = decltype(jc)::value;
+        if (jj >= w) return;
         unsigned long long key = 0ull;
 #pragma unroll
         for (int q = 0; q < RPT; ++q) {
@@ -307,7 +365,7 @@ __global__ __launch_bounds__(NT) void nd_gj_fused_kernel(const int32_t* __restri
 #pragma unroll
             for (int j = 0; j < W; ++j) fma_acc(r[q][j], nfm, prow[j]);
         }
-    }
+    });
 #pragma unroll
     for (int q = 0; q < RPT; ++q) {
         const int32_t i = tid + NT * q;
@@ -326,24 +384,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void nd_gj_stage_kernel(const int32_t* __restrict__ lvl_nodes, const NdNodeDev* __restrict__ nodes,
                                                           const T* __restrict__ front, const int32_t* __restrict__ ipiv, int32_t kb, int32_t kw,
                                                           int32_t ycap, int32_t c_lo, int32_t c_hi, T* __restrict__ ybuf) {
-    const int32_t t = lvl_nodes[blockIdx.x];
-    const NdNodeDev nd = nodes[t];
-    const int32_t m = nd.m, ld = nd.f;
-    const int32_t nb = min(kw, m - kb);
-    const int32_t c = c_lo + (int32_t)blockIdx.y * 256 + threadIdx.x;
-    if (nb <= 0 || m <= kNB || c >= min(m, c_hi)) return;
-    const T* a = front + nd.front_off;
-    T* yb = ybuf + (size_t)ycap * nd.piv_off;
-    const int32_t* pv = ipiv + nd.piv_off + kb;
-    int32_t j = 0;
-    for (; j + 4 <= nb; j += 4) {  // (independent loads, issued together)
-        const T v0 = a[(size_t)pv[j] * ld + c], v1 = a[(size_t)pv[j + 1] * ld + c], v2 = a[(size_t)pv[j + 2] * ld + c], v3 = a[(size_t)pv[j + 3] * ld + c];
-        yb[(size_t)j * m + c] = v0;
-        yb[(size_t)(j + 1) * m + c] = v1;
-        yb[(size_t)(j + 2) * m + c] = v2;
-        yb[(size_t)(j + 3) * m + c] = v3;
-    }
-    for (; j < nb; ++j) yb[(size_t)j * m + c] = a[(size_t)pv[j] * ld + c];
+    const NdNodeDev nd = nodes[lvl_nodes[blockIdx.x]];
+    gj_stage_column<T>(nd, front, ipiv, kb, kw, ycap, c_lo + (int32_t)blockIdx.y * 256 + (int32_t)threadIdx.x, c_hi, ybuf);
 }
 
 // the columns outside the finished block: A[i, c] = (i is a pivot row of the block ? 0 : A[i, c]) + sum_j Wb[i, j] Yb[j, c]
@@ -747,12 +789,11 @@ __device__ __forceinline__ void mfma_tile_product(int32_t K, FA loadA, FB loadB,
     }
 }
 
+// one 64 x 64 tile (node t, tile row and column packed) of the product KIND
 template <typename T, int KIND>
-__global__ __launch_bounds__(256) void nd_gemm_mfma_kernel(const int32_t* __restrict__ tiles, const NdNodeDev* __restrict__ nodes,
-                                                           T* __restrict__ front, T* __restrict__ lfac, T* __restrict__ ufac) {
+__device__ __forceinline__ void gemm_mfma_tile(int32_t t, int32_t packed, const NdNodeDev* __restrict__ nodes, T* __restrict__ front,
+                                               T* __restrict__ lfac, T* __restrict__ ufac, MfmaTile<T>& sm) {
     constexpr int NPL = MfmaTile<T>::NPL;
-    __shared__ MfmaTile<T> sm;
-    const int32_t t = tiles[2 * blockIdx.x], packed = tiles[2 * blockIdx.x + 1];
     const int32_t tm = packed >> 16, tn = packed & 0xFFFF;
     const NdNodeDev nd = nodes[t];
     const int32_t m = nd.m, f = nd.f, b = f - m;
@@ -805,6 +846,25 @@ __global__ __launch_bounds__(256) void nd_gemm_mfma_kernel(const int32_t* __rest
                 else *c = v;
             }
         }
+}
+
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void nd_gemm_mfma_kernel(const int32_t* __restrict__ tiles, const NdNodeDev* __restrict__ nodes,
+                                                           T* __restrict__ front, T* __restrict__ lfac, T* __restrict__ ufac) {
+    __shared__ MfmaTile<T> sm;
+    gemm_mfma_tile<T, KIND>(tiles[2 * blockIdx.x], tiles[2 * blockIdx.x + 1], nodes, front, lfac, ufac, sm);
+}
+
+// kinds 0 and 2 of a chunk in one launch (both need the inverse alone; kind 1 follows, it reads kind 0's result): the first
+// count0 workgroups take the tiles of kind 0, the others those of kind 2, each tile with the arithmetic of its own kernel
+template <typename T>
+__global__ __launch_bounds__(256) void nd_gemm_mfma_pair_kernel(const int32_t* __restrict__ tiles0, int32_t count0, const int32_t* __restrict__ tiles2,
+                                                                const NdNodeDev* __restrict__ nodes, T* __restrict__ front, T* __restrict__ lfac,
+                                                                T* __restrict__ ufac) {
+    __shared__ MfmaTile<T> sm;
+    const int32_t g = (int32_t)blockIdx.x;
+    if (g < count0) gemm_mfma_tile<T, 0>(tiles0[2 * g], tiles0[2 * g + 1], nodes, front, lfac, ufac, sm);
+    else gemm_mfma_tile<T, 2>(tiles2[2 * (g - count0)], tiles2[2 * (g - count0) + 1], nodes, front, lfac, ufac, sm);
 }
 
 // Gauss-Jordan, tournament path: the columns outside a finished group of kw <= kSB pivot columns [kb, kb + kw) of every node,
@@ -942,26 +1002,35 @@ void launch_block(lsa_ctx* ctx, lsa_ndlu* f, const NdChunk& L, int32_t kb, doubl
     };
     const int32_t kend = std::min(kb + kNB, L.max_m);
     const bool others = std::min(kNB, L.max_m - kb) > W;  // the block has columns besides one panel
+    constexpr bool between = 2 * W < kNB;                 // ... and block columns outside both the previous and the current panel can exist
+    const bool outside = L.max_m > kNB;                   // columns outside the block exist (in the larger nodes)
     int32_t kprev = -1, active_prev = 0;
     for (int32_t k0 = kb; k0 < kend; k0 += W) {
         const int32_t active = active_at(k0);
         if (active == 0) break;
         // (the tiles of this launch serve the nodes that had the previous panel: a superset of those that have this one)
-        hipLaunchKernelGGL((nd_gj_fused_kernel<T, NT, RPT, W>), dim3(std::max(active, active_prev), others && kprev >= 0 ? 1 + kNB / 16 : 1), dim3(NT), 0, st, lv,
-                           f->d_nodes, front, f->d_ipiv, f->d_rowq, kb, k0, kprev, f->d_flag, tiny2);
+        ND_LAUNCH(f, (nd_gj_fused_kernel<T, NT, RPT, W>), dim3(std::max(active, active_prev), others && between && kprev >= 0 ? 1 + kNB / 16 : 1), dim3(NT), 0,
+                  st, lv, f->d_nodes, front, f->d_ipiv, f->d_rowq, kb, k0, kprev, f->d_flag, tiny2, 0, (T*)f->d_ybuf, 0);
         kprev = k0;
         active_prev = active;
     }
-    if (others && kprev >= 0)  // the last panel's update of the block's other columns
-        hipLaunchKernelGGL((nd_gj_fused_kernel<T, NT, RPT, W>), dim3(active_prev, 1 + kNB / 16), dim3(NT), 0, st, lv, f->d_nodes, front, f->d_ipiv, f->d_rowq, kb,
-                           -1, kprev, f->d_flag, tiny2);
-    if (L.max_m > kNB) {  // columns outside the block exist (in the larger nodes)
+    const bool finish = others && kprev >= 0;
+    const bool ride = finish && outside && f->gj_panel != 8;  // the staging rides in the finishing launch
+    if (finish) {  // the last panel's update of the block's other columns
+        // (two panels: only the columns before the last panel are left.  The staging serves every node that has the block, the
+        //  tiles those that had the last panel: a prefix of them, the others leave at wp <= 0)
+        const int32_t ftiles = between ? kNB / 16 : (kprev - kb + 15) / 16;
+        ND_LAUNCH(f, (nd_gj_fused_kernel<T, NT, RPT, W>), dim3(ride ? active_at(kb) : active_prev, 1 + ftiles + (ride ? (L.max_m + NT - 1) / NT : 0)), dim3(NT),
+                  0, st, lv, f->d_nodes, front, f->d_ipiv, f->d_rowq, kb, -1, kprev, f->d_flag, tiny2, ride ? 1 + ftiles : 0, (T*)f->d_ybuf, L.max_m);
+    }
+    if (outside) {
         const int32_t active = active_at(kb);
-        hipLaunchKernelGGL((nd_gj_stage_kernel<T>), dim3(active, (L.max_m + 255) / 256), dim3(256), 0, st, lv, f->d_nodes, (const T*)front, f->d_ipiv, kb,
-                           kNB, kNB, 0, L.max_m, (T*)f->d_ybuf);
+        if (!ride)
+            ND_LAUNCH(f, (nd_gj_stage_kernel<T>), dim3(active, (L.max_m + 255) / 256), dim3(256), 0, st, lv, f->d_nodes, (const T*)front, f->d_ipiv, kb, kNB, kNB,
+                      0, L.max_m, (T*)f->d_ybuf);
         const int32_t tiles = (L.max_m + kGT - 1) / kGT;
-        hipLaunchKernelGGL((nd_gj_gemm_kernel<T>), dim3(active, tiles, tiles), dim3(256), 0, st, lv, f->d_nodes, front, f->d_rowq, kb, (const T*)f->d_ybuf, 0, 0,
-                           0, 0, 0);
+        ND_LAUNCH(f, (nd_gj_gemm_kernel<T>), dim3(active, tiles, tiles), dim3(256), 0, st, lv, f->d_nodes, front, f->d_rowq, kb, (const T*)f->d_ybuf, 0, 0,
+                  0, 0, 0);
     }
 }
 
@@ -974,18 +1043,18 @@ void launch_tournament(lsa_ndlu* f, const NdChunk& L, int32_t kb, double tiny2, 
     const int32_t active = (int32_t)(std::lower_bound(L.sorted_m.begin(), L.sorted_m.end(), kb, std::greater<int32_t>()) - L.sorted_m.begin());
     if (active == 0) return;
     int32_t sets = (L.max_m + tp_first<T>::rows - 1) / tp_first<T>::rows;
-    hipLaunchKernelGGL((nd_tp_round_kernel<T, true, false>), dim3(active, sets), dim3(256), 0, st, lv, f->d_nodes, front, f->d_ipiv, f->d_rowq, kb, 0,
-                       (const int32_t*)nullptr, f->d_cand[0], (T*)nullptr, f->d_flag, tiny2);
+    ND_LAUNCH(f, (nd_tp_round_kernel<T, true, false>), dim3(active, sets), dim3(256), 0, st, lv, f->d_nodes, front, f->d_ipiv, f->d_rowq, kb, 0,
+              (const int32_t*)nullptr, f->d_cand[0], (T*)nullptr, f->d_flag, tiny2);
     int src = 0;
     for (int32_t round = 0;; ++round) {
         const int32_t groups = (sets + kTA - 1) / kTA;
         if (groups == 1) {
-            hipLaunchKernelGGL((nd_tp_round_kernel<T, false, true>), dim3(active, 1), dim3(256), 0, st, lv, f->d_nodes, front, f->d_ipiv, f->d_rowq, kb, round,
-                               (const int32_t*)f->d_cand[src], (int32_t*)nullptr, (T*)f->d_dinv, f->d_flag, tiny2);
+            ND_LAUNCH(f, (nd_tp_round_kernel<T, false, true>), dim3(active, 1), dim3(256), 0, st, lv, f->d_nodes, front, f->d_ipiv, f->d_rowq, kb, round,
+                      (const int32_t*)f->d_cand[src], (int32_t*)nullptr, (T*)f->d_dinv, f->d_flag, tiny2);
             break;
         }
-        hipLaunchKernelGGL((nd_tp_round_kernel<T, false, false>), dim3(active, groups), dim3(256), 0, st, lv, f->d_nodes, front, f->d_ipiv, f->d_rowq, kb, round,
-                           (const int32_t*)f->d_cand[src], f->d_cand[src ^ 1], (T*)nullptr, f->d_flag, tiny2);
+        ND_LAUNCH(f, (nd_tp_round_kernel<T, false, false>), dim3(active, groups), dim3(256), 0, st, lv, f->d_nodes, front, f->d_ipiv, f->d_rowq, kb, round,
+                  (const int32_t*)f->d_cand[src], f->d_cand[src ^ 1], (T*)nullptr, f->d_flag, tiny2);
         src ^= 1;
         sets = groups;
     }
@@ -1011,12 +1080,12 @@ int launch_level_tp(lsa_ctx* ctx, lsa_ndlu* f, const NdChunk& L, double tiny2) {
     const int32_t sbw = wide ? f->sb_cols : kNB, ycap = f->ycap;
     const int32_t tiles = (L.max_m + kGT - 1) / kGT;
     auto stage = [&](int32_t active, int32_t k0, int32_t kw, int32_t c_lo, int32_t c_hi) {
-        hipLaunchKernelGGL((nd_gj_stage_kernel<T>), dim3(active, (c_hi - c_lo + 255) / 256), dim3(256), 0, st, lv, f->d_nodes, (const T*)front, f->d_ipiv, k0, kw,
-                           ycap, c_lo, c_hi, (T*)f->d_ybuf);
+        ND_LAUNCH(f, (nd_gj_stage_kernel<T>), dim3(active, (c_hi - c_lo + 255) / 256), dim3(256), 0, st, lv, f->d_nodes, (const T*)front, f->d_ipiv, k0, kw,
+                  ycap, c_lo, c_hi, (T*)f->d_ybuf);
     };
     auto update = [&](int32_t active, int32_t k0, int32_t kw, int32_t zt0, int32_t ztn, int32_t only_lo, int32_t only_hi, int32_t skip_lo, int32_t skip_hi) {
-        hipLaunchKernelGGL((nd_gj_update_kernel<T>), dim3(active, tiles, ztn), dim3(256), 0, st, lv, f->d_nodes, front, f->d_rowq, k0, kw, (const T*)f->d_ybuf,
-                           ycap, only_lo, only_hi, skip_lo, skip_hi, zt0);
+        ND_LAUNCH(f, (nd_gj_update_kernel<T>), dim3(active, tiles, ztn), dim3(256), 0, st, lv, f->d_nodes, front, f->d_rowq, k0, kw, (const T*)f->d_ybuf,
+                  ycap, only_lo, only_hi, skip_lo, skip_hi, zt0);
     };
     launch_tournament<T>(f, L, 0, tiny2, st);
     for (int32_t sb0 = 0; sb0 < L.max_m; sb0 += sbw) {
@@ -1025,8 +1094,8 @@ int launch_level_tp(lsa_ctx* ctx, lsa_ndlu* f, const NdChunk& L, double tiny2) {
         for (int32_t kb = sb0; kb < sb1; kb += kNB) {
             const int32_t active = active_at(kb);
             if (active == 0) break;
-            hipLaunchKernelGGL((nd_tp_colblock_kernel<T>), dim3(active, (L.max_m + 255) / 256), dim3(256), 0, st, lv, f->d_nodes, front, f->d_rowq, kb,
-                               (const T*)f->d_dinv);
+            ND_LAUNCH(f, (nd_tp_colblock_kernel<T>), dim3(active, (L.max_m + 255) / 256), dim3(256), 0, st, lv, f->d_nodes, front, f->d_rowq, kb,
+                      (const T*)f->d_dinv);
             if (sb1 - sb0 > kNB) {  // the super-block's other columns (earlier blocks' included), so that its next block can be searched
                 stage(active, kb, kNB, sb0, sb1);
                 update(active, kb, kNB, sb0 / kGT, (sb1 + kGT - 1) / kGT - sb0 / kGT, sb0, sb1, 0, 0);
@@ -1064,6 +1133,7 @@ int nd_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C) {
     T* upd = (T*)f->d_upd;
     int rc0 = LSA_OK;
     double max2 = 0.0;
+    f->factor_launches = 0;
     {
         // (a local failure up to here -- non-finite input, a HIP error -- is agreed on by all ranks before the first exchange)
         auto head = [&]() -> int {
@@ -1072,7 +1142,7 @@ int nd_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C) {
             LSA_HIP_CHECK(ctx, hipMemsetAsync(f->d_maxabs, 0, sizeof(unsigned long long), st));
             if (S.nnz > 0) {
                 const int blocks = (int)std::min<int64_t>((S.nnz + 255) / 256, (int64_t)ctx->num_cu * 2);
-                hipLaunchKernelGGL((nd_maxabs2_kernel<T>), dim3(blocks), dim3(256), 0, st, S.nnz, (const T*)C->val, f->d_maxabs);
+                ND_LAUNCH(f, (nd_maxabs2_kernel<T>), dim3(blocks), dim3(256), 0, st, S.nnz, (const T*)C->val, f->d_maxabs);
             }
             unsigned long long mbits = 0;
             LSA_HIP_CHECK(ctx, hipMemcpyAsync(&mbits, f->d_maxabs, sizeof mbits, hipMemcpyDeviceToHost, st));
@@ -1101,12 +1171,12 @@ int nd_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C) {
         LSA_HIP_CHECK(ctx, hipMemsetAsync(f->d_work, 0, (size_t)L.work_entries * sizeof(T), st));
         if (L.asm_count > 0) {
             const int blocks = (int)std::min<int64_t>((L.asm_count + 255) / 256, (int64_t)ctx->num_cu * 16);
-            hipLaunchKernelGGL((nd_assemble_kernel<T>), dim3(blocks), dim3(256), 0, st, L.asm_count, (const T*)C->val, f->d_asm_src + L.asm_begin,
-                               f->d_asm_dst + L.asm_begin, front);
+            ND_LAUNCH(f, (nd_assemble_kernel<T>), dim3(blocks), dim3(256), 0, st, L.asm_count, (const T*)C->val, f->d_asm_src + L.asm_begin,
+                      f->d_asm_dst + L.asm_begin, front);
         }
         for (const TileList& e : L.ext)
             if (e.count > 0)
-                hipLaunchKernelGGL((nd_extend_add_kernel<T>), dim3(e.count), dim3(256), 0, st, tl + 2 * e.off, f->d_nodes, f->d_cmap, front, (const T*)upd);
+                ND_LAUNCH(f, (nd_extend_add_kernel<T>), dim3(e.count), dim3(256), 0, st, tl + 2 * e.off, f->d_nodes, f->d_cmap, front, (const T*)upd);
         // distributed top nodes: their children's update matrices, in row chunks.  Per step: every rank copies its piece (rows of
         // a distributed child it holds, or of a subtree root it owns) into its slot of the staging buffer, one in-place
         // all-gather, then every rank adds the rows it keeps -- the pivot block and F12 rows on every rank, boundary rows on
@@ -1131,13 +1201,21 @@ int nd_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C) {
             for (int r = 0; r < S.nranks; ++r) {
                 const NdChunk::XPiece& pc = step[(size_t)r];
                 if (pc.nrows <= 0) continue;
-                hipLaunchKernelGGL((nd_extend_add_staged_kernel<T>), dim3((pc.nrows + 15) / 16), dim3(256), 0, st, f->d_nodes, f->d_cmap, front,
-                                   (const T*)(stage + (size_t)r * (size_t)stride), pc.child, pc.row0, pc.nrows);
+                ND_LAUNCH(f, (nd_extend_add_staged_kernel<T>), dim3((pc.nrows + 15) / 16), dim3(256), 0, st, f->d_nodes, f->d_cmap, front,
+                          (const T*)(stage + (size_t)r * (size_t)stride), pc.child, pc.row0, pc.nrows);
             }
         }
         if (L.max_m >= f->tp_min) LSA_CHECK(launch_level_tp<T>(ctx, f, L, tiny2));
         for (int32_t kb = 0; kb < L.max_m && L.max_m < f->tp_min; kb += kNB) {
-            if (L.max_m <= 64) launch_block<T, 64, 1, 8>(ctx, f, L, kb, tiny2);
+            // 16-column panels only on request: a thread holds its row of one in registers up to 512 rows (1024 threads have half the
+            // registers), but a panel launch of 16 pivots takes as long as two of 8 (21-27 against 11.5-13.6 us with complex
+            // factors: the pivots are a serial chain, and each one updates twice the columns), so that the default keeps 8
+            if (f->gj_panel == 16 && L.max_m <= 512) {
+                if (L.max_m <= 64) launch_block<T, 64, 1, 16>(ctx, f, L, kb, tiny2);
+                else if (L.max_m <= 128) launch_block<T, 128, 1, 16>(ctx, f, L, kb, tiny2);
+                else if (L.max_m <= 256) launch_block<T, 256, 1, 16>(ctx, f, L, kb, tiny2);
+                else launch_block<T, 512, 1, 16>(ctx, f, L, kb, tiny2);
+            } else if (L.max_m <= 64) launch_block<T, 64, 1, 8>(ctx, f, L, kb, tiny2);
             else if (L.max_m <= 128) launch_block<T, 128, 1, 8>(ctx, f, L, kb, tiny2);
             else if (L.max_m <= 256) launch_block<T, 256, 1, 8>(ctx, f, L, kb, tiny2);
             else if (L.max_m <= 512) launch_block<T, 512, 1, 8>(ctx, f, L, kb, tiny2);
@@ -1148,24 +1226,30 @@ int nd_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C) {
             else launch_block<T, 1024, 16, 1>(ctx, f, L, kb, tiny2);
         }
         if (L.unperm.count > 0)
-            hipLaunchKernelGGL((nd_unperm_kernel<T>), dim3(L.unperm.count), dim3(256), 0, st, tl + 2 * L.unperm.off, f->d_nodes, front, f->d_ipiv,
-                               f->d_rowq, lfac);
+            ND_LAUNCH(f, (nd_unperm_kernel<T>), dim3(L.unperm.count), dim3(256), 0, st, tl + 2 * L.unperm.off, f->d_nodes, front, f->d_ipiv,
+                      f->d_rowq, lfac);
         auto product = [&](auto kind) {
             constexpr int KIND = decltype(kind)::value;
             if (L.gemm[KIND].count == 0) return;
-            hipLaunchKernelGGL((nd_gemm_mfma_kernel<T, KIND>), dim3(L.gemm[KIND].count), dim3(256), 0, st, tl + 2 * L.gemm[KIND].off, f->d_nodes, front, lfac, ufac);
+            ND_LAUNCH(f, (nd_gemm_mfma_kernel<T, KIND>), dim3(L.gemm[KIND].count), dim3(256), 0, st, tl + 2 * L.gemm[KIND].off, f->d_nodes, front, lfac, ufac);
         };
-        product(std::integral_constant<int, 0>{});
-        product(std::integral_constant<int, 1>{});
-        product(std::integral_constant<int, 2>{});
+        if (f->gj_panel != 8 && L.gemm[0].count > 0 && L.gemm[2].count > 0) {  // S1 and S2 depend on the inverse alone: one launch
+            ND_LAUNCH(f, (nd_gemm_mfma_pair_kernel<T>), dim3(L.gemm[0].count + L.gemm[2].count), dim3(256), 0, st, tl + 2 * L.gemm[0].off, (int32_t)L.gemm[0].count,
+                      tl + 2 * L.gemm[2].off, f->d_nodes, front, lfac, ufac);
+            product(std::integral_constant<int, 1>{});
+        } else {
+            product(std::integral_constant<int, 0>{});
+            product(std::integral_constant<int, 1>{});
+            product(std::integral_constant<int, 2>{});
+        }
         if (L.save.count > 0)
-            hipLaunchKernelGGL((nd_save_update_kernel<T>), dim3(L.save.count), dim3(256), 0, st, tl + 2 * L.save.off, f->d_nodes, (const T*)front, upd);
+            ND_LAUNCH(f, (nd_save_update_kernel<T>), dim3(L.save.count), dim3(256), 0, st, tl + 2 * L.save.off, f->d_nodes, (const T*)front, upd);
     }
     if (f->top.s > 0)  // the merged top of the sweeps, assembled from the blocks just made (the second launch reads the first one's -Q_c)
         for (int q = 0, t0 = 0; q < 2; t0 += f->top_tiles[q++])
             if (f->top_tiles[q] > 0)
-                hipLaunchKernelGGL((nd_top_gemm_kernel<T>), dim3(f->top_tiles[q]), dim3(256), 0, st, f->d_top_tiles + 2 * t0, f->d_top_jobs, f->d_cmap,
-                                   (const T*)lfac, (const T*)ufac, (T*)f->d_top, f->top.s);
+                ND_LAUNCH(f, (nd_top_gemm_kernel<T>), dim3(f->top_tiles[q]), dim3(256), 0, st, f->d_top_tiles + 2 * t0, f->d_top_jobs, f->d_cmap,
+                          (const T*)lfac, (const T*)ufac, (T*)f->d_top, f->top.s);
     if (!exchanged && S.nranks > 1 && f->xupd_slot > 0)  // (no replicated level: still a collective)
         LSA_CHECK(k_allgather_inplace(ctx, f->d_upd, (size_t)f->xupd_slot * sizeof(T)));
     int32_t hflag[4] = {0, 0, 0, 0};
@@ -1206,7 +1290,7 @@ int nd_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C) {
         const double eps = atof(pe);
         if (eps != 0.0 && f->ufac_entries > 0) {
             const int blocks = (int)std::min<int64_t>((f->ufac_entries + 255) / 256, (int64_t)ctx->num_cu * 16);
-            hipLaunchKernelGGL((nd_scale_kernel<T>), dim3(blocks), dim3(256), 0, st, f->ufac_entries, ufac, 1.0 + eps);
+            ND_LAUNCH(f, (nd_scale_kernel<T>), dim3(blocks), dim3(256), 0, st, f->ufac_entries, ufac, 1.0 + eps);
             LSA_HIP_CHECK(ctx, hipStreamSynchronize(st));
         }
     }

@@ -172,6 +172,8 @@ struct lsa_ndlu {
     int32_t sb_min = 1 << 30;                  // ... and from this many rows on, with super-blocks of kSB columns (nd_gj_update_kernel)
     int32_t sb_cols = 128;                     // columns of a super-block (kSB; LSA_ND_SB_COLS, a multiple of 64, for measurements)
     int32_t ycap = 32;                         // rows of d_ybuf per unknown: kNB, or sb_cols when a chunk works in super-blocks
+    int32_t gj_panel = 0;                      // LSA_ND_GJ_PANEL: 0 = regrouped launches, panel width by instance; 16 = 16-column panels up to 512 rows; 8 = the earlier launch sequence
+    int32_t factor_launches = 0;               // kernel launches of the last numeric factorisation
     hipStream_t side = nullptr;                // ... the next block's tournament runs here, under the current block's update
     hipEvent_t ev_panel = nullptr, ev_pivots = nullptr;
     double seconds_analyse = 0.0, seconds_numeric = 0.0;

@@ -711,7 +711,7 @@ static int op_build(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, const lsa_
             rc = lsa_ndlu_create(ctx, fac_src, 0, &op->nd);
         if (rc == LSA_OK && op->nd) {
             double sa = 1.0;
-            (void)lsa_ndlu_info(op->nd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sa, nullptr);
+            (void)lsa_ndlu_info(op->nd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sa, nullptr, nullptr);
             op->st.analysis_reused = sa == 0.0 ? 1 : 0;
         }
         if (rc == LSA_ERR_OOM) {
@@ -1604,7 +1604,7 @@ int krylov_extend_batch(lsa_ctx* ctx, KrylovGroupBuf* gb, lsa_krylov* const* ks,
         if (lead < 0) break;
         int rc = lsa_ensure_scratch(ctx, 0, cells * (colb + 2 * sizeof(double)));
         int32_t sweep_launches = 0;
-        (void)lsa_ndlu_info(ks[lead]->op->nd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sweep_launches, nullptr, nullptr);
+        (void)lsa_ndlu_info(ks[lead]->op->nd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sweep_launches, nullptr, nullptr, nullptr);
         // ---- the rounds
         for (int32_t s = 0; s < rounds && rc == LSA_OK; ++s) {
             int32_t R = 0, jr[kKrylovGroupMax], fr[kKrylovGroupMax];

@@ -217,7 +217,8 @@ SIGNATURES = {
     "lsa_ndlu_set_multi_transposed": (ctypes.c_int, [_P, _P, ctypes.c_int]),
     "lsa_ndlu_multi_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "lsa_ndlu_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64),
-                                     ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_DBL), ctypes.POINTER(_DBL)]),
+                                     ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_DBL), ctypes.POINTER(_DBL),
+                                     ctypes.POINTER(_I32)]),
     "lsa_ndlu_sweep_level": (ctypes.c_int, [_P, _I32] + [ctypes.POINTER(_I32)] * 6),
     "lsa_gmres": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, _DBL, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_I32), ctypes.POINTER(_DBL)]),
     "lsa_op_create": (ctypes.c_int, [_P, _P, _P, _DBL * 2, ctypes.c_int, ctypes.POINTER(lsa_op_options), _PP]),
@@ -812,13 +813,14 @@ class NdLu:
         self._C = C
 
     def info(self) -> dict:
-        nt, nl, mf, nla = _I32(0), _I32(0), _I32(0), _I32(0)
+        nt, nl, mf, nla, nfl = _I32(0), _I32(0), _I32(0), _I32(0), _I32(0)
         fe, fre, ab = _I64(0), _I64(0), _I64(0)
         sa, sn = _DBL(0.0), _DBL(0.0)
         self.ctx._lib.lsa_ndlu_info(self.handle, ctypes.byref(nt), ctypes.byref(nl), ctypes.byref(mf), ctypes.byref(fe), ctypes.byref(fre),
-                                    ctypes.byref(ab), ctypes.byref(nla), ctypes.byref(sa), ctypes.byref(sn))
+                                    ctypes.byref(ab), ctypes.byref(nla), ctypes.byref(sa), ctypes.byref(sn), ctypes.byref(nfl))
         return {"tree_nodes": nt.value, "levels": nl.value, "max_front": mf.value, "factor_entries": fe.value, "front_entries": fre.value,
-                "apply_bytes": ab.value, "apply_launches": nla.value, "seconds_analyse": sa.value, "seconds_numeric": sn.value}
+                "apply_bytes": ab.value, "apply_launches": nla.value, "seconds_analyse": sa.value, "seconds_numeric": sn.value,
+                "factor_launches": nfl.value}
 
     def sweep_levels(self) -> list[dict]:
         """Per tree level (leaves first) what the sweeps launch: nodes, the widest pivot block, the rows of an upward and of a
