@@ -107,6 +107,11 @@ int lsa_spmv(lsa_ctx *ctx, const lsa_mat *A, const lsa_vec *x, lsa_vec *y);
  * values) is built once per pattern and shared by the matrices of that pattern; additions in a fixed order.  The adjoint
  * eigenproblem of Sensitivity/__init__.py:47-57,247-248 */
 int lsa_spmv_transpose(lsa_ctx *ctx, const lsa_mat *A, int conj, const lsa_vec *x, lsa_vec *y);
+/* y[z] = A_z^T x[z] or A_z^H x[z] (conj != 0), z < J <= 16, in ONE launch for matrices of one pattern (the C_k = A - z_k M built on
+ * A's index arrays by lsa_csr_axpby, or equal host patterns), one shape and one dtype, on the transposed index they share; vectors
+ * of one dtype, no y[z] among the inputs or twice.  Every output's entries are summed by the same 16 lanes in the same order as in
+ * lsa_spmv_transpose: each y[z] holds exactly its bits.  LSA_ERR_ARG, naming what differs, for anything else. */
+int lsa_spmv_transpose_batch(lsa_ctx *ctx, int32_t J, const lsa_mat *const *A, int conj, const lsa_vec *const *x, lsa_vec *const *y);
 /* Which kernel lsa_spmv launches for this matrix and vector type (template arguments included) and the bytes that
  * kernel moves per launch: values + column indices (2-byte offsets from the row's first column when the compressed form
  * is in use) + row pointers + one read of x and one write of y.  The numerator of an HBM-roofline fraction.  The name is that
@@ -235,6 +240,11 @@ int lsa_ndlu_solve_batch(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, const lsa_
  * eigenproblem (Sensitivity/__init__.py:47-57,247-287 forms A^H, M^H explicitly and factorises again) needs no second
  * factorisation and no transposed matrix. */
 int lsa_ndlu_solve_adjoint(lsa_ctx *ctx, lsa_ndlu *f, int conj, const lsa_vec *b, lsa_vec *x);
+/* x[z] = C_z^-T b[z] (conj = 0) or C_z^-H b[z] (conj != 0), z < J <= 16, under the rules of lsa_ndlu_solve_batch (factorisations of
+ * one analysis on one rank, vectors of one dtype, no shared factorisation or output: LSA_ERR_ARG otherwise): the transposed sweeps
+ * of the whole batch in one launch per tree level and direction, and each x[z] holds exactly the bits
+ * lsa_ndlu_solve_adjoint(f[z], conj, b[z]) gives.  b[z] == x[z] solves in place; several problems may read one b. */
+int lsa_ndlu_solve_batch_adjoint(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, int conj, const lsa_vec *const *b, lsa_vec *const *x);
 int lsa_ndlu_solve_time(lsa_ctx *ctx, lsa_ndlu *f, const lsa_vec *b, lsa_vec *x, int iters, double *avg_ms);
 /* X[:, q] = op(C)^-1 B[:, q], q < nrhs, on ONE factorisation: PETSc MatMatSolve / KSPMatSolve (the reference reaches them through
  * the kept KSP of iKSP, Solver/utils.py:331-419, one right-hand side at a time).  trans: 0 = C^-1, 1 = C^-T, 2 = C^-H.  B and X are
@@ -706,6 +716,11 @@ typedef struct {
     double seconds_product;    /* device seconds of their check products, weight products, sums and the accumulation       */
     double seconds_dense;      /* host seconds of the loop's dense eigen-solves (lsa_stochastic_solve)                      */
     lsa_stats solver;          /* counters of the inner solves (op_applies, refined_solves, backward_accepted, max_rel_res) */
+    int32_t batch_adjoint;     /* lsa_stochastic_set_batch_adjoint is on                                                    */
+    int64_t adjoint_batches;   /* grouped calls of the batched transposed sweeps with more than one set, since creation     */
+    int64_t forward_batches;   /* ... and of the batched forward sweeps                                                     */
+    double seconds_solve_adjoint;   /* the adjoint sweeps' share of seconds_solve                                           */
+    double seconds_product_adjoint; /* the adjoint check products' share of seconds_product                                 */
 } lsa_stochastic_stats;
 /* A, M: real (LSA_F64) whole square matrices on one shared pattern, both outliving the handle.  shifts[2 nodes]: the nodes z_k (re,
  * im pairs); weights[nodes]: w_k > 0.  Builds C_k = A - z_k M and keeps nodes factor sets alive on one ordering and one pattern-only
@@ -732,9 +747,14 @@ int lsa_stochastic_set_weights(lsa_ctx *ctx, lsa_stochastic *h, const lsa_mat *Q
 int lsa_stochastic_set_kind(lsa_ctx *ctx, lsa_stochastic *h, int32_t kind);
 /* on != 0: the forward solves of a step (the second ones of kind 0, the first ones of kind 1) go through the batched sweeps of
  * lsa_ndlu_solve_batch, in groups of at most 16 factor sets of one analysis; a node that carries the refinement step runs alone.  The
- * results are those of the default, bit for bit.  Off by default.  (Batched adjoint sweeps are not built: those solves run node by
- * node.) */
+ * results are those of the default, bit for bit.  Off by default.  (The adjoint solves have a switch of their own:
+ * lsa_stochastic_set_batch_adjoint.) */
 int lsa_stochastic_set_batch_forward(lsa_ctx *ctx, lsa_stochastic *h, int on);
+/* on != 0: the adjoint solves of a step (the first ones of kind 0, the second ones of kind 1) go through the batched transposed
+ * sweeps of lsa_ndlu_solve_batch_adjoint, in groups of at most 16 factor sets of one analysis -- a node that carries the refinement
+ * step runs alone --, and their check products C_k^H z_k through lsa_spmv_transpose_batch in groups of 16.  The log, the verdicts
+ * and every result are those of the default, bit for bit.  Off by default; does not begin the iteration anew. */
+int lsa_stochastic_set_batch_adjoint(lsa_ctx *ctx, lsa_stochastic *h, int on);
 /* on != 0: every solve of every node carries the refinement step from the start (for tests: at small sizes no solve misses ksp_rtol) */
 int lsa_stochastic_set_refinement(lsa_ctx *ctx, lsa_stochastic *h, int on);
 /* One operator apply on a host vector in the matrices' own numbering: host_y = S host_v (kind 1: S'), each of its 2 nodes solves

@@ -18,8 +18,8 @@ iteration on it with ``nodes`` factorisations of ``A - i omega_k M`` kept alive 
 the integrand is the caller's to check, by solving again with more.  Near sharp resonances the leading variances converge slowly in
 ``nodes`` (their sum converges much sooner); ``discount=beta`` evaluates ``W`` at ``beta + i omega`` and smooths the integrand, as it
 does for the resolvent.  Forcing and response windows and weights mean what they mean in :class:`Solver.resolvent.ResolventSolver`
-and are built on the device the same way (``CsrMatrix.windowed``).  Batched adjoint sweeps, a trace or captured-fraction estimate,
-several ranks, complex pencils and refactorising factor sets when ``nodes`` of them do not fit are not built.
+and are built on the device the same way (``CsrMatrix.windowed``).  ``batch_adjoint=True`` sends the adjoint solves of a step through
+the batched transposed sweeps (same bits; off by default).  A trace or captured-fraction estimate, several ranks, complex pencils and refactorising factor sets when ``nodes`` of them do not fit are not built.
 """
 
 from __future__ import annotations
@@ -136,7 +136,7 @@ class StochasticForcingSolver:
     def __init__(self, A, M, cfg: StochasticConfig | None = None, *, device: int = 0, layout: str = "single",
                  pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
                  ksp_rtol: float | None = None, forcing_window=None, response_window=None, forcing_weight=None, response_weight=None,
-                 discount: float = 0.0, batch_forward: bool = True) -> None:
+                 discount: float = 0.0, batch_forward: bool = True, batch_adjoint: bool = False) -> None:
         if A is None:
             raise ValueError("Operator A is required.")
         if M is None:
@@ -179,6 +179,9 @@ class StochasticForcingSolver:
         # the forward solves of a step through the batched sweeps: same bits, and 0.79-0.92 of the default's time per step on every
         # case measured, so the front end switches it on; a new library handle has it off
         self._batch_forward = bool(batch_forward)
+        # the adjoint solves through the batched transposed sweeps and their check products in groups of 16 per launch: same bits;
+        # off until its measurement has been through the GPU suite
+        self._batch_adjoint = bool(batch_adjoint)
         self._force_refinement = False  # (tests: every solve with the refinement step)
 
     @property
@@ -233,10 +236,13 @@ class StochasticForcingSolver:
             basis.set_kind(KINDS[kind])
             if self._batch_forward:
                 basis.set_batch_forward(True)
+            if self._batch_adjoint:
+                basis.set_batch_adjoint(True)
             if self._force_refinement:
                 basis.set_refinement(True)
             rng = np.random.default_rng(self._seed)
             out = basis.solve(nev, cfg.atol, cfg.max_it, v0=rng.standard_normal(self._n)[perm], seed=self._seed, max_out=nev)
+            batches = basis.info()  # (the grouped sweep calls of the iteration alone, like its solve counts: before the spectrum's applies)
             k = len(out["variances"])
             spectrum = np.zeros((k, om.size))
             for j in range(k):  # one apply per mode: node k's share of e_j^T Q S e_j
@@ -253,8 +259,10 @@ class StochasticForcingSolver:
                  "refined_adjoint": out["refined_adjoint"], "refined_forward": out["refined_forward"],
                  "refinements": out["refined_adjoint"] + out["refined_forward"], "backward_accepted": st["backward_accepted"],
                  "max_rel_res": st["max_rel_res"], "analysis_reused": bool(st["analysis_reused"]), "batch_forward": self._batch_forward,
+                 "batch_adjoint": bool(info["batch_adjoint"]), "adjoint_batches": batches["adjoint_batches"], "forward_batches": batches["forward_batches"],
                  "stochastic_bytes": info["bytes"], "seconds_factor": info["seconds_factor"], "seconds_solve": info["seconds_solve"],
-                 "seconds_product": info["seconds_product"], "seconds_dense": info["seconds_dense"], "seconds_expand": out["seconds_expand"],
+                 "seconds_product": info["seconds_product"], "seconds_solve_adjoint": info["seconds_solve_adjoint"],
+                 "seconds_product_adjoint": info["seconds_product_adjoint"], "seconds_dense": info["seconds_dense"], "seconds_expand": out["seconds_expand"],
                  "seconds_restart": out["seconds_restart"], "seconds_total": time.time() - started}
         return StochasticResult(out["variances"], out["modes"], kind, om, w, spectrum, out["estimates"], stats, beta)
 

@@ -262,6 +262,10 @@ constexpr int kKrylovGroupMax = 16;
 // y = A x                       (spmv.hip)
 int k_spmv(lsa_ctx* ctx, const lsa_mat* A, int xdtype, const void* x, void* y);
 int k_spmv_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, int xdtype, const void* x, void* y);
+// ys[z] = mats[z]^T xs[z] (conj != 0: ^H), z < J <= 16, in one launch on the transposed index of one pattern; each ys[z] holds
+// k_spmv_transpose's bits.  LSA_ERR_ARG naming what differs unless n, ncols, nnz and dtype agree and the matrices share the pattern
+// object or their index arrays, or have equal host patterns
+int k_spmv_transpose_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* mats, int conj, int xdtype, const void* const* xs, void* const* ys);
 // `to` has `from`'s pattern and scalar type (lsa_csr_window): it borrows the row groups and compressed indices k_spmv uses for `from`
 // (built here where `from` has not met a product yet), so that both take one kernel form; owns_extras = false, `from` outlives `to`
 void spmv_share_extras(const lsa_mat* from, lsa_mat* to);

@@ -836,26 +836,42 @@ int lsa_ndlu_solve(lsa_ctx* ctx, lsa_ndlu* f, const lsa_vec* b, lsa_vec* x) {
     return LSA_OK;
 }
 
-int lsa_ndlu_solve_batch(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const lsa_vec* const* b, lsa_vec* const* x) {
-    if (!ctx || !f || !b || !x) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: null argument");
-    if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: J = %d outside [1, %d]", J, kNdBatchMax);
+// the argument rules of a batched solve, forward or transposed (`who` names the entry in the message), and the device pointers
+static int nd_batch_check(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, const lsa_vec* const* b, lsa_vec* const* x, const void** bd,
+                          void** xd) {
+    if (!ctx || !f || !b || !x) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument", who);
+    if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: J = %d outside [1, %d]", who, J, kNdBatchMax);
     for (int32_t z = 0; z < J; ++z) {
-        if (!f[z] || !b[z] || !x[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: null argument (problem %d)", z);
+        if (!f[z] || !b[z] || !x[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument (problem %d)", who, z);
         if (b[z]->n != f[z]->S.n || x[z]->n != f[z]->S.n || b[z]->dtype != x[z]->dtype || x[z]->dtype != x[0]->dtype)
-            return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: shape/dtype mismatch (problem %d)", z);
+            return lsa_set_error(ctx, LSA_ERR_ARG, "%s: shape/dtype mismatch (problem %d)", who, z);
         if (!nd_batch_compatible(f[0], f[z]))
-            return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: factorisation %d is not of the same analysis as factorisation 0", z);
+            return lsa_set_error(ctx, LSA_ERR_ARG, "%s: factorisation %d is not of the same analysis as factorisation 0", who, z);
         for (int32_t y = 0; y < z; ++y)
             if (f[y] == f[z] || x[y]->d == x[z]->d || x[y]->d == b[z]->d || b[y]->d == x[z]->d)
-                return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_batch: problems %d and %d share a factorisation or an output", y, z);
+                return lsa_set_error(ctx, LSA_ERR_ARG, "%s: problems %d and %d share a factorisation or an output", who, y, z);
     }
-    const void* bd[kNdBatchMax];
-    void* xd[kNdBatchMax];
     for (int32_t z = 0; z < J; ++z) {
         bd[z] = b[z]->d;
         xd[z] = x[z]->d;
     }
+    return LSA_OK;
+}
+
+int lsa_ndlu_solve_batch(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const lsa_vec* const* b, lsa_vec* const* x) {
+    const void* bd[kNdBatchMax];
+    void* xd[kNdBatchMax];
+    LSA_CHECK(nd_batch_check(ctx, "lsa_ndlu_solve_batch", J, f, b, x, bd, xd));
     LSA_CHECK(ndlu_solve_batch_dev(ctx, J, f, x[0]->dtype, bd, xd));
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return LSA_OK;
+}
+
+int lsa_ndlu_solve_batch_adjoint(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, const lsa_vec* const* b, lsa_vec* const* x) {
+    const void* bd[kNdBatchMax];
+    void* xd[kNdBatchMax];
+    LSA_CHECK(nd_batch_check(ctx, "lsa_ndlu_solve_batch_adjoint", J, f, b, x, bd, xd));
+    LSA_CHECK(ndlu_solve_batch_adjoint_dev(ctx, J, f, conj, x[0]->dtype, bd, xd));
     LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return LSA_OK;
 }

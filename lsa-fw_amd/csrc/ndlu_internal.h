@@ -216,6 +216,9 @@ int ndlu_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C);
 // such a b_z is replaced in the caller's array by the problem's own copy of it)
 bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g);
 int ndlu_solve_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, const void** b, void* const* x);
+// ... and x_z = C_z^-T b_z (conj == 0) or C_z^-H b_z (conj != 0; real factors: the transposed solve) under the same rules: the
+// transposed sweeps of all J problems in one launch per level and direction, each x_z with the bits of ndlu_solve_adjoint_dev
+int ndlu_solve_batch_adjoint_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, const void** b, void* const* x);
 // ndlu_multi.hip: X[:, q] = C^-1 B[:, q], q < nrhs, on device pointers (column q at q * ld scalars; B == X with ldb == ldx allowed),
 // in passes of up to kNdMultiMax (complex vectors: 4) columns that share every factor load; not synchronised.  One rank, no distributed node.
 int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx);

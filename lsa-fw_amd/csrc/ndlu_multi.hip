@@ -492,7 +492,7 @@ __global__ __launch_bounds__(256) void nd_sweepT_multi_kernel(const NdSweepNode*
     }
 }
 
-// x_q = C^-T b_q (C^-H b_q with CONJ) for the R columns of one pass: the launches of nd_apply_T for one rank and no distributed
+// x_q = C^-T b_q (C^-H b_q with CONJ) for the R columns of one pass: the launches of nd_sweepT for one rank and no distributed
 // node -- all levels upward, then all levels downward, the unmerged blocks throughout (the transposed sweeps do not use the
 // assembled top).  Column 0 runs on the factorisation's own update vectors, column q > 0 on f->multi[q - 1].ubuf; the slot rows
 // and boundary vectors of the forward sweeps are not touched.

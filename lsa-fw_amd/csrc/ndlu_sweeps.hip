@@ -1,6 +1,7 @@
 // Nested-dissection multifrontal LU, the solves: the upward and downward sweeps over the tree (one launch per level and
 // direction; the root and its children as one launch where the top is merged), their exchanges over distributed nodes, the
-// transposed sweeps, and the one driver behind lsa_ndlu_solve, lsa_ndlu_solve_batch and the solver's inner solves.
+// transposed sweeps (solo and batched alike: lsa_ndlu_solve_adjoint, lsa_ndlu_solve_batch_adjoint), and the one driver behind
+// lsa_ndlu_solve, lsa_ndlu_solve_batch and the solver's inner solves.
 // Layout and sweep scheme: ndlu.hip; records and tables: ndlu_internal.h.
 #include "ndlu_sweep_parts.h"
 
@@ -85,7 +86,8 @@ __device__ __forceinline__ void nd_fwd_tile(const NdSweepNode& nd, int32_t r0, V
 // ---- what a sweep launch gets per problem: the factors and vectors of NB factorisations of one analysis, by value in the
 // kernel arguments (the problem index picks them: a uniform load from the argument segment).  The tables are shared.  A solo
 // solve is the batch of one (NB = 1: 64 bytes, the problem index a constant); lsa_ndlu_solve_batch instantiates NB = kNdBatchMax
-// whatever J.  Every problem runs the same grid and tiles, so it gets the same bits either way.
+// whatever J.  Every problem runs the same grid and tiles, so it gets the same bits either way.  The transposed sweeps
+// (nd_sweepT_kernel) take the same record and read lfac, ufac, rhs, x and ubuf of it.
 template <int NB>
 struct NdSweepPtrs {
     const void* lfac[NB];
@@ -305,21 +307,18 @@ __global__ __launch_bounds__(256) void nd_dist_unpack_kernel(const int32_t* __re
 // Column access of row-major blocks: 64 lanes run along a row (coalesced), four slices of the rows per workgroup.  These
 // sweeps keep the pull form (gather rows + update vectors) and address the vectors through idx.
 // (maybe_conj: ndlu_sweep_parts.h, shared with the multi-column form of this kernel in ndlu_multi.hip.)
-template <typename MT, typename VT, bool CONJ, bool DOWN>
-__global__ __launch_bounds__(256) void nd_sweepT_kernel(const NdSweepNode* __restrict__ lnodes, const MT* __restrict__ lfac, const MT* __restrict__ ufac,
-                                                        const int32_t* __restrict__ idx, const int32_t* __restrict__ gell,
-                                                        const VT* __restrict__ rhs, VT* __restrict__ x, VT* __restrict__ ubuf,
-                                                        const int64_t* __restrict__ tgoff, VT* __restrict__ pz, int64_t tg_slot, int32_t rank) {
-    __shared__ VT vs[kCH];
-    __shared__ VT part[4][64];
-    const NdSweepNode nd = lnodes[blockIdx.x];
+// One tile: 64 outputs from c0 of node nd.  DIST: the node may be distributed (this rank's rows only, the sums go to the rank's
+// slot of the partial buffer); a batch has no such node.
+template <typename MT, typename VT, bool CONJ, bool DOWN, bool DIST>
+__device__ __forceinline__ void nd_sweepT_tile(const NdSweepNode& nd, int32_t c0, VT* vs, VT (*part)[64], const MT* __restrict__ lfac,
+                                               const MT* __restrict__ ufac, const int32_t* __restrict__ idx, const int32_t* __restrict__ gell,
+                                               const VT* __restrict__ rhs, VT* __restrict__ x, VT* __restrict__ ubuf, const int64_t* __restrict__ tgoff,
+                                               VT* __restrict__ pz, int64_t tg_slot, int32_t rank) {
     const int32_t m = nd.m, f = nd.f, b = f - m;
-    const bool dist = (nd.flags & 1) != 0;  // a distributed node: this rank's rows only, the sums go to its slot of the partial buffer
+    const bool dist = DIST && (nd.flags & 1) != 0;
     const int32_t ncols = DOWN ? m : f;                         // outputs of this sweep
     const int32_t klo = DOWN ? nd.brow0 : nd.orow0;             // rows summed over: this rank's (all of them unless the node is distributed)
     const int32_t K = DOWN ? nd.brow : nd.orows;
-    const int32_t c0 = (int32_t)blockIdx.y * 64;
-    if (c0 >= ncols || (DOWN && b == 0)) return;
     const int32_t* ix = idx + nd.idx_off;
     const int32_t* ge = gell + nd.ge_off;
     const int tid = threadIdx.x, lane = tid & 63, sl = tid >> 6;
@@ -360,6 +359,22 @@ __global__ __launch_bounds__(256) void nd_sweepT_kernel(const NdSweepNode* __res
         else if (r < m) x[ix[r]] = z;
         else ubuf[nd.u_off + (r - m)] = s_sub(gather_updates(ge, nd.nchild, f, r, ubuf, scalar_traits<VT>::zero()), z);
     }
+}
+
+// transposed sweep, one tree level: workgroup (x = node of the level, y = tile of 64 outputs, z = problem).  Of the per-problem
+// pointers only lfac, ufac, rhs, x and ubuf are read; the partial-sum arguments of distributed nodes serve NB = 1 alone.
+template <typename MT, typename VT, bool CONJ, bool DOWN, int NB>
+__global__ __launch_bounds__(256) void nd_sweepT_kernel(const NdSweepNode* __restrict__ lnodes, const int32_t* __restrict__ idx,
+                                                        const int32_t* __restrict__ gell, NdSweepPtrs<NB> p, const int64_t* __restrict__ tgoff,
+                                                        VT* __restrict__ pz, int64_t tg_slot, int32_t rank) {
+    __shared__ VT vs[kCH];
+    __shared__ VT part[4][64];
+    const NdSweepNode nd = lnodes[blockIdx.x];
+    const int32_t c0 = (int32_t)blockIdx.y * 64;
+    if (c0 >= (DOWN ? nd.m : nd.f) || (DOWN && nd.f == nd.m)) return;
+    const int z = NB == 1 ? 0 : blockIdx.z;
+    nd_sweepT_tile<MT, VT, CONJ, DOWN, NB == 1>(nd, c0, vs, part, (const MT*)p.lfac[z], (const MT*)p.ufac[z], idx, gell, (const VT*)p.rhs[z], (VT*)p.x[z],
+                                                (VT*)p.ubuf[z], tgoff, pz, tg_slot, rank);
 }
 
 // The distributed nodes of a level after the exchange of their partial sums: z = the ranks' partials added in rank order (the same
@@ -488,39 +503,53 @@ int nd_ensure_transposed_dist(lsa_ctx* ctx, lsa_ndlu* f) {
     return LSA_OK;
 }
 
-template <typename MT, typename VT, bool CONJ>
-int nd_apply_T(lsa_ctx* ctx, lsa_ndlu* f, const VT* b, VT* x) {
+// x_z = C_z^-T b_z (CONJ: C_z^-H) for J <= NB factorisations of one analysis, in the shape of nd_sweep: one launch per level and
+// direction for all of them, on the tables of f[0].  A solo solve is J = NB = 1; the exchanges over distributed nodes act on f[0]
+// alone.  The sweeps have no assembled top: every level is launched in both directions.
+template <typename MT, typename VT, bool CONJ, int NB>
+int nd_sweepT(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const VT* const* b, VT* const* x) {
     hipStream_t st = ctx->stream;
-    const MT* lfac = (const MT*)f->d_lfac;
-    const MT* ufac = (const MT*)f->d_ufac;
-    const NdSymbolic& S = f->S;
-    LSA_CHECK(nd_ensure_transposed_dist(ctx, f));
-    VT* pz = (VT*)f->d_tg;
-    for (size_t li = 0; li <= f->levels.size(); ++li) {
-        if ((int32_t)li == S.phase_b_level && S.nranks > 1 && S.xu_slot > 0) LSA_CHECK(k_allgather_inplace(ctx, f->d_ubuf, (size_t)S.xu_slot * sizeof(VT)));
-        if (li == f->levels.size()) break;
-        const NdLevel& L = f->levels[li];
-        const int64_t slot = L.dist_count > 0 ? f->tg_slot[li] : 0;
+    lsa_ndlu* f0 = f[0];
+    const NdSymbolic& S = f0->S;
+    if (J < 1 || J > NB || (J > 1 && (S.nranks > 1 || S.has_dist)))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu: a batch of %d transposed solves needs one rank, no distributed node and at most %d problems", J, NB);
+    NdSweepPtrs<NB> p;
+    memset(&p, 0, sizeof p);
+    for (int32_t z = 0; z < J; ++z) {
+        p.lfac[z] = f[z]->d_lfac;
+        p.ufac[z] = f[z]->d_ufac;
+        p.rhs[z] = b[z];
+        p.x[z] = x[z];
+        p.ubuf[z] = f[z]->d_ubuf;
+    }
+    LSA_CHECK(nd_ensure_transposed_dist(ctx, f0));
+    VT* pz = (VT*)f0->d_tg;
+    VT* x0 = x[0];
+    for (size_t li = 0; li <= f0->levels.size(); ++li) {
+        if ((int32_t)li == S.phase_b_level && S.nranks > 1 && S.xu_slot > 0) LSA_CHECK(k_allgather_inplace(ctx, f0->d_ubuf, (size_t)S.xu_slot * sizeof(VT)));
+        if (li == f0->levels.size()) break;
+        const NdLevel& L = f0->levels[li];
+        const int64_t slot = L.dist_count > 0 ? f0->tg_slot[li] : 0;
         if (L.fwd_tiles > 0)
-            hipLaunchKernelGGL((nd_sweepT_kernel<MT, VT, CONJ, false>), dim3(L.node_count, (L.max_f + 63) / 64), dim3(256), 0, st, f->d_lnodes + L.node_begin,
-                               lfac, ufac, f->d_idx, f->d_gell, b, x, (VT*)f->d_ubuf, f->d_tgoff ? f->d_tgoff + L.node_begin : nullptr, pz, slot, S.rank);
+            hipLaunchKernelGGL((nd_sweepT_kernel<MT, VT, CONJ, false, NB>), dim3(L.node_count, (L.max_f + 63) / 64, J), dim3(256), 0, st,
+                               f0->d_lnodes + L.node_begin, f0->d_idx, f0->d_gell, p, f0->d_tgoff ? f0->d_tgoff + L.node_begin : nullptr, pz, slot, S.rank);
         if (L.dist_count > 0) {
             // the distributed nodes of the level: every rank summed over its rows; partials to all, added in rank order
             LSA_CHECK(k_allgather_inplace(ctx, pz, (size_t)slot * sizeof(VT)));
-            hipLaunchKernelGGL((nd_distT_finish_kernel<VT, false>), dim3(L.node_count, (L.max_f + 255) / 256), dim3(256), 0, st, f->d_lnodes + L.node_begin,
-                               f->d_tgoff + L.node_begin, f->d_idx, f->d_gell, (const VT*)pz, slot, S.nranks, S.rank, L.ux_slot, x, (VT*)f->d_ubuf);
+            hipLaunchKernelGGL((nd_distT_finish_kernel<VT, false>), dim3(L.node_count, (L.max_f + 255) / 256), dim3(256), 0, st, f0->d_lnodes + L.node_begin,
+                               f0->d_tgoff + L.node_begin, f0->d_idx, f0->d_gell, (const VT*)pz, slot, S.nranks, S.rank, L.ux_slot, x0, (VT*)f0->d_ubuf);
         }
     }
-    for (size_t l = f->levels.size(); l-- > 0;) {
-        const NdLevel& L = f->levels[l];
-        const int64_t slot = L.dist_count > 0 ? f->tg_slot[l] : 0;
+    for (size_t l = f0->levels.size(); l-- > 0;) {
+        const NdLevel& L = f0->levels[l];
+        const int64_t slot = L.dist_count > 0 ? f0->tg_slot[l] : 0;
         if (L.bwd_tiles > 0 || L.dist_count > 0)
-            hipLaunchKernelGGL((nd_sweepT_kernel<MT, VT, CONJ, true>), dim3(L.node_count, (L.max_m + 63) / 64), dim3(256), 0, st, f->d_lnodes + L.node_begin,
-                               lfac, ufac, f->d_idx, f->d_gell, b, x, (VT*)f->d_ubuf, f->d_tgoff ? f->d_tgoff + L.node_begin : nullptr, pz, slot, S.rank);
+            hipLaunchKernelGGL((nd_sweepT_kernel<MT, VT, CONJ, true, NB>), dim3(L.node_count, (L.max_m + 63) / 64, J), dim3(256), 0, st,
+                               f0->d_lnodes + L.node_begin, f0->d_idx, f0->d_gell, p, f0->d_tgoff ? f0->d_tgoff + L.node_begin : nullptr, pz, slot, S.rank);
         if (L.dist_count > 0) {
             LSA_CHECK(k_allgather_inplace(ctx, pz, (size_t)slot * sizeof(VT)));
-            hipLaunchKernelGGL((nd_distT_finish_kernel<VT, true>), dim3(L.node_count, (L.max_m + 255) / 256), dim3(256), 0, st, f->d_lnodes + L.node_begin,
-                               f->d_tgoff + L.node_begin, f->d_idx, f->d_gell, (const VT*)pz, slot, S.nranks, S.rank, L.ux_slot, x, (VT*)f->d_ubuf);
+            hipLaunchKernelGGL((nd_distT_finish_kernel<VT, true>), dim3(L.node_count, (L.max_m + 255) / 256), dim3(256), 0, st, f0->d_lnodes + L.node_begin,
+                               f0->d_tgoff + L.node_begin, f0->d_idx, f0->d_gell, (const VT*)pz, slot, S.nranks, S.rank, L.ux_slot, x0, (VT*)f0->d_ubuf);
         }
     }
     LSA_HIP_CHECK(ctx, hipGetLastError());
@@ -554,6 +583,17 @@ int nd_solve(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int v
     });
 }
 
+template <int NB>
+int nd_solve_adjoint(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, const void** bd, void* const* x) {
+    return nd_dispatch_solve(ctx, who, J, f, vdtype, bd, x, [&](auto mt, auto vt) {
+        using MT = decltype(mt);
+        using VT = decltype(vt);
+        if constexpr (std::is_same<MT, cplx>::value)  // (real factors: C^H = C^T)
+            if (conj) return nd_sweepT<MT, VT, true, NB>(ctx, J, f, (const VT* const*)bd, (VT* const*)x);
+        return nd_sweepT<MT, VT, false, NB>(ctx, J, f, (const VT* const*)bd, (VT* const*)x);
+    });
+}
+
 }  // namespace
 
 // g can run in a batch with f: one rank, no distributed nodes, and the same analysis (pattern, constraints, forest or leaf size,
@@ -579,13 +619,12 @@ bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g) {
 
 // x = C^-T b (conj == 0) or C^-H b (conj != 0) on the factors of C
 int ndlu_solve_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, const void* b, void* x) {
-    return nd_dispatch_solve(ctx, "lsa_ndlu_solve_adjoint", 1, &f, vdtype, &b, &x, [&](auto mt, auto vt) {
-        using MT = decltype(mt);
-        using VT = decltype(vt);
-        if constexpr (std::is_same<MT, cplx>::value)  // (real factors: C^H = C^T)
-            if (conj) return nd_apply_T<MT, VT, true>(ctx, f, (const VT*)b, (VT*)x);
-        return nd_apply_T<MT, VT, false>(ctx, f, (const VT*)b, (VT*)x);
-    });
+    return nd_solve_adjoint<1>(ctx, "lsa_ndlu_solve_adjoint", 1, &f, conj, vdtype, &b, &x);
+}
+
+// the same for J factorisations of one analysis (nd_batch_compatible), one launch per level and direction for all of them
+int ndlu_solve_batch_adjoint_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, const void** b, void* const* x) {
+    return nd_solve_adjoint<kNdBatchMax>(ctx, "lsa_ndlu_solve_batch_adjoint", J, f, conj, vdtype, b, x);
 }
 
 // x = C^-1 b on device pointers (b and x distinct or identical: an aliased right-hand side is copied first)

@@ -449,9 +449,9 @@ int k_spmv(lsa_ctx* ctx, const lsa_mat* A, int xdtype, const void* x, void* y) {
 // rounding depended on the order in which additions arrived -- 11 of 12 adjoint solves in processes sharing a GPU differed in
 // the last bits, tools/micro/repro_under_sharing.py, and the ranks of a sharded adjoint solve need replicated vectors alike.)
 template <typename MT, typename VT>
-__global__ __launch_bounds__(256) void spmv_transpose_pull_kernel(int32_t ncols, int conj, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                                                  const int32_t* __restrict__ src, const MT* __restrict__ val,
-                                                                  const VT* __restrict__ x, VT* __restrict__ y) {
+__device__ __forceinline__ void spmv_transpose_pull(int32_t ncols, int conj, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                    const int32_t* __restrict__ src, const MT* __restrict__ val, const VT* __restrict__ x,
+                                                    VT* __restrict__ y) {
     constexpr int LPR = 16;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int32_t lane = (int32_t)(gid % LPR);
@@ -467,6 +467,31 @@ __global__ __launch_bounds__(256) void spmv_transpose_pull_kernel(int32_t ncols,
         for (int m = LPR / 2; m > 0; m >>= 1) acc = s_add(acc, shfl_xor_t<VT>(acc, m));
         if (lane == 0) y[c] = acc;
     }
+}
+
+template <typename MT, typename VT>
+__global__ __launch_bounds__(256) void spmv_transpose_pull_kernel(int32_t ncols, int conj, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                                  const int32_t* __restrict__ src, const MT* __restrict__ val,
+                                                                  const VT* __restrict__ x, VT* __restrict__ y) {
+    spmv_transpose_pull<MT, VT>(ncols, conj, rp, ci, src, val, x, y);
+}
+
+// The same for up to kSpmvBatchMax matrices on ONE transposed index (one pattern): blockIdx.y is the problem, its values and
+// vectors come by value in the kernel arguments (a uniform load by the problem index).  An output's entries meet the same 16 lanes
+// in the same order whatever the grid, so every problem gets k_spmv_transpose's bits.
+constexpr int kSpmvBatchMax = 16;
+struct SpmvTransposePtrs {
+    const void* val[kSpmvBatchMax];
+    const void* x[kSpmvBatchMax];
+    void* y[kSpmvBatchMax];
+};
+
+template <typename MT, typename VT>
+__global__ __launch_bounds__(256) void spmv_transpose_pull_batch_kernel(int32_t ncols, int conj, const int32_t* __restrict__ rp,
+                                                                        const int32_t* __restrict__ ci, const int32_t* __restrict__ src,
+                                                                        SpmvTransposePtrs p) {
+    const int z = blockIdx.y;
+    spmv_transpose_pull<MT, VT>(ncols, conj, rp, ci, src, (const MT*)p.val[z], (const VT*)p.x[z], (VT*)p.y[z]);
 }
 
 static int ensure_transpose(lsa_ctx* ctx, const lsa_mat* A) {
@@ -522,6 +547,50 @@ int k_spmv_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, int xdtype, const
     return LSA_OK;
 }
 
+// whether B has A's pattern: the index arrays or the pattern object shared, or equal host copies
+static bool spmv_same_pattern(const lsa_mat* A, const lsa_mat* B) {
+    if (A->rp == B->rp && A->ci == B->ci) return true;
+    if (A->h_shared && A->h_shared == B->h_shared) return true;
+    if (A->h_rp.size() == 0 || A->h_ci.size() == 0 || B->h_rp.size() == 0 || B->h_ci.size() == 0) return false;
+    return A->h_rp == B->h_rp && A->h_ci == B->h_ci;
+}
+
+int k_spmv_transpose_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* mats, int conj, int xdtype, const void* const* xs, void* const* ys) {
+    if (J < 1 || J > kSpmvBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose_batch: J = %d outside [1, %d]", J, kSpmvBatchMax);
+    const lsa_mat* A = mats[0];
+    if (A->row0 != 0 || A->n != A->ncols) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose_batch: sharded matrices are not supported");
+    for (int32_t z = 1; z < J; ++z) {
+        const lsa_mat* B = mats[z];
+        if (B->n != A->n) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose_batch: matrix %d has n = %d, matrix 0 has n = %d", z, B->n, A->n);
+        if (B->ncols != A->ncols || B->row0 != A->row0)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose_batch: matrix %d has ncols = %d, matrix 0 has ncols = %d", z, B->ncols, A->ncols);
+        if (B->nnz != A->nnz)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose_batch: matrix %d has nnz = %lld, matrix 0 has nnz = %lld", z, (long long)B->nnz, (long long)A->nnz);
+        if (B->dtype != A->dtype) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose_batch: matrix %d has another dtype than matrix 0", z);
+        if (!spmv_same_pattern(A, B)) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose_batch: matrix %d has another pattern than matrix 0", z);
+    }
+    if (A->dtype == LSA_C128 && xdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose_batch: a complex matrix needs complex vectors");
+    LSA_CHECK(ensure_transpose(ctx, A));
+    const TransposeIndex& T = *A->h_shared->tr;
+    SpmvTransposePtrs p;
+    memset(&p, 0, sizeof p);
+    for (int32_t z = 0; z < J; ++z) {
+        p.val[z] = mats[z]->val;
+        p.x[z] = xs[z];
+        p.y[z] = ys[z];
+    }
+    const int threads = 256;
+    const int64_t want = ((int64_t)A->ncols * 16 + threads - 1) / threads, cap = (int64_t)ctx->num_cu * 64;
+    const dim3 grid((unsigned)(want < 1 ? 1 : (want > cap ? cap : want)), (unsigned)J);
+    if (A->dtype == LSA_F64 && xdtype == LSA_F64)
+        hipLaunchKernelGGL((spmv_transpose_pull_batch_kernel<double, double>), grid, dim3(threads), 0, ctx->stream, A->ncols, conj, T.rp, T.ci, T.src, p);
+    else if (A->dtype == LSA_F64)
+        hipLaunchKernelGGL((spmv_transpose_pull_batch_kernel<double, cplx>), grid, dim3(threads), 0, ctx->stream, A->ncols, conj, T.rp, T.ci, T.src, p);
+    else
+        hipLaunchKernelGGL((spmv_transpose_pull_batch_kernel<cplx, cplx>), grid, dim3(threads), 0, ctx->stream, A->ncols, conj, T.rp, T.ci, T.src, p);
+    return lsa_check_launch(ctx, "spmv_transpose_pull_batch_kernel");
+}
+
 // ---- C-ABI -----------------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -546,6 +615,25 @@ int lsa_spmv_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, const lsa_vec* 
     LSA_CHECK(check_spmv_args(ctx, A, x, y, "lsa_spmv_transpose"));
     if (y->n != A->ncols) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_transpose: y has the wrong length");
     return k_spmv_transpose(ctx, A, conj, x->dtype, x->d, y->d);
+}
+
+int lsa_spmv_transpose_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* A, int conj, const lsa_vec* const* x, lsa_vec* const* y) {
+    if (!ctx || !A || !x || !y) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_transpose_batch: null argument");
+    if (J < 1 || J > kSpmvBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_transpose_batch: J = %d outside [1, %d]", J, kSpmvBatchMax);
+    const void* xd[kSpmvBatchMax];
+    void* yd[kSpmvBatchMax];
+    for (int32_t z = 0; z < J; ++z) {
+        if (!A[z] || !x[z] || !y[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_transpose_batch: null argument (problem %d)", z);
+        LSA_CHECK(check_spmv_args(ctx, A[z], x[z], y[z], "lsa_spmv_transpose_batch"));
+        if (y[z]->n != A[z]->ncols) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_transpose_batch: y has the wrong length (problem %d)", z);
+        if (x[z]->dtype != x[0]->dtype) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_transpose_batch: the vectors of problem %d have another dtype than those of problem 0", z);
+        for (int32_t w = 0; w < z; ++w)
+            if (y[z]->d == y[w]->d || y[z]->d == x[w]->d || y[w]->d == x[z]->d)
+                return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_transpose_batch: problems %d and %d share an output", w, z);
+        xd[z] = x[z]->d;
+        yd[z] = y[z]->d;
+    }
+    return k_spmv_transpose_batch(ctx, J, A, conj, x[0]->dtype, xd, yd);
 }
 
 int lsa_spmv_info(lsa_ctx* ctx, const lsa_mat* A, int xdtype, char* kernel, int32_t kernel_len, int64_t* bytes_moved) {

@@ -12,8 +12,9 @@
 //
 // One step j of kind 0 (rhs = Q_q v_j is left by the previous step's tail):
 //     b = rhs + 0 i                             sf_widen_kernel: one complex right-hand side for all nodes
-//     for every node k:  z_k = C_k^-H b         the transposed, conjugated sweeps (ndlu_solve_adjoint_dev), node by node
-//                        ca_k = C_k^H z_k       k_spmv_transpose, for the check
+//     for every node k:  z_k = C_k^-H b         the transposed, conjugated sweeps (ndlu_solve_adjoint_dev), node by node, or the
+//                                               batched ones in groups of <= 16 sets (set_batch_adjoint)
+//                        ca_k = C_k^H z_k       k_spmv_transpose, for the check (set_batch_adjoint: k_spmv_transpose_batch, 16 per launch)
 //     TM = Q_f [z_0 .. z_{N-1}]                 one k_spmm on the block
 //     for every node k:  w_k = C_k^-1 tm_k      ndlu_solve_dev, or the batched sweeps in groups of <= 16 sets (set_batch_forward)
 //     CF[:, k] = C_k w_k for all k              sf_shifted_spmm_kernel: ONE launch, A's and M's values read once for <= 16 columns
@@ -26,7 +27,8 @@
 // lanczos.hip stay as they are: the real basis' one check slot gets the pair (rhs, rhs), which cannot fail.
 //
 // Every sum runs in a fixed order and there are no floating-point atomics: two runs give the same bits, and so do the batched and
-// the node-by-node forward solves (each column of lsa_ndlu_solve_batch holds lsa_ndlu_solve's bits).
+// the node-by-node solves of either direction (each column of lsa_ndlu_solve_batch holds lsa_ndlu_solve's bits, each of
+// lsa_ndlu_solve_batch_adjoint lsa_ndlu_solve_adjoint's, each of k_spmv_transpose_batch k_spmv_transpose's).
 //   sf_shifted_spmm_kernel   the entries of a row strided over the 8 lanes of its row group, each lane adding its entries in order;
 //                            then the xor tree over the 8 lanes (ci_spmm_kernel's order)
 //   sf_sums_kernel           the rows of a chunk (dot_chunks) strided over the 256 threads, the xor tree of the wavefront, the four
@@ -236,10 +238,12 @@ struct lsa_stochastic {
     bool timed = false;              // the events of a queued step have not been read yet
     // refine[dir][k]: node k's solves of that direction (0 forward, 1 adjoint) carry the refinement step; used: what the step being judged was queued with
     std::vector<char> refine[2], used[2];
-    bool force_refine = false, batch_forward = false;
+    bool force_refine = false, batch_forward = false, batch_adjoint = false;
     int64_t solves_adj = 0, solves_fwd = 0, refined_adj = 0, refined_fwd = 0;
+    int64_t adjoint_batches = 0, forward_batches = 0;  // grouped calls of the batched sweeps with more than one set
     int64_t bytes = 0;
     double sec_factor = 0.0, sec_solve = 0.0, sec_product = 0.0, sec_dense = 0.0;
+    double sec_solve_adj = 0.0, sec_product_adj = 0.0;  // the adjoint solves' share of sec_solve, their check products' of sec_product
 };
 
 namespace {
@@ -272,14 +276,15 @@ int sf_times_c(lsa_ctx* ctx, lsa_stochastic* h, int32_t k, bool adjoint, const c
     return adjoint ? k_spmv_transpose(ctx, h->C[(size_t)k], 1, LSA_C128, x, y) : k_spmv(ctx, h->C[(size_t)k], LSA_C128, x, y);
 }
 
-// X[:, k] = C_k^-1 B_k (adjoint: C_k^-H) for all nodes, B_k = B + k ldb (ldb = 0: one right-hand side for all).  Forward solves under
-// set_batch_forward go through the batched sweeps in groups of compatible sets; a node whose solves carry the refinement step
-// runs alone and takes x += C^-1 (b - C x) behind its solve.
+// X[:, k] = C_k^-1 B_k (adjoint: C_k^-H) for all nodes, B_k = B + k ldb (ldb = 0: one right-hand side for all).  Under the
+// direction's switch (set_batch_forward, set_batch_adjoint) the solves go through the batched sweeps of that direction in groups
+// of at most kNdBatchMax compatible sets; a node whose solves carry the refinement step runs alone and takes
+// x += C^-1 (b - C x) behind its solve.
 int sf_solve_all(lsa_ctx* ctx, lsa_stochastic* h, bool adjoint, const cplx* B, int64_t ldb, cplx* X) {
     const int64_t n = h->n;
     const std::vector<char>& ref = h->used[adjoint ? 1 : 0];
     std::vector<char> done((size_t)h->N, 0);
-    if (!adjoint && h->batch_forward) {
+    if (adjoint ? h->batch_adjoint : h->batch_forward) {
         int32_t k = 0;
         while (k < h->N) {
             if (ref[(size_t)k]) {
@@ -299,8 +304,12 @@ int sf_solve_all(lsa_ctx* ctx, lsa_stochastic* h, bool adjoint, const cplx* B, i
                 done[(size_t)q] = 1;
                 ++J;
             }
-            if (J > 1) LSA_CHECK(ndlu_solve_batch_dev(ctx, J, f, LSA_C128, bs, xs));
-            else LSA_CHECK(ndlu_solve_dev(ctx, f[0], LSA_C128, bs[0], xs[0]));
+            if (J > 1) {
+                LSA_CHECK(adjoint ? ndlu_solve_batch_adjoint_dev(ctx, J, f, 1, LSA_C128, bs, xs) : ndlu_solve_batch_dev(ctx, J, f, LSA_C128, bs, xs));
+                ++(adjoint ? h->adjoint_batches : h->forward_batches);
+            } else {
+                LSA_CHECK(adjoint ? ndlu_solve_adjoint_dev(ctx, f[0], 1, LSA_C128, bs[0], xs[0]) : ndlu_solve_dev(ctx, f[0], LSA_C128, bs[0], xs[0]));
+            }
             k = q;
         }
     }
@@ -318,10 +327,25 @@ int sf_solve_all(lsa_ctx* ctx, lsa_stochastic* h, bool adjoint, const cplx* B, i
     return LSA_OK;
 }
 
-// Z[:, k] = C_k X[:, k] for all nodes in one launch, or C_k^H X[:, k] node by node
+// Z[:, k] = C_k X[:, k] for all nodes in one launch, or C_k^H X[:, k] node by node -- under set_batch_adjoint in groups of
+// kNdBatchMax nodes per launch (the C_k are built on A's index arrays: one transposed index serves them all)
 int sf_check_products(lsa_ctx* ctx, lsa_stochastic* h, bool adjoint, const cplx* X, cplx* Z) {
     if (!adjoint) return k_shifted_spmm(ctx, h->A, h->M, h->N, h->zdev, X, Z);
-    for (int32_t k = 0; k < h->N; ++k) LSA_CHECK(sf_times_c(ctx, h, k, true, X + (size_t)k * (size_t)h->n, Z + (size_t)k * (size_t)h->n));
+    const size_t n = (size_t)h->n;
+    if (!h->batch_adjoint) {
+        for (int32_t k = 0; k < h->N; ++k) LSA_CHECK(sf_times_c(ctx, h, k, true, X + (size_t)k * n, Z + (size_t)k * n));
+        return LSA_OK;
+    }
+    for (int32_t k0 = 0; k0 < h->N; k0 += kNdBatchMax) {
+        const int32_t J = std::min<int32_t>(kNdBatchMax, h->N - k0);
+        const void* xs[kNdBatchMax];
+        void* zs[kNdBatchMax];
+        for (int32_t z = 0; z < J; ++z) {
+            xs[z] = X + (size_t)(k0 + z) * n;
+            zs[z] = Z + (size_t)(k0 + z) * n;
+        }
+        LSA_CHECK(k_spmv_transpose_batch(ctx, J, h->C.data() + k0, 1, LSA_C128, xs, zs));
+    }
     return LSA_OK;
 }
 
@@ -377,6 +401,9 @@ int sf_judge(lsa_ctx* ctx, lsa_stochastic* h, const char* who, const char* what,
         (void)hipGetLastError();
         h->sec_solve += 1e-3 * (ms[0] + ms[3]);
         h->sec_product += 1e-3 * (ms[1] + ms[2] + ms[4] + ms[5]);
+        const int a = sf_adjoint(h, 0) ? 0 : 3;  // the adjoint solves are the first or the second ones; their check products follow them
+        h->sec_solve_adj += 1e-3 * ms[a];
+        h->sec_product_adj += 1e-3 * ms[a + 1];
         h->timed = false;
     }
     const int32_t N = h->N;
@@ -642,6 +669,12 @@ int lsa_stochastic_set_batch_forward(lsa_ctx* ctx, lsa_stochastic* h, int on) {
     return LSA_OK;
 }
 
+int lsa_stochastic_set_batch_adjoint(lsa_ctx* ctx, lsa_stochastic* h, int on) {
+    if (!ctx || !h) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_stochastic_set_batch_adjoint: null argument");
+    h->batch_adjoint = on != 0;
+    return LSA_OK;
+}
+
 int lsa_stochastic_set_refinement(lsa_ctx* ctx, lsa_stochastic* h, int on) {
     if (!ctx || !h) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_stochastic_set_refinement: null argument");
     h->force_refine = on != 0;
@@ -679,6 +712,11 @@ int lsa_stochastic_info(const lsa_stochastic* h, lsa_stochastic_stats* out) {
     out->seconds_product = h->sec_product;
     out->seconds_dense = h->sec_dense;
     out->solver = h->st;
+    out->batch_adjoint = h->batch_adjoint ? 1 : 0;
+    out->adjoint_batches = h->adjoint_batches;
+    out->forward_batches = h->forward_batches;
+    out->seconds_solve_adjoint = h->sec_solve_adj;
+    out->seconds_product_adjoint = h->sec_product_adj;
     return LSA_OK;
 }
 

@@ -3,12 +3,13 @@ that is white in time, the structures that carry it (EOFs) or feed it (stochasti
 variance comes from, on a frequency quadrature (``StochasticForcingSolver``).
 
     python lsa-fw_amd/examples/stochastic_forcing.py [--case S5k] [--modes 4] [--nodes 8 16] [--band 0 1.5] [--scale S]
-                                                     [--kind eofs|optimals] [--discount B] [--response-window X0 X1]
+                                                     [--kind eofs|optimals] [--discount B] [--response-window X0 X1] [--batch-adjoint]
 
 The numbers are those of the QUADRATURE operator ``(1 / pi) sum_k w_k Re W(i omega_k)``, not of the integral: give several ``--nodes`` and
 compare.  The wake has sharp resonances (the least stable eigenvalue sits at 0.018 + 0.738j), so the leading variances move a lot
 between 8 and 16 nodes while their sum over all modes does not; ``--discount B`` evaluates at ``B + i omega`` and smooths the integrand.
-``--scale S`` integrates over the whole axis through ``omega = S tan(theta)`` instead of the band.  Needs an AMD GPU (there is no CPU
+``--scale S`` integrates over the whole axis through ``omega = S tan(theta)`` instead of the band.  ``--batch-adjoint`` sends the adjoint
+solves of a step through the batched transposed sweeps (the same numbers, bit for bit).  Needs an AMD GPU (there is no CPU
 fallback).
 """
 
@@ -38,6 +39,7 @@ def main() -> None:
     ap.add_argument("--kind", choices=("eofs", "optimals"), default="eofs")
     ap.add_argument("--discount", type=float, default=0.0)
     ap.add_argument("--response-window", type=float, nargs=2, metavar=("X0", "X1"), default=None)
+    ap.add_argument("--batch-adjoint", action="store_true", help="the adjoint solves of a step through the batched transposed sweeps (same bits)")
     args = ap.parse_args()
     es = fem.cylinder_case(args.case)
     window = None
@@ -47,12 +49,12 @@ def main() -> None:
     print(f"{args.case}: n = {es.n}, kind {args.kind}, discount {args.discount}")
     for nodes in args.nodes:
         sf = StochasticForcingSolver(es.A, es.M, StochasticConfig(num_modes=args.modes, ncv=args.ncv, atol=1e-8, nodes=nodes), response_window=window,
-                                     discount=args.discount)
+                                     discount=args.discount, batch_adjoint=args.batch_adjoint)
         res = sf.solve(band=(0.0, np.inf), scale=args.scale, kind=args.kind) if args.scale is not None else sf.solve(band=tuple(args.band), kind=args.kind)
         sf.release()
         st = res.stats
         print(f"nodes = {nodes}: variances " + " ".join(f"{v:.6f}" for v in res.variances) + f"   ({st['applies']} applies, {st['restarts']} restarts, "
-              f"factor {st['seconds_factor']:.3f} s, steps {st['seconds_expand']:.3f} s)")
+              f"{st['adjoint_batches']} batched adjoint sweeps, factor {st['seconds_factor']:.3f} s, steps {st['seconds_expand']:.3f} s)")
         print("    omega      " + "".join(f"mode {j + 1:<9d}" for j in range(len(res.variances))))
         for k, om in enumerate(res.omegas):
             print(f"{om:10.4f}   " + "".join(f"{res.spectrum[j, k]:<14.6f}" for j in range(len(res.variances))))

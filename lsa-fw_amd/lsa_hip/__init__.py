@@ -152,6 +152,11 @@ class lsa_stochastic_stats(ctypes.Structure):
         ("seconds_product", ctypes.c_double),
         ("seconds_dense", ctypes.c_double),
         ("solver", lsa_stats),
+        ("batch_adjoint", ctypes.c_int32),
+        ("adjoint_batches", ctypes.c_int64),
+        ("forward_batches", ctypes.c_int64),
+        ("seconds_solve_adjoint", ctypes.c_double),
+        ("seconds_product_adjoint", ctypes.c_double),
     ]
 
 
@@ -178,6 +183,7 @@ SIGNATURES = {
     "lsa_csr_window": (ctypes.c_int, [_P, _P, _P, _P, _PP]),
     "lsa_spmv": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_spmv_transpose": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P]),
+    "lsa_spmv_transpose_batch": (ctypes.c_int, [_P, _I32, _PP, ctypes.c_int, _PP, _PP]),
     "lsa_spmv_info": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_char_p, _I32, ctypes.POINTER(_I64)]),
     "lsa_spmv_time": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.POINTER(_DBL)]),
     "lsa_ilu_create": (ctypes.c_int, [_P, _P, ctypes.c_int, _DBL, _PP]),
@@ -209,6 +215,7 @@ SIGNATURES = {
     "lsa_ndlu_destroy": (None, [_P]),
     "lsa_ndlu_solve": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_ndlu_solve_batch": (ctypes.c_int, [_P, _I32, _PP, _PP, _PP]),
+    "lsa_ndlu_solve_batch_adjoint": (ctypes.c_int, [_P, _I32, _PP, ctypes.c_int, _PP, _PP]),
     "lsa_ndlu_prepared_memory": (ctypes.c_int, [_P, _P]),
     "lsa_ndlu_solve_adjoint": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P]),
     "lsa_ndlu_solve_time": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.POINTER(_DBL)]),
@@ -290,6 +297,7 @@ SIGNATURES = {
     "lsa_stochastic_set_weights": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_stochastic_set_kind": (ctypes.c_int, [_P, _P, _I32]),
     "lsa_stochastic_set_batch_forward": (ctypes.c_int, [_P, _P, ctypes.c_int]),
+    "lsa_stochastic_set_batch_adjoint": (ctypes.c_int, [_P, _P, ctypes.c_int]),
     "lsa_stochastic_set_refinement": (ctypes.c_int, [_P, _P, ctypes.c_int]),
     "lsa_stochastic_apply": (ctypes.c_int, [_P, _P, _P, _P, _P]),
     "lsa_stochastic_solve": (ctypes.c_int, [_P, _P, ctypes.POINTER(lsa_ks_options), _P, _I32, _P, _P, _P, ctypes.POINTER(lsa_ks_result), _P]),
@@ -600,6 +608,19 @@ class CsrMatrix:
     def rmatvec(self, x: DeviceVector, y: DeviceVector, conj: bool = True) -> None:
         self.ctx.check(self.ctx._lib.lsa_spmv_transpose(self.ctx.handle, self.handle, int(conj), x.handle, y.handle))
 
+    @staticmethod
+    def spmv_transpose_batch(mats: "list[CsrMatrix]", xs: "list[DeviceVector]", ys: "list[DeviceVector]", conj: bool = False) -> None:
+        """``ys[z] = mats[z]^T xs[z]`` (``conj``: ``mats[z]^H xs[z]``) for up to 16 matrices of one pattern and dtype in one launch
+        (``lsa_spmv_transpose_batch``), each result bit-identical to :meth:`rmatvec`."""
+        J = len(mats)
+        if J == 0 or len(xs) != J or len(ys) != J:
+            raise ValueError("spmv_transpose_batch needs as many inputs and outputs as matrices (at least one)")
+        ctx = mats[0].ctx
+        if any(m.ctx is not ctx for m in mats) or any(v.ctx is not ctx for v in list(xs) + list(ys)):
+            raise ValueError("spmv_transpose_batch: the matrices and vectors must live in one context")
+        arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
+        ctx.check(ctx._lib.lsa_spmv_transpose_batch(ctx.handle, J, arr(mats), int(conj), arr(xs), arr(ys)))
+
     def matmat(self, X: DeviceVector, Y: DeviceVector, ncols: int, ldx: int | None = None, ldy: int | None = None) -> None:
         """``Y[:, c] = self @ X[:, c]`` for ``ncols`` columns (``lsa_spmm``).  ``X`` and ``Y`` are column-major complex128 blocks in
         one vector each (column ``c`` at ``c * ld``, ``ld`` defaulting to ``n``).  Two calls give the same bytes; a column need not
@@ -838,9 +859,13 @@ class NdLu:
         self.ctx.check(self.ctx._lib.lsa_ndlu_solve(self.ctx.handle, self.handle, b.handle, x.handle))
 
     @staticmethod
-    def solve_batch(factors: "list[NdLu]", bs: "list[DeviceVector]", xs: "list[DeviceVector]") -> None:
+    def solve_batch(factors: "list[NdLu]", bs: "list[DeviceVector]", xs: "list[DeviceVector]", trans: str = "N") -> None:
         """``xs[z] = C_z^-1 bs[z]`` for up to 16 factorisations of one analysis in one context (``lsa_ndlu_solve_batch``): one
-        launch per tree level and direction for the whole batch, each result bit-identical to :meth:`solve`."""
+        launch per tree level and direction for the whole batch, each result bit-identical to :meth:`solve`.  ``trans="T"`` /
+        ``"H"``: ``C_z^-T`` / ``C_z^-H`` through the batched transposed sweeps (``lsa_ndlu_solve_batch_adjoint``), each result
+        bit-identical to :meth:`solve_adjoint`."""
+        if trans not in _TRANS:
+            raise ValueError(f"trans must be 'N', 'T' or 'H', got {trans!r}")
         J = len(factors)
         if J == 0 or len(bs) != J or len(xs) != J:
             raise ValueError("solve_batch needs as many right-hand sides and outputs as factorisations (at least one)")
@@ -850,7 +875,10 @@ class NdLu:
         if any(f.ctx is not ctx for f in factors) or any(v.ctx is not ctx for v in list(bs) + list(xs)):
             raise ValueError("solve_batch: the factorisations and vectors must live in one context")
         arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
-        ctx.check(ctx._lib.lsa_ndlu_solve_batch(ctx.handle, J, arr(factors), arr(bs), arr(xs)))
+        if trans == "N":
+            ctx.check(ctx._lib.lsa_ndlu_solve_batch(ctx.handle, J, arr(factors), arr(bs), arr(xs)))
+        else:
+            ctx.check(ctx._lib.lsa_ndlu_solve_batch_adjoint(ctx.handle, J, arr(factors), int(trans == "H"), arr(bs), arr(xs)))
 
     def solve_adjoint(self, b: DeviceVector, x: DeviceVector, conj: bool = True) -> None:
         """x = C^-H b (``conj``) or C^-T b on the same factors."""
@@ -1424,6 +1452,11 @@ class StochasticBasis:
     def set_batch_forward(self, on: bool) -> None:
         """``True``: the forward solves of a step run through the batched sweeps of ``lsa_ndlu_solve_batch``; same bits."""
         self.ctx.check(self.ctx._lib.lsa_stochastic_set_batch_forward(self.ctx.handle, self.handle, int(bool(on))))
+
+    def set_batch_adjoint(self, on: bool) -> None:
+        """``True``: the adjoint solves of a step run through the batched transposed sweeps of ``lsa_ndlu_solve_batch_adjoint`` and
+        their check products through ``lsa_spmv_transpose_batch``; same bits."""
+        self.ctx.check(self.ctx._lib.lsa_stochastic_set_batch_adjoint(self.ctx.handle, self.handle, int(bool(on))))
 
     def set_refinement(self, on: bool) -> None:
         """``True``: every solve carries the refinement step from the start (for tests)."""

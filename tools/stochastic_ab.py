@@ -6,6 +6,9 @@
 analysis, the real thick-restart Lanczos iteration on ``S = (1 / pi) sum_k w_k Re W(i omega_k)`` with all ``2 nodes`` inner solves of a step,
 their checks and the orthogonalisation on the device, one read-back per step; then one apply per mode for the spectrum.
 ``library_batch`` (a'): the same with ``batch_forward=True`` (the forward solves of a step through the batched sweeps; same bits).
+``library_batch_both`` (a''): ``batch_forward=True, batch_adjoint=True`` (the adjoint solves through the batched transposed sweeps and
+their check products 16 per launch as well; same bits).  Its figures are ratios to ``library_batch`` OF THE SAME RUN: the per-step
+time, and the adjoint sweeps and adjoint check products of all steps and applies from the handle's HIP events.
 ``host`` (b): ARPACK on a ``LinearOperator`` whose product calls ``nodes`` kept ``iKSP`` factorisations on the same device
 (``solve_many(adjoint=True)``, a product with ``M`` in scipy, ``solve``, per node: two host round trips per node and product) and sums
 the real parts on the host.  ``S`` is self-adjoint in the ``M``-inner product, not in the Euclidean one ARPACK's symmetric driver
@@ -43,16 +46,19 @@ def problem(case: str):
     return fem.cube_case(case) if case.startswith("C") else fem.cylinder_case(case)
 
 
-def library(es, nodes: int, batch: bool = False) -> dict:
+def library(es, nodes: int, batch: bool = False, batch_adjoint: bool = False) -> dict:
     from Solver.stochastic import StochasticConfig, StochasticForcingSolver
 
     t0 = time.perf_counter()
-    sf = StochasticForcingSolver(es.A, es.M, StochasticConfig(num_modes=MODES, ncv=NCV, atol=TOL, nodes=nodes), batch_forward=batch)
+    sf = StochasticForcingSolver(es.A, es.M, StochasticConfig(num_modes=MODES, ncv=NCV, atol=TOL, nodes=nodes), batch_forward=batch,
+                                 batch_adjoint=batch_adjoint)
     res = sf.solve(band=BAND)
     sf.release()
     st = res.stats
     return {"variances": res.variances, "seconds": time.perf_counter() - t0, "seconds_factor": st["seconds_factor"],
             "seconds_steps": st["seconds_expand"], "seconds_sweeps_device": st["seconds_solve"], "seconds_products_device": st["seconds_product"],
+            "seconds_adjoint_sweeps_device": st["seconds_solve_adjoint"], "seconds_adjoint_products_device": st["seconds_product_adjoint"],
+            "adjoint_batches": st["adjoint_batches"], "forward_batches": st["forward_batches"],
             "seconds_host_dense": st["seconds_dense"], "applies": st["applies"], "restarts": st["restarts"], "refinements": st["refinements"],
             "seconds_per_step": st["seconds_expand"] / max(st["applies"], 1), "bytes": st["stochastic_bytes"]}
 
@@ -108,10 +114,11 @@ def main(argv=None) -> None:
     ap.add_argument("--cases", nargs="+", default=["S30k", "C160k"])
     ap.add_argument("--nodes", nargs="+", type=int, default=[8, 16])
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--no-host", action="store_true", help="the two library settings alone")
+    ap.add_argument("--no-host", action="store_true", help="the library settings alone")
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "stochastic_ab.json")
     args = ap.parse_args(argv)
-    settings = {"library": lambda es, N: library(es, N), "library_batch": lambda es, N: library(es, N, True)}
+    settings = {"library": lambda es, N: library(es, N), "library_batch": lambda es, N: library(es, N, True),
+                "library_batch_both": lambda es, N: library(es, N, True, True)}
     if not args.no_host:
         settings["host"] = host
     result = {"config": {"num_modes": MODES, "ncv": NCV, "tol": TOL, "band": BAND, "reps": args.reps}, "cases": []}
@@ -125,12 +132,20 @@ def main(argv=None) -> None:
                     runs[name].append(fn(es, N))
             a = warm["library"]["variances"]
             entry = {"case": case, "n": int(es.A.shape[0]), "nodes": N, "variances": a.tolist(),
-                     "batch_bit_identical": bool(np.array_equal(a, warm["library_batch"]["variances"]))}
+                     "batch_bit_identical": bool(np.array_equal(a, warm["library_batch"]["variances"])),
+                     "batch_both_bit_identical": bool(np.array_equal(a, warm["library_batch_both"]["variances"]))}
             for name in settings:
                 entry[name] = {"seconds": spread([r["seconds"] for r in runs[name]]), "last": plain(runs[name][-1])}
                 if name != "host":
                     entry[name]["seconds_per_step"] = spread([r["seconds_per_step"] for r in runs[name]])
+                    for key in ("seconds_adjoint_sweeps_device", "seconds_adjoint_products_device"):
+                        entry[name][key] = spread([r[key] for r in runs[name]])
             entry["batch_per_step_ratio_median"] = entry["library_batch"]["seconds_per_step"]["median"] / entry["library"]["seconds_per_step"]["median"]
+            both, base = entry["library_batch_both"], entry["library_batch"]  # (same steps on both sides: the bits are the same)
+            entry["batch_both_ratios_to_library_batch_median"] = {
+                "per_step": both["seconds_per_step"]["median"] / base["seconds_per_step"]["median"],
+                "adjoint_sweeps": both["seconds_adjoint_sweeps_device"]["median"] / base["seconds_adjoint_sweeps_device"]["median"],
+                "adjoint_products": both["seconds_adjoint_products_device"]["median"] / base["seconds_adjoint_products_device"]["median"]}
             if "host" in settings:
                 b = warm["host"]["variances"]
                 entry["variance_difference"] = float(np.abs(a - b).max() / a[0]) if a.shape == b.shape else None
