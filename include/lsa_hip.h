@@ -270,6 +270,20 @@ int lsa_ndlu_set_multi_transposed(lsa_ctx *ctx, lsa_ndlu *f, int on);
  * pass (1: column by column, 0: none yet), extra_bytes = device memory of the per-column sweep buffers, launches_per_pass = dependent launches of
  * one pass (those of one lsa_ndlu_solve) */
 int lsa_ndlu_multi_info(const lsa_ndlu *f, int32_t *width, int64_t *extra_bytes, int32_t *launches_per_pass);
+/* X[z][:, q] = C_z^-1 B[z][:, q], z < J <= 16, q < nrhs: the block solve of lsa_ndlu_solve_multi on J factorisations of one analysis,
+ * every launch of the sweeps carrying all columns of a pass for all J of them.  The rules of lsa_ndlu_solve_batch hold for the
+ * factorisations (one analysis, one rank, no distributed node, vectors of one dtype) and those of lsa_ndlu_solve_multi for the
+ * blocks, which share ldb and ldx (ld >= n, each vector at least ld (nrhs - 1) + n long, complex factors need complex vectors).
+ * B[z] == X[z] with ldb == ldx solves in place; several sets may read ONE B (the region eigensolver's case); two sets sharing a
+ * factorisation or an X, or any other overlap: LSA_ERR_ARG.  trans must be 0: the transposed form is not built (LSA_ERR_ARG).
+ * Column q of set z holds exactly the bits lsa_ndlu_solve(f[z], .) gives for it.  The pass width is the smallest every set has
+ * sweep buffers for; a last single column goes through the sweeps of lsa_ndlu_solve_batch, and nrhs = 1 is that call. */
+int lsa_ndlu_solve_multi_batch(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, int trans, int32_t nrhs, const lsa_vec *const *B, int64_t ldb,
+                               lsa_vec *const *X, int64_t ldx);
+/* `iters` such block solves back to back (every B[z] apart from every X[z]), timed as lsa_ndlu_solve_multi_time; *avg_ms = mean per
+ * block solve of all J sets */
+int lsa_ndlu_solve_multi_batch_time(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, int trans, int32_t nrhs, const lsa_vec *const *B,
+                                    int64_t ldb, lsa_vec *const *X, int64_t ldx, int iters, double *avg_ms);
 /* Inertia (numbers of negative, zero, positive eigenvalues) of a REAL SYMMETRIC C from its factorisation: what SLEPc's spectrum
  * slicing takes from the symmetric-indefinite factorisation behind EPS.setInterval / EPS_ALL (Solver/utils.py:248-254: the
  * number of eigenvalues of a definite pencil below sigma is the number of negative eigenvalues of A - sigma M).  Sum over the
@@ -689,6 +703,22 @@ int lsa_contour_set_row_permutation(lsa_ctx *ctx, lsa_contour *h, const int32_t 
 int lsa_contour_solve(lsa_ctx *ctx, lsa_contour *h, double tol, int32_t max_it, const void *Y0_host, int32_t max_out, void *lam_out,
                       void *X_out, double *res_out, lsa_contour_result *result);
 int lsa_contour_info(const lsa_contour *h, lsa_contour_stats *out);
+/* on != 0: an iteration solves the block B = M Y on the nodes in lockstep -- the nodes that do not carry the refinement step in runs
+ * of at most 16 factor sets of one analysis, each run one lsa_ndlu_solve_multi_batch from the shared B -- and then checks and
+ * accumulates node by node in node order as before.  A node that carries the refinement step, or has a column that misses ksp_rtol,
+ * goes through the node-by-node solve (which solves again to the same bits, then refines), so results, verdicts, counters and
+ * error texts are those of the default, byte for byte.  Needs keep_factors (LSA_ERR_ARG without) and one n x subspace solution
+ * block per node: nodes * n * subspace * 16 bytes, counted into lsa_contour_stats.bytes (LSA_ERR_OOM with the bytes needed and free
+ * where they do not fit; the switch then stays off).  on = 0 releases the blocks.  Off by default. */
+int lsa_contour_set_batch_nodes(lsa_ctx *ctx, lsa_contour *h, int on);
+typedef struct {
+    int32_t enabled;           /* 1: lsa_contour_set_batch_nodes is on                                                     */
+    int32_t pad0;
+    int64_t groups;            /* batched groups launched: multi-column passes of lsa_ndlu_solve_multi_batch, per run of nodes */
+    int64_t batched_columns;   /* column solves (node x column) done in those                                              */
+    int64_t serial_columns;    /* column solves done node by node (repeated ones of a fall-back included)                  */
+} lsa_contour_batch_stats;
+int lsa_contour_batch_info(const lsa_contour *h, lsa_contour_batch_stats *out);
 
 /* ---- stochastic forcing: EOFs and stochastic optimals of M q' = A q + f on a frequency quadrature ----------------------------------
  * Under forcing that is white in time with spatial covariance weight Q_f, the response covariance of a stable (A, M) is

@@ -99,6 +99,7 @@ class RegionConfig:
     atol: float = 1e-10  # residual ||A x - lam M x|| / (||A x|| + |lam| ||M x||) of every Ritz pair inside
     max_it: int = 20  # iterations allowed
     keep_factors: bool | None = None  # all factor sets alive / one refactorised per node and iteration / None: by the free memory
+    batch_nodes: bool = False  # solve an iteration's block on all nodes in lockstep (kept factor sets, one more block per node); same bytes
 
 
 @dataclass
@@ -124,6 +125,10 @@ def _check_config(cfg: RegionConfig) -> None:
         raise ValueError(f"max_it = {cfg.max_it!r} must be at least 1")
     if cfg.keep_factors not in (None, True, False):
         raise ValueError(f"keep_factors = {cfg.keep_factors!r} must be True, False or None")
+    if not isinstance(cfg.batch_nodes, (bool, np.bool_)):
+        raise ValueError(f"batch_nodes = {cfg.batch_nodes!r} must be True or False")
+    if cfg.batch_nodes and cfg.keep_factors is False:
+        raise ValueError("batch_nodes = True needs the factor sets of all nodes alive: keep_factors = False refactorises one set node by node")
 
 
 class RegionEigenSolver:
@@ -177,11 +182,13 @@ class RegionEigenSolver:
         return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
 
     def _keep_factors(self, ctx) -> bool:
-        """``cfg.keep_factors``, or whether ``nodes`` factor sets and the blocks fit 0.8 of the free device memory."""
+        """``cfg.keep_factors``, or whether ``nodes`` factor sets and the blocks (six, and one more per node under ``batch_nodes``)
+        fit 0.8 of the free device memory."""
         if self._cfg.keep_factors is not None:
             return bool(self._cfg.keep_factors)
+        blocks = 6 + (self._cfg.nodes if self._cfg.batch_nodes else 0)
         try:
-            need = self._cfg.nodes * ctx.prepared_lu_bytes() + 6 * 16 * self._n * self._cfg.subspace
+            need = self._cfg.nodes * ctx.prepared_lu_bytes() + blocks * 16 * self._n * self._cfg.subspace
         except ValueError:  # (no analysis parked in the context: nothing to size by)
             return False
         return need <= 0.8 * ctx.mem_info()[0]
@@ -208,13 +215,18 @@ class RegionEigenSolver:
             raise NotImplementedError("The region eigensolver needs the exact LU")
         ctx, perm = prep["ctx"], prep["perm"]
         keep = self._keep_factors(ctx)
+        batch = bool(cfg.batch_nodes) and keep
+        if cfg.batch_nodes and not batch:
+            logger.warning("Region: batch_nodes is set, but %d factor sets and %d solution blocks do not fit the free device memory: the factors "
+                           "are not kept and the nodes are solved one by one", cfg.nodes, cfg.nodes)
         cs = None
         try:
             cs = lsa_hip.ContourSolver(ctx, prep["dA"], prep["dM"], cfg.nodes, ell.centre, ell.rx, ell.ry, cfg.subspace, keep_factors=keep,
-                                       ksp_rtol=self._ksp_rtol)
+                                       ksp_rtol=self._ksp_rtol, batch_nodes=batch)
             cs.set_row_permutation(perm)
             out = cs.solve(cfg.atol, cfg.max_it, np.asfortranarray(Y0[perm]))
             info = cs.info()
+            binfo = cs.batch_info()
         finally:
             del cs  # (the handle goes before the matrices it borrows)
         lam, X, res = out["eigenvalues"], out["eigenvectors"], out["residuals"]
@@ -233,7 +245,8 @@ class RegionEigenSolver:
                  "max_rel_res": out["worst_rel_res"], "factors_kept": info["kept"], "nodes": info["nodes"],
                  "contour_bytes": info["bytes"], "analysis_reused": bool(st["analysis_reused"]), "seconds_factor": info["seconds_factor"],
                  "seconds_solve": info["seconds_solve"], "seconds_product": info["seconds_product"], "seconds_gram": info["seconds_gram"],
-                 "seconds_dense": info["seconds_dense"], "seconds_total": time.time() - started}
+                 "seconds_dense": info["seconds_dense"], "seconds_total": time.time() - started, "batch_nodes": binfo["enabled"],
+                 "batched_groups": binfo["groups"], "batched_columns": binfo["batched_columns"]}
         return RegionResult(lam[sel], np.asfortranarray(X[:, sel]), res[sel], int(np.count_nonzero(sel)), bool(out["complete"]),
                             float(out["estimate"]), int(out["iterations"]), stats)
 

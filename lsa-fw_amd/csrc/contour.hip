@@ -1,7 +1,8 @@
 // Region eigensolver: all eigenvalues of A x = lambda M x inside an ellipse, with a statement of completeness, by a contour-integral
 // (FEAST-type) subspace iteration on an n x L complex128 block Y (column-major):
 //     B = M Y                                                  ci_spmm_kernel
-//     for every node z_k of the contour: X = C_k^-1 B on the nested-dissection LU of C_k = A - z_k M (ndlu_solve_multi_dev), each
+//     for every node z_k of the contour: X = C_k^-1 B on the nested-dissection LU of C_k = A - z_k M (ndlu_solve_multi_dev; under
+//         lsa_contour_set_batch_nodes all nodes' X_k first, in lockstep: ndlu_solve_multi_batch_dev), each
 //         column checked (R = C_k X by ci_spmm_kernel, the three sums by ci_residual_kernel), then Q (+)= -w_k X
 //                                                              ci_accumulate_kernel
 //     U = orth(Q) through the Gram matrix, twice               ci_gram_kernel + host Hermitian eigen-decomposition + k_basis_gemm
@@ -352,6 +353,10 @@ struct lsa_contour {
     cplx *qdev = nullptr, *lamdev = nullptr;  // L x L coefficients of k_basis_gemm, L Ritz values
     double *sums = nullptr, *imag2 = nullptr;  // 3 L column sums; what k_columns_canonical reports (not read)
     int32_t* row_perm = nullptr;
+    // lsa_contour_set_batch_nodes: one n x L solution block per node (node k at XN + k n L), and what the lockstep solves did
+    bool batch_nodes = false;
+    cplx* XN = nullptr;
+    int64_t batch_groups = 0, batch_columns = 0, serial_columns = 0;
     lsa_stats st{};
     int64_t bytes = 0;
     double sec_factor = 0.0, sec_solve = 0.0, sec_product = 0.0, sec_gram = 0.0, sec_dense = 0.0;
@@ -365,7 +370,7 @@ void ct_free(lsa_contour* h) {
     for (lsa_mat* c : h->C)
         if (c) lsa_mat_destroy(c);
     for (void* p : {(void*)h->Y, (void*)h->B, (void*)h->X, (void*)h->Q, (void*)h->W1, (void*)h->W2, (void*)h->qdev, (void*)h->lamdev, (void*)h->sums,
-                    (void*)h->imag2, (void*)h->row_perm})
+                    (void*)h->imag2, (void*)h->row_perm, (void*)h->XN})
         if (p) (void)hipFree(p);
     delete h;
 }
@@ -423,6 +428,16 @@ int ct_factors(lsa_ctx* ctx, lsa_contour* h, int32_t k, lsa_ndlu** f) {
     return LSA_OK;
 }
 
+// the accepted columns of a node's block solve into the counters (s: the three sums per column of ct_column_sums)
+void ct_book_columns(lsa_contour* h, int32_t cols, const double* s, bool refined, double* worst) {
+    for (int32_t j = 0; j < cols; ++j) {
+        const double res = std::sqrt(s[3 * (size_t)j]), bnorm = std::sqrt(s[3 * (size_t)j + 1]);
+        if (res > h->ksp_rtol * bnorm) ++h->st.backward_accepted;
+        stats_book_direct_solve(&h->st, 1, refined, res, bnorm);
+        if (bnorm > 0.0) *worst = std::max(*worst, res / bnorm);
+    }
+}
+
 // X = C_k^-1 B for cols columns, every column judged by the rule of lsa_lanczos_extend: within ksp_rtol, else one refinement step (and
 // every later block solve of this node carries it), else a backward error within 1e-12 ||C_k||_F ||x||, else LSA_ERR_DIVERGED
 int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, double* worst) {
@@ -466,14 +481,65 @@ int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, double
             h->refine[(size_t)k] = 1;
             continue;
         }
-        for (int32_t j = 0; j < cols; ++j) {
-            const double res = std::sqrt(s[3 * (size_t)j]), bnorm = std::sqrt(s[3 * (size_t)j + 1]);
-            if (res > h->ksp_rtol * bnorm) ++h->st.backward_accepted;
-            stats_book_direct_solve(&h->st, 1, refined, res, bnorm);
-            if (bnorm > 0.0) *worst = std::max(*worst, res / bnorm);
-        }
+        ct_book_columns(h, cols, s.data(), refined, worst);
         break;
     }
+    h->sec_solve += now_s() - t0;
+    if (h->batch_nodes) h->serial_columns += cols;
+    return rc;
+}
+
+// lsa_contour_set_batch_nodes: X_k = C_k^-1 B for every node that does not carry the refinement step, into the nodes' own blocks
+// -- runs of at most kNdBatchMax compatible factor sets (the grouping of sf_solve_all, stochastic.hip), each run one block solve on
+// all its sets from the shared B.  solved[k] = 1: X_k is there, with the bits ct_block_solve's first solve gives.
+int ct_batch_solve(lsa_ctx* ctx, lsa_contour* h, int32_t cols, std::vector<char>& solved) {
+    const int64_t n = h->n;
+    const double t0 = now_s();
+    int32_t k = 0;
+    int rc = LSA_OK;
+    while (k < h->N && rc == LSA_OK) {
+        if (h->refine[(size_t)k]) {
+            ++k;
+            continue;
+        }
+        lsa_ndlu* f[kNdBatchMax];
+        const void* bs[kNdBatchMax];
+        void* xs[kNdBatchMax];
+        int32_t J = 0, q = k;
+        for (; q < h->N && J < kNdBatchMax; ++q) {
+            if (h->refine[(size_t)q]) continue;
+            if (J > 0 && !nd_batch_compatible(f[0], h->F[(size_t)q])) break;
+            f[J] = h->F[(size_t)q];
+            bs[J] = h->B;
+            xs[J] = h->XN + (size_t)q * (size_t)n * (size_t)h->L;
+            solved[(size_t)q] = 1;
+            ++J;
+        }
+        if (cols > 1) {
+            rc = ndlu_solve_multi_batch_dev(ctx, J, f, LSA_C128, cols, bs, n, xs, n);
+            h->batch_groups += f[0]->multi_passes;
+        } else {
+            rc = ndlu_solve_batch_dev(ctx, J, f, LSA_C128, bs, xs);
+        }
+        h->batch_columns += (int64_t)J * cols;
+        k = q;
+    }
+    h->sec_solve += now_s() - t0;
+    return rc;
+}
+
+// the check of a node's batched block: the product and the column sums of ct_block_solve on X_k.  *ok = 0: a column misses ksp_rtol
+// (or is not finite) -- nothing is booked, and ct_block_solve takes the node; else the columns are booked as its unrefined solves are.
+int ct_batch_check(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, const cplx* Xk, double* worst, bool* ok) {
+    const int64_t n = h->n;
+    const double t0 = now_s();
+    std::vector<double> s((size_t)3 * cols);
+    int rc = k_spmm(ctx, h->C[(size_t)k], cols, Xk, n, h->W1, n);
+    if (rc == LSA_OK) rc = ct_column_sums(ctx, h, cols, h->B, h->W1, Xk, nullptr, s.data());
+    *ok = rc == LSA_OK;
+    for (int32_t j = 0; j < cols && *ok; ++j)
+        if (!(std::sqrt(s[3 * (size_t)j]) <= h->ksp_rtol * std::sqrt(s[3 * (size_t)j + 1]))) *ok = false;
+    if (*ok) ct_book_columns(h, cols, s.data(), false, worst);
     h->sec_solve += now_s() - t0;
     return rc;
 }
@@ -691,6 +757,40 @@ int lsa_contour_info(const lsa_contour* h, lsa_contour_stats* out) {
     return LSA_OK;
 }
 
+int lsa_contour_set_batch_nodes(lsa_ctx* ctx, lsa_contour* h, int on) {
+    if (!ctx || !h) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_set_batch_nodes: null argument");
+    if (on && !h->keep) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_set_batch_nodes: the handle was made with keep_factors = 0: solving the nodes in lockstep needs all their factor sets alive");
+    const size_t need = (size_t)h->N * (size_t)h->n * (size_t)h->L * sizeof(cplx);
+    if (on && !h->XN) {
+        if (hipMalloc((void**)&h->XN, need) != hipSuccess) {
+            (void)hipGetLastError();
+            h->XN = nullptr;
+            size_t free_b = 0, total_b = 0;
+            (void)hipMemGetInfo(&free_b, &total_b);
+            return lsa_set_error(ctx, LSA_ERR_OOM, "lsa_contour_set_batch_nodes: %d solution blocks of %lld x %d need %.0f bytes, %.0f bytes of device memory are free", h->N,
+                                 (long long)h->n, h->L, (double)need, (double)free_b);
+        }
+        h->bytes += (int64_t)need;
+    } else if (!on && h->XN) {
+        LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipFree(h->XN);
+        h->XN = nullptr;
+        h->bytes -= (int64_t)need;
+    }
+    h->batch_nodes = on != 0;
+    return LSA_OK;
+}
+
+int lsa_contour_batch_info(const lsa_contour* h, lsa_contour_batch_stats* out) {
+    if (!h || !out) return LSA_ERR_ARG;
+    out->enabled = h->batch_nodes ? 1 : 0;
+    out->pad0 = 0;
+    out->groups = h->batch_groups;
+    out->batched_columns = h->batch_columns;
+    out->serial_columns = h->serial_columns;
+    return LSA_OK;
+}
+
 int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, const void* Y0_host, int32_t max_out, void* lam_out, void* X_out,
                       double* res_out, lsa_contour_result* result) {
     if (!ctx || !h || !Y0_host || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_solve: null argument");
@@ -715,9 +815,20 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
         LSA_CHECK(k_spmm(ctx, h->M, cols, h->Y, n, h->B, n));
         h->st.spmv_calls += cols;
         h->sec_product += now_s() - t0;
+        std::vector<char> solved((size_t)h->N, 0);
+        if (h->batch_nodes) LSA_CHECK(ct_batch_solve(ctx, h, cols, solved));
         for (int32_t k = 0; k < h->N; ++k) {
-            LSA_CHECK(ct_block_solve(ctx, h, k, cols, &worst));
-            LSA_CHECK(ct_accumulate(ctx, n, cols, -h->w[(size_t)k], h->X, k == 0 ? 0.0 : 1.0, h->Q));
+            const cplx* Xk = h->X;
+            bool ok = false;
+            if (solved[(size_t)k]) {
+                Xk = h->XN + (size_t)k * (size_t)n * (size_t)L;
+                LSA_CHECK(ct_batch_check(ctx, h, k, cols, Xk, &worst, &ok));
+            }
+            if (!ok) {  // the default path; after a batched solve that missed: the same solve again, then its refinement step
+                LSA_CHECK(ct_block_solve(ctx, h, k, cols, &worst));
+                Xk = h->X;
+            }
+            LSA_CHECK(ct_accumulate(ctx, n, cols, -h->w[(size_t)k], Xk, k == 0 ? 0.0 : 1.0, h->Q));
         }
         if (it == 0) {  // the stochastic estimate of the count inside: Re sum_j y_j^H q_j / L
             std::vector<ci_z> G((size_t)cols * cols);

@@ -35,7 +35,7 @@ namespace {
 void nd_free(lsa_ndlu* f) {
     if (!f) return;
     ndlu_multi_free(f);
-    for (void* p : {f->d_top, (void*)f->d_top_icmap, (void*)f->d_top_jobs, (void*)f->d_top_tiles})
+    for (void* p : {f->d_top, (void*)f->d_top_rec, (void*)f->d_top_icmap, (void*)f->d_top_jobs, (void*)f->d_top_tiles})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)f->d_lnodes_bwd, (void*)f->d_dist_nodes, (void*)f->d_child_ptr, (void*)f->d_child_idx, f->d_xstage, f->d_xg, (void*)f->d_tgoff, f->d_tg})
         if (p) (void)hipFree(p);
@@ -127,6 +127,7 @@ int nd_setup_top(lsa_ctx* ctx, lsa_ndlu* f, const std::vector<NdNodeDev>& nodes)
     LSA_CHECK(upload(ctx, jobs, &f->d_top_jobs));
     LSA_CHECK(upload(ctx, tiles, &f->d_top_tiles));
     LSA_HIP_ALLOC(ctx, hipMalloc(&f->d_top, (size_t)(s * s) * esize(f->dtype)));
+    LSA_CHECK(upload(ctx, std::vector<NdTop>(1, tp), &f->d_top_rec));
     f->top = tp;
     f->top_level = lr;
     f->top_replaced_entries = replaced;
@@ -951,6 +952,76 @@ int lsa_ndlu_solve_multi_time(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs
     LSA_CHECK(nd_multi_run(ctx, f, trans, nrhs, B, ldb, X, ldx));  // (the first call makes the per-column buffers)
     LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     for (int i = 0; i < iters; ++i) LSA_CHECK(nd_multi_run(ctx, f, trans, nrhs, B, ldb, X, ldx));
+    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0.f;
+    LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    *avg_ms = (double)ms / iters;
+    return LSA_OK;
+}
+
+// the rules of a block solve on J factor sets: those of nd_batch_check for the sets, of nd_multi_check for every set's blocks, and
+// between sets no shared factorisation or X and no overlap but ONE B read by several; the device pointers
+static int nd_multi_batch_check(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int trans, int32_t nrhs, const lsa_vec* const* B, int64_t ldb,
+                                lsa_vec* const* X, int64_t ldx, const void** bd, void** xd) {
+    if (!ctx || !f || !B || !X) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument", who);
+    if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: J = %d outside [1, %d]", who, J, kNdBatchMax);
+    if (trans != 0) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: trans = %d: the transposed form of the block solve on a batch of factor sets is not built", who, trans);
+    for (int32_t z = 0; z < J; ++z) {
+        if (!f[z] || !B[z] || !X[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument (set %d)", who, z);
+        if (!nd_batch_compatible(f[0], f[z])) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: factorisation %d is not of the same analysis as factorisation 0", who, z);
+        if (X[z]->dtype != X[0]->dtype) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the vectors of set %d differ in dtype from those of set 0", who, z);
+        LSA_CHECK(nd_multi_check(ctx, who, f[z], 0, nrhs, B[z], ldb, X[z], ldx));
+    }
+    const size_t es = esize(X[0]->dtype);
+    const int64_t n = f[0]->S.n;
+    const size_t span_b = (size_t)(ldb * (int64_t)(nrhs - 1) + n) * es, span_x = (size_t)(ldx * (int64_t)(nrhs - 1) + n) * es;
+    auto overlap = [](const void* a, size_t na, const void* b, size_t nb) { return (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na; };
+    for (int32_t z = 0; z < J; ++z)
+        for (int32_t y = 0; y < z; ++y) {
+            if (f[y] == f[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: sets %d and %d share a factorisation", who, y, z);
+            if (overlap(X[y]->d, span_x, X[z]->d, span_x)) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: sets %d and %d share an X or their X overlap", who, y, z);
+            if (overlap(X[y]->d, span_x, B[z]->d, span_b) || overlap(B[y]->d, span_b, X[z]->d, span_x))
+                return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the X of one of the sets %d and %d overlaps the B of the other", who, y, z);
+            if (B[y]->d != B[z]->d && overlap(B[y]->d, span_b, B[z]->d, span_b))
+                return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the B of sets %d and %d overlap (several sets may read ONE B)", who, y, z);
+        }
+    for (int32_t z = 0; z < J; ++z) {
+        bd[z] = B[z]->d;
+        xd[z] = X[z]->d;
+    }
+    return LSA_OK;
+}
+
+// the checked block solve on J sets, queued on the stream (one column: the batched solo sweeps)
+static int nd_multi_batch_run(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, int32_t nrhs, const void* const* bd, int64_t ldb, void* const* xd, int64_t ldx) {
+    if (nrhs > 1) return ndlu_solve_multi_batch_dev(ctx, J, f, vdtype, nrhs, bd, ldb, xd, ldx);
+    const void* b1[kNdBatchMax];
+    for (int32_t z = 0; z < J; ++z) b1[z] = bd[z];  // (an aliased entry is replaced by the set's own copy)
+    return ndlu_solve_batch_dev(ctx, J, f, vdtype, b1, xd);
+}
+
+int lsa_ndlu_solve_multi_batch(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int trans, int32_t nrhs, const lsa_vec* const* B, int64_t ldb, lsa_vec* const* X,
+                               int64_t ldx) {
+    const void* bd[kNdBatchMax];
+    void* xd[kNdBatchMax];
+    LSA_CHECK(nd_multi_batch_check(ctx, "lsa_ndlu_solve_multi_batch", J, f, trans, nrhs, B, ldb, X, ldx, bd, xd));
+    LSA_CHECK(nd_multi_batch_run(ctx, J, f, X[0]->dtype, nrhs, bd, ldb, xd, ldx));
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return LSA_OK;
+}
+
+int lsa_ndlu_solve_multi_batch_time(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int trans, int32_t nrhs, const lsa_vec* const* B, int64_t ldb, lsa_vec* const* X,
+                                    int64_t ldx, int iters, double* avg_ms) {
+    if (!avg_ms || iters < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch_time: bad argument");
+    const void* bd[kNdBatchMax];
+    void* xd[kNdBatchMax];
+    LSA_CHECK(nd_multi_batch_check(ctx, "lsa_ndlu_solve_multi_batch_time", J, f, trans, nrhs, B, ldb, X, ldx, bd, xd));
+    for (int32_t z = 0; z < J; ++z)
+        if (bd[z] == xd[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch_time: repeated solves need B and X apart (set %d)", z);
+    LSA_CHECK(nd_multi_batch_run(ctx, J, f, X[0]->dtype, nrhs, bd, ldb, xd, ldx));  // (the first call makes the per-column buffers)
+    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    for (int i = 0; i < iters; ++i) LSA_CHECK(nd_multi_batch_run(ctx, J, f, X[0]->dtype, nrhs, bd, ldb, xd, ldx));
     LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0.f;

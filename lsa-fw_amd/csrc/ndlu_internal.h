@@ -181,6 +181,7 @@ struct lsa_ndlu {
     // the root and its children as one assembled inverse (nd_top_kernel): top.s = 0 where the forest is not eligible
     NdTop top = {};
     int32_t top_level = -1;                    // the root's level; the level below it has no launch of its own
+    NdTop* d_top_rec = nullptr;                // `top` in device memory: a multi-column launch for a batch of sets has no room for it in its arguments
     void* d_top = nullptr;                     // T, top.s^2 scalars of the factor type, assembled by every numeric factorisation
     int32_t* d_top_icmap = nullptr;            // per child of the root, per own row of the root: its position in the child's boundary, or -1
     NdTopJob* d_top_jobs = nullptr;
@@ -195,8 +196,11 @@ struct lsa_ndlu {
         int acc_vbytes = 0;
     };
     std::vector<MultiColumn> multi;
+    void* multi_stage = nullptr;     // the copy of an aliased block's columns for one pass of the forward block solves (counted in multi_bytes)
+    int64_t multi_stage_bytes = 0;
     bool multi_full = false;     // an allocation failed: no further columns are tried
     int64_t multi_bytes = 0;
+    int32_t multi_passes = 0;    // multi-column passes (two columns or more) of the last forward block solve
     int32_t multi_width = 0;     // widest pass of the last multi-column solve (1: column by column; 0: none yet)
     bool multi_transposed = false;  // lsa_ndlu_set_multi_transposed: block solves with trans != 0 run in wide passes too
 };
@@ -223,4 +227,9 @@ int ndlu_solve_batch_adjoint_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, in
 // in passes of up to kNdMultiMax (complex vectors: 4) columns that share every factor load; not synchronised.  One rank, no distributed node.
 int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx);
 // (the transposed block solve, ndlu_solve_multi_adjoint_dev: lsa_internal.h)
+// ... and X[z][:, q] = C_z^-1 B[z][:, q] for J <= kNdBatchMax factorisations that nd_batch_compatible passed, one launch per level and
+// direction for all columns of a pass on all of them, every column with the bits of ndlu_solve_dev; the blocks share ldb and ldx, several
+// sets may read one B, and B[z] == X[z] (with ldb == ldx) is allowed; not synchronised
+int ndlu_solve_multi_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb, void* const* X,
+                               int64_t ldx);
 void ndlu_multi_free(lsa_ndlu* f);

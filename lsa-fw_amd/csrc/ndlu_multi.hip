@@ -6,23 +6,48 @@
 // column q holds exactly the bits lsa_ndlu_solve gives for it.  (A lane's sequence sl, sl + LPR, ... runs on across chunks, so
 // the chunk -- kMCH entries per column, a multiple of 256 -- is free: four complex or eight real columns of kMCH = 256 are 16 KB of LDS.)
 // Columns beyond the first have sweep buffers of their own (lsa_ndlu::multi), made by the first such solve.
+// The same kernels carry the R columns through J <= 16 factor sets of one analysis in one launch (lsa_ndlu_solve_multi_batch: the set
+// is the grid's last dimension, NdMultiPtrs<R, NB>); the one-set solve is their instance of set capacity one.
 // The transposed systems C^-T / C^-H have the same form (nd_sweepT_multi_kernel, ndlu_solve_multi_adjoint_dev): nd_sweepT_kernel with R
 // columns carried through every launch, on the update vectors of the same per-column buffers.
 #include "ndlu_sweep_parts.h"
 
 namespace {
 
-// what a multi-column launch gets: one factor set, R sets of vectors and sweep buffers (by value in the kernel arguments; the
-// column index is a compile-time constant wherever it is used)
+// what a multi-column launch gets per factor set: its factors, the first column of its right-hand sides and solutions, and the
+// sweep buffers of the R columns of the pass (the column index is a compile-time constant wherever it is used)
 template <int R>
-struct NdMultiPtrs {
+struct NdMultiSet {
     const void *lfac, *ufac, *top;
-    const void* rhs[R];
-    void* x[R];
+    const void* rhs0;
+    void* x0;
     void* ubuf[R];
     void* acc[R];
     void* xb[R];
 };
+
+// ... and per launch: NB such records by value in the kernel arguments (the set index picks one: a uniform load from the argument
+// segment) and the two leading dimensions, which all sets share -- column q of a set's right-hand sides is rhs0 + q ldb, of its
+// solutions x0 + q ldx.  One set is the batch of one (NB = 1, the set index a constant: lsa_ndlu_solve_multi); a batch of sets
+// instantiates NB = kNdBatchMax whatever J (lsa_ndlu_solve_multi_batch).  Every set runs the same grid and tiles, so it gets the
+// same bits either way.  A record with pointers to every column's right-hand side and solution (3 + 5 R of them) would not fit
+// the 4 KB of kernel arguments at NB = 16, R = 8; this one (5 + 3 R) is 3712 bytes there.
+template <int R, int NB>
+struct NdMultiPtrs {
+    NdMultiSet<R> set[NB];
+    int64_t ldb, ldx;
+};
+// the widest instance with the largest of the other arguments beside it (nd_fwd_multi_kernel: four table pointers; the merged top
+// of a batch takes its NdTop record through a pointer for this reason -- by value it is 368 bytes more), with room for the 256
+// bytes of hidden arguments the compiler appends
+static_assert(sizeof(NdMultiPtrs<kNdMultiMax, kNdBatchMax>) == (size_t)(5 + 3 * kNdMultiMax) * 8 * kNdBatchMax + 16, "multi-set record layout");
+static_assert(sizeof(NdMultiPtrs<kNdMultiMax, kNdBatchMax>) + 4 * sizeof(void*) + 256 <= 4096, "kernel arguments of a multi-column, multi-set launch");
+
+// the NdTop record as a launch passes it: by value for one set (as nd_top_kernel takes it), through device memory for a batch
+template <int NB>
+using NdTopArg = typename std::conditional<NB == 1, NdTop, const NdTop*>::type;
+__device__ __forceinline__ const NdTop& nd_top_ref(const NdTop& t) { return t; }
+__device__ __forceinline__ const NdTop& nd_top_ref(const NdTop* t) { return *t; }
 
 // acc0[q] += Fa[0:cn] . vs_q, acc1[q] += Fb[0:cn] . vs_q for the R staged columns (vs_q = vs + q * kMCH): the loads and the order
 // of two_row_dot, each factor scalar used R times
@@ -78,13 +103,17 @@ __device__ __forceinline__ void two_row_dot_prefetched_multi(const MT* __restric
 
 // upward sweep, one tree level, R columns: workgroup (x = node of the level, y = tile of 512 / LPR rows of its packed L block);
 // nd_fwd_tile of ndlu_sweeps.hip per column (no distributed node reaches this form)
-template <typename MT, typename VT, int LPR, bool ORDERED, int R>
+template <typename MT, typename VT, int LPR, bool ORDERED, int R, int NB>
 __global__ __launch_bounds__(256) void nd_fwd_multi_kernel(const NdSweepNode* __restrict__ lnodes, const int32_t* __restrict__ idx,
-                                                           const int32_t* __restrict__ gell, const int32_t* __restrict__ cmap, NdMultiPtrs<R> p) {
+                                                           const int32_t* __restrict__ gell, const int32_t* __restrict__ cmap, NdMultiPtrs<R, NB> pp) {
     __shared__ VT vs[R * kMCH];
     const NdSweepNode nd = lnodes[blockIdx.x];
     const int32_t r0 = (int32_t)blockIdx.y * (512 / LPR);
     if (r0 >= nd.orows + nd.brow) return;
+    const NdMultiSet<R>& p = pp.set[blockIdx.z];  // (NB = 1: the grid has one layer; the uniform load of the record, as for a batch)
+    const VT* rhs0 = (const VT*)p.rhs0;
+    VT* x0 = (VT*)p.x0;
+    const int64_t ldb = pp.ldb, ldx = pp.ldx;
     const int32_t m = nd.m, f = nd.f;
     const int32_t mr = nd.orows, floc = mr + nd.brow;
     const int32_t* ix = idx + nd.idx_off;
@@ -131,7 +160,7 @@ __global__ __launch_bounds__(256) void nd_fwd_multi_kernel(const NdSweepNode* __
             const int32_t src = ORDERED ? nd.own0 + c0 + tid : ix[c0 + tid];
 #pragma unroll
             for (int q = 0; q < R; ++q) {
-                const VT v = ((const VT*)p.rhs[q])[src];
+                const VT v = rhs0[q * ldb + src];
                 vs[q * kMCH + tid] = push ? slot_sum((const VT*)p.acc[q] + slot0, nd.nchild, f, c0 + tid, v)
                                           : gather_updates(ge, nd.nchild, f, c0 + tid, (const VT*)p.ubuf[q], v);
             }
@@ -148,7 +177,7 @@ __global__ __launch_bounds__(256) void nd_fwd_multi_kernel(const NdSweepNode* __
     for (int q = 0; q < R; ++q) {
         const VT s0 = lanes_sum<LPR>(acc0[q]), s1 = lanes_sum<LPR>(acc1[q]);
         if (sl == 0) {
-            VT* x = (VT*)p.x[q];
+            VT* x = x0 + q * ldx;
             VT* xb = (VT*)p.xb[q];
             VT* acc = (VT*)p.acc[q];
             VT* ubuf = (VT*)p.ubuf[q];
@@ -173,14 +202,17 @@ __global__ __launch_bounds__(256) void nd_fwd_multi_kernel(const NdSweepNode* __
 }
 
 // downward sweep, one tree level, R columns: nd_bwd_tile per column
-template <typename MT, typename VT, int LPR, bool ORDERED, int R>
+template <typename MT, typename VT, int LPR, bool ORDERED, int R, int NB>
 __global__ __launch_bounds__(256) void nd_bwd_multi_kernel(const NdSweepNode* __restrict__ lnodes, const int32_t* __restrict__ idx,
-                                                           const int32_t* __restrict__ gell, NdMultiPtrs<R> p) {
+                                                           const int32_t* __restrict__ gell, NdMultiPtrs<R, NB> pp) {
     constexpr int ROWS = 512 / LPR;
     __shared__ VT vs[R * kMCH];
     const NdSweepNode nd = lnodes[blockIdx.x];
     const int32_t r0 = (int32_t)blockIdx.y * ROWS, ty = (int32_t)blockIdx.y;
     if (r0 >= nd.m || nd.f == nd.m) return;
+    const NdMultiSet<R>& p = pp.set[blockIdx.z];  // (NB = 1: the grid has one layer; the uniform load of the record, as for a batch)
+    VT* x0 = (VT*)p.x0;
+    const int64_t ldx = pp.ldx;
     const int32_t m = nd.m, f = nd.f, b = f - m;
     const int32_t* ix = idx + nd.idx_off;
     const int32_t* ge = gell + nd.ge_off;
@@ -196,7 +228,7 @@ __global__ __launch_bounds__(256) void nd_bwd_multi_kernel(const NdSweepNode* __
     VT xa[R], xc[R], acc0[R], acc1[R];
 #pragma unroll
     for (int q = 0; q < R; ++q) {
-        const VT* x = (const VT*)p.x[q];
+        const VT* x = x0 + q * ldx;
         xa[q] = x[ia];
         xc[q] = x[ib];
         acc0[q] = acc1[q] = scalar_traits<VT>::zero();
@@ -216,7 +248,7 @@ __global__ __launch_bounds__(256) void nd_bwd_multi_kernel(const NdSweepNode* __
     for (int q = 0; q < R; ++q) {
         const VT s0 = lanes_sum<LPR>(acc0[q]), s1 = lanes_sum<LPR>(acc1[q]);
         if (sl == 0) {
-            VT* x = (VT*)p.x[q];
+            VT* x = x0 + q * ldx;
             VT* xb = (VT*)p.xb[q];
             if (ra < m) {
                 const VT v = s_sub(xa[q], s0);
@@ -248,10 +280,16 @@ __global__ __launch_bounds__(256) void nd_bwd_multi_kernel(const NdSweepNode* __
 }
 
 // the merged top, R columns: nd_top_tile per column (8 rows of T per workgroup, a wave per row pair)
-template <typename MT, typename VT, int R>
-__global__ __launch_bounds__(256) void nd_top_multi_kernel(NdTop tp, const int32_t* __restrict__ icmap, const int32_t* __restrict__ gell, NdMultiPtrs<R> p) {
+template <typename MT, typename VT, int R, int NB>
+__global__ __launch_bounds__(256) void nd_top_multi_kernel(NdTopArg<NB> tpa, const int32_t* __restrict__ icmap, const int32_t* __restrict__ gell,
+                                                           NdMultiPtrs<R, NB> pp) {
     constexpr int LPR = 64;
     __shared__ VT vs[R * kMCH];
+    const NdTop& tp = nd_top_ref(tpa);
+    const NdMultiSet<R>& p = pp.set[blockIdx.y];
+    const VT* rhs0 = (const VT*)p.rhs0;
+    VT* x0 = (VT*)p.x0;
+    const int64_t ldb = pp.ldb, ldx = pp.ldx;
     const int32_t r0 = (int32_t)blockIdx.x * 8;
     const int32_t s = tp.s, K = tp.nchild;
     const NdTopNode& Rt = tp.node[K];
@@ -274,7 +312,7 @@ __global__ __launch_bounds__(256) void nd_top_multi_kernel(NdTop tp, const int32
 #pragma unroll
                 for (int q = 0; q < R; ++q) {
                     const VT* acc = (const VT*)p.acc[q];
-                    VT z = ((const VT*)p.rhs[q])[Rt.own0 + k];
+                    VT z = rhs0[q * ldb + Rt.own0 + k];
                     for (int32_t c = 0; c < K; ++c) {
                         const NdTopNode& nd = tp.node[c];
                         const int32_t pp = icmap[(size_t)c * Rt.m + k];
@@ -289,7 +327,7 @@ __global__ __launch_bounds__(256) void nd_top_multi_kernel(NdTop tp, const int32
                     const int32_t r = j - nd.off;
 #pragma unroll
                     for (int q = 0; q < R; ++q)
-                        vs[q * kMCH + tid] = slot_sum((const VT*)p.acc[q] + nd.acc_off, nd.nchild, nd.f, r, ((const VT*)p.rhs[q])[nd.own0 + r]);
+                        vs[q * kMCH + tid] = slot_sum((const VT*)p.acc[q] + nd.acc_off, nd.nchild, nd.f, r, rhs0[q * ldb + nd.own0 + r]);
                 }
             }
         }
@@ -302,55 +340,68 @@ __global__ __launch_bounds__(256) void nd_top_multi_kernel(NdTop tp, const int32
     for (int q = 0; q < R; ++q) {
         const VT s0 = lanes_sum<LPR>(acc0[q]), s1 = lanes_sum<LPR>(acc1[q]);
         if (sl == 0) {
-            if (ra < s) nd_top_store(tp, ra, s0, icmap, gell, (VT*)p.x[q], (VT*)p.xb[q]);
-            if (rb < s) nd_top_store(tp, rb, s1, icmap, gell, (VT*)p.x[q], (VT*)p.xb[q]);
+            if (ra < s) nd_top_store(tp, ra, s0, icmap, gell, x0 + q * ldx, (VT*)p.xb[q]);
+            if (rb < s) nd_top_store(tp, rb, s1, icmap, gell, x0 + q * ldx, (VT*)p.xb[q]);
         }
     }
 }
 
-// x_q = C^-1 b_q for the R columns of one pass: nd_sweep of ndlu_sweeps.hip for one rank and no distributed node, the same
-// grids, one launch per level and direction for all columns.  Column 0 runs on the factorisation's own sweep buffers, column
-// q > 0 on f->multi[q - 1].
-template <typename MT, typename VT, bool ORDERED, int R>
-int nd_sweep_multi(lsa_ctx* ctx, lsa_ndlu* f, const VT* const* b, VT* const* x) {
+// x_zq = C_z^-1 b_zq for the R columns of one pass on J <= NB factor sets of one analysis: nd_sweep of ndlu_sweeps.hip for one rank
+// and no distributed node, the same grids with the set as their last dimension, one launch per level and direction for all
+// columns of all sets, on the tables of f[0].  Column q of set z is b[z] + q ldb -> x[z] + q ldx; column 0 runs on the
+// factorisation's own sweep buffers, column q > 0 on f[z]->multi[q - 1].
+template <typename MT, typename VT, bool ORDERED, int R, int NB>
+int nd_sweep_multi(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const VT* const* b, int64_t ldb, VT* const* x, int64_t ldx) {
     hipStream_t st = ctx->stream;
-    NdMultiPtrs<R> p;
-    p.lfac = f->d_lfac;
-    p.ufac = f->d_ufac;
-    p.top = f->d_top;
-    const size_t acc_bytes = (size_t)std::max<int64_t>(f->acc_entries, 1) * 16;
-    for (int q = 0; q < R; ++q) {
-        void* acc = q == 0 ? f->d_acc : f->multi[(size_t)q - 1].acc;
-        int& vbytes = q == 0 ? f->acc_vbytes : f->multi[(size_t)q - 1].acc_vbytes;
-        if (vbytes != (int)sizeof(VT)) {  // (the rule of nd_sweep, per copy of the slot rows)
-            LSA_HIP_CHECK(ctx, hipMemsetAsync(acc, 0, acc_bytes, st));
-            vbytes = (int)sizeof(VT);
+    const lsa_ndlu* f0 = f[0];
+    if (J < 1 || J > NB) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu: a block solve on %d factor sets, at most %d", J, NB);
+    NdMultiPtrs<R, NB> p;
+    memset(&p, 0, sizeof p);
+    p.ldb = ldb;
+    p.ldx = ldx;
+    for (int32_t z = 0; z < J; ++z) {
+        lsa_ndlu* g = f[z];
+        NdMultiSet<R>& s = p.set[z];
+        s.lfac = g->d_lfac;
+        s.ufac = g->d_ufac;
+        s.top = g->d_top;
+        s.rhs0 = b[z];
+        s.x0 = x[z];
+        const size_t acc_bytes = (size_t)std::max<int64_t>(g->acc_entries, 1) * 16;
+        for (int q = 0; q < R; ++q) {
+            void* acc = q == 0 ? g->d_acc : g->multi[(size_t)q - 1].acc;
+            int& vbytes = q == 0 ? g->acc_vbytes : g->multi[(size_t)q - 1].acc_vbytes;
+            if (vbytes != (int)sizeof(VT)) {  // (the rule of nd_sweep, per copy of the slot rows)
+                LSA_HIP_CHECK(ctx, hipMemsetAsync(acc, 0, acc_bytes, st));
+                vbytes = (int)sizeof(VT);
+            }
+            s.acc[q] = acc;
+            s.ubuf[q] = q == 0 ? g->d_ubuf : g->multi[(size_t)q - 1].ubuf;
+            s.xb[q] = q == 0 ? g->d_xb : g->multi[(size_t)q - 1].xb;
         }
-        p.rhs[q] = b[q];
-        p.x[q] = x[q];
-        p.acc[q] = acc;
-        p.ubuf[q] = q == 0 ? f->d_ubuf : f->multi[(size_t)q - 1].ubuf;
-        p.xb[q] = q == 0 ? f->d_xb : f->multi[(size_t)q - 1].xb;
     }
-    const bool top = ORDERED && f->top.s > 0;
-    for (size_t li = 0; li < f->levels.size(); ++li) {
-        const NdLevel& L = f->levels[li];
-        if (top && (int32_t)li + 1 == f->top_level) continue;  // the root's children: inside the root's launch
-        if (top && (int32_t)li == f->top_level) {
-            hipLaunchKernelGGL((nd_top_multi_kernel<MT, VT, R>), dim3((f->top.s + 7) / 8), dim3(256), 0, st, f->top, f->d_top_icmap, f->d_gell, p);
+    const bool top = ORDERED && f0->top.s > 0;
+    for (size_t li = 0; li < f0->levels.size(); ++li) {
+        const NdLevel& L = f0->levels[li];
+        if (top && (int32_t)li + 1 == f0->top_level) continue;  // the root's children: inside the root's launch
+        if (top && (int32_t)li == f0->top_level) {
+            NdTopArg<NB> tp;
+            if constexpr (NB == 1) tp = f0->top;
+            else tp = f0->d_top_rec;
+            hipLaunchKernelGGL((nd_top_multi_kernel<MT, VT, R, NB>), dim3((f0->top.s + 7) / 8, J), dim3(256), 0, st, tp, f0->d_top_icmap, f0->d_gell, p);
         } else if (L.fwd_tiles > 0) {
             nd_with_lpr<true>(L.sweep_rows, [&](auto lpr) {
-                hipLaunchKernelGGL((nd_fwd_multi_kernel<MT, VT, decltype(lpr)::value, ORDERED, R>), dim3(L.node_count, L.fwd_tiles), dim3(256), 0, st,
-                                   f->d_lnodes + L.node_begin, f->d_idx, f->d_gell, f->d_cmap, p);
+                hipLaunchKernelGGL((nd_fwd_multi_kernel<MT, VT, decltype(lpr)::value, ORDERED, R, NB>), dim3(L.node_count, L.fwd_tiles, J), dim3(256), 0, st,
+                                   f0->d_lnodes + L.node_begin, f0->d_idx, f0->d_gell, f0->d_cmap, p);
             });
         }
     }
-    for (size_t l = f->levels.size(); l-- > 0;) {
-        const NdLevel& L = f->levels[l];
-        if (L.bwd_tiles > 0 && !(top && (int32_t)l + 1 == f->top_level)) {
+    for (size_t l = f0->levels.size(); l-- > 0;) {
+        const NdLevel& L = f0->levels[l];
+        if (L.bwd_tiles > 0 && !(top && (int32_t)l + 1 == f0->top_level)) {
             nd_with_lpr<false>(L.bwd_rows, [&](auto lpr) {
-                hipLaunchKernelGGL((nd_bwd_multi_kernel<MT, VT, decltype(lpr)::value, ORDERED, R>), dim3(L.node_count, L.bwd_tiles), dim3(256), 0, st,
-                                   f->d_lnodes_bwd + L.node_begin, f->d_idx, f->d_gell, p);
+                hipLaunchKernelGGL((nd_bwd_multi_kernel<MT, VT, decltype(lpr)::value, ORDERED, R, NB>), dim3(L.node_count, L.bwd_tiles, J), dim3(256), 0, st,
+                                   f0->d_lnodes_bwd + L.node_begin, f0->d_idx, f0->d_gell, p);
             });
         }
     }
@@ -566,40 +617,62 @@ int32_t nd_pass_width(int32_t left, int32_t most) {
     return w >= 8 ? 8 : w >= 4 ? 4 : w >= 2 ? 2 : 1;
 }
 
-template <typename MT, typename VT>
-int nd_solve_multi(lsa_ctx* ctx, lsa_ndlu* f, int32_t nrhs, const VT* B, int64_t ldb, VT* X, int64_t ldx) {
+// An aliased block (B == X, ldb == ldx) is solved from a copy: the sweeps read a right-hand side after they began to write the
+// solution.  The record of a launch addresses a set's columns by one base and the shared leading dimension, so the copy of a
+// pass's W columns is one strided block of the set's own (lsa_ndlu::multi_stage, grown on demand), the columns ldb apart as in B.
+template <typename VT>
+int nd_multi_stage(lsa_ctx* ctx, lsa_ndlu* f, int32_t W, const VT* b, int64_t ldb, const VT** out) {
+    const size_t need = ((size_t)(W - 1) * (size_t)ldb + (size_t)f->S.n) * sizeof(VT);
+    if (f->multi_stage_bytes < (int64_t)need) {
+        if (f->multi_stage) (void)hipFree(f->multi_stage);
+        f->multi_stage = nullptr;
+        f->multi_bytes -= f->multi_stage_bytes;
+        f->multi_stage_bytes = 0;
+        LSA_HIP_ALLOC(ctx, hipMalloc(&f->multi_stage, need));
+        f->multi_stage_bytes = (int64_t)need;
+        f->multi_bytes += (int64_t)need;
+    }
+    LSA_HIP_CHECK(ctx, hipMemcpy2DAsync(f->multi_stage, (size_t)ldb * sizeof(VT), b, (size_t)ldb * sizeof(VT), (size_t)f->S.n * sizeof(VT), (size_t)W,
+                                        hipMemcpyDeviceToDevice, ctx->stream));
+    *out = (const VT*)f->multi_stage;
+    return LSA_OK;
+}
+
+// X[z][:, q] = C_z^-1 B[z][:, q] for J <= NB factor sets (J = NB = 1: lsa_ndlu_solve_multi), in passes of 8, 4 or 2 columns, the
+// widest every set has buffers for; a last single column goes through the solo sweeps (of the batch, for J sets)
+template <typename MT, typename VT, int NB>
+int nd_solve_multi(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int32_t nrhs, const VT* const* B, int64_t ldb, VT* const* X, int64_t ldx) {
     // (buffers for the widest pass that will run: the first)
-    const int32_t avail = nd_multi_ensure(ctx, f, nd_pass_width(nrhs, nd_multi_cap(sizeof(VT))));
-    const size_t nbytes = (size_t)f->S.n * sizeof(VT);
-    f->multi_width = 1;
+    const int32_t want = nd_pass_width(nrhs, nd_multi_cap(sizeof(VT)));
+    int32_t avail = want;
+    for (int32_t z = 0; z < J; ++z) avail = std::min(avail, nd_multi_ensure(ctx, f[z], want));
+    for (int32_t z = 0; z < J; ++z) f[z]->multi_width = 1, f[z]->multi_passes = 0;
     for (int32_t q0 = 0; q0 < nrhs;) {
         const int32_t R = nd_pass_width(nrhs - q0, avail);  // a remainder runs in narrower passes
+        const VT* b[NB];
+        VT* x[NB];
+        for (int32_t z = 0; z < J; ++z) {
+            b[z] = B[z] + (int64_t)q0 * ldb;
+            x[z] = X[z] + (int64_t)q0 * ldx;
+        }
         if (R == 1) {
-            LSA_CHECK(ndlu_solve_dev(ctx, f, scalar_traits<VT>::dtype, B + (int64_t)q0 * ldb, X + (int64_t)q0 * ldx));
+            if constexpr (NB == 1) LSA_CHECK(ndlu_solve_dev(ctx, f[0], scalar_traits<VT>::dtype, b[0], x[0]));
+            else LSA_CHECK(ndlu_solve_batch_dev(ctx, J, f, scalar_traits<VT>::dtype, (const void**)b, (void* const*)x));
             q0 += 1;
             continue;
         }
-        const VT* b[kNdMultiMax];
-        VT* x[kNdMultiMax];
-        for (int32_t q = 0; q < R; ++q) {
-            b[q] = B + (int64_t)(q0 + q) * ldb;
-            x[q] = X + (int64_t)(q0 + q) * ldx;
-            if (b[q] == x[q]) {  // in place: the sweeps read a right-hand side after they began to write the solution
-                void* tmp = q == 0 ? f->d_tmp : f->multi[(size_t)q - 1].tmp;
-                LSA_HIP_CHECK(ctx, hipMemcpyAsync(tmp, b[q], nbytes, hipMemcpyDeviceToDevice, ctx->stream));
-                b[q] = (const VT*)tmp;
-            }
-        }
+        for (int32_t z = 0; z < J; ++z)
+            if (b[z] == x[z]) LSA_CHECK(nd_multi_stage(ctx, f[z], R, b[z], ldb, &b[z]));
         auto run = [&](auto width) {
             constexpr int W = decltype(width)::value;
-            return f->ordered ? nd_sweep_multi<MT, VT, true, W>(ctx, f, b, x) : nd_sweep_multi<MT, VT, false, W>(ctx, f, b, x);
+            return f[0]->ordered ? nd_sweep_multi<MT, VT, true, W, NB>(ctx, J, f, b, ldb, x, ldx) : nd_sweep_multi<MT, VT, false, W, NB>(ctx, J, f, b, ldb, x, ldx);
         };
         if constexpr (sizeof(VT) == 8) {
             if (R == 8) LSA_CHECK(run(std::integral_constant<int, 8>{}));
         }
         if (R == 4) LSA_CHECK(run(std::integral_constant<int, 4>{}));
         if (R == 2) LSA_CHECK(run(std::integral_constant<int, 2>{}));
-        f->multi_width = std::max(f->multi_width, R);
+        for (int32_t z = 0; z < J; ++z) f[z]->multi_width = std::max(f[z]->multi_width, R), ++f[z]->multi_passes;
         q0 += R;
     }
     return LSA_OK;
@@ -647,16 +720,38 @@ void ndlu_multi_free(lsa_ndlu* f) {
         for (void* q : {c.ubuf, c.xb, c.acc, c.tmp})
             if (q) (void)hipFree(q);
     f->multi.clear();
+    if (f->multi_stage) (void)hipFree(f->multi_stage);
+    f->multi_stage = nullptr;
+    f->multi_stage_bytes = 0;
     f->multi_bytes = 0;
 }
 
+namespace {
+
+template <int NB>
+int nd_solve_multi_sets(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb,
+                        void* const* X, int64_t ldx) {
+    for (int32_t z = 0; z < J; ++z)
+        if (f[z]->S.nranks > 1 || f[z]->S.has_dist) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the multi-column sweeps need one rank and no distributed node", who);
+    if (f[0]->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: complex factors need complex vectors", who);
+    if (f[0]->S.n == 0) return LSA_OK;
+    if (f[0]->dtype == LSA_C128) return nd_solve_multi<cplx, cplx, NB>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
+    if (vdtype == LSA_C128) return nd_solve_multi<double, cplx, NB>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
+    return nd_solve_multi<double, double, NB>(ctx, J, f, nrhs, (const double* const*)B, ldb, (double* const*)X, ldx);
+}
+
+}  // namespace
+
 int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx) {
-    if (f->S.nranks > 1 || f->S.has_dist) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi: the multi-column sweeps need one rank and no distributed node");
-    if (f->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi: complex factors need complex vectors");
-    if (f->S.n == 0) return LSA_OK;
-    if (f->dtype == LSA_C128) return nd_solve_multi<cplx, cplx>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
-    if (vdtype == LSA_C128) return nd_solve_multi<double, cplx>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
-    return nd_solve_multi<double, double>(ctx, f, nrhs, (const double*)B, ldb, (double*)X, ldx);
+    return nd_solve_multi_sets<1>(ctx, "lsa_ndlu_solve_multi", 1, &f, vdtype, nrhs, &B, ldb, &X, ldx);
+}
+
+// the same block solve on J <= kNdBatchMax factor sets of one analysis (nd_batch_compatible), every launch carrying all columns of
+// a pass for all sets; B[z] may be one block for several sets, or X[z] itself (with ldb == ldx)
+int ndlu_solve_multi_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb, void* const* X,
+                               int64_t ldx) {
+    if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch: J = %d outside [1, %d]", J, kNdBatchMax);
+    return nd_solve_multi_sets<kNdBatchMax>(ctx, "lsa_ndlu_solve_multi_batch", J, f, vdtype, nrhs, B, ldb, X, ldx);
 }
 
 // X[:, q] = C^-T B[:, q] (conj == 0) or C^-H B[:, q] on the factors of C, in passes that share every factor load

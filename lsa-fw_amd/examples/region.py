@@ -33,6 +33,7 @@ def main() -> None:
     ap.add_argument("--subspace", type=int, default=48)
     ap.add_argument("--atol", type=float, default=1e-10)
     ap.add_argument("--max-it", type=int, default=20)
+    ap.add_argument("--batch-nodes", action="store_true", help="solve every iteration's block on all nodes in lockstep (same bytes; one more block per node)")
     args = ap.parse_args()
     logging.basicConfig(level=logging.WARNING)
     if args.region is not None:
@@ -42,7 +43,8 @@ def main() -> None:
     else:
         region = Ellipse(complex(fem.SIGMA_RE50), 0.12, 0.12)
     es = fem.cylinder_case(args.case)
-    rs = RegionEigenSolver(es.A, es.M, RegionConfig(nodes=args.nodes, subspace=args.subspace, atol=args.atol, max_it=args.max_it))
+    rs = RegionEigenSolver(es.A, es.M, RegionConfig(nodes=args.nodes, subspace=args.subspace, atol=args.atol, max_it=args.max_it,
+                                                     batch_nodes=args.batch_nodes))
     res = rs.solve(region)
     st = res.stats
     print(f"{args.case}: n = {es.n}; {region}")
@@ -50,7 +52,8 @@ def main() -> None:
           f"the ellipse {res.estimate:.1f}; factors {'kept' if st['factors_kept'] else 'refactorised per node'}")
     print(f"seconds: factor {st['seconds_factor']:.4f}, block solves {st['seconds_solve']:.4f}, products {st['seconds_product']:.4f}, "
           f"Gram {st['seconds_gram']:.4f}, host dense {st['seconds_dense']:.4f}, total {st['seconds_total']:.4f}; {st['block_solves']} column solves, "
-          f"{st['refined_solves']} refined")
+          f"{st['refined_solves']} refined" + (f"; nodes in lockstep: {st['batched_groups']} batched groups, {st['batched_columns']} column solves"
+                                                if st["batch_nodes"] else ""))
     for lam, r in zip(res.eigenvalues, res.residuals):
         print(f"  {lam.real:+.12f} {lam.imag:+.12f}j   residual {r:.2e}")
     rs.release()

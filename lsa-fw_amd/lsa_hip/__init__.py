@@ -142,6 +142,16 @@ class lsa_contour_stats(ctypes.Structure):
     ]
 
 
+class lsa_contour_batch_stats(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_int32),
+        ("pad0", ctypes.c_int32),
+        ("groups", ctypes.c_int64),
+        ("batched_columns", ctypes.c_int64),
+        ("serial_columns", ctypes.c_int64),
+    ]
+
+
 class lsa_stochastic_stats(ctypes.Structure):
     _fields_ = [
         ("nodes", ctypes.c_int32),
@@ -221,6 +231,8 @@ SIGNATURES = {
     "lsa_ndlu_solve_time": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.POINTER(_DBL)]),
     "lsa_ndlu_solve_multi": (ctypes.c_int, [_P, _P, ctypes.c_int, _I32, _P, _I64, _P, _I64]),
     "lsa_ndlu_solve_multi_time": (ctypes.c_int, [_P, _P, ctypes.c_int, _I32, _P, _I64, _P, _I64, ctypes.c_int, ctypes.POINTER(_DBL)]),
+    "lsa_ndlu_solve_multi_batch": (ctypes.c_int, [_P, _I32, _PP, ctypes.c_int, _I32, _PP, _I64, _PP, _I64]),
+    "lsa_ndlu_solve_multi_batch_time": (ctypes.c_int, [_P, _I32, _PP, ctypes.c_int, _I32, _PP, _I64, _PP, _I64, ctypes.c_int, ctypes.POINTER(_DBL)]),
     "lsa_ndlu_set_multi_transposed": (ctypes.c_int, [_P, _P, ctypes.c_int]),
     "lsa_ndlu_multi_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "lsa_ndlu_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64),
@@ -290,6 +302,8 @@ SIGNATURES = {
     "lsa_contour_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
     "lsa_contour_solve": (ctypes.c_int, [_P, _P, _DBL, _I32, _P, _I32, _P, _P, _P, ctypes.POINTER(lsa_contour_result)]),
     "lsa_contour_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_contour_stats)]),
+    "lsa_contour_set_batch_nodes": (ctypes.c_int, [_P, _P, ctypes.c_int]),
+    "lsa_contour_batch_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_contour_batch_stats)]),
     "lsa_shifted_spmm": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P]),
     "lsa_stochastic_create": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _I32, _DBL, _PP]),
     "lsa_stochastic_destroy": (None, [_P]),
@@ -908,6 +922,42 @@ class NdLu:
         self.ctx.check(self.ctx._lib.lsa_ndlu_solve_multi_time(*self._multi_args(B, X, nrhs, ldb, ldx, trans), int(iters), ctypes.byref(ms)))
         return ms.value
 
+    @staticmethod
+    def _multi_batch_args(factors, Bs, Xs, nrhs, ldb, ldx, trans):
+        # (the three argument errors come first: nothing of the library, not even a context, is touched before them)
+        J = len(factors)
+        if J < 1 or J > NDLU_BATCH_MAX:
+            raise ValueError(f"solve_multi_batch takes between 1 and {NDLU_BATCH_MAX} factorisations, got {J}")
+        if len(Bs) != J or len(Xs) != J:
+            raise ValueError(f"solve_multi_batch needs as many blocks B and X as factorisations ({J}), got {len(Bs)} and {len(Xs)}")
+        if trans != "N":
+            raise ValueError(f"solve_multi_batch: trans must be 'N', got {trans!r}: the transposed form on a batch of factor sets is not built")
+        ctx = factors[0].ctx
+        if any(f.ctx is not ctx for f in factors) or any(v.ctx is not ctx for v in list(Bs) + list(Xs)):
+            raise ValueError("solve_multi_batch: the factorisations and vectors must live in one context")
+        arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
+        n = factors[0].n
+        return ctx, (ctx.handle, J, arr(factors), 0, int(nrhs), arr(Bs), int(n if ldb is None else ldb), arr(Xs), int(n if ldx is None else ldx))
+
+    @staticmethod
+    def solve_multi_batch(factors: "list[NdLu]", Bs: "list[DeviceVector]", Xs: "list[DeviceVector]", nrhs: int, ldb: int | None = None,
+                          ldx: int | None = None, trans: str = "N") -> None:
+        """``Xs[z][:, q] = C_z^-1 Bs[z][:, q]`` for ``nrhs`` columns on up to 16 factorisations of one analysis
+        (``lsa_ndlu_solve_multi_batch``): every launch of the sweeps carries all columns of a pass for all sets.  The blocks share
+        ``ldb`` and ``ldx`` (default ``n``); several sets may read one ``B``; ``Bs[z] is Xs[z]`` solves in place.  Every column is
+        bit-identical to :meth:`solve`.  ``trans`` must be ``"N"``: the transposed form is not built."""
+        ctx, args = NdLu._multi_batch_args(factors, Bs, Xs, nrhs, ldb, ldx, trans)
+        ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch(*args))
+
+    @staticmethod
+    def time_solve_multi_batch(factors: "list[NdLu]", Bs: "list[DeviceVector]", Xs: "list[DeviceVector]", nrhs: int, iters: int,
+                               ldb: int | None = None, ldx: int | None = None) -> float:
+        """Mean milliseconds of one block solve on all sets over ``iters`` back-to-back repetitions (``lsa_ndlu_solve_multi_batch_time``)."""
+        ctx, args = NdLu._multi_batch_args(factors, Bs, Xs, nrhs, ldb, ldx, "N")
+        ms = _DBL(0.0)
+        ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch_time(*args, int(iters), ctypes.byref(ms)))
+        return ms.value
+
     def set_multi_transposed(self, on: bool) -> None:
         """``True``: :meth:`solve_multi` and :meth:`time_solve_multi` with ``trans`` ``"T"`` / ``"H"`` run in the wide passes of
         ``trans="N"`` (``lsa_ndlu_set_multi_transposed``; same bits per column).  Off by default: column by column."""
@@ -1352,7 +1402,7 @@ class ContourSolver:
     iteration; both return the same bytes.  ``A`` and ``M`` share one pattern, ``M`` is real."""
 
     def __init__(self, ctx: Context, A: CsrMatrix, M: CsrMatrix, nodes: int, centre: complex, rx: float, ry: float, subspace: int, *,
-                 keep_factors: bool = True, ksp_rtol: float = 1e-12):
+                 keep_factors: bool = True, ksp_rtol: float = 1e-12, batch_nodes: bool = False):
         self.ctx, self._keep = ctx, (A, M)  # (the handle borrows both matrices)
         self.n, self.subspace, self.nodes = A.shape[0], int(subspace), int(nodes)
         centre = complex(centre)
@@ -1360,6 +1410,20 @@ class ContourSolver:
         ctx.check(ctx._lib.lsa_contour_create(ctx.handle, A.handle, None if M is None else M.handle, self.nodes, (_DBL * 2)(centre.real, centre.imag),
                                               (_DBL * 2)(float(rx), float(ry)), self.subspace, int(bool(keep_factors)), float(ksp_rtol), ctypes.byref(h)))
         self.handle = h
+        if batch_nodes:
+            self.set_batch_nodes(True)
+
+    def set_batch_nodes(self, on: bool) -> None:
+        """``True``: an iteration solves its block on all nodes in lockstep, in runs of up to 16 factor sets per launch
+        (``lsa_contour_set_batch_nodes``); needs ``keep_factors`` and one more ``n x subspace`` block per node.  Same bytes as off."""
+        self.ctx.check(self.ctx._lib.lsa_contour_set_batch_nodes(self.ctx.handle, self.handle, int(bool(on))))
+
+    def batch_info(self) -> dict:
+        """``lsa_contour_batch_info``: ``enabled``, ``groups`` (batched groups launched), ``batched_columns`` and
+        ``serial_columns`` (column solves done in batches / node by node)."""
+        st = lsa_contour_batch_stats()
+        self.ctx.check(self.ctx._lib.lsa_contour_batch_info(self.handle, ctypes.byref(st)))
+        return {"enabled": bool(st.enabled), "groups": st.groups, "batched_columns": st.batched_columns, "serial_columns": st.serial_columns}
 
     def set_row_permutation(self, perm: np.ndarray | None) -> None:
         """``perm[i]`` = the caller's index of row ``i``: the vectors of :meth:`solve` come back in the caller's numbering."""

@@ -20,6 +20,12 @@ the file exists (one case per call keeps a call short).
 checked bit for bit against solo adjoint solves.  The solo figure and every ``nrhs`` are timed ``--rounds`` times in turn and the
 medians are recorded (all rounds are kept in the file).  ``--parent-solo-us`` is then the parent commit's
 ``time_solve_multi(..., nrhs=1, trans=...)`` of the same process order on the same box.
+
+``--sets J`` measures the block solve on a batch of factor sets instead (``--out`` then defaults to ``profiles/multi_batch.json``):
+J factorisations of the case at J shifts on one ordering, one block of ``--nrhs`` columns (the first figure given; default 4) per
+set.  ``NdLu.time_solve_multi_batch`` on all sets against ``NdLu.time_solve_multi`` looped over the sets, in the same process,
+alternating for ``--rounds`` rounds after a warm-up; the medians are recorded as milliseconds per column per set.  Every block is
+checked bit for bit against ``solve_multi`` on its set alone.
 """
 
 from __future__ import annotations
@@ -102,6 +108,61 @@ def measure_transposed(case: str, counts: list[int], iters: int, trans: str, rou
     return out
 
 
+def measure_sets(case: str, J: int, nrhs: int, iters: int, rounds: int) -> dict:
+    """``solve_multi_batch`` on J factor sets against ``solve_multi`` looped over them: ms per column per set."""
+    import statistics
+
+    import numpy as np
+    import scipy.sparse as sp
+
+    import lsa_hip
+    from synthetic import fem
+
+    es = fem.cylinder_case(case)
+    shifts = [fem.SIGMA_RE50 + 0.01 * j * (1 + 1j) for j in range(J)]
+    C0 = sp.csr_matrix((es.A.data - shifts[0] * es.M.data, es.A.indices, es.A.indptr), shape=es.A.shape)
+    zd = C0.diagonal() == 0
+    o = lsa_hip.nd_order(C0, 0, constraint=zd if (zd.any() and C0.nnz > 60 * es.n) else None)
+    A = sp.csr_matrix(es.A)[o["perm"]][:, o["perm"]].tocsr()
+    M = sp.csr_matrix((es.M.data, es.A.indices, es.A.indptr), shape=es.A.shape)[o["perm"]][:, o["perm"]].tocsr()
+    for m in (A, M):
+        m.sort_indices()
+    ctx = lsa_hip.Context(0)
+    n = es.n
+    fs, keep = [], []
+    for z in shifts:
+        C = sp.csr_matrix((A.data - z * M.data, A.indices, A.indptr), shape=A.shape)
+        dC = lsa_hip.CsrMatrix.from_scipy(ctx, C)
+        fs.append(lsa_hip.NdLu(ctx, dC, 0, tree={"first": o["first"], "size": o["size"], "parent": o["parent"]}))
+        keep.append(dC)
+    rng = np.random.default_rng(0)
+    B = np.asfortranarray(rng.standard_normal((n, nrhs)) + 1j * rng.standard_normal((n, nrhs)))
+    dB = lsa_hip.DeviceVector.from_numpy(ctx, B.reshape(-1, order="F"))
+    dXs = [lsa_hip.DeviceVector(ctx, n * nrhs, np.complex128) for _ in range(J)]
+    dY = lsa_hip.DeviceVector(ctx, n * nrhs, np.complex128)
+    lsa_hip.NdLu.solve_multi_batch(fs, [dB] * J, dXs, nrhs)
+    same = True
+    for f, dX in zip(fs, dXs):
+        f.solve_multi(dB, dY, nrhs)
+        same = same and bool(np.array_equal(dX.numpy(), dY.numpy()))
+    loop_iters = max(3, iters // J)
+    looped = lambda: sum(f.time_solve_multi(dB, dY, nrhs, iters=loop_iters) for f in fs)  # noqa: E731
+    batched = lambda: lsa_hip.NdLu.time_solve_multi_batch(fs, [dB] * J, dXs, nrhs, iters=loop_iters)  # noqa: E731
+    looped(), batched()  # warm-up
+    loop_rounds, batch_rounds = [], []
+    for _ in range(rounds):
+        loop_rounds.append(looped())
+        batch_rounds.append(batched())
+    lm, bm = statistics.median(loop_rounds), statistics.median(batch_rounds)
+    per = 1.0 / (J * nrhs)
+    out = {"case": case, "n": int(n), "sets": J, "nrhs": nrhs, "rounds": rounds, "iters": loop_iters, "apply_launches": int(fs[0].info()["apply_launches"]),
+           "looped_ms_per_column_per_set": lm * per, "batched_ms_per_column_per_set": bm * per, "looped_over_batched": lm / bm,
+           "looped_ms_rounds": loop_rounds, "batched_ms_rounds": batch_rounds, "bit_identical_to_solve_multi": same, "width": fs[0].multi_info()["width"]}
+    print(f"{case} sets={J} nrhs={nrhs}: looped solve_multi {lm * per * 1e3:.1f} us, solve_multi_batch {bm * per * 1e3:.1f} us per column per set "
+          f"({lm / bm:.2f}x), bits {'same' if same else 'DIFFER'}", flush=True)
+    return out
+
+
 def measure(case: str, counts: list[int], iters: int, parent_solo_us: float | None = None) -> dict:
     import numpy as np
     import scipy.sparse as sp
@@ -170,15 +231,19 @@ def main() -> None:
     ap.add_argument("--parent-solo-us", nargs="+", type=float, default=None, help="per case: the parent commit's bench_ndlu.py figure on this box")
     ap.add_argument("--trans", choices=["N", "T", "H"], default="N", help="N: C^-1 (the default); T / H: the transposed / adjoint block solve in wide passes")
     ap.add_argument("--rounds", type=int, default=3, help="--trans T / H: rounds of (solo, every nrhs) whose medians are recorded")
-    ap.add_argument("--out", default=None, help="default: profiles/multi_rhs.json, or profiles/multi_rhs_adjoint.json with --trans T / H")
+    ap.add_argument("--sets", type=int, default=0, help="J > 0: the block solve on J factor sets (solve_multi_batch) against solve_multi looped over them")
+    ap.add_argument("--out", default=None, help="default: profiles/multi_rhs.json, or profiles/multi_rhs_adjoint.json with --trans T / H, or profiles/multi_batch.json with --sets")
     args = ap.parse_args()
-    path = Path(args.out) if args.out else ROOT / "profiles" / ("multi_rhs.json" if args.trans == "N" else "multi_rhs_adjoint.json")
+    name = "multi_batch.json" if args.sets else "multi_rhs.json" if args.trans == "N" else "multi_rhs_adjoint.json"
+    path = Path(args.out) if args.out else ROOT / "profiles" / name
     doc = json.loads(path.read_text()) if path.exists() else {"tool": "tools/multi_rhs_throughput.py", "runs": []}
     if args.parent_solo_us is not None and len(args.parent_solo_us) != len(args.cases):
         ap.error("--parent-solo-us needs one figure per case")
     for i, case in enumerate(args.cases):
         parent = None if args.parent_solo_us is None else args.parent_solo_us[i]
-        if args.trans == "N":
+        if args.sets:
+            doc["runs"].append(measure_sets(case, args.sets, 4 if len(args.nrhs) > 1 else args.nrhs[0], args.iters, args.rounds))
+        elif args.trans == "N":
             doc["runs"].append(measure(case, args.nrhs, args.iters, parent))
         else:
             doc["runs"].append(measure_transposed(case, args.nrhs, args.iters, args.trans, args.rounds, parent))

@@ -8,7 +8,9 @@ spare (at least 12 asked for).  Alternating, after one warm-up of each, fresh so
 to release: (a) ``RegionEigenSolver`` with kept factor sets, (b) with one refactorised set, (c) ``EigenSolver`` (Krylov-Schur,
 shift-invert at ``target = centre``, ``nev`` = the count), which finds the same pairs without the proof.  Medians and spreads of
 ``reps`` samples; for (a) and (b) also the split factor / block solves / products / Gram / host dense of ``lsa_contour_info`` and the
-iterations.  Needs an AMD GPU.
+iterations.  ``--batch-nodes`` adds one more row, (d) kept factor sets with the nodes solved in lockstep
+(``RegionConfig(batch_nodes=True)``): the same regions in the same process, so that ``seconds_solve`` and the wall time stand beside
+those of (a), the switch off; ``--skip-krylov`` leaves (b) and (c) out for that comparison alone.  Needs an AMD GPU.
 """
 
 from __future__ import annotations
@@ -38,16 +40,17 @@ def choose_circle(es, centre: complex, inside: int, subspace: int):
     return 0.5 * float(d[inside - 1] + d[inside]), float(d[inside - 1]), float(d[inside])
 
 
-def region_sample(es, centre, radius, cfg_args, keep: bool) -> dict:
+def region_sample(es, centre, radius, cfg_args, keep: bool, batch_nodes: bool = False) -> dict:
     from Solver.region import Ellipse, RegionConfig, RegionEigenSolver
 
     t0 = time.perf_counter()
-    rs = RegionEigenSolver(es.A, es.M, RegionConfig(keep_factors=keep, **cfg_args))
+    rs = RegionEigenSolver(es.A, es.M, RegionConfig(keep_factors=keep, batch_nodes=batch_nodes, **cfg_args))
     res = rs.solve(Ellipse(centre, radius, radius))
     rs.release()
     dt = time.perf_counter() - t0
     return {"seconds": dt, "count": res.count, "complete": res.complete, "iterations": res.iterations, "max_residual": float(np.max(res.residuals, initial=0.0)),
             "refined_solves": res.stats["refined_solves"], "block_solves": res.stats["block_solves"], "eigenvalues": res.eigenvalues,
+            "batched_groups": res.stats["batched_groups"], "batched_columns": res.stats["batched_columns"],
             **{k: res.stats[k] for k in SPLIT}}
 
 
@@ -87,6 +90,8 @@ def main(argv=None) -> None:
     ap.add_argument("--atol", type=float, default=1e-10)
     ap.add_argument("--max-it", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--batch-nodes", action="store_true", help="one more row: kept factor sets, the nodes solved in lockstep")
+    ap.add_argument("--skip-krylov", action="store_true", help="only the kept rows (with --batch-nodes: the switch off and on)")
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "region_ab.json")
     args = ap.parse_args(argv)
     cfg_args = {"nodes": args.nodes, "subspace": args.subspace, "atol": args.atol, "max_it": args.max_it}
@@ -99,19 +104,30 @@ def main(argv=None) -> None:
         samplers = {"kept": lambda: region_sample(es, centre, radius, cfg_args, True),
                     "refactorised": lambda: region_sample(es, centre, radius, cfg_args, False),
                     "krylov_schur": lambda: krylov_sample(es, centre, args.inside, args.atol)}
+        if args.batch_nodes:
+            samplers["kept_batch_nodes"] = lambda: region_sample(es, centre, radius, cfg_args, True, True)
+        if args.skip_krylov:
+            samplers = {k: fn for k, fn in samplers.items() if k.startswith("kept")}
         runs = {k: [] for k in samplers}
         for fn in samplers.values():
             fn()  # warm-up: code objects, host caches
         for _ in range(args.reps):
             for k, fn in samplers.items():
                 runs[k].append(fn())
-        lam_r, lam_k = runs["kept"][0]["eigenvalues"], runs["krylov_schur"][0]["eigenvalues"]
-        inside_k = lam_k[np.abs(lam_k - centre) < radius]
-        diff = max((float(np.min(np.abs(lam_r - z))) for z in inside_k), default=float("nan")) if lam_r.size else float("nan")
+        lam_r = runs["kept"][0]["eigenvalues"]
         case = {"case": name, "n": int(es.n), "centre": [centre.real, centre.imag], "radius": radius, "nearest_inside": d_in, "nearest_outside": d_out,
-                "kept": summarise(runs["kept"], SPLIT), "refactorised": summarise(runs["refactorised"], SPLIT),
-                "krylov_schur": summarise(runs["krylov_schur"], ("seconds_factor",)), "krylov_inside": int(inside_k.size), "eigenvalue_difference": diff}
-        case["proof_cost_ratio"] = case["kept"]["seconds"]["median"] / case["krylov_schur"]["seconds"]["median"]
+                "kept": summarise(runs["kept"], SPLIT)}
+        if "kept_batch_nodes" in runs:
+            case["kept_batch_nodes"] = summarise(runs["kept_batch_nodes"], SPLIT)
+            case["batch_nodes_same_bytes"] = bool(runs["kept_batch_nodes"][0]["eigenvalues"].tobytes() == lam_r.tobytes())
+            case["seconds_solve_off_over_on"] = case["kept"]["seconds_solve"]["median"] / case["kept_batch_nodes"]["seconds_solve"]["median"]
+        if not args.skip_krylov:
+            lam_k = runs["krylov_schur"][0]["eigenvalues"]
+            inside_k = lam_k[np.abs(lam_k - centre) < radius]
+            diff = max((float(np.min(np.abs(lam_r - z))) for z in inside_k), default=float("nan")) if lam_r.size else float("nan")
+            case.update(refactorised=summarise(runs["refactorised"], SPLIT), krylov_schur=summarise(runs["krylov_schur"], ("seconds_factor",)),
+                        krylov_inside=int(inside_k.size), eigenvalue_difference=diff)
+            case["proof_cost_ratio"] = case["kept"]["seconds"]["median"] / case["krylov_schur"]["seconds"]["median"]
         result["cases"].append(case)
         print(json.dumps(case), flush=True)
     args.out.parent.mkdir(parents=True, exist_ok=True)
