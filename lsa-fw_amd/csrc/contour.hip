@@ -22,9 +22,7 @@
 #include <complex>
 #include <numeric>
 
-#include "lsa_internal.h"
-#include "nd_internal.h"
-#include "ndlu_internal.h"
+#include "shifted_sets.h"
 
 namespace {
 
@@ -336,18 +334,14 @@ typedef std::complex<double> ci_z;
 
 struct lsa_contour {
     lsa_ctx* ctx = nullptr;
-    const lsa_mat *A = nullptr, *M = nullptr;
     int64_t n = 0;
     int32_t N = 0, L = 0;  // nodes, columns of the subspace
     bool keep = false;     // N factor sets alive, or one that is refactorised node by node
     double ksp_rtol = 0.0;
     double centre[2] = {0.0, 0.0}, radii[2] = {0.0, 0.0};
-    std::vector<ci_z> z, w;         // nodes and weights
-    std::vector<lsa_mat*> C;        // C_k = A - z_k M (values only: A's index arrays)
-    std::vector<double> normF;      // ||C_k||_F
-    std::vector<lsa_ndlu*> F;       // keep: N factor sets, else one
-    int32_t cur = -1;               // the node whose values F[0] holds (refactorised sets)
-    std::vector<char> refine;       // per node: its block solves carry the refinement step
+    std::vector<ci_z> w;            // the nodes' weights
+    // the pencils C_k = A - z_k M at the nodes with their factor sets; refine[0][k]: node k's block solves carry the refinement step
+    shifted_sets* S = nullptr;
     // n x L blocks: the basis, M Y, a node's solutions, the quadrature sum, and two work blocks (C_k X; A U and M U)
     cplx *Y = nullptr, *B = nullptr, *X = nullptr, *Q = nullptr, *W1 = nullptr, *W2 = nullptr;
     cplx *qdev = nullptr, *lamdev = nullptr;  // L x L coefficients of k_basis_gemm, L Ritz values
@@ -359,16 +353,13 @@ struct lsa_contour {
     int64_t batch_groups = 0, batch_columns = 0, serial_columns = 0;
     lsa_stats st{};
     int64_t bytes = 0;
-    double sec_factor = 0.0, sec_solve = 0.0, sec_product = 0.0, sec_gram = 0.0, sec_dense = 0.0;
+    double sec_solve = 0.0, sec_product = 0.0, sec_gram = 0.0, sec_dense = 0.0;
 };
 
 namespace {
 
 void ct_free(lsa_contour* h) {
-    for (lsa_ndlu* f : h->F)
-        if (f) lsa_ndlu_destroy(f);
-    for (lsa_mat* c : h->C)
-        if (c) lsa_mat_destroy(c);
+    shifted_sets_free(h->S);
     for (void* p : {(void*)h->Y, (void*)h->B, (void*)h->X, (void*)h->Q, (void*)h->W1, (void*)h->W2, (void*)h->qdev, (void*)h->lamdev, (void*)h->sums,
                     (void*)h->imag2, (void*)h->row_perm, (void*)h->XN})
         if (p) (void)hipFree(p);
@@ -409,25 +400,6 @@ int ct_times_host(lsa_ctx* ctx, lsa_contour* h, int m, int k, const cplx* V, con
     return basis_times_host_matrix(ctx, LSA_C128, h->n, m, k, V, T, m, h->qdev, Out, 0);
 }
 
-// the factors of node k: its own set, or the one set refactorised for it
-int ct_factors(lsa_ctx* ctx, lsa_contour* h, int32_t k, lsa_ndlu** f) {
-    if (h->keep) {
-        *f = h->F[(size_t)k];
-        return LSA_OK;
-    }
-    if (h->cur != k) {
-        const double t0 = now_s();
-        h->cur = -1;
-        int rc = lsa_ndlu_refactor(ctx, h->F[0], h->C[(size_t)k]);
-        if (rc == LSA_OK) rc = ct_sync(ctx);
-        h->sec_factor += now_s() - t0;
-        if (rc != LSA_OK) return lsa_set_error(ctx, rc, "lsa_contour: node %d (z = %.6g%+.6gi): %s", k, h->z[(size_t)k].real(), h->z[(size_t)k].imag(), std::string(ctx->err).c_str());
-        h->cur = k;
-    }
-    *f = h->F[0];
-    return LSA_OK;
-}
-
 // the accepted columns of a node's block solve into the counters (s: the three sums per column of ct_column_sums)
 void ct_book_columns(lsa_contour* h, int32_t cols, const double* s, bool refined, double* worst) {
     for (int32_t j = 0; j < cols; ++j) {
@@ -443,33 +415,36 @@ void ct_book_columns(lsa_contour* h, int32_t cols, const double* s, bool refined
 int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, double* worst) {
     const int64_t n = h->n;
     lsa_ndlu* f = nullptr;
-    LSA_CHECK(ct_factors(ctx, h, k, &f));
+    LSA_CHECK(shifted_sets_factors(ctx, h->S, "lsa_contour", k, &f));
+    const lsa_mat* C = h->S->C[(size_t)k];
+    char& refine = h->S->refine[0][(size_t)k];
     const double t0 = now_s();
     std::vector<double> s((size_t)3 * cols);
     bool refined = false;
     int rc = ndlu_solve_multi_dev(ctx, f, LSA_C128, cols, h->B, n, h->X, n);
     while (rc == LSA_OK) {
-        if (h->refine[(size_t)k] && !refined) {
+        if (refine && !refined) {
             // R = B - C X;  D = C^-1 R;  X += D
-            rc = k_spmm(ctx, h->C[(size_t)k], cols, h->X, n, h->W1, n);
+            rc = k_spmm(ctx, C, cols, h->X, n, h->W1, n);
             if (rc == LSA_OK) rc = ct_accumulate(ctx, n, cols, ci_z(1.0, 0.0), h->B, -1.0, h->W1);
             if (rc == LSA_OK) rc = ndlu_solve_multi_dev(ctx, f, LSA_C128, cols, h->W1, n, h->W1, n);
             if (rc == LSA_OK) rc = ct_accumulate(ctx, n, cols, ci_z(1.0, 0.0), h->W1, 1.0, h->X);
             if (rc != LSA_OK) break;
             refined = true;
         }
-        rc = k_spmm(ctx, h->C[(size_t)k], cols, h->X, n, h->W1, n);
+        rc = k_spmm(ctx, C, cols, h->X, n, h->W1, n);
         if (rc == LSA_OK) rc = ct_column_sums(ctx, h, cols, h->B, h->W1, h->X, nullptr, s.data());
         if (rc != LSA_OK) break;
         bool again = false;
         for (int32_t j = 0; j < cols && rc == LSA_OK; ++j) {
             const double res = std::sqrt(s[3 * (size_t)j]), bnorm = std::sqrt(s[3 * (size_t)j + 1]), xnorm = std::sqrt(s[3 * (size_t)j + 2]);
-            if (res <= h->ksp_rtol * bnorm) continue;
-            if (!refined && std::isfinite(res)) {
+            bool backward = false;
+            const int verdict = shifted_sets_verdict(h->S, k, h->ksp_rtol, refined, res, bnorm, xnorm, &backward);
+            if (verdict > 0) {
                 again = true;
                 break;
             }
-            if (!(refined && h->normF[(size_t)k] > 0.0 && res <= 1e-12 * h->normF[(size_t)k] * xnorm))
+            if (verdict < 0)
                 rc = refined ? lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_contour_solve: the solve of column %d at node %d left a relative residual of %.3e "
                                                                     "after its refinement step (ksp_rtol %.1e) and a backward error above 1e-12 ||C||_F", j, k,
                                              bnorm > 0.0 ? res / bnorm : res, h->ksp_rtol)
@@ -478,7 +453,7 @@ int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, double
         }
         if (rc != LSA_OK) break;
         if (again) {
-            h->refine[(size_t)k] = 1;
+            refine = 1;
             continue;
         }
         ct_book_columns(h, cols, s.data(), refined, worst);
@@ -490,39 +465,30 @@ int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, double
 }
 
 // lsa_contour_set_batch_nodes: X_k = C_k^-1 B for every node that does not carry the refinement step, into the nodes' own blocks
-// -- runs of at most kNdBatchMax compatible factor sets (the grouping of sf_solve_all, stochastic.hip), each run one block solve on
-// all its sets from the shared B.  solved[k] = 1: X_k is there, with the bits ct_block_solve's first solve gives.
+// -- run by run (shifted_sets_next_run), each run one block solve on all its sets from the shared B.  solved[k] = 1: X_k is there,
+// with the bits ct_block_solve's first solve gives.
 int ct_batch_solve(lsa_ctx* ctx, lsa_contour* h, int32_t cols, std::vector<char>& solved) {
     const int64_t n = h->n;
     const double t0 = now_s();
-    int32_t k = 0;
     int rc = LSA_OK;
-    while (k < h->N && rc == LSA_OK) {
-        if (h->refine[(size_t)k]) {
-            ++k;
-            continue;
-        }
-        lsa_ndlu* f[kNdBatchMax];
+    shifted_run run;
+    for (int32_t k = 0; k < h->N && rc == LSA_OK;) {
+        k = shifted_sets_next_run(h->S, k, h->S->refine[0], &run);
+        if (run.J == 0) break;
         const void* bs[kNdBatchMax];
         void* xs[kNdBatchMax];
-        int32_t J = 0, q = k;
-        for (; q < h->N && J < kNdBatchMax; ++q) {
-            if (h->refine[(size_t)q]) continue;
-            if (J > 0 && !nd_batch_compatible(f[0], h->F[(size_t)q])) break;
-            f[J] = h->F[(size_t)q];
-            bs[J] = h->B;
-            xs[J] = h->XN + (size_t)q * (size_t)n * (size_t)h->L;
-            solved[(size_t)q] = 1;
-            ++J;
+        for (int32_t z = 0; z < run.J; ++z) {
+            bs[z] = h->B;
+            xs[z] = h->XN + (size_t)run.node[z] * (size_t)n * (size_t)h->L;
+            solved[(size_t)run.node[z]] = 1;
         }
         if (cols > 1) {
-            rc = ndlu_solve_multi_batch_dev(ctx, J, f, LSA_C128, cols, bs, n, xs, n);
-            h->batch_groups += f[0]->multi_passes;
+            rc = ndlu_solve_multi_batch_dev(ctx, run.J, run.f, LSA_C128, cols, bs, n, xs, n);
+            h->batch_groups += run.f[0]->multi_passes;
         } else {
-            rc = ndlu_solve_batch_dev(ctx, J, f, LSA_C128, bs, xs);
+            rc = ndlu_solve_batch_dev(ctx, run.J, run.f, LSA_C128, bs, xs);
         }
-        h->batch_columns += (int64_t)J * cols;
-        k = q;
+        h->batch_columns += (int64_t)run.J * cols;
     }
     h->sec_solve += now_s() - t0;
     return rc;
@@ -534,7 +500,7 @@ int ct_batch_check(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, const 
     const int64_t n = h->n;
     const double t0 = now_s();
     std::vector<double> s((size_t)3 * cols);
-    int rc = k_spmm(ctx, h->C[(size_t)k], cols, Xk, n, h->W1, n);
+    int rc = k_spmm(ctx, h->S->C[(size_t)k], cols, Xk, n, h->W1, n);
     if (rc == LSA_OK) rc = ct_column_sums(ctx, h, cols, h->B, h->W1, Xk, nullptr, s.data());
     *ok = rc == LSA_OK;
     for (int32_t j = 0; j < cols && *ok; ++j)
@@ -603,66 +569,6 @@ double ct_radius2(const lsa_contour* h, ci_z lam) {
 
 }  // namespace
 
-// The factor sets of a quadrature over shifts, for lsa_contour_create and lsa_stochastic_create: C[k] = A - z_k M on A's index arrays
-// and normF[k] = ||C_k||_F (the backward-error judgement's scale; sum_dev: a device double) for all nodes, then nsets <= nodes factor
-// sets F[0..nsets).  The first set takes the analysis the context holds prepared (lsa_ndlu_prepare / _prepare_tree), or analyses;
-// every further one redoes the pattern-only phase from the first one's forest: one ordering, one analysis, the bits of a
-// refactorisation.  budget > 0: LSA_ERR_OOM, with the bytes needed and the bytes available, where nsets sets (the figures of
-// lsa_ndlu_prepared_memory) exceed that fraction of the free device memory -- judged on the prepared analysis before anything is
-// factorised, else on the first set's before the second.  What was made before a failure stays in C and F for the caller to release.
-int shifted_factor_sets(lsa_ctx* ctx, const char* who, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* z, size_t nsets, double* sum_dev,
-                        double budget, lsa_mat** C, double* normF, lsa_ndlu** F) {
-    auto fits = [&](const NdSymbolic& S) {
-        int64_t out[8] = {};
-        size_t free_b = 0, total_b = 0;
-        if (nd_memory_report(S, (int32_t)sizeof(cplx), 0, out, nullptr, nullptr, nullptr) != LSA_OK || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return (int)LSA_OK;
-        const double need = (double)nsets * (double)(out[0] + out[1] + out[2] + out[4] + out[7]);
-        if (need <= budget * (double)free_b) return (int)LSA_OK;
-        return lsa_set_error(ctx, LSA_ERR_OOM, "%s: %d factor sets need %.0f bytes, %.1f of the %.0f bytes of free device memory hold %.0f; fewer nodes fit "
-                                               "(refactorising sets node by node is not built)", who, (int)nsets, need, budget, (double)free_b, budget * (double)free_b);
-    };
-    bool judged = false;
-    if (budget > 0.0 && ctx->nd_cache && ctx->nd_cache->dtype == LSA_C128 && ctx->nd_cache->S.n == A->n && ctx->nd_cache->S.nnz == A->nnz) {
-        LSA_CHECK(fits(ctx->nd_cache->S));
-        judged = true;
-    }
-    int rc = LSA_OK;
-    for (int32_t k = 0; k < nodes && rc == LSA_OK; ++k) {
-        const double one[2] = {1.0, 0.0}, mz[2] = {-z[2 * k], -z[2 * k + 1]};
-        rc = lsa_csr_axpby(ctx, A, M, one, mz, LSA_C128, &C[k]);
-        if (rc == LSA_OK) rc = k_nrm2(ctx, LSA_C128, A->nnz, C[k]->val, sum_dev);
-        double v2 = 0.0;
-        if (rc == LSA_OK && (hipMemcpyAsync(&v2, sum_dev, sizeof v2, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess))
-            rc = lsa_set_error(ctx, LSA_ERR_HIP, "%s: reading ||C||_F failed", who);
-        if (rc == LSA_OK && std::isfinite(v2)) normF[k] = std::sqrt(v2);
-    }
-    for (size_t k = 0; k < nsets && rc == LSA_OK; ++k) {
-        if (k == 0) {
-            rc = lsa_ndlu_create(ctx, C[0], 0, &F[0]);
-        } else {
-            const NdSymbolic& S = F[0]->S;
-            if (budget > 0.0 && !judged) {
-                LSA_CHECK(fits(S));
-                judged = true;
-            }
-            if (S.tree_hash != 0) {
-                std::vector<int32_t> first((size_t)S.nt), size((size_t)S.nt);
-                for (int32_t t = 0; t < S.nt; ++t) {
-                    first[(size_t)t] = S.perm[(size_t)S.node_start[(size_t)t]];
-                    size[(size_t)t] = S.node_start[(size_t)t + 1] - S.node_start[(size_t)t];
-                }
-                lsa_ndlu_drop_cache(ctx);
-                rc = lsa_ndlu_create_tree(ctx, C[k], S.nt, first.data(), size.data(), S.parent.data(), nullptr, &F[k]);
-            } else {
-                lsa_ndlu_drop_cache(ctx);
-                rc = lsa_ndlu_create(ctx, C[k], S.leaf_size, &F[k]);
-            }
-        }
-        if (rc != LSA_OK) rc = lsa_set_error(ctx, rc, "%s: node %d (z = %.6g%+.6gi): %s", who, (int)k, z[2 * k], z[2 * k + 1], std::string(ctx->err).c_str());
-    }
-    return rc;
-}
-
 extern "C" {
 
 int lsa_contour_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double centre[2], const double radii[2], int32_t subspace,
@@ -682,8 +588,6 @@ int lsa_contour_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t
     if (!(ksp_rtol > 0.0)) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_create: ksp_rtol = %.3e must be positive", ksp_rtol);
     lsa_contour* h = new lsa_contour();
     h->ctx = ctx;
-    h->A = A;
-    h->M = M;
     h->n = A->n;
     h->N = nodes;
     h->L = subspace;
@@ -693,14 +597,11 @@ int lsa_contour_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t
         h->centre[q] = centre[q];
         h->radii[q] = radii[q];
     }
-    h->refine.assign((size_t)nodes, 0);
-    h->C.assign((size_t)nodes, nullptr);
-    h->normF.assign((size_t)nodes, 0.0);
-    h->F.assign(h->keep ? (size_t)nodes : 1, nullptr);
+    std::vector<ci_z> z;
     const double pi = 3.14159265358979323846;
     for (int32_t k = 0; k < nodes; ++k) {
         const double th = 2.0 * pi * (k + 0.5) / nodes;
-        h->z.push_back(ci_z(centre[0] + radii[0] * std::cos(th), centre[1] + radii[1] * std::sin(th)));
+        z.push_back(ci_z(centre[0] + radii[0] * std::cos(th), centre[1] + radii[1] * std::sin(th)));
         h->w.push_back(ci_z(radii[1] * std::cos(th) / nodes, radii[0] * std::sin(th) / nodes));
     }
     const size_t blk = (size_t)h->n * sizeof(cplx) * (size_t)subspace, LL = (size_t)subspace * subspace * sizeof(cplx);
@@ -713,21 +614,14 @@ int lsa_contour_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t
         ct_free(h);
         return lsa_set_error(ctx, LSA_ERR_OOM, "lsa_contour_create: out of device memory (n=%d, subspace=%d)", A->n, subspace);
     }
-    h->bytes = (int64_t)(6 * blk + LL);
-    const double t0 = now_s();
-    int rc = shifted_factor_sets(ctx, "lsa_contour_create", A, M, nodes, reinterpret_cast<const double*>(h->z.data()), h->F.size(), h->sums, 0.0, h->C.data(),
-                                 h->normF.data(), h->F.data());
-    h->bytes += (int64_t)nodes * A->nnz * (int64_t)sizeof(cplx);
-    if (rc == LSA_OK) rc = ct_sync(ctx);
+    h->bytes = (int64_t)(6 * blk + LL) + (int64_t)nodes * A->nnz * (int64_t)sizeof(cplx);
+    const int rc = shifted_sets_create(ctx, "lsa_contour_create", A, M, z, h->keep ? (size_t)nodes : 1, 0.0, &h->S);
     if (rc != LSA_OK) {
-        const std::string msg = ctx->err;
         ct_free(h);
-        return lsa_set_error(ctx, rc, "%s", msg.c_str());
+        return rc;
     }
-    h->cur = 0;
-    h->st.analysis_reused = h->F[0]->seconds_analyse == 0.0 ? 1 : 0;
-    h->sec_factor = now_s() - t0;
-    h->st.seconds_factor = h->sec_factor;
+    h->st.analysis_reused = h->S->analysis_reused;
+    h->st.seconds_factor = h->S->seconds_factor;
     *out = h;
     return LSA_OK;
 }
@@ -748,7 +642,7 @@ int lsa_contour_info(const lsa_contour* h, lsa_contour_stats* out) {
     out->kept = h->keep ? 1 : 0;
     out->nodes = h->N;
     out->bytes = h->bytes;
-    out->seconds_factor = h->sec_factor;
+    out->seconds_factor = h->S->seconds_factor;
     out->seconds_solve = h->sec_solve;
     out->seconds_product = h->sec_product;
     out->seconds_gram = h->sec_gram;
@@ -812,7 +706,7 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
     for (; it < max_it; ++it) {
         // B = M Y, then the quadrature over the nodes: Q = -sum_k w_k C_k^-1 B
         double t0 = now_s();
-        LSA_CHECK(k_spmm(ctx, h->M, cols, h->Y, n, h->B, n));
+        LSA_CHECK(k_spmm(ctx, h->S->M, cols, h->Y, n, h->B, n));
         h->st.spmv_calls += cols;
         h->sec_product += now_s() - t0;
         std::vector<char> solved((size_t)h->N, 0);
@@ -845,8 +739,8 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
         LSA_CHECK(ct_orth_pass(ctx, h, h->X, r1, h->Y, &r));
         // A U, M U and the projected pencil
         t0 = now_s();
-        LSA_CHECK(k_spmm(ctx, h->A, r, h->Y, n, h->W1, n));
-        LSA_CHECK(k_spmm(ctx, h->M, r, h->Y, n, h->W2, n));
+        LSA_CHECK(k_spmm(ctx, h->S->A, r, h->Y, n, h->W1, n));
+        LSA_CHECK(k_spmm(ctx, h->S->M, r, h->Y, n, h->W2, n));
         h->st.spmv_calls += 2 * r;
         LSA_CHECK(ct_sync(ctx));
         h->sec_product += now_s() - t0;

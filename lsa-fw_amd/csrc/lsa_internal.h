@@ -276,16 +276,6 @@ int k_spmm(lsa_ctx* ctx, const lsa_mat* A, int32_t ncols, const void* X, int64_t
 // G_host (p x q column-major) = U^H W over n rows, p, q <= 128: fixed-order two-stage sums; synchronises.  U == W (one block): real diagonal
 int k_block_gram(lsa_ctx* ctx, int64_t n, int32_t p, const void* U, int64_t ldu, int32_t q, const void* W, int64_t ldw, void* G_host);
 
-// The kept factor sets of a quadrature over shifts (contour.hip; lsa_contour_create and lsa_stochastic_create): C[k] = A - z_k M on A's
-// index arrays and normF[k] = ||C_k||_F for k < nodes (z: re, im pairs; sum_dev: a device double), then nsets <= nodes exact LUs
-// F[0..nsets) on one ordering and one analysis.  budget > 0: LSA_ERR_OOM before factorising where nsets sets exceed that fraction of
-// the free device memory.  What a failed call made stays in C and F for the caller to release.
-struct lsa_ndlu;
-int shifted_factor_sets(lsa_ctx* ctx, const char* who, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* z, size_t nsets, double* sum_dev,
-                        double budget, lsa_mat** C, double* normF, lsa_ndlu** F);
-// Y[:, k] = (A - z_k M) X[:, k], k < N: A, M real on one pattern, X, Y n x N complex (ld n), z_dev N complex on the device (stochastic.hip)
-int k_shifted_spmm(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t N, const void* z_dev, const void* X, void* Y);
-
 // Z = Mh^-1 Ah for r x r complex host matrices (column-major, ld r) by LU with partial pivoting, both overwritten (dense.hip); false: singular
 bool dense_lu_solve(int32_t r, void* Mh, void* Ah);
 
@@ -414,11 +404,14 @@ struct lsa_op_parts {
 int lsa_op_get_parts(lsa_op* op, lsa_op_parts* out);
 // The library's judgement of a direct solve x of right-hand side b (res = |b - C x|): within ksp_rtol, or, after the refinement step,
 // a backward error within 1e-12 ||C||_F -- |b - C x| cannot go below eps ||C|| |x|, whatever the solver.  0: accepted (*backward says
-// by which rule), 1: again with the refinement step switched on, -1: diverged.
-inline int direct_solve_verdict(const lsa_op_parts& P, bool refine, double res, double bnorm, double xnorm, bool* backward) {
-    *backward = refine && res > P.ksp_rtol * bnorm && P.normF > 0.0 && res <= 1e-12 * P.normF * xnorm;
-    if (res <= P.ksp_rtol * bnorm || *backward) return 0;
+// by which rule), 1: again with the refinement step switched on, -1: diverged.  normF: ||C||_F (0: unknown).
+inline int direct_solve_verdict(double ksp_rtol, double normF, bool refine, double res, double bnorm, double xnorm, bool* backward) {
+    *backward = refine && res > ksp_rtol * bnorm && normF > 0.0 && res <= 1e-12 * normF * xnorm;
+    if (res <= ksp_rtol * bnorm || *backward) return 0;
     return (!refine && std::isfinite(res)) ? 1 : -1;
+}
+inline int direct_solve_verdict(const lsa_op_parts& P, bool refine, double res, double bnorm, double xnorm, bool* backward) {
+    return direct_solve_verdict(P.ksp_rtol, P.normF, refine, res, bnorm, xnorm, backward);
 }
 
 // ---- the basis of the self-adjoint outer iterations (lanczos.hip): real or complex scalars, orthonormal in a real symmetric inner

@@ -6,7 +6,7 @@
 // a REAL operator, self-adjoint and non-negative in the Q_q-semi-inner product.  So the real thick-restart Lanczos iteration of
 // lanczos.hip serves as it is -- basis, reorthogonalisation, tail, restart and Ritz vectors are an lsa_lanczos this handle owns --
 // with S as the operator behind a step (lanczos_operator), on N factor sets of C_k kept alive on one ordering and one analysis
-// (shifted_factor_sets, contour.hip: the sets lsa_contour_create keeps).  The stochastic optimals (kind 1) are the eigenvectors of
+// (shifted_sets.hip: the family lsa_contour_create keeps too).  The stochastic optimals (kind 1) are the eigenvectors of
 // S' = (1 / pi) sum_k w_k Re(C_k^-H Q_q C_k^-1 Q_f) in the Q_f-inner product: the same step with the two solves and the two weights
 // swapped.  The results are those of the quadrature operator; whether N nodes resolve the integral is the caller's to check.
 //
@@ -29,90 +29,25 @@
 // Every sum runs in a fixed order and there are no floating-point atomics: two runs give the same bits, and so do the batched and
 // the node-by-node solves of either direction (each column of lsa_ndlu_solve_batch holds lsa_ndlu_solve's bits, each of
 // lsa_ndlu_solve_batch_adjoint lsa_ndlu_solve_adjoint's, each of k_spmv_transpose_batch k_spmv_transpose's).
-//   sf_shifted_spmm_kernel   the entries of a row strided over the 8 lanes of its row group, each lane adding its entries in order;
-//                            then the xor tree over the 8 lanes (ci_spmm_kernel's order)
-//   sf_sums_kernel           the rows of a chunk (dot_chunks) strided over the 256 threads, the xor tree of the wavefront, the four
+//   sf_shifted_spmm_kernel   shifted_sets.hip
+//   sf_sums_kernel          the rows of a chunk (dot_chunks) strided over the 256 threads, the xor tree of the wavefront, the four
 //                            waves in wave order; sf_sums_finish_kernel adds the chunks strided over 64 lanes and the same tree
 //                            (tg_march_kernel / tg_log_kernel's order)
 #include <algorithm>
 #include <cmath>
 #include <complex>
 
-#include "lsa_internal.h"
-#include "nd_internal.h"
-#include "ndlu_internal.h"
+#include "shifted_sets.h"
 
 namespace {
 
 constexpr int kSfThreads = 256;   // four wavefronts of 64
-constexpr int kSfRowLanes = 8;    // lanes that share a row of sf_shifted_spmm_kernel
-constexpr int kSfColTile = 16;    // columns whose accumulators a lane holds at once: 16 x 16 bytes
 constexpr int kSfEvents = 7;      // the boundaries of a step's six phases
 
 __device__ __forceinline__ double sf_wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
-}
-
-// Y[:, k] = (A - z_k M) X[:, k], k < N.  Row r belongs to the 8 lanes 8 (r % 32) .. of workgroup r / 32; lane s takes the entries
-// rp[r] + s, rp[r] + s + 8, ...: one load of the column index and of the two real values per entry serves a pass of up to 16 columns
-// (all 16 entries of that row of X requested before the first multiply-add of a full pass); N > 16 takes further passes inside the
-// launch.  c = a - z m is formed per column in registers: Re c = fma(-Re z, m, a), Im c = -(Im z) m.  Rows beyond n take an empty
-// range, so that every lane of a wavefront reaches the shuffles.
-__global__ __launch_bounds__(kSfThreads) void sf_shifted_spmm_kernel(int32_t n, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                                                     const double* __restrict__ a, const double* __restrict__ m, int N,
-                                                                     const cplx* __restrict__ z, const cplx* __restrict__ X, int64_t ldx,
-                                                                     cplx* __restrict__ Y, int64_t ldy) {
-    const int sub = threadIdx.x & (kSfRowLanes - 1);
-    const int64_t row = (int64_t)blockIdx.x * (kSfThreads / kSfRowLanes) + (threadIdx.x / kSfRowLanes);
-    int32_t p0 = 0, p1 = 0;
-    if (row < n) {
-        p0 = rp[row];
-        p1 = rp[row + 1];
-    }
-    for (int k0 = 0; k0 < N; k0 += kSfColTile) {
-        const int nc = (N - k0 < kSfColTile) ? N - k0 : kSfColTile;
-        cplx zz[kSfColTile], acc[kSfColTile];
-#pragma unroll
-        for (int u = 0; u < kSfColTile; ++u) {
-            zz[u] = (u < nc) ? rz_ld(z + k0 + u) : cplx{0.0, 0.0};
-            acc[u] = cplx{0.0, 0.0};
-        }
-        const cplx* Xt = X + (int64_t)k0 * ldx;
-        if (nc == kSfColTile) {
-            for (int32_t p = p0 + sub; p < p1; p += kSfRowLanes) {
-                const cplx* x = Xt + ci[p];
-                const double av = a[p], mv = m[p];
-                cplx xv[kSfColTile];
-#pragma unroll
-                for (int u = 0; u < kSfColTile; ++u) xv[u] = rz_ld(x + (int64_t)u * ldx);
-#pragma unroll
-                for (int u = 0; u < kSfColTile; ++u) fma_acc(acc[u], cplx{fma(-zz[u].re, mv, av), -(zz[u].im * mv)}, xv[u]);
-            }
-        } else {
-            for (int32_t p = p0 + sub; p < p1; p += kSfRowLanes) {
-                const cplx* x = Xt + ci[p];
-                const double av = a[p], mv = m[p];
-#pragma unroll
-                for (int u = 0; u < kSfColTile; ++u)
-                    if (u < nc) fma_acc(acc[u], cplx{fma(-zz[u].re, mv, av), -(zz[u].im * mv)}, rz_ld(x + (int64_t)u * ldx));
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kSfColTile; ++u) {
-#pragma unroll
-            for (int off = kSfRowLanes / 2; off >= 1; off >>= 1) {
-                acc[u].re += __shfl_xor(acc[u].re, off, 64);
-                acc[u].im += __shfl_xor(acc[u].im, off, 64);
-            }
-        }
-        if (sub == 0 && row < n) {
-#pragma unroll
-            for (int u = 0; u < kSfColTile; ++u)
-                if (u < nc) rz_st(Y + row + (int64_t)(k0 + u) * ldy, acc[u]);
-        }
-    }
 }
 
 // The sums of all 2N solves of a step over the rows of one chunk: workgroup (chunk, s) writes part[(4 s + q) nchunks + chunk],
@@ -200,49 +135,37 @@ int sf_grid(lsa_ctx* ctx, int64_t n, int per_cu) {
 
 }  // namespace
 
-int k_shifted_spmm(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t N, const void* z_dev, const void* X, void* Y) {
-    if (A->n < 1 || N < 1) return LSA_OK;
-    const int per_block = kSfThreads / kSfRowLanes;
-    hipLaunchKernelGGL(sf_shifted_spmm_kernel, dim3((A->n + per_block - 1) / per_block), dim3(kSfThreads), 0, ctx->stream, A->n, A->rp, A->ci,
-                       (const double*)A->val, (const double*)M->val, N, (const cplx*)z_dev, (const cplx*)X, (int64_t)A->n, (cplx*)Y, (int64_t)A->n);
-    return lsa_check_launch(ctx, "sf_shifted_spmm_kernel");
-}
-
 typedef std::complex<double> sf_z;
 
 struct lsa_stochastic {
     lsa_ctx* ctx = nullptr;
-    const lsa_mat *A = nullptr, *M = nullptr;
     int64_t n = 0;
     int32_t N = 0, ncv = 0, kind = 0;
     double ksp_rtol = 0.0;
-    std::vector<sf_z> z;             // the nodes
     std::vector<double> c;           // w_k / pi
-    std::vector<lsa_mat*> C;         // C_k = A - z_k M (values only: A's index arrays)
-    std::vector<double> normF;       // ||C_k||_F
-    std::vector<lsa_ndlu*> F;        // N factor sets, kept
+    // the pencils C_k = A - z_k M at the nodes, all N factor sets alive; refine[dir][k]: node k's solves of that direction carry the
+    // refinement step
+    shifted_sets* S = nullptr;
     const lsa_mat *Qf = nullptr, *Qq = nullptr;  // the weights (lsa_stochastic_set_weights; borrowed): both are M on a new handle
     lsa_stats st{};
     lsa_op_parts P{};                // what the basis reads of an operator: n, the inner product's matrix, st
     lsa_lanczos* lz = nullptr;       // the real basis and everything of a step but its operator
     lanczos_operator hook{};
-    cplx* zdev = nullptr;            // the N nodes
     double* cdev = nullptr;          // the N coefficients w_k / pi
     // the step's vectors: the widened right-hand side; n x N blocks of the first solutions, their check products, the weighted first
     // solutions, the second solutions and their check products; a residual and a correction for refinement steps
     cplx *b = nullptr, *X1 = nullptr, *Z1 = nullptr, *TM = nullptr, *X2 = nullptr, *Z2 = nullptr, *r = nullptr, *d = nullptr;
-    double *part = nullptr, *log = nullptr, *rnorms = nullptr, *sum1 = nullptr;
+    double *part = nullptr, *log = nullptr, *rnorms = nullptr;
     double* hlog = nullptr;          // pinned host copy of the log
     double *vdev = nullptr, *rhsdev = nullptr, *ydev = nullptr;  // lsa_stochastic_apply's vector, Q v and S v
     hipEvent_t ev[kSfEvents] = {};
     bool timed = false;              // the events of a queued step have not been read yet
-    // refine[dir][k]: node k's solves of that direction (0 forward, 1 adjoint) carry the refinement step; used: what the step being judged was queued with
-    std::vector<char> refine[2], used[2];
+    std::vector<char> used[2];       // the family's refinement flags (or all ones: force_refine) the step being judged was queued with
     bool force_refine = false, batch_forward = false, batch_adjoint = false;
     int64_t solves_adj = 0, solves_fwd = 0, refined_adj = 0, refined_fwd = 0;
     int64_t adjoint_batches = 0, forward_batches = 0;  // grouped calls of the batched sweeps with more than one set
     int64_t bytes = 0;
-    double sec_factor = 0.0, sec_solve = 0.0, sec_product = 0.0, sec_dense = 0.0;
+    double sec_solve = 0.0, sec_product = 0.0, sec_dense = 0.0;
     double sec_solve_adj = 0.0, sec_product_adj = 0.0;  // the adjoint solves' share of sec_solve, their check products' of sec_product
 };
 
@@ -250,12 +173,9 @@ namespace {
 
 void sf_free(lsa_stochastic* h) {
     if (h->lz) lsa_lanczos_destroy(h->lz);
-    for (lsa_ndlu* f : h->F)
-        if (f) lsa_ndlu_destroy(f);
-    for (lsa_mat* c : h->C)
-        if (c) lsa_mat_destroy(c);
-    for (void* p : {(void*)h->zdev, (void*)h->cdev, (void*)h->b, (void*)h->X1, (void*)h->Z1, (void*)h->TM, (void*)h->X2, (void*)h->Z2, (void*)h->r, (void*)h->d,
-                    (void*)h->part, (void*)h->log, (void*)h->rnorms, (void*)h->sum1, (void*)h->vdev, (void*)h->rhsdev, (void*)h->ydev})
+    shifted_sets_free(h->S);
+    for (void* p : {(void*)h->cdev, (void*)h->b, (void*)h->X1, (void*)h->Z1, (void*)h->TM, (void*)h->X2, (void*)h->Z2, (void*)h->r, (void*)h->d,
+                    (void*)h->part, (void*)h->log, (void*)h->rnorms, (void*)h->vdev, (void*)h->rhsdev, (void*)h->ydev})
         if (p) (void)hipFree(p);
     if (h->hlog) (void)hipHostFree(h->hlog);
     for (hipEvent_t e : h->ev)
@@ -269,11 +189,11 @@ const lsa_mat* sf_inner(const lsa_stochastic* h) { return h->kind == 0 ? h->Qq :
 const lsa_mat* sf_middle(const lsa_stochastic* h) { return h->kind == 0 ? h->Qf : h->Qq; }
 
 int sf_sweeps(lsa_ctx* ctx, lsa_stochastic* h, int32_t k, bool adjoint, const cplx* b, cplx* x) {
-    return adjoint ? ndlu_solve_adjoint_dev(ctx, h->F[(size_t)k], 1, LSA_C128, b, x) : ndlu_solve_dev(ctx, h->F[(size_t)k], LSA_C128, b, x);
+    return adjoint ? ndlu_solve_adjoint_dev(ctx, h->S->F[(size_t)k], 1, LSA_C128, b, x) : ndlu_solve_dev(ctx, h->S->F[(size_t)k], LSA_C128, b, x);
 }
 
 int sf_times_c(lsa_ctx* ctx, lsa_stochastic* h, int32_t k, bool adjoint, const cplx* x, cplx* y) {
-    return adjoint ? k_spmv_transpose(ctx, h->C[(size_t)k], 1, LSA_C128, x, y) : k_spmv(ctx, h->C[(size_t)k], LSA_C128, x, y);
+    return adjoint ? k_spmv_transpose(ctx, h->S->C[(size_t)k], 1, LSA_C128, x, y) : k_spmv(ctx, h->S->C[(size_t)k], LSA_C128, x, y);
 }
 
 // X[:, k] = C_k^-1 B_k (adjoint: C_k^-H) for all nodes, B_k = B + k ldb (ldb = 0: one right-hand side for all).  Under the
@@ -285,32 +205,23 @@ int sf_solve_all(lsa_ctx* ctx, lsa_stochastic* h, bool adjoint, const cplx* B, i
     const std::vector<char>& ref = h->used[adjoint ? 1 : 0];
     std::vector<char> done((size_t)h->N, 0);
     if (adjoint ? h->batch_adjoint : h->batch_forward) {
-        int32_t k = 0;
-        while (k < h->N) {
-            if (ref[(size_t)k]) {
-                ++k;
-                continue;
-            }
-            lsa_ndlu* f[kNdBatchMax];
+        shifted_run run;
+        for (int32_t k = 0; k < h->N;) {
+            k = shifted_sets_next_run(h->S, k, ref, &run);
+            if (run.J == 0) break;
             const void* bs[kNdBatchMax];
             void* xs[kNdBatchMax];
-            int32_t J = 0, q = k;
-            for (; q < h->N && J < kNdBatchMax; ++q) {
-                if (ref[(size_t)q]) continue;
-                if (J > 0 && !nd_batch_compatible(f[0], h->F[(size_t)q])) break;
-                f[J] = h->F[(size_t)q];
-                bs[J] = B + (size_t)q * (size_t)ldb;
-                xs[J] = X + (size_t)q * (size_t)n;
-                done[(size_t)q] = 1;
-                ++J;
+            for (int32_t z = 0; z < run.J; ++z) {
+                bs[z] = B + (size_t)run.node[z] * (size_t)ldb;
+                xs[z] = X + (size_t)run.node[z] * (size_t)n;
+                done[(size_t)run.node[z]] = 1;
             }
-            if (J > 1) {
-                LSA_CHECK(adjoint ? ndlu_solve_batch_adjoint_dev(ctx, J, f, 1, LSA_C128, bs, xs) : ndlu_solve_batch_dev(ctx, J, f, LSA_C128, bs, xs));
+            if (run.J > 1) {
+                LSA_CHECK(adjoint ? ndlu_solve_batch_adjoint_dev(ctx, run.J, run.f, 1, LSA_C128, bs, xs) : ndlu_solve_batch_dev(ctx, run.J, run.f, LSA_C128, bs, xs));
                 ++(adjoint ? h->adjoint_batches : h->forward_batches);
             } else {
-                LSA_CHECK(adjoint ? ndlu_solve_adjoint_dev(ctx, f[0], 1, LSA_C128, bs[0], xs[0]) : ndlu_solve_dev(ctx, f[0], LSA_C128, bs[0], xs[0]));
+                LSA_CHECK(adjoint ? ndlu_solve_adjoint_dev(ctx, run.f[0], 1, LSA_C128, bs[0], xs[0]) : ndlu_solve_dev(ctx, run.f[0], LSA_C128, bs[0], xs[0]));
             }
-            k = q;
         }
     }
     const double one[2] = {1.0, 0.0};
@@ -330,7 +241,7 @@ int sf_solve_all(lsa_ctx* ctx, lsa_stochastic* h, bool adjoint, const cplx* B, i
 // Z[:, k] = C_k X[:, k] for all nodes in one launch, or C_k^H X[:, k] node by node -- under set_batch_adjoint in groups of
 // kNdBatchMax nodes per launch (the C_k are built on A's index arrays: one transposed index serves them all)
 int sf_check_products(lsa_ctx* ctx, lsa_stochastic* h, bool adjoint, const cplx* X, cplx* Z) {
-    if (!adjoint) return k_shifted_spmm(ctx, h->A, h->M, h->N, h->zdev, X, Z);
+    if (!adjoint) return k_shifted_spmm(ctx, h->S->A, h->S->M, h->N, h->S->zdev, X, Z);
     const size_t n = (size_t)h->n;
     if (!h->batch_adjoint) {
         for (int32_t k = 0; k < h->N; ++k) LSA_CHECK(sf_times_c(ctx, h, k, true, X + (size_t)k * n, Z + (size_t)k * n));
@@ -344,7 +255,7 @@ int sf_check_products(lsa_ctx* ctx, lsa_stochastic* h, bool adjoint, const cplx*
             xs[z] = X + (size_t)(k0 + z) * n;
             zs[z] = Z + (size_t)(k0 + z) * n;
         }
-        LSA_CHECK(k_spmv_transpose_batch(ctx, J, h->C.data() + k0, 1, LSA_C128, xs, zs));
+        LSA_CHECK(k_spmv_transpose_batch(ctx, J, h->S->C.data() + k0, 1, LSA_C128, xs, zs));
     }
     return LSA_OK;
 }
@@ -354,7 +265,7 @@ int sf_enqueue(lsa_ctx* ctx, lsa_stochastic* h, const double* rhs, double* w) {
     const int64_t n = h->n;
     const int32_t N = h->N;
     for (int dir = 0; dir < 2; ++dir) {
-        h->used[dir] = h->refine[dir];
+        h->used[dir] = h->S->refine[dir];
         if (h->force_refine) h->used[dir].assign((size_t)N, 1);
     }
     const bool first_adj = sf_adjoint(h, 0), second_adj = sf_adjoint(h, 1);
@@ -420,17 +331,15 @@ int sf_judge(lsa_ctx* ctx, lsa_stochastic* h, const char* who, const char* what,
         const double* e = h->hlog + (size_t)4 * (size_t)s;
         One& o = sv[(size_t)s];
         o = One{h->used[adj ? 1 : 0][(size_t)k] != 0, false, std::sqrt(e[0]), std::sqrt(e[1])};
-        lsa_op_parts P = h->P;
-        P.normF = h->normF[(size_t)k];
-        const int v = direct_solve_verdict(P, o.refine, o.res, o.bnorm, std::sqrt(e[2]), &o.backward);
+        const int v = shifted_sets_verdict(h->S, k, h->ksp_rtol, o.refine, o.res, o.bnorm, std::sqrt(e[2]), &o.backward);
         if (v < 0) {
             lsa_set_error(ctx, LSA_ERR_DIVERGED, "%s: the %s solve of node %d (z = %.6g%+.6gi) of %s %d left a relative residual of %.3e%s (ksp_rtol %.1e)%s", who,
-                          adj ? "adjoint" : "forward", k, h->z[(size_t)k].real(), h->z[(size_t)k].imag(), what, where, o.bnorm > 0.0 ? o.res / o.bnorm : o.res,
+                          adj ? "adjoint" : "forward", k, h->S->z[(size_t)k].real(), h->S->z[(size_t)k].imag(), what, where, o.bnorm > 0.0 ? o.res / o.bnorm : o.res,
                           o.refine ? " after its refinement step" : ", which is not finite", h->ksp_rtol, o.refine ? " and a backward error above 1e-12 ||C||_F" : "");
             return -1;
         }
         if (v > 0) {
-            h->refine[adj ? 1 : 0][(size_t)k] = 1;
+            h->S->refine[adj ? 1 : 0][(size_t)k] = 1;
             worst = 1;
         }
     }
@@ -461,13 +370,6 @@ int sf_hook_enqueue(lsa_ctx* ctx, void* self, int32_t, const void* rhs, void* w,
 int sf_hook_read_back(lsa_ctx* ctx, void* self) { return sf_read_back(ctx, (lsa_stochastic*)self); }
 
 int sf_hook_judge(lsa_ctx* ctx, void* self, int32_t j, const lanczos_sums*) { return sf_judge(ctx, (lsa_stochastic*)self, "lsa_stochastic_solve", "step", j); }
-
-bool sf_same_pattern(const lsa_mat* A, const lsa_mat* M) {
-    if (M->n != A->n || M->ncols != A->ncols || M->nnz != A->nnz) return false;
-    if (A->rp == M->rp && A->ci == M->ci) return true;
-    if (A->h_rp.size() > 0 && M->h_rp.size() > 0 && A->h_ci.size() > 0 && M->h_ci.size() > 0) return A->h_rp == M->h_rp && A->h_ci == M->h_ci;
-    return true;
-}
 
 }  // namespace
 
@@ -509,28 +411,6 @@ int stochastic_ritz_vectors(lsa_ctx* ctx, lsa_stochastic* h, int32_t m, int32_t 
 
 extern "C" {
 
-int lsa_shifted_spmm(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* shifts, const lsa_vec* X, lsa_vec* Y) {
-    if (!ctx || !A || !M || !shifts || !X || !Y) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: null argument");
-    if (A->n != A->ncols || A->row0 != 0) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: A is a row shard (%d x %d): whole square matrices only", A->n, A->ncols);
-    if (A->dtype != LSA_F64 || M->dtype != LSA_F64) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: A or M is complex: real matrices only");
-    if (!sf_same_pattern(A, M)) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: A and M do not share one pattern");
-    if (nodes < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: %d columns", nodes);
-    if (X->dtype != LSA_C128 || Y->dtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: the blocks must be complex128");
-    if (X->d == Y->d) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: X and Y must not alias");
-    const int64_t need = (int64_t)A->n * nodes;
-    if (X->n < need || Y->n < need)
-        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: blocks of %d columns of %d rows do not fit vectors of %lld and %lld entries", nodes, A->n,
-                             (long long)X->n, (long long)Y->n);
-    cplx* zdev = nullptr;
-    LSA_HIP_ALLOC(ctx, hipMalloc((void**)&zdev, (size_t)nodes * sizeof(cplx)));
-    int rc = LSA_OK;
-    if (hipMemcpy(zdev, shifts, (size_t)nodes * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess) rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_shifted_spmm: the upload of the shifts failed");
-    if (rc == LSA_OK) rc = k_shifted_spmm(ctx, A, M, nodes, zdev, X->d, Y->d);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == LSA_OK) rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_shifted_spmm: the kernel failed");
-    (void)hipFree(zdev);
-    return rc;
-}
-
 int lsa_stochastic_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* shifts, const double* weights, int32_t ncv,
                           double ksp_rtol, lsa_stochastic** out) {
     if (!ctx || !A || !out || !shifts || !weights) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_stochastic_create: null argument");
@@ -552,25 +432,18 @@ int lsa_stochastic_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int3
     }
     lsa_stochastic* h = new lsa_stochastic();
     h->ctx = ctx;
-    h->A = A;
-    h->M = M;
     h->n = A->n;
     h->N = nodes;
     h->ncv = ncv;
     h->ksp_rtol = ksp_rtol;
     h->Qf = h->Qq = M;
+    std::vector<sf_z> z;
     const double pi = 3.14159265358979323846;
     for (int32_t k = 0; k < nodes; ++k) {
-        h->z.push_back(sf_z(shifts[2 * k], shifts[2 * k + 1]));
+        z.push_back(sf_z(shifts[2 * k], shifts[2 * k + 1]));
         h->c.push_back(weights[k] / pi);
     }
-    h->C.assign((size_t)nodes, nullptr);
-    h->F.assign((size_t)nodes, nullptr);
-    h->normF.assign((size_t)nodes, 0.0);
-    for (int dir = 0; dir < 2; ++dir) {
-        h->refine[dir].assign((size_t)nodes, 0);
-        h->used[dir].assign((size_t)nodes, 0);
-    }
+    for (int dir = 0; dir < 2; ++dir) h->used[dir].assign((size_t)nodes, 0);
     h->P.n = h->n;
     h->P.Kmul = M;
     h->P.ksp_rtol = ksp_rtol;
@@ -583,13 +456,12 @@ int lsa_stochastic_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int3
     for (cplx** p : {&h->b, &h->r, &h->d}) ok = ok && hipMalloc((void**)p, vb) == hipSuccess;
     for (cplx** p : {&h->X1, &h->Z1, &h->TM, &h->X2, &h->Z2}) ok = ok && hipMalloc((void**)p, blk) == hipSuccess;
     for (double** p : {&h->vdev, &h->rhsdev, &h->ydev}) ok = ok && hipMalloc((void**)p, vb / 2) == hipSuccess;
-    ok = ok && hipMalloc((void**)&h->zdev, (size_t)nodes * sizeof(cplx)) == hipSuccess && hipMalloc((void**)&h->cdev, (size_t)nodes * sizeof(double)) == hipSuccess &&
+    ok = ok && hipMalloc((void**)&h->cdev, (size_t)nodes * sizeof(double)) == hipSuccess &&
          hipMalloc((void**)&h->part, (size_t)8 * (size_t)nodes * (size_t)nchunks * sizeof(double)) == hipSuccess &&
          hipMalloc((void**)&h->log, (size_t)8 * (size_t)nodes * sizeof(double)) == hipSuccess && hipMalloc((void**)&h->rnorms, 2 * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&h->sum1, sizeof(double)) == hipSuccess && hipHostMalloc((void**)&h->hlog, (size_t)8 * (size_t)nodes * sizeof(double)) == hipSuccess;
+         hipHostMalloc((void**)&h->hlog, (size_t)8 * (size_t)nodes * sizeof(double)) == hipSuccess;
     for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    ok = ok && hipMemcpy(h->zdev, h->z.data(), (size_t)nodes * sizeof(cplx), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(h->cdev, h->c.data(), (size_t)nodes * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+    ok = ok && hipMemcpy(h->cdev, h->c.data(), (size_t)nodes * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemset(h->log, 0, (size_t)8 * (size_t)nodes * sizeof(double)) == hipSuccess;  // (a start vector's read-back copies it before any step)
     if (!ok) {
         (void)hipGetLastError();
@@ -597,10 +469,8 @@ int lsa_stochastic_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int3
         return lsa_set_error(ctx, LSA_ERR_OOM, "lsa_stochastic_create: out of device memory (n=%d, nodes=%d)", A->n, nodes);
     }
     h->bytes = (int64_t)(3 * vb + 5 * blk + 3 * (vb / 2)) + (int64_t)nodes * A->nnz * (int64_t)sizeof(cplx) + (int64_t)2 * 8 * h->n * (ncv + 1);
+    int rc = shifted_sets_create(ctx, "lsa_stochastic_create", A, M, z, (size_t)nodes, 0.8, &h->S);
     const double t0 = now_s();
-    int rc = shifted_factor_sets(ctx, "lsa_stochastic_create", A, M, nodes, reinterpret_cast<const double*>(h->z.data()), (size_t)nodes, h->sum1, 0.8, h->C.data(),
-                                 h->normF.data(), h->F.data());
-    if (rc == LSA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_stochastic_create: the factorisations failed");
     if (rc == LSA_OK) rc = lanczos_create_basis_on(ctx, nullptr, h->P, ncv, LSA_F64, "lsa_stochastic", &h->lz);
     if (rc == LSA_OK) {
         h->hook = lanczos_operator{h, 1, sf_hook_enqueue, sf_hook_read_back, sf_hook_judge};
@@ -611,12 +481,10 @@ int lsa_stochastic_create(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int3
         sf_free(h);
         return lsa_set_error(ctx, rc, "%s", msg.c_str());
     }
-    int64_t mem[8] = {};
-    if (nd_memory_report(h->F[0]->S, (int32_t)sizeof(cplx), 0, mem, nullptr, nullptr, nullptr) == LSA_OK)
-        h->bytes += (int64_t)nodes * (mem[0] + mem[1] + mem[2] + mem[4] + mem[7]);
-    h->st.analysis_reused = h->F[0]->seconds_analyse == 0.0 ? 1 : 0;
-    h->sec_factor = now_s() - t0;
-    h->st.seconds_factor = h->sec_factor;
+    h->bytes += (int64_t)nodes * std::max<int64_t>(shifted_sets_bytes_per_set(h->S->F[0]->S), 0);
+    h->st.analysis_reused = h->S->analysis_reused;
+    h->S->seconds_factor += now_s() - t0;  // (this handle's figure counts its basis in)
+    h->st.seconds_factor = h->S->seconds_factor;
     *out = h;
     return LSA_OK;
 }
@@ -645,12 +513,12 @@ int lsa_stochastic_set_weights(lsa_ctx* ctx, lsa_stochastic* h, const lsa_mat* Q
             return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_stochastic_set_weights: the %s weight is %d x %d (from row %d), the problem has size %lld", which, Q->n,
                                  Q->ncols, Q->row0, (long long)h->n);
     }
-    h->Qf = Qf ? Qf : h->M;
-    h->Qq = Qq ? Qq : h->M;
+    h->Qf = Qf ? Qf : h->S->M;
+    h->Qq = Qq ? Qq : h->S->M;
     // other inner products begin as a new handle does: no right-hand side is left over (the basis forgets it), the refinement steps
     // are off again, and a start vector must follow (the basis in hand is orthonormal in the old weight)
     lanczos_set_inner_product(h->lz, sf_inner(h));
-    for (int dir = 0; dir < 2; ++dir) h->refine[dir].assign((size_t)h->N, 0);
+    for (int dir = 0; dir < 2; ++dir) h->S->refine[dir].assign((size_t)h->N, 0);
     return LSA_OK;
 }
 
@@ -659,7 +527,7 @@ int lsa_stochastic_set_kind(lsa_ctx* ctx, lsa_stochastic* h, int32_t kind) {
     if (kind != 0 && kind != 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_stochastic_set_kind: kind = %d is neither 0 (EOFs) nor 1 (stochastic optimals)", kind);
     h->kind = kind;
     lanczos_set_inner_product(h->lz, sf_inner(h));
-    for (int dir = 0; dir < 2; ++dir) h->refine[dir].assign((size_t)h->N, 0);
+    for (int dir = 0; dir < 2; ++dir) h->S->refine[dir].assign((size_t)h->N, 0);
     return LSA_OK;
 }
 
@@ -707,7 +575,7 @@ int lsa_stochastic_info(const lsa_stochastic* h, lsa_stochastic_stats* out) {
     out->nodes = h->N;
     out->kind = h->kind;
     out->bytes = h->bytes;
-    out->seconds_factor = h->sec_factor;
+    out->seconds_factor = h->S->seconds_factor;
     out->seconds_solve = h->sec_solve;
     out->seconds_product = h->sec_product;
     out->seconds_dense = h->sec_dense;
