@@ -275,7 +275,8 @@ int lsa_ndlu_multi_info(const lsa_ndlu *f, int32_t *width, int64_t *extra_bytes,
  * factorisations (one analysis, one rank, no distributed node, vectors of one dtype) and those of lsa_ndlu_solve_multi for the
  * blocks, which share ldb and ldx (ld >= n, each vector at least ld (nrhs - 1) + n long, complex factors need complex vectors).
  * B[z] == X[z] with ldb == ldx solves in place; several sets may read ONE B (the region eigensolver's case); two sets sharing a
- * factorisation or an X, or any other overlap: LSA_ERR_ARG.  trans must be 0: the transposed form is not built (LSA_ERR_ARG).
+ * factorisation or an X, or any other overlap: LSA_ERR_ARG.  trans must be 0 (LSA_ERR_ARG otherwise): the transposed form is an
+ * entry of its own, lsa_ndlu_solve_multi_batch_adjoint.
  * Column q of set z holds exactly the bits lsa_ndlu_solve(f[z], .) gives for it.  The pass width is the smallest every set has
  * sweep buffers for; a last single column goes through the sweeps of lsa_ndlu_solve_batch, and nrhs = 1 is that call. */
 int lsa_ndlu_solve_multi_batch(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, int trans, int32_t nrhs, const lsa_vec *const *B, int64_t ldb,
@@ -284,6 +285,20 @@ int lsa_ndlu_solve_multi_batch(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, int 
  * block solve of all J sets */
 int lsa_ndlu_solve_multi_batch_time(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, int trans, int32_t nrhs, const lsa_vec *const *B,
                                     int64_t ldb, lsa_vec *const *X, int64_t ldx, int iters, double *avg_ms);
+/* X[z][:, q] = C_z^-T B[z][:, q] (conj = 0) or C_z^-H B[z][:, q] (conj != 0), z < J <= 16, q < nrhs: the transposed block solve on J
+ * factorisations of one analysis, every launch of the transposed sweeps carrying all columns of a pass for all J of them -- what a
+ * left (adjoint) phase of the region eigensolver needs on the factor sets of its nodes.  The rules are those of
+ * lsa_ndlu_solve_multi_batch, word for word: one analysis, one rank, no distributed node, vectors of one dtype; the blocks share ldb
+ * and ldx; several sets may read ONE B; B[z] == X[z] with ldb == ldx solves in place; two sets sharing a factorisation or an X, or
+ * any other overlap: LSA_ERR_ARG, X untouched.  Passes of 8, 4 or 2 real or 4 or 2 complex columns, the widest every set has sweep
+ * buffers for; a last single column goes through the sweeps of lsa_ndlu_solve_batch_adjoint, and nrhs = 1 is that call.  Column q of
+ * set z holds exactly the bits lsa_ndlu_solve_adjoint(f[z], conj, .) gives for it.  Independent of lsa_ndlu_set_multi_transposed
+ * (that switch belongs to lsa_ndlu_solve_multi). */
+int lsa_ndlu_solve_multi_batch_adjoint(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, int conj, int32_t nrhs, const lsa_vec *const *B,
+                                       int64_t ldb, lsa_vec *const *X, int64_t ldx);
+/* `iters` such block solves back to back (every B[z] apart from every X[z]), timed as lsa_ndlu_solve_multi_batch_time */
+int lsa_ndlu_solve_multi_batch_adjoint_time(lsa_ctx *ctx, int32_t J, lsa_ndlu *const *f, int conj, int32_t nrhs, const lsa_vec *const *B,
+                                            int64_t ldb, lsa_vec *const *X, int64_t ldx, int iters, double *avg_ms);
 /* Inertia (numbers of negative, zero, positive eigenvalues) of a REAL SYMMETRIC C from its factorisation: what SLEPc's spectrum
  * slicing takes from the symmetric-indefinite factorisation behind EPS.setInterval / EPS_ALL (Solver/utils.py:248-254: the
  * number of eigenvalues of a definite pencil below sigma is the number of negative eigenvalues of A - sigma M).  Sum over the
@@ -653,11 +668,32 @@ int lsa_growth_solve(lsa_ctx *ctx, lsa_growth *g, const lsa_ks_options *opts, co
  * apart.  Every pass of up to 8 columns reads A's indices and values once.  The sums are not in lsa_spmv's order: column c need not
  * hold lsa_spmv's bits. */
 int lsa_spmm(lsa_ctx *ctx, const lsa_mat *A, int32_t ncols, const lsa_vec *X, int64_t ldx, lsa_vec *Y, int64_t ldy);
+/* Y[:, 0:ncols] = A^T X[:, 0:ncols] (conj = 0) or A^H X[:, 0:ncols] (conj != 0): MatTransposeMatMult on a dense block, under the block
+ * rules of lsa_spmm.  It runs in pull form on the transposed index the matrices of one pattern share (built by the first transposed
+ * product): no atomics, every output's entries added in a fixed order, every pass of up to 8 columns reading the index and the values
+ * once.  Like lsa_spmm it need not reproduce lsa_spmv_transpose's bits. */
+int lsa_spmm_transpose(lsa_ctx *ctx, const lsa_mat *A, int conj, int32_t ncols, const lsa_vec *X, int64_t ldx, lsa_vec *Y, int64_t ldy);
 /* G = U^H W over the first n rows: U has p columns, W has q, 1 <= p, q <= 128; G is the caller's p x q column-major complex host
  * array.  Per-workgroup partial sums, then one finishing pass in chunk order; synchronises.  U and W one and the same block
  * (same vector, ld and column count): the diagonal is returned exactly real. */
 int lsa_block_gram(lsa_ctx *ctx, int64_t n, int32_t p, const lsa_vec *U, int64_t ldu, int32_t q, const lsa_vec *W, int64_t ldw, void *G);
 typedef struct lsa_contour lsa_contour;
+/* what the left phases of a handle did, booked apart from lsa_contour_info / lsa_contour_batch_info (which a left phase leaves as they were) */
+typedef struct {
+    int32_t solves;            /* lsa_contour_solve_left calls so far                                                     */
+    int32_t iterations;        /* their iterations                                                                        */
+    int64_t block_solves;      /* column solves with C_k^H accepted                                                       */
+    int64_t refined_solves;    /* ... of them with the refinement step                                                    */
+    int64_t backward_accepted; /* ... accepted on the backward error                                                      */
+    int64_t groups;            /* as lsa_contour_batch_stats, the left phases only                                        */
+    int64_t batched_columns;
+    int64_t serial_columns;
+    double seconds_factor;     /* refactorisations during the left phases (one set refactorised node by node)            */
+    double seconds_solve;
+    double seconds_product;
+    double seconds_gram;
+    double seconds_dense;
+} lsa_contour_left_stats;
 typedef struct {
     int32_t iterations;        /* iterations run                                                                          */
     int32_t rank;              /* columns of the last orthonormal basis (<= subspace)                                     */
@@ -719,6 +755,19 @@ typedef struct {
     int64_t serial_columns;    /* column solves done node by node (repeated ones of a fall-back included)                  */
 } lsa_contour_batch_stats;
 int lsa_contour_batch_info(const lsa_contour *h, lsa_contour_batch_stats *out);
+/* The left phase on the same handle and the same factor sets: the iteration of lsa_contour_solve on the adjoint pencil (A^H, M^H),
+ * whose node matrices on the conjugate contour are C_k^H -- no factorisation, no analysis, no new device memory.  One iteration on the
+ * block Y: B = M^H Y (lsa_spmm_transpose's kernel); Q = -sum_k conj(w_k) C_k^-H B (the transposed block sweeps; under
+ * lsa_contour_set_batch_nodes runs of up to 16 sets through those of lsa_ndlu_solve_multi_batch_adjoint); U = Q orthonormalised
+ * twice; Ritz pairs (mu, s) of (U^H A^H U, U^H M^H U), residual ||A^H w - mu M^H w|| / (||A^H w|| + |mu| ||M^H w||), inside when
+ * conj(mu) lies in the ellipse.  Every column solve is checked against C_k^H x as the right phase checks against C_k x, with the
+ * nodes' adjoint refinement flags.  Stopping rule, `complete`, `estimate`, counters, output order and canonical phase are those of
+ * lsa_contour_solve; lam_out holds lambda = conj(mu), the values in the caller's region, W_out the left eigenvectors
+ * (w^H A = lambda w^H M).  Kept, refactorised and lockstep factor sets return the same bytes.  The handle's own books
+ * (lsa_contour_info, lsa_contour_batch_info) are left as they were: the left phases' go to lsa_contour_left_info. */
+int lsa_contour_solve_left(lsa_ctx *ctx, lsa_contour *h, double tol, int32_t max_it, const void *Y0_host, int32_t max_out, void *lam_out,
+                           void *W_out, double *res_out, lsa_contour_result *result);
+int lsa_contour_left_info(const lsa_contour *h, lsa_contour_left_stats *out);
 
 /* ---- stochastic forcing: EOFs and stochastic optimals of M q' = A q + f on a frequency quadrature ----------------------------------
  * Under forcing that is white in time with spatial covariance weight Q_f, the response covariance of a stable (A, M) is

@@ -14,9 +14,19 @@ a nested-dissection LU of ``A - z_k M``; the Ritz pairs of the projected pencil 
 ``complete`` is true when the iteration stopped because every Ritz value inside the ellipse had converged (an iteration that shows
 none inside is confirmed by a second one first) AND directions of the subspace were left over: then the ``count`` eigenvalues returned are all there are.  ``subspace`` must exceed the count inside
 generously (a dense spectrum next to the contour slows the iteration down to the quadrature's filter at the ``(subspace + 1)``-th
-nearest eigenvalue); ``estimate`` (a stochastic estimate of the count, from the first quadrature) helps sizing it.  The conjugate-node
-saving for real pencils, two-sided projection, automatic growth of the subspace and more than one GPU are not built (DESIGN.md,
-section 9).
+nearest eigenvalue); ``estimate`` (a stochastic estimate of the count, from the first quadrature) helps sizing it.
+
+``RegionConfig(two_sided=True)`` adds the left phase: the same iteration on the adjoint pencil ``(A^H, M^H)``, whose node matrices on
+the conjugate contour are ``(A - z_k M)^H`` -- the factor sets of the right phase, no second factorisation
+(``lsa_contour_solve_left``).  From the same start block it returns ``left_eigenvalues`` / ``left_residuals_raw`` as the phase found
+them and, when ``left_complete``, ``left_eigenvectors = W G^-H`` with ``G = W^H M X`` (so column ``i`` belongs to ``eigenvalues[i]``
+and ``W^H M X = I``: no pairing by nearest value, clusters included), their residuals ``left_residuals`` against ``eigenvalues[i]``,
+and the eigenvalue condition numbers ``kappa_i = ||w_i|| ||M x_i|| / |w_i^H M x_i|``.  ``left_complete`` needs the left phase
+complete, its count equal to ``count``, and ``G`` numerically nonsingular: ``sigma_min(G) > count * eps * sigma_max(G)`` (the rank
+rule of ``numpy.linalg.matrix_rank``); otherwise the three stay ``None`` and a warning names the condition.
+
+The conjugate-node saving for real pencils, two-sided (oblique) projection inside the iteration, automatic growth of the subspace
+and more than one GPU are not built.
 """
 
 from __future__ import annotations
@@ -100,6 +110,7 @@ class RegionConfig:
     max_it: int = 20  # iterations allowed
     keep_factors: bool | None = None  # all factor sets alive / one refactorised per node and iteration / None: by the free memory
     batch_nodes: bool = False  # solve an iteration's block on all nodes in lockstep (kept factor sets, one more block per node); same bytes
+    two_sided: bool = False  # after the right phase, the left phase on the same factor sets: left eigenvectors and condition numbers
 
 
 @dataclass
@@ -112,6 +123,15 @@ class RegionResult:
     estimate: float  # stochastic estimate of the count inside the ellipse (first quadrature): for sizing `subspace`
     iterations: int
     stats: dict = field(default_factory=dict)
+    # two_sided=True only (else None): the left phase as it returned, filtered by the region ...
+    left_eigenvalues: np.ndarray | None = None
+    left_residuals_raw: np.ndarray | None = None
+    left_complete: bool | None = None  # the left phase completed, found `count` values, and G = W^H M X is numerically nonsingular
+    # ... and, when left_complete: W G^-H (column i belongs to eigenvalues[i], W^H M X = I), its residuals against eigenvalues[i]
+    # (||A^H w - conj(lam) M^H w|| / (||A^H w|| + |lam| ||M^H w||)), and kappa_i = ||w_i|| ||M x_i|| / |w_i^H M x_i|
+    left_eigenvectors: np.ndarray | None = None
+    left_residuals: np.ndarray | None = None
+    condition_numbers: np.ndarray | None = None
 
 
 def _check_config(cfg: RegionConfig) -> None:
@@ -127,6 +147,8 @@ def _check_config(cfg: RegionConfig) -> None:
         raise ValueError(f"keep_factors = {cfg.keep_factors!r} must be True, False or None")
     if not isinstance(cfg.batch_nodes, (bool, np.bool_)):
         raise ValueError(f"batch_nodes = {cfg.batch_nodes!r} must be True or False")
+    if not isinstance(cfg.two_sided, (bool, np.bool_)):
+        raise ValueError(f"two_sided = {cfg.two_sided!r} must be True or False")
     if cfg.batch_nodes and cfg.keep_factors is False:
         raise ValueError("batch_nodes = True needs the factor sets of all nodes alive: keep_factors = False refactorises one set node by node")
 
@@ -225,8 +247,10 @@ class RegionEigenSolver:
                                        ksp_rtol=self._ksp_rtol, batch_nodes=batch)
             cs.set_row_permutation(perm)
             out = cs.solve(cfg.atol, cfg.max_it, np.asfortranarray(Y0[perm]))
+            left = cs.solve_left(cfg.atol, cfg.max_it, np.asfortranarray(Y0[perm])) if cfg.two_sided else None
             info = cs.info()
             binfo = cs.batch_info()
+            linfo = cs.left_info() if cfg.two_sided else None
         finally:
             del cs  # (the handle goes before the matrices it borrows)
         lam, X, res = out["eigenvalues"], out["eigenvectors"], out["residuals"]
@@ -247,8 +271,59 @@ class RegionEigenSolver:
                  "seconds_solve": info["seconds_solve"], "seconds_product": info["seconds_product"], "seconds_gram": info["seconds_gram"],
                  "seconds_dense": info["seconds_dense"], "seconds_total": time.time() - started, "batch_nodes": binfo["enabled"],
                  "batched_groups": binfo["groups"], "batched_columns": binfo["batched_columns"]}
-        return RegionResult(lam[sel], np.asfortranarray(X[:, sel]), res[sel], int(np.count_nonzero(sel)), bool(out["complete"]),
-                            float(out["estimate"]), int(out["iterations"]), stats)
+        result = RegionResult(lam[sel], np.asfortranarray(X[:, sel]), res[sel], int(np.count_nonzero(sel)), bool(out["complete"]),
+                              float(out["estimate"]), int(out["iterations"]), stats)
+        if left is not None:
+            stats["left"] = {"iterations": left["iterations"], "rank": left["rank"], "inside_ellipse": left["inside"],
+                             "converged_inside": left["converged_inside"], "block_solves": left["block_solves"],
+                             "refined_solves": left["refined_solves"], "backward_accepted": left["backward_accepted"],
+                             "max_rel_res": left["worst_rel_res"], "seconds_factor": linfo["seconds_factor"], "seconds_solve": linfo["seconds_solve"],
+                             "seconds_product": linfo["seconds_product"], "seconds_gram": linfo["seconds_gram"], "seconds_dense": linfo["seconds_dense"],
+                             "batched_groups": linfo["groups"], "batched_columns": linfo["batched_columns"], "serial_columns": linfo["serial_columns"]}
+            self._biorthonormalise(result, region, left, prep)
+            stats["seconds_total"] = time.time() - started
+        return result
+
+    def _biorthonormalise(self, result: RegionResult, region, left: dict, prep: dict) -> None:
+        """The left fields of ``result`` from the left phase's pairs: ``G = W^H M X`` (``lsa_spmm``, ``lsa_block_gram``), ``W G^-H``, the
+        residuals of its columns against ``eigenvalues[i]`` (``lsa_spmm_transpose``) and ``kappa_i``."""
+        import lsa_hip
+
+        lsel = region.contains(left["eigenvalues"])
+        result.left_eigenvalues, result.left_residuals_raw = left["eigenvalues"][lsel], left["residuals"][lsel]
+        W, c, n = left["eigenvectors"][:, lsel], result.count, self._n
+        why = None
+        if not left["complete"]:
+            why = (f"the left phase did not complete ({left['converged_inside']} of {left['inside']} Ritz values inside converged in "
+                   f"{left['iterations']} iterations, rank {left['rank']})")
+        elif W.shape[1] != c:
+            why = f"the left phase found {W.shape[1]} eigenvalues in the region, the right phase {c}"
+        elif c > 0:
+            ctx, perm = prep["ctx"], prep["perm"]
+            block = lambda V: lsa_hip.DeviceVector.from_numpy(ctx, np.asfortranarray(V[perm]).reshape(-1, order="F"))  # noqa: E731
+            host = lambda d: d.numpy().reshape((n, c), order="F")  # noqa: E731
+            dMX = lsa_hip.DeviceVector(ctx, n * c, np.complex128)
+            prep["dM"].matmat(block(result.eigenvectors), dMX, c)
+            G = lsa_hip.block_gram(ctx, n, block(W), c, dMX, c)
+            sv = np.linalg.svd(G, compute_uv=False)
+            if not (np.all(np.isfinite(sv)) and sv[-1] > c * np.finfo(float).eps * sv[0]):
+                why = f"G = W^H M X is numerically singular (singular values from {sv[0]:.3e} down to {sv[-1]:.3e})"
+            else:
+                Wb = W @ np.linalg.inv(G).conj().T
+                dW, dAW, dMW = block(Wb), lsa_hip.DeviceVector(ctx, n * c, np.complex128), lsa_hip.DeviceVector(ctx, n * c, np.complex128)
+                prep["dA"].matmat_transpose(dW, dAW, c, conj=True)
+                prep["dM"].matmat_transpose(dW, dMW, c, conj=True)
+                AW, MW, MX, lam = host(dAW), host(dMW), host(dMX), result.eigenvalues
+                result.left_eigenvectors = np.asfortranarray(Wb)
+                result.left_residuals = np.linalg.norm(AW - MW * lam.conj(), axis=0) / (np.linalg.norm(AW, axis=0) + np.abs(lam) * np.linalg.norm(MW, axis=0) + 1e-16)
+                wMx = np.sum(Wb[perm].conj() * MX, axis=0)
+                result.condition_numbers = np.linalg.norm(Wb, axis=0) * np.linalg.norm(MX, axis=0) / np.abs(wMx)
+        else:
+            result.left_eigenvectors = np.zeros((n, 0), dtype=np.complex128, order="F")
+            result.left_residuals, result.condition_numbers = np.zeros(0), np.zeros(0)
+        result.left_complete = why is None
+        if why is not None:
+            logger.warning("Region: no left eigenvectors and condition numbers: %s", why)
 
     def sweep(self, regions, Y0: np.ndarray | None = None) -> list[RegionResult]:
         """One result per region on ONE context, ordering and LU analysis (``stats["analysis_reused"]``); every region returns the

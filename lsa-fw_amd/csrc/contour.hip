@@ -9,8 +9,9 @@
 //     A_h = U^H (A U), M_h = U^H (M U), Ritz pairs of M_h^-1 A_h on the host (complex LU, lsa_dense_schur)
 //     residuals of all Ritz pairs from A U, M U and S          k_basis_gemm + ci_residual_kernel
 // Q = -sum_k w_k C_k^-1 M Y is the quadrature of the spectral projector (1 / 2 pi i) oint (z M - A)^-1 M dz applied to Y.  The two
-// building blocks are also entry points of their own (lsa_spmm, lsa_block_gram); blocks have leading dimensions >= n there and n
-// inside the iteration.
+// building blocks are also entry points of their own (lsa_spmm, lsa_block_gram), and so is the transposed block product a left
+// (adjoint) phase needs (lsa_spmm_transpose: ci_spmm_kernel on the pattern's transposed index); blocks have leading dimensions >= n
+// there and n inside the iteration.
 //
 // Every sum runs in a fixed order and there are no floating-point atomics: two calls give the same bits.
 //   ci_spmm_kernel   the entries of a row strided over the 8 lanes of its row group, each lane adding its entries in order; then the
@@ -52,10 +53,20 @@ __device__ __forceinline__ void ci_st(cplx* p, cplx v) {
 // entries rp[r] + s, rp[r] + s + 8, ...: one load of the column index and of the value per entry, then the nc entries of that row
 // of X (all requested before the first multiply-add of a full pass).  Rows beyond n take an empty range, so that every lane of a
 // wavefront reaches the shuffles.
-template <typename MT>
+// TRANS: Y = A^T X (conj != 0: A^H X) in pull form on the pattern's transposed index (TransposeIndex: rp, ci are its arrays, the
+// value of entry p lies at val[src[p]]) -- an output's entries ordered by row, the same lanes and tree, no atomics.
+template <typename MT, bool TRANS>
 __global__ __launch_bounds__(kCiThreads) void ci_spmm_kernel(int32_t n, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                                             const MT* __restrict__ val, int nc, const cplx* __restrict__ X, int64_t ldx,
-                                                             cplx* __restrict__ Y, int64_t ldy) {
+                                                             const int32_t* __restrict__ src, int conj, const MT* __restrict__ val, int nc,
+                                                             const cplx* __restrict__ X, int64_t ldx, cplx* __restrict__ Y, int64_t ldy) {
+    auto entry = [&](int32_t p) {
+        if constexpr (TRANS) {
+            const MT a = ci_ld(val + src[p]);
+            return conj ? s_conj(a) : a;
+        } else {
+            return ci_ld(val + p);
+        }
+    };
     const int sub = threadIdx.x & (kCiRowLanes - 1);
     const int64_t row = (int64_t)blockIdx.x * (kCiThreads / kCiRowLanes) + (threadIdx.x / kCiRowLanes);
     int32_t p0 = 0, p1 = 0;
@@ -69,7 +80,7 @@ __global__ __launch_bounds__(kCiThreads) void ci_spmm_kernel(int32_t n, const in
     if (nc == kCiColTile) {
         for (int32_t p = p0 + sub; p < p1; p += kCiRowLanes) {
             const cplx* x = X + ci[p];
-            const MT a = ci_ld(val + p);
+            const MT a = entry(p);
             cplx xv[kCiColTile];
 #pragma unroll
             for (int u = 0; u < kCiColTile; ++u) xv[u] = ci_ld(x + (int64_t)u * ldx);
@@ -79,7 +90,7 @@ __global__ __launch_bounds__(kCiThreads) void ci_spmm_kernel(int32_t n, const in
     } else {
         for (int32_t p = p0 + sub; p < p1; p += kCiRowLanes) {
             const cplx* x = X + ci[p];
-            const MT a = ci_ld(val + p);
+            const MT a = entry(p);
 #pragma unroll
             for (int u = 0; u < kCiColTile; ++u)
                 if (u < nc) fma_acc(acc[u], a, ci_ld(x + (int64_t)u * ldx));
@@ -274,11 +285,35 @@ int k_spmm(lsa_ctx* ctx, const lsa_mat* A, int32_t ncols, const void* X, int64_t
         const cplx* x = (const cplx*)X + (int64_t)c0 * ldx;
         cplx* y = (cplx*)Y + (int64_t)c0 * ldy;
         if (A->dtype == LSA_C128)
-            hipLaunchKernelGGL(ci_spmm_kernel<cplx>, dim3(blocks), dim3(kCiThreads), 0, ctx->stream, A->n, A->rp, A->ci, (const cplx*)A->val, nc, x, ldx, y, ldy);
+            hipLaunchKernelGGL((ci_spmm_kernel<cplx, false>), dim3(blocks), dim3(kCiThreads), 0, ctx->stream, A->n, A->rp, A->ci, nullptr, 0,
+                               (const cplx*)A->val, nc, x, ldx, y, ldy);
         else
-            hipLaunchKernelGGL(ci_spmm_kernel<double>, dim3(blocks), dim3(kCiThreads), 0, ctx->stream, A->n, A->rp, A->ci, (const double*)A->val, nc, x, ldx, y, ldy);
+            hipLaunchKernelGGL((ci_spmm_kernel<double, false>), dim3(blocks), dim3(kCiThreads), 0, ctx->stream, A->n, A->rp, A->ci, nullptr, 0,
+                               (const double*)A->val, nc, x, ldx, y, ldy);
     }
     return ci_check_launch(ctx, "k_spmm");
+}
+
+// Y[:, c] = A^T X[:, c] (conj != 0: A^H X[:, c]) for a whole square matrix: the passes of k_spmm on the transposed index of A's pattern
+// (built by the first transposed product of any matrix of the pattern, shared by all of them)
+int k_spmm_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, int32_t ncols, const void* X, int64_t ldx, void* Y, int64_t ldy) {
+    if (A->n < 1 || ncols < 1) return LSA_OK;
+    const TransposeIndex* T = nullptr;
+    LSA_CHECK(k_transpose_index(ctx, A, &T));
+    const int per_block = kCiThreads / kCiRowLanes;
+    const int blocks = (A->ncols + per_block - 1) / per_block;
+    for (int32_t c0 = 0; c0 < ncols; c0 += kCiColTile) {
+        const int nc = std::min<int32_t>(kCiColTile, ncols - c0);
+        const cplx* x = (const cplx*)X + (int64_t)c0 * ldx;
+        cplx* y = (cplx*)Y + (int64_t)c0 * ldy;
+        if (A->dtype == LSA_C128)
+            hipLaunchKernelGGL((ci_spmm_kernel<cplx, true>), dim3(blocks), dim3(kCiThreads), 0, ctx->stream, A->ncols, T->rp, T->ci, T->src, conj,
+                               (const cplx*)A->val, nc, x, ldx, y, ldy);
+        else
+            hipLaunchKernelGGL((ci_spmm_kernel<double, true>), dim3(blocks), dim3(kCiThreads), 0, ctx->stream, A->ncols, T->rp, T->ci, T->src, conj,
+                               (const double*)A->val, nc, x, ldx, y, ldy);
+    }
+    return ci_check_launch(ctx, "k_spmm_transpose");
 }
 
 int k_block_gram(lsa_ctx* ctx, int64_t n, int32_t p, const void* U, int64_t ldu, int32_t q, const void* W, int64_t ldw, void* G_host) {
@@ -312,6 +347,20 @@ int lsa_spmm(lsa_ctx* ctx, const lsa_mat* A, int32_t ncols, const lsa_vec* X, in
         return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm: a block of %d columns of %d rows with ldx = %lld, ldy = %lld does not fit vectors of %lld and %lld entries "
                                                "(ld >= n, length >= ld (ncols - 1) + n)", ncols, A->n, (long long)ldx, (long long)ldy, (long long)X->n, (long long)Y->n);
     return k_spmm(ctx, A, ncols, X->d, ldx, Y->d, ldy);
+}
+
+int lsa_spmm_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, int32_t ncols, const lsa_vec* X, int64_t ldx, lsa_vec* Y, int64_t ldy) {
+    if (!ctx || !A || !X || !Y) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm_transpose: null argument");
+    if (A->n != A->ncols || A->row0 != 0)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm_transpose: the matrix is a row shard (%d x %d): whole square matrices only", A->n, A->ncols);
+    if (ncols < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm_transpose: %d columns", ncols);
+    if (X->dtype != LSA_C128 || Y->dtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm_transpose: the blocks must be complex128");
+    if (X->d == Y->d) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm_transpose: X and Y must not alias");
+    if (!ci_block_fits(X, A->n, ncols, ldx) || !ci_block_fits(Y, A->ncols, ncols, ldy))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmm_transpose: a block of %d columns of %d rows with ldx = %lld, ldy = %lld does not fit vectors of %lld and %lld "
+                                               "entries (ld >= n, length >= ld (ncols - 1) + n)", ncols, A->n, (long long)ldx, (long long)ldy, (long long)X->n,
+                             (long long)Y->n);
+    return k_spmm_transpose(ctx, A, conj, ncols, X->d, ldx, Y->d, ldy);
 }
 
 int lsa_block_gram(lsa_ctx* ctx, int64_t n, int32_t p, const lsa_vec* U, int64_t ldu, int32_t q, const lsa_vec* W, int64_t ldw, void* G) {
@@ -354,6 +403,7 @@ struct lsa_contour {
     lsa_stats st{};
     int64_t bytes = 0;
     double sec_solve = 0.0, sec_product = 0.0, sec_gram = 0.0, sec_dense = 0.0;
+    lsa_contour_left_stats left{};  // what the left phases did and took: booked apart from everything above (lsa_contour_left_info)
 };
 
 namespace {
@@ -400,6 +450,16 @@ int ct_times_host(lsa_ctx* ctx, lsa_contour* h, int m, int k, const cplx* V, con
     return basis_times_host_matrix(ctx, LSA_C128, h->n, m, k, V, T, m, h->qdev, Out, 0);
 }
 
+// The two phases share every step; `adj` picks the operators.  Right phase: A, M, C_k.  Left phase: their conjugate transposes -- the
+// pencil (A^H, M^H), whose node matrices on the conjugate contour are C_k^H = A^H - conj(z_k) M^H: the same factor sets, the
+// transposed sweeps and the transposed block product.
+int ct_mul(lsa_ctx* ctx, bool adj, const lsa_mat* A, int32_t cols, const cplx* X, int64_t n, cplx* Y) {
+    return adj ? k_spmm_transpose(ctx, A, 1, cols, X, n, Y, n) : k_spmm(ctx, A, cols, X, n, Y, n);
+}
+int ct_solve_dev(lsa_ctx* ctx, bool adj, lsa_ndlu* f, int32_t cols, const cplx* B, int64_t n, cplx* X) {
+    return adj ? ndlu_solve_multi_adjoint_dev(ctx, f, 1, LSA_C128, cols, B, n, X, n) : ndlu_solve_multi_dev(ctx, f, LSA_C128, cols, B, n, X, n);
+}
+
 // the accepted columns of a node's block solve into the counters (s: the three sums per column of ct_column_sums)
 void ct_book_columns(lsa_contour* h, int32_t cols, const double* s, bool refined, double* worst) {
     for (int32_t j = 0; j < cols; ++j) {
@@ -412,27 +472,28 @@ void ct_book_columns(lsa_contour* h, int32_t cols, const double* s, bool refined
 
 // X = C_k^-1 B for cols columns, every column judged by the rule of lsa_lanczos_extend: within ksp_rtol, else one refinement step (and
 // every later block solve of this node carries it), else a backward error within 1e-12 ||C_k||_F ||x||, else LSA_ERR_DIVERGED
-int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, double* worst) {
+int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, bool adj, int32_t k, int32_t cols, double* worst) {
     const int64_t n = h->n;
     lsa_ndlu* f = nullptr;
     LSA_CHECK(shifted_sets_factors(ctx, h->S, "lsa_contour", k, &f));
     const lsa_mat* C = h->S->C[(size_t)k];
-    char& refine = h->S->refine[0][(size_t)k];
+    char& refine = h->S->refine[adj ? 1 : 0][(size_t)k];
+    const char* who = adj ? "lsa_contour_solve_left: the adjoint solve" : "lsa_contour_solve: the solve";
     const double t0 = now_s();
     std::vector<double> s((size_t)3 * cols);
     bool refined = false;
-    int rc = ndlu_solve_multi_dev(ctx, f, LSA_C128, cols, h->B, n, h->X, n);
+    int rc = ct_solve_dev(ctx, adj, f, cols, h->B, n, h->X);
     while (rc == LSA_OK) {
         if (refine && !refined) {
             // R = B - C X;  D = C^-1 R;  X += D
-            rc = k_spmm(ctx, C, cols, h->X, n, h->W1, n);
+            rc = ct_mul(ctx, adj, C, cols, h->X, n, h->W1);
             if (rc == LSA_OK) rc = ct_accumulate(ctx, n, cols, ci_z(1.0, 0.0), h->B, -1.0, h->W1);
-            if (rc == LSA_OK) rc = ndlu_solve_multi_dev(ctx, f, LSA_C128, cols, h->W1, n, h->W1, n);
+            if (rc == LSA_OK) rc = ct_solve_dev(ctx, adj, f, cols, h->W1, n, h->W1);
             if (rc == LSA_OK) rc = ct_accumulate(ctx, n, cols, ci_z(1.0, 0.0), h->W1, 1.0, h->X);
             if (rc != LSA_OK) break;
             refined = true;
         }
-        rc = k_spmm(ctx, C, cols, h->X, n, h->W1, n);
+        rc = ct_mul(ctx, adj, C, cols, h->X, n, h->W1);
         if (rc == LSA_OK) rc = ct_column_sums(ctx, h, cols, h->B, h->W1, h->X, nullptr, s.data());
         if (rc != LSA_OK) break;
         bool again = false;
@@ -445,11 +506,11 @@ int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, double
                 break;
             }
             if (verdict < 0)
-                rc = refined ? lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_contour_solve: the solve of column %d at node %d left a relative residual of %.3e "
-                                                                    "after its refinement step (ksp_rtol %.1e) and a backward error above 1e-12 ||C||_F", j, k,
+                rc = refined ? lsa_set_error(ctx, LSA_ERR_DIVERGED, "%s of column %d at node %d left a relative residual of %.3e "
+                                                                    "after its refinement step (ksp_rtol %.1e) and a backward error above 1e-12 ||C||_F", who, j, k,
                                              bnorm > 0.0 ? res / bnorm : res, h->ksp_rtol)
-                             : lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_contour_solve: the solve of column %d at node %d left a residual that is not finite "
-                                                                    "(%.3e, ||b|| = %.3e); no refinement step was taken", j, k, res, bnorm);
+                             : lsa_set_error(ctx, LSA_ERR_DIVERGED, "%s of column %d at node %d left a residual that is not finite "
+                                                                    "(%.3e, ||b|| = %.3e); no refinement step was taken", who, j, k, res, bnorm);
         }
         if (rc != LSA_OK) break;
         if (again) {
@@ -467,13 +528,13 @@ int ct_block_solve(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, double
 // lsa_contour_set_batch_nodes: X_k = C_k^-1 B for every node that does not carry the refinement step, into the nodes' own blocks
 // -- run by run (shifted_sets_next_run), each run one block solve on all its sets from the shared B.  solved[k] = 1: X_k is there,
 // with the bits ct_block_solve's first solve gives.
-int ct_batch_solve(lsa_ctx* ctx, lsa_contour* h, int32_t cols, std::vector<char>& solved) {
+int ct_batch_solve(lsa_ctx* ctx, lsa_contour* h, bool adj, int32_t cols, std::vector<char>& solved) {
     const int64_t n = h->n;
     const double t0 = now_s();
     int rc = LSA_OK;
     shifted_run run;
     for (int32_t k = 0; k < h->N && rc == LSA_OK;) {
-        k = shifted_sets_next_run(h->S, k, h->S->refine[0], &run);
+        k = shifted_sets_next_run(h->S, k, h->S->refine[adj ? 1 : 0], &run);
         if (run.J == 0) break;
         const void* bs[kNdBatchMax];
         void* xs[kNdBatchMax];
@@ -483,10 +544,11 @@ int ct_batch_solve(lsa_ctx* ctx, lsa_contour* h, int32_t cols, std::vector<char>
             solved[(size_t)run.node[z]] = 1;
         }
         if (cols > 1) {
-            rc = ndlu_solve_multi_batch_dev(ctx, run.J, run.f, LSA_C128, cols, bs, n, xs, n);
+            rc = adj ? ndlu_solve_multi_batch_adjoint_dev(ctx, run.J, run.f, 1, LSA_C128, cols, bs, n, xs, n)
+                     : ndlu_solve_multi_batch_dev(ctx, run.J, run.f, LSA_C128, cols, bs, n, xs, n);
             h->batch_groups += run.f[0]->multi_passes;
         } else {
-            rc = ndlu_solve_batch_dev(ctx, run.J, run.f, LSA_C128, bs, xs);
+            rc = adj ? ndlu_solve_batch_adjoint_dev(ctx, run.J, run.f, 1, LSA_C128, bs, xs) : ndlu_solve_batch_dev(ctx, run.J, run.f, LSA_C128, bs, xs);
         }
         h->batch_columns += (int64_t)run.J * cols;
     }
@@ -496,11 +558,11 @@ int ct_batch_solve(lsa_ctx* ctx, lsa_contour* h, int32_t cols, std::vector<char>
 
 // the check of a node's batched block: the product and the column sums of ct_block_solve on X_k.  *ok = 0: a column misses ksp_rtol
 // (or is not finite) -- nothing is booked, and ct_block_solve takes the node; else the columns are booked as its unrefined solves are.
-int ct_batch_check(lsa_ctx* ctx, lsa_contour* h, int32_t k, int32_t cols, const cplx* Xk, double* worst, bool* ok) {
+int ct_batch_check(lsa_ctx* ctx, lsa_contour* h, bool adj, int32_t k, int32_t cols, const cplx* Xk, double* worst, bool* ok) {
     const int64_t n = h->n;
     const double t0 = now_s();
     std::vector<double> s((size_t)3 * cols);
-    int rc = k_spmm(ctx, h->S->C[(size_t)k], cols, Xk, n, h->W1, n);
+    int rc = ct_mul(ctx, adj, h->S->C[(size_t)k], cols, Xk, n, h->W1);
     if (rc == LSA_OK) rc = ct_column_sums(ctx, h, cols, h->B, h->W1, Xk, nullptr, s.data());
     *ok = rc == LSA_OK;
     for (int32_t j = 0; j < cols && *ok; ++j)
@@ -685,13 +747,18 @@ int lsa_contour_batch_info(const lsa_contour* h, lsa_contour_batch_stats* out) {
     return LSA_OK;
 }
 
-int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, const void* Y0_host, int32_t max_out, void* lam_out, void* X_out,
-                      double* res_out, lsa_contour_result* result) {
-    if (!ctx || !h || !Y0_host || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_solve: null argument");
-    if (!(tol > 0.0) || max_it < 1 || max_out < 0 || (max_out > 0 && (!lam_out || !res_out)))
-        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_solve: bad argument (tol %.3e, max_it %d, max_out %d)", tol, max_it, max_out);
+}  // extern "C"
+
+// The iteration of either phase from the start block Y0 (the steps of this file's header).  adj: the left phase -- the same steps on the
+// adjoint pencil (A^H, M^H), whose eigenvalues mu are the conjugates of the pencil's and whose region is the conjugate ellipse: Ritz
+// pairs (mu, s) of (U^H A^H U, U^H M^H U), residual ||A^H w - mu M^H w|| / (||A^H w|| + |mu| ||M^H w||), inside when conj(mu) lies in
+// the caller's ellipse, and lam_out holds conj(mu).
+static int ct_iterate(lsa_ctx* ctx, lsa_contour* h, bool adj, const char* who, double tol, int32_t max_it, const void* Y0_host, int32_t max_out, void* lam_out,
+                      void* X_out, double* res_out, lsa_contour_result* result) {
     const int64_t n = h->n;
     const int32_t L = h->L;
+    // the value in the caller's region: the Ritz value itself, or for the left phase the conjugate of the adjoint pencil's mu
+    auto region_value = [adj](ci_z v) { return adj ? std::conj(v) : v; };
     *result = lsa_contour_result{};
     const int64_t solves0 = h->st.op_applies, refined0 = h->st.refined_solves, backward0 = h->st.backward_accepted;
     LSA_HIP_CHECK(ctx, hipMemcpyAsync(h->Y, Y0_host, (size_t)n * L * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
@@ -704,25 +771,26 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
     std::vector<int32_t> in_idx;
     int32_t it = 0;
     for (; it < max_it; ++it) {
-        // B = M Y, then the quadrature over the nodes: Q = -sum_k w_k C_k^-1 B
+        // B = M Y, then the quadrature over the nodes: Q = -sum_k w_k C_k^-1 B (left phase: B = M^H Y, Q = -sum_k conj(w_k) C_k^-H B: the
+        // adjoint pencil's nodes conj(z_k) run through the conjugate contour at the angles -theta_k, where its weights are conj(w_k))
         double t0 = now_s();
-        LSA_CHECK(k_spmm(ctx, h->S->M, cols, h->Y, n, h->B, n));
+        LSA_CHECK(ct_mul(ctx, adj, h->S->M, cols, h->Y, n, h->B));
         h->st.spmv_calls += cols;
         h->sec_product += now_s() - t0;
         std::vector<char> solved((size_t)h->N, 0);
-        if (h->batch_nodes) LSA_CHECK(ct_batch_solve(ctx, h, cols, solved));
+        if (h->batch_nodes) LSA_CHECK(ct_batch_solve(ctx, h, adj, cols, solved));
         for (int32_t k = 0; k < h->N; ++k) {
             const cplx* Xk = h->X;
             bool ok = false;
             if (solved[(size_t)k]) {
                 Xk = h->XN + (size_t)k * (size_t)n * (size_t)L;
-                LSA_CHECK(ct_batch_check(ctx, h, k, cols, Xk, &worst, &ok));
+                LSA_CHECK(ct_batch_check(ctx, h, adj, k, cols, Xk, &worst, &ok));
             }
             if (!ok) {  // the default path; after a batched solve that missed: the same solve again, then its refinement step
-                LSA_CHECK(ct_block_solve(ctx, h, k, cols, &worst));
+                LSA_CHECK(ct_block_solve(ctx, h, adj, k, cols, &worst));
                 Xk = h->X;
             }
-            LSA_CHECK(ct_accumulate(ctx, n, cols, -h->w[(size_t)k], Xk, k == 0 ? 0.0 : 1.0, h->Q));
+            LSA_CHECK(ct_accumulate(ctx, n, cols, adj ? -std::conj(h->w[(size_t)k]) : -h->w[(size_t)k], Xk, k == 0 ? 0.0 : 1.0, h->Q));
         }
         if (it == 0) {  // the stochastic estimate of the count inside: Re sum_j y_j^H q_j / L
             std::vector<ci_z> G((size_t)cols * cols);
@@ -739,8 +807,8 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
         LSA_CHECK(ct_orth_pass(ctx, h, h->X, r1, h->Y, &r));
         // A U, M U and the projected pencil
         t0 = now_s();
-        LSA_CHECK(k_spmm(ctx, h->S->A, r, h->Y, n, h->W1, n));
-        LSA_CHECK(k_spmm(ctx, h->S->M, r, h->Y, n, h->W2, n));
+        LSA_CHECK(ct_mul(ctx, adj, h->S->A, r, h->Y, n, h->W1));
+        LSA_CHECK(ct_mul(ctx, adj, h->S->M, r, h->Y, n, h->W2));
         h->st.spmv_calls += 2 * r;
         LSA_CHECK(ct_sync(ctx));
         h->sec_product += now_s() - t0;
@@ -750,9 +818,9 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
         LSA_CHECK(k_block_gram(ctx, n, r, h->Y, n, r, h->W2, n, Mh.data()));
         h->sec_gram += now_s() - t0;
         t0 = now_s();
-        if (!dense_lu_solve(r, Mh.data(), Ah.data())) return lsa_set_error(ctx, LSA_ERR_ZERO_PIVOT, "lsa_contour_solve: U^H M U is singular at iteration %d (rank %d)", it, r);
+        if (!dense_lu_solve(r, Mh.data(), Ah.data())) return lsa_set_error(ctx, LSA_ERR_ZERO_PIVOT, "%s: U^H M U is singular at iteration %d (rank %d)", who, it, r);
         std::vector<ci_z> Qs((size_t)r * r), St((size_t)r * r);
-        if (lsa_dense_schur(r, Ah.data(), r, Qs.data(), r) != LSA_OK) return lsa_set_error(ctx, LSA_ERR_DIVERGED, "lsa_contour_solve: the QR algorithm stalled on the projected problem");
+        if (lsa_dense_schur(r, Ah.data(), r, Qs.data(), r) != LSA_OK) return lsa_set_error(ctx, LSA_ERR_DIVERGED, "%s: the QR algorithm stalled on the projected problem", who);
         LSA_CHECK(lsa_dense_tri_eigenvectors(r, Ah.data(), r, St.data(), r));
         lam.assign((size_t)r, ci_z());
         S.assign((size_t)r * r, ci_z());
@@ -762,7 +830,7 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
                 for (int32_t i = 0; i < r; ++i) S[(size_t)j * r + i] += Qs[(size_t)k * r + i] * St[(size_t)j * r + k];
         }
         for (const ci_z& l : lam)
-            if (!std::isfinite(l.real()) || !std::isfinite(l.imag())) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "lsa_contour_solve: a Ritz value is not finite at iteration %d", it);
+            if (!std::isfinite(l.real()) || !std::isfinite(l.imag())) return lsa_set_error(ctx, LSA_ERR_NONFINITE, "%s: a Ritz value is not finite at iteration %d", who, it);
         h->sec_dense += now_s() - t0;
         // residuals ||A x - lam M x|| / (||A x|| + |lam| ||M x||) of all Ritz pairs from A U S and M U S
         t0 = now_s();
@@ -778,7 +846,7 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
         conv = 0;
         for (int32_t j = 0; j < r; ++j) {
             res[(size_t)j] = std::sqrt(s[3 * (size_t)j]) / (std::sqrt(s[3 * (size_t)j + 1]) + std::abs(lam[(size_t)j]) * std::sqrt(s[3 * (size_t)j + 2]) + 1e-16);
-            if (ct_radius2(h, lam[(size_t)j]) < 1.0) {
+            if (ct_radius2(h, region_value(lam[(size_t)j])) < 1.0) {
                 in_idx.push_back(j);
                 if (res[(size_t)j] <= tol) ++conv;
             }
@@ -803,11 +871,11 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
     result->backward_accepted = h->st.backward_accepted - backward0;
     result->worst_rel_res = worst;
     // the inside pairs, nearest the centre (in the ellipse's own metric) first
-    std::stable_sort(in_idx.begin(), in_idx.end(), [&](int32_t a, int32_t b) { return ct_radius2(h, lam[(size_t)a]) < ct_radius2(h, lam[(size_t)b]); });
+    std::stable_sort(in_idx.begin(), in_idx.end(), [&](int32_t a, int32_t b) { return ct_radius2(h, region_value(lam[(size_t)a])) < ct_radius2(h, region_value(lam[(size_t)b])); });
     const int32_t nout = std::min<int32_t>(inside, max_out);
     result->nout = nout;
     for (int32_t c = 0; c < nout; ++c) {
-        ((ci_z*)lam_out)[c] = lam[(size_t)in_idx[(size_t)c]];
+        ((ci_z*)lam_out)[c] = region_value(lam[(size_t)in_idx[(size_t)c]]);
         res_out[c] = res[(size_t)in_idx[(size_t)c]];
     }
     if (nout > 0 && X_out) {
@@ -824,6 +892,53 @@ int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, 
         LSA_CHECK(ct_sync(ctx));
     }
     h->st.seconds_solve = h->sec_solve;
+    return LSA_OK;
+}
+
+extern "C" {
+
+int lsa_contour_solve(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, const void* Y0_host, int32_t max_out, void* lam_out, void* X_out,
+                      double* res_out, lsa_contour_result* result) {
+    if (!ctx || !h || !Y0_host || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_solve: null argument");
+    if (!(tol > 0.0) || max_it < 1 || max_out < 0 || (max_out > 0 && (!lam_out || !res_out)))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_solve: bad argument (tol %.3e, max_it %d, max_out %d)", tol, max_it, max_out);
+    return ct_iterate(ctx, h, false, "lsa_contour_solve", tol, max_it, Y0_host, max_out, lam_out, X_out, res_out, result);
+}
+
+// The left phase on the same handle and factor sets.  Its counters and times are booked apart: the handle's own books (lsa_contour_info,
+// lsa_contour_batch_info) are put back as they were, the differences go to lsa_contour_left_info.
+int lsa_contour_solve_left(lsa_ctx* ctx, lsa_contour* h, double tol, int32_t max_it, const void* Y0_host, int32_t max_out, void* lam_out, void* W_out,
+                           double* res_out, lsa_contour_result* result) {
+    if (!ctx || !h || !Y0_host || !result) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_solve_left: null argument");
+    if (!(tol > 0.0) || max_it < 1 || max_out < 0 || (max_out > 0 && (!lam_out || !res_out)))
+        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_contour_solve_left: bad argument (tol %.3e, max_it %d, max_out %d)", tol, max_it, max_out);
+    const lsa_stats st0 = h->st;
+    const double sec0[5] = {h->sec_solve, h->sec_product, h->sec_gram, h->sec_dense, h->S->seconds_factor};
+    const int64_t b0[3] = {h->batch_groups, h->batch_columns, h->serial_columns};
+    const int rc = ct_iterate(ctx, h, true, "lsa_contour_solve_left", tol, max_it, Y0_host, max_out, lam_out, W_out, res_out, result);
+    lsa_contour_left_stats& l = h->left;
+    l.solves += 1;
+    l.iterations += result->iterations;
+    l.block_solves += h->st.op_applies - st0.op_applies;
+    l.refined_solves += h->st.refined_solves - st0.refined_solves;
+    l.backward_accepted += h->st.backward_accepted - st0.backward_accepted;
+    l.groups += h->batch_groups - b0[0];
+    l.batched_columns += h->batch_columns - b0[1];
+    l.serial_columns += h->serial_columns - b0[2];
+    l.seconds_solve += h->sec_solve - sec0[0];
+    l.seconds_product += h->sec_product - sec0[1];
+    l.seconds_gram += h->sec_gram - sec0[2];
+    l.seconds_dense += h->sec_dense - sec0[3];
+    l.seconds_factor += h->S->seconds_factor - sec0[4];
+    h->st = st0;
+    h->sec_solve = sec0[0], h->sec_product = sec0[1], h->sec_gram = sec0[2], h->sec_dense = sec0[3];
+    h->batch_groups = b0[0], h->batch_columns = b0[1], h->serial_columns = b0[2];
+    return rc;
+}
+
+int lsa_contour_left_info(const lsa_contour* h, lsa_contour_left_stats* out) {
+    if (!h || !out) return LSA_ERR_ARG;
+    *out = h->left;
     return LSA_OK;
 }
 

@@ -262,6 +262,8 @@ constexpr int kKrylovGroupMax = 16;
 // y = A x                       (spmv.hip)
 int k_spmv(lsa_ctx* ctx, const lsa_mat* A, int xdtype, const void* x, void* y);
 int k_spmv_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, int xdtype, const void* x, void* y);
+// the transposed index of the pattern of a whole square A, built on first use and shared by the matrices of the pattern
+int k_transpose_index(lsa_ctx* ctx, const lsa_mat* A, const TransposeIndex** out);
 // ys[z] = mats[z]^T xs[z] (conj != 0: ^H), z < J <= 16, in one launch on the transposed index of one pattern; each ys[z] holds
 // k_spmv_transpose's bits.  LSA_ERR_ARG naming what differs unless n, ncols, nnz and dtype agree and the matrices share the pattern
 // object or their index arrays, or have equal host patterns
@@ -273,6 +275,9 @@ void spmv_share_extras(const lsa_mat* from, lsa_mat* to);
 // Block kernels of the region eigensolver (contour.hip): complex128 column-major blocks, column c at c * ld, ld >= n
 // Y[:, 0:ncols] = A X[:, 0:ncols] for a whole square A (f64 or c128), in passes of 8 columns that read A once each; not k_spmv's bits
 int k_spmm(lsa_ctx* ctx, const lsa_mat* A, int32_t ncols, const void* X, int64_t ldx, void* Y, int64_t ldy);
+// Y[:, 0:ncols] = A^T X[:, 0:ncols] (conj != 0: A^H), the same passes on the pattern's transposed index: no atomics, a fixed summation
+// order; not k_spmv_transpose's bits
+int k_spmm_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, int32_t ncols, const void* X, int64_t ldx, void* Y, int64_t ldy);
 // G_host (p x q column-major) = U^H W over n rows, p, q <= 128: fixed-order two-stage sums; synchronises.  U == W (one block): real diagonal
 int k_block_gram(lsa_ctx* ctx, int64_t n, int32_t p, const void* U, int64_t ldu, int32_t q, const void* W, int64_t ldw, void* G_host);
 

@@ -1030,6 +1030,45 @@ int lsa_ndlu_solve_multi_batch_time(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f,
     return LSA_OK;
 }
 
+// the transposed block solve on J sets, an entry of its own (the forward entry goes on refusing trans != 0): the rules of
+// nd_multi_batch_check; queued on the stream (one column: the batched solo transposed sweeps)
+static int nd_multi_batch_adjoint_run(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, int32_t nrhs, const void* const* bd, int64_t ldb,
+                                      void* const* xd, int64_t ldx) {
+    if (nrhs > 1) return ndlu_solve_multi_batch_adjoint_dev(ctx, J, f, conj, vdtype, nrhs, bd, ldb, xd, ldx);
+    const void* b1[kNdBatchMax];
+    for (int32_t z = 0; z < J; ++z) b1[z] = bd[z];  // (nd_dispatch_solve replaces an aliased entry by the set's own copy, d_tmp)
+    return ndlu_solve_batch_adjoint_dev(ctx, J, f, conj, vdtype, b1, xd);
+}
+
+int lsa_ndlu_solve_multi_batch_adjoint(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int32_t nrhs, const lsa_vec* const* B, int64_t ldb,
+                                       lsa_vec* const* X, int64_t ldx) {
+    const void* bd[kNdBatchMax];
+    void* xd[kNdBatchMax];
+    LSA_CHECK(nd_multi_batch_check(ctx, "lsa_ndlu_solve_multi_batch_adjoint", J, f, 0, nrhs, B, ldb, X, ldx, bd, xd));
+    LSA_CHECK(nd_multi_batch_adjoint_run(ctx, J, f, conj, X[0]->dtype, nrhs, bd, ldb, xd, ldx));
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return LSA_OK;
+}
+
+int lsa_ndlu_solve_multi_batch_adjoint_time(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int32_t nrhs, const lsa_vec* const* B, int64_t ldb,
+                                            lsa_vec* const* X, int64_t ldx, int iters, double* avg_ms) {
+    if (!avg_ms || iters < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch_adjoint_time: bad argument");
+    const void* bd[kNdBatchMax];
+    void* xd[kNdBatchMax];
+    LSA_CHECK(nd_multi_batch_check(ctx, "lsa_ndlu_solve_multi_batch_adjoint_time", J, f, 0, nrhs, B, ldb, X, ldx, bd, xd));
+    for (int32_t z = 0; z < J; ++z)
+        if (bd[z] == xd[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch_adjoint_time: repeated solves need B and X apart (set %d)", z);
+    LSA_CHECK(nd_multi_batch_adjoint_run(ctx, J, f, conj, X[0]->dtype, nrhs, bd, ldb, xd, ldx));  // (the first call makes the per-column buffers)
+    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    for (int i = 0; i < iters; ++i) LSA_CHECK(nd_multi_batch_adjoint_run(ctx, J, f, conj, X[0]->dtype, nrhs, bd, ldb, xd, ldx));
+    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0.f;
+    LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    *avg_ms = (double)ms / iters;
+    return LSA_OK;
+}
+
 int lsa_ndlu_set_multi_transposed(lsa_ctx* ctx, lsa_ndlu* f, int on) {
     if (!ctx || !f) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_set_multi_transposed: null argument");
     f->multi_transposed = on != 0;

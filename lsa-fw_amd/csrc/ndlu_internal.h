@@ -200,7 +200,7 @@ struct lsa_ndlu {
     int64_t multi_stage_bytes = 0;
     bool multi_full = false;     // an allocation failed: no further columns are tried
     int64_t multi_bytes = 0;
-    int32_t multi_passes = 0;    // multi-column passes (two columns or more) of the last forward block solve
+    int32_t multi_passes = 0;    // multi-column passes (two columns or more) of the last forward block solve, or of the last block solve on a batch of sets in either direction
     int32_t multi_width = 0;     // widest pass of the last multi-column solve (1: column by column; 0: none yet)
     bool multi_transposed = false;  // lsa_ndlu_set_multi_transposed: block solves with trans != 0 run in wide passes too
 };
@@ -232,4 +232,8 @@ int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, co
 // sets may read one B, and B[z] == X[z] (with ldb == ldx) is allowed; not synchronised
 int ndlu_solve_multi_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb, void* const* X,
                                int64_t ldx);
+// ... and the transposed form, X[z][:, q] = C_z^-T B[z][:, q] (conj != 0: C_z^-H), under the same rules: every column with the bits of
+// ndlu_solve_adjoint_dev
+int ndlu_solve_multi_batch_adjoint_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb,
+                                       void* const* X, int64_t ldx);
 void ndlu_multi_free(lsa_ndlu* f);

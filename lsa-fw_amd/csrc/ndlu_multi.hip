@@ -9,7 +9,8 @@
 // The same kernels carry the R columns through J <= 16 factor sets of one analysis in one launch (lsa_ndlu_solve_multi_batch: the set
 // is the grid's last dimension, NdMultiPtrs<R, NB>); the one-set solve is their instance of set capacity one.
 // The transposed systems C^-T / C^-H have the same form (nd_sweepT_multi_kernel, ndlu_solve_multi_adjoint_dev): nd_sweepT_kernel with R
-// columns carried through every launch, on the update vectors of the same per-column buffers.
+// columns carried through every launch, on the update vectors of the same per-column buffers -- and, templated on the set capacity
+// like the forward kernels, through J <= 16 factor sets in one launch (lsa_ndlu_solve_multi_batch_adjoint).
 #include "ndlu_sweep_parts.h"
 
 namespace {
@@ -415,12 +416,27 @@ int nd_sweep_multi(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const VT* const*
 // of a lane adds the rows sl, sl + 4, ... in ascending order into one accumulator -- a sequence that runs on across chunks, so the
 // chunk of kMCH = 256 entries gives the bits of the solo kernel's kCH --, the slices are added as (p0 + p1) + (p2 + p3), and the
 // epilogue is the solo one.  No distributed node reaches this form.
+// The same kernel carries the R columns through J <= NB factor sets of one analysis (the set is the grid's last dimension, its
+// record picked from the launch arguments as in the forward kernels): one set is the batch of one (NB = 1, lsa_ndlu_solve_multi),
+// a batch of sets instantiates NB = kNdBatchMax whatever J (lsa_ndlu_solve_multi_batch_adjoint).  Every set runs the same grid and
+// tiles, so it gets the same bits either way.
 template <int R>
-struct NdMultiTPtrs {
+struct NdMultiTSet {
+    const void *lfac, *ufac;
     const void* rhs[R];
     void* x[R];
     void* ubuf[R];
 };
+// Every column keeps a pointer of its own for its right-hand side and its solution (unlike NdMultiSet: one base and a shared leading
+// dimension): without the slot rows and boundary vectors of the forward sweeps the record has room for them -- 2 + 3 R pointers, 3328
+// bytes at NB = 16, R = 8 -- and the one-set solve goes on staging an aliased column in that column's own buffer.
+template <int R, int NB>
+struct NdMultiTPtrs {
+    NdMultiTSet<R> set[NB];
+};
+static_assert(sizeof(NdMultiTPtrs<kNdMultiMax, kNdBatchMax>) == (size_t)(2 + 3 * kNdMultiMax) * 8 * kNdBatchMax, "transposed multi-set record layout");
+// the widest instance beside the kernel's three table pointers, with room for the 256 bytes of hidden arguments the compiler appends
+static_assert(sizeof(NdMultiTPtrs<kNdMultiMax, kNdBatchMax>) + 3 * sizeof(void*) + 256 <= 4096, "kernel arguments of a transposed multi-column, multi-set launch");
 
 // gather_updates for R update vectors: v[q] += the children's entries of ubuf[q] that land on front position j, the gather rows'
 // entries loaded once; per column the additions of gather_updates in their order
@@ -451,10 +467,9 @@ __device__ __forceinline__ void gather_updates_multi(const int32_t* __restrict__
     }
 }
 
-template <typename MT, typename VT, bool CONJ, bool DOWN, int R>
-__global__ __launch_bounds__(256) void nd_sweepT_multi_kernel(const NdSweepNode* __restrict__ lnodes, const MT* __restrict__ lfac,
-                                                              const MT* __restrict__ ufac, const int32_t* __restrict__ idx,
-                                                              const int32_t* __restrict__ gell, NdMultiTPtrs<R> p) {
+template <typename MT, typename VT, bool CONJ, bool DOWN, int R, int NB>
+__global__ __launch_bounds__(256) void nd_sweepT_multi_kernel(const NdSweepNode* __restrict__ lnodes, const int32_t* __restrict__ idx,
+                                                              const int32_t* __restrict__ gell, NdMultiTPtrs<R, NB> pp) {
     __shared__ VT vs[R * kMCH];
     __shared__ VT part[R][4][64];
     static_assert(kMCH == 256, "one staged entry per thread and column");
@@ -466,6 +481,9 @@ __global__ __launch_bounds__(256) void nd_sweepT_multi_kernel(const NdSweepNode*
     const int32_t K = DOWN ? nd.brow : nd.orows;
     const int32_t c0 = (int32_t)blockIdx.y * 64;
     if (c0 >= ncols || (DOWN && b == 0)) return;
+    const NdMultiTSet<R>& p = pp.set[blockIdx.z];  // (NB = 1: the grid has one layer; the uniform load of the record, as for a batch)
+    const MT* __restrict__ lfac = (const MT*)p.lfac;
+    const MT* __restrict__ ufac = (const MT*)p.ufac;
     const int32_t* ix = idx + nd.idx_off;
     const int32_t* ge = gell + nd.ge_off;
     const int tid = threadIdx.x, lane = tid & 63, sl = tid >> 6;
@@ -543,32 +561,33 @@ __global__ __launch_bounds__(256) void nd_sweepT_multi_kernel(const NdSweepNode*
     }
 }
 
-// x_q = C^-T b_q (C^-H b_q with CONJ) for the R columns of one pass: the launches of nd_sweepT for one rank and no distributed
-// node -- all levels upward, then all levels downward, the unmerged blocks throughout (the transposed sweeps do not use the
-// assembled top).  Column 0 runs on the factorisation's own update vectors, column q > 0 on f->multi[q - 1].ubuf; the slot rows
-// and boundary vectors of the forward sweeps are not touched.
-template <typename MT, typename VT, bool CONJ, int R>
-int nd_sweepT_multi(lsa_ctx* ctx, lsa_ndlu* f, const VT* const* b, VT* const* x) {
+// x_zq = C_z^-T b_zq (C_z^-H b_zq with CONJ) for the R columns of one pass on J <= NB factor sets of one analysis: the launches of
+// nd_sweepT for one rank and no distributed node -- all levels upward, then all levels downward, the unmerged blocks throughout (the
+// transposed sweeps do not use the assembled top) --, the set as the grids' last dimension, on the tables of f[0].  The caller gave
+// p the columns' right-hand sides and solutions; column 0 of a set runs on the factorisation's own update vectors, column q > 0 on
+// f[z]->multi[q - 1].ubuf; the slot rows and boundary vectors of the forward sweeps are not touched.
+template <typename MT, typename VT, bool CONJ, int R, int NB>
+int nd_sweepT_multi(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, NdMultiTPtrs<R, NB>& p) {
     hipStream_t st = ctx->stream;
-    const MT* lfac = (const MT*)f->d_lfac;
-    const MT* ufac = (const MT*)f->d_ufac;
-    NdMultiTPtrs<R> p;
-    for (int q = 0; q < R; ++q) {
-        p.rhs[q] = b[q];
-        p.x[q] = x[q];
-        p.ubuf[q] = q == 0 ? f->d_ubuf : f->multi[(size_t)q - 1].ubuf;
+    const lsa_ndlu* f0 = f[0];
+    if (J < 1 || J > NB) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu: a transposed block solve on %d factor sets, at most %d", J, NB);
+    for (int32_t z = 0; z < J; ++z) {
+        NdMultiTSet<R>& s = p.set[z];
+        s.lfac = f[z]->d_lfac;
+        s.ufac = f[z]->d_ufac;
+        for (int q = 0; q < R; ++q) s.ubuf[q] = q == 0 ? f[z]->d_ubuf : f[z]->multi[(size_t)q - 1].ubuf;
     }
-    for (size_t li = 0; li < f->levels.size(); ++li) {
-        const NdLevel& L = f->levels[li];
+    for (size_t li = 0; li < f0->levels.size(); ++li) {
+        const NdLevel& L = f0->levels[li];
         if (L.fwd_tiles > 0)
-            hipLaunchKernelGGL((nd_sweepT_multi_kernel<MT, VT, CONJ, false, R>), dim3(L.node_count, (L.max_f + 63) / 64), dim3(256), 0, st,
-                               f->d_lnodes + L.node_begin, lfac, ufac, f->d_idx, f->d_gell, p);
+            hipLaunchKernelGGL((nd_sweepT_multi_kernel<MT, VT, CONJ, false, R, NB>), dim3(L.node_count, (L.max_f + 63) / 64, J), dim3(256), 0, st,
+                               f0->d_lnodes + L.node_begin, f0->d_idx, f0->d_gell, p);
     }
-    for (size_t l = f->levels.size(); l-- > 0;) {
-        const NdLevel& L = f->levels[l];
+    for (size_t l = f0->levels.size(); l-- > 0;) {
+        const NdLevel& L = f0->levels[l];
         if (L.bwd_tiles > 0)
-            hipLaunchKernelGGL((nd_sweepT_multi_kernel<MT, VT, CONJ, true, R>), dim3(L.node_count, (L.max_m + 63) / 64), dim3(256), 0, st,
-                               f->d_lnodes + L.node_begin, lfac, ufac, f->d_idx, f->d_gell, p);
+            hipLaunchKernelGGL((nd_sweepT_multi_kernel<MT, VT, CONJ, true, R, NB>), dim3(L.node_count, (L.max_m + 63) / 64, J), dim3(256), 0, st,
+                               f0->d_lnodes + L.node_begin, f0->d_idx, f0->d_gell, p);
     }
     LSA_HIP_CHECK(ctx, hipGetLastError());
     return LSA_OK;
@@ -702,12 +721,60 @@ int nd_solve_multi_adjoint(lsa_ctx* ctx, lsa_ndlu* f, int32_t nrhs, const VT* B,
                 b[q] = (const VT*)tmp;
             }
         }
+        auto run = [&](auto width) {
+            constexpr int W = decltype(width)::value;
+            NdMultiTPtrs<W, 1> p;
+            for (int q = 0; q < W; ++q) p.set[0].rhs[q] = b[q], p.set[0].x[q] = x[q];
+            return nd_sweepT_multi<MT, VT, CONJ, W, 1>(ctx, 1, &f, p);
+        };
         if constexpr (sizeof(VT) == 8) {
-            if (R == 8) LSA_CHECK((nd_sweepT_multi<MT, VT, CONJ, 8>(ctx, f, b, x)));
+            if (R == 8) LSA_CHECK(run(std::integral_constant<int, 8>{}));
         }
-        if (R == 4) LSA_CHECK((nd_sweepT_multi<MT, VT, CONJ, 4>(ctx, f, b, x)));
-        if (R == 2) LSA_CHECK((nd_sweepT_multi<MT, VT, CONJ, 2>(ctx, f, b, x)));
+        if (R == 4) LSA_CHECK(run(std::integral_constant<int, 4>{}));
+        if (R == 2) LSA_CHECK(run(std::integral_constant<int, 2>{}));
         f->multi_width = std::max(f->multi_width, R);
+        q0 += R;
+    }
+    return LSA_OK;
+}
+
+// ... and on J <= kNdBatchMax factor sets: the passes of nd_solve_multi for a batch (the widest every set has buffers for, an aliased
+// block staged as there), a last single column through the batched solo transposed sweeps
+template <typename MT, typename VT, bool CONJ>
+int nd_solve_multi_batch_adjoint(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int32_t nrhs, const VT* const* B, int64_t ldb, VT* const* X, int64_t ldx) {
+    const int32_t want = nd_pass_width(nrhs, nd_multi_cap(sizeof(VT)));
+    int32_t avail = want;
+    for (int32_t z = 0; z < J; ++z) avail = std::min(avail, nd_multi_ensure(ctx, f[z], want));
+    for (int32_t z = 0; z < J; ++z) f[z]->multi_width = 1, f[z]->multi_passes = 0;
+    for (int32_t q0 = 0; q0 < nrhs;) {
+        const int32_t R = nd_pass_width(nrhs - q0, avail);
+        const VT* b[kNdBatchMax];
+        VT* x[kNdBatchMax];
+        for (int32_t z = 0; z < J; ++z) {
+            b[z] = B[z] + (int64_t)q0 * ldb;
+            x[z] = X[z] + (int64_t)q0 * ldx;
+        }
+        if (R == 1) {
+            LSA_CHECK(ndlu_solve_batch_adjoint_dev(ctx, J, f, CONJ, scalar_traits<VT>::dtype, (const void**)b, (void* const*)x));
+            q0 += 1;
+            continue;
+        }
+        for (int32_t z = 0; z < J; ++z)
+            if (b[z] == x[z]) LSA_CHECK(nd_multi_stage(ctx, f[z], R, b[z], ldb, &b[z]));
+        auto run = [&](auto width) {
+            constexpr int W = decltype(width)::value;
+            NdMultiTPtrs<W, kNdBatchMax> p;
+            memset(&p, 0, sizeof p);
+            for (int32_t z = 0; z < J; ++z)
+                for (int q = 0; q < W; ++q) p.set[z].rhs[q] = b[z] + (int64_t)q * ldb, p.set[z].x[q] = x[z] + (int64_t)q * ldx;
+            return nd_sweepT_multi<MT, VT, CONJ, W, kNdBatchMax>(ctx, J, f, p);
+        };
+        if constexpr (sizeof(VT) == 8) {
+            if (R == 8) LSA_CHECK(run(std::integral_constant<int, 8>{}));
+        }
+        if (R == 4) LSA_CHECK(run(std::integral_constant<int, 4>{}));
+        if (R == 2) LSA_CHECK(run(std::integral_constant<int, 2>{}));
+        for (int32_t z = 0; z < J; ++z) f[z]->multi_width = std::max(f[z]->multi_width, R), ++f[z]->multi_passes;
         q0 += R;
     }
     return LSA_OK;
@@ -767,4 +834,23 @@ int ndlu_solve_multi_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype
     // (real factors: C^H = C^T, one instance)
     if (vdtype == LSA_C128) return nd_solve_multi_adjoint<double, cplx, false>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
     return nd_solve_multi_adjoint<double, double, false>(ctx, f, nrhs, (const double*)B, ldb, (double*)X, ldx);
+}
+
+// ... and X[z][:, q] = C_z^-T B[z][:, q] (C_z^-H with conj != 0) on J <= kNdBatchMax factor sets of one analysis (nd_batch_compatible),
+// every launch carrying all columns of a pass for all sets; the rules of ndlu_solve_multi_batch_dev for B and X
+int ndlu_solve_multi_batch_adjoint_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb,
+                                       void* const* X, int64_t ldx) {
+    const char* who = "lsa_ndlu_solve_multi_batch_adjoint";
+    if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: J = %d outside [1, %d]", who, J, kNdBatchMax);
+    for (int32_t z = 0; z < J; ++z)
+        if (f[z]->S.nranks > 1 || f[z]->S.has_dist) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the multi-column sweeps need one rank and no distributed node", who);
+    if (f[0]->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: complex factors need complex vectors", who);
+    if (f[0]->S.n == 0) return LSA_OK;
+    if (f[0]->dtype == LSA_C128) {
+        if (conj) return nd_solve_multi_batch_adjoint<cplx, cplx, true>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
+        return nd_solve_multi_batch_adjoint<cplx, cplx, false>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
+    }
+    // (real factors: C^H = C^T, one instance)
+    if (vdtype == LSA_C128) return nd_solve_multi_batch_adjoint<double, cplx, false>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
+    return nd_solve_multi_batch_adjoint<double, double, false>(ctx, J, f, nrhs, (const double* const*)B, ldb, (double* const*)X, ldx);
 }

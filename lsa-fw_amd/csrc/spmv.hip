@@ -524,6 +524,12 @@ static int ensure_transpose(lsa_ctx* ctx, const lsa_mat* A) {
     return LSA_OK;
 }
 
+int k_transpose_index(lsa_ctx* ctx, const lsa_mat* A, const TransposeIndex** out) {
+    LSA_CHECK(ensure_transpose(ctx, A));
+    *out = A->h_shared->tr.get();
+    return LSA_OK;
+}
+
 int k_spmv_transpose(lsa_ctx* ctx, const lsa_mat* A, int conj, int xdtype, const void* x, void* y) {
     if (A->row0 != 0 || A->n != A->ncols) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose: sharded matrices are not supported");
     LSA_CHECK(ensure_transpose(ctx, A));

@@ -3,11 +3,13 @@
 target cannot answer.
 
     python lsa-fw_amd/examples/region.py [--case S5k] [--region A B C D] [--ellipse RE IM RX RY] [--nodes 16] [--subspace 48]
+                                          [--two-sided]
 
 ``--region A B C D`` is the rectangle ``A < Re < B``, ``C < Im < D`` (the arguments of ``set_interval_complex``), solved on its
 circumscribing ellipse; the default is the circle of radius 0.12 about the least stable eigenvalue 0.018 + 0.738j of the wake at
 Re = 50.  The spectrum is dense: when the run reports a full subspace, raise ``--subspace`` (the printed estimate helps) or shrink the
-region.  Needs an AMD GPU (there is no CPU fallback).
+region.  ``--two-sided`` adds the left phase on the same factor sets and prints every eigenvalue with its condition number ``kappa``
+and its left residual.  Needs an AMD GPU (there is no CPU fallback).
 """
 
 from __future__ import annotations
@@ -34,6 +36,7 @@ def main() -> None:
     ap.add_argument("--atol", type=float, default=1e-10)
     ap.add_argument("--max-it", type=int, default=20)
     ap.add_argument("--batch-nodes", action="store_true", help="solve every iteration's block on all nodes in lockstep (same bytes; one more block per node)")
+    ap.add_argument("--two-sided", action="store_true", help="also the left phase: left eigenvectors, and kappa and the left residual of every eigenvalue")
     args = ap.parse_args()
     logging.basicConfig(level=logging.WARNING)
     if args.region is not None:
@@ -44,7 +47,7 @@ def main() -> None:
         region = Ellipse(complex(fem.SIGMA_RE50), 0.12, 0.12)
     es = fem.cylinder_case(args.case)
     rs = RegionEigenSolver(es.A, es.M, RegionConfig(nodes=args.nodes, subspace=args.subspace, atol=args.atol, max_it=args.max_it,
-                                                     batch_nodes=args.batch_nodes))
+                                                     batch_nodes=args.batch_nodes, two_sided=args.two_sided))
     res = rs.solve(region)
     st = res.stats
     print(f"{args.case}: n = {es.n}; {region}")
@@ -54,8 +57,13 @@ def main() -> None:
           f"Gram {st['seconds_gram']:.4f}, host dense {st['seconds_dense']:.4f}, total {st['seconds_total']:.4f}; {st['block_solves']} column solves, "
           f"{st['refined_solves']} refined" + (f"; nodes in lockstep: {st['batched_groups']} batched groups, {st['batched_columns']} column solves"
                                                 if st["batch_nodes"] else ""))
-    for lam, r in zip(res.eigenvalues, res.residuals):
-        print(f"  {lam.real:+.12f} {lam.imag:+.12f}j   residual {r:.2e}")
+    if args.two_sided:
+        lt = st["left"]
+        print(f"left phase: {lt['iterations']} iterations, {lt['block_solves']} column solves ({lt['refined_solves']} refined, {lt['batched_columns']} in "
+              f"lockstep), block solves {lt['seconds_solve']:.4f} s; left_complete = {res.left_complete}")
+    for i, (lam, r) in enumerate(zip(res.eigenvalues, res.residuals)):
+        left = f"   kappa {res.condition_numbers[i]:.3e}   left residual {res.left_residuals[i]:.2e}" if res.left_complete else ""
+        print(f"  {lam.real:+.12f} {lam.imag:+.12f}j   residual {r:.2e}" + left)
     rs.release()
 
 

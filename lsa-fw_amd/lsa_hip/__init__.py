@@ -142,6 +142,24 @@ class lsa_contour_stats(ctypes.Structure):
     ]
 
 
+class lsa_contour_left_stats(ctypes.Structure):
+    _fields_ = [
+        ("solves", ctypes.c_int32),
+        ("iterations", ctypes.c_int32),
+        ("block_solves", ctypes.c_int64),
+        ("refined_solves", ctypes.c_int64),
+        ("backward_accepted", ctypes.c_int64),
+        ("groups", ctypes.c_int64),
+        ("batched_columns", ctypes.c_int64),
+        ("serial_columns", ctypes.c_int64),
+        ("seconds_factor", ctypes.c_double),
+        ("seconds_solve", ctypes.c_double),
+        ("seconds_product", ctypes.c_double),
+        ("seconds_gram", ctypes.c_double),
+        ("seconds_dense", ctypes.c_double),
+    ]
+
+
 class lsa_contour_batch_stats(ctypes.Structure):
     _fields_ = [
         ("enabled", ctypes.c_int32),
@@ -233,6 +251,8 @@ SIGNATURES = {
     "lsa_ndlu_solve_multi_time": (ctypes.c_int, [_P, _P, ctypes.c_int, _I32, _P, _I64, _P, _I64, ctypes.c_int, ctypes.POINTER(_DBL)]),
     "lsa_ndlu_solve_multi_batch": (ctypes.c_int, [_P, _I32, _PP, ctypes.c_int, _I32, _PP, _I64, _PP, _I64]),
     "lsa_ndlu_solve_multi_batch_time": (ctypes.c_int, [_P, _I32, _PP, ctypes.c_int, _I32, _PP, _I64, _PP, _I64, ctypes.c_int, ctypes.POINTER(_DBL)]),
+    "lsa_ndlu_solve_multi_batch_adjoint": (ctypes.c_int, [_P, _I32, _PP, ctypes.c_int, _I32, _PP, _I64, _PP, _I64]),
+    "lsa_ndlu_solve_multi_batch_adjoint_time": (ctypes.c_int, [_P, _I32, _PP, ctypes.c_int, _I32, _PP, _I64, _PP, _I64, ctypes.c_int, ctypes.POINTER(_DBL)]),
     "lsa_ndlu_set_multi_transposed": (ctypes.c_int, [_P, _P, ctypes.c_int]),
     "lsa_ndlu_multi_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "lsa_ndlu_info": (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64),
@@ -296,6 +316,7 @@ SIGNATURES = {
     "lsa_growth_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
     "lsa_growth_solve": (ctypes.c_int, [_P, _P, ctypes.POINTER(lsa_ks_options), _P, _I32, _P, _P, _P, _P, _P, _P, ctypes.POINTER(lsa_ks_result), _P]),
     "lsa_spmm": (ctypes.c_int, [_P, _P, _I32, _P, _I64, _P, _I64]),
+    "lsa_spmm_transpose": (ctypes.c_int, [_P, _P, ctypes.c_int, _I32, _P, _I64, _P, _I64]),
     "lsa_block_gram": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _P, _I64, _P]),
     "lsa_contour_create": (ctypes.c_int, [_P, _P, _P, _I32, _DBL * 2, _DBL * 2, _I32, ctypes.c_int, _DBL, _PP]),
     "lsa_contour_destroy": (None, [_P]),
@@ -304,6 +325,8 @@ SIGNATURES = {
     "lsa_contour_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_contour_stats)]),
     "lsa_contour_set_batch_nodes": (ctypes.c_int, [_P, _P, ctypes.c_int]),
     "lsa_contour_batch_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_contour_batch_stats)]),
+    "lsa_contour_solve_left": (ctypes.c_int, [_P, _P, _DBL, _I32, _P, _I32, _P, _P, _P, ctypes.POINTER(lsa_contour_result)]),
+    "lsa_contour_left_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_contour_left_stats)]),
     "lsa_shifted_spmm": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P]),
     "lsa_stochastic_create": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _I32, _DBL, _PP]),
     "lsa_stochastic_destroy": (None, [_P]),
@@ -643,6 +666,14 @@ class CsrMatrix:
         self.ctx.check(self.ctx._lib.lsa_spmm(self.ctx.handle, self.handle, int(ncols), X.handle, int(n if ldx is None else ldx), Y.handle,
                                               int(n if ldy is None else ldy)))
 
+    def matmat_transpose(self, X: DeviceVector, Y: DeviceVector, ncols: int, conj: bool = True, ldx: int | None = None,
+                         ldy: int | None = None) -> None:
+        """``Y[:, c] = self^H @ X[:, c]`` (``conj``) or ``self^T @ X[:, c]`` for ``ncols`` columns (``lsa_spmm_transpose``), blocks as
+        in :meth:`matmat`.  No atomics: two calls give the same bytes; a column need not hold the bytes of :meth:`rmatvec`."""
+        n = self.shape[0]
+        self.ctx.check(self.ctx._lib.lsa_spmm_transpose(self.ctx.handle, self.handle, int(bool(conj)), int(ncols), X.handle,
+                                                        int(n if ldx is None else ldx), Y.handle, int(n if ldy is None else ldy)))
+
     def matvec_info(self, vector_dtype=np.complex128) -> dict:
         """Kernel ``lsa_spmv`` launches for this matrix / vector type and the bytes it moves per launch."""
         name = ctypes.create_string_buffer(128)
@@ -945,7 +976,7 @@ class NdLu:
         """``Xs[z][:, q] = C_z^-1 Bs[z][:, q]`` for ``nrhs`` columns on up to 16 factorisations of one analysis
         (``lsa_ndlu_solve_multi_batch``): every launch of the sweeps carries all columns of a pass for all sets.  The blocks share
         ``ldb`` and ``ldx`` (default ``n``); several sets may read one ``B``; ``Bs[z] is Xs[z]`` solves in place.  Every column is
-        bit-identical to :meth:`solve`.  ``trans`` must be ``"N"``: the transposed form is not built."""
+        bit-identical to :meth:`solve`.  ``trans`` must be ``"N"``: the transposed form is :meth:`solve_multi_batch_adjoint`."""
         ctx, args = NdLu._multi_batch_args(factors, Bs, Xs, nrhs, ldb, ldx, trans)
         ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch(*args))
 
@@ -956,6 +987,42 @@ class NdLu:
         ctx, args = NdLu._multi_batch_args(factors, Bs, Xs, nrhs, ldb, ldx, "N")
         ms = _DBL(0.0)
         ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch_time(*args, int(iters), ctypes.byref(ms)))
+        return ms.value
+
+    @staticmethod
+    def _multi_batch_adjoint_args(factors, Bs, Xs, nrhs, conj, ldb, ldx):
+        # (the two argument errors come first: nothing of the library, not even a context, is touched before them)
+        J = len(factors)
+        if J < 1 or J > NDLU_BATCH_MAX:
+            raise ValueError(f"solve_multi_batch_adjoint takes between 1 and {NDLU_BATCH_MAX} factorisations, got {J}")
+        if len(Bs) != J or len(Xs) != J:
+            raise ValueError(f"solve_multi_batch_adjoint needs as many blocks B and X as factorisations ({J}), got {len(Bs)} and {len(Xs)}")
+        ctx = factors[0].ctx
+        if any(f.ctx is not ctx for f in factors) or any(v.ctx is not ctx for v in list(Bs) + list(Xs)):
+            raise ValueError("solve_multi_batch_adjoint: the factorisations and vectors must live in one context")
+        arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
+        n = factors[0].n
+        return ctx, (ctx.handle, J, arr(factors), int(bool(conj)), int(nrhs), arr(Bs), int(n if ldb is None else ldb), arr(Xs),
+                     int(n if ldx is None else ldx))
+
+    @staticmethod
+    def solve_multi_batch_adjoint(factors: "list[NdLu]", Bs: "list[DeviceVector]", Xs: "list[DeviceVector]", nrhs: int, conj: bool = True,
+                                  ldb: int | None = None, ldx: int | None = None) -> None:
+        """``Xs[z][:, q] = C_z^-H Bs[z][:, q]`` (``conj``) or ``C_z^-T Bs[z][:, q]`` for ``nrhs`` columns on up to 16 factorisations of
+        one analysis (``lsa_ndlu_solve_multi_batch_adjoint``): every launch of the transposed sweeps carries all columns of a pass for
+        all sets.  The rules for the blocks are those of :meth:`solve_multi_batch`.  Every column is bit-identical to
+        :meth:`solve_adjoint`."""
+        ctx, args = NdLu._multi_batch_adjoint_args(factors, Bs, Xs, nrhs, conj, ldb, ldx)
+        ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch_adjoint(*args))
+
+    @staticmethod
+    def time_solve_multi_batch_adjoint(factors: "list[NdLu]", Bs: "list[DeviceVector]", Xs: "list[DeviceVector]", nrhs: int, iters: int,
+                                       conj: bool = True, ldb: int | None = None, ldx: int | None = None) -> float:
+        """Mean milliseconds of one transposed block solve on all sets over ``iters`` back-to-back repetitions
+        (``lsa_ndlu_solve_multi_batch_adjoint_time``)."""
+        ctx, args = NdLu._multi_batch_adjoint_args(factors, Bs, Xs, nrhs, conj, ldb, ldx)
+        ms = _DBL(0.0)
+        ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch_adjoint_time(*args, int(iters), ctypes.byref(ms)))
         return ms.value
 
     def set_multi_transposed(self, on: bool) -> None:
@@ -1430,7 +1497,7 @@ class ContourSolver:
         p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
         self.ctx.check(self.ctx._lib.lsa_contour_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
 
-    def solve(self, tol: float, max_it: int, Y0: np.ndarray, max_out: int | None = None) -> dict:
+    def solve(self, tol: float, max_it: int, Y0: np.ndarray, max_out: int | None = None, _entry: str = "lsa_contour_solve") -> dict:
         """The iteration from the start block ``Y0`` (``n x subspace``, the matrices' own row numbering).  Returns the Ritz pairs
         inside the ellipse (``eigenvalues``, ``eigenvectors``, ``residuals``) and the fields of ``lsa_contour_result``."""
         Y0 = np.asfortranarray(Y0, dtype=np.complex128)
@@ -1441,13 +1508,26 @@ class ContourSolver:
         res = np.zeros(max(max_out, 1), dtype=np.float64)
         X = np.empty((self.n, max_out), dtype=np.complex128, order="F")
         out = lsa_contour_result()
-        self.ctx.check(self.ctx._lib.lsa_contour_solve(self.ctx.handle, self.handle, float(tol), int(max_it), _ptr(Y0), max_out, _ptr(lam), _ptr(X),
-                                                       _ptr(res), ctypes.byref(out)))
+        self.ctx.check(getattr(self.ctx._lib, _entry)(self.ctx.handle, self.handle, float(tol), int(max_it), _ptr(Y0), max_out, _ptr(lam), _ptr(X),
+                                                      _ptr(res), ctypes.byref(out)))
         k = out.nout
         d = {name: getattr(out, name) for name, _ in lsa_contour_result._fields_}
         d["complete"] = bool(out.complete)
         d.update(eigenvalues=lam[:k].copy(), eigenvectors=np.asfortranarray(X[:, :k]), residuals=res[:k].copy())
         return d
+
+    def solve_left(self, tol: float, max_it: int, Y0: np.ndarray, max_out: int | None = None) -> dict:
+        """The left phase on the same factor sets (``lsa_contour_solve_left``): the iteration of :meth:`solve` on the adjoint pencil.
+        ``eigenvalues`` are the values in the caller's region, ``eigenvectors`` the left eigenvectors ``w`` (``w^H A = lambda w^H M``),
+        ``residuals`` those of ``A^H w = conj(lambda) M^H w``.  The books of :meth:`info` and :meth:`batch_info` are left as they were:
+        the left phases' are in :meth:`left_info`."""
+        return self.solve(tol, max_it, Y0, max_out, _entry="lsa_contour_solve_left")
+
+    def left_info(self) -> dict:
+        """``lsa_contour_left_info``: what the left phases of this handle did and took."""
+        st = lsa_contour_left_stats()
+        self.ctx.check(self.ctx._lib.lsa_contour_left_info(self.handle, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in lsa_contour_left_stats._fields_}
 
     def info(self) -> dict:
         """``lsa_contour_info``: kept or refactorised factor sets, device bytes of the handle's own buffers, the phase times, and the

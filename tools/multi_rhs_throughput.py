@@ -25,7 +25,9 @@ medians are recorded (all rounds are kept in the file).  ``--parent-solo-us`` is
 J factorisations of the case at J shifts on one ordering, one block of ``--nrhs`` columns (the first figure given; default 4) per
 set.  ``NdLu.time_solve_multi_batch`` on all sets against ``NdLu.time_solve_multi`` looped over the sets, in the same process,
 alternating for ``--rounds`` rounds after a warm-up; the medians are recorded as milliseconds per column per set.  Every block is
-checked bit for bit against ``solve_multi`` on its set alone.
+checked bit for bit against ``solve_multi`` on its set alone.  With ``--trans T`` / ``H`` the transposed form is measured
+(``NdLu.time_solve_multi_batch_adjoint`` against ``time_solve_multi(trans=...)`` with the transposed switch on, looped over the sets;
+``--out`` then defaults to ``profiles/multi_batch_adjoint.json``).
 """
 
 from __future__ import annotations
@@ -108,8 +110,9 @@ def measure_transposed(case: str, counts: list[int], iters: int, trans: str, rou
     return out
 
 
-def measure_sets(case: str, J: int, nrhs: int, iters: int, rounds: int) -> dict:
-    """``solve_multi_batch`` on J factor sets against ``solve_multi`` looped over them: ms per column per set."""
+def measure_sets(case: str, J: int, nrhs: int, iters: int, rounds: int, trans: str = "N") -> dict:
+    """``solve_multi_batch`` (``trans`` T / H: ``solve_multi_batch_adjoint``) on J factor sets against ``solve_multi`` in that direction
+    looped over them: ms per column per set."""
     import statistics
 
     import numpy as np
@@ -140,14 +143,20 @@ def measure_sets(case: str, J: int, nrhs: int, iters: int, rounds: int) -> dict:
     dB = lsa_hip.DeviceVector.from_numpy(ctx, B.reshape(-1, order="F"))
     dXs = [lsa_hip.DeviceVector(ctx, n * nrhs, np.complex128) for _ in range(J)]
     dY = lsa_hip.DeviceVector(ctx, n * nrhs, np.complex128)
-    lsa_hip.NdLu.solve_multi_batch(fs, [dB] * J, dXs, nrhs)
+    loop_iters = max(3, iters // J)
+    if trans == "N":
+        lsa_hip.NdLu.solve_multi_batch(fs, [dB] * J, dXs, nrhs)
+        batched = lambda: lsa_hip.NdLu.time_solve_multi_batch(fs, [dB] * J, dXs, nrhs, iters=loop_iters)  # noqa: E731
+    else:
+        for f in fs:
+            f.set_multi_transposed(True)  # (the looped side's wide passes; the batch entry does not read the switch)
+        lsa_hip.NdLu.solve_multi_batch_adjoint(fs, [dB] * J, dXs, nrhs, conj=trans == "H")
+        batched = lambda: lsa_hip.NdLu.time_solve_multi_batch_adjoint(fs, [dB] * J, dXs, nrhs, iters=loop_iters, conj=trans == "H")  # noqa: E731
     same = True
     for f, dX in zip(fs, dXs):
-        f.solve_multi(dB, dY, nrhs)
+        f.solve_multi(dB, dY, nrhs, trans=trans)
         same = same and bool(np.array_equal(dX.numpy(), dY.numpy()))
-    loop_iters = max(3, iters // J)
-    looped = lambda: sum(f.time_solve_multi(dB, dY, nrhs, iters=loop_iters) for f in fs)  # noqa: E731
-    batched = lambda: lsa_hip.NdLu.time_solve_multi_batch(fs, [dB] * J, dXs, nrhs, iters=loop_iters)  # noqa: E731
+    looped = lambda: sum(f.time_solve_multi(dB, dY, nrhs, iters=loop_iters, trans=trans) for f in fs)  # noqa: E731
     looped(), batched()  # warm-up
     loop_rounds, batch_rounds = [], []
     for _ in range(rounds):
@@ -155,10 +164,10 @@ def measure_sets(case: str, J: int, nrhs: int, iters: int, rounds: int) -> dict:
         batch_rounds.append(batched())
     lm, bm = statistics.median(loop_rounds), statistics.median(batch_rounds)
     per = 1.0 / (J * nrhs)
-    out = {"case": case, "n": int(n), "sets": J, "nrhs": nrhs, "rounds": rounds, "iters": loop_iters, "apply_launches": int(fs[0].info()["apply_launches"]),
+    out = {"case": case, "n": int(n), "sets": J, "nrhs": nrhs, "trans": trans, "rounds": rounds, "iters": loop_iters, "apply_launches": int(fs[0].info()["apply_launches"]),
            "looped_ms_per_column_per_set": lm * per, "batched_ms_per_column_per_set": bm * per, "looped_over_batched": lm / bm,
            "looped_ms_rounds": loop_rounds, "batched_ms_rounds": batch_rounds, "bit_identical_to_solve_multi": same, "width": fs[0].multi_info()["width"]}
-    print(f"{case} sets={J} nrhs={nrhs}: looped solve_multi {lm * per * 1e3:.1f} us, solve_multi_batch {bm * per * 1e3:.1f} us per column per set "
+    print(f"{case} sets={J} nrhs={nrhs} trans={trans}: looped solve_multi {lm * per * 1e3:.1f} us, batched {bm * per * 1e3:.1f} us per column per set "
           f"({lm / bm:.2f}x), bits {'same' if same else 'DIFFER'}", flush=True)
     return out
 
@@ -232,9 +241,9 @@ def main() -> None:
     ap.add_argument("--trans", choices=["N", "T", "H"], default="N", help="N: C^-1 (the default); T / H: the transposed / adjoint block solve in wide passes")
     ap.add_argument("--rounds", type=int, default=3, help="--trans T / H: rounds of (solo, every nrhs) whose medians are recorded")
     ap.add_argument("--sets", type=int, default=0, help="J > 0: the block solve on J factor sets (solve_multi_batch) against solve_multi looped over them")
-    ap.add_argument("--out", default=None, help="default: profiles/multi_rhs.json, or profiles/multi_rhs_adjoint.json with --trans T / H, or profiles/multi_batch.json with --sets")
+    ap.add_argument("--out", default=None, help="default: profiles/multi_rhs.json, or profiles/multi_rhs_adjoint.json with --trans T / H, or profiles/multi_batch.json (multi_batch_adjoint.json) with --sets")
     args = ap.parse_args()
-    name = "multi_batch.json" if args.sets else "multi_rhs.json" if args.trans == "N" else "multi_rhs_adjoint.json"
+    name = ("multi_batch.json" if args.trans == "N" else "multi_batch_adjoint.json") if args.sets else "multi_rhs.json" if args.trans == "N" else "multi_rhs_adjoint.json"
     path = Path(args.out) if args.out else ROOT / "profiles" / name
     doc = json.loads(path.read_text()) if path.exists() else {"tool": "tools/multi_rhs_throughput.py", "runs": []}
     if args.parent_solo_us is not None and len(args.parent_solo_us) != len(args.cases):
@@ -242,7 +251,7 @@ def main() -> None:
     for i, case in enumerate(args.cases):
         parent = None if args.parent_solo_us is None else args.parent_solo_us[i]
         if args.sets:
-            doc["runs"].append(measure_sets(case, args.sets, 4 if len(args.nrhs) > 1 else args.nrhs[0], args.iters, args.rounds))
+            doc["runs"].append(measure_sets(case, args.sets, 4 if len(args.nrhs) > 1 else args.nrhs[0], args.iters, args.rounds, args.trans))
         elif args.trans == "N":
             doc["runs"].append(measure(case, args.nrhs, args.iters, parent))
         else:
