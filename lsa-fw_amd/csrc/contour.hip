@@ -1,8 +1,8 @@
 // Region eigensolver: all eigenvalues of A x = lambda M x inside an ellipse, with a statement of completeness, by a contour-integral
 // (FEAST-type) subspace iteration on an n x L complex128 block Y (column-major):
 //     B = M Y                                                  ci_spmm_kernel
-//     for every node z_k of the contour: X = C_k^-1 B on the nested-dissection LU of C_k = A - z_k M (ndlu_solve_multi_dev; under
-//         lsa_contour_set_batch_nodes all nodes' X_k first, in lockstep: ndlu_solve_multi_batch_dev), each
+//     for every node z_k of the contour: X = C_k^-1 B on the nested-dissection LU of C_k = A - z_k M (ndlu_solve_run; under
+//         lsa_contour_set_batch_nodes all nodes' X_k first, in lockstep: the same request on a batch of sets), each
 //         column checked (R = C_k X by ci_spmm_kernel, the three sums by ci_residual_kernel), then Q (+)= -w_k X
 //                                                              ci_accumulate_kernel
 //     U = orth(Q) through the Gram matrix, twice               ci_gram_kernel + host Hermitian eigen-decomposition + k_basis_gemm
@@ -457,7 +457,10 @@ int ct_mul(lsa_ctx* ctx, bool adj, const lsa_mat* A, int32_t cols, const cplx* X
     return adj ? k_spmm_transpose(ctx, A, 1, cols, X, n, Y, n) : k_spmm(ctx, A, cols, X, n, Y, n);
 }
 int ct_solve_dev(lsa_ctx* ctx, bool adj, lsa_ndlu* f, int32_t cols, const cplx* B, int64_t n, cplx* X) {
-    return adj ? ndlu_solve_multi_adjoint_dev(ctx, f, 1, LSA_C128, cols, B, n, X, n) : ndlu_solve_multi_dev(ctx, f, LSA_C128, cols, B, n, X, n);
+    const void* b = B;
+    void* x = X;
+    const NdSolve rq = {1, &f, false, adj ? 2 : 0, LSA_C128, cols, &b, n, &x, n, adj ? "lsa_contour_solve_left" : "lsa_contour_solve"};
+    return ndlu_solve_run(ctx, rq);
 }
 
 // the accepted columns of a node's block solve into the counters (s: the three sums per column of ct_column_sums)
@@ -543,13 +546,10 @@ int ct_batch_solve(lsa_ctx* ctx, lsa_contour* h, bool adj, int32_t cols, std::ve
             xs[z] = h->XN + (size_t)run.node[z] * (size_t)n * (size_t)h->L;
             solved[(size_t)run.node[z]] = 1;
         }
-        if (cols > 1) {
-            rc = adj ? ndlu_solve_multi_batch_adjoint_dev(ctx, run.J, run.f, 1, LSA_C128, cols, bs, n, xs, n)
-                     : ndlu_solve_multi_batch_dev(ctx, run.J, run.f, LSA_C128, cols, bs, n, xs, n);
-            h->batch_groups += run.f[0]->multi_passes;
-        } else {
-            rc = adj ? ndlu_solve_batch_adjoint_dev(ctx, run.J, run.f, 1, LSA_C128, bs, xs) : ndlu_solve_batch_dev(ctx, run.J, run.f, LSA_C128, bs, xs);
-        }
+        const NdSolve rq = {run.J, run.f, true, adj ? 2 : 0, LSA_C128, cols, bs, n, xs, n, adj ? "lsa_contour_solve_left" : "lsa_contour_solve"};
+        NdSolveInfo ran;
+        rc = ndlu_solve_run(ctx, rq, &ran);
+        h->batch_groups += ran.passes;
         h->batch_columns += (int64_t)run.J * cols;
     }
     h->sec_solve += now_s() - t0;

@@ -252,6 +252,21 @@ inline int dot_chunks(int64_t n, int64_t* rows_per_chunk) {
         if (_rc != LSA_OK) return _rc; \
     } while (0)
 
+// the timed entries (lsa_*_time): `run` queued once beforehand if `warm` (what a first call builds stays outside the measurement),
+// then iters times between the context's two events; the mean milliseconds of one run
+template <typename F>
+int lsa_time_runs(lsa_ctx* ctx, bool warm, int iters, double* avg_ms, F&& run) {
+    if (warm) LSA_CHECK(run());
+    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    for (int i = 0; i < iters; ++i) LSA_CHECK(run());
+    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0.f;
+    LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    *avg_ms = (double)ms / iters;
+    return LSA_OK;
+}
+
 // problems of one lockstep group (lsa_krylov_solve_batch): the capacity of the batched DCGS2 argument records (blas.hip), of the
 // batched sweeps (kNdBatchMax, ndlu_internal.h: asserted equal there) and of the per-problem arrays of lsa_ks_batch_info
 constexpr int kKrylovGroupMax = 16;
@@ -540,11 +555,5 @@ int blk_setup(lsa_ctx* ctx, lsa_ilu* pc, int32_t B);
 int blk_solve(lsa_ctx* ctx, lsa_ilu* pc, int which, int vdtype, const void* b, void* x);
 void blk_release(lsa_ilu* pc);
 
-// ---- nested-dissection multifrontal LU (ndlu_sweeps.hip) -------------------------------------------------------
+// ---- nested-dissection multifrontal LU: the solves on its factors are declared in ndlu_internal.h (ndlu_solve_dev, NdSolve)
 struct lsa_ndlu;
-int ndlu_solve_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, const void* b, void* x);
-int ndlu_solve_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, const void* b, void* x);
-// ndlu_multi.hip: X[:, q] = C^-T B[:, q] (conj == 0) or C^-H B[:, q], q < nrhs, on device pointers (column q at q * ld scalars; B == X
-// with ldb == ldx allowed), in passes that carry their columns through one launch per tree level and direction of the transposed
-// sweeps; each column holds the bits of ndlu_solve_adjoint_dev.  One rank, no distributed node; not synchronised.
-int ndlu_solve_multi_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx);

@@ -837,44 +837,51 @@ int lsa_ndlu_solve(lsa_ctx* ctx, lsa_ndlu* f, const lsa_vec* b, lsa_vec* x) {
     return LSA_OK;
 }
 
-// the argument rules of a batched solve, forward or transposed (`who` names the entry in the message), and the device pointers
-static int nd_batch_check(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, const lsa_vec* const* b, lsa_vec* const* x, const void** bd,
-                          void** xd) {
+// what the rules of every solve on J factor sets share (`who` names the entry in the messages, `unit` a member), in the order the
+// entries have always applied them: the head -- nothing null, J in range --, then per member that it is there and, behind the
+// entry's own rules for its vectors, that it is of the analysis of the first
+static int nd_sets_head(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, const lsa_vec* const* b, lsa_vec* const* x) {
     if (!ctx || !f || !b || !x) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument", who);
     if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: J = %d outside [1, %d]", who, J, kNdBatchMax);
+    return LSA_OK;
+}
+static int nd_member_there(lsa_ctx* ctx, const char* who, const char* unit, int32_t z, lsa_ndlu* const* f, const lsa_vec* const* b, lsa_vec* const* x) {
+    if (!f[z] || !b[z] || !x[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument (%s %d)", who, unit, z);
+    return LSA_OK;
+}
+static int nd_member_compatible(lsa_ctx* ctx, const char* who, int32_t z, lsa_ndlu* const* f) {
+    if (!nd_batch_compatible(f[0], f[z])) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: factorisation %d is not of the same analysis as factorisation 0", who, z);
+    return LSA_OK;
+}
+
+// one column on each of J problems, forward or transposed: checked, queued and awaited
+static int nd_batch_solve(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int trans, const lsa_vec* const* b, lsa_vec* const* x) {
+    const void* bd[kNdBatchMax];
+    void* xd[kNdBatchMax];
+    LSA_CHECK(nd_sets_head(ctx, who, J, f, b, x));
     for (int32_t z = 0; z < J; ++z) {
-        if (!f[z] || !b[z] || !x[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument (problem %d)", who, z);
+        LSA_CHECK(nd_member_there(ctx, who, "problem", z, f, b, x));
         if (b[z]->n != f[z]->S.n || x[z]->n != f[z]->S.n || b[z]->dtype != x[z]->dtype || x[z]->dtype != x[0]->dtype)
             return lsa_set_error(ctx, LSA_ERR_ARG, "%s: shape/dtype mismatch (problem %d)", who, z);
-        if (!nd_batch_compatible(f[0], f[z]))
-            return lsa_set_error(ctx, LSA_ERR_ARG, "%s: factorisation %d is not of the same analysis as factorisation 0", who, z);
-        for (int32_t y = 0; y < z; ++y)
-            if (f[y] == f[z] || x[y]->d == x[z]->d || x[y]->d == b[z]->d || b[y]->d == x[z]->d)
-                return lsa_set_error(ctx, LSA_ERR_ARG, "%s: problems %d and %d share a factorisation or an output", who, y, z);
-    }
-    for (int32_t z = 0; z < J; ++z) {
+        LSA_CHECK(nd_member_compatible(ctx, who, z, f));
         bd[z] = b[z]->d;
         xd[z] = x[z]->d;
+        for (int32_t y = 0; y < z; ++y)
+            if (f[y] == f[z] || xd[y] == xd[z] || xd[y] == bd[z] || bd[y] == xd[z])
+                return lsa_set_error(ctx, LSA_ERR_ARG, "%s: problems %d and %d share a factorisation or an output", who, y, z);
     }
+    const NdSolve rq = {J, f, true, trans, x[0]->dtype, 1, bd, 0, xd, 0, who};
+    LSA_CHECK(ndlu_solve_run(ctx, rq));
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return LSA_OK;
 }
 
 int lsa_ndlu_solve_batch(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const lsa_vec* const* b, lsa_vec* const* x) {
-    const void* bd[kNdBatchMax];
-    void* xd[kNdBatchMax];
-    LSA_CHECK(nd_batch_check(ctx, "lsa_ndlu_solve_batch", J, f, b, x, bd, xd));
-    LSA_CHECK(ndlu_solve_batch_dev(ctx, J, f, x[0]->dtype, bd, xd));
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return LSA_OK;
+    return nd_batch_solve(ctx, "lsa_ndlu_solve_batch", J, f, 0, b, x);
 }
 
 int lsa_ndlu_solve_batch_adjoint(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, const lsa_vec* const* b, lsa_vec* const* x) {
-    const void* bd[kNdBatchMax];
-    void* xd[kNdBatchMax];
-    LSA_CHECK(nd_batch_check(ctx, "lsa_ndlu_solve_batch_adjoint", J, f, b, x, bd, xd));
-    LSA_CHECK(ndlu_solve_batch_adjoint_dev(ctx, J, f, conj, x[0]->dtype, bd, xd));
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return LSA_OK;
+    return nd_batch_solve(ctx, "lsa_ndlu_solve_batch_adjoint", J, f, conj ? 2 : 1, b, x);
 }
 
 int lsa_ndlu_solve_adjoint(lsa_ctx* ctx, lsa_ndlu* f, int conj, const lsa_vec* b, lsa_vec* x) {
@@ -888,14 +895,7 @@ int lsa_ndlu_solve_adjoint(lsa_ctx* ctx, lsa_ndlu* f, int conj, const lsa_vec* b
 int lsa_ndlu_solve_time(lsa_ctx* ctx, lsa_ndlu* f, const lsa_vec* b, lsa_vec* x, int iters, double* avg_ms) {
     if (!ctx || !f || !b || !x || !avg_ms || iters < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_time: bad argument");
     if (b->n != f->S.n || x->n != f->S.n || b->dtype != x->dtype || b->d == x->d) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_time: shape/dtype mismatch");
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; ++i) LSA_CHECK(ndlu_solve_dev(ctx, f, b->dtype, b->d, x->d));
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0.f;
-    LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *avg_ms = (double)ms / iters;
-    return LSA_OK;
+    return lsa_time_runs(ctx, false, iters, avg_ms, [&] { return ndlu_solve_dev(ctx, f, b->dtype, b->d, x->d); });
 }
 
 // shape, dtype and overlap rules of a block solve; `who` names the entry in the message
@@ -920,56 +920,18 @@ static int nd_multi_check(lsa_ctx* ctx, const char* who, const lsa_ndlu* f, int 
     return LSA_OK;
 }
 
-// the columns of a checked block solve, queued on the stream
-static int nd_multi_run(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx) {
-    const size_t es = esize(B->dtype);
-    if (trans == 0 && nrhs > 1 && f->S.nranks == 1 && !f->S.has_dist) return ndlu_solve_multi_dev(ctx, f, B->dtype, nrhs, B->d, ldb, X->d, ldx);
-    if (trans != 0 && f->multi_transposed && nrhs > 1 && f->S.nranks == 1 && !f->S.has_dist)
-        return ndlu_solve_multi_adjoint_dev(ctx, f, trans == 2, B->dtype, nrhs, B->d, ldb, X->d, ldx);
-    // one column, a forest cut over ranks, the transposed systems unless lsa_ndlu_set_multi_transposed: the existing sweeps, column by column
-    if (nrhs > 1) f->multi_width = 1;
-    for (int32_t q = 0; q < nrhs; ++q) {
-        const void* b = (const char*)B->d + (size_t)q * (size_t)ldb * es;
-        void* x = (char*)X->d + (size_t)q * (size_t)ldx * es;
-        if (trans == 0) LSA_CHECK(ndlu_solve_dev(ctx, f, B->dtype, b, x));
-        else LSA_CHECK(ndlu_solve_adjoint_dev(ctx, f, trans == 2, B->dtype, b, x));
-    }
-    return LSA_OK;
-}
-
-int lsa_ndlu_solve_multi(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx) {
-    LSA_CHECK(nd_multi_check(ctx, "lsa_ndlu_solve_multi", f, trans, nrhs, B, ldb, X, ldx));
-    LSA_CHECK(nd_multi_run(ctx, f, trans, nrhs, B, ldb, X, ldx));
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return LSA_OK;
-}
-
-int lsa_ndlu_solve_multi_time(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx, int iters,
-                              double* avg_ms) {
-    if (!avg_ms || iters < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_time: bad argument");
-    LSA_CHECK(nd_multi_check(ctx, "lsa_ndlu_solve_multi_time", f, trans, nrhs, B, ldb, X, ldx));
-    if (B->d == X->d) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_time: repeated solves need B and X apart");
-    LSA_CHECK(nd_multi_run(ctx, f, trans, nrhs, B, ldb, X, ldx));  // (the first call makes the per-column buffers)
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; ++i) LSA_CHECK(nd_multi_run(ctx, f, trans, nrhs, B, ldb, X, ldx));
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0.f;
-    LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *avg_ms = (double)ms / iters;
-    return LSA_OK;
-}
-
-// the rules of a block solve on J factor sets: those of nd_batch_check for the sets, of nd_multi_check for every set's blocks, and
-// between sets no shared factorisation or X and no overlap but ONE B read by several; the device pointers
-static int nd_multi_batch_check(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int trans, int32_t nrhs, const lsa_vec* const* B, int64_t ldb,
+// the rules of a block solve on J factor sets: what they share with the single-column batch, those of nd_multi_check for every
+// set's blocks, and between sets no shared factorisation or X and no overlap but ONE B read by several; the device pointers.
+// `refused`: the trans a forward entry was given (the transposed form has entries of its own: it goes on refusing trans != 0).
+static int nd_multi_batch_check(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int refused, int32_t nrhs, const lsa_vec* const* B, int64_t ldb,
                                 lsa_vec* const* X, int64_t ldx, const void** bd, void** xd) {
-    if (!ctx || !f || !B || !X) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument", who);
-    if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: J = %d outside [1, %d]", who, J, kNdBatchMax);
-    if (trans != 0) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: trans = %d: the transposed form of the block solve on a batch of factor sets is not built", who, trans);
+    LSA_CHECK(nd_sets_head(ctx, who, J, f, B, X));
+    if (refused != 0) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: trans = %d: the transposed form of the block solve on a batch of factor sets is not built", who, refused);
     for (int32_t z = 0; z < J; ++z) {
-        if (!f[z] || !B[z] || !X[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument (set %d)", who, z);
-        if (!nd_batch_compatible(f[0], f[z])) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: factorisation %d is not of the same analysis as factorisation 0", who, z);
+        LSA_CHECK(nd_member_there(ctx, who, "set", z, f, B, X));
+        LSA_CHECK(nd_member_compatible(ctx, who, z, f));
+        bd[z] = B[z]->d;
+        xd[z] = X[z]->d;
         if (X[z]->dtype != X[0]->dtype) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the vectors of set %d differ in dtype from those of set 0", who, z);
         LSA_CHECK(nd_multi_check(ctx, who, f[z], 0, nrhs, B[z], ldb, X[z], ldx));
     }
@@ -980,93 +942,91 @@ static int nd_multi_batch_check(lsa_ctx* ctx, const char* who, int32_t J, lsa_nd
     for (int32_t z = 0; z < J; ++z)
         for (int32_t y = 0; y < z; ++y) {
             if (f[y] == f[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: sets %d and %d share a factorisation", who, y, z);
-            if (overlap(X[y]->d, span_x, X[z]->d, span_x)) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: sets %d and %d share an X or their X overlap", who, y, z);
-            if (overlap(X[y]->d, span_x, B[z]->d, span_b) || overlap(B[y]->d, span_b, X[z]->d, span_x))
+            if (overlap(xd[y], span_x, xd[z], span_x)) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: sets %d and %d share an X or their X overlap", who, y, z);
+            if (overlap(xd[y], span_x, bd[z], span_b) || overlap(bd[y], span_b, xd[z], span_x))
                 return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the X of one of the sets %d and %d overlaps the B of the other", who, y, z);
-            if (B[y]->d != B[z]->d && overlap(B[y]->d, span_b, B[z]->d, span_b))
+            if (bd[y] != bd[z] && overlap(bd[y], span_b, bd[z], span_b))
                 return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the B of sets %d and %d overlap (several sets may read ONE B)", who, y, z);
         }
-    for (int32_t z = 0; z < J; ++z) {
-        bd[z] = B[z]->d;
-        xd[z] = X[z]->d;
-    }
     return LSA_OK;
 }
 
-// the checked block solve on J sets, queued on the stream (one column: the batched solo sweeps)
-static int nd_multi_batch_run(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, int32_t nrhs, const void* const* bd, int64_t ldb, void* const* xd, int64_t ldx) {
-    if (nrhs > 1) return ndlu_solve_multi_batch_dev(ctx, J, f, vdtype, nrhs, bd, ldb, xd, ldx);
-    const void* b1[kNdBatchMax];
-    for (int32_t z = 0; z < J; ++z) b1[z] = bd[z];  // (an aliased entry is replaced by the set's own copy)
-    return ndlu_solve_batch_dev(ctx, J, f, vdtype, b1, xd);
+// lsa_ndlu_solve_multi and, with avg_ms, its timed form: the checked block solve queued once and awaited, or queued once (the first
+// call makes the per-column buffers) and then timed over iters repetitions
+static int nd_multi_solve(lsa_ctx* ctx, const char* who, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx, int iters,
+                          double* avg_ms) {
+    LSA_CHECK(nd_multi_check(ctx, who, f, trans, nrhs, B, ldb, X, ldx));
+    if (avg_ms && B->d == X->d) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: repeated solves need B and X apart", who);
+    const void* bd = B->d;
+    void* xd = X->d;
+    const NdSolve rq = {1, &f, false, trans, B->dtype, nrhs, &bd, ldb, &xd, ldx, who};
+    const bool block = f->S.nranks == 1 && !f->S.has_dist && (trans == 0 || f->multi_transposed);
+    auto run = [&] {
+        if (nrhs == 1 || block) return ndlu_solve_run(ctx, rq);
+        // a forest cut over ranks, distributed nodes, the transposed systems unless lsa_ndlu_set_multi_transposed: column by column
+        // (the one writer of the two fields beside ndlu_solve_run)
+        f->multi_width = 1, f->multi_passes = 0;
+        const size_t es = esize(B->dtype);
+        for (int32_t q = 0; q < nrhs; ++q) {
+            const void* b = (const char*)bd + (size_t)q * (size_t)ldb * es;
+            void* x = (char*)xd + (size_t)q * (size_t)ldx * es;
+            LSA_CHECK(trans == 0 ? ndlu_solve_dev(ctx, f, B->dtype, b, x) : ndlu_solve_adjoint_dev(ctx, f, trans == 2, B->dtype, b, x));
+        }
+        return (int)LSA_OK;
+    };
+    if (avg_ms) return lsa_time_runs(ctx, true, iters, avg_ms, run);
+    LSA_CHECK(run());
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return LSA_OK;
+}
+
+int lsa_ndlu_solve_multi(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx) {
+    return nd_multi_solve(ctx, "lsa_ndlu_solve_multi", f, trans, nrhs, B, ldb, X, ldx, 0, nullptr);
+}
+
+int lsa_ndlu_solve_multi_time(lsa_ctx* ctx, lsa_ndlu* f, int trans, int32_t nrhs, const lsa_vec* B, int64_t ldb, lsa_vec* X, int64_t ldx, int iters,
+                              double* avg_ms) {
+    if (!avg_ms || iters < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_time: bad argument");
+    return nd_multi_solve(ctx, "lsa_ndlu_solve_multi_time", f, trans, nrhs, B, ldb, X, ldx, iters, avg_ms);
+}
+
+// the block solve on J sets and, with avg_ms, its timed form.  `trans`: what the entry was given -- the forward entries refuse all but 0
+// (nd_multi_batch_check), the transposed ones say 1 or 2 through `adjoint`.
+static int nd_multi_batch_solve(lsa_ctx* ctx, const char* who, bool adjoint, int32_t J, lsa_ndlu* const* f, int trans, int32_t nrhs, const lsa_vec* const* B,
+                                int64_t ldb, lsa_vec* const* X, int64_t ldx, int iters, double* avg_ms) {
+    const void* bd[kNdBatchMax];
+    void* xd[kNdBatchMax];
+    LSA_CHECK(nd_multi_batch_check(ctx, who, J, f, adjoint ? 0 : trans, nrhs, B, ldb, X, ldx, bd, xd));
+    for (int32_t z = 0; avg_ms && z < J; ++z)
+        if (bd[z] == xd[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: repeated solves need B and X apart (set %d)", who, z);
+    const NdSolve rq = {J, f, true, trans, X[0]->dtype, nrhs, bd, ldb, xd, ldx, who};
+    auto run = [&] { return ndlu_solve_run(ctx, rq); };
+    if (avg_ms) return lsa_time_runs(ctx, true, iters, avg_ms, run);
+    LSA_CHECK(run());
+    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return LSA_OK;
 }
 
 int lsa_ndlu_solve_multi_batch(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int trans, int32_t nrhs, const lsa_vec* const* B, int64_t ldb, lsa_vec* const* X,
                                int64_t ldx) {
-    const void* bd[kNdBatchMax];
-    void* xd[kNdBatchMax];
-    LSA_CHECK(nd_multi_batch_check(ctx, "lsa_ndlu_solve_multi_batch", J, f, trans, nrhs, B, ldb, X, ldx, bd, xd));
-    LSA_CHECK(nd_multi_batch_run(ctx, J, f, X[0]->dtype, nrhs, bd, ldb, xd, ldx));
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return LSA_OK;
+    return nd_multi_batch_solve(ctx, "lsa_ndlu_solve_multi_batch", false, J, f, trans, nrhs, B, ldb, X, ldx, 0, nullptr);
 }
 
 int lsa_ndlu_solve_multi_batch_time(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int trans, int32_t nrhs, const lsa_vec* const* B, int64_t ldb, lsa_vec* const* X,
                                     int64_t ldx, int iters, double* avg_ms) {
     if (!avg_ms || iters < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch_time: bad argument");
-    const void* bd[kNdBatchMax];
-    void* xd[kNdBatchMax];
-    LSA_CHECK(nd_multi_batch_check(ctx, "lsa_ndlu_solve_multi_batch_time", J, f, trans, nrhs, B, ldb, X, ldx, bd, xd));
-    for (int32_t z = 0; z < J; ++z)
-        if (bd[z] == xd[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch_time: repeated solves need B and X apart (set %d)", z);
-    LSA_CHECK(nd_multi_batch_run(ctx, J, f, X[0]->dtype, nrhs, bd, ldb, xd, ldx));  // (the first call makes the per-column buffers)
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; ++i) LSA_CHECK(nd_multi_batch_run(ctx, J, f, X[0]->dtype, nrhs, bd, ldb, xd, ldx));
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0.f;
-    LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *avg_ms = (double)ms / iters;
-    return LSA_OK;
-}
-
-// the transposed block solve on J sets, an entry of its own (the forward entry goes on refusing trans != 0): the rules of
-// nd_multi_batch_check; queued on the stream (one column: the batched solo transposed sweeps)
-static int nd_multi_batch_adjoint_run(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, int32_t nrhs, const void* const* bd, int64_t ldb,
-                                      void* const* xd, int64_t ldx) {
-    if (nrhs > 1) return ndlu_solve_multi_batch_adjoint_dev(ctx, J, f, conj, vdtype, nrhs, bd, ldb, xd, ldx);
-    const void* b1[kNdBatchMax];
-    for (int32_t z = 0; z < J; ++z) b1[z] = bd[z];  // (nd_dispatch_solve replaces an aliased entry by the set's own copy, d_tmp)
-    return ndlu_solve_batch_adjoint_dev(ctx, J, f, conj, vdtype, b1, xd);
+    return nd_multi_batch_solve(ctx, "lsa_ndlu_solve_multi_batch_time", false, J, f, trans, nrhs, B, ldb, X, ldx, iters, avg_ms);
 }
 
 int lsa_ndlu_solve_multi_batch_adjoint(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int32_t nrhs, const lsa_vec* const* B, int64_t ldb,
                                        lsa_vec* const* X, int64_t ldx) {
-    const void* bd[kNdBatchMax];
-    void* xd[kNdBatchMax];
-    LSA_CHECK(nd_multi_batch_check(ctx, "lsa_ndlu_solve_multi_batch_adjoint", J, f, 0, nrhs, B, ldb, X, ldx, bd, xd));
-    LSA_CHECK(nd_multi_batch_adjoint_run(ctx, J, f, conj, X[0]->dtype, nrhs, bd, ldb, xd, ldx));
-    LSA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return LSA_OK;
+    return nd_multi_batch_solve(ctx, "lsa_ndlu_solve_multi_batch_adjoint", true, J, f, conj ? 2 : 1, nrhs, B, ldb, X, ldx, 0, nullptr);
 }
 
 int lsa_ndlu_solve_multi_batch_adjoint_time(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int32_t nrhs, const lsa_vec* const* B, int64_t ldb,
                                             lsa_vec* const* X, int64_t ldx, int iters, double* avg_ms) {
     if (!avg_ms || iters < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch_adjoint_time: bad argument");
-    const void* bd[kNdBatchMax];
-    void* xd[kNdBatchMax];
-    LSA_CHECK(nd_multi_batch_check(ctx, "lsa_ndlu_solve_multi_batch_adjoint_time", J, f, 0, nrhs, B, ldb, X, ldx, bd, xd));
-    for (int32_t z = 0; z < J; ++z)
-        if (bd[z] == xd[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch_adjoint_time: repeated solves need B and X apart (set %d)", z);
-    LSA_CHECK(nd_multi_batch_adjoint_run(ctx, J, f, conj, X[0]->dtype, nrhs, bd, ldb, xd, ldx));  // (the first call makes the per-column buffers)
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; ++i) LSA_CHECK(nd_multi_batch_adjoint_run(ctx, J, f, conj, X[0]->dtype, nrhs, bd, ldb, xd, ldx));
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0.f;
-    LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *avg_ms = (double)ms / iters;
-    return LSA_OK;
+    return nd_multi_batch_solve(ctx, "lsa_ndlu_solve_multi_batch_adjoint_time", true, J, f, conj ? 2 : 1, nrhs, B, ldb, X, ldx, iters, avg_ms);
 }
 
 int lsa_ndlu_set_multi_transposed(lsa_ctx* ctx, lsa_ndlu* f, int on) {

@@ -200,8 +200,8 @@ struct lsa_ndlu {
     int64_t multi_stage_bytes = 0;
     bool multi_full = false;     // an allocation failed: no further columns are tried
     int64_t multi_bytes = 0;
-    int32_t multi_passes = 0;    // multi-column passes (two columns or more) of the last forward block solve, or of the last block solve on a batch of sets in either direction
-    int32_t multi_width = 0;     // widest pass of the last multi-column solve (1: column by column; 0: none yet)
+    int32_t multi_passes = 0;    // passes of two columns or more of the last solve of several columns (written by ndlu_solve_run, and by the column-by-column loop of lsa_ndlu_solve_multi)
+    int32_t multi_width = 0;     // ... and its widest pass (1: column by column; 0: none yet)
     bool multi_transposed = false;  // lsa_ndlu_set_multi_transposed: block solves with trans != 0 run in wide passes too
 };
 
@@ -215,25 +215,43 @@ int upload(lsa_ctx* ctx, const std::vector<U>& h, U** d) {
 
 // ndlu_factor.hip: the numeric factorisation of C on the analysis and buffers of f (factor type f->dtype)
 int ndlu_numeric(lsa_ctx* ctx, lsa_ndlu* f, const lsa_mat* C);
-// ndlu_sweeps.hip (ndlu_solve_dev and ndlu_solve_adjoint_dev: lsa_internal.h).  Whether g can run in a batch with f; x_z = C_z^-1 b_z
-// for J <= kNdBatchMax factorisations that nd_batch_compatible passed, on device pointers, not synchronised (b_z == x_z allowed:
-// such a b_z is replaced in the caller's array by the problem's own copy of it)
+// ---- solves on the factors, on device pointers, queued on the context's stream and not synchronised.
+// ndlu_sweeps.hip: x = C^-1 b, and x = C^-T b (conj == 0) or C^-H b (real factors: the transposed solve); b == x is allowed.  The two
+// calls of a Krylov step; every other form is a request.
+int ndlu_solve_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, const void* b, void* x);
+int ndlu_solve_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, const void* b, void* x);
+// whether g can run in a batch with f
 bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g);
-int ndlu_solve_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, const void** b, void* const* x);
-// ... and x_z = C_z^-T b_z (conj == 0) or C_z^-H b_z (conj != 0; real factors: the transposed solve) under the same rules: the
-// transposed sweeps of all J problems in one launch per level and direction, each x_z with the bits of ndlu_solve_adjoint_dev
-int ndlu_solve_batch_adjoint_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, const void** b, void* const* x);
-// ndlu_multi.hip: X[:, q] = C^-1 B[:, q], q < nrhs, on device pointers (column q at q * ld scalars; B == X with ldb == ldx allowed),
-// in passes of up to kNdMultiMax (complex vectors: 4) columns that share every factor load; not synchronised.  One rank, no distributed node.
-int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx);
-// (the transposed block solve, ndlu_solve_multi_adjoint_dev: lsa_internal.h)
-// ... and X[z][:, q] = C_z^-1 B[z][:, q] for J <= kNdBatchMax factorisations that nd_batch_compatible passed, one launch per level and
-// direction for all columns of a pass on all of them, every column with the bits of ndlu_solve_dev; the blocks share ldb and ldx, several
-// sets may read one B, and B[z] == X[z] (with ldb == ldx) is allowed; not synchronised
-int ndlu_solve_multi_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb, void* const* X,
-                               int64_t ldx);
-// ... and the transposed form, X[z][:, q] = C_z^-T B[z][:, q] (conj != 0: C_z^-H), under the same rules: every column with the bits of
-// ndlu_solve_adjoint_dev
-int ndlu_solve_multi_batch_adjoint_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb,
-                                       void* const* X, int64_t ldx);
+
+// One request for every form of the solve: X[z][:, q] = op(C_z)^-1 B[z][:, q] for q < nrhs on the factor sets f[z], z < J, with op
+// by trans (0: C, 1: C^T, 2: C^H).  Column q of a set lies at B[z] + q ldb and X[z] + q ldx scalars of vdtype; the sets share ldb and
+// ldx, several sets may read one B, and B[z] == X[z] (with ldb == ldx) is allowed.
+//   sets = false: one factorisation (J = 1) on the sweeps' instances of capacity one, the only form for a forest cut over ranks or
+//                 with distributed nodes, and then for one column only;
+//   sets = true:  J <= kNdBatchMax factorisations that nd_batch_compatible passed, on the instances of capacity kNdBatchMax whatever J:
+//                 one launch per level and direction for all of them.
+// One column runs the single-column sweeps.  More run in passes of up to kNdMultiMax (complex vectors: 4) columns that share every
+// factor load (ndlu_multi.hip), a last odd column through the single-column sweeps again; every column of every set has the bits
+// ndlu_solve_dev or ndlu_solve_adjoint_dev give for it.
+struct NdSolve {
+    int32_t J;
+    lsa_ndlu* const* f;
+    bool sets;
+    int trans, vdtype;
+    int32_t nrhs;
+    const void* const* B;
+    int64_t ldb;
+    void* const* X;
+    int64_t ldx;
+    const char* who;  // the entry's name for messages
+};
+// what a request ran as: its passes of two or more columns and the widest pass (one column: 0 and 1)
+struct NdSolveInfo {
+    int32_t passes, width;
+};
+// ndlu_multi.hip: runs the request; never writes to the caller's pointer arrays.  A request of several columns leaves its pass count and
+// widest pass in multi_passes and multi_width of every set, one of a single column leaves them alone.  `who` prefixes every message:
+// the C entry's name, or the name of the solver that built the request.
+int ndlu_solve_run(lsa_ctx* ctx, const NdSolve& rq, NdSolveInfo* info = nullptr);
+int ndlu_solve_column(lsa_ctx* ctx, const NdSolve& rq, const void* const* b, void* const* x);  // ndlu_sweeps.hip: its single-column part
 void ndlu_multi_free(lsa_ndlu* f);

@@ -1,4 +1,4 @@
-// Nested-dissection multifrontal LU, solves with a block of right-hand sides on ONE factorisation (lsa_ndlu_solve_multi): the
+// Nested-dissection multifrontal LU, solves with a block of right-hand sides (lsa_ndlu_solve_multi and its kin): the
 // sweeps of ndlu_sweeps.hip with R columns carried through every launch.  A workgroup owns the tile of rows of the packed L_t /
 // U_t / T it owns there, stages the R vectors' chunks side by side in LDS, loads every factor scalar ONCE and accumulates R
 // pairs of row sums from it.  Per column nothing else changes: the lane partition (LPR per level), each lane's ascending
@@ -6,11 +6,13 @@
 // column q holds exactly the bits lsa_ndlu_solve gives for it.  (A lane's sequence sl, sl + LPR, ... runs on across chunks, so
 // the chunk -- kMCH entries per column, a multiple of 256 -- is free: four complex or eight real columns of kMCH = 256 are 16 KB of LDS.)
 // Columns beyond the first have sweep buffers of their own (lsa_ndlu::multi), made by the first such solve.
-// The same kernels carry the R columns through J <= 16 factor sets of one analysis in one launch (lsa_ndlu_solve_multi_batch: the set
-// is the grid's last dimension, NdMultiPtrs<R, NB>); the one-set solve is their instance of set capacity one.
-// The transposed systems C^-T / C^-H have the same form (nd_sweepT_multi_kernel, ndlu_solve_multi_adjoint_dev): nd_sweepT_kernel with R
-// columns carried through every launch, on the update vectors of the same per-column buffers -- and, templated on the set capacity
-// like the forward kernels, through J <= 16 factor sets in one launch (lsa_ndlu_solve_multi_batch_adjoint).
+// The same kernels carry the R columns through J <= 16 factor sets of one analysis in one launch (the set is the grid's last
+// dimension, NdMultiPtrs<R, NB>); the one-set solve is their instance of set capacity one.  The transposed systems C^-T / C^-H have
+// the same form (nd_sweepT_multi_kernel): nd_sweepT_kernel with R columns carried through every launch, on the update vectors of the
+// same per-column buffers, templated on the set capacity like the forward kernels.
+// Every form -- forward or transposed, one set or a batch, one column or many -- is one request (NdSolve, ndlu_internal.h) to
+// ndlu_solve_run at the end of this file: one dispatch on the scalar types and the direction (nd_dispatch_solve), one pass driver
+// (nd_solve_passes).
 #include "ndlu_sweep_parts.h"
 
 namespace {
@@ -657,126 +659,75 @@ int nd_multi_stage(lsa_ctx* ctx, lsa_ndlu* f, int32_t W, const VT* b, int64_t ld
     return LSA_OK;
 }
 
-// X[z][:, q] = C_z^-1 B[z][:, q] for J <= NB factor sets (J = NB = 1: lsa_ndlu_solve_multi), in passes of 8, 4 or 2 columns, the
-// widest every set has buffers for; a last single column goes through the solo sweeps (of the batch, for J sets)
-template <typename MT, typename VT, int NB>
-int nd_solve_multi(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int32_t nrhs, const VT* const* B, int64_t ldb, VT* const* X, int64_t ldx) {
+// fn(std::integral_constant<int, R>) for the pass widths that are built: 8 for 8-byte vector scalars only (nd_multi_cap), 4 and 2
+template <typename VT, typename F>
+int nd_with_width(int32_t R, F&& fn) {
+    if constexpr (sizeof(VT) == 8)
+        if (R == 8) return fn(std::integral_constant<int, 8>{});
+    if (R == 4) return fn(std::integral_constant<int, 4>{});
+    return fn(std::integral_constant<int, 2>{});
+}
+
+// The one pass driver: the request's nrhs >= 2 columns on its J <= NB sets in passes of 8, 4 or 2 columns, the widest every set has
+// buffers for (a remainder runs in narrower passes); a last single column goes through the single-column sweeps of the same capacity
+// and direction.  DIR (0 N, 1 T, 2 H) supplies only its launch record and its sweep.  An aliased block is solved from a copy, as the
+// form has always staged it: the forward passes and the transposed ones on a batch of sets in the set's strided stage block
+// (nd_multi_stage), the transposed passes on one set column by column in the columns' own tmp buffers.
+template <typename MT, typename VT, int NB, int DIR>
+int nd_solve_passes(lsa_ctx* ctx, const NdSolve& rq, NdSolveInfo* info) {
+    const int32_t J = rq.J;
+    lsa_ndlu* const* f = rq.f;
+    const int64_t ldb = rq.ldb, ldx = rq.ldx;
     // (buffers for the widest pass that will run: the first)
-    const int32_t want = nd_pass_width(nrhs, nd_multi_cap(sizeof(VT)));
+    const int32_t want = nd_pass_width(rq.nrhs, nd_multi_cap(sizeof(VT)));
     int32_t avail = want;
     for (int32_t z = 0; z < J; ++z) avail = std::min(avail, nd_multi_ensure(ctx, f[z], want));
-    for (int32_t z = 0; z < J; ++z) f[z]->multi_width = 1, f[z]->multi_passes = 0;
-    for (int32_t q0 = 0; q0 < nrhs;) {
-        const int32_t R = nd_pass_width(nrhs - q0, avail);  // a remainder runs in narrower passes
+    NdSolveInfo done = {0, 1};
+    for (int32_t q0 = 0; q0 < rq.nrhs;) {
+        const int32_t R = nd_pass_width(rq.nrhs - q0, avail);
         const VT* b[NB];
         VT* x[NB];
         for (int32_t z = 0; z < J; ++z) {
-            b[z] = B[z] + (int64_t)q0 * ldb;
-            x[z] = X[z] + (int64_t)q0 * ldx;
+            b[z] = (const VT*)rq.B[z] + (int64_t)q0 * ldb;
+            x[z] = (VT*)rq.X[z] + (int64_t)q0 * ldx;
         }
         if (R == 1) {
-            if constexpr (NB == 1) LSA_CHECK(ndlu_solve_dev(ctx, f[0], scalar_traits<VT>::dtype, b[0], x[0]));
-            else LSA_CHECK(ndlu_solve_batch_dev(ctx, J, f, scalar_traits<VT>::dtype, (const void**)b, (void* const*)x));
+            LSA_CHECK(ndlu_solve_column(ctx, rq, (const void* const*)b, (void* const*)x));
             q0 += 1;
             continue;
         }
-        for (int32_t z = 0; z < J; ++z)
-            if (b[z] == x[z]) LSA_CHECK(nd_multi_stage(ctx, f[z], R, b[z], ldb, &b[z]));
-        auto run = [&](auto width) {
-            constexpr int W = decltype(width)::value;
-            return f[0]->ordered ? nd_sweep_multi<MT, VT, true, W, NB>(ctx, J, f, b, ldb, x, ldx) : nd_sweep_multi<MT, VT, false, W, NB>(ctx, J, f, b, ldb, x, ldx);
-        };
-        if constexpr (sizeof(VT) == 8) {
-            if (R == 8) LSA_CHECK(run(std::integral_constant<int, 8>{}));
-        }
-        if (R == 4) LSA_CHECK(run(std::integral_constant<int, 4>{}));
-        if (R == 2) LSA_CHECK(run(std::integral_constant<int, 2>{}));
-        for (int32_t z = 0; z < J; ++z) f[z]->multi_width = std::max(f[z]->multi_width, R), ++f[z]->multi_passes;
-        q0 += R;
-    }
-    return LSA_OK;
-}
-
-// the transposed block solve: the passes of nd_solve_multi; a last single column goes through the solo adjoint solve
-template <typename MT, typename VT, bool CONJ>
-int nd_solve_multi_adjoint(lsa_ctx* ctx, lsa_ndlu* f, int32_t nrhs, const VT* B, int64_t ldb, VT* X, int64_t ldx) {
-    const int32_t avail = nd_multi_ensure(ctx, f, nd_pass_width(nrhs, nd_multi_cap(sizeof(VT))));
-    const size_t nbytes = (size_t)f->S.n * sizeof(VT);
-    f->multi_width = 1;
-    for (int32_t q0 = 0; q0 < nrhs;) {
-        const int32_t R = nd_pass_width(nrhs - q0, avail);
-        if (R == 1) {
-            LSA_CHECK(ndlu_solve_adjoint_dev(ctx, f, CONJ, scalar_traits<VT>::dtype, B + (int64_t)q0 * ldb, X + (int64_t)q0 * ldx));
-            q0 += 1;
-            continue;
-        }
-        const VT* b[kNdMultiMax];
-        VT* x[kNdMultiMax];
-        for (int32_t q = 0; q < R; ++q) {
-            b[q] = B + (int64_t)(q0 + q) * ldb;
-            x[q] = X + (int64_t)(q0 + q) * ldx;
-            if (b[q] == x[q]) {  // in place: a tile reads the node's right-hand side while the others write its solution
-                void* tmp = q == 0 ? f->d_tmp : f->multi[(size_t)q - 1].tmp;
-                LSA_HIP_CHECK(ctx, hipMemcpyAsync(tmp, b[q], nbytes, hipMemcpyDeviceToDevice, ctx->stream));
-                b[q] = (const VT*)tmp;
-            }
-        }
-        auto run = [&](auto width) {
-            constexpr int W = decltype(width)::value;
-            NdMultiTPtrs<W, 1> p;
-            for (int q = 0; q < W; ++q) p.set[0].rhs[q] = b[q], p.set[0].x[q] = x[q];
-            return nd_sweepT_multi<MT, VT, CONJ, W, 1>(ctx, 1, &f, p);
-        };
-        if constexpr (sizeof(VT) == 8) {
-            if (R == 8) LSA_CHECK(run(std::integral_constant<int, 8>{}));
-        }
-        if (R == 4) LSA_CHECK(run(std::integral_constant<int, 4>{}));
-        if (R == 2) LSA_CHECK(run(std::integral_constant<int, 2>{}));
-        f->multi_width = std::max(f->multi_width, R);
-        q0 += R;
-    }
-    return LSA_OK;
-}
-
-// ... and on J <= kNdBatchMax factor sets: the passes of nd_solve_multi for a batch (the widest every set has buffers for, an aliased
-// block staged as there), a last single column through the batched solo transposed sweeps
-template <typename MT, typename VT, bool CONJ>
-int nd_solve_multi_batch_adjoint(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int32_t nrhs, const VT* const* B, int64_t ldb, VT* const* X, int64_t ldx) {
-    const int32_t want = nd_pass_width(nrhs, nd_multi_cap(sizeof(VT)));
-    int32_t avail = want;
-    for (int32_t z = 0; z < J; ++z) avail = std::min(avail, nd_multi_ensure(ctx, f[z], want));
-    for (int32_t z = 0; z < J; ++z) f[z]->multi_width = 1, f[z]->multi_passes = 0;
-    for (int32_t q0 = 0; q0 < nrhs;) {
-        const int32_t R = nd_pass_width(nrhs - q0, avail);
-        const VT* b[kNdBatchMax];
-        VT* x[kNdBatchMax];
-        for (int32_t z = 0; z < J; ++z) {
-            b[z] = B[z] + (int64_t)q0 * ldb;
-            x[z] = X[z] + (int64_t)q0 * ldx;
-        }
-        if (R == 1) {
-            LSA_CHECK(ndlu_solve_batch_adjoint_dev(ctx, J, f, CONJ, scalar_traits<VT>::dtype, (const void**)b, (void* const*)x));
-            q0 += 1;
-            continue;
-        }
-        for (int32_t z = 0; z < J; ++z)
-            if (b[z] == x[z]) LSA_CHECK(nd_multi_stage(ctx, f[z], R, b[z], ldb, &b[z]));
-        auto run = [&](auto width) {
-            constexpr int W = decltype(width)::value;
-            NdMultiTPtrs<W, kNdBatchMax> p;
-            memset(&p, 0, sizeof p);
+        if constexpr (DIR == 0 || NB > 1)
             for (int32_t z = 0; z < J; ++z)
-                for (int q = 0; q < W; ++q) p.set[z].rhs[q] = b[z] + (int64_t)q * ldb, p.set[z].x[q] = x[z] + (int64_t)q * ldx;
-            return nd_sweepT_multi<MT, VT, CONJ, W, kNdBatchMax>(ctx, J, f, p);
-        };
-        if constexpr (sizeof(VT) == 8) {
-            if (R == 8) LSA_CHECK(run(std::integral_constant<int, 8>{}));
-        }
-        if (R == 4) LSA_CHECK(run(std::integral_constant<int, 4>{}));
-        if (R == 2) LSA_CHECK(run(std::integral_constant<int, 2>{}));
-        for (int32_t z = 0; z < J; ++z) f[z]->multi_width = std::max(f[z]->multi_width, R), ++f[z]->multi_passes;
+                if (b[z] == x[z]) LSA_CHECK(nd_multi_stage(ctx, f[z], R, b[z], ldb, &b[z]));
+        LSA_CHECK(nd_with_width<VT>(R, [&](auto width) {
+            constexpr int W = decltype(width)::value;
+            if constexpr (DIR == 0) {
+                return f[0]->ordered ? nd_sweep_multi<MT, VT, true, W, NB>(ctx, J, f, b, ldb, x, ldx) : nd_sweep_multi<MT, VT, false, W, NB>(ctx, J, f, b, ldb, x, ldx);
+            } else {
+                NdMultiTPtrs<W, NB> p;
+                memset(&p, 0, sizeof p);
+                for (int32_t z = 0; z < J; ++z)
+                    for (int q = 0; q < W; ++q) {
+                        const VT* bq = b[z] + (int64_t)q * ldb;
+                        VT* xq = x[z] + (int64_t)q * ldx;
+                        if constexpr (NB == 1)
+                            if (bq == xq) {  // in place: a tile reads the node's right-hand side while the others write its solution
+                                void* tmp = q == 0 ? f[z]->d_tmp : f[z]->multi[(size_t)q - 1].tmp;
+                                LSA_HIP_CHECK(ctx, hipMemcpyAsync(tmp, bq, (size_t)f[z]->S.n * sizeof(VT), hipMemcpyDeviceToDevice, ctx->stream));
+                                bq = (const VT*)tmp;
+                            }
+                        p.set[z].rhs[q] = bq;
+                        p.set[z].x[q] = xq;
+                    }
+                return nd_sweepT_multi<MT, VT, DIR == 2, W, NB>(ctx, J, f, p);
+            }
+        }));
+        done.width = std::max(done.width, R);
+        ++done.passes;
         q0 += R;
     }
+    for (int32_t z = 0; z < J; ++z) f[z]->multi_width = done.width, f[z]->multi_passes = done.passes;
+    if (info) *info = done;
     return LSA_OK;
 }
 
@@ -793,64 +744,16 @@ void ndlu_multi_free(lsa_ndlu* f) {
     f->multi_bytes = 0;
 }
 
-namespace {
-
-template <int NB>
-int nd_solve_multi_sets(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb,
-                        void* const* X, int64_t ldx) {
-    for (int32_t z = 0; z < J; ++z)
-        if (f[z]->S.nranks > 1 || f[z]->S.has_dist) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the multi-column sweeps need one rank and no distributed node", who);
-    if (f[0]->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: complex factors need complex vectors", who);
-    if (f[0]->S.n == 0) return LSA_OK;
-    if (f[0]->dtype == LSA_C128) return nd_solve_multi<cplx, cplx, NB>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
-    if (vdtype == LSA_C128) return nd_solve_multi<double, cplx, NB>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
-    return nd_solve_multi<double, double, NB>(ctx, J, f, nrhs, (const double* const*)B, ldb, (double* const*)X, ldx);
-}
-
-}  // namespace
-
-int ndlu_solve_multi_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx) {
-    return nd_solve_multi_sets<1>(ctx, "lsa_ndlu_solve_multi", 1, &f, vdtype, nrhs, &B, ldb, &X, ldx);
-}
-
-// the same block solve on J <= kNdBatchMax factor sets of one analysis (nd_batch_compatible), every launch carrying all columns of
-// a pass for all sets; B[z] may be one block for several sets, or X[z] itself (with ldb == ldx)
-int ndlu_solve_multi_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb, void* const* X,
-                               int64_t ldx) {
-    if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi_batch: J = %d outside [1, %d]", J, kNdBatchMax);
-    return nd_solve_multi_sets<kNdBatchMax>(ctx, "lsa_ndlu_solve_multi_batch", J, f, vdtype, nrhs, B, ldb, X, ldx);
-}
-
-// X[:, q] = C^-T B[:, q] (conj == 0) or C^-H B[:, q] on the factors of C, in passes that share every factor load
-int ndlu_solve_multi_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, int32_t nrhs, const void* B, int64_t ldb, void* X, int64_t ldx) {
-    if (f->S.nranks > 1 || f->S.has_dist)
-        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi: the transposed multi-column sweeps need one rank and no distributed node");
-    if (f->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_ndlu_solve_multi: complex factors need complex vectors");
-    if (f->S.n == 0) return LSA_OK;
-    if (f->dtype == LSA_C128) {
-        if (conj) return nd_solve_multi_adjoint<cplx, cplx, true>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
-        return nd_solve_multi_adjoint<cplx, cplx, false>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
-    }
-    // (real factors: C^H = C^T, one instance)
-    if (vdtype == LSA_C128) return nd_solve_multi_adjoint<double, cplx, false>(ctx, f, nrhs, (const cplx*)B, ldb, (cplx*)X, ldx);
-    return nd_solve_multi_adjoint<double, double, false>(ctx, f, nrhs, (const double*)B, ldb, (double*)X, ldx);
-}
-
-// ... and X[z][:, q] = C_z^-T B[z][:, q] (C_z^-H with conj != 0) on J <= kNdBatchMax factor sets of one analysis (nd_batch_compatible),
-// every launch carrying all columns of a pass for all sets; the rules of ndlu_solve_multi_batch_dev for B and X
-int ndlu_solve_multi_batch_adjoint_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, int32_t nrhs, const void* const* B, int64_t ldb,
-                                       void* const* X, int64_t ldx) {
-    const char* who = "lsa_ndlu_solve_multi_batch_adjoint";
-    if (J < 1 || J > kNdBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: J = %d outside [1, %d]", who, J, kNdBatchMax);
-    for (int32_t z = 0; z < J; ++z)
-        if (f[z]->S.nranks > 1 || f[z]->S.has_dist) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the multi-column sweeps need one rank and no distributed node", who);
-    if (f[0]->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: complex factors need complex vectors", who);
-    if (f[0]->S.n == 0) return LSA_OK;
-    if (f[0]->dtype == LSA_C128) {
-        if (conj) return nd_solve_multi_batch_adjoint<cplx, cplx, true>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
-        return nd_solve_multi_batch_adjoint<cplx, cplx, false>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
-    }
-    // (real factors: C^H = C^T, one instance)
-    if (vdtype == LSA_C128) return nd_solve_multi_batch_adjoint<double, cplx, false>(ctx, J, f, nrhs, (const cplx* const*)B, ldb, (cplx* const*)X, ldx);
-    return nd_solve_multi_batch_adjoint<double, double, false>(ctx, J, f, nrhs, (const double* const*)B, ldb, (double* const*)X, ldx);
+// the one internal entry of the solves (NdSolve, ndlu_internal.h): one column is the single-column sweep, more go to the pass driver
+int ndlu_solve_run(lsa_ctx* ctx, const NdSolve& rq, NdSolveInfo* info) {
+    if (info) *info = {0, 1};
+    const int32_t most = rq.sets ? kNdBatchMax : 1;
+    if (rq.J < 1 || rq.J > most) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: J = %d outside [1, %d]", rq.who, rq.J, most);
+    if (rq.nrhs == 1) return ndlu_solve_column(ctx, rq, rq.B, rq.X);
+    return nd_dispatch_solve(ctx, rq.who, true, rq.J, rq.f, rq.trans, rq.vdtype, [&](auto mt, auto vt, auto dir) {
+        using MT = decltype(mt);
+        using VT = decltype(vt);
+        constexpr int DIR = decltype(dir)::value;
+        return rq.sets ? nd_solve_passes<MT, VT, kNdBatchMax, DIR>(ctx, rq, info) : nd_solve_passes<MT, VT, 1, DIR>(ctx, rq, info);
+    });
 }

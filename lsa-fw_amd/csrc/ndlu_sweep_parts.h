@@ -255,4 +255,22 @@ void nd_with_lpr(int32_t sweep_rows, F&& launch) {
     launch(std::integral_constant<int, 16>{});
 }
 
+// The one place that picks a solve's instance, single columns and blocks alike: fn(factor scalar, vector scalar, direction) for the
+// factor dtype, the vector dtype and trans (0 N, 1 T, 2 H) of a solve on J factorisations, behind the argument checks.  The direction
+// is std::integral_constant<int, 0 | 1 | 2>; real factors never get 2 (C^H = C^T, one instance).  `block`: the multi-column sweeps,
+// which have no form for a forest cut over ranks.  `who` names the entry in the message.
+template <typename F>
+int nd_dispatch_solve(lsa_ctx* ctx, const char* who, bool block, int32_t J, lsa_ndlu* const* f, int trans, int vdtype, F&& fn) {
+    using N = std::integral_constant<int, 0>;
+    using T = std::integral_constant<int, 1>;
+    using H = std::integral_constant<int, 2>;
+    for (int32_t z = 0; block && z < J; ++z)
+        if (f[z]->S.nranks > 1 || f[z]->S.has_dist) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the multi-column sweeps need one rank and no distributed node", who);
+    if (f[0]->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: complex factors need complex vectors", who);
+    if (f[0]->S.n == 0) return LSA_OK;
+    if (f[0]->dtype == LSA_C128) return trans == 0 ? fn(cplx{}, cplx{}, N{}) : trans == 2 ? fn(cplx{}, cplx{}, H{}) : fn(cplx{}, cplx{}, T{});
+    if (vdtype == LSA_C128) return trans == 0 ? fn(double{}, cplx{}, N{}) : fn(double{}, cplx{}, T{});
+    return trans == 0 ? fn(double{}, double{}, N{}) : fn(double{}, double{}, T{});
+}
+
 }  // namespace

@@ -556,41 +556,23 @@ int nd_sweepT(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, const VT* const* b, V
     return LSA_OK;
 }
 
-// the one place that picks the sweeps' instance: fn(factor scalar, vector scalar) for the (factor dtype, vector dtype) of a
-// solve, after an aliased right-hand side of each of the J problems went to the problem's own buffer (bd: J pointers, updated).
-// `who` names the entry in the message.
-template <typename F>
-int nd_dispatch_solve(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int vdtype, const void** bd, void* const* x, F&& fn) {
-    if (f[0]->dtype == LSA_C128 && vdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: complex factors need complex vectors", who);
-    if (f[0]->S.n == 0) return LSA_OK;
-    for (int32_t z = 0; z < J; ++z)
-        if (bd[z] == x[z]) {
-            LSA_HIP_CHECK(ctx, hipMemcpyAsync(f[z]->d_tmp, bd[z], (size_t)f[z]->S.n * esize(vdtype), hipMemcpyDeviceToDevice, ctx->stream));
-            bd[z] = f[z]->d_tmp;
-        }
-    if (f[0]->dtype == LSA_C128) return fn(cplx{}, cplx{});
-    if (vdtype == LSA_C128) return fn(double{}, cplx{});
-    return fn(double{}, double{});
-}
-
+// x_z = C_z^-1 b_z (trans 1: C_z^-T, 2: C_z^-H) for J problems on the sweeps of capacity NB, after an aliased right-hand side of
+// each of them went to the problem's own buffer (bd: J pointers, updated)
 template <int NB>
-int nd_solve(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int vdtype, const void** bd, void* const* x) {
-    return nd_dispatch_solve(ctx, who, J, f, vdtype, bd, x, [&](auto mt, auto vt) {
+int nd_solve(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int trans, int vdtype, const void** bd, void* const* x) {
+    return nd_dispatch_solve(ctx, who, false, J, f, trans, vdtype, [&](auto mt, auto vt, auto dir) {
         using MT = decltype(mt);
         using VT = decltype(vt);
-        return f[0]->ordered ? nd_sweep<MT, VT, true, NB>(ctx, J, f, (const VT* const*)bd, (VT* const*)x)
-                             : nd_sweep<MT, VT, false, NB>(ctx, J, f, (const VT* const*)bd, (VT* const*)x);
-    });
-}
-
-template <int NB>
-int nd_solve_adjoint(lsa_ctx* ctx, const char* who, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, const void** bd, void* const* x) {
-    return nd_dispatch_solve(ctx, who, J, f, vdtype, bd, x, [&](auto mt, auto vt) {
-        using MT = decltype(mt);
-        using VT = decltype(vt);
-        if constexpr (std::is_same<MT, cplx>::value)  // (real factors: C^H = C^T)
-            if (conj) return nd_sweepT<MT, VT, true, NB>(ctx, J, f, (const VT* const*)bd, (VT* const*)x);
-        return nd_sweepT<MT, VT, false, NB>(ctx, J, f, (const VT* const*)bd, (VT* const*)x);
+        constexpr int DIR = decltype(dir)::value;
+        for (int32_t z = 0; z < J; ++z)
+            if (bd[z] == x[z]) {
+                LSA_HIP_CHECK(ctx, hipMemcpyAsync(f[z]->d_tmp, bd[z], (size_t)f[z]->S.n * sizeof(VT), hipMemcpyDeviceToDevice, ctx->stream));
+                bd[z] = f[z]->d_tmp;
+            }
+        if constexpr (DIR != 0) return nd_sweepT<MT, VT, DIR == 2, NB>(ctx, J, f, (const VT* const*)bd, (VT* const*)x);
+        else
+            return f[0]->ordered ? nd_sweep<MT, VT, true, NB>(ctx, J, f, (const VT* const*)bd, (VT* const*)x)
+                                 : nd_sweep<MT, VT, false, NB>(ctx, J, f, (const VT* const*)bd, (VT* const*)x);
     });
 }
 
@@ -617,20 +599,18 @@ bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g) {
     return true;
 }
 
+// x = C^-1 b on device pointers (b and x distinct or identical: an aliased right-hand side is copied first)
+int ndlu_solve_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, const void* b, void* x) { return nd_solve<1>(ctx, "lsa_ndlu_solve", 1, &f, 0, vdtype, &b, &x); }
+
 // x = C^-T b (conj == 0) or C^-H b (conj != 0) on the factors of C
 int ndlu_solve_adjoint_dev(lsa_ctx* ctx, lsa_ndlu* f, int conj, int vdtype, const void* b, void* x) {
-    return nd_solve_adjoint<1>(ctx, "lsa_ndlu_solve_adjoint", 1, &f, conj, vdtype, &b, &x);
+    return nd_solve<1>(ctx, "lsa_ndlu_solve_adjoint", 1, &f, conj ? 2 : 1, vdtype, &b, &x);
 }
 
-// the same for J factorisations of one analysis (nd_batch_compatible), one launch per level and direction for all of them
-int ndlu_solve_batch_adjoint_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int conj, int vdtype, const void** b, void* const* x) {
-    return nd_solve_adjoint<kNdBatchMax>(ctx, "lsa_ndlu_solve_batch_adjoint", J, f, conj, vdtype, b, x);
-}
-
-// x = C^-1 b on device pointers (b and x distinct or identical: an aliased right-hand side is copied first)
-int ndlu_solve_dev(lsa_ctx* ctx, lsa_ndlu* f, int vdtype, const void* b, void* x) { return nd_solve<1>(ctx, "lsa_ndlu_solve", 1, &f, vdtype, &b, &x); }
-
-// the same for J factorisations of one analysis (nd_batch_compatible), one launch per level and direction for all of them
-int ndlu_solve_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, const void** b, void* const* x) {
-    return nd_solve<kNdBatchMax>(ctx, "lsa_ndlu_solve_batch", J, f, vdtype, b, x);
+// one column of a request (ndlu_solve_run, ndlu_multi.hip): b[z] -> x[z] on the sweeps of its capacity and direction.  The sweeps
+// work on a copy of the pointers, where an aliased right-hand side is replaced by the problem's own copy of it.
+int ndlu_solve_column(lsa_ctx* ctx, const NdSolve& rq, const void* const* b, void* const* x) {
+    const void* bd[kNdBatchMax];
+    std::copy(b, b + rq.J, bd);  // (ndlu_solve_run checked J)
+    return rq.sets ? nd_solve<kNdBatchMax>(ctx, rq.who, rq.J, rq.f, rq.trans, rq.vdtype, bd, x) : nd_solve<1>(ctx, rq.who, 1, rq.f, rq.trans, rq.vdtype, bd, x);
 }

@@ -26,7 +26,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "lsa_internal.h"
+#include "ndlu_internal.h"
 
 namespace {
 
@@ -168,7 +168,10 @@ int rz_forcings_block(lsa_ctx* ctx, lsa_resolvent* l, cplx* Q, int32_t nvec, con
             return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent forcings: gain %d is %.3e: no forcing belongs to it", c, gain[c]);
     // (a product is counted where its column is accepted: a column the loop takes over forms, and counts, its own)
     for (int32_t c = 0; c < nvec; ++c) LSA_CHECK(k_spmv(ctx, l->Qq, LSA_C128, Q + (size_t)c * (size_t)n, l->blk_tm + (size_t)c * (size_t)n));
-    LSA_CHECK(ndlu_solve_multi_adjoint_dev(ctx, l->P.nd, 1, LSA_C128, nvec, l->blk_tm, n, l->blk_za, n));
+    const void* tms = l->blk_tm;
+    void* zas = l->blk_za;
+    const NdSolve rq = {1, &l->P.nd, false, 2, LSA_C128, nvec, &tms, n, &zas, n, "lsa_resolvent forcings"};
+    LSA_CHECK(ndlu_solve_run(ctx, rq));
     for (int32_t c = 0; c < nvec; ++c) {
         const cplx* tm = l->blk_tm + (size_t)c * (size_t)n;
         const cplx* za = l->blk_za + (size_t)c * (size_t)n;

@@ -6,20 +6,13 @@
 #include <cmath>
 #include <complex>
 
-#include "lsa_internal.h"
+#include "ndlu_internal.h"  // (the solves on the exact LU's factors; esize, now_s, k_allgather_inplace)
 
 int ilu_check_abort(lsa_ctx* ctx, lsa_ilu* pc);
-bool nd_batch_compatible(const lsa_ndlu* f, const lsa_ndlu* g);                                                      // ndlu_sweeps.hip
-int ndlu_solve_batch_dev(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, int vdtype, const void** b, void* const* x);  // ndlu_sweeps.hip
-int k_allgather_inplace(lsa_ctx* ctx, void* vec, size_t bytes_per_rank);  // comm.hip
 
 namespace {
 
 using zc = std::complex<double>;
-inline size_t esize(int dtype) { return dtype == LSA_C128 ? 16 : 8; }
-inline double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // The switches of the Krylov steps ("Environment knobs"), read once per process.
 struct KrylovSwitches {
@@ -1506,7 +1499,7 @@ int krylov_restart_queued(lsa_ctx* ctx, lsa_krylov* k, int32_t m, int32_t knew, 
 // ---- lockstep expansion of a group (lsa_krylov_solve_batch, dense.hip) ---------------------------------------------------------
 // Problems whose plan is the pipelined DCGS2 tail form on factors of one analysis advance together: a round queues one step of
 // every such problem that still has one in this read-back period -- M v_j where the previous tail did not leave it, ONE batched
-// sweep pair (ndlu_solve_batch_dev), ONE batched reduction, update and tail -- and one read-back covers up to k->batch rounds of
+// sweep pair (ndlu_solve_run on the round's sets), ONE batched reduction, update and tail -- and one read-back covers up to k->batch rounds of
 // all of them (their slots, pairs and checks lie round-major in the group's buffers: two copies, one synchronisation).  The
 // accept loop is accept_steps per problem over its own slots.  A problem whose plan changes (a miss of ksp_rtol, k->pipeline
 // going false), that breaks down or is not eligible finishes its expansion through extend_rest from its cursor, exactly as its
@@ -1640,7 +1633,8 @@ int krylov_extend_batch(lsa_ctx* ctx, KrylovGroupBuf* gb, lsa_krylov* const* ks,
                 parts[R] = gb->tail_parts + cell * 2 * (size_t)gb->nparts;
                 ++R;
             }
-            if (rc == LSA_OK) rc = ndlu_solve_batch_dev(ctx, R, nd, LSA_C128, rhs, xr);
+            const NdSolve sweeps = {R, nd, true, 0, LSA_C128, 1, rhs, 0, xr, 0, "lsa_krylov_solve_batch"};
+            if (rc == LSA_OK) rc = ndlu_solve_run(ctx, sweeps);
             if (rc == LSA_OK) rc = k_dcgs2_step_batch(ctx, R, ks[lead]->n, jr, Vr, ks[lead]->n, yr, fr, slot, ncv, work);
             if (rc == LSA_OK) rc = k_dcgs2_tail_batch(ctx, R, ks[lead]->n, jr, Vr, ks[lead]->n, yr, work, Mr, Cr, tr, parts, slot, ncv);
             for (int32_t z = 0; z < J; ++z)

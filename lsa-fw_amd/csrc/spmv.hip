@@ -677,14 +677,7 @@ int lsa_spmv_time(lsa_ctx* ctx, const lsa_mat* A, const lsa_vec* x, lsa_vec* y, 
     LSA_CHECK(check_spmv_args(ctx, A, x, y, "lsa_spmv_time"));
     if (iters <= 0 || !avg_ms) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_time: iters must be positive");
     if (y->n != A->n) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_time: y has the wrong length");
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; ++i) LSA_CHECK(k_spmv(ctx, A, x->dtype, x->d, y->d));
-    LSA_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    LSA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0.f;
-    LSA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *avg_ms = (double)ms / iters;
-    return LSA_OK;
+    return lsa_time_runs(ctx, false, iters, avg_ms, [&] { return k_spmv(ctx, A, x->dtype, x->d, y->d); });
 }
 
 }  // extern "C"

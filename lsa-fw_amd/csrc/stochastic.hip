@@ -12,11 +12,11 @@
 //
 // One step j of kind 0 (rhs = Q_q v_j is left by the previous step's tail):
 //     b = rhs + 0 i                             sf_widen_kernel: one complex right-hand side for all nodes
-//     for every node k:  z_k = C_k^-H b         the transposed, conjugated sweeps (ndlu_solve_adjoint_dev), node by node, or the
+//     for every node k:  z_k = C_k^-H b         the transposed, conjugated sweeps (ndlu_solve_run), node by node, or the
 //                                               batched ones in groups of <= 16 sets (set_batch_adjoint)
 //                        ca_k = C_k^H z_k       k_spmv_transpose, for the check (set_batch_adjoint: k_spmv_transpose_batch, 16 per launch)
 //     TM = Q_f [z_0 .. z_{N-1}]                 one k_spmm on the block
-//     for every node k:  w_k = C_k^-1 tm_k      ndlu_solve_dev, or the batched sweeps in groups of <= 16 sets (set_batch_forward)
+//     for every node k:  w_k = C_k^-1 tm_k      the forward sweeps, or the batched ones in groups of <= 16 sets (set_batch_forward)
 //     CF[:, k] = C_k w_k for all k              sf_shifted_spmm_kernel: ONE launch, A's and M's values read once for <= 16 columns
 //     log[4 s + 0..3], s < 2N                   sf_sums_kernel + sf_sums_finish_kernel: |b - z|^2, |b|^2, |x|^2 of all 2N solves and
 //                                               Re(rhs^H w_k) of the second ones, one launch pair
@@ -188,8 +188,16 @@ bool sf_adjoint(const lsa_stochastic* h, int pos) { return (h->kind == 0) == (po
 const lsa_mat* sf_inner(const lsa_stochastic* h) { return h->kind == 0 ? h->Qq : h->Qf; }
 const lsa_mat* sf_middle(const lsa_stochastic* h) { return h->kind == 0 ? h->Qf : h->Qq; }
 
+// x_z = C_z^-1 b_z (adjoint: C_z^-H b_z) on J factor sets: one set is the solo instance of the sweeps, a longer run the batch
+int sf_request(lsa_ctx* ctx, int32_t J, lsa_ndlu* const* f, bool adjoint, const void* const* b, void* const* x) {
+    const NdSolve rq = {J, f, J > 1, adjoint ? 2 : 0, LSA_C128, 1, b, 0, x, 0, "lsa_stochastic"};
+    return ndlu_solve_run(ctx, rq);
+}
+
 int sf_sweeps(lsa_ctx* ctx, lsa_stochastic* h, int32_t k, bool adjoint, const cplx* b, cplx* x) {
-    return adjoint ? ndlu_solve_adjoint_dev(ctx, h->S->F[(size_t)k], 1, LSA_C128, b, x) : ndlu_solve_dev(ctx, h->S->F[(size_t)k], LSA_C128, b, x);
+    const void* bs = b;
+    void* xs = x;
+    return sf_request(ctx, 1, &h->S->F[(size_t)k], adjoint, &bs, &xs);
 }
 
 int sf_times_c(lsa_ctx* ctx, lsa_stochastic* h, int32_t k, bool adjoint, const cplx* x, cplx* y) {
@@ -216,12 +224,8 @@ int sf_solve_all(lsa_ctx* ctx, lsa_stochastic* h, bool adjoint, const cplx* B, i
                 xs[z] = X + (size_t)run.node[z] * (size_t)n;
                 done[(size_t)run.node[z]] = 1;
             }
-            if (run.J > 1) {
-                LSA_CHECK(adjoint ? ndlu_solve_batch_adjoint_dev(ctx, run.J, run.f, 1, LSA_C128, bs, xs) : ndlu_solve_batch_dev(ctx, run.J, run.f, LSA_C128, bs, xs));
-                ++(adjoint ? h->adjoint_batches : h->forward_batches);
-            } else {
-                LSA_CHECK(adjoint ? ndlu_solve_adjoint_dev(ctx, run.f[0], 1, LSA_C128, bs[0], xs[0]) : ndlu_solve_dev(ctx, run.f[0], LSA_C128, bs[0], xs[0]));
-            }
+            LSA_CHECK(sf_request(ctx, run.J, run.f, adjoint, bs, xs));
+            if (run.J > 1) ++(adjoint ? h->adjoint_batches : h->forward_batches);
         }
     }
     const double one[2] = {1.0, 0.0};

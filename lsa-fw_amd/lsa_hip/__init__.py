@@ -911,19 +911,8 @@ class NdLu:
         bit-identical to :meth:`solve_adjoint`."""
         if trans not in _TRANS:
             raise ValueError(f"trans must be 'N', 'T' or 'H', got {trans!r}")
-        J = len(factors)
-        if J == 0 or len(bs) != J or len(xs) != J:
-            raise ValueError("solve_batch needs as many right-hand sides and outputs as factorisations (at least one)")
-        if J > NDLU_BATCH_MAX:
-            raise ValueError(f"solve_batch takes at most {NDLU_BATCH_MAX} factorisations, got {J}")
-        ctx = factors[0].ctx
-        if any(f.ctx is not ctx for f in factors) or any(v.ctx is not ctx for v in list(bs) + list(xs)):
-            raise ValueError("solve_batch: the factorisations and vectors must live in one context")
-        arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
-        if trans == "N":
-            ctx.check(ctx._lib.lsa_ndlu_solve_batch(ctx.handle, J, arr(factors), arr(bs), arr(xs)))
-        else:
-            ctx.check(ctx._lib.lsa_ndlu_solve_batch_adjoint(ctx.handle, J, arr(factors), int(trans == "H"), arr(bs), arr(xs)))
+        ctx, args = NdLu._sets_args("solve_batch", factors, bs, xs, None if trans == "N" else int(trans == "H"))
+        ctx.check((ctx._lib.lsa_ndlu_solve_batch if trans == "N" else ctx._lib.lsa_ndlu_solve_batch_adjoint)(*args))
 
     def solve_adjoint(self, b: DeviceVector, x: DeviceVector, conj: bool = True) -> None:
         """x = C^-H b (``conj``) or C^-T b on the same factors."""
@@ -954,21 +943,34 @@ class NdLu:
         return ms.value
 
     @staticmethod
-    def _multi_batch_args(factors, Bs, Xs, nrhs, ldb, ldx, trans):
-        # (the three argument errors come first: nothing of the library, not even a context, is touched before them)
+    def _sets_args(name, factors, Bs, Xs, flag, nrhs=None, ldb=None, ldx=None, refuse=None):
+        """The arguments of a C entry for a batch of factor sets, behind the checks of the method ``name``: the lists, the
+        one-context rule, the handle arrays, and for blocks (``nrhs`` given) the leading dimensions, ``n`` by default.  ``flag``:
+        the entry's ``trans`` or ``conj`` argument (``None``: it has none); ``refuse``: an argument error of the caller's, raised
+        in its place among the checks."""
+        # (the argument errors come first: nothing of the library, not even a context, is touched before them)
         J = len(factors)
-        if J < 1 or J > NDLU_BATCH_MAX:
-            raise ValueError(f"solve_multi_batch takes between 1 and {NDLU_BATCH_MAX} factorisations, got {J}")
-        if len(Bs) != J or len(Xs) != J:
-            raise ValueError(f"solve_multi_batch needs as many blocks B and X as factorisations ({J}), got {len(Bs)} and {len(Xs)}")
-        if trans != "N":
-            raise ValueError(f"solve_multi_batch: trans must be 'N', got {trans!r}: the transposed form on a batch of factor sets is not built")
+        if nrhs is None:  # one vector per problem
+            if J == 0 or len(Bs) != J or len(Xs) != J:
+                raise ValueError(f"{name} needs as many right-hand sides and outputs as factorisations (at least one)")
+            if J > NDLU_BATCH_MAX:
+                raise ValueError(f"{name} takes at most {NDLU_BATCH_MAX} factorisations, got {J}")
+        else:
+            if J < 1 or J > NDLU_BATCH_MAX:
+                raise ValueError(f"{name} takes between 1 and {NDLU_BATCH_MAX} factorisations, got {J}")
+            if len(Bs) != J or len(Xs) != J:
+                raise ValueError(f"{name} needs as many blocks B and X as factorisations ({J}), got {len(Bs)} and {len(Xs)}")
+        if refuse:
+            raise ValueError(refuse)
         ctx = factors[0].ctx
         if any(f.ctx is not ctx for f in factors) or any(v.ctx is not ctx for v in list(Bs) + list(Xs)):
-            raise ValueError("solve_multi_batch: the factorisations and vectors must live in one context")
+            raise ValueError(f"{name}: the factorisations and vectors must live in one context")
         arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
+        head = (ctx.handle, J, arr(factors)) + (() if flag is None else (flag,))
+        if nrhs is None:
+            return ctx, head + (arr(Bs), arr(Xs))
         n = factors[0].n
-        return ctx, (ctx.handle, J, arr(factors), 0, int(nrhs), arr(Bs), int(n if ldb is None else ldb), arr(Xs), int(n if ldx is None else ldx))
+        return ctx, head + (int(nrhs), arr(Bs), int(n if ldb is None else ldb), arr(Xs), int(n if ldx is None else ldx))
 
     @staticmethod
     def solve_multi_batch(factors: "list[NdLu]", Bs: "list[DeviceVector]", Xs: "list[DeviceVector]", nrhs: int, ldb: int | None = None,
@@ -977,33 +979,18 @@ class NdLu:
         (``lsa_ndlu_solve_multi_batch``): every launch of the sweeps carries all columns of a pass for all sets.  The blocks share
         ``ldb`` and ``ldx`` (default ``n``); several sets may read one ``B``; ``Bs[z] is Xs[z]`` solves in place.  Every column is
         bit-identical to :meth:`solve`.  ``trans`` must be ``"N"``: the transposed form is :meth:`solve_multi_batch_adjoint`."""
-        ctx, args = NdLu._multi_batch_args(factors, Bs, Xs, nrhs, ldb, ldx, trans)
+        refuse = None if trans == "N" else f"solve_multi_batch: trans must be 'N', got {trans!r}: the transposed form on a batch of factor sets is not built"
+        ctx, args = NdLu._sets_args("solve_multi_batch", factors, Bs, Xs, 0, nrhs, ldb, ldx, refuse)
         ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch(*args))
 
     @staticmethod
     def time_solve_multi_batch(factors: "list[NdLu]", Bs: "list[DeviceVector]", Xs: "list[DeviceVector]", nrhs: int, iters: int,
                                ldb: int | None = None, ldx: int | None = None) -> float:
         """Mean milliseconds of one block solve on all sets over ``iters`` back-to-back repetitions (``lsa_ndlu_solve_multi_batch_time``)."""
-        ctx, args = NdLu._multi_batch_args(factors, Bs, Xs, nrhs, ldb, ldx, "N")
+        ctx, args = NdLu._sets_args("solve_multi_batch", factors, Bs, Xs, 0, nrhs, ldb, ldx)
         ms = _DBL(0.0)
         ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch_time(*args, int(iters), ctypes.byref(ms)))
         return ms.value
-
-    @staticmethod
-    def _multi_batch_adjoint_args(factors, Bs, Xs, nrhs, conj, ldb, ldx):
-        # (the two argument errors come first: nothing of the library, not even a context, is touched before them)
-        J = len(factors)
-        if J < 1 or J > NDLU_BATCH_MAX:
-            raise ValueError(f"solve_multi_batch_adjoint takes between 1 and {NDLU_BATCH_MAX} factorisations, got {J}")
-        if len(Bs) != J or len(Xs) != J:
-            raise ValueError(f"solve_multi_batch_adjoint needs as many blocks B and X as factorisations ({J}), got {len(Bs)} and {len(Xs)}")
-        ctx = factors[0].ctx
-        if any(f.ctx is not ctx for f in factors) or any(v.ctx is not ctx for v in list(Bs) + list(Xs)):
-            raise ValueError("solve_multi_batch_adjoint: the factorisations and vectors must live in one context")
-        arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
-        n = factors[0].n
-        return ctx, (ctx.handle, J, arr(factors), int(bool(conj)), int(nrhs), arr(Bs), int(n if ldb is None else ldb), arr(Xs),
-                     int(n if ldx is None else ldx))
 
     @staticmethod
     def solve_multi_batch_adjoint(factors: "list[NdLu]", Bs: "list[DeviceVector]", Xs: "list[DeviceVector]", nrhs: int, conj: bool = True,
@@ -1012,7 +999,7 @@ class NdLu:
         one analysis (``lsa_ndlu_solve_multi_batch_adjoint``): every launch of the transposed sweeps carries all columns of a pass for
         all sets.  The rules for the blocks are those of :meth:`solve_multi_batch`.  Every column is bit-identical to
         :meth:`solve_adjoint`."""
-        ctx, args = NdLu._multi_batch_adjoint_args(factors, Bs, Xs, nrhs, conj, ldb, ldx)
+        ctx, args = NdLu._sets_args("solve_multi_batch_adjoint", factors, Bs, Xs, int(bool(conj)), nrhs, ldb, ldx)
         ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch_adjoint(*args))
 
     @staticmethod
@@ -1020,7 +1007,7 @@ class NdLu:
                                        conj: bool = True, ldb: int | None = None, ldx: int | None = None) -> float:
         """Mean milliseconds of one transposed block solve on all sets over ``iters`` back-to-back repetitions
         (``lsa_ndlu_solve_multi_batch_adjoint_time``)."""
-        ctx, args = NdLu._multi_batch_adjoint_args(factors, Bs, Xs, nrhs, conj, ldb, ldx)
+        ctx, args = NdLu._sets_args("solve_multi_batch_adjoint", factors, Bs, Xs, int(bool(conj)), nrhs, ldb, ldx)
         ms = _DBL(0.0)
         ctx.check(ctx._lib.lsa_ndlu_solve_multi_batch_adjoint_time(*args, int(iters), ctypes.byref(ms)))
         return ms.value
