@@ -467,7 +467,7 @@ __global__ __launch_bounds__(256) void nd_gj_gemm_kernel(const int32_t* __restri
 // pairs per 32 columns, each reading its column with a stride of a front row.  Levels whose tallest pivot block has
 // LSA_ND_TP_MIN rows or more choose the 32 pivot rows of a block by a tournament instead (communication-avoiding LU,
 // Grigori, Demmel, Xiang 2011): every 256 rows pick their 32 best rows by Gaussian elimination with partial pivoting on
-// their slice of the block's columns (thread per row, the row in registers); winners meet four sets at a time until one
+// their slice of the block's columns (thread per row, the row in registers); winners meet eight sets at a time (kTA) until one
 // set is left; the last workgroup inverts the 32 x 32 pivot tile.  The block's columns then are one small product per row
 // (nd_tp_colblock_kernel), and the staged rank-32 product above does the rest: 5-7 launches per 32 columns, all of them
 // wide.  The pivot rows reach ipiv / rowq as with the panel launches, so everything downstream is unchanged.
