@@ -37,9 +37,8 @@ from dataclasses import dataclass, field
 import numpy as np
 import scipy.sparse as sp
 
-from .eigen import _require_matching_squares, _wrap
-from .resolvent import checked_side, device_weight, shared_pattern
-from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType, symmetry_defect, _SYMMETRY_TOL
+from .exact_lu import ExactLuFrontEnd, checked_side
+from .utils import PreconditionerType
 
 logger = logging.getLogger(__name__)
 
@@ -104,28 +103,23 @@ def horizon_steps(T, dt: float) -> int:
     return int(steps)
 
 
-class TransientGrowthSolver:
+class TransientGrowthSolver(ExactLuFrontEnd):
     """Optimal energy gains of ``(A, M)`` over horizons ``T = N dt``; thin shell around :class:`iEpsSolver` 's preparation (union
     pattern, nested-dissection ordering, permuted numbering, upload, LU) and ``lsa_hip.GrowthBasis``.  The operator and its
     factorisation of ``A - M / dt`` (``scheme="sdirk2"``: ``A - M / (gamma dt)``) are built by the first :meth:`solve` and kept until :meth:`release`."""
 
+    NAME = "Transient growth"
+    NEEDS_M = "the energy is measured in the M-inner product"
+    NEEDS_LU = "every solve of the march runs on its factors"
+    REAL_A = "Transient growth needs real A and M (a real march on real factors); A is complex"
+    REAL_M = "Transient growth needs real A and M (a real march on real factors); M is complex"
+
     def __init__(self, A, M, cfg: TransientGrowthConfig, *, constrained="auto", device: int = 0, layout: str = "single",
                  pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
                  ksp_rtol: float | None = None, response_window=None, response_weight=None) -> None:
-        if A is None:
-            raise ValueError("Operator A is required.")
-        if M is None:
-            raise ValueError("Transient growth needs M: the energy is measured in the M-inner product")
-        if cfg is None:
+        if A is not None and M is not None and cfg is None:  # (after the refusals of a missing A or M, before the pencil is looked at)
             raise ValueError("Transient growth needs a TransientGrowthConfig: the time step dt has no default")
-        A, M = _wrap(A), _wrap(M)
-        _require_matching_squares(A, M)
-        As, Ms = A.as_scipy_array(), M.as_scipy_array()
-        if As.dtype.kind == "c" or Ms.dtype.kind == "c":
-            raise ValueError(f"Transient growth needs real A and M (a real march on real factors); {'A' if As.dtype.kind == 'c' else 'M'} is complex")
-        defect = symmetry_defect(Ms)
-        if not defect <= _SYMMETRY_TOL:
-            raise ValueError(f"Transient growth needs a symmetric M; its relative symmetry defect is {defect:.3e}")
+        A, M, As, Ms = self._checked_pencil(A, M)
         # the response weight: a window (Q = D M D) or a matrix, checked here and built on the device with the basis
         self._response = checked_side("response", response_window, response_weight, Ms)
         self._cfg = cfg
@@ -153,22 +147,9 @@ class TransientGrowthSolver:
                     raise ValueError(f"constrained index {int(coupled[0])} is coupled to other dofs in A or M ({coupled.size} such indices): only a "
                                      "dof whose row and column hold no off-diagonal non-zero can be left out of the flow")
                 self._constrained = idx
-        if layout != "single":
-            raise NotImplementedError(f"Transient growth runs on one GPU; the layout is '{layout}'")
-        pc_type = PreconditionerType(pc_type)
-        if pc_type not in (PreconditionerType.LU, PreconditionerType.CHOLESKY) or ilu_levels is not None:
-            raise NotImplementedError("Transient growth needs the exact LU (PreconditionerType.LU): every solve of the march runs on its "
-                                      f"factors; the preconditioner is {pc_type.name}" + ("" if ilu_levels is None else f" with ILU level {ilu_levels}"))
-        eps = iEpsSolver(A, M, device=device, seed=seed, ksp_rtol=ksp_rtol)
-        eps.set_problem_type(iEpsProblemType.GNHEP)
-        eps.set_st_type(iSTType.SINVERT)
-        eps.set_st_pc_type(pc_type)
-        eps.set_tolerances(cfg.atol, cfg.max_it)
-        eps.set_dimensions(cfg.num_modes, cfg.ncv)
-        eps.set_target(1.0 / (SCHEMES[cfg.scheme] * cfg.dt))
-        self._eps = eps
-        self._seed = seed
-        self._n = n
+        self._set_up(A, M, cfg.atol, cfg.max_it, (cfg.num_modes, cfg.ncv), device=device, layout=layout, pc_type=pc_type, ilu_levels=ilu_levels,
+                     seed=seed, ksp_rtol=ksp_rtol)
+        self._eps.set_target(1.0 / (SCHEMES[cfg.scheme] * cfg.dt))
         self._run = None  # the operator (with its factors) and the basis, from the first solve to release()
         self._basis = None
 
@@ -181,27 +162,17 @@ class TransientGrowthSolver:
         """The dof indices left out of the flow (sorted)."""
         return self._constrained
 
-    @property
-    def solver(self) -> iEpsSolver:
-        """The eigen path's solver object whose preparation this one shares."""
-        return self._eps
-
     def _open(self, steps: int):
         import lsa_hip
 
-        eps = self._eps
-        run = eps._open(basis=False)
+        run, prep = self._open_operator()
         try:
-            prep, op = eps._prepared, run["op"]
-            if prep["pc_code"] != 2 or op.stats().get("pc_fallback"):
-                raise NotImplementedError("Transient growth needs the exact LU; it does not fit the device memory")
             keep = np.ones(self._n)
             keep[self._constrained] = 0.0
-            basis = lsa_hip.GrowthBasis(prep["ctx"], op, run["ncv"], steps, keep[prep["perm"]], self._cfg.scheme)  # (the iteration runs in permuted numbering)
+            basis = lsa_hip.GrowthBasis(prep["ctx"], run["op"], run["ncv"], steps, keep[prep["perm"]], self._cfg.scheme)  # (the iteration runs in permuted numbering)
             basis.set_row_permutation(prep["perm"])
             if self._response is not None:
-                pattern = shared_pattern(eps._A.as_scipy_array(), eps._M.as_scipy_array()) if self._response[0] == "weight" else None
-                basis.set_response_weight(device_weight(prep, self._response, pattern))
+                basis.set_response_weight(*self._weights_on_device(prep, (self._response,)))
         except BaseException:
             run.clear()
             raise
@@ -251,7 +222,7 @@ class TransientGrowthSolver:
         if self._run is not None:
             self._run.clear()
             self._run = None
-        self._eps.release()
+        super().release()
 
     def __del__(self):
         try:

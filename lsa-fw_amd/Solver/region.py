@@ -38,8 +38,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .eigen import _require_matching_squares, _wrap
-from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType
+from .exact_lu import ExactLuFrontEnd
+from .utils import PreconditionerType
 
 logger = logging.getLogger(__name__)
 
@@ -153,49 +153,30 @@ def _check_config(cfg: RegionConfig) -> None:
         raise ValueError("batch_nodes = True needs the factor sets of all nodes alive: keep_factors = False refactorises one set node by node")
 
 
-class RegionEigenSolver:
+class RegionEigenSolver(ExactLuFrontEnd):
     """All eigenvalues of ``(A, M)`` inside a region; thin shell around :class:`iEpsSolver` 's preparation (union pattern,
     nested-dissection ordering, permuted numbering, upload, pattern-only LU analysis) and ``lsa_hip.ContourSolver``."""
+
+    NAME = "The region eigensolver"
+    NEEDS_M = "the contour integral is that of the pencil (A, M)"
+    NEEDS_LU = "every node of the contour is a block solve on its factors"
+    REAL_M = "The region eigensolver needs a real M; M is complex"
+    SYMMETRIC_M = False
 
     def __init__(self, A, M, cfg: RegionConfig | None = None, *, device: int = 0, layout: str = "single",
                  pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
                  ksp_rtol: float | None = None) -> None:
-        if A is None:
-            raise ValueError("Operator A is required.")
-        if M is None:
-            raise ValueError("The region eigensolver needs M: the contour integral is that of the pencil (A, M)")
-        A, M = _wrap(A), _wrap(M)
-        _require_matching_squares(A, M)
-        if M.as_scipy_array().dtype.kind == "c":
-            raise ValueError("The region eigensolver needs a real M; M is complex")
+        A, M, _, _ = self._checked_pencil(A, M)
         self._cfg = cfg if cfg is not None else RegionConfig()
         _check_config(self._cfg)
         if self._cfg.subspace > A.shape[0]:
             raise ValueError(f"subspace = {self._cfg.subspace} exceeds the problem size {A.shape[0]}")
-        if layout != "single":
-            raise NotImplementedError(f"The region eigensolver runs on one GPU; the layout is '{layout}'")
-        pc_type = PreconditionerType(pc_type)
-        if pc_type not in (PreconditionerType.LU, PreconditionerType.CHOLESKY) or ilu_levels is not None:
-            raise NotImplementedError("The region eigensolver needs the exact LU (PreconditionerType.LU): every node of the contour is a block "
-                                      f"solve on its factors; the preconditioner is {pc_type.name}" + ("" if ilu_levels is None else f" with ILU level {ilu_levels}"))
-        eps = iEpsSolver(A, M, device=device, seed=seed, ksp_rtol=ksp_rtol)
-        eps.set_problem_type(iEpsProblemType.GNHEP)
-        eps.set_st_type(iSTType.SINVERT)
-        eps.set_st_pc_type(pc_type)
-        eps.set_tolerances(self._cfg.atol, self._cfg.max_it)
-        self._eps = eps
-        self._n = A.shape[0]
-        self._seed = seed
-        self._ksp_rtol = ksp_rtol if ksp_rtol is not None else float(np.clip(self._cfg.atol * 1e-2, 1e-13, 1e-8))
+        self._set_up(A, M, self._cfg.atol, self._cfg.max_it, None, device=device, layout=layout, pc_type=pc_type, ilu_levels=ilu_levels, seed=seed,
+                     ksp_rtol=ksp_rtol)
 
     @property
     def config(self) -> RegionConfig:
         return self._cfg
-
-    @property
-    def solver(self) -> iEpsSolver:
-        """The eigen path's solver object whose preparation this one shares (``prepare()``, ``release()``)."""
-        return self._eps
 
     def start_block(self) -> np.ndarray:
         """The default start block: ``n x subspace`` complex normal from ``default_rng(seed)``, in the caller's row order."""
@@ -222,7 +203,7 @@ class RegionEigenSolver:
 
         if not isinstance(region, (Ellipse, Rectangle)):
             raise ValueError(f"region must be an Ellipse or a Rectangle, got {region!r}")
-        ell, cfg, eps = region.ellipse(), self._cfg, self._eps
+        ell, cfg = region.ellipse(), self._cfg
         if Y0 is None:
             Y0 = self.start_block()
         Y0 = np.asarray(Y0, dtype=np.complex128)
@@ -230,12 +211,7 @@ class RegionEigenSolver:
             raise ValueError(f"Y0 must have shape ({self._n}, {cfg.subspace}), got {Y0.shape}")
         started = time.time()
         z, _ = contour_nodes(ell, cfg.nodes)
-        eps.set_target(complex(z[0]))  # (a node is never real: the analysis is prepared for complex factors)
-        eps.prepare()
-        prep = eps._prepared
-        if prep["pc_code"] != 2:
-            raise NotImplementedError("The region eigensolver needs the exact LU")
-        ctx, perm = prep["ctx"], prep["perm"]
+        prep, ctx, perm = self._prepare(complex(z[0]))  # (a node is never real: the analysis is prepared for complex factors)
         keep = self._keep_factors(ctx)
         batch = bool(cfg.batch_nodes) and keep
         if cfg.batch_nodes and not batch:
@@ -333,6 +309,3 @@ class RegionEigenSolver:
             if not isinstance(r, (Ellipse, Rectangle)):
                 raise ValueError(f"region must be an Ellipse or a Rectangle, got {r!r}")
         return [self.solve(r, Y0) for r in regions]
-
-    def release(self) -> None:
-        self._eps.release()

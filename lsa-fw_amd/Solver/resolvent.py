@@ -32,10 +32,9 @@ import time
 from dataclasses import dataclass, field
 
 import numpy as np
-import scipy.sparse as sp
 
-from .eigen import _require_matching_squares, _wrap
-from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType, symmetry_defect, _onto_pattern, _permute, _SYMMETRY_TOL
+from .exact_lu import ExactLuFrontEnd, checked_side, checked_weight, checked_window, device_weight, shared_pattern  # noqa: F401  (re-exported)
+from .utils import PreconditionerType
 
 logger = logging.getLogger(__name__)
 
@@ -84,151 +83,39 @@ def _real_discount(beta) -> float:
     return float(z.real)
 
 
-def checked_window(name: str, window, Ms) -> np.ndarray:
-    """The window ``name`` as ``n`` float64 dof weights; ``ValueError`` unless it is a real array of ``n`` non-negative finite entries
-    under which ``D M D`` keeps a positive diagonal entry (some mass inside).  Pure host work."""
-    n = Ms.shape[0]
-    d = np.asarray(window)
-    if d.dtype.kind == "c":
-        raise ValueError(f"{name} has complex entries: a window is a real array of non-negative dof weights")
-    if d.dtype.kind not in "fiub":
-        raise ValueError(f"{name} must be a real array of dof weights, got dtype {d.dtype}")
-    if d.shape != (n,):
-        raise ValueError(f"{name} must have shape ({n},), got {d.shape}")
-    d = np.ascontiguousarray(d, dtype=np.float64)
-    if not np.isfinite(d).all():
-        raise ValueError(f"{name} has NaN or infinite entries")
-    if (d < 0.0).any():
-        raise ValueError(f"{name} has negative entries: a window is non-negative")
-    if not ((d * Ms.diagonal()) * d > 0.0).any():
-        raise ValueError(f"{name} leaves no mass inside: D M D has no positive diagonal entry")
-    return d
-
-
-def checked_weight(name: str, weight, n: int):
-    """The weight ``name`` as a float64 CSR matrix; ``ValueError`` unless it is real, ``n x n``, finite and symmetric (the rule ``M``
-    is held to).  Pure host work."""
-    Q = _wrap(weight).as_scipy_array()
-    if Q.shape != (n, n):
-        raise ValueError(f"{name} must have shape ({n}, {n}), got {Q.shape}")
-    if Q.dtype.kind == "c":
-        raise ValueError(f"{name} is complex: a weight is a real symmetric positive semidefinite matrix")
-    Q = sp.csr_matrix(Q, dtype=np.float64)
-    Q.sum_duplicates()  # (also sorts the indices: one entry per position, as the upload wants them)
-    if not np.isfinite(Q.data).all():
-        raise ValueError(f"{name} has NaN or infinite entries")
-    defect = symmetry_defect(Q)
-    if not defect <= _SYMMETRY_TOL:
-        raise ValueError(f"{name} must be symmetric; its relative symmetry defect is {defect:.3e}")
-    return Q
-
-
-def checked_side(side: str, window, weight, Ms):
-    """One side's weighting as given to a front end: ``None`` (``M``), ``("window", d)`` or ``("weight", Q)``; a window and a weight
-    for the same side is a ``ValueError``."""
-    if window is not None and weight is not None:
-        raise ValueError(f"{side}_window and {side}_weight are both given: one side takes a window or a weight, not both")
-    if window is not None:
-        return "window", checked_window(f"{side}_window", window, Ms)
-    if weight is not None:
-        return "weight", checked_weight(f"{side}_weight", weight, Ms.shape[0])
-    return None
-
-
-def shared_pattern(A, M):
-    """The pattern the prepared device pair ``(A, M)`` stands on, as a CSR matrix of ones: the union of both (``iEpsSolver.prepare``)."""
-    ones = lambda X: sp.csr_matrix((np.ones(X.nnz), X.indices, X.indptr), shape=X.shape)  # noqa: E731
-    union = (ones(sp.csr_matrix(A)) + ones(sp.csr_matrix(M))).tocsr()
-    union.sort_indices()
-    return union
-
-
-def device_weight(prep: dict, spec, pattern=None):
-    """The device matrix of a checked side on the prepared, permuted numbering: ``D M D`` by ``CsrMatrix.windowed`` on the prepared
-    ``M`` for a window, an upload of the permuted matrix for a weight, ``None`` for ``M`` itself.  A weight whose entries all lie on
-    ``pattern`` (:func:`shared_pattern`) is uploaded on that pattern, explicit zeros included: its products then run in the kernel form
-    and summation order of ``M``'s, and ``weight = M`` gives the bits of no weight."""
-    import lsa_hip
-
-    if spec is None:
-        return None
-    kind, what = spec
-    perm = prep["perm"]
-    if kind == "window":
-        return prep["dM"].windowed(what[perm])
-    if pattern is not None:
-        mine = sp.csr_matrix((np.ones(what.nnz), what.indices, what.indptr), shape=what.shape)
-        if (pattern + mine).nnz == pattern.nnz:
-            what = _onto_pattern(what, pattern)
-    return lsa_hip.CsrMatrix.from_scipy(prep["ctx"], _permute(what, perm))
-
-
-class ResolventSolver:
+class ResolventSolver(ExactLuFrontEnd):
     """Optimal gains of ``(A, M)`` at real frequencies (``discount``: at ``beta + i omega``), with optional forcing and response
     windows or weights; thin shell around :class:`iEpsSolver` 's preparation (union pattern,
     nested-dissection ordering, permuted numbering, upload, pattern-only LU analysis) and ``lsa_hip.ResolventBasis``."""
+
+    NAME = "Resolvent analysis"
+    NEEDS_M = "the gains are measured in the M-inner product"
+    NEEDS_LU = "both inner solves of a step run on its factors"
+    REAL_M = "Resolvent analysis needs a real M (the M-inner product); M is complex"
 
     def __init__(self, A, M, cfg: ResolventConfig | None = None, *, device: int = 0, layout: str = "single",
                  pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
                  ksp_rtol: float | None = None, block_forcings: bool = False, forcing_window=None, response_window=None,
                  forcing_weight=None, response_weight=None, discount: float = 0.0) -> None:
-        if A is None:
-            raise ValueError("Operator A is required.")
-        if M is None:
-            raise ValueError("Resolvent analysis needs M: the gains are measured in the M-inner product")
-        A, M = _wrap(A), _wrap(M)
-        _require_matching_squares(A, M)
-        Ms = M.as_scipy_array()
-        if Ms.dtype.kind == "c":
-            raise ValueError("Resolvent analysis needs a real M (the M-inner product); M is complex")
-        defect = symmetry_defect(Ms)
-        if not defect <= _SYMMETRY_TOL:
-            raise ValueError(f"Resolvent analysis needs a symmetric M; its relative symmetry defect is {defect:.3e}")
+        A, M, _, Ms = self._checked_pencil(A, M)
         # forcing and response weights: a window D (n non-negative dof weights in the caller's numbering: Q = D M D) or a real
         # symmetric positive semidefinite matrix per side; checked here, built on the device once per preparation
         self._sides = (checked_side("forcing", forcing_window, forcing_weight, Ms), checked_side("response", response_window, response_weight, Ms))
         self._discount = _real_discount(discount)
         self.last_map_stats: list[dict] = []
-        self._cfg = cfg if cfg is not None else ResolventConfig()
-        if self._cfg.num_modes < 1:
+        self._cfg = cfg = cfg if cfg is not None else ResolventConfig()
+        if cfg.num_modes < 1:
             raise ValueError("num_modes must be at least 1")
-        if self._cfg.ncv <= self._cfg.num_modes:
-            raise ValueError(f"ncv = {self._cfg.ncv} must exceed num_modes = {self._cfg.num_modes}")
-        if layout != "single":
-            raise NotImplementedError(f"Resolvent analysis runs on one GPU; the layout is '{layout}'")
-        pc_type = PreconditionerType(pc_type)
-        if pc_type not in (PreconditionerType.LU, PreconditionerType.CHOLESKY) or ilu_levels is not None:
-            raise NotImplementedError("Resolvent analysis needs the exact LU (PreconditionerType.LU): both inner solves of a step run on its "
-                                      f"factors; the preconditioner is {pc_type.name}" + ("" if ilu_levels is None else f" with ILU level {ilu_levels}"))
-        eps = iEpsSolver(A, M, device=device, seed=seed, ksp_rtol=ksp_rtol)
-        eps.set_problem_type(iEpsProblemType.GNHEP)
-        eps.set_st_type(iSTType.SINVERT)
-        eps.set_st_pc_type(pc_type)
-        eps.set_tolerances(self._cfg.atol, self._cfg.max_it)
-        eps.set_dimensions(self._cfg.num_modes, self._cfg.ncv)
-        self._eps = eps
-        self._seed = seed
+        if cfg.ncv <= cfg.num_modes:
+            raise ValueError(f"ncv = {cfg.ncv} must exceed num_modes = {cfg.num_modes}")
+        self._set_up(A, M, cfg.atol, cfg.max_it, (cfg.num_modes, cfg.ncv), device=device, layout=layout, pc_type=pc_type, ilu_levels=ilu_levels,
+                     seed=seed, ksp_rtol=ksp_rtol)
         # the forcings' adjoint solves as one block solve on the factors (same bits; off by default)
         self._block_forcings = bool(block_forcings)
 
     @property
     def config(self) -> ResolventConfig:
         return self._cfg
-
-    @property
-    def solver(self) -> iEpsSolver:
-        """The eigen path's solver object whose preparation this one shares (``prepare()``, ``release()``)."""
-        return self._eps
-
-    def _weights_on_device(self, prep: dict):
-        """(Qf, Qq) as device matrices (``None``: ``M``), built once per preparation and kept with it."""
-        built = prep.get("resolvent_weights")
-        if built is None:
-            eps = self._eps
-            needs = any(spec is not None and spec[0] == "weight" for spec in self._sides)
-            pattern = shared_pattern(eps._A.as_scipy_array(), eps._M.as_scipy_array()) if needs else None
-            built = prep["resolvent_weights"] = tuple(device_weight(prep, spec, pattern) for spec in self._sides)
-        return built
 
     def _iterate(self, shift: complex, nev: int, forcings: bool, warm=None):
         """The iteration at one complex shift: factorises ``A - shift M`` (a real shift: real factors) and runs ``nev`` modes.
@@ -238,22 +125,19 @@ class ResolventSolver:
 
         eps, cfg = self._eps, self._cfg
         started = time.time()
-        before = getattr(eps, "_prepared", None)
-        eps.set_target(shift)
-        run = eps._open(basis=False)
+        before = eps.prepared
+        run, prep = self._open_operator(shift)
         basis = None
         try:
-            prep, op = eps._prepared, run["op"]
+            op = run["op"]
             prepared_anew = prep is not before  # (the first solve, or a change between real and complex factors)
-            if prep["pc_code"] != 2 or op.stats().get("pc_fallback"):
-                raise NotImplementedError("Resolvent analysis needs the exact LU; it does not fit the device memory")
             basis = lsa_hip.ResolventBasis(prep["ctx"], op, run["ncv"])
             basis.set_row_permutation(prep["perm"])
             if self._block_forcings:
                 basis.set_block_forcings(True)
             if any(spec is not None for spec in self._sides):
-                basis.set_weights(*self._weights_on_device(prep))
-            v0 = eps._start_vector(basis.n) if warm is None else np.asarray(warm, dtype=np.complex128)[prep["perm"]]
+                basis.set_weights(*self._weights_on_device(prep, self._sides, "resolvent_weights"))
+            v0 = eps.start_vector(basis.n) if warm is None else np.asarray(warm, dtype=np.complex128)[prep["perm"]]
             out = basis.solve(nev, cfg.atol, cfg.max_it, v0=v0, seed=self._seed, max_out=nev, forcings=forcings)
             st = op.stats()
             basis_bytes = basis.basis_bytes
@@ -325,6 +209,3 @@ class ResolventSolver:
             warm = response
         self.last_map_stats = stats
         return gains.reshape(z.shape)
-
-    def release(self) -> None:
-        self._eps.release()

@@ -31,9 +31,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .eigen import _require_matching_squares, _wrap
-from .resolvent import _real_discount, checked_side, device_weight, shared_pattern
-from .utils import PreconditionerType, iEpsProblemType, iEpsSolver, iSTType, symmetry_defect, _SYMMETRY_TOL
+from .exact_lu import ExactLuFrontEnd, checked_side
+from .resolvent import _real_discount
+from .utils import PreconditionerType
 
 logger = logging.getLogger(__name__)
 
@@ -127,55 +127,34 @@ def plan_factor_sets(nodes: int, bytes_per_set: int, free_bytes: int, fraction: 
     return need
 
 
-class StochasticForcingSolver:
+class StochasticForcingSolver(ExactLuFrontEnd):
     """EOFs and stochastic optimals of a real pair ``(A, M)`` on a frequency quadrature, with optional forcing and response windows
     or weights; thin shell around :class:`iEpsSolver` 's preparation (union pattern, nested-dissection ordering, permuted numbering,
     upload, pattern-only LU analysis) and ``lsa_hip.StochasticBasis``.  The results are those of the quadrature operator;
     convergence in ``nodes`` is the caller's to check, and ``discount`` smooths the integrand."""
 
+    NAME = "Stochastic forcing"
+    NEEDS_M = "the variance is measured in the M-inner product"
+    NEEDS_LU = "every node of the quadrature is a pair of solves on its factors"
+    REAL_A = "Stochastic forcing needs a real A: the quadrature over omega >= 0 stands for the whole axis only for a real pencil"
+    REAL_M = "Stochastic forcing needs a real M (the M-inner product); M is complex"
+
     def __init__(self, A, M, cfg: StochasticConfig | None = None, *, device: int = 0, layout: str = "single",
                  pc_type: PreconditionerType = PreconditionerType.LU, ilu_levels: int | None = None, seed: int = 0,
                  ksp_rtol: float | None = None, forcing_window=None, response_window=None, forcing_weight=None, response_weight=None,
                  discount: float = 0.0, batch_forward: bool = True, batch_adjoint: bool = False) -> None:
-        if A is None:
-            raise ValueError("Operator A is required.")
-        if M is None:
-            raise ValueError("Stochastic forcing needs M: the variance is measured in the M-inner product")
-        A, M = _wrap(A), _wrap(M)
-        _require_matching_squares(A, M)
-        if A.as_scipy_array().dtype.kind == "c":
-            raise ValueError("Stochastic forcing needs a real A: the quadrature over omega >= 0 stands for the whole axis only for a real pencil")
-        Ms = M.as_scipy_array()
-        if Ms.dtype.kind == "c":
-            raise ValueError("Stochastic forcing needs a real M (the M-inner product); M is complex")
-        defect = symmetry_defect(Ms)
-        if not defect <= _SYMMETRY_TOL:
-            raise ValueError(f"Stochastic forcing needs a symmetric M; its relative symmetry defect is {defect:.3e}")
+        A, M, _, Ms = self._checked_pencil(A, M)
         self._sides = (checked_side("forcing", forcing_window, forcing_weight, Ms), checked_side("response", response_window, response_weight, Ms))
         self._discount = _real_discount(discount)
-        self._cfg = cfg if cfg is not None else StochasticConfig()
-        if self._cfg.num_modes < 1:
+        self._cfg = cfg = cfg if cfg is not None else StochasticConfig()
+        if cfg.num_modes < 1:
             raise ValueError("num_modes must be at least 1")
-        if self._cfg.ncv <= self._cfg.num_modes:
-            raise ValueError(f"ncv = {self._cfg.ncv} must exceed num_modes = {self._cfg.num_modes}")
-        if not isinstance(self._cfg.nodes, (int, np.integer)) or self._cfg.nodes < 1:
-            raise ValueError(f"nodes = {self._cfg.nodes!r} must be at least 1")
-        if layout != "single":
-            raise NotImplementedError(f"Stochastic forcing runs on one GPU; the layout is '{layout}'")
-        pc_type = PreconditionerType(pc_type)
-        if pc_type not in (PreconditionerType.LU, PreconditionerType.CHOLESKY) or ilu_levels is not None:
-            raise NotImplementedError("Stochastic forcing needs the exact LU (PreconditionerType.LU): every node of the quadrature is a pair of "
-                                      f"solves on its factors; the preconditioner is {pc_type.name}" + ("" if ilu_levels is None else f" with ILU level {ilu_levels}"))
-        eps = iEpsSolver(A, M, device=device, seed=seed, ksp_rtol=ksp_rtol)
-        eps.set_problem_type(iEpsProblemType.GNHEP)
-        eps.set_st_type(iSTType.SINVERT)
-        eps.set_st_pc_type(pc_type)
-        eps.set_tolerances(self._cfg.atol, self._cfg.max_it)
-        eps.set_dimensions(self._cfg.num_modes, self._cfg.ncv)
-        self._eps = eps
-        self._n = A.shape[0]
-        self._seed = seed
-        self._ksp_rtol = ksp_rtol if ksp_rtol is not None else float(np.clip(self._cfg.atol * 1e-2, 1e-13, 1e-8))
+        if cfg.ncv <= cfg.num_modes:
+            raise ValueError(f"ncv = {cfg.ncv} must exceed num_modes = {cfg.num_modes}")
+        if not isinstance(cfg.nodes, (int, np.integer)) or cfg.nodes < 1:
+            raise ValueError(f"nodes = {cfg.nodes!r} must be at least 1")
+        self._set_up(A, M, cfg.atol, cfg.max_it, (cfg.num_modes, cfg.ncv), device=device, layout=layout, pc_type=pc_type, ilu_levels=ilu_levels,
+                     seed=seed, ksp_rtol=ksp_rtol)
         # the forward solves of a step through the batched sweeps: same bits, and 0.79-0.92 of the default's time per step on every
         # case measured (DESIGN.md, section 6), so the front end switches it on; a new library handle has it off
         self._batch_forward = bool(batch_forward)
@@ -188,21 +167,6 @@ class StochasticForcingSolver:
     def config(self) -> StochasticConfig:
         return self._cfg
 
-    @property
-    def solver(self) -> iEpsSolver:
-        """The eigen path's solver object whose preparation this one shares (``prepare()``, ``release()``)."""
-        return self._eps
-
-    def _weights_on_device(self, prep: dict):
-        """(Qf, Qq) as device matrices (``None``: ``M``), built once per preparation and kept with it."""
-        built = prep.get("stochastic_weights")
-        if built is None:
-            eps = self._eps
-            needs = any(spec is not None and spec[0] == "weight" for spec in self._sides)
-            pattern = shared_pattern(eps._A.as_scipy_array(), eps._M.as_scipy_array()) if needs else None
-            built = prep["stochastic_weights"] = tuple(device_weight(prep, spec, pattern) for spec in self._sides)
-        return built
-
     def solve(self, band=None, *, scale: float | None = None, omegas=None, weights=None, kind: str = "eofs", discount: float | None = None) -> StochasticResult:
         """The leading variances and modes of the quadrature operator over ``band=(a, b)`` (Gauss-Legendre, ``cfg.nodes`` nodes),
         ``band=(0, inf)`` with ``scale=s`` (``omega = s tan(theta)``) or explicit ``omegas`` and ``weights``.  ``kind="eofs"``: the
@@ -214,15 +178,10 @@ class StochasticForcingSolver:
             raise ValueError(f"kind = {kind!r} must be 'eofs' or 'optimals'")
         om, w = quadrature(self._cfg.nodes, band, scale, omegas, weights)
         beta = self._discount if discount is None else _real_discount(discount)
-        cfg, eps, nev = self._cfg, self._eps, self._cfg.num_modes
+        cfg, nev = self._cfg, self._cfg.num_modes
         shifts = beta + 1j * om
         started = time.time()
-        eps.set_target(complex(beta, max(float(om.max()), 1.0)))  # (never real: the analysis is prepared for complex factors)
-        eps.prepare()
-        prep = eps._prepared
-        if prep["pc_code"] != 2:
-            raise NotImplementedError("Stochastic forcing needs the exact LU")
-        ctx, perm = prep["ctx"], prep["perm"]
+        prep, ctx, perm = self._prepare(complex(beta, max(float(om.max()), 1.0)))  # (never real: the analysis is prepared for complex factors)
         try:
             plan_factor_sets(om.size, ctx.prepared_lu_bytes(), ctx.mem_info()[0])
         except ValueError:  # (no analysis parked in the context: the library judges on the first set's)
@@ -232,7 +191,7 @@ class StochasticForcingSolver:
             basis = lsa_hip.StochasticBasis(ctx, prep["dA"], prep["dM"], shifts, w, min(cfg.ncv, self._n), ksp_rtol=self._ksp_rtol)
             basis.set_row_permutation(perm)
             if any(spec is not None for spec in self._sides):
-                basis.set_weights(*self._weights_on_device(prep))
+                basis.set_weights(*self._weights_on_device(prep, self._sides, "stochastic_weights"))
             basis.set_kind(KINDS[kind])
             if self._batch_forward:
                 basis.set_batch_forward(True)
@@ -265,6 +224,3 @@ class StochasticForcingSolver:
                  "seconds_product_adjoint": info["seconds_product_adjoint"], "seconds_dense": info["seconds_dense"], "seconds_expand": out["seconds_expand"],
                  "seconds_restart": out["seconds_restart"], "seconds_total": time.time() - started}
         return StochasticResult(out["variances"], out["modes"], kind, om, w, spectrum, out["estimates"], stats, beta)
-
-    def release(self) -> None:
-        self._eps.release()

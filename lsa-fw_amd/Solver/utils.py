@@ -1,16 +1,16 @@
-"""Drop-in for the EPS half of ``/root/reference/Solver/utils.py`` on MI355X.
+"""Drop-in for the EPS and KSP halves of the reference's ``Solver/utils.py`` on MI355X.
 
-Same names, argument meaning and error behaviour as the reference wrapper over ``SLEPc.EPS``
+Same names, argument meaning and error behaviour as the reference wrappers over ``SLEPc.EPS`` and ``PETSc.KSP``
 (``Solver/utils.py:27-328``); the arithmetic runs in ``liblsa_hip.so`` (HIP kernels) instead of SLEPc/PETSc:
 
 ============================  ======================================================================================
 reference (slepc4py)          here
 ============================  ======================================================================================
-``EPS`` Krylov-Schur          ``lsa_hip.krylov_schur`` (host logic) over ``lsa_hip.KrylovBasis`` (device basis, CGS2)
-``ST`` SINVERT / SHIFT        ``lsa_hip.ShiftInvertOperator`` (C = A - sigma M built on the device)
-``KSP`` of the ST             device GMRES (right-preconditioned, CGS2)
-``PC`` ILU / LU               device ILU(k) + sync-free SpTRSV; LU/CHOLESKY map to a higher fill level
-``BV`` / ``DS``               HIP tall-skinny kernels / LAPACK on the ncv x ncv Hessenberg
+``EPS`` Krylov-Schur          the library's own loop (``lsa_krylov_solve``) on the device basis of ``lsa_hip.KrylovBasis``
+``ST`` SINVERT/SHIFT/CAYLEY   ``lsa_hip.ShiftInvertOperator`` (``C = A - sigma M`` built on the device)
+``PC`` LU / CHOLESKY          exact nested-dissection multifrontal LU on the device (``lsa_ndlu_*``), solved directly
+``PC`` ILU, ``KSP``           device ILU(k) under right-preconditioned GMRES (also where the exact factors do not fit)
+``BV`` / ``DS``               HIP tall-skinny kernels / the library's own dense Schur algebra on the host
 ============================  ======================================================================================
 
 There is no CPU fallback: ``solve()`` raises if the HIP library or a GPU is missing.
@@ -788,6 +788,17 @@ class iEpsSolver:
             run.clear()  # (basis and operator go before the next solve builds its own)
         if left is not None:
             self._pair_left(*left)  # (after the factors are gone: the pairing's device blocks need none of the run)
+
+    # ---- the public names the analysis front ends (Solver/exact_lu.py) use: thin, nothing new -------------------------
+    operators = property(lambda self: (self._A, self._M), doc="The wrapped pair ``(A, M)``.")
+    prepared = property(lambda self: getattr(self, "_prepared", None), doc="What :meth:`prepare` left (``None`` before, and after :meth:`release`).")
+
+    def open_operator(self) -> dict:
+        """:meth:`_open` for a caller that brings its own basis: the operator alone, built and factorised; the caller clears it."""
+        return self._open(basis=False)
+
+    def start_vector(self, n: int) -> np.ndarray:
+        return self._start_vector(n)
 
     def _start_vector(self, n: int) -> np.ndarray:
         """The complex start vector of the library's Krylov-Schur loop, drawn here so that every driver begins from the same one."""

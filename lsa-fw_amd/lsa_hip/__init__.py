@@ -503,7 +503,103 @@ class Context:
         return {"allgather_calls": calls.value, "allgather_bytes_received": nbytes.value}
 
 
-class DeviceVector:
+class _Handle:
+    """An object of the library in a context ``self.ctx``: ``self.handle`` from ``lsa_<_prefix>_create`` (or a like entry), given back
+    to ``lsa_<_prefix>_destroy`` once, while the context lives.  An object whose constructor raised before the handle existed calls
+    nothing."""
+
+    _prefix = ""
+
+    def _call(self, entry: str, *args) -> None:
+        """``lsa_<_prefix>_<entry>(ctx, handle, *args)``, checked."""
+        self.ctx.check(getattr(self.ctx._lib, f"lsa_{self._prefix}_{entry}")(self.ctx.handle, self.handle, *args))
+
+    def __del__(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            getattr(self.ctx._lib, f"lsa_{self._prefix}_destroy")(self.handle)
+            self.handle = None
+
+
+def _ks_options(nev, tol, max_restarts, which=0, transform=0, sigma=0.0, antishift=0.0, target=None, seed=0) -> lsa_ks_options:
+    """The options of a library loop (``target=None``: the shift).  The Lanczos-type loops on an operator of their own leave
+    ``which``, ``transform`` and the three complex fields at zero."""
+    pair = lambda z: (_DBL * 2)(complex(z).real, complex(z).imag)  # noqa: E731
+    return lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=int(which), transform=int(transform), sigma=pair(sigma),
+                          antishift=pair(antishift), target=pair(sigma if target is None else target), seed=int(seed), keep_fraction=0.5)
+
+
+class _LanczosHandle(_Handle):
+    """A handle that runs the library's restarted Lanczos loop (``lsa_lanczos_*`` itself, or a handle that owns one and brings the
+    operator): ``n`` rows, ``ncv`` columns, scalars of ``_dtype``.  :meth:`_set_start`, :meth:`_extend` and :meth:`_basis` are
+    published (as ``set_start``, ``extend``, ``basis``) by the classes whose C API has these entries."""
+
+    _dtype = np.float64
+    _counters: tuple = ()  # the names of the four solve counters ``lsa_<_prefix>_solve`` fills, in its order (none: it has no such argument)
+    _has_perm = False
+
+    @property
+    def basis_bytes(self) -> int:
+        """Device bytes of the ``n x (ncv + 1)`` arrays of the iteration: the basis, the restart's second basis and, with a row
+        permutation, the output vectors in the caller's numbering."""
+        return np.dtype(self._dtype).itemsize * self.n * (self.ncv + 1) * (3 if self._has_perm else 2)
+
+    def set_row_permutation(self, perm: np.ndarray | None) -> None:
+        """``perm[i]`` = the caller's index of basis row ``i``: the vectors of :meth:`solve` come back in the caller's numbering."""
+        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        self._call("set_row_permutation", None if p is None else _ptr(p))
+        self._has_perm = p is not None
+
+    def _start(self, v) -> np.ndarray:
+        return _start_vector(v, self.n, self._dtype)
+
+    def _set_start(self, v: np.ndarray) -> None:
+        self._call("set_start", _ptr(self._start(v)))
+
+    def _extend(self, j0: int, j1: int, T: np.ndarray) -> int:
+        """Steps j0..j1-1 of the iteration writing ``alpha_j``, ``beta_j`` into the Fortran-ordered (ncv+1, ncv) real T; returns the
+        breakdown step or -1."""
+        assert T.flags.f_contiguous and T.dtype == np.float64
+        bd = _I32(-1)
+        self._call("extend", int(j0), int(j1), _ptr(T), T.shape[0], ctypes.byref(bd))
+        return bd.value
+
+    def _basis(self, ncols: int) -> np.ndarray:
+        """The first ``ncols`` basis vectors on the host, in the basis' own row numbering."""
+        V = np.empty((self.n, int(ncols)), dtype=self._dtype, order="F")
+        self._call("basis", int(ncols), _ptr(V))
+        return V
+
+    def _max_out(self, max_out) -> int:
+        return self.ncv if max_out is None else min(int(max_out), self.ncv)
+
+    def _solve(self, o: lsa_ks_options, v0, max_out: int, *outputs):
+        """``lsa_<_prefix>_solve`` from ``v0`` (``None``: the library's start) into ``outputs``, the arrays of ``max_out`` columns or
+        entries between ``max_out`` and the estimates in the entry's argument list (``None``: a null pointer).  Returns ``(k, tail)``:
+        the columns written, and what every result ends with -- ``estimates``, the seven fields of ``lsa_ks_result`` and the solve
+        counters under this class' names."""
+        est = np.zeros(max(max_out, 1), dtype=np.float64)
+        counts = np.zeros(4, dtype=np.int64)
+        res = lsa_ks_result()
+        v = None if v0 is None else self._start(v0)
+        self._call("solve", ctypes.byref(o), None if v is None else _ptr(v), max_out, *[None if a is None else _ptr(a) for a in outputs], _ptr(est),
+                   ctypes.byref(res), *([_ptr(counts)] if self._counters else []))
+        tail = {"estimates": est[:res.nout].copy(), "nconv": int(res.nconv), "restarts": int(res.restarts), "applies": int(res.op_applies),
+                "next_unconverged": float(res.next_unconverged), "seconds_expand": res.seconds_expand, "seconds_dense": res.seconds_dense,
+                "seconds_restart": res.seconds_restart, **{name: int(c) for name, c in zip(self._counters, counts)}}
+        return res.nout, tail
+
+
+def _start_vector(v, n: int, dtype) -> np.ndarray:
+    """A start vector as a contiguous ``dtype`` array; ``ValueError`` unless it has shape ``(n,)``."""
+    v = np.ascontiguousarray(v, dtype=dtype)
+    if v.shape != (n,):
+        raise ValueError(f"start vector must have shape ({n},)")
+    return v
+
+
+class DeviceVector(_Handle):
+    _prefix = "vec"
+
     def __init__(self, ctx: Context, n: int, dtype=np.complex128):
         self.ctx = ctx
         self.n = int(n)
@@ -532,14 +628,11 @@ class DeviceVector:
         self.ctx.check(self.ctx._lib.lsa_vec_download(self.ctx.handle, self.handle, _ptr(out)))
         return out
 
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_vec_destroy(self.handle)
-            self.handle = None
 
-
-class CsrMatrix:
+class CsrMatrix(_Handle):
     """CSR matrix resident in HBM (int32 indices, float64 or complex128 values, sorted columns)."""
+
+    _prefix = "mat"
 
     def __init__(self, ctx: Context, handle, shape, nnz: int, dtype, keep=()):
         self.ctx, self.handle, self.shape, self.nnz, self.dtype = ctx, handle, shape, int(nnz), np.dtype(dtype)
@@ -687,14 +780,11 @@ class CsrMatrix:
         self.ctx.check(self.ctx._lib.lsa_spmv_time(self.ctx.handle, self.handle, x.handle, y.handle, int(iters), ctypes.byref(ms)))
         return ms.value
 
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_mat_destroy(self.handle)
-            self.handle = None
 
-
-class Ilu:
+class Ilu(_Handle):
     """ILU(k) factors + triangular-solve schedule on the device."""
+
+    _prefix = "ilu"
 
     def __init__(self, ctx: Context, C: CsrMatrix, levels: int = 0, shift_tol: float = 0.0):
         self.ctx, self._C = ctx, C
@@ -730,11 +820,6 @@ class Ilu:
         val = np.empty(nnz, dtype=self.dtype)
         self.ctx.check(self.ctx._lib.lsa_ilu_download(self.ctx.handle, self.handle, _ptr(rp), _ptr(ci), _ptr(val)))
         return rp, ci, val
-
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_ilu_destroy(self.handle)
-            self.handle = None
 
 
 class NdAnalysis:
@@ -856,8 +941,10 @@ NDLU_MULTI_CHUNK = 256  # vector entries per column a multi-column sweep tile st
 _TRANS = {"N": 0, "T": 1, "H": 2}
 
 
-class NdLu:
+class NdLu(_Handle):
     """Nested-dissection multifrontal LU of a CSR matrix, resident on the device (``lsa_ndlu_*``)."""
+
+    _prefix = "ndlu"
 
     def __init__(self, ctx: Context, C: CsrMatrix, leaf_size: int = 0, tree: dict | None = None):
         """``tree``: ``{"first", "size", "parent"[, "owner"]}`` selects ``lsa_ndlu_create_tree`` (subtree-parallel when
@@ -1031,11 +1118,6 @@ class NdLu:
         self.ctx.check(self.ctx._lib.lsa_ndlu_inertia(self.ctx.handle, self.handle, ctypes.byref(ng), ctypes.byref(ze), ctypes.byref(ps)))
         return ng.value, ze.value, ps.value
 
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_ndlu_destroy(self.handle)
-            self.handle = None
-
 
 def gmres(ctx: Context, C: CsrMatrix, pc: Ilu | None, b: DeviceVector, x: DeviceVector, *, rtol=1e-10, restart=200, maxit=2000,
           use_x0=False):
@@ -1047,9 +1129,11 @@ def gmres(ctx: Context, C: CsrMatrix, pc: Ilu | None, b: DeviceVector, x: Device
     return its.value, rr.value
 
 
-class ShiftInvertOperator:
+class ShiftInvertOperator(_Handle):
     """``y = (A - sigma M)^-1 M x`` (mode 0, iSTType.SINVERT), ``y = M^-1 (A - sigma M) x`` (mode 1, iSTType.SHIFT) or
     ``y = (A - sigma M)^-1 (A + nu M) x`` (mode 2, iSTType.CAYLEY with antishift ``nu``)."""
+
+    _prefix = "op"
 
     def __init__(self, ctx: Context, A: CsrMatrix, M: CsrMatrix | None, sigma: complex, *, mode: int = 0, antishift: complex = 0.0,
                  ilu_levels: int = 0,
@@ -1105,15 +1189,12 @@ class ShiftInvertOperator:
         self.ctx._lib.lsa_op_stats(self.handle, ctypes.byref(st))
         return {name: getattr(st, name) for name, _ in lsa_stats._fields_}
 
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_op_destroy(self.handle)
-            self.handle = None
 
-
-class KrylovBasis:
+class KrylovBasis(_Handle):
     """Arnoldi basis in HBM + the recurrences Krylov-Schur needs.  Implements the backend protocol of
     :func:`lsa_hip.krylov_schur.krylov_schur` (``n``, ``ncv``, ``inject``, ``extend``, ``restart``, ``ritz_vectors``)."""
+
+    _prefix = "krylov"
 
     def __init__(self, ctx: Context, op: ShiftInvertOperator, ncv: int, mask: np.ndarray | None = None):
         """``mask`` (0/1 per slot) zeroes the padding slots of injected vectors in the sharded block layout."""
@@ -1129,9 +1210,7 @@ class KrylovBasis:
         self.ctx.check(self.ctx._lib.lsa_krylov_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
 
     def inject(self, j: int, v: np.ndarray) -> None:
-        v = np.ascontiguousarray(v, dtype=np.complex128)
-        if v.shape != (self.n,):
-            raise ValueError(f"start vector must have shape ({self.n},)")
+        v = _start_vector(v, self.n, np.complex128)
         if self._mask is not None:
             v = np.ascontiguousarray(v * self._mask)
         self.ctx.check(self.ctx._lib.lsa_krylov_inject(self.ctx.handle, self.handle, int(j), _ptr(v)))
@@ -1162,20 +1241,8 @@ class KrylovBasis:
                 self.imag_norms = out
         return X
 
-    @staticmethod
-    def _ks_options(nev, tol, max_restarts, which, transform, sigma, antishift, target, seed) -> lsa_ks_options:
-        target = sigma if target is None else target
-        return lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=int(which), transform=int(transform),
-                              sigma=(_DBL * 2)(complex(sigma).real, complex(sigma).imag), antishift=(_DBL * 2)(complex(antishift).real, complex(antishift).imag),
-                              target=(_DBL * 2)(complex(target).real, complex(target).imag), seed=int(seed), keep_fraction=0.5)
-
     def _ks_start(self, v0):
-        if v0 is None:
-            return None
-        v = np.ascontiguousarray(v0, dtype=np.complex128)
-        if v.shape != (self.n,):
-            raise ValueError(f"start vector must have shape ({self.n},)")
-        return v
+        return None if v0 is None else _start_vector(v0, self.n, np.complex128)
 
     def _ks_collect(self, res: lsa_ks_result, theta, lam, est, X, max_out):
         """What a library solve left in its output arrays, as a :class:`lsa_hip.krylov_schur.KrylovSchurResult` plus ``lam``."""
@@ -1200,7 +1267,7 @@ class KrylovBasis:
         matrix is the library's own).  ``which``: EPSWhich code (``iEpsWhich.value``); ``transform``: 0 shift-invert,
         1 shift, 2 Cayley.  Returns a :class:`lsa_hip.krylov_schur.KrylovSchurResult` plus the eigenvalues ``lam``."""
         max_out = self.ncv if max_out is None else int(max_out)
-        o = self._ks_options(nev, tol, max_restarts, which, transform, sigma, antishift, target, seed)
+        o = _ks_options(nev, tol, max_restarts, which, transform, sigma, antishift, target, seed)
         theta = np.zeros(max(max_out, 1), dtype=np.complex128)
         lam = np.zeros(max(max_out, 1), dtype=np.complex128)
         est = np.zeros(max(max_out, 1), dtype=np.float64)
@@ -1232,8 +1299,8 @@ class KrylovBasis:
             raise ValueError("solve_batch: bases with a mask (projected operators, sharded layout) are solved one by one")
         ctx = bases[0].ctx if J else ctx  # (``ctx``: only needed for an empty list, whose refusal is the library's too)
         max_out = (bases[0].ncv if J else 0) if max_out is None else int(max_out)
-        opts = [KrylovBasis._ks_options(nev, tol, max_restarts, which, transform, per(sigmas, z), per(antishift, z),
-                                        None if targets is None else per(targets, z), seed) for z in range(J)]
+        opts = [_ks_options(nev, tol, max_restarts, which, transform, per(sigmas, z), per(antishift, z), None if targets is None else per(targets, z), seed)
+                for z in range(J)]
         vs = [None if v0s is None else bases[z]._ks_start(v0s if isinstance(v0s, np.ndarray) and v0s.ndim == 1 else v0s[z]) for z in range(J)]
         theta = [np.zeros(max(max_out, 1), dtype=np.complex128) for _ in range(J)]
         lam = [np.zeros(max(max_out, 1), dtype=np.complex128) for _ in range(J)]
@@ -1266,15 +1333,13 @@ class KrylovBasis:
                     "solo_steps": [int(info.solo_steps[z]) for z in range(J)]}
         return out, counters
 
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_krylov_destroy(self.handle)
-            self.handle = None
 
-
-class LanczosBasis:
+class LanczosBasis(_LanczosHandle):
     """Real ``M``-orthonormal Lanczos basis in HBM for a symmetric-definite pencil (``lsa_lanczos_*``): the symmetric counterpart of
     :class:`KrylovBasis`.  ``op`` must be a shift-invert operator with real exact factors (``pc_type=2``, real shift)."""
+
+    _prefix = "lanczos"
+    set_start, extend, basis = _LanczosHandle._set_start, _LanczosHandle._extend, _LanczosHandle._basis
 
     def __init__(self, ctx: Context, op: ShiftInvertOperator, ncv: int):
         self.ctx, self._op = ctx, op
@@ -1282,39 +1347,6 @@ class LanczosBasis:
         h = ctypes.c_void_p()
         ctx.check(ctx._lib.lsa_lanczos_create(ctx.handle, op.handle, self.ncv, ctypes.byref(h)))
         self.handle = h
-        self._has_perm = False
-
-    @property
-    def basis_bytes(self) -> int:
-        """Device bytes of the ``n x (ncv + 1)`` arrays the handle owns: the basis, the restart's second basis and, with a row
-        permutation, the Ritz vectors in the caller's numbering."""
-        return 8 * self.n * (self.ncv + 1) * (3 if self._has_perm else 2)
-
-    def set_row_permutation(self, perm: np.ndarray | None) -> None:
-        """``perm[i]`` = the caller's index of basis row ``i``: the vectors of :meth:`solve` come back in the caller's numbering."""
-        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
-        self.ctx.check(self.ctx._lib.lsa_lanczos_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
-        self._has_perm = p is not None
-
-    def set_start(self, v: np.ndarray) -> None:
-        v = np.ascontiguousarray(v, dtype=np.float64)
-        if v.shape != (self.n,):
-            raise ValueError(f"start vector must have shape ({self.n},)")
-        self.ctx.check(self.ctx._lib.lsa_lanczos_set_start(self.ctx.handle, self.handle, _ptr(v)))
-
-    def extend(self, j0: int, j1: int, T: np.ndarray) -> int:
-        """Lanczos steps j0..j1-1 writing ``alpha_j``, ``beta_j`` into the Fortran-ordered (ncv+1, ncv) real T; returns the
-        breakdown step or -1."""
-        assert T.flags.f_contiguous and T.dtype == np.float64
-        bd = _I32(-1)
-        self.ctx.check(self.ctx._lib.lsa_lanczos_extend(self.ctx.handle, self.handle, int(j0), int(j1), _ptr(T), T.shape[0], ctypes.byref(bd)))
-        return bd.value
-
-    def basis(self, ncols: int) -> np.ndarray:
-        """The first ``ncols`` basis vectors on the host, in the basis' own row numbering."""
-        V = np.empty((self.n, int(ncols)), dtype=np.float64, order="F")
-        self.ctx.check(self.ctx._lib.lsa_lanczos_basis(self.ctx.handle, self.handle, int(ncols), _ptr(V)))
-        return V
 
     def solve(self, nev: int, tol: float, max_restarts: int, which: int, sigma: float, *, target: float | None = None,
               v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None, vectors: bool = True):
@@ -1322,42 +1354,27 @@ class LanczosBasis:
         :class:`lsa_hip.krylov_schur.KrylovSchurResult` with real ``theta``, real ``M``-orthonormal ``vectors`` and ``lam``."""
         from .krylov_schur import KrylovSchurResult
 
-        max_out = self.ncv if max_out is None else min(int(max_out), self.ncv)
-        target = sigma if target is None else target
-        o = lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=int(which), transform=0,
-                           sigma=(_DBL * 2)(float(sigma), 0.0), antishift=(_DBL * 2)(0.0, 0.0), target=(_DBL * 2)(float(target), 0.0),
-                           seed=int(seed), keep_fraction=0.5)
+        max_out = self._max_out(max_out)
+        o = _ks_options(nev, tol, max_restarts, which, sigma=float(sigma), target=None if target is None else float(target), seed=seed)
         theta = np.zeros(max(max_out, 1), dtype=np.float64)
         lam = np.zeros(max(max_out, 1), dtype=np.float64)
-        est = np.zeros(max(max_out, 1), dtype=np.float64)
         X = np.empty((self.n, max_out), dtype=np.float64, order="F") if vectors else None
-        res = lsa_ks_result()
-        v = None
-        if v0 is not None:
-            v = np.ascontiguousarray(v0, dtype=np.float64)
-            if v.shape != (self.n,):
-                raise ValueError(f"start vector must have shape ({self.n},)")
-        self.ctx.check(self.ctx._lib.lsa_lanczos_solve(self.ctx.handle, self.handle, ctypes.byref(o), None if v is None else _ptr(v), max_out,
-                                                       _ptr(theta), _ptr(lam), None if X is None else _ptr(X), _ptr(est), ctypes.byref(res)))
-        k = res.nout
+        k, t = self._solve(o, v0, max_out, theta, lam, X)
         vec = np.zeros((self.n, 0), dtype=np.float64) if X is None else (X[:, :k] if k == max_out else np.asfortranarray(X[:, :k]))
-        r = KrylovSchurResult(theta[:k].copy(), vec, est[:k].copy(), int(res.nconv), int(res.restarts), int(res.op_applies),
-                              [{"nconv": int(res.nconv), "next_unconverged": float(res.next_unconverged), "seconds_expand": res.seconds_expand,
-                                "seconds_dense": res.seconds_dense, "seconds_restart": res.seconds_restart}])
+        r = KrylovSchurResult(theta[:k].copy(), vec, t["estimates"], t["nconv"], t["restarts"], t["applies"],
+                              [{key: t[key] for key in ("nconv", "next_unconverged", "seconds_expand", "seconds_dense", "seconds_restart")}])
         r.lam = lam[:k].copy()
         return r
 
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_lanczos_destroy(self.handle)
-            self.handle = None
 
-
-class ResolventBasis:
+class ResolventBasis(_LanczosHandle):
     """Complex ``M``-orthonormal Lanczos basis in HBM for the resolvent's ``W = C^-1 M C^-H M``, ``C = A - i omega M``
     (``lsa_resolvent_*``): the counterpart of :class:`LanczosBasis` for optimal gains.  ``op`` must be a shift-invert operator
     (mode 0) at ``sigma = 1j * omega`` (or ``beta + 1j * omega``: the discounted resolvent) with exact factors (``pc_type=2``) and a
     real ``M``.  :meth:`set_weights` puts a forcing and a response weight where ``M`` stands: ``W = C^-1 Qf C^-H Qq``."""
+
+    _prefix, _dtype, _counters = "resolvent", np.complex128, ("adjoint_solves", "forward_solves", "refined_adjoint", "refined_forward")
+    set_start, extend, basis = _LanczosHandle._set_start, _LanczosHandle._extend, _LanczosHandle._basis
 
     def __init__(self, ctx: Context, op: ShiftInvertOperator, ncv: int):
         self.ctx, self._op = ctx, op
@@ -1366,94 +1383,40 @@ class ResolventBasis:
         h = ctypes.c_void_p()
         ctx.check(ctx._lib.lsa_resolvent_create(ctx.handle, op.handle, self.ncv, ctypes.byref(h)))
         self.handle = h
-        self._has_perm = False
-
-    @property
-    def basis_bytes(self) -> int:
-        """Device bytes of the ``n x (ncv + 1)`` arrays the handle owns: the basis, the restart's second basis and, with a row
-        permutation, the output vectors in the caller's numbering."""
-        return 16 * self.n * (self.ncv + 1) * (3 if self._has_perm else 2)
-
-    def set_row_permutation(self, perm: np.ndarray | None) -> None:
-        """``perm[i]`` = the caller's index of basis row ``i``: the vectors of :meth:`solve` come back in the caller's numbering."""
-        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
-        self.ctx.check(self.ctx._lib.lsa_resolvent_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
-        self._has_perm = p is not None
 
     def set_block_forcings(self, on: bool) -> None:
         """``True``: the forcings of :meth:`solve` take their adjoint solves as one block solve on the factors
         (``lsa_resolvent_set_block_forcings``); the results are those of the default, bit for bit."""
-        self.ctx.check(self.ctx._lib.lsa_resolvent_set_block_forcings(self.ctx.handle, self.handle, int(bool(on))))
+        self._call("set_block_forcings", int(bool(on)))
 
     def set_weights(self, forcing: "CsrMatrix | None" = None, response: "CsrMatrix | None" = None) -> None:
         """Forcing weight ``Q_f`` and response weight ``Q_q`` in place of ``M`` (``None``: ``M``; ``lsa_resolvent_set_weights``): real
         symmetric positive semidefinite ``n x n`` device matrices, which this object keeps alive.  A start vector (or :meth:`solve`)
         must follow."""
-        self.ctx.check(self.ctx._lib.lsa_resolvent_set_weights(self.ctx.handle, self.handle, None if forcing is None else forcing.handle,
-                                                               None if response is None else response.handle))
+        self._call("set_weights", None if forcing is None else forcing.handle, None if response is None else response.handle)
         self._weights = (forcing, response)
-
-    def _start(self, v) -> np.ndarray:
-        v = np.ascontiguousarray(v, dtype=np.complex128)
-        if v.shape != (self.n,):
-            raise ValueError(f"start vector must have shape ({self.n},)")
-        return v
-
-    def set_start(self, v: np.ndarray) -> None:
-        v = self._start(v)
-        self.ctx.check(self.ctx._lib.lsa_resolvent_set_start(self.ctx.handle, self.handle, _ptr(v)))
-
-    def extend(self, j0: int, j1: int, T: np.ndarray) -> int:
-        """Steps j0..j1-1 on ``W`` writing ``alpha_j``, ``beta_j`` into the Fortran-ordered (ncv+1, ncv) real T; returns the
-        breakdown step or -1."""
-        assert T.flags.f_contiguous and T.dtype == np.float64
-        bd = _I32(-1)
-        self.ctx.check(self.ctx._lib.lsa_resolvent_extend(self.ctx.handle, self.handle, int(j0), int(j1), _ptr(T), T.shape[0], ctypes.byref(bd)))
-        return bd.value
-
-    def basis(self, ncols: int) -> np.ndarray:
-        """The first ``ncols`` basis vectors on the host, in the basis' own row numbering."""
-        V = np.empty((self.n, int(ncols)), dtype=np.complex128, order="F")
-        self.ctx.check(self.ctx._lib.lsa_resolvent_basis(self.ctx.handle, self.handle, int(ncols), _ptr(V)))
-        return V
 
     def solve(self, nev: int, tol: float, max_restarts: int, *, v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None,
               forcings: bool = True) -> dict:
         """The whole iteration inside the library (``lsa_resolvent_solve``).  Returns a dict: ``theta`` (``sigma_j^2``), ``gains``
         (descending), ``responses`` and ``forcings`` (n x k complex, ``M``-orthonormal; ``forcings`` is ``None`` when not asked for),
         ``estimates``, ``nconv``, ``restarts``, ``applies``, the loop's phase times and the handle's solve counts so far."""
-        max_out = self.ncv if max_out is None else min(int(max_out), self.ncv)
-        o = lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=0, transform=0, sigma=(_DBL * 2)(0.0, 0.0),
-                           antishift=(_DBL * 2)(0.0, 0.0), target=(_DBL * 2)(0.0, 0.0), seed=int(seed), keep_fraction=0.5)
+        max_out = self._max_out(max_out)
         theta = np.zeros(max(max_out, 1), dtype=np.float64)
         gains = np.zeros(max(max_out, 1), dtype=np.float64)
-        est = np.zeros(max(max_out, 1), dtype=np.float64)
         Q = np.empty((self.n, max_out), dtype=np.complex128, order="F")
         F = np.empty((self.n, max_out), dtype=np.complex128, order="F") if forcings else None
-        counts = np.zeros(4, dtype=np.int64)
-        res = lsa_ks_result()
-        v = None if v0 is None else self._start(v0)
-        self.ctx.check(self.ctx._lib.lsa_resolvent_solve(self.ctx.handle, self.handle, ctypes.byref(o), None if v is None else _ptr(v), max_out,
-                                                         _ptr(theta), _ptr(gains), _ptr(Q), None if F is None else _ptr(F), _ptr(est),
-                                                         ctypes.byref(res), _ptr(counts)))
-        k = res.nout
+        k, tail = self._solve(_ks_options(nev, tol, max_restarts, seed=seed), v0, max_out, theta, gains, Q, F)
         return {"theta": theta[:k].copy(), "gains": gains[:k].copy(), "responses": np.asfortranarray(Q[:, :k]),
-                "forcings": None if F is None else np.asfortranarray(F[:, :k]), "estimates": est[:k].copy(), "nconv": int(res.nconv),
-                "restarts": int(res.restarts), "applies": int(res.op_applies), "next_unconverged": float(res.next_unconverged),
-                "seconds_expand": res.seconds_expand, "seconds_dense": res.seconds_dense, "seconds_restart": res.seconds_restart,
-                "adjoint_solves": int(counts[0]), "forward_solves": int(counts[1]), "refined_adjoint": int(counts[2]),
-                "refined_forward": int(counts[3])}
-
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_resolvent_destroy(self.handle)
-            self.handle = None
+                "forcings": None if F is None else np.asfortranarray(F[:, :k]), **tail}
 
 
-class ContourSolver:
+class ContourSolver(_Handle):
     """Contour-integral subspace iteration for the eigenvalues of ``(A, M)`` inside an ellipse (``lsa_contour_*``): ``nodes``
     factorisations of ``A - z_k M`` on one LU analysis, kept alive (``keep_factors=True``) or refactorised node by node in every
     iteration; both return the same bytes.  ``A`` and ``M`` share one pattern, ``M`` is real."""
+
+    _prefix = "contour"
 
     def __init__(self, ctx: Context, A: CsrMatrix, M: CsrMatrix, nodes: int, centre: complex, rx: float, ry: float, subspace: int, *,
                  keep_factors: bool = True, ksp_rtol: float = 1e-12, batch_nodes: bool = False):
@@ -1526,11 +1489,6 @@ class ContourSolver:
         d["solver"] = {name: getattr(st.solver, name) for name, _ in lsa_stats._fields_}
         return d
 
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_contour_destroy(self.handle)
-            self.handle = None
-
 
 def shifted_spmm(ctx: Context, A: CsrMatrix, M: CsrMatrix, shifts, X: np.ndarray) -> np.ndarray:
     """``Y[:, k] = (A - shifts[k] M) X[:, k]`` for all columns in one launch (``lsa_shifted_spmm``): ``A``, ``M`` real on one
@@ -1546,11 +1504,13 @@ def shifted_spmm(ctx: Context, A: CsrMatrix, M: CsrMatrix, shifts, X: np.ndarray
     return dY.numpy().reshape((n, z.size), order="F")
 
 
-class StochasticBasis:
+class StochasticBasis(_LanczosHandle):
     """Real Lanczos basis in HBM for the stochastic-forcing operator ``S = (1 / pi) sum_k w_k Re(C_k^-1 Qf C_k^-H Qq)``,
     ``C_k = A - z_k M`` (``lsa_stochastic_*``): ``len(shifts)`` factorisations kept alive on one LU analysis behind every step.
     ``A`` and ``M`` are real and share one pattern.  ``kind`` 0: EOFs (``Qq`` the inner product), 1: stochastic optimals (the two
     solves and the two weights swapped, ``Qf`` the inner product).  The results are those of the quadrature given."""
+
+    _prefix, _counters = "stochastic", ("adjoint_solves", "forward_solves", "refined_adjoint", "refined_forward")
 
     def __init__(self, ctx: Context, A: CsrMatrix, M: CsrMatrix, shifts, weights, ncv: int, *, ksp_rtol: float = 1e-12):
         self.ctx, self._keep = ctx, (A, M)  # (the handle borrows both matrices)
@@ -1565,33 +1525,27 @@ class StochasticBasis:
                                                  self.ncv, float(ksp_rtol), ctypes.byref(h)))
         self.handle = h
 
-    def set_row_permutation(self, perm: np.ndarray | None) -> None:
-        """``perm[i]`` = the caller's index of basis row ``i``: the modes of :meth:`solve` come back in the caller's numbering."""
-        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
-        self.ctx.check(self.ctx._lib.lsa_stochastic_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
-
     def set_weights(self, forcing: "CsrMatrix | None" = None, response: "CsrMatrix | None" = None) -> None:
         """Forcing weight ``Q_f`` and response weight ``Q_q`` in place of ``M`` (``None``: ``M``; ``lsa_stochastic_set_weights``): real
         symmetric positive semidefinite ``n x n`` device matrices, which this object keeps alive."""
-        self.ctx.check(self.ctx._lib.lsa_stochastic_set_weights(self.ctx.handle, self.handle, None if forcing is None else forcing.handle,
-                                                                None if response is None else response.handle))
+        self._call("set_weights", None if forcing is None else forcing.handle, None if response is None else response.handle)
         self._weights = (forcing, response)
 
     def set_kind(self, kind: int) -> None:
-        self.ctx.check(self.ctx._lib.lsa_stochastic_set_kind(self.ctx.handle, self.handle, int(kind)))
+        self._call("set_kind", int(kind))
 
     def set_batch_forward(self, on: bool) -> None:
         """``True``: the forward solves of a step run through the batched sweeps of ``lsa_ndlu_solve_batch``; same bits."""
-        self.ctx.check(self.ctx._lib.lsa_stochastic_set_batch_forward(self.ctx.handle, self.handle, int(bool(on))))
+        self._call("set_batch_forward", int(bool(on)))
 
     def set_batch_adjoint(self, on: bool) -> None:
         """``True``: the adjoint solves of a step run through the batched transposed sweeps of ``lsa_ndlu_solve_batch_adjoint`` and
         their check products through ``lsa_spmv_transpose_batch``; same bits."""
-        self.ctx.check(self.ctx._lib.lsa_stochastic_set_batch_adjoint(self.ctx.handle, self.handle, int(bool(on))))
+        self._call("set_batch_adjoint", int(bool(on)))
 
     def set_refinement(self, on: bool) -> None:
         """``True``: every solve carries the refinement step from the start (for tests)."""
-        self.ctx.check(self.ctx._lib.lsa_stochastic_set_refinement(self.ctx.handle, self.handle, int(bool(on))))
+        self._call("set_refinement", int(bool(on)))
 
     def apply(self, v: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
         """``(S v, node terms)`` for a host vector in the matrices' own row numbering (``lsa_stochastic_apply``); the node terms sum
@@ -1600,34 +1554,18 @@ class StochasticBasis:
         if v.shape != (self.n,):
             raise ValueError(f"the vector must have shape ({self.n},)")
         y, terms = np.empty(self.n), np.zeros(self.nodes)
-        self.ctx.check(self.ctx._lib.lsa_stochastic_apply(self.ctx.handle, self.handle, _ptr(v), _ptr(y), _ptr(terms)))
+        self._call("apply", _ptr(v), _ptr(y), _ptr(terms))
         return y, terms
 
     def solve(self, nev: int, tol: float, max_restarts: int, *, v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None) -> dict:
         """The whole iteration inside the library (``lsa_stochastic_solve``).  Returns a dict: ``variances`` (descending), ``modes``
         (n x k real, orthonormal in the kind's weight), ``estimates``, ``nconv``, ``restarts``, ``applies``, the loop's phase times
         and the handle's solve counts so far."""
-        max_out = self.ncv if max_out is None else min(int(max_out), self.ncv)
-        o = lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=0, transform=0, sigma=(_DBL * 2)(0.0, 0.0),
-                           antishift=(_DBL * 2)(0.0, 0.0), target=(_DBL * 2)(0.0, 0.0), seed=int(seed), keep_fraction=0.5)
+        max_out = self._max_out(max_out)
         theta = np.zeros(max(max_out, 1), dtype=np.float64)
-        est = np.zeros(max(max_out, 1), dtype=np.float64)
         X = np.empty((self.n, max_out), dtype=np.float64, order="F")
-        counts = np.zeros(4, dtype=np.int64)
-        res = lsa_ks_result()
-        v = None
-        if v0 is not None:
-            v = np.ascontiguousarray(v0, dtype=np.float64)
-            if v.shape != (self.n,):
-                raise ValueError(f"start vector must have shape ({self.n},)")
-        self.ctx.check(self.ctx._lib.lsa_stochastic_solve(self.ctx.handle, self.handle, ctypes.byref(o), None if v is None else _ptr(v), max_out,
-                                                          _ptr(theta), _ptr(X), _ptr(est), ctypes.byref(res), _ptr(counts)))
-        k = res.nout
-        return {"variances": theta[:k].copy(), "modes": np.asfortranarray(X[:, :k]), "estimates": est[:k].copy(), "nconv": int(res.nconv),
-                "restarts": int(res.restarts), "applies": int(res.op_applies), "next_unconverged": float(res.next_unconverged),
-                "seconds_expand": res.seconds_expand, "seconds_dense": res.seconds_dense, "seconds_restart": res.seconds_restart,
-                "adjoint_solves": int(counts[0]), "forward_solves": int(counts[1]), "refined_adjoint": int(counts[2]),
-                "refined_forward": int(counts[3])}
+        k, tail = self._solve(_ks_options(nev, tol, max_restarts, seed=seed), v0, max_out, theta, X)
+        return {"variances": theta[:k].copy(), "modes": np.asfortranarray(X[:, :k]), **tail}
 
     def info(self) -> dict:
         """``lsa_stochastic_info``: nodes, kind, device bytes, the phase times, and the inner solves' counters under ``"solver"``."""
@@ -1637,13 +1575,8 @@ class StochasticBasis:
         d["solver"] = {name: getattr(st.solver, name) for name, _ in lsa_stats._fields_}
         return d
 
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_stochastic_destroy(self.handle)
-            self.handle = None
 
-
-class GrowthBasis:
+class GrowthBasis(_LanczosHandle):
     """Real ``M``-orthonormal Lanczos basis in HBM for the transient-growth operator ``W = Phi+ Phi``, ``Phi = (-sigma C^-1 M)^N``,
     ``C = A - sigma M``, ``sigma = 1 / dt`` (``lsa_growth_*``): a march of ``2 N`` solves on one factorisation behind every step.
     ``op`` must be a shift-invert operator (mode 0) at the real positive ``sigma`` with real exact factors (``pc_type=2``) and a real
@@ -1652,6 +1585,8 @@ class GrowthBasis:
     second order in ``dt``, ``sigma = 1 / (gamma dt)``, ``Phi = (S (a S + b I))^N`` with ``S = -sigma C^-1 M``, ``4 N`` solves a step."""
 
     SCHEMES = {"euler": 0, "sdirk2": 1}
+    _prefix, _counters = "growth", ("forward_solves", "transposed_solves", "refined_forward", "refined_transposed")
+    set_start, extend, basis = _LanczosHandle._set_start, _LanczosHandle._extend, _LanczosHandle._basis
 
     def __init__(self, ctx: Context, op: ShiftInvertOperator, ncv: int, nsteps: int, keep: np.ndarray | None = None, scheme: str = "euler"):
         if scheme not in self.SCHEMES:
@@ -1668,95 +1603,41 @@ class GrowthBasis:
         h = ctypes.c_void_p()
         ctx.check(ctx._lib.lsa_growth_create(ctx.handle, op.handle, self.ncv, self.nsteps, None if k is None else _ptr(k), ctypes.byref(h)))
         self.handle = h
-        self._has_perm = False
         if scheme != "euler":
             self.set_scheme_code(self.SCHEMES[scheme])
 
     def set_scheme_code(self, code: int) -> None:
         """``lsa_growth_set_scheme`` with the bare code (0: implicit Euler, 1: SDIRK2); any other is the library's ``ValueError``."""
-        self.ctx.check(self.ctx._lib.lsa_growth_set_scheme(self.ctx.handle, self.handle, int(code)))
+        self._call("set_scheme", int(code))
         self.scheme = {v: k for k, v in self.SCHEMES.items()}[int(code)]
-
-    @property
-    def basis_bytes(self) -> int:
-        """Device bytes of the ``n x (ncv + 1)`` arrays the handle owns: the basis, the restart's second basis and, with a row
-        permutation, the output vectors in the caller's numbering."""
-        return 8 * self.n * (self.ncv + 1) * (3 if self._has_perm else 2)
-
-    def set_row_permutation(self, perm: np.ndarray | None) -> None:
-        """``perm[i]`` = the caller's index of basis row ``i``: the vectors of :meth:`solve` come back in the caller's numbering."""
-        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
-        self.ctx.check(self.ctx._lib.lsa_growth_set_row_permutation(self.ctx.handle, self.handle, None if p is None else _ptr(p)))
-        self._has_perm = p is not None
 
     def set_response_weight(self, Q: "CsrMatrix | None") -> None:
         """The response weight ``Q`` in place of ``M`` at the horizon (``None``: ``M``; ``lsa_growth_set_response_weight``): the gains
         become ``max ||q(T)||_Q^2 / ||q(0)||_M^2``.  A real symmetric positive semidefinite ``n x n`` device matrix, kept alive here."""
-        self.ctx.check(self.ctx._lib.lsa_growth_set_response_weight(self.ctx.handle, self.handle, None if Q is None else Q.handle))
+        self._call("set_response_weight", None if Q is None else Q.handle)
         self._weight = Q
 
     def set_steps(self, nsteps: int) -> None:
         """Another horizon of ``nsteps`` steps on the same handle and factors."""
-        self.ctx.check(self.ctx._lib.lsa_growth_set_steps(self.ctx.handle, self.handle, int(nsteps)))
+        self._call("set_steps", int(nsteps))
         self.nsteps = int(nsteps)
-
-    def _start(self, v) -> np.ndarray:
-        v = np.ascontiguousarray(v, dtype=np.float64)
-        if v.shape != (self.n,):
-            raise ValueError(f"start vector must have shape ({self.n},)")
-        return v
-
-    def set_start(self, v: np.ndarray) -> None:
-        v = self._start(v)
-        self.ctx.check(self.ctx._lib.lsa_growth_set_start(self.ctx.handle, self.handle, _ptr(v)))
-
-    def extend(self, j0: int, j1: int, T: np.ndarray) -> int:
-        """Steps j0..j1-1 on ``W`` writing ``alpha_j``, ``beta_j`` into the Fortran-ordered (ncv+1, ncv) real T; returns the
-        breakdown step or -1."""
-        assert T.flags.f_contiguous and T.dtype == np.float64
-        bd = _I32(-1)
-        self.ctx.check(self.ctx._lib.lsa_growth_extend(self.ctx.handle, self.handle, int(j0), int(j1), _ptr(T), T.shape[0], ctypes.byref(bd)))
-        return bd.value
-
-    def basis(self, ncols: int) -> np.ndarray:
-        """The first ``ncols`` basis vectors on the host, in the basis' own row numbering."""
-        V = np.empty((self.n, int(ncols)), dtype=np.float64, order="F")
-        self.ctx.check(self.ctx._lib.lsa_growth_basis(self.ctx.handle, self.handle, int(ncols), _ptr(V)))
-        return V
 
     def solve(self, nev: int, tol: float, max_restarts: int, *, v0: np.ndarray | None = None, seed: int = 0, max_out: int | None = None) -> dict:
         """The whole iteration inside the library (``lsa_growth_solve``).  Returns a dict: ``gains`` (descending), ``initial``
         (n x k, ``M``-orthonormal), ``responses`` (n x k, ``Phi q0``), ``energy`` (k x (nsteps + 1), the ``M``-energy),
         ``response_energy`` (k, the energy at ``T`` in the response weight), ``estimates``, ``nconv``,
         ``restarts``, ``applies``, the loop's phase times and the handle's solve counts so far."""
-        max_out = self.ncv if max_out is None else min(int(max_out), self.ncv)
-        o = lsa_ks_options(nev=int(nev), max_restarts=int(max_restarts), tol=float(tol), which=0, transform=0, sigma=(_DBL * 2)(0.0, 0.0),
-                           antishift=(_DBL * 2)(0.0, 0.0), target=(_DBL * 2)(0.0, 0.0), seed=int(seed), keep_fraction=0.5)
+        max_out = self._max_out(max_out)
         theta = np.zeros(max(max_out, 1), dtype=np.float64)
         gains = np.zeros(max(max_out, 1), dtype=np.float64)
-        est = np.zeros(max(max_out, 1), dtype=np.float64)
         Q0 = np.zeros((self.n, max_out), dtype=np.float64, order="F")
         QT = np.zeros((self.n, max_out), dtype=np.float64, order="F")
         energy = np.zeros((max(max_out, 1), self.nsteps + 1), dtype=np.float64)
-        counts = np.zeros(4, dtype=np.int64)
-        res = lsa_ks_result()
-        v = None if v0 is None else self._start(v0)
-        self.ctx.check(self.ctx._lib.lsa_growth_solve(self.ctx.handle, self.handle, ctypes.byref(o), None if v is None else _ptr(v), max_out,
-                                                      _ptr(theta), _ptr(gains), _ptr(Q0), _ptr(QT), _ptr(energy), _ptr(est), ctypes.byref(res),
-                                                      _ptr(counts)))
-        k = res.nout
+        k, tail = self._solve(_ks_options(nev, tol, max_restarts, seed=seed), v0, max_out, theta, gains, Q0, QT, energy)
         renergy = np.zeros(max(k, 1), dtype=np.float64)
-        self.ctx.check(self.ctx._lib.lsa_growth_response_energy(self.ctx.handle, self.handle, k, _ptr(renergy)))
+        self._call("response_energy", k, _ptr(renergy))
         return {"gains": gains[:k].copy(), "initial": np.asfortranarray(Q0[:, :k]), "responses": np.asfortranarray(QT[:, :k]),
-                "energy": energy[:k].copy(), "response_energy": renergy[:k].copy(), "estimates": est[:k].copy(), "nconv": int(res.nconv), "restarts": int(res.restarts),
-                "applies": int(res.op_applies), "next_unconverged": float(res.next_unconverged), "seconds_expand": res.seconds_expand,
-                "seconds_dense": res.seconds_dense, "seconds_restart": res.seconds_restart, "forward_solves": int(counts[0]),
-                "transposed_solves": int(counts[1]), "refined_forward": int(counts[2]), "refined_transposed": int(counts[3])}
-
-    def __del__(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx._lib.lsa_growth_destroy(self.handle)
-            self.handle = None
+                "energy": energy[:k].copy(), "response_energy": renergy[:k].copy(), **tail}
 
 
 def dense_syev(A: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
