@@ -785,6 +785,12 @@ int lsa_contour_left_info(const lsa_contour *h, lsa_contour_left_stats *out);
  * entries of a row are strided over 8 lanes, each adding its own in order, then a fixed tree: the same bits on every call.
  * The check product of the forward solves of a stochastic-forcing step; exported for tests. */
 int lsa_shifted_spmm(lsa_ctx *ctx, const lsa_mat *A, const lsa_mat *M, int32_t nodes, const double *shifts, const lsa_vec *X, lsa_vec *Y);
+/* Y[:, c] = (A - z_c M)^H X[:, c] for c < nodes in ONE launch, on the transposed index of the shared pattern (built on first use, as
+ * for lsa_spmv_transpose); arguments, checks and messages as lsa_shifted_spmm.  Every non-zero's row index, source position and two
+ * real values are read once for up to 16 columns; the entries of an output row are strided over 8 lanes, each adding its own in
+ * order, then a fixed tree: the same bits on every call, not those of lsa_spmv_transpose (another summation order).  The check
+ * product of the adjoint block solves of lsa_stochastic_trace; exported for tests. */
+int lsa_shifted_spmm_transpose(lsa_ctx *ctx, const lsa_mat *A, const lsa_mat *M, int32_t nodes, const double *shifts, const lsa_vec *X, lsa_vec *Y);
 typedef struct lsa_stochastic lsa_stochastic;
 typedef struct {
     int32_t nodes;
@@ -852,6 +858,48 @@ int lsa_stochastic_apply(lsa_ctx *ctx, lsa_stochastic *h, const double *host_v, 
 int lsa_stochastic_solve(lsa_ctx *ctx, lsa_stochastic *h, const lsa_ks_options *opts, const double *v0, int32_t max_out, double *theta_out,
                          double *X_out, double *est_out, lsa_ks_result *result, int64_t *counts);
 int lsa_stochastic_info(const lsa_stochastic *h, lsa_stochastic_stats *out);
+/* ---- the trace of the quadrature operator by block probes: tr S = sum of ALL variances, the total the leading ones are a share of.
+ * For a real probe z, z^T S z is unbiased for tr S when E[z z^T] = I, and with two solves of ONE direction
+ *     z^T S  z = (1 / pi) sum_k w_k Re[(C_k^-H z)^H Qf (C_k^-H Qq z)]     (kind 0: adjoint solves only)
+ *     z^T S' z = (1 / pi) sum_k w_k Re[(C_k^-1 z)^H Qq (C_k^-1 Qf z)]     (kind 1: forward solves only)
+ * so a probe is two independent columns, z and Q z (Q the kind's weight), shared by all nodes: no dependent second solve.  With
+ * ndeflate modes U of the handle's kind, orthonormal in Q, the second column is Q p with p = z - U (U^T Q z), and
+ * tr S = sum_j theta_j + E[z^T S p]: the probes resolve only the remainder. */
+typedef struct {
+    int64_t solves_adjoint;    /* accepted adjoint solves (kind 0: 2 nodes nprobes)                                         */
+    int64_t solves_forward;    /* accepted forward solves (kind 1)                                                          */
+    int64_t refined_solves;    /* ... of either direction that carried the refinement step                                  */
+    int64_t batches;           /* batches of probes queued, those done again after a missed solve included                  */
+    int64_t grouped_sweeps;    /* block solves on more than one factor set in one sweep                                     */
+    int32_t widest_pass;       /* most columns that shared the factor loads of a sweep (complex vectors: 4)                 */
+    int32_t batch;             /* probes per batch, as given or chosen                                                      */
+    double seconds_solve;      /* device seconds of the sweeps (HIP events around the phases)                               */
+    double seconds_product;    /* ... of the probes, the deflation, the check products and the weight products              */
+    double seconds_forms;      /* ... of the forms and check sums                                                           */
+    int64_t bytes;             /* device bytes the call held beside the handle's                                            */
+} lsa_stochastic_trace_stats;
+/* forms[r] = z_r^T S p_r (kind 1: S') for r < nprobes, and node_terms[k nprobes + r] = node k's share (w_k / pi) Re(...) of it
+ * (NULL: none); forms[r] is the sum of its column of node_terms in node order, on the host.  probes: n x nprobes real, column-major,
+ * the caller's row numbering (lsa_stochastic_set_row_permutation), or NULL: Rademacher probes from `seed`, those of
+ * lsa_stochastic_probes.  U: n x ndeflate real in the caller's numbering, the modes lsa_stochastic_solve gave for the handle's kind
+ * and weights (ndeflate = 0: none; at most 128).  Per batch of `batch` probes (0: 8, or fewer where the n x 2 batch nodes complex
+ * blocks exceed 0.8 of the free device memory) the call queues the probes, the deflation, one block solve of 2 batch columns per
+ * run of at most 16 factor sets from ONE right-hand block, the check products of all columns in one launch, the weight product and
+ * the forms, then reads 7 doubles per (node, probe) back behind ONE synchronisation.  Every one of the 2 nodes nprobes solves is
+ * judged as a step's are: within ksp_rtol, else that node and direction carry the refinement step from then on (the node's block
+ * then runs alone with a block refinement step behind it) and the batch is done again, else a backward error within 1e-12 ||C_k||_F
+ * ||x||, else LSA_ERR_DIVERGED naming node, direction and probe.  Every column holds the bits of its solo sweep and every sum runs
+ * in a fixed order: the results do not depend on `batch`, and two calls give the same bits.  The Lanczos basis is neither read nor
+ * disturbed: the call may come before or after lsa_stochastic_solve.  LSA_ERR_ARG, naming the condition: nprobes < 1, ndeflate < 0
+ * or > 128, ndeflate > 0 with U NULL, batch < 0, a U whose Gram matrix U^T Q U (summed on the device, before any solve) is further
+ * from I than 1e-6 in an entry.  LSA_ERR_OOM with the bytes needed and available where a given batch, or one probe, does not fit. */
+int lsa_stochastic_trace(lsa_ctx *ctx, lsa_stochastic *h, int32_t nprobes, uint64_t seed, const double *probes, int32_t ndeflate, const double *U,
+                         int32_t batch, double *forms, double *node_terms, lsa_stochastic_trace_stats *stats);
+/* The generator of lsa_stochastic_trace alone: Z_host (n x nprobes, column-major, the caller's numbering) = the Rademacher probes of
+ * `seed`.  With mix(x) = splitmix64's output function (x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) 0xBF58476D1CE4E5B9; x = (x ^ x >> 27)
+ * 0x94D049BB133111EB; x ^ x >> 31, all modulo 2^64): Z[i, p] = +1 where the top bit of mix(mix(mix(seed) + p) + i) is 0, else -1,
+ * i the CALLER's row: a pure function of (seed, p, i), whatever the permutation, the batch width or the probes of a launch. */
+int lsa_stochastic_probes(lsa_ctx *ctx, lsa_stochastic *h, int32_t nprobes, uint64_t seed, double *Z_host);
 
 /* ---- MatrixMarket reader (host only): the A.mtx / M.mtx stage boundary --------------------------------------------
  * Stands in for scipy.io.mmread + the per-entry setValue loop of iPETScMatrix.from_path / from_matrix

@@ -19,7 +19,14 @@ the integrand is the caller's to check, by solving again with more.  Near sharp 
 ``nodes`` (their sum converges much sooner); ``discount=beta`` evaluates ``W`` at ``beta + i omega`` and smooths the integrand, as it
 does for the resolvent.  Forcing and response windows and weights mean what they mean in :class:`Solver.resolvent.ResolventSolver`
 and are built on the device the same way (``CsrMatrix.windowed``).  ``batch_adjoint=True`` sends the adjoint solves of a step through
-the batched transposed sweeps (same bits; off by default).  A trace or captured-fraction estimate, several ranks, complex pencils and refactorising factor sets when ``nodes`` of them do not fit are not built.
+the batched transposed sweeps (same bits; off by default).
+
+``solve(..., trace=32)`` (or a :class:`TraceConfig`) adds the total variance ``tr S`` -- the sum of ALL variances -- estimated by block
+probes on the same handle and factor sets (``lsa_stochastic_trace``), deflated with the converged modes, and with it the share of the
+total the leading modes carry (``res.total_variance``, ``res.captured``); ``total_variance(...)`` gives the trace alone, without an
+eigen-iteration.  The trace is far more stable in ``nodes`` than the leading variances are.  Hutch++-style sketching, adaptive stopping
+on a requested standard error, several ranks, complex pencils and refactorising factor sets when ``nodes`` of them do not fit are not
+built.
 """
 
 from __future__ import annotations
@@ -50,6 +57,16 @@ class StochasticConfig:
     nodes: int = 16  # quadrature nodes = factorisations kept alive (``band=`` rules; explicit ``omegas`` bring their own count)
 
 
+@dataclass(frozen=True)
+class TraceConfig:
+    """The block-probe estimate of the total variance ``tr S`` behind ``solve(trace=...)``."""
+
+    probes: "int | np.ndarray" = 32  # Rademacher probes generated on the device from ``seed``, or an ``n x R`` real array of the caller's own
+    seed: int = 0
+    deflate: bool = True  # remove the converged modes from the probes: they then resolve only ``tr S - sum(theta)``
+    batch: int = 0  # probes per block solve (0: chosen by the library from the free memory, 8 at most)
+
+
 @dataclass
 class StochasticResult:
     """``Q`` below is the weight of the kind: the response weight ``Qq`` for EOFs, the forcing weight ``Qf`` for stochastic optimals
@@ -64,6 +81,65 @@ class StochasticResult:
     estimates: np.ndarray  # relative residual estimates of the variances
     stats: dict = field(default_factory=dict)
     discount: float = 0.0
+    # with ``solve(trace=...)`` (``None`` otherwise):
+    total_variance: float | None = None  # the estimate of tr S, the sum of all variances of the quadrature operator
+    total_variance_stderr: float | None = None  # its standard error over the probes (nan for one probe, 0 for the n unit vectors)
+    captured: np.ndarray | None = None  # k cumulative fractions sum_{i <= j} variances[i] / total_variance
+    captured_stderr: np.ndarray | None = None  # ... and their first-order errors
+    node_totals: np.ndarray | None = None  # N: node k's share of total_variance, the frequency-resolved variance
+
+
+def trace_summary(forms, variances=None, exact: bool = False) -> dict:
+    """The estimate of ``tr S`` from the forms ``z_r^T S p_r`` of ``R`` probes deflated by modes with the given ``variances`` (``None``:
+    no deflation): ``total = sum(variances) + mean(forms)`` and ``stderr = std(forms, ddof=1) / sqrt(R)`` (``nan`` for ``R = 1``).
+    ``exact=True``: the probes were the ``n`` unit vectors, so ``total = sum(variances) + sum(forms)`` and ``stderr = 0``.  Returns a dict:
+    ``total``, ``stderr``, ``remainder`` (the probes' part), ``exact``."""
+    f = np.atleast_1d(np.asarray(forms, dtype=np.float64))
+    if f.ndim != 1 or f.size < 1:
+        raise ValueError(f"forms must be a non-empty vector, got shape {f.shape}")
+    head = 0.0 if variances is None else float(np.sum(np.asarray(variances, dtype=np.float64)))
+    if exact:
+        rest, err = float(f.sum()), 0.0
+    else:
+        rest = float(f.mean())
+        err = float(f.std(ddof=1) / math.sqrt(f.size)) if f.size > 1 else math.nan
+    return {"total": head + rest, "stderr": err, "remainder": rest, "exact": bool(exact)}
+
+
+def captured_fractions(variances, total: float, stderr: float = 0.0) -> tuple[np.ndarray, np.ndarray]:
+    """``(fractions, errors)``: the cumulative shares ``sum_{i <= j} variances[i] / total`` of the total variance and their first-order
+    errors ``fraction * stderr / total`` (the variances themselves are taken as exact)."""
+    if not (math.isfinite(total) and total > 0.0):
+        raise ValueError(f"total = {total!r} must be positive and finite")
+    frac = np.cumsum(np.asarray(variances, dtype=np.float64)) / float(total)
+    return frac, frac * (float(stderr) / float(total))
+
+
+def checked_trace(trace, n: int) -> "TraceConfig | None":
+    """``solve``'s ``trace=`` as a :class:`TraceConfig` (``None`` stays ``None``; an int is a probe count).  ``ValueError`` for a count
+    below 1, a probe array that is not ``n x R`` real with ``R >= 1``, or a negative batch.  Pure host logic."""
+    if trace is None:
+        return None
+    if not isinstance(trace, TraceConfig):
+        trace = TraceConfig(probes=trace)
+    p = trace.probes
+    if isinstance(p, (bool, np.bool_)):
+        raise ValueError(f"trace: probes = {p!r} must be a count or an array")
+    if isinstance(p, (int, np.integer)):
+        if p < 1:
+            raise ValueError(f"trace: probes = {int(p)} must be at least 1")
+    else:
+        p = np.asarray(p)
+        if p.ndim != 2 or p.shape[0] != n or p.shape[1] < 1 or not np.isrealobj(p):
+            raise ValueError(f"trace: a probe array must be real with shape ({n}, R), R >= 1, got {p.shape} {p.dtype}")
+        trace = TraceConfig(np.asfortranarray(p, dtype=np.float64), trace.seed, trace.deflate, trace.batch)
+    if not isinstance(trace.batch, (int, np.integer)) or trace.batch < 0:
+        raise ValueError(f"trace: batch = {trace.batch!r} must be 0 (chosen) or positive")
+    return trace
+
+
+def _unit_vectors(p) -> bool:
+    return isinstance(p, np.ndarray) and p.shape[0] == p.shape[1] and np.array_equal(p, np.eye(p.shape[0]))
 
 
 def gauss_legendre_band(a: float, b: float, nodes: int) -> tuple[np.ndarray, np.ndarray]:
@@ -167,15 +243,20 @@ class StochasticForcingSolver(ExactLuFrontEnd):
     def config(self) -> StochasticConfig:
         return self._cfg
 
-    def solve(self, band=None, *, scale: float | None = None, omegas=None, weights=None, kind: str = "eofs", discount: float | None = None) -> StochasticResult:
+    def solve(self, band=None, *, scale: float | None = None, omegas=None, weights=None, kind: str = "eofs", discount: float | None = None,
+              trace: "int | TraceConfig | None" = None) -> StochasticResult:
         """The leading variances and modes of the quadrature operator over ``band=(a, b)`` (Gauss-Legendre, ``cfg.nodes`` nodes),
         ``band=(0, inf)`` with ``scale=s`` (``omega = s tan(theta)``) or explicit ``omegas`` and ``weights``.  ``kind="eofs"``: the
         response structures, orthonormal in ``Qq``; ``kind="optimals"``: the forcing structures, orthonormal in ``Qf``.  A second call
-        on the same solver keeps the context, the ordering, the LU analysis and the weights on the device."""
+        on the same solver keeps the context, the ordering, the LU analysis and the weights on the device.  ``trace=`` (a probe count
+        or a :class:`TraceConfig`): after the modes converge, the block-probe estimate of the total variance on the same handle and
+        factor sets fills ``total_variance``, ``captured`` and ``node_totals`` of the result; everything else is what the call returns
+        without it."""
         import lsa_hip
 
         if kind not in KINDS:
             raise ValueError(f"kind = {kind!r} must be 'eofs' or 'optimals'")
+        trace = checked_trace(trace, self._n)
         om, w = quadrature(self._cfg.nodes, band, scale, omegas, weights)
         beta = self._discount if discount is None else _real_discount(discount)
         cfg, nev = self._cfg, self._cfg.num_modes
@@ -207,6 +288,10 @@ class StochasticForcingSolver(ExactLuFrontEnd):
             for j in range(k):  # one apply per mode: node k's share of e_j^T Q S e_j
                 spectrum[j] = basis.apply(np.ascontiguousarray(out["modes"][perm, j]))[1]
             info = basis.info()
+            traced = None
+            if trace is not None:  # (after everything else: what a solve without trace= returns is in hand)
+                kc = min(int(out["nconv"]), k) if trace.deflate else 0
+                traced = self._trace(basis, trace, out["modes"][:, :kc] if kc else None)
         finally:
             del basis  # (the handle goes before the matrices it borrows)
         if out["nconv"] < nev:
@@ -223,4 +308,56 @@ class StochasticForcingSolver(ExactLuFrontEnd):
                  "seconds_product": info["seconds_product"], "seconds_solve_adjoint": info["seconds_solve_adjoint"],
                  "seconds_product_adjoint": info["seconds_product_adjoint"], "seconds_dense": info["seconds_dense"], "seconds_expand": out["seconds_expand"],
                  "seconds_restart": out["seconds_restart"], "seconds_total": time.time() - started}
-        return StochasticResult(out["variances"], out["modes"], kind, om, w, spectrum, out["estimates"], stats, beta)
+        res = StochasticResult(out["variances"], out["modes"], kind, om, w, spectrum, out["estimates"], stats, beta)
+        if traced is not None:
+            kc = min(int(out["nconv"]), k) if trace.deflate else 0
+            summary = trace_summary(traced["forms"], out["variances"][:kc] if kc else None, exact=traced["exact"])
+            res.total_variance, res.total_variance_stderr = summary["total"], summary["stderr"]
+            res.captured, res.captured_stderr = captured_fractions(out["variances"], summary["total"], summary["stderr"])
+            res.node_totals = spectrum[:kc].sum(axis=0) + traced["node_rest"]
+            stats["trace"] = traced["stats"]
+        return res
+
+    @staticmethod
+    def _trace(basis, trace: TraceConfig, modes) -> dict:
+        """The library's estimator on ``basis``: the forms, node ``k``'s share of the probes' part of the total, the library's stats."""
+        p = trace.probes
+        given = isinstance(p, np.ndarray)
+        out = basis.trace(p.shape[1] if given else int(p), seed=trace.seed, probes=p if given else None, modes=modes, batch=int(trace.batch))
+        exact = given and _unit_vectors(p)
+        rest = out["node_terms"].sum(axis=1) if exact else out["node_terms"].mean(axis=1)
+        return {"forms": out["forms"], "node_rest": rest, "stats": out["stats"], "exact": exact}
+
+    def total_variance(self, band=None, *, scale: float | None = None, omegas=None, weights=None, probes=32, seed: int = 0, discount: float | None = None,
+                       kind: str = "eofs", batch: int = 0) -> tuple[float, float, np.ndarray]:
+        """``(total, stderr, node_totals)``: the block-probe estimate of ``tr S`` of the quadrature operator the arguments name (as
+        :meth:`solve`'s), its standard error over the probes, and node ``k``'s share of it, without an eigen-iteration.  ``probes``: a
+        count of Rademacher probes generated from ``seed``, or an ``n x R`` real array (the ``n`` unit vectors give the trace itself).  The
+        library's stats of the call stay in ``self.trace_stats``."""
+        import lsa_hip
+
+        if kind not in KINDS:
+            raise ValueError(f"kind = {kind!r} must be 'eofs' or 'optimals'")
+        trace = checked_trace(TraceConfig(probes=probes, seed=seed, deflate=False, batch=batch), self._n)
+        om, w = quadrature(self._cfg.nodes, band, scale, omegas, weights)
+        beta = self._discount if discount is None else _real_discount(discount)
+        prep, ctx, perm = self._prepare(complex(beta, max(float(om.max()), 1.0)))
+        try:
+            plan_factor_sets(om.size, ctx.prepared_lu_bytes(), ctx.mem_info()[0])
+        except ValueError:
+            pass
+        basis = None
+        try:
+            basis = lsa_hip.StochasticBasis(ctx, prep["dA"], prep["dM"], beta + 1j * om, w, 1, ksp_rtol=self._ksp_rtol)
+            basis.set_row_permutation(perm)
+            if any(spec is not None for spec in self._sides):
+                basis.set_weights(*self._weights_on_device(prep, self._sides, "stochastic_weights"))
+            basis.set_kind(KINDS[kind])
+            if self._force_refinement:
+                basis.set_refinement(True)
+            traced = self._trace(basis, trace, None)
+        finally:
+            del basis
+        summary = trace_summary(traced["forms"], None, exact=traced["exact"])
+        self.trace_stats = traced["stats"]
+        return summary["total"], summary["stderr"], traced["node_rest"]

@@ -704,6 +704,8 @@ void lanczos_set_inner_product(lsa_lanczos* l, const lsa_mat* Q) {
 
 void* lanczos_ritz_device(const lsa_lanczos* l) { return l->V2; }
 
+const int32_t* lanczos_row_permutation(const lsa_lanczos* l) { return l->row_perm; }
+
 int lanczos_ritz_to_host(lsa_ctx* ctx, lsa_lanczos* l, int32_t nvec, void* X) {
     return basis_columns_to_host(ctx, l->dtype, l->n, nvec, l->row_perm, l->V2, &l->xtmp, l->ncv + 1, X);
 }

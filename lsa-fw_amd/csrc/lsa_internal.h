@@ -457,6 +457,8 @@ int lanczos_ritz_vectors(lsa_ctx* ctx, lsa_lanczos* l, int32_t m, int32_t nvec, 
 // nvec of them to the host in the caller's row numbering
 void* lanczos_ritz_device(const lsa_lanczos* l);
 int lanczos_ritz_to_host(lsa_ctx* ctx, lsa_lanczos* l, int32_t nvec, void* X);
+// the device copy of the row permutation (basis row i is the caller's row perm[i]), or null where none is set
+const int32_t* lanczos_row_permutation(const lsa_lanczos* l);
 // The operator behind a step: it queues w = OP v_j and names the inner solves the step's first reduction checks.  The default of a
 // real basis is the single solve w = C^-1 rhs on the op's shared refinement flag; growth.hip puts a march of solves there,
 // resolvent.hip an adjoint solve, a weight and a forward solve.

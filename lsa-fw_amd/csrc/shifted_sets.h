@@ -61,5 +61,7 @@ inline int shifted_sets_verdict(const shifted_sets* s, int32_t k, double ksp_rto
 
 // Y[:, k] = (A - z_k M) X[:, k], k < N: A, M real on one pattern, X, Y n x N complex (ld n), z_dev N complex on the device
 int k_shifted_spmm(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t N, const void* z_dev, const void* X, void* Y);
+// Y[:, c] = (A - z_c M)^H X[:, c], c < N, on the pattern's transposed index (k_transpose_index) in one launch; not k_spmv_transpose's bits
+int k_shifted_spmm_transpose(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t N, const void* z_dev, const void* X, void* Y);
 // whether M has A's pattern, as far as the handles can tell without a read-back
 bool sf_same_pattern(const lsa_mat* A, const lsa_mat* M);

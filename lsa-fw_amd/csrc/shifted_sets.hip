@@ -5,6 +5,7 @@
 // Every sum runs in a fixed order and there are no floating-point atomics: two runs give the same bits.
 //   sf_shifted_spmm_kernel   the entries of a row strided over the 8 lanes of its row group, each lane adding its entries in order;
 //                            then the xor tree over the 8 lanes (ci_spmm_kernel's order)
+//   sf_shifted_spmm_transpose_kernel   the same order over the entries of a row of the transposed index
 #include "shifted_sets.h"
 
 #include <cmath>
@@ -58,6 +59,69 @@ __global__ __launch_bounds__(kSfThreads) void sf_shifted_spmm_kernel(int32_t n, 
 #pragma unroll
                 for (int u = 0; u < kSfColTile; ++u)
                     if (u < nc) fma_acc(acc[u], cplx{fma(-zz[u].re, mv, av), -(zz[u].im * mv)}, rz_ld(x + (int64_t)u * ldx));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kSfColTile; ++u) {
+#pragma unroll
+            for (int off = kSfRowLanes / 2; off >= 1; off >>= 1) {
+                acc[u].re += __shfl_xor(acc[u].re, off, 64);
+                acc[u].im += __shfl_xor(acc[u].im, off, 64);
+            }
+        }
+        if (sub == 0 && row < n) {
+#pragma unroll
+            for (int u = 0; u < kSfColTile; ++u)
+                if (u < nc) rz_st(Y + row + (int64_t)(k0 + u) * ldy, acc[u]);
+        }
+    }
+}
+
+// Y[:, c] = (A - z_c M)^H X[:, c], c < N, on the pattern's transposed index (rp, ci, src of k_transpose_index: output row r sums the
+// entries q in [rp[r], rp[r + 1]), the values at position src[q] of the CSR arrays times X[ci[q], c]).  The shape of
+// sf_shifted_spmm_kernel: 8 lanes per output row, lane s takes the entries rp[r] + s, rp[r] + s + 8, ..., one load of the row index,
+// the source position and the two real values per entry serves a pass of up to 16 columns, the 16 loads of X of a full pass requested
+// before the first multiply-add; then the xor tree over the 8 lanes.  conj(a - z m) is formed per column in registers:
+// Re = fma(-Re z, m, a), Im = (Im z) m.
+__global__ __launch_bounds__(kSfThreads) void sf_shifted_spmm_transpose_kernel(int32_t n, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                                               const int32_t* __restrict__ src, const double* __restrict__ a,
+                                                                               const double* __restrict__ m, int N, const cplx* __restrict__ z,
+                                                                               const cplx* __restrict__ X, int64_t ldx, cplx* __restrict__ Y, int64_t ldy) {
+    const int sub = threadIdx.x & (kSfRowLanes - 1);
+    const int64_t row = (int64_t)blockIdx.x * (kSfThreads / kSfRowLanes) + (threadIdx.x / kSfRowLanes);
+    int32_t p0 = 0, p1 = 0;
+    if (row < n) {
+        p0 = rp[row];
+        p1 = rp[row + 1];
+    }
+    for (int k0 = 0; k0 < N; k0 += kSfColTile) {
+        const int nc = (N - k0 < kSfColTile) ? N - k0 : kSfColTile;
+        cplx zz[kSfColTile], acc[kSfColTile];
+#pragma unroll
+        for (int u = 0; u < kSfColTile; ++u) {
+            zz[u] = (u < nc) ? rz_ld(z + k0 + u) : cplx{0.0, 0.0};
+            acc[u] = cplx{0.0, 0.0};
+        }
+        const cplx* Xt = X + (int64_t)k0 * ldx;
+        if (nc == kSfColTile) {
+            for (int32_t p = p0 + sub; p < p1; p += kSfRowLanes) {
+                const cplx* x = Xt + ci[p];
+                const int32_t q = src[p];
+                const double av = a[q], mv = m[q];
+                cplx xv[kSfColTile];
+#pragma unroll
+                for (int u = 0; u < kSfColTile; ++u) xv[u] = rz_ld(x + (int64_t)u * ldx);
+#pragma unroll
+                for (int u = 0; u < kSfColTile; ++u) fma_acc(acc[u], cplx{fma(-zz[u].re, mv, av), zz[u].im * mv}, xv[u]);
+            }
+        } else {
+            for (int32_t p = p0 + sub; p < p1; p += kSfRowLanes) {
+                const cplx* x = Xt + ci[p];
+                const int32_t q = src[p];
+                const double av = a[q], mv = m[q];
+#pragma unroll
+                for (int u = 0; u < kSfColTile; ++u)
+                    if (u < nc) fma_acc(acc[u], cplx{fma(-zz[u].re, mv, av), zz[u].im * mv}, rz_ld(x + (int64_t)u * ldx));
             }
         }
 #pragma unroll
@@ -224,6 +288,16 @@ int k_shifted_spmm(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t N, 
     return lsa_check_launch(ctx, "sf_shifted_spmm_kernel");
 }
 
+int k_shifted_spmm_transpose(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t N, const void* z_dev, const void* X, void* Y) {
+    if (A->n < 1 || N < 1) return LSA_OK;
+    const TransposeIndex* T = nullptr;
+    LSA_CHECK(k_transpose_index(ctx, A, &T));
+    const int per_block = kSfThreads / kSfRowLanes;
+    hipLaunchKernelGGL(sf_shifted_spmm_transpose_kernel, dim3((A->ncols + per_block - 1) / per_block), dim3(kSfThreads), 0, ctx->stream, A->ncols, T->rp, T->ci,
+                       T->src, (const double*)A->val, (const double*)M->val, N, (const cplx*)z_dev, (const cplx*)X, (int64_t)A->n, (cplx*)Y, (int64_t)A->n);
+    return lsa_check_launch(ctx, "sf_shifted_spmm_transpose_kernel");
+}
+
 bool sf_same_pattern(const lsa_mat* A, const lsa_mat* M) {
     if (M->n != A->n || M->ncols != A->ncols || M->nnz != A->nnz) return false;
     if (A->rp == M->rp && A->ci == M->ci) return true;
@@ -231,28 +305,38 @@ bool sf_same_pattern(const lsa_mat* A, const lsa_mat* M) {
     return true;
 }
 
-extern "C" {
-
-int lsa_shifted_spmm(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* shifts, const lsa_vec* X, lsa_vec* Y) {
-    if (!ctx || !A || !M || !shifts || !X || !Y) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: null argument");
-    if (A->n != A->ncols || A->row0 != 0) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: A is a row shard (%d x %d): whole square matrices only", A->n, A->ncols);
-    if (A->dtype != LSA_F64 || M->dtype != LSA_F64) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: A or M is complex: real matrices only");
-    if (!sf_same_pattern(A, M)) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: A and M do not share one pattern");
-    if (nodes < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: %d columns", nodes);
-    if (X->dtype != LSA_C128 || Y->dtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: the blocks must be complex128");
-    if (X->d == Y->d) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: X and Y must not alias");
+// lsa_shifted_spmm and lsa_shifted_spmm_transpose: the checks, the upload of the shifts, the one launch, the synchronisation
+static int ss_shifted_spmm_entry(lsa_ctx* ctx, const char* who, bool transpose, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* shifts,
+                                 const lsa_vec* X, lsa_vec* Y) {
+    if (!ctx || !A || !M || !shifts || !X || !Y) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument", who);
+    if (A->n != A->ncols || A->row0 != 0) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: A is a row shard (%d x %d): whole square matrices only", who, A->n, A->ncols);
+    if (A->dtype != LSA_F64 || M->dtype != LSA_F64) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: A or M is complex: real matrices only", who);
+    if (!sf_same_pattern(A, M)) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: A and M do not share one pattern", who);
+    if (nodes < 1) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: %d columns", who, nodes);
+    if (X->dtype != LSA_C128 || Y->dtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the blocks must be complex128", who);
+    if (X->d == Y->d) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: X and Y must not alias", who);
     const int64_t need = (int64_t)A->n * nodes;
     if (X->n < need || Y->n < need)
-        return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_shifted_spmm: blocks of %d columns of %d rows do not fit vectors of %lld and %lld entries", nodes, A->n,
+        return lsa_set_error(ctx, LSA_ERR_ARG, "%s: blocks of %d columns of %d rows do not fit vectors of %lld and %lld entries", who, nodes, A->n,
                              (long long)X->n, (long long)Y->n);
     cplx* zdev = nullptr;
     LSA_HIP_ALLOC(ctx, hipMalloc((void**)&zdev, (size_t)nodes * sizeof(cplx)));
     int rc = LSA_OK;
-    if (hipMemcpy(zdev, shifts, (size_t)nodes * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess) rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_shifted_spmm: the upload of the shifts failed");
-    if (rc == LSA_OK) rc = k_shifted_spmm(ctx, A, M, nodes, zdev, X->d, Y->d);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == LSA_OK) rc = lsa_set_error(ctx, LSA_ERR_HIP, "lsa_shifted_spmm: the kernel failed");
+    if (hipMemcpy(zdev, shifts, (size_t)nodes * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess) rc = lsa_set_error(ctx, LSA_ERR_HIP, "%s: the upload of the shifts failed", who);
+    if (rc == LSA_OK) rc = transpose ? k_shifted_spmm_transpose(ctx, A, M, nodes, zdev, X->d, Y->d) : k_shifted_spmm(ctx, A, M, nodes, zdev, X->d, Y->d);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == LSA_OK) rc = lsa_set_error(ctx, LSA_ERR_HIP, "%s: the kernel failed", who);
     (void)hipFree(zdev);
     return rc;
+}
+
+extern "C" {
+
+int lsa_shifted_spmm(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* shifts, const lsa_vec* X, lsa_vec* Y) {
+    return ss_shifted_spmm_entry(ctx, "lsa_shifted_spmm", false, A, M, nodes, shifts, X, Y);
+}
+
+int lsa_shifted_spmm_transpose(lsa_ctx* ctx, const lsa_mat* A, const lsa_mat* M, int32_t nodes, const double* shifts, const lsa_vec* X, lsa_vec* Y) {
+    return ss_shifted_spmm_entry(ctx, "lsa_shifted_spmm_transpose", true, A, M, nodes, shifts, X, Y);
 }
 
 }  // extern "C"

@@ -188,6 +188,22 @@ class lsa_stochastic_stats(ctypes.Structure):
     ]
 
 
+class lsa_stochastic_trace_stats(ctypes.Structure):
+    _fields_ = [
+        ("solves_adjoint", ctypes.c_int64),
+        ("solves_forward", ctypes.c_int64),
+        ("refined_solves", ctypes.c_int64),
+        ("batches", ctypes.c_int64),
+        ("grouped_sweeps", ctypes.c_int64),
+        ("widest_pass", ctypes.c_int32),
+        ("batch", ctypes.c_int32),
+        ("seconds_solve", ctypes.c_double),
+        ("seconds_product", ctypes.c_double),
+        ("seconds_forms", ctypes.c_double),
+        ("bytes", ctypes.c_int64),
+    ]
+
+
 _P = ctypes.c_void_p
 _I32, _I64, _DBL = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -328,6 +344,7 @@ SIGNATURES = {
     "lsa_contour_solve_left": (ctypes.c_int, [_P, _P, _DBL, _I32, _P, _I32, _P, _P, _P, ctypes.POINTER(lsa_contour_result)]),
     "lsa_contour_left_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_contour_left_stats)]),
     "lsa_shifted_spmm": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P]),
+    "lsa_shifted_spmm_transpose": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P]),
     "lsa_stochastic_create": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _I32, _DBL, _PP]),
     "lsa_stochastic_destroy": (None, [_P]),
     "lsa_stochastic_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
@@ -339,6 +356,8 @@ SIGNATURES = {
     "lsa_stochastic_apply": (ctypes.c_int, [_P, _P, _P, _P, _P]),
     "lsa_stochastic_solve": (ctypes.c_int, [_P, _P, ctypes.POINTER(lsa_ks_options), _P, _I32, _P, _P, _P, ctypes.POINTER(lsa_ks_result), _P]),
     "lsa_stochastic_info": (ctypes.c_int, [_P, ctypes.POINTER(lsa_stochastic_stats)]),
+    "lsa_stochastic_trace": (ctypes.c_int, [_P, _P, _I32, ctypes.c_uint64, _P, _I32, _P, _I32, _P, _P, ctypes.POINTER(lsa_stochastic_trace_stats)]),
+    "lsa_stochastic_probes": (ctypes.c_int, [_P, _P, _I32, ctypes.c_uint64, _P]),
     "lsa_mm_open": (ctypes.c_int, [ctypes.c_char_p, _PP, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int)]),
     "lsa_mm_read_csr": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_mm_error": (ctypes.c_char_p, [_P]),
@@ -1490,7 +1509,7 @@ class ContourSolver(_Handle):
         return d
 
 
-def shifted_spmm(ctx: Context, A: CsrMatrix, M: CsrMatrix, shifts, X: np.ndarray) -> np.ndarray:
+def shifted_spmm(ctx: Context, A: CsrMatrix, M: CsrMatrix, shifts, X: np.ndarray, *, _entry: str = "lsa_shifted_spmm") -> np.ndarray:
     """``Y[:, k] = (A - shifts[k] M) X[:, k]`` for all columns in one launch (``lsa_shifted_spmm``): ``A``, ``M`` real on one
     pattern, ``X`` an ``n x N`` complex block on the host; returns ``Y`` on the host."""
     z = np.ascontiguousarray(shifts, dtype=np.complex128).ravel()
@@ -1500,8 +1519,14 @@ def shifted_spmm(ctx: Context, A: CsrMatrix, M: CsrMatrix, shifts, X: np.ndarray
         raise ValueError(f"the block must have shape ({n}, {z.size}), got {X.shape}")
     dX = DeviceVector.from_numpy(ctx, X.ravel(order="F"))
     dY = DeviceVector(ctx, n * z.size, np.complex128)
-    ctx.check(ctx._lib.lsa_shifted_spmm(ctx.handle, A.handle, M.handle, z.size, _ptr(z), dX.handle, dY.handle))
+    ctx.check(getattr(ctx._lib, _entry)(ctx.handle, A.handle, M.handle, z.size, _ptr(z), dX.handle, dY.handle))
     return dY.numpy().reshape((n, z.size), order="F")
+
+
+def shifted_spmm_transpose(ctx: Context, A: CsrMatrix, M: CsrMatrix, shifts, X: np.ndarray) -> np.ndarray:
+    """``Y[:, k] = (A - shifts[k] M)^H X[:, k]`` for all columns in one launch on the pattern's transposed index
+    (``lsa_shifted_spmm_transpose``); arguments as :func:`shifted_spmm`."""
+    return shifted_spmm(ctx, A, M, shifts, X, _entry="lsa_shifted_spmm_transpose")
 
 
 class StochasticBasis(_LanczosHandle):
@@ -1566,6 +1591,40 @@ class StochasticBasis(_LanczosHandle):
         X = np.empty((self.n, max_out), dtype=np.float64, order="F")
         k, tail = self._solve(_ks_options(nev, tol, max_restarts, seed=seed), v0, max_out, theta, X)
         return {"variances": theta[:k].copy(), "modes": np.asfortranarray(X[:, :k]), **tail}
+
+    def probes(self, nprobes: int, seed: int = 0) -> np.ndarray:
+        """The ``n x nprobes`` Rademacher probes of ``seed`` in the caller's row numbering (``lsa_stochastic_probes``): entry ``(i, p)``
+        is a pure function of ``(seed, p, i)``, whatever the row permutation."""
+        nprobes = int(nprobes)
+        if nprobes < 1:
+            raise ValueError(f"nprobes = {nprobes} must be at least 1")
+        Z = np.empty((self.n, nprobes), dtype=np.float64, order="F")
+        self._call("probes", nprobes, ctypes.c_uint64(int(seed)), _ptr(Z))
+        return Z
+
+    def trace(self, nprobes: int, seed: int = 0, probes: np.ndarray | None = None, modes: np.ndarray | None = None, batch: int = 0) -> dict:
+        """Block-probe forms for the trace of the quadrature operator (``lsa_stochastic_trace``): ``forms[r] = z_r^T S p_r`` (kind 1:
+        ``S'``) with ``p = z - U (U^T Q z)`` for the modes ``U`` given (``n x d``, the caller's numbering, orthonormal in the kind's
+        weight; ``None``: ``p = z``), so that ``tr S = sum(theta) + E[forms]``.  ``probes``: ``n x nprobes`` real in the caller's
+        numbering (``None``: the Rademacher probes of ``seed``).  Returns a dict: ``forms`` (``nprobes``), ``node_terms``
+        (``nodes x nprobes``, the columns sum to ``forms``) and ``stats`` (``lsa_stochastic_trace_stats``)."""
+        nprobes = int(nprobes)
+        Z = U = None
+        if probes is not None:
+            Z = np.asfortranarray(probes, dtype=np.float64)
+            if Z.shape != (self.n, nprobes):
+                raise ValueError(f"the probes must have shape ({self.n}, {nprobes}), got {Z.shape}")
+        d = 0
+        if modes is not None:
+            U = np.asfortranarray(modes, dtype=np.float64)
+            if U.ndim != 2 or U.shape[0] != self.n:
+                raise ValueError(f"the modes must have shape ({self.n}, d), got {U.shape}")
+            d = U.shape[1]
+        forms, terms = np.zeros(max(nprobes, 1)), np.zeros((self.nodes, max(nprobes, 1)))
+        st = lsa_stochastic_trace_stats()
+        self._call("trace", nprobes, ctypes.c_uint64(int(seed)), None if Z is None else _ptr(Z), d, None if U is None or d == 0 else _ptr(U), int(batch),
+                   _ptr(forms), _ptr(terms), ctypes.byref(st))
+        return {"forms": forms[:nprobes], "node_terms": terms[:, :nprobes], "stats": {name: getattr(st, name) for name, _ in lsa_stochastic_trace_stats._fields_}}
 
     def info(self) -> dict:
         """``lsa_stochastic_info``: nodes, kind, device bytes, the phase times, and the inner solves' counters under ``"solver"``."""

@@ -1,6 +1,7 @@
 """Stochastic forcing: the library's iteration on kept factor sets against what a user can drive from the host on kept factors.
 
     python tools/stochastic_ab.py [--cases S30k C160k] [--nodes 8 16] [--reps 3] [--out profiles/stochastic_ab.json]
+    python tools/stochastic_ab.py --trace P [--reps 3] [--out profiles/stochastic_trace.json]
 
 ``library`` (a): ``Solver.stochastic.StochasticForcingSolver.solve`` -- set-up, ``nodes`` factorisations of ``A - i omega_k M`` on one
 analysis, the real thick-restart Lanczos iteration on ``S = (1 / pi) sum_k w_k Re W(i omega_k)`` with all ``2 nodes`` inner solves of a step,
@@ -19,6 +20,13 @@ num_modes 4, ncv 24, tolerance 1e-8, Gauss-Legendre on the band [0, 1.5].  Every
 preparation, factorisations, iteration, release inside the clock); the settings alternate in one process after one warm-up of each;
 medians and spread over ``reps`` samples.  The variances of (a') are compared with those of (a) bit for bit, those of (b) in
 relative size.  No test asserts these times.
+
+``--trace P``: the total variance by ``P`` block probes.  ``library``: one ``lsa_stochastic_trace`` call (two independent columns per probe
+through one direction's block sweeps on runs of up to 16 factor sets, one read-back per batch of probes).  ``host_loop``: ``P`` calls of
+``basis.apply`` from Python (``2 nodes`` dependent solves and one synchronisation each) with ``z^T (S z)`` evaluated in numpy.  Both on
+the SAME handle -- the same kept factor sets -- and the same probes (the generator's, seed 0); the factorisations are outside both
+clocks.  S30k at 8 and 16 nodes and C160k at 8 nodes; after one warm-up of each the two alternate ``reps`` times; medians, the spread, the
+ratio of the medians, the largest difference between the two sets of forms, and the library's phase split from its stats.
 """
 
 from __future__ import annotations
@@ -101,6 +109,49 @@ def host(es, nodes: int) -> dict:
             "seconds_iteration": t3 - t2, "products": products[0] - 1, "seconds_per_product": (t3 - t2) / max(products[0] - 1, 1)}
 
 
+def trace_ab(case: str, nodes: int, probes: int, reps: int) -> dict:
+    import lsa_hip
+    from Solver.stochastic import StochasticConfig, StochasticForcingSolver, gauss_legendre_band, trace_summary
+
+    es = problem(case)
+    sf = StochasticForcingSolver(es.A, es.M, StochasticConfig(num_modes=MODES, ncv=NCV, atol=TOL, nodes=nodes))
+    om, w = gauss_legendre_band(*BAND, nodes)
+    prep, ctx, perm = sf._prepare(complex(0.0, max(float(om.max()), 1.0)))
+    basis = lsa_hip.StochasticBasis(ctx, prep["dA"], prep["dM"], 1j * om, w, 1, ksp_rtol=sf._ksp_rtol)
+    try:
+        basis.set_row_permutation(perm)
+        basis.set_batch_forward(True)  # (what the front end's applies run with)
+        Z = basis.probes(probes, seed=0)
+        Zown = np.ascontiguousarray(Z[perm].T)  # (apply takes the matrices' own numbering)
+
+        def library():
+            t0 = time.perf_counter()
+            out = basis.trace(probes, probes=Z)
+            return time.perf_counter() - t0, out["forms"], out["stats"]
+
+        def host_loop():
+            t0 = time.perf_counter()
+            forms = np.array([v @ basis.apply(v)[0] for v in Zown])
+            return time.perf_counter() - t0, forms, None
+
+        library(), host_loop()  # warm-up: code objects, the sweeps' column buffers
+        lib, loop = [], []
+        for _ in range(reps):
+            lib.append(library())
+            loop.append(host_loop())
+    finally:
+        del basis
+        sf.release()
+    fa, fb, st = lib[-1][1], loop[-1][1], lib[-1][2]
+    summary = trace_summary(fa)
+    entry = {"case": case, "n": int(es.A.shape[0]), "nodes": nodes, "probes": probes, "library_seconds": spread([r[0] for r in lib]),
+             "host_loop_seconds": spread([r[0] for r in loop]), "forms_max_relative_difference": float(np.abs(fa - fb).max() / np.abs(fb).max()),
+             "total": summary["total"], "stderr": summary["stderr"], "library_stats": st,
+             "library_phase_seconds": {"solve": st["seconds_solve"], "product": st["seconds_product"], "forms": st["seconds_forms"]}}
+    entry["host_loop_over_library_median"] = entry["host_loop_seconds"]["median"] / entry["library_seconds"]["median"]
+    return entry
+
+
 def plain(run: dict) -> dict:
     return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in run.items()}
 
@@ -116,7 +167,17 @@ def main(argv=None) -> None:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-host", action="store_true", help="the library settings alone")
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "stochastic_ab.json")
+    ap.add_argument("--trace", type=int, default=None, metavar="P", help="the trace estimator against a host loop of P applies instead")
     args = ap.parse_args(argv)
+    if args.trace is not None:
+        out = args.out if args.out != ROOT / "profiles" / "stochastic_ab.json" else ROOT / "profiles" / "stochastic_trace.json"
+        result = {"config": {"band": BAND, "probes": args.trace, "seed": 0, "reps": args.reps}, "cases": []}
+        for case, N in (("S30k", 8), ("S30k", 16), ("C160k", 8)):
+            result["cases"].append(trace_ab(case, N, args.trace, args.reps))
+            print(json.dumps(result["cases"][-1]), flush=True)
+            out.parent.mkdir(parents=True, exist_ok=True)
+            out.write_text(json.dumps(result, indent=1) + "\n")
+        return
     settings = {"library": lambda es, N: library(es, N), "library_batch": lambda es, N: library(es, N, True),
                 "library_batch_both": lambda es, N: library(es, N, True, True)}
     if not args.no_host:
