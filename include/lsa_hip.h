@@ -112,6 +112,11 @@ int lsa_spmv_transpose(lsa_ctx *ctx, const lsa_mat *A, int conj, const lsa_vec *
  * of one dtype, no y[z] among the inputs or twice.  Every output's entries are summed by the same 16 lanes in the same order as in
  * lsa_spmv_transpose: each y[z] holds exactly its bits.  LSA_ERR_ARG, naming what differs, for anything else. */
 int lsa_spmv_transpose_batch(lsa_ctx *ctx, int32_t J, const lsa_mat *const *A, int conj, const lsa_vec *const *x, lsa_vec *const *y);
+/* y[z] = A_z x[z], z < J <= 16, in ONE launch for whole square matrices of one pattern, one shape and one dtype (the same matrix may
+ * stand in several slots: Q x_k for all members of a lockstep group); vectors of one dtype, no y[z] among the inputs or twice.  Each
+ * problem walks its rows through the kernel body lsa_spmv runs for this pattern and these scalar types (sub-wave rows, compressed
+ * indices or row groups), so each y[z] holds exactly lsa_spmv's bits.  LSA_ERR_ARG, naming what differs, for anything else. */
+int lsa_spmv_batch(lsa_ctx *ctx, int32_t J, const lsa_mat *const *A, const lsa_vec *const *x, lsa_vec *const *y);
 /* Which kernel lsa_spmv launches for this matrix and vector type (template arguments included) and the bytes that
  * kernel moves per launch: values + column indices (2-byte offsets from the row's first column when the compressed form
  * is in use) + row pointers + one read of x and one write of y.  The numerator of an HBM-roofline fraction.  The name is that
@@ -585,6 +590,31 @@ int lsa_resolvent_basis(lsa_ctx *ctx, const lsa_resolvent *r, int32_t ncols, voi
  * ((beta + i omega) M - A)^-1, and 1 / sigma_1 at a point z is the epsilon-level of the energy-norm pseudospectrum there. */
 int lsa_resolvent_solve(lsa_ctx *ctx, lsa_resolvent *r, const lsa_ks_options *opts, const void *v0, int32_t max_out, double *theta_out,
                         double *gain_out, void *Q_out, void *F_out, double *est_out, lsa_ks_result *result, int64_t *counts);
+/* ---- lockstep sweeps: up to 16 frequencies of one sweep advance together ------------------------------------------------------------
+ * lsa_resolvent_extend for the active members of a group (active NULL: all), member z from its own j0[z] to the common j1 into its own
+ * T[z].  Members whose factors are complex and of one LU analysis (the pattern-only phase redone on the lead's analysis), whose step
+ * runs the fused kernels (LSA_LANCZOS_FUSED) and whose refinement steps are off advance in ROUNDS: one step of every member that
+ * still has one as ONE launch per launch of a solo step -- the adjoint sweeps of all factor sets, C_k^H z_k (the batched transposed
+ * product), Q_f z_k (lsa_spmv_batch's kernel), the forward sweeps, C_k w_k, then per Gram-Schmidt pass the Q_q product, the batched
+ * reduction and the batched update, the last product and reduction and the batched tail -- and ONE copy of all members' slots behind
+ * ONE synchronisation.  The number of basis columns is per member; a member at j1 waits.  A member outside the set (real factors, another
+ * analysis, refinement on), or one whose solve misses ksp_rtol in a round, runs its steps through lsa_resolvent_extend's code inside
+ * this call.  Every member is left with exactly the bits of its own lsa_resolvent_extend.  status[z] / breakdown[z] per member: a
+ * failing member does not stop the others, its text names it; the call returns the first non-zero status.  LSA_ERR_ARG at once, with
+ * a text, for J outside [1, 16], a null handle, a handle or an operator given twice, handles of another context, differing n or ncv,
+ * or weights on more than one pattern.  For tests. */
+int lsa_resolvent_extend_batch(lsa_ctx *ctx, int32_t J, lsa_resolvent *const *r, const uint8_t *active, const int32_t *j0, int32_t j1,
+                               double *const *T, int32_t ldt, int32_t *breakdown, int32_t *status);
+/* lsa_resolvent_solve for J members of a group: the expansions through the rounds above, Ritz values, convergence tests and restarts
+ * per member on the host; nev, tol and max_restarts may differ between the members.  A member that converges or exhausts its restarts
+ * forms its responses and forcings on its own factor set (lsa_resolvent_set_block_forcings honoured) and leaves while the rest go on.
+ * Every array argument has J entries (v0, Q_out, F_out, est_out and their entries may be NULL as in the solo call; counts: NULL or
+ * 4 J entries); every member returns exactly the bits of its own lsa_resolvent_solve.  info (NULL or the record of
+ * lsa_krylov_solve_batch): rounds, launches, read-backs, and per member the steps accepted from rounds and the steps that ran alone,
+ * whose sum is the member's operator applies.  Errors as lsa_resolvent_extend_batch, and F_out[z] without Q_out[z]. */
+int lsa_resolvent_solve_batch(lsa_ctx *ctx, int32_t J, lsa_resolvent *const *r, const lsa_ks_options *const *opts, const void *const *v0,
+                              int32_t max_out, double *const *theta_out, double *const *gain_out, void *const *Q_out, void *const *F_out,
+                              double *const *est_out, lsa_ks_result *results, int64_t *counts, int32_t *status, lsa_ks_batch_info *info);
 
 /* ---- transient growth: optimal energy gains and initial conditions of M q' = A q over a finite horizon ---------------------------
  * One implicit-Euler step (M - dt A) q+ = M q is q+ = -sigma C^-1 M q with C = A - sigma M, sigma = 1 / dt; over N steps the propagator

@@ -84,9 +84,10 @@ def batch_key(eps) -> tuple[tuple | None, str]:
     return key, ""
 
 
-def plan_batches(solvers, max_batch: int = 8, *, bytes_per_problem: int = 0, memory_budget: int = 0) -> BatchPlan:
+def plan_batches(solvers, max_batch: int = 8, *, bytes_per_problem: int = 0, memory_budget: int = 0, keys=None) -> BatchPlan:
     """Groups of ``solvers`` (:class:`Solver.utils.iEpsSolver`) with equal :func:`batch_key`, in input order, at most
-    ``max_batch`` per group -- and at most ``memory_budget // bytes_per_problem`` when both are given."""
+    ``max_batch`` per group -- and at most ``memory_budget // bytes_per_problem`` when both are given.  ``keys``: the results of
+    :func:`batch_key` where the caller has them already (the frequencies of one resolvent sweep share one solver and one key)."""
     if not isinstance(max_batch, (int, np.integer)) or isinstance(max_batch, bool) or not 1 <= max_batch <= MAX_BATCH:
         raise ValueError(f"max_batch must be an integer in [1, {MAX_BATCH}], got {max_batch!r}")
     cap = int(max_batch)
@@ -95,7 +96,7 @@ def plan_batches(solvers, max_batch: int = 8, *, bytes_per_problem: int = 0, mem
     plan = BatchPlan()
     open_groups: dict[tuple, list[int]] = {}
     for i, eps in enumerate(solvers):
-        key, reason = batch_key(eps)
+        key, reason = batch_key(eps) if keys is None else keys[i]
         if key is None:
             plan.alone[i] = reason
             continue

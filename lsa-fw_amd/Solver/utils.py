@@ -713,15 +713,16 @@ class iEpsSolver:
                           "n": n, "sinvert": sinvert, "cayley": self._st_type is iSTType.CAYLEY, "sigma": sigma, "pc_code": pc_code,
                           "levels": levels, "nd_tree": nd_tree, "share": share, "cplx_factors": cplx_factors}
 
-    def redo_pattern_phase(self) -> None:
+    def redo_pattern_phase(self, own_context: bool = False) -> None:
         """The pattern-only LU phase of :meth:`prepare` again, from the shared forest, for a member of a batch group that took
         its context from another: when the previous member's factorisation did not run on the group's analysis (a zero pivot
         made the library analyse again with constraints), the analysis it left in the context is not the one this problem's
-        solo solve would use."""
+        solo solve would use.  ``own_context``: the same for a solver that keeps several factorisations alive on its OWN context
+        (the frequencies of a lockstep resolvent sweep), which shares it with nobody."""
         import lsa_hip
 
         prep = self._prepared
-        if prep is None or prep["nd_tree"] is None or prep["share"] is None:
+        if prep is None or prep.get("nd_tree") is None or (prep.get("share") is None and not own_context):
             return
         nd_tree = prep["nd_tree"]
         try:

@@ -817,37 +817,89 @@ struct TrlStochasticBasis {
     double back(double theta) const { return theta; }
 };
 
+// What the loop keeps per problem: the projected matrix, its eigenvectors, the vectors kept, the counters, the clock, the generator and
+// the result, as KsState does for Krylov-Schur.  trl_solve is the loop over one state; lsa_resolvent_solve_batch the loop over J.
 template <class Basis>
-int trl_solve(lsa_ctx* ctx, Basis& b, const lsa_ks_options* o, const typename Basis::scalar* v0, int32_t max_out, double* theta_out,
-              double* lambda_out, typename Basis::scalar* X_out, double* est_out, lsa_ks_result* result) {
+struct TrlState {
     using S = typename Basis::scalar;
-    const int32_t m = b.m;
-    const int64_t n = b.n;
-    max_out = std::min(max_out, m);
-    const int nev = std::min<int>(o->nev, m);
-    const double keep_fraction = ks_keep_fraction(o);
-    Rng rng = ks_rng(o);
-    std::vector<S> vec((size_t)n);
-    if (v0) memcpy(vec.data(), v0, (size_t)n * sizeof(S));
-    else b.random(rng, vec);
-    LSA_CHECK(b.inject(0, vec.data()));
-    const int ldt = m + 1;
-    std::vector<double> T((size_t)ldt * m, 0.0), Y((size_t)m * m), theta((size_t)m), est((size_t)m), rel((size_t)m), keys((size_t)m);
-    std::vector<int> rank((size_t)m);
-    auto Tm = [&](int r, int c) -> double& { return T[(size_t)c * ldt + r]; };
+    lsa_ctx* ctx;
+    Basis b;
+    const lsa_ks_options* o;
+    int32_t max_out;
+    double *theta_out, *lambda_out;
+    S* X_out;
+    double* est_out;
+    lsa_ks_result* result;
+    int32_t m = 0;
+    int64_t n = 0;
+    int nev = 0, ldt = 0;
+    double keep_fraction = 0.5;
+    Rng rng;
+    std::vector<S> vec;
+    std::vector<double> T, Y, theta, est, rel, keys;
+    std::vector<int> rank;
     int kept = 0, restarts = 0;
     int64_t applies = 0;
-    memset(result, 0, sizeof *result);
     KsClock clk;
-    auto extend = [&](int j, int32_t* bd) { return b.extend(j, T.data(), ldt, bd); };
-    auto inject_random = [&](int j) {
+
+    double& Tm(int r, int c) { return T[(size_t)c * ldt + r]; }
+    // injects the start vector, sizes the host arrays
+    int init(const S* v0) {
+        m = b.m;
+        n = b.n;
+        max_out = std::min(max_out, m);
+        nev = std::min<int>(o->nev, m);
+        keep_fraction = ks_keep_fraction(o);
+        rng = ks_rng(o);
+        vec.resize((size_t)n);
+        if (v0) memcpy(vec.data(), v0, (size_t)n * sizeof(S));
+        else b.random(rng, vec);
+        LSA_CHECK(b.inject(0, vec.data()));
+        ldt = m + 1;
+        T.assign((size_t)ldt * m, 0.0);
+        Y.resize((size_t)m * m);
+        for (auto* a : {&theta, &est, &rel, &keys}) a->resize((size_t)m);
+        rank.resize((size_t)m);
+        memset(result, 0, sizeof *result);
+        return LSA_OK;
+    }
+    int inject_random(int j) {
         b.random(rng, vec);
         return b.inject(j, vec.data());
-    };
-    while (true) {
+    }
+    // the expansion from `kept` to m vectors
+    int expand() {
         clk.start();
-        LSA_CHECK(ks_expand(kept, m, &applies, extend, inject_random));
+        LSA_CHECK(ks_expand(kept, m, &applies, [&](int j, int32_t* bd) { return b.extend(j, T.data(), ldt, bd); }, [&](int j) { return inject_random(j); }));
         clk.lap(clk.expand);
+        return LSA_OK;
+    }
+    // The expansion whose first run of steps a lockstep driver has made (its status and breakdown step, `seconds` of wall time booked
+    // to this problem): what follows a breakdown -- the fresh direction, the rest of the steps -- is the solo code's.  *later_steps:
+    // the steps the solo code ran here after that first run (none unless it broke down).
+    int expand_after(int rc0, int32_t bd0, double seconds, int64_t* later_steps) {
+        bool first = true;
+        const int64_t before = applies + (bd0 < 0 ? m - kept : bd0 - kept + 1);
+        *later_steps = 0;
+        clk.start();
+        LSA_CHECK(ks_expand(kept, m, &applies,
+                            [&](int j, int32_t* bd) {
+                                if (!first) return b.extend(j, T.data(), ldt, bd);
+                                first = false;
+                                LSA_CHECK(rc0);
+                                *bd = bd0;
+                                return (int)LSA_OK;
+                            },
+                            [&](int j) { return inject_random(j); }));
+        clk.lap(clk.expand);
+        clk.expand += seconds;
+        *later_steps = applies - before;
+        return LSA_OK;
+    }
+    // The body of the loop after an expansion: Ritz pairs, convergence test, then either the result (*done) or the restart.
+    int after_expand(bool* done) {
+        *done = false;
+        clk.start();
         const double beta = Tm(m, m - 1);
         for (int c = 0; c < m; ++c)
             for (int r = 0; r < m; ++r) Y[(size_t)c * m + r] = Tm(r, c);
@@ -877,6 +929,7 @@ int trl_solve(lsa_ctx* ctx, Basis& b, const lsa_ks_options* o, const typename Ba
             }
             clk.lap(clk.dense);
             ks_fill_result(result, clk, nconv, nout, restarts, applies, nconv < m ? rel[(size_t)rank[(size_t)nconv]] : 0.0);
+            *done = true;
             return LSA_OK;
         }
         // ---- keep the wanted Ritz vectors and restart: T <- diag(theta_kept) with the spike beta y_{m,i} in row and column knew ----
@@ -896,7 +949,20 @@ int trl_solve(lsa_ctx* ctx, Basis& b, const lsa_ks_options* o, const typename Ba
         }
         kept = knew;
         ++restarts;
+        return LSA_OK;
     }
+};
+
+template <class Basis>
+int trl_solve(lsa_ctx* ctx, Basis& b, const lsa_ks_options* o, const typename Basis::scalar* v0, int32_t max_out, double* theta_out,
+              double* lambda_out, typename Basis::scalar* X_out, double* est_out, lsa_ks_result* result) {
+    TrlState<Basis> st{ctx, b, o, max_out, theta_out, lambda_out, X_out, est_out, result};
+    LSA_CHECK(st.init(v0));
+    for (bool done = false; !done;) {
+        LSA_CHECK(st.expand());
+        LSA_CHECK(st.after_expand(&done));
+    }
+    return LSA_OK;
 }
 
 }  // namespace
@@ -1406,6 +1472,90 @@ int lsa_resolvent_solve(lsa_ctx* ctx, lsa_resolvent* r, const lsa_ks_options* o,
     const int rc = trl_solve(ctx, b, o, (const cplx*)v0, max_out, theta_out, gain_out, (cplx*)Q_out, est_out, result);
     if (counts) resolvent_counts(r, counts);
     return rc;
+}
+
+// The same iteration for J frequencies of one sweep at once: the loop over J states, their expansions through resolvent_extend_batch
+// (one batched launch per launch of a solo step and one read-back per round for the members in lockstep, the solo code for the others),
+// everything after an expansion per member through the state's own method.  A member that is done forms its vectors and forcings on
+// its own factor set and leaves while the rest go on.
+int lsa_resolvent_solve_batch(lsa_ctx* ctx, int32_t J, lsa_resolvent* const* rs, const lsa_ks_options* const* opts, const void* const* v0, int32_t max_out,
+                              double* const* theta_out, double* const* gain_out, void* const* Q_out, void* const* F_out, double* const* est_out,
+                              lsa_ks_result* results, int64_t* counts, int32_t* status, lsa_ks_batch_info* info) {
+    const char* who = "lsa_resolvent_solve_batch";
+    if (!ctx || !rs || !opts || !results || !status) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument", who);
+    LSA_CHECK(resolvent_group_check(ctx, who, J, rs));
+    if (max_out > 0 && (!theta_out || !gain_out)) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: output buffers are required", who);
+    for (int32_t z = 0; z < J; ++z) {
+        if (!opts[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null options (problem %d)", who, z);
+        if (F_out && F_out[z] && !(Q_out && Q_out[z]))
+            return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the forcings are computed from the responses: F_out needs Q_out (problem %d)", who, z);
+    }
+    if (info) memset(info, 0, sizeof *info);
+    typedef TrlState<TrlResolventBasis> State;
+    std::vector<State> st;
+    st.reserve((size_t)J);
+    uint8_t active[kKrylovGroupMax] = {};
+    int32_t kept[kKrylovGroupMax] = {}, bd[kKrylovGroupMax], erc[kKrylovGroupMax];
+    double* Ts[kKrylovGroupMax] = {};
+    int32_t nactive = 0;
+    std::string errs[kKrylovGroupMax];     // the error text of every problem that failed
+    auto leave = [&](int32_t z, int rc) {  // problem z is done: with its result, or with its own error
+        if (rc != LSA_OK && status[z] == LSA_OK) {
+            status[z] = rc;
+            if (errs[z].empty()) errs[z] = ctx->err;  // (resolvent_extend_batch has left the text of its own errors)
+        }
+        nactive -= active[z];
+        active[z] = 0;
+    };
+    for (int32_t z = 0; z < J; ++z) {
+        status[z] = LSA_OK;
+        TrlResolventBasis b{ctx, rs[z], F_out ? (cplx*)F_out[z] : nullptr};
+        (void)resolvent_shape(rs[z], &b.n, &b.m);
+        st.push_back(State{ctx, b, opts[z], max_out, theta_out ? theta_out[z] : nullptr, gain_out ? gain_out[z] : nullptr, Q_out ? (cplx*)Q_out[z] : nullptr,
+                           est_out ? est_out[z] : nullptr, &results[z]});
+        memset(&results[z], 0, sizeof results[z]);
+        active[z] = 1;
+        ++nactive;
+        int rc = ks_check_options(ctx, who, opts[z], max_out, st[(size_t)z].theta_out, st[(size_t)z].lambda_out);
+        if (rc == LSA_OK) rc = st[(size_t)z].init(v0 ? (const cplx*)v0[z] : nullptr);
+        if (rc != LSA_OK) {
+            lsa_name_problem(ctx, z);
+            leave(z, rc);
+        }
+        Ts[z] = st[(size_t)z].T.data();
+    }
+    LanczosGroupBuf gb;
+    int grc = nactive > 0 ? resolvent_group_alloc(ctx, J, rs, &gb) : (memset(&gb, 0, sizeof gb), (int)LSA_OK);
+    while (grc == LSA_OK && nactive > 0) {
+        const int32_t m = st[0].b.m;
+        for (int32_t z = 0; z < J; ++z) kept[z] = st[(size_t)z].kept;
+        const int32_t na = nactive;
+        const double t0 = now_s();
+        grc = resolvent_extend_batch(ctx, &gb, J, rs, active, kept, m, Ts, m + 1, bd, erc, errs, info);
+        if (grc != LSA_OK) break;
+        const double share = (now_s() - t0) / na;
+        for (int32_t z = 0; z < J; ++z) {
+            if (!active[z]) continue;
+            State& s = st[(size_t)z];
+            bool done = false;
+            int64_t later = 0;
+            int rc = s.expand_after(erc[z], bd[z], share, &later);
+            if (info) info->solo_steps[z] += later;  // (what followed a breakdown: the solo code's steps too)
+            if (rc == LSA_OK) rc = s.after_expand(&done);
+            if (rc != LSA_OK && erc[z] == LSA_OK) lsa_name_problem(ctx, z);  // (resolvent_extend_batch has named its own)
+            if (rc != LSA_OK || done) leave(z, rc);
+        }
+    }
+    lanczos_group_free(&gb);
+    if (counts)
+        for (int32_t z = 0; z < J; ++z) resolvent_counts(rs[z], counts + 4 * (size_t)z);
+    if (info && info->rounds > 0) info->launches_per_round = (double)info->launches / (double)info->rounds;
+    if (grc != LSA_OK) {  // the group's own buffers could not be had: an error of every problem that was still going
+        for (int32_t z = 0; z < J; ++z)
+            if (active[z]) status[z] = grc;
+        return grc;
+    }
+    return resolvent_group_status(ctx, J, status, errs);
 }
 
 // Transient growth (growth.hip): the same loop on the real basis of W = Phi+ Phi, a march of 2N solves behind every step; theta_j = G_j,

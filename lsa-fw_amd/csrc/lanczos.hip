@@ -283,10 +283,10 @@ __global__ __launch_bounds__(kLzThreads) void lz_sign_kernel(int64_t n, double* 
 // sums kLzColTile columns over the rows of its chunk into part[c * ldp + chunk].  The workgroups of tile 0 also sum the two inner-solve
 // checks over their rows when chk_part is given: chk_part[4 chunk + 0..3] = |b1 - z1|^2, |b1|^2, |b2 - z2|^2, |b2|^2.  A full tile
 // has its eight 16-byte loads of a row in flight before the first addition.
-__global__ __launch_bounds__(kLzThreads) void rz_dot_kernel(int64_t n, int ncols, int64_t rows_per_block, const cplx* __restrict__ V, int64_t ldv,
-                                                            const cplx* t, const cplx* w, cplx* __restrict__ part, int ldp,
-                                                            const cplx* __restrict__ b1, const cplx* __restrict__ z1, const cplx* __restrict__ b2,
-                                                            const cplx* __restrict__ z2, double* __restrict__ chk_part) {
+// (the body is shared by the solo kernel and the batched one: one copy of the chunking, the tiling and the order of every sum)
+__device__ __forceinline__ void rz_dot_body(int64_t n, int ncols, int64_t rows_per_block, const cplx* __restrict__ V, int64_t ldv, const cplx* t,
+                                            const cplx* w, cplx* __restrict__ part, int ldp, const cplx* __restrict__ b1, const cplx* __restrict__ z1,
+                                            const cplx* __restrict__ b2, const cplx* __restrict__ z2, double* __restrict__ chk_part) {
     __shared__ cplx wsum[4][kLzColTile];
     __shared__ double csum[4][4];
     const int chunk = blockIdx.x;
@@ -352,14 +352,56 @@ __global__ __launch_bounds__(kLzThreads) void rz_dot_kernel(int64_t n, int ncols
     }
 }
 
+__global__ __launch_bounds__(kLzThreads) void rz_dot_kernel(int64_t n, int ncols, int64_t rows_per_block, const cplx* __restrict__ V, int64_t ldv,
+                                                            const cplx* t, const cplx* w, cplx* __restrict__ part, int ldp,
+                                                            const cplx* __restrict__ b1, const cplx* __restrict__ z1, const cplx* __restrict__ b2,
+                                                            const cplx* __restrict__ z2, double* __restrict__ chk_part) {
+    rz_dot_body(n, ncols, rows_per_block, V, ldv, t, w, part, ldp, b1, z1, b2, z2, chk_part);
+}
+
+// The batched forms of the three complex step kernels: up to kRzGroupMax problems of one n in one launch, the problem as the grid's
+// last dimension, its pointers and its number of basis columns by value in the kernel arguments (the members of a lockstep group sit
+// at different j after their restarts).  Each problem runs the solo kernel's body on the solo kernel's grid in the leading dimensions.
+constexpr int kRzGroupMax = 16;
+struct RzDotArgs {
+    const cplx *V[kRzGroupMax], *t[kRzGroupMax], *w[kRzGroupMax];
+    cplx* part[kRzGroupMax];
+    const cplx *b1[kRzGroupMax], *z1[kRzGroupMax], *b2[kRzGroupMax], *z2[kRzGroupMax];
+    double* chk_part[kRzGroupMax];
+    int ncols[kRzGroupMax];
+};
+struct RzUpdateArgs {
+    const cplx *V[kRzGroupMax], *part[kRzGroupMax];
+    cplx *w[kRzGroupMax], *h_out[kRzGroupMax];
+    int ncols[kRzGroupMax];
+};
+struct RzTailArgs {
+    const cplx *w[kRzGroupMax], *t[kRzGroupMax], *part[kRzGroupMax];
+    cplx *vnext[kRzGroupMax], *rhs_next[kRzGroupMax];
+    const double* chk_part[kRzGroupMax];
+    double* out[kRzGroupMax];
+};
+// (the kernel arguments of a launch are limited to 4096 bytes; the scalars beside a record take under 64)
+static_assert(sizeof(RzDotArgs) + 64 <= 4096 && sizeof(RzUpdateArgs) + 64 <= 4096 && sizeof(RzTailArgs) + 64 <= 4096,
+              "the arguments of a batched step kernel exceed the kernel-argument limit");
+static_assert(kRzGroupMax == kKrylovGroupMax, "a lockstep group of the complex basis fills the per-problem arrays of lsa_ks_batch_info");
+
+// grid (chunks, column tiles of the member with most columns, problems): a workgroup whose tile lies beyond its problem's ncols + 1
+// columns returns before touching memory
+__global__ __launch_bounds__(kLzThreads) void rz_dot_batch_kernel(int64_t n, int64_t rows_per_block, int64_t ldv, int ldp, RzDotArgs a) {
+    const int z = blockIdx.z;
+    const int ncols = a.ncols[z];
+    if ((int)blockIdx.y * kLzColTile >= ncols + 1) return;
+    rz_dot_body(n, ncols, rows_per_block, a.V[z], ldv, a.t[z], a.w[z], a.part[z], ldp, a.b1[z], a.z1[z], a.b2[z], a.z2[z], a.chk_part[z]);
+}
+
 // w -= V h for the columns 0..ncols-1.  The prologue finishes h from the partial sums (lz_finish_sum: every workgroup gets the same
 // bits; wave q takes the columns q, q + 4, ...); workgroup 0 writes h to h_out for the host.  Then a thread per row, the rows of a
 // workgroup strided over the grid: eight entries of the row are requested at a time -- the first eight ahead of the prologue, which
 // does not depend on them -- and added column after column.  The dynamic LDS holds h alone (no static LDS in front of it: 16-byte
 // aligned entries).
-__global__ __launch_bounds__(kLzThreads) void rz_update_kernel(int64_t n, int ncols, const cplx* __restrict__ V, int64_t ldv,
-                                                               const cplx* __restrict__ part, int nchunks, int ldp, cplx* w,
-                                                               cplx* __restrict__ h_out) {
+__device__ __forceinline__ void rz_update_body(int64_t n, int ncols, const cplx* __restrict__ V, int64_t ldv, const cplx* __restrict__ part, int nchunks,
+                                               int ldp, cplx* w, cplx* __restrict__ h_out) {
     extern __shared__ __attribute__((aligned(16))) char rz_dyn[];
     cplx* hs = reinterpret_cast<cplx*>(rz_dyn);  // ncols coefficients
     const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
@@ -393,13 +435,24 @@ __global__ __launch_bounds__(kLzThreads) void rz_update_kernel(int64_t n, int nc
     }
 }
 
+__global__ __launch_bounds__(kLzThreads) void rz_update_kernel(int64_t n, int ncols, const cplx* __restrict__ V, int64_t ldv,
+                                                               const cplx* __restrict__ part, int nchunks, int ldp, cplx* w,
+                                                               cplx* __restrict__ h_out) {
+    rz_update_body(n, ncols, V, ldv, part, nchunks, ldp, w, h_out);
+}
+
+// grid (row workgroups, problems); the dynamic LDS holds the coefficients of the member with most columns
+__global__ __launch_bounds__(kLzThreads) void rz_update_batch_kernel(int64_t n, int64_t ldv, int nchunks, int ldp, RzUpdateArgs a) {
+    const int z = blockIdx.y;
+    rz_update_body(n, a.ncols[z], a.V[z], ldv, a.part[z], nchunks, ldp, a.w[z], a.h_out[z]);
+}
+
 // From the partial sums of w^H t (part[0..nchunks), lz_finish_sum): beta^2 = its real part, then v_next = w / beta and
 // rhs_next = t / beta.  Workgroup 0 leaves beta^2, the imaginary part (rounding) and the four sums of the two inner-solve checks
 // (chk_part, nchk quadruples) in out[0..6).  A beta^2 that is not positive and finite scales by zero: the host reads it from the slot
 // and stops.
-__global__ __launch_bounds__(kLzThreads) void rz_tail_kernel(int64_t n, const cplx* w, const cplx* t, const cplx* __restrict__ part, int nchunks,
-                                                             cplx* vnext, cplx* rhs_next, const double* __restrict__ chk_part, int nchk,
-                                                             double* __restrict__ out) {
+__device__ __forceinline__ void rz_tail_body(int64_t n, const cplx* w, const cplx* t, const cplx* __restrict__ part, int nchunks, cplx* vnext,
+                                             cplx* rhs_next, const double* __restrict__ chk_part, int nchk, double* __restrict__ out) {
     __shared__ double b2s;
     if (threadIdx.x < 64) {
         const cplx a = lz_finish_sum(part, nchunks, threadIdx.x);
@@ -430,6 +483,18 @@ __global__ __launch_bounds__(kLzThreads) void rz_tail_kernel(int64_t n, const cp
         rz_st(vnext + i, s_mul(inv, wi));
         rz_st(rhs_next + i, s_mul(inv, ti));
     }
+}
+
+__global__ __launch_bounds__(kLzThreads) void rz_tail_kernel(int64_t n, const cplx* w, const cplx* t, const cplx* __restrict__ part, int nchunks,
+                                                             cplx* vnext, cplx* rhs_next, const double* __restrict__ chk_part, int nchk,
+                                                             double* __restrict__ out) {
+    rz_tail_body(n, w, t, part, nchunks, vnext, rhs_next, chk_part, nchk, out);
+}
+
+// grid (row workgroups, problems)
+__global__ __launch_bounds__(kLzThreads) void rz_tail_batch_kernel(int64_t n, int nchunks, int nchk, RzTailArgs a) {
+    const int z = blockIdx.y;
+    rz_tail_body(n, a.w[z], a.t[z], a.part[z], nchunks, a.vnext[z], a.rhs_next[z], a.chk_part[z], nchk, a.out[z]);
 }
 
 // the fused kernels unless LSA_LANCZOS_FUSED=0 (read once per process, like LSA_KRYLOV_FUSED): then k_multi_dot + k_multi_axpy
@@ -640,6 +705,49 @@ int lz_solve_judge(lsa_ctx* ctx, void* self, int32_t j, const lanczos_sums* s) {
     return verdict;
 }
 
+// ---- what follows a step's read-back, over the basis' own host slot: one copy for the solo loop and the lockstep rounds --------------
+// the operator's judgement of the step's checked solves.  0: accepted (and booked), 1: do the step again, -1: failed (the error is set)
+int lz_judge_step(lsa_ctx* ctx, lsa_lanczos* l, int32_t j) {
+    const LzSlot S = lz_slot(l);
+    const double* h = l->hslot.data();
+    lanczos_sums sums[2];
+    for (int k = 0; k < lz_nchecks(l); ++k)
+        sums[k] = lanczos_sums{std::sqrt(h[S.chk + 2 * k]), std::sqrt(h[S.chk + 2 * k + 1]), l->chk[k].refined ? std::sqrt(h[S.xnorm + k]) : 0.0};
+    return l->hook->judge(ctx, l->hook->self, j, sums);
+}
+
+// alpha_j and beta_j of an accepted step into T, the definiteness check and the breakdown rule; the right-hand side buffers change roles
+int lz_accept_step(lsa_ctx* ctx, lsa_lanczos* l, int32_t j, double* T, int32_t ldt, bool* broke_out) {
+    const bool cx = l->dtype == LSA_C128;
+    const size_t sc = cx ? 2 : 1;  // doubles per scalar
+    const LzSlot S = lz_slot(l);
+    const double* h = l->hslot.data();
+    *broke_out = false;
+    // Re h_i of both passes.  alpha_j = Re h_j: OP is self-adjoint in the inner product, the imaginary part is rounding and is dropped
+    auto re = [&](int32_t i) { return h[sc * (size_t)i] + h[S.h + sc * (size_t)i]; };
+    const double alpha = re(j);
+    const double b2 = h[S.out];
+    if (!std::isfinite(alpha) || !std::isfinite(b2))
+        return lsa_set_error(ctx, LSA_ERR_NONFINITE, "%s: non-finite recurrence coefficient at step %d", cx ? "resolvent" : "Lanczos", j);
+    // what is left of w after both passes, against the size of what was taken out of it (the rule of the general loop's columns)
+    double colmax = std::fabs(alpha);
+    for (int32_t i = 0; i < j; ++i)
+        colmax = std::max(colmax, cx ? std::hypot(re(i), h[2 * (size_t)i + 1] + h[S.h + 2 * (size_t)i + 1]) : std::fabs(re(i)));
+    const double thr = 1e-14 * std::max(colmax, 1e-300);
+    if (b2 < -thr * thr)
+        return lsa_set_error(ctx, LSA_ERR_ARG, "%s_extend: w^%s M w = %.3e at step %d: M is not positive %s on the Krylov space", l->who, cx ? "H" : "T", b2, j,
+                             cx ? "semidefinite" : "definite");
+    const double beta = b2 > 0.0 ? std::sqrt(b2) : 0.0;
+    const bool broke = beta <= thr;
+    T[(size_t)j * ldt + j] = alpha;
+    T[(size_t)j * ldt + j + 1] = broke ? 0.0 : beta;
+    if (j + 1 < l->ncv && j + 1 < ldt) T[(size_t)(j + 1) * ldt + j] = broke ? 0.0 : beta;
+    l->cur ^= 1;
+    l->rhs_for = broke ? -1 : j + 1;
+    *broke_out = broke;
+    return LSA_OK;
+}
+
 }  // namespace
 
 int lanczos_create_basis(lsa_ctx* ctx, lsa_op* op, int32_t ncv, int dtype, const char* who, lsa_lanczos** out) {
@@ -785,11 +893,8 @@ int lsa_lanczos_extend(lsa_ctx* ctx, lsa_lanczos* l, int32_t j0, int32_t j1, dou
     if (!l->hook) return lsa_set_error(ctx, LSA_ERR_ARG, "%s_extend: the basis has no operator behind its step", l->who);
     if (breakdown) *breakdown = -1;
     const double t0 = now_s();
-    const bool cx = l->dtype == LSA_C128;
-    const size_t sc = cx ? 2 : 1;  // doubles per scalar
     const int nchk = lz_nchecks(l);
     const LzSlot S = lz_slot(l);
-    const double* h = l->hslot.data();
     int rc = LSA_OK;
     for (int32_t j = j0; j < j1 && rc == LSA_OK; ++j) {
         if (l->rhs_for != j) {  // (after lsa_lanczos_basis users, a restart that moved another column here, or the standard problem's first step)
@@ -806,10 +911,7 @@ int lsa_lanczos_extend(lsa_ctx* ctx, lsa_lanczos* l, int32_t j0, int32_t j1, dou
             if (rc == LSA_OK) rc = lz_orth_tail(ctx, l, j + 1, j + 1, true);
             if (rc == LSA_OK) rc = lz_read_slot(ctx, l);
             if (rc != LSA_OK) break;
-            lanczos_sums sums[2];
-            for (int k = 0; k < nchk; ++k)
-                sums[k] = lanczos_sums{std::sqrt(h[S.chk + 2 * k]), std::sqrt(h[S.chk + 2 * k + 1]), l->chk[k].refined ? std::sqrt(h[S.xnorm + k]) : 0.0};
-            const int verdict = l->hook->judge(ctx, l->hook->self, j, sums);
+            const int verdict = lz_judge_step(ctx, l, j);
             if (verdict == 0) break;
             if (verdict < 0) {  // (the operator has set the error)
                 rc = LSA_ERR_DIVERGED;
@@ -817,33 +919,10 @@ int lsa_lanczos_extend(lsa_ctx* ctx, lsa_lanczos* l, int32_t j0, int32_t j1, dou
             }
         }
         if (rc != LSA_OK) break;
-        // Re h_i of both passes.  alpha_j = Re h_j: OP is self-adjoint in the inner product, the imaginary part is rounding and is dropped
-        auto re = [&](int32_t i) { return h[sc * (size_t)i] + h[S.h + sc * (size_t)i]; };
-        const double alpha = re(j);
-        const double b2 = h[S.out];
-        if (!std::isfinite(alpha) || !std::isfinite(b2)) {
-            rc = lsa_set_error(ctx, LSA_ERR_NONFINITE, "%s: non-finite recurrence coefficient at step %d", cx ? "resolvent" : "Lanczos", j);
-            break;
-        }
-        // what is left of w after both passes, against the size of what was taken out of it (the rule of the general loop's columns)
-        double colmax = std::fabs(alpha);
-        for (int32_t i = 0; i < j; ++i)
-            colmax = std::max(colmax, cx ? std::hypot(re(i), h[2 * (size_t)i + 1] + h[S.h + 2 * (size_t)i + 1]) : std::fabs(re(i)));
-        const double thr = 1e-14 * std::max(colmax, 1e-300);
-        if (b2 < -thr * thr) {
-            rc = lsa_set_error(ctx, LSA_ERR_ARG, "%s_extend: w^%s M w = %.3e at step %d: M is not positive %s on the Krylov space", l->who, cx ? "H" : "T", b2, j,
-                               cx ? "semidefinite" : "definite");
-            break;
-        }
-        const double beta = b2 > 0.0 ? std::sqrt(b2) : 0.0;
-        const bool broke = beta <= thr;
-        T[(size_t)j * ldt + j] = alpha;
-        T[(size_t)j * ldt + j + 1] = broke ? 0.0 : beta;
-        if (j + 1 < l->ncv && j + 1 < ldt) T[(size_t)(j + 1) * ldt + j] = broke ? 0.0 : beta;
-        l->cur ^= 1;
-        l->rhs_for = j + 1;
+        bool broke = false;
+        rc = lz_accept_step(ctx, l, j, T, ldt, &broke);
+        if (rc != LSA_OK) break;
         if (broke) {
-            l->rhs_for = -1;
             if (breakdown) *breakdown = j;
             break;
         }
@@ -851,6 +930,210 @@ int lsa_lanczos_extend(lsa_ctx* ctx, lsa_lanczos* l, int32_t j0, int32_t j1, dou
     l->P.st->seconds_solve += now_s() - t0;
     return rc;
 }
+
+}  // extern "C"
+
+// ---- lockstep expansion of a group of complex bases (lsa_resolvent_extend_batch, lsa_resolvent_solve_batch) -------------------------
+// Bases of one n and ncv whose operator the group operator can queue for several members at once advance together: a round is one
+// step of every member that still has one -- the group operator's batched launches for w_z = OP v_j(z), then per pass ONE product with
+// the members' Q, ONE rz_dot_batch_kernel and ONE rz_update_batch_kernel, the last product and reduction, ONE rz_tail_batch_kernel -- and
+// ONE copy of all members' slots (they lie side by side in the group's buffer) behind ONE synchronisation.  The members sit at
+// different j; one that has reached j1 waits.  What follows the read-back is lz_judge_step and lz_accept_step per member over its own
+// slot, the code of lsa_lanczos_extend.  A member that is not eligible, or whose solve misses ksp_rtol in a round (its operator has
+// switched the refinement step on; its right-hand side of the step is intact), runs the rest of its steps through lsa_lanczos_extend
+// from there, exactly as its solo expansion does.
+int lanczos_group_alloc(lsa_ctx* ctx, int32_t J, lsa_lanczos* const* ls, LanczosGroupBuf* gb) {
+    memset(gb, 0, sizeof *gb);
+    gb->J = J;
+    gb->slot_doubles = lz_slot(ls[0]).doubles;
+    const size_t bytes = (size_t)J * gb->slot_doubles * sizeof(double);
+    LSA_HIP_ALLOC(ctx, hipMalloc((void**)&gb->slots, bytes));
+    // (the cells no kernel writes -- the unfused form's scalar, the refined solves' norms -- travel with the copy and are never looked at)
+    LSA_HIP_CHECK(ctx, hipMemsetAsync(gb->slots, 0, bytes, ctx->stream));
+    return LSA_OK;
+}
+
+void lanczos_group_free(LanczosGroupBuf* gb) {
+    if (gb->slots) (void)hipFree(gb->slots);
+    memset(gb, 0, sizeof *gb);
+}
+
+int lanczos_extend_batch(lsa_ctx* ctx, LanczosGroupBuf* gb, lsa_lanczos* const* ls, const lanczos_group_operator* gop, const uint8_t* active,
+                         const int32_t* j0, int32_t j1, double* const* T, int32_t ldt, int32_t* breakdown, int32_t* status, std::string* errs,
+                         lsa_ks_batch_info* info) {
+    const int32_t J = gb->J;
+    auto fail = [&](int32_t z, int rc) {  // member z stops with its own status and its own text, which names it
+        status[z] = rc;
+        lsa_name_problem(ctx, z);
+        errs[z] = ctx->err;
+    };
+    int32_t jc[kRzGroupMax];  // the members' cursors
+    bool lock[kRzGroupMax];   // still asked for the lockstep set
+    int32_t lead = -1;
+    for (int32_t z = 0; z < J; ++z) {
+        jc[z] = j0[z];
+        lock[z] = false;
+        if (!active[z]) continue;
+        breakdown[z] = -1;
+        status[z] = LSA_OK;
+        lsa_lanczos* l = ls[z];
+        if (j0[z] < 0 || j1 < j0[z] || j1 > l->ncv || ldt < j1 + 1) {
+            (void)lsa_set_error(ctx, LSA_ERR_ARG, "%s_extend: bad step range [%d, %d) for ncv %d", l->who, j0[z], j1, l->ncv);
+            fail(z, LSA_ERR_ARG);
+            continue;
+        }
+        bool in = l->dtype == LSA_C128 && lz_fused() && l->Q && l->hook && !l->hook->read_back && l->hslot.size() == gb->slot_doubles;
+        if (in && lead >= 0) in = l->n == ls[lead]->n && l->ncv == ls[lead]->ncv;
+        if (in) in = gop->eligible(gop->self, z, lead);
+        if (in && lead < 0) lead = z;
+        lock[z] = in;
+    }
+    const size_t sd = gb->slot_doubles;
+    int64_t rows_per_block = 0;
+    const int64_t n = lead >= 0 ? ls[lead]->n : 0;
+    const int nchunks = lead >= 0 ? dot_chunks(n, &rows_per_block) : 0;
+    int rc = lead >= 0 ? lsa_ensure_scratch(ctx, 0, (size_t)J * sd * sizeof(double)) : (int)LSA_OK;
+    while (rc == LSA_OK) {
+        // ---- the members of this round
+        int32_t R = 0, idx[kRzGroupMax];
+        for (int32_t z = 0; z < J; ++z)
+            if (active[z] && lock[z] && status[z] == LSA_OK && breakdown[z] < 0 && jc[z] < j1) idx[R++] = z;
+        if (R == 0) break;
+        const double t0 = now_s();
+        int32_t launches = 0;
+        const lsa_mat* Qs[kRzGroupMax];
+        const void *rhs[kRzGroupMax], *wc[kRzGroupMax];
+        void *w[kRzGroupMax], *zz[kRzGroupMax], *t[kRzGroupMax];
+        lanczos_check* chk[kRzGroupMax];
+        int maxcols = 0;
+        for (int32_t r = 0; r < R && rc == LSA_OK; ++r) {
+            lsa_lanczos* l = ls[idx[r]];
+            const int32_t j = jc[idx[r]];
+            const LzSlot S = lz_slot(l);
+            if (l->rhs_for != j) {  // (as in the solo loop: a restart moved another column here)
+                rc = lz_mass(ctx, l, lz_col(l, j), l->rhs[l->cur]);
+                l->rhs_for = j;
+                if (rc == LSA_OK) ++launches;
+            }
+            for (int k = 0; k < 2; ++k) l->chk[k] = lanczos_check{nullptr, nullptr, false, l->slot + S.xnorm + k};
+            Qs[r] = l->Q;
+            rhs[r] = l->rhs[l->cur];
+            w[r] = l->w, wc[r] = l->w;
+            zz[r] = l->z;
+            t[r] = l->t;
+            chk[r] = l->chk;
+            maxcols = std::max(maxcols, (int)j + 1);
+        }
+        if (rc == LSA_OK) rc = gop->enqueue(ctx, gop->self, R, idx, rhs, w, zz, chk, &launches);
+        // ---- two passes of Gram-Schmidt in the members' inner products, the last product and reduction, the tail
+        RzDotArgs da;
+        RzUpdateArgs ua;
+        RzTailArgs ta;
+        memset(&da, 0, sizeof da);
+        memset(&ua, 0, sizeof ua);
+        memset(&ta, 0, sizeof ta);
+        for (int32_t r = 0; r < R; ++r) {
+            lsa_lanczos* l = ls[idx[r]];
+            const int32_t j = jc[idx[r]];
+            const LzSlot S = lz_slot(l);
+            double* slot = gb->slots + (size_t)idx[r] * sd;
+            da.V[r] = ua.V[r] = (const cplx*)l->V;
+            da.t[r] = ta.t[r] = (const cplx*)l->t;
+            da.w[r] = ta.w[r] = (const cplx*)l->w;
+            ua.w[r] = (cplx*)l->w;
+            da.part[r] = (cplx*)l->part;
+            ua.part[r] = ta.part[r] = (const cplx*)l->part;
+            da.b1[r] = (const cplx*)l->chk[0].b, da.z1[r] = (const cplx*)l->chk[0].z;
+            da.b2[r] = (const cplx*)l->chk[1].b, da.z2[r] = (const cplx*)l->chk[1].z;
+            da.chk_part[r] = l->chk_part;
+            ta.chk_part[r] = l->chk_part;
+            da.ncols[r] = ua.ncols[r] = j + 1;
+            ta.vnext[r] = (cplx*)lz_col(l, j + 1);
+            ta.rhs_next[r] = (cplx*)l->rhs[l->cur ^ 1];
+            ta.out[r] = slot + S.out;
+        }
+        const dim3 threads(kLzThreads);
+        for (int pass = 0; pass < 2 && rc == LSA_OK; ++pass) {
+            rc = k_spmv_batch(ctx, R, Qs, LSA_C128, wc, t);
+            if (rc != LSA_OK) break;
+            for (int32_t r = 0; r < R; ++r) {
+                ++ls[idx[r]]->P.st->spmv_calls;
+                ua.h_out[r] = (cplx*)(gb->slots + (size_t)idx[r] * sd + (size_t)pass * lz_slot(ls[idx[r]]).h);
+                if (pass == 1) da.chk_part[r] = nullptr;  // (the checks ride in the first reduction)
+            }
+            hipLaunchKernelGGL(rz_dot_batch_kernel, dim3(nchunks, (maxcols + 1 + kLzColTile - 1) / kLzColTile, R), threads, 0, ctx->stream, n, rows_per_block, n,
+                               nchunks, da);
+            hipLaunchKernelGGL(rz_update_batch_kernel, dim3(lz_grid(ctx, n, 2), R), threads, (size_t)maxcols * sizeof(cplx), ctx->stream, n, n, nchunks, nchunks, ua);
+            launches += 3;  // (counted as they are queued: a round that fails on the way has launched what it has launched)
+        }
+        if (rc == LSA_OK) rc = k_spmv_batch(ctx, R, Qs, LSA_C128, wc, t);
+        bool queued = false;  // the whole round, tail included
+        if (rc == LSA_OK) {
+            for (int32_t r = 0; r < R; ++r) da.ncols[r] = 0, da.chk_part[r] = nullptr, ++ls[idx[r]]->P.st->spmv_calls;
+            hipLaunchKernelGGL(rz_dot_batch_kernel, dim3(nchunks, 1, R), threads, 0, ctx->stream, n, rows_per_block, n, nchunks, da);
+            hipLaunchKernelGGL(rz_tail_batch_kernel, dim3(lz_grid(ctx, n, 8), R), threads, 0, ctx->stream, n, nchunks, nchunks, ta);
+            launches += 3;
+            rc = lsa_check_launch(ctx, "resolvent step (lockstep)");
+            queued = rc == LSA_OK;
+        }
+        // ---- ONE copy of the group's slots, ONE synchronisation
+        if (rc == LSA_OK && hipMemcpyAsync(ctx->pinned, gb->slots, (size_t)J * sd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            rc = lsa_set_error(ctx, LSA_ERR_HIP, "%s: read-back of a lockstep round failed", ls[lead]->who);
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == LSA_OK)
+            rc = lsa_set_error(ctx, LSA_ERR_HIP, "%s: a lockstep round failed on the device", ls[lead]->who);
+        if (info) {
+            if (queued) ++info->rounds, ++info->periods;
+            info->launches += launches;
+        }
+        if (rc != LSA_OK) {  // the device work of the whole round is lost: an error of every member of it
+            const std::string text = ctx->err;
+            for (int32_t r = 0; r < R; ++r) {
+                ctx->err = text;
+                fail(idx[r], rc);
+            }
+            rc = LSA_OK;
+            break;
+        }
+        const double share = (now_s() - t0) / R;
+        for (int32_t r = 0; r < R; ++r) {
+            const int32_t z = idx[r];
+            lsa_lanczos* l = ls[z];
+            memcpy(l->hslot.data(), (const double*)ctx->pinned + (size_t)z * sd, sd * sizeof(double));
+            l->P.st->seconds_solve += share;
+            const int verdict = lz_judge_step(ctx, l, jc[z]);
+            if (verdict > 0) {  // (the operator has switched a refinement step on: this step and the later ones run alone)
+                lock[z] = false;
+                continue;
+            }
+            if (verdict < 0) {
+                fail(z, LSA_ERR_DIVERGED);
+                continue;
+            }
+            bool broke = false;
+            const int arc = lz_accept_step(ctx, l, jc[z], T[z], ldt, &broke);
+            if (arc != LSA_OK) {
+                fail(z, arc);
+                continue;
+            }
+            if (info) ++info->lockstep_steps[z];
+            if (broke) breakdown[z] = jc[z];
+            ++jc[z];
+        }
+    }
+    if (rc != LSA_OK) return rc;  // (the pinned buffer could not be had: nothing was queued)
+    // ---- whatever is left of each expansion, through the solo code
+    for (int32_t z = 0; z < J; ++z) {
+        if (!active[z] || status[z] != LSA_OK || breakdown[z] >= 0 || jc[z] >= j1) continue;
+        int32_t bd = -1;
+        const int xrc = lsa_lanczos_extend(ctx, ls[z], jc[z], j1, T[z], ldt, &bd);
+        breakdown[z] = bd;
+        if (xrc != LSA_OK) fail(z, xrc);
+        else if (info) info->solo_steps[z] += (bd >= 0 ? bd + 1 : j1) - jc[z];
+    }
+    return LSA_OK;
+}
+
+extern "C" {
 
 int lsa_lanczos_basis(lsa_ctx* ctx, const lsa_lanczos* l, int32_t ncols, double* host_V) {
     if (!ctx || !l || !host_V) return lsa_set_error(ctx, LSA_ERR_ARG, "%s_basis: null argument", l ? l->who : "lsa_lanczos");

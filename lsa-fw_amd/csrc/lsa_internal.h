@@ -283,6 +283,9 @@ int k_transpose_index(lsa_ctx* ctx, const lsa_mat* A, const TransposeIndex** out
 // k_spmv_transpose's bits.  LSA_ERR_ARG naming what differs unless n, ncols, nnz and dtype agree and the matrices share the pattern
 // object or their index arrays, or have equal host patterns
 int k_spmv_transpose_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* mats, int conj, int xdtype, const void* const* xs, void* const* ys);
+// ys[z] = mats[z] xs[z], z < J <= 16, in one launch on the index arrays of one pattern (whole square matrices; the same matrix may
+// stand in several slots); each ys[z] holds k_spmv's bits.  LSA_ERR_ARG naming what differs, as k_spmv_transpose_batch
+int k_spmv_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* mats, int xdtype, const void* const* xs, void* const* ys);
 // `to` has `from`'s pattern and scalar type (lsa_csr_window): it borrows the row groups and compressed indices k_spmv uses for `from`
 // (built here where `from` has not met a product yet), so that both take one kernel form; owns_extras = false, `from` outlives `to`
 void spmv_share_extras(const lsa_mat* from, lsa_mat* to);
@@ -483,6 +486,33 @@ struct lanczos_operator {
 // hook outlives the basis' steps; null: the default.  LSA_ERR_ARG where nchecks is not what the basis' kernels take.
 int lanczos_set_operator(lsa_ctx* ctx, lsa_lanczos* l, const lanczos_operator* hook);
 
+// ---- the lockstep expansion of a group of complex bases (lanczos.hip), driven by lsa_resolvent_solve_batch (dense.hip) -------------
+// The operator of a group: it says which members it can queue together and queues w = OP v_j for R of them in batched launches.
+struct lanczos_group_operator {
+    void* self;
+    // whether member z may advance in lockstep in this expansion, beside member `lead` (-1: z would lead)
+    bool (*eligible)(void* self, int32_t z, int32_t lead);
+    // queue w[r] = OP v from rhs[r] for the members idx[0..R) (rhs stays intact; z[r]: a work vector) and fill chk[r][0..2); every
+    // member's own judge follows the read-back.  Adds its kernel launches to *launches.
+    int (*enqueue)(lsa_ctx* ctx, void* self, int32_t R, const int32_t* idx, const void* const* rhs, void* const* w, void* const* z,
+                   lanczos_check* const* chk, int32_t* launches);
+};
+struct LanczosGroupBuf {  // the members' slots side by side: one copy reads a round back
+    int32_t J;
+    size_t slot_doubles;
+    double* slots;
+};
+int lanczos_group_alloc(lsa_ctx* ctx, int32_t J, lsa_lanczos* const* ls, LanczosGroupBuf* gb);
+void lanczos_group_free(LanczosGroupBuf* gb);
+// lsa_lanczos_extend(ls[z], j0[z], j1, T[z], ldt) for every active member z, in lockstep where the basis and the group operator allow;
+// status[z] and breakdown[z] per member (an error stops that member alone; its text, naming the problem, goes to errs[z]); info:
+// counters, or null.  Every member is left with the bits of its own lsa_lanczos_extend.
+int lanczos_extend_batch(lsa_ctx* ctx, LanczosGroupBuf* gb, lsa_lanczos* const* ls, const lanczos_group_operator* gop, const uint8_t* active,
+                         const int32_t* j0, int32_t j1, double* const* T, int32_t ldt, int32_t* breakdown, int32_t* status, std::string* errs,
+                         lsa_ks_batch_info* info);
+// whether B has A's pattern: the index arrays or the pattern object shared, or equal host copies (spmv.hip)
+bool k_spmv_same_pattern(const lsa_mat* A, const lsa_mat* B);
+
 // ---- the resolvent iteration (resolvent.hip): the basis with complex scalars and the step W = C^-1 Q_f C^-H Q_q behind it; the loop
 // is the one of lsa_lanczos_solve (dense.hip), which reaches the handle through these pieces --------------------------------------
 int resolvent_shape(const lsa_resolvent* r, int64_t* n, int32_t* ncv);
@@ -496,6 +526,14 @@ int resolvent_ritz_vectors(lsa_ctx* ctx, lsa_resolvent* r, int32_t m, int32_t nv
 int resolvent_forcings(lsa_ctx* ctx, lsa_resolvent* r, int32_t nvec, const double* gain, cplx* F);
 // accepted adjoint solves, accepted forward solves, and how many of each carried the refinement step
 void resolvent_counts(const lsa_resolvent* r, int64_t counts[4]);
+// A lockstep group (lsa_resolvent_extend_batch, lsa_resolvent_solve_batch): the argument errors of a group -- J outside [1, 16], a null
+// or foreign handle, a handle or an operator given twice, other shapes, weights on more than one pattern --, its buffers, the
+// expansion of every active member (lanczos_extend_batch behind the group's operator), and the context's text from the members' errors
+int resolvent_group_check(lsa_ctx* ctx, const char* who, int32_t J, lsa_resolvent* const* rs);
+int resolvent_group_alloc(lsa_ctx* ctx, int32_t J, lsa_resolvent* const* rs, LanczosGroupBuf* gb);
+int resolvent_extend_batch(lsa_ctx* ctx, LanczosGroupBuf* gb, int32_t J, lsa_resolvent* const* rs, const uint8_t* active, const int32_t* j0, int32_t j1,
+                           double* const* T, int32_t ldt, int32_t* breakdown, int32_t* status, std::string* errs, lsa_ks_batch_info* info);
+int resolvent_group_status(lsa_ctx* ctx, int32_t J, const int32_t* status, const std::string* errs);
 
 // ---- transient growth (growth.hip): the real basis of an lsa_lanczos with a march of 2N solves behind every step; the loop is the
 // one of lsa_lanczos_solve (dense.hip), which reaches the handle through these pieces ------------------------------------------------

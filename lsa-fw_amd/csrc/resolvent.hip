@@ -283,6 +283,106 @@ int resolvent_forcings(lsa_ctx* ctx, lsa_resolvent* l, int32_t nvec, const doubl
     return lanczos_ritz_to_host(ctx, l->lz, nvec, F);
 }
 
+// ---- the operator of a lockstep group: W_z = C_z^-1 Q_f C_z^-H for several frequencies of one sweep in batched launches ---------------
+// A member is in while its factors are complex and of the lead's analysis (nd_batch_compatible) and neither direction carries its
+// refinement step; the round is rz_hook_enqueue's sequence with one launch where it has one: the adjoint sweeps of all members' factor
+// sets (ndlu_solve_run on a batch of sets, trans = 2), C_z^H z_z (k_spmv_transpose_batch), Q_f z_z (k_spmv_batch), the forward sweeps,
+// C_z w_z (k_spmv_batch).  Every piece leaves its solo bits per member, and each member's own rz_hook_judge follows the read-back.
+namespace {
+
+bool rz_group_eligible(void* self, int32_t z, int32_t lead) {
+    lsa_resolvent* const* rs = (lsa_resolvent* const*)self;
+    const lsa_resolvent* l = rs[z];
+    if (l->P.Kfac->dtype != LSA_C128 || l->refine_adj || l->refine_fwd) return false;
+    return lead < 0 || nd_batch_compatible(rs[lead]->P.nd, l->P.nd);
+}
+
+int rz_group_enqueue(lsa_ctx* ctx, void* self, int32_t R, const int32_t* idx, const void* const* rhs, void* const* w, void* const* cf,
+                     lanczos_check* const* chk, int32_t* launches) {
+    lsa_resolvent* const* rs = (lsa_resolvent* const*)self;
+    lsa_ndlu* nd[kKrylovGroupMax];
+    const lsa_mat *C[kKrylovGroupMax], *Qf[kKrylovGroupMax];
+    const void *za_c[kKrylovGroupMax], *tm_c[kKrylovGroupMax], *w_c[kKrylovGroupMax];
+    void *za[kKrylovGroupMax], *ca[kKrylovGroupMax], *tm[kKrylovGroupMax];
+    for (int32_t r = 0; r < R; ++r) {
+        lsa_resolvent* l = rs[idx[r]];
+        l->used_adj = l->used_fwd = false;
+        nd[r] = l->P.nd;
+        C[r] = l->P.Kfac;
+        Qf[r] = l->Qf;
+        za[r] = l->za, za_c[r] = l->za;
+        ca[r] = l->ca;
+        tm[r] = l->tm, tm_c[r] = l->tm;
+        w_c[r] = w[r];
+        ++l->P.st->spmv_calls;
+    }
+    const NdSolve adj = {R, nd, true, 2, LSA_C128, 1, rhs, 0, za, 0, "lsa_resolvent_extend_batch"};
+    LSA_CHECK(ndlu_solve_run(ctx, adj));
+    LSA_CHECK(k_spmv_transpose_batch(ctx, R, C, 1, LSA_C128, za_c, ca));
+    LSA_CHECK(k_spmv_batch(ctx, R, Qf, LSA_C128, za_c, tm));
+    const NdSolve fwd = {R, nd, true, 0, LSA_C128, 1, tm_c, 0, w, 0, "lsa_resolvent_extend_batch"};
+    LSA_CHECK(ndlu_solve_run(ctx, fwd));
+    LSA_CHECK(k_spmv_batch(ctx, R, C, LSA_C128, w_c, cf));
+    for (int32_t r = 0; r < R; ++r) {
+        const lsa_resolvent* l = rs[idx[r]];
+        chk[r][0].b = rhs[r], chk[r][0].z = l->ca, chk[r][0].refined = false;
+        chk[r][1].b = l->tm, chk[r][1].z = cf[r], chk[r][1].refined = false;
+    }
+    int32_t sweep_launches = 0;
+    (void)lsa_ndlu_info(nd[0], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sweep_launches, nullptr, nullptr, nullptr);
+    *launches += 2 * sweep_launches + 3;
+    return LSA_OK;
+}
+
+}  // namespace
+
+int resolvent_group_check(lsa_ctx* ctx, const char* who, int32_t J, lsa_resolvent* const* rs) {
+    if (J < 1 || J > kKrylovGroupMax) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: J = %d outside [1, %d]", who, J, kKrylovGroupMax);
+    if (!rs) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null argument", who);
+    for (int32_t z = 0; z < J; ++z) {
+        if (!rs[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: null handle (problem %d)", who, z);
+        if (rs[z]->ctx != ctx) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the handle of problem %d lives in another context", who, z);
+        for (int32_t y = 0; y < z; ++y)
+            if (rs[y] == rs[z] || rs[y]->op == rs[z]->op) return lsa_set_error(ctx, LSA_ERR_ARG, "%s: problems %d and %d share a handle or an operator", who, y, z);
+        if (rs[z]->n != rs[0]->n || rs[z]->ncv != rs[0]->ncv)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "%s: problem %d has another shape (n = %lld, ncv = %d) than problem 0 (n = %lld, ncv = %d)", who, z,
+                                 (long long)rs[z]->n, rs[z]->ncv, (long long)rs[0]->n, rs[0]->ncv);
+        // the batched products take each member's own weights on the index arrays of ONE pattern
+        if ((rs[z]->Qf != rs[0]->Qf && !k_spmv_same_pattern(rs[0]->Qf, rs[z]->Qf)) || (rs[z]->Qq != rs[0]->Qq && !k_spmv_same_pattern(rs[0]->Qq, rs[z]->Qq)))
+            return lsa_set_error(ctx, LSA_ERR_ARG, "%s: the weights of problem %d have another pattern than those of problem 0: the members of a group may hold "
+                                                   "different weights only on one pattern (lsa_csr_window of one M)", who, z);
+    }
+    return LSA_OK;
+}
+
+int resolvent_extend_batch(lsa_ctx* ctx, LanczosGroupBuf* gb, int32_t J, lsa_resolvent* const* rs, const uint8_t* active, const int32_t* j0, int32_t j1,
+                           double* const* T, int32_t ldt, int32_t* breakdown, int32_t* status, std::string* errs, lsa_ks_batch_info* info) {
+    lsa_lanczos* ls[kKrylovGroupMax];
+    for (int32_t z = 0; z < J; ++z) ls[z] = rs[z]->lz;
+    const lanczos_group_operator gop{(void*)rs, rz_group_eligible, rz_group_enqueue};
+    return lanczos_extend_batch(ctx, gb, ls, &gop, active, j0, j1, T, ldt, breakdown, status, errs, info);
+}
+
+// the context's error text: those of all failed problems in problem order, each naming its problem; returns the first non-zero status
+int resolvent_group_status(lsa_ctx* ctx, int32_t J, const int32_t* status, const std::string* errs) {
+    int first_rc = LSA_OK;
+    std::string all;
+    for (int32_t z = 0; z < J; ++z)
+        if (status[z] != LSA_OK) {
+            if (first_rc == LSA_OK) first_rc = status[z];
+            else all += "; ";
+            all += errs[z];
+        }
+    if (first_rc != LSA_OK) ctx->err = all;
+    return first_rc;
+}
+
+int resolvent_group_alloc(lsa_ctx* ctx, int32_t J, lsa_resolvent* const* rs, LanczosGroupBuf* gb) {
+    lsa_lanczos* ls[kKrylovGroupMax];
+    for (int32_t z = 0; z < J; ++z) ls[z] = rs[z]->lz;
+    return lanczos_group_alloc(ctx, J, ls, gb);
+}
+
 extern "C" {
 
 int lsa_resolvent_create(lsa_ctx* ctx, lsa_op* op, int32_t ncv, lsa_resolvent** out) {
@@ -368,6 +468,26 @@ int lsa_resolvent_set_start(lsa_ctx* ctx, lsa_resolvent* l, const void* host_v) 
 int lsa_resolvent_extend(lsa_ctx* ctx, lsa_resolvent* l, int32_t j0, int32_t j1, double* T, int32_t ldt, int32_t* breakdown) {
     if (!ctx || !l || !T) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_extend: null argument");
     return lsa_lanczos_extend(ctx, l->lz, j0, j1, T, ldt, breakdown);
+}
+
+int lsa_resolvent_extend_batch(lsa_ctx* ctx, int32_t J, lsa_resolvent* const* rs, const uint8_t* active, const int32_t* j0, int32_t j1, double* const* T,
+                               int32_t ldt, int32_t* breakdown, int32_t* status) {
+    if (!ctx || !rs || !j0 || !T || !breakdown || !status) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_extend_batch: null argument");
+    LSA_CHECK(resolvent_group_check(ctx, "lsa_resolvent_extend_batch", J, rs));
+    uint8_t all[kKrylovGroupMax];
+    for (int32_t z = 0; z < J; ++z) {
+        all[z] = active ? active[z] : 1;
+        if (all[z] && !T[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_resolvent_extend_batch: null T (problem %d)", z);
+        status[z] = LSA_OK;
+        breakdown[z] = -1;
+    }
+    LanczosGroupBuf gb;
+    std::string errs[kKrylovGroupMax];
+    int rc = resolvent_group_alloc(ctx, J, rs, &gb);
+    if (rc == LSA_OK) rc = resolvent_extend_batch(ctx, &gb, J, rs, all, j0, j1, T, ldt, breakdown, status, errs, nullptr);
+    lanczos_group_free(&gb);
+    if (rc != LSA_OK) return rc;
+    return resolvent_group_status(ctx, J, status, errs);
 }
 
 int lsa_resolvent_basis(lsa_ctx* ctx, const lsa_resolvent* l, int32_t ncols, void* host_V) {

@@ -38,10 +38,10 @@ __device__ __forceinline__ T stream_load(const T* p) {
     }
 }
 
+// (the body is shared with the batched form below: one copy of the order in which a row's entries are summed)
 template <typename MT, typename VT, int LPR, bool NT>
-__global__ __launch_bounds__(256) void spmv_subwave_kernel(int32_t n, const int32_t* __restrict__ rp,
-                                                           const int32_t* __restrict__ ci, const MT* __restrict__ val,
-                                                           const VT* __restrict__ x, VT* __restrict__ y) {
+__device__ __forceinline__ void spmv_subwave_rows(int32_t n, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci, const MT* __restrict__ val,
+                                                  const VT* __restrict__ x, VT* __restrict__ y) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int32_t lane = (int32_t)(gid % LPR);
     int64_t row = gid / LPR;
@@ -54,6 +54,13 @@ __global__ __launch_bounds__(256) void spmv_subwave_kernel(int32_t n, const int3
         for (int m = LPR / 2; m > 0; m >>= 1) acc = s_add(acc, shfl_xor_t<VT>(acc, m));
         if (lane == 0) y[row] = acc;
     }
+}
+
+template <typename MT, typename VT, int LPR, bool NT>
+__global__ __launch_bounds__(256) void spmv_subwave_kernel(int32_t n, const int32_t* __restrict__ rp,
+                                                           const int32_t* __restrict__ ci, const MT* __restrict__ val,
+                                                           const VT* __restrict__ x, VT* __restrict__ y) {
+    spmv_subwave_rows<MT, VT, LPR, NT>(n, rp, ci, val, x, y);
 }
 
 // Two rows per sub-wave in flight (more independent loads per lane): rows r and r + stride/2 are processed together.
@@ -116,9 +123,9 @@ __global__ __launch_bounds__(256) void spmv_xcd_kernel(int32_t n, int32_t rows_p
 
 // 16-bit column indices relative to the first column of the row: 18 | 10 bytes per entry instead of 20 | 12
 template <typename MT, typename VT, int LPR>
-__global__ __launch_bounds__(256) void spmv_subwave16_kernel(int32_t n, const int32_t* __restrict__ rp, const uint16_t* __restrict__ ci16,
-                                                             const int32_t* __restrict__ cbase, const MT* __restrict__ val,
-                                                             const VT* __restrict__ x, VT* __restrict__ y) {
+__device__ __forceinline__ void spmv_subwave16_rows(int32_t n, const int32_t* __restrict__ rp, const uint16_t* __restrict__ ci16,
+                                                    const int32_t* __restrict__ cbase, const MT* __restrict__ val, const VT* __restrict__ x,
+                                                    VT* __restrict__ y) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int32_t lane = (int32_t)(gid % LPR);
     int64_t row = gid / LPR;
@@ -132,6 +139,13 @@ __global__ __launch_bounds__(256) void spmv_subwave16_kernel(int32_t n, const in
         for (int m = LPR / 2; m > 0; m >>= 1) acc = s_add(acc, shfl_xor_t<VT>(acc, m));
         if (lane == 0) y[row] = acc;
     }
+}
+
+template <typename MT, typename VT, int LPR>
+__global__ __launch_bounds__(256) void spmv_subwave16_kernel(int32_t n, const int32_t* __restrict__ rp, const uint16_t* __restrict__ ci16,
+                                                             const int32_t* __restrict__ cbase, const MT* __restrict__ val,
+                                                             const VT* __restrict__ x, VT* __restrict__ y) {
+    spmv_subwave16_rows<MT, VT, LPR>(n, rp, ci16, cbase, val, x, y);
 }
 
 // Row groups: the rows of one mesh node (ux, uy[, uz][, p]) have one and the same column pattern.  A sub-wave takes a
@@ -162,7 +176,7 @@ __device__ __forceinline__ double row16_sum(double v) {
 __device__ __forceinline__ cplx row16_sum(cplx v) { return cplx{row16_sum(v.re), row16_sum(v.im)}; }
 
 template <typename MT, typename VT, int LPR, bool C16, bool XCD>
-__global__ __launch_bounds__(256) void spmv_group_kernel(int32_t ngroups, int32_t chunk, const int4* __restrict__ gstart,
+__device__ __forceinline__ void spmv_group_rows(int32_t ngroups, int32_t chunk, const int4* __restrict__ gstart,
                                                          const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
                                                          const uint16_t* __restrict__ ci16, const int32_t* __restrict__ cbase,
                                                          const MT* __restrict__ val, const VT* __restrict__ x, VT* __restrict__ y) {
@@ -211,6 +225,14 @@ __global__ __launch_bounds__(256) void spmv_group_kernel(int32_t ngroups, int32_
                 if (k < g) y[r0 + k] = acc[k];
         }
     }
+}
+
+template <typename MT, typename VT, int LPR, bool C16, bool XCD>
+__global__ __launch_bounds__(256) void spmv_group_kernel(int32_t ngroups, int32_t chunk, const int4* __restrict__ gstart,
+                                                         const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                         const uint16_t* __restrict__ ci16, const int32_t* __restrict__ cbase,
+                                                         const MT* __restrict__ val, const VT* __restrict__ x, VT* __restrict__ y) {
+    spmv_group_rows<MT, VT, LPR, C16, XCD>(ngroups, chunk, gstart, rp, ci, ci16, cbase, val, x, y);
 }
 
 // builds A->grp_start from the host pattern; false when grouping does not pay (mean group below 1.5 rows)
@@ -561,6 +583,8 @@ static bool spmv_same_pattern(const lsa_mat* A, const lsa_mat* B) {
     return A->h_rp == B->h_rp && A->h_ci == B->h_ci;
 }
 
+bool k_spmv_same_pattern(const lsa_mat* A, const lsa_mat* B) { return spmv_same_pattern(A, B); }
+
 int k_spmv_transpose_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* mats, int conj, int xdtype, const void* const* xs, void* const* ys) {
     if (J < 1 || J > kSpmvBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_transpose_batch: J = %d outside [1, %d]", J, kSpmvBatchMax);
     const lsa_mat* A = mats[0];
@@ -595,6 +619,99 @@ int k_spmv_transpose_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* mats, 
     else
         hipLaunchKernelGGL((spmv_transpose_pull_batch_kernel<cplx, cplx>), grid, dim3(threads), 0, ctx->stream, A->ncols, conj, T.rp, T.ci, T.src, p);
     return lsa_check_launch(ctx, "spmv_transpose_pull_batch_kernel");
+}
+
+// ---- ys[z] = mats[z] xs[z] for up to kSpmvBatchMax matrices of ONE pattern in one launch ----------------------------------------------
+// blockIdx.y is the problem; its values and vectors come by value (SpmvTransposePtrs), the index arrays are those of matrix 0.  Every
+// problem walks its rows through the body k_spmv's kernel runs for this pattern and these scalar types -- the plain sub-wave rows, the
+// compressed indices or the row groups, by launch_spmv's rules and with its grid in x -- so a row's entries meet the same lanes in
+// the same order and every ys[z] holds k_spmv's bits.  The same matrix may stand in several slots (Q_f z_k for all members of a
+// lockstep group).
+template <typename MT, typename VT, int LPR>
+__global__ __launch_bounds__(256) void spmv_subwave_batch_kernel(int32_t n, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                                 SpmvTransposePtrs p) {
+    const int z = blockIdx.y;
+    spmv_subwave_rows<MT, VT, LPR, false>(n, rp, ci, (const MT*)p.val[z], (const VT*)p.x[z], (VT*)p.y[z]);
+}
+
+template <typename MT, typename VT, int LPR>
+__global__ __launch_bounds__(256) void spmv_subwave16_batch_kernel(int32_t n, const int32_t* __restrict__ rp, const uint16_t* __restrict__ ci16,
+                                                                   const int32_t* __restrict__ cbase, SpmvTransposePtrs p) {
+    const int z = blockIdx.y;
+    spmv_subwave16_rows<MT, VT, LPR>(n, rp, ci16, cbase, (const MT*)p.val[z], (const VT*)p.x[z], (VT*)p.y[z]);
+}
+
+template <typename MT, typename VT, int LPR>
+__global__ __launch_bounds__(256) void spmv_group_batch_kernel(int32_t ngroups, const int4* __restrict__ gstart, const int32_t* __restrict__ rp,
+                                                               const int32_t* __restrict__ ci, SpmvTransposePtrs p) {
+    const int z = blockIdx.y;
+    spmv_group_rows<MT, VT, LPR, false, false>(ngroups, 0, gstart, rp, ci, (const uint16_t*)nullptr, (const int32_t*)nullptr, (const MT*)p.val[z],
+                                               (const VT*)p.x[z], (VT*)p.y[z]);
+}
+
+// the default decisions of launch_spmv (no variant word) on the pattern of A, with the problem as the grid's second dimension
+template <typename MT, typename VT, int LPR>
+static void launch_spmv_batch(lsa_ctx* ctx, const lsa_mat* A, int32_t J, const SpmvTransposePtrs& p) {
+    const int threads = 256;
+    const int64_t want = ((int64_t)A->n * LPR + threads - 1) / threads, cap = (int64_t)ctx->num_cu * 64;
+    const unsigned blocks = (unsigned)(want < 1 ? 1 : (want > cap ? cap : want));
+    if (spmv_wants_groups(A, 0) && ensure_groups(A)) {
+        const int64_t gwant = ((int64_t)A->ngroups * LPR + threads - 1) / threads, gcap = (int64_t)ctx->num_cu * 256;
+        const unsigned gblocks = (unsigned)(gwant < 1 ? 1 : (gwant > gcap ? gcap : gwant));
+        hipLaunchKernelGGL((spmv_group_batch_kernel<MT, VT, LPR>), dim3(gblocks, (unsigned)J), dim3(threads), 0, ctx->stream, A->ngroups,
+                           (const int4*)A->grp_start, A->rp, A->ci, p);
+        return;
+    }
+    if (spmv_wants_ci16(A, 0) && ensure_ci16(A)) {
+        hipLaunchKernelGGL((spmv_subwave16_batch_kernel<MT, VT, LPR>), dim3(blocks, (unsigned)J), dim3(threads), 0, ctx->stream, A->n, A->rp,
+                           (const uint16_t*)A->ci16, (const int32_t*)A->cbase, p);
+        return;
+    }
+    hipLaunchKernelGGL((spmv_subwave_batch_kernel<MT, VT, LPR>), dim3(blocks, (unsigned)J), dim3(threads), 0, ctx->stream, A->n, A->rp, A->ci, p);
+}
+
+template <typename MT, typename VT>
+static void dispatch_spmv_batch(lsa_ctx* ctx, const lsa_mat* A, int32_t J, const SpmvTransposePtrs& p) {
+    switch (spmv_lanes_per_row(A, 0)) {
+        case 4: launch_spmv_batch<MT, VT, 4>(ctx, A, J, p); break;
+        case 8: launch_spmv_batch<MT, VT, 8>(ctx, A, J, p); break;
+        case 32: launch_spmv_batch<MT, VT, 32>(ctx, A, J, p); break;
+        case 64: launch_spmv_batch<MT, VT, 64>(ctx, A, J, p); break;
+        default: launch_spmv_batch<MT, VT, 16>(ctx, A, J, p); break;
+    }
+}
+
+int k_spmv_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* mats, int xdtype, const void* const* xs, void* const* ys) {
+    if (J < 1 || J > kSpmvBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_batch: J = %d outside [1, %d]", J, kSpmvBatchMax);
+    const lsa_mat* A = mats[0];
+    for (int32_t z = 1; z < J; ++z) {
+        const lsa_mat* B = mats[z];
+        if (B == A) continue;
+        if (B->n != A->n || B->ncols != A->ncols || B->row0 != A->row0)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_batch: matrix %d is %d x %d (from row %d), matrix 0 is %d x %d (from row %d)", z, B->n, B->ncols, B->row0,
+                                 A->n, A->ncols, A->row0);
+        if (B->nnz != A->nnz)
+            return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_batch: matrix %d has nnz = %lld, matrix 0 has nnz = %lld", z, (long long)B->nnz, (long long)A->nnz);
+        if (B->dtype != A->dtype) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_batch: matrix %d has another dtype than matrix 0", z);
+        if (!spmv_same_pattern(A, B)) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_batch: matrix %d has another pattern than matrix 0", z);
+    }
+    if (A->dtype == LSA_C128 && xdtype != LSA_C128) return lsa_set_error(ctx, LSA_ERR_ARG, "spmv_batch: a complex matrix needs complex vectors");
+    if (spmv_variant() != 0) {
+        // the development knob picks forms the batched kernels do not have: the members' products one by one, each k_spmv itself
+        for (int32_t z = 0; z < J; ++z) LSA_CHECK(k_spmv(ctx, mats[z], xdtype, xs[z], ys[z]));
+        return LSA_OK;
+    }
+    SpmvTransposePtrs p;
+    memset(&p, 0, sizeof p);
+    for (int32_t z = 0; z < J; ++z) {
+        p.val[z] = mats[z]->val;
+        p.x[z] = xs[z];
+        p.y[z] = ys[z];
+    }
+    if (A->dtype == LSA_F64 && xdtype == LSA_F64) dispatch_spmv_batch<double, double>(ctx, A, J, p);
+    else if (A->dtype == LSA_F64) dispatch_spmv_batch<double, cplx>(ctx, A, J, p);
+    else dispatch_spmv_batch<cplx, cplx>(ctx, A, J, p);
+    return lsa_check_launch(ctx, "spmv_batch");
 }
 
 // ---- C-ABI -----------------------------------------------------------------------------------------------------
@@ -640,6 +757,26 @@ int lsa_spmv_transpose_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* A, i
         yd[z] = y[z]->d;
     }
     return k_spmv_transpose_batch(ctx, J, A, conj, x[0]->dtype, xd, yd);
+}
+
+int lsa_spmv_batch(lsa_ctx* ctx, int32_t J, const lsa_mat* const* A, const lsa_vec* const* x, lsa_vec* const* y) {
+    if (!ctx || !A || !x || !y) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_batch: null argument");
+    if (J < 1 || J > kSpmvBatchMax) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_batch: J = %d outside [1, %d]", J, kSpmvBatchMax);
+    const void* xd[kSpmvBatchMax];
+    void* yd[kSpmvBatchMax];
+    for (int32_t z = 0; z < J; ++z) {
+        if (!A[z] || !x[z] || !y[z]) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_batch: null argument (problem %d)", z);
+        LSA_CHECK(check_spmv_args(ctx, A[z], x[z], y[z], "lsa_spmv_batch"));
+        if (A[z]->row0 != 0 || A[z]->n != A[z]->ncols) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_batch: sharded matrices are not supported (problem %d)", z);
+        if (y[z]->n != A[z]->n) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_batch: y has the wrong length (problem %d)", z);
+        if (x[z]->dtype != x[0]->dtype) return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_batch: the vectors of problem %d have another dtype than those of problem 0", z);
+        for (int32_t w = 0; w < z; ++w)
+            if (y[z]->d == y[w]->d || y[z]->d == x[w]->d || y[w]->d == x[z]->d)
+                return lsa_set_error(ctx, LSA_ERR_ARG, "lsa_spmv_batch: problems %d and %d share an output", w, z);
+        xd[z] = x[z]->d;
+        yd[z] = y[z]->d;
+    }
+    return k_spmv_batch(ctx, J, A, x[0]->dtype, xd, yd);
 }
 
 int lsa_spmv_info(lsa_ctx* ctx, const lsa_mat* A, int xdtype, char* kernel, int32_t kernel_len, int64_t* bytes_moved) {

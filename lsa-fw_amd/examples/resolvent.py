@@ -3,7 +3,7 @@ Re = 50 over a list of frequencies, on ONE context, ordering and LU analysis (``
 
     python lsa-fw_amd/examples/resolvent.py [--case S5k] [--modes 3] [--omegas 0 0.2 0.4 0.6 0.738 0.9 1.2]
                                             [--forcing-window X0 X1 [Y0 Y1]] [--response-window X0 X1] [--discount B]
-                                            [--norm-map RE0 RE1 NRE IM0 IM1 NIM]
+                                            [--norm-map RE0 RE1 NRE IM0 IM1 NIM] [--lockstep J]
 
 The wake is marginally stable and strongly non-normal: the least stable eigenvalue sits at 0.018 + 0.738j, and the gains around
 omega = 0.74 -- and, larger still, at low frequencies -- say how much a harmonic forcing is amplified, which the eigenvalues alone
@@ -11,7 +11,8 @@ understate.  ``--forcing-window`` confines the forcing to a box and ``--response
 (``sigma = max ||q||_Qq / ||f||_Qf``, ``Q = D M D`` with the 0/1 window ``D``): what is published for long domains, where the whole-domain
 gain depends on where the mesh ends.  ``--discount B`` shifts to ``((B + i omega) M - A)^-1``, the discounted resolvent for an unstable
 base flow, and ``--norm-map`` prints ``sigma_1(z)`` on a grid of complex points: ``1 / sigma_1`` is the epsilon-level of the energy-norm
-pseudospectrum.  Needs an AMD GPU (there is no CPU fallback).
+pseudospectrum.  ``--lockstep J`` advances up to J (at most 16) frequencies, or map points off the real axis, together: one batched
+launch per launch of a solo step, the same numbers.  Needs an AMD GPU (there is no CPU fallback).
 """
 
 from __future__ import annotations
@@ -52,6 +53,7 @@ def main() -> None:
     ap.add_argument("--response-window", type=float, nargs=2, metavar=("X0", "X1"), default=None)
     ap.add_argument("--discount", type=float, default=0.0)
     ap.add_argument("--norm-map", type=float, nargs=6, metavar=("RE0", "RE1", "NRE", "IM0", "IM1", "NIM"), default=None)
+    ap.add_argument("--lockstep", type=int, default=0, metavar="J", help="advance up to J frequencies (or map points) together")
     args = ap.parse_args()
     es = fem.cylinder_case(args.case)
     rs = ResolventSolver(es.A, es.M, ResolventConfig(num_modes=args.modes, ncv=args.ncv, atol=1e-8), forcing_window=box_window(es, args.forcing_window),
@@ -60,14 +62,15 @@ def main() -> None:
     if args.norm_map is not None:
         re0, re1, nre, im0, im1, nim = args.norm_map
         re, im = np.linspace(re0, re1, int(nre)), np.linspace(im0, im1, int(nim))
-        sigma1 = rs.norm_map(re[None, :] + 1j * im[:, None])
+        pts = re[None, :] + 1j * im[:, None]
+        sigma1 = rs.norm_map(pts, warm_start=False, lockstep=True, max_batch=args.lockstep) if args.lockstep else rs.norm_map(pts)
         print("sigma_1(z), rows Im z, columns Re z:   " + "".join(f"{r:<12.4f}" for r in re))
         for w, row in zip(im, sigma1):
             print(f"{w:36.4f}   " + "".join(f"{g:<12.4e}" for g in row))
         rs.release()
         return
     print("   omega   " + "".join(f"sigma_{j + 1:<8d}" for j in range(args.modes)) + "applies restarts  factor s   steps s  analysis reused")
-    for res in rs.sweep(args.omegas):
+    for res in (rs.sweep(args.omegas, lockstep=True, max_batch=args.lockstep) if args.lockstep else rs.sweep(args.omegas)):
         st = res.stats
         print(f"{res.omega:8.4f}   " + "".join(f"{g:<14.6f}" for g in res.gains) + f"{st['applies']:7d} {st['restarts']:8d} "
               f"{st['seconds_factor']:9.4f} {st['seconds_expand']:9.4f}  {st['analysis_reused']}")

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 from pathlib import Path
 
 import numpy as np
@@ -228,6 +229,7 @@ SIGNATURES = {
     "lsa_spmv": (ctypes.c_int, [_P, _P, _P, _P]),
     "lsa_spmv_transpose": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P]),
     "lsa_spmv_transpose_batch": (ctypes.c_int, [_P, _I32, _PP, ctypes.c_int, _PP, _PP]),
+    "lsa_spmv_batch": (ctypes.c_int, [_P, _I32, _PP, _PP, _PP]),
     "lsa_spmv_info": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_char_p, _I32, ctypes.POINTER(_I64)]),
     "lsa_spmv_time": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.POINTER(_DBL)]),
     "lsa_ilu_create": (ctypes.c_int, [_P, _P, ctypes.c_int, _DBL, _PP]),
@@ -320,6 +322,8 @@ SIGNATURES = {
     "lsa_resolvent_extend": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, ctypes.POINTER(_I32)]),
     "lsa_resolvent_basis": (ctypes.c_int, [_P, _P, _I32, _P]),
     "lsa_resolvent_solve": (ctypes.c_int, [_P, _P, ctypes.POINTER(lsa_ks_options), _P, _I32, _P, _P, _P, _P, _P, ctypes.POINTER(lsa_ks_result), _P]),
+    "lsa_resolvent_extend_batch": (ctypes.c_int, [_P, _I32, _PP, _P, _P, _I32, _PP, _I32, _P, _P]),
+    "lsa_resolvent_solve_batch": (ctypes.c_int, [_P, _I32, _PP, _PP, _PP, _I32, _PP, _PP, _PP, _PP, _PP, _P, _P, _P, _P]),
     "lsa_growth_create": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _PP]),
     "lsa_growth_destroy": (None, [_P]),
     "lsa_growth_set_row_permutation": (ctypes.c_int, [_P, _P, _P]),
@@ -769,6 +773,19 @@ class CsrMatrix(_Handle):
             raise ValueError("spmv_transpose_batch: the matrices and vectors must live in one context")
         arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
         ctx.check(ctx._lib.lsa_spmv_transpose_batch(ctx.handle, J, arr(mats), int(conj), arr(xs), arr(ys)))
+
+    @staticmethod
+    def spmv_batch(mats: "list[CsrMatrix]", xs: "list[DeviceVector]", ys: "list[DeviceVector]") -> None:
+        """``ys[z] = mats[z] xs[z]`` for up to 16 whole square matrices of one pattern and dtype in one launch (``lsa_spmv_batch``);
+        the same matrix may stand in several slots.  Each result is bit-identical to :meth:`matvec`."""
+        J = len(mats)
+        if J == 0 or len(xs) != J or len(ys) != J:
+            raise ValueError("spmv_batch needs as many inputs and outputs as matrices (at least one)")
+        ctx = mats[0].ctx
+        if any(m.ctx is not ctx for m in mats) or any(v.ctx is not ctx for v in list(xs) + list(ys)):
+            raise ValueError("spmv_batch: the matrices and vectors must live in one context")
+        arr = lambda objs: (ctypes.c_void_p * J)(*[o.handle.value for o in objs])  # noqa: E731
+        ctx.check(ctx._lib.lsa_spmv_batch(ctx.handle, J, arr(mats), arr(xs), arr(ys)))
 
     def matmat(self, X: DeviceVector, Y: DeviceVector, ncols: int, ldx: int | None = None, ldy: int | None = None) -> None:
         """``Y[:, c] = self @ X[:, c]`` for ``ncols`` columns (``lsa_spmm``).  ``X`` and ``Y`` are column-major complex128 blocks in
@@ -1428,6 +1445,85 @@ class ResolventBasis(_LanczosHandle):
         k, tail = self._solve(_ks_options(nev, tol, max_restarts, seed=seed), v0, max_out, theta, gains, Q, F)
         return {"theta": theta[:k].copy(), "gains": gains[:k].copy(), "responses": np.asfortranarray(Q[:, :k]),
                 "forcings": None if F is None else np.asfortranarray(F[:, :k]), **tail}
+
+    @staticmethod
+    def extend_batch(bases: "list[ResolventBasis]", j0s, j1: int, Ts: "list[np.ndarray]", raise_on_error: bool = True):
+        """:meth:`extend` for up to 16 bases of one context and shape in one library call (``lsa_resolvent_extend_batch``): basis ``z``
+        from its own ``j0s[z]`` to the common ``j1`` into its own Fortran-ordered ``Ts[z]``, in lockstep rounds where the members'
+        factors allow; every basis is left with the bits of its own :meth:`extend`.  Returns ``(breakdowns, statuses)``.  For tests."""
+        bases = list(bases)
+        J = len(bases)
+        if J == 0 or len(j0s) != J or len(Ts) != J:
+            raise ValueError("extend_batch needs one start column and one T per basis (at least one)")
+        ctx = bases[0].ctx
+        for T in Ts:
+            assert T.flags.f_contiguous and T.dtype == np.float64 and T.shape[0] == Ts[0].shape[0]
+        j0 = (ctypes.c_int32 * J)(*[int(j) for j in j0s])
+        bd = (ctypes.c_int32 * J)()
+        status = (ctypes.c_int32 * J)()
+        arr = lambda ptrs: (ctypes.c_void_p * J)(*ptrs)  # noqa: E731
+        rc = ctx._lib.lsa_resolvent_extend_batch(ctx.handle, J, arr([b.handle.value for b in bases]), None, j0, int(j1), arr([T.ctypes.data for T in Ts]),
+                                                 Ts[0].shape[0], bd, status)
+        if rc != 0 and (raise_on_error or all(st == 0 for st in status)):
+            ctx.check(rc)
+        return [int(b) for b in bd], [int(s) for s in status]
+
+    @staticmethod
+    def solve_batch(bases: "list[ResolventBasis]", nevs, tol, max_it, *, v0s=None, seed: int = 0, max_out: int | None = None, forcings=True,
+                    raise_on_error: bool = True, ctx: Context | None = None):
+        """:meth:`solve` for up to 16 bases of one context and one shape in one library call (``lsa_resolvent_solve_batch``): the
+        frequencies whose factors are complex and of one LU analysis advance in lockstep -- one batched launch per launch of a solo
+        step and one read-back per round for all of them --, every basis returns the bits of its own :meth:`solve`.  ``nevs``,
+        ``tol``, ``max_it`` (the restarts allowed), ``forcings`` and ``v0s``: one value for all, or one per basis.
+
+        Returns ``(results, info)``: the dicts of :meth:`solve` in order, and the counters of ``lsa_ks_batch_info`` (``rounds``,
+        ``launches``, ``periods``, ``launches_per_round``, ``lockstep_steps`` and ``solo_steps`` per basis).  A basis that failed
+        raises (the first failing one's status, with the texts of all failed ones, each naming its problem) unless
+        ``raise_on_error`` is off: then its entry is its own exception and the others are results."""
+        bases = list(bases)
+        J = len(bases)
+        per = lambda x, z: x[z] if isinstance(x, (list, tuple, np.ndarray)) and not np.isscalar(x) else x  # noqa: E731
+        ctx = bases[0].ctx if J else ctx  # (``ctx``: only needed for an empty list, whose refusal is the library's too)
+        if ctx is None:
+            raise ValueError("solve_batch needs at least one basis")
+        max_out = (bases[0].ncv if J else 0) if max_out is None else min(int(max_out), bases[0].ncv if J else 0)
+        opts = [_ks_options(int(per(nevs, z)), float(per(tol, z)), int(per(max_it, z)), seed=seed) for z in range(J)]
+        vs = [None if v0s is None else bases[z]._start(v0s if isinstance(v0s, np.ndarray) and v0s.ndim == 1 else v0s[z]) for z in range(J)]
+        theta = [np.zeros(max(max_out, 1), dtype=np.float64) for _ in range(J)]
+        gains = [np.zeros(max(max_out, 1), dtype=np.float64) for _ in range(J)]
+        est = [np.zeros(max(max_out, 1), dtype=np.float64) for _ in range(J)]
+        Q = [np.empty((b.n, max_out), dtype=np.complex128, order="F") for b in bases]
+        F = [np.empty((b.n, max_out), dtype=np.complex128, order="F") if per(forcings, z) else None for z, b in enumerate(bases)]
+        res = (lsa_ks_result * max(J, 1))()
+        status = (ctypes.c_int32 * max(J, 1))()
+        counts = np.zeros((max(J, 1), 4), dtype=np.int64)
+        info = lsa_ks_batch_info()
+        arr = lambda ptrs: (ctypes.c_void_p * max(J, 1))(*ptrs)  # noqa: E731
+        addr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        rc = ctx._lib.lsa_resolvent_solve_batch(ctx.handle, J, arr([None if b is None else b.handle.value for b in bases]),
+                                                arr([ctypes.addressof(o) for o in opts]), arr([addr(v) for v in vs]), max_out, arr([addr(a) for a in theta]),
+                                                arr([addr(a) for a in gains]), arr([addr(a) for a in Q]), arr([addr(a) for a in F]),
+                                                arr([addr(a) for a in est]), ctypes.byref(res), _ptr(counts), ctypes.byref(status), ctypes.byref(info))
+        text = ctx._lib.lsa_last_error(ctx.handle).decode(errors="replace") if rc != 0 else ""
+        if rc != 0 and (raise_on_error or all(st == 0 for st in status)):
+            ctx.check(rc)
+        out = []
+        for z, b in enumerate(bases):
+            if status[z] != 0:
+                # (the joined text is cut only in front of a problem's prefix: a member's own message may hold "; ")
+                mine = next((t for t in re.split(r"; (?=problem \d+: )", text) if t.startswith(f"problem {z}:")), f"problem {z} failed: {text}")
+                out.append(ValueError(mine) if status[z] == -1 else LsaError(status[z], mine))
+                continue
+            r, k = res[z], res[z].nout
+            out.append({"theta": theta[z][:k].copy(), "gains": gains[z][:k].copy(), "responses": np.asfortranarray(Q[z][:, :k]),
+                        "forcings": None if F[z] is None else np.asfortranarray(F[z][:, :k]), "estimates": est[z][:k].copy(), "nconv": int(r.nconv),
+                        "restarts": int(r.restarts), "applies": int(r.op_applies), "next_unconverged": float(r.next_unconverged),
+                        "seconds_expand": r.seconds_expand, "seconds_dense": r.seconds_dense, "seconds_restart": r.seconds_restart,
+                        **{name: int(c) for name, c in zip(ResolventBasis._counters, counts[z])}})
+        counters = {"rounds": int(info.rounds), "launches": int(info.launches), "periods": int(info.periods),
+                    "launches_per_round": float(info.launches_per_round), "lockstep_steps": [int(info.lockstep_steps[z]) for z in range(J)],
+                    "solo_steps": [int(info.solo_steps[z]) for z in range(J)]}
+        return out, counters
 
 
 class ContourSolver(_Handle):

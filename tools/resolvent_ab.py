@@ -28,6 +28,11 @@ windowed copies of ``M`` in flight: the like-for-like figure), alternately after
 (``CsrMatrix.windowed``: the upload of the window, ``window_values_kernel`` and the synchronisation) on every case given; the result goes
 under the key ``resolvent`` of ``profiles/windows_ab.json``.  The weighted step has the launches of the plain one, so the figure to
 compare is ``seconds_per_step``; the iteration counts differ, since the windowed problem is another problem.
+
+``--lockstep J`` times a sweep of J distinct frequencies three ways in the same process, fresh solvers for each, alternately after a
+warm-up of each: the sequential ``sweep`` (the default path: the baseline), ``sweep(lockstep=True)`` and the host-driven ARPACK loop.
+Per frequency it reports the factor / step / host-dense / restart-and-forcings split from the stats, plus rounds and launches per
+round, and whether the lockstep sweep returned the sequential one's bytes; the rows go to ``profiles/resolvent_lockstep.json``.
 """
 
 from __future__ import annotations
@@ -205,6 +210,81 @@ def windows_ab(cases, reps: int) -> dict:
     return out
 
 
+def sweep_frequencies(omega: float, J: int) -> list:
+    """J distinct non-zero frequencies around the case's own (a case whose frequency is 0 sweeps 0.2 ... upwards)."""
+    base = omega if omega != 0.0 else 0.2
+    return [base * (0.6 + 0.8 * k / max(J - 1, 1)) for k in range(J)]
+
+
+def sweep_run(es, omegas, lockstep: bool, max_batch: int = 16) -> dict:
+    """One sweep on a fresh solver, construction to release: the per-frequency split from the stats."""
+    from Solver.resolvent import ResolventConfig, ResolventSolver
+
+    t0 = time.perf_counter()
+    rs = ResolventSolver(es.A, es.M, ResolventConfig(num_modes=MODES, ncv=NCV, atol=TOL))
+    res = rs.sweep(omegas, forcings=True, lockstep=lockstep, max_batch=max_batch)
+    info = list(rs.last_lockstep_info)
+    rs.release()
+    J = len(omegas)
+    tot = lambda key: sum(r.stats[key] for r in res)  # noqa: E731
+    return {"seconds": time.perf_counter() - t0, "gains": [r.gains.tolist() for r in res], "responses": [r.responses for r in res],
+            "forcings": [r.forcings for r in res],
+            "per_frequency": {"factor": tot("seconds_factor") / J, "steps": tot("seconds_expand") / J, "host_dense": tot("seconds_dense") / J,
+                              "restart_vectors_forcings": tot("seconds_restart") / J},
+            "applies": [r.stats["applies"] for r in res], "lockstep_steps": [r.stats.get("lockstep_steps", 0) for r in res],
+            "solo_steps": [r.stats.get("solo_steps", r.stats["applies"]) for r in res],
+            "rounds": sum(i["rounds"] for i in info), "launches_per_round": (sum(i["launches"] for i in info) / max(sum(i["rounds"] for i in info), 1))}
+
+
+def host_sweep(es, omegas) -> dict:
+    """The host loop at every frequency; ``{"refused": text}`` where it cannot run one (``iKSP``'s factorisation has no re-analysis
+    with constraints: a zero pivot inside a front ends it, where the operator build of the library analyses again)."""
+    import lsa_hip
+
+    t0 = time.perf_counter()
+    try:
+        runs = [host(es, w) for w in omegas]
+    except lsa_hip.LsaError as exc:
+        return {"refused": str(exc)}
+    return {"seconds": time.perf_counter() - t0, "gains": [r["gains"].tolist() for r in runs],
+            "per_frequency": {"setup_and_factor": sum(r["seconds_setup"] + r["seconds_first_product"] for r in runs) / len(runs),
+                              "iteration": sum(r["seconds_iteration"] for r in runs) / len(runs)}}
+
+
+def lockstep_ab(cases, reps: int, J: int) -> dict:
+    """A sweep of J distinct frequencies three ways in one process -- the sequential ``sweep`` (the baseline: the default path), the
+    lockstep ``sweep`` and the host-driven ARPACK loop --, fresh solvers for each, alternately after one warm-up of each."""
+    out = {"config": {"num_modes": MODES, "ncv": NCV, "tol": TOL, "reps": reps, "frequencies": J}, "cases": []}
+    for case in cases:
+        es, omega = problem(case)
+        omegas = sweep_frequencies(omega, J)
+        settings = {"sequential": lambda: sweep_run(es, omegas, False), "lockstep": lambda: sweep_run(es, omegas, True, min(J, 16)),
+                    "host": lambda: host_sweep(es, omegas)}
+        # (where the device does not hold J factor sets the front end cuts the group: `rounds` and `lockstep_steps` show what ran together)
+        warm = {name: fn() for name, fn in settings.items()}
+        same = all(np.array_equal(a, b) for key in ("responses", "forcings") for a, b in zip(warm["sequential"][key], warm["lockstep"][key]))
+        same = same and warm["sequential"]["gains"] == warm["lockstep"]["gains"]
+        if "refused" in warm["host"]:  # (stated, and left out of the alternation)
+            del settings["host"]
+        runs = {name: [] for name in settings}
+        for _ in range(reps):
+            for name, fn in settings.items():
+                runs[name].append(fn())
+        strip = lambda r: {k: v for k, v in r.items() if k not in ("responses", "forcings", "gains")}  # noqa: E731
+        entry = {"case": case, "n": int(es.A.shape[0]), "omegas": omegas, "lockstep_bytes_equal_sequential": bool(same),
+                 **{name: {"seconds": spread([r["seconds"] for r in runs[name]]),
+                           "per_frequency": {k: spread([r["per_frequency"][k] for r in runs[name]]) for k in runs[name][0]["per_frequency"]},
+                           "last": strip(runs[name][-1])} for name in settings}}
+        if "refused" in warm["host"]:
+            entry["host"] = warm["host"]
+        entry["sweep_speedup_median"] = entry["sequential"]["seconds"]["median"] / entry["lockstep"]["seconds"]["median"]
+        entry["step_seconds_ratio_median"] = (entry["lockstep"]["per_frequency"]["steps"]["median"] /
+                                              entry["sequential"]["per_frequency"]["steps"]["median"])
+        out["cases"].append(entry)
+        print(json.dumps(entry), flush=True)
+    return out
+
+
 def plain(run: dict) -> dict:
     return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in run.items()}
 
@@ -221,7 +301,17 @@ def main(argv=None) -> None:
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "resolvent_ab.json")
     ap.add_argument("--forcings", action="store_true", help="the forcings phase with block_forcings off and on -> key forcings_phase of --out")
     ap.add_argument("--windows", action="store_true", help="the windowed solve against the plain one -> key resolvent of profiles/windows_ab.json")
+    ap.add_argument("--lockstep", type=int, default=0, metavar="J",
+                    help="a sweep of J frequencies: sequential, lockstep and host loop -> key lockstep_J of profiles/resolvent_lockstep.json")
     args = ap.parse_args(argv)
+    if args.lockstep:
+        path = ROOT / "profiles" / "resolvent_lockstep.json"
+        doc = json.loads(path.read_text()) if path.exists() else {}
+        for entry in lockstep_ab(args.cases, args.reps, args.lockstep)["cases"]:
+            doc[f"{entry['case']}_lockstep_{args.lockstep}"] = {"config": {"num_modes": MODES, "ncv": NCV, "tol": TOL, "reps": args.reps}, **entry}
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(doc, indent=1) + "\n")
+        return
     if args.windows:
         path = ROOT / "profiles" / "windows_ab.json"
         doc = json.loads(path.read_text()) if path.exists() else {}
